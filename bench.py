@@ -19,6 +19,11 @@ and `per_rank` objects of the line).  Rank 0 prints ONE JSON line.
 Started with --gpus N > 1 and no launcher environment (no RANK / WORLD_SIZE), this process becomes a
 launcher: it never imports torch.cuda nor loads librscm_gpu.so, starts N children of itself with RANK,
 LOCAL_RANK, WORLD_SIZE and MASTER_* set, relays rank 0's line and exits non-zero if any rank failed.
+
+--dump-outputs DIR: after the timed steps rank 0 writes what the last one computed for a fixed, seeded
+sample of its members (dump_sample) -- their status flags, and the Ts and Td series of those whose
+series are finite -- to DIR/<name>.npy, so that two builds can be compared output for output on
+identical inputs (dump_outputs).
 """
 import argparse
 import json
@@ -42,6 +47,7 @@ HBM_STORE_STREAM_GBS = 5460.0  # what a store-only streaming kernel reaches on t
 FP64_VALU_PEAK_TINSTR = 39.3   # 256 CU x 4 SIMD x 16 f64 lanes x 2.4 GHz (FMA would count 2 flops)
 ALG_BYTES_PER_MEMBER_YEAR = 16.0   # store Ts, Td
 ALG_OPS_PER_MEMBER_YEAR = 700.0    # 620 add/mul + 80 div, exact mode
+DUMP_MEMBERS = 4096            # --dump-outputs: members sampled (Ts + Td: at most 2 x 751 rows x 8 B x 4096 = 49 MB, under the 64 MB cap)
 
 
 def profile_entry(kind, members, mode):
@@ -811,6 +817,36 @@ def one_pass(ens):
     ens.run(sync=False)
 
 
+def dump_sample(members):
+    """The members --dump-outputs writes: every one up to DUMP_MEMBERS, else a fixed sample drawn with SEED, ascending."""
+    if members <= DUMP_MEMBERS:
+        return np.arange(members)
+    return np.sort(np.random.default_rng(SEED).choice(members, DUMP_MEMBERS, replace=False))
+
+
+def dump_outputs(ens, path, chunk=16384):
+    """What a caller of the timed path receives after its last step, for the members of dump_sample, as <path>/<name>.npy in f64:
+    status ([n]: the status bytes of rscm_ens_status, 0 = ok), and the stored Ts and Td series ([751][k], every year) of the k
+    sampled members whose series are finite, with their indices in members ([k]).  The members that run away to inf / NaN (a few
+    per cent of the draw, flagged in status) have no finite series to compare; every value written is finite."""
+    os.makedirs(path, exist_ok=True)
+    idx = dump_sample(ens.n_members)
+    series = {}
+    for name, var in (("surface_temperature", "Surface Temperature"), ("deep_ocean_temperature", "Deep Ocean Temperature")):
+        out = np.empty((ens.n_times, len(idx)))
+        for m0 in range(0, ens.n_members, chunk):   # a block of members at a time: host memory stays bounded at any --members
+            m1 = min(ens.n_members, m0 + chunk)
+            sel = (idx >= m0) & (idx < m1)
+            if sel.any():
+                out[:, sel] = ens.get_series(var, m_begin=m0, m_end=m1)[:, idx[sel] - m0]
+        series[name] = out
+    finite = np.all([np.isfinite(s).all(axis=0) for s in series.values()], axis=0)
+    np.save(os.path.join(path, "status.npy"), ens.status()[idx].astype(np.float64))
+    np.save(os.path.join(path, "members.npy"), idx[finite].astype(np.float64))
+    for name, s in series.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(s[:, finite]))
+
+
 def _coll_device(torch, dist):
     return "cuda" if dist.get_backend() == "nccl" else "cpu"
 
@@ -1271,7 +1307,13 @@ def main():
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="no GPU work: the ranks meet over gloo, run the contract's barrier / max-over-ranks / rank report and rank 0 "
                          "prints a line with value null (tests/test_distributed_cpu.py checks the launcher and the N > 1 plumbing with it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, rank 0 writes what the last one computed for a fixed, seeded sample of "
+                         f"{DUMP_MEMBERS} of its members (status; Ts, Td series of the members whose series are finite) as "
+                         "DIR/<name>.npy in f64")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1 (the number of timed steps)")
 
     # No launcher environment and more than one GPU asked for: this process starts the ranks itself and never touches the GPU
     # (decided from argv and the environment alone, before torch.cuda or librscm_gpu.so are loaded).
@@ -1335,6 +1377,8 @@ def main():
 
     ens = make_ensemble(args.members, local_rank, rank, world, mode, stream)
     wall, kernel_ms = timed_passes(ens, args.steps, args.warmup, torch, dist, world, tstream)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ens, args.dump_outputs)
     n_fail = int(ens.status().sum())
     fails = _gather_obj(dist, n_fail)
     run_plan = ens.last_run_plan()

@@ -2,7 +2,7 @@
 with their op tables by value in the kernel arguments (rscm_gpu_set_lockstep_fusion(1)) and through device memory (3).
 Measured: 0.173 vs 0.174-0.176 s."""
 import os, sys, time, json, io, contextlib
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rscm_amd import _lib as L
 from scripts.bench_magicc_chain import build_chain
 lib = L.load()

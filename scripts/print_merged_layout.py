@@ -1,5 +1,5 @@
 import ctypes as C, sys, os
-sys.path.insert(0, os.environ.get("GRAFT_REPO_ROOT", "/root/repo"))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from rscm_amd import _lib as L
 from scripts.bench_magicc_chain import build_chain
 lib = L.load()

@@ -1,15 +1,16 @@
 """Extract the emissions-driven MAGICC7 scenario the reference's regression suite holds
 (tests/regression/data/ghg_forcing/03_emissions_driven.csv + _config.json under the reference tree:
 SSP245 emissions in, concentrations / forcing / temperature out) into one JSON fixture: the World
-rows, years 1750-2100.  Data only.  Run in the build container:
+rows, years 1750-2100.  Data only.  Run with the reference's checkout as the argument:
 
-    python tests/golden/make_emissions_goldens.py
+    python tests/golden/make_emissions_goldens.py <reference checkout>
 """
 import csv
 import json
 import os
+import sys
 
-SRC = "/root/reference/tests/regression/data/ghg_forcing"
+SRC = os.path.join(sys.argv[1], "tests", "regression", "data", "ghg_forcing")
 HERE = os.path.dirname(os.path.abspath(__file__))
 name = "03_emissions_driven"
 cfg = json.load(open(os.path.join(SRC, name + "_config.json")))

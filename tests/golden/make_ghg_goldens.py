@@ -2,16 +2,17 @@
 forcing (tests/regression/data/ghg_forcing/*.csv + *_config.json under the reference tree) into
 one JSON fixture: per scenario the MAGICC config keys tests/regression/test_ghg_forcing.py reads
 and the World rows of the variables it compares (concentrations in, ERF|CO2/CH4/N2O, total ERF and
-Surface Temperature out).  Data only.  Run in the build container:
+Surface Temperature out).  Data only.  Run with the reference's checkout as the argument:
 
-    python tests/golden/make_ghg_goldens.py
+    python tests/golden/make_ghg_goldens.py <reference checkout>
 """
 import csv
 import glob
 import json
 import os
+import sys
 
-SRC = "/root/reference/tests/regression/data/ghg_forcing"
+SRC = os.path.join(sys.argv[1], "tests", "regression", "data", "ghg_forcing")
 HERE = os.path.dirname(os.path.abspath(__file__))
 KEEP = ("core_co2ch4n2o_rfmethod", "core_climatesensitivity", "core_delq2xco2", "core_rfrapidadjust_co2",
         "core_rfrapidadjust_ch4", "core_rfrapidadjust_n2o", "rf_total_runmodus", "startyear", "endyear")

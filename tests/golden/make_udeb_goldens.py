@@ -2,16 +2,17 @@
 ClimateUDEB (tests/regression/data/ocean_udeb/*.csv + *_config.json under the reference tree)
 into one small JSON fixture: per scenario the MAGICC config keys the test maps onto
 ClimateUDEBParameters (tests/regression/test_ocean_udeb.py:57-109) and the World
-"Surface Temperature" row.  Data only.  Run in the build container:
+"Surface Temperature" row.  Data only.  Run with the reference's checkout as the argument:
 
-    python tests/golden/make_udeb_goldens.py
+    python tests/golden/make_udeb_goldens.py <reference checkout>
 """
 import csv
 import glob
 import json
 import os
+import sys
 
-SRC = "/root/reference/tests/regression/data/ocean_udeb"
+SRC = os.path.join(sys.argv[1], "tests", "regression", "data", "ocean_udeb")
 HERE = os.path.dirname(os.path.abspath(__file__))
 KEEP = ("core_climatesensitivity", "core_delq2xco2", "core_initial_upwelling_rate",
         "core_upwelling_variable_part", "core_ocn_depthdependent", "core_verticaldiff_top_dkdt",
