@@ -73,8 +73,10 @@ extern "C" {
  *      rscm_gpu_set_udeb_variant(3)
  *   5  no entry point changed.  The shipped library no longer reads RSCM_SPLIT_CHUNK / _CHUNK2 / _FIRST, RSCM_LOCKSTEP_SPLIT or
  *      RSCM_UDEB_VARIANT (section "Environment" above); internal header: rscm_gpu_experiments_build, and
- *      rscm_gpu_fail_chunk_launch is consumed by the next cut run whether or not k is reached */
-#define RSCM_GPU_ABI_MINOR 5
+ *      rscm_gpu_fail_chunk_launch is consumed by the next cut run whether or not k is reached
+ *   6  exact quantiles of any storage layout (windowed, output store) and of sharded ensembles: rscm_ens_quantile_rows and the
+ *      staged select rscm_ens_select_begin / _pass / _commit / _result / _end */
+#define RSCM_GPU_ABI_MINOR 6
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -711,6 +713,43 @@ RSCM_API int rscm_ens_summary_series(rscm_ens* h, int32_t var_id, int32_t t_begi
  * statistics; q in [0, 1]. */
 RSCM_API int rscm_ens_quantile_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t n_q,
                                       const double* q, double* out, double* count);
+
+/* ---- exact quantiles of any storage layout and of sharded ensembles (ABI minor 6) ----------- */
+/* The quantiles rscm_ens_quantile_series defines (numpy.nanquantile, method "linear", the same bits) of stored variable var_id
+ * over the rows t_begin, t_begin + t_stride, ... < t_end, read wherever each row is resident: full storage, the window of a
+ * RSCM_FLAG_WINDOWED handle or its output store.  No sort and no member-sized scratch: a radix select of eight passes, each
+ * one histogram of 256 int64 counts per row and target (two targets per quantile).  Signed zeros: -0.0 orders before +0.0
+ * (rscm_ens_quantile_series' sort keeps the two in member order, so a zero result may carry the other sign there).
+ * out[rows][n_q]; count[rows] (or NULL) = members that are not NaN.  Rows beyond the current time index: count 0, quantiles
+ * NaN.  A row that is not resident (slid out of the window and not in the output store), or any row but 0 of a
+ * RSCM_FLAG_NO_SERIES handle: RSCM_ERR_STATE.  q in [0, 1], 1 <= n_q <= 128. */
+RSCM_API int rscm_ens_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q,
+                                    const double* q, double* out, double* count);
+/* The same select in stages, so that a host holding one shard of an ensemble per handle (one rank per GPU, or several
+ * handles in one process) can sum the handles' histograms between the passes -- the quantiles of the WHOLE ensemble with
+ * int64 SUM as the only collective, so the result carries the same bits at any number of ranks:
+ *
+ *     rscm_ens_select_begin(h, var, t0, t1, stride, n_q, q);
+ *     for (;;) {
+ *         rscm_ens_select_pass(h, &done, &buf, &n);     // this handle's counts; the stream is synchronised on return
+ *         if (done) break;
+ *         SUM-all-reduce buf[n] (int64, in place, device memory) over all handles; wait for it to complete
+ *         rscm_ens_select_commit(h);                    // consumes the reduced buffer
+ *     }
+ *     rscm_ens_select_result(h, out, count);            // every handle returns the same numbers
+ *     rscm_ens_select_end(h);
+ *
+ * Every handle must be given the same q, the same row range and stride and be at the same time index; anything else is a
+ * caller error (the buffers then differ in size or meaning and the result is undefined).  The handle must not run, and its
+ * rows must not be written, between begin and the last pass.  One staged select per handle at a time: begin on a handle
+ * with one in flight is RSCM_ERR_STATE; rscm_ens_destroy ends one in flight.  The buffer belongs to the handle and stays
+ * valid until the next pass or end.  Passes: eight while any row of the range is computed, none otherwise. */
+RSCM_API int rscm_ens_select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q,
+                                   const double* q);
+RSCM_API int rscm_ens_select_pass(rscm_ens* h, int32_t* done, int64_t** buf_dev, int64_t* n);
+RSCM_API int rscm_ens_select_commit(rscm_ens* h);
+RSCM_API int rscm_ens_select_result(rscm_ens* h, double* out, double* count);
+RSCM_API int rscm_ens_select_end(rscm_ens* h);
 
 /* Copy the parameter matrix back to the host as [P][N] (e.g. after rscm_ens_sample_lhs). */
 RSCM_API int rscm_ens_get_params(rscm_ens* h, double* out_soa);

@@ -296,6 +296,12 @@ SIGNATURES = {
     "rscm_ens_status_devptr": (C.c_int, [_h, C.POINTER(C.c_void_p)]),
     "rscm_ens_quantile_series": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "rscm_ens_summary_series": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, _dp]),
+    "rscm_ens_quantile_rows": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "rscm_ens_select_begin": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
+    "rscm_ens_select_pass": (C.c_int, [_h, _ip, C.POINTER(C.POINTER(C.c_int64)), C.POINTER(C.c_int64)]),
+    "rscm_ens_select_commit": (C.c_int, [_h]),
+    "rscm_ens_select_result": (C.c_int, [_h, _dp, _dp]),
+    "rscm_ens_select_end": (C.c_int, [_h]),
     "rscm_sampler_create": (C.c_int, [_h, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp, _dp, C.c_int32, _ip, _ip,
                                       _dp, _dp, C.c_int32, C.c_double, C.c_uint64, C.POINTER(_h)]),
     "rscm_sampler_create_sharded": (C.c_int, [_h, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp, _dp, C.c_int32, _ip, _ip,

@@ -1310,6 +1310,13 @@ class GraphModel:
         ens, vid = self.variable_home(name)
         return ens.get_series(vid, **kw)
 
+    def quantile_rows(self, name: str, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> Dict[str, np.ndarray]:
+        """Ensemble quantiles of ``name`` (``numpy.nanquantile``, linear) over the rows ``t_begin, t_begin + t_stride, ...
+        < t_end``, reduced on the device wherever the rows are resident (a windowed graph's window or output store included):
+        ``Ensemble.quantile_rows`` of the variable's home."""
+        ens, vid = self.variable_home(name)
+        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride)
+
     def set_member_params(self, names: Sequence[str], values) -> None:
         """``values[N][len(names)]``: per-member values of the named component parameters; every
         other parameter keeps the value its component was built with."""

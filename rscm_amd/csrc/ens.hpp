@@ -77,6 +77,9 @@ struct LockstepPlan {
     static constexpr int32_t kRing = 128;
 };
 
+// A staged quantile select in flight on a handle (rscm_ens_select_begin .. _end, rscm_gpu.cpp)
+struct SelectState;
+
 struct rscm_ens {
     int32_t kind = 0;
     int64_t N = 0;
@@ -172,6 +175,7 @@ struct rscm_ens {
     bool link_order_check = true;
     int32_t link_refs = 0;  // links of other ensembles into this one's series
 
+    SelectState* select = nullptr;  // rscm_ens_select_begin .. rscm_ens_select_end
     LockstepPlan* plan = nullptr;  // rscm_ens_run_lockstep with this handle first
     WindowDeferral* defer = nullptr;  // set while rscm_ens_run_lockstep collects this handle's window upkeep (lockstep.cpp)
 
@@ -284,6 +288,8 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
 int step_finish(rscm_ens* h, int32_t step_begin, int32_t step_end);
 int run_range(rscm_ens* h, int32_t step_begin, int32_t step_end, bool timed);
 }
+// frees the staged select in flight on h, if any (select_host.cpp)
+void select_release(rscm_ens* h);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (rscm_gpu.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
 

@@ -732,6 +732,22 @@ hipError_t launch_summary_rows(const double* rows, int64_t n, int32_t n_rows, do
 // per row of rows[n_rows][N]: out[r] = {count of non-NaN, quantile q[0], ..., q[n_q-1]} (numpy nanquantile, linear)
 hipError_t launch_quantile_rows(const double* rows, int64_t N, int32_t n_rows, const double* d_q, int32_t n_q, double* d_out,
                                 hipStream_t s);
+// multi-pass radix select (select.hip): 8-bit digits, eight passes; one histogram of kSelBins int64 counts per row in pass 0, per
+// (row, target) later, where target 2k / 2k + 1 of a row is the lower / upper order statistic of quantile k.  Targets are
+// histogrammed kSelGroup per launch (LDS: kSelGroup x kSelBins 32-bit counters).
+constexpr int kSelBins = 256;
+constexpr int kSelPasses = 8;
+constexpr int kSelGroup = 16;
+int32_t select_blocks_per_row(int64_t N, int32_t n_rows);
+// zeroes d_hist[hist_elems], then adds this pass's counts of rows d_rows[n_rows][N] (device array of row pointers)
+hipError_t launch_select_hist(const double* const* d_rows, int64_t N, int32_t n_rows, int32_t pass, const uint64_t* d_prefix, int32_t n_t,
+                              int64_t* d_hist, size_t hist_elems, hipStream_t s);
+// consumes the (reduced) histograms of `pass`: per (row, target) the bucket of its remaining rank; pass 0 also sets d_count[row]
+hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
+                                uint64_t* d_prefix, int64_t* d_rank, hipStream_t s);
+// after the last commit: d_out[r] = {count, quantile q[0], ..., q[n_q-1]} from the selected keys, as launch_quantile_rows
+hipError_t launch_select_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, const double* d_q,
+                                double* d_out, hipStream_t s);
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);

@@ -1,0 +1,245 @@
+// Exact ensemble quantiles by a multi-pass radix select over resident rows, for gfx950 (MI355X).
+//
+// The same numbers as quantile.hip (numpy.nanquantile, method "linear"), reached without sorting and
+// without member-sized scratch: every double maps to an order-preserving 64-bit key (-0.0 before +0.0,
+// NaNs of either sign left out), and each target order statistic is found
+// digit by digit from the top.  Pass p histograms digit p (8 bits) of the members whose key matches a
+// target's prefix of p digits; a commit then picks, per (row, target), the bucket holding the target's
+// remaining rank and extends the prefix.  Eight passes give the whole key.
+//
+// Signed zeros: rocPRIM's radix sort (quantile.hip) takes -0.0 and +0.0 as one key and keeps them in
+// member order, so where a quantile lands on a zero its sign depends on where the members sit.  The
+// select's order (-0.0 first) depends on the member set alone, which is what lets shards combine; the
+// two paths agree bit for bit everywhere else.
+//
+// Everything summed across workgroups (and, by the caller, across ranks) is an int64 count: integer
+// sums are exact and independent of their order, so the result does not depend on the block count,
+// the number of ranks or the order in which they add.  No float atomics.
+//
+// Rows reach the kernels through a device array of row pointers (the host resolves them with
+// rscm_ens::row_ptr), so full storage, the window and the strided output store all work alike.
+#include <hip/hip_runtime.h>
+
+#include "rscm_device.hpp"
+
+namespace rscm {
+
+namespace {
+
+constexpr int kSelThreads = 256;
+
+__device__ __forceinline__ uint64_t order_key(double x)
+{
+    const uint64_t u = (uint64_t)__double_as_longlong(x);
+    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__device__ __forceinline__ double key_value(uint64_t k)
+{
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+
+// Adds one to bin[b] for every lane with `valid`; called by all 64 lanes of the wave together.  When
+// every counting lane has the same bin (clustered members: the top digits of a variable's keys are
+// mostly equal) one lane adds the lane count instead of 64 atomics on one LDS address.
+__device__ __forceinline__ void lds_count(unsigned* bins, unsigned b, bool valid)
+{
+    const uint64_t m = __ballot(valid);
+    if (m == 0) return;
+    const int lead = __ffsll((unsigned long long)m) - 1;
+    const unsigned b0 = (unsigned)__shfl((int)b, lead, 64);
+    if (__ballot(valid && b == b0) == m) {
+        if ((int)(threadIdx.x & 63) == lead) atomicAdd(&bins[b0], (unsigned)__popcll(m));
+    } else if (valid) {
+        atomicAdd(&bins[b], 1u);
+    }
+}
+
+// One pass over rows[r] (blockIdx.y) for the targets [g0, g0 + gn) of each row.  Pass 0 fills one
+// histogram per row (all targets share the empty prefix): hist[r][256].  Later passes fill
+// hist[r][n_t][256] for the targets of the group.  Blocks of one row split its members in pair-aligned
+// chunks; each flushes its LDS counts with one integer atomic per non-zero bin.
+__global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* const* __restrict__ rows, int64_t N, int32_t pass,
+                                                                   const uint64_t* __restrict__ prefix, int32_t n_t, int32_t g0,
+                                                                   int32_t gn, unsigned long long* __restrict__ hist)
+{
+    __shared__ unsigned bins[kSelGroup * kSelBins];
+    __shared__ uint64_t pre[kSelGroup];
+    const int32_t r = (int32_t)blockIdx.y;
+    const int32_t nh = pass == 0 ? 1 : gn;
+    for (int32_t i = (int32_t)threadIdx.x; i < nh * kSelBins; i += kSelThreads) bins[i] = 0u;
+    if ((int32_t)threadIdx.x < nh && pass > 0) pre[threadIdx.x] = prefix[(size_t)r * n_t + g0 + threadIdx.x];
+    __syncthreads();
+
+    const double* row = rows[r];
+    // rows start 8-byte aligned (odd N): the first member goes alone, the rest as 16-byte pairs
+    const int64_t head = ((uintptr_t)row & 15) ? 1 : 0;
+    const int64_t pairs = (N - head) / 2;
+    const int64_t per = (pairs + gridDim.x - 1) / gridDim.x;
+    const int64_t pb = (int64_t)blockIdx.x * per, pe = pb + per < pairs ? pb + per : pairs;
+    const int shift = 56 - 8 * pass;   // the digit of this pass: bits [shift, shift + 8)
+    const double2* row2 = reinterpret_cast<const double2*>(row + head);
+
+    auto count = [&](double x, bool in) {
+        const bool ok = in && x == x;
+        const uint64_t k = order_key(x);
+        const unsigned d = (unsigned)(k >> shift) & (kSelBins - 1);
+        if (pass == 0) {
+            lds_count(bins, d, ok);
+            return;
+        }
+        const uint64_t top = k >> (shift + 8);
+        for (int32_t t = 0; t < gn; ++t) lds_count(bins + t * kSelBins, d, ok && top == pre[t]);
+    };
+
+    for (int64_t base = pb; base < pe; base += kSelThreads) {   // uniform trip count: whole waves call lds_count
+        const int64_t i = base + threadIdx.x;
+        const bool in = i < pe;
+        const double2 v = in ? row2[i] : make_double2(0.0, 0.0);
+        count(v.x, in);
+        count(v.y, in);
+    }
+    if (blockIdx.x == 0 && threadIdx.x < 64) {   // the unpaired head and tail members, one wave
+        const bool in_head = head && threadIdx.x == 0;
+        const bool in_tail = ((N - head) & 1) && threadIdx.x == 1;
+        const double x = in_head ? row[0] : (in_tail ? row[N - 1] : 0.0);
+        count(x, in_head || in_tail);
+    }
+    __syncthreads();
+    unsigned long long* out = hist + (pass == 0 ? (size_t)r * kSelBins : ((size_t)r * n_t + g0) * kSelBins);
+    for (int32_t i = (int32_t)threadIdx.x; i < nh * kSelBins; i += kSelThreads)
+        if (bins[i]) atomicAdd(out + i, (unsigned long long)bins[i]);
+}
+
+// One thread per (row, target).  Target t of row r is order statistic ip (t even) or ip + 1 clipped
+// (t odd) of quantile q[t / 2], numpy's linear method on the row's n non-NaN members; n is the sum of
+// the (reduced) pass-0 histogram, so it is the global count.  rank < 0: the row has no member.
+__global__ void select_commit_kernel(const long long* __restrict__ hist, int32_t pass, int32_t n_rows, int32_t n_t,
+                                     const double* __restrict__ q, int64_t* __restrict__ count, uint64_t* __restrict__ prefix,
+                                     int64_t* __restrict__ rank)
+{
+    const int32_t idx = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx >= n_rows * n_t) return;
+    const int32_t r = idx / n_t, t = idx % n_t;
+    const long long* h;
+    int64_t want;
+    if (pass == 0) {
+        h = hist + (size_t)r * kSelBins;
+        int64_t n = 0;
+        for (int b = 0; b < kSelBins; ++b) n += h[b];
+        if (t == 0) count[r] = n;
+        if (n == 0) {
+            prefix[idx] = 0;
+            rank[idx] = -1;
+            return;
+        }
+        const double vi = (double)(n - 1) * q[t / 2];   // numpy _compute_virtual_index for "linear"
+        double prev = floor(vi);
+        if (prev < 0.0) prev = 0.0;
+        if (prev > (double)(n - 1)) prev = (double)(n - 1);
+        const int64_t ip = (int64_t)prev;
+        want = (t & 1) ? (ip + 1 < n ? ip + 1 : n - 1) : ip;
+    } else {
+        want = rank[idx];
+        if (want < 0) return;
+        h = hist + (size_t)idx * kSelBins;
+    }
+    int64_t below = 0;
+    int b = 0;
+    for (; b < kSelBins - 1; ++b) {
+        if (want < below + h[b]) break;
+        below += h[b];
+    }
+    prefix[idx] = pass == 0 ? (uint64_t)b : (prefix[idx] << 8) | (uint64_t)b;
+    rank[idx] = want - below;
+}
+
+// out[r][0] = count, out[r][1 + k] = quantile q[k]: the two order statistics from their full keys,
+// then numpy's _lerp exactly as quantile_kernel (quantile.hip) applies it.
+__global__ void select_finish_kernel(const int64_t* __restrict__ count, const uint64_t* __restrict__ keys, int32_t n_rows, int32_t n_q,
+                                     const double* __restrict__ q, double* __restrict__ out)
+{
+    const int32_t idx = (int32_t)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (idx >= n_rows * (n_q + 1)) return;
+    const int32_t r = idx / (n_q + 1), k = idx % (n_q + 1);
+    const int64_t n = count[r];
+    if (k == 0) {
+        out[idx] = (double)n;
+        return;
+    }
+    if (n == 0) {
+        out[idx] = __builtin_nan("");
+        return;
+    }
+    const double t = q[k - 1];
+    const double vi = (double)(n - 1) * t;
+    double prev = floor(vi);
+    if (prev < 0.0) prev = 0.0;
+    if (prev > (double)(n - 1)) prev = (double)(n - 1);
+    const double g = vi - prev;
+    const size_t s = (size_t)r * (2 * n_q) + 2 * (k - 1);
+    const double a = key_value(keys[s]), b = key_value(keys[s + 1]);
+    const double d = b - a;
+    double v = a + d * g;
+    if (g >= 0.5) v = b - d * (1.0 - g);
+    if (d == 0.0) v = a;
+    out[idx] = v;
+}
+
+}  // namespace
+
+int32_t select_blocks_per_row(int64_t N, int32_t n_rows)
+{
+    // enough workgroups to fill the chip (~8 per CU) but at least ~4096 members each, so that the flush
+    // (one integer atomic per non-zero bin) stays small next to the members a block reads
+    const int64_t by_size = (N + 4095) / 4096;
+    const int64_t by_chip = (2048 + n_rows - 1) / n_rows;
+    int64_t b = by_size < by_chip ? by_size : by_chip;
+    if (b < 1) b = 1;
+    if (b > 65535) b = 65535;
+    return (int32_t)b;
+}
+
+hipError_t launch_select_hist(const double* const* d_rows, int64_t N, int32_t n_rows, int32_t pass, const uint64_t* d_prefix, int32_t n_t,
+                              int64_t* d_hist, size_t hist_elems, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(d_hist, 0, hist_elems * sizeof(int64_t), s);
+    if (e != hipSuccess || n_rows <= 0 || N <= 0) return e;
+    const unsigned bpr = (unsigned)select_blocks_per_row(N, n_rows);
+    constexpr int32_t kMaxGridY = 65535;
+    for (int32_t r0 = 0; r0 < n_rows; r0 += kMaxGridY) {   // rows in slices the grid's y dimension can index
+        const int32_t nr = n_rows - r0 < kMaxGridY ? n_rows - r0 : kMaxGridY;
+        const size_t row_elems = (size_t)kSelBins * (pass == 0 ? 1 : (size_t)n_t);
+        auto* h = reinterpret_cast<unsigned long long*>(d_hist) + (size_t)r0 * row_elems;
+        const uint64_t* pre = d_prefix + (size_t)r0 * n_t;
+        for (int32_t g0 = 0; g0 < (pass == 0 ? 1 : n_t); g0 += kSelGroup) {
+            const int32_t gn = pass == 0 ? 1 : (n_t - g0 < kSelGroup ? n_t - g0 : kSelGroup);
+            hipLaunchKernelGGL(select_hist_kernel, dim3(bpr, (unsigned)nr), dim3(kSelThreads), 0, s, d_rows + r0, N, pass, pre, n_t, g0,
+                               gn, h);
+            if ((e = hipGetLastError()) != hipSuccess) return e;
+        }
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
+                                uint64_t* d_prefix, int64_t* d_rank, hipStream_t s)
+{
+    const int64_t threads = (int64_t)n_rows * n_t;
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(select_commit_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s,
+                       reinterpret_cast<const long long*>(d_hist), pass, n_rows, n_t, d_q, d_count, d_prefix, d_rank);
+    return hipGetLastError();
+}
+
+hipError_t launch_select_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, const double* d_q,
+                                double* d_out, hipStream_t s)
+{
+    const int64_t threads = (int64_t)n_rows * (n_q + 1);
+    if (threads <= 0) return hipSuccess;
+    hipLaunchKernelGGL(select_finish_kernel, dim3((unsigned)((threads + 255) / 256)), dim3(256), 0, s, d_count, d_keys, n_rows, n_q, d_q,
+                       d_out);
+    return hipGetLastError();
+}
+
+}  // namespace rscm

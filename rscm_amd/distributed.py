@@ -9,7 +9,9 @@ in the CPU tests), are:
 
 * ``gather_members``: all-gather of one small per-member vector (log-likelihood, status) --
   8 B per member, e.g. 8 MB for 1e6 members;
-* ``reduce_summary``: all-reduce of count/sum/min/max.
+* ``reduce_summary``: all-reduce of count/sum/min/max;
+* ``quantile_rows_global``: eight all-reduces (int64 SUM) of radix-select histograms -- a few
+  hundred counts per row and quantile, however many members there are.
 
 Full time series are never gathered: 12 GB into one GPU's seven xGMI links would serialise on
 rank 0 for no benefit; each rank copies its own shard to the host if asked.
@@ -128,6 +130,39 @@ def reduce_summary(local: Dict[str, float], group=None) -> Dict[str, float]:
             "min": float(mn.item()), "max": float(mx.item())}
 
 
+def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+                         group=None) -> Dict[str, np.ndarray]:
+    """Quantiles of the WHOLE sharded ensemble (``Ensemble.quantile_rows`` of all ranks' members together), on every rank.
+
+    Each rank runs the staged radix select on its own shard (``Ensemble.select``); between the passes the ranks sum their
+    int64 histograms -- the only collective, exact and independent of order, so the result has the same bits at any number
+    of ranks and equals the single-process ``quantile_rows`` of the gathered ensemble.  With ``nccl`` the library's buffer is
+    reduced in place through ``__cuda_array_interface__``; with ``gloo`` it goes through the host.  Every rank must pass the
+    same ``q`` and rows and stand at the same time index.  Single process: ``ensemble.quantile_rows``."""
+    if not is_distributed():
+        return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride)
+    import torch
+    from .ensemble import DeviceVector
+    d = _dist()
+    dev = _device_for_backend()
+    with ensemble.select(var, q, t_begin, t_end, t_stride) as s:
+        while True:
+            buf = s.next_pass()
+            if buf is None:
+                break
+            if isinstance(buf, DeviceVector) and dev.type == "cuda":
+                t = torch.as_tensor(buf, device=dev)            # zero-copy view of the library's buffer
+                d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+                torch.cuda.current_stream(dev).synchronize()    # the commit runs on the ensemble's stream
+                s.commit()
+            else:
+                host = buf.to_host() if isinstance(buf, DeviceVector) else np.ascontiguousarray(buf, dtype=np.int64)
+                t = torch.from_numpy(host.copy()).to(dev)
+                d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+                s.commit(t.cpu().numpy())
+        return s.result()
+
+
 class ShardedEnsemble:
     """One global ensemble of ``n_total`` members, this rank holding its block on its GPU.
 
@@ -169,3 +204,7 @@ class ShardedEnsemble:
 
     def summary_global(self, var, tidx: int) -> Dict[str, float]:
         return reduce_summary(self.ensemble.summary(var, tidx))
+
+    def quantile_rows_global(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> Dict[str, np.ndarray]:
+        """Quantiles of the global ensemble at the rows ``t_begin, t_begin + t_stride, ... < t_end`` (``quantile_rows_global``)."""
+        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride)

@@ -400,6 +400,79 @@ class Ensemble:
         L.check(self._lib.rscm_ens_quantile_series(self._h, self._var(var), t_begin, t_end, qq.size, L.dptr(qq), L.dptr(out), L.dptr(cnt)))
         return {"count": cnt.astype(np.int64), "quantiles": out}
 
+    def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> Dict[str, np.ndarray]:
+        """``quantile_series``'s numbers (the same bits) over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any
+        storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows: a radix
+        select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``."""
+        qq = np.atleast_1d(L.f64(q))
+        t_end = self.n_times if t_end is None else t_end
+        rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
+        out, cnt = np.empty((rows, qq.size)), np.empty(rows)
+        L.check(self._lib.rscm_ens_quantile_rows(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), L.dptr(out),
+                                                 L.dptr(cnt)))
+        return {"count": cnt.astype(np.int64), "quantiles": out}
+
+    def select(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> "QuantileSelect":
+        """``quantile_rows`` in stages, for a caller that sums the histograms of several handles between the passes (the
+        shards of one ensemble: ``rscm_amd.distributed.quantile_rows_global``).  Use as a context manager."""
+        return QuantileSelect(self, var, q, t_begin, t_end, t_stride)
+
+
+class QuantileSelect:
+    """A staged select in flight on one ensemble (rscm_ens_select_*)::
+
+        with ens.select(var, q) as s:
+            while (buf := s.next_pass()) is not None:
+                ... SUM-all-reduce buf (int64) over every shard ...
+                s.commit()            # or s.commit(reduced_host_array)
+            res = s.result()
+    """
+
+    def __init__(self, ens: Ensemble, var, q, t_begin: int, t_end: Optional[int], t_stride: int):
+        self.ens = ens
+        self.q = np.atleast_1d(L.f64(q))
+        t_end = ens.n_times if t_end is None else t_end
+        self.rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
+        L.check(ens._lib.rscm_ens_select_begin(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q)))
+        self._open = True
+        self._buf = None
+
+    def next_pass(self) -> Optional[DeviceVector]:
+        """This handle's int64 histograms of the next pass, in device memory, or ``None`` when no pass is left."""
+        done, n = C.c_int32(0), C.c_int64(0)
+        p = C.POINTER(C.c_int64)()
+        L.check(self.ens._lib.rscm_ens_select_pass(self.ens._h, C.byref(done), C.byref(p), C.byref(n)))
+        if done.value:
+            self._buf = None
+            return None
+        self._buf = DeviceVector(C.cast(p, C.c_void_p).value, n.value, np.int64, self.ens)
+        return self._buf
+
+    def commit(self, reduced: Optional[np.ndarray] = None) -> None:
+        """Move every target one digit on from the (reduced) buffer; ``reduced``: host sums to copy into it first."""
+        if reduced is not None:
+            r = np.ascontiguousarray(reduced, dtype=np.int64)
+            if self._buf is None or r.size != self._buf.n:
+                raise ValueError("reduced histograms do not match this pass's buffer")
+            L.check(L.load().rscm_gpu_copy_to_device(self.ens.device, C.c_void_p(self._buf.ptr), r.ctypes.data_as(C.c_void_p), r.nbytes))
+        L.check(self.ens._lib.rscm_ens_select_commit(self.ens._h))
+
+    def result(self) -> Dict[str, np.ndarray]:
+        out, cnt = np.empty((self.rows, self.q.size)), np.empty(self.rows)
+        L.check(self.ens._lib.rscm_ens_select_result(self.ens._h, L.dptr(out), L.dptr(cnt)))
+        return {"count": cnt.astype(np.int64), "quantiles": out}
+
+    def close(self) -> None:
+        if self._open:
+            self._open = False
+            L.check(self.ens._lib.rscm_ens_select_end(self.ens._h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
 
 class _PinnedOwner:
     def __init__(self, ptr):

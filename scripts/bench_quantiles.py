@@ -1,6 +1,8 @@
-"""Plume statistics on the device (run on the GPU box): rscm_ens_summary_series and
-rscm_ens_quantile_series over all 751 rows of a two-layer ensemble, against moving the series to the
-host and calling numpy."""
+"""Plume statistics on the device (run on the GPU box): rscm_ens_summary_series,
+rscm_ens_quantile_series (segmented radix sort) and rscm_ens_quantile_rows (radix select, csrc/select.hip)
+over all 751 rows of a two-layer ensemble, against moving the series to the host and calling numpy.
+Wall times of one call after a warm-up; the kernel times come from a separate
+`rocprofv3 --kernel-trace --stats -- python scripts/bench_quantiles.py` run."""
 import os
 import sys
 import time
@@ -22,9 +24,13 @@ for n in (100_000, 1_000_000):
         e.set_initial(2, 0.0)
         e.run()
         e.quantile_series(1, q, 0, 8)
+        e.quantile_rows(1, q, 0, 8)
         t0 = time.perf_counter(); s = e.summary_series(1); t_sum = time.perf_counter() - t0
         t0 = time.perf_counter(); g = e.quantile_series(1, q); t_q = time.perf_counter() - t0
-        line = f"N={n}: summary_series {t_sum*1e3:.1f} ms, quantile_series (5 quantiles x 751 rows) {t_q*1e3:.1f} ms"
+        t0 = time.perf_counter(); r = e.quantile_rows(1, q); t_r = time.perf_counter() - t0
+        same = np.array_equal(r["quantiles"].view(np.uint64), g["quantiles"].view(np.uint64))
+        line = (f"N={n}: summary_series {t_sum*1e3:.1f} ms, quantile_series (5 quantiles x 751 rows) {t_q*1e3:.1f} ms, "
+                f"quantile_rows {t_r*1e3:.1f} ms (bit-equal: {same})")
         if n <= 100_000:
             t0 = time.perf_counter(); ts = e.get_series(1); t_copy = time.perf_counter() - t0
             t0 = time.perf_counter()

@@ -35,7 +35,31 @@ def build(members, years, exact, window=16, device=0, member_offset=0, members_t
     return model
 
 
-def run(members, years, exact, window=16, device=0, member_offset=0, members_total=None):
+PLUME_Q = [0.05, 0.17, 0.5, 0.83, 0.95]
+
+
+def plume(model):
+    """The annual plume of surface temperature on the device (GraphModel.quantile_rows over the output store, a radix select),
+    timed after one warm-up call, against copying the same rows to the host and calling numpy.nanquantile."""
+    model.quantile_rows("Surface Temperature", PLUME_Q, t_stride=12)
+    t0 = time.perf_counter()
+    got = model.quantile_rows("Surface Temperature", PLUME_Q, t_stride=12)
+    dev_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    ser = model.get_series("Surface Temperature", t_stride=12)
+    copy_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    with np.errstate(all="ignore"):
+        want = np.nanquantile(ser, PLUME_Q, axis=1).T
+    np_s = time.perf_counter() - t0
+    return {"rows": int(ser.shape[0]), "quantiles": PLUME_Q, "quantile_rows_ms": dev_s * 1e3, "host_copy_ms": copy_s * 1e3,
+            "host_copy_mb": ser.nbytes / 1e6, "numpy_nanquantile_ms": np_s * 1e3,
+            "equals_numpy": bool(np.array_equal(got["quantiles"], want, equal_nan=True)),
+            "median_warming_end_K": float(got["quantiles"][-1][2]), "band_5_95_end_K": [float(got["quantiles"][-1][0]),
+                                                                                           float(got["quantiles"][-1][4])]}
+
+
+def run(members, years, exact, window=16, device=0, member_offset=0, members_total=None, with_plume=False):
     free0, total = L.mem_info(device)
     t0 = time.perf_counter()
     model = build_chain(members, years, "topological", steps_per_year=12, device=device, member_offset=member_offset,
@@ -51,13 +75,14 @@ def run(members, years, exact, window=16, device=0, member_offset=0, members_tot
     nl, ns = C.c_int64(), C.c_int64()
     L.check(L.load().rscm_gpu_lockstep_stats(C.byref(nl), C.byref(ns)))
     rows = {n: model.get_series(n, t_stride=12) for n in NAMES}
+    plume_out = plume(model) if with_plume else None
     T = years * 12 + 1
     warm = model.ensembles["Transform:Surface Temperature"].summary(1, T - 1)
     co2 = model.ensembles["CO2Budget"].summary(1, T - 1)
     status = int(model.ensembles["ClimateUDEB"].status().sum())
     model.close()
     return dict(build_s=build_s, run_s=run_s, hbm_gib=(free0 - free1) / 2**30, hbm_total_gib=total / 2**30, launches=int(nl.value),
-                component_steps=int(ns.value), warm=warm, co2=co2, failed=status), rows
+                component_steps=int(ns.value), warm=warm, co2=co2, failed=status, plume=plume_out), rows
 
 
 def first_64(members, years, exact, window=16, device=0, member_offset=0, members_total=None):
@@ -99,9 +124,11 @@ def main():
     ap.add_argument("--fusion", type=int, default=1, help="rscm_gpu_set_lockstep_fusion mode 0..3 (include/rscm_gpu_internal.h)")
     ap.add_argument("--no-anchor", action="store_true",
                     help="skip the 64-member parity anchor (profiling passes: half the dispatches; the anchor is checked by every un-profiled run)")
+    ap.add_argument("--plume", action="store_true",
+                    help="also time the annual 5/17/50/83/95 %% plume of surface temperature on the device (quantile_rows) against numpy")
     args = ap.parse_args()
     L.check(L.load().rscm_gpu_set_lockstep_fusion(args.fusion))
-    big, rows = run(args.members, args.years, args.exact, args.window)
+    big, rows = run(args.members, args.years, args.exact, args.window, with_plume=args.plume)
     small_rows = {n: rows[n][:, :64] for n in NAMES} if args.no_anchor else first_64(args.members, args.years, args.exact, args.window)
     same = {}
     for n in NAMES:
@@ -116,8 +143,10 @@ def main():
            "hbm_total_gib": big["hbm_total_gib"], "failed_members": big["failed"],
            "warming_end_K": big["warm"], "co2_end_ppm": big["co2"],
            "first_64_members_equal_a_64_member_run": same}
+    if args.plume:
+        out["plume"] = big["plume"]
     print(json.dumps(out))
-    sys.exit(0 if all(same.values()) and big["failed"] == 0 else 1)
+    sys.exit(0 if all(same.values()) and big["failed"] == 0 and (not args.plume or big["plume"]["equals_numpy"]) else 1)
 
 
 if __name__ == "__main__":
