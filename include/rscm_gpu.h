@@ -75,8 +75,11 @@ extern "C" {
  *      RSCM_UDEB_VARIANT (section "Environment" above); internal header: rscm_gpu_experiments_build, and
  *      rscm_gpu_fail_chunk_launch is consumed by the next cut run whether or not k is reached
  *   6  exact quantiles of any storage layout (windowed, output store) and of sharded ensembles: rscm_ens_quantile_rows and the
- *      staged select rscm_ens_select_begin / _pass / _commit / _result / _end */
-#define RSCM_GPU_ABI_MINOR 6
+ *      staged select rscm_ens_select_begin / _pass / _commit / _result / _end
+ *   7  likelihood-weighted quantiles (numpy "inverted_cdf" with integer weights): rscm_ens_set_member_weights,
+ *      rscm_ens_member_weights_devptr, rscm_ens_loglik_max, rscm_ens_set_weights_from_loglik, rscm_ens_weighted_quantile_rows,
+ *      rscm_ens_select_begin_weighted */
+#define RSCM_GPU_ABI_MINOR 7
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -750,6 +753,40 @@ RSCM_API int rscm_ens_select_pass(rscm_ens* h, int32_t* done, int64_t** buf_dev,
 RSCM_API int rscm_ens_select_commit(rscm_ens* h);
 RSCM_API int rscm_ens_select_result(rscm_ens* h, double* out, double* count);
 RSCM_API int rscm_ens_select_end(rscm_ens* h);
+
+/* ---- likelihood-weighted quantiles (ABI minor 7) ------------------------------------------------ */
+/* Member weights: int64, one per member, >= 0, summing over the handle's N members to at most 2^53; handle-owned, kept across
+ * rscm_ens_run and rscm_ens_rewind, freed by rscm_ens_destroy.  w (host, or device memory on the handle's device with
+ * on_device != 0) holds N values; a negative one, or a total above 2^53, is RSCM_ERR_INVALID and leaves the weights set
+ * before.  (The bound keeps every histogram sum of the weighted select from wrapping, over up to 2^10 handles.)  Not while a
+ * staged select is in flight (RSCM_ERR_STATE). */
+RSCM_API int rscm_ens_set_member_weights(rscm_ens* h, const int64_t* w, int32_t on_device);
+/* Device address of the [N] int64 weights; RSCM_ERR_STATE (and NULL) if none are set. */
+RSCM_API int rscm_ens_member_weights_devptr(rscm_ens* h, void** out);
+/* *out = max ll[i] over members with status 0 and a finite ll[i]; -inf if there is none.  ll[N]: host or (on_device) device
+ * memory, e.g. the vector of rscm_ens_loglik_device.  A max is exact, so the maxima of shards reduce to the global one. */
+RSCM_API int rscm_ens_loglik_max(rscm_ens* h, const double* ll, int32_t on_device, double* out);
+/* Member weights from a log-likelihood: w[i] = llround(exp(min(ll[i] - ll_max, 0)) * 2^bits) for members with status 0 and a
+ * finite ll[i], else 0.  0 <= bits <= 52; ll_max finite or -inf (members above it get 2^bits).  Members whose likelihood
+ * ratio to ll_max is below 2^-(bits+1) get weight 0.  Sharded ensembles pass one global ll_max and bits, so that every rank's
+ * weights are on one scale; bits <= 53 - ceil(log2(N_total)) keeps every row weight W <= 2^53.  Weights whose total exceeds
+ * 2^53 are refused as by rscm_ens_set_member_weights (RSCM_ERR_INVALID; the weights set before stay). */
+RSCM_API int rscm_ens_set_weights_from_loglik(rscm_ens* h, const double* ll, int32_t on_device, double ll_max, int32_t bits);
+/* numpy.nanquantile(row, q, weights=w, method="inverted_cdf") of stored variable var_id over the rows of
+ * rscm_ens_quantile_rows, with the handle's member weights: per (row, q) the smallest integer C >= 1 with
+ * (double)C / (double)W >= q, W the summed weight of the row's non-NaN members, and the first member in key order at which
+ * the cumulative weight reaches C.  NaN members are left out with their weights; a zero-weight member is never returned.
+ * out[rows][n_q]; weight[rows] (or NULL) = W, exact as a double.  W == 0 (and rows beyond the time index): weight 0,
+ * quantiles NaN.  Signed zeros as rscm_ens_quantile_rows.  No weights set: RSCM_ERR_STATE; a row with W > 2^53:
+ * RSCM_ERR_INVALID; other errors as rscm_ens_quantile_rows. */
+RSCM_API int rscm_ens_weighted_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride,
+                                             int32_t n_q, const double* q, double* out, double* weight);
+/* The weighted select in stages: begin with this, then the loop of rscm_ens_select_pass / _commit / _result / _end above,
+ * unchanged.  The buffer holds int64 weight sums (one histogram per row and quantile after pass 0); _result's count receives
+ * W.  The first commit checks W <= 2^53 on the reduced buffer, so every handle of a sharded select returns RSCM_ERR_INVALID
+ * together; end the select then.  The weights must not change between begin and the last pass. */
+RSCM_API int rscm_ens_select_begin_weighted(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride,
+                                            int32_t n_q, const double* q);
 
 /* Copy the parameter matrix back to the host as [P][N] (e.g. after rscm_ens_sample_lhs). */
 RSCM_API int rscm_ens_get_params(rscm_ens* h, double* out_soa);

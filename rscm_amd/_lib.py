@@ -302,6 +302,12 @@ SIGNATURES = {
     "rscm_ens_select_commit": (C.c_int, [_h]),
     "rscm_ens_select_result": (C.c_int, [_h, _dp, _dp]),
     "rscm_ens_select_end": (C.c_int, [_h]),
+    "rscm_ens_set_member_weights": (C.c_int, [_h, C.POINTER(C.c_int64), C.c_int32]),
+    "rscm_ens_member_weights_devptr": (C.c_int, [_h, C.POINTER(C.c_void_p)]),
+    "rscm_ens_loglik_max": (C.c_int, [_h, _dp, C.c_int32, _dp]),
+    "rscm_ens_set_weights_from_loglik": (C.c_int, [_h, _dp, C.c_int32, C.c_double, C.c_int32]),
+    "rscm_ens_weighted_quantile_rows": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
+    "rscm_ens_select_begin_weighted": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
     "rscm_sampler_create": (C.c_int, [_h, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp, _dp, C.c_int32, _ip, _ip,
                                       _dp, _dp, C.c_int32, C.c_double, C.c_uint64, C.POINTER(_h)]),
     "rscm_sampler_create_sharded": (C.c_int, [_h, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp, _dp, C.c_int32, _ip, _ip,

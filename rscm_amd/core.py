@@ -1310,12 +1310,39 @@ class GraphModel:
         ens, vid = self.variable_home(name)
         return ens.get_series(vid, **kw)
 
-    def quantile_rows(self, name: str, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> Dict[str, np.ndarray]:
+    def quantile_rows(self, name: str, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+                      weighted: bool = False) -> Dict[str, np.ndarray]:
         """Ensemble quantiles of ``name`` (``numpy.nanquantile``, linear) over the rows ``t_begin, t_begin + t_stride, ...
         < t_end``, reduced on the device wherever the rows are resident (a windowed graph's window or output store included):
-        ``Ensemble.quantile_rows`` of the variable's home."""
+        ``Ensemble.quantile_rows`` of the variable's home.  ``weighted``: with the member weights (``set_member_weights`` /
+        ``set_weights_from_loglik``), ``method="inverted_cdf"``; the result then has ``"weight"`` in place of ``"count"``."""
         ens, vid = self.variable_home(name)
-        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride)
+        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted)
+
+    def set_member_weights(self, w) -> None:
+        """Integer member weights (``[N]`` int64 >= 0) for ``quantile_rows(..., weighted=True)``, set on every ensemble of the
+        graph: they all share the member index."""
+        for ens in self.ensembles.values():
+            ens.set_member_weights(w)
+
+    def set_weights_from_loglik(self, ll, bits: Optional[int] = None, ll_max: Optional[float] = None):
+        """Member weights from a per-member log-likelihood ``ll`` (``[N]``, computed by the caller) on every ensemble of the
+        graph, as ``Ensemble.set_weights_from_loglik``.  A member that failed in any ensemble of the graph gets weight 0
+        everywhere, so that every variable's plume reads one member set.  Returns the ``(ll_max, bits)`` used."""
+        from .ensemble import DeviceVector, default_weight_bits
+        x = ll.to_host() if isinstance(ll, DeviceVector) else np.array(ll, dtype=np.float64)
+        if x.shape != (self.n_members,):
+            raise ValueError(f"log-likelihood: need {self.n_members} values, got shape {x.shape}")
+        for ens in self.ensembles.values():
+            x[ens.status() != 0] = -np.inf
+        if ll_max is None:
+            fin = x[np.isfinite(x)]
+            ll_max = float(fin.max()) if fin.size else -np.inf
+        if bits is None:
+            bits = default_weight_bits(self.n_members)
+        for ens in self.ensembles.values():
+            ens.set_weights_from_loglik(x, bits, ll_max)
+        return float(ll_max), int(bits)
 
     def set_member_params(self, names: Sequence[str], values) -> None:
         """``values[N][len(names)]``: per-member values of the named component parameters; every

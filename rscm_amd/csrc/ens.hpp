@@ -176,6 +176,7 @@ struct rscm_ens {
     int32_t link_refs = 0;  // links of other ensembles into this one's series
 
     SelectState* select = nullptr;  // rscm_ens_select_begin .. rscm_ens_select_end
+    int64_t* d_weights = nullptr;   // [N] member weights of the weighted select (rscm_ens_set_member_weights)
     LockstepPlan* plan = nullptr;  // rscm_ens_run_lockstep with this handle first
     WindowDeferral* defer = nullptr;  // set while rscm_ens_run_lockstep collects this handle's window upkeep (lockstep.cpp)
 

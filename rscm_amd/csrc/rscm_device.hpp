@@ -748,6 +748,22 @@ hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_r
 // after the last commit: d_out[r] = {count, quantile q[0], ..., q[n_q-1]} from the selected keys, as launch_quantile_rows
 hipError_t launch_select_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, const double* d_q,
                                 double* d_out, hipStream_t s);
+// the weighted select (wselect.hip): the same passes over int64 member weights d_w[N] (numpy's "inverted_cdf"); one target per
+// quantile; pass 0's reduced histogram sums to W per row, stored as d_count; a row with W > 2^53 sets *d_over and gets NaN
+hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, int64_t N, int32_t n_rows, int32_t pass,
+                               const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
+hipError_t launch_wselect_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
+                                 uint64_t* d_prefix, int64_t* d_rank, int32_t* d_over, hipStream_t s);
+// d_out[r] = {W, quantile q[0], ..., q[n_q-1]}
+hipError_t launch_wselect_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, double* d_out, hipStream_t s);
+// *d_key = max(*d_key, order key of ll[i]) over members with status 0 and finite ll (the caller seeds it with the key of -inf)
+hipError_t launch_loglik_max(const double* d_ll, const uint8_t* d_status, int64_t N, unsigned long long* d_key, hipStream_t s);
+// d_w[i] = llround(exp(min(ll[i] - ll_max, 0)) * 2^bits) for status 0 and finite ll, else 0
+hipError_t launch_weights_from_loglik(const double* d_ll, const uint8_t* d_status, int64_t N, double ll_max, int32_t bits, int64_t* d_w,
+                                      hipStream_t s);
+// *d_flag = 1 if any d_w[i] < 0; *d_total += the sum of the weights, saturated so that it never wraps and exceeds 2^53 iff
+// the true sum does (the caller zeroes both)
+hipError_t launch_weights_check(const int64_t* d_w, int64_t N, int32_t* d_flag, unsigned long long* d_total, hipStream_t s);
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);

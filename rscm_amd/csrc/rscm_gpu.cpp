@@ -767,6 +767,7 @@ int rscm_ens_destroy(rscm_ens* h)
     (void)hipFree(h->d_loglik);
     (void)hipFree(h->d_obs);
     select_release(h);
+    (void)hipFree(h->d_weights);
     if (h->plan) {
         (void)hipFree(h->plan->d_ops);
         if (h->plan->staging) (void)hipHostFree(h->plan->staging);

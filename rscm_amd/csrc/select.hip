@@ -21,23 +21,13 @@
 #include <hip/hip_runtime.h>
 
 #include "rscm_device.hpp"
+#include "select_keys.hpp"
 
 namespace rscm {
 
 namespace {
 
 constexpr int kSelThreads = 256;
-
-__device__ __forceinline__ uint64_t order_key(double x)
-{
-    const uint64_t u = (uint64_t)__double_as_longlong(x);
-    return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-
-__device__ __forceinline__ double key_value(uint64_t k)
-{
-    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
-}
 
 // Adds one to bin[b] for every lane with `valid`; called by all 64 lanes of the wave together.  When
 // every counting lane has the same bin (clustered members: the top digits of a variable's keys are

@@ -1,10 +1,16 @@
-// Host side of the staged quantile select (rscm_ens_select_* and rscm_ens_quantile_rows; kernels in select.hip).
+// Host side of the staged quantile select (rscm_ens_select_* and rscm_ens_quantile_rows; kernels in select.hip), of its weighted
+// form (rscm_ens_select_begin_weighted, rscm_ens_weighted_quantile_rows; wselect.hip) and of the member weights it reads.
 //
 // A select resolves its rows once, at begin, into a device array of row pointers (rscm_ens::row_ptr: full storage, the window or
 // the strided output store), then alternates pass (histograms of this handle's members) and commit (the reduced histograms move
 // every target one digit on) kSelPasses times.  Between the two a caller with several handles -- ranks of one sharded ensemble,
 // or two ensembles on one GPU -- sums the int64 buffers of all of them; every handle then commits the same sums and so reaches
-// the same keys.
+// the same keys.  The weighted select runs the same stages over the handle's int64 member weights: one target per quantile, and
+// pass 0's reduced histograms give each row's weight W, which the first commit checks against 2^53 on every handle.
+#include <cmath>
+#include <cstring>
+#include <limits>
+
 #include "ens.hpp"
 
 struct SelectState {
@@ -14,6 +20,7 @@ struct SelectState {
     int32_t n_q = 0, n_t = 0;
     int32_t pass = 0;       // the next pass to histogram
     bool awaiting_commit = false;
+    bool weighted = false;  // rscm_ens_select_begin_weighted: count holds W, n_t == n_q
     const double** d_rows = nullptr;
     double* d_q = nullptr;
     int64_t* d_hist = nullptr;
@@ -22,9 +29,12 @@ struct SelectState {
     uint64_t* d_prefix = nullptr;
     int64_t* d_rank = nullptr;
     double* d_out = nullptr;
+    int32_t* d_over = nullptr;   // weighted: set by the first commit if a row's W exceeds 2^53
 
     void release()
     {
+        (void)hipFree(d_over);
+        d_over = nullptr;
         (void)hipFree(d_rows);
         (void)hipFree(d_q);
         (void)hipFree(d_hist);
@@ -46,8 +56,10 @@ namespace {
 
 constexpr int32_t kMaxSelectQuantiles = 128;
 
-int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q)
+int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q,
+                bool weighted = false)
 {
+    if (weighted && !h->d_weights) return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
     if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
     if (t_begin < 0 || t_end > h->T || t_begin > t_end || t_stride < 1)
         return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d", t_begin, t_end, t_stride);
@@ -60,7 +72,8 @@ int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, in
     s.t_begin = t_begin;
     s.t_stride = t_stride;
     s.n_q = n_q;
-    s.n_t = 2 * n_q;
+    s.n_t = weighted ? n_q : 2 * n_q;
+    s.weighted = weighted;
     std::vector<const double*> rows;
     for (int32_t t = t_begin; t < t_end; t += t_stride) {
         ++s.n_rows;
@@ -84,6 +97,7 @@ int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, in
     HIPCHK(rscm::dev_malloc(&s.d_prefix, nc * nt * sizeof(uint64_t)));
     HIPCHK(rscm::dev_malloc(&s.d_rank, nc * nt * sizeof(int64_t)));
     HIPCHK(rscm::dev_malloc(&s.d_out, nc * (size_t)(n_q + 1) * sizeof(double)));
+    if (weighted) HIPCHK(rscm::dev_malloc(&s.d_over, sizeof(int32_t)));
     HIPCHK(hipMemcpyAsync(s.d_rows, rows.data(), nc * sizeof(double*), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(s.d_q, q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));   // the host vectors go out of scope
@@ -101,7 +115,10 @@ int select_pass(rscm_ens* h, SelectState& s, int32_t* done, int64_t** buf_dev, i
     }
     if (int rc = set_device(h)) return rc;
     const size_t elems = (size_t)s.n_comp * rscm::kSelBins * (s.pass == 0 ? 1 : (size_t)s.n_t);
-    HIPCHK(rscm::launch_select_hist(s.d_rows, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
+    if (s.weighted)
+        HIPCHK(rscm::launch_wselect_hist(s.d_rows, h->d_weights, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
+    else
+        HIPCHK(rscm::launch_select_hist(s.d_rows, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     s.awaiting_commit = true;
     *done = 0;
@@ -114,6 +131,20 @@ int select_commit(rscm_ens* h, SelectState& s)
 {
     if (!s.awaiting_commit) return fail(RSCM_ERR_STATE, "select: no pass to commit");
     if (int rc = set_device(h)) return rc;
+    if (s.weighted) {
+        const bool first = s.pass == 0;
+        if (first) HIPCHK(hipMemsetAsync(s.d_over, 0, sizeof(int32_t), h->stream));
+        HIPCHK(rscm::launch_wselect_commit(s.d_hist, s.pass, s.n_comp, s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, s.d_over, h->stream));
+        s.awaiting_commit = false;
+        if (++s.pass == rscm::kSelPasses) HIPCHK(rscm::launch_wselect_finish(s.d_count, s.d_prefix, s.n_comp, s.n_q, s.d_out, h->stream));
+        if (first) {
+            int32_t over = 0;
+            HIPCHK(hipMemcpyAsync(&over, s.d_over, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPCHK(hipStreamSynchronize(h->stream));
+            if (over) return fail(RSCM_ERR_INVALID, "weighted select: the weights of a row's non-NaN members sum to more than 2^53");
+        }
+        return RSCM_OK;
+    }
     HIPCHK(rscm::launch_select_commit(s.d_hist, s.pass, s.n_comp, s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, h->stream));
     s.awaiting_commit = false;
     if (++s.pass == rscm::kSelPasses)
@@ -141,6 +172,39 @@ int select_result(rscm_ens* h, SelectState& s, double* out, double* count)
     return RSCM_OK;
 }
 
+int select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q, bool weighted)
+{
+    if (h->select) return fail(RSCM_ERR_STATE, "a select is already in flight on this handle: rscm_ens_select_end it first");
+    auto* s = new SelectState();
+    if (int rc = select_init(h, *s, var_id, t_begin, t_end, t_stride, n_q, q, weighted)) {
+        s->release();
+        delete s;
+        return rc;
+    }
+    h->select = s;
+    return RSCM_OK;
+}
+
+int quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q, double* out,
+                  double* count, bool weighted)
+{
+    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
+    SelectState s;   // its own state: a staged select in flight on the handle is left alone
+    int rc = select_init(h, s, var_id, t_begin, t_end, t_stride, n_q, q, weighted);
+    int32_t done = 0;
+    while (rc == RSCM_OK) {
+        if ((rc = select_pass(h, s, &done, nullptr, nullptr)) != RSCM_OK || done) break;
+        rc = select_commit(h, s);
+    }
+    if (rc == RSCM_OK) rc = select_result(h, s, out, count);
+    if (s.d_rows) {
+        (void)hipSetDevice(h->device);
+        (void)hipStreamSynchronize(h->stream);
+    }
+    s.release();
+    return rc;
+}
+
 }  // namespace
 
 void select_release(rscm_ens* h)
@@ -157,15 +221,15 @@ int rscm_ens_select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t 
 {
     GUARD_BEGIN
     NEED(h);
-    if (h->select) return fail(RSCM_ERR_STATE, "a select is already in flight on this handle: rscm_ens_select_end it first");
-    auto* s = new SelectState();
-    if (int rc = select_init(h, *s, var_id, t_begin, t_end, t_stride, n_q, q)) {
-        s->release();
-        delete s;
-        return rc;
-    }
-    h->select = s;
-    return RSCM_OK;
+    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, false);
+    GUARD_END
+}
+
+int rscm_ens_select_begin_weighted(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q)
+{
+    GUARD_BEGIN
+    NEED(h);
+    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, true);
     GUARD_END
 }
 
@@ -215,21 +279,162 @@ int rscm_ens_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t
 {
     GUARD_BEGIN
     NEED(h);
+    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, count, false);
+    GUARD_END
+}
+
+int rscm_ens_weighted_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q,
+                                    const double* q, double* out, double* weight)
+{
+    GUARD_BEGIN
+    NEED(h);
+    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, weight, true);
+    GUARD_END
+}
+
+}  // extern "C"
+
+// ---- member weights of the weighted select ----
+
+namespace {
+
+// Makes d_new[N] (device memory, taken over: freed on failure) the handle's weights if no weight is negative and they sum to at
+// most 2^53.  That bound on every handle keeps every histogram sum of the weighted select from wrapping (wselect.hip); on any
+// failure the weights set before stay.
+int install_weights(rscm_ens* h, int64_t* d_new)
+{
+    int32_t* d_flag = nullptr;
+    unsigned long long* d_total = nullptr;
+    int32_t neg = 0;
+    unsigned long long total = 0;
+    hipError_t e = rscm::dev_malloc(&d_flag, sizeof(int32_t));
+    if (e == hipSuccess) e = rscm::dev_malloc(&d_total, sizeof total);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, sizeof total, h->stream);
+    if (e == hipSuccess) e = rscm::launch_weights_check(d_new, h->N, d_flag, d_total, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&neg, d_flag, sizeof neg, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_flag);
+    (void)hipFree(d_total);
+    if (e != hipSuccess || neg || total > (1ull << 53)) {
+        (void)hipFree(d_new);
+        HIPCHK(e);
+        if (neg) return fail(RSCM_ERR_INVALID, "a member weight is negative");
+        return fail(RSCM_ERR_INVALID, "the member weights of this handle sum to more than 2^53");
+    }
+    (void)hipFree(h->d_weights);
+    h->d_weights = d_new;
+    return RSCM_OK;
+}
+
+// ll on the device: the caller's pointer, or (host input) a copy in *tmp, which the caller frees
+int device_loglik(rscm_ens* h, const double* ll, int32_t on_device, double** tmp, const double** d_ll)
+{
+    *tmp = nullptr;
+    if (on_device) {
+        *d_ll = ll;
+        return RSCM_OK;
+    }
+    HIPCHK(rscm::dev_malloc(tmp, (size_t)h->N * sizeof(double)));
+    HIPCHK(hipMemcpyAsync(*tmp, ll, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    *d_ll = *tmp;
+    return RSCM_OK;
+}
+
+int loglik_max(rscm_ens* h, const double* d_ll, double* out)
+{
+    unsigned long long* d_key = nullptr;
+    const double lo = -std::numeric_limits<double>::infinity();
+    uint64_t u;
+    std::memcpy(&u, &lo, sizeof u);
+    unsigned long long key = (u >> 63) ? ~u : (u | 0x8000000000000000ull);   // order key of -inf (select_keys.hpp)
+    hipError_t e = rscm::dev_malloc(&d_key, sizeof key);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_key, &key, sizeof key, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = rscm::launch_loglik_max(d_ll, h->d_status, h->N, d_key, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&key, d_key, sizeof key, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_key);
+    HIPCHK(e);
+    u = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
+    std::memcpy(out, &u, sizeof u);
+    return RSCM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rscm_ens_set_member_weights(rscm_ens* h, const int64_t* w, int32_t on_device)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!w) return fail(RSCM_ERR_INVALID, "weights are NULL");
+    if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
+    if (int rc = set_device(h)) return rc;
+    int64_t* d_new = nullptr;
+    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(int64_t)));
+    hipError_t e = hipMemcpyAsync(d_new, w, (size_t)h->N * sizeof(int64_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                  h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(d_new);
+        HIPCHK(e);
+    }
+    return install_weights(h, d_new);
+    GUARD_END
+}
+
+int rscm_ens_member_weights_devptr(rscm_ens* h, void** out)
+{
+    NEED(h);
     if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
-    SelectState s;   // its own state: a staged select in flight on the handle is left alone
-    int rc = select_init(h, s, var_id, t_begin, t_end, t_stride, n_q, q);
-    int32_t done = 0;
-    while (rc == RSCM_OK) {
-        if ((rc = select_pass(h, s, &done, nullptr, nullptr)) != RSCM_OK || done) break;
-        rc = select_commit(h, s);
-    }
-    if (rc == RSCM_OK) rc = select_result(h, s, out, count);
-    if (s.d_rows) {
-        (void)hipSetDevice(h->device);
-        (void)hipStreamSynchronize(h->stream);
-    }
-    s.release();
+    *out = h->d_weights;
+    if (!h->d_weights) return fail(RSCM_ERR_STATE, "no member weights set");
+    return RSCM_OK;
+}
+
+int rscm_ens_loglik_max(rscm_ens* h, const double* ll, int32_t on_device, double* out)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!ll || !out) return fail(RSCM_ERR_INVALID, "ll or out is NULL");
+    if (int rc = set_device(h)) return rc;
+    double* tmp = nullptr;
+    const double* d_ll = nullptr;
+    int rc = device_loglik(h, ll, on_device, &tmp, &d_ll);
+    if (rc == RSCM_OK) rc = loglik_max(h, d_ll, out);
+    (void)hipStreamSynchronize(h->stream);
+    (void)hipFree(tmp);
     return rc;
+    GUARD_END
+}
+
+int rscm_ens_set_weights_from_loglik(rscm_ens* h, const double* ll, int32_t on_device, double ll_max, int32_t bits)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!ll) return fail(RSCM_ERR_INVALID, "ll is NULL");
+    if (bits < 0 || bits > 52) return fail(RSCM_ERR_INVALID, "bits = %d: must be in [0, 52]", bits);
+    if (std::isnan(ll_max) || ll_max == std::numeric_limits<double>::infinity())
+        return fail(RSCM_ERR_INVALID, "ll_max must be finite or -inf, got %g", ll_max);
+    if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
+    if (int rc = set_device(h)) return rc;
+    int64_t* d_new = nullptr;
+    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(int64_t)));
+    double* tmp = nullptr;
+    const double* d_ll = nullptr;
+    int rc = device_loglik(h, ll, on_device, &tmp, &d_ll);
+    hipError_t e = hipSuccess;
+    if (rc == RSCM_OK) e = rscm::launch_weights_from_loglik(d_ll, h->d_status, h->N, ll_max, bits, d_new, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    (void)hipFree(tmp);
+    if (rc != RSCM_OK || e != hipSuccess || es != hipSuccess) {
+        (void)hipFree(d_new);
+        if (rc != RSCM_OK) return rc;
+        HIPCHK(e);
+        HIPCHK(es);
+    }
+    return install_weights(h, d_new);   // refused if N weights of up to 2^bits sum to more than 2^53
     GUARD_END
 }
 

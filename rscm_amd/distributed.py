@@ -11,7 +11,9 @@ in the CPU tests), are:
   8 B per member, e.g. 8 MB for 1e6 members;
 * ``reduce_summary``: all-reduce of count/sum/min/max;
 * ``quantile_rows_global``: eight all-reduces (int64 SUM) of radix-select histograms -- a few
-  hundred counts per row and quantile, however many members there are.
+  hundred counts per row and quantile, however many members there are (weight sums instead of
+  counts for the likelihood-weighted quantiles);
+* ``ShardedEnsemble.constrain``: one all-reduce (MAX) of the local log-likelihood maxima.
 
 Full time series are never gathered: 12 GB into one GPU's seven xGMI links would serialise on
 rank 0 for no benefit; each rank copies its own shard to the host if asked.
@@ -131,21 +133,28 @@ def reduce_summary(local: Dict[str, float], group=None) -> Dict[str, float]:
 
 
 def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                         group=None) -> Dict[str, np.ndarray]:
+                         group=None, weighted: bool = False) -> Dict[str, np.ndarray]:
     """Quantiles of the WHOLE sharded ensemble (``Ensemble.quantile_rows`` of all ranks' members together), on every rank.
 
     Each rank runs the staged radix select on its own shard (``Ensemble.select``); between the passes the ranks sum their
     int64 histograms -- the only collective, exact and independent of order, so the result has the same bits at any number
     of ranks and equals the single-process ``quantile_rows`` of the gathered ensemble.  With ``nccl`` the library's buffer is
     reduced in place through ``__cuda_array_interface__``; with ``gloo`` it goes through the host.  Every rank must pass the
-    same ``q`` and rows and stand at the same time index.  Single process: ``ensemble.quantile_rows``."""
+    same ``q`` and rows and stand at the same time index.  Single process: ``ensemble.quantile_rows``.
+
+    ``weighted``: the likelihood-weighted quantiles (``Ensemble.quantile_rows(..., weighted=True)``) of the whole ensemble,
+    the ranks' member weights on one scale (``ShardedEnsemble.constrain``); the histograms then hold int64 weight sums and
+    the result has ``"weight"`` in place of ``"count"``."""
     if not is_distributed():
+        if weighted:
+            return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride, weighted=True)
         return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride)
     import torch
     from .ensemble import DeviceVector
     d = _dist()
     dev = _device_for_backend()
-    with ensemble.select(var, q, t_begin, t_end, t_stride) as s:
+    sel = ensemble.select(var, q, t_begin, t_end, t_stride, weighted=True) if weighted else ensemble.select(var, q, t_begin, t_end, t_stride)
+    with sel as s:
         while True:
             buf = s.next_pass()
             if buf is None:
@@ -205,6 +214,25 @@ class ShardedEnsemble:
     def summary_global(self, var, tidx: int) -> Dict[str, float]:
         return reduce_summary(self.ensemble.summary(var, tidx))
 
-    def quantile_rows_global(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> Dict[str, np.ndarray]:
-        """Quantiles of the global ensemble at the rows ``t_begin, t_begin + t_stride, ... < t_end`` (``quantile_rows_global``)."""
-        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride)
+    def quantile_rows_global(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+                             weighted: bool = False) -> Dict[str, np.ndarray]:
+        """Quantiles of the global ensemble at the rows ``t_begin, t_begin + t_stride, ... < t_end`` (``quantile_rows_global``);
+        ``weighted``: with the member weights ``constrain`` set."""
+        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride, weighted=weighted)
+
+    def constrain(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, bits: Optional[int] = None):
+        """Weight this rank's members by their fit to observations, on one scale across all ranks: the Gaussian
+        log-likelihood on the device, a MAX all-reduce of the local maxima, then ``set_weights_from_loglik`` with the global
+        max and ``bits`` (default ``53 - ceil(log2(n_total))``).  Returns the ``(ll_max, bits)`` used, the same on every rank."""
+        from .ensemble import default_weight_bits
+        ll = self.ensemble.loglik(obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device=True)
+        ll_max = self.ensemble.loglik_max(ll)
+        if is_distributed():
+            import torch
+            d = _dist()
+            m = torch.tensor([ll_max], dtype=torch.float64, device=_device_for_backend())
+            d.all_reduce(m, op=d.ReduceOp.MAX)
+            ll_max = float(m.item())
+        if bits is None:
+            bits = default_weight_bits(self.n_total)
+        return self.ensemble.set_weights_from_loglik(ll, bits, ll_max)

@@ -400,22 +400,100 @@ class Ensemble:
         L.check(self._lib.rscm_ens_quantile_series(self._h, self._var(var), t_begin, t_end, qq.size, L.dptr(qq), L.dptr(out), L.dptr(cnt)))
         return {"count": cnt.astype(np.int64), "quantiles": out}
 
-    def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> Dict[str, np.ndarray]:
+    def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+                      weighted: bool = False) -> Dict[str, np.ndarray]:
         """``quantile_series``'s numbers (the same bits) over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any
         storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows: a radix
-        select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``."""
+        select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``.
+
+        ``weighted``: ``numpy.nanquantile(row, q, weights=w, method="inverted_cdf")`` with the member weights
+        (``set_member_weights`` / ``set_weights_from_loglik``; rscm_ens_weighted_quantile_rows).  Returns
+        ``{"weight": [rows] (summed weight of the non-NaN members), "quantiles": [rows][len(q)]}``."""
         qq = np.atleast_1d(L.f64(q))
         t_end = self.n_times if t_end is None else t_end
         rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
         out, cnt = np.empty((rows, qq.size)), np.empty(rows)
-        L.check(self._lib.rscm_ens_quantile_rows(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), L.dptr(out),
-                                                 L.dptr(cnt)))
-        return {"count": cnt.astype(np.int64), "quantiles": out}
+        fn = self._lib.rscm_ens_weighted_quantile_rows if weighted else self._lib.rscm_ens_quantile_rows
+        L.check(fn(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), L.dptr(out), L.dptr(cnt)))
+        return {"weight" if weighted else "count": cnt.astype(np.int64), "quantiles": out}
 
-    def select(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> "QuantileSelect":
+    def select(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+               weighted: bool = False) -> "QuantileSelect":
         """``quantile_rows`` in stages, for a caller that sums the histograms of several handles between the passes (the
-        shards of one ensemble: ``rscm_amd.distributed.quantile_rows_global``).  Use as a context manager."""
-        return QuantileSelect(self, var, q, t_begin, t_end, t_stride)
+        shards of one ensemble: ``rscm_amd.distributed.quantile_rows_global``).  Use as a context manager.  ``weighted``: the
+        weighted select; ``result()`` then returns ``{"weight", "quantiles"}``."""
+        return QuantileSelect(self, var, q, t_begin, t_end, t_stride, weighted)
+
+    # -- member weights (the weighted quantiles) ---------------------------------------------
+    def set_member_weights(self, w) -> None:
+        """Integer member weights for ``quantile_rows(..., weighted=True)``: ``[N]`` int64 >= 0, a numpy array or an int64
+        ``DeviceVector`` (device memory on this ensemble's GPU).  They stay across ``run`` and ``rewind``."""
+        if isinstance(w, DeviceVector):
+            if w.n != self.n_members or w.dtype != np.int64:
+                raise ValueError(f"weights: need an int64 device vector of {self.n_members} members")
+            L.check(self._lib.rscm_ens_set_member_weights(self._h, C.cast(C.c_void_p(w.ptr), C.POINTER(C.c_int64)), 1))
+            return
+        a = np.asarray(w)
+        if a.shape != (self.n_members,):
+            raise ValueError(f"weights: need {self.n_members} values, got shape {a.shape}")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("weights must be integers (quantise float weights first: set_weights_from_loglik)")
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        L.check(self._lib.rscm_ens_set_member_weights(self._h, a.ctypes.data_as(C.POINTER(C.c_int64)), 0))
+
+    def member_weights_device(self) -> DeviceVector:
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_member_weights_devptr(self._h, C.byref(p)))
+        return DeviceVector(p.value, self.n_members, np.int64, self)
+
+    def member_weights(self) -> np.ndarray:
+        """The member weights, ``[N]`` int64, copied to the host."""
+        return self.member_weights_device().to_host()
+
+    def _loglik_arg(self, ll):
+        if isinstance(ll, DeviceVector):
+            if ll.n != self.n_members or ll.dtype != np.float64:
+                raise ValueError(f"log-likelihood: need a float64 device vector of {self.n_members} members")
+            return C.cast(C.c_void_p(ll.ptr), C.POINTER(C.c_double)), 1, None
+        a = np.ascontiguousarray(ll, dtype=np.float64)
+        if a.shape != (self.n_members,):
+            raise ValueError(f"log-likelihood: need {self.n_members} values, got shape {a.shape}")
+        return L.dptr(a), 0, a
+
+    def loglik_max(self, ll) -> float:
+        """max ``ll`` over members with status ok and a finite value (``-inf`` if none); ``ll``: numpy or ``DeviceVector``."""
+        p, on_dev, _keep = self._loglik_arg(ll)
+        out = C.c_double()
+        L.check(self._lib.rscm_ens_loglik_max(self._h, p, on_dev, C.byref(out)))
+        return out.value
+
+    def set_weights_from_loglik(self, ll, bits: Optional[int] = None, ll_max: Optional[float] = None,
+                                n_total: Optional[int] = None):
+        """Member weights ``llround(exp(min(ll - ll_max, 0)) * 2**bits)`` for ok members with a finite ``ll``, 0 otherwise.
+        ``ll_max`` defaults to ``loglik_max(ll)``; ``bits`` to ``53 - ceil(log2(n_total))`` (52 for one member), which keeps
+        every row's summed weight within 2^53; ``n_total`` (default: this ensemble's members) is the size of the whole ensemble
+        when this one is a shard.  Returns the ``(ll_max, bits)`` used."""
+        if ll_max is None:
+            ll_max = self.loglik_max(ll)
+        if bits is None:
+            bits = default_weight_bits(self.n_members if n_total is None else n_total)
+        p, on_dev, _keep = self._loglik_arg(ll)
+        L.check(self._lib.rscm_ens_set_weights_from_loglik(self._h, p, on_dev, float(ll_max), int(bits)))
+        return float(ll_max), int(bits)
+
+    def weights_ess(self) -> float:
+        """Effective sample size of the member weights, ``(sum w)^2 / sum w^2`` in float64 on the host (a diagnostic)."""
+        w = self.member_weights().astype(np.float64)
+        s2 = float(np.dot(w, w))
+        return float(w.sum()) ** 2 / s2 if s2 > 0 else 0.0
+
+
+def default_weight_bits(n_total: int) -> int:
+    """The quantisation depth that keeps ``n_total`` weights of at most ``2**bits`` summing to at most 2^53."""
+    n = int(n_total)
+    if n <= 1:
+        return 52
+    return 53 - (n - 1).bit_length()   # ceil(log2(n)) for n >= 2
 
 
 class QuantileSelect:
@@ -428,12 +506,14 @@ class QuantileSelect:
             res = s.result()
     """
 
-    def __init__(self, ens: Ensemble, var, q, t_begin: int, t_end: Optional[int], t_stride: int):
+    def __init__(self, ens: Ensemble, var, q, t_begin: int, t_end: Optional[int], t_stride: int, weighted: bool = False):
         self.ens = ens
         self.q = np.atleast_1d(L.f64(q))
+        self.weighted = bool(weighted)
         t_end = ens.n_times if t_end is None else t_end
         self.rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
-        L.check(ens._lib.rscm_ens_select_begin(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q)))
+        begin = ens._lib.rscm_ens_select_begin_weighted if weighted else ens._lib.rscm_ens_select_begin
+        L.check(begin(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q)))
         self._open = True
         self._buf = None
 
@@ -460,7 +540,7 @@ class QuantileSelect:
     def result(self) -> Dict[str, np.ndarray]:
         out, cnt = np.empty((self.rows, self.q.size)), np.empty(self.rows)
         L.check(self.ens._lib.rscm_ens_select_result(self.ens._h, L.dptr(out), L.dptr(cnt)))
-        return {"count": cnt.astype(np.int64), "quantiles": out}
+        return {"weight" if self.weighted else "count": cnt.astype(np.int64), "quantiles": out}
 
     def close(self) -> None:
         if self._open:

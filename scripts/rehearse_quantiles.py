@@ -10,6 +10,11 @@ store.
     RSCM_BENCH_BACKEND=gloo python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \\
         --master-addr 127.0.0.1 --master-port 29561 scripts/rehearse_quantiles.py --out OUT_DIR
 Every rank writes <out>/rank<k>.json; exit code 0 iff all checks hold.
+
+--weighted also constrains the ensemble by its fit to three surface-temperature "observations" (ShardedEnsemble.constrain: the
+device log-likelihood, a MAX all-reduce of the local maxima, quantisation with the global member count) and checks the
+likelihood-weighted quantiles of the whole ensemble (quantile_rows_global(weighted=True)) against the single process that
+quantises the gathered log-likelihood itself: the same weights and the same bits, and numpy's weighted "inverted_cdf".
 """
 import argparse
 import json
@@ -41,10 +46,37 @@ def adversarial_rows(n):
             rng.choice([-0.0, 0.0], n)]
 
 
+def weighted_checks(tag, se, whole, stride, n_total, obs_tidx):
+    """Sharded constrain + weighted quantiles of the whole ensemble against the single process, bit for bit."""
+    from rscm_amd.ensemble import default_weight_bits
+    obs = dict(obs_var=["Surface Temperature"] * 3, obs_tidx=obs_tidx, obs_value=[0.3, 0.5, 0.7], obs_sigma=[0.2, 0.2, 0.2])
+    ll_max, bits = se.constrain(**obs)
+    ll = whole.loglik(**obs, on_device=True)
+    want_max, want_bits = whole.set_weights_from_loglik(ll, n_total=n_total)
+    out = {f"{tag}_w_scale_equal": ll_max == want_max and bits == want_bits == default_weight_bits(n_total),
+           f"{tag}_w_equal": bool(np.array_equal(se.ensemble.member_weights(), whole.member_weights()[se.offset:se.offset + se.count]))}
+    got = se.quantile_rows_global("Surface Temperature", Q, 0, None, stride, weighted=True)
+    want = whole.quantile_rows("Surface Temperature", Q, 0, None, stride, weighted=True)
+    out[f"{tag}_weighted_bit_equal"] = bool(np.array_equal(got["quantiles"].view(np.uint64), want["quantiles"].view(np.uint64)))
+    out[f"{tag}_weighted_weight_equal"] = bool(np.array_equal(got["weight"], want["weight"]))
+    ser = whole.get_series("Surface Temperature", 0, None, stride)
+    w = whole.member_weights()
+    ok = want["weight"] > 0
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        npq = np.nanquantile(ser[ok], Q, axis=1, weights=np.broadcast_to(w, ser[ok].shape), method="inverted_cdf").T
+    unsign = lambda x: np.where(x == 0, 0.0, x)  # noqa: E731  (the key order puts -0.0 first; numpy keeps member order)
+    out[f"{tag}_weighted_numpy_equal"] = bool(np.array_equal(unsign(got["quantiles"][ok]), unsign(npq))
+                                              and np.isnan(got["quantiles"][~ok]).all())
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--members", type=int, default=30_001)
     ap.add_argument("--out", required=True, help="directory for the per-rank result files")
+    ap.add_argument("--weighted", action="store_true", help="also check the likelihood-weighted quantiles (ShardedEnsemble.constrain)")
     args = ap.parse_args()
     import torch.distributed as dist
     import rscm_amd
@@ -97,6 +129,8 @@ def main():
                     warnings.simplefilter("ignore", RuntimeWarning)
                     npq = np.nanquantile(ser, Q, axis=1).T
             checks[f"{tag}_numpy_equal"] = bool(np.array_equal(got["quantiles"], npq, equal_nan=True))
+            if args.weighted:
+                checks.update(weighted_checks(tag, se, whole, stride, n_total, [144, 146, 148] if window else [60, 100, 140]))
         se.ensemble.close()
     ok = all(checks.values())
     res = {"rank": rank, "world": world, "members": n_total, "ok": ok, "checks": checks}

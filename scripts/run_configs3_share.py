@@ -4,7 +4,7 @@ MONTHLY model steps 1750-2500 (9001 points, 9000 steps), ClimateUDEB and OceanCa
 model step, series in a window of --window rows (default 96: 3.5 GB of the 288; the window slides once every ~80 steps) with annual
 (every 12th) rows of every variable kept.
 
-    python scripts/run_configs3_share.py [--members 125000] [--years 750] [--exact]
+    python scripts/run_configs3_share.py [--members 125000] [--years 750] [--exact] [--plume [--weighted]]
 
 Prints one JSON line: build / run wall time, HBM allocated, launches, member-years/s (a member-year = 12 model
 steps here), ensemble statistics at the end, and -- the parity anchor at this size -- whether the first 64
@@ -59,7 +59,44 @@ def plume(model):
                                                                                            float(got["quantiles"][-1][4])]}
 
 
-def run(members, years, exact, window=16, device=0, member_offset=0, members_total=None, with_plume=False):
+HIST_YEARS = (1850, 2014)   # the "historical" annual rows the weighted plume is constrained on
+OBS_SIGMA = 0.1             # K
+
+
+def weighted_plume(model):
+    """The constrained plume: member weights from each member's fit to a historical record of annual surface temperature, then
+    the weighted annual plume on the device (GraphModel.quantile_rows(weighted=True), numpy's "inverted_cdf"), against numpy's
+    weighted nanquantile of the rows copied to the host.  The repository holds no observed record, so the record is a synthetic
+    stand-in: member 0's own run (as scripts/calibrate_magicc_chain.py does).  The log-likelihood is formed on the host from
+    the rows of the output store -- glue, not a device path."""
+    ser = model.get_series("Surface Temperature", t_stride=12)
+    lo, hi = HIST_YEARS[0] - 1750, min(HIST_YEARS[1] - 1750, ser.shape[0] - 1)
+    hist = ser[lo:hi + 1]
+    obs = hist[:, 0].copy()
+    with np.errstate(all="ignore"):
+        ll = -0.5 * (((hist - obs[:, None]) / OBS_SIGMA) ** 2).sum(axis=0)
+    ll_max, bits = model.set_weights_from_loglik(ll)
+    w = model.ensembles["ClimateUDEB"].member_weights()
+    model.quantile_rows("Surface Temperature", PLUME_Q, t_stride=12, weighted=True)
+    t0 = time.perf_counter()
+    got = model.quantile_rows("Surface Temperature", PLUME_Q, t_stride=12, weighted=True)
+    dev_s = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    live = got["weight"] > 0
+    with np.errstate(all="ignore"):
+        want = np.full_like(got["quantiles"], np.nan)
+        want[live] = np.nanquantile(ser[live], PLUME_Q, axis=1, weights=np.broadcast_to(w, ser[live].shape), method="inverted_cdf").T
+    np_s = time.perf_counter() - t0
+    same = np.array_equal(np.where(got["quantiles"] == 0, 0.0, got["quantiles"]), np.where(want == 0, 0.0, want), equal_nan=True)
+    return {"constrained_on": f"annual surface temperature {HIST_YEARS[0]}-{lo + 1750 + hist.shape[0] - 1}, member 0's run as "
+                              f"the record, sigma {OBS_SIGMA} K", "ll_max": ll_max, "bits": bits,
+            "ess": model.ensembles["ClimateUDEB"].weights_ess(), "weighted_quantile_rows_ms": dev_s * 1e3,
+            "numpy_weighted_nanquantile_ms": np_s * 1e3, "equals_numpy": bool(same),
+            "median_warming_end_K": float(got["quantiles"][-1][2]),
+            "band_5_95_end_K": [float(got["quantiles"][-1][0]), float(got["quantiles"][-1][4])]}
+
+
+def run(members, years, exact, window=16, device=0, member_offset=0, members_total=None, with_plume=False, weighted=False):
     free0, total = L.mem_info(device)
     t0 = time.perf_counter()
     model = build_chain(members, years, "topological", steps_per_year=12, device=device, member_offset=member_offset,
@@ -76,6 +113,8 @@ def run(members, years, exact, window=16, device=0, member_offset=0, members_tot
     L.check(L.load().rscm_gpu_lockstep_stats(C.byref(nl), C.byref(ns)))
     rows = {n: model.get_series(n, t_stride=12) for n in NAMES}
     plume_out = plume(model) if with_plume else None
+    if with_plume and weighted:
+        plume_out["weighted"] = weighted_plume(model)
     T = years * 12 + 1
     warm = model.ensembles["Transform:Surface Temperature"].summary(1, T - 1)
     co2 = model.ensembles["CO2Budget"].summary(1, T - 1)
@@ -126,9 +165,11 @@ def main():
                     help="skip the 64-member parity anchor (profiling passes: half the dispatches; the anchor is checked by every un-profiled run)")
     ap.add_argument("--plume", action="store_true",
                     help="also time the annual 5/17/50/83/95 %% plume of surface temperature on the device (quantile_rows) against numpy")
+    ap.add_argument("--weighted", action="store_true",
+                    help="with --plume: also the plume weighted by each member's fit to a historical record (see weighted_plume)")
     args = ap.parse_args()
     L.check(L.load().rscm_gpu_set_lockstep_fusion(args.fusion))
-    big, rows = run(args.members, args.years, args.exact, args.window, with_plume=args.plume)
+    big, rows = run(args.members, args.years, args.exact, args.window, with_plume=args.plume, weighted=args.weighted)
     small_rows = {n: rows[n][:, :64] for n in NAMES} if args.no_anchor else first_64(args.members, args.years, args.exact, args.window)
     same = {}
     for n in NAMES:
@@ -146,7 +187,8 @@ def main():
     if args.plume:
         out["plume"] = big["plume"]
     print(json.dumps(out))
-    sys.exit(0 if all(same.values()) and big["failed"] == 0 and (not args.plume or big["plume"]["equals_numpy"]) else 1)
+    sys.exit(0 if all(same.values()) and big["failed"] == 0 and (not args.plume or big["plume"]["equals_numpy"])
+             and (not (args.plume and args.weighted) or big["plume"]["weighted"]["equals_numpy"]) else 1)
 
 
 if __name__ == "__main__":
