@@ -78,8 +78,11 @@ extern "C" {
  *      staged select rscm_ens_select_begin / _pass / _commit / _result / _end
  *   7  likelihood-weighted quantiles (numpy "inverted_cdf" with integer weights): rscm_ens_set_member_weights,
  *      rscm_ens_member_weights_devptr, rscm_ens_loglik_max, rscm_ens_set_weights_from_loglik, rscm_ens_weighted_quantile_rows,
- *      rscm_ens_select_begin_weighted */
-#define RSCM_GPU_ABI_MINOR 7
+ *      rscm_ens_select_begin_weighted
+ *   8  anomalies, per-member indicators and exceedance: rscm_ens_set_baseline, rscm_ens_set_baseline_values,
+ *      rscm_ens_baseline_devptr, rscm_ens_clear_baseline, rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex,
+ *      rscm_ens_member_indicators, rscm_ens_quantile_vectors, rscm_ens_select_begin_vectors, rscm_ens_exceedance */
+#define RSCM_GPU_ABI_MINOR 8
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -787,6 +790,52 @@ RSCM_API int rscm_ens_weighted_quantile_rows(rscm_ens* h, int32_t var_id, int32_
  * together; end the select then.  The weights must not change between begin and the last pass. */
 RSCM_API int rscm_ens_select_begin_weighted(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride,
                                             int32_t n_q, const double* q);
+
+/* ---- anomalies, per-member indicators and exceedance (ABI minor 8) ------------------------------ */
+/* Rows are those of rscm_ens_quantile_rows (t_begin, t_begin + t_stride, ... < t_end, any storage layout); the time of row t is
+ * time_bounds[t] of the handle.  The baseline b[N] is handle-owned, kept across rscm_ens_run and rscm_ens_rewind, freed by
+ * rscm_ens_destroy; one per handle.  It does not change while a staged select is in flight (RSCM_ERR_STATE).
+ * rscm_ens_set_baseline: b[i] = the sum of member i's values over the rows in row order (f64, no FMA) divided by the row count
+ * (IEEE division); a NaN in a member's rows makes its b[i] NaN.  At least one row; every row computed (RSCM_ERR_STATE) and
+ * resident (RSCM_ERR_STATE, as rscm_ens_quantile_rows).  On failure the baseline set before stays. */
+RSCM_API int rscm_ens_set_baseline(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride);
+/* b: N values, host or (on_device != 0) device memory on the handle's device. */
+RSCM_API int rscm_ens_set_baseline_values(rscm_ens* h, const double* b, int32_t on_device);
+/* Device address of the [N] baseline; RSCM_ERR_STATE (and NULL) if none is set. */
+RSCM_API int rscm_ens_baseline_devptr(rscm_ens* h, void** out);
+RSCM_API int rscm_ens_clear_baseline(rscm_ens* h);
+/* Flags of the _ex and vector selects */
+#define RSCM_SELECT_WEIGHTED 1 /* the member weights, numpy "inverted_cdf" (rscm_ens_weighted_quantile_rows) */
+#define RSCM_SELECT_ANOMALY 2  /* of the anomalies x[i] - b[i] (one IEEE subtraction) against the baseline; stored rows only */
+/* rscm_ens_quantile_rows (flags 0) and rscm_ens_weighted_quantile_rows (RSCM_SELECT_WEIGHTED) with flags: the same
+ * definitions applied to each member's anomaly with RSCM_SELECT_ANOMALY (a NaN anomaly is left out).  count[rows] receives the
+ * count, or W when weighted.  Anomaly without a baseline: RSCM_ERR_STATE; an unknown flag: RSCM_ERR_INVALID. */
+RSCM_API int rscm_ens_quantile_rows_ex(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q,
+                                       const double* q, int32_t flags, double* out, double* count);
+/* The staged form: begin with this, then rscm_ens_select_pass / _commit / _result / _end, unchanged. */
+RSCM_API int rscm_ens_select_begin_ex(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q,
+                                      const double* q, int32_t flags);
+/* Per-member indicators over the rows, of x or (anomaly != 0) of x - b: a member with a NaN value in any row gets NaN in every
+ * indicator, else mean = sum in row order / row count, peak = the maximum, peak_time = time of the first row attaining it
+ * (numpy.argmax), crossing[k] = time of the first row with value >= thr[k], +inf if none; 0 <= n_thr <= 8.  Written to the
+ * handle-owned block of `slot` (0 <= slot < 4), [3 + n_thr][N] doubles from *out_dev: mean, peak, peak_time, crossings.  A slot's
+ * address stays for the handle's life; its contents until the next call on the slot.  Rows as rscm_ens_set_baseline; anomaly
+ * without a baseline and a select in flight: RSCM_ERR_STATE; a bad slot: RSCM_ERR_INVALID. */
+RSCM_API int rscm_ens_member_indicators(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t anomaly,
+                                        int32_t n_thr, const double* thr, int32_t slot, void** out_dev);
+/* The quantiles of rscm_ens_quantile_rows_ex with vec_dev[n_vec] (a host array) of device addresses of N doubles on the handle's
+ * device (indicators, rscm_ens_params_devptr rows, a log-likelihood) as the rows: out[n_vec][n_q], count[n_vec].
+ * RSCM_SELECT_ANOMALY: RSCM_ERR_INVALID; so is an address that is not device memory of N doubles on the handle's device.  The
+ * vectors must not change between begin and the last pass of the staged form. */
+RSCM_API int rscm_ens_quantile_vectors(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t n_q, const double* q,
+                                       int32_t flags, double* out, double* count);
+RSCM_API int rscm_ens_select_begin_vectors(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t n_q, const double* q,
+                                           int32_t flags);
+/* Exceedance of the device vector vec_dev[N]: hits[k] = the number of non-NaN members with v >= thr[k] (weighted != 0: the sum of
+ * their member weights), *total = the number (summed weight) of non-NaN members; 0 <= n_thr <= 8.  int64, exact, so the sums of
+ * shards are those of the whole ensemble; the probability is hits / total.  Weighted without weights: RSCM_ERR_STATE. */
+RSCM_API int rscm_ens_exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted, int64_t* hits,
+                                 int64_t* total);
 
 /* Copy the parameter matrix back to the host as [P][N] (e.g. after rscm_ens_sample_lhs). */
 RSCM_API int rscm_ens_get_params(rscm_ens* h, double* out_soa);

@@ -28,6 +28,8 @@ COMP_TWO_LAYER, COMP_CARBON_CYCLE = 0, 1
 MODE_EXACT, MODE_FAST = 0, 1
 FLAG_NO_SERIES = 1
 FLAG_WINDOWED = 2
+SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
+SELECT_ANOMALY = 2
 
 TL_VARS = {"Effective Radiative Forcing": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2}
 CP_VARS = {"Emissions|CO2|Anthropogenic": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2,
@@ -308,6 +310,17 @@ SIGNATURES = {
     "rscm_ens_set_weights_from_loglik": (C.c_int, [_h, _dp, C.c_int32, C.c_double, C.c_int32]),
     "rscm_ens_weighted_quantile_rows": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "rscm_ens_select_begin_weighted": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp]),
+    "rscm_ens_set_baseline": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rscm_ens_set_baseline_values": (C.c_int, [_h, _dp, C.c_int32]),
+    "rscm_ens_baseline_devptr": (C.c_int, [_h, C.POINTER(C.c_void_p)]),
+    "rscm_ens_clear_baseline": (C.c_int, [_h]),
+    "rscm_ens_quantile_rows_ex": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp]),
+    "rscm_ens_select_begin_ex": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32]),
+    "rscm_ens_member_indicators": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32,
+                                             C.POINTER(C.c_void_p)]),
+    "rscm_ens_quantile_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, _dp]),
+    "rscm_ens_select_begin_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32]),
+    "rscm_ens_exceedance": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rscm_sampler_create": (C.c_int, [_h, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp, _dp, C.c_int32, _ip, _ip,
                                       _dp, _dp, C.c_int32, C.c_double, C.c_uint64, C.POINTER(_h)]),
     "rscm_sampler_create_sharded": (C.c_int, [_h, C.c_int32, C.c_int32, _ip, _dp, _ip, _dp, _dp, _dp, _dp, C.c_int32, _ip, _ip,

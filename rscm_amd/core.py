@@ -1311,13 +1311,48 @@ class GraphModel:
         return ens.get_series(vid, **kw)
 
     def quantile_rows(self, name: str, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                      weighted: bool = False) -> Dict[str, np.ndarray]:
+                      weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
         """Ensemble quantiles of ``name`` (``numpy.nanquantile``, linear) over the rows ``t_begin, t_begin + t_stride, ...
         < t_end``, reduced on the device wherever the rows are resident (a windowed graph's window or output store included):
         ``Ensemble.quantile_rows`` of the variable's home.  ``weighted``: with the member weights (``set_member_weights`` /
-        ``set_weights_from_loglik``), ``method="inverted_cdf"``; the result then has ``"weight"`` in place of ``"count"``."""
+        ``set_weights_from_loglik``), ``method="inverted_cdf"``; the result then has ``"weight"`` in place of ``"count"``.
+        ``anomaly``: of each member's anomaly against the baseline ``set_baseline`` gave the variable's home."""
         ens, vid = self.variable_home(name)
+        if anomaly:
+            return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=True)
         return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted)
+
+    def set_baseline(self, name: str, t_begin: int, t_end: int, t_stride: int = 1) -> None:
+        """Each member's mean of ``name`` over the rows ``t_begin, t_begin + t_stride, ... < t_end`` as the baseline of the
+        variable's home ensemble (``Ensemble.set_baseline``; one baseline per ensemble, so variables sharing a home share it)."""
+        ens, vid = self.variable_home(name)
+        ens.set_baseline(vid, t_begin, t_end, t_stride)
+
+    def set_baseline_values(self, name: str, b) -> None:
+        self.variable_home(name)[0].set_baseline_values(b)
+
+    def baseline(self, name: str) -> np.ndarray:
+        return self.variable_home(name)[0].baseline()
+
+    def clear_baseline(self, name: str) -> None:
+        self.variable_home(name)[0].clear_baseline()
+
+    def indicators(self, name: str, t_begin: int, t_end: int, t_stride: int = 1, thresholds=(), anomaly: bool = False,
+                   slot: int = 0) -> Dict[str, object]:
+        """``Ensemble.indicators`` of ``name`` on its home ensemble: device vectors ``mean``, ``peak``, ``peak_time``,
+        ``crossing``, which ``quantile_vectors`` and ``exceedance`` read."""
+        ens, vid = self.variable_home(name)
+        return ens.indicators(vid, t_begin, t_end, t_stride, thresholds, anomaly, slot)
+
+    def quantile_vectors(self, vectors, q, weighted: bool = False) -> Dict[str, np.ndarray]:
+        """``Ensemble.quantile_vectors`` on the ensemble that owns the vectors (every ensemble of the graph shares the member
+        index and, after ``set_member_weights`` / ``set_weights_from_loglik``, the weights)."""
+        vs = list(vectors)
+        return vs[0].owner.quantile_vectors(vs, q, weighted=weighted)
+
+    def exceedance(self, vector, thresholds, weighted: bool = False) -> Dict[str, object]:
+        """``Ensemble.exceedance`` on the ensemble that owns the vector."""
+        return vector.owner.exceedance(vector, thresholds, weighted=weighted)
 
     def set_member_weights(self, w) -> None:
         """Integer member weights (``[N]`` int64 >= 0) for ``quantile_rows(..., weighted=True)``, set on every ensemble of the

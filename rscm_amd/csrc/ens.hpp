@@ -177,6 +177,9 @@ struct rscm_ens {
 
     SelectState* select = nullptr;  // rscm_ens_select_begin .. rscm_ens_select_end
     int64_t* d_weights = nullptr;   // [N] member weights of the weighted select (rscm_ens_set_member_weights)
+    double* d_base = nullptr;       // [N] baseline of the anomaly select and indicators (rscm_ens_set_baseline)
+    static constexpr int32_t kIndSlots = 4;
+    double* d_ind[kIndSlots] = {};  // [3 + kMaxThresholds][N] per slot of rscm_ens_member_indicators, allocated at first use
     LockstepPlan* plan = nullptr;  // rscm_ens_run_lockstep with this handle first
     WindowDeferral* defer = nullptr;  // set while rscm_ens_run_lockstep collects this handle's window upkeep (lockstep.cpp)
 
@@ -291,6 +294,13 @@ int run_range(rscm_ens* h, int32_t step_begin, int32_t step_end, bool timed);
 }
 // frees the staged select in flight on h, if any (select_host.cpp)
 void select_release(rscm_ens* h);
+// the rows t_begin, t_begin + t_stride, ... < t_end of var_id that this model instance has computed (t <= time_index), as device
+// addresses (rscm_ens::row_ptr); *n_range = the rows of the whole range.  RSCM_ERR_STATE if a computed row is not resident.  The
+// caller has checked var_id and the range (select_host.cpp).
+int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
+                 int32_t* n_range);
+// RSCM_OK if p is device memory on h's device holding at least N doubles from p on, else RSCM_ERR_INVALID (select_host.cpp)
+int check_member_vector(const rscm_ens* h, const double* p, const char* what);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (rscm_gpu.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
 

@@ -1,0 +1,154 @@
+// Per-member indicators of an ensemble and exceedance counts, for gfx950 (MI355X).
+//
+// indicators_kernel: one thread per member walks a device array of row pointers (resolved by the host with rscm_ens::row_ptr,
+// as the radix select's are: full storage, the window, the output store) and keeps, in registers, the sum in row order, the
+// maximum and the time of the first row attaining it, and the time of the first row at or above each of up to kMaxThresholds
+// thresholds.  Lanes of a wave read consecutive members of one row, so every load is coalesced; each row is read once.  The
+// values are the member's x or its anomaly x - b[i] against the handle's baseline (one IEEE subtraction).  A NaN in any row makes
+// every indicator of the member NaN.  Without the per-row extras (all == false) the same kernel forms the baseline itself: the
+// mean over the reference rows.  The sum starts at -0.0, the additive identity, so it is numpy's rows[0] + rows[1] + ... exactly
+// (-ffp-contract=off: no FMA), and the mean is one IEEE division.
+//
+// exceedance_kernel: per block, the counts (or the summed int64 member weights) of members at or above each threshold and of
+// non-NaN members go into LDS int64 bins, then one integer atomic per bin.  No float atomics: the sums are exact and independent
+// of the block count, and shards of one ensemble add them exactly.  With the weights' bound (a handle's weights sum to at most
+// 2^53, wselect.hip) nothing wraps.
+#include <hip/hip_runtime.h>
+
+#include "rscm_device.hpp"
+
+namespace rscm {
+
+namespace {
+
+constexpr int kIndThreads = 256;
+constexpr int kIndBatch = 8;   // rows whose loads a thread issues before it uses them
+
+template <bool kAnom, bool kAll>
+__global__ __launch_bounds__(kIndThreads) void indicators_kernel(const double* const* __restrict__ rows, const double* __restrict__ time,
+                                                                  int32_t n_rows, const double* __restrict__ base, int64_t N,
+                                                                  int32_t n_thr, Thresholds thr, double* __restrict__ out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kIndThreads + threadIdx.x;
+    if (i >= N) return;
+    const double b = kAnom ? base[i] : 0.0;
+    double sum = -0.0, peak = -__builtin_inf(), peak_t = time[0];
+    double cross[kMaxThresholds];
+#pragma unroll
+    for (int k = 0; k < kMaxThresholds; ++k) cross[k] = __builtin_inf();
+    unsigned found = 0u;
+    bool nan = false;
+
+    auto take = [&](double x, double t) {
+        if constexpr (kAnom) x = x - b;
+        nan = nan || x != x;
+        sum = sum + x;
+        if constexpr (kAll) {
+            if (x > peak) {
+                peak = x;
+                peak_t = t;
+            }
+#pragma unroll
+            for (int k = 0; k < kMaxThresholds; ++k) {
+                if (k < n_thr && !(found & (1u << k)) && x >= thr.v[k]) {
+                    found |= 1u << k;
+                    cross[k] = t;
+                }
+            }
+        }
+    };
+
+    int32_t r = 0;
+    for (; r + kIndBatch <= n_rows; r += kIndBatch) {
+        double x[kIndBatch];
+#pragma unroll
+        for (int j = 0; j < kIndBatch; ++j) x[j] = rows[r + j][i];
+#pragma unroll
+        for (int j = 0; j < kIndBatch; ++j) take(x[j], kAll ? time[r + j] : 0.0);
+    }
+    for (; r < n_rows; ++r) take(rows[r][i], kAll ? time[r] : 0.0);
+
+    const double qnan = __builtin_nan("");
+    out[i] = nan ? qnan : sum / (double)n_rows;
+    if constexpr (kAll) {
+        out[N + i] = nan ? qnan : peak;
+        out[2 * N + i] = nan ? qnan : peak_t;
+        for (int32_t k = 0; k < n_thr; ++k) out[(3 + (int64_t)k) * N + i] = nan ? qnan : cross[k];
+    }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
+{
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
+
+constexpr int kExcBlocks = 1024;
+
+template <bool kW>
+__global__ __launch_bounds__(kIndThreads) void exceedance_kernel(const double* __restrict__ v, const int64_t* __restrict__ w, int64_t N,
+                                                                  int32_t n_thr, Thresholds thr, unsigned long long* __restrict__ acc)
+{
+    __shared__ unsigned long long bins[kMaxThresholds + 1];
+    if (threadIdx.x <= kMaxThresholds) bins[threadIdx.x] = 0ull;
+    __syncthreads();
+    unsigned long long hit[kMaxThresholds], tot = 0ull;
+#pragma unroll
+    for (int k = 0; k < kMaxThresholds; ++k) hit[k] = 0ull;
+    for (int64_t i = (int64_t)blockIdx.x * kIndThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kIndThreads) {
+        const double x = v[i];
+        const unsigned long long wt = kW ? (unsigned long long)w[i] : 1ull;
+        if (x == x) {
+            tot += wt;
+#pragma unroll
+            for (int k = 0; k < kMaxThresholds; ++k)
+                if (k < n_thr && x >= thr.v[k]) hit[k] += wt;
+        }
+    }
+    tot = wave_sum(tot);
+#pragma unroll
+    for (int k = 0; k < kMaxThresholds; ++k)
+        if (k < n_thr) hit[k] = wave_sum(hit[k]);
+    if ((threadIdx.x & 63) == 0) {
+        if (tot) atomicAdd(&bins[kMaxThresholds], tot);
+#pragma unroll
+        for (int k = 0; k < kMaxThresholds; ++k)
+            if (k < n_thr && hit[k]) atomicAdd(&bins[k], hit[k]);
+    }
+    __syncthreads();
+    if ((int32_t)threadIdx.x < n_thr && bins[threadIdx.x]) atomicAdd(&acc[threadIdx.x], bins[threadIdx.x]);
+    if ((int32_t)threadIdx.x == n_thr && bins[kMaxThresholds]) atomicAdd(&acc[n_thr], bins[kMaxThresholds]);
+}
+
+}  // namespace
+
+hipError_t launch_indicators(const double* const* d_rows, const double* d_time, int32_t n_rows, const double* d_base, int64_t N, bool all,
+                             int32_t n_thr, const Thresholds& thr, double* d_out, hipStream_t s)
+{
+    if (N <= 0 || n_rows <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((N + kIndThreads - 1) / kIndThreads));
+    if (d_base && all)
+        hipLaunchKernelGGL((indicators_kernel<true, true>), grid, dim3(kIndThreads), 0, s, d_rows, d_time, n_rows, d_base, N, n_thr, thr, d_out);
+    else if (d_base)
+        hipLaunchKernelGGL((indicators_kernel<true, false>), grid, dim3(kIndThreads), 0, s, d_rows, d_time, n_rows, d_base, N, n_thr, thr, d_out);
+    else if (all)
+        hipLaunchKernelGGL((indicators_kernel<false, true>), grid, dim3(kIndThreads), 0, s, d_rows, d_time, n_rows, d_base, N, n_thr, thr, d_out);
+    else
+        hipLaunchKernelGGL((indicators_kernel<false, false>), grid, dim3(kIndThreads), 0, s, d_rows, d_time, n_rows, d_base, N, n_thr, thr, d_out);
+    return hipGetLastError();
+}
+
+hipError_t launch_exceedance(const double* d_v, const int64_t* d_w, int64_t N, int32_t n_thr, const Thresholds& thr,
+                             unsigned long long* d_acc, hipStream_t s)
+{
+    if (N <= 0) return hipSuccess;
+    const int64_t need = (N + kIndThreads - 1) / kIndThreads;
+    const dim3 grid((unsigned)(need < kExcBlocks ? need : kExcBlocks));
+    if (d_w)
+        hipLaunchKernelGGL(exceedance_kernel<true>, grid, dim3(kIndThreads), 0, s, d_v, d_w, N, n_thr, thr, d_acc);
+    else
+        hipLaunchKernelGGL(exceedance_kernel<false>, grid, dim3(kIndThreads), 0, s, d_v, d_w, N, n_thr, thr, d_acc);
+    return hipGetLastError();
+}
+
+}  // namespace rscm

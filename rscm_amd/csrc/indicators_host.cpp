@@ -1,0 +1,192 @@
+// Host side of the handle's baseline (rscm_ens_set_baseline*, the anomaly select's b[i]), of the per-member indicators
+// (rscm_ens_member_indicators) and of the exceedance counts (rscm_ens_exceedance); kernels in indicators.hip.
+//
+// Rows are resolved as the radix select resolves them (resolve_rows: full storage, the window, the output store) and must all be
+// computed.  The baseline and the indicator slots are handle-owned and kept across run and rewind, as the member weights are; a
+// staged select may read either, so neither changes while one is in flight.
+#include <cmath>
+#include <cstring>
+#include <limits>
+
+#include "ens.hpp"
+
+namespace {
+
+// The device row pointers and row times of the computed rows t_begin, t_begin + t_stride, ... < t_end of var_id; every row of the
+// range must be computed and resident
+int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
+                std::vector<double>& times)
+{
+    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
+    if (t_begin < 0 || t_end > h->T || t_begin >= t_end || t_stride < 1)
+        return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d (at least one row)", t_begin, t_end, t_stride);
+    if (!h->windowed && h->rows != h->T && t_end > 1)
+        return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
+    int32_t n_range = 0;
+    if (int rc = resolve_rows(h, var_id, t_begin, t_end, t_stride, rows, &n_range)) return rc;
+    if ((int32_t)rows.size() != n_range)
+        return fail(RSCM_ERR_STATE, "rows of [%d, %d) are beyond the current time index %d", t_begin, t_end, h->time_index);
+    for (int32_t t = t_begin; t < t_end; t += t_stride) times.push_back(h->bounds[t]);
+    return RSCM_OK;
+}
+
+// Runs the indicator kernel over the rows into d_out ([1][N] with all false, else [3 + n_thr][N]) and waits for it
+int run_indicators(rscm_ens* h, const std::vector<const double*>& rows, const std::vector<double>& times, const double* d_base, bool all,
+                   int32_t n_thr, const double* thr, double* d_out)
+{
+    rscm::Thresholds th{};
+    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
+    const double** d_rows = nullptr;
+    double* d_time = nullptr;
+    hipError_t e = rscm::dev_malloc(&d_rows, rows.size() * sizeof(double*));
+    if (e == hipSuccess) e = rscm::dev_malloc(&d_time, times.size() * sizeof(double));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_time, times.data(), times.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = rscm::launch_indicators(d_rows, d_time, (int32_t)rows.size(), d_base, h->N, all, n_thr, th, d_out, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_rows);
+    (void)hipFree(d_time);
+    HIPCHK(e);
+    HIPCHK(es);
+    return RSCM_OK;
+}
+
+int check_thresholds(int32_t n_thr, const double* thr, int32_t lo)
+{
+    if (n_thr < lo || n_thr > rscm::kMaxThresholds || (n_thr > 0 && !thr))
+        return fail(RSCM_ERR_INVALID, "bad threshold list (%d to %d thresholds)", lo, rscm::kMaxThresholds);
+    return RSCM_OK;
+}
+
+int no_select(const rscm_ens* h)
+{
+    if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
+    return RSCM_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rscm_ens_set_baseline(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (int rc = no_select(h)) return rc;
+    std::vector<const double*> rows;
+    std::vector<double> times;
+    if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
+    if (int rc = set_device(h)) return rc;
+    double* d_new = nullptr;
+    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(double)));
+    if (int rc = run_indicators(h, rows, times, nullptr, false, 0, nullptr, d_new)) {
+        (void)hipFree(d_new);
+        return rc;
+    }
+    (void)hipFree(h->d_base);
+    h->d_base = d_new;
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_set_baseline_values(rscm_ens* h, const double* b, int32_t on_device)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!b) return fail(RSCM_ERR_INVALID, "baseline is NULL");
+    if (int rc = no_select(h)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (on_device)
+        if (int rc = check_member_vector(h, b, "baseline")) return rc;
+    double* d_new = nullptr;
+    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(double)));
+    hipError_t e = hipMemcpyAsync(d_new, b, (size_t)h->N * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
+                                  h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)hipFree(d_new);
+        HIPCHK(e);
+    }
+    (void)hipFree(h->d_base);
+    h->d_base = d_new;
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_baseline_devptr(rscm_ens* h, void** out)
+{
+    NEED(h);
+    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
+    *out = h->d_base;
+    if (!h->d_base) return fail(RSCM_ERR_STATE, "no baseline set");
+    return RSCM_OK;
+}
+
+int rscm_ens_clear_baseline(rscm_ens* h)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (int rc = no_select(h)) return rc;
+    if (h->d_base) {
+        if (int rc = set_device(h)) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_base);
+        h->d_base = nullptr;
+    }
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_member_indicators(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t anomaly, int32_t n_thr,
+                               const double* thr, int32_t slot, void** out_dev)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
+    *out_dev = nullptr;
+    if (slot < 0 || slot >= rscm_ens::kIndSlots) return fail(RSCM_ERR_INVALID, "slot %d: must be in [0, %d)", slot, rscm_ens::kIndSlots);
+    if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
+    if (anomaly && !h->d_base) return fail(RSCM_ERR_STATE, "no baseline: rscm_ens_set_baseline or rscm_ens_set_baseline_values first");
+    if (int rc = no_select(h)) return rc;
+    std::vector<const double*> rows;
+    std::vector<double> times;
+    if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
+    if (int rc = set_device(h)) return rc;
+    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
+    if (int rc = run_indicators(h, rows, times, anomaly ? h->d_base : nullptr, true, n_thr, thr, h->d_ind[slot])) return rc;
+    *out_dev = h->d_ind[slot];
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted, int64_t* hits,
+                        int64_t* total)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!total || (n_thr > 0 && !hits)) return fail(RSCM_ERR_INVALID, "hits or total is NULL");
+    if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
+    if (weighted && !h->d_weights)
+        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
+    if (int rc = set_device(h)) return rc;
+    if (int rc = check_member_vector(h, vec_dev, "vector")) return rc;
+    rscm::Thresholds th{};
+    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
+    unsigned long long acc[rscm::kMaxThresholds + 1] = {};
+    unsigned long long* d_acc = nullptr;
+    const size_t bytes = (size_t)(n_thr + 1) * sizeof(unsigned long long);
+    hipError_t e = rscm::dev_malloc(&d_acc, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, bytes, h->stream);
+    if (e == hipSuccess) e = rscm::launch_exceedance(vec_dev, weighted ? h->d_weights : nullptr, h->N, n_thr, th, d_acc, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(acc, d_acc, bytes, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_acc);
+    HIPCHK(e);
+    HIPCHK(es);
+    for (int32_t k = 0; k < n_thr; ++k) hits[k] = (int64_t)acc[k];
+    *total = (int64_t)acc[n_thr];
+    return RSCM_OK;
+    GUARD_END
+}
+
+}  // extern "C"

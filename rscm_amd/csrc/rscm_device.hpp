@@ -739,9 +739,10 @@ constexpr int kSelBins = 256;
 constexpr int kSelPasses = 8;
 constexpr int kSelGroup = 16;
 int32_t select_blocks_per_row(int64_t N, int32_t n_rows);
-// zeroes d_hist[hist_elems], then adds this pass's counts of rows d_rows[n_rows][N] (device array of row pointers)
-hipError_t launch_select_hist(const double* const* d_rows, int64_t N, int32_t n_rows, int32_t pass, const uint64_t* d_prefix, int32_t n_t,
-                              int64_t* d_hist, size_t hist_elems, hipStream_t s);
+// zeroes d_hist[hist_elems], then adds this pass's counts of rows d_rows[n_rows][N] (device array of row pointers); d_base
+// non-null: of the anomalies x - d_base[i] (d_base[N] 16-byte aligned)
+hipError_t launch_select_hist(const double* const* d_rows, const double* d_base, int64_t N, int32_t n_rows, int32_t pass,
+                              const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
 // consumes the (reduced) histograms of `pass`: per (row, target) the bucket of its remaining rank; pass 0 also sets d_count[row]
 hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
                                 uint64_t* d_prefix, int64_t* d_rank, hipStream_t s);
@@ -750,8 +751,8 @@ hipError_t launch_select_finish(const int64_t* d_count, const uint64_t* d_keys, 
                                 double* d_out, hipStream_t s);
 // the weighted select (wselect.hip): the same passes over int64 member weights d_w[N] (numpy's "inverted_cdf"); one target per
 // quantile; pass 0's reduced histogram sums to W per row, stored as d_count; a row with W > 2^53 sets *d_over and gets NaN
-hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, int64_t N, int32_t n_rows, int32_t pass,
-                               const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
+hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, int64_t N, int32_t n_rows,
+                               int32_t pass, const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
 hipError_t launch_wselect_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
                                  uint64_t* d_prefix, int64_t* d_rank, int32_t* d_over, hipStream_t s);
 // d_out[r] = {W, quantile q[0], ..., q[n_q-1]}
@@ -764,6 +765,19 @@ hipError_t launch_weights_from_loglik(const double* d_ll, const uint8_t* d_statu
 // *d_flag = 1 if any d_w[i] < 0; *d_total += the sum of the weights, saturated so that it never wraps and exceeds 2^53 iff
 // the true sum does (the caller zeroes both)
 hipError_t launch_weights_check(const int64_t* d_w, int64_t N, int32_t* d_flag, unsigned long long* d_total, hipStream_t s);
+// per-member indicators (indicators.hip) over rows d_rows[n_rows][N] at times d_time[n_rows], of x or (d_base non-null) of
+// x - d_base[i]: a member with a NaN value gets NaN everywhere, else out[0][i] = sum in row order / n_rows and, with all,
+// out[1] = max, out[2] = time of the first row attaining it, out[3 + k] = time of the first row >= thr[k] (+inf: none)
+constexpr int kMaxThresholds = 8;
+struct Thresholds {
+    double v[kMaxThresholds];
+};
+hipError_t launch_indicators(const double* const* d_rows, const double* d_time, int32_t n_rows, const double* d_base, int64_t N, bool all,
+                             int32_t n_thr, const Thresholds& thr, double* d_out, hipStream_t s);
+// d_acc[k] += number (d_w non-null: summed weight) of members with v[i] >= thr[k], k < n_thr; d_acc[n_thr] += the same over the
+// non-NaN members.  int64 sums, one integer atomic per block and bin; the caller zeroes d_acc[n_thr + 1].
+hipError_t launch_exceedance(const double* d_v, const int64_t* d_w, int64_t N, int32_t n_thr, const Thresholds& thr,
+                             unsigned long long* d_acc, hipStream_t s);
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);

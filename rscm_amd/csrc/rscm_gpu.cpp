@@ -768,6 +768,8 @@ int rscm_ens_destroy(rscm_ens* h)
     (void)hipFree(h->d_obs);
     select_release(h);
     (void)hipFree(h->d_weights);
+    (void)hipFree(h->d_base);
+    for (double* p : h->d_ind) (void)hipFree(p);
     if (h->plan) {
         (void)hipFree(h->plan->d_ops);
         if (h->plan->staging) (void)hipHostFree(h->plan->staging);

@@ -17,7 +17,9 @@
 // the number of ranks or the order in which they add.  No float atomics.
 //
 // Rows reach the kernels through a device array of row pointers (the host resolves them with
-// rscm_ens::row_ptr), so full storage, the window and the strided output store all work alike.
+// rscm_ens::row_ptr), so full storage, the window and the strided output store all work alike -- and so does any device
+// vector of N doubles (rscm_ens_select_begin_vectors: indicators, parameter rows).  The histogram pass can count each
+// member's anomaly x - b[i] against the handle's baseline instead of x (rscm_ens_set_baseline).
 #include <hip/hip_runtime.h>
 
 #include "rscm_device.hpp"
@@ -49,9 +51,15 @@ __device__ __forceinline__ void lds_count(unsigned* bins, unsigned b, bool valid
 // histogram per row (all targets share the empty prefix): hist[r][256].  Later passes fill
 // hist[r][n_t][256] for the targets of the group.  Blocks of one row split its members in pair-aligned
 // chunks; each flushes its LDS counts with one integer atomic per non-zero bin.
-__global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* const* __restrict__ rows, int64_t N, int32_t pass,
-                                                                   const uint64_t* __restrict__ prefix, int32_t n_t, int32_t g0,
-                                                                   int32_t gn, unsigned long long* __restrict__ hist)
+//
+// kAnom: member i counts the key of its anomaly x - base[i] (one IEEE subtraction; a NaN anomaly is left out).  base is
+// handle-owned, hence 16-byte aligned: its pairs line up with the row's only when the row has no unpaired head member.  The
+// plain instantiation (kAnom false) never reads base.
+template <bool kAnom>
+__global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* const* __restrict__ rows, const double* __restrict__ base,
+                                                                   int64_t N, int32_t pass, const uint64_t* __restrict__ prefix,
+                                                                   int32_t n_t, int32_t g0, int32_t gn,
+                                                                   unsigned long long* __restrict__ hist)
 {
     __shared__ unsigned bins[kSelGroup * kSelBins];
     __shared__ uint64_t pre[kSelGroup];
@@ -82,17 +90,29 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* 
         for (int32_t t = 0; t < gn; ++t) lds_count(bins + t * kSelBins, d, ok && top == pre[t]);
     };
 
-    for (int64_t base = pb; base < pe; base += kSelThreads) {   // uniform trip count: whole waves call lds_count
-        const int64_t i = base + threadIdx.x;
+    for (int64_t c0 = pb; c0 < pe; c0 += kSelThreads) {   // uniform trip count: whole waves call lds_count
+        const int64_t i = c0 + threadIdx.x;
         const bool in = i < pe;
-        const double2 v = in ? row2[i] : make_double2(0.0, 0.0);
+        double2 v = in ? row2[i] : make_double2(0.0, 0.0);
+        if constexpr (kAnom) {
+            if (in) {
+                const double* bp = base + head + 2 * i;
+                const double2 b = head ? make_double2(bp[0], bp[1]) : *reinterpret_cast<const double2*>(bp);
+                v.x = v.x - b.x;
+                v.y = v.y - b.y;
+            }
+        }
         count(v.x, in);
         count(v.y, in);
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) {   // the unpaired head and tail members, one wave
         const bool in_head = head && threadIdx.x == 0;
         const bool in_tail = ((N - head) & 1) && threadIdx.x == 1;
-        const double x = in_head ? row[0] : (in_tail ? row[N - 1] : 0.0);
+        const int64_t m = in_head ? 0 : N - 1;
+        double x = (in_head || in_tail) ? row[m] : 0.0;
+        if constexpr (kAnom) {
+            if (in_head || in_tail) x = x - base[m];
+        }
         count(x, in_head || in_tail);
     }
     __syncthreads();
@@ -190,8 +210,8 @@ int32_t select_blocks_per_row(int64_t N, int32_t n_rows)
     return (int32_t)b;
 }
 
-hipError_t launch_select_hist(const double* const* d_rows, int64_t N, int32_t n_rows, int32_t pass, const uint64_t* d_prefix, int32_t n_t,
-                              int64_t* d_hist, size_t hist_elems, hipStream_t s)
+hipError_t launch_select_hist(const double* const* d_rows, const double* d_base, int64_t N, int32_t n_rows, int32_t pass,
+                              const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(d_hist, 0, hist_elems * sizeof(int64_t), s);
     if (e != hipSuccess || n_rows <= 0 || N <= 0) return e;
@@ -204,8 +224,12 @@ hipError_t launch_select_hist(const double* const* d_rows, int64_t N, int32_t n_
         const uint64_t* pre = d_prefix + (size_t)r0 * n_t;
         for (int32_t g0 = 0; g0 < (pass == 0 ? 1 : n_t); g0 += kSelGroup) {
             const int32_t gn = pass == 0 ? 1 : (n_t - g0 < kSelGroup ? n_t - g0 : kSelGroup);
-            hipLaunchKernelGGL(select_hist_kernel, dim3(bpr, (unsigned)nr), dim3(kSelThreads), 0, s, d_rows + r0, N, pass, pre, n_t, g0,
-                               gn, h);
+            if (d_base)
+                hipLaunchKernelGGL(select_hist_kernel<true>, dim3(bpr, (unsigned)nr), dim3(kSelThreads), 0, s, d_rows + r0, d_base, N, pass,
+                                   pre, n_t, g0, gn, h);
+            else
+                hipLaunchKernelGGL(select_hist_kernel<false>, dim3(bpr, (unsigned)nr), dim3(kSelThreads), 0, s, d_rows + r0, d_base, N,
+                                   pass, pre, n_t, g0, gn, h);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }

@@ -1,5 +1,7 @@
 // Host side of the staged quantile select (rscm_ens_select_* and rscm_ens_quantile_rows; kernels in select.hip), of its weighted
-// form (rscm_ens_select_begin_weighted, rscm_ens_weighted_quantile_rows; wselect.hip) and of the member weights it reads.
+// form (rscm_ens_select_begin_weighted, rscm_ens_weighted_quantile_rows; wselect.hip), of the flagged and vector forms
+// (rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex: anomalies against the handle's baseline; rscm_ens_quantile_vectors,
+// rscm_ens_select_begin_vectors: device vectors of N doubles as rows) and of the member weights it reads.
 //
 // A select resolves its rows once, at begin, into a device array of row pointers (rscm_ens::row_ptr: full storage, the window or
 // the strided output store), then alternates pass (histograms of this handle's members) and commit (the reduced histograms move
@@ -21,6 +23,7 @@ struct SelectState {
     int32_t pass = 0;       // the next pass to histogram
     bool awaiting_commit = false;
     bool weighted = false;  // rscm_ens_select_begin_weighted: count holds W, n_t == n_q
+    const double* d_base = nullptr;   // RSCM_SELECT_ANOMALY: the handle's baseline (it cannot change while the select is staged)
     const double** d_rows = nullptr;
     double* d_q = nullptr;
     int64_t* d_hist = nullptr;
@@ -56,35 +59,35 @@ namespace {
 
 constexpr int32_t kMaxSelectQuantiles = 128;
 
-int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q,
-                bool weighted = false)
+constexpr int32_t kMaxSelectVectors = 4096;
+
+// The checks every select makes first: the flags and what they need, then the quantile list (after the caller's own checks)
+int select_flags(rscm_ens* h, int32_t flags)
 {
-    if (weighted && !h->d_weights) return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
-    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
-    if (t_begin < 0 || t_end > h->T || t_begin > t_end || t_stride < 1)
-        return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d", t_begin, t_end, t_stride);
+    if (flags & ~(RSCM_SELECT_WEIGHTED | RSCM_SELECT_ANOMALY)) return fail(RSCM_ERR_INVALID, "unknown select flags 0x%x", flags);
+    if ((flags & RSCM_SELECT_WEIGHTED) && !h->d_weights)
+        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
+    if ((flags & RSCM_SELECT_ANOMALY) && !h->d_base)
+        return fail(RSCM_ERR_STATE, "no baseline: rscm_ens_set_baseline or rscm_ens_set_baseline_values first");
+    return RSCM_OK;
+}
+
+int check_quantiles(int32_t n_q, const double* q)
+{
     if (n_q < 1 || n_q > kMaxSelectQuantiles || !q) return fail(RSCM_ERR_INVALID, "bad quantile list (1 to %d quantiles)", kMaxSelectQuantiles);
     for (int32_t k = 0; k < n_q; ++k)
         if (!(q[k] >= 0.0 && q[k] <= 1.0)) return fail(RSCM_ERR_INVALID, "Quantiles must be in the range [0, 1], got %g", q[k]);
-    if (!h->windowed && h->rows != h->T && t_end > 1)
-        return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
-    s.var = var_id;
-    s.t_begin = t_begin;
-    s.t_stride = t_stride;
+    return RSCM_OK;
+}
+
+// Fills s for the computed rows `rows` (of s.n_rows) and uploads the row pointers and quantiles
+int select_setup(rscm_ens* h, SelectState& s, const std::vector<const double*>& rows, int32_t n_q, const double* q, int32_t flags)
+{
+    const bool weighted = (flags & RSCM_SELECT_WEIGHTED) != 0;
     s.n_q = n_q;
     s.n_t = weighted ? n_q : 2 * n_q;
     s.weighted = weighted;
-    std::vector<const double*> rows;
-    for (int32_t t = t_begin; t < t_end; t += t_stride) {
-        ++s.n_rows;
-        if (t > h->time_index) continue;   // never computed by this model instance
-        const double* p = h->row_ptr(var_id, t);
-        if (!p)
-            return fail(RSCM_ERR_STATE, "row %d of variable %d is not resident: the window holds [%d, %d) and the output store every %d-th row%s",
-                        t, var_id, h->win0, h->win0 + h->rows, h->out_stride,
-                        h->out_slot.empty() || h->out_slot[var_id] < 0 ? " of other variables" : "");
-        rows.push_back(p);
-    }
+    s.d_base = (flags & RSCM_SELECT_ANOMALY) ? h->d_base : nullptr;
     s.n_comp = (int32_t)rows.size();
     if (s.n_comp == 0) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
@@ -104,6 +107,42 @@ int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, in
     return RSCM_OK;
 }
 
+int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q,
+                int32_t flags)
+{
+    if (int rc = select_flags(h, flags)) return rc;
+    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
+    if (t_begin < 0 || t_end > h->T || t_begin > t_end || t_stride < 1)
+        return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d", t_begin, t_end, t_stride);
+    if (int rc = check_quantiles(n_q, q)) return rc;
+    if (!h->windowed && h->rows != h->T && t_end > 1)
+        return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
+    s.var = var_id;
+    s.t_begin = t_begin;
+    s.t_stride = t_stride;
+    std::vector<const double*> rows;
+    if (int rc = resolve_rows(h, var_id, t_begin, t_end, t_stride, rows, &s.n_rows)) return rc;
+    return select_setup(h, s, rows, n_q, q, flags);
+}
+
+// The select over n_vec device vectors of N doubles (the rows are the vectors; every one is "computed")
+int select_init_vectors(rscm_ens* h, SelectState& s, int32_t n_vec, const double* const* vec, int32_t n_q, const double* q, int32_t flags)
+{
+    if (flags & RSCM_SELECT_ANOMALY) return fail(RSCM_ERR_INVALID, "RSCM_SELECT_ANOMALY applies to stored rows, not to vectors");
+    if (int rc = select_flags(h, flags)) return rc;
+    if (n_vec < 1 || n_vec > kMaxSelectVectors || !vec) return fail(RSCM_ERR_INVALID, "bad vector list (1 to %d vectors)", kMaxSelectVectors);
+    if (int rc = check_quantiles(n_q, q)) return rc;
+    if (int rc = set_device(h)) return rc;
+    std::vector<const double*> rows(vec, vec + n_vec);
+    for (int32_t k = 0; k < n_vec; ++k) {
+        char what[32];
+        std::snprintf(what, sizeof what, "vector %d", k);
+        if (int rc = check_member_vector(h, rows[k], what)) return rc;
+    }
+    s.n_rows = n_vec;
+    return select_setup(h, s, rows, n_q, q, flags);
+}
+
 int select_pass(rscm_ens* h, SelectState& s, int32_t* done, int64_t** buf_dev, int64_t* n)
 {
     if (s.awaiting_commit) return fail(RSCM_ERR_STATE, "select: commit the previous pass first");
@@ -116,9 +155,10 @@ int select_pass(rscm_ens* h, SelectState& s, int32_t* done, int64_t** buf_dev, i
     if (int rc = set_device(h)) return rc;
     const size_t elems = (size_t)s.n_comp * rscm::kSelBins * (s.pass == 0 ? 1 : (size_t)s.n_t);
     if (s.weighted)
-        HIPCHK(rscm::launch_wselect_hist(s.d_rows, h->d_weights, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
+        HIPCHK(rscm::launch_wselect_hist(s.d_rows, h->d_weights, s.d_base, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems,
+                                         h->stream));
     else
-        HIPCHK(rscm::launch_select_hist(s.d_rows, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
+        HIPCHK(rscm::launch_select_hist(s.d_rows, s.d_base, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     s.awaiting_commit = true;
     *done = 0;
@@ -172,11 +212,15 @@ int select_result(rscm_ens* h, SelectState& s, double* out, double* count)
     return RSCM_OK;
 }
 
-int select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q, bool weighted)
+// vec == nullptr: the rows of var_id; else the n_vec vectors (var_id .. t_stride unused)
+int select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q, int32_t flags,
+                 int32_t n_vec = 0, const double* const* vec = nullptr)
 {
     if (h->select) return fail(RSCM_ERR_STATE, "a select is already in flight on this handle: rscm_ens_select_end it first");
     auto* s = new SelectState();
-    if (int rc = select_init(h, *s, var_id, t_begin, t_end, t_stride, n_q, q, weighted)) {
+    const int rc = vec || n_vec ? select_init_vectors(h, *s, n_vec, vec, n_q, q, flags)
+                                : select_init(h, *s, var_id, t_begin, t_end, t_stride, n_q, q, flags);
+    if (rc) {
         s->release();
         delete s;
         return rc;
@@ -186,11 +230,12 @@ int select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, in
 }
 
 int quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q, double* out,
-                  double* count, bool weighted)
+                  double* count, int32_t flags, int32_t n_vec = 0, const double* const* vec = nullptr)
 {
     if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
     SelectState s;   // its own state: a staged select in flight on the handle is left alone
-    int rc = select_init(h, s, var_id, t_begin, t_end, t_stride, n_q, q, weighted);
+    int rc = vec || n_vec ? select_init_vectors(h, s, n_vec, vec, n_q, q, flags)
+                          : select_init(h, s, var_id, t_begin, t_end, t_stride, n_q, q, flags);
     int32_t done = 0;
     while (rc == RSCM_OK) {
         if ((rc = select_pass(h, s, &done, nullptr, nullptr)) != RSCM_OK || done) break;
@@ -207,6 +252,42 @@ int quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, i
 
 }  // namespace
 
+int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
+                 int32_t* n_range)
+{
+    *n_range = 0;
+    for (int32_t t = t_begin; t < t_end; t += t_stride) {
+        ++*n_range;
+        if (t > h->time_index) continue;   // never computed by this model instance
+        const double* p = h->row_ptr(var_id, t);
+        if (!p)
+            return fail(RSCM_ERR_STATE, "row %d of variable %d is not resident: the window holds [%d, %d) and the output store every %d-th row%s",
+                        t, var_id, h->win0, h->win0 + h->rows, h->out_stride,
+                        h->out_slot.empty() || h->out_slot[var_id] < 0 ? " of other variables" : "");
+        rows.push_back(p);
+    }
+    return RSCM_OK;
+}
+
+int check_member_vector(const rscm_ens* h, const double* p, const char* what)
+{
+    if (!p) return fail(RSCM_ERR_INVALID, "%s is NULL", what);
+    if ((uintptr_t)p & 7) return fail(RSCM_ERR_INVALID, "%s is not 8-byte aligned", what);
+    hipPointerAttribute_t a{};
+    if (hipPointerGetAttributes(&a, p) != hipSuccess || a.type != hipMemoryTypeDevice || a.device != h->device) {
+        (void)hipGetLastError();
+        return fail(RSCM_ERR_INVALID, "%s is not device memory on device %d", what, h->device);
+    }
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) != hipSuccess ||
+        (const char*)p + (size_t)h->N * sizeof(double) > (const char*)base + size) {
+        (void)hipGetLastError();
+        return fail(RSCM_ERR_INVALID, "%s does not hold %lld doubles", what, (long long)h->N);
+    }
+    return RSCM_OK;
+}
+
 void select_release(rscm_ens* h)
 {
     if (!h->select) return;
@@ -221,7 +302,7 @@ int rscm_ens_select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t 
 {
     GUARD_BEGIN
     NEED(h);
-    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, false);
+    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, 0);
     GUARD_END
 }
 
@@ -229,7 +310,25 @@ int rscm_ens_select_begin_weighted(rscm_ens* h, int32_t var_id, int32_t t_begin,
 {
     GUARD_BEGIN
     NEED(h);
-    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, true);
+    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, RSCM_SELECT_WEIGHTED);
+    GUARD_END
+}
+
+int rscm_ens_select_begin_ex(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q,
+                             int32_t flags)
+{
+    GUARD_BEGIN
+    NEED(h);
+    return select_begin(h, var_id, t_begin, t_end, t_stride, n_q, q, flags);
+    GUARD_END
+}
+
+int rscm_ens_select_begin_vectors(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t n_q, const double* q, int32_t flags)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!vec_dev || n_vec < 1) return fail(RSCM_ERR_INVALID, "bad vector list (1 to %d vectors)", kMaxSelectVectors);
+    return select_begin(h, 0, 0, 0, 1, n_q, q, flags, n_vec, vec_dev);
     GUARD_END
 }
 
@@ -279,7 +378,7 @@ int rscm_ens_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t
 {
     GUARD_BEGIN
     NEED(h);
-    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, count, false);
+    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, count, 0);
     GUARD_END
 }
 
@@ -288,7 +387,26 @@ int rscm_ens_weighted_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin
 {
     GUARD_BEGIN
     NEED(h);
-    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, weight, true);
+    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, weight, RSCM_SELECT_WEIGHTED);
+    GUARD_END
+}
+
+int rscm_ens_quantile_rows_ex(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_q, const double* q,
+                              int32_t flags, double* out, double* count)
+{
+    GUARD_BEGIN
+    NEED(h);
+    return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, count, flags);
+    GUARD_END
+}
+
+int rscm_ens_quantile_vectors(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t n_q, const double* q, int32_t flags,
+                              double* out, double* count)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!vec_dev || n_vec < 1) return fail(RSCM_ERR_INVALID, "bad vector list (1 to %d vectors)", kMaxSelectVectors);
+    return quantile_rows(h, 0, 0, 0, 1, n_q, q, out, count, flags, n_vec, vec_dev);
     GUARD_END
 }
 

@@ -49,10 +49,12 @@ __device__ __forceinline__ void lds_wadd(unsigned long long* bins, unsigned b, u
 
 // select_hist_kernel (select.hip) with member i adding w[i]: the same row split, pair loads, head and tail.  The 64-bit LDS
 // bins are dynamic shared memory, nh x kSelBins x 8 B: 2 KiB in pass 0, at most kSelGroup x 2 KiB = 32 KiB later.
+// kAnom: the key of x - base[i], as select_hist_kernel<true> (base handle-owned, 16-byte aligned like w).
+template <bool kAnom>
 __global__ __launch_bounds__(kWSelThreads) void wselect_hist_kernel(const double* const* __restrict__ rows, const int64_t* __restrict__ w,
-                                                                     int64_t N, int32_t pass, const uint64_t* __restrict__ prefix,
-                                                                     int32_t n_t, int32_t g0, int32_t gn,
-                                                                     unsigned long long* __restrict__ hist)
+                                                                     const double* __restrict__ base, int64_t N, int32_t pass,
+                                                                     const uint64_t* __restrict__ prefix, int32_t n_t, int32_t g0,
+                                                                     int32_t gn, unsigned long long* __restrict__ hist)
 {
     extern __shared__ unsigned long long wbins[];
     __shared__ uint64_t pre[kSelGroup];
@@ -83,13 +85,19 @@ __global__ __launch_bounds__(kWSelThreads) void wselect_hist_kernel(const double
         for (int32_t t = 0; t < gn; ++t) lds_wadd(wbins + t * kSelBins, d, wt, ok && top == pre[t]);
     };
 
-    for (int64_t base = pb; base < pe; base += kWSelThreads) {   // uniform trip count: whole waves call lds_wadd
-        const int64_t i = base + threadIdx.x;
+    for (int64_t c0 = pb; c0 < pe; c0 += kWSelThreads) {   // uniform trip count: whole waves call lds_wadd
+        const int64_t i = c0 + threadIdx.x;
         const bool in = i < pe;
         double2 v = make_double2(0.0, 0.0);
         unsigned long long w0 = 0ull, w1 = 0ull;
         if (in) {
             v = row2[i];
+            if constexpr (kAnom) {
+                const double* bp = base + head + 2 * i;
+                const double2 b = head ? make_double2(bp[0], bp[1]) : *reinterpret_cast<const double2*>(bp);
+                v.x = v.x - b.x;
+                v.y = v.y - b.y;
+            }
             if (head) {
                 w0 = (unsigned long long)wp[2 * i];
                 w1 = (unsigned long long)wp[2 * i + 1];
@@ -106,7 +114,10 @@ __global__ __launch_bounds__(kWSelThreads) void wselect_hist_kernel(const double
         const bool in_head = head && threadIdx.x == 0;
         const bool in_tail = ((N - head) & 1) && threadIdx.x == 1;
         const int64_t m = in_head ? 0 : N - 1;
-        const double x = (in_head || in_tail) ? row[m] : 0.0;
+        double x = (in_head || in_tail) ? row[m] : 0.0;
+        if constexpr (kAnom) {
+            if (in_head || in_tail) x = x - base[m];
+        }
         const unsigned long long wt = (in_head || in_tail) ? (unsigned long long)w[m] : 0ull;
         count(x, wt, in_head || in_tail);
     }
@@ -260,8 +271,8 @@ unsigned grid_of(int64_t n) { return (unsigned)((n + kWSelThreads - 1) / kWSelTh
 
 }  // namespace
 
-hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, int64_t N, int32_t n_rows, int32_t pass,
-                               const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s)
+hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, int64_t N, int32_t n_rows,
+                               int32_t pass, const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(d_hist, 0, hist_elems * sizeof(int64_t), s);
     if (e != hipSuccess || n_rows <= 0 || N <= 0) return e;
@@ -275,8 +286,12 @@ hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, 
         for (int32_t g0 = 0; g0 < (pass == 0 ? 1 : n_t); g0 += kSelGroup) {
             const int32_t gn = pass == 0 ? 1 : (n_t - g0 < kSelGroup ? n_t - g0 : kSelGroup);
             const size_t lds = (size_t)gn * kSelBins * sizeof(unsigned long long);
-            hipLaunchKernelGGL(wselect_hist_kernel, dim3(bpr, (unsigned)nr), dim3(kWSelThreads), lds, s, d_rows + r0, d_w, N, pass, pre,
-                               n_t, g0, gn, h);
+            if (d_base)
+                hipLaunchKernelGGL(wselect_hist_kernel<true>, dim3(bpr, (unsigned)nr), dim3(kWSelThreads), lds, s, d_rows + r0, d_w, d_base, N,
+                                   pass, pre, n_t, g0, gn, h);
+            else
+                hipLaunchKernelGGL(wselect_hist_kernel<false>, dim3(bpr, (unsigned)nr), dim3(kWSelThreads), lds, s, d_rows + r0, d_w, d_base,
+                                   N, pass, pre, n_t, g0, gn, h);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }

@@ -13,7 +13,11 @@ in the CPU tests), are:
 * ``quantile_rows_global``: eight all-reduces (int64 SUM) of radix-select histograms -- a few
   hundred counts per row and quantile, however many members there are (weight sums instead of
   counts for the likelihood-weighted quantiles);
-* ``ShardedEnsemble.constrain``: one all-reduce (MAX) of the local log-likelihood maxima.
+* ``ShardedEnsemble.constrain``: one all-reduce (MAX) of the local log-likelihood maxima;
+* ``quantile_vectors_global``: the same histogram all-reduces over per-member vectors (indicators, parameter rows);
+* ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums.
+
+Baselines and per-member indicators (``Ensemble.set_baseline``, ``Ensemble.indicators``) are per member and need none.
 
 Full time series are never gathered: 12 GB into one GPU's seven xGMI links would serialise on
 rank 0 for no benefit; each rank copies its own shard to the host if asked.
@@ -132,28 +136,12 @@ def reduce_summary(local: Dict[str, float], group=None) -> Dict[str, float]:
             "min": float(mn.item()), "max": float(mx.item())}
 
 
-def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                         group=None, weighted: bool = False) -> Dict[str, np.ndarray]:
-    """Quantiles of the WHOLE sharded ensemble (``Ensemble.quantile_rows`` of all ranks' members together), on every rank.
-
-    Each rank runs the staged radix select on its own shard (``Ensemble.select``); between the passes the ranks sum their
-    int64 histograms -- the only collective, exact and independent of order, so the result has the same bits at any number
-    of ranks and equals the single-process ``quantile_rows`` of the gathered ensemble.  With ``nccl`` the library's buffer is
-    reduced in place through ``__cuda_array_interface__``; with ``gloo`` it goes through the host.  Every rank must pass the
-    same ``q`` and rows and stand at the same time index.  Single process: ``ensemble.quantile_rows``.
-
-    ``weighted``: the likelihood-weighted quantiles (``Ensemble.quantile_rows(..., weighted=True)``) of the whole ensemble,
-    the ranks' member weights on one scale (``ShardedEnsemble.constrain``); the histograms then hold int64 weight sums and
-    the result has ``"weight"`` in place of ``"count"``."""
-    if not is_distributed():
-        if weighted:
-            return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride, weighted=True)
-        return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride)
+def _reduce_select(sel, group=None) -> Dict[str, np.ndarray]:
+    """Runs a staged select (``QuantileSelect`` or a stand-in) to its result, SUM-all-reducing each pass's int64 buffer."""
     import torch
     from .ensemble import DeviceVector
     d = _dist()
     dev = _device_for_backend()
-    sel = ensemble.select(var, q, t_begin, t_end, t_stride, weighted=True) if weighted else ensemble.select(var, q, t_begin, t_end, t_stride)
     with sel as s:
         while True:
             buf = s.next_pass()
@@ -170,6 +158,54 @@ def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int
                 d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
                 s.commit(t.cpu().numpy())
         return s.result()
+
+
+def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+                         group=None, weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
+    """Quantiles of the WHOLE sharded ensemble (``Ensemble.quantile_rows`` of all ranks' members together), on every rank.
+
+    Each rank runs the staged radix select on its own shard (``Ensemble.select``); between the passes the ranks sum their
+    int64 histograms -- the only collective, exact and independent of order, so the result has the same bits at any number
+    of ranks and equals the single-process ``quantile_rows`` of the gathered ensemble.  With ``nccl`` the library's buffer is
+    reduced in place through ``__cuda_array_interface__``; with ``gloo`` it goes through the host.  Every rank must pass the
+    same ``q`` and rows and stand at the same time index.  Single process: ``ensemble.quantile_rows``.
+
+    ``weighted``: the likelihood-weighted quantiles (``Ensemble.quantile_rows(..., weighted=True)``) of the whole ensemble,
+    the ranks' member weights on one scale (``ShardedEnsemble.constrain``); the histograms then hold int64 weight sums and
+    the result has ``"weight"`` in place of ``"count"``.
+
+    ``anomaly``: of each member's anomaly against its baseline (every rank's ``Ensemble.set_baseline`` over the same rows)."""
+    kw = {}
+    if weighted:
+        kw["weighted"] = True
+    if anomaly:
+        kw["anomaly"] = True
+    if not is_distributed():
+        return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride, **kw)
+    return _reduce_select(ensemble.select(var, q, t_begin, t_end, t_stride, **kw), group)
+
+
+def quantile_vectors_global(ensemble, vectors, q, group=None, weighted: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.quantile_vectors`` of the WHOLE sharded ensemble on every rank: each rank passes its shard of each vector
+    (its members' indicators, parameter rows ...) in the same order; the histograms are summed as in ``quantile_rows_global``."""
+    if not is_distributed():
+        return ensemble.quantile_vectors(vectors, q, weighted=weighted)
+    return _reduce_select(ensemble.select_vectors(vectors, q, weighted=weighted), group)
+
+
+def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool = False) -> Dict[str, object]:
+    """``Ensemble.exceedance`` of the WHOLE sharded ensemble on every rank: the ranks' int64 hits and totals are SUM-reduced
+    (exact and independent of order), then ``probability = hits / total``."""
+    from .ensemble import exceedance_result
+    local = ensemble.exceedance(vector, thresholds, weighted=weighted)
+    if not is_distributed():
+        return local
+    import torch
+    d = _dist()
+    t = torch.from_numpy(np.append(np.asarray(local["hits"], dtype=np.int64), np.int64(local["total"]))).to(_device_for_backend())
+    d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+    acc = t.cpu().numpy()
+    return exceedance_result(acc[:-1], int(acc[-1]))
 
 
 class ShardedEnsemble:
@@ -215,10 +251,18 @@ class ShardedEnsemble:
         return reduce_summary(self.ensemble.summary(var, tidx))
 
     def quantile_rows_global(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                             weighted: bool = False) -> Dict[str, np.ndarray]:
+                             weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
         """Quantiles of the global ensemble at the rows ``t_begin, t_begin + t_stride, ... < t_end`` (``quantile_rows_global``);
-        ``weighted``: with the member weights ``constrain`` set."""
-        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride, weighted=weighted)
+        ``weighted``: with the member weights ``constrain`` set; ``anomaly``: of the anomalies against the members' baselines."""
+        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly)
+
+    def quantile_vectors_global(self, vectors, q, weighted: bool = False) -> Dict[str, np.ndarray]:
+        """Quantiles of per-member vectors of the global ensemble (``quantile_vectors_global``)."""
+        return quantile_vectors_global(self.ensemble, vectors, q, weighted=weighted)
+
+    def exceedance_global(self, vector, thresholds, weighted: bool = False) -> Dict[str, object]:
+        """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""
+        return exceedance_global(self.ensemble, vector, thresholds, weighted=weighted)
 
     def constrain(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, bits: Optional[int] = None):
         """Weight this rank's members by their fit to observations, on one scale across all ranks: the Gaussian

@@ -401,28 +401,125 @@ class Ensemble:
         return {"count": cnt.astype(np.int64), "quantiles": out}
 
     def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                      weighted: bool = False) -> Dict[str, np.ndarray]:
+                      weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
         """``quantile_series``'s numbers (the same bits) over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any
         storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows: a radix
         select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``.
 
         ``weighted``: ``numpy.nanquantile(row, q, weights=w, method="inverted_cdf")`` with the member weights
         (``set_member_weights`` / ``set_weights_from_loglik``; rscm_ens_weighted_quantile_rows).  Returns
-        ``{"weight": [rows] (summed weight of the non-NaN members), "quantiles": [rows][len(q)]}``."""
+        ``{"weight": [rows] (summed weight of the non-NaN members), "quantiles": [rows][len(q)]}``.
+
+        ``anomaly``: the same quantiles of each member's own anomaly ``x[i] - b[i]`` against the baseline (``set_baseline``;
+        rscm_ens_quantile_rows_ex) -- not the plume minus a quantile of the baseline."""
         qq = np.atleast_1d(L.f64(q))
         t_end = self.n_times if t_end is None else t_end
         rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
         out, cnt = np.empty((rows, qq.size)), np.empty(rows)
-        fn = self._lib.rscm_ens_weighted_quantile_rows if weighted else self._lib.rscm_ens_quantile_rows
-        L.check(fn(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), L.dptr(out), L.dptr(cnt)))
+        if anomaly:
+            flags = L.SELECT_ANOMALY | (L.SELECT_WEIGHTED if weighted else 0)
+            L.check(self._lib.rscm_ens_quantile_rows_ex(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), flags,
+                                                        L.dptr(out), L.dptr(cnt)))
+        else:
+            fn = self._lib.rscm_ens_weighted_quantile_rows if weighted else self._lib.rscm_ens_quantile_rows
+            L.check(fn(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), L.dptr(out), L.dptr(cnt)))
         return {"weight" if weighted else "count": cnt.astype(np.int64), "quantiles": out}
 
     def select(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-               weighted: bool = False) -> "QuantileSelect":
+               weighted: bool = False, anomaly: bool = False) -> "QuantileSelect":
         """``quantile_rows`` in stages, for a caller that sums the histograms of several handles between the passes (the
         shards of one ensemble: ``rscm_amd.distributed.quantile_rows_global``).  Use as a context manager.  ``weighted``: the
-        weighted select; ``result()`` then returns ``{"weight", "quantiles"}``."""
-        return QuantileSelect(self, var, q, t_begin, t_end, t_stride, weighted)
+        weighted select; ``result()`` then returns ``{"weight", "quantiles"}``.  ``anomaly``: of the anomalies against the
+        baseline."""
+        return QuantileSelect(self, var, q, t_begin, t_end, t_stride, weighted, anomaly)
+
+    # -- baseline, per-member indicators, exceedance ------------------------------------------
+    def set_baseline(self, var, t_begin: int, t_end: int, t_stride: int = 1) -> None:
+        """The baseline ``b[i]``: member i's mean of ``var`` over the rows ``t_begin, t_begin + t_stride, ... < t_end`` (the sum
+        in row order divided by the row count; NaN if any of its rows is), computed on the device and kept by the handle
+        across ``run`` and ``rewind``.  ``quantile_rows(..., anomaly=True)`` and ``indicators(..., anomaly=True)`` read it."""
+        L.check(self._lib.rscm_ens_set_baseline(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride)))
+
+    def set_baseline_values(self, b) -> None:
+        """The baseline from ``[N]`` float64 values: a numpy array or a ``DeviceVector`` on this ensemble's GPU."""
+        if isinstance(b, DeviceVector):
+            if b.n != self.n_members or b.dtype != np.float64:
+                raise ValueError(f"baseline: need a float64 device vector of {self.n_members} members")
+            L.check(self._lib.rscm_ens_set_baseline_values(self._h, C.cast(C.c_void_p(b.ptr), C.POINTER(C.c_double)), 1))
+            return
+        a = np.ascontiguousarray(b, dtype=np.float64)
+        if a.shape != (self.n_members,):
+            raise ValueError(f"baseline: need {self.n_members} values, got shape {a.shape}")
+        L.check(self._lib.rscm_ens_set_baseline_values(self._h, L.dptr(a), 0))
+
+    def baseline_device(self) -> DeviceVector:
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_baseline_devptr(self._h, C.byref(p)))
+        return DeviceVector(p.value, self.n_members, np.float64, self)
+
+    def baseline(self) -> np.ndarray:
+        """The baseline, ``[N]`` float64, copied to the host."""
+        return self.baseline_device().to_host()
+
+    def clear_baseline(self) -> None:
+        L.check(self._lib.rscm_ens_clear_baseline(self._h))
+
+    def indicators(self, var, t_begin: int, t_end: int, t_stride: int = 1, thresholds=(), anomaly: bool = False,
+                   slot: int = 0) -> Dict[str, object]:
+        """Per-member indicators of ``var`` over the rows ``t_begin, t_begin + t_stride, ... < t_end`` (of the anomaly against
+        the baseline with ``anomaly``), left on the device in indicator slot ``slot`` (0-3; each slot's vectors stay valid
+        until its next use): ``{"mean", "peak", "peak_time", "crossing": [one per threshold]}``, ``DeviceVector``s of ``[N]``
+        float64.  ``peak_time`` is the time of the first row attaining the peak; ``crossing[k]`` that of the first row
+        ``>= thresholds[k]`` (``inf`` if none).  A member with a NaN in any row has NaN in every indicator."""
+        thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_member_indicators(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride), int(bool(anomaly)),
+                                                     thr.size, L.dptr(thr), int(slot), C.byref(p)))
+        n, base = self.n_members, p.value
+        vec = [DeviceVector(base + 8 * n * j, n, np.float64, self) for j in range(3 + thr.size)]
+        return {"mean": vec[0], "peak": vec[1], "peak_time": vec[2], "crossing": vec[3:]}
+
+    def _vectors(self, vectors):
+        vs = list(vectors)
+        for v in vs:
+            if not isinstance(v, DeviceVector) or v.n != self.n_members or v.dtype != np.float64:
+                raise ValueError(f"vectors: need float64 DeviceVectors of {self.n_members} members")
+        arr = (C.POINTER(C.c_double) * len(vs))(*[C.cast(C.c_void_p(v.ptr), C.POINTER(C.c_double)) for v in vs])
+        return arr, len(vs)
+
+    def quantile_vectors(self, vectors, q, weighted: bool = False) -> Dict[str, np.ndarray]:
+        """``quantile_rows``' quantiles with device vectors of ``[N]`` float64 as the rows: indicators, parameter rows
+        (``params_vector``), a log-likelihood.  Returns ``{"count" | "weight": [len(vectors)], "quantiles": [len(vectors)][len(q)]}``."""
+        arr, n_vec = self._vectors(vectors)
+        qq = np.atleast_1d(L.f64(q))
+        out, cnt = np.empty((n_vec, qq.size)), np.empty(n_vec)
+        L.check(self._lib.rscm_ens_quantile_vectors(self._h, n_vec, arr, qq.size, L.dptr(qq), L.SELECT_WEIGHTED if weighted else 0,
+                                                    L.dptr(out), L.dptr(cnt)))
+        return {"weight" if weighted else "count": cnt.astype(np.int64), "quantiles": out}
+
+    def select_vectors(self, vectors, q, weighted: bool = False) -> "QuantileSelect":
+        """``quantile_vectors`` in stages (``select``'s protocol): ``rscm_amd.distributed.quantile_vectors_global``."""
+        return QuantileSelect(self, None, q, 0, None, 1, weighted, vectors=vectors)
+
+    def exceedance(self, vector, thresholds, weighted: bool = False) -> Dict[str, object]:
+        """Exceedance of a ``[N]`` float64 ``DeviceVector``: ``{"hits": [k] int64 (members, or with ``weighted`` their summed
+        weight, with ``v >= thresholds[k]``), "total": int64 (non-NaN members or their weight), "probability": hits / total}``
+        (NaN where total is 0).  Integer sums, so those of shards add up to the whole ensemble's."""
+        (arr, _n) = self._vectors([vector])
+        thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        hits, total = np.zeros(thr.size, dtype=np.int64), C.c_int64(0)
+        L.check(self._lib.rscm_ens_exceedance(self._h, arr[0], thr.size, L.dptr(thr), int(bool(weighted)),
+                                              hits.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total)))
+        return exceedance_result(hits, total.value)
+
+    def params_vector(self, row: int) -> DeviceVector:
+        """Parameter row ``row`` of the ``[P][N]`` block as a ``DeviceVector`` (rscm_ens_params_devptr), e.g. for
+        ``quantile_vectors``.  Once handed out, the block is read per member for the handle's life."""
+        if not (0 <= row < self.n_params):
+            raise ValueError(f"parameter row {row} out of range")
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_params_devptr(self._h, C.byref(p)))
+        return DeviceVector(p.value + 8 * self.n_members * row, self.n_members, np.float64, self)
 
     # -- member weights (the weighted quantiles) ---------------------------------------------
     def set_member_weights(self, w) -> None:
@@ -488,6 +585,14 @@ class Ensemble:
         return float(w.sum()) ** 2 / s2 if s2 > 0 else 0.0
 
 
+def exceedance_result(hits, total: int) -> Dict[str, object]:
+    """``{"hits", "total", "probability"}`` from int64 sums; the probability is ``hits / total`` in float64, NaN when total is 0."""
+    hits = np.asarray(hits, dtype=np.int64)
+    total = int(total)
+    prob = hits.astype(np.float64) / float(total) if total else np.full(hits.shape, np.nan)
+    return {"hits": hits, "total": total, "probability": prob}
+
+
 def default_weight_bits(n_total: int) -> int:
     """The quantisation depth that keeps ``n_total`` weights of at most ``2**bits`` summing to at most 2^53."""
     n = int(n_total)
@@ -506,14 +611,24 @@ class QuantileSelect:
             res = s.result()
     """
 
-    def __init__(self, ens: Ensemble, var, q, t_begin: int, t_end: Optional[int], t_stride: int, weighted: bool = False):
+    def __init__(self, ens: Ensemble, var, q, t_begin: int, t_end: Optional[int], t_stride: int, weighted: bool = False,
+                 anomaly: bool = False, vectors=None):
         self.ens = ens
         self.q = np.atleast_1d(L.f64(q))
         self.weighted = bool(weighted)
-        t_end = ens.n_times if t_end is None else t_end
-        self.rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
-        begin = ens._lib.rscm_ens_select_begin_weighted if weighted else ens._lib.rscm_ens_select_begin
-        L.check(begin(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q)))
+        flags = L.SELECT_WEIGHTED if weighted else 0
+        if vectors is not None:                      # rscm_ens_select_begin_vectors: the vectors are the rows
+            arr, self.rows = ens._vectors(vectors)
+            L.check(ens._lib.rscm_ens_select_begin_vectors(ens._h, self.rows, arr, self.q.size, L.dptr(self.q), flags))
+        else:
+            t_end = ens.n_times if t_end is None else t_end
+            self.rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
+            if anomaly:
+                L.check(ens._lib.rscm_ens_select_begin_ex(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q),
+                                                          flags | L.SELECT_ANOMALY))
+            else:
+                begin = ens._lib.rscm_ens_select_begin_weighted if weighted else ens._lib.rscm_ens_select_begin
+                L.check(begin(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q)))
         self._open = True
         self._buf = None
 
