@@ -65,6 +65,12 @@ RSCM_API int rscm_gpu_set_udeb_variant(int32_t variant);
  * the parity tests); 1 the two-stream cut where it applies whatever the environment says.  The same bits either way. */
 RSCM_API int rscm_gpu_set_run_plan(int32_t mode);
 
+/* Which test decides whether a speculative year of the calling THREAD's EXACT two-layer launches (whole-axis, likelihood-only and
+ * fused group launches) is replayed with IEEE division (csrc/two_layer_body.hpp): 0 (default) the sub-step states where every member
+ * of a wavefront has its parameters in the boxes of csrc/two_layer_box.hpp, the numerators elsewhere; 1 every numerator, always
+ * (the guard before the state boxes: the yardstick of tests/test_gpu_two_layer_guard.py).  The same bits either way. */
+RSCM_API int rscm_gpu_set_two_layer_guard(int32_t numerators);
+
 /* 1 if this library was built with -DRSCM_EXPERIMENTS (`make -C rscm_amd/csrc EXPERIMENTS=1`): the environment-variable experiment
  * knobs of csrc/experiment_env.hpp (RSCM_SPLIT_CHUNK / _CHUNK2 / _FIRST, RSCM_LOCKSTEP_SPLIT, RSCM_UDEB_VARIANT) are compiled in.
  * 0 for the shipped library, whose launch plans read only the two variables documented in rscm_gpu.h ("Environment").

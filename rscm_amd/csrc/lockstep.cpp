@@ -59,6 +59,13 @@ int rscm_gpu_set_run_plan(int32_t mode)
     return RSCM_OK;
 }
 
+int rscm_gpu_set_two_layer_guard(int32_t numerators)
+{
+    if (numerators != 0 && numerators != 1) return fail(RSCM_ERR_INVALID, "two-layer guard %d (0 default, 1 every numerator)", numerators);
+    set_two_layer_guard(numerators);
+    return RSCM_OK;
+}
+
 int rscm_gpu_derive_launches(int64_t* out)
 {
     const int64_t n = take_derive_launches();

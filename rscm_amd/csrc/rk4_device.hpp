@@ -46,6 +46,16 @@ __device__ __forceinline__ int32_t window_tag(double x)
     return t;
 }
 
+// (|x| >> 31 bits) - edge: one v_lshl_add_u32 with the edge's negation in an SGPR (VOP3 takes no literal).  With
+// edge = (1023 + lo) << 21 and span = (hi - lo) << 21 the result is below span exactly for 2^lo <= |x| < 2^hi (the sign is
+// shifted out; zeros, denormals, inf and NaN are outside any box with -1022 <= lo < hi <= 1024).
+__device__ __forceinline__ uint32_t box_tag(double x, uint32_t neg_edge)
+{
+    uint32_t t;
+    asm("v_lshl_add_u32 %0, %1, 1, %2" : "=v"(t) : "v"(__double2hiint(x)), "s"(neg_edge));
+    return t;
+}
+
 __device__ __forceinline__ bool divisor_in_window(double d)
 {
     const uint32_t ed = ((uint32_t)__double2hiint(d) >> 20) & 0x7FFu;
@@ -163,6 +173,11 @@ __device__ __forceinline__ double log_f64(double x)
 __device__ __forceinline__ int32_t max3_i32(int32_t a, int32_t b, int32_t c)
 {
     return max(max(a, b), c);  // v_max3_i32
+}
+
+__device__ __forceinline__ uint32_t max3_u32(uint32_t a, uint32_t b, uint32_t c)
+{
+    return max(max(a, b), c);  // v_max3_u32
 }
 
 __device__ __forceinline__ bool is_finite(double x)

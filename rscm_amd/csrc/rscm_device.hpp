@@ -346,6 +346,8 @@ struct TwoLayerArgs {
     int32_t n_obs;
     int32_t normalize;
     int32_t first_is_deep;        // which variable's group comes first in the caller's order
+    int32_t numerator_guard;      // EXACT: 1 forces the per-numerator guard of every speculative year (test hook,
+                                  // rscm_gpu_set_two_layer_guard); 0 guards the sub-step states where the boxes allow it
     const int32_t* obs_tidx;      // [n_obs] ascending
     const int32_t* obs_is_deep;   // [n_obs] 0: Surface Temperature, 1: Deep Ocean Temperature
     const double* obs_value;

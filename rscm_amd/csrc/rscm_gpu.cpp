@@ -1353,6 +1353,9 @@ int step_links(rscm_ens* h, int32_t step_begin, int32_t step_end, rscm::InputLin
 // -1 by the environment and the sizes (default), 0 always one plain launch, 1 the two-stream cut where it applies.
 static thread_local int32_t t_run_plan = -1;
 void set_run_plan(int32_t mode) { t_run_plan = mode; }
+// Test hook (rscm_gpu_set_two_layer_guard): 1 makes the calling thread's EXACT two-layer launches guard every numerator.
+static thread_local int32_t t_tl_numerator_guard = 0;
+void set_two_layer_guard(int32_t numerators) { t_tl_numerator_guard = numerators; }
 
 struct MemberSplit {
     bool on = false;
@@ -1464,6 +1467,7 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
         a.h = h->h_tl;
         a.h_half = h->h_tl / 2.0;
         a.h_sixth = h->h_tl / 6.0;
+        a.numerator_guard = t_tl_numerator_guard;
         a.ts = h->series(RSCM_TL_VAR_TS);
         a.td = h->series(RSCM_TL_VAR_TD);
         a.status = h->d_status;
@@ -2198,6 +2202,7 @@ hipError_t launch_loglik(rscm_ens* h)
     a.h = h->h_tl;
     a.h_half = h->h_tl / 2.0;
     a.h_sixth = h->h_tl / 6.0;
+    a.numerator_guard = t_tl_numerator_guard;
     a.ts = h->series(RSCM_TL_VAR_TS);
     a.td = h->series(RSCM_TL_VAR_TD);
     a.status = h->d_status;

@@ -3,8 +3,11 @@
 // replaces in the reference and why it is written this way.
 #pragma once
 
+#include <type_traits>
+
 #include "rk4_device.hpp"
 #include "rscm_device.hpp"
+#include "two_layer_box.hpp"
 
 namespace rscm {
 namespace tl {
@@ -19,7 +22,8 @@ struct TLConst {
 //   heat_exchange_surface = efficacy*eta*temperature_difference      ((efficacy*eta) first)
 //   dts = (erf - lambda_eff*ts - heat_exchange_surface) / heat_capacity_surface
 //   dtd = (eta*temperature_difference) / heat_capacity_deep
-template <bool SPEC>
+// SPEC: the three-instruction quotients; TAGS: with one window tag per numerator (the per-numerator guard).
+template <bool SPEC, bool TAGS = SPEC>
 __device__ __forceinline__ void rhs_exact(const TLConst& p, double erf, double ts, double td,
                                           double& dts, double& dtd, int32_t& acc)
 {
@@ -31,23 +35,23 @@ __device__ __forceinline__ void rhs_exact(const TLConst& p, double erf, double t
     if constexpr (SPEC) {
         dts = spec_div(num_s, p.cs, p.rcs);
         dtd = spec_div(num_d, p.cd, p.rcd);
-        acc = max3_i32(acc, window_tag(num_s), window_tag(num_d));
+        if constexpr (TAGS) acc = max3_i32(acc, window_tag(num_s), window_tag(num_d));
     } else {
         dts = num_s / p.cs;
         dtd = num_d / p.cd;
     }
 }
 
-template <bool SPEC>
+template <bool SPEC, bool TAGS = SPEC>
 __device__ __forceinline__ void rk4_step_exact(const TLConst& p, double erf, double h,
                                                double half_step, double sixth, double& ts,
                                                double& td, int32_t& acc)
 {
     double k1s, k1d, k2s, k2d, k3s, k3d, k4s, k4d;
-    rhs_exact<SPEC>(p, erf, ts, td, k1s, k1d, acc);
-    rhs_exact<SPEC>(p, erf, ts + k1s * half_step, td + k1d * half_step, k2s, k2d, acc);
-    rhs_exact<SPEC>(p, erf, ts + k2s * half_step, td + k2d * half_step, k3s, k3d, acc);
-    rhs_exact<SPEC>(p, erf, ts + k3s * h, td + k3d * h, k4s, k4d, acc);
+    rhs_exact<SPEC, TAGS>(p, erf, ts, td, k1s, k1d, acc);
+    rhs_exact<SPEC, TAGS>(p, erf, ts + k1s * half_step, td + k1d * half_step, k2s, k2d, acc);
+    rhs_exact<SPEC, TAGS>(p, erf, ts + k2s * half_step, td + k2d * half_step, k3s, k3d, acc);
+    rhs_exact<SPEC, TAGS>(p, erf, ts + k3s * h, td + k3d * h, k4s, k4d, acc);
     if constexpr (SPEC) {
         // (k1 + k2*2) + k3*2: the doubling is exact, so the fused form rounds identically
         ts = rk4_combine_fused2(ts, k1s, k2s, k3s, k4s, sixth);
@@ -57,6 +61,51 @@ __device__ __forceinline__ void rk4_step_exact(const TLConst& p, double erf, dou
         td = rk4_combine(td, k1d, k2d, k3d, k4d, sixth);
     }
 }
+
+// The state guard ("Guarding the states").  A member whose parameters, step and forcing lie in the boxes
+// of two_layer_box.hpp keeps every numerator of a sub-step in spec_div's window whenever |Ts| and |Td| at the sub-step's start lie
+// in the state box -- proven by scripts/two_layer_box_proof.py for those constants (tests/test_two_layer_box.py).  So a speculative
+// year needs one tag per state value and sub-step instead of one per numerator.
+namespace box {
+
+constexpr double pow2(int e)
+{
+    double r = 1.0;
+    for (; e > 0; --e) r *= 2.0;
+    for (; e < 0; ++e) r *= 0.5;
+    return r;
+}
+
+static_assert(kCsLo >= -128 && kCsHi <= 129 && kCdLo >= -128 && kCdHi <= 129, "heat-capacity boxes must lie in the divisor window");
+
+// box_tag's operands for a magnitude box [2^lo, 2^hi)
+constexpr uint32_t neg_edge(int lo) { return 0u - ((uint32_t)(1023 + lo) << 21); }
+constexpr uint32_t span(int lo, int hi) { return (uint32_t)(hi - lo) << 21; }
+
+__device__ __forceinline__ bool positive_in(double x, int lo, int hi)
+{
+    return x >= pow2(lo) && x < pow2(hi);
+}
+
+// +0, or a magnitude in the forcing box (-0 is not: it would make a numerator -0)
+__device__ __forceinline__ bool forcing_in(double f)
+{
+    return (__double_as_longlong(f) == 0) | (box_tag(f, neg_edge(kForcingLo)) < span(kForcingLo, kForcingHi));  // no branch
+}
+
+__device__ __forceinline__ bool params_in(const TLConst& p, double h, double half_step)
+{
+    return positive_in(p.lambda0, kLambda0Lo, kLambda0Hi) &&
+           (__double_as_longlong(p.a) == 0 || positive_in(p.a, kALo, kAHi)) &&
+           positive_in(p.eff_eta, kEffEtaLo, kEffEtaHi) && positive_in(p.eta, kEtaLo, kEtaHi) &&
+           positive_in(p.cs, kCsLo, kCsHi) && positive_in(p.cd, kCdLo, kCdHi) &&
+           positive_in(h, kHLo, kHHi) && positive_in(half_step, kHLo, kHHi);
+}
+
+}  // namespace box
+
+// the sub-step count of the annual axis (h = 0.1): its year body is unrolled
+constexpr int32_t kUnrolledSubSteps = 10;
 
 struct TLFast {
     double l0, a, ee, ed;  // lambda0/Cs, a/Cs, efficacy*eta/Cs, eta/Cd
@@ -207,35 +256,61 @@ __device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const doub
         p.rcd = dcd.r;
         // 0 (never "all inside") when a heat capacity is outside the divisor window
         const int32_t acc0 = (dcs.ok && dcd.ok) ? (int32_t)0x80000000 : 0;
-        for (int32_t n = step_begin; n < step_end; ++n) {
-            const double erf = erf_next;
-            const int32_t m = m_next;
-            const int32_t np = n < last ? n + 1 : n;
-            erf_next = forcing_ahead(n, np, erf_next);
-            m_next = a.nsub[np];
-            const double ts0 = ts, td0 = td;
-            int32_t acc = acc0;
-            for (int32_t s = 0; s < m; ++s) rk4_step_exact<true>(p, erf, h, half_step, sixth, ts, td, acc);
-            // A NaN state at the start of the year makes every value of the year NaN on either
-            // path; everything else must have stayed inside the window.
-            const bool settled = (ts0 != ts0) || (td0 != td0);
-            if (__builtin_expect(acc >= 0 && !settled, 0)) {
-                ts = ts0;
-                td = td0;
-                int32_t unused = 0;
-                for (int32_t s = 0; s < m; ++s) rk4_step_exact<false>(p, erf, h, half_step, sixth, ts, td, unused);
+        // one decision per wavefront: every member in the boxes -> the state guard
+        const bool guard_states = __all(!a.numerator_guard && box::params_in(p, h, half_step));
+        auto years = [&](auto states) {
+            constexpr bool kStates = decltype(states)::value;
+            for (int32_t n = step_begin; n < step_end; ++n) {
+                const double erf = erf_next;
+                const int32_t m = m_next;
+                const int32_t np = n < last ? n + 1 : n;
+                erf_next = forcing_ahead(n, np, erf_next);
+                m_next = a.nsub[np];
+                const double ts0 = ts, td0 = td;
+                bool replay;
+                if constexpr (kStates) {
+                    constexpr uint32_t kEdge = box::neg_edge(box::kStateLo), kSpan = box::span(box::kStateLo, box::kStateHi);
+                    uint32_t acc = box::forcing_in(erf) ? 0u : ~0u;
+                    int32_t no_tags = 0;
+                    auto sub_step = [&]() {
+                        acc = max3_u32(acc, box_tag(ts, kEdge), box_tag(td, kEdge));
+                        rk4_step_exact<true, false>(p, erf, h, half_step, sixth, ts, td, no_tags);
+                    };
+                    if (m == kUnrolledSubSteps) {
+#pragma unroll
+                        for (int32_t s = 0; s < kUnrolledSubSteps; ++s) sub_step();
+                    } else {
+                        for (int32_t s = 0; s < m; ++s) sub_step();
+                    }
+                    replay = acc >= kSpan;
+                } else {
+                    int32_t acc = acc0;
+                    for (int32_t s = 0; s < m; ++s) rk4_step_exact<true>(p, erf, h, half_step, sixth, ts, td, acc);
+                    replay = acc >= 0;
+                }
+                // A NaN state at the start of the year makes every value of the year NaN on either
+                // path; everything else must have stayed inside the window.
+                const bool settled = (ts0 != ts0) || (td0 != td0);
+                if (__builtin_expect(replay && !settled, 0)) {
+                    ts = ts0;
+                    td = td0;
+                    int32_t unused = 0;
+                    for (int32_t s = 0; s < m; ++s) rk4_step_exact<false>(p, erf, h, half_step, sixth, ts, td, unused);
+                }
+                if constexpr (STORE) {
+                    *out_ts = ts;
+                    *out_td = td;
+                    cache.put(0, ts);
+                    cache.put(1, td);
+                    out_ts += N;
+                    out_td += N;
+                } else {
+                    lik_consume(a, lik, n + 1, ts, td);
+                }
             }
-            if constexpr (STORE) {
-                *out_ts = ts;
-                *out_td = td;
-                cache.put(0, ts);
-                cache.put(1, td);
-                out_ts += N;
-                out_td += N;
-            } else {
-                lik_consume(a, lik, n + 1, ts, td);
-            }
-        }
+        };
+        if (guard_states) years(std::true_type());
+        else years(std::false_type());
     } else {
         double inv_cs;
         const TLFast p = make_fast(lambda0, pa, efficacy, eta, cs, cd, inv_cs);

@@ -1,0 +1,205 @@
+#!/usr/bin/env python3
+"""Checks that one EXACT two-layer RK4 sub-step started inside the boxes of rscm_amd/csrc/two_layer_box.hpp keeps every numerator in
+spec_div's window, so that the state-guarded year loop of two_layer_body.hpp may skip the per-numerator tags.
+
+Every value of the sub-step is followed as an abstract double: which of {+0, -0, positive, negative} it can be, a power of two
+2^lo that bounds its magnitude from below when it is not zero, and a number hi that bounds it from above.  The operations are the
+kernel's, in its order (two_layer_body.hpp, rhs_exact / rk4_step_exact), each rounded to nearest:
+
+  product   nonzero x*y: |x*y| >= 2^(lo_x + lo_y), a double, so the rounded product is too; hi = hi_x * hi_y rounded up.
+            A zero factor gives a zero whose sign is the product of the signs.
+  quotient  by a divisor in [2^dlo, 2^dhi): a nonzero quotient exceeds 2^(lo_n - dhi); hi = hi_n / 2^dlo.
+  sum       x + y of nonzero operands.  Same sign: |x + y| >= max(|x|, |y|).  Opposite signs: if |y| < |x|/2 the sum exceeds |x|/2,
+            if |y| > 2|x| it exceeds |x|; otherwise both operands are at least |x|/2 >= 2^(lo_x - 1), so both are multiples of
+            2^(lo_x - 53) and so is their difference: it is 0 or at least 2^(lo_x - 53).  The same holds with x and y exchanged, so a
+            nonzero sum is at least 2^(max(lo_x, lo_y) - 53).  A sum that cancels exactly is +0; it is -0 only if both operands are
+            -0.  With one zero operand the sum is the other operand (or a zero by the rules of signs).
+
+Every lower bound stays far above 2^-1022, so denormals (where the ulp argument would change) never enter.  The numerators must
+be +0 (spec_div(+0) = +0 = IEEE; -0 would come out as +0) or lie in [2^-511, 2^513), and k2, k3 below 2^1023 so that 2*k2 and 2*k3
+are finite (rk4_combine_fused2).  The end of the sub-step needs nothing: it is the next sub-step's start, checked there.
+
+    python scripts/two_layer_box_proof.py            # prints the bounds of every numerator; exit status 1 if the proof fails
+"""
+import math
+import os
+import re
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+HEADER = os.path.join(ROOT, "rscm_amd", "csrc", "two_layer_box.hpp")
+
+WINDOW_LO, WINDOW_HI = -511, 513     # numerator window [2^-511, 2^513): biased exponent in [512, 1535]
+DIVISOR_LO, DIVISOR_HI = -128, 129   # divisor window [2^-128, 2^129)
+MIN_EXP = -1022 + 60                 # lower bounds must stay this far above the denormals
+
+
+def read_boxes(path=HEADER):
+    """{name: (lo, hi)} from the constexpr pairs of the header (kXxxLo = a, kXxxHi = b)."""
+    text = open(path).read()
+    vals = {}
+    for line in re.findall(r"^\s*constexpr\s+int\s+([^;]*);", text, re.M):
+        vals.update((m.group(1), int(m.group(2))) for m in re.finditer(r"k(\w+)\s*=\s*(-?\d+)", line))
+    boxes = {}
+    for k, v in vals.items():
+        if k.endswith("Lo"):
+            boxes[k[:-2]] = (v, vals[k[:-2] + "Hi"])
+    return boxes
+
+
+def _up(x):
+    return math.nextafter(x, math.inf)
+
+
+class V:
+    """An abstract double: kinds (subset of '+0', '-0', '+', '-'), nonzero magnitude >= 2^lo, magnitude <= hi."""
+
+    def __init__(self, kinds, lo, hi):
+        self.kinds, self.lo, self.hi = frozenset(kinds), lo, hi
+        if self.nonzero():
+            if lo < MIN_EXP:
+                raise ProofError(f"lower bound 2^{lo} too close to the denormals")
+            if not hi < math.ldexp(1.0, 1023):
+                raise ProofError(f"upper bound {hi!r} may overflow")
+
+    def nonzero(self):
+        return bool(self.kinds & {"+", "-"})
+
+    def __repr__(self):
+        return f"V({sorted(self.kinds)}, >=2^{self.lo}, <={self.hi:.3g})"
+
+
+class ProofError(Exception):
+    pass
+
+
+def positive_box(lo, hi, zero=False):
+    return V({"+", "+0"} if zero else {"+"}, lo, math.ldexp(1.0, hi))
+
+
+def magnitude_box(lo, hi, zero=False):
+    return V({"+", "-", "+0"} if zero else {"+", "-"}, lo, math.ldexp(1.0, hi))
+
+
+def _sign(k):
+    return -1 if k in ("-", "-0") else 1
+
+
+def mul(x, y):
+    kinds = set()
+    for a in x.kinds:
+        for b in y.kinds:
+            s = _sign(a) * _sign(b)
+            if a in ("+0", "-0") or b in ("+0", "-0"):
+                kinds.add("+0" if s > 0 else "-0")
+            else:
+                kinds.add("+" if s > 0 else "-")
+    return V(kinds, x.lo + y.lo, _up(x.hi * y.hi))
+
+
+def neg(x):
+    flip = {"+0": "-0", "-0": "+0", "+": "-", "-": "+"}
+    return V({flip[k] for k in x.kinds}, x.lo, x.hi)
+
+
+def add(x, y):
+    kinds, los = set(), []
+    for a in x.kinds:
+        for b in y.kinds:
+            za, zb = a in ("+0", "-0"), b in ("+0", "-0")
+            if za and zb:
+                kinds.add("-0" if (a, b) == ("-0", "-0") else "+0")
+            elif za:
+                kinds.add(b)
+                los.append(y.lo)
+            elif zb:
+                kinds.add(a)
+                los.append(x.lo)
+            elif a == b:
+                kinds.add(a)
+                los.append(max(x.lo, y.lo))
+            else:
+                kinds |= {"+", "-", "+0"}
+                los.append(max(x.lo, y.lo) - 53)
+    return V(kinds, min(los) if los else 0, _up(x.hi + y.hi))
+
+
+def sub(x, y):
+    return add(x, neg(y))
+
+
+def div(n, dlo, dhi):
+    """n / d for d in [2^dlo, 2^dhi), d > 0."""
+    return V(set(n.kinds), n.lo - dhi, _up(n.hi / math.ldexp(1.0, dlo)))
+
+
+def check_numerator(name, x):
+    if "-0" in x.kinds:
+        raise ProofError(f"{name} may be -0")
+    if x.nonzero():
+        if x.lo < WINDOW_LO:
+            raise ProofError(f"{name} may be as small as 2^{x.lo}, below 2^{WINDOW_LO}")
+        if not x.hi < math.ldexp(1.0, WINDOW_HI):
+            raise ProofError(f"{name} may reach {x.hi!r}, not below 2^{WINDOW_HI}")
+
+
+def prove(boxes, log=None):
+    """Raise ProofError unless every numerator of a sub-step started inside `boxes` is +0 or inside the window; return the
+    numerators' abstract values {name: V}."""
+    b = boxes
+    for name in ("Cs", "Cd"):
+        lo, hi = b[name]
+        if lo < DIVISOR_LO or hi > DIVISOR_HI:
+            raise ProofError(f"{name} box [2^{lo}, 2^{hi}) leaves the divisor window")
+    for name, (lo, hi) in b.items():
+        if lo >= hi:
+            raise ProofError(f"{name} box [2^{lo}, 2^{hi}) is empty")
+    lam0 = positive_box(*b["Lambda0"])
+    pa = positive_box(*b["A"], zero=True)
+    ee = positive_box(*b["EffEta"])
+    eta = positive_box(*b["Eta"])
+    erf = magnitude_box(*b["Forcing"], zero=True)
+    h = positive_box(*b["H"])                         # h and h / 2 alike
+    ts = magnitude_box(*b["State"])
+    td = magnitude_box(*b["State"])
+    cs, cd = b["Cs"], b["Cd"]
+
+    out = {}
+
+    def rhs(stage, x, y):
+        diff = sub(x, y)
+        lam = sub(lam0, mul(pa, x))
+        num_s = sub(sub(erf, mul(lam, x)), mul(ee, diff))
+        num_d = mul(eta, diff)
+        for nm, v in ((f"num_s[{stage}]", num_s), (f"num_d[{stage}]", num_d)):
+            check_numerator(nm, v)
+            out[nm] = v
+            if log:
+                log(f"{nm:10s} {sorted(v.kinds)}  nonzero >= 2^{v.lo}  <= {v.hi:.4g} (2^{math.log2(v.hi):.1f})")
+        return div(num_s, *cs), div(num_d, *cd)
+
+    k1s, k1d = rhs(1, ts, td)
+    k2s, k2d = rhs(2, add(ts, mul(k1s, h)), add(td, mul(k1d, h)))
+    k3s, k3d = rhs(3, add(ts, mul(k2s, h)), add(td, mul(k2d, h)))
+    rhs(4, add(ts, mul(k3s, h)), add(td, mul(k3d, h)))
+    for nm, k in (("k2s", k2s), ("k2d", k2d), ("k3s", k3s), ("k3d", k3d)):
+        if not 2.0 * k.hi < math.inf:
+            raise ProofError(f"2*{nm} may overflow")
+    return out
+
+
+def main():
+    boxes = read_boxes()
+    for k, (lo, hi) in sorted(boxes.items()):
+        print(f"{k:8s} [2^{lo}, 2^{hi})")
+    try:
+        prove(boxes, log=print)
+    except ProofError as e:
+        print(f"FAILED: {e}")
+        return 1
+    print("every numerator is +0 or inside [2^-511, 2^513); 2*k2 and 2*k3 are finite")
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
