@@ -1318,9 +1318,7 @@ class GraphModel:
         ``set_weights_from_loglik``), ``method="inverted_cdf"``; the result then has ``"weight"`` in place of ``"count"``.
         ``anomaly``: of each member's anomaly against the baseline ``set_baseline`` gave the variable's home."""
         ens, vid = self.variable_home(name)
-        if anomaly:
-            return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=True)
-        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted)
+        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly)
 
     def set_baseline(self, name: str, t_begin: int, t_end: int, t_stride: int = 1) -> None:
         """Each member's mean of ``name`` over the rows ``t_begin, t_begin + t_stride, ... < t_end`` as the baseline of the

@@ -12,7 +12,7 @@
 // exceedance_kernel: per block, the counts (or the summed int64 member weights) of members at or above each threshold and of
 // non-NaN members go into LDS int64 bins, then one integer atomic per bin.  No float atomics: the sums are exact and independent
 // of the block count, and shards of one ensemble add them exactly.  With the weights' bound (a handle's weights sum to at most
-// 2^53, wselect.hip) nothing wraps.
+// 2^53, weights.hip) nothing wraps.
 #include <hip/hip_runtime.h>
 
 #include "rscm_device.hpp"

@@ -735,30 +735,26 @@ hipError_t launch_summary_rows(const double* rows, int64_t n, int32_t n_rows, do
 hipError_t launch_quantile_rows(const double* rows, int64_t N, int32_t n_rows, const double* d_q, int32_t n_q, double* d_out,
                                 hipStream_t s);
 // multi-pass radix select (select.hip): 8-bit digits, eight passes; one histogram of kSelBins int64 counts per row in pass 0, per
-// (row, target) later, where target 2k / 2k + 1 of a row is the lower / upper order statistic of quantile k.  Targets are
-// histogrammed kSelGroup per launch (LDS: kSelGroup x kSelBins 32-bit counters).
+// (row, target) later.  Unweighted, target 2k / 2k + 1 of a row is the lower / upper order statistic of quantile k; weighted
+// (int64 member weights d_w[N], numpy's "inverted_cdf"), the histograms sum weights and there is one target per quantile.
+// Targets are histogrammed kSelGroup per launch (LDS: kSelGroup x kSelBins 32-bit counts, or gn x kSelBins 64-bit weight sums).
 constexpr int kSelBins = 256;
 constexpr int kSelPasses = 8;
 constexpr int kSelGroup = 16;
 int32_t select_blocks_per_row(int64_t N, int32_t n_rows);
-// zeroes d_hist[hist_elems], then adds this pass's counts of rows d_rows[n_rows][N] (device array of row pointers); d_base
-// non-null: of the anomalies x - d_base[i] (d_base[N] 16-byte aligned)
-hipError_t launch_select_hist(const double* const* d_rows, const double* d_base, int64_t N, int32_t n_rows, int32_t pass,
-                              const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
-// consumes the (reduced) histograms of `pass`: per (row, target) the bucket of its remaining rank; pass 0 also sets d_count[row]
+// zeroes d_hist[hist_elems], then adds this pass's counts of rows d_rows[n_rows][N] (device array of row pointers); d_w non-null:
+// member i adds d_w[i]; d_base non-null: of the anomalies x - d_base[i] (d_w and d_base 16-byte aligned)
+hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, int64_t N, int32_t n_rows,
+                              int32_t pass, const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
+// consumes the (reduced) histograms of `pass`: per (row, target) the bucket of its remaining rank; pass 0 also sets d_count[row].
+// d_over non-null: the weighted commit, where d_count is the row's weight W and a row with W > 2^53 sets *d_over and gets NaN
 hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
-                                uint64_t* d_prefix, int64_t* d_rank, hipStream_t s);
-// after the last commit: d_out[r] = {count, quantile q[0], ..., q[n_q-1]} from the selected keys, as launch_quantile_rows
+                                uint64_t* d_prefix, int64_t* d_rank, int32_t* d_over, hipStream_t s);
+// after the last commit: d_out[r] = {count (weighted: W), quantile q[0], ..., q[n_q-1]} from the selected keys, as
+// launch_quantile_rows (weighted: the values of the keys)
 hipError_t launch_select_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, const double* d_q,
-                                double* d_out, hipStream_t s);
-// the weighted select (wselect.hip): the same passes over int64 member weights d_w[N] (numpy's "inverted_cdf"); one target per
-// quantile; pass 0's reduced histogram sums to W per row, stored as d_count; a row with W > 2^53 sets *d_over and gets NaN
-hipError_t launch_wselect_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, int64_t N, int32_t n_rows,
-                               int32_t pass, const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
-hipError_t launch_wselect_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
-                                 uint64_t* d_prefix, int64_t* d_rank, int32_t* d_over, hipStream_t s);
-// d_out[r] = {W, quantile q[0], ..., q[n_q-1]}
-hipError_t launch_wselect_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, double* d_out, hipStream_t s);
+                                bool weighted, double* d_out, hipStream_t s);
+// the member weights (weights.hip):
 // *d_key = max(*d_key, order key of ll[i]) over members with status 0 and finite ll (the caller seeds it with the key of -inf)
 hipError_t launch_loglik_max(const double* d_ll, const uint8_t* d_status, int64_t N, unsigned long long* d_key, hipStream_t s);
 // d_w[i] = llround(exp(min(ll[i] - ll_max, 0)) * 2^bits) for status 0 and finite ll, else 0

@@ -1,7 +1,7 @@
 // Host side of the staged quantile select (rscm_ens_select_* and rscm_ens_quantile_rows; kernels in select.hip), of its weighted
-// form (rscm_ens_select_begin_weighted, rscm_ens_weighted_quantile_rows; wselect.hip), of the flagged and vector forms
+// form (rscm_ens_select_begin_weighted, rscm_ens_weighted_quantile_rows), of the flagged and vector forms
 // (rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex: anomalies against the handle's baseline; rscm_ens_quantile_vectors,
-// rscm_ens_select_begin_vectors: device vectors of N doubles as rows) and of the member weights it reads.
+// rscm_ens_select_begin_vectors: device vectors of N doubles as rows) and of the member weights it reads (weights.hip).
 //
 // A select resolves its rows once, at begin, into a device array of row pointers (rscm_ens::row_ptr: full storage, the window or
 // the strided output store), then alternates pass (histograms of this handle's members) and commit (the reduced histograms move
@@ -10,10 +10,10 @@
 // the same keys.  The weighted select runs the same stages over the handle's int64 member weights: one target per quantile, and
 // pass 0's reduced histograms give each row's weight W, which the first commit checks against 2^53 on every handle.
 #include <cmath>
-#include <cstring>
 #include <limits>
 
 #include "ens.hpp"
+#include "select_keys.hpp"
 
 struct SelectState {
     int32_t var = 0, t_begin = 0, t_stride = 1;
@@ -22,7 +22,7 @@ struct SelectState {
     int32_t n_q = 0, n_t = 0;
     int32_t pass = 0;       // the next pass to histogram
     bool awaiting_commit = false;
-    bool weighted = false;  // rscm_ens_select_begin_weighted: count holds W, n_t == n_q
+    bool weighted = false;  // RSCM_SELECT_WEIGHTED, the mode of the kernels: count holds W, n_t == n_q
     const double* d_base = nullptr;   // RSCM_SELECT_ANOMALY: the handle's baseline (it cannot change while the select is staged)
     const double** d_rows = nullptr;
     double* d_q = nullptr;
@@ -154,11 +154,8 @@ int select_pass(rscm_ens* h, SelectState& s, int32_t* done, int64_t** buf_dev, i
     }
     if (int rc = set_device(h)) return rc;
     const size_t elems = (size_t)s.n_comp * rscm::kSelBins * (s.pass == 0 ? 1 : (size_t)s.n_t);
-    if (s.weighted)
-        HIPCHK(rscm::launch_wselect_hist(s.d_rows, h->d_weights, s.d_base, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems,
-                                         h->stream));
-    else
-        HIPCHK(rscm::launch_select_hist(s.d_rows, s.d_base, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
+    HIPCHK(rscm::launch_select_hist(s.d_rows, s.weighted ? h->d_weights : nullptr, s.d_base, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t,
+                                    s.d_hist, elems, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     s.awaiting_commit = true;
     *done = 0;
@@ -171,24 +168,18 @@ int select_commit(rscm_ens* h, SelectState& s)
 {
     if (!s.awaiting_commit) return fail(RSCM_ERR_STATE, "select: no pass to commit");
     if (int rc = set_device(h)) return rc;
-    if (s.weighted) {
-        const bool first = s.pass == 0;
-        if (first) HIPCHK(hipMemsetAsync(s.d_over, 0, sizeof(int32_t), h->stream));
-        HIPCHK(rscm::launch_wselect_commit(s.d_hist, s.pass, s.n_comp, s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, s.d_over, h->stream));
-        s.awaiting_commit = false;
-        if (++s.pass == rscm::kSelPasses) HIPCHK(rscm::launch_wselect_finish(s.d_count, s.d_prefix, s.n_comp, s.n_q, s.d_out, h->stream));
-        if (first) {
-            int32_t over = 0;
-            HIPCHK(hipMemcpyAsync(&over, s.d_over, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPCHK(hipStreamSynchronize(h->stream));
-            if (over) return fail(RSCM_ERR_INVALID, "weighted select: the weights of a row's non-NaN members sum to more than 2^53");
-        }
-        return RSCM_OK;
-    }
-    HIPCHK(rscm::launch_select_commit(s.d_hist, s.pass, s.n_comp, s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, h->stream));
+    const bool check_w = s.weighted && s.pass == 0;   // the first weighted commit checks every row's W against 2^53
+    if (check_w) HIPCHK(hipMemsetAsync(s.d_over, 0, sizeof(int32_t), h->stream));
+    HIPCHK(rscm::launch_select_commit(s.d_hist, s.pass, s.n_comp, s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, s.d_over, h->stream));
     s.awaiting_commit = false;
     if (++s.pass == rscm::kSelPasses)
-        HIPCHK(rscm::launch_select_finish(s.d_count, s.d_prefix, s.n_comp, s.n_q, s.d_q, s.d_out, h->stream));
+        HIPCHK(rscm::launch_select_finish(s.d_count, s.d_prefix, s.n_comp, s.n_q, s.d_q, s.weighted, s.d_out, h->stream));
+    if (check_w) {
+        int32_t over = 0;
+        HIPCHK(hipMemcpyAsync(&over, s.d_over, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        if (over) return fail(RSCM_ERR_INVALID, "weighted select: the weights of a row's non-NaN members sum to more than 2^53");
+    }
     return RSCM_OK;
 }
 
@@ -417,7 +408,7 @@ int rscm_ens_quantile_vectors(rscm_ens* h, int32_t n_vec, const double* const* v
 namespace {
 
 // Makes d_new[N] (device memory, taken over: freed on failure) the handle's weights if no weight is negative and they sum to at
-// most 2^53.  That bound on every handle keeps every histogram sum of the weighted select from wrapping (wselect.hip); on any
+// most 2^53.  That bound on every handle keeps every histogram sum of the weighted select from wrapping (select.hip); on any
 // failure the weights set before stay.
 int install_weights(rscm_ens* h, int64_t* d_new)
 {
@@ -463,10 +454,7 @@ int device_loglik(rscm_ens* h, const double* ll, int32_t on_device, double** tmp
 int loglik_max(rscm_ens* h, const double* d_ll, double* out)
 {
     unsigned long long* d_key = nullptr;
-    const double lo = -std::numeric_limits<double>::infinity();
-    uint64_t u;
-    std::memcpy(&u, &lo, sizeof u);
-    unsigned long long key = (u >> 63) ? ~u : (u | 0x8000000000000000ull);   // order key of -inf (select_keys.hpp)
+    unsigned long long key = rscm::order_key(-std::numeric_limits<double>::infinity());
     hipError_t e = rscm::dev_malloc(&d_key, sizeof key);
     if (e == hipSuccess) e = hipMemcpyAsync(d_key, &key, sizeof key, hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = rscm::launch_loglik_max(d_ll, h->d_status, h->N, d_key, h->stream);
@@ -474,8 +462,7 @@ int loglik_max(rscm_ens* h, const double* d_ll, double* out)
     if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
     (void)hipFree(d_key);
     HIPCHK(e);
-    u = (key >> 63) ? (key & 0x7FFFFFFFFFFFFFFFull) : ~key;
-    std::memcpy(out, &u, sizeof u);
+    *out = rscm::key_value(key);
     return RSCM_OK;
 }
 

@@ -175,6 +175,7 @@ def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int
     the result has ``"weight"`` in place of ``"count"``.
 
     ``anomaly``: of each member's anomaly against its baseline (every rank's ``Ensemble.set_baseline`` over the same rows)."""
+    # a keyword goes to the ensemble only when set: an ensemble-like object that has no weighted or anomaly form need not take it
     kw = {}
     if weighted:
         kw["weighted"] = True

@@ -403,26 +403,22 @@ class Ensemble:
     def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
                       weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
         """``quantile_series``'s numbers (the same bits) over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any
-        storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows: a radix
+        storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows_ex: a radix
         select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``.
 
         ``weighted``: ``numpy.nanquantile(row, q, weights=w, method="inverted_cdf")`` with the member weights
-        (``set_member_weights`` / ``set_weights_from_loglik``; rscm_ens_weighted_quantile_rows).  Returns
+        (``set_member_weights`` / ``set_weights_from_loglik``; RSCM_SELECT_WEIGHTED).  Returns
         ``{"weight": [rows] (summed weight of the non-NaN members), "quantiles": [rows][len(q)]}``.
 
         ``anomaly``: the same quantiles of each member's own anomaly ``x[i] - b[i]`` against the baseline (``set_baseline``;
-        rscm_ens_quantile_rows_ex) -- not the plume minus a quantile of the baseline."""
+        RSCM_SELECT_ANOMALY) -- not the plume minus a quantile of the baseline."""
         qq = np.atleast_1d(L.f64(q))
         t_end = self.n_times if t_end is None else t_end
         rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
         out, cnt = np.empty((rows, qq.size)), np.empty(rows)
-        if anomaly:
-            flags = L.SELECT_ANOMALY | (L.SELECT_WEIGHTED if weighted else 0)
-            L.check(self._lib.rscm_ens_quantile_rows_ex(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), flags,
-                                                        L.dptr(out), L.dptr(cnt)))
-        else:
-            fn = self._lib.rscm_ens_weighted_quantile_rows if weighted else self._lib.rscm_ens_quantile_rows
-            L.check(fn(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), L.dptr(out), L.dptr(cnt)))
+        flags = L.SELECT_WEIGHTED * bool(weighted) | L.SELECT_ANOMALY * bool(anomaly)
+        L.check(self._lib.rscm_ens_quantile_rows_ex(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), flags,
+                                                    L.dptr(out), L.dptr(cnt)))
         return {"weight" if weighted else "count": cnt.astype(np.int64), "quantiles": out}
 
     def select(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
@@ -616,19 +612,14 @@ class QuantileSelect:
         self.ens = ens
         self.q = np.atleast_1d(L.f64(q))
         self.weighted = bool(weighted)
-        flags = L.SELECT_WEIGHTED if weighted else 0
+        flags = L.SELECT_WEIGHTED * bool(weighted) | L.SELECT_ANOMALY * bool(anomaly)
         if vectors is not None:                      # rscm_ens_select_begin_vectors: the vectors are the rows
             arr, self.rows = ens._vectors(vectors)
             L.check(ens._lib.rscm_ens_select_begin_vectors(ens._h, self.rows, arr, self.q.size, L.dptr(self.q), flags))
         else:
             t_end = ens.n_times if t_end is None else t_end
             self.rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
-            if anomaly:
-                L.check(ens._lib.rscm_ens_select_begin_ex(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q),
-                                                          flags | L.SELECT_ANOMALY))
-            else:
-                begin = ens._lib.rscm_ens_select_begin_weighted if weighted else ens._lib.rscm_ens_select_begin
-                L.check(begin(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q)))
+            L.check(ens._lib.rscm_ens_select_begin_ex(ens._h, ens._var(var), t_begin, t_end, t_stride, self.q.size, L.dptr(self.q), flags))
         self._open = True
         self._buf = None
 

@@ -4,7 +4,7 @@ over all 751 rows of a two-layer ensemble, against moving the series to the host
 Wall times of one call after a warm-up; the kernel times come from a separate
 `rocprofv3 --kernel-trace --stats -- python scripts/bench_quantiles.py` run.
 
---weighted also times the likelihood-weighted select (rscm_ens_weighted_quantile_rows, csrc/wselect.hip) next to the unweighted
+--weighted also times the likelihood-weighted select (quantile_rows(weighted=True), csrc/select.hip) next to the unweighted
 one: member weights quantised from a synthetic log-likelihood (set_weights_from_loglik), and numpy's weighted "inverted_cdf"
 on the host at 1e5 members for the bits."""
 import os

@@ -1,8 +1,8 @@
 """Worker for tests/test_distributed_indicators_cpu.py: one rank of a gloo group running rscm_amd.distributed's
 quantile_rows_global(anomaly=True), quantile_vectors_global and exceedance_global.  The compute needs a GPU, so the rank's
 ensemble is a stand-in: rows, weights and the indicator vector are known functions of the GLOBAL member id, each member's
-baseline and anomalies come from tests/host_indicators.py, and the staged selects are the numpy restatements of select.hip /
-wselect.hip.  What is under test is the product's loops and reductions."""
+baseline and anomalies come from tests/host_indicators.py, and the staged selects are the numpy restatements of select.hip's
+two modes.  What is under test is the product's loops and reductions."""
 import json
 import os
 import sys

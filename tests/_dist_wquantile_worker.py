@@ -1,8 +1,9 @@
 """Worker for tests/test_distributed_weighted_quantiles_cpu.py: one rank of a gloo group running ShardedEnsemble.constrain and the
 weighted rscm_amd.distributed.quantile_rows_global.  The compute needs a GPU, so the rank's ensemble is a stand-in: rows,
 log-likelihoods and status are known functions of the GLOBAL member id, the weights are quantised in numpy as the device does,
-and the staged select is the numpy restatement of csrc/wselect.hip (tests/host_wselect.py).  What is under test is the
-product's loops: the MAX all-reduce of the local maxima, then pass, all-reduce (int64 SUM over gloo), commit, result."""
+and the staged select is the numpy restatement of the weighted select of csrc/select.hip (tests/host_wselect.py).  What is
+under test is the product's loops: the MAX all-reduce of the local maxima, then pass, all-reduce (int64 SUM over gloo), commit,
+result."""
 import json
 import os
 import sys

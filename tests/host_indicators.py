@@ -1,5 +1,5 @@
-"""Baselines, anomalies, per-member indicators and exceedance (rscm_amd/csrc/indicators.hip, the anomaly select of select.hip /
-wselect.hip) restated in numpy: the definitions of DESIGN.md section 8k, which the GPU tests compare the device against bit for bit
+"""Baselines, anomalies, per-member indicators and exceedance (rscm_amd/csrc/indicators.hip, the anomaly select of
+select.hip) restated in numpy: the definitions of DESIGN.md section 8k, which the GPU tests compare the device against bit for bit
 and the CPU rehearsal of rscm_amd.distributed (tests/_dist_indicator_worker.py) uses as its stand-in ensemble's arithmetic."""
 import numpy as np
 

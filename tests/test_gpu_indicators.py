@@ -1,5 +1,5 @@
 """GPU tier: anomaly plumes, per-member indicators, quantiles of per-member vectors and exceedance (csrc/indicators.hip, the
-anomaly flag of the selects in select.hip / wselect.hip; rscm_ens_set_baseline, rscm_ens_quantile_rows_ex,
+anomaly flag of the select in select.hip; rscm_ens_set_baseline, rscm_ens_quantile_rows_ex,
 rscm_ens_member_indicators, rscm_ens_quantile_vectors, rscm_ens_exceedance).  The oracle is the numpy restatement in
 tests/host_indicators.py on rows copied to the host, compared bit for bit: zeros without their sign (the select's key order puts
 -0.0 first, numpy keeps member order) and any NaN equal to any NaN."""

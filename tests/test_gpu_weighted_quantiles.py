@@ -1,7 +1,8 @@
-"""GPU tier: likelihood-weighted ensemble quantiles (csrc/wselect.hip, rscm_ens_weighted_quantile_rows, the weighted staged
-select, the member weights and their quantisation from a log-likelihood).  The oracle is
+"""GPU tier: likelihood-weighted ensemble quantiles (the weighted select of csrc/select.hip, rscm_ens_weighted_quantile_rows, the
+weighted staged select, the member weights and their quantisation from a log-likelihood, csrc/weights.hip).  The oracle is
 numpy.nanquantile(row, q, weights=w, method="inverted_cdf"), compared bit for bit with zeros taken without their sign (the key
 order puts -0.0 first, numpy keeps member order)."""
+import ctypes as C
 import warnings
 
 import numpy as np
@@ -65,6 +66,39 @@ def _weights(rng, n):
     return w
 
 
+def _legacy_entry_points_match_ex(e, rows):
+    """The four entry points older than the flags (rscm_ens_quantile_rows, rscm_ens_weighted_quantile_rows,
+    rscm_ens_select_begin, rscm_ens_select_begin_weighted) give the bits of their _ex form with the matching flags."""
+    from rscm_amd import _lib as L
+    lib, q = L.load(), np.asarray(Q, dtype=np.float64)
+
+    def staged(begin, *flags):
+        L.check(begin(e._h, 1, 0, rows, 1, q.size, L.dptr(q), *flags))
+        try:
+            done, p, n = C.c_int32(0), C.POINTER(C.c_int64)(), C.c_int64(0)
+            while True:
+                L.check(lib.rscm_ens_select_pass(e._h, C.byref(done), C.byref(p), C.byref(n)))
+                if done.value:
+                    break
+                L.check(lib.rscm_ens_select_commit(e._h))
+            out, cnt = np.empty((rows, q.size)), np.empty(rows)
+            L.check(lib.rscm_ens_select_result(e._h, L.dptr(out), L.dptr(cnt)))
+        finally:
+            L.check(lib.rscm_ens_select_end(e._h))
+        return out, cnt
+
+    def direct(fn, *flags):
+        out, cnt = np.empty((rows, q.size)), np.empty(rows)
+        L.check(fn(e._h, 1, 0, rows, 1, q.size, L.dptr(q), *flags, L.dptr(out), L.dptr(cnt)))
+        return out, cnt
+
+    for flags, legacy_rows, legacy_begin in ((0, lib.rscm_ens_quantile_rows, lib.rscm_ens_select_begin),
+                                             (L.SELECT_WEIGHTED, lib.rscm_ens_weighted_quantile_rows, lib.rscm_ens_select_begin_weighted)):
+        want = direct(lib.rscm_ens_quantile_rows_ex, flags)
+        for got in (direct(legacy_rows), staged(legacy_begin), staged(lib.rscm_ens_select_begin_ex, flags)):
+            assert all(np.array_equal(a.view(np.uint64), b.view(np.uint64)) for a, b in zip(got, want))
+
+
 def test_weighted_rows_equal_numpy_bit_for_bit(ra):
     """1e5 members x 751 rows, random int64 weights with zeros, NaN members in some rows and failed members: every row at
     seven quantiles equals numpy's weighted nanquantile, and ``weight`` is numpy's per-row sum over non-NaN members."""
@@ -88,6 +122,7 @@ def test_weighted_rows_equal_numpy_bit_for_bit(ra):
         assert _same(got["quantiles"], want)
         mid = e.quantile_rows("Surface Temperature", Q, 3, 700, 7, weighted=True)    # strided
         assert _same(mid["quantiles"], got["quantiles"][3:700:7]) and np.array_equal(mid["weight"], W[3:700:7])
+        _legacy_entry_points_match_ex(e, 40)
         e.rewind()
         e.run(40)                                                                  # weights survive rewind and run
         part = e.quantile_rows(1, Q, 0, 60, weighted=True)

@@ -1,4 +1,4 @@
-"""CPU tier: the weighted radix select of csrc/wselect.hip, restated in numpy (tests/host_wselect.py), against
+"""CPU tier: the weighted radix select of csrc/select.hip, restated in numpy (tests/host_wselect.py), against
 numpy.nanquantile(row, q, weights=w, method="inverted_cdf") -- on rows with NaNs, +-inf, ties and zero weights, weights near the
 2^53 bound, and shards of one member set split unevenly -- and the C* search against a brute-force minimum."""
 import warnings
