@@ -8,9 +8,11 @@
 // the walker positions -- no host round trip per half-ensemble.
 //
 // Random numbers: Philox4x32-10 keyed by the seed, counter = (iteration, half, walker, stream), so a
-// run is reproducible and independent of launch geometry.  The reference draws from thread_rng:
-// only the distribution is comparable (tests/test_gpu_sampler.py checks moments and the
-// acceptance rule), as for the Latin hypercube.
+// run is reproducible and independent of launch geometry.  The device chain is pinned bit for bit to
+// the numpy restatement in tests/host_sampler.py (tests/test_gpu_sampler_exact.py): every proposal,
+// partner and accept decision.  Only the comparison with the reference's host sampler, which draws
+// from thread_rng, is distributional (tests/test_gpu_sampler.py checks moments and the acceptance
+// rule), as for the Latin hypercube.
 #include "philox.hpp"
 #include "rscm_device.hpp"
 

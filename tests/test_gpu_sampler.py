@@ -1,7 +1,9 @@
 """The device stretch-move sampler (rscm_sampler_* of the C ABI, csrc/sampler.hip) against the
 host sampler of rscm_amd.calibrate, which mirrors crates/rscm-calibrate/src/sampler/.  The
-reference draws from thread_rng, so samplers compare by distribution: moments of a known
-posterior, the acceptance rule, invariance of the prior, and -- exactly -- the scores it assigns."""
+reference draws from thread_rng, so the two samplers compare by distribution: moments of a known
+posterior, the acceptance rule, invariance of the prior, and -- exactly -- the scores it assigns.
+The device chain itself is pinned bit for bit to the numpy restatement of tests/host_sampler.py
+(tests/test_gpu_sampler_exact.py)."""
 import numpy as np
 import pytest
 
