@@ -258,7 +258,7 @@ static bool plan_split(const LockstepPlan* plan, const int32_t* idx, const int32
     for (int32_t t = 2; t <= count; ++t) {
         int32_t comp[rscm::kGroupTableOps];
         for (int32_t k = 0; k < t; ++k) comp[k] = k;
-        for (bool changed = true; changed;) {   // connected sets of the ops before the tail (at most eight ops)
+        for (bool changed = true; changed;) {   // connected sets of the ops before the tail (at most kGroupTableOps = 12 ops)
             changed = false;
             for (int32_t a = 0; a < t; ++a)
                 for (int32_t b = 0; b < t; ++b)

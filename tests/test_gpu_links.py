@@ -18,6 +18,7 @@ import numpy as np
 import pytest
 
 from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn, f_syn, two_layer_params
+from tests.host_lockstep import read_at_steps, relative_error
 
 pytestmark = pytest.mark.gpu
 
@@ -556,21 +557,15 @@ def test_full_emissions_driven_magicc_graph_closed_loop(ra, execution_order):
 
     def seen(name, consumer, force_end=False):
         """What `consumer` read of `name` at every step n (length T, last entry unused)."""
-        out = np.full(T, np.nan)
         if name not in producer:
             return np.asarray(exo[name], dtype=np.float64).copy()
-        if force_end or sources.get((name, consumer)) == "UpstreamOutput":
-            if pos[producer[name]] < pos[consumer]:
-                out[:-1] = S[name][1:]
-            return out       # a producer that runs later has not written index n+1 yet: NaN
-        out[:-1] = S[name][:-1]
-        return out
+        # a producer that runs later has not written index n+1 yet: NaN
+        return read_at_steps(np.asarray(S[name], dtype=np.float64), force_end or sources.get((name, consumer)) == "UpstreamOutput",
+                             pos[producer[name]] < pos[consumer])
 
     def check(name, got, want, tol):
-        assert (np.isnan(got) == np.isnan(want)).all(), (name, np.isnan(got).sum(), np.isnan(want).sum())
-        ok = ~np.isnan(want)
-        err = np.abs(got[ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))
-        assert err.size == 0 or err.max() <= tol, (name, err.max())
+        err = relative_error(got, want, name)
+        assert err <= tol, (name, err)
 
     def P(c):
         return np.asarray(by_name[c].param_vector(), dtype=np.float64)
@@ -691,24 +686,16 @@ def _closed_loop_member(model, exo, init, contributors, b, member, series=None):
     sources = model.variable_sources()
 
     def seen(name, consumer, force_end=False):
-        out = np.full(T, np.nan)
         if name not in producer:
             return np.asarray(exo[name], dtype=np.float64).copy()
-        if force_end or sources.get((name, consumer)) == "UpstreamOutput":
-            if pos[producer[name]] < pos[consumer]:
-                out[:-1] = S[name][1:]
-            return out
-        out[:-1] = S[name][:-1]
-        return out
+        return read_at_steps(np.asarray(S[name], dtype=np.float64), force_end or sources.get((name, consumer)) == "UpstreamOutput",
+                             pos[producer[name]] < pos[consumer])
 
     worst = {}
 
     def check(name, got, want, tol):
-        assert (np.isnan(got) == np.isnan(want)).all(), (name, member, np.isnan(got).sum(), np.isnan(want).sum())
-        ok = ~np.isnan(want)
-        err = np.abs(got[ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))
-        worst[name] = float(err.max()) if err.size else 0.0
-        assert err.size == 0 or err.max() <= tol, (name, member, err.max())
+        worst[name] = err = relative_error(got, want, f"{name} (member {member})")
+        assert err <= tol, (name, member, err)
 
     def P(c):
         return np.ascontiguousarray(model.ensembles[c].get_params()[:, member])
