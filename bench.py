@@ -24,6 +24,13 @@ LOCAL_RANK, WORLD_SIZE and MASTER_* set, relays rank 0's line and exits non-zero
 sample of its members (dump_sample) -- their status flags, and the Ts and Td series of those whose
 series are finite -- to DIR/<name>.npy, so that two builds can be compared output for output on
 identical inputs (dump_outputs).
+
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs and prints the line (`cpu_baseline` null, `extra` empty).  --full also takes, after
+the headline and in this order, the CPU baseline, the side measurements in `extra` (other modes,
+sizes and kinds, graphs, the samplers; with N > 1 the scale_* configs on every rank), the loss
+gather of `collective` and the ensemble check of the details; --no-cpu-baseline, --no-extra,
+--no-scale and --scale-only trim what --full adds.
 """
 import argparse
 import json
@@ -887,7 +894,7 @@ def timed_passes(ens, steps, warmup, torch, dist, world, tstream, collective=Non
 
 
 def loss_gather_report(ens, members, world, dist):
-    """Outside the timed region, only with a process group: BASELINE configs[4]'s exchange -- every rank scores its members on the
+    """Outside the timed region, only with --full and a process group: BASELINE configs[4]'s exchange -- every rank scores its members on the
     device (Gaussian log-likelihood against 18 Surface Temperature observations 1850..2020) and the ranks all-gather the per-member
     losses from device memory (rscm_amd.distributed.gather_members: RCCL over xGMI with the nccl backend, 8 B per member).  Timed with
     the host clock, barrier to return; a failure is reported in the line, it never costs the headline."""
@@ -1288,22 +1295,25 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--members", type=int, default=100_000, help="members per GPU (configs[1]: 1e5)")
     ap.add_argument("--mode", choices=["exact", "fast"], default="exact")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the secondary 1e6-member / fast-mode lines")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also take the CPU baseline, every side measurement (`extra`), the loss gather (N > 1) "
+                         "and the ensemble check; a plain run measures the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the secondary 1e6-member / fast-mode lines")
     ap.add_argument("--scale-members", type=int, default=1_000_000,
                     help="members per GPU of scale_exact_1e6 / scale_coupled_fast_1e6 (the north-star's weak-scaling point; tests pass less)")
     ap.add_argument("--share-members", type=int, default=125_000, help="members per GPU of scale_configs3_share (configs[3]: 1e6 / 8)")
     ap.add_argument("--share-years", type=int, default=750, help="years (x 12 monthly steps) of scale_configs3_share")
     ap.add_argument("--scale-walkers", type=int, default=100_000, help="walkers per iteration of scale_calibrate_sharded_1e5 (configs[4])")
     ap.add_argument("--scale-sweeps", type=int, default=200, help="timed sweeps of scale_calibrate_sharded_1e5")
-    ap.add_argument("--scale-only", action="store_true", help="of the extras, only the scale_* ones (tests)")
+    ap.add_argument("--scale-only", action="store_true", help="with --full: of the extras, only the scale_* ones (tests)")
     ap.add_argument("--extras-budget", type=float, default=540.0,
                     help="seconds after the headline at which a watchdog prints the line as it stands and ends the process, should a side "
-                         "measurement hang (default 540; the whole default run takes about a minute)")
+                         "measurement hang (default 540; a whole --full run takes about a minute)")
     ap.add_argument("--details", default="bench_details.json",
                     help="where rank 0 writes the FULL record (every roofline object with its notes, per-rank facts, run plans); stdout "
                          "carries only the compact line built from it.  Empty string: stderr only")
-    ap.add_argument("--no-scale", action="store_true", help="skip the scale_* extras (the configs defined on more than one GPU)")
+    ap.add_argument("--no-scale", action="store_true", help="with --full: skip the scale_* extras (the configs defined on more than one GPU)")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="no GPU work: the ranks meet over gloo, run the contract's barrier / max-over-ranks / rank report and rank 0 "
                          "prints a line with value null (tests/test_distributed_cpu.py checks the launcher and the N > 1 plumbing with it)")
@@ -1382,8 +1392,12 @@ def main():
     n_fail = int(ens.status().sum())
     fails = _gather_obj(dist, n_fail)
     run_plan = ens.last_run_plan()
-    s_mid = ens.summary("Surface Temperature", 270)  # year 2020
-    gather = loss_gather_report(ens, args.members, world, dist)
+    check = {"failed_members_rank0": n_fail}
+    gather = None
+    if args.full:
+        s_mid = ens.summary("Surface Temperature", 270)  # year 2020
+        check.update(Ts_2020_mean_rank0=s_mid["mean"], finite_members_2020_rank0=s_mid["count"])
+        gather = loss_gather_report(ens, args.members, world, dist)
     ens.close()
     collective, per_rank = rank_report(kernel_ms, wall, args.steps, torch, dist)
     if gather is not None:
@@ -1395,8 +1409,8 @@ def main():
     describe_run_plan(roofline_hbm, run_plan)
 
     extra = {}
-    # The record is complete from here on: the headline stands, the CPU baseline is taken next, the side measurements fill `extra`
-    # in place.  Should one of them hang (a collective that never returns on some rank, a kernel that never ends), the watchdog
+    # The record is complete from here on: the headline stands; with --full the CPU baseline is taken next and the side measurements
+    # fill `extra` in place.  Should one of them hang (a collective that never returns on some rank, a kernel that never ends), the watchdog
     # prints the line as it is after --extras-budget seconds and ends the process with WATCHDOG_EXIT: a side measurement never
     # costs the headline, not even by not coming back, and a hang is never reported as a clean run.
     out = {
@@ -1431,14 +1445,13 @@ def main():
         "collective": collective,
         "per_rank": per_rank,
         "cpu_baseline": None,
-        "check": {"failed_members_rank0": n_fail, "Ts_2020_mean_rank0": s_mid["mean"],
-                  "finite_members_2020_rank0": s_mid["count"]},
+        "check": check,
         "extra": extra,
     }
 
     # The CPU leg comes right after the headline and before any extra: whatever happens later (a watchdog print included), the line
-    # carries `cpu_baseline`.
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    # of a --full run carries `cpu_baseline`.
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         try:
             out["cpu_baseline"] = cpu_baseline()
         except Exception as exc:  # noqa: BLE001 -- the GPU figure must not be lost to the CPU leg
@@ -1480,15 +1493,15 @@ def main():
             extra[label] = {"error": f"{type(exc).__name__}: {exc}"[:300]}
             print(f"bench.py: extra {label} failed: {exc}", file=sys.stderr)
 
-    # Every config that is defined on more than one GPU, on ALL ranks (and under the same keys at N = 1): scale_exact_1e6,
+    # --full: every config that is defined on more than one GPU, on ALL ranks (and under the same keys at N = 1): scale_exact_1e6,
     # scale_coupled_fast_1e6, scale_configs3_share, scale_calibrate_sharded_1e5[_per_gpu].  After the headline, which is unchanged.
-    if not args.no_extra and not args.no_scale:
+    if args.full and not args.no_extra and not args.no_scale:
         try:
             scale_extras(args, rank, local_rank, world, torch, dist, tstream, stream, years, extra)
         except Exception as exc:  # noqa: BLE001 -- e.g. a collective that fails because a peer's watchdog has ended it: the headline stands
             print(f"bench.py: rank {rank}: the scale extras stopped: {type(exc).__name__}: {exc}", file=sys.stderr)
 
-    if rank == 0 and world == 1 and not args.no_extra and not args.scale_only:
+    if rank == 0 and world == 1 and args.full and not args.no_extra and not args.scale_only:
         def two_layer_case(members, m, cp):
             e2 = make_ensemble(members, local_rank, 0, 1, m, stream, coupled=cp)
             k = max(3, args.steps // 4)

@@ -1,4 +1,4 @@
-"""profiles/<tag>.txt from `rocprofv3 --kernel-trace --stats -- python3 bench.py`: the stats table,
+"""profiles/<tag>.txt from `rocprofv3 --kernel-trace --stats -- python3 bench.py --full`: the stats table,
 the per-(kernel, grid) averages from kernel_trace.csv (bench.py launches the same kernel at
 several ensemble sizes), and bench.py's own JSON line with its HIP-event kernel time."""
 import collections

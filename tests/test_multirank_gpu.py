@@ -104,7 +104,7 @@ def test_bench_two_ranks_with_and_without_a_launcher():
     ranks itself) and under torch.distributed.run -- each print ONE valid line; with two ranks the whole-job value is about twice
     one rank's share of it (both ranks on this box's one GPU: they take turns on the card), and every rank's own kernel time is in
     the line.  Collectives over gloo here; on the driver's 8-GPU node the same code path runs RCCL."""
-    small = ["--steps", "3", "--warmup", "1", "--no-extra", "--no-cpu-baseline", "--members", "20000"]
+    small = ["--steps", "3", "--warmup", "1", "--full", "--no-extra", "--no-cpu-baseline", "--members", "20000"]
     one, full = _bench_line(["--gpus", "1", *small], {})
     assert one["n_gpus"] == 1 and one["value"] > 0 and one["per_rank"]["kernel_ms"][0] > 0
     assert one["roofline"]["frac"] > 0 and one["roofline"]["kernel_ms"] > 0 and one["cpu_baseline"] is None
@@ -124,9 +124,25 @@ def test_bench_two_ranks_with_and_without_a_launcher():
         assert len(two["config"]["failed_members_per_rank"]) == 2 and two["config"]["failed_members"] == sum(two["config"]["failed_members_per_rank"])
 
 
+@pytest.mark.gpu
+@pytest.mark.skipif(_gpus() < 1, reason="needs a GPU")
+def test_bench_plain_run_measures_the_headline_alone():
+    """Without --full the bench sets up, warms up, times its steps and prints the line: no CPU baseline, no side measurement, no
+    loss gather and no ensemble check, at one rank and at two -- the headline's keys as a --full run has them."""
+    small = ["--steps", "3", "--warmup", "1", "--members", "20000"]
+    one, full = _bench_line(["--gpus", "1", *small], {})
+    assert one["n_gpus"] == 1 and one["value"] > 0 and one["ms_per_step"] > 0 and one["unit"] == "member-years/s" and one["dtype"] == "f64"
+    assert one["higher_is_better"] is True and one["roofline"]["kernel_ms"] > 0 and one["per_rank"]["kernel_ms"][0] > 0
+    assert one["cpu_baseline"] is None and one["extra"] == {} and full["extra"] == {}
+    assert full["check"] == {"failed_members_rank0": full["config"]["failed_members"]}
+    two, full = _bench_line(["--gpus", "2", *small], {"RSCM_BENCH_BACKEND": "gloo", "RSCM_BENCH_DEVICE": "0"})
+    assert two["n_gpus"] == 2 and two["value"] > 0 and two["collective"]["ranks_seen"] == 2 and len(two["per_rank"]["kernel_ms"]) == 2
+    assert two["extra"] == {} and "loss_gather_ms" not in two["collective"] and "loss_gather" not in full["collective"]
+
+
 SCALE_KEYS = ("scale_exact_1e6", "scale_coupled_fast_1e6", "scale_configs3_share", "scale_calibrate_sharded_1e5",
               "scale_calibrate_sharded_1e5_per_gpu")
-SCALE_SMALL = ["--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--members", "20000", "--scale-members", "30000",
+SCALE_SMALL = ["--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--members", "20000", "--scale-members", "30000",
                "--share-members", "1024", "--share-years", "2", "--scale-walkers", "4096", "--scale-sweeps", "3"]
 
 
@@ -189,10 +205,10 @@ def test_bench_watchdog_keeps_the_headline_when_side_measurements_do_not_finish(
     8-GPU node would otherwise take the headline with it), the watchdog prints the line as it stands and ends the process with
     exit code 3 (bench.WATCHDOG_EXIT: line valid, extras unfinished -- never a clean 0).  Here the budget is simply too short for
     the extras."""
-    line, _ = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--members", "20000", "--extras-budget", "1.5"], {},
+    line, _ = _bench_line(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--members", "20000", "--extras-budget", "1.5"], {},
                           expect_code=3)
     assert line["value"] > 0 and line["n_gpus"] == 1 and "watchdog" in line and "unfinished" in line["watchdog"]
     assert isinstance(line["extra"], dict) and "calibrate_graph_device_1e5_fast" not in line["extra"]
-    two, _ = _bench_line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--members", "20000", "--extras-budget", "1.5"],
+    two, _ = _bench_line(["--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline", "--members", "20000", "--extras-budget", "1.5"],
                          {"RSCM_BENCH_BACKEND": "gloo", "RSCM_BENCH_DEVICE": "0"}, expect_code=3)
     assert two["value"] > 0 and two["n_gpus"] == 2 and "watchdog" in two
