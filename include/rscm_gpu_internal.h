@@ -71,6 +71,12 @@ RSCM_API int rscm_gpu_set_run_plan(int32_t mode);
  * (the guard before the state boxes: the yardstick of tests/test_gpu_two_layer_guard.py).  The same bits either way. */
 RSCM_API int rscm_gpu_set_two_layer_guard(int32_t numerators);
 
+/* Which guard the wavefronts of the calling THREAD's stand-alone EXACT two-layer launches took (csrc/two_layer_body.hpp): copies the
+ * device's counts since the last call into counts[3] (if not null) -- wavefronts with a tag per numerator, with the state tagged at
+ * every sub-step, with the state tagged per chunk of sub-steps (csrc/two_layer_chunk_box.hpp) -- zeroes them, then turns counting on
+ * (enable 1) or off (0) for the calling thread.  Waits for the device.  Counts only; the results are the same bits either way. */
+RSCM_API int rscm_gpu_two_layer_guard_counts(int32_t device_id, int32_t enable, int64_t* counts);
+
 /* 1 if this library was built with -DRSCM_EXPERIMENTS (`make -C rscm_amd/csrc EXPERIMENTS=1`): the environment-variable experiment
  * knobs of csrc/experiment_env.hpp (RSCM_SPLIT_CHUNK / _CHUNK2 / _FIRST, RSCM_LOCKSTEP_SPLIT, RSCM_UDEB_VARIANT) are compiled in.
  * 0 for the shipped library, whose launch plans read only the two variables documented in rscm_gpu.h ("Environment").

@@ -33,6 +33,18 @@ namespace rscm {
 // kernels either branch per division (div_const) or validate a whole model year at once
 // (two_layer.hip).  tests/test_gpu_parity.py checks the identity on random and edge-case
 // operands through rscm_gpu_selftest_div.
+//
+// The wide window.  For a divisor in the narrower box [2^-2, 2^14) the same conditions hold for
+//     |n| in [2^-960, 2^760)                                             "wide numerator window"
+// (two_layer_chunk_box.hpp, kWideDivLo/Hi, kWideNumLo/Hi): the biased exponent of n is at least
+// 63 (> 53), exponent(n) - exponent(d) is at most 761 (< 768), n/d lies in [2^-975, 2^762) and
+// 1/d in (2^-14, 2^2], all normal, so div_scale scales nothing and div_fixup passes the quotient
+// through.  q = n*r is normal and finite; the remainder fma(-d,q,n) is exact, being a multiple
+// of ulp(d)*ulp(q) >= 2^(e_n - 105) >= 2^-1065 with a magnitude below |n|; the correction
+// fma(rem,r,q) rounds once to the quotient.  The EXACT two-layer chunk guard relies on it
+// (two_layer_body.hpp); scripts/two_layer_box_proof.py (check_wide_window) checks these
+// conditions for the header's constants and tests/test_gpu_two_layer_chunk_guard.py the
+// identity on the device, on both sides of every edge.
 // ---------------------------------------------------------------------------------------------
 
 // tag < 0  <=>  biased exponent of x in [512, 1535]: (hi << 1) moves exponent bit 10 to bit 31
@@ -82,7 +94,8 @@ __device__ __forceinline__ double guarded_rcp(double d)
     return r;
 }
 
-// The three-instruction quotient; equals n/d bit for bit inside the two windows.
+// The three-instruction quotient; equals n/d bit for bit inside the divisor and numerator windows, or
+// for a divisor in [2^-2, 2^14) inside the wide numerator window.
 __device__ __forceinline__ double spec_div(double n, double d, double r)
 {
     const double q = n * r;

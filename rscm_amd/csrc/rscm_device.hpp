@@ -348,6 +348,8 @@ struct TwoLayerArgs {
     int32_t first_is_deep;        // which variable's group comes first in the caller's order
     int32_t numerator_guard;      // EXACT: 1 forces the per-numerator guard of every speculative year (test hook,
                                   // rscm_gpu_set_two_layer_guard); 0 guards the sub-step states where the boxes allow it
+    int32_t count_guards;         // EXACT stand-alone launches: 1 counts the guard each wavefront took (test hook,
+                                  // rscm_gpu_two_layer_guard_counts); 0 counts nothing
     const int32_t* obs_tidx;      // [n_obs] ascending
     const int32_t* obs_is_deep;   // [n_obs] 0: Surface Temperature, 1: Deep Ocean Temperature
     const double* obs_value;
@@ -665,6 +667,9 @@ bool launch_group_seq(const GroupTable& table, int32_t n_ops, int64_t n_members,
 
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);
+// the current device's wavefront counts per guard of the counting launches (TwoLayerArgs::count_guards) into out[3] (if not null),
+// then zeroes them; waits for the device first
+hipError_t two_layer_guard_counts(int64_t* out);
 hipError_t launch_coupled(const CoupledArgs& a, int mode, hipStream_t s);
 hipError_t launch_udeb(const UdebArgs& a, hipStream_t s);
 bool udeb_layers_unrolled(int32_t n_layers);  // the layer counts whose columns stay on chip (2 .. kUdebMaxOnChipLayers)

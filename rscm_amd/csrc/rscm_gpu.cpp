@@ -1356,6 +1356,8 @@ void set_run_plan(int32_t mode) { t_run_plan = mode; }
 // Test hook (rscm_gpu_set_two_layer_guard): 1 makes the calling thread's EXACT two-layer launches guard every numerator.
 static thread_local int32_t t_tl_numerator_guard = 0;
 void set_two_layer_guard(int32_t numerators) { t_tl_numerator_guard = numerators; }
+// Test hook (rscm_gpu_two_layer_guard_counts): 1 makes the calling thread's stand-alone EXACT two-layer launches count their guards.
+static thread_local int32_t t_tl_count_guards = 0;
 
 struct MemberSplit {
     bool on = false;
@@ -1468,6 +1470,7 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
         a.h_half = h->h_tl / 2.0;
         a.h_sixth = h->h_tl / 6.0;
         a.numerator_guard = t_tl_numerator_guard;
+        a.count_guards = t_tl_count_guards;
         a.ts = h->series(RSCM_TL_VAR_TS);
         a.td = h->series(RSCM_TL_VAR_TD);
         a.status = h->d_status;
@@ -2203,6 +2206,7 @@ hipError_t launch_loglik(rscm_ens* h)
     a.h_half = h->h_tl / 2.0;
     a.h_sixth = h->h_tl / 6.0;
     a.numerator_guard = t_tl_numerator_guard;
+    a.count_guards = t_tl_count_guards;
     a.ts = h->series(RSCM_TL_VAR_TS);
     a.td = h->series(RSCM_TL_VAR_TD);
     a.status = h->d_status;
@@ -2473,6 +2477,18 @@ int rscm_ens_ocean_fast_info(rscm_ens* h, int32_t* uses_recurrence, double* fit_
     if (uses_recurrence) *uses_recurrence = h->ocean_recur_ok ? 1 : 0;
     if (fit_error) *fit_error = h->ocean_fit_error;
     return RSCM_OK;
+}
+
+int rscm_gpu_two_layer_guard_counts(int32_t device_id, int32_t enable, int64_t* counts)
+{
+    GUARD_BEGIN
+    if (enable != 0 && enable != 1) return fail(RSCM_ERR_INVALID, "guard counting %d (0 off, 1 on)", enable);
+    HIPCHK(hipSetDevice(device_id));
+    hipError_t e = rscm::two_layer_guard_counts(counts);
+    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "two_layer_guard_counts: %s", hipGetErrorString(e));
+    t_tl_count_guards = enable;
+    return RSCM_OK;
+    GUARD_END
 }
 
 int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const double* den,

@@ -40,6 +40,10 @@ namespace rscm {
 
 namespace {
 
+// test hook (rscm_gpu_two_layer_guard_counts): per guard (tl::kGuardNumerators / kGuardStates / kGuardChunks), the wavefronts of the
+// counting launches that took it
+__device__ unsigned long long g_guard_counts[tl::kGuardKinds];
+
 template <int MODE, bool LDS, bool STORE>
 __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 {
@@ -55,7 +59,10 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
-    tl::two_layer_body<MODE, LDS, STORE>(a, lds_forcing, i, a.step_begin, a.step_end);
+    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE>(a, lds_forcing, i, a.step_begin, a.step_end);
+    if constexpr (MODE == 0) {
+        if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
+    }
 }
 
 }  // namespace
@@ -95,6 +102,18 @@ hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s)
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s)
 {
     return launch_impl<false>(a, mode, s);
+}
+
+hipError_t two_layer_guard_counts(int64_t* out)
+{
+    unsigned long long c[tl::kGuardKinds] = {};
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess && out) e = hipMemcpyFromSymbol(c, HIP_SYMBOL(g_guard_counts), sizeof c);
+    if (e != hipSuccess) return e;
+    if (out)
+        for (int k = 0; k < tl::kGuardKinds; ++k) out[k] = (int64_t)c[k];
+    const unsigned long long zero[tl::kGuardKinds] = {};
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_guard_counts), zero, sizeof zero);
 }
 
 }  // namespace rscm

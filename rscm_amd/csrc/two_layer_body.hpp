@@ -8,6 +8,7 @@
 #include "rk4_device.hpp"
 #include "rscm_device.hpp"
 #include "two_layer_box.hpp"
+#include "two_layer_chunk_box.hpp"
 
 namespace rscm {
 namespace tl {
@@ -87,10 +88,11 @@ __device__ __forceinline__ bool positive_in(double x, int lo, int hi)
     return x >= pow2(lo) && x < pow2(hi);
 }
 
-// +0, or a magnitude in the forcing box (-0 is not: it would make a numerator -0)
+// +0, or a magnitude in the forcing box [2^lo, 2^hi) (-0 is not: it would make a numerator -0)
+template <int lo = kForcingLo, int hi = kForcingHi>
 __device__ __forceinline__ bool forcing_in(double f)
 {
-    return (__double_as_longlong(f) == 0) | (box_tag(f, neg_edge(kForcingLo)) < span(kForcingLo, kForcingHi));  // no branch
+    return (__double_as_longlong(f) == 0) | (box_tag(f, neg_edge(lo)) < span(lo, hi));  // no branch
 }
 
 __device__ __forceinline__ bool params_in(const TLConst& p, double h, double half_step)
@@ -103,6 +105,27 @@ __device__ __forceinline__ bool params_in(const TLConst& p, double h, double hal
 }
 
 }  // namespace box
+
+// The chunk guard ("Guarding chunks of sub-steps"): with the narrower boxes of two_layer_chunk_box.hpp every
+// numerator of chunk::kChunkSubSteps consecutive sub-steps stays in spec_div's wide window once the state at the chunk's start is in
+// the chunk's state box, so the state is tagged at every kChunkSubSteps-th sub-step only (scripts/two_layer_box_proof.py, prove_chunk).
+namespace chunk {
+
+static_assert(kWideDivLo >= box::kCsLo && kWideDivHi <= box::kCdHi && kCsLo >= kWideDivLo && kCsHi <= kWideDivHi &&
+                  kCdLo >= kWideDivLo && kCdHi <= kWideDivHi,
+              "the chunk's heat capacities must lie in the wide window's divisor box");
+
+__device__ __forceinline__ bool params_in(const TLConst& p, double h, double half_step, double sixth)
+{
+    using box::positive_in;
+    return positive_in(p.lambda0, kLambda0Lo, kLambda0Hi) &&
+           (__double_as_longlong(p.a) == 0 || positive_in(p.a, kALo, kAHi)) &&
+           positive_in(p.eff_eta, kEffEtaLo, kEffEtaHi) && positive_in(p.eta, kEtaLo, kEtaHi) &&
+           positive_in(p.cs, kCsLo, kCsHi) && positive_in(p.cd, kCdLo, kCdHi) &&
+           positive_in(h, kHLo, kHHi) && positive_in(half_step, kHalfLo, kHalfHi) && positive_in(sixth, kSixthLo, kSixthHi);
+}
+
+}  // namespace chunk
 
 // the sub-step count of the annual axis (h = 0.1): its year body is unrolled
 constexpr int32_t kUnrolledSubSteps = 10;
@@ -190,8 +213,12 @@ __device__ __forceinline__ void lik_consume(const TwoLayerArgs& a, LikAcc& L, in
 // lds_forcing ([n_scen][len]); otherwise read through L2 (table or linked series).
 // Cache: NoCache for the stand-alone kernels; the fused multi-step launch (group.hip) keeps parameters, the
 // state and the linked forcing of the current step in LDS between its steps (rscm_device.hpp, LdsCache).
+// Returns the guard of the wavefront's speculative years (EXACT; the same in every lane): kGuardNumerators, kGuardStates or
+// kGuardChunks; -1 in FAST mode.
+enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuardKinds = 3 };
+
 template <int MODE, bool LDS, bool STORE, class Cache = NoCache>
-__device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
+__device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
                                                int32_t step_end, const Cache& cache = Cache())
 {
     const int32_t len = step_end - step_begin;
@@ -243,6 +270,7 @@ __device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const doub
     double erf_next = forcing_first();
     int32_t m_next = a.nsub[step_begin];
 
+    int32_t guard = -1;
     if constexpr (MODE == 0) {
         TLConst p;
         p.lambda0 = lambda0;
@@ -256,10 +284,14 @@ __device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const doub
         p.rcd = dcd.r;
         // 0 (never "all inside") when a heat capacity is outside the divisor window
         const int32_t acc0 = (dcs.ok && dcd.ok) ? (int32_t)0x80000000 : 0;
-        // one decision per wavefront: every member in the boxes -> the state guard
+        // one decision per wavefront: every member in the boxes -> the state guard; in the chunk boxes as well -> the chunk guard
         const bool guard_states = __all(!a.numerator_guard && box::params_in(p, h, half_step));
-        auto years = [&](auto states) {
-            constexpr bool kStates = decltype(states)::value;
+        const bool guard_chunks = guard_states && __all(chunk::params_in(p, h, half_step, sixth));
+        // kGuard 0: a tag per numerator; 1: the state at every sub-step; kChunkSubSteps: the state at every kGuard-th sub-step
+        auto years = [&](auto guard) {
+            constexpr int32_t kGuard = decltype(guard)::value;
+            constexpr bool kStates = kGuard > 0;
+            constexpr bool kChunks = kGuard > 1;   // the chunk guard covers the unrolled 10-sub-step year only
             for (int32_t n = step_begin; n < step_end; ++n) {
                 const double erf = erf_next;
                 const int32_t m = m_next;
@@ -269,20 +301,31 @@ __device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const doub
                 const double ts0 = ts, td0 = td;
                 bool replay;
                 if constexpr (kStates) {
-                    constexpr uint32_t kEdge = box::neg_edge(box::kStateLo), kSpan = box::span(box::kStateLo, box::kStateHi);
-                    uint32_t acc = box::forcing_in(erf) ? 0u : ~0u;
                     int32_t no_tags = 0;
-                    auto sub_step = [&]() {
-                        acc = max3_u32(acc, box_tag(ts, kEdge), box_tag(td, kEdge));
+                    auto sub_step = [&](uint32_t& acc, uint32_t edge, bool tag) {
+                        if (tag) acc = max3_u32(acc, box_tag(ts, edge), box_tag(td, edge));
                         rk4_step_exact<true, false>(p, erf, h, half_step, sixth, ts, td, no_tags);
                     };
-                    if (m == kUnrolledSubSteps) {
+                    if (kChunks && m == kUnrolledSubSteps) {
+                        // the chunk guard: the state at every kGuard-th sub-step against the chunk's boxes
+                        constexpr uint32_t kEdge = box::neg_edge(chunk::kStateLo), kSpan = box::span(chunk::kStateLo, chunk::kStateHi);
+                        uint32_t acc = box::forcing_in<chunk::kForcingLo, chunk::kForcingHi>(erf) ? 0u : ~0u;
 #pragma unroll
-                        for (int32_t s = 0; s < kUnrolledSubSteps; ++s) sub_step();
+                        for (int32_t s = 0; s < kUnrolledSubSteps; ++s) sub_step(acc, kEdge, s % kGuard == 0);
+                        replay = acc >= kSpan;
                     } else {
-                        for (int32_t s = 0; s < m; ++s) sub_step();
+                        // the state guard: the state at every sub-step against two_layer_box.hpp's boxes -- also the generic loop of a
+                        // wavefront that takes the chunk guard, so that loop replays exactly where it did before the chunk guard
+                        constexpr uint32_t kEdge = box::neg_edge(box::kStateLo), kSpan = box::span(box::kStateLo, box::kStateHi);
+                        uint32_t acc = box::forcing_in(erf) ? 0u : ~0u;
+                        if (m == kUnrolledSubSteps) {
+#pragma unroll
+                            for (int32_t s = 0; s < kUnrolledSubSteps; ++s) sub_step(acc, kEdge, true);
+                        } else {
+                            for (int32_t s = 0; s < m; ++s) sub_step(acc, kEdge, true);
+                        }
+                        replay = acc >= kSpan;
                     }
-                    replay = acc >= kSpan;
                 } else {
                     int32_t acc = acc0;
                     for (int32_t s = 0; s < m; ++s) rk4_step_exact<true>(p, erf, h, half_step, sixth, ts, td, acc);
@@ -309,8 +352,10 @@ __device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const doub
                 }
             }
         };
-        if (guard_states) years(std::true_type());
-        else years(std::false_type());
+        if (guard_chunks) years(std::integral_constant<int32_t, chunk::kChunkSubSteps>());
+        else if (guard_states) years(std::integral_constant<int32_t, 1>());
+        else years(std::integral_constant<int32_t, 0>());
+        guard = guard_chunks ? kGuardChunks : guard_states ? kGuardStates : kGuardNumerators;
     } else {
         double inv_cs;
         const TLFast p = make_fast(lambda0, pa, efficacy, eta, cs, cd, inv_cs);
@@ -342,6 +387,7 @@ __device__ __forceinline__ void two_layer_body(const TwoLayerArgs& a, const doub
                                              : (0.0 + lik.part_s) + lik.part_d;
         a.loglik[i] = lik.bad ? -__builtin_inf() : total;
     }
+    return guard;
 }
 
 }  // namespace tl

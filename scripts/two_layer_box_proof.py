@@ -20,6 +20,12 @@ be +0 (spec_div(+0) = +0 = IEEE; -0 would come out as +0) or lie in [2^-511, 2^5
 are finite (rk4_combine_fused2).  The end of the sub-step needs nothing: it is the next sub-step's start, checked there.
 
     python scripts/two_layer_box_proof.py            # prints the bounds of every numerator; exit status 1 if the proof fails
+
+prove_chunk() makes the same argument for kChunkSubSteps consecutive sub-steps of rscm_amd/csrc/two_layer_chunk_box.hpp, started from
+its state box and NOT re-boxed in between: the states at the start of the second and later sub-steps are the abstract results of the
+RK4 combination y + ((fma(k2, 2, k1) + 2*k3) + k4) * (h/6) (the doubling is exact), and may be +0 where a combination cancels.  Its
+numerators must lie in the wide window that spec_div keeps for boxed divisors (rk4_device.hpp); check_wide_window() checks that window
+against the hardware's conditions for the unscaled division.
 """
 import math
 import os
@@ -28,18 +34,25 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "rscm_amd", "csrc", "two_layer_box.hpp")
+CHUNK_HEADER = os.path.join(ROOT, "rscm_amd", "csrc", "two_layer_chunk_box.hpp")
 
 WINDOW_LO, WINDOW_HI = -511, 513     # numerator window [2^-511, 2^513): biased exponent in [512, 1535]
 DIVISOR_LO, DIVISOR_HI = -128, 129   # divisor window [2^-128, 2^129)
 MIN_EXP = -1022 + 60                 # lower bounds must stay this far above the denormals
 
 
-def read_boxes(path=HEADER):
-    """{name: (lo, hi)} from the constexpr pairs of the header (kXxxLo = a, kXxxHi = b)."""
+def read_constants(path):
+    """{name: value} of the header's `constexpr int kXxx = n` constants."""
     text = open(path).read()
     vals = {}
     for line in re.findall(r"^\s*constexpr\s+int\s+([^;]*);", text, re.M):
         vals.update((m.group(1), int(m.group(2))) for m in re.finditer(r"k(\w+)\s*=\s*(-?\d+)", line))
+    return vals
+
+
+def read_boxes(path=HEADER):
+    """{name: (lo, hi)} from the constexpr pairs of the header (kXxxLo = a, kXxxHi = b)."""
+    vals = read_constants(path)
     boxes = {}
     for k, v in vals.items():
         if k.endswith("Lo"):
@@ -133,14 +146,15 @@ def div(n, dlo, dhi):
     return V(set(n.kinds), n.lo - dhi, _up(n.hi / math.ldexp(1.0, dlo)))
 
 
-def check_numerator(name, x):
+def check_numerator(name, x, window=(WINDOW_LO, WINDOW_HI)):
+    lo, hi = window
     if "-0" in x.kinds:
         raise ProofError(f"{name} may be -0")
     if x.nonzero():
-        if x.lo < WINDOW_LO:
-            raise ProofError(f"{name} may be as small as 2^{x.lo}, below 2^{WINDOW_LO}")
-        if not x.hi < math.ldexp(1.0, WINDOW_HI):
-            raise ProofError(f"{name} may reach {x.hi!r}, not below 2^{WINDOW_HI}")
+        if x.lo < lo:
+            raise ProofError(f"{name} may be as small as 2^{x.lo}, below 2^{lo}")
+        if not x.hi < math.ldexp(1.0, hi):
+            raise ProofError(f"{name} may reach {x.hi!r}, not below 2^{hi}")
 
 
 def prove(boxes, log=None):
@@ -188,6 +202,77 @@ def prove(boxes, log=None):
     return out
 
 
+def check_wide_window(boxes):
+    """The wide numerator window [2^nlo, 2^nhi) for divisors d in [2^dlo, 2^dhi) (both positive powers of two apart from the edges)
+    against the conditions under which v_div_scale_f64 leaves n and d unscaled and v_div_fixup_f64 passes the quotient through
+    (rk4_device.hpp): d and 1/d normal, exponent(n) - exponent(d) < 768, n/d normal, biased exponent of n above 53.  The last one is
+    also what makes the remainder fma(-d, q, n) exact: it is a multiple of ulp(d) * ulp(q) >= 2^(e_n - 1 - 104) >= 2^-1074."""
+    dlo, dhi = boxes["WideDiv"]
+    nlo, nhi = boxes["WideNum"]
+    if dlo < DIVISOR_LO or dhi > DIVISOR_HI:
+        raise ProofError(f"wide divisor box [2^{dlo}, 2^{dhi}) leaves the divisor window")
+    if nlo - 1 + 1023 <= 53:
+        raise ProofError(f"numerators down to 2^{nlo} would be scaled (biased exponent <= 53)")
+    if (nhi - 1) - dlo >= 768:
+        raise ProofError(f"numerators up to 2^{nhi} against divisors from 2^{dlo}: exponent difference reaches 768")
+    if nlo - dhi < -1022 + 8:
+        raise ProofError(f"quotients down to 2^{nlo - dhi} come too close to the denormals")
+    for name in ("Cs", "Cd"):
+        lo, hi = boxes[name]
+        if lo < dlo or hi > dhi:
+            raise ProofError(f"{name} box [2^{lo}, 2^{hi}) leaves the wide divisor box [2^{dlo}, 2^{dhi})")
+
+
+def prove_chunk(boxes, n_sub=None, log=None):
+    """Raise ProofError unless every numerator of n_sub (default: the header's kChunkSubSteps) consecutive sub-steps started inside
+    the chunk boxes is +0 or inside the wide window and every 2*k2, 2*k3 is finite; return the numerators' abstract values."""
+    b = boxes
+    if n_sub is None:
+        n_sub = read_constants(CHUNK_HEADER)["ChunkSubSteps"]
+    check_wide_window(b)
+    for name, (lo, hi) in b.items():
+        if lo >= hi:
+            raise ProofError(f"{name} box [2^{lo}, 2^{hi}) is empty")
+    window = b["WideNum"]
+    lam0 = positive_box(*b["Lambda0"])
+    pa = positive_box(*b["A"], zero=True)
+    ee = positive_box(*b["EffEta"])
+    eta = positive_box(*b["Eta"])
+    erf = magnitude_box(*b["Forcing"], zero=True)
+    h, half, sixth = positive_box(*b["H"]), positive_box(*b["Half"]), positive_box(*b["Sixth"])
+    two = V({"+"}, 1, 2.0)                            # the exact doubling of rk4_combine_fused2
+    ts = magnitude_box(*b["State"])
+    td = magnitude_box(*b["State"])
+    cs, cd = b["Cs"], b["Cd"]
+    out = {}
+
+    def rhs(tag, x, y):
+        diff = sub(x, y)
+        lam = sub(lam0, mul(pa, x))
+        num_s = sub(sub(erf, mul(lam, x)), mul(ee, diff))
+        num_d = mul(eta, diff)
+        for nm, v in ((f"num_s[{tag}]", num_s), (f"num_d[{tag}]", num_d)):
+            check_numerator(nm, v, window)
+            out[nm] = v
+            if log:
+                log(f"{nm:12s} {sorted(v.kinds)}  nonzero >= 2^{v.lo}  <= {v.hi:.4g} (2^{math.log2(v.hi):.1f})")
+        return div(num_s, *cs), div(num_d, *cd)
+
+    def combine(y, k1, k2, k3, k4):
+        return add(y, mul(add(add(add(k1, mul(k2, two)), mul(k3, two)), k4), sixth))
+
+    for s in range(n_sub):
+        k1s, k1d = rhs(f"{s}.1", ts, td)
+        k2s, k2d = rhs(f"{s}.2", add(ts, mul(k1s, half)), add(td, mul(k1d, half)))
+        k3s, k3d = rhs(f"{s}.3", add(ts, mul(k2s, half)), add(td, mul(k2d, half)))
+        k4s, k4d = rhs(f"{s}.4", add(ts, mul(k3s, h)), add(td, mul(k3d, h)))
+        for nm, k in (("k2s", k2s), ("k2d", k2d), ("k3s", k3s), ("k3d", k3d)):
+            if not 2.0 * k.hi < math.inf:
+                raise ProofError(f"2*{nm} of sub-step {s} may overflow")
+        ts, td = combine(ts, k1s, k2s, k3s, k4s), combine(td, k1d, k2d, k3d, k4d)
+    return out
+
+
 def main():
     boxes = read_boxes()
     for k, (lo, hi) in sorted(boxes.items()):
@@ -198,6 +283,18 @@ def main():
         print(f"FAILED: {e}")
         return 1
     print("every numerator is +0 or inside [2^-511, 2^513); 2*k2 and 2*k3 are finite")
+    chunk = read_boxes(CHUNK_HEADER)
+    n_sub = read_constants(CHUNK_HEADER)["ChunkSubSteps"]
+    print(f"\nchunks of {n_sub} sub-steps:")
+    for k, (lo, hi) in sorted(chunk.items()):
+        print(f"{k:8s} [2^{lo}, 2^{hi})")
+    try:
+        prove_chunk(chunk, log=print)
+    except ProofError as e:
+        print(f"FAILED: {e}")
+        return 1
+    lo, hi = chunk["WideNum"]
+    print(f"every numerator of {n_sub} sub-steps is +0 or inside [2^{lo}, 2^{hi}); 2*k2 and 2*k3 are finite")
     return 0
 
 
