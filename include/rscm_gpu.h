@@ -81,8 +81,10 @@ extern "C" {
  *      rscm_ens_select_begin_weighted
  *   8  anomalies, per-member indicators and exceedance: rscm_ens_set_baseline, rscm_ens_set_baseline_values,
  *      rscm_ens_baseline_devptr, rscm_ens_clear_baseline, rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex,
- *      rscm_ens_member_indicators, rscm_ens_quantile_vectors, rscm_ens_select_begin_vectors, rscm_ens_exceedance */
-#define RSCM_GPU_ABI_MINOR 8
+ *      rscm_ens_member_indicators, rscm_ens_quantile_vectors, rscm_ens_select_begin_vectors, rscm_ens_exceedance
+ *   9  likelihoods against anomalies from a reference period: rscm_ens_loglik_ref, rscm_ens_loglik_ref_device,
+ *      rscm_ens_run_loglik_ref, rscm_ens_run_loglik_ref_device, rscm_sampler_set_reference */
+#define RSCM_GPU_ABI_MINOR 9
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -612,6 +614,42 @@ RSCM_API int rscm_ens_run_loglik(rscm_ens* h, int32_t n_obs, const int32_t* obs_
 RSCM_API int rscm_ens_run_loglik_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var,
                                         const int32_t* obs_tidx, const double* obs_value,
                                         const double* obs_sigma, int32_t normalize, void** out_dev);
+/* ---- likelihoods against anomalies from a reference period (ABI minor 9) ------------------------
+ * Observed warming is published as an anomaly from a reference period (relative to 1850-1900); a member's own mean over that
+ * period differs from member to member, so the shift belongs to the model side.  Reference periods travel as parallel arrays, one
+ * entry per variable that has one (a variable at most once; one without an observation: RSCM_ERR_INVALID): the rows ref_begin[e],
+ * ref_begin[e] + ref_stride[e], ... < ref_end[e] of variable ref_var[e] -- the row convention of rscm_ens_set_baseline.  For member
+ * i and such a variable
+ *     b[i] = the sum of the member's values over the reference rows in row order (f64, no FMA) divided by the row count:
+ *            exactly the bits rscm_ens_set_baseline produces,
+ *     model value at an observation = x[i](t_obs) - b[i], one IEEE subtraction: the bits of RSCM_SELECT_ANOMALY,
+ * and from there on the expressions and summation order of rscm_ens_loglik.  A variable without a period is scored as by
+ * rscm_ens_loglik; two variables may have different periods; a member whose b is not finite is a failed member (-inf).  A reference
+ * row beyond the current time index gives -inf for every member and one that is not resident RSCM_ERR_STATE, both as for an
+ * observation row.  The handle's own baseline (rscm_ens_set_baseline) is neither read nor changed.  With n_ref == 0 each call
+ * is its counterpart without _ref.
+ *
+ * rscm_ens_loglik_ref / _device: the stored series, any kind and any resident storage layout. */
+RSCM_API int rscm_ens_loglik_ref(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
+                                 const double* obs_value, const double* obs_sigma, int32_t normalize, int32_t n_ref,
+                                 const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
+                                 const int32_t* ref_stride, double* out);
+RSCM_API int rscm_ens_loglik_ref_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
+                                        const double* obs_value, const double* obs_sigma, int32_t normalize, int32_t n_ref,
+                                        const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
+                                        const int32_t* ref_stride, void** out_dev);
+/* The fused two-layer run + likelihood with reference periods, under the restrictions of rscm_ens_run_loglik: the value of
+ * rscm_ens_run followed by rscm_ens_loglik_ref, bit for bit, in both arithmetic modes; no series row is written, the time index
+ * stays 0.  Each thread sums its member's reference rows while it steps; the model values of the observations at rows up to a
+ * period's last wait in a handle-owned scratch (8 bytes per member each, written once and read once) until that row has formed b. */
+RSCM_API int rscm_ens_run_loglik_ref(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
+                                     const double* obs_value, const double* obs_sigma, int32_t normalize, int32_t n_ref,
+                                     const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
+                                     const int32_t* ref_stride, double* out);
+RSCM_API int rscm_ens_run_loglik_ref_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
+                                            const double* obs_value, const double* obs_sigma, int32_t normalize, int32_t n_ref,
+                                            const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
+                                            const int32_t* ref_stride, void** out_dev);
 /* ---- device stretch-move sampler ------------------------------------------------------------
  * EnsembleSampler::run (crates/rscm-calibrate/src/sampler/ensemble.rs:496-547) with StretchMove
  * (sampler/moves.rs:40-125) and the ParameterSet prior kept on the GPU: per half-ensemble update
@@ -693,6 +731,13 @@ RSCM_API int rscm_sampler_destroy(rscm_sampler* s);
  * launches.  This is how ensembles of the reference's usual size (tens of walkers) fill a GPU:
  * thousands of them side by side, e.g. for an R-hat across independent runs.  Default 1. */
 RSCM_API int rscm_sampler_set_groups(rscm_sampler* s, int32_t n_groups);
+/* Reference periods for the sampler's observations (see rscm_ens_loglik_ref), after any of the three rscm_sampler_create* calls and
+ * before rscm_sampler_set_positions (RSCM_ERR_STATE once positions are set).  ref_owner: the handle index of each period's variable
+ * for a graph sampler, NULL otherwise.  A fused evaluator's launches, and a graph's lock-step runs, then end at the later of the
+ * last observed index and the last reference row.  Every rank of a sharded sampler is given the same periods.  n_ref == 0 removes
+ * them. */
+RSCM_API int rscm_sampler_set_reference(rscm_sampler* s, int32_t n_ref, const int32_t* ref_owner, const int32_t* ref_var,
+                                        const int32_t* ref_begin, const int32_t* ref_end, const int32_t* ref_stride);
 /* positions[n_walkers][n_dims] row-major (the Chain layout); scores every walker and zeroes the
  * acceptance counters. */
 RSCM_API int rscm_sampler_set_positions(rscm_sampler* s, const double* positions);

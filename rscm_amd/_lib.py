@@ -297,6 +297,12 @@ SIGNATURES = {
     "rscm_ens_run_loglik": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, _dp]),
     "rscm_ens_loglik_device": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.POINTER(C.c_void_p)]),
     "rscm_ens_run_loglik_device": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.POINTER(C.c_void_p)]),
+    "rscm_ens_loglik_ref": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.c_int32, _ip, _ip, _ip, _ip, _dp]),
+    "rscm_ens_run_loglik_ref": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.c_int32, _ip, _ip, _ip, _ip, _dp]),
+    "rscm_ens_loglik_ref_device": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.c_int32, _ip, _ip, _ip, _ip,
+                                             C.POINTER(C.c_void_p)]),
+    "rscm_ens_run_loglik_ref_device": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _dp, C.c_int32, C.c_int32, _ip, _ip, _ip, _ip,
+                                                 C.POINTER(C.c_void_p)]),
     "rscm_ens_status_devptr": (C.c_int, [_h, C.POINTER(C.c_void_p)]),
     "rscm_ens_quantile_series": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp]),
     "rscm_ens_summary_series": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, _dp]),
@@ -337,6 +343,7 @@ SIGNATURES = {
     "rscm_sampler_sync": (C.c_int, [_h]),
     "rscm_sampler_destroy": (C.c_int, [_h]),
     "rscm_sampler_set_groups": (C.c_int, [_h, C.c_int32]),
+    "rscm_sampler_set_reference": (C.c_int, [_h, C.c_int32, _ip, _ip, _ip, _ip, _ip]),
     "rscm_sampler_set_positions": (C.c_int, [_h, _dp]),
     "rscm_sampler_iterate": (C.c_int, [_h, C.c_int32]),
     "rscm_sampler_last_ms": (C.c_int, [_h, C.POINTER(C.c_float)]),

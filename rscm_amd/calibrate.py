@@ -241,12 +241,27 @@ class Observation:
 
 
 class VariableTarget:
+    """target.rs:63-145.  ``reference_period``: ``None``, or ``(start, end)`` inclusive at both ends -- the observations are
+    anomalies from the model's own mean over that period ("Reference periods")."""
+
     def __init__(self, name: str):
         self.name = name
         self.observations: List[Observation] = []
+        self.reference_period: Optional[Tuple[float, float]] = None
 
     def add(self, time, value, uncertainty) -> "VariableTarget":
         self.observations.append(Observation(time, value, uncertainty))
+        return self
+
+    def add_relative(self, time, value, relative_uncertainty) -> "VariableTarget":
+        """``uncertainty = |value| * relative_uncertainty`` (target.rs:128-136); a zero value raises like any non-positive one."""
+        return self.add(time, value, abs(float(value)) * float(relative_uncertainty))
+
+    def with_reference_period(self, start, end) -> "VariableTarget":
+        start, end = float(start), float(end)
+        if not start <= end:
+            raise ValueError(f"Reference period start ({start}) must not be after its end ({end})")
+        self.reference_period = (start, end)
         return self
 
 
@@ -261,6 +276,14 @@ class Target:
 
     def add_observation(self, variable: str, time, value, uncertainty) -> "Target":
         self.add_variable(variable).add(time, value, uncertainty)
+        return self
+
+    def add_observation_relative(self, variable: str, time, value, relative_error) -> "Target":
+        self.add_variable(variable).add_relative(time, value, relative_error)
+        return self
+
+    def set_reference_period(self, variable: str, start, end) -> "Target":
+        self.add_variable(variable).with_reference_period(start, end)
         return self
 
     def get_variable(self, name: str) -> Optional[VariableTarget]:
@@ -281,6 +304,12 @@ def time_key(t: float) -> str:
     return f"{t:.6f}"
 
 
+def reference_rows(times, period) -> List[int]:
+    """The contiguous rows ``n`` of a time axis with ``start <= times[n] <= end`` (possibly none)."""
+    start, end = period
+    return [n for n, t in enumerate(times) if start <= t <= end]
+
+
 class GaussianLikelihood:
     """likelihood.rs:167-250.  ``ln_likelihood`` is the host form over the reference's
     ``{variable: {time: value}}`` output; the batch form runs on the device."""
@@ -289,11 +318,32 @@ class GaussianLikelihood:
         self.normalize = bool(normalize)
 
     def ln_likelihood(self, output: Dict[str, Dict[float, float]], target: Target) -> float:
+        """A variable with a ``reference_period`` is scored as an anomaly: ``b`` = the sum of the output's values at its times
+        inside the period, in ascending time order, divided by their count; the model value at an observation is ``x - b``.  This
+        form sees only the times the output holds: ``ModelRunner.run`` leaves NaN values out of its output, so a reference row
+        that is NaN is absent here and averaged over, where the batch forms (``log_likelihood_batch``, the device sampler), which
+        know the axis, fail the member.  A non-finite value present inside the period raises, as one at an observed time does; so
+        does a period that holds none of the output's times (``KeyError``, like a missing observation time)."""
         total = 0.0
         for name, vt in target.variables():
             if name not in output:
                 raise KeyError(f"Model output missing variable: {name}")
             keyed = {time_key(t): v for t, v in output[name].items()}
+            base = None
+            if vt.reference_period is not None:
+                start, end = vt.reference_period
+                inside = sorted(t for t in output[name] if start <= t <= end)
+                if not inside:
+                    raise KeyError(f"Model output missing every time of the reference period {start}-{end} for variable {name}")
+                acc = None
+                for t in inside:
+                    x = output[name][t]
+                    if not math.isfinite(x):
+                        raise ValueError(f"Model output contains non-finite value for {name} at time {t} (reference period)")
+                    acc = x if acc is None else acc + x
+                base = acc / len(inside)
+                if not math.isfinite(base):
+                    raise ValueError(f"Reference-period mean of {name} is not finite")
             ln_l = 0.0
             for obs in vt.observations:
                 k = time_key(obs.time)
@@ -302,6 +352,8 @@ class GaussianLikelihood:
                 m = keyed[k]
                 if not math.isfinite(m):
                     raise ValueError(f"Model output contains non-finite value for {name} at time {obs.time}")
+                if base is not None:
+                    m = m - base
                 residual = obs.value - m
                 chi = (residual * residual) / (obs.uncertainty * obs.uncertainty)
                 l = -0.5 * chi
@@ -509,6 +561,15 @@ class ModelRunner:
                 ot.append(idx)
                 val.append(obs.value)
                 sig.append(obs.uncertainty)
+        # reference periods as rows of the model axis; a period with no row there is a missing time: -inf for every member
+        reference = {}
+        for name, vt in target.variables():
+            if vt.reference_period is not None and vt.observations:
+                rows = reference_rows(probe._axis.values(), vt.reference_period)
+                if not rows:
+                    return np.full(p.shape[0], -np.inf)
+                reference[name] = (rows[0], rows[-1] + 1)
+        ref_kw = {"reference": reference} if reference else {}   # without a period: the calls as they were
         # Multi-GPU: every rank holds the same batch (same seeds => same proposals, nothing to
         # scatter), evaluates its contiguous block of members and all-gathers 8 B per member.
         from .distributed import gather_members, is_distributed, shard_bounds
@@ -522,22 +583,25 @@ class ModelRunner:
         elif fused:  # run + likelihood in one kernel, nothing written to HBM but ln L
             m = self._lik_model(p.shape[0])
             self._load(m, p)
-            local = m.ensemble.run_loglik(ov, ot, val, sig, likelihood.normalize, on_device=is_distributed())
+            local = m.ensemble.run_loglik(ov, ot, val, sig, likelihood.normalize, on_device=is_distributed(), **ref_kw)
         elif self._graph:
             # observations grouped by the ensemble that holds their variable, in the target's order;
             # a member that fails anywhere is -inf (-inf + finite)
             m = self._run(p)
             local = np.zeros(p.shape[0])
-            groups: Dict[int, Tuple[object, list]] = {}
+            groups: Dict[int, Tuple[object, list, dict]] = {}
             for k, name in enumerate(ov):
                 ens, vid = m.variable_home(name)
-                groups.setdefault(id(ens), (ens, []))[1].append((vid, ot[k], val[k], sig[k]))
-            for ens, obs in groups.values():
+                g = groups.setdefault(id(ens), (ens, [], {}))
+                g[1].append((vid, ot[k], val[k], sig[k]))
+                if name in reference:
+                    g[2][vid] = reference[name]
+            for ens, obs, ref in groups.values():
                 v, t_, x, s = zip(*obs)
-                local = local + ens.loglik(list(v), list(t_), list(x), list(s), likelihood.normalize)
+                local = local + ens.loglik(list(v), list(t_), list(x), list(s), likelihood.normalize, **({"reference": ref} if ref else {}))
         else:
             m = self._run(p)
-            local = m.ensemble.loglik(ov, ot, val, sig, likelihood.normalize, on_device=is_distributed())
+            local = m.ensemble.loglik(ov, ot, val, sig, likelihood.normalize, on_device=is_distributed(), **ref_kw)
         return gather_members(local, n_total) if is_distributed() else local
 
     def close(self) -> None:
@@ -946,6 +1010,19 @@ class DeviceEnsembleSampler:
                 ov.append(model.ensemble.var_ids[name]), ot.append(idx), val.append(obs.value), sig.append(obs.uncertainty)
         return np.array(ov, dtype=np.int32), np.array(ot, dtype=np.int32), L.f64(val), L.f64(sig)
 
+    def _reference(self, model: Model, var_of):
+        """The target's reference periods as rows of the model axis: ``[(var_of(name), t_begin, t_end, 1), ...]``; a period with
+        no row on the axis is a missing time (``KeyError``)."""
+        out = []
+        for name, vt in self.target.variables():
+            if vt.reference_period is None or not vt.observations:
+                continue
+            rows = reference_rows(model._axis.values(), vt.reference_period)
+            if not rows:
+                raise KeyError(f"Model output missing every time of the reference period {vt.reference_period} of {name}")
+            out.append((var_of(name), rows[0], rows[-1] + 1, 1))
+        return out
+
     def run(self, n_iterations: int, init: "WalkerInit", thin: int = 1, n_walkers: Optional[int] = None,
             rng: Optional[np.random.Generator] = None, seed: int = 0, n_groups: int = 1,
             shard: Optional[bool] = None) -> "Chain":
@@ -1007,6 +1084,11 @@ class DeviceEnsembleSampler:
                                                   L.dptr(phi), len(ov), L.iptr(oo), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
                                                   1 if self.likelihood.normalize else 0, self.a,
                                                   C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), rank, world, C.byref(h)))
+
+            def owner_and_var(name):
+                owner_ens, vid = model.variable_home(name)
+                return next(j for j, e in enumerate(handles) if e is owner_ens), vid
+            ref = [(o, v, b, e, st) for (o, v), b, e, st in self._reference(model, owner_and_var)]
         else:
             two_layer = self.runner._model(1).ensemble.kind == L.KIND_TWO_LAYER
             model = self.runner._lik_model(n_eval) if two_layer else self.runner._model(n_eval)
@@ -1019,7 +1101,12 @@ class DeviceEnsembleSampler:
                                                     L.dptr(pa), L.dptr(pb), L.dptr(plo), L.dptr(phi), len(ov), L.iptr(ov), L.iptr(ot),
                                                     L.dptr(val), L.dptr(sig), 1 if self.likelihood.normalize else 0, self.a,
                                                     C.c_uint64(seed & 0xFFFFFFFFFFFFFFFF), rank, world, C.byref(h)))
+            ref = [(None,) + r for r in self._reference(model, lambda name: model.ensemble.var_ids[name])]
         try:
+            if ref:  # every rank of a sharded sampler is given the same periods
+                ro, rv, rb, re_, rs = (np.array(x, dtype=np.int32) if x[0] is not None else None for x in zip(*ref))
+                L.check(lib.rscm_sampler_set_reference(h, len(ref), None if ro is None else L.iptr(ro), L.iptr(rv), L.iptr(rb),
+                                                       L.iptr(re_), L.iptr(rs)))
             if world > 1 or (is_distributed() and shard is not False):
                 return self._run_sharded(lib, h, ens, pos, n_iterations, thin, n_walkers, world)
             if n_groups != 1:

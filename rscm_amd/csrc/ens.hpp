@@ -162,6 +162,15 @@ struct rscm_ens {
     int32_t obs_n = 0, obs_normalize = 0, obs_first_is_deep = 0;
     int32_t obs_last_tidx = 0;        // the latest time index any prepared observation refers to
     bool loglik_stop_at_last_obs = false;  // fused run+likelihood launches end there (the device sampler: only ln L is used)
+    // reference periods of the prepared observations (prepare_ref; cleared by prepare_obs)
+    std::vector<int32_t> obs_merged_tidx, obs_merged_deep;   // host copy of the merged observation order
+    bool ref_active = false;
+    rscm::TwoLayerRefArgs ref{};
+    int32_t ref_last_row = 0;         // the latest reference row of any period
+    int32_t* d_ref_slot = nullptr;    // [obs_n]
+    size_t ref_slot_capacity = 0;
+    double* d_defer = nullptr;        // [n_deferred][N] model values waiting for their variable's b
+    size_t defer_capacity = 0;        // in rows
 
     hipStream_t stream = nullptr;
     bool own_stream = false;
@@ -309,6 +318,18 @@ int window_flush(WindowDeferral* d, hipStream_t stream);
 extern "C" {
 int prepare_obs(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value, const double* obs_sigma,
                 int32_t normalize);
+// reference periods for the observations prepare_obs holds (n_ref == 0: none): validates, lays out the deferred observations' scratch
+int prepare_ref(rscm_ens* h, int32_t n_ref, const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end, const int32_t* ref_stride);
+// shapes of a reference-period list on an axis of T rows: ranges as rscm_ens_set_baseline, each variable at most once
+// (per owner where ref_owner is given: the graph sampler)
+int check_reference(int32_t T, int32_t n_ref, const int32_t* ref_owner, const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
+                    const int32_t* ref_stride);
+// The stored-series likelihood with reference periods, ready to launch: observation j reads obs_rows[j] and belongs to group grp[j];
+// obs_ref[j] is its group's reference entry (-1: none), entry e averages ref_rows[ref_off[e] .. ref_off[e + 1]).  *d_blob (hipFree'd by
+// the caller) holds the tables *args points into.
+int upload_loglik_ref(int32_t n_obs, const double* const* obs_rows, const double* obs_value, const double* obs_sigma, const int32_t* grp,
+                      const int32_t* obs_ref, int32_t n_ref, const int32_t* ref_off, const double* const* ref_rows, int32_t normalize,
+                      int64_t n_members, double* out, void** d_blob, rscm::LoglikRefArgs* args);
 int check_loglik_ready(rscm_ens* h);
 hipError_t launch_loglik(rscm_ens* h);   // asynchronous, with the prepared observations; fills h->d_loglik
 }

@@ -150,6 +150,58 @@ __global__ __launch_bounds__(kBlock) void loglik_kernel(LoglikArgs a)
     a.out[i] = bad ? -__builtin_inf() : total;
 }
 
+// The same with reference periods ("Reference periods"): at the start of a group that has one the thread forms its
+// member's b -- the reference rows summed in row order, divided by their count: the bits of rscm_ens_set_baseline -- and scores the
+// group's observations with m - b (one subtraction: RSCM_SELECT_ANOMALY's bits).  A non-finite b fails the member.  Row reads are
+// coalesced [row][member], as the observation rows are.
+__global__ __launch_bounds__(kBlock) void loglik_ref_kernel(LoglikRefArgs r)
+{
+    const LoglikArgs& a = r.lik;
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_members) return;
+    const double ln_2pi = 1.8378770664093453;  // ln(2*pi) rounded to f64
+    double total = 0.0, partial = 0.0, b = 0.0;
+    bool bad = false, anom = false;
+    for (int32_t j = 0; j < a.n_obs; ++j) {
+        const bool first = j == 0 || a.obs_group[j] != a.obs_group[j - 1];
+        if (first && j > 0) {
+            total += partial;
+            partial = 0.0;
+        }
+        if (first) {
+            const int32_t e = r.obs_ref[j];
+            anom = e >= 0;
+            if (anom) {
+                const int32_t k0 = r.ref_off[e], k1 = r.ref_off[e + 1];
+                double sum = r.ref_rows[k0][i];
+                for (int32_t k = k0 + 1; k < k1; ++k) sum += r.ref_rows[k][i];
+                b = sum / (double)(k1 - k0);
+                if (!is_finite(b)) {
+                    bad = true;
+                    break;
+                }
+            }
+        }
+        double m = a.obs_series[j][i];
+        if (!is_finite(m)) {
+            bad = true;
+            break;
+        }
+        if (anom) m = m - b;
+        const double sigma = a.obs_sigma[j];
+        const double residual = a.obs_value[j] - m;
+        const double chi = (residual * residual) / (sigma * sigma);
+        double l = -0.5 * chi;
+        if (a.normalize) {
+            l -= 0.5 * ln_2pi;
+            l -= log(sigma);
+        }
+        partial += l;
+    }
+    total += partial;
+    a.out[i] = bad ? -__builtin_inf() : total;
+}
+
 // ---- summaries: count/sum/min/max over finite members ---------------------------------------
 struct Stat4 {
     double cnt, sum, mn, mx;
@@ -400,6 +452,14 @@ hipError_t launch_loglik(const LoglikArgs& a, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
     hipLaunchKernelGGL(loglik_kernel, dim3((unsigned)((a.n_members + kBlock - 1) / kBlock)),
+                       dim3(kBlock), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_loglik_ref(const LoglikRefArgs& a, hipStream_t s)
+{
+    if (a.lik.n_members <= 0) return hipSuccess;
+    hipLaunchKernelGGL(loglik_ref_kernel, dim3((unsigned)((a.lik.n_members + kBlock - 1) / kBlock)),
                        dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }

@@ -357,6 +357,17 @@ struct TwoLayerArgs {
     double* loglik;               // [N]
 };
 
+// Reference periods of the fused likelihood (launch_two_layer_loglik_ref; DESIGN.md section 7, "Reference periods"), index 0: Surface
+// Temperature, 1: Deep Ocean Temperature.  A variable with on[v] is scored as the anomaly from the member's own mean b over the rows
+// begin[v], begin[v] + stride[v], ... <= last[v]: the thread sums those rows while it steps; the model values of that variable's
+// observations at rows <= last[v] wait in `defer` until the last reference row has formed b.
+struct TwoLayerRefArgs {
+    int32_t on[2];
+    int32_t begin[2], last[2], stride[2], count[2];
+    const int32_t* obs_slot;   // [n_obs] (the merged order of TwoLayerArgs::obs_tidx): row of `defer`, -1 for an observation scored on the fly
+    double* defer;             // [n_deferred][N] handle-owned scratch
+};
+
 // Coupled chain CarbonCycle -> CO2ERF -> Sum -> TwoLayer over steps [step_begin, step_end).
 struct CoupledArgs {
     int64_t n_members;
@@ -616,6 +627,15 @@ struct LoglikArgs {
     double* out;                      // [N]
 };
 
+// loglik_kernel with reference periods (loglik_ref_kernel): the observations of a group whose obs_ref is r >= 0 are scored as anomalies
+// from b = (the sum of the rows ref_rows[ref_off[r] .. ref_off[r + 1]) in that order) / their count.
+struct LoglikRefArgs {
+    LoglikArgs lik;
+    const int32_t* obs_ref;            // [n_obs] reference entry of the observation's group, -1: none
+    const int32_t* ref_off;            // [n_ref + 1] offsets into ref_rows
+    const double* const* ref_rows;     // device pointers to the [N] reference rows
+};
+
 // One component of a fused lock-step launch (csrc/group.hip): the arguments its own kernel would get;
 // the step range comes with the launch.  The table of ops lives in device memory and is read with
 // scalar loads.
@@ -667,6 +687,7 @@ bool launch_group_seq(const GroupTable& table, int32_t n_ops, int64_t n_members,
 
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);
+hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s);
 // the current device's wavefront counts per guard of the counting launches (TwoLayerArgs::count_guards) into out[3] (if not null),
 // then zeroes them; waits for the device first
 hipError_t two_layer_guard_counts(int64_t* out);
@@ -698,6 +719,7 @@ hipError_t launch_sampler_accept(const SamplerArgs& a, hipStream_t s);
 hipError_t launch_sampler_pack(const SamplerArgs& a, hipStream_t s);
 hipError_t launch_sampler_unpack(const SamplerArgs& a, hipStream_t s);
 hipError_t launch_loglik(const LoglikArgs& a, hipStream_t s);
+hipError_t launch_loglik_ref(const LoglikRefArgs& a, hipStream_t s);
 hipError_t launch_fill(double* p, int64_t n, double v, hipStream_t s);
 hipError_t launch_broadcast_row(double* row, int64_t n, const double* src, int64_t n_src,
                                 hipStream_t s);

@@ -40,6 +40,14 @@ struct rscm_sampler {
     bool fused = true;
     void* d_sobs = nullptr;          // stored path: observation rows, values, sigmas, groups
     rscm::LoglikArgs lik{};
+    // the observations as given at creation (rscm_sampler_set_reference lays the stored path's tables out again)
+    std::vector<int32_t> obs_owner, obs_var, obs_tidx;
+    std::vector<double> obs_value, obs_sigma;
+    int32_t normalize = 0;
+    bool use_ref = false;            // stored path: score with loglik_ref_kernel and lik_ref
+    void* d_sref = nullptr;
+    rscm::LoglikRefArgs lik_ref{};
+    int32_t obs_last_step = 0;       // graph evaluator: the last observed index
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // graph evaluator (rscm_sampler_create_graph): every half-step rewinds these handles, runs them in lock-step up
     // to the last observed index and scores the stored series; ev is the first of them
@@ -105,7 +113,7 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         HIPCHK(rscm::launch_sampler_propose(a, s->ev->stream));
         if (s->graph_last_step > 0)
             if (int rc = rscm_ens_run_lockstep(s->graph.data(), (int32_t)s->graph.size(), 0, s->graph_last_step)) return rc;
-        HIPCHK(rscm::launch_loglik(s->lik, s->ev->stream));
+        HIPCHK(s->use_ref ? rscm::launch_loglik_ref(s->lik_ref, s->ev->stream) : rscm::launch_loglik(s->lik, s->ev->stream));
         HIPCHK(rscm::launch_sampler_accept(a, s->ev->stream));
         if (s->sharded) {
             rscm::SamplerArgs p = a;
@@ -123,7 +131,7 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         s->ev->time_index = 0;  // every evaluation is a fresh Model::run of the half
         if (int rc = rscm_ens_run_async(s->ev, 0, s->ev->T - 1)) return rc;
         s->ev->time_index = 0;
-        HIPCHK(rscm::launch_loglik(s->lik, s->ev->stream));
+        HIPCHK(s->use_ref ? rscm::launch_loglik_ref(s->lik_ref, s->ev->stream) : rscm::launch_loglik(s->lik, s->ev->stream));
     }
     HIPCHK(rscm::launch_sampler_accept(a, s->ev->stream));
     if (s->sharded) {  // this rank's block of the updated half, ready for the all-gather
@@ -220,6 +228,13 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
     s->n_local = (int32_t)h->N;
     s->stretch_a = stretch_a;
     s->seed = seed;
+    if (n_obs > 0) {
+        s->obs_var.assign(obs_var, obs_var + n_obs);
+        s->obs_tidx.assign(obs_tidx, obs_tidx + n_obs);
+        s->obs_value.assign(obs_value, obs_value + n_obs);
+        s->obs_sigma.assign(obs_sigma, obs_sigma + n_obs);
+    }
+    s->normalize = normalize ? 1 : 0;
     auto cleanup = [&](int rc) {
         rscm_sampler_destroy(s);
         return rc;
@@ -364,6 +379,15 @@ int rscm_sampler_create_graph(rscm_ens* const* handles, int32_t n_handles, int32
     s->graph_sampled_rows = sampled;
     s->graph_clear = clear_between_runs != 0;
     s->graph_last_step = last_step;
+    s->obs_last_step = last_step;
+    if (n_obs > 0) {
+        s->obs_owner.assign(obs_owner, obs_owner + n_obs);
+        s->obs_var.assign(obs_var, obs_var + n_obs);
+        s->obs_tidx.assign(obs_tidx, obs_tidx + n_obs);
+        s->obs_value.assign(obs_value, obs_value + n_obs);
+        s->obs_sigma.assign(obs_sigma, obs_sigma + n_obs);
+    }
+    s->normalize = normalize ? 1 : 0;
     s->W = n_walkers;
     s->D = n_dims;
     s->rank = rank;
@@ -459,11 +483,13 @@ int rscm_sampler_destroy(rscm_sampler* s)
     if (s->ev) {
         (void)hipStreamSynchronize(s->ev->stream);
         s->ev->loglik_stop_at_last_obs = false;
+        s->ev->ref_active = false;
     }
     (void)hipFree(s->d_rows); (void)hipFree(s->d_kind); (void)hipFree(s->d_base); (void)hipFree(s->d_pa);
     (void)hipFree(s->d_pb); (void)hipFree(s->d_plo); (void)hipFree(s->d_phi); (void)hipFree(s->d_pos); (void)hipFree(s->d_logp); (void)hipFree(s->d_prop);
     (void)hipFree(s->d_z); (void)hipFree(s->d_lp); (void)hipFree(s->d_nacc); (void)hipFree(s->d_nprop);
     (void)hipFree(s->d_sobs);
+    (void)hipFree(s->d_sref);
     (void)hipFree((void*)s->d_param_ptr);
     (void)hipFree(s->d_send);
     (void)hipFree(s->d_recv);
@@ -480,6 +506,65 @@ static int sampler_ready(rscm_sampler* s)
     if (!s->graph.empty()) return set_device(h);   // rscm_ens_run_lockstep checks every handle of the graph when it runs
     h->time_index = 0;
     return check_loglik_ready(h);
+}
+
+int rscm_sampler_set_reference(rscm_sampler* s, int32_t n_ref, const int32_t* ref_owner, const int32_t* ref_var, const int32_t* ref_begin,
+                               const int32_t* ref_end, const int32_t* ref_stride)
+{
+    GUARD_BEGIN
+    if (!s) return fail(RSCM_ERR_INVALID, "sampler is NULL");
+    if (s->positions_set) return fail(RSCM_ERR_STATE, "reference periods are set before the walker positions (rscm_sampler_set_positions scores with them)");
+    rscm_ens* h = s->ev;
+    const bool graph = !s->graph.empty();
+    if (n_ref > 0 && graph != (ref_owner != nullptr))
+        return fail(RSCM_ERR_INVALID, graph ? "a graph sampler needs ref_owner" : "ref_owner is for graph samplers: pass NULL");
+    if (s->fused) return prepare_ref(h, n_ref, ref_var, ref_begin, ref_end, ref_stride);
+    if (int rc = check_reference(h->T, n_ref, graph ? ref_owner : nullptr, ref_var, ref_begin, ref_end, ref_stride)) return rc;
+    if (int rc = set_device(h)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    (void)hipFree(s->d_sref);
+    s->d_sref = nullptr;
+    s->use_ref = false;
+    s->graph_last_step = s->obs_last_step;
+    if (n_ref == 0) return RSCM_OK;
+    const int32_t n_obs = (int32_t)s->obs_var.size();
+    std::vector<const double*> ptrs((size_t)n_obs), ref_rows;
+    std::vector<int32_t> grp((size_t)n_obs), obs_ref((size_t)n_obs, -1), ref_off((size_t)n_ref + 1, 0);
+    auto owner_of = [&](int32_t j) { return graph ? s->obs_owner[(size_t)j] : 0; };
+    auto handle_of = [&](int32_t k) { return graph ? s->graph[(size_t)k] : h; };
+    for (int32_t j = 0; j < n_obs; ++j) {  // as at creation
+        const rscm_ens* g = handle_of(owner_of(j));
+        ptrs[(size_t)j] = g->series(s->obs_var[(size_t)j]) + (size_t)s->obs_tidx[(size_t)j] * g->N;
+        if (!graph) grp[(size_t)j] = s->obs_var[(size_t)j];
+        else grp[(size_t)j] = (j > 0 && owner_of(j) == owner_of(j - 1) && s->obs_var[(size_t)j] == s->obs_var[(size_t)j - 1]) ? grp[(size_t)j - 1] : j;
+    }
+    int32_t last_step = s->obs_last_step;
+    for (int32_t e = 0; e < n_ref; ++e) {
+        const int32_t owner = graph ? ref_owner[e] : 0;
+        if (graph && (owner < 0 || owner >= (int32_t)s->graph.size())) return fail(RSCM_ERR_INVALID, "reference period %d: owner %d out of range", e, owner);
+        const rscm_ens* g = handle_of(owner);
+        if (ref_var[e] < 1 || ref_var[e] >= g->V) return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no stored series", e, ref_var[e]);
+        if (ref_end[e] > g->T) return fail(RSCM_ERR_INVALID, "reference period %d: rows beyond the owner's axis", e);
+        bool observed = false;
+        for (int32_t j = 0; j < n_obs; ++j)
+            if (owner_of(j) == owner && s->obs_var[(size_t)j] == ref_var[e]) {
+                obs_ref[(size_t)j] = e;
+                observed = true;
+            }
+        if (!observed) return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no observation", e, ref_var[e]);
+        for (int32_t t = ref_begin[e]; t < ref_end[e]; t += ref_stride[e]) {
+            ref_rows.push_back(g->series(ref_var[e]) + (size_t)t * g->N);
+            last_step = std::max(last_step, t);
+        }
+        ref_off[(size_t)e + 1] = (int32_t)ref_rows.size();
+    }
+    if (int rc = upload_loglik_ref(n_obs, ptrs.data(), s->obs_value.data(), s->obs_sigma.data(), grp.data(), obs_ref.data(), n_ref, ref_off.data(),
+                                   ref_rows.data(), s->normalize, h->N, h->d_loglik, &s->d_sref, &s->lik_ref))
+        return rc;
+    s->use_ref = true;
+    s->graph_last_step = last_step;   // the graph steps to the last row the likelihood reads
+    return RSCM_OK;
+    GUARD_END
 }
 
 int rscm_sampler_set_groups(rscm_sampler* s, int32_t n_groups)

@@ -65,6 +65,29 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     }
 }
 
+// The fused likelihood with reference periods: an instantiation of its own, so that launches without a period run the kernels above
+// unchanged.
+template <int MODE, bool LDS>
+__global__ __launch_bounds__(kBlock) void two_layer_ref_kernel(TwoLayerArgs a, TwoLayerRefArgs r)
+{
+    extern __shared__ double lds_forcing[];
+    if constexpr (LDS) {
+        const int32_t len = a.step_end - a.step_begin;
+        const int32_t total = a.n_scen * len;
+        for (int32_t idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int32_t s = idx / len, k = idx - s * len;
+            lds_forcing[idx] = a.forcing[(size_t)s * a.n_times + a.step_begin + a.src_off + k];
+        }
+        __syncthreads();
+    }
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_members) return;
+    const int32_t guard = tl::two_layer_body<MODE, LDS, false, NoCache, true>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(), &r);
+    if constexpr (MODE == 0) {
+        if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
+    }
+}
+
 }  // namespace
 
 // (Round 5 built ONE persistent launch with a dependency-ordered work queue here -- tasks = (64-member block, chunk of steps) claimed by
@@ -102,6 +125,23 @@ hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s)
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s)
 {
     return launch_impl<false>(a, mode, s);
+}
+
+hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s)
+{
+    if (a.n_members <= 0) return hipSuccess;
+    const size_t lds = a.lds_forcing ? (size_t)a.n_scen * (a.step_end - a.step_begin) * sizeof(double) : 0;
+    const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
+    void (*kern)(TwoLayerArgs, TwoLayerRefArgs) =
+        mode == 0 ? (a.lds_forcing ? two_layer_ref_kernel<0, true> : two_layer_ref_kernel<0, false>)
+                  : (a.lds_forcing ? two_layer_ref_kernel<1, true> : two_layer_ref_kernel<1, false>);
+    if (lds > (size_t)kMaxStaticLds) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, s, a, r);
+    return hipGetLastError();
 }
 
 hipError_t two_layer_guard_counts(int64_t* out)

@@ -209,6 +209,77 @@ __device__ __forceinline__ void lik_consume(const TwoLayerArgs& a, LikAcc& L, in
     }
 }
 
+// The same with reference periods (REF launches; DESIGN.md section 7, "Reference periods").  A variable with a period is scored as the
+// anomaly from the member's own mean b over the reference rows.  The thread adds each reference row to the variable's sum as it passes
+// it (the sum starts at -0.0, the additive identity: the bits of rscm_ens_set_baseline).  An observation of that variable at a row up
+// to the period's last cannot be scored yet: its model value goes to the handle's scratch ([slot][N], one coalesced store).  When the
+// last reference row is in, b = sum / count is formed and the waiting observations are scored in observation order (one coalesced load
+// each); later ones are scored on the fly.  A variable's partial sum so sees the addends loglik_ref_kernel (ensemble_ops.hip) gives it,
+// in the same order: the two paths agree bit for bit.
+struct LikRef {
+    double sum_s = -0.0, sum_d = -0.0, b_s = 0.0, b_d = 0.0;
+    bool have_s = false, have_d = false;
+};
+
+__device__ __forceinline__ double lik_term(const TwoLayerArgs& a, int32_t k, double m)
+{
+    const double sigma = a.obs_sigma[k];
+    const double residual = a.obs_value[k] - m;
+    const double chi = (residual * residual) / (sigma * sigma);
+    double l = -0.5 * chi;
+    if (a.normalize) {
+        l -= 0.5 * 1.8378770664093453;  // ln(2*pi)
+        l -= log(sigma);
+    }
+    return l;
+}
+
+// the last reference row of a variable is in: form b and score the observations that waited for it (all of the variable's so far)
+__device__ __forceinline__ void lik_settle(const TwoLayerArgs& a, const TwoLayerRefArgs& r, LikAcc& L, bool deep, double sum, int32_t count,
+                                           double& b, double& part, int64_t i, int64_t N)
+{
+    b = sum / (double)count;
+    if (!is_finite(b)) L.bad = true;
+    for (int32_t k = 0; k < L.oi; ++k) {  // wave-uniform
+        const int32_t slot = r.obs_slot[k];
+        if ((a.obs_is_deep[k] != 0) != deep || slot < 0) continue;
+        part += lik_term(a, k, r.defer[(size_t)slot * N + i] - b);
+    }
+}
+
+__device__ __forceinline__ void lik_consume_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, LikAcc& L, LikRef& R, int32_t row,
+                                                double ts, double td, int64_t i, int64_t N)
+{
+    auto reference_row = [&](int32_t v) {  // wave-uniform
+        return r.on[v] && row >= r.begin[v] && row <= r.last[v] && (r.stride[v] == 1 || (row - r.begin[v]) % r.stride[v] == 0);
+    };
+    if (reference_row(0)) R.sum_s += ts;
+    if (reference_row(1)) R.sum_d += td;
+    while (L.oi < a.n_obs && a.obs_tidx[L.oi] == row) {  // wave-uniform
+        const bool deep = a.obs_is_deep[L.oi] != 0;
+        const double m = deep ? td : ts;
+        if (!is_finite(m)) L.bad = true;
+        const int32_t slot = r.obs_slot[L.oi];
+        if (slot >= 0) {
+            r.defer[(size_t)slot * N + i] = m;
+        } else {
+            const bool anomaly = deep ? r.on[1] != 0 : r.on[0] != 0;
+            const double l = lik_term(a, L.oi, anomaly ? m - (deep ? R.b_d : R.b_s) : m);
+            if (deep) L.part_d += l;
+            else L.part_s += l;
+        }
+        ++L.oi;
+    }
+    if (r.on[0] && row == r.last[0]) {
+        lik_settle(a, r, L, false, R.sum_s, r.count[0], R.b_s, L.part_s, i, N);
+        R.have_s = true;
+    }
+    if (r.on[1] && row == r.last[1]) {
+        lik_settle(a, r, L, true, R.sum_d, r.count[1], R.b_d, L.part_d, i, N);
+        R.have_d = true;
+    }
+}
+
 // Member i over the steps [a.step_begin, a.step_end).  LDS: the forcing slice staged by the caller in
 // lds_forcing ([n_scen][len]); otherwise read through L2 (table or linked series).
 // Cache: NoCache for the stand-alone kernels; the fused multi-step launch (group.hip) keeps parameters, the
@@ -217,10 +288,12 @@ __device__ __forceinline__ void lik_consume(const TwoLayerArgs& a, LikAcc& L, in
 // kGuardChunks; -1 in FAST mode.
 enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuardKinds = 3 };
 
-template <int MODE, bool LDS, bool STORE, class Cache = NoCache>
+// REF (with STORE == false): the fused likelihood with the reference periods of *ref (lik_consume_ref).
+template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
-                                               int32_t step_end, const Cache& cache = Cache())
+                                               int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
 {
+    static_assert(!(REF && STORE), "reference periods belong to the fused likelihood");
     const int32_t len = step_end - step_begin;
     const int64_t N = a.row_stride;   // the rows' stride (the caller has checked i against a.n_members)
 
@@ -264,7 +337,12 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
     const int32_t last = step_end - 1;
 
     LikAcc lik;
-    if constexpr (!STORE) lik_consume(a, lik, step_begin, ts, td);  // observations of the start row
+    [[maybe_unused]] LikRef lik_ref;
+    [[maybe_unused]] auto consume = [&](int32_t row) {
+        if constexpr (REF) lik_consume_ref(a, *ref, lik, lik_ref, row, ts, td, i, N);
+        else lik_consume(a, lik, row, ts, td);
+    };
+    if constexpr (!STORE) consume(step_begin);  // observations (and a reference row) of the start row
 
     // next year's forcing and sub-step count are fetched a year ahead of their use
     double erf_next = forcing_first();
@@ -348,7 +426,7 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
                     out_ts += N;
                     out_td += N;
                 } else {
-                    lik_consume(a, lik, n + 1, ts, td);
+                    consume(n + 1);
                 }
             }
         };
@@ -375,7 +453,7 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
                 out_ts += N;
                 out_td += N;
             } else {
-                lik_consume(a, lik, n + 1, ts, td);
+                consume(n + 1);
             }
         }
     }
@@ -383,6 +461,9 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
     if constexpr (!STORE) {
         // observations whose row is never reached were never computed -> member failure
         if (lik.oi < a.n_obs) lik.bad = true;
+        if constexpr (REF) {  // ... and so is a period whose last row is never reached
+            if ((ref->on[0] && !lik_ref.have_s) || (ref->on[1] && !lik_ref.have_d)) lik.bad = true;
+        }
         const double total = a.first_is_deep ? (0.0 + lik.part_d) + lik.part_s
                                              : (0.0 + lik.part_s) + lik.part_d;
         a.loglik[i] = lik.bad ? -__builtin_inf() : total;

@@ -236,8 +236,8 @@ class ShardedEnsemble:
         self.ensemble.rewind()
         self.ensemble.run()
 
-    def loglik_global(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize=False) -> np.ndarray:
-        local = self.ensemble.loglik(obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device=True)
+    def loglik_global(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize=False, reference=None) -> np.ndarray:
+        local = self.ensemble.loglik(obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device=True, reference=reference)
         return gather_members(local, self.n_total)
 
     def status_global(self) -> np.ndarray:
@@ -265,12 +265,14 @@ class ShardedEnsemble:
         """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""
         return exceedance_global(self.ensemble, vector, thresholds, weighted=weighted)
 
-    def constrain(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, bits: Optional[int] = None):
+    def constrain(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, bits: Optional[int] = None, reference=None):
         """Weight this rank's members by their fit to observations, on one scale across all ranks: the Gaussian
         log-likelihood on the device, a MAX all-reduce of the local maxima, then ``set_weights_from_loglik`` with the global
-        max and ``bits`` (default ``53 - ceil(log2(n_total))``).  Returns the ``(ll_max, bits)`` used, the same on every rank."""
+        max and ``bits`` (default ``53 - ceil(log2(n_total))``).  Returns the ``(ll_max, bits)`` used, the same on every rank.
+        ``reference`` (``Ensemble.loglik``): the observations of those variables are anomalies from a reference period, so an
+        anomaly plume (``quantile_rows_global(..., weighted=True, anomaly=True)``) is weighted by anomaly fit."""
         from .ensemble import default_weight_bits
-        ll = self.ensemble.loglik(obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device=True)
+        ll = self.ensemble.loglik(obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device=True, reference=reference)
         ll_max = self.ensemble.loglik_max(ll)
         if is_distributed():
             import torch

@@ -336,14 +336,38 @@ class Ensemble:
         self.sync()
         return DeviceVector(p.value, self.n_members, np.uint8, self)
 
-    def loglik(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, on_device: bool = False):
+    def _reference(self, reference):
+        """``{variable: (t_begin, t_end[, t_stride])}`` in row indices (the rows of ``set_baseline``) as the C boundary's arrays."""
+        rv, rb, re_, rs = [], [], [], []
+        for var, rows in dict(reference).items():
+            rows = tuple(int(x) for x in rows)
+            if len(rows) not in (2, 3):
+                raise ValueError(f"reference period of {var!r}: (t_begin, t_end[, t_stride]) expected, got {rows}")
+            rv.append(self._var(var)), rb.append(rows[0]), re_.append(rows[1]), rs.append(rows[2] if len(rows) == 3 else 1)
+        return tuple(np.ascontiguousarray(x, dtype=np.int32) for x in (rv, rb, re_, rs))
+
+    def loglik(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, on_device: bool = False, reference=None):
         """Gaussian log-likelihood per member, ``[N]``; ``on_device`` leaves it in device memory (a
-        ``DeviceVector``) for a reduction or all-gather without a host round trip."""
+        ``DeviceVector``) for a reduction or all-gather without a host round trip.  ``reference``:
+        ``{variable: (t_begin, t_end[, t_stride])}`` in row indices -- that variable's observations are anomalies from the
+        member's own mean over those rows (rscm_ens_loglik_ref)."""
         ov = np.ascontiguousarray([self._var(v) for v in np.atleast_1d(obs_var)], dtype=np.int32)
         ot = np.ascontiguousarray(obs_tidx, dtype=np.int32)
         val, sig = L.f64(obs_value), L.f64(obs_sigma)
         if not (len(ov) == len(ot) == len(val) == len(sig)):
             raise ValueError("observation arrays differ in length")
+        if reference:
+            rv, rb, re_, rs = self._reference(reference)
+            ref = (len(rv), L.iptr(rv), L.iptr(rb), L.iptr(re_), L.iptr(rs))
+            if on_device:
+                p = C.c_void_p()
+                L.check(self._lib.rscm_ens_loglik_ref_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
+                                                             int(normalize), *ref, C.byref(p)))
+                return DeviceVector(p.value, self.n_members, np.float64, self)
+            out = np.empty(self.n_members)
+            L.check(self._lib.rscm_ens_loglik_ref(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig), int(normalize),
+                                                  *ref, L.dptr(out)))
+            return out
         if on_device:
             p = C.c_void_p()
             L.check(self._lib.rscm_ens_loglik_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val),
@@ -354,13 +378,26 @@ class Ensemble:
                                           L.dptr(sig), int(normalize), L.dptr(out)))
         return out
 
-    def run_loglik(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, on_device: bool = False):
-        """Fused run + Gaussian log-likelihood: no series is written (see rscm_ens_run_loglik)."""
+    def run_loglik(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, on_device: bool = False, reference=None):
+        """Fused run + Gaussian log-likelihood: no series is written (see rscm_ens_run_loglik).  ``reference`` as for ``loglik``
+        (rscm_ens_run_loglik_ref)."""
         ov = np.ascontiguousarray([self._var(v) for v in np.atleast_1d(obs_var)], dtype=np.int32)
         ot = np.ascontiguousarray(obs_tidx, dtype=np.int32)
         val, sig = L.f64(obs_value), L.f64(obs_sigma)
         if not (len(ov) == len(ot) == len(val) == len(sig)):
             raise ValueError("observation arrays differ in length")
+        if reference:
+            rv, rb, re_, rs = self._reference(reference)
+            ref = (len(rv), L.iptr(rv), L.iptr(rb), L.iptr(re_), L.iptr(rs))
+            if on_device:
+                p = C.c_void_p()
+                L.check(self._lib.rscm_ens_run_loglik_ref_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
+                                                                 int(normalize), *ref, C.byref(p)))
+                return DeviceVector(p.value, self.n_members, np.float64, self)
+            out = np.empty(self.n_members)
+            L.check(self._lib.rscm_ens_run_loglik_ref(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
+                                                      int(normalize), *ref, L.dptr(out)))
+            return out
         if on_device:
             p = C.c_void_p()
             L.check(self._lib.rscm_ens_run_loglik_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val),
