@@ -83,8 +83,10 @@ extern "C" {
  *      rscm_ens_baseline_devptr, rscm_ens_clear_baseline, rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex,
  *      rscm_ens_member_indicators, rscm_ens_quantile_vectors, rscm_ens_select_begin_vectors, rscm_ens_exceedance
  *   9  likelihoods against anomalies from a reference period: rscm_ens_loglik_ref, rscm_ens_loglik_ref_device,
- *      rscm_ens_run_loglik_ref, rscm_ens_run_loglik_ref_device, rscm_sampler_set_reference */
-#define RSCM_GPU_ABI_MINOR 9
+ *      rscm_ens_run_loglik_ref, rscm_ens_run_loglik_ref_device, rscm_sampler_set_reference
+ *  10  posterior ensembles on the device: rscm_ens_weights_stats, rscm_ens_resample, rscm_gpu_resample_offset,
+ *      rscm_ens_gather_members */
+#define RSCM_GPU_ABI_MINOR 10
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -881,6 +883,47 @@ RSCM_API int rscm_ens_select_begin_vectors(rscm_ens* h, int32_t n_vec, const dou
  * shards are those of the whole ensemble; the probability is hits / total.  Weighted without weights: RSCM_ERR_STATE. */
 RSCM_API int rscm_ens_exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted, int64_t* hits,
                                  int64_t* total);
+
+/* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
+/* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,
+ * *w_max = the largest weight, sum_sq = sum w^2 as a 128-bit integer {high word, low word}.  The sums are exact, so the sums of
+ * shards are those of the whole ensemble (the effective sample size is total^2 / sum_sq).  No weights set: RSCM_ERR_STATE. */
+RSCM_API int rscm_ens_weights_stats(rscm_ens* h, int64_t* total, int64_t* n_nonzero, int64_t* w_max, uint64_t sum_sq[2]);
+/* Systematic resampling in integer form.  W = w_total is the summed weight of the whole ensemble, M the number of draws
+ * (1 <= M <= 2^31), s an integer offset (0 <= s < W).  Draw k (0 <= k < M) sits at the integer point
+ *     t_k = floor((s + k W) / M) = k q + floor((s + k r) / M),   W = q M + r,
+ * and its ancestor is the member i with C[i-1] <= t_k < C[i], C the inclusive running sum of the weights in member order: a
+ * zero-weight member is never drawn, member i is drawn floor(M w_i / W) or ceil(M w_i / W) times, ancestors are non-decreasing
+ * in k.  This handle owns the weight range [w_before, w_before + W_local) of the global order (W_local = its own summed weight):
+ * the call returns the contiguous run of draws k_first .. k_first + count - 1 whose points fall in that range and their LOCAL
+ * member indices, int64, in a handle-owned device buffer *anc_dev that stays valid until the next rscm_ens_resample on the handle
+ * or its destruction.  Every step is 64-bit integer arithmetic, so the runs of the handles of a split ensemble concatenate to the
+ * draw of the whole ensemble on one handle, bit for bit.  One handle alone passes w_before = 0 and w_total = W_local and gets
+ * count == M.  No weights set, or a staged select in flight: RSCM_ERR_STATE; w_total <= 0, M or s out of range, or
+ * w_before + W_local > w_total: RSCM_ERR_INVALID (the buffer of an earlier call keeps its contents). */
+RSCM_API int rscm_ens_resample(rscm_ens* h, int64_t M, int64_t s, int64_t w_before, int64_t w_total, int64_t* k_first, int64_t* count,
+                               void** anc_dev);
+/* The offset of a seeded draw, computed on the host so that every rank derives the same one: *s = floor(R W / 2^64), W = w_total,
+ * R = (x1 << 32) | x0 of the Philox4x32-10 block (x0, x1, x2, x3) with key (seed & 0xFFFFFFFF, seed >> 32) and counter
+ * (0, 0, 0, RSCM_RESAMPLE_STREAM_TAG).  w_total <= 0: RSCM_ERR_INVALID. */
+#define RSCM_RESAMPLE_STREAM_TAG 0x52534D50u /* "RSMP" */
+RSCM_API int rscm_gpu_resample_offset(uint64_t seed, int64_t w_total, int64_t* s);
+/* Members [dst_offset, dst_offset + count) of dst become copies of src's members anc[0 .. count) (int64; host memory, or with
+ * on_device != 0 device memory on the handles' device, e.g. the buffer of rscm_ens_resample) AT src's CURRENT TIME INDEX k:
+ * every parameter row, row k of every stored variable and the rows before it that the kind looks back at, the status bytes and
+ * the internal component state (ClimateUDEB: ocean columns, scalars and history rows 0..k; OceanCarbon: the flux ring).  dst
+ * needs no rscm_ens_set_params of its own: it takes the configuration src derived from its structural rows.  Afterwards dst
+ * stands at time index k with parameters and state rows set, sums parked by another run void and its member constants to be
+ * re-formed.  Its forcing is NOT touched: the caller gives dst its own scenarios (rscm_ens_set_forcing) before or after.
+ * dst must be of src's kind, on its device, with bitwise the same time bounds, the same mode and the same RK4 step sizes, else
+ * RSCM_ERR_INVALID; any member count.  Both may be windowed (row k and the look-back rows must be resident in src, else
+ * RSCM_ERR_STATE; dst's window is moved to k); RSCM_FLAG_NO_SERIES on either side: RSCM_ERR_INVALID.  The first call onto a
+ * destination fixes k; later calls for other blocks, while dst still stands where the first call left it, must come from a
+ * source at the same k with the same structural parameter rows (RSCM_ERR_STATE / RSCM_ERR_INVALID).  Members of dst that no
+ * call has written keep whatever they held: running them is the caller's business.  A staged select in flight on either
+ * handle: RSCM_ERR_STATE.  An ancestor outside [0, n_members of src): RSCM_ERR_INVALID, checked on the device before anything
+ * is copied.  dst == src: RSCM_ERR_INVALID. */
+RSCM_API int rscm_ens_gather_members(rscm_ens* dst, int64_t dst_offset, rscm_ens* src, const int64_t* anc, int32_t on_device, int64_t count);
 
 /* Copy the parameter matrix back to the host as [P][N] (e.g. after rscm_ens_sample_lhs). */
 RSCM_API int rscm_ens_get_params(rscm_ens* h, double* out_soa);

@@ -1377,6 +1377,25 @@ class GraphModel:
             ens.set_weights_from_loglik(x, bits, ll_max)
         return float(ll_max), int(bits)
 
+    def resample(self, n_draws: int, seed: int = 0, offset: Optional[int] = None):
+        """``Ensemble.resample`` with the member weights ``set_member_weights`` / ``set_weights_from_loglik`` put on every
+        ensemble of the graph (they all share the member index): the ancestors as an int64 device vector."""
+        return next(iter(self.ensembles.values())).resample(n_draws, seed, offset)
+
+    def branch(self, dst_model: "GraphModel", ancestors, dst_offset: int = 0) -> None:
+        """``Ensemble.branch`` handle by handle: the same ancestors applied to every ensemble of the graph, so that member ``j``
+        of ``dst_model`` (built from the same builder, any member count, full or windowed storage) continues member
+        ``ancestors[j]`` of this model from the current step.  ``dst_model`` keeps its own exogenous series."""
+        if self._host_nodes or dst_model._host_nodes:
+            raise NotImplementedError("branching graphs with Python components is not available")
+        if list(dst_model._order) != list(self._order) or set(dst_model.ensembles) != set(self.ensembles):
+            raise ValueError("the destination is not a model of this graph")
+        for ens in self.ensembles.values():
+            ens.sync()
+        for name, ens in self.ensembles.items():
+            ens.branch(dst_model.ensembles[name], ancestors, dst_offset)
+        dst_model.time_index = self.time_index
+
     def set_member_params(self, names: Sequence[str], values) -> None:
         """``values[N][len(names)]``: per-member values of the named component parameters; every
         other parameter keeps the value its component was built with."""

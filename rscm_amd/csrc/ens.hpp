@@ -186,6 +186,14 @@ struct rscm_ens {
 
     SelectState* select = nullptr;  // rscm_ens_select_begin .. rscm_ens_select_end
     int64_t* d_weights = nullptr;   // [N] member weights of the weighted select (rscm_ens_set_member_weights)
+    // posterior resampling (resample_host.cpp): the running sum of the weights with its scan scratch, and the ancestors of the last draw
+    int64_t* d_cumw = nullptr;      // [N + scan_scratch_elems(N)], allocated at the first rscm_ens_resample
+    int64_t* d_anc = nullptr;       // [anc_capacity] local member indices (rscm_ens_resample hands this out)
+    int64_t anc_capacity = 0;
+    // a destination of rscm_ens_gather_members: the time index its members were gathered at (-1: never a destination) and element 0 of
+    // every parameter row of the source that configured it
+    int32_t gather_k = -1;
+    std::vector<double> gather_p0;
     double* d_base = nullptr;       // [N] baseline of the anomaly select and indicators (rscm_ens_set_baseline)
     static constexpr int32_t kIndSlots = 4;
     double* d_ind[kIndSlots] = {};  // [3 + kMaxThresholds][N] per slot of rscm_ens_member_indicators, allocated at first use

@@ -790,6 +790,33 @@ hipError_t launch_weights_from_loglik(const double* d_ll, const uint8_t* d_statu
 // *d_flag = 1 if any d_w[i] < 0; *d_total += the sum of the weights, saturated so that it never wraps and exceeds 2^53 iff
 // the true sum does (the caller zeroes both)
 hipError_t launch_weights_check(const int64_t* d_w, int64_t N, int32_t* d_flag, unsigned long long* d_total, hipStream_t s);
+// posterior resampling (resample.hip):
+// d_out[5] = {sum w, count w != 0, max w, sum w^2 low word, sum w^2 high word}, exact, through d_partial[5 * weights_stats_partials(N)]
+int32_t weights_stats_partials(int64_t N);
+hipError_t launch_weights_stats(const int64_t* d_w, int64_t N, unsigned long long* d_partial, unsigned long long* d_out, hipStream_t s);
+// d_out[i] = d_in[0] + ... + d_in[i] (d_in == d_out allowed) in three launches per level over d_scratch[scan_scratch_elems(n)]; no
+// workgroup waits on another
+int64_t scan_scratch_elems(int64_t n);
+hipError_t launch_inclusive_scan(const int64_t* d_in, int64_t* d_out, int64_t n, int64_t* d_scratch, hipStream_t s);
+// d_anc[j] = the first member i with d_cum[i] > t_k - w_before, k = k_first + j, t_k = k q + floor((s0 + k r) / M), for j < count
+hipError_t launch_ancestors(const int64_t* d_cum, int64_t N, int64_t k_first, int64_t count, uint64_t M, uint64_t q, uint64_t r, uint64_t s0,
+                            uint64_t w_before, int64_t* d_anc, hipStream_t s);
+// *d_flag = 1 if any d_anc[j] is outside [0, n_src) (the caller zeroes it)
+hipError_t launch_ancestors_check(const int64_t* d_anc, int64_t count, int64_t n_src, int32_t* d_flag, hipStream_t s);
+// The member gather of rscm_ens_gather_members: piece p copies rows r < rows of elements of elem_bytes (8: f64, 1: status byte),
+// dst[r * dst_stride + j] = src[r * src_stride + d_anc[j]] for j < count (strides in elements; dst already points at the first
+// destination member).  One launch over a table of up to kMaxGatherPieces pieces.
+constexpr int kMaxGatherPieces = 48;
+struct GatherPiece {
+    const void* src;
+    void* dst;
+    int64_t src_stride, dst_stride;
+    int32_t rows, elem_bytes;
+};
+struct GatherBatch {
+    GatherPiece pieces[kMaxGatherPieces];
+};
+hipError_t launch_gather_members(const GatherBatch& batch, int32_t n_pieces, const int64_t* d_anc, int64_t count, int64_t n_src, hipStream_t s);
 // per-member indicators (indicators.hip) over rows d_rows[n_rows][N] at times d_time[n_rows], of x or (d_base non-null) of
 // x - d_base[i]: a member with a NaN value gets NaN everywhere, else out[0][i] = sum in row order / n_rows and, with all,
 // out[1] = max, out[2] = time of the first row attaining it, out[3 + k] = time of the first row >= thr[k] (+inf: none)

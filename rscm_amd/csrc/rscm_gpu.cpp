@@ -770,6 +770,8 @@ int rscm_ens_destroy(rscm_ens* h)
     (void)hipFree(h->d_defer);
     select_release(h);
     (void)hipFree(h->d_weights);
+    (void)hipFree(h->d_cumw);
+    (void)hipFree(h->d_anc);
     (void)hipFree(h->d_base);
     for (double* p : h->d_ind) (void)hipFree(p);
     if (h->plan) {
@@ -1186,6 +1188,187 @@ int rscm_ens_set_internal_state(rscm_ens* h, const double* in, int64_t n_doubles
     h->time_index = time_index;
     h->ocean_tile_base = -1;
     h->ocean_modes_at = -1;
+    return RSCM_OK;
+    GUARD_END
+}
+
+// ---- branching: members of one handle copied into another at the source's time index (ABI minor 10) ----
+namespace {
+
+struct GatherRow { const void* src; void* dst; int32_t elem_bytes; };
+
+// Rows that follow each other at one pair of strides become one piece; the pieces go out kMaxGatherPieces per launch.
+int gather_launch(const std::vector<GatherRow>& rows, int64_t src_N, int64_t dst_N, const int64_t* d_anc, int64_t count, hipStream_t stream)
+{
+    rscm::GatherBatch batch;
+    memset((void*)&batch, 0, sizeof batch);
+    int32_t n = 0;
+    auto flush = [&]() -> hipError_t {
+        const hipError_t e = n > 0 ? rscm::launch_gather_members(batch, n, d_anc, count, src_N, stream) : hipSuccess;
+        n = 0;
+        return e;
+    };
+    for (const GatherRow& r : rows) {
+        if (n > 0) {
+            rscm::GatherPiece& g = batch.pieces[n - 1];
+            if (g.elem_bytes == r.elem_bytes) {
+                const int64_t ds = ((const char*)r.src - (const char*)g.src) / r.elem_bytes, dd = ((char*)r.dst - (char*)g.dst) / r.elem_bytes;
+                if (g.rows == 1 && ds > 0 && dd > 0) {
+                    g.src_stride = ds; g.dst_stride = dd; g.rows = 2;
+                    continue;
+                }
+                if (g.rows > 1 && ds == g.src_stride * g.rows && dd == g.dst_stride * g.rows && g.rows < (1 << 20)) {
+                    ++g.rows;
+                    continue;
+                }
+            }
+        }
+        if (n == rscm::kMaxGatherPieces) HIPCHK(flush());
+        rscm::GatherPiece& g = batch.pieces[n++];
+        g.src = r.src; g.dst = r.dst; g.src_stride = src_N; g.dst_stride = dst_N; g.rows = 1; g.elem_bytes = r.elem_bytes;
+    }
+    HIPCHK(flush());
+    return RSCM_OK;
+}
+
+}  // namespace
+
+int rscm_ens_gather_members(rscm_ens* dst, int64_t dst_offset, rscm_ens* src, const int64_t* anc, int32_t on_device, int64_t count)
+{
+    GUARD_BEGIN
+    NEED(dst);
+    NEED(src);
+    if (dst == src) return fail(RSCM_ERR_INVALID, "source and destination are the same handle");
+    if (count < 0 || dst_offset < 0 || dst_offset > dst->N || count > dst->N - dst_offset)
+        return fail(RSCM_ERR_INVALID, "members [%lld, %lld + %lld) are outside the destination's %lld", (long long)dst_offset,
+                    (long long)dst_offset, (long long)count, (long long)dst->N);
+    if (count > 0 && !anc) return fail(RSCM_ERR_INVALID, "ancestors are NULL");
+    if (dst->kind != src->kind) return fail(RSCM_ERR_INVALID, "kinds differ: destination %d, source %d", dst->kind, src->kind);
+    if (dst->device != src->device) return fail(RSCM_ERR_INVALID, "the handles live on devices %d and %d", dst->device, src->device);
+    if (dst->T != src->T || memcmp(dst->bounds.data(), src->bounds.data(), src->bounds.size() * sizeof(double)) != 0)
+        return fail(RSCM_ERR_INVALID, "the time axes differ");
+    if (dst->mode != src->mode) return fail(RSCM_ERR_INVALID, "the arithmetic modes differ");
+    if (memcmp(&dst->h_tl, &src->h_tl, sizeof(double)) != 0 || memcmp(&dst->h_cc, &src->h_cc, sizeof(double)) != 0)
+        return fail(RSCM_ERR_INVALID, "the RK4 step sizes differ");
+    if ((!dst->windowed && dst->rows != dst->T) || (!src->windowed && src->rows != src->T))
+        return fail(RSCM_ERR_INVALID, "a handle without stored series (RSCM_FLAG_NO_SERIES) cannot be branched");
+    if (dst->select || src->select) return fail(RSCM_ERR_STATE, "a select is in flight: rscm_ens_select_end it first");
+    if (!src->params_set) return fail(RSCM_ERR_STATE, "the source has no parameters");
+    if ((src->kind == RSCM_KIND_UDEB && !src->udeb_ready) || (src->kind == RSCM_KIND_OCEAN_CARBON && !src->ocean_ready))
+        return fail(RSCM_ERR_STATE, "the source is not configured");
+    const int32_t k = src->time_index, P = src->P, V = src->V;
+    const int32_t t0 = std::max(0, k - src->lookback);
+    for (int32_t v = 1; v < V; ++v)
+        for (int32_t t = t0; t <= k; ++t)
+            if (!src->row_ptr(v, t))
+                return fail(RSCM_ERR_STATE, "row %d of variable %d is not resident in the source any more", t, v);
+    const bool later = dst->gather_k >= 0 && dst->time_index == dst->gather_k && dst->params_set;   // another block of the same branch
+    if (later && dst->gather_k != k)
+        return fail(RSCM_ERR_STATE, "the destination was gathered at time index %d, this source stands at %d", dst->gather_k, k);
+    if (int rc = set_device(src)) return rc;
+    HIPCHK(hipStreamSynchronize(src->stream));
+    HIPCHK(hipStreamSynchronize(dst->stream));
+
+    // element 0 of every parameter row of the source: its structural rows are uniform, and they configure the destination
+    std::vector<double> p0((size_t)P);
+    HIPCHK(hipMemcpy2D(p0.data(), sizeof(double), src->d_params, (size_t)src->N * sizeof(double), sizeof(double), (size_t)P, hipMemcpyDeviceToHost));
+    if (later) {
+        for (int32_t j = 0; j < P; ++j)
+            if (structural_row(src->kind, j) && memcmp(&p0[j], &dst->gather_p0[j], sizeof(double)) != 0)
+                return fail(RSCM_ERR_INVALID, "parameter row %d (%s) of this source differs from the one the destination was configured from", j,
+                            structural_row(src->kind, j));
+        if (src->lookback != dst->lookback) return fail(RSCM_ERR_INVALID, "the look-back of this source differs from the destination's");
+    }
+
+    // the ancestors on the device, checked there before anything is written
+    int64_t* d_tmp = nullptr;
+    const int64_t* d_anc = anc;
+    struct Free { int64_t*& p; int32_t*& f; ~Free() { (void)hipFree(p); (void)hipFree(f); } };
+    int32_t* d_flag = nullptr;
+    Free guard{d_tmp, d_flag};
+    if (count > 0) {
+        if (!on_device) {
+            HIPCHK(rscm::dev_malloc(&d_tmp, (size_t)count * sizeof(int64_t)));
+            HIPCHK(hipMemcpyAsync(d_tmp, anc, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, dst->stream));
+            d_anc = d_tmp;
+        }
+        int32_t bad = 0;
+        HIPCHK(rscm::dev_malloc(&d_flag, sizeof(int32_t)));
+        HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int32_t), dst->stream));
+        HIPCHK(rscm::launch_ancestors_check(d_anc, count, src->N, d_flag, dst->stream));
+        HIPCHK(hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(hipStreamSynchronize(dst->stream));
+        if (bad) return fail(RSCM_ERR_INVALID, "an ancestor is outside [0, %lld)", (long long)src->N);
+    }
+
+    if (!later) {
+        // the destination takes the configuration the source derived from its structural rows
+        const int32_t was = dst->time_index;
+        dst->time_index = 0;   // its own internal state is about to be replaced: a change of its shape is no error
+        int rc = RSCM_OK;
+        if (dst->kind == RSCM_KIND_UDEB) rc = configure_udeb(dst, 1, [&](int j, int64_t) { return p0[(size_t)j]; });
+        if (dst->kind == RSCM_KIND_OCEAN_CARBON) rc = configure_ocean(dst, 1, [&](int j, int64_t) { return p0[(size_t)j]; });
+        dst->time_index = was;
+        if (rc) return rc;
+        dst->ghg_method = src->ghg_method;
+        dst->lookback = src->lookback;
+        if (dst->windowed) {
+            if (dst->rows < 2 * dst->keep_rows())
+                return fail(RSCM_ERR_INVALID, "the destination's window of %d rows is too short for a look-back of %d rows", dst->rows, dst->lookback);
+            if (int rc2 = window_seek(dst, k)) return rc2;
+            if (k == 0) dst->row0_saved = false;
+        }
+        dst->gather_p0 = p0;
+    }
+    if (dst->windowed && (t0 < dst->win0 || k >= dst->win0 + dst->rows))
+        return fail(RSCM_ERR_STATE, "rows %d..%d do not lie in the destination's window [%d, %d)", t0, k, dst->win0, dst->win0 + dst->rows);
+
+    std::vector<GatherRow> rows;
+    for (int32_t j = 0; j < P; ++j)
+        rows.push_back({src->d_params + (size_t)j * src->N, dst->d_params + (size_t)j * dst->N + dst_offset, 8});
+    for (int32_t t = t0; t <= k; ++t)
+        for (int32_t v = 1; v < V; ++v)
+            rows.push_back({src->row_ptr(v, t), dst->series(v) + (size_t)t * dst->N + dst_offset, 8});
+    if (src->kind == RSCM_KIND_UDEB) {
+        for (int32_t r = 0; r < 2 * src->udeb_n_layers; ++r)
+            rows.push_back({src->d_ocean + (size_t)r * src->N, dst->d_ocean + (size_t)r * dst->N + dst_offset, 8});
+        for (int32_t r = 0; r < rscm::kUdebScalars; ++r)
+            rows.push_back({src->d_scal + (size_t)r * src->N, dst->d_scal + (size_t)r * dst->N + dst_offset, 8});
+        for (int32_t r = 0; r <= k; ++r)
+            rows.push_back({src->d_hist + (size_t)r * src->N, dst->d_hist + (size_t)r * dst->N + dst_offset, 8});
+    } else if (src->kind == RSCM_KIND_OCEAN_CARBON) {
+        if (dst->ocean_hist_rows != src->ocean_hist_rows || dst->ocean_steps != src->ocean_steps)
+            return fail(RSCM_ERR_INVALID, "the flux-history rings differ: %lld and %lld rows", (long long)dst->ocean_hist_rows, (long long)src->ocean_hist_rows);
+        // the pulses still held sit at the same ring positions on both sides
+        const int64_t total = (int64_t)k * src->ocean_steps, R = src->ocean_hist_rows;
+        const int64_t cnt = std::min(total, R), first = cnt > 0 ? (total - cnt) % R : 0;
+        for (int64_t i = 0; i < cnt; ++i) {
+            const int64_t r = (first + i) % R;
+            rows.push_back({src->d_ocean_hist + (size_t)r * src->N, dst->d_ocean_hist + (size_t)r * dst->N + dst_offset, 8});
+        }
+    }
+    rows.push_back({src->d_status, dst->d_status + dst_offset, 1});
+    if (count > 0)
+        if (int rc = gather_launch(rows, src->N, dst->N, d_anc, count, dst->stream)) return rc;
+    HIPCHK(hipStreamSynchronize(dst->stream));
+
+    // rows that hold one value for every member: only those that did in the source and, for a later block, hold the same bits as before
+    uint64_t uni = dst->params_exposed ? 0 : src->uniform_rows;
+    if (later) {
+        uni &= dst->uniform_rows;
+        for (int32_t j = 0; j < P && j < 64; ++j)
+            if (memcmp(&p0[j], &dst->gather_p0[j], sizeof(double)) != 0) uni &= ~(1ull << j);
+    } else if (dst_offset != 0)
+        uni = 0;   // element 0, which the kernels read for such a row, is not among the members written
+    dst->uniform_rows = uni;
+    dst->derived_dirty = true;
+    dst->params_set = true;
+    for (int32_t v = 1; v < V; ++v)
+        if (dst->is_state(v)) dst->initial_set[v] = 1;
+    dst->time_index = k;
+    dst->gather_k = k;
+    dst->ocean_tile_base = -1;
+    dst->ocean_modes_at = -1;
     return RSCM_OK;
     GUARD_END
 }

@@ -15,7 +15,9 @@ in the CPU tests), are:
   counts for the likelihood-weighted quantiles);
 * ``ShardedEnsemble.constrain``: one all-reduce (MAX) of the local log-likelihood maxima;
 * ``quantile_vectors_global``: the same histogram all-reduces over per-member vectors (indicators, parameter rows);
-* ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums.
+* ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums;
+* ``weights_stats_global``: one all-reduce (int64 SUM) of the exact weight sums and one (MAX) of the largest weight;
+* ``resample_global``: one all-gather of each rank's exact summed weight (8 B per rank); no member crosses a rank.
 
 Baselines and per-member indicators (``Ensemble.set_baseline``, ``Ensemble.indicators``) are per member and need none.
 
@@ -209,6 +211,56 @@ def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool =
     return exceedance_result(acc[:-1], int(acc[-1]))
 
 
+def weights_stats_global(ensemble, group=None) -> Dict[str, object]:
+    """``Ensemble.weights_stats`` of the WHOLE sharded ensemble on every rank: the ranks' exact integers are SUM-reduced (``w_max``:
+    MAX) -- sum w^2 as four 32-bit limbs, each of which sums without wrapping over any number of ranks an int64 can count -- and
+    the effective sample size is formed once from the reduced integers."""
+    from .ensemble import weights_stats_result
+    local = ensemble.weights_stats()
+    if not is_distributed():
+        return local
+    import torch
+    d = _dist()
+    dev = _device_for_backend()
+    sq = int(local["sum_sq"])
+    limbs = [(sq >> (32 * k)) & 0xFFFFFFFF for k in range(4)]
+    t = torch.tensor([int(local["total"]), int(local["n_nonzero"])] + limbs, dtype=torch.int64, device=dev)
+    m = torch.tensor([int(local["w_max"])], dtype=torch.int64, device=dev)
+    d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+    d.all_reduce(m, op=d.ReduceOp.MAX, group=group)
+    acc = [int(x) for x in t.cpu().numpy()]
+    return weights_stats_result(acc[0], acc[1], int(m.item()), sum(acc[2 + k] << (32 * k) for k in range(4)))
+
+
+def resample_global(ensemble, n_draws: int, seed: int = 0, group=None, offset: Optional[int] = None):
+    """This rank's share of ONE systematic draw of ``n_draws`` members from the whole sharded ensemble's weights:
+    ``(k_first, count, ancestors)`` -- the contiguous run of draws whose ancestors this rank owns and their LOCAL member
+    indices (``Ensemble.resample``: an int64 device vector).  The ranks all-gather their exact summed weights (rank order is
+    member order), every rank derives the same offset from ``seed``, and the rest is integer arithmetic per rank: the runs of
+    all ranks concatenate to the draw a single process makes from the gathered weights, bit for bit, at any number of ranks.
+    A rank's posterior shard is the draws it owns; shards are of unequal size and no member crosses a rank."""
+    from .ensemble import resample_offset
+    w_local = int(ensemble.weights_stats()["total"])
+    if not is_distributed():
+        w_before, w_total = 0, w_local
+    else:
+        import torch
+        d = _dist()
+        world, rank = d.get_world_size(group), d.get_rank(group)
+        dev = _device_for_backend()
+        mine = torch.tensor([w_local], dtype=torch.int64, device=dev)
+        gathered = torch.empty(world, dtype=torch.int64, device=dev)
+        d.all_gather_into_tensor(gathered, mine, group=group)
+        totals = [int(x) for x in gathered.cpu().numpy()]
+        w_before, w_total = sum(totals[:rank]), sum(totals)
+    if w_total <= 0:
+        raise ValueError("the member weights of the whole ensemble sum to zero: nothing to draw from")
+    if offset is None:
+        offset = resample_offset(seed, w_total)
+    anc = ensemble.resample(n_draws, offset=offset, w_before=w_before, w_total=w_total)
+    return anc.k_first, len(anc), anc
+
+
 class ShardedEnsemble:
     """One global ensemble of ``n_total`` members, this rank holding its block on its GPU.
 
@@ -283,3 +335,11 @@ class ShardedEnsemble:
         if bits is None:
             bits = default_weight_bits(self.n_total)
         return self.ensemble.set_weights_from_loglik(ll, bits, ll_max)
+
+    def weights_stats_global(self) -> Dict[str, object]:
+        """Exact weight statistics and effective sample size of the global ensemble (``weights_stats_global``)."""
+        return weights_stats_global(self.ensemble)
+
+    def resample(self, n_draws: int, seed: int = 0, offset: Optional[int] = None):
+        """This rank's ``(k_first, count, ancestors)`` of one systematic draw from the global ensemble (``resample_global``)."""
+        return resample_global(self.ensemble, n_draws, seed, offset=offset)

@@ -617,6 +617,83 @@ class Ensemble:
         s2 = float(np.dot(w, w))
         return float(w.sum()) ** 2 / s2 if s2 > 0 else 0.0
 
+    # -- posterior ensembles: weight statistics, systematic resampling, branching --------------
+    def weights_stats(self) -> Dict[str, object]:
+        """Exact statistics of the member weights, reduced on the device in integers: ``total`` (sum w), ``n_nonzero``,
+        ``w_max`` and ``sum_sq`` (sum w^2, up to 2^106) as Python ints, and ``ess = total^2 / sum_sq`` formed once on the host
+        from them (0.0 without weight).  The integers of shards add up to those of the whole ensemble
+        (``distributed.weights_stats_global``)."""
+        total, nnz, wmax = C.c_int64(), C.c_int64(), C.c_int64()
+        sq = (C.c_uint64 * 2)()
+        L.check(self._lib.rscm_ens_weights_stats(self._h, C.byref(total), C.byref(nnz), C.byref(wmax), sq))
+        return weights_stats_result(total.value, nnz.value, wmax.value, (int(sq[0]) << 64) | int(sq[1]))
+
+    def resample(self, n_draws: int, seed: int = 0, offset: Optional[int] = None, w_before: int = 0,
+                 w_total: Optional[int] = None) -> DeviceVector:
+        """Systematic resampling of the member weights in integer arithmetic (``rscm_ens_resample``): the ancestors (local
+        member indices, int64, non-decreasing) of this ensemble's share of ``n_draws`` equally weighted draws, left on the
+        device and valid until the next ``resample``.  ``offset`` (default: ``resample_offset(seed, w_total)``) is the integer
+        start 0 <= s < W.  A shard of a larger ensemble passes the weight ``w_before`` of the members before its own and the
+        global ``w_total``; the returned vector then holds the contiguous run of draws ``k_first .. k_first + len - 1``
+        (attribute ``k_first``) whose ancestors this ensemble owns."""
+        if w_total is None:
+            w_total = self.weights_stats()["total"] + int(w_before)
+        if offset is None:
+            offset = resample_offset(seed, w_total)
+        k_first, count, p = C.c_int64(), C.c_int64(), C.c_void_p()
+        L.check(self._lib.rscm_ens_resample(self._h, int(n_draws), int(offset), int(w_before), int(w_total), C.byref(k_first),
+                                            C.byref(count), C.byref(p)))
+        v = DeviceVector(p.value or 0, count.value, np.int64, self)
+        v.k_first = k_first.value
+        return v
+
+    def branch(self, dst: "Ensemble", ancestors, dst_offset: int = 0) -> None:
+        """Members ``[dst_offset, dst_offset + len(ancestors))`` of ``dst`` become copies of this ensemble's members
+        ``ancestors`` (an int64 ``DeviceVector`` of ``resample``, or integers on the host) at the current time index, on the
+        device (``rscm_ens_gather_members``): parameters, the current rows, look-back rows, status and internal component
+        state.  ``dst`` needs no ``set_params``; it keeps its own forcing, which is the point: give it the scenarios to
+        project under.  Members of ``dst`` that no call has written are the caller's business."""
+        if isinstance(ancestors, DeviceVector):
+            if ancestors.dtype != np.int64:
+                raise ValueError("ancestors: need an int64 device vector")
+            n, ptr, on_dev, keep = ancestors.n, C.cast(C.c_void_p(ancestors.ptr), C.POINTER(C.c_int64)), 1, ancestors
+        else:
+            keep = np.ascontiguousarray(ancestors, dtype=np.int64)
+            if keep.ndim != 1:
+                raise ValueError("ancestors: need a vector of member indices")
+            n, ptr, on_dev = keep.size, keep.ctypes.data_as(C.POINTER(C.c_int64)), 0
+        L.check(self._lib.rscm_ens_gather_members(dst._h, int(dst_offset), self._h, ptr, on_dev, n))
+
+    def posterior(self, factory, n_draws: int, seed: int = 0, scenarios: int = 1):
+        """An equally weighted posterior ensemble ready to project: ``dst = factory(n_draws * scenarios)`` (an ``Ensemble`` of
+        this kind on this axis, mode and device), the same ``n_draws`` resampled members gathered into each of the
+        ``scenarios`` blocks.  Returns ``(dst, scenario_of_member)`` with ``scenario_of_member = repeat(arange(scenarios),
+        n_draws)`` for the caller's ``dst.set_forcing(series, scenario_of_member)``."""
+        n_draws, scenarios = int(n_draws), int(scenarios)
+        if n_draws < 1 or scenarios < 1:
+            raise ValueError("need n_draws >= 1 and scenarios >= 1")
+        anc = self.resample(n_draws, seed)
+        dst = factory(n_draws * scenarios)
+        for sidx in range(scenarios):
+            self.branch(dst, anc, sidx * n_draws)
+        return dst, np.repeat(np.arange(scenarios, dtype=np.int32), n_draws)
+
+
+def weights_stats_result(total: int, n_nonzero: int, w_max: int, sum_sq: int) -> Dict[str, object]:
+    """The dict of ``Ensemble.weights_stats`` from exact integers; ``ess = total^2 / sum_sq`` as one correctly rounded division."""
+    total, sum_sq = int(total), int(sum_sq)
+    from fractions import Fraction
+    ess = float(Fraction(total * total, sum_sq)) if sum_sq else 0.0
+    return {"total": total, "n_nonzero": int(n_nonzero), "w_max": int(w_max), "sum_sq": sum_sq, "ess": ess}
+
+
+def resample_offset(seed: int, w_total: int) -> int:
+    """The integer offset ``floor(R * w_total / 2^64)`` of a seeded systematic draw, ``R`` one 64-bit word of the library's Philox
+    stream (``rscm_gpu_resample_offset``; computed on the host, so every rank derives the same one)."""
+    s = C.c_int64()
+    L.check(L.load().rscm_gpu_resample_offset(C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), int(w_total), C.byref(s)))
+    return s.value
+
 
 def exceedance_result(hits, total: int) -> Dict[str, object]:
     """``{"hits", "total", "probability"}`` from int64 sums; the probability is ``hits / total`` in float64, NaN when total is 0."""
