@@ -85,8 +85,10 @@ extern "C" {
  *   9  likelihoods against anomalies from a reference period: rscm_ens_loglik_ref, rscm_ens_loglik_ref_device,
  *      rscm_ens_run_loglik_ref, rscm_ens_run_loglik_ref_device, rscm_sampler_set_reference
  *  10  posterior ensembles on the device: rscm_ens_weights_stats, rscm_ens_resample, rscm_gpu_resample_offset,
- *      rscm_ens_gather_members */
-#define RSCM_GPU_ABI_MINOR 10
+ *      rscm_ens_gather_members
+ *  11  per-group quantiles and exceedance: rscm_ens_set_member_groups, rscm_ens_member_groups_devptr,
+ *      rscm_ens_clear_member_groups, RSCM_SELECT_GROUPED, rscm_ens_exceedance_grouped */
+#define RSCM_GPU_ABI_MINOR 11
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -793,7 +795,8 @@ RSCM_API int rscm_ens_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin
  *     rscm_ens_select_end(h);
  *
  * Every handle must be given the same q, the same row range and stride and be at the same time index; anything else is a
- * caller error (the buffers then differ in size or meaning and the result is undefined).  The handle must not run, and its
+ * caller error (the buffers then differ in size or meaning and the result is undefined).  With RSCM_SELECT_GROUPED every handle
+ * must also carry the same n_groups (the group ids themselves are each handle's own members').  The handle must not run, and its
  * rows must not be written, between begin and the last pass.  One staged select per handle at a time: begin on a handle
  * with one in flight is RSCM_ERR_STATE; rscm_ens_destroy ends one in flight.  The buffer belongs to the handle and stays
  * valid until the next pass or end.  Passes: eight while any row of the range is computed, none otherwise. */
@@ -851,7 +854,7 @@ RSCM_API int rscm_ens_set_baseline_values(rscm_ens* h, const double* b, int32_t 
 /* Device address of the [N] baseline; RSCM_ERR_STATE (and NULL) if none is set. */
 RSCM_API int rscm_ens_baseline_devptr(rscm_ens* h, void** out);
 RSCM_API int rscm_ens_clear_baseline(rscm_ens* h);
-/* Flags of the _ex and vector selects */
+/* Flags of the _ex and vector selects (RSCM_SELECT_GROUPED, 4: with the member groups below) */
 #define RSCM_SELECT_WEIGHTED 1 /* the member weights, numpy "inverted_cdf" (rscm_ens_weighted_quantile_rows) */
 #define RSCM_SELECT_ANOMALY 2  /* of the anomalies x[i] - b[i] (one IEEE subtraction) against the baseline; stored rows only */
 /* rscm_ens_quantile_rows (flags 0) and rscm_ens_weighted_quantile_rows (RSCM_SELECT_WEIGHTED) with flags: the same
@@ -883,6 +886,32 @@ RSCM_API int rscm_ens_select_begin_vectors(rscm_ens* h, int32_t n_vec, const dou
  * shards are those of the whole ensemble; the probability is hits / total.  Weighted without weights: RSCM_ERR_STATE. */
 RSCM_API int rscm_ens_exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted, int64_t* hits,
                                  int64_t* total);
+
+/* ---- member groups: per-group quantiles and exceedance (ABI minor 11) ---------------------------- */
+/* group[N]: int32, -1 = the member belongs to no group and is left out of every grouped statistic, else 0 <= id < n_groups.
+ * 1 <= n_groups <= 64.  Host memory, or device memory on the handle's device (on_device != 0).  The groups are handle-owned (a
+ * copy is taken), kept across rscm_ens_run, rscm_ens_rewind and rscm_ens_gather_members INTO the handle (a branch does not touch
+ * the destination's groups, as it does not touch its forcing), freed by rscm_ens_destroy; they are not part of a checkpoint.  The
+ * ids are checked on the device: one outside [-1, n_groups), or n_groups outside [1, 64], is RSCM_ERR_INVALID and leaves the
+ * groups set before.  Not while a staged select is in flight (RSCM_ERR_STATE). */
+RSCM_API int rscm_ens_set_member_groups(rscm_ens* h, const int32_t* group, int32_t on_device, int32_t n_groups);
+/* Device address of the [N] int32 group ids and their n_groups; RSCM_ERR_STATE (and NULL, 0) if none are set. */
+RSCM_API int rscm_ens_member_groups_devptr(rscm_ens* h, void** out, int32_t* n_groups);
+RSCM_API int rscm_ens_clear_member_groups(rscm_ens* h);
+/* A further flag of rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex, rscm_ens_quantile_vectors and
+ * rscm_ens_select_begin_vectors, alone or with the flags those calls already take: one result per row AND group.  For every row r
+ * and group g the result is exactly what the same call without the flag returns for an ensemble consisting of the members with
+ * group[i] == g, in member order (plain: count = the group's non-NaN members; weighted: W = their summed weight, checked against
+ * 2^53 per (row, group) at the first commit; anomaly: of x[i] - b[i]; signed zeros as rscm_ens_quantile_rows).  A group with no
+ * non-NaN member in a row: count 0, quantiles NaN.  out[rows][n_groups][n_q], count[rows][n_groups]; rows beyond the time index
+ * as without the flag, for every group.  The staged buffer is [rows][n_groups][256] int64 in pass 0 and
+ * [rows][n_groups][n_t][256] later (n_t = 2 n_q, weighted n_q); rscm_ens_select_pass reports its size, and _commit, _result and
+ * _end keep their protocol.  No groups set: RSCM_ERR_STATE.  The groups must not change between begin and the last pass. */
+#define RSCM_SELECT_GROUPED 4
+/* hits[n_groups][n_thr], total[n_groups]: rscm_ens_exceedance per group; int64, exact, so shards add up.  Members of no group
+ * (-1) are left out.  No groups set, or weighted without weights: RSCM_ERR_STATE. */
+RSCM_API int rscm_ens_exceedance_grouped(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted,
+                                         int64_t* hits, int64_t* total);
 
 /* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
 /* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,

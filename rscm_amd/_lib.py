@@ -30,6 +30,7 @@ FLAG_NO_SERIES = 1
 FLAG_WINDOWED = 2
 SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
 SELECT_ANOMALY = 2
+SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
 
 TL_VARS = {"Effective Radiative Forcing": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2}
 CP_VARS = {"Emissions|CO2|Anthropogenic": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2,
@@ -329,6 +330,10 @@ SIGNATURES = {
     "rscm_ens_quantile_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, _dp]),
     "rscm_ens_select_begin_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32]),
     "rscm_ens_exceedance": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rscm_ens_set_member_groups": (C.c_int, [_h, _ip, C.c_int32, C.c_int32]),
+    "rscm_ens_member_groups_devptr": (C.c_int, [_h, C.POINTER(C.c_void_p), _ip]),
+    "rscm_ens_clear_member_groups": (C.c_int, [_h]),
+    "rscm_ens_exceedance_grouped": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rscm_ens_weights_stats": (C.c_int, [_h, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     "rscm_ens_resample": (C.c_int, [_h, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_void_p)]),

@@ -1311,14 +1311,16 @@ class GraphModel:
         return ens.get_series(vid, **kw)
 
     def quantile_rows(self, name: str, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                      weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
+                      weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Ensemble quantiles of ``name`` (``numpy.nanquantile``, linear) over the rows ``t_begin, t_begin + t_stride, ...
         < t_end``, reduced on the device wherever the rows are resident (a windowed graph's window or output store included):
         ``Ensemble.quantile_rows`` of the variable's home.  ``weighted``: with the member weights (``set_member_weights`` /
         ``set_weights_from_loglik``), ``method="inverted_cdf"``; the result then has ``"weight"`` in place of ``"count"``.
-        ``anomaly``: of each member's anomaly against the baseline ``set_baseline`` gave the variable's home."""
+        ``anomaly``: of each member's anomaly against the baseline ``set_baseline`` gave the variable's home.  ``grouped``: per
+        member group (``set_member_groups``), group-major as ``Ensemble.quantile_rows`` returns it."""
         ens, vid = self.variable_home(name)
-        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly)
+        kw = {"grouped": True} if grouped else {}
+        return ens.quantile_rows(vid, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, **kw)
 
     def set_baseline(self, name: str, t_begin: int, t_end: int, t_stride: int = 1) -> None:
         """Each member's mean of ``name`` over the rows ``t_begin, t_begin + t_stride, ... < t_end`` as the baseline of the
@@ -1342,15 +1344,27 @@ class GraphModel:
         ens, vid = self.variable_home(name)
         return ens.indicators(vid, t_begin, t_end, t_stride, thresholds, anomaly, slot)
 
-    def quantile_vectors(self, vectors, q, weighted: bool = False) -> Dict[str, np.ndarray]:
+    def quantile_vectors(self, vectors, q, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """``Ensemble.quantile_vectors`` on the ensemble that owns the vectors (every ensemble of the graph shares the member
-        index and, after ``set_member_weights`` / ``set_weights_from_loglik``, the weights)."""
+        index and, after ``set_member_weights`` / ``set_weights_from_loglik`` / ``set_member_groups``, the weights and groups)."""
         vs = list(vectors)
-        return vs[0].owner.quantile_vectors(vs, q, weighted=weighted)
+        kw = {"grouped": True} if grouped else {}
+        return vs[0].owner.quantile_vectors(vs, q, weighted=weighted, **kw)
 
-    def exceedance(self, vector, thresholds, weighted: bool = False) -> Dict[str, object]:
+    def exceedance(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """``Ensemble.exceedance`` on the ensemble that owns the vector."""
-        return vector.owner.exceedance(vector, thresholds, weighted=weighted)
+        kw = {"grouped": True} if grouped else {}
+        return vector.owner.exceedance(vector, thresholds, weighted=weighted, **kw)
+
+    def set_member_groups(self, groups, n_groups: Optional[int] = None) -> None:
+        """Member groups (``[N]`` int32, -1 or ``0 <= id < n_groups``) for the ``grouped=True`` statistics, set on every device
+        ensemble of the graph: they all share the member index.  ``branch`` leaves a destination's groups alone."""
+        for ens in self.ensembles.values():
+            ens.set_member_groups(groups, n_groups)
+
+    def clear_member_groups(self) -> None:
+        for ens in self.ensembles.values():
+            ens.clear_member_groups()
 
     def set_member_weights(self, w) -> None:
         """Integer member weights (``[N]`` int64 >= 0) for ``quantile_rows(..., weighted=True)``, set on every ensemble of the

@@ -194,6 +194,8 @@ struct rscm_ens {
     // every parameter row of the source that configured it
     int32_t gather_k = -1;
     std::vector<double> gather_p0;
+    int32_t* d_groups = nullptr;    // [N] member groups of the grouped select and exceedance (rscm_ens_set_member_groups), -1: none
+    int32_t n_groups = 0;
     double* d_base = nullptr;       // [N] baseline of the anomaly select and indicators (rscm_ens_set_baseline)
     static constexpr int32_t kIndSlots = 4;
     double* d_ind[kIndSlots] = {};  // [3 + kMaxThresholds][N] per slot of rscm_ens_member_indicators, allocated at first use

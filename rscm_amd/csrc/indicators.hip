@@ -12,7 +12,7 @@
 // exceedance_kernel: per block, the counts (or the summed int64 member weights) of members at or above each threshold and of
 // non-NaN members go into LDS int64 bins, then one integer atomic per bin.  No float atomics: the sums are exact and independent
 // of the block count, and shards of one ensemble add them exactly.  With the weights' bound (a handle's weights sum to at most
-// 2^53, weights.hip) nothing wraps.
+// 2^53, weights.hip) nothing wraps.  exceedance_grouped_kernel: the same sums per member group (rscm_ens_set_member_groups).
 #include <hip/hip_runtime.h>
 
 #include "rscm_device.hpp"
@@ -120,6 +120,69 @@ __global__ __launch_bounds__(kIndThreads) void exceedance_kernel(const double* _
     if ((int32_t)threadIdx.x == n_thr && bins[kMaxThresholds]) atomicAdd(&acc[n_thr], bins[kMaxThresholds]);
 }
 
+// exceedance_kernel per member group: acc[g][n_thr + 1] (the hits, then the total) over the members with group[i] == g (-1:
+// none).  A thread keeps the integer sums of ONE group in registers -- the group of the members it has met since its last flush --
+// and flushes them into the block's LDS int64 bins [n_groups][kMaxThresholds + 1] when it meets another: with contiguous groups that
+// is once or twice per thread.  The last flush goes through a wave ladder when the whole wave holds one group (one lane adds the
+// wave's sums).  Then one integer atomic per non-zero bin and block: exact, and the order in which blocks finish does not matter.
+template <bool kW>
+__global__ __launch_bounds__(kIndThreads) void exceedance_grouped_kernel(const double* __restrict__ v, const int64_t* __restrict__ w,
+                                                                          const int32_t* __restrict__ group, int32_t n_groups, int64_t N,
+                                                                          int32_t n_thr, Thresholds thr, unsigned long long* __restrict__ acc)
+{
+    constexpr int kRow = kMaxThresholds + 1;
+    __shared__ unsigned long long bins[kMaxMemberGroups * kRow];
+    for (int32_t i = (int32_t)threadIdx.x; i < n_groups * kRow; i += kIndThreads) bins[i] = 0ull;
+    __syncthreads();
+    unsigned long long hit[kMaxThresholds], tot = 0ull;
+#pragma unroll
+    for (int k = 0; k < kMaxThresholds; ++k) hit[k] = 0ull;
+    int32_t cur = -1;   // the group the registers hold sums of
+    auto flush = [&]() {
+        if (cur < 0) return;
+        if (tot) atomicAdd(&bins[cur * kRow + kMaxThresholds], tot);
+#pragma unroll
+        for (int k = 0; k < kMaxThresholds; ++k)
+            if (k < n_thr && hit[k]) atomicAdd(&bins[cur * kRow + k], hit[k]);
+        tot = 0ull;
+#pragma unroll
+        for (int k = 0; k < kMaxThresholds; ++k) hit[k] = 0ull;
+    };
+    for (int64_t i = (int64_t)blockIdx.x * kIndThreads + threadIdx.x; i < N; i += (int64_t)gridDim.x * kIndThreads) {
+        const int32_t g = group[i];
+        const double x = v[i];
+        if (g < 0 || x != x) continue;
+        if (g != cur) {
+            flush();
+            cur = g;
+        }
+        const unsigned long long wt = kW ? (unsigned long long)w[i] : 1ull;
+        tot += wt;
+#pragma unroll
+        for (int k = 0; k < kMaxThresholds; ++k)
+            if (k < n_thr && x >= thr.v[k]) hit[k] += wt;
+    }
+    // whole waves arrive here together; lanes that met no member of a group hold zeros and take the wave's group
+    const uint64_t have = __ballot(cur >= 0);
+    if (have != 0) {
+        const int32_t c0 = __shfl(cur, __ffsll((unsigned long long)have) - 1, 64);
+        if (__ballot(cur >= 0 && cur != c0) == 0) {
+            tot = wave_sum(tot);
+#pragma unroll
+            for (int k = 0; k < kMaxThresholds; ++k)
+                if (k < n_thr) hit[k] = wave_sum(hit[k]);
+            cur = (threadIdx.x & 63) == 0 ? c0 : -1;
+        }
+        flush();
+    }
+    __syncthreads();
+    for (int32_t i = (int32_t)threadIdx.x; i < n_groups * kRow; i += kIndThreads) {
+        const int32_t g = i / kRow, k = i % kRow;
+        if (!bins[i] || (k >= n_thr && k != kMaxThresholds)) continue;
+        atomicAdd(&acc[g * (n_thr + 1) + (k == kMaxThresholds ? n_thr : k)], bins[i]);
+    }
+}
+
 }  // namespace
 
 hipError_t launch_indicators(const double* const* d_rows, const double* d_time, int32_t n_rows, const double* d_base, int64_t N, bool all,
@@ -148,6 +211,19 @@ hipError_t launch_exceedance(const double* d_v, const int64_t* d_w, int64_t N, i
         hipLaunchKernelGGL(exceedance_kernel<true>, grid, dim3(kIndThreads), 0, s, d_v, d_w, N, n_thr, thr, d_acc);
     else
         hipLaunchKernelGGL(exceedance_kernel<false>, grid, dim3(kIndThreads), 0, s, d_v, d_w, N, n_thr, thr, d_acc);
+    return hipGetLastError();
+}
+
+hipError_t launch_exceedance_grouped(const double* d_v, const int64_t* d_w, const int32_t* d_group, int32_t n_groups, int64_t N,
+                                     int32_t n_thr, const Thresholds& thr, unsigned long long* d_acc, hipStream_t s)
+{
+    if (N <= 0) return hipSuccess;
+    const int64_t need = (N + kIndThreads - 1) / kIndThreads;
+    const dim3 grid((unsigned)(need < kExcBlocks ? need : kExcBlocks));
+    if (d_w)
+        hipLaunchKernelGGL(exceedance_grouped_kernel<true>, grid, dim3(kIndThreads), 0, s, d_v, d_w, d_group, n_groups, N, n_thr, thr, d_acc);
+    else
+        hipLaunchKernelGGL(exceedance_grouped_kernel<false>, grid, dim3(kIndThreads), 0, s, d_v, d_w, d_group, n_groups, N, n_thr, thr, d_acc);
     return hipGetLastError();
 }
 

@@ -1,5 +1,5 @@
 // Host side of the handle's baseline (rscm_ens_set_baseline*, the anomaly select's b[i]), of the per-member indicators
-// (rscm_ens_member_indicators) and of the exceedance counts (rscm_ens_exceedance); kernels in indicators.hip.
+// (rscm_ens_member_indicators) and of the exceedance counts (rscm_ens_exceedance, rscm_ens_exceedance_grouped); kernels in indicators.hip.
 //
 // Rows are resolved as the radix select resolves them (resolve_rows: full storage, the window, the output store) and must all be
 // computed.  The baseline and the indicator slots are handle-owned and kept across run and rewind, as the member weights are; a
@@ -185,6 +185,41 @@ int rscm_ens_exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const
     HIPCHK(es);
     for (int32_t k = 0; k < n_thr; ++k) hits[k] = (int64_t)acc[k];
     *total = (int64_t)acc[n_thr];
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_exceedance_grouped(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted, int64_t* hits,
+                                int64_t* total)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!total || (n_thr > 0 && !hits)) return fail(RSCM_ERR_INVALID, "hits or total is NULL");
+    if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
+    if (!h->d_groups) return fail(RSCM_ERR_STATE, "no member groups: rscm_ens_set_member_groups first");
+    if (weighted && !h->d_weights)
+        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
+    if (int rc = set_device(h)) return rc;
+    if (int rc = check_member_vector(h, vec_dev, "vector")) return rc;
+    rscm::Thresholds th{};
+    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
+    const int32_t G = h->n_groups;
+    std::vector<unsigned long long> acc((size_t)G * (n_thr + 1));
+    unsigned long long* d_acc = nullptr;
+    const size_t bytes = acc.size() * sizeof(unsigned long long);
+    hipError_t e = rscm::dev_malloc(&d_acc, bytes);
+    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, bytes, h->stream);
+    if (e == hipSuccess)
+        e = rscm::launch_exceedance_grouped(vec_dev, weighted ? h->d_weights : nullptr, h->d_groups, G, h->N, n_thr, th, d_acc, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(acc.data(), d_acc, bytes, hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_acc);
+    HIPCHK(e);
+    HIPCHK(es);
+    for (int32_t g = 0; g < G; ++g) {
+        for (int32_t k = 0; k < n_thr; ++k) hits[(size_t)g * n_thr + k] = (int64_t)acc[(size_t)g * (n_thr + 1) + k];
+        total[g] = (int64_t)acc[(size_t)g * (n_thr + 1) + n_thr];
+    }
     return RSCM_OK;
     GUARD_END
 }

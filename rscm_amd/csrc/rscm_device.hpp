@@ -768,11 +768,18 @@ hipError_t launch_quantile_rows(const double* rows, int64_t N, int32_t n_rows, c
 constexpr int kSelBins = 256;
 constexpr int kSelPasses = 8;
 constexpr int kSelGroup = 16;
+constexpr int kMaxMemberGroups = 64;
 int32_t select_blocks_per_row(int64_t N, int32_t n_rows);
 // zeroes d_hist[hist_elems], then adds this pass's counts of rows d_rows[n_rows][N] (device array of row pointers); d_w non-null:
-// member i adds d_w[i]; d_base non-null: of the anomalies x - d_base[i] (d_w and d_base 16-byte aligned)
-hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, int64_t N, int32_t n_rows,
-                              int32_t pass, const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s);
+// member i adds d_w[i]; d_base non-null: of the anomalies x - d_base[i] (d_w and d_base 16-byte aligned).  d_group non-null (the
+// grouped select, 8-byte aligned): member i counts only into the histograms of group d_group[i] (-1: none), the buffer being
+// [n_rows][n_groups][256] in pass 0 and [n_rows][n_groups][n_t][256] later, d_prefix [n_rows][n_groups][n_t]: (row, group) is a
+// virtual row of the commit and finish launches
+hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, const int32_t* d_group,
+                              int32_t n_groups, int64_t N, int32_t n_rows, int32_t pass, const uint64_t* d_prefix, int32_t n_t,
+                              int64_t* d_hist, size_t hist_elems, hipStream_t s);
+// *d_flag = 1 if any d_group[i] is outside [-1, n_groups) (the caller zeroes it)
+hipError_t launch_groups_check(const int32_t* d_group, int64_t N, int32_t n_groups, int32_t* d_flag, hipStream_t s);
 // consumes the (reduced) histograms of `pass`: per (row, target) the bucket of its remaining rank; pass 0 also sets d_count[row].
 // d_over non-null: the weighted commit, where d_count is the row's weight W and a row with W > 2^53 sets *d_over and gets NaN
 hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
@@ -830,6 +837,9 @@ hipError_t launch_indicators(const double* const* d_rows, const double* d_time, 
 // non-NaN members.  int64 sums, one integer atomic per block and bin; the caller zeroes d_acc[n_thr + 1].
 hipError_t launch_exceedance(const double* d_v, const int64_t* d_w, int64_t N, int32_t n_thr, const Thresholds& thr,
                              unsigned long long* d_acc, hipStream_t s);
+// the same per group: d_acc[g][n_thr + 1] (hits, then the total) over the members with d_group[i] == g; the caller zeroes it
+hipError_t launch_exceedance_grouped(const double* d_v, const int64_t* d_w, const int32_t* d_group, int32_t n_groups, int64_t N,
+                                     int32_t n_thr, const Thresholds& thr, unsigned long long* d_acc, hipStream_t s);
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);

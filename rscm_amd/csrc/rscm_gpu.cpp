@@ -773,6 +773,7 @@ int rscm_ens_destroy(rscm_ens* h)
     (void)hipFree(h->d_cumw);
     (void)hipFree(h->d_anc);
     (void)hipFree(h->d_base);
+    (void)hipFree(h->d_groups);
     for (double* p : h->d_ind) (void)hipFree(p);
     if (h->plan) {
         (void)hipFree(h->plan->d_ops);

@@ -27,6 +27,10 @@
 // select with every counted member adding its weight instead of 1: one target per quantile, no interpolation.  Weights are int64
 // and W <= 2^53 (the handle refuses weights that sum to more; weights.hip), so every histogram sum -- across workgroups here and
 // across ranks by the caller -- is exact and independent of its order, as the unweighted counts are.
+//
+// The grouped select (kG; rscm_ens_set_member_groups) gives every member a group and every (row, group) its
+// own histograms, targets and result: the same select with (row, group) as the row of the commit and finish kernels and a
+// histogram pass that counts a member only into the histograms of its own group.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -86,11 +90,22 @@ __device__ __forceinline__ void lds_add(SelBin<kW>* bins, unsigned b, SelBin<kW>
 // kAnom: member i counts the key of its anomaly x - base[i] (one IEEE subtraction; a NaN anomaly is left out).  base is
 // handle-owned, hence 16-byte aligned: its pairs line up with the row's only when the row has no unpaired head member.  The
 // plain instantiations (kAnom false) never read base.
-template <bool kW, bool kAnom>
+//
+// kG (the grouped select): member i counts only into the histograms of its own group, group[i] (-1: none).  A row then has
+// n_slots histograms -- slot g in pass 0, slot g * n_t + t later -- laid out [r][n_slots][256], and a launch fills the slots
+// [g0, g0 + gn), gn <= kSelGroup, in LDS exactly as the ungrouped launch fills gn targets.  The group picks the LDS base: a
+// member looks only at the targets of its own group that lie in the launch's slots (at most min(n_t, gn) comparisons, not one
+// per slot), and lds_add gets the bin index within all gn histograms, so a wave whose members share group, target and digit --
+// contiguous groups, clustered keys -- still adds once.  group is handle-owned (16-byte aligned): its ids are read as int2 pairs
+// when the row has no unpaired head member, else one by one, as the weights' pairs are.  The ids are read first, and a lane whose
+// two members belong to no group of the launch's slots does not load them: with contiguous groups the launches after the first
+// skip the rows of the other groups.  The instantiations without kG never read group or n_slots.
+template <bool kW, bool kAnom, bool kG = false>
 __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* const* __restrict__ rows, const int64_t* __restrict__ w,
                                                                    const double* __restrict__ base, int64_t N, int32_t pass,
                                                                    const uint64_t* __restrict__ prefix, int32_t n_t, int32_t g0,
-                                                                   int32_t gn, unsigned long long* __restrict__ hist)
+                                                                   int32_t gn, unsigned long long* __restrict__ hist,
+                                                                   const int32_t* __restrict__ group, int32_t n_slots)
 {
     using Bin = SelBin<kW>;
     Bin* bins;
@@ -103,10 +118,15 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* 
     }
     __shared__ uint64_t pre[kSelGroup];
     const int32_t r = (int32_t)blockIdx.y;
-    const int32_t nh = pass == 0 ? 1 : gn;
+    const int32_t nh = kG ? gn : (pass == 0 ? 1 : gn);
     for (int32_t i = (int32_t)threadIdx.x; i < nh * kSelBins; i += kSelThreads) bins[i] = 0;
-    if ((int32_t)threadIdx.x < nh && pass > 0) pre[threadIdx.x] = prefix[(size_t)r * n_t + g0 + threadIdx.x];
+    if ((int32_t)threadIdx.x < nh && pass > 0) pre[threadIdx.x] = prefix[(size_t)r * (kG ? n_slots : n_t) + g0 + threadIdx.x];
     __syncthreads();
+    // kG: the groups with a slot in this launch, and the targets of one group a member has to look at (the launch's slots lie in
+    // one group: those; else all n_t)
+    const int32_t per_g = pass == 0 ? 1 : n_t;
+    const int32_t g_lo = kG ? g0 / per_g : 0, g_hi = kG ? (g0 + gn - 1) / per_g : 0;
+    const int32_t t_lo = kG && g_lo == g_hi ? g0 - g_lo * per_g : 0, t_hi = kG && g_lo == g_hi ? t_lo + gn : n_t;
 
     const double* row = rows[r];
     // rows start 8-byte aligned (odd N): the first member goes alone, the rest as 16-byte pairs
@@ -117,11 +137,28 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* 
     const int shift = 56 - 8 * pass;   // the digit of this pass: bits [shift, shift + 8)
     const double2* row2 = reinterpret_cast<const double2*>(row + head);
     const int64_t* wp = w + head;   // kW: the weights of the pairs
+    const int32_t* gp = group + head;   // kG: the groups of the pairs
 
-    auto count = [&](double x, Bin v, bool in) {
+    auto count = [&](double x, Bin v, bool in, int32_t g) {
         const bool ok = in && x == x;
         const uint64_t k = order_key(x);
         const unsigned d = (unsigned)(k >> shift) & (kSelBins - 1);
+        if constexpr (kG) {
+            if (pass == 0) {
+                const int32_t s = g - g0;
+                const bool mine = ok && s >= 0 && s < gn;
+                lds_add<kW>(bins, (unsigned)(mine ? s : 0) * kSelBins + d, v, mine);
+                return;
+            }
+            const uint64_t top = k >> (shift + 8);
+            const int32_t sb = g * n_t - g0;   // the member's first slot, relative to the launch's
+            for (int32_t t = t_lo; t < t_hi; ++t) {
+                const bool mine = ok && g >= g_lo && sb + t >= 0 && sb + t < gn;
+                const int32_t s = mine ? sb + t : 0;
+                lds_add<kW>(bins, (unsigned)s * kSelBins + d, v, mine && top == pre[s]);
+            }
+            return;
+        }
         if (pass == 0) {
             lds_add<kW>(bins, d, v, ok);
             return;
@@ -135,7 +172,22 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* 
         const bool in = i < pe;
         double2 v = make_double2(0.0, 0.0);
         Bin v0 = kW ? 0 : 1, v1 = v0;   // what each member of the pair adds
-        if (in) {
+        int32_t ga = -1, gb = -1;
+        bool ld = in;
+        if constexpr (kG) {
+            if (in) {
+                if (head) {
+                    ga = gp[2 * i];
+                    gb = gp[2 * i + 1];
+                } else {
+                    const int2 p = reinterpret_cast<const int2*>(gp)[i];
+                    ga = p.x;
+                    gb = p.y;
+                }
+            }
+            ld = (ga >= g_lo && ga <= g_hi) || (gb >= g_lo && gb <= g_hi);
+        }
+        if (ld) {
             v = row2[i];
             if constexpr (kAnom) {
                 const double* bp = base + head + 2 * i;
@@ -154,8 +206,8 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* 
                 }
             }
         }
-        count(v.x, v0, in);
-        count(v.y, v1, in);
+        count(v.x, v0, in, ga);
+        count(v.y, v1, in, gb);
     }
     if (blockIdx.x == 0 && threadIdx.x < 64) {   // the unpaired head and tail members, one wave
         const bool in_head = head && threadIdx.x == 0;
@@ -168,10 +220,13 @@ __global__ __launch_bounds__(kSelThreads) void select_hist_kernel(const double* 
         }
         Bin v = 1;
         if constexpr (kW) v = in ? (Bin)w[m] : 0ull;
-        count(x, v, in);
+        int32_t g = -1;
+        if constexpr (kG) g = in ? group[m] : -1;
+        count(x, v, in, g);
     }
     __syncthreads();
-    unsigned long long* out = hist + (pass == 0 ? (size_t)r * kSelBins : ((size_t)r * n_t + g0) * kSelBins);
+    unsigned long long* out = hist + (kG ? ((size_t)r * n_slots + g0) * kSelBins
+                                         : (pass == 0 ? (size_t)r * kSelBins : ((size_t)r * n_t + g0) * kSelBins));
     for (int32_t i = (int32_t)threadIdx.x; i < nh * kSelBins; i += kSelThreads)
         if (bins[i]) atomicAdd(out + i, (unsigned long long)bins[i]);
 }
@@ -293,6 +348,14 @@ __global__ void select_finish_kernel(const int64_t* __restrict__ count, const ui
     }
 }
 
+__global__ void groups_check_kernel(const int32_t* __restrict__ group, int64_t N, int32_t n_groups, int32_t* __restrict__ flag)
+{
+    bool bad = false;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (int64_t)gridDim.x * blockDim.x)
+        bad = bad || group[i] < -1 || group[i] >= n_groups;
+    if (bad) *flag = 1;
+}
+
 }  // namespace
 
 int32_t select_blocks_per_row(int64_t N, int32_t n_rows)
@@ -307,15 +370,34 @@ int32_t select_blocks_per_row(int64_t N, int32_t n_rows)
     return (int32_t)b;
 }
 
-hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, int64_t N, int32_t n_rows,
-                              int32_t pass, const uint64_t* d_prefix, int32_t n_t, int64_t* d_hist, size_t hist_elems, hipStream_t s)
+hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, const double* d_base, const int32_t* d_group,
+                              int32_t n_groups, int64_t N, int32_t n_rows, int32_t pass, const uint64_t* d_prefix, int32_t n_t,
+                              int64_t* d_hist, size_t hist_elems, hipStream_t s)
 {
     hipError_t e = hipMemsetAsync(d_hist, 0, hist_elems * sizeof(int64_t), s);
     if (e != hipSuccess || n_rows <= 0 || N <= 0) return e;
-    const auto kernel = d_w ? (d_base ? select_hist_kernel<true, true> : select_hist_kernel<true, false>)
-                            : (d_base ? select_hist_kernel<false, true> : select_hist_kernel<false, false>);
     const unsigned bpr = (unsigned)select_blocks_per_row(N, n_rows);
     constexpr int32_t kMaxGridY = 65535;
+    if (d_group) {   // the grouped select: n_slots histograms per row, kSelGroup of them per launch
+        const auto gkernel = d_w ? (d_base ? select_hist_kernel<true, true, true> : select_hist_kernel<true, false, true>)
+                                 : (d_base ? select_hist_kernel<false, true, true> : select_hist_kernel<false, false, true>);
+        const int32_t n_slots = pass == 0 ? n_groups : n_groups * n_t;
+        for (int32_t r0 = 0; r0 < n_rows; r0 += kMaxGridY) {
+            const int32_t nr = n_rows - r0 < kMaxGridY ? n_rows - r0 : kMaxGridY;
+            auto* h = reinterpret_cast<unsigned long long*>(d_hist) + (size_t)r0 * n_slots * kSelBins;
+            const uint64_t* pre = d_prefix + (size_t)r0 * n_groups * n_t;
+            for (int32_t s0 = 0; s0 < n_slots; s0 += kSelGroup) {
+                const int32_t sn = n_slots - s0 < kSelGroup ? n_slots - s0 : kSelGroup;
+                const size_t lds = d_w ? (size_t)sn * kSelBins * sizeof(unsigned long long) : 0;
+                hipLaunchKernelGGL(gkernel, dim3(bpr, (unsigned)nr), dim3(kSelThreads), lds, s, d_rows + r0, d_w, d_base, N, pass, pre, n_t,
+                                   s0, sn, h, d_group, n_slots);
+                if ((e = hipGetLastError()) != hipSuccess) return e;
+            }
+        }
+        return hipSuccess;
+    }
+    const auto kernel = d_w ? (d_base ? select_hist_kernel<true, true> : select_hist_kernel<true, false>)
+                            : (d_base ? select_hist_kernel<false, true> : select_hist_kernel<false, false>);
     for (int32_t r0 = 0; r0 < n_rows; r0 += kMaxGridY) {   // rows in slices the grid's y dimension can index
         const int32_t nr = n_rows - r0 < kMaxGridY ? n_rows - r0 : kMaxGridY;
         const size_t row_elems = (size_t)kSelBins * (pass == 0 ? 1 : (size_t)n_t);
@@ -325,11 +407,19 @@ hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, c
             const int32_t gn = pass == 0 ? 1 : (n_t - g0 < kSelGroup ? n_t - g0 : kSelGroup);
             const size_t lds = d_w ? (size_t)gn * kSelBins * sizeof(unsigned long long) : 0;   // the weighted bins
             hipLaunchKernelGGL(kernel, dim3(bpr, (unsigned)nr), dim3(kSelThreads), lds, s, d_rows + r0, d_w, d_base, N, pass, pre, n_t, g0,
-                               gn, h);
+                               gn, h, nullptr, 0);
             if ((e = hipGetLastError()) != hipSuccess) return e;
         }
     }
     return hipSuccess;
+}
+
+hipError_t launch_groups_check(const int32_t* d_group, int64_t N, int32_t n_groups, int32_t* d_flag, hipStream_t s)
+{
+    if (N <= 0) return hipSuccess;
+    const int64_t need = (N + 255) / 256;
+    hipLaunchKernelGGL(groups_check_kernel, dim3((unsigned)(need < 1024 ? need : 1024)), dim3(256), 0, s, d_group, N, n_groups, d_flag);
+    return hipGetLastError();
 }
 
 hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,

@@ -9,6 +9,10 @@
 // or two ensembles on one GPU -- sums the int64 buffers of all of them; every handle then commits the same sums and so reaches
 // the same keys.  The weighted select runs the same stages over the handle's int64 member weights: one target per quantile, and
 // pass 0's reduced histograms give each row's weight W, which the first commit checks against 2^53 on every handle.
+//
+// The grouped select (RSCM_SELECT_GROUPED) is the same again with (row, group) as the row of the commit and finish launches: the
+// histogram pass counts each member into its own group's histograms (select.hip), the buffers are [rows][n_groups][...], and
+// count, prefix, rank and out have n_comp x n_groups rows.  The member groups themselves (rscm_ens_set_member_groups) are at the end.
 #include <cmath>
 #include <limits>
 
@@ -23,6 +27,9 @@ struct SelectState {
     int32_t pass = 0;       // the next pass to histogram
     bool awaiting_commit = false;
     bool weighted = false;  // RSCM_SELECT_WEIGHTED, the mode of the kernels: count holds W, n_t == n_q
+    int32_t n_groups = 0;   // RSCM_SELECT_GROUPED: the handle's groups (they cannot change while the select is staged), else 0
+    const int32_t* d_group = nullptr;
+    int32_t v_rows() const { return n_comp * (n_groups ? n_groups : 1); }   // (row, group) pairs: the rows of commit and finish
     const double* d_base = nullptr;   // RSCM_SELECT_ANOMALY: the handle's baseline (it cannot change while the select is staged)
     const double** d_rows = nullptr;
     double* d_q = nullptr;
@@ -64,11 +71,12 @@ constexpr int32_t kMaxSelectVectors = 4096;
 // The checks every select makes first: the flags and what they need, then the quantile list (after the caller's own checks)
 int select_flags(rscm_ens* h, int32_t flags)
 {
-    if (flags & ~(RSCM_SELECT_WEIGHTED | RSCM_SELECT_ANOMALY)) return fail(RSCM_ERR_INVALID, "unknown select flags 0x%x", flags);
+    if (flags & ~(RSCM_SELECT_WEIGHTED | RSCM_SELECT_ANOMALY | RSCM_SELECT_GROUPED)) return fail(RSCM_ERR_INVALID, "unknown select flags 0x%x", flags);
     if ((flags & RSCM_SELECT_WEIGHTED) && !h->d_weights)
         return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
     if ((flags & RSCM_SELECT_ANOMALY) && !h->d_base)
         return fail(RSCM_ERR_STATE, "no baseline: rscm_ens_set_baseline or rscm_ens_set_baseline_values first");
+    if ((flags & RSCM_SELECT_GROUPED) && !h->d_groups) return fail(RSCM_ERR_STATE, "no member groups: rscm_ens_set_member_groups first");
     return RSCM_OK;
 }
 
@@ -88,12 +96,14 @@ int select_setup(rscm_ens* h, SelectState& s, const std::vector<const double*>& 
     s.n_t = weighted ? n_q : 2 * n_q;
     s.weighted = weighted;
     s.d_base = (flags & RSCM_SELECT_ANOMALY) ? h->d_base : nullptr;
+    s.n_groups = (flags & RSCM_SELECT_GROUPED) ? h->n_groups : 0;
+    s.d_group = s.n_groups ? h->d_groups : nullptr;
     s.n_comp = (int32_t)rows.size();
     if (s.n_comp == 0) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
-    const size_t nc = (size_t)s.n_comp, nt = (size_t)s.n_t;
+    const size_t nr = (size_t)s.n_comp, nc = (size_t)s.v_rows(), nt = (size_t)s.n_t;
     s.hist_elems = nc * nt * rscm::kSelBins;
-    HIPCHK(rscm::dev_malloc(&s.d_rows, nc * sizeof(double*)));
+    HIPCHK(rscm::dev_malloc(&s.d_rows, nr * sizeof(double*)));
     HIPCHK(rscm::dev_malloc(&s.d_q, (size_t)n_q * sizeof(double)));
     HIPCHK(rscm::dev_malloc(&s.d_hist, s.hist_elems * sizeof(int64_t)));
     HIPCHK(rscm::dev_malloc(&s.d_count, nc * sizeof(int64_t)));
@@ -101,7 +111,7 @@ int select_setup(rscm_ens* h, SelectState& s, const std::vector<const double*>& 
     HIPCHK(rscm::dev_malloc(&s.d_rank, nc * nt * sizeof(int64_t)));
     HIPCHK(rscm::dev_malloc(&s.d_out, nc * (size_t)(n_q + 1) * sizeof(double)));
     if (weighted) HIPCHK(rscm::dev_malloc(&s.d_over, sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(s.d_rows, rows.data(), nc * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(s.d_rows, rows.data(), nr * sizeof(double*), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipMemcpyAsync(s.d_q, q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));   // the host vectors go out of scope
     return RSCM_OK;
@@ -153,9 +163,9 @@ int select_pass(rscm_ens* h, SelectState& s, int32_t* done, int64_t** buf_dev, i
         return RSCM_OK;
     }
     if (int rc = set_device(h)) return rc;
-    const size_t elems = (size_t)s.n_comp * rscm::kSelBins * (s.pass == 0 ? 1 : (size_t)s.n_t);
-    HIPCHK(rscm::launch_select_hist(s.d_rows, s.weighted ? h->d_weights : nullptr, s.d_base, h->N, s.n_comp, s.pass, s.d_prefix, s.n_t,
-                                    s.d_hist, elems, h->stream));
+    const size_t elems = (size_t)s.v_rows() * rscm::kSelBins * (s.pass == 0 ? 1 : (size_t)s.n_t);
+    HIPCHK(rscm::launch_select_hist(s.d_rows, s.weighted ? h->d_weights : nullptr, s.d_base, s.d_group, s.n_groups, h->N, s.n_comp, s.pass,
+                                    s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     s.awaiting_commit = true;
     *done = 0;
@@ -170,15 +180,17 @@ int select_commit(rscm_ens* h, SelectState& s)
     if (int rc = set_device(h)) return rc;
     const bool check_w = s.weighted && s.pass == 0;   // the first weighted commit checks every row's W against 2^53
     if (check_w) HIPCHK(hipMemsetAsync(s.d_over, 0, sizeof(int32_t), h->stream));
-    HIPCHK(rscm::launch_select_commit(s.d_hist, s.pass, s.n_comp, s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, s.d_over, h->stream));
+    HIPCHK(rscm::launch_select_commit(s.d_hist, s.pass, s.v_rows(), s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, s.d_over, h->stream));
     s.awaiting_commit = false;
     if (++s.pass == rscm::kSelPasses)
-        HIPCHK(rscm::launch_select_finish(s.d_count, s.d_prefix, s.n_comp, s.n_q, s.d_q, s.weighted, s.d_out, h->stream));
+        HIPCHK(rscm::launch_select_finish(s.d_count, s.d_prefix, s.v_rows(), s.n_q, s.d_q, s.weighted, s.d_out, h->stream));
     if (check_w) {
         int32_t over = 0;
         HIPCHK(hipMemcpyAsync(&over, s.d_over, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
-        if (over) return fail(RSCM_ERR_INVALID, "weighted select: the weights of a row's non-NaN members sum to more than 2^53");
+        if (over)
+            return fail(RSCM_ERR_INVALID, "weighted select: the weights of a row's non-NaN members%s sum to more than 2^53",
+                        s.n_groups ? " in one group" : "");
     }
     return RSCM_OK;
 }
@@ -188,17 +200,18 @@ int select_result(rscm_ens* h, SelectState& s, double* out, double* count)
     if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
     if (s.n_comp > 0 && s.pass < rscm::kSelPasses)
         return fail(RSCM_ERR_STATE, "select: %d of %d passes are still to run", rscm::kSelPasses - s.pass, rscm::kSelPasses);
-    std::vector<double> host((size_t)s.n_comp * (s.n_q + 1));
+    const int32_t G = s.n_groups ? s.n_groups : 1;   // out[rows][G][n_q], count[rows][G]
+    std::vector<double> host((size_t)s.v_rows() * (s.n_q + 1));
     if (s.n_comp > 0) {
         if (int rc = set_device(h)) return rc;
         HIPCHK(hipMemcpyAsync(host.data(), s.d_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    for (int32_t r = 0; r < s.n_rows; ++r) {
-        const bool c = r < s.n_comp;
-        if (count) count[r] = c ? host[(size_t)r * (s.n_q + 1)] : 0.0;
+    for (size_t r = 0; r < (size_t)s.n_rows * G; ++r) {
+        const bool c = r < (size_t)s.v_rows();
+        if (count) count[r] = c ? host[r * (s.n_q + 1)] : 0.0;
         for (int32_t k = 0; k < s.n_q; ++k)
-            out[(size_t)r * s.n_q + k] = c ? host[(size_t)r * (s.n_q + 1) + 1 + k] : std::numeric_limits<double>::quiet_NaN();
+            out[r * s.n_q + k] = c ? host[r * (s.n_q + 1) + 1 + k] : std::numeric_limits<double>::quiet_NaN();
     }
     return RSCM_OK;
 }
@@ -540,6 +553,71 @@ int rscm_ens_set_weights_from_loglik(rscm_ens* h, const double* ll, int32_t on_d
         HIPCHK(es);
     }
     return install_weights(h, d_new);   // refused if N weights of up to 2^bits sum to more than 2^53
+    GUARD_END
+}
+
+}  // extern "C"
+
+// ---- member groups of the grouped select and exceedance ----
+
+extern "C" {
+
+int rscm_ens_set_member_groups(rscm_ens* h, const int32_t* group, int32_t on_device, int32_t n_groups)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!group) return fail(RSCM_ERR_INVALID, "groups are NULL");
+    if (n_groups < 1 || n_groups > rscm::kMaxMemberGroups)
+        return fail(RSCM_ERR_INVALID, "n_groups = %d: must be in [1, %d]", n_groups, rscm::kMaxMemberGroups);
+    if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
+    if (int rc = set_device(h)) return rc;
+    int32_t* d_new = nullptr;
+    int32_t* d_flag = nullptr;
+    int32_t bad = 0;
+    const size_t bytes = (size_t)h->N * sizeof(int32_t);
+    hipError_t e = rscm::dev_malloc(&d_new, bytes);
+    if (e == hipSuccess) e = rscm::dev_malloc(&d_flag, sizeof(int32_t));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_new, group, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), h->stream);
+    if (e == hipSuccess) e = rscm::launch_groups_check(d_new, h->N, n_groups, d_flag, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_flag);
+    if (e != hipSuccess || bad) {
+        (void)hipFree(d_new);
+        HIPCHK(e);
+        return fail(RSCM_ERR_INVALID, "a member's group id is outside [-1, %d)", n_groups);
+    }
+    (void)hipFree(h->d_groups);
+    h->d_groups = d_new;
+    h->n_groups = n_groups;
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_member_groups_devptr(rscm_ens* h, void** out, int32_t* n_groups)
+{
+    NEED(h);
+    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
+    *out = h->d_groups;
+    if (n_groups) *n_groups = h->d_groups ? h->n_groups : 0;
+    if (!h->d_groups) return fail(RSCM_ERR_STATE, "no member groups set");
+    return RSCM_OK;
+}
+
+int rscm_ens_clear_member_groups(rscm_ens* h)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
+    if (h->d_groups) {
+        if (int rc = set_device(h)) return rc;
+        HIPCHK(hipStreamSynchronize(h->stream));
+        (void)hipFree(h->d_groups);
+        h->d_groups = nullptr;
+        h->n_groups = 0;
+    }
+    return RSCM_OK;
     GUARD_END
 }
 

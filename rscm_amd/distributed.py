@@ -163,7 +163,7 @@ def _reduce_select(sel, group=None) -> Dict[str, np.ndarray]:
 
 
 def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                         group=None, weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
+                         group=None, weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
     """Quantiles of the WHOLE sharded ensemble (``Ensemble.quantile_rows`` of all ranks' members together), on every rank.
 
     Each rank runs the staged radix select on its own shard (``Ensemble.select``); between the passes the ranks sum their
@@ -176,35 +176,48 @@ def quantile_rows_global(ensemble, var, q, t_begin: int = 0, t_end: Optional[int
     the ranks' member weights on one scale (``ShardedEnsemble.constrain``); the histograms then hold int64 weight sums and
     the result has ``"weight"`` in place of ``"count"``.
 
-    ``anomaly``: of each member's anomaly against its baseline (every rank's ``Ensemble.set_baseline`` over the same rows)."""
-    # a keyword goes to the ensemble only when set: an ensemble-like object that has no weighted or anomaly form need not take it
+    ``anomaly``: of each member's anomaly against its baseline (every rank's ``Ensemble.set_baseline`` over the same rows).
+
+    ``grouped``: per member group (every rank's ``Ensemble.set_member_groups`` for its own members, with the same ``n_groups``
+    on every rank; a rank may hold no member of a group): the buffers carry one histogram per group, the result is group-major."""
+    # a keyword goes to the ensemble only when set: an ensemble-like object that has no weighted, anomaly or grouped form need not take it
     kw = {}
     if weighted:
         kw["weighted"] = True
     if anomaly:
         kw["anomaly"] = True
+    if grouped:
+        kw["grouped"] = True
     if not is_distributed():
         return ensemble.quantile_rows(var, q, t_begin, t_end, t_stride, **kw)
     return _reduce_select(ensemble.select(var, q, t_begin, t_end, t_stride, **kw), group)
 
 
-def quantile_vectors_global(ensemble, vectors, q, group=None, weighted: bool = False) -> Dict[str, np.ndarray]:
+def quantile_vectors_global(ensemble, vectors, q, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
     """``Ensemble.quantile_vectors`` of the WHOLE sharded ensemble on every rank: each rank passes its shard of each vector
     (its members' indicators, parameter rows ...) in the same order; the histograms are summed as in ``quantile_rows_global``."""
+    kw = {"grouped": True} if grouped else {}
     if not is_distributed():
-        return ensemble.quantile_vectors(vectors, q, weighted=weighted)
-    return _reduce_select(ensemble.select_vectors(vectors, q, weighted=weighted), group)
+        return ensemble.quantile_vectors(vectors, q, weighted=weighted, **kw)
+    return _reduce_select(ensemble.select_vectors(vectors, q, weighted=weighted, **kw), group)
 
 
-def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool = False) -> Dict[str, object]:
+def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
     """``Ensemble.exceedance`` of the WHOLE sharded ensemble on every rank: the ranks' int64 hits and totals are SUM-reduced
-    (exact and independent of order), then ``probability = hits / total``."""
-    from .ensemble import exceedance_result
-    local = ensemble.exceedance(vector, thresholds, weighted=weighted)
+    (exact and independent of order), then ``probability = hits / total``.  ``grouped``: per member group, ``[G][k] + [G]`` int64
+    in one reduction (the same ``n_groups`` on every rank)."""
+    from .ensemble import exceedance_grouped_result, exceedance_result
+    local = ensemble.exceedance(vector, thresholds, weighted=weighted, **({"grouped": True} if grouped else {}))
     if not is_distributed():
         return local
     import torch
     d = _dist()
+    if grouped:
+        hits = np.asarray(local["hits"], dtype=np.int64)
+        t = torch.from_numpy(np.concatenate([hits.ravel(), np.asarray(local["total"], dtype=np.int64)])).to(_device_for_backend())
+        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+        acc = t.cpu().numpy()
+        return exceedance_grouped_result(acc[:hits.size].reshape(hits.shape), acc[hits.size:])
     t = torch.from_numpy(np.append(np.asarray(local["hits"], dtype=np.int64), np.int64(local["total"]))).to(_device_for_backend())
     d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
     acc = t.cpu().numpy()
@@ -304,18 +317,19 @@ class ShardedEnsemble:
         return reduce_summary(self.ensemble.summary(var, tidx))
 
     def quantile_rows_global(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                             weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
+                             weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Quantiles of the global ensemble at the rows ``t_begin, t_begin + t_stride, ... < t_end`` (``quantile_rows_global``);
-        ``weighted``: with the member weights ``constrain`` set; ``anomaly``: of the anomalies against the members' baselines."""
-        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly)
+        ``weighted``: with the member weights ``constrain`` set; ``anomaly``: of the anomalies against the members' baselines;
+        ``grouped``: per member group."""
+        return quantile_rows_global(self.ensemble, var, q, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, grouped=grouped)
 
-    def quantile_vectors_global(self, vectors, q, weighted: bool = False) -> Dict[str, np.ndarray]:
+    def quantile_vectors_global(self, vectors, q, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Quantiles of per-member vectors of the global ensemble (``quantile_vectors_global``)."""
-        return quantile_vectors_global(self.ensemble, vectors, q, weighted=weighted)
+        return quantile_vectors_global(self.ensemble, vectors, q, weighted=weighted, grouped=grouped)
 
-    def exceedance_global(self, vector, thresholds, weighted: bool = False) -> Dict[str, object]:
+    def exceedance_global(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""
-        return exceedance_global(self.ensemble, vector, thresholds, weighted=weighted)
+        return exceedance_global(self.ensemble, vector, thresholds, weighted=weighted, grouped=grouped)
 
     def constrain(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, bits: Optional[int] = None, reference=None):
         """Weight this rank's members by their fit to observations, on one scale across all ranks: the Gaussian

@@ -438,7 +438,7 @@ class Ensemble:
         return {"count": cnt.astype(np.int64), "quantiles": out}
 
     def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-                      weighted: bool = False, anomaly: bool = False) -> Dict[str, np.ndarray]:
+                      weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """``quantile_series``'s numbers (the same bits) over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any
         storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows_ex: a radix
         select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``.
@@ -448,23 +448,28 @@ class Ensemble:
         ``{"weight": [rows] (summed weight of the non-NaN members), "quantiles": [rows][len(q)]}``.
 
         ``anomaly``: the same quantiles of each member's own anomaly ``x[i] - b[i]`` against the baseline (``set_baseline``;
-        RSCM_SELECT_ANOMALY) -- not the plume minus a quantile of the baseline."""
+        RSCM_SELECT_ANOMALY) -- not the plume minus a quantile of the baseline.
+
+        ``grouped``: one result per member group (``set_member_groups``; RSCM_SELECT_GROUPED), each exactly what the call
+        returns for an ensemble of that group's members alone, from one series of passes over the rows.  Group-major:
+        ``{"count" | "weight": [G][rows], "quantiles": [G][rows][len(q)]}``."""
         qq = np.atleast_1d(L.f64(q))
         t_end = self.n_times if t_end is None else t_end
         rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
-        out, cnt = np.empty((rows, qq.size)), np.empty(rows)
-        flags = L.SELECT_WEIGHTED * bool(weighted) | L.SELECT_ANOMALY * bool(anomaly)
+        G = self._n_groups(grouped)
+        out, cnt = np.empty((rows, G, qq.size)), np.empty((rows, G))
+        flags = select_flags(weighted, anomaly, grouped)
         L.check(self._lib.rscm_ens_quantile_rows_ex(self._h, self._var(var), t_begin, t_end, t_stride, qq.size, L.dptr(qq), flags,
                                                     L.dptr(out), L.dptr(cnt)))
-        return {"weight" if weighted else "count": cnt.astype(np.int64), "quantiles": out}
+        return select_result(out, cnt, weighted, grouped)
 
     def select(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
-               weighted: bool = False, anomaly: bool = False) -> "QuantileSelect":
+               weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> "QuantileSelect":
         """``quantile_rows`` in stages, for a caller that sums the histograms of several handles between the passes (the
         shards of one ensemble: ``rscm_amd.distributed.quantile_rows_global``).  Use as a context manager.  ``weighted``: the
         weighted select; ``result()`` then returns ``{"weight", "quantiles"}``.  ``anomaly``: of the anomalies against the
-        baseline."""
-        return QuantileSelect(self, var, q, t_begin, t_end, t_stride, weighted, anomaly)
+        baseline.  ``grouped``: per member group; every handle of one sharded select must carry the same number of groups."""
+        return QuantileSelect(self, var, q, t_begin, t_end, t_stride, weighted, anomaly, grouped=grouped)
 
     # -- baseline, per-member indicators, exceedance ------------------------------------------
     def set_baseline(self, var, t_begin: int, t_end: int, t_stride: int = 1) -> None:
@@ -520,26 +525,84 @@ class Ensemble:
         arr = (C.POINTER(C.c_double) * len(vs))(*[C.cast(C.c_void_p(v.ptr), C.POINTER(C.c_double)) for v in vs])
         return arr, len(vs)
 
-    def quantile_vectors(self, vectors, q, weighted: bool = False) -> Dict[str, np.ndarray]:
+    def quantile_vectors(self, vectors, q, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """``quantile_rows``' quantiles with device vectors of ``[N]`` float64 as the rows: indicators, parameter rows
-        (``params_vector``), a log-likelihood.  Returns ``{"count" | "weight": [len(vectors)], "quantiles": [len(vectors)][len(q)]}``."""
+        (``params_vector``), a log-likelihood.  Returns ``{"count" | "weight": [len(vectors)], "quantiles": [len(vectors)][len(q)]}``;
+        with ``grouped`` per member group, group-major as ``quantile_rows``."""
         arr, n_vec = self._vectors(vectors)
         qq = np.atleast_1d(L.f64(q))
-        out, cnt = np.empty((n_vec, qq.size)), np.empty(n_vec)
-        L.check(self._lib.rscm_ens_quantile_vectors(self._h, n_vec, arr, qq.size, L.dptr(qq), L.SELECT_WEIGHTED if weighted else 0,
+        G = self._n_groups(grouped)
+        out, cnt = np.empty((n_vec, G, qq.size)), np.empty((n_vec, G))
+        L.check(self._lib.rscm_ens_quantile_vectors(self._h, n_vec, arr, qq.size, L.dptr(qq), select_flags(weighted, False, grouped),
                                                     L.dptr(out), L.dptr(cnt)))
-        return {"weight" if weighted else "count": cnt.astype(np.int64), "quantiles": out}
+        return select_result(out, cnt, weighted, grouped)
 
-    def select_vectors(self, vectors, q, weighted: bool = False) -> "QuantileSelect":
+    def select_vectors(self, vectors, q, weighted: bool = False, grouped: bool = False) -> "QuantileSelect":
         """``quantile_vectors`` in stages (``select``'s protocol): ``rscm_amd.distributed.quantile_vectors_global``."""
-        return QuantileSelect(self, None, q, 0, None, 1, weighted, vectors=vectors)
+        return QuantileSelect(self, None, q, 0, None, 1, weighted, vectors=vectors, grouped=grouped)
 
-    def exceedance(self, vector, thresholds, weighted: bool = False) -> Dict[str, object]:
+    # -- member groups (the grouped quantiles and exceedance) ----------------------------------
+    def set_member_groups(self, groups, n_groups: Optional[int] = None) -> None:
+        """Member groups for the ``grouped=True`` statistics: ``[N]`` int32 ids, -1 (the member is in no group) or
+        ``0 <= id < n_groups <= 64``; a numpy array or an int32 ``DeviceVector`` on this ensemble's GPU.  ``n_groups`` defaults to
+        ``max + 1`` for host arrays.  They stay across ``run``, ``rewind`` and a ``branch`` into this ensemble."""
+        if isinstance(groups, DeviceVector):
+            if groups.n != self.n_members or groups.dtype != np.int32:
+                raise ValueError(f"groups: need an int32 device vector of {self.n_members} members")
+            if n_groups is None:
+                raise ValueError("groups: n_groups is needed with a device vector")
+            L.check(self._lib.rscm_ens_set_member_groups(self._h, C.cast(C.c_void_p(groups.ptr), C.POINTER(C.c_int32)), 1, int(n_groups)))
+            return
+        a = np.asarray(groups)
+        if a.shape != (self.n_members,):
+            raise ValueError(f"groups: need {self.n_members} values, got shape {a.shape}")
+        if not np.issubdtype(a.dtype, np.integer):
+            raise TypeError("groups must be integers")
+        if n_groups is None:
+            n_groups = max(int(a.max()) + 1, 1)
+        a = np.ascontiguousarray(a, dtype=np.int32)
+        L.check(self._lib.rscm_ens_set_member_groups(self._h, L.iptr(a), 0, int(n_groups)))
+
+    def member_groups_device(self) -> DeviceVector:
+        """The group ids as an int32 ``DeviceVector`` carrying ``n_groups``."""
+        p, g = C.c_void_p(), C.c_int32(0)
+        L.check(self._lib.rscm_ens_member_groups_devptr(self._h, C.byref(p), C.byref(g)))
+        v = DeviceVector(p.value, self.n_members, np.int32, self)
+        v.n_groups = g.value
+        return v
+
+    def member_groups(self) -> np.ndarray:
+        """The member groups, ``[N]`` int32, copied to the host."""
+        return self.member_groups_device().to_host()
+
+    @property
+    def n_groups(self) -> int:
+        """The number of member groups set, 0 if none."""
+        p, g = C.c_void_p(), C.c_int32(0)
+        self._lib.rscm_ens_member_groups_devptr(self._h, C.byref(p), C.byref(g))
+        return g.value
+
+    def clear_member_groups(self) -> None:
+        L.check(self._lib.rscm_ens_clear_member_groups(self._h))
+
+    def _n_groups(self, grouped: bool) -> int:
+        """The group dimension of a result buffer: 1 without ``grouped`` (and without groups: the library then refuses the call)."""
+        return max(self.n_groups, 1) if grouped else 1
+
+    def exceedance(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """Exceedance of a ``[N]`` float64 ``DeviceVector``: ``{"hits": [k] int64 (members, or with ``weighted`` their summed
         weight, with ``v >= thresholds[k]``), "total": int64 (non-NaN members or their weight), "probability": hits / total}``
-        (NaN where total is 0).  Integer sums, so those of shards add up to the whole ensemble's."""
+        (NaN where total is 0).  Integer sums, so those of shards add up to the whole ensemble's.  ``grouped``: per member group,
+        ``{"hits": [G][k], "total": [G], "probability": [G][k]}``."""
         (arr, _n) = self._vectors([vector])
         thr = np.ascontiguousarray(np.atleast_1d(np.asarray(thresholds, dtype=np.float64)))
+        if grouped:
+            G = self._n_groups(True)
+            ghits, gtotal = np.zeros((G, thr.size), dtype=np.int64), np.zeros(G, dtype=np.int64)
+            L.check(self._lib.rscm_ens_exceedance_grouped(self._h, arr[0], thr.size, L.dptr(thr), int(bool(weighted)),
+                                                          ghits.ctypes.data_as(C.POINTER(C.c_int64)),
+                                                          gtotal.ctypes.data_as(C.POINTER(C.c_int64))))
+            return exceedance_grouped_result(ghits, gtotal)
         hits, total = np.zeros(thr.size, dtype=np.int64), C.c_int64(0)
         L.check(self._lib.rscm_ens_exceedance(self._h, arr[0], thr.size, L.dptr(thr), int(bool(weighted)),
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total)))
@@ -668,7 +731,8 @@ class Ensemble:
         """An equally weighted posterior ensemble ready to project: ``dst = factory(n_draws * scenarios)`` (an ``Ensemble`` of
         this kind on this axis, mode and device), the same ``n_draws`` resampled members gathered into each of the
         ``scenarios`` blocks.  Returns ``(dst, scenario_of_member)`` with ``scenario_of_member = repeat(arange(scenarios),
-        n_draws)`` for the caller's ``dst.set_forcing(series, scenario_of_member)``."""
+        n_draws)`` for the caller's ``dst.set_forcing(series, scenario_of_member)``.  The same vector becomes ``dst``'s member
+        groups (``set_member_groups``), so ``dst.quantile_rows(var, q, grouped=True)`` is the plume per scenario."""
         n_draws, scenarios = int(n_draws), int(scenarios)
         if n_draws < 1 or scenarios < 1:
             raise ValueError("need n_draws >= 1 and scenarios >= 1")
@@ -676,7 +740,10 @@ class Ensemble:
         dst = factory(n_draws * scenarios)
         for sidx in range(scenarios):
             self.branch(dst, anc, sidx * n_draws)
-        return dst, np.repeat(np.arange(scenarios, dtype=np.int32), n_draws)
+        scenario_of_member = np.repeat(np.arange(scenarios, dtype=np.int32), n_draws)
+        if scenarios <= 64:   # more scenarios than the library has groups: the blocks stay ungrouped
+            dst.set_member_groups(scenario_of_member, scenarios)
+        return dst, scenario_of_member
 
 
 def weights_stats_result(total: int, n_nonzero: int, w_max: int, sum_sq: int) -> Dict[str, object]:
@@ -703,6 +770,29 @@ def exceedance_result(hits, total: int) -> Dict[str, object]:
     return {"hits": hits, "total": total, "probability": prob}
 
 
+def exceedance_grouped_result(hits, total) -> Dict[str, object]:
+    """The grouped form: ``hits[G][k]``, ``total[G]``; a group without weight has NaN probabilities."""
+    hits, total = np.asarray(hits, dtype=np.int64), np.asarray(total, dtype=np.int64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        prob = np.where(total[:, None] != 0, hits.astype(np.float64) / total.astype(np.float64)[:, None], np.nan)
+    return {"hits": hits, "total": total, "probability": prob}
+
+
+def select_flags(weighted: bool, anomaly: bool, grouped: bool) -> int:
+    return L.SELECT_WEIGHTED * bool(weighted) | L.SELECT_ANOMALY * bool(anomaly) | L.SELECT_GROUPED * bool(grouped)
+
+
+def select_result(out: np.ndarray, cnt: np.ndarray, weighted: bool, grouped: bool) -> Dict[str, np.ndarray]:
+    """The result dict of a select from the library's ``out[rows][G][n_q]`` and ``count[rows][G]``: group-major with ``grouped``,
+    the group axis dropped without."""
+    cnt = cnt.astype(np.int64)
+    if grouped:
+        out, cnt = np.ascontiguousarray(out.transpose(1, 0, 2)), np.ascontiguousarray(cnt.T)
+    else:
+        out, cnt = out[:, 0, :], cnt[:, 0]
+    return {"weight" if weighted else "count": cnt, "quantiles": out}
+
+
 def default_weight_bits(n_total: int) -> int:
     """The quantisation depth that keeps ``n_total`` weights of at most ``2**bits`` summing to at most 2^53."""
     n = int(n_total)
@@ -722,11 +812,13 @@ class QuantileSelect:
     """
 
     def __init__(self, ens: Ensemble, var, q, t_begin: int, t_end: Optional[int], t_stride: int, weighted: bool = False,
-                 anomaly: bool = False, vectors=None):
+                 anomaly: bool = False, vectors=None, grouped: bool = False):
         self.ens = ens
         self.q = np.atleast_1d(L.f64(q))
         self.weighted = bool(weighted)
-        flags = L.SELECT_WEIGHTED * bool(weighted) | L.SELECT_ANOMALY * bool(anomaly)
+        self.grouped = bool(grouped)
+        self.n_groups = ens._n_groups(grouped)
+        flags = select_flags(weighted, anomaly, grouped)
         if vectors is not None:                      # rscm_ens_select_begin_vectors: the vectors are the rows
             arr, self.rows = ens._vectors(vectors)
             L.check(ens._lib.rscm_ens_select_begin_vectors(ens._h, self.rows, arr, self.q.size, L.dptr(self.q), flags))
@@ -758,9 +850,9 @@ class QuantileSelect:
         L.check(self.ens._lib.rscm_ens_select_commit(self.ens._h))
 
     def result(self) -> Dict[str, np.ndarray]:
-        out, cnt = np.empty((self.rows, self.q.size)), np.empty(self.rows)
+        out, cnt = np.empty((self.rows, self.n_groups, self.q.size)), np.empty((self.rows, self.n_groups))
         L.check(self.ens._lib.rscm_ens_select_result(self.ens._h, L.dptr(out), L.dptr(cnt)))
-        return {"weight" if self.weighted else "count": cnt.astype(np.int64), "quantiles": out}
+        return select_result(out, cnt, self.weighted, self.grouped)
 
     def close(self) -> None:
         if self._open:
