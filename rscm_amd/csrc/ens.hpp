@@ -1,5 +1,5 @@
 // Host-side internals shared by the translation units of librscm_gpu.so (rscm_gpu.cpp: handles, validation,
-// marshalling; lockstep.cpp: the lock-step scheduler of component graphs).  Not part of the boundary
+// marshalling; lockstep.cpp: the lock-step scheduler of component graphs; loglik_host.cpp: the likelihoods).  Not part of the boundary
 // (include/rscm_gpu.h) and not visible outside the library (-fvisibility=hidden).
 #pragma once
 
@@ -311,6 +311,8 @@ int step_links(rscm_ens* h, int32_t step_begin, int32_t step_end, rscm::InputLin
 int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::InputLinks& links, int32_t linked, rscm::GroupOp* op_out);
 int step_finish(rscm_ens* h, int32_t step_begin, int32_t step_end);
 int run_range(rscm_ens* h, int32_t step_begin, int32_t step_end, bool timed);
+// what every two-layer launch takes from the handle: step_launch and the fused run + likelihood (loglik_host.cpp)
+rscm::TwoLayerArgs two_layer_args(const rscm_ens* h, int32_t step_begin, int32_t step_end);
 }
 // frees the staged select in flight on h, if any (select_host.cpp)
 void select_release(rscm_ens* h);
@@ -324,8 +326,37 @@ int check_member_vector(const rscm_ens* h, const double* p, const char* what);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (rscm_gpu.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
 
-// the fused run+likelihood pieces the sampler (sampler_host.cpp) shares with rscm_ens_run_loglik (rscm_gpu.cpp)
+// An observation list and its reference periods as the boundary passes them.  owner: the handle of a list that each entry refers
+// to (the graph sampler), null: all refer to the first.
+struct ObsList {
+    int32_t n;
+    const int32_t *owner, *var, *tidx;
+    const double *value, *sigma;
+    int32_t normalize;
+};
+struct RefList {
+    int32_t n;
+    const int32_t *owner, *var, *begin, *end, *stride;
+};
+// ... resolved to the device rows the stored-series likelihood reads (loglik_kernel, ensemble_ops.hip)
+struct LoglikRows {
+    std::vector<const double*> obs_rows, ref_rows;   // observation j's row; entry e averages ref_rows[ref_off[e] .. ref_off[e + 1])
+    std::vector<int32_t> grp, obs_ref, ref_off;      // observation j's group and its group's reference entry (-1: none)
+    int32_t last_row = 0;      // the last row any of them reads
+    bool uncomputed = false;   // a row beyond its handle's time index is read: every member scores -inf, no row is resolved
+    std::vector<unsigned char> staging;   // upload_loglik's host copy of the table, the source of its asynchronous copy
+};
+// the likelihood's host side (loglik_host.cpp), shared with the sampler (sampler_host.cpp)
 extern "C" {
+// Validates the lists against the handles and resolves the rows.  whole_series: the samplers' evaluators, which store their whole series
+// and are run afresh for every score (rows at series(var) + t * N, the time index does not matter); else a handle's own likelihood (rows
+// where they are resident, rscm_ens::row_ptr; RSCM_ERR_STATE if one is not).
+int resolve_loglik_rows(rscm_ens* const* handles, int32_t n_handles, bool whole_series, const ObsList& o, const RefList& r, LoglikRows* out);
+// Lays rows, values, sigmas, groups and reference tables out in one device allocation, *d_blob (hipFree'd by the caller, also after a
+// failure), and points *args into it: ready for launch_loglik on `stream`.  The copy is enqueued on `stream` from rows.staging: rows
+// must live until the caller has synchronised that stream.
+int upload_loglik(LoglikRows& rows, const ObsList& o, int64_t n_members, double* out, hipStream_t stream, void** d_blob,
+                  rscm::LoglikArgs* args);
 int prepare_obs(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value, const double* obs_sigma,
                 int32_t normalize);
 // reference periods for the observations prepare_obs holds (n_ref == 0: none): validates, lays out the deferred observations' scratch
@@ -334,12 +365,6 @@ int prepare_ref(rscm_ens* h, int32_t n_ref, const int32_t* ref_var, const int32_
 // (per owner where ref_owner is given: the graph sampler)
 int check_reference(int32_t T, int32_t n_ref, const int32_t* ref_owner, const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
                     const int32_t* ref_stride);
-// The stored-series likelihood with reference periods, ready to launch: observation j reads obs_rows[j] and belongs to group grp[j];
-// obs_ref[j] is its group's reference entry (-1: none), entry e averages ref_rows[ref_off[e] .. ref_off[e + 1]).  *d_blob (hipFree'd by
-// the caller) holds the tables *args points into.
-int upload_loglik_ref(int32_t n_obs, const double* const* obs_rows, const double* obs_value, const double* obs_sigma, const int32_t* grp,
-                      const int32_t* obs_ref, int32_t n_ref, const int32_t* ref_off, const double* const* ref_rows, int32_t normalize,
-                      int64_t n_members, double* out, void** d_blob, rscm::LoglikRefArgs* args);
 int check_loglik_ready(rscm_ens* h);
 hipError_t launch_loglik(rscm_ens* h);   // asynchronous, with the prepared observations; fills h->d_loglik
 }

@@ -119,62 +119,38 @@ __global__ __launch_bounds__(kBlock) void window_batch_kernel(const WindowBatch 
 // normalised: l -= 0.5*ln(2*pi); l -= ln(sigma).  Per-variable partial sums, then their total
 // (likelihood.rs:206-226, 238-248).  A non-finite model value is a member failure -> -inf
 // (likelihood.rs:216-221, sampler/ensemble.rs:163-172).
+// Reference periods ("Reference periods"): at the start of a group whose obs_ref is >= 0 the thread forms its
+// member's b -- the reference rows summed in row order, divided by their count: the bits of rscm_ens_set_baseline -- and scores the
+// group's observations with m - b (one subtraction: RSCM_SELECT_ANOMALY's bits).  A non-finite b fails the member.  Row reads are
+// coalesced [row][member], as the observation rows are.
+// One body, instantiated twice: REF = false, launched for a table without periods (LoglikArgs::obs_ref null), leaves the reference
+// bookkeeping out of the loop.  The kernel is bound by instruction issue, and as one instantiation the period-free launch was 9-23 %
+// slower than the kernel it replaces in every form tried (profiles/loglik_one_path.txt).
+template <bool REF>
 __global__ __launch_bounds__(kBlock) void loglik_kernel(LoglikArgs a)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
     const double ln_2pi = 1.8378770664093453;  // ln(2*pi) rounded to f64
     double total = 0.0, partial = 0.0;
+    [[maybe_unused]] double b = 0.0;
     bool bad = false;
+    [[maybe_unused]] bool anom = false;
     for (int32_t j = 0; j < a.n_obs; ++j) {
-        if (j > 0 && a.obs_group[j] != a.obs_group[j - 1]) {
-            total += partial;
-            partial = 0.0;
-        }
-        const double m = a.obs_series[j][i];
-        if (!is_finite(m)) {
-            bad = true;
-            break;
-        }
-        const double sigma = a.obs_sigma[j];
-        const double residual = a.obs_value[j] - m;
-        const double chi = (residual * residual) / (sigma * sigma);
-        double l = -0.5 * chi;
-        if (a.normalize) {
-            l -= 0.5 * ln_2pi;
-            l -= log(sigma);
-        }
-        partial += l;
-    }
-    total += partial;
-    a.out[i] = bad ? -__builtin_inf() : total;
-}
-
-// The same with reference periods ("Reference periods"): at the start of a group that has one the thread forms its
-// member's b -- the reference rows summed in row order, divided by their count: the bits of rscm_ens_set_baseline -- and scores the
-// group's observations with m - b (one subtraction: RSCM_SELECT_ANOMALY's bits).  A non-finite b fails the member.  Row reads are
-// coalesced [row][member], as the observation rows are.
-__global__ __launch_bounds__(kBlock) void loglik_ref_kernel(LoglikRefArgs r)
-{
-    const LoglikArgs& a = r.lik;
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= a.n_members) return;
-    const double ln_2pi = 1.8378770664093453;  // ln(2*pi) rounded to f64
-    double total = 0.0, partial = 0.0, b = 0.0;
-    bool bad = false, anom = false;
-    for (int32_t j = 0; j < a.n_obs; ++j) {
+        // the row is asked for first: the uniform loads of the group's bookkeeping then overlap its latency instead of preceding it
+        double m = a.obs_series[j][i];
         const bool first = j == 0 || a.obs_group[j] != a.obs_group[j - 1];
         if (first && j > 0) {
             total += partial;
             partial = 0.0;
         }
-        if (first) {
-            const int32_t e = r.obs_ref[j];
+        if (REF && first) {
+            const int32_t e = a.obs_ref[j];
             anom = e >= 0;
             if (anom) {
-                const int32_t k0 = r.ref_off[e], k1 = r.ref_off[e + 1];
-                double sum = r.ref_rows[k0][i];
-                for (int32_t k = k0 + 1; k < k1; ++k) sum += r.ref_rows[k][i];
+                const int32_t k0 = a.ref_off[e], k1 = a.ref_off[e + 1];
+                double sum = a.ref_rows[k0][i];
+                for (int32_t k = k0 + 1; k < k1; ++k) sum += a.ref_rows[k][i];
                 b = sum / (double)(k1 - k0);
                 if (!is_finite(b)) {
                     bad = true;
@@ -182,12 +158,11 @@ __global__ __launch_bounds__(kBlock) void loglik_ref_kernel(LoglikRefArgs r)
                 }
             }
         }
-        double m = a.obs_series[j][i];
         if (!is_finite(m)) {
             bad = true;
             break;
         }
-        if (anom) m = m - b;
+        if (REF && anom) m = m - b;
         const double sigma = a.obs_sigma[j];
         const double residual = a.obs_value[j] - m;
         const double chi = (residual * residual) / (sigma * sigma);
@@ -451,16 +426,9 @@ hipError_t launch_broadcast_row(double* row, int64_t n, const double* src, int64
 hipError_t launch_loglik(const LoglikArgs& a, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
-    hipLaunchKernelGGL(loglik_kernel, dim3((unsigned)((a.n_members + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_loglik_ref(const LoglikRefArgs& a, hipStream_t s)
-{
-    if (a.lik.n_members <= 0) return hipSuccess;
-    hipLaunchKernelGGL(loglik_ref_kernel, dim3((unsigned)((a.lik.n_members + kBlock - 1) / kBlock)),
-                       dim3(kBlock), 0, s, a);
+    const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
+    if (a.obs_ref) hipLaunchKernelGGL(loglik_kernel<true>, grid, dim3(kBlock), 0, s, a);
+    else hipLaunchKernelGGL(loglik_kernel<false>, grid, dim3(kBlock), 0, s, a);
     return hipGetLastError();
 }
 

@@ -625,15 +625,11 @@ struct LoglikArgs {
     const double* obs_value;
     const double* obs_sigma;
     double* out;                      // [N]
-};
-
-// loglik_kernel with reference periods (loglik_ref_kernel): the observations of a group whose obs_ref is r >= 0 are scored as anomalies
-// from b = (the sum of the rows ref_rows[ref_off[r] .. ref_off[r + 1]) in that order) / their count.
-struct LoglikRefArgs {
-    LoglikArgs lik;
-    const int32_t* obs_ref;            // [n_obs] reference entry of the observation's group, -1: none
-    const int32_t* ref_off;            // [n_ref + 1] offsets into ref_rows
-    const double* const* ref_rows;     // device pointers to the [N] reference rows
+    // reference periods: the observations of a group whose obs_ref is r >= 0 are scored as anomalies from
+    // b = (the sum of the rows ref_rows[ref_off[r] .. ref_off[r + 1]) in that order) / their count
+    const int32_t* obs_ref;           // [n_obs] reference entry of the observation's group, -1: none; null: no group has one
+    const int32_t* ref_off;           // [n_ref + 1] offsets into ref_rows
+    const double* const* ref_rows;    // device pointers to the [N] reference rows
 };
 
 // One component of a fused lock-step launch (csrc/group.hip): the arguments its own kernel would get;
@@ -719,7 +715,6 @@ hipError_t launch_sampler_accept(const SamplerArgs& a, hipStream_t s);
 hipError_t launch_sampler_pack(const SamplerArgs& a, hipStream_t s);
 hipError_t launch_sampler_unpack(const SamplerArgs& a, hipStream_t s);
 hipError_t launch_loglik(const LoglikArgs& a, hipStream_t s);
-hipError_t launch_loglik_ref(const LoglikRefArgs& a, hipStream_t s);
 hipError_t launch_fill(double* p, int64_t n, double v, hipStream_t s);
 hipError_t launch_broadcast_row(double* row, int64_t n, const double* src, int64_t n_src,
                                 hipStream_t s);

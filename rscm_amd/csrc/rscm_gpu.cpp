@@ -1625,6 +1625,36 @@ static int run_member_split(rscm_ens* h, const MemberSplit& m, int32_t step_begi
     return RSCM_OK;
 }
 
+// What every launch of the two-layer kernels takes from the handle (step_launch here, the fused run + likelihood of loglik_host.cpp):
+// members, axis, shared forcing and scenarios, sub-step table, guard hooks, series, status.
+rscm::TwoLayerArgs two_layer_args(const rscm_ens* h, int32_t step_begin, int32_t step_end)
+{
+    const size_t lds_bytes = (size_t)h->n_scen * (size_t)(step_end - step_begin) * sizeof(double);
+    rscm::TwoLayerArgs a{};
+    a.n_members = h->N;
+    a.row_stride = h->N;
+    a.n_times = h->T;
+    a.step_begin = step_begin;
+    a.step_end = step_end;
+    a.n_scen = h->n_scen;
+    a.src_off = h->source == RSCM_SRC_UPSTREAM ? 1 : 0;
+    a.lds_forcing = lds_bytes <= (size_t)rscm::kMaxLds - 1024 ? 1 : 0;
+    a.params = h->d_params;
+    a.uniform_rows = h->uniform_rows;
+    a.forcing = h->d_forcing;
+    a.scen = h->d_scen;
+    a.nsub = h->d_nsub_tl;
+    a.h = h->h_tl;
+    a.h_half = h->h_tl / 2.0;
+    a.h_sixth = h->h_tl / 6.0;
+    a.numerator_guard = t_tl_numerator_guard;
+    a.count_guards = t_tl_count_guards;
+    a.ts = h->series(RSCM_TL_VAR_TS);
+    a.td = h->series(RSCM_TL_VAR_TD);
+    a.status = h->d_status;
+    return a;
+}
+
 int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::InputLinks& links, int32_t linked,
                 rscm::GroupOp* op_out)
 {
@@ -1632,34 +1662,14 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
     const size_t lds_bytes = (size_t)h->n_scen * (size_t)len * sizeof(double);
     if (!op_out) h->last_blocks = h->last_chunks = 1;
     if (h->kind == RSCM_KIND_TWO_LAYER) {
-        rscm::TwoLayerArgs a{};
-        a.n_members = h->N;
-        a.row_stride = h->N;
-        a.n_times = h->T;
-        a.step_begin = step_begin;
-        a.step_end = step_end;
-        a.n_scen = h->n_scen;
-        a.src_off = h->source == RSCM_SRC_UPSTREAM ? 1 : 0;
-        a.lds_forcing = lds_bytes <= (size_t)rscm::kMaxLds - 1024 ? 1 : 0;
-        a.params = h->d_params;
-        a.uniform_rows = h->uniform_rows;
-        a.forcing = h->d_forcing;
+        rscm::TwoLayerArgs a = two_layer_args(h, step_begin, step_end);
         if (linked) {
             a.link = links.row[0];
             a.src_off = links.off[0];
             a.lds_forcing = 0;
             a.n_scen = 1;
+            a.scen = nullptr;
         }
-        a.scen = linked ? nullptr : h->d_scen;
-        a.nsub = h->d_nsub_tl;
-        a.h = h->h_tl;
-        a.h_half = h->h_tl / 2.0;
-        a.h_sixth = h->h_tl / 6.0;
-        a.numerator_guard = t_tl_numerator_guard;
-        a.count_guards = t_tl_count_guards;
-        a.ts = h->series(RSCM_TL_VAR_TS);
-        a.td = h->series(RSCM_TL_VAR_TD);
-        a.status = h->d_status;
         if (op_out) {  // the arguments go into the fused launch's table instead (csrc/group.hip)
             a.lds_forcing = 0;
             op_out->kind = h->kind;
@@ -2203,356 +2213,11 @@ int rscm_ens_status(rscm_ens* h, uint8_t* out)
     GUARD_END
 }
 
-int check_reference(int32_t T, int32_t n_ref, const int32_t* ref_owner, const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end,
-                    const int32_t* ref_stride)
-{
-    if (n_ref < 0 || (n_ref > 0 && (!ref_var || !ref_begin || !ref_end || !ref_stride))) return fail(RSCM_ERR_INVALID, "bad reference-period arrays");
-    for (int32_t e = 0; e < n_ref; ++e) {
-        if (ref_begin[e] < 0 || ref_end[e] > T || ref_begin[e] >= ref_end[e] || ref_stride[e] < 1)
-            return fail(RSCM_ERR_INVALID, "reference period %d: bad time range [%d, %d) stride %d (at least one row)", e, ref_begin[e], ref_end[e],
-                        ref_stride[e]);
-        for (int32_t k = 0; k < e; ++k)
-            if (ref_var[k] == ref_var[e] && (!ref_owner || ref_owner[k] == ref_owner[e])) return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has a period already", e, ref_var[e]);
-    }
-    return RSCM_OK;
-}
-
-int upload_loglik_ref(int32_t n_obs, const double* const* obs_rows, const double* obs_value, const double* obs_sigma, const int32_t* grp,
-                      const int32_t* obs_ref, int32_t n_ref, const int32_t* ref_off, const double* const* ref_rows, int32_t normalize,
-                      int64_t n_members, double* out, void** d_blob, rscm::LoglikRefArgs* args)
-{
-    const size_t n_rows = (size_t)ref_off[n_ref];
-    const size_t sz_ptr = (size_t)n_obs * sizeof(double*), sz_rptr = n_rows * sizeof(double*), sz_d = (size_t)n_obs * sizeof(double),
-                 sz_i = (size_t)n_obs * sizeof(int32_t), sz_off = (size_t)(n_ref + 1) * sizeof(int32_t);
-    const size_t off_rptr = sz_ptr, off_val = off_rptr + sz_rptr, off_sig = off_val + sz_d, off_grp = off_sig + sz_d, off_ref = off_grp + sz_i,
-                 off_off = off_ref + sz_i;
-    std::vector<unsigned char> blob(off_off + sz_off + 8);
-    if (n_obs > 0) {
-        memcpy(blob.data(), obs_rows, sz_ptr);
-        memcpy(blob.data() + off_val, obs_value, sz_d);
-        memcpy(blob.data() + off_sig, obs_sigma, sz_d);
-        memcpy(blob.data() + off_grp, grp, sz_i);
-        memcpy(blob.data() + off_ref, obs_ref, sz_i);
-    }
-    if (n_rows > 0) memcpy(blob.data() + off_rptr, ref_rows, sz_rptr);
-    memcpy(blob.data() + off_off, ref_off, sz_off);
-    *d_blob = nullptr;
-    HIPCHK(rscm::dev_malloc(d_blob, blob.size()));
-    HIPCHK(hipMemcpy(*d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    char* d = (char*)*d_blob;
-    args->lik.n_members = n_members;
-    args->lik.n_obs = n_obs;
-    args->lik.normalize = normalize ? 1 : 0;
-    args->lik.obs_series = (const double* const*)d;
-    args->lik.obs_value = (const double*)(d + off_val);
-    args->lik.obs_sigma = (const double*)(d + off_sig);
-    args->lik.obs_group = (const int32_t*)(d + off_grp);
-    args->lik.out = out;
-    args->obs_ref = (const int32_t*)(d + off_ref);
-    args->ref_off = (const int32_t*)(d + off_off);
-    args->ref_rows = (const double* const*)(d + off_rptr);
-    return RSCM_OK;
-}
-
-// loglik_on_device with reference periods (n_ref > 0)
-static int loglik_ref_on_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value,
-                                const double* obs_sigma, int32_t normalize, int32_t n_ref, const int32_t* ref_var, const int32_t* ref_begin,
-                                const int32_t* ref_end, const int32_t* ref_stride)
-{
-    if (n_obs < 0 || (n_obs > 0 && (!obs_var || !obs_tidx || !obs_value || !obs_sigma)))
-        return fail(RSCM_ERR_INVALID, "bad observation arrays");
-    if (int rc = check_reference(h->T, n_ref, nullptr, ref_var, ref_begin, ref_end, ref_stride)) return rc;
-    bool uncomputed = false;
-    for (int32_t j = 0; j < n_obs; ++j) {
-        if (obs_var[j] < 1 || obs_var[j] >= h->V) return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, obs_var[j]);
-        if (obs_tidx[j] < 0 || obs_tidx[j] >= h->T) return fail(RSCM_ERR_INVALID, "observation %d: time index %d out of range", j, obs_tidx[j]);
-        if (obs_tidx[j] > h->time_index) uncomputed = true;
-        if (j > 0 && obs_var[j] != obs_var[j - 1])
-            for (int32_t k = 0; k < j; ++k)
-                if (obs_var[k] == obs_var[j]) return fail(RSCM_ERR_INVALID, "observations must be grouped by variable");
-    }
-    std::vector<int32_t> obs_ref((size_t)n_obs, -1), ref_off((size_t)n_ref + 1, 0);
-    std::vector<const double*> ref_rows;
-    for (int32_t e = 0; e < n_ref; ++e) {
-        bool observed = false;
-        for (int32_t j = 0; j < n_obs; ++j)
-            if (obs_var[j] == ref_var[e]) {
-                obs_ref[(size_t)j] = e;
-                observed = true;
-            }
-        if (!observed) return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no observation", e, ref_var[e]);
-        for (int32_t t = ref_begin[e]; t < ref_end[e]; t += ref_stride[e])
-            if (t > h->time_index) uncomputed = true;  // a reference row not yet computed: as an observation there
-    }
-    if (int rc = set_device(h)) return rc;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
-    if (uncomputed) {
-        HIPCHK(rscm::launch_fill(h->d_loglik, h->N, -std::numeric_limits<double>::infinity(), h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return RSCM_OK;
-    }
-    std::vector<const double*> ptrs((size_t)n_obs);
-    for (int32_t j = 0; j < n_obs; ++j) {
-        ptrs[(size_t)j] = h->row_ptr(obs_var[j], obs_tidx[j]);
-        if (!ptrs[(size_t)j])
-            return fail(RSCM_ERR_STATE, "observation %d: row %d of variable %d is not resident (NO_SERIES handle, or outside the window and the output stride)",
-                        j, obs_tidx[j], obs_var[j]);
-    }
-    for (int32_t e = 0; e < n_ref; ++e) {
-        for (int32_t t = ref_begin[e]; t < ref_end[e]; t += ref_stride[e]) {
-            const double* p = h->row_ptr(ref_var[e], t);
-            if (!p)
-                return fail(RSCM_ERR_STATE, "reference period %d: row %d of variable %d is not resident (NO_SERIES handle, or outside the window and the output stride)",
-                            e, t, ref_var[e]);
-            ref_rows.push_back(p);
-        }
-        ref_off[(size_t)e + 1] = (int32_t)ref_rows.size();
-    }
-    void* d_blob = nullptr;
-    rscm::LoglikRefArgs a{};
-    int rc = upload_loglik_ref(n_obs, ptrs.data(), obs_value, obs_sigma, obs_var, obs_ref.data(), n_ref, ref_off.data(), ref_rows.data(), normalize,
-                               h->N, h->d_loglik, &d_blob, &a);
-    if (rc == RSCM_OK) {
-        hipError_t e = rscm::launch_loglik_ref(a, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(RSCM_ERR_DEVICE, "loglik: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(d_blob);
-    return rc;
-}
-
-// Gaussian log-likelihood of every member into h->d_loglik (device), synchronised before return.
-static int loglik_on_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                            const double* obs_value, const double* obs_sigma, int32_t normalize)
-{
-    if (n_obs < 0 || (n_obs > 0 && (!obs_var || !obs_tidx || !obs_value || !obs_sigma)))
-        return fail(RSCM_ERR_INVALID, "bad observation arrays");
-    bool uncomputed = false;
-    for (int32_t j = 0; j < n_obs; ++j) {
-        if (obs_var[j] < 1 || obs_var[j] >= h->V) return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, obs_var[j]);
-        if (obs_tidx[j] < 0 || obs_tidx[j] >= h->T) return fail(RSCM_ERR_INVALID, "observation %d: time index %d out of range", j, obs_tidx[j]);
-        if (obs_tidx[j] > h->time_index) uncomputed = true;  // NaN there -> skipped by extract_outputs -> missing time -> Err
-        if (j > 0 && obs_var[j] != obs_var[j - 1])
-            for (int32_t k = 0; k < j; ++k)
-                if (obs_var[k] == obs_var[j])
-                    return fail(RSCM_ERR_INVALID, "observations must be grouped by variable");
-    }
-    if (int rc = set_device(h)) return rc;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
-    if (uncomputed) {
-        HIPCHK(rscm::launch_fill(h->d_loglik, h->N, -std::numeric_limits<double>::infinity(), h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        return RSCM_OK;
-    }
-    std::vector<const double*> ptrs(n_obs);
-    for (int32_t j = 0; j < n_obs; ++j) {
-        ptrs[j] = h->row_ptr(obs_var[j], obs_tidx[j]);
-        if (!ptrs[j])
-            return fail(RSCM_ERR_STATE, "observation %d: row %d of variable %d is not resident (NO_SERIES handle, or outside the window and the output stride)",
-                        j, obs_tidx[j], obs_var[j]);
-    }
-    void* d_blob = nullptr;
-    const size_t sz_ptr = (size_t)n_obs * sizeof(double*), sz_i = (size_t)n_obs * sizeof(int32_t),
-                 sz_d = (size_t)n_obs * sizeof(double);
-    const size_t off_val = sz_ptr, off_sig = off_val + sz_d, off_grp = off_sig + sz_d;
-    std::vector<unsigned char> blob(off_grp + sz_i + 8);
-    if (n_obs > 0) {
-        memcpy(blob.data(), ptrs.data(), sz_ptr);
-        memcpy(blob.data() + off_val, obs_value, sz_d);
-        memcpy(blob.data() + off_sig, obs_sigma, sz_d);
-        memcpy(blob.data() + off_grp, obs_var, sz_i);
-    }
-    HIPCHK(rscm::dev_malloc(&d_blob, blob.size()));
-    hipError_t e = hipMemcpyAsync(d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, h->stream);
-    rscm::LoglikArgs a{};
-    a.n_members = h->N;
-    a.n_obs = n_obs;
-    a.normalize = normalize ? 1 : 0;
-    a.obs_series = (const double* const*)d_blob;
-    a.obs_value = (const double*)((char*)d_blob + off_val);
-    a.obs_sigma = (const double*)((char*)d_blob + off_sig);
-    a.obs_group = (const int32_t*)((char*)d_blob + off_grp);
-    a.out = h->d_loglik;
-    if (e == hipSuccess) e = rscm::launch_loglik(a, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_blob);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "loglik: %s", hipGetErrorString(e));
-    return RSCM_OK;
-}
-
-int rscm_ens_loglik(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                    const double* obs_value, const double* obs_sigma, int32_t normalize, double* out)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
-    if (int rc = loglik_on_device(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize)) return rc;
-    HIPCHK(hipMemcpy(out, h->d_loglik, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
-    return RSCM_OK;
-    GUARD_END
-}
-
-int rscm_ens_loglik_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                           const double* obs_value, const double* obs_sigma, int32_t normalize, void** out_dev)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
-    *out_dev = nullptr;
-    if (int rc = loglik_on_device(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize)) return rc;
-    *out_dev = h->d_loglik;
-    return RSCM_OK;
-    GUARD_END
-}
-
-int rscm_ens_loglik_ref(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value,
-                        const double* obs_sigma, int32_t normalize, int32_t n_ref, const int32_t* ref_var, const int32_t* ref_begin,
-                        const int32_t* ref_end, const int32_t* ref_stride, double* out)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
-    if (n_ref == 0) return rscm_ens_loglik(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, out);
-    if (int rc = loglik_ref_on_device(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, n_ref, ref_var, ref_begin, ref_end, ref_stride))
-        return rc;
-    HIPCHK(hipMemcpy(out, h->d_loglik, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost));
-    return RSCM_OK;
-    GUARD_END
-}
-
-int rscm_ens_loglik_ref_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value,
-                               const double* obs_sigma, int32_t normalize, int32_t n_ref, const int32_t* ref_var, const int32_t* ref_begin,
-                               const int32_t* ref_end, const int32_t* ref_stride, void** out_dev)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
-    if (n_ref == 0) return rscm_ens_loglik_device(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, out_dev);
-    *out_dev = nullptr;
-    if (int rc = loglik_ref_on_device(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, n_ref, ref_var, ref_begin, ref_end, ref_stride))
-        return rc;
-    *out_dev = h->d_loglik;
-    return RSCM_OK;
-    GUARD_END
-}
-
 int rscm_ens_status_devptr(rscm_ens* h, void** out)
 {
     NEED(h);
     if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
     *out = h->d_status;
-    return RSCM_OK;
-}
-
-
-// Validate a set of observations for the fused run+likelihood kernel and keep it on the device
-// (h->d_obs): groups of one variable each, ascending time indices inside a group.
-int prepare_obs(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                const double* obs_value, const double* obs_sigma, int32_t normalize)
-{
-    if (h->kind != RSCM_KIND_TWO_LAYER) return fail(RSCM_ERR_INVALID, "run_loglik supports the two-layer kind");
-    if (h->windowed) return fail(RSCM_ERR_INVALID, "run_loglik writes no series: use a plain or RSCM_FLAG_NO_SERIES handle, not a windowed one");
-    if (n_obs < 0 || (n_obs > 0 && (!obs_var || !obs_tidx || !obs_value || !obs_sigma)))
-        return fail(RSCM_ERR_INVALID, "bad observation arrays");
-    const int32_t first_var = n_obs > 0 ? obs_var[0] : RSCM_TL_VAR_TS;
-    for (int32_t j = 0; j < n_obs; ++j) {
-        if (obs_var[j] != RSCM_TL_VAR_TS && obs_var[j] != RSCM_TL_VAR_TD)
-            return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, obs_var[j]);
-        if (obs_tidx[j] < 0 || obs_tidx[j] >= h->T) return fail(RSCM_ERR_INVALID, "observation %d: time index %d out of range", j, obs_tidx[j]);
-        if (j > 0 && obs_var[j] != obs_var[j - 1] && obs_var[j] == first_var)
-            return fail(RSCM_ERR_INVALID, "observations must be grouped by variable");
-        if (j > 0 && obs_var[j] == obs_var[j - 1] && obs_tidx[j] < obs_tidx[j - 1])
-            return fail(RSCM_ERR_INVALID, "run_loglik needs ascending time indices inside a variable group "
-                                          "(use rscm_ens_run + rscm_ens_loglik for arbitrary order)");
-    }
-    if (int rc = set_device(h)) return rc;
-    // merge the (at most two) groups by time index; ties keep the first group's variable first
-    std::vector<int32_t> order(n_obs);
-    for (int32_t j = 0; j < n_obs; ++j) order[j] = j;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return obs_tidx[x] < obs_tidx[y]; });
-    const size_t sz_i = (size_t)n_obs * sizeof(int32_t), sz_d = (size_t)n_obs * sizeof(double);
-    std::vector<unsigned char> blob(2 * sz_d + 2 * sz_i + 16);
-    double* bv = (double*)blob.data();
-    double* bs = bv + n_obs;
-    int32_t* bt = (int32_t*)(bs + n_obs);
-    int32_t* bd = bt + n_obs;
-    for (int32_t k = 0; k < n_obs; ++k) {
-        const int32_t j = order[k];
-        bv[k] = obs_value[j];
-        bs[k] = obs_sigma[j];
-        bt[k] = obs_tidx[j];
-        bd[k] = obs_var[j] == RSCM_TL_VAR_TD ? 1 : 0;
-    }
-    HIPCHK(hipStreamSynchronize(h->stream));  // a launch may still be reading the previous plan
-    if (blob.size() > h->obs_capacity) {
-        HIPCHK(hipFree(h->d_obs));
-        h->d_obs = nullptr;
-        h->obs_capacity = 0;
-        HIPCHK(rscm::dev_malloc(&h->d_obs, blob.size()));
-        h->obs_capacity = blob.size();
-    }
-    HIPCHK(hipMemcpy(h->d_obs, blob.data(), blob.size(), hipMemcpyHostToDevice));
-    h->obs_merged_tidx.assign(bt, bt + n_obs);
-    h->obs_merged_deep.assign(bd, bd + n_obs);
-    h->ref_active = false;
-    h->ref_last_row = 0;
-    h->obs_n = n_obs;
-    h->obs_last_tidx = 0;
-    for (int32_t j = 0; j < n_obs; ++j) h->obs_last_tidx = std::max(h->obs_last_tidx, obs_tidx[j]);
-    h->obs_normalize = normalize ? 1 : 0;
-    h->obs_first_is_deep = first_var == RSCM_TL_VAR_TD ? 1 : 0;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
-    return RSCM_OK;
-}
-
-int prepare_ref(rscm_ens* h, int32_t n_ref, const int32_t* ref_var, const int32_t* ref_begin, const int32_t* ref_end, const int32_t* ref_stride)
-{
-    h->ref_active = false;
-    h->ref_last_row = 0;
-    if (int rc = check_reference(h->T, n_ref, nullptr, ref_var, ref_begin, ref_end, ref_stride)) return rc;
-    if (n_ref == 0) return RSCM_OK;
-    rscm::TwoLayerRefArgs r{};
-    for (int32_t e = 0; e < n_ref; ++e) {
-        if (ref_var[e] != RSCM_TL_VAR_TS && ref_var[e] != RSCM_TL_VAR_TD)
-            return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no stored series", e, ref_var[e]);
-        const int32_t v = ref_var[e] == RSCM_TL_VAR_TD ? 1 : 0;
-        if (std::find(h->obs_merged_deep.begin(), h->obs_merged_deep.end(), v) == h->obs_merged_deep.end())
-            return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no observation", e, ref_var[e]);
-        r.on[v] = 1;
-        r.begin[v] = ref_begin[e];
-        r.stride[v] = ref_stride[e];
-        r.count[v] = (ref_end[e] - ref_begin[e] + ref_stride[e] - 1) / ref_stride[e];
-        r.last[v] = ref_begin[e] + (r.count[v] - 1) * ref_stride[e];
-        h->ref_last_row = std::max(h->ref_last_row, r.last[v]);
-    }
-    // an observation of a variable with a period, at a row up to the period's last, waits in the scratch for its variable's b
-    std::vector<int32_t> slot((size_t)h->obs_n, -1);
-    int32_t n_defer = 0;
-    for (int32_t k = 0; k < h->obs_n; ++k) {
-        const int32_t v = h->obs_merged_deep[(size_t)k];
-        if (r.on[v] && h->obs_merged_tidx[(size_t)k] <= r.last[v]) slot[(size_t)k] = n_defer++;
-    }
-    if (int rc = set_device(h)) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));  // a launch may still be using the previous layout
-    if (slot.size() > h->ref_slot_capacity) {
-        HIPCHK(hipFree(h->d_ref_slot));
-        h->d_ref_slot = nullptr;
-        h->ref_slot_capacity = 0;
-        HIPCHK(rscm::dev_malloc(&h->d_ref_slot, slot.size() * sizeof(int32_t)));
-        h->ref_slot_capacity = slot.size();
-    }
-    HIPCHK(hipMemcpy(h->d_ref_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((size_t)n_defer > h->defer_capacity) {
-        HIPCHK(hipFree(h->d_defer));
-        h->d_defer = nullptr;
-        h->defer_capacity = 0;
-        HIPCHK(rscm::dev_malloc(&h->d_defer, (size_t)n_defer * (size_t)h->N * sizeof(double)));
-        h->defer_capacity = (size_t)n_defer;
-    }
-    r.obs_slot = h->d_ref_slot;
-    r.defer = h->d_defer;
-    h->ref = r;
-    h->ref_active = true;
     return RSCM_OK;
 }
 
@@ -2568,121 +2233,6 @@ int check_loglik_ready(rscm_ens* h)
             return fail(RSCM_ERR_STATE, "state variable %d has no initial value (MissingInitialValue)", v);
     if (int rc = set_device(h)) return rc;
     return refresh_schedule(h);
-}
-
-// Asynchronous fused run+likelihood launch with the prepared observations; fills h->d_loglik.
-hipError_t launch_loglik(rscm_ens* h)
-{
-    // Steps after the last observed index cannot change ln L (GaussianLikelihood reads the model at the
-    // observation times only, likelihood.rs:206-226): a caller that uses nothing but ln L -- the device
-    // sampler -- lets the launch end there (1850-2020 observations on a 1750-2500 axis: 270 of 750 steps).
-    // With reference periods (prepare_ref) "observed" includes the reference rows.
-    const int32_t last_read = h->ref_active ? std::max(h->obs_last_tidx, h->ref_last_row) : h->obs_last_tidx;
-    const int32_t len = h->loglik_stop_at_last_obs ? std::max(1, std::min(h->T - 1, last_read)) : h->T - 1;
-    const size_t lds_bytes = (size_t)h->n_scen * (size_t)len * sizeof(double);
-    rscm::TwoLayerArgs a{};
-    a.n_members = h->N;
-    a.row_stride = h->N;
-    a.n_times = h->T;
-    a.step_begin = 0;
-    a.step_end = len;
-    a.n_scen = h->n_scen;
-    a.src_off = h->source == RSCM_SRC_UPSTREAM ? 1 : 0;
-    a.lds_forcing = lds_bytes <= (size_t)rscm::kMaxLds - 1024 ? 1 : 0;
-    a.params = h->d_params;
-        a.uniform_rows = h->uniform_rows;
-    a.forcing = h->d_forcing;
-    a.scen = h->d_scen;
-    a.nsub = h->d_nsub_tl;
-    a.h = h->h_tl;
-    a.h_half = h->h_tl / 2.0;
-    a.h_sixth = h->h_tl / 6.0;
-    a.numerator_guard = t_tl_numerator_guard;
-    a.count_guards = t_tl_count_guards;
-    a.ts = h->series(RSCM_TL_VAR_TS);
-    a.td = h->series(RSCM_TL_VAR_TD);
-    a.status = h->d_status;
-    a.n_obs = h->obs_n;
-    a.normalize = h->obs_normalize;
-    a.first_is_deep = h->obs_first_is_deep;
-    a.obs_value = (const double*)h->d_obs;
-    a.obs_sigma = a.obs_value + h->obs_n;
-    a.obs_tidx = (const int32_t*)(a.obs_sigma + h->obs_n);
-    a.obs_is_deep = a.obs_tidx + h->obs_n;
-    a.loglik = h->d_loglik;
-    if (h->ref_active) return rscm::launch_two_layer_loglik_ref(a, h->ref, h->mode, h->stream);
-    return rscm::launch_two_layer_loglik(a, h->mode, h->stream);
-}
-
-
-static int run_loglik_impl(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                           const double* obs_value, const double* obs_sigma, int32_t normalize, double* out_host, int32_t n_ref = 0,
-                           const int32_t* ref_var = nullptr, const int32_t* ref_begin = nullptr, const int32_t* ref_end = nullptr,
-                           const int32_t* ref_stride = nullptr)
-{
-    if (int rc = prepare_obs(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize)) return rc;
-    if (n_ref != 0)
-        if (int rc = prepare_ref(h, n_ref, ref_var, ref_begin, ref_end, ref_stride)) return rc;
-    if (int rc = check_loglik_ready(h)) return rc;
-    hipError_t e = hipEventRecord(h->ev0, h->stream);
-    if (e == hipSuccess) e = launch_loglik(h);
-    if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-    if (e == hipSuccess && out_host)
-        e = hipMemcpyAsync(out_host, h->d_loglik, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "run_loglik: %s", hipGetErrorString(e));
-    h->timed = true;
-    return RSCM_OK;
-}
-
-int rscm_ens_run_loglik(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                        const double* obs_value, const double* obs_sigma, int32_t normalize, double* out)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
-    return run_loglik_impl(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, out);
-    GUARD_END
-}
-
-int rscm_ens_run_loglik_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx,
-                               const double* obs_value, const double* obs_sigma, int32_t normalize, void** out_dev)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
-    *out_dev = nullptr;
-    if (int rc = run_loglik_impl(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, nullptr)) return rc;
-    *out_dev = h->d_loglik;
-    return RSCM_OK;
-    GUARD_END
-}
-
-int rscm_ens_run_loglik_ref(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value,
-                            const double* obs_sigma, int32_t normalize, int32_t n_ref, const int32_t* ref_var, const int32_t* ref_begin,
-                            const int32_t* ref_end, const int32_t* ref_stride, double* out)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
-    return run_loglik_impl(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, out, n_ref, ref_var, ref_begin, ref_end, ref_stride);
-    GUARD_END
-}
-
-int rscm_ens_run_loglik_ref_device(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value,
-                                   const double* obs_sigma, int32_t normalize, int32_t n_ref, const int32_t* ref_var,
-                                   const int32_t* ref_begin, const int32_t* ref_end, const int32_t* ref_stride, void** out_dev)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
-    *out_dev = nullptr;
-    if (int rc = run_loglik_impl(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize, nullptr, n_ref, ref_var, ref_begin, ref_end,
-                                 ref_stride))
-        return rc;
-    *out_dev = h->d_loglik;
-    return RSCM_OK;
-    GUARD_END
 }
 
 int rscm_gpu_copy_to_device(int32_t device_id, void* device_ptr, const void* host, int64_t n_bytes)

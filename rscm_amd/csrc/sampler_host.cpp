@@ -38,16 +38,12 @@ struct rscm_sampler {
     // fused: the two-layer run+likelihood kernel scores a half; otherwise the half is run through
     // rscm_ens_run_async (any kind, stored series) and scored by the likelihood kernel
     bool fused = true;
-    void* d_sobs = nullptr;          // stored path: observation rows, values, sigmas, groups
+    void* d_sobs = nullptr;          // stored path: the tables lik points into (upload_loglik)
     rscm::LoglikArgs lik{};
     // the observations as given at creation (rscm_sampler_set_reference lays the stored path's tables out again)
     std::vector<int32_t> obs_owner, obs_var, obs_tidx;
     std::vector<double> obs_value, obs_sigma;
     int32_t normalize = 0;
-    bool use_ref = false;            // stored path: score with loglik_ref_kernel and lik_ref
-    void* d_sref = nullptr;
-    rscm::LoglikRefArgs lik_ref{};
-    int32_t obs_last_step = 0;       // graph evaluator: the last observed index
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // graph evaluator (rscm_sampler_create_graph): every half-step rewinds these handles, runs them in lock-step up
     // to the last observed index and scores the stored series; ev is the first of them
@@ -56,6 +52,11 @@ struct rscm_sampler {
     bool graph_clear = false;                  // NaN the stored rows before every run (graphs in which a consumer runs ahead of its producer)
     int32_t graph_last_step = 0;
     double** d_param_ptr = nullptr;            // [D] device addresses of the sampled rows
+    ObsList observations() const
+    {
+        return {(int32_t)obs_var.size(), graph.empty() ? nullptr : obs_owner.data(), obs_var.data(), obs_tidx.data(), obs_value.data(),
+                obs_sigma.data(), normalize};
+    }
 };
 
 namespace {
@@ -113,7 +114,7 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         HIPCHK(rscm::launch_sampler_propose(a, s->ev->stream));
         if (s->graph_last_step > 0)
             if (int rc = rscm_ens_run_lockstep(s->graph.data(), (int32_t)s->graph.size(), 0, s->graph_last_step)) return rc;
-        HIPCHK(s->use_ref ? rscm::launch_loglik_ref(s->lik_ref, s->ev->stream) : rscm::launch_loglik(s->lik, s->ev->stream));
+        HIPCHK(rscm::launch_loglik(s->lik, s->ev->stream));
         HIPCHK(rscm::launch_sampler_accept(a, s->ev->stream));
         if (s->sharded) {
             rscm::SamplerArgs p = a;
@@ -131,7 +132,7 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         s->ev->time_index = 0;  // every evaluation is a fresh Model::run of the half
         if (int rc = rscm_ens_run_async(s->ev, 0, s->ev->T - 1)) return rc;
         s->ev->time_index = 0;
-        HIPCHK(s->use_ref ? rscm::launch_loglik_ref(s->lik_ref, s->ev->stream) : rscm::launch_loglik(s->lik, s->ev->stream));
+        HIPCHK(rscm::launch_loglik(s->lik, s->ev->stream));
     }
     HIPCHK(rscm::launch_sampler_accept(a, s->ev->stream));
     if (s->sharded) {  // this rank's block of the updated half, ready for the all-gather
@@ -139,6 +140,105 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         p.exchange = s->d_send;
         HIPCHK(rscm::launch_sampler_pack(p, s->ev->stream));
     }
+    return RSCM_OK;
+}
+
+// what both creators ask of the walkers, the ranks and the stretch scale
+int check_walkers(int32_t n_walkers, int32_t rank, int32_t n_ranks, double stretch_a)
+{
+    if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(RSCM_ERR_INVALID, "bad rank %d of %d", rank, n_ranks);
+    if (n_walkers < 2) return fail(RSCM_ERR_INVALID, "Must have at least 2 walkers");          // ensemble.rs:120-127
+    if (n_walkers % 2) return fail(RSCM_ERR_INVALID, "Number of walkers must be even");
+    if ((n_walkers / 2) % n_ranks)
+        return fail(RSCM_ERR_INVALID, "half the walkers (%d) must split evenly over %d ranks", n_walkers / 2, n_ranks);
+    if (!(stretch_a > 1.0)) return fail(RSCM_ERR_INVALID, "Stretch move scale parameter must be > 1.0, got %g", stretch_a);  // moves.rs:40-48
+    return RSCM_OK;
+}
+
+// ... and of the prior of dimension d
+int check_prior(int32_t d, const int32_t* prior_kind, const double* prior_a, const double* prior_b, const double* prior_low, const double* prior_high)
+{
+    if (prior_kind[d] < 0 || prior_kind[d] > 2) return fail(RSCM_ERR_INVALID, "dimension %d: unknown prior kind %d", d, prior_kind[d]);
+    if (prior_kind[d] == 0 && !(prior_b[d] > prior_a[d])) return fail(RSCM_ERR_INVALID, "dimension %d: Uniform needs high > low", d);
+    if (prior_kind[d] != 0 && !(prior_b[d] > 0.0)) return fail(RSCM_ERR_INVALID, "dimension %d: the scale parameter must be > 0", d);
+    if ((prior_low && prior_high) && !(prior_low[d] < prior_high[d])) return fail(RSCM_ERR_INVALID, "dimension %d: Bound needs low < high", d);
+    return RSCM_OK;
+}
+
+// What both creators set, allocate and upload: the walkers' state, the priors, the exchange buffers, counters and events; the
+// observations are kept for rscm_sampler_set_reference.  On failure the caller destroys s.
+int sampler_init(rscm_sampler* s, rscm_ens* ev, int32_t n_walkers, int32_t n_dims, const int32_t* prior_kind, const double* prior_a,
+                 const double* prior_b, const double* prior_low, const double* prior_high, const ObsList& o, double stretch_a, uint64_t seed,
+                 int32_t rank, int32_t n_ranks)
+{
+    s->ev = ev;
+    s->W = n_walkers;
+    s->D = n_dims;
+    s->rank = rank;
+    s->n_ranks = n_ranks;
+    s->sharded = n_ranks > 1;
+    s->n_local = (int32_t)ev->N;
+    s->stretch_a = stretch_a;
+    s->seed = seed;
+    if (o.n > 0) {
+        if (o.owner) s->obs_owner.assign(o.owner, o.owner + o.n);
+        s->obs_var.assign(o.var, o.var + o.n);
+        s->obs_tidx.assign(o.tidx, o.tidx + o.n);
+        s->obs_value.assign(o.value, o.value + o.n);
+        s->obs_sigma.assign(o.sigma, o.sigma + o.n);
+    }
+    s->normalize = o.normalize ? 1 : 0;
+    const size_t W = (size_t)n_walkers, H = (size_t)ev->N, D = (size_t)n_dims;  // H: this rank's block of a half
+    HIPCHK(rscm::dev_malloc(&s->d_kind, D * sizeof(int32_t)));
+    HIPCHK(rscm::dev_malloc(&s->d_pa, D * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_pb, D * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_plo, D * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_phi, D * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_pos, D * W * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_logp, W * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_prop, D * H * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_z, H * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_lp, H * sizeof(double)));
+    HIPCHK(rscm::dev_malloc(&s->d_send, (D + 1) * H * sizeof(double)));   // 2 x (D + 1) x H doubles: also for one rank (the exchange of
+    HIPCHK(rscm::dev_malloc(&s->d_recv, (size_t)n_ranks * (D + 1) * H * sizeof(double)));   // a one-rank group is a copy)
+    HIPCHK(rscm::dev_malloc(&s->d_nacc, W * sizeof(int64_t)));
+    HIPCHK(rscm::dev_malloc(&s->d_nprop, W * sizeof(int64_t)));
+    HIPCHK(hipMemcpy(s->d_kind, prior_kind, D * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->d_pa, prior_a, D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->d_pb, prior_b, D * sizeof(double), hipMemcpyHostToDevice));
+    std::vector<double> lo(D, -std::numeric_limits<double>::infinity()), hi(D, std::numeric_limits<double>::infinity());
+    if (prior_low && prior_high)
+        for (size_t d = 0; d < D; ++d) { lo[d] = prior_low[d]; hi[d] = prior_high[d]; }
+    HIPCHK(hipMemcpy(s->d_plo, lo.data(), D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->d_phi, hi.data(), D * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(s->d_nacc, 0, W * sizeof(int64_t)));
+    HIPCHK(hipMemset(s->d_nprop, 0, W * sizeof(int64_t)));
+    HIPCHK(hipEventCreate(&s->ev0));
+    HIPCHK(hipEventCreate(&s->ev1));
+    return RSCM_OK;
+}
+
+// Puts the stored path's table for these resolved rows (of the observations kept in s) in place of the one s holds; the graph steps to
+// the last row the likelihood reads.  On failure s keeps its table.
+int sampler_install_table(rscm_sampler* s, LoglikRows& rows)
+{
+    rscm_ens* h = s->ev;
+    if (int rc = set_device(h)) return rc;
+    void* d_new = nullptr;
+    rscm::LoglikArgs a{};
+    int rc = upload_loglik(rows, s->observations(), h->N, h->d_loglik, h->stream, &d_new, &a);
+    if (rc == RSCM_OK) {  // the copy is in, and no launch reads the previous table any more
+        const hipError_t e = hipStreamSynchronize(h->stream);
+        if (e != hipSuccess) rc = fail(RSCM_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
+    }
+    if (rc != RSCM_OK) {
+        (void)hipFree(d_new);
+        return rc;
+    }
+    (void)hipFree(s->d_sobs);
+    s->d_sobs = d_new;
+    s->lik = a;
+    s->graph_last_step = rows.last_row;
     return RSCM_OK;
 }
 
@@ -168,16 +268,11 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
     *out = nullptr;
     rscm_ens* h = evaluator;
     NEED(h);
-    if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(RSCM_ERR_INVALID, "bad rank %d of %d", rank, n_ranks);
     if (h->windowed) return fail(RSCM_ERR_INVALID, "the sampler's evaluator must not be a windowed ensemble");
-    if (n_walkers < 2) return fail(RSCM_ERR_INVALID, "Must have at least 2 walkers");          // ensemble.rs:120-127
-    if (n_walkers % 2) return fail(RSCM_ERR_INVALID, "Number of walkers must be even");
-    if ((n_walkers / 2) % n_ranks)
-        return fail(RSCM_ERR_INVALID, "half the walkers (%d) must split evenly over %d ranks", n_walkers / 2, n_ranks);
+    if (int rc = check_walkers(n_walkers, rank, n_ranks, stretch_a)) return rc;
     if (h->N != n_walkers / 2 / n_ranks)
         return fail(RSCM_ERR_INVALID, "the evaluating ensemble must have n_walkers / 2 / n_ranks = %d members, it has %lld",
                     n_walkers / 2 / n_ranks, (long long)h->N);
-    if (!(stretch_a > 1.0)) return fail(RSCM_ERR_INVALID, "Stretch move scale parameter must be > 1.0, got %g", stretch_a);  // moves.rs:40-48
     if (n_dims < 1 || n_dims > h->P || !param_rows || !base_params || !prior_kind || !prior_a || !prior_b)
         return fail(RSCM_ERR_INVALID, "bad parameter description");
     for (int32_t d = 0; d < n_dims; ++d) {
@@ -187,10 +282,7 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
                         "parameters are set -- and cannot be sampled on the device", d, param_rows[d], name);
         for (int32_t e2 = 0; e2 < d; ++e2)
             if (param_rows[e2] == param_rows[d]) return fail(RSCM_ERR_INVALID, "parameter row %d sampled twice", param_rows[d]);
-        if (prior_kind[d] < 0 || prior_kind[d] > 2) return fail(RSCM_ERR_INVALID, "dimension %d: unknown prior kind %d", d, prior_kind[d]);
-        if (prior_kind[d] == 0 && !(prior_b[d] > prior_a[d])) return fail(RSCM_ERR_INVALID, "dimension %d: Uniform needs high > low", d);
-        if (prior_kind[d] != 0 && !(prior_b[d] > 0.0)) return fail(RSCM_ERR_INVALID, "dimension %d: the scale parameter must be > 0", d);
-        if ((prior_low && prior_high) && !(prior_low[d] < prior_high[d])) return fail(RSCM_ERR_INVALID, "dimension %d: Bound needs low < high", d);
+        if (int rc = check_prior(d, prior_kind, prior_a, prior_b, prior_low, prior_high)) return rc;
     }
     // the fused kernel takes two-layer observations with ascending time indices inside a group
     bool fused = h->kind == RSCM_KIND_TWO_LAYER;
@@ -198,6 +290,8 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
         if (!obs_var || !obs_tidx) return fail(RSCM_ERR_INVALID, "bad observation arrays");
         if (j > 0 && obs_var[j] == obs_var[j - 1] && obs_tidx[j] < obs_tidx[j - 1]) fused = false;
     }
+    const ObsList o = {n_obs, nullptr, obs_var, obs_tidx, obs_value, obs_sigma, normalize};
+    LoglikRows rows;   // stored path: resolved before anything is allocated, uploaded once the sampler exists
     if (fused) {
         if (int rc = prepare_obs(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize)) return rc;
         h->loglik_stop_at_last_obs = true;   // cleared again by rscm_sampler_destroy
@@ -205,105 +299,25 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
         if (h->rows != h->T)
             return fail(RSCM_ERR_INVALID, "this evaluator stores no series: only the fused two-layer likelihood "
                                           "(ascending observation times) is available for it");
-        if (n_obs < 0 || (n_obs > 0 && (!obs_var || !obs_tidx || !obs_value || !obs_sigma)))
-            return fail(RSCM_ERR_INVALID, "bad observation arrays");
-        for (int32_t j = 0; j < n_obs; ++j) {
-            if (obs_var[j] < 1 || obs_var[j] >= h->V) return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, obs_var[j]);
-            if (obs_tidx[j] < 0 || obs_tidx[j] >= h->T) return fail(RSCM_ERR_INVALID, "observation %d: time index %d out of range", j, obs_tidx[j]);
-            if (j > 0 && obs_var[j] != obs_var[j - 1])
-                for (int32_t k = 0; k < j; ++k)
-                    if (obs_var[k] == obs_var[j]) return fail(RSCM_ERR_INVALID, "observations must be grouped by variable");
-        }
+        if (int rc = resolve_loglik_rows(&h, 1, true, o, {}, &rows)) return rc;
         if (int rc = set_device(h)) return rc;
         if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
     }
     rscm_sampler* s = new rscm_sampler();
-    s->ev = h;
     s->fused = fused;
-    s->W = n_walkers;
-    s->D = n_dims;
-    s->rank = rank;
-    s->n_ranks = n_ranks;
-    s->sharded = n_ranks > 1;
-    s->n_local = (int32_t)h->N;
-    s->stretch_a = stretch_a;
-    s->seed = seed;
-    if (n_obs > 0) {
-        s->obs_var.assign(obs_var, obs_var + n_obs);
-        s->obs_tidx.assign(obs_tidx, obs_tidx + n_obs);
-        s->obs_value.assign(obs_value, obs_value + n_obs);
-        s->obs_sigma.assign(obs_sigma, obs_sigma + n_obs);
-    }
-    s->normalize = normalize ? 1 : 0;
-    auto cleanup = [&](int rc) {
+    auto fill = [&]() -> int {
+        if (int rc = sampler_init(s, h, n_walkers, n_dims, prior_kind, prior_a, prior_b, prior_low, prior_high, o, stretch_a, seed, rank, n_ranks))
+            return rc;
+        HIPCHK(rscm::dev_malloc(&s->d_rows, (size_t)n_dims * sizeof(int32_t)));
+        HIPCHK(rscm::dev_malloc(&s->d_base, (size_t)h->P * sizeof(double)));
+        HIPCHK(hipMemcpy(s->d_rows, param_rows, (size_t)n_dims * sizeof(int32_t), hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(s->d_base, base_params, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
+        return fused ? RSCM_OK : sampler_install_table(s, rows);   // the observation rows of the stored series, once
+    };
+    if (int rc = fill()) {
         rscm_sampler_destroy(s);
         return rc;
-    };
-    const size_t W = (size_t)n_walkers, H = (size_t)h->N, D = (size_t)n_dims;  // H: this rank's block of a half
-#define CK(expr)                                                                               \
-    do {                                                                                       \
-        hipError_t e2_ = (expr);                                                               \
-        if (e2_ != hipSuccess)                                                                 \
-            return cleanup(fail(e2_ == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, \
-                                "%s failed: %s", #expr, hipGetErrorString(e2_)));              \
-    } while (0)
-    CK(rscm::dev_malloc(&s->d_rows, D * sizeof(int32_t)));
-    CK(rscm::dev_malloc(&s->d_kind, D * sizeof(int32_t)));
-    CK(rscm::dev_malloc(&s->d_base, (size_t)h->P * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_pa, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_pb, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_plo, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_phi, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_pos, D * W * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_logp, W * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_prop, D * H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_z, H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_lp, H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_send, (D + 1) * H * sizeof(double)));   // 2 x (D + 1) x H doubles: also for one rank (the exchange of
-    CK(rscm::dev_malloc(&s->d_recv, (size_t)n_ranks * (D + 1) * H * sizeof(double)));   // a one-rank group is a copy)
-    CK(rscm::dev_malloc(&s->d_nacc, W * sizeof(int64_t)));
-    CK(rscm::dev_malloc(&s->d_nprop, W * sizeof(int64_t)));
-    CK(hipMemcpy(s->d_rows, param_rows, D * sizeof(int32_t), hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->d_kind, prior_kind, D * sizeof(int32_t), hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->d_base, base_params, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->d_pa, prior_a, D * sizeof(double), hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->d_pb, prior_b, D * sizeof(double), hipMemcpyHostToDevice));
-    {
-        std::vector<double> lo(D, -std::numeric_limits<double>::infinity()), hi(D, std::numeric_limits<double>::infinity());
-        if (prior_low && prior_high)
-            for (size_t d = 0; d < D; ++d) { lo[d] = prior_low[d]; hi[d] = prior_high[d]; }
-        CK(hipMemcpy(s->d_plo, lo.data(), D * sizeof(double), hipMemcpyHostToDevice));
-        CK(hipMemcpy(s->d_phi, hi.data(), D * sizeof(double), hipMemcpyHostToDevice));
     }
-    CK(hipMemset(s->d_nacc, 0, W * sizeof(int64_t)));
-    CK(hipMemset(s->d_nprop, 0, W * sizeof(int64_t)));
-    CK(hipEventCreate(&s->ev0));
-    CK(hipEventCreate(&s->ev1));
-    if (!fused) {  // the observation rows of the stored series, once
-        const size_t sz_ptr = (size_t)n_obs * sizeof(double*), sz_i = (size_t)n_obs * sizeof(int32_t),
-                     sz_d = (size_t)n_obs * sizeof(double);
-        const size_t off_val = sz_ptr, off_sig = off_val + sz_d, off_grp = off_sig + sz_d;
-        std::vector<unsigned char> blob(off_grp + sz_i + 8);
-        std::vector<const double*> ptrs(n_obs);
-        for (int32_t j = 0; j < n_obs; ++j) ptrs[j] = h->series(obs_var[j]) + (size_t)obs_tidx[j] * h->N;
-        if (n_obs > 0) {
-            memcpy(blob.data(), ptrs.data(), sz_ptr);
-            memcpy(blob.data() + off_val, obs_value, sz_d);
-            memcpy(blob.data() + off_sig, obs_sigma, sz_d);
-            memcpy(blob.data() + off_grp, obs_var, sz_i);
-        }
-        CK(rscm::dev_malloc(&s->d_sobs, blob.size()));
-        CK(hipMemcpy(s->d_sobs, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        s->lik.n_members = h->N;
-        s->lik.n_obs = n_obs;
-        s->lik.normalize = normalize ? 1 : 0;
-        s->lik.obs_series = (const double* const*)s->d_sobs;
-        s->lik.obs_value = (const double*)((char*)s->d_sobs + off_val);
-        s->lik.obs_sigma = (const double*)((char*)s->d_sobs + off_sig);
-        s->lik.obs_group = (const int32_t*)((char*)s->d_sobs + off_grp);
-        s->lik.out = h->d_loglik;
-    }
-#undef CK
     *out = s;
     return RSCM_OK;
     GUARD_END
@@ -320,12 +334,7 @@ int rscm_sampler_create_graph(rscm_ens* const* handles, int32_t n_handles, int32
     if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
     *out = nullptr;
     if (!handles || n_handles < 1) return fail(RSCM_ERR_INVALID, "need at least one handle");
-    if (n_ranks < 1 || rank < 0 || rank >= n_ranks) return fail(RSCM_ERR_INVALID, "bad rank %d of %d", rank, n_ranks);
-    if (n_walkers < 2) return fail(RSCM_ERR_INVALID, "Must have at least 2 walkers");          // ensemble.rs:120-127
-    if (n_walkers % 2) return fail(RSCM_ERR_INVALID, "Number of walkers must be even");
-    if ((n_walkers / 2) % n_ranks)
-        return fail(RSCM_ERR_INVALID, "half the walkers (%d) must split evenly over %d ranks", n_walkers / 2, n_ranks);
-    if (!(stretch_a > 1.0)) return fail(RSCM_ERR_INVALID, "Stretch move scale parameter must be > 1.0, got %g", stretch_a);  // moves.rs:40-48
+    if (int rc = check_walkers(n_walkers, rank, n_ranks, stretch_a)) return rc;
     if (n_dims < 1 || !param_owner || !param_rows || !prior_kind || !prior_a || !prior_b) return fail(RSCM_ERR_INVALID, "bad parameter description");
     rscm_ens* lead = handles[0];
     for (int32_t k = 0; k < n_handles; ++k) {
@@ -349,129 +358,34 @@ int rscm_sampler_create_graph(rscm_ens* const* handles, int32_t n_handles, int32
         for (int32_t e2 = 0; e2 < d; ++e2)
             if (param_owner[e2] == param_owner[d] && param_rows[e2] == param_rows[d])
                 return fail(RSCM_ERR_INVALID, "parameter row %d of handle %d sampled twice", param_rows[d], param_owner[d]);
-        if (prior_kind[d] < 0 || prior_kind[d] > 2) return fail(RSCM_ERR_INVALID, "dimension %d: unknown prior kind %d", d, prior_kind[d]);
-        if (prior_kind[d] == 0 && !(prior_b[d] > prior_a[d])) return fail(RSCM_ERR_INVALID, "dimension %d: Uniform needs high > low", d);
-        if (prior_kind[d] != 0 && !(prior_b[d] > 0.0)) return fail(RSCM_ERR_INVALID, "dimension %d: the scale parameter must be > 0", d);
-        if ((prior_low && prior_high) && !(prior_low[d] < prior_high[d])) return fail(RSCM_ERR_INVALID, "dimension %d: Bound needs low < high", d);
+        if (int rc = check_prior(d, prior_kind, prior_a, prior_b, prior_low, prior_high)) return rc;
         if (param_rows[d] < 64) sampled[(size_t)param_owner[d]] |= 1ull << param_rows[d];
     }
-    if (n_obs < 0 || (n_obs > 0 && (!obs_owner || !obs_var || !obs_tidx || !obs_value || !obs_sigma))) return fail(RSCM_ERR_INVALID, "bad observation arrays");
-    int32_t last_step = 0;
-    for (int32_t j = 0; j < n_obs; ++j) {
-        if (obs_owner[j] < 0 || obs_owner[j] >= n_handles) return fail(RSCM_ERR_INVALID, "observation %d: owner %d out of range", j, obs_owner[j]);
-        const rscm_ens* h = handles[obs_owner[j]];
-        if (obs_var[j] < 1 || obs_var[j] >= h->V) return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, obs_var[j]);
-        if (obs_tidx[j] < 0 || obs_tidx[j] >= h->T) return fail(RSCM_ERR_INVALID, "observation %d: time index %d out of range", j, obs_tidx[j]);
-        last_step = std::max(last_step, obs_tidx[j]);
-        // one contiguous run per (owner, variable), as rscm_sampler_create_sharded and the host likelihood require: the kernel closes a
-        // partial sum at every change of group, so an interleaved order would change the association of the sum (likelihood.rs:206-248)
-        if (j > 0 && (obs_owner[j] != obs_owner[j - 1] || obs_var[j] != obs_var[j - 1]))
-            for (int32_t e2 = 0; e2 < j - 1; ++e2)
-                if (obs_owner[e2] == obs_owner[j] && obs_var[e2] == obs_var[j])
-                    return fail(RSCM_ERR_INVALID, "observation %d: the observations of (handle %d, variable %d) must be contiguous", j, obs_owner[j], obs_var[j]);
-    }
+    if (n_obs > 0 && !obs_owner) return fail(RSCM_ERR_INVALID, "bad observation arrays");
+    const ObsList o = {n_obs, obs_owner, obs_var, obs_tidx, obs_value, obs_sigma, normalize};
+    LoglikRows rows;
+    if (int rc = resolve_loglik_rows(handles, n_handles, true, o, {}, &rows)) return rc;
     if (int rc = set_device(lead)) return rc;
     if (!lead->d_loglik) HIPCHK(rscm::dev_malloc(&lead->d_loglik, (size_t)lead->N * sizeof(double)));
     rscm_sampler* s = new rscm_sampler();
-    s->ev = lead;
     s->fused = false;
     s->graph.assign(handles, handles + n_handles);
     s->graph_sampled_rows = sampled;
     s->graph_clear = clear_between_runs != 0;
-    s->graph_last_step = last_step;
-    s->obs_last_step = last_step;
-    if (n_obs > 0) {
-        s->obs_owner.assign(obs_owner, obs_owner + n_obs);
-        s->obs_var.assign(obs_var, obs_var + n_obs);
-        s->obs_tidx.assign(obs_tidx, obs_tidx + n_obs);
-        s->obs_value.assign(obs_value, obs_value + n_obs);
-        s->obs_sigma.assign(obs_sigma, obs_sigma + n_obs);
-    }
-    s->normalize = normalize ? 1 : 0;
-    s->W = n_walkers;
-    s->D = n_dims;
-    s->rank = rank;
-    s->n_ranks = n_ranks;
-    s->sharded = n_ranks > 1;
-    s->n_local = (int32_t)lead->N;
-    s->stretch_a = stretch_a;
-    s->seed = seed;
-    auto cleanup = [&](int rc) {
+    auto fill = [&]() -> int {
+        if (int rc = sampler_init(s, lead, n_walkers, n_dims, prior_kind, prior_a, prior_b, prior_low, prior_high, o, stretch_a, seed, rank, n_ranks))
+            return rc;
+        std::vector<double*> ptrs((size_t)n_dims);
+        for (int32_t d = 0; d < n_dims; ++d) ptrs[(size_t)d] = handles[param_owner[d]]->d_params + (size_t)param_rows[d] * (size_t)lead->N;
+        HIPCHK(rscm::dev_malloc((void**)&s->d_param_ptr, ptrs.size() * sizeof(double*)));
+        HIPCHK(hipMemcpy(s->d_param_ptr, ptrs.data(), ptrs.size() * sizeof(double*), hipMemcpyHostToDevice));
+        // the observation rows where their owners store them; one partial sum per (owner, variable) in the caller's order
+        return sampler_install_table(s, rows);
+    };
+    if (int rc = fill()) {
         rscm_sampler_destroy(s);
         return rc;
-    };
-    const size_t W = (size_t)n_walkers, H = (size_t)lead->N, D = (size_t)n_dims;
-#define CK(expr)                                                                               \
-    do {                                                                                       \
-        hipError_t e2_ = (expr);                                                               \
-        if (e2_ != hipSuccess)                                                                 \
-            return cleanup(fail(e2_ == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, \
-                                "%s failed: %s", #expr, hipGetErrorString(e2_)));              \
-    } while (0)
-    CK(rscm::dev_malloc(&s->d_kind, D * sizeof(int32_t)));
-    CK(rscm::dev_malloc(&s->d_pa, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_pb, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_plo, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_phi, D * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_pos, D * W * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_logp, W * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_prop, D * H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_z, H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_lp, H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_send, (D + 1) * H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_recv, (size_t)n_ranks * (D + 1) * H * sizeof(double)));
-    CK(rscm::dev_malloc(&s->d_nacc, W * sizeof(int64_t)));
-    CK(rscm::dev_malloc(&s->d_nprop, W * sizeof(int64_t)));
-    CK(rscm::dev_malloc((void**)&s->d_param_ptr, D * sizeof(double*)));
-    {
-        std::vector<double*> ptrs(D);
-        for (size_t d = 0; d < D; ++d) ptrs[d] = handles[param_owner[d]]->d_params + (size_t)param_rows[d] * H;
-        CK(hipMemcpy(s->d_param_ptr, ptrs.data(), D * sizeof(double*), hipMemcpyHostToDevice));
     }
-    CK(hipMemcpy(s->d_kind, prior_kind, D * sizeof(int32_t), hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->d_pa, prior_a, D * sizeof(double), hipMemcpyHostToDevice));
-    CK(hipMemcpy(s->d_pb, prior_b, D * sizeof(double), hipMemcpyHostToDevice));
-    {
-        std::vector<double> lo(D, -std::numeric_limits<double>::infinity()), hi(D, std::numeric_limits<double>::infinity());
-        if (prior_low && prior_high)
-            for (size_t d = 0; d < D; ++d) { lo[d] = prior_low[d]; hi[d] = prior_high[d]; }
-        CK(hipMemcpy(s->d_plo, lo.data(), D * sizeof(double), hipMemcpyHostToDevice));
-        CK(hipMemcpy(s->d_phi, hi.data(), D * sizeof(double), hipMemcpyHostToDevice));
-    }
-    CK(hipMemset(s->d_nacc, 0, W * sizeof(int64_t)));
-    CK(hipMemset(s->d_nprop, 0, W * sizeof(int64_t)));
-    CK(hipEventCreate(&s->ev0));
-    CK(hipEventCreate(&s->ev1));
-    {   // the observation rows where their owners store them; one partial sum per (owner, variable) in the caller's order
-        const size_t sz_ptr = (size_t)n_obs * sizeof(double*), sz_i = (size_t)n_obs * sizeof(int32_t), sz_d = (size_t)n_obs * sizeof(double);
-        const size_t off_val = sz_ptr, off_sig = off_val + sz_d, off_grp = off_sig + sz_d;
-        std::vector<unsigned char> blob(off_grp + sz_i + 8);
-        std::vector<const double*> ptrs((size_t)n_obs);
-        std::vector<int32_t> grp((size_t)n_obs);
-        for (int32_t j = 0; j < n_obs; ++j) {
-            const rscm_ens* h = handles[obs_owner[j]];
-            ptrs[(size_t)j] = h->series(obs_var[j]) + (size_t)obs_tidx[j] * h->N;
-            // the group id: the index of the run's first observation (unique per (owner, variable) whatever the variable count)
-            grp[(size_t)j] = (j > 0 && obs_owner[j] == obs_owner[j - 1] && obs_var[j] == obs_var[j - 1]) ? grp[(size_t)j - 1] : j;
-        }
-        if (n_obs > 0) {
-            memcpy(blob.data(), ptrs.data(), sz_ptr);
-            memcpy(blob.data() + off_val, obs_value, sz_d);
-            memcpy(blob.data() + off_sig, obs_sigma, sz_d);
-            memcpy(blob.data() + off_grp, grp.data(), sz_i);
-        }
-        CK(rscm::dev_malloc(&s->d_sobs, blob.size()));
-        CK(hipMemcpy(s->d_sobs, blob.data(), blob.size(), hipMemcpyHostToDevice));
-        s->lik.n_members = lead->N;
-        s->lik.n_obs = n_obs;
-        s->lik.normalize = normalize ? 1 : 0;
-        s->lik.obs_series = (const double* const*)s->d_sobs;
-        s->lik.obs_value = (const double*)((char*)s->d_sobs + off_val);
-        s->lik.obs_sigma = (const double*)((char*)s->d_sobs + off_sig);
-        s->lik.obs_group = (const int32_t*)((char*)s->d_sobs + off_grp);
-        s->lik.out = lead->d_loglik;
-    }
-#undef CK
     *out = s;
     return RSCM_OK;
     GUARD_END
@@ -489,7 +403,6 @@ int rscm_sampler_destroy(rscm_sampler* s)
     (void)hipFree(s->d_pb); (void)hipFree(s->d_plo); (void)hipFree(s->d_phi); (void)hipFree(s->d_pos); (void)hipFree(s->d_logp); (void)hipFree(s->d_prop);
     (void)hipFree(s->d_z); (void)hipFree(s->d_lp); (void)hipFree(s->d_nacc); (void)hipFree(s->d_nprop);
     (void)hipFree(s->d_sobs);
-    (void)hipFree(s->d_sref);
     (void)hipFree((void*)s->d_param_ptr);
     (void)hipFree(s->d_send);
     (void)hipFree(s->d_recv);
@@ -519,51 +432,11 @@ int rscm_sampler_set_reference(rscm_sampler* s, int32_t n_ref, const int32_t* re
     if (n_ref > 0 && graph != (ref_owner != nullptr))
         return fail(RSCM_ERR_INVALID, graph ? "a graph sampler needs ref_owner" : "ref_owner is for graph samplers: pass NULL");
     if (s->fused) return prepare_ref(h, n_ref, ref_var, ref_begin, ref_end, ref_stride);
-    if (int rc = check_reference(h->T, n_ref, graph ? ref_owner : nullptr, ref_var, ref_begin, ref_end, ref_stride)) return rc;
-    if (int rc = set_device(h)) return rc;
-    HIPCHK(hipStreamSynchronize(h->stream));
-    (void)hipFree(s->d_sref);
-    s->d_sref = nullptr;
-    s->use_ref = false;
-    s->graph_last_step = s->obs_last_step;
-    if (n_ref == 0) return RSCM_OK;
-    const int32_t n_obs = (int32_t)s->obs_var.size();
-    std::vector<const double*> ptrs((size_t)n_obs), ref_rows;
-    std::vector<int32_t> grp((size_t)n_obs), obs_ref((size_t)n_obs, -1), ref_off((size_t)n_ref + 1, 0);
-    auto owner_of = [&](int32_t j) { return graph ? s->obs_owner[(size_t)j] : 0; };
-    auto handle_of = [&](int32_t k) { return graph ? s->graph[(size_t)k] : h; };
-    for (int32_t j = 0; j < n_obs; ++j) {  // as at creation
-        const rscm_ens* g = handle_of(owner_of(j));
-        ptrs[(size_t)j] = g->series(s->obs_var[(size_t)j]) + (size_t)s->obs_tidx[(size_t)j] * g->N;
-        if (!graph) grp[(size_t)j] = s->obs_var[(size_t)j];
-        else grp[(size_t)j] = (j > 0 && owner_of(j) == owner_of(j - 1) && s->obs_var[(size_t)j] == s->obs_var[(size_t)j - 1]) ? grp[(size_t)j - 1] : j;
-    }
-    int32_t last_step = s->obs_last_step;
-    for (int32_t e = 0; e < n_ref; ++e) {
-        const int32_t owner = graph ? ref_owner[e] : 0;
-        if (graph && (owner < 0 || owner >= (int32_t)s->graph.size())) return fail(RSCM_ERR_INVALID, "reference period %d: owner %d out of range", e, owner);
-        const rscm_ens* g = handle_of(owner);
-        if (ref_var[e] < 1 || ref_var[e] >= g->V) return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no stored series", e, ref_var[e]);
-        if (ref_end[e] > g->T) return fail(RSCM_ERR_INVALID, "reference period %d: rows beyond the owner's axis", e);
-        bool observed = false;
-        for (int32_t j = 0; j < n_obs; ++j)
-            if (owner_of(j) == owner && s->obs_var[(size_t)j] == ref_var[e]) {
-                obs_ref[(size_t)j] = e;
-                observed = true;
-            }
-        if (!observed) return fail(RSCM_ERR_INVALID, "reference period %d: variable %d has no observation", e, ref_var[e]);
-        for (int32_t t = ref_begin[e]; t < ref_end[e]; t += ref_stride[e]) {
-            ref_rows.push_back(g->series(ref_var[e]) + (size_t)t * g->N);
-            last_step = std::max(last_step, t);
-        }
-        ref_off[(size_t)e + 1] = (int32_t)ref_rows.size();
-    }
-    if (int rc = upload_loglik_ref(n_obs, ptrs.data(), s->obs_value.data(), s->obs_sigma.data(), grp.data(), obs_ref.data(), n_ref, ref_off.data(),
-                                   ref_rows.data(), s->normalize, h->N, h->d_loglik, &s->d_sref, &s->lik_ref))
+    LoglikRows rows;
+    if (int rc = resolve_loglik_rows(graph ? s->graph.data() : &h, graph ? (int32_t)s->graph.size() : 1, true, s->observations(),
+                                     {n_ref, graph ? ref_owner : nullptr, ref_var, ref_begin, ref_end, ref_stride}, &rows))
         return rc;
-    s->use_ref = true;
-    s->graph_last_step = last_step;   // the graph steps to the last row the likelihood reads
-    return RSCM_OK;
+    return sampler_install_table(s, rows);
     GUARD_END
 }
 

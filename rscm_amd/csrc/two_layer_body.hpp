@@ -214,7 +214,7 @@ __device__ __forceinline__ void lik_consume(const TwoLayerArgs& a, LikAcc& L, in
 // it (the sum starts at -0.0, the additive identity: the bits of rscm_ens_set_baseline).  An observation of that variable at a row up
 // to the period's last cannot be scored yet: its model value goes to the handle's scratch ([slot][N], one coalesced store).  When the
 // last reference row is in, b = sum / count is formed and the waiting observations are scored in observation order (one coalesced load
-// each); later ones are scored on the fly.  A variable's partial sum so sees the addends loglik_ref_kernel (ensemble_ops.hip) gives it,
+// each); later ones are scored on the fly.  A variable's partial sum so sees the addends loglik_kernel (ensemble_ops.hip) gives it,
 // in the same order: the two paths agree bit for bit.
 struct LikRef {
     double sum_s = -0.0, sum_d = -0.0, b_s = 0.0, b_d = 0.0;

@@ -346,67 +346,37 @@ class Ensemble:
             rv.append(self._var(var)), rb.append(rows[0]), re_.append(rows[1]), rs.append(rows[2] if len(rows) == 3 else 1)
         return tuple(np.ascontiguousarray(x, dtype=np.int32) for x in (rv, rb, re_, rs))
 
+    def _loglik(self, entry, obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device, reference):
+        """``entry`` is ``"loglik"`` or ``"run_loglik"``: calls ``rscm_ens_{entry}[_ref][_device]``."""
+        ov = np.ascontiguousarray([self._var(v) for v in np.atleast_1d(obs_var)], dtype=np.int32)
+        ot = np.ascontiguousarray(obs_tidx, dtype=np.int32)
+        val, sig = L.f64(obs_value), L.f64(obs_sigma)
+        if not (len(ov) == len(ot) == len(val) == len(sig)):
+            raise ValueError("observation arrays differ in length")
+        args = [self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig), int(normalize)]
+        if reference:
+            ref = self._reference(reference)
+            args += [len(ref[0])] + [L.iptr(x) for x in ref]
+        fn = getattr(self._lib, "rscm_ens_" + entry + ("_ref" if reference else "") + ("_device" if on_device else ""))
+        if on_device:
+            p = C.c_void_p()
+            L.check(fn(*args, C.byref(p)))
+            return DeviceVector(p.value, self.n_members, np.float64, self)
+        out = np.empty(self.n_members)
+        L.check(fn(*args, L.dptr(out)))
+        return out
+
     def loglik(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, on_device: bool = False, reference=None):
         """Gaussian log-likelihood per member, ``[N]``; ``on_device`` leaves it in device memory (a
         ``DeviceVector``) for a reduction or all-gather without a host round trip.  ``reference``:
         ``{variable: (t_begin, t_end[, t_stride])}`` in row indices -- that variable's observations are anomalies from the
         member's own mean over those rows (rscm_ens_loglik_ref)."""
-        ov = np.ascontiguousarray([self._var(v) for v in np.atleast_1d(obs_var)], dtype=np.int32)
-        ot = np.ascontiguousarray(obs_tidx, dtype=np.int32)
-        val, sig = L.f64(obs_value), L.f64(obs_sigma)
-        if not (len(ov) == len(ot) == len(val) == len(sig)):
-            raise ValueError("observation arrays differ in length")
-        if reference:
-            rv, rb, re_, rs = self._reference(reference)
-            ref = (len(rv), L.iptr(rv), L.iptr(rb), L.iptr(re_), L.iptr(rs))
-            if on_device:
-                p = C.c_void_p()
-                L.check(self._lib.rscm_ens_loglik_ref_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
-                                                             int(normalize), *ref, C.byref(p)))
-                return DeviceVector(p.value, self.n_members, np.float64, self)
-            out = np.empty(self.n_members)
-            L.check(self._lib.rscm_ens_loglik_ref(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig), int(normalize),
-                                                  *ref, L.dptr(out)))
-            return out
-        if on_device:
-            p = C.c_void_p()
-            L.check(self._lib.rscm_ens_loglik_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val),
-                                                     L.dptr(sig), int(normalize), C.byref(p)))
-            return DeviceVector(p.value, self.n_members, np.float64, self)
-        out = np.empty(self.n_members)
-        L.check(self._lib.rscm_ens_loglik(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val),
-                                          L.dptr(sig), int(normalize), L.dptr(out)))
-        return out
+        return self._loglik("loglik", obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device, reference)
 
     def run_loglik(self, obs_var, obs_tidx, obs_value, obs_sigma, normalize: bool = False, on_device: bool = False, reference=None):
         """Fused run + Gaussian log-likelihood: no series is written (see rscm_ens_run_loglik).  ``reference`` as for ``loglik``
         (rscm_ens_run_loglik_ref)."""
-        ov = np.ascontiguousarray([self._var(v) for v in np.atleast_1d(obs_var)], dtype=np.int32)
-        ot = np.ascontiguousarray(obs_tidx, dtype=np.int32)
-        val, sig = L.f64(obs_value), L.f64(obs_sigma)
-        if not (len(ov) == len(ot) == len(val) == len(sig)):
-            raise ValueError("observation arrays differ in length")
-        if reference:
-            rv, rb, re_, rs = self._reference(reference)
-            ref = (len(rv), L.iptr(rv), L.iptr(rb), L.iptr(re_), L.iptr(rs))
-            if on_device:
-                p = C.c_void_p()
-                L.check(self._lib.rscm_ens_run_loglik_ref_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
-                                                                 int(normalize), *ref, C.byref(p)))
-                return DeviceVector(p.value, self.n_members, np.float64, self)
-            out = np.empty(self.n_members)
-            L.check(self._lib.rscm_ens_run_loglik_ref(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val), L.dptr(sig),
-                                                      int(normalize), *ref, L.dptr(out)))
-            return out
-        if on_device:
-            p = C.c_void_p()
-            L.check(self._lib.rscm_ens_run_loglik_device(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val),
-                                                         L.dptr(sig), int(normalize), C.byref(p)))
-            return DeviceVector(p.value, self.n_members, np.float64, self)
-        out = np.empty(self.n_members)
-        L.check(self._lib.rscm_ens_run_loglik(self._h, len(ov), L.iptr(ov), L.iptr(ot), L.dptr(val),
-                                              L.dptr(sig), int(normalize), L.dptr(out)))
-        return out
+        return self._loglik("run_loglik", obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device, reference)
 
     def summary(self, var, tidx: int) -> Dict[str, float]:
         out = np.empty(4)

@@ -1,7 +1,7 @@
 """Reference periods on the device (ABI minor 9; DESIGN.md section 7, "Reference periods"): a target variable observed as an anomaly
 from a reference period is scored against x - b, b the member's own mean over the period's rows.
 
-  * the stored path (rscm_ens_loglik_ref, loglik_ref_kernel) against the numpy restatement of tests/host_likelihood.py on the fetched
+  * the stored path (rscm_ens_loglik_ref, loglik_kernel) against the numpy restatement of tests/host_likelihood.py on the fetched
     series: bit for bit unnormalised (add, subtract, multiply, divide only; the library is built with contraction off), rtol 1e-13
     normalised (the device's log is not glibc's: the tolerance tests/test_gpu_parity.py applies to the normalised likelihood);
   * the fused two-layer run + likelihood (rscm_ens_run_loglik_ref, two_layer_ref_kernel) against the stored path, bit for bit in both
@@ -123,6 +123,11 @@ def test_stored_loglik_with_reference_periods_equals_numpy(ra):
                 assert not np.array_equal(got, e.loglik(ov, ot, val, sig, normalize))
             dev = e.loglik(ov, ot, val, sig, False, on_device=True, reference=reference)
             assert_bit_equal(dev.to_host(), e.loglik(ov, ot, val, sig, False, reference=reference), f"{name}: on_device")
+            # the same kernel scores a table without periods: its bits are the restatement's too, group boundaries included
+            assert_bit_equal(e.loglik(ov, ot, val, sig, False), hl.loglik(series, ov, ot, val, sig, False, None), f"{name}: no period")
+        none = np.empty(0, dtype=np.int32)
+        assert_bit_equal(e.loglik(none, none, np.empty(0), np.empty(0), False), hl.loglik(series, none, none, [], [], False, None),
+                         "no observations")
         assert_bit_equal(e.baseline(), kept, "the handle's own baseline after likelihood calls")
         # a member that is not finite inside the period only (not at an observed row) is a failed member
         for member, bad in ((42, np.nan), (43, np.inf)):
@@ -354,7 +359,8 @@ def test_sampler_scores_are_log_prior_plus_the_reference_period_likelihood(ra):
 
 
 def test_sampler_scores_with_a_stored_series_evaluator(ra):
-    """The coupled kind has no fused likelihood: its sampler runs a half and scores the stored series with loglik_ref_kernel."""
+    """The coupled kind has no fused likelihood: its sampler runs a half and scores the stored series with loglik_kernel, from the
+    one table rscm_sampler_set_reference lays out again -- with the periods, and without them once they are removed."""
     from rscm_amd import calibrate as cal
     from rscm_amd import _lib as L
     t = axis_values(1750, 1900)
@@ -388,10 +394,24 @@ def test_sampler_scores_with_a_stored_series_evaluator(ra):
             got = _log_prob(lib, h, pos)
         finally:
             lib.rscm_sampler_destroy(h)
+        h = _c_sampler(ev, W, rows, base, lo, hi, obs)
+        try:
+            never = _log_prob(lib, h, pos)
+        finally:
+            lib.rscm_sampler_destroy(h)
+        h = _c_sampler(ev, W, rows, base, lo, hi, obs)
+        try:
+            L.check(_set_reference(lib, h, reference))
+            L.check(lib.rscm_sampler_set_reference(h, 0, None, None, None, None, None))
+            removed = _log_prob(lib, h, pos)
+        finally:
+            lib.rscm_sampler_destroy(h)
         whole.run()
         ll = whole.loglik(*obs, reference=reference)
         assert_bit_equal(got, lp + ll, "stored-series evaluator")
         assert np.isfinite(got).all() and not np.array_equal(got, lp + whole.loglik(*obs))
+        assert_bit_equal(never, lp + whole.loglik(*obs), "stored-series evaluator: never given a period")
+        assert_bit_equal(removed, lp + whole.loglik(*obs), "stored-series evaluator: periods removed again")
 
 
 # ------------------------------------------------------------------------------------------------ the sampler through the Python front
@@ -505,11 +525,12 @@ def test_graph_sampler_scores_with_a_reference_period(ra):
     assert runner._graph
     truth = runner.run([1.25, 30.0])
     base = baseline(np.array([[truth["Surface Temperature"][float(y)]] for y in range(1790, 1821)]))[0]
-    target = cal.Target()
-    for y in range(1780, 1841, 10):   # the period 1790-1820 ends before the last observation; CO2 is observed later still
-        target.add_observation("Surface Temperature", float(y), truth["Surface Temperature"][float(y)] - base, 0.01)
-    for y in range(1780, 1851, 10):
-        target.add_observation("Atmospheric Concentration|CO2", float(y), truth["Atmospheric Concentration|CO2"][float(y)], 0.2)
+    target, absolute = cal.Target(), cal.Target()
+    for tg in (target, absolute):
+        for y in range(1780, 1841, 10):   # the period 1790-1820 ends before the last observation; CO2 is observed later still
+            tg.add_observation("Surface Temperature", float(y), truth["Surface Temperature"][float(y)] - base, 0.01)
+        for y in range(1780, 1851, 10):
+            tg.add_observation("Atmospheric Concentration|CO2", float(y), truth["Atmospheric Concentration|CO2"][float(y)], 0.2)
     target.set_reference_period("Surface Temperature", 1790, 1820)
     params = cal.ParameterSet().add("TwoLayer.lambda0", cal.Uniform(0.8, 1.6)).add("tau", cal.Uniform(15.0, 45.0))
     lik = cal.GaussianLikelihood()
@@ -526,6 +547,12 @@ def test_graph_sampler_scores_with_a_reference_period(ra):
     assert same.any() and (~same).any() and want[7] == -np.inf
     assert_bit_equal(got_lp[same], want[same], "graph evaluator: walkers that did not move")
     assert_bit_equal(got_lp[~same], host.log_posterior_batch(got_pos[~same]), "graph evaluator: accepted proposals")
+    # the same target without its period: the table of the graph evaluator with no reference entry
+    want = cal.EnsembleSampler(params, runner, lik, absolute).log_posterior_batch(pos)
+    chain = cal.DeviceEnsembleSampler(params, runner, lik, absolute).run(1, cal.WalkerInit.explicit(pos), n_walkers=W, seed=3)
+    same = (chain.flat_samples() == pos).all(axis=1)
+    assert same.any() and np.isfinite(want[same]).any()
+    assert_bit_equal(chain.flat_log_probs()[same], want[same], "graph evaluator: no period")
     # a period that ends after the last observation: the graph steps on to the period's last row
     late = cal.Target()
     late.add_observation("Surface Temperature", 1780.0, 0.01, 0.05).add_observation("Surface Temperature", 1800.0, 0.02, 0.05)
