@@ -87,8 +87,10 @@ extern "C" {
  *  10  posterior ensembles on the device: rscm_ens_weights_stats, rscm_ens_resample, rscm_gpu_resample_offset,
  *      rscm_ens_gather_members
  *  11  per-group quantiles and exceedance: rscm_ens_set_member_groups, rscm_ens_member_groups_devptr,
- *      rscm_ens_clear_member_groups, RSCM_SELECT_GROUPED, rscm_ens_exceedance_grouped */
-#define RSCM_GPU_ABI_MINOR 11
+ *      rscm_ens_clear_member_groups, RSCM_SELECT_GROUPED, rscm_ens_exceedance_grouped
+ *  12  two-layer mix handles -- per-member forcing as a scaled sum of shared components: rscm_ens_create_mix,
+ *      rscm_ens_n_forcing_components, RSCM_TL_P_COEFF0, RSCM_TL_MAX_COMPONENTS */
+#define RSCM_GPU_ABI_MINOR 12
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -369,6 +371,10 @@ extern "C" {
  *   erf_2xco2 (co2_erf.rs:18-25; CO2ERF.conc_pi == conc_pi as in docs/notebooks/coupled_model.py) */
 #define RSCM_TL_NPARAMS 6
 #define RSCM_CP_NPARAMS 10
+/* A two-layer MIX handle (rscm_ens_create_mix) with K forcing components has P = 6 + K: rows RSCM_TL_P_COEFF0 .. RSCM_TL_P_COEFF0 + K - 1
+ * are the members' coefficients c_0 .. c_K-1 of the components. */
+#define RSCM_TL_P_COEFF0 6
+#define RSCM_TL_MAX_COMPONENTS 8
 
 /* VariableSource of the shared input as seen by its consumer (state/mod.rs:156-170) */
 #define RSCM_SRC_EXOGENOUS 0 /* read index n   */
@@ -439,12 +445,33 @@ RSCM_API int rscm_ens_create_ex(int32_t kind, int64_t n_members, int32_t n_times
 RSCM_API int rscm_ens_create_windowed(int32_t kind, int64_t n_members, int32_t n_times, const double* time_bounds,
                                       int32_t device_id, uint32_t flags, int32_t window_rows, int32_t out_stride,
                                       int32_t n_out_vars, const int32_t* out_vars, rscm_ens** out);
+/* A two-layer MIX handle (ABI minor 12): an ensemble whose members differ in their FORCING as well as in the six model parameters.
+ * The shared input block is [n_scen][K][n_times], K = n_components forcing components per scenario (rscm_ens_set_forcing takes it in
+ * the layout of the multi-input kinds; scenario_of_member and `source` keep their meaning), and member i in scenario s is forced at
+ * model index n by
+ *     F = S[s][0][n] * c_0[i];   F = F + S[s][k][n] * c_k[i]   for k = 1 .. K-1, in that order
+ * -- IEEE f64 multiplies and adds, each rounded on its own (no FMA), in BOTH arithmetic modes: RSCM_MODE_FAST changes what happens
+ * to F afterwards, not how F is formed.  NaN and Inf propagate and no contributor is skipped: this is an exogenous series formed per
+ * member (what a factory closure that scales exogenous series does in the reference's ModelRunner), NOT the schema aggregate of
+ * RSCM_KIND_AGGREGATE, which skips NaN contributors.
+ * The coefficients c_k are parameter rows RSCM_TL_P_COEFF0 + k of the handle: rscm_ens_n_params reports 6 + K, and every call that
+ * moves parameter rows (rscm_ens_set_params / _aos, rscm_ens_get_params, rscm_ens_params_devptr, rscm_ens_sample_lhs with 6 + K bounds,
+ * the samplers' param_rows, rscm_ens_gather_members) carries them.  rscm_ens_n_inputs reports K.
+ * kind must be RSCM_KIND_TWO_LAYER; flags 0 or RSCM_FLAG_NO_SERIES (no windowed storage); n_components in [1, RSCM_TL_MAX_COMPONENTS];
+ * anything else is RSCM_ERR_INVALID.  A mix handle runs on its own: rscm_ens_link_input onto it, rscm_ens_run_lockstep and
+ * rscm_sampler_create_graph with it, and rscm_ens_gather_members between handles of different component counts return
+ * RSCM_ERR_INVALID (rscm_sampler_create takes it as the one evaluator). */
+RSCM_API int rscm_ens_create_mix(int32_t kind, int64_t n_members, int32_t n_times, const double* time_bounds, int32_t device_id,
+                                 uint32_t flags, int32_t n_components, rscm_ens** out);
 RSCM_API int rscm_ens_destroy(rscm_ens* h);
 
 RSCM_API int rscm_ens_n_params(const rscm_ens* h, int32_t* out);
 RSCM_API int rscm_ens_n_vars(const rscm_ens* h, int32_t* out);
-/* Rows per scenario of the shared input block (variable 0): 1 for the first three kinds. */
+/* Rows per scenario of the shared input block (variable 0): 1 for the first three kinds, K for a mix handle. */
 RSCM_API int rscm_ens_n_inputs(const rscm_ens* h, int32_t* out);
+/* K of a handle made by rscm_ens_create_mix, 0 for every other handle (a plain two-layer handle and a mix handle with K = 1 both
+ * report one input row). */
+RSCM_API int rscm_ens_n_forcing_components(const rscm_ens* h, int32_t* out);
 RSCM_API int rscm_ens_n_members(const rscm_ens* h, int64_t* out);
 RSCM_API int rscm_ens_n_times(const rscm_ens* h, int32_t* out);
 

@@ -28,6 +28,8 @@ COMP_TWO_LAYER, COMP_CARBON_CYCLE = 0, 1
 MODE_EXACT, MODE_FAST = 0, 1
 FLAG_NO_SERIES = 1
 FLAG_WINDOWED = 2
+TL_P_COEFF0 = 6          # a mix ensemble's coefficient rows start here (RSCM_TL_P_COEFF0)
+TL_MAX_COMPONENTS = 8    # RSCM_TL_MAX_COMPONENTS
 SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
 SELECT_ANOMALY = 2
 SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
@@ -241,10 +243,12 @@ SIGNATURES = {
                                      C.POINTER(_h)]),
     "rscm_ens_create_windowed": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_uint32, C.c_int32, C.c_int32,
                                            C.c_int32, _ip, C.POINTER(_h)]),
+    "rscm_ens_create_mix": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _dp, C.c_int32, C.c_uint32, C.c_int32, C.POINTER(_h)]),
     "rscm_ens_destroy": (C.c_int, [_h]),
     "rscm_ens_n_params": (C.c_int, [_h, _ip]),
     "rscm_ens_n_vars": (C.c_int, [_h, _ip]),
     "rscm_ens_n_inputs": (C.c_int, [_h, _ip]),
+    "rscm_ens_n_forcing_components": (C.c_int, [_h, _ip]),
     "rscm_ens_n_members": (C.c_int, [_h, C.POINTER(C.c_int64)]),
     "rscm_ens_n_times": (C.c_int, [_h, _ip]),
     "rscm_ens_set_mode": (C.c_int, [_h, C.c_int32]),

@@ -467,6 +467,7 @@ class ModelBuilder:
         self._schema: Optional[VariableSchema] = None
         self._device = 0
         self._grid_weights: Dict["GridType", List[float]] = {}
+        self._mix: Optional[Tuple[str, Dict[str, Timeseries], Dict[str, float]]] = None   # with_forcing_components
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -495,6 +496,71 @@ class ModelBuilder:
     def with_exogenous_variable(self, name: str, timeseries: Timeseries) -> "ModelBuilder":
         self._exogenous.add_timeseries(name, timeseries, VariableType.Exogenous)
         return self
+
+    def with_forcing_components(self, variable: str, components: Dict[str, Timeseries],
+                                scales: Optional[Dict[str, float]] = None) -> "ModelBuilder":
+        """Extension: supply the exogenous ``variable`` as a sum of named component series, each scaled PER MEMBER -- what a
+        factory closure that scales exogenous series does in the reference's ``ModelRunner``, kept on the device.  For the model
+        that is one ``TwoLayer`` reading ``variable`` as its forcing, ``build()`` makes a mix ensemble
+        (``Ensemble(..., forcing_components=names)``): member i is forced by ``((S_0 c_0 + S_1 c_1) + ...)``, every product and
+        sum rounded on its own, NaN and Inf propagating (an exogenous series formed per member, not the schema's Weighted
+        aggregate, which skips NaN contributors).  The coefficients are model parameters named ``"forcing_scale|<name>"``
+        after the component's own in ``Model.param_order``; ``scales`` gives their base values (default 1.0)."""
+        names = [str(n) for n in components]
+        if not 1 <= len(names) <= L.TL_MAX_COMPONENTS:
+            raise ValueError(f"with_forcing_components takes 1 to {L.TL_MAX_COMPONENTS} components, got {len(names)}")
+        for n, ts in components.items():
+            if not isinstance(ts, Timeseries):
+                raise TypeError(f"component {n!r} must be a Timeseries")
+        unknown = [n for n in (scales or {}) if n not in components]
+        if unknown:
+            raise ValueError(f"scales given for unknown component(s) {unknown}; components: {names}")
+        self._mix = (str(variable), {str(n): ts for n, ts in components.items()},
+                     {n: float((scales or {}).get(n, 1.0)) for n in names})
+        return self
+
+    def forcing_mix_plan(self) -> Optional[Dict[str, object]]:
+        """What ``build()`` makes of ``with_forcing_components`` (None without it), formed on the host: ``names``, the
+        ``param_order`` and ``base_params`` of the model and the ``[K][T]`` component block on the model's axis.  Raises
+        ``ValueError`` for a model shape the mix ensemble does not cover."""
+        if self._mix is None:
+            return None
+        variable, components, scales = self._mix
+        endogenous, sources, exo_names, aggregates = self._resolve()
+        types = [c.type_name for c in self._components]
+        erf = "Effective Radiative Forcing"
+        hint = ("per-member forcing components are available for the model that is one TwoLayer reading the variable as its "
+                "exogenous forcing; for any other graph put a Weighted aggregate (VariableSchema.add_aggregate) in front of the consumer")
+        if any(getattr(c, "is_python", False) for c in self._components) or types != ["TwoLayer"] or aggregates:
+            raise ValueError(f"with_forcing_components: this model has components {types}"
+                             f"{' and schema aggregates' if aggregates else ''}; {hint}")
+        if variable != erf or variable not in exo_names:
+            raise ValueError(f"with_forcing_components: {variable!r} is not the exogenous forcing the TwoLayer reads ({erf!r}); {hint}")
+        if variable in self._exogenous:
+            raise ValueError(f"with_forcing_components: {variable!r} is also supplied with with_exogenous_variable; give one of the two")
+        rows = []
+        for name, ts in components.items():
+            self._check_units(variable, ts.units)
+            rows.append(ts.interpolate_into(self._axis).values())
+        names = tuple(components)
+        base = [self._components[0].parameters[k] for k in TL_PARAM_ORDER] + [scales[n] for n in names]
+        return {"names": names, "param_order": TL_PARAM_ORDER + tuple(f"forcing_scale|{n}" for n in names),
+                "base_params": np.array(base, dtype=np.float64), "block": np.stack(rows)}
+
+    def _build_mix(self, n_members: int, store_series: bool) -> "Model":
+        plan = self.forcing_mix_plan()
+        endogenous, sources, _, _ = self._resolve()
+        ens = Ensemble(L.KIND_TWO_LAYER, n_members, self._axis.bounds(), device=self._device, store_series=store_series,
+                       forcing_components=plan["names"])
+        ens.set_step_size(L.COMP_TWO_LAYER, 0.1)
+        ens.set_params(np.repeat(plan["base_params"][:, None], n_members, axis=1))
+        ens.set_forcing(plan["block"][None], None, L.SRC_EXOGENOUS)
+        for name, vid in ens.var_ids.items():
+            if vid > 0 and name in self._initial:
+                ens.set_initial(vid, self._initial[name])
+        model = Model(ens, self._axis, sources, endogenous, plan["block"], dict(self._initial), plan["param_order"], plan["base_params"])
+        model._builder = self
+        return model
 
     def with_exogenous_collection(self, collection: TimeseriesCollection) -> "ModelBuilder":
         for name in collection.names():
@@ -1030,6 +1096,10 @@ class ModelBuilder:
         (model/builder.rs:735-830); 1e5 members x 9001 monthly points x 36 series do not fit a GPU that
         way.  ``get_series(name, t_stride=output_stride)`` reads the kept rows."""
         endogenous, sources, exo_names, aggregates = self._resolve()
+        if self._mix is not None:
+            if series_window is not None:
+                raise ValueError("with_forcing_components: a mix ensemble has no windowed storage (series_window)")
+            return self._build_mix(n_members, store_series)
         if series_window is not None:
             if any(getattr(c, "is_python", False) for c in self._components):
                 raise NotImplementedError("Python components read whole host series: no series_window for such graphs")

@@ -112,6 +112,7 @@ struct rscm_ens {
     double* d_series = nullptr;  // [(V-1)][T][N], variable v at slot v-1
     double* d_forcing = nullptr; // [S][n_inputs][T]
     int32_t n_inputs = 1;        // rows per scenario of the shared input block
+    int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
     double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;
     // OceanCarbon: flux history (internal state) and the tabulated impulse response

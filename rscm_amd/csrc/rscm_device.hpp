@@ -21,6 +21,8 @@ enum Kind : int {
 constexpr int kBlock = RSCM_BLOCK;           // 256 = 4 wavefronts of 64: one per SIMD of a CU
 constexpr int kMaxStaticLds = 64 * 1024;     // above this the launcher raises the dynamic limit
 constexpr int kMaxLds = 160 * 1024;          // CDNA4: 160 KiB per CU
+constexpr int kMaxForcingComponents = 8;     // RSCM_TL_MAX_COMPONENTS: forcing components of a two-layer mix handle
+constexpr int kTwoLayerCoeff0 = 6;           // RSCM_TL_P_COEFF0: the parameter row of its first coefficient
 
 // Linked inputs (rscm_ens_link_input): input row k of a member is read from the stored series of
 // another ensemble of the same shape -- row[k] is that series, [T][N], off[k] the index offset of
@@ -328,10 +330,10 @@ struct TwoLayerArgs {
     int32_t step_begin, step_end;
     int32_t n_scen;
     int32_t src_off;         // 0: Exogenous -> F[n]; 1: UpstreamOutput -> F[n+1]
-    int32_t lds_forcing;     // 1: forcing slice staged in LDS, 0: read through L2
-    const double* params;    // [6][N]
+    int32_t lds_forcing;     // 1: forcing slice staged in LDS ([S][max(n_comp, 1)][len]), 0: read through L2
+    const double* params;    // [6][N] ([6 + n_comp][N] for a mix handle)
     uint64_t uniform_rows;   // bit j: parameter row j (< 64) holds one value for all members (param_at)
-    const double* forcing;   // [S][T]
+    const double* forcing;   // [S][T] ([S][n_comp][T] for a mix handle)
     const double* link;      // [T][N] linked forcing (InputLinks, one row) or nullptr
     const int32_t* scen;     // [N] or nullptr
     const int32_t* nsub;     // [T-1] RK4 sub-steps of step n = ceil((b[n+1]-b[n])/h)
@@ -350,6 +352,10 @@ struct TwoLayerArgs {
                                   // rscm_gpu_set_two_layer_guard); 0 guards the sub-step states where the boxes allow it
     int32_t count_guards;         // EXACT stand-alone launches: 1 counts the guard each wavefront took (test hook,
                                   // rscm_gpu_two_layer_guard_counts); 0 counts nothing
+    int32_t n_comp;               // 0: `forcing` is [S][T].  K in 1..kMaxForcingComponents (a mix handle, rscm_ens_create_mix): `forcing`
+                                  // is [S][K][T], `params` has rows 6..6+K-1 and member i is forced by ((S_0 c_0 + S_1 c_1) + ...) + S_K-1 c_K-1,
+                                  // every product and sum rounded on its own (the MIX instantiations; never linked).  Sits in what was
+                                  // padding: the layout of the other fields is that of the plain launches
     const int32_t* obs_tidx;      // [n_obs] ascending
     const int32_t* obs_is_deep;   // [n_obs] 0: Surface Temperature, 1: Deep Ocean Temperature
     const double* obs_value;
@@ -681,6 +687,16 @@ bool group_seq_available(const int32_t* kinds, int32_t n_ops);
 bool launch_group_seq(const GroupTable& table, int32_t n_ops, int64_t n_members, int32_t step_begin, int32_t step_end, int32_t cache_slots,
                       hipStream_t s, hipError_t* status);
 
+// bytes of LDS a two-layer launch stages for `len` steps: [n_scen][max(n_comp, 1)][len] doubles.  The one place the size is formed:
+// the launchers use it, and the host decides lds_forcing with it (two_layer_fits_lds) wherever it cuts a run
+inline size_t two_layer_lds_bytes(int32_t n_scen, int32_t n_comp, int32_t len)
+{
+    return (size_t)n_scen * (size_t)(n_comp > 0 ? n_comp : 1) * (size_t)len * sizeof(double);
+}
+inline bool two_layer_fits_lds(int32_t n_scen, int32_t n_comp, int32_t len)
+{
+    return two_layer_lds_bytes(n_scen, n_comp, len) <= (size_t)kMaxLds - 1024;
+}
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);
 hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s);

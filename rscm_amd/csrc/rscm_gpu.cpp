@@ -227,6 +227,8 @@ static double ocean_fit_modes(const std::vector<double>& tab, int model, double 
 
 constexpr double kOceanFitTolerance = 5e-10;  // largest deviation of the fitted far response accepted for RSCM_MODE_FAST
 
+static_assert(rscm::kMaxForcingComponents == RSCM_TL_MAX_COMPONENTS && rscm::kTwoLayerCoeff0 == RSCM_TL_P_COEFF0 && RSCM_TL_P_COEFF0 == RSCM_TL_NPARAMS,
+              "the mix handle's constants in rscm_device.hpp and rscm_gpu.h must agree");
 static_assert(rscm::kKindOzoneForcing == RSCM_KIND_OZONE_FORCING && rscm::kKindAerosolDirect == RSCM_KIND_AEROSOL_DIRECT &&
                   rscm::kKindAerosolIndirect == RSCM_KIND_AEROSOL_INDIRECT && rscm::kKindCh4Chemistry == RSCM_KIND_CH4_CHEMISTRY &&
                   rscm::kKindN2oChemistry == RSCM_KIND_N2O_CHEMISTRY && rscm::kKindCo2Budget == RSCM_KIND_CO2_BUDGET &&
@@ -587,9 +589,36 @@ int rscm_ens_create_ex(int32_t kind, int64_t n_members, int32_t n_times, const d
     return rscm_ens_create_windowed(kind, n_members, n_times, time_bounds, device_id, flags, 16, 0, -1, nullptr, out);
 }
 
+// n_components > 0: a two-layer mix handle (rscm_ens_create_mix, which has checked kind, flags and the count)
+static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const double* time_bounds, int32_t device_id, uint32_t flags,
+                         int32_t window_rows, int32_t out_stride, int32_t n_out_vars, const int32_t* out_vars, int32_t n_components,
+                         rscm_ens** out);
+
 int rscm_ens_create_windowed(int32_t kind, int64_t n_members, int32_t n_times, const double* time_bounds,
                              int32_t device_id, uint32_t flags, int32_t window_rows, int32_t out_stride,
                              int32_t n_out_vars, const int32_t* out_vars, rscm_ens** out)
+{
+    return create_handle(kind, n_members, n_times, time_bounds, device_id, flags, window_rows, out_stride, n_out_vars, out_vars, 0, out);
+}
+
+int rscm_ens_create_mix(int32_t kind, int64_t n_members, int32_t n_times, const double* time_bounds, int32_t device_id, uint32_t flags,
+                        int32_t n_components, rscm_ens** out)
+{
+    GUARD_BEGIN
+    if (out) *out = nullptr;
+    if (kind != RSCM_KIND_TWO_LAYER)
+        return fail(RSCM_ERR_INVALID, "forcing components are available for the two-layer kind only (RSCM_KIND_TWO_LAYER), got kind %d", kind);
+    if (flags & ~(uint32_t)RSCM_FLAG_NO_SERIES)
+        return fail(RSCM_ERR_INVALID, "a mix handle takes flags 0 or RSCM_FLAG_NO_SERIES (no windowed storage), got 0x%x", flags);
+    if (n_components < 1 || n_components > RSCM_TL_MAX_COMPONENTS)
+        return fail(RSCM_ERR_INVALID, "n_components must be in [1, %d], got %d", RSCM_TL_MAX_COMPONENTS, n_components);
+    return create_handle(kind, n_members, n_times, time_bounds, device_id, flags, 16, 0, -1, nullptr, n_components, out);
+    GUARD_END
+}
+
+static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const double* time_bounds, int32_t device_id, uint32_t flags,
+                         int32_t window_rows, int32_t out_stride, int32_t n_out_vars, const int32_t* out_vars, int32_t n_components,
+                         rscm_ens** out)
 {
     GUARD_BEGIN
     if (flags & ~(uint32_t)(RSCM_FLAG_NO_SERIES | RSCM_FLAG_WINDOWED)) return fail(RSCM_ERR_INVALID, "unknown flags 0x%x", flags);
@@ -636,6 +665,11 @@ int rscm_ens_create_windowed(int32_t kind, int64_t n_members, int32_t n_times, c
     h->P = kP[kind];
     h->V = kV[kind];
     h->n_inputs = kInputs[kind];
+    if (n_components > 0) {   // the coefficients are parameter rows 6 .. 6 + K - 1, the components the K rows of the input block
+        h->n_comp = n_components;
+        h->P = RSCM_TL_P_COEFF0 + n_components;
+        h->n_inputs = n_components;
+    }
     h->bounds.assign(time_bounds, time_bounds + n_times + 1);
     h->initial_set.assign(h->V, 0);
     h->out_slot.assign(h->V, -1);
@@ -795,6 +829,7 @@ int rscm_ens_destroy(rscm_ens* h)
 int rscm_ens_n_params(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->P; return RSCM_OK; }
 int rscm_ens_n_vars(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->V; return RSCM_OK; }
 int rscm_ens_n_inputs(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->n_inputs; return RSCM_OK; }
+int rscm_ens_n_forcing_components(const rscm_ens* h, int32_t* out) { NEED(h); if (!out) return fail(RSCM_ERR_INVALID, "out is NULL"); *out = h->n_comp; return RSCM_OK; }
 int rscm_ens_n_members(const rscm_ens* h, int64_t* out) { NEED(h); *out = h->N; return RSCM_OK; }
 int rscm_ens_n_times(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->T; return RSCM_OK; }
 int rscm_ens_time_index(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->time_index; return RSCM_OK; }
@@ -996,6 +1031,9 @@ int rscm_ens_link_input(rscm_ens* h, int32_t input_row, rscm_ens* src, int32_t s
     if (src == h) return fail(RSCM_ERR_INVALID, "an ensemble cannot link to itself (its own states are read in the kernel)");
     if (h->kind == RSCM_KIND_COUPLED || h->kind == RSCM_KIND_HALOCARBON)
         return fail(RSCM_ERR_INVALID, "the inputs of this kind cannot be linked (they are exogenous emissions)");
+    if (h->n_comp > 0)
+        return fail(RSCM_ERR_INVALID, "the forcing components of a mix handle (rscm_ens_create_mix) cannot be linked: they are shared "
+                                      "scenario rows scaled per member");
     if (input_row < 0 || input_row >= h->n_inputs || input_row >= rscm::kMaxLinks)
         return fail(RSCM_ERR_INVALID, "input row %d out of range [0, %d)", input_row, h->n_inputs);
     if (src_var < 1 || src_var >= src->V) return fail(RSCM_ERR_INVALID, "variable %d of the source has no stored series", src_var);
@@ -1245,6 +1283,8 @@ int rscm_ens_gather_members(rscm_ens* dst, int64_t dst_offset, rscm_ens* src, co
                     (long long)dst_offset, (long long)count, (long long)dst->N);
     if (count > 0 && !anc) return fail(RSCM_ERR_INVALID, "ancestors are NULL");
     if (dst->kind != src->kind) return fail(RSCM_ERR_INVALID, "kinds differ: destination %d, source %d", dst->kind, src->kind);
+    if (dst->n_comp != src->n_comp)
+        return fail(RSCM_ERR_INVALID, "the forcing component counts differ: destination %d, source %d", dst->n_comp, src->n_comp);
     if (dst->device != src->device) return fail(RSCM_ERR_INVALID, "the handles live on devices %d and %d", dst->device, src->device);
     if (dst->T != src->T || memcmp(dst->bounds.data(), src->bounds.data(), src->bounds.size() * sizeof(double)) != 0)
         return fail(RSCM_ERR_INVALID, "the time axes differ");
@@ -1629,7 +1669,6 @@ static int run_member_split(rscm_ens* h, const MemberSplit& m, int32_t step_begi
 // members, axis, shared forcing and scenarios, sub-step table, guard hooks, series, status.
 rscm::TwoLayerArgs two_layer_args(const rscm_ens* h, int32_t step_begin, int32_t step_end)
 {
-    const size_t lds_bytes = (size_t)h->n_scen * (size_t)(step_end - step_begin) * sizeof(double);
     rscm::TwoLayerArgs a{};
     a.n_members = h->N;
     a.row_stride = h->N;
@@ -1638,7 +1677,8 @@ rscm::TwoLayerArgs two_layer_args(const rscm_ens* h, int32_t step_begin, int32_t
     a.step_end = step_end;
     a.n_scen = h->n_scen;
     a.src_off = h->source == RSCM_SRC_UPSTREAM ? 1 : 0;
-    a.lds_forcing = lds_bytes <= (size_t)rscm::kMaxLds - 1024 ? 1 : 0;
+    a.n_comp = h->n_comp;
+    a.lds_forcing = rscm::two_layer_fits_lds(h->n_scen, h->n_comp, step_end - step_begin) ? 1 : 0;
     a.params = h->d_params;
     a.uniform_rows = h->uniform_rows;
     a.forcing = h->d_forcing;
@@ -1670,6 +1710,8 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
             a.n_scen = 1;
             a.scen = nullptr;
         }
+        if (h->n_comp > 0 && (linked || op_out))   // (rscm_ens_link_input and rscm_ens_run_lockstep refuse the handle before this)
+            return fail(RSCM_ERR_INVALID, "a mix handle runs on its own: no linked input, no lock-step launch");
         if (op_out) {  // the arguments go into the fused launch's table instead (csrc/group.hip)
             a.lds_forcing = 0;
             op_out->kind = h->kind;
@@ -1685,8 +1727,8 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
                     c.n_members = cnt;
                     c.step_begin = b;
                     c.step_end = e;
-                    c.lds_forcing = (size_t)h->n_scen * (size_t)(e - b) * sizeof(double) <= (size_t)rscm::kMaxLds - 1024 ? 1 : 0;
-                    c.params = a.params + m0;
+                    c.lds_forcing = rscm::two_layer_fits_lds(h->n_scen, h->n_comp, e - b) ? 1 : 0;
+                    c.params = a.params + m0;   // every row moves with the block, a mix handle's coefficient rows included (stride N)
                     if (a.scen) c.scen = a.scen + m0;
                     c.ts = a.ts + m0;
                     c.td = a.td + m0;

@@ -340,6 +340,9 @@ int rscm_sampler_create_graph(rscm_ens* const* handles, int32_t n_handles, int32
     for (int32_t k = 0; k < n_handles; ++k) {
         rscm_ens* h = handles[k];
         NEED(h);
+        if (h->n_comp > 0)
+            return fail(RSCM_ERR_INVALID, "handle %d is a mix handle (rscm_ens_create_mix): it cannot be part of a graph sampler; "
+                                          "rscm_sampler_create takes it as its one evaluator", k);
         if (h->N != n_walkers / 2 / n_ranks)
             return fail(RSCM_ERR_INVALID, "handle %d: every ensemble of the graph must have n_walkers / 2 / n_ranks = %d members, it has %lld", k,
                         n_walkers / 2 / n_ranks, (long long)h->N);

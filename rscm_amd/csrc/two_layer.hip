@@ -44,13 +44,14 @@ namespace {
 // counting launches that took it
 __device__ unsigned long long g_guard_counts[tl::kGuardKinds];
 
-template <int MODE, bool LDS, bool STORE>
+// MIX: a mix handle's launch (a.n_comp >= 1): the staged table is [n_scen][n_comp][len], n_scen * n_comp rows laid out like scenarios
+template <int MODE, bool LDS, bool STORE, bool MIX = false>
 __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 {
     extern __shared__ double lds_forcing[];
     if constexpr (LDS) {
         const int32_t len = a.step_end - a.step_begin;
-        const int32_t total = a.n_scen * len;
+        const int32_t total = (MIX ? a.n_scen * a.n_comp : a.n_scen) * len;
         for (int32_t idx = threadIdx.x; idx < total; idx += kBlock) {
             const int32_t s = idx / len, k = idx - s * len;
             lds_forcing[idx] = a.forcing[(size_t)s * a.n_times + a.step_begin + a.src_off + k];
@@ -59,7 +60,7 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
-    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE>(a, lds_forcing, i, a.step_begin, a.step_end);
+    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE, NoCache, false, MIX>(a, lds_forcing, i, a.step_begin, a.step_end);
     if constexpr (MODE == 0) {
         if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
     }
@@ -67,13 +68,13 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 
 // The fused likelihood with reference periods: an instantiation of its own, so that launches without a period run the kernels above
 // unchanged.
-template <int MODE, bool LDS>
+template <int MODE, bool LDS, bool MIX = false>
 __global__ __launch_bounds__(kBlock) void two_layer_ref_kernel(TwoLayerArgs a, TwoLayerRefArgs r)
 {
     extern __shared__ double lds_forcing[];
     if constexpr (LDS) {
         const int32_t len = a.step_end - a.step_begin;
-        const int32_t total = a.n_scen * len;
+        const int32_t total = (MIX ? a.n_scen * a.n_comp : a.n_scen) * len;
         for (int32_t idx = threadIdx.x; idx < total; idx += kBlock) {
             const int32_t s = idx / len, k = idx - s * len;
             lds_forcing[idx] = a.forcing[(size_t)s * a.n_times + a.step_begin + a.src_off + k];
@@ -82,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void two_layer_ref_kernel(TwoLayerArgs a, T
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
-    const int32_t guard = tl::two_layer_body<MODE, LDS, false, NoCache, true>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(), &r);
+    const int32_t guard = tl::two_layer_body<MODE, LDS, false, NoCache, true, MIX>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(), &r);
     if constexpr (MODE == 0) {
         if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
     }
@@ -103,11 +104,15 @@ static hipError_t launch_impl(const TwoLayerArgs& a, int mode, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
     if (STORE && a.step_end <= a.step_begin) return hipSuccess;
-    const size_t lds = a.lds_forcing ? (size_t)a.n_scen * (a.step_end - a.step_begin) * sizeof(double) : 0;
+    if (a.n_comp < 0 || a.n_comp > kMaxForcingComponents || (a.n_comp > 0 && a.link)) return hipErrorInvalidValue;
+    const size_t lds = a.lds_forcing ? two_layer_lds_bytes(a.n_scen, a.n_comp, a.step_end - a.step_begin) : 0;
     const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
     void (*kern)(TwoLayerArgs) =
-        mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, STORE> : two_layer_kernel<0, false, STORE>)
-                  : (a.lds_forcing ? two_layer_kernel<1, true, STORE> : two_layer_kernel<1, false, STORE>);
+        a.n_comp > 0
+            ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, STORE, true> : two_layer_kernel<0, false, STORE, true>)
+                         : (a.lds_forcing ? two_layer_kernel<1, true, STORE, true> : two_layer_kernel<1, false, STORE, true>))
+            : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, STORE> : two_layer_kernel<0, false, STORE>)
+                         : (a.lds_forcing ? two_layer_kernel<1, true, STORE> : two_layer_kernel<1, false, STORE>));
     if (lds > (size_t)kMaxStaticLds) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -130,11 +135,14 @@ hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t 
 hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
-    const size_t lds = a.lds_forcing ? (size_t)a.n_scen * (a.step_end - a.step_begin) * sizeof(double) : 0;
+    if (a.n_comp < 0 || a.n_comp > kMaxForcingComponents || (a.n_comp > 0 && a.link)) return hipErrorInvalidValue;
+    const size_t lds = a.lds_forcing ? two_layer_lds_bytes(a.n_scen, a.n_comp, a.step_end - a.step_begin) : 0;
     const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
     void (*kern)(TwoLayerArgs, TwoLayerRefArgs) =
-        mode == 0 ? (a.lds_forcing ? two_layer_ref_kernel<0, true> : two_layer_ref_kernel<0, false>)
-                  : (a.lds_forcing ? two_layer_ref_kernel<1, true> : two_layer_ref_kernel<1, false>);
+        a.n_comp > 0 ? (mode == 0 ? (a.lds_forcing ? two_layer_ref_kernel<0, true, true> : two_layer_ref_kernel<0, false, true>)
+                                  : (a.lds_forcing ? two_layer_ref_kernel<1, true, true> : two_layer_ref_kernel<1, false, true>))
+                     : (mode == 0 ? (a.lds_forcing ? two_layer_ref_kernel<0, true> : two_layer_ref_kernel<0, false>)
+                                  : (a.lds_forcing ? two_layer_ref_kernel<1, true> : two_layer_ref_kernel<1, false>));
     if (lds > (size_t)kMaxStaticLds) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

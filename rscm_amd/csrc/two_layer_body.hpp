@@ -289,7 +289,13 @@ __device__ __forceinline__ void lik_consume_ref(const TwoLayerArgs& a, const Two
 enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuardKinds = 3 };
 
 // REF (with STORE == false): the fused likelihood with the reference periods of *ref (lik_consume_ref).
-template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false>
+// MIX (a mix handle, a.n_comp = K in 1..kMaxForcingComponents; stand-alone launches only, never linked): the forcing of member i is
+// formed per year from the K rows of its scenario, [S][K][T] (LDS: [S][K][len]), and the coefficients in parameter rows 6..6+K-1:
+//     F = S_0[n] * c_0;   F = F + S_k[n] * c_k   for k = 1 .. K-1, in that order,
+// every product and sum rounded on its own in BOTH arithmetic modes (the file is compiled with -ffp-contract=off and nothing here is
+// written as an FMA).  NaN and Inf propagate, no row is skipped and none is padded with 0 * S (that would change -0.0, NaN and Inf):
+// the loop below is unrolled to eight with a wave-uniform k < K around each term, so the coefficients stay in registers.
+template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
                                                int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
 {
@@ -309,8 +315,30 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
     const double* fglob = a.link ? a.link + (size_t)a.src_off * N + i : a.forcing + (size_t)scen * a.n_times + a.src_off;
     const size_t fstride = a.link ? (size_t)N : (size_t)1;
     const int32_t fl0 = scen * len - step_begin;  // lds_forcing[fl0 + n], n >= step_begin
+    // MIX: the member's coefficients, read once, and where row 0 of its scenario's block starts (row k follows mix_row elements later)
+    using mix_index = std::conditional_t<LDS, int32_t, int64_t>;   // (the staged table is indexed in 32 bits like lds_forcing[fl0 + n])
+    [[maybe_unused]] double coeff[kMaxForcingComponents];
+    [[maybe_unused]] const int32_t n_comp = MIX ? a.n_comp : 0;   // wave-uniform (kernarg)
+    [[maybe_unused]] const mix_index mix_row = LDS ? len : a.n_times;
+    [[maybe_unused]] const double* mix_base = LDS ? lds_forcing : a.forcing;
+    [[maybe_unused]] mix_index mix0 = 0;   // mix_base[mix0 + n]: component 0 at model index n (n >= step_begin for the staged table)
+    if constexpr (MIX) {
+        static_assert(!Cache::kOn, "a mix handle is never part of a fused launch");
+#pragma unroll
+        for (int k = 0; k < kMaxForcingComponents; ++k)
+            coeff[k] = k < n_comp ? cache.param(a.params, a.uniform_rows, kTwoLayerCoeff0 + k, N, i) : 0.0;
+        if constexpr (LDS) mix0 = (mix_index)scen * n_comp * len - step_begin;
+        else mix0 = (mix_index)scen * n_comp * a.n_times + a.src_off;
+    }
     auto forcing_at = [&](int32_t n) -> double {
-        if constexpr (LDS) return lds_forcing[fl0 + n];
+        if constexpr (MIX) {
+            const mix_index at = mix0 + n;
+            double f = mix_base[at] * coeff[0];
+#pragma unroll
+            for (int k = 1; k < kMaxForcingComponents; ++k)
+                if (k < n_comp) f = f + mix_base[at + (mix_index)k * mix_row] * coeff[k];
+            return f;
+        } else if constexpr (LDS) return lds_forcing[fl0 + n];
         else return fglob[(size_t)n * fstride];
     };
     // the year a fused launch is at: the linked forcing from the producer's LDS slot if it is kept there

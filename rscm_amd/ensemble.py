@@ -44,10 +44,15 @@ class DeviceVector:
 class Ensemble:
     def __init__(self, kind: int, n_members: int, time_bounds: Sequence[float], device: int = 0,
                  store_series: bool = True, window_rows: Optional[int] = None, output_stride: int = 0,
-                 output_vars: Optional[Sequence] = None):
+                 output_vars: Optional[Sequence] = None, forcing_components=None):
         """``window_rows``: keep only a sliding window of that many rows of every series
         (``RSCM_FLAG_WINDOWED``) plus, with ``output_stride`` > 0, every ``output_stride``-th row of
-        ``output_vars`` (names or ids; None: all) -- for long axes stepped in lock-step."""
+        ``output_vars`` (names or ids; None: all) -- for long axes stepped in lock-step.
+
+        ``forcing_components`` (two-layer kind; an int K or a sequence of K names, 1 <= K <= 8): a *mix*
+        ensemble (``rscm_ens_create_mix``).  ``set_forcing`` then takes K component series per scenario,
+        ``[S][K][T]``, and member i is forced by ``((S_0 c_0 + S_1 c_1) + ...) + S_K-1 c_K-1`` with its own
+        coefficients c_k = parameter rows 6 .. 6+K-1 (``coefficient_row``): ``n_params`` is 6 + K."""
         self._lib = L.load()
         b = L.f64(time_bounds)
         if b.ndim != 1 or len(b) < 3:
@@ -58,6 +63,19 @@ class Ensemble:
         self.bounds = b
         self.device = device
         var_ids, self.n_params, input_rows = L.KIND_TABLE[kind]
+        self.n_forcing_components = 0
+        if forcing_components is not None:
+            if kind != L.KIND_TWO_LAYER:
+                raise ValueError("forcing_components are available for the two-layer kind only")
+            if window_rows is not None:
+                raise ValueError("a mix ensemble has no windowed storage")
+            names = (tuple(f"component_{k}" for k in range(forcing_components)) if isinstance(forcing_components, (int, np.integer))
+                     else tuple(str(x) for x in forcing_components))
+            if not 1 <= len(names) <= L.TL_MAX_COMPONENTS or len(set(names)) != len(names):
+                raise ValueError(f"forcing_components: 1 to {L.TL_MAX_COMPONENTS} distinct components, got {len(names)} name(s)")
+            self.n_forcing_components = len(names)
+            self.n_params = L.TL_P_COEFF0 + len(names)   # the coefficients are parameter rows 6 .. 6 + K - 1
+            input_rows = names
         self.var_ids: Dict[str, int] = dict(var_ids)
         self.input_rows = input_rows  # names of the rows of the input block, or None
         self.n_inputs = len(input_rows) if input_rows else 1
@@ -65,7 +83,10 @@ class Ensemble:
         self.store_series = bool(store_series)
         self.window_rows = None if window_rows is None or window_rows >= self.n_times else int(window_rows)
         self.output_stride = int(output_stride) if self.window_rows else 0
-        if self.window_rows:
+        if self.n_forcing_components:
+            L.check(self._lib.rscm_ens_create_mix(kind, self.n_members, self.n_times, L.dptr(b), device,
+                                                  0 if store_series else L.FLAG_NO_SERIES, self.n_forcing_components, C.byref(h)))
+        elif self.window_rows:
             ov = None
             if output_vars is not None:
                 ov = np.ascontiguousarray([self._var(v) for v in output_vars], dtype=np.int32)
@@ -81,11 +102,16 @@ class Ensemble:
         got = [C.c_int32() for _ in range(3)]
         for fn, x in zip((self._lib.rscm_ens_n_params, self._lib.rscm_ens_n_vars, self._lib.rscm_ens_n_inputs), got):
             L.check(fn(self._h, C.byref(x)))
-        want = (self.n_params, max(self.var_ids.values()) + 1, self.n_inputs)
+        want = (self.n_params, max(self.var_ids.values()) + 1, self.n_inputs)   # (a mix ensemble: 6 + K rows, K inputs)
         if tuple(x.value for x in got) != want:
             self.close()
             raise RuntimeError(f"kind {kind}: library reports (params, vars, inputs) = {tuple(x.value for x in got)}, "
                                f"package tables say {want}")
+        k = C.c_int32()
+        L.check(self._lib.rscm_ens_n_forcing_components(self._h, C.byref(k)))
+        if k.value != self.n_forcing_components:
+            self.close()
+            raise RuntimeError(f"library reports {k.value} forcing components, asked for {self.n_forcing_components}")
 
     # -- lifecycle --------------------------------------------------------------------------
     def close(self) -> None:
@@ -129,6 +155,15 @@ class Ensemble:
             raise ValueError(f"Expected {self.n_params} parameters per member "
                              f"([{self.n_members}][{self.n_params}]), got {p.shape}")
         L.check(self._lib.rscm_ens_set_params_aos(self._h, L.dptr(p)))
+
+    def coefficient_row(self, component) -> int:
+        """The parameter row that holds the coefficient of a forcing component (name or index) of a mix ensemble."""
+        if not self.n_forcing_components:
+            raise ValueError("not a mix ensemble (forcing_components was not given)")
+        k = self.input_rows.index(component) if isinstance(component, str) else int(component)
+        if not 0 <= k < self.n_forcing_components:
+            raise ValueError(f"component {component!r} out of range [0, {self.n_forcing_components})")
+        return L.TL_P_COEFF0 + k
 
     def set_forcing(self, series, scenario_of_member=None, source: int = L.SRC_EXOGENOUS,
                     var=0) -> None:

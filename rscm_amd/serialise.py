@@ -99,9 +99,17 @@ def component_registry() -> Dict[str, type]:
 def describe(builder, model) -> Dict[str, object]:
     """The builder's description plus the model's checkpoint as a TOML-ready dict."""
     from .core import GraphModel
+    doc = describe_builder(builder)
+    doc["model"].update({"graph": isinstance(model, GraphModel), "n_members": int(model.n_members), "time_index": int(model.time_index),
+                         "execution_order": getattr(model, "_execution_order", "reference")})
+    doc["state"] = _plain(model.checkpoint())
+    return doc
+
+
+def describe_builder(builder) -> Dict[str, object]:
+    """The description part of ``describe``: what ``builder_from`` needs to set a ModelBuilder up again (no device involved)."""
     doc: Dict[str, object] = {
-        "model": {"format": "rscm_amd-model-1", "graph": isinstance(model, GraphModel), "n_members": int(model.n_members),
-                  "time_index": int(model.time_index), "execution_order": getattr(model, "_execution_order", "reference"),
+        "model": {"format": "rscm_amd-model-1", "graph": False, "n_members": 1, "time_index": 0, "execution_order": "reference",
                   "device": int(builder._device)},
         "time_axis": {"bounds": builder._axis.bounds()},
         "components": [{"type": c.type_name, **({"step_size": float(c.step_size)} if hasattr(c, "step_size") else {}),
@@ -121,7 +129,13 @@ def describe(builder, model) -> Dict[str, object]:
                                         for n, (u, op, c, w) in s.aggregates.items()]}
     if builder._grid_weights:
         doc["grid_weights"] = {k.name: list(v) for k, v in builder._grid_weights.items()}
-    doc["state"] = _plain(model.checkpoint())
+    if getattr(builder, "_mix", None) is not None:   # ModelBuilder.with_forcing_components
+        variable, components, scales = builder._mix
+        doc["forcing_components"] = {"variable": variable,
+                                     "components": [{"name": n, "scale": float(scales[n]), "units": ts.units,
+                                                     "interpolation": ts.interpolation_strategy.name,
+                                                     "bounds": ts.time_axis.bounds(), "values": ts.values()}
+                                                    for n, ts in components.items()]}
     return doc
 
 
@@ -139,6 +153,14 @@ def _plain(x):
 
 def rebuild(doc: Dict[str, object]):
     """ModelBuilder + restored model from a description written by ``describe``."""
+    b = builder_from(doc)
+    model = b.build(n_members=int(doc["model"]["n_members"]), execution_order=doc["model"].get("execution_order", "reference"))
+    model.restore(_arrays(doc["state"]))
+    return model
+
+
+def builder_from(doc: Dict[str, object]):
+    """The ModelBuilder a description written by ``describe`` / ``describe_builder`` sets up (nothing is built)."""
     from . import core
     if doc.get("model", {}).get("format") != "rscm_amd-model-1":
         raise ValueError("not a model written by rscm_amd (missing or unknown [model] format)")
@@ -166,9 +188,13 @@ def rebuild(doc: Dict[str, object]):
         ts = core.Timeseries(np.array(e["values"], dtype=np.float64), core.TimeAxis.from_bounds(np.array(e["bounds"], dtype=np.float64)),
                              e.get("units", ""), core.InterpolationStrategy[e["interpolation"]])
         b.with_exogenous_variable(e["name"], ts)
-    model = b.build(n_members=int(doc["model"]["n_members"]), execution_order=doc["model"].get("execution_order", "reference"))
-    model.restore(_arrays(doc["state"]))
-    return model
+    if "forcing_components" in doc:
+        fc = doc["forcing_components"]
+        series = {c["name"]: core.Timeseries(np.array(c["values"], dtype=np.float64),
+                                             core.TimeAxis.from_bounds(np.array(c["bounds"], dtype=np.float64)), c.get("units", ""),
+                                             core.InterpolationStrategy[c["interpolation"]]) for c in fc["components"]}
+        b.with_forcing_components(fc["variable"], series, {c["name"]: float(c["scale"]) for c in fc["components"]})
+    return b
 
 
 _ARRAY_KEYS = ("bounds", "params", "internal")
