@@ -1231,7 +1231,7 @@ def load_checkpoint(path) -> Dict[str, object]:
     return out
 
 
-# components whose step is a kernel of their own (csrc/lockstep.cpp, fusable()); the others share fused launches
+# components whose step is a kernel of their own (csrc/kinds.hpp, `fusable`); the others share fused launches
 OWN_KERNEL_TYPES = ("ClimateUDEB", "OceanCarbon", "HalocarbonChemistry")
 
 # type name -> ensemble kind, for graphs assembled from linked ensembles

@@ -1,5 +1,6 @@
 // Host-side internals shared by the translation units of librscm_gpu.so (rscm_gpu.cpp: handles, validation,
-// marshalling; lockstep.cpp: the lock-step scheduler of component graphs; loglik_host.cpp: the likelihoods).  Not part of the boundary
+// marshalling; launch_host.cpp: one launch range of one handle; lockstep.cpp: the lock-step scheduler of component graphs;
+// loglik_host.cpp: the likelihoods).  Not part of the boundary
 // (include/rscm_gpu.h) and not visible outside the library (-fvisibility=hidden).
 #pragma once
 
@@ -35,6 +36,7 @@ inline hipError_t dev_malloc(T** p, size_t n)
 #include <string>
 #include <vector>
 
+#include "kinds.hpp"
 #include "rscm_device.hpp"
 
 // thread-local error text behind rscm_gpu_last_error(); returns `code`
@@ -100,7 +102,7 @@ struct rscm_ens {
     uint64_t uniform_rows = 0;   // bit j: parameter row j (< 64) holds one value for every member (the kernels then read element 0: param_at)
     // member constants of the kinds that have them (GhgForcing, TerrestrialCarbon; rscm_device.hpp, launch_*_derive): [kDerivedRows][N],
     // re-formed by ensure_derived() at the next run after anything wrote the parameter block
-    // whole-axis runs as two member blocks on two streams in chunks of model steps (rscm_gpu.cpp, plan_member_split): the second stream
+    // whole-axis runs as two member blocks on two streams in chunks of model steps (launch_host.cpp, plan_member_split): the second stream
     // and the fork / join events, created with the first such run
     int32_t last_blocks = 1, last_chunks = 1;   // how the last run was cut (rscm_ens_last_run_plan)
     hipStream_t split_stream = nullptr;
@@ -239,19 +241,14 @@ struct rscm_ens {
             return d_out + ((size_t)out_slot[var] * out_rows + (size_t)(t / out_stride)) * N;
         return nullptr;
     }
-    bool is_state(int32_t var) const
-    {
-        if (kind == RSCM_KIND_TWO_LAYER) return var == RSCM_TL_VAR_TS || var == RSCM_TL_VAR_TD;
-        if (kind == RSCM_KIND_UDEB) return var >= RSCM_UD_VAR_ST_NH_OCEAN && var <= RSCM_UD_VAR_ST_SH_LAND;
-        if (kind == RSCM_KIND_CH4_CHEMISTRY || kind == RSCM_KIND_N2O_CHEMISTRY) return var == RSCM_CHEM_VAR_CONC;
-        if (kind == RSCM_KIND_CO2_BUDGET) return var == 1;
-        if (kind == RSCM_KIND_TERRESTRIAL_CARBON) return var >= 1 && var <= 4;
-        if (kind == RSCM_KIND_OCEAN_CARBON) return var == 1 || var == 2;
-        if (kind == RSCM_KIND_HALOCARBON) return var >= 1 && var <= RSCM_HC_NSPECIES;
-        if (kind == RSCM_KIND_CARBON_CYCLE) return var >= 1 && var <= 3;
-        if (kind >= RSCM_KIND_GHG_FORCING) return false;  // stateless components
-        return var >= RSCM_CP_VAR_TS && var <= RSCM_CP_VAR_CUM_EMIS;
-    }
+    const rscm::KindInfo& info() const { return rscm::kKinds[kind]; }
+    bool is_state(int32_t var) const { return var >= info().state_first && var <= info().state_last; }
+    // a checkpoint, a gathered member or a time index set from outside carries its own state rows
+    void mark_states_set() { std::fill(initial_set.begin() + info().state_first, initial_set.begin() + info().state_last + 1, (uint8_t)1); }
+    // whether a linked input is read at index n + 1 of its source
+    bool reads_end(const Link& l) const { return info().reads_end || l.off == 1; }
+    // OceanCarbon: the sums parked for a split tile and the running mode sums no longer belong to where the handle stands
+    void ocean_forget_partial_sums() { ocean_tile_base = -1; ocean_modes_at = -1; }
 };
 
 // Parameter rows from which the HOST derives state when rscm_ens_set_params / rscm_ens_sample_lhs configure an ensemble
@@ -297,7 +294,7 @@ inline int set_device(const rscm_ens* h)
     return RSCM_OK;
 }
 
-// One launch range of one handle, in pieces (rscm_gpu.cpp); rscm_ens_run_lockstep (lockstep.cpp) fuses the
+// One launch range of one handle, in pieces (launch_host.cpp); rscm_ens_run_lockstep (lockstep.cpp) fuses the
 // launches of several handles out of the same pieces.
 extern "C" {
 int step_check(rscm_ens* h, int32_t step_begin, int32_t step_end, bool derive = true);
@@ -308,13 +305,16 @@ int64_t take_derive_launches();           // test hook: member-constant kernels 
 int ensure_derived(rscm_ens* h);   // (every run starts with current member constants: run_range after its first event, rscm_ens_run_lockstep once per call)
 int step_window_pre(rscm_ens* h, int32_t step_begin, int32_t step_end);
 int step_links(rscm_ens* h, int32_t step_begin, int32_t step_end, rscm::InputLinks& links, int32_t& linked_out);
-// op_out: nothing is launched, the arguments go into a fused launch's table (kind -1: this handle cannot be fused)
+// op_out (zeroed by the caller): nothing is launched, the arguments go into a fused launch's table with a step range of [0, 0) -- the
+// range is an argument of the fused launch.  RSCM_ERR_STATE for a handle that cannot be fused (can_fuse).
 int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::InputLinks& links, int32_t linked, rscm::GroupOp* op_out);
 int step_finish(rscm_ens* h, int32_t step_begin, int32_t step_end);
 int run_range(rscm_ens* h, int32_t step_begin, int32_t step_end, bool timed);
 // what every two-layer launch takes from the handle: step_launch and the fused run + likelihood (loglik_host.cpp)
 rscm::TwoLayerArgs two_layer_args(const rscm_ens* h, int32_t step_begin, int32_t step_end);
 }
+// Whether the handle's one-step launch can join a fused launch (kinds.hpp; GhgForcing's table path uses host-built rows)
+inline bool can_fuse(const rscm_ens* h) { return h->info().fusable && (h->kind != RSCM_KIND_GHG_FORCING || h->n_linked > 0); }
 // frees the staged select in flight on h, if any (select_host.cpp)
 void select_release(rscm_ens* h);
 // the rows t_begin, t_begin + t_stride, ... < t_end of var_id that this model instance has computed (t <= time_index), as device
@@ -326,6 +326,11 @@ int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_e
 int check_member_vector(const rscm_ens* h, const double* p, const char* what);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (rscm_gpu.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
+// the handle's own window and its RK4 sub-step tables (rscm_gpu.cpp)
+int window_reset(rscm_ens* h, bool clear);
+int window_slide(rscm_ens* h, int32_t new_win0);
+int window_store_row(rscm_ens* h, int32_t t);
+int refresh_schedule(rscm_ens* h);
 
 // An observation list and its reference periods as the boundary passes them.  owner: the handle of a list that each entry refers
 // to (the graph sampler), null: all refer to the first.

@@ -122,50 +122,14 @@ int rscm_gpu_lockstep_merged_launches(int64_t* out)
     return RSCM_OK;
 }
 
-// Kinds whose one-step launch the group kernel can absorb (csrc/group.hip): the light per-member
-// components.  ClimateUDEB, OceanCarbon, HalocarbonChemistry and the fused coupled chain keep their own
-// launches; GhgForcing joins only with linked concentrations (its table path uses host-built rows).
-static bool fusable(const rscm_ens* h)
-{
-    switch (h->kind) {
-        case RSCM_KIND_TWO_LAYER: case RSCM_KIND_OZONE_FORCING: case RSCM_KIND_AEROSOL_DIRECT: case RSCM_KIND_AEROSOL_INDIRECT:
-        case RSCM_KIND_CH4_CHEMISTRY: case RSCM_KIND_N2O_CHEMISTRY: case RSCM_KIND_CO2_BUDGET: case RSCM_KIND_TERRESTRIAL_CARBON:
-        case RSCM_KIND_FOURBOX_OHU: case RSCM_KIND_OSPP: case RSCM_KIND_CARBON_CYCLE: case RSCM_KIND_CO2_ERF: case RSCM_KIND_AGGREGATE:
-            return true;
-        case RSCM_KIND_GHG_FORCING: return h->n_linked > 0;
-        default: return false;
-    }
-}
-
-// the step range is an argument of the fused launch, not part of the table
-static void clear_step_fields(rscm::GroupOp& op)
-{
-    switch (op.kind) {
-        case RSCM_KIND_TWO_LAYER: op.u.tl.step_begin = op.u.tl.step_end = 0; break;
-        case RSCM_KIND_GHG_FORCING: op.u.ghg.step_begin = op.u.ghg.step_end = 0; break;
-        case RSCM_KIND_CH4_CHEMISTRY: case RSCM_KIND_N2O_CHEMISTRY: op.u.chem.step_begin = op.u.chem.step_end = 0; break;
-        case RSCM_KIND_CO2_BUDGET: case RSCM_KIND_TERRESTRIAL_CARBON: case RSCM_KIND_CARBON_CYCLE:
-            op.u.carbon.step_begin = op.u.carbon.step_end = 0; break;
-        default: op.u.pw.step_begin = op.u.pw.step_end = 0; break;
-    }
-}
-
 // LDS slots for a multi-step launch of a graph of light components (csrc/group.hip, CACHED): every op that
-// can keep values there gets one slot per series (the latest row: its own state for the next step, and what
-// its consumers read) and, while the budget lasts, one per parameter row if any of its rows varies over the
-// members.  A link is served from the producer's slot when the value it wants is the one the slot holds at
+// can keep values there (group_kind_is_small: every kind the light variant of the group kernel runs) gets one slot
+// per series (the latest row: its own state for the next step, and what its consumers read) and, while the budget
+// lasts, one per parameter row if any of its rows varies over the members.  A link is served from the producer's
+// slot when the value it wants is the one the slot holds at
 // that point of the step: a producer earlier in the order read at n+1 (this step's value), or a producer
 // later in the order read at n (what it left in the previous step -- not at a launch's first step).
 static constexpr int32_t kCacheSlotBudget = 20;  // x 2 KiB per workgroup: four workgroups (16 wavefronts) per CU
-static bool keeps_slots(int32_t kind)
-{
-    switch (kind) {
-        case RSCM_KIND_TWO_LAYER: case RSCM_KIND_CARBON_CYCLE: case RSCM_KIND_AEROSOL_INDIRECT: case RSCM_KIND_FOURBOX_OHU:
-        case RSCM_KIND_OSPP: case RSCM_KIND_CO2_ERF: case RSCM_KIND_AGGREGATE: case RSCM_KIND_CO2_BUDGET:
-            return true;  // every kind the light variant of the group kernel runs
-        default: return false;
-    }
-}
 static int32_t assign_cache_slots(LockstepPlan* plan, int32_t first, int32_t count, std::vector<rscm::OpCache>& out, bool param_slots)
 {
     out.assign((size_t)count, rscm::OpCache{});
@@ -177,7 +141,7 @@ static int32_t assign_cache_slots(LockstepPlan* plan, int32_t first, int32_t cou
         c.link_warm = 0;
         const rscm_ens* h = plan->handles[first + k];
         const int32_t n_series = h->V - 1;
-        if (keeps_slots(h->kind) && n_series > 0 && next + n_series <= kCacheSlotBudget) {
+        if (rscm::group_kind_is_small(h->kind) && n_series > 0 && next + n_series <= kCacheSlotBudget) {
             c.series_slot = next;
             next += n_series;
         }
@@ -186,14 +150,14 @@ static int32_t assign_cache_slots(LockstepPlan* plan, int32_t first, int32_t cou
         const rscm_ens* h = plan->handles[first + k];
         const uint64_t all_rows = h->P >= 64 ? ~0ull : ((1ull << h->P) - 1ull);
         const bool varies = (h->uniform_rows & all_rows) != all_rows;
-        if (param_slots && keeps_slots(h->kind) && h->kind != RSCM_KIND_AGGREGATE && varies && h->P <= 16 && next + h->P <= kCacheSlotBudget) {
+        if (param_slots && rscm::group_kind_is_small(h->kind) && h->kind != RSCM_KIND_AGGREGATE && varies && h->P <= 16 && next + h->P <= kCacheSlotBudget) {
             out[(size_t)k].param_slot = next;
             next += h->P;
         }
     }
     for (int32_t k = 0; k < count; ++k) {
         const rscm_ens* h = plan->handles[first + k];
-        if (!keeps_slots(h->kind)) continue;
+        if (!rscm::group_kind_is_small(h->kind)) continue;
         for (int32_t j = 0; j < rscm::kMaxLinks && j < h->n_inputs; ++j) {
             const auto& l = h->links[j];
             if (!l.src) continue;
@@ -201,7 +165,7 @@ static int32_t assign_cache_slots(LockstepPlan* plan, int32_t first, int32_t cou
             for (int32_t q = 0; q < count; ++q)
                 if (plan->handles[first + q] == l.src) at = q;
             if (at < 0 || out[(size_t)at].series_slot < 0 || l.var < 1 || l.var > l.src->V - 1) continue;
-            const bool reads_end = h->kind == RSCM_KIND_AGGREGATE || l.off == 1;
+            const bool reads_end = h->reads_end(l);
             if (at < k ? !reads_end : reads_end) continue;  // the slot holds the other row at that point
             out[(size_t)k].link_slot[j] = out[(size_t)at].series_slot + (l.var - 1);
             if (at >= k) out[(size_t)k].link_warm |= 1u << j;
@@ -219,19 +183,6 @@ struct SplitPlan {
     int32_t order[rscm::kGroupTableOps];
     int32_t n_first = 0, n_second = 0;
 };
-static int32_t op_cost(int32_t kind)
-{
-    // (one unit ~ a dependent round trip to memory plus a few dozen instructions; the chemistry's Prather passes, the forcing
-    // formulas' logarithms and the RK4 box models weigh by their instruction counts on top)
-    switch (kind) {
-        case RSCM_KIND_TWO_LAYER: return 12;
-        case RSCM_KIND_CH4_CHEMISTRY: return 6;
-        case RSCM_KIND_N2O_CHEMISTRY: return 5;
-        case RSCM_KIND_CARBON_CYCLE: case RSCM_KIND_GHG_FORCING: case RSCM_KIND_TERRESTRIAL_CARBON: return 4;
-        case RSCM_KIND_OZONE_FORCING: case RSCM_KIND_AEROSOL_DIRECT: return 2;
-        default: return 1;
-    }
-}
 // idx[k]: the handle of op k in the plan; off[k]: 0 = the launch's step n, 1 = step n + 1 (a merged launch).  Op k reads row
 // s_k + (1 if it reads at the end of its step, else l.off) of a producer q, which writes row s_q + 1: tied when the two are the same row.
 static bool plan_split(const LockstepPlan* plan, const int32_t* idx, const int32_t* off, int32_t count, SplitPlan* out)
@@ -242,12 +193,12 @@ static bool plan_split(const LockstepPlan* plan, const int32_t* idx, const int32
     int32_t cost[rscm::kGroupTableOps], serial = 0;
     for (int32_t k = 0; k < count; ++k) {
         const rscm_ens* h = plan->handles[idx[k]];
-        cost[k] = op_cost(h->kind);
+        cost[k] = h->info().op_cost;
         serial += cost[k];
         for (int32_t j = 0; j < rscm::kMaxLinks && j < h->n_inputs; ++j) {
             const auto& l = h->links[j];
             if (!l.src) continue;
-            const bool reads_end = h->kind == RSCM_KIND_AGGREGATE || l.off == 1;
+            const bool reads_end = h->reads_end(l);
             const int32_t reads_row = off[k] + (reads_end ? 1 : 0);
             for (int32_t q = 0; q < count; ++q)
                 if (plan->handles[idx[q]] == l.src && q != k && reads_row == off[q] + 1) tie[k][q] = tie[q][k] = true;
@@ -355,8 +306,6 @@ static int fused_segment(LockstepPlan* plan, int32_t first, int32_t count, int32
         rscm::GroupOp op;
         memset((void*)&op, 0, sizeof op);
         if (int rc = step_launch(h, at, at + 1, links, linked, &op)) return rc;
-        if (op.kind < 0) return fail(RSCM_ERR_STATE, "handle %d (kind %d) cannot be fused", idx[k], h->kind);
-        clear_step_fields(op);
         op.step_off = off[k];
         if (cache_slots > 0) {
             op.cache = slots[(size_t)k];
@@ -422,13 +371,13 @@ int rscm_ens_run_lockstep(rscm_ens* const* handles, int32_t n_handles, int32_t s
         if (handles[k]->time_index != step_begin)
             return fail(RSCM_ERR_STATE, "handle %d is at time index %d, not at step_begin %d", k, handles[k]->time_index, step_begin);
     }
-    // Consecutive fusable components become one launch per step (csrc/group.hip); the others, and
-    // fusable ones on their own, keep their kernels.
+    // Consecutive fusable components (can_fuse: the light per-member kinds of kinds.hpp) become one launch per step (csrc/group.hip);
+    // the others, and fusable ones on their own, keep their kernels.
     std::vector<std::pair<int32_t, int32_t>> segments;  // (first, count)
     for (int32_t k = 0; k < n_handles;) {
         int32_t c = 1;
-        if (t_ls.fuse && fusable(handles[k]))
-            while (k + c < n_handles && c < rscm::kMaxGroupOps && fusable(handles[k + c]) && handles[k + c]->N == handles[k]->N &&
+        if (t_ls.fuse && can_fuse(handles[k]))
+            while (k + c < n_handles && c < rscm::kMaxGroupOps && can_fuse(handles[k + c]) && handles[k + c]->N == handles[k]->N &&
                    handles[k + c]->device == handles[k]->device)
                 ++c;
         segments.emplace_back(k, c);
@@ -505,13 +454,13 @@ int rscm_ens_run_lockstep(rscm_ens* const* handles, int32_t n_handles, int32_t s
     if (t_ls.fuse && t_ls.merge && t_ls.by_value && plan && segments.size() >= 3 && step_end - step_begin >= 2) {
         const auto& F = segments.front();
         const auto& L = segments.back();
-        merged = fusable(handles[F.first]) && fusable(handles[L.first]) && F.second + L.second <= rscm::kGroupTableOps &&
+        merged = can_fuse(handles[F.first]) && can_fuse(handles[L.first]) && F.second + L.second <= rscm::kGroupTableOps &&
                  handles[F.first]->N == handles[L.first]->N && handles[F.first]->device == handles[L.first]->device;
         for (int32_t k = F.first; merged && k < F.first + F.second; ++k) {
             const rscm_ens* h = handles[k];
             for (int32_t j = 0; j < rscm::kMaxLinks && j < h->n_inputs; ++j) {
                 const auto& l = h->links[j];
-                if (!l.src || !(h->kind == RSCM_KIND_AGGREGATE || l.off == 1)) continue;
+                if (!l.src || !h->reads_end(l)) continue;
                 bool inside = false;
                 for (int32_t q = F.first; q < F.first + F.second; ++q) inside = inside || handles[q] == l.src;
                 if (!inside) merged = false;

@@ -58,7 +58,7 @@ class KindInfo:
     inputs: Tuple[str, ...]        # value class per input row (None: exogenous only, e.g. the halocarbon emissions)
     outputs: Dict[int, str]        # stored variable id -> value class
     init: Dict[int, float]         # row 0 of every stored variable
-    light: bool                    # fusable() in csrc/lockstep.cpp (GhgForcing: only with linked inputs)
+    light: bool                    # the kind's `fusable` in csrc/kinds.hpp (GhgForcing: only with linked inputs)
     perturb: Tuple[int, ...] = ()  # parameter rows drawn per member (x U(0.9, 1.1))
     tol: float = 1e-12             # relative tolerance of the closed-loop check (those of the single-component GPU tests)
 
@@ -97,7 +97,7 @@ CATALOGUE = {
                           False, (3, 10), tol=1e-9),
 }
 LIGHT_KINDS = tuple(k for k, v in CATALOGUE.items() if v.light)
-# group_kind_is_small (csrc/group.hip) -- the same kinds as keeps_slots (csrc/lockstep.cpp): a launch of these only may keep LDS slots
+# group_kind_is_small (csrc/group.hip): a launch of these only may keep LDS slots
 SMALL_KINDS = (L.KIND_TWO_LAYER, L.KIND_AEROSOL_INDIRECT, L.KIND_FOURBOX_OHU, L.KIND_OSPP, L.KIND_CO2_ERF, L.KIND_AGGREGATE,
                L.KIND_CO2_BUDGET, L.KIND_CARBON_CYCLE)
 # group_seq_available: SeqCoupled and SeqForced have a kernel of their own (group_seq_kernel)
@@ -182,7 +182,7 @@ class Node:
 
     @property
     def light(self) -> bool:
-        """fusable() of csrc/lockstep.cpp."""
+        """can_fuse() of csrc/ens.hpp."""
         return self.info.light and (self.kind != L.KIND_GHG_FORCING or len(self.links) > 0)
 
     @property

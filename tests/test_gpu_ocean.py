@@ -90,6 +90,60 @@ def test_ocean_gpu_vs_oracle(ra, orc, n):
     assert np.array_equal(got[:, :, off], want[:, :, off], equal_nan=True)  # members without the exp: exact
 
 
+def test_ocean_one_step_launches_in_any_pattern(ra, orc):
+    """A lone EXACT handle stepped in short launches that start inside and outside a split two-year tile: one-step launches
+    pair up into tiles, a longer launch or a rewind in the middle of a tile drops the sums parked for its second year.  Every
+    pattern stays within test_ocean_gpu_vs_oracle's tolerance of the oracle; the rerun after a rewind repeats its first run's
+    bits."""
+    from tests import host_lockstep as H
+    n, T = 130, 11   # two wavefronts and a ragged tail; ten model steps of twelve sub-steps
+    b = np.arange(T + 1, dtype=float) + 1850.0
+    yr = np.arange(T, dtype=float)
+    P = H.default_params(ra.KIND_OCEAN_CARBON, n, np.random.default_rng(130))
+    inputs = np.stack([H.EXO["co2_conc"](yr), H.EXO["temp"](yr)])
+    want = orc.ocean_run(b, P, inputs, 278.0, 0.0, threads=8)
+    ok = ~np.isnan(want)
+
+    def check(got, what):
+        assert (np.isnan(got) == np.isnan(want)).all(), what
+        err = np.abs(got[ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))
+        print(f"{what}: max deviation {err.max():.3e}")
+        assert err.max() <= TOL, f"{what}: max deviation {err.max():.3e}"
+
+    def series(e, rows=T):
+        assert not e.status().any()
+        return np.stack([e.get_series(v, 0, rows) for v in (1, 2, 3)])
+
+    def stepped(lengths, rewind_at=None):
+        assert sum(lengths) == T - 1
+        with ra.Ensemble(ra.KIND_OCEAN_CARBON, n, b) as e:
+            e.set_mode(ra.MODE_EXACT)
+            e.set_params(P)
+            e.set_forcing(inputs)
+            e.set_initial(1, 278.0)
+            e.set_initial(2, 0.0)
+            first = None
+            if rewind_at is not None:   # single steps up to the middle of a tile, then back to the start
+                for _ in range(rewind_at):
+                    e.run(e.time_index + 1)
+                first = series(e, rewind_at + 1)
+                e.rewind()
+            for c in lengths:
+                e.run(e.time_index + c)
+            return series(e), first
+
+    ones = (1,) * (T - 1)
+    all_ones, _ = stepped(ones)
+    check(all_ones, "all ones")
+    check(stepped((2,) + (1,) * (T - 3))[0], "(2, 1, 1, ...)")
+    check(stepped((1, 4) + (1,) * (T - 6))[0], "(1, 4, 1, 1, ...)")
+    # steps 0 and 1 are one tile, step 2 starts the next: time index 3 is the middle of a tile
+    rerun, first = stepped(ones, rewind_at=3)
+    check(rerun, "ones, rewound in the middle of a tile")
+    assert np.array_equal(rerun[:, :4], first, equal_nan=True)
+    assert np.array_equal(rerun, all_ones, equal_nan=True)
+
+
 @pytest.mark.parametrize("max_hist", [0, 5, 12, 30, 100])
 def test_ocean_gpu_bounded_history(ra, orc, max_hist):
     """max_history_months shorter than the run: the window slides inside a year (5), across

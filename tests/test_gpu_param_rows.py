@@ -15,7 +15,7 @@ The kinds with a FAST mode repeat (a) and (d) in it.
 
 The light kinds repeat every mask of (a), (c) and (d) through rscm_ens_run_lockstep: the same bits as run().  A call on one handle
 alone is never fused (csrc/lockstep.cpp: a fused launch takes a segment of more than one handle), so the handle goes
-  - next to a CO2ERF handle: one fused multi-step launch (csrc/group.hip).  The small kinds (keeps_slots) get LDS slots for their
+  - next to a CO2ERF handle: one fused multi-step launch (csrc/group.hip).  The small kinds (group_kind_is_small) get LDS slots for their
     series and, where a row varies, for their parameters; OzoneForcing, AerosolDirect, CH4Chemistry, N2OChemistry and
     TerrestrialCarbon are not small and run the fused launch without any slot; GhgForcing without linked inputs is not fusable at
     all, its call is one-step launches of its own kernel;

@@ -1163,7 +1163,7 @@ def test_runs_cut_into_member_blocks_and_chunks_keep_the_bits(ra, orc, kind, mod
 
 @pytest.mark.parametrize("fail_at", [1, 2, 7, 24])   # the first launch of either block, one in the middle, the very last
 def test_a_failed_chunk_launch_joins_the_streams_and_leaves_the_run_undone(ra, orc, fail_at):
-    """The error path of the cut runs (rscm_gpu.cpp run_member_split): when a chunk's launch fails, the caller's stream is still
+    """The error path of the cut runs (launch_host.cpp run_member_split): when a chunk's launch fails, the caller's stream is still
     joined with the handle's helper stream (nothing issued there outlives the call unseen), rscm_ens_run returns RSCM_ERR_DEVICE, the
     time index has not moved -- and the handle is intact: the same run issued again gives the uncut path's bits.  No real launch
     can be made to fail on demand: rscm_gpu_fail_chunk_launch (include/rscm_gpu_internal.h) makes the k-th chunk launch of the
