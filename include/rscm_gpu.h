@@ -89,8 +89,10 @@ extern "C" {
  *  11  per-group quantiles and exceedance: rscm_ens_set_member_groups, rscm_ens_member_groups_devptr,
  *      rscm_ens_clear_member_groups, RSCM_SELECT_GROUPED, rscm_ens_exceedance_grouped
  *  12  two-layer mix handles -- per-member forcing as a scaled sum of shared components: rscm_ens_create_mix,
- *      rscm_ens_n_forcing_components, RSCM_TL_P_COEFF0, RSCM_TL_MAX_COMPONENTS */
-#define RSCM_GPU_ABI_MINOR 12
+ *      rscm_ens_n_forcing_components, RSCM_TL_P_COEFF0, RSCM_TL_MAX_COMPONENTS
+ *  13  seeded forcing noise of a two-layer handle (internal variability): rscm_ens_set_forcing_noise, rscm_ens_clear_forcing_noise,
+ *      rscm_ens_forcing_noise, rscm_ens_forcing_noise_rows, RSCM_NOISE_STREAM_TAG */
+#define RSCM_GPU_ABI_MINOR 13
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -488,6 +490,44 @@ RSCM_API int rscm_ens_set_params_aos(rscm_ens* h, const double* aos);
  * scenario_of_member[N] or NULL (all members use scenario 0). */
 RSCM_API int rscm_ens_set_forcing(rscm_ens* h, int32_t var_id, int32_t n_scen, const double* series,
                          const int32_t* scenario_of_member, int32_t source);
+/* Forcing noise (ABI minor 13): internal variability of a two-layer ensemble as white noise in the heat flux into the upper layer
+ * (Hasselmann).  With noise on, member i of the handle reads forcing-axis index t -- the index actually read, n + the offset of
+ * `source`, so `source` keeps its meaning -- and is forced there by
+ *     F' = F + sigma * z(seed, g, t),        g = member_offset + i, i counted in the whole handle,
+ * the product and the sum each rounded on its own (no FMA) in BOTH arithmetic modes.  F is the scenario value, or for a mix handle
+ * (rscm_ens_create_mix) the mix sum formed first.  NaN and Inf propagate.  The arithmetic is done whenever noise is on, sigma == 0
+ * included (F + 0 * z: a forcing of -0.0 becomes +0.0 where z > 0); off is rscm_ens_clear_forcing_noise.
+ * z is a standard normal deviate that is a pure function of (seed, g, t) -- white in t, independent between members, no state: chunked
+ * runs, the cut of a large run into member blocks, rscm_ens_rewind, checkpoints and rscm_ens_gather_members see the same noise by
+ * construction, and nothing is stored for it.  Its definition, every step exact or a single IEEE f64 operation (a host restates it
+ * with the same bits: tests/host_forcing_noise.py):
+ *   block    philox4x32_10 with counter {lo32(g), hi32(g), t >> 1, RSCM_NOISE_STREAM_TAG} and key {lo32(seed), hi32(seed)};
+ *            even t takes words (0,1) as (lo,hi), odd t words (2,3)
+ *   uniform  k = ((hi << 32) | lo) >> 12 (52 bits);  u = (double)(2k + 1) * 2^-53, exact, in (0,1), symmetric about 1/2;  q = u - 0.5
+ *   deviate  Wichura's AS241 PPND16 with its published constants, numerators and denominators of degree 7 in Horner form
+ *            (((c7 r + c6) r + c5) ...):
+ *              |q| <= 0.425:  r = 0.180625 - q*q;  z = (A(r) * q) / B(r)
+ *              otherwise      p = q < 0 ? u : 1.0 - u (exact);  r = sqrt(-ln(p));
+ *                             r <= 5: r -= 1.6, z = C(r) / D(r);  else r -= 5, z = E(r) / F(r);  z negated if q < 0
+ *   ln(p)    for p in [2^-53, 0.075], in + - * / only: p = m 2^e by bits, m in [1,2); if m > 1.4142135623730951 then m *= 0.5, e += 1;
+ *            s = (m - 1)/(m + 1);  w = s*s;  P = 1/25, then P = P*w + 1/(2j+1) for j = 11 .. 1 (each constant the f64 nearest the
+ *            fraction);  s2 = s + s;  ln(p) = e * 0.6931471805599453 + (s2 + s2*(w*P))
+ * (k = 0 gives -8.2095..., k = 2^52 - 1 gives +8.2095...: |z| is bounded.)
+ * An option of a RSCM_KIND_TWO_LAYER handle, not a kind.  RSCM_ERR_INVALID: sigma negative or not finite; member_offset < 0 (a shard
+ * passes the global index of its first member); another kind; a windowed or RSCM_FLAG_NO_SERIES handle; a handle with a linked input.
+ * A handle with noise runs on its own: rscm_ens_link_input onto it, rscm_ens_run_lockstep, rscm_sampler_create* with it and the fused
+ * rscm_ens_run_loglik* return RSCM_ERR_INVALID (the likelihood of one noise realisation per walker index is not a target the stretch
+ * move samples).  rscm_ens_run* followed by the stored rscm_ens_loglik* is how a noisy ensemble is weighted, resampled and branched.
+ * rscm_ens_gather_members leaves the destination's setting alone: like the forcing, the noise belongs to dst -- give dst a seed or an
+ * offset of its own and the copies of one ancestor diverge. */
+#define RSCM_NOISE_STREAM_TAG 0x4E5Au /* "NZ" */
+RSCM_API int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma, int64_t member_offset);
+RSCM_API int rscm_ens_clear_forcing_noise(rscm_ens* h);
+/* The setting: *on 1 or 0, and the three numbers (0 when off).  Any pointer may be NULL. */
+RSCM_API int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, double* sigma, int64_t* member_offset);
+/* The term itself: out[(t - t_begin) * N + i] = sigma * z(seed, member_offset + i, t) for t in [t_begin, t_end) within [0, n_times];
+ * `out` is host memory, or with on_device != 0 device memory filled on the handle's stream.  RSCM_ERR_STATE without noise. */
+RSCM_API int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, double* out, int32_t on_device);
 /* Initial value(s) at time index 0 of a state variable: n_values == 1 (broadcast) or N.
  * Also rewinds the time index to 0. */
 /* Linked input: row `input_row` of h's input block is read, member by member, from the stored series

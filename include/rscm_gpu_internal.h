@@ -116,6 +116,11 @@ RSCM_API int rscm_gpu_ocean_fit_selftest(int32_t model, double irf_scale, double
 RSCM_API int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const double* den,
                                    double* out_ref, double* out_fast, uint8_t* used_fast);
 
+/* z[j] = the device's normal deviate of the 52-bit integer k52[j] (the low 52 bits are used): the AS241 evaluation of a forcing-noise
+ * draw (rscm_ens_set_forcing_noise in rscm_gpu.h) without the Philox block in front, so that chosen k put every branch in play.
+ * Runs on the calling thread's current device. */
+RSCM_API int rscm_gpu_selftest_normal(const uint64_t* k52, int64_t n, double* z);
+
 #ifdef __cplusplus
 }
 #endif

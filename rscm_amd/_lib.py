@@ -30,6 +30,7 @@ FLAG_NO_SERIES = 1
 FLAG_WINDOWED = 2
 TL_P_COEFF0 = 6          # a mix ensemble's coefficient rows start here (RSCM_TL_P_COEFF0)
 TL_MAX_COMPONENTS = 8    # RSCM_TL_MAX_COMPONENTS
+NOISE_STREAM_TAG = 0x4E5A   # RSCM_NOISE_STREAM_TAG: the Philox stream of the forcing noise
 SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
 SELECT_ANOMALY = 2
 SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
@@ -249,6 +250,10 @@ SIGNATURES = {
     "rscm_ens_n_vars": (C.c_int, [_h, _ip]),
     "rscm_ens_n_inputs": (C.c_int, [_h, _ip]),
     "rscm_ens_n_forcing_components": (C.c_int, [_h, _ip]),
+    "rscm_ens_set_forcing_noise": (C.c_int, [_h, C.c_uint64, C.c_double, C.c_int64]),
+    "rscm_ens_clear_forcing_noise": (C.c_int, [_h]),
+    "rscm_ens_forcing_noise": (C.c_int, [_h, _ip, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_int64)]),
+    "rscm_ens_forcing_noise_rows": (C.c_int, [_h, C.c_int32, C.c_int32, _dp, C.c_int32]),
     "rscm_ens_n_members": (C.c_int, [_h, C.POINTER(C.c_int64)]),
     "rscm_ens_n_times": (C.c_int, [_h, _ip]),
     "rscm_ens_set_mode": (C.c_int, [_h, C.c_int32]),
@@ -371,6 +376,7 @@ SIGNATURES = {
     "rscm_gpu_copy_to_device": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),
     "rscm_gpu_ocean_fit_selftest": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_int64, _dp, _ip, _ip, _ip, _dp]),
     "rscm_ens_ocean_fast_info": (C.c_int, [_h, _ip, _dp]),
+    "rscm_gpu_selftest_normal": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, _dp]),
     "rscm_gpu_selftest_div": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _bp]),
 }
 

@@ -428,6 +428,9 @@ class ModelRunner:
 
     def __init__(self, model: ModelBuilder, param_names: Sequence[str],
                  output_variables: Sequence[str], mode: int = L.MODE_EXACT, execution_order: str = "reference"):
+        if getattr(model, "_noise", None) is not None:
+            raise ValueError("ModelRunner: the builder has forcing noise (with_forcing_noise); a batch evaluator would score one noise "
+                             "realisation per batch index.  Build the model, run it and score the stored series instead")
         self._builder = model
         self._param_names = list(param_names)
         self._outputs = list(output_variables)
@@ -974,6 +977,9 @@ class DeviceEnsembleSampler:
             raise ValueError(f"Stretch move scale parameter must be > 1.0, got {stretch_a}")
         if list(params.param_names) != runner.param_names:
             raise ValueError("the parameter set must name the runner's parameters, in its order")
+        if getattr(getattr(runner, "_builder", None), "_noise", None) is not None:
+            raise ValueError("DeviceEnsembleSampler: the runner's builder has forcing noise (with_forcing_noise); the likelihood of one "
+                             "noise realisation per walker index is not a target the stretch move samples")
         self.params, self.runner, self.likelihood, self.target = params, runner, likelihood, target
         self.a = float(stretch_a)
         self.default_n_walkers = max(2 * len(params), 32)

@@ -468,6 +468,7 @@ class ModelBuilder:
         self._device = 0
         self._grid_weights: Dict["GridType", List[float]] = {}
         self._mix: Optional[Tuple[str, Dict[str, Timeseries], Dict[str, float]]] = None   # with_forcing_components
+        self._noise: Optional[Tuple[float, int]] = None   # with_forcing_noise: (sigma, seed)
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -519,6 +520,39 @@ class ModelBuilder:
                      {n: float((scales or {}).get(n, 1.0)) for n in names})
         return self
 
+    def with_forcing_noise(self, sigma: float, seed: int) -> "ModelBuilder":
+        """Extension: internal variability.  Where ``build()`` returns the single two-layer ensemble (one ``TwoLayer`` reading
+        its exogenous forcing, with or without ``with_forcing_components``), member i is forced by ``F + sigma * z(seed, i, t)``:
+        seeded white noise in the heat flux into the upper layer, a pure function of (seed, member, index on the forcing axis)
+        (``Ensemble.set_forcing_noise``).  Any other build -- a graph of linked ensembles, ``series_window``, a likelihood-only
+        model -- raises ``ValueError``; so do ``ModelRunner`` and ``DeviceEnsembleSampler`` on such a builder: the likelihood of
+        one noise realisation per walker is not a target the stretch move samples.  Run the model, score the stored series
+        (``Ensemble.loglik``), weight, resample and branch instead."""
+        sigma, seed = float(sigma), int(seed)
+        if not (sigma >= 0.0 and math.isfinite(sigma)):
+            raise ValueError(f"with_forcing_noise: sigma must be finite and not negative, got {sigma}")
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"with_forcing_noise: seed must fit 64 unsigned bits, got {seed}")
+        self._noise = (sigma, seed)
+        return self
+
+    def _check_forcing_noise(self, store_series: bool, series_window) -> None:
+        """Raises ``ValueError`` unless ``build()`` with these arguments yields the single two-layer (or mix) ensemble with
+        stored series, the one shape forcing noise is an option of.  Needs no device."""
+        why = None
+        types = [c.type_name for c in self._components]
+        if series_window is not None:
+            why = "series_window builds a graph of windowed ensembles"
+        elif any(getattr(c, "is_python", False) for c in self._components) or types != ["TwoLayer"]:
+            why = f"this model (components {types}) builds a GraphModel or another kind"
+        elif self._mix is None and self._resolve()[3]:
+            why = "a schema aggregate in front of the TwoLayer builds a GraphModel"
+        elif not store_series:
+            why = "a likelihood-only model (store_series=False) keeps no series to add the noise's effect to"
+        if why:
+            raise ValueError(f"with_forcing_noise: {why}; forcing noise is an option of the single two-layer ensemble "
+                             "(one TwoLayer reading its exogenous forcing, whole series stored)")
+
     def forcing_mix_plan(self) -> Optional[Dict[str, object]]:
         """What ``build()`` makes of ``with_forcing_components`` (None without it), formed on the host: ``names``, the
         ``param_order`` and ``base_params`` of the model and the ``[K][T]`` component block on the model's axis.  Raises
@@ -558,6 +592,8 @@ class ModelBuilder:
         for name, vid in ens.var_ids.items():
             if vid > 0 and name in self._initial:
                 ens.set_initial(vid, self._initial[name])
+        if self._noise is not None:
+            ens.set_forcing_noise(*self._noise)
         model = Model(ens, self._axis, sources, endogenous, plan["block"], dict(self._initial), plan["param_order"], plan["base_params"])
         model._builder = self
         return model
@@ -1095,6 +1131,8 @@ class ModelBuilder:
         names; None: every variable).  The reference holds whole collections, one member at a time
         (model/builder.rs:735-830); 1e5 members x 9001 monthly points x 36 series do not fit a GPU that
         way.  ``get_series(name, t_stride=output_stride)`` reads the kept rows."""
+        if self._noise is not None:
+            self._check_forcing_noise(store_series, series_window)
         endogenous, sources, exo_names, aggregates = self._resolve()
         if self._mix is not None:
             if series_window is not None:
@@ -1161,6 +1199,8 @@ class ModelBuilder:
             ens.set_step_size(comp_id, step)
         ens.set_params(np.repeat(np.array(params, dtype=np.float64)[:, None], n_members, axis=1))
         ens.set_forcing(forcing, None, src)
+        if self._noise is not None:   # (_check_forcing_noise: this is the two-layer ensemble)
+            ens.set_forcing_noise(*self._noise)
         for name, vid in ens.var_ids.items():
             if vid > 0 and name in self._initial:
                 ens.set_initial(vid, self._initial[name])

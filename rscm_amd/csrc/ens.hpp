@@ -114,6 +114,11 @@ struct rscm_ens {
     double* d_series = nullptr;  // [(V-1)][T][N], variable v at slot v-1
     double* d_forcing = nullptr; // [S][n_inputs][T]
     int32_t n_inputs = 1;        // rows per scenario of the shared input block
+    // rscm_ens_set_forcing_noise: member i is forced by F + noise_sigma * z(noise_seed, noise_offset + i, t) (forcing_noise.hpp)
+    bool noise_on = false;
+    uint64_t noise_seed = 0;
+    double noise_sigma = 0.0;
+    int64_t noise_offset = 0;
     int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
     double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;

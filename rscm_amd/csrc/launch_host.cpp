@@ -290,6 +290,12 @@ void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, con
     a.count_guards = t_tl_count_guards;
     a.ts = h->series(RSCM_TL_VAR_TS);
     a.td = h->series(RSCM_TL_VAR_TD);
+    if (h->noise_on) {   // (rscm_ens_set_forcing_noise; step_launch refuses a linked or fused launch of such a handle)
+        a.noise_on = 1;
+        a.noise_seed = h->noise_seed;
+        a.noise_sigma = h->noise_sigma;
+        a.noise_member0 = h->noise_offset;
+    }
 }
 rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t end, int64_t m0, int64_t count)
 {
@@ -303,6 +309,7 @@ rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t 
     c.ts = a.ts + m0;
     c.td = a.td + m0;
     c.status = a.status + m0;
+    c.noise_member0 = a.noise_member0 + m0;   // the kernel counts members from the block's first: the noise is a function of the id in the ensemble
     return c;
 }
 
@@ -560,6 +567,8 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
     const rscm::Family family = h->info().family;
     if (h->n_comp > 0 && (linked || op_out))   // (rscm_ens_link_input and rscm_ens_run_lockstep refuse the handle before this)
         return fail(RSCM_ERR_INVALID, "a mix handle runs on its own: no linked input, no lock-step launch");
+    if (h->noise_on && (linked || op_out))   // (likewise refused before this)
+        return fail(RSCM_ERR_INVALID, "a handle with forcing noise runs on its own: no linked input, no lock-step launch");
     if (op_out) {  // the step range is an argument of the fused launch, not part of the table
         if (!can_fuse(h)) return fail(RSCM_ERR_STATE, "this handle (kind %d) cannot be fused", h->kind);
         op_out->kind = h->kind;

@@ -23,6 +23,7 @@ constexpr int kMaxStaticLds = 64 * 1024;     // above this the launcher raises t
 constexpr int kMaxLds = 160 * 1024;          // CDNA4: 160 KiB per CU
 constexpr int kMaxForcingComponents = 8;     // RSCM_TL_MAX_COMPONENTS: forcing components of a two-layer mix handle
 constexpr int kTwoLayerCoeff0 = 6;           // RSCM_TL_P_COEFF0: the parameter row of its first coefficient
+constexpr uint32_t kNoiseStreamTag = 0x4E5Au;   // RSCM_NOISE_STREAM_TAG ("NZ"): the Philox stream of the forcing noise (forcing_noise.hpp)
 
 // Linked inputs (rscm_ens_link_input): input row k of a member is read from the stored series of
 // another ensemble of the same shape -- row[k] is that series, [T][N], off[k] the index offset of
@@ -361,6 +362,15 @@ struct TwoLayerArgs {
     const double* obs_value;
     const double* obs_sigma;
     double* loglik;               // [N]
+    // Forcing noise (rscm_ens_set_forcing_noise; the NOISE instantiations: stand-alone stored runs, never linked).  noise_on 1: member
+    // i of this launch is forced by F' = F + noise_sigma * z(noise_seed, noise_member0 + i, t) at forcing-axis index t = n + src_off
+    // (forcing_noise.hpp).  noise_member0 is the id in the whole ensemble of the launch's first member: the handle's member_offset,
+    // plus the block's first member where the host launches a block (block_of, launch_host.cpp).  At the end: the other fields
+    // keep the offsets of the launches without it
+    uint64_t noise_seed;
+    double noise_sigma;
+    int64_t noise_member0;
+    int32_t noise_on;
 };
 
 // Reference periods of the fused likelihood (launch_two_layer_loglik_ref; DESIGN.md section 7, "Reference periods"), index 0: Surface
@@ -698,6 +708,11 @@ inline bool two_layer_fits_lds(int32_t n_scen, int32_t n_comp, int32_t len)
     return two_layer_lds_bytes(n_scen, n_comp, len) <= (size_t)kMaxLds - 1024;
 }
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
+// out[(t - t_begin) * n_members + i] = sigma * z(seed, member0 + i, t) for t in [t_begin, t_end): the term a noise handle adds to its forcing
+hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end,
+                                     double* out, hipStream_t s);
+// z[j] = the deviate of the 52-bit integer k52[j] (test hook, rscm_gpu_selftest_normal)
+hipError_t launch_normal_selftest(const uint64_t* k52, int64_t n, double* z, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);
 hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s);
 // the current device's wavefront counts per guard of the counting launches (TwoLayerArgs::count_guards) into out[3] (if not null),

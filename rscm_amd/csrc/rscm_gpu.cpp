@@ -226,6 +226,10 @@ static double ocean_fit_modes(const std::vector<double>& tab, int model, double 
 
 constexpr double kOceanFitTolerance = 5e-10;  // largest deviation of the fitted far response accepted for RSCM_MODE_FAST
 
+static_assert(rscm::kNoiseStreamTag == RSCM_NOISE_STREAM_TAG, "the noise stream's tag in rscm_device.hpp and rscm_gpu.h must agree");
+static_assert(RSCM_NOISE_STREAM_TAG != 0x57A7u && RSCM_NOISE_STREAM_TAG != 0xACCEu && RSCM_NOISE_STREAM_TAG != 0x5EEDu &&
+                  RSCM_NOISE_STREAM_TAG != 0xA5A5u && RSCM_NOISE_STREAM_TAG != RSCM_RESAMPLE_STREAM_TAG,
+              "every Philox stream of the library has a tag of its own");
 static_assert(rscm::kMaxForcingComponents == RSCM_TL_MAX_COMPONENTS && rscm::kTwoLayerCoeff0 == RSCM_TL_P_COEFF0 && RSCM_TL_P_COEFF0 == RSCM_TL_NPARAMS,
               "the mix handle's constants in rscm_device.hpp and rscm_gpu.h must agree");
 static_assert(rscm::kKindOzoneForcing == RSCM_KIND_OZONE_FORCING && rscm::kKindAerosolDirect == RSCM_KIND_AEROSOL_DIRECT &&
@@ -1017,6 +1021,9 @@ int rscm_ens_link_input(rscm_ens* h, int32_t input_row, rscm_ens* src, int32_t s
     if (h->n_comp > 0)
         return fail(RSCM_ERR_INVALID, "the forcing components of a mix handle (rscm_ens_create_mix) cannot be linked: they are shared "
                                       "scenario rows scaled per member");
+    if (h->noise_on)
+        return fail(RSCM_ERR_INVALID, "a handle with forcing noise (rscm_ens_set_forcing_noise) takes no linked input: the noise is added to "
+                                      "its own shared forcing; clear the noise first");
     if (input_row < 0 || input_row >= h->n_inputs || input_row >= rscm::kMaxLinks)
         return fail(RSCM_ERR_INVALID, "input row %d out of range [0, %d)", input_row, h->n_inputs);
     if (src_var < 1 || src_var >= src->V) return fail(RSCM_ERR_INVALID, "variable %d of the source has no stored series", src_var);
@@ -1805,6 +1812,83 @@ int rscm_ens_ocean_fast_info(rscm_ens* h, int32_t* uses_recurrence, double* fit_
     if (uses_recurrence) *uses_recurrence = h->ocean_recur_ok ? 1 : 0;
     if (fit_error) *fit_error = h->ocean_fit_error;
     return RSCM_OK;
+}
+
+int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma, int64_t member_offset)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (h->kind != RSCM_KIND_TWO_LAYER)
+        return fail(RSCM_ERR_INVALID, "forcing noise is available for the two-layer kind only (RSCM_KIND_TWO_LAYER), this handle has kind %d", h->kind);
+    if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(RSCM_ERR_INVALID, "sigma must be finite and not negative, got %g", sigma);
+    if (member_offset < 0) return fail(RSCM_ERR_INVALID, "member_offset must not be negative, got %lld", (long long)member_offset);
+    if (h->windowed || h->rows != h->T)
+        return fail(RSCM_ERR_INVALID, "forcing noise needs a handle that stores its whole series (no windowed storage, no RSCM_FLAG_NO_SERIES)");
+    if (h->n_linked > 0) return fail(RSCM_ERR_INVALID, "this handle has a linked input: the noise is added to a handle's own shared forcing");
+    h->noise_on = true;
+    h->noise_seed = seed;
+    h->noise_sigma = sigma;
+    h->noise_offset = member_offset;
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_clear_forcing_noise(rscm_ens* h)
+{
+    NEED(h);
+    h->noise_on = false;
+    h->noise_seed = 0;
+    h->noise_sigma = 0.0;
+    h->noise_offset = 0;
+    return RSCM_OK;
+}
+
+int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, double* sigma, int64_t* member_offset)
+{
+    NEED(h);
+    if (on) *on = h->noise_on ? 1 : 0;
+    if (seed) *seed = h->noise_seed;
+    if (sigma) *sigma = h->noise_sigma;
+    if (member_offset) *member_offset = h->noise_offset;
+    return RSCM_OK;
+}
+
+int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, double* out, int32_t on_device)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!h->noise_on) return fail(RSCM_ERR_STATE, "this handle has no forcing noise (rscm_ens_set_forcing_noise)");
+    if (t_begin < 0 || t_end < t_begin || t_end > h->T)
+        return fail(RSCM_ERR_INVALID, "rows [%d, %d) are not within the forcing axis [0, %d)", t_begin, t_end, h->T);
+    if (t_end == t_begin) return RSCM_OK;
+    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
+    if (int rc = set_device(h)) return rc;
+    const size_t bytes = (size_t)(t_end - t_begin) * (size_t)h->N * sizeof(double);
+    double* d = out;
+    if (!on_device) HIPCHK(rscm::dev_malloc(&d, bytes));
+    hipError_t e = rscm::launch_forcing_noise_rows(h->noise_seed, h->noise_sigma, h->noise_offset, h->N, t_begin, t_end, d, h->stream);
+    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && !on_device) e = hipStreamSynchronize(h->stream);
+    if (!on_device) (void)hipFree(d);
+    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "forcing_noise_rows: %s", hipGetErrorString(e));
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_gpu_selftest_normal(const uint64_t* k52, int64_t n, double* z)
+{
+    GUARD_BEGIN
+    if (n < 0 || !k52 || !z) return fail(RSCM_ERR_INVALID, "bad arguments");
+    if (n == 0) return RSCM_OK;
+    double* d = nullptr;   // [n] integers, then [n] deviates
+    HIPCHK(rscm::dev_malloc(&d, 2 * (size_t)n * sizeof(double)));
+    hipError_t e = hipMemcpy(d, k52, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rscm::launch_normal_selftest(reinterpret_cast<const uint64_t*>(d), n, d + n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(z, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "selftest_normal: %s", hipGetErrorString(e));
+    return RSCM_OK;
+    GUARD_END
 }
 
 int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const double* den,

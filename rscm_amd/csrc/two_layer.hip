@@ -45,7 +45,8 @@ namespace {
 __device__ unsigned long long g_guard_counts[tl::kGuardKinds];
 
 // MIX: a mix handle's launch (a.n_comp >= 1): the staged table is [n_scen][n_comp][len], n_scen * n_comp rows laid out like scenarios
-template <int MODE, bool LDS, bool STORE, bool MIX = false>
+// NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing
+template <int MODE, bool LDS, bool STORE, bool MIX = false, bool NOISE = false>
 __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 {
     extern __shared__ double lds_forcing[];
@@ -60,10 +61,27 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
-    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE, NoCache, false, MIX>(a, lds_forcing, i, a.step_begin, a.step_end);
+    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE, NoCache, false, MIX, NOISE>(a, lds_forcing, i, a.step_begin, a.step_end);
     if constexpr (MODE == 0) {
         if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
     }
+}
+
+// sigma * z for rows [t_begin, t_end) x n members: what a noise handle adds to its forcing (rscm_ens_forcing_noise_rows)
+__global__ __launch_bounds__(kBlock) void forcing_noise_rows_kernel(uint64_t seed, double sigma, int64_t member0, int64_t n, int32_t t_begin,
+                                                                    int32_t t_end, double* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t g = (uint64_t)(member0 + i);
+    double* o = out + i;
+    for (int32_t t = t_begin; t < t_end; ++t, o += n) *o = sigma * noise::draw(seed, g, (uint32_t)t);
+}
+
+__global__ __launch_bounds__(kBlock) void normal_selftest_kernel(const uint64_t* k52, int64_t n, double* z)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j < n) z[j] = noise::normal_from_k(k52[j] & 0x000FFFFFFFFFFFFFull);
 }
 
 // The fused likelihood with reference periods: an instantiation of its own, so that launches without a period run the kernels above
@@ -113,6 +131,18 @@ static hipError_t launch_impl(const TwoLayerArgs& a, int mode, hipStream_t s)
                          : (a.lds_forcing ? two_layer_kernel<1, true, STORE, true> : two_layer_kernel<1, false, STORE, true>))
             : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, STORE> : two_layer_kernel<0, false, STORE>)
                          : (a.lds_forcing ? two_layer_kernel<1, true, STORE> : two_layer_kernel<1, false, STORE>));
+    if (a.noise_on) {   // the stored run of a handle that is not linked: the only launch that carries noise
+        if constexpr (STORE) {
+            if (a.link) return hipErrorInvalidValue;
+            kern = a.n_comp > 0
+                       ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, true> : two_layer_kernel<0, false, true, true, true>)
+                                    : (a.lds_forcing ? two_layer_kernel<1, true, true, true, true> : two_layer_kernel<1, false, true, true, true>))
+                       : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, true> : two_layer_kernel<0, false, true, false, true>)
+                                    : (a.lds_forcing ? two_layer_kernel<1, true, true, false, true> : two_layer_kernel<1, false, true, false, true>));
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
     if (lds > (size_t)kMaxStaticLds) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -132,9 +162,26 @@ hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t 
     return launch_impl<false>(a, mode, s);
 }
 
+hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end,
+                                     double* out, hipStream_t s)
+{
+    if (n_members <= 0 || t_end <= t_begin) return hipSuccess;
+    hipLaunchKernelGGL(forcing_noise_rows_kernel, dim3((unsigned)((n_members + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, seed, sigma, member0,
+                       n_members, t_begin, t_end, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_normal_selftest(const uint64_t* k52, int64_t n, double* z, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(normal_selftest_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, k52, n, z);
+    return hipGetLastError();
+}
+
 hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
+    if (a.noise_on) return hipErrorInvalidValue;   // (the fused likelihood of a noise handle is refused at the entry points)
     if (a.n_comp < 0 || a.n_comp > kMaxForcingComponents || (a.n_comp > 0 && a.link)) return hipErrorInvalidValue;
     const size_t lds = a.lds_forcing ? two_layer_lds_bytes(a.n_scen, a.n_comp, a.step_end - a.step_begin) : 0;
     const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));

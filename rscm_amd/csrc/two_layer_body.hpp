@@ -5,6 +5,7 @@
 
 #include <type_traits>
 
+#include "forcing_noise.hpp"
 #include "rk4_device.hpp"
 #include "rscm_device.hpp"
 #include "two_layer_box.hpp"
@@ -295,11 +296,19 @@ enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuar
 // every product and sum rounded on its own in BOTH arithmetic modes (the file is compiled with -ffp-contract=off and nothing here is
 // written as an FMA).  NaN and Inf propagate, no row is skipped and none is padded with 0 * S (that would change -0.0, NaN and Inf):
 // the loop below is unrolled to eight with a wave-uniform k < K around each term, so the coefficients stay in registers.
-template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false>
+// NOISE (a handle with rscm_ens_set_forcing_noise; stand-alone STORE launches only, never linked): the forcing read at forcing-axis
+// index t = n + a.src_off -- the scenario value, or the mix sum formed first -- becomes
+//     F' = F + a.noise_sigma * z(a.noise_seed, a.noise_member0 + i, t),
+// product and sum rounded on their own in BOTH modes, z the stateless deviate of forcing_noise.hpp.  forcing_at adds the term, so the
+// draw for year n + 1 is made in the look-ahead slot of year n and the box guard and the replay see F' like any forcing.  A Philox
+// block serves an even index and the odd one after it: the second pair of words waits in two registers for the next year (which
+// index they serve is wave-uniform), so the ten rounds run every other year.
+template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, bool NOISE = false>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
                                                int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
 {
     static_assert(!(REF && STORE), "reference periods belong to the fused likelihood");
+    static_assert(!NOISE || (STORE && !Cache::kOn), "forcing noise belongs to the stand-alone stored run");
     const int32_t len = step_end - step_begin;
     const int64_t N = a.row_stride;   // the rows' stride (the caller has checked i against a.n_members)
 
@@ -330,6 +339,32 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
         if constexpr (LDS) mix0 = (mix_index)scen * n_comp * len - step_begin;
         else mix0 = (mix_index)scen * n_comp * a.n_times + a.src_off;
     }
+    // NOISE: the member's id in the whole ensemble, and words (2,3) of the last even index's block with the (odd) index they serve
+    [[maybe_unused]] const uint64_t noise_g = NOISE ? (uint64_t)(a.noise_member0 + i) : 0;
+    [[maybe_unused]] uint32_t noise_lo = 0, noise_hi = 0;
+    [[maybe_unused]] int32_t noise_t = -1;   // wave-uniform
+    [[maybe_unused]] auto noisy = [&](int32_t n, double f) -> double {
+        const int32_t t = n + a.src_off;
+        uint32_t lo, hi;
+        if (t == noise_t) {
+            lo = noise_lo;
+            hi = noise_hi;
+        } else {
+            uint32_t c[4];
+            noise::block_of(a.noise_seed, noise_g, (uint32_t)t, c);
+            if (t & 1) {
+                lo = c[2];
+                hi = c[3];
+            } else {
+                lo = c[0];
+                hi = c[1];
+                noise_lo = c[2];
+                noise_hi = c[3];
+                noise_t = t + 1;
+            }
+        }
+        return f + a.noise_sigma * noise::normal_from_k(noise::k_of(lo, hi));
+    };
     auto forcing_at = [&](int32_t n) -> double {
         if constexpr (MIX) {
             const mix_index at = mix0 + n;
@@ -337,8 +372,10 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
 #pragma unroll
             for (int k = 1; k < kMaxForcingComponents; ++k)
                 if (k < n_comp) f = f + mix_base[at + (mix_index)k * mix_row] * coeff[k];
-            return f;
-        } else if constexpr (LDS) return lds_forcing[fl0 + n];
+            if constexpr (NOISE) return noisy(n, f);
+            else return f;
+        } else if constexpr (NOISE) return noisy(n, LDS ? lds_forcing[fl0 + n] : fglob[(size_t)n * fstride]);
+        else if constexpr (LDS) return lds_forcing[fl0 + n];
         else return fglob[(size_t)n * fstride];
     };
     // the year a fused launch is at: the linked forcing from the producer's LDS slot if it is kept there
@@ -348,9 +385,9 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
         }
         return forcing_at(step_begin);
     };
-    // next year's forcing: a fused launch calls per year (n == last), there is no next year to fetch
+    // next year's forcing: a fused launch calls per year (n == last), there is no next year to fetch (nor, with NOISE, to draw for)
     auto forcing_ahead = [&](int32_t n, int32_t np, double current) -> double {
-        if constexpr (Cache::kOn) return n < np ? forcing_at(np) : current;
+        if constexpr (Cache::kOn || NOISE) return n < np ? forcing_at(np) : current;
         else return forcing_at(np);
     };
 

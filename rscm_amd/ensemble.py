@@ -189,6 +189,35 @@ class Ensemble:
         L.check(self._lib.rscm_ens_set_forcing(self._h, self._var(var), s.shape[0], L.dptr(s),
                                                L.iptr(sc), source))
 
+    def set_forcing_noise(self, sigma: float, seed: int, member_offset: int = 0) -> None:
+        """Internal variability (two-layer kind, mix ensembles included): member i is forced at forcing-axis index t by
+        ``F + sigma * z(seed, member_offset + i, t)``, z a standard normal deviate that is a pure function of its three
+        arguments (``rscm_ens_set_forcing_noise``) -- white in t, independent between members, the same whatever way the run is
+        cut, rewound, checkpointed or branched.  ``member_offset`` is the global index of this ensemble's first member (a shard
+        passes its own).  The fused ``run_loglik``, ``link_input``, ``run_lockstep`` and the device sampler refuse such an
+        ensemble; ``run()`` followed by ``loglik()`` scores it."""
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
+        L.check(self._lib.rscm_ens_set_forcing_noise(self._h, C.c_uint64(seed), float(sigma), int(member_offset)))
+
+    def clear_forcing_noise(self) -> None:
+        L.check(self._lib.rscm_ens_clear_forcing_noise(self._h))
+
+    @property
+    def forcing_noise(self) -> Optional[Dict[str, object]]:
+        """``{"sigma", "seed", "member_offset"}`` of ``set_forcing_noise``, or None without noise."""
+        on, seed, sigma, off = C.c_int32(), C.c_uint64(), C.c_double(), C.c_int64()
+        L.check(self._lib.rscm_ens_forcing_noise(self._h, C.byref(on), C.byref(seed), C.byref(sigma), C.byref(off)))
+        return {"sigma": sigma.value, "seed": seed.value, "member_offset": off.value} if on.value else None
+
+    def forcing_noise_rows(self, t_begin: int = 0, t_end: Optional[int] = None) -> np.ndarray:
+        """``[t_end - t_begin][N]``: the term ``sigma * z`` the members' forcing gets at forcing-axis indices ``t_begin .. t_end - 1``."""
+        t_end = self.n_times if t_end is None else int(t_end)
+        out = np.empty((max(t_end - int(t_begin), 0), self.n_members))
+        L.check(self._lib.rscm_ens_forcing_noise_rows(self._h, int(t_begin), t_end, L.dptr(out), 0))
+        return out
+
     def link_input(self, input_row, src: "Ensemble", src_var, source: int = L.SRC_EXOGENOUS) -> None:
         """Read input row ``input_row`` (index or name) member by member from ``src``'s stored
         series ``src_var`` instead of the scenario table: an edge of a component graph kept on the
@@ -309,10 +338,14 @@ class Ensemble:
         if n.value:
             internal = np.empty(n.value)
             L.check(self._lib.rscm_ens_get_internal_state(self._h, L.dptr(internal)))
-        return {"kind": self.kind, "n_members": self.n_members, "bounds": self.bounds.copy(),
-                "time_index": k, "params": self.get_params(),
-                "state": {name: self.get_series(v, k, k + 1)[0] for name, v in names.items()},
-                "history": history, "internal": internal}
+        ck = {"kind": self.kind, "n_members": self.n_members, "bounds": self.bounds.copy(),
+              "time_index": k, "params": self.get_params(),
+              "state": {name: self.get_series(v, k, k + 1)[0] for name, v in names.items()},
+              "history": history, "internal": internal}
+        noise = self.forcing_noise if self.kind == L.KIND_TWO_LAYER else None
+        if noise is not None:   # (stateless: the three numbers are all there is to carry)
+            ck["forcing_noise"] = {"sigma": noise["sigma"], "seed": np.uint64(noise["seed"]), "member_offset": noise["member_offset"]}
+        return ck
 
     def restore(self, ck: Dict[str, object], clear_later_rows: bool = False) -> None:
         """``clear_later_rows``: make every stored row after the checkpoint's time index NaN again, as
@@ -322,6 +355,12 @@ class Ensemble:
                 or not np.array_equal(ck["bounds"], self.bounds)):
             raise ValueError("checkpoint does not match this ensemble (kind, members or time axis)")
         self.set_params(ck["params"])
+        if self.kind == L.KIND_TWO_LAYER:   # the noise setting is the checkpoint's: none where it has none
+            noise = ck.get("forcing_noise")
+            if noise is None:
+                self.clear_forcing_noise()
+            else:
+                self.set_forcing_noise(float(noise["sigma"]), int(noise["seed"]), int(noise["member_offset"]))
         k = int(ck["time_index"])
         # the stepper first: a windowed ensemble positions its window at k, then the rows go in
         internal = ck.get("internal")
@@ -737,7 +776,12 @@ class Ensemble:
         this kind on this axis, mode and device), the same ``n_draws`` resampled members gathered into each of the
         ``scenarios`` blocks.  Returns ``(dst, scenario_of_member)`` with ``scenario_of_member = repeat(arange(scenarios),
         n_draws)`` for the caller's ``dst.set_forcing(series, scenario_of_member)``.  The same vector becomes ``dst``'s member
-        groups (``set_member_groups``), so ``dst.quantile_rows(var, q, grouped=True)`` is the plume per scenario."""
+        groups (``set_member_groups``), so ``dst.quantile_rows(var, q, grouped=True)`` is the plume per scenario.
+
+        Copies of one ancestor stay identical for ever under a shared forcing.  Giving ``dst`` its own forcing noise
+        (``dst.set_forcing_noise(sigma, seed)`` in ``factory`` or afterwards; the noise belongs to ``dst`` like the forcing and
+        a branch leaves it alone) is what makes them diverge: member j of ``dst`` then draws the variability of its own index,
+        whatever ancestor it copies."""
         n_draws, scenarios = int(n_draws), int(scenarios)
         if n_draws < 1 or scenarios < 1:
             raise ValueError("need n_draws >= 1 and scenarios >= 1")

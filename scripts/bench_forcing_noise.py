@@ -1,0 +1,73 @@
+"""Cost of the seeded forcing noise of a two-layer ensemble (rscm_ens_set_forcing_noise) on the GPU: the same handle run with the
+noise on and off, in alternation.  Device-event times (rscm_ens_last_run_ms), two warm-up rounds, then --runs timed rounds; the
+median and the minimum are printed, and the ratio of the medians.  The draw is a Philox block every other year and an AS241
+deviate every year, on top of a year of ten RK4 sub-steps.  profiles/forcing_noise_bench.txt holds one output of this script.
+
+    python scripts/bench_forcing_noise.py [--runs 10] [--sizes 100000 1000000]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rscm_amd  # noqa: E402
+
+T = 751
+BOUNDS = np.arange(T + 1, dtype=np.float64) + 1750.0
+LO = np.array([0.8, 0.0, 1.0, 0.5, 5.0, 50.0])
+HI = np.array([1.5, 0.1, 1.8, 1.0, 15.0, 200.0])
+SIGMA, SEED = 0.3, 20260327
+
+
+def ensemble(n, K, mode):
+    """K == 0: the plain two-layer handle; K > 0: a mix handle."""
+    e = rscm_amd.Ensemble(rscm_amd.KIND_TWO_LAYER, n, BOUNDS, forcing_components=K if K else None)
+    e.set_mode(mode)
+    lo, hi = (np.r_[LO, np.full(K, 0.7)], np.r_[HI, np.full(K, 1.3)]) if K else (LO, HI)
+    e.sample_lhs(SEED, lo, hi)
+    t = np.arange(T, dtype=np.float64)
+    base = 4.0 * (1.0 - np.exp(-t / 120.0)) + 0.3 * np.sin(2.0 * np.pi * t / 11.0)
+    e.set_forcing(np.stack([base / K * (1.0 + 0.1 * np.cos(0.05 * t * (k + 1))) for k in range(K)])[None] if K else base)
+    e.set_initial(1, 0.0)
+    e.set_initial(2, 0.0)
+    return e
+
+
+def timed(e, runs):
+    """{"off": [ms], "on": [ms]} of one handle: two warm-up rounds, then `runs` rounds of off, on."""
+    out = {"off": [], "on": []}
+    for r in range(runs + 2):
+        for name in ("off", "on"):
+            if name == "on":
+                e.set_forcing_noise(SIGMA, SEED)
+            else:
+                e.clear_forcing_noise()
+            e.rewind()
+            e.run()
+            if r >= 2:
+                out[name].append(e.last_run_ms())
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--sizes", type=int, nargs="+", default=[100000, 1000000])
+    a = ap.parse_args()
+    for n in a.sizes:
+        for mode, mode_name in ((rscm_amd.MODE_EXACT, "EXACT"), (rscm_amd.MODE_FAST, "FAST")):
+            for K, what in ((0, "plain two-layer"), (4, "mix K=4")):
+                e = ensemble(n, K, mode)
+                ms = timed(e, a.runs)
+                blocks, chunks = e.last_run_plan()
+                e.close()
+                off, on = np.asarray(ms["off"]), np.asarray(ms["on"])
+                print(f"{n} members x {T - 1} steps, {mode_name}, {what} (noise run cut into {blocks} block(s) x {chunks} chunk(s))")
+                print(f"  noise off  median {np.median(off):9.3f} ms   min {off.min():9.3f} ms   ({off.size} runs)")
+                print(f"  noise on   median {np.median(on):9.3f} ms   min {on.min():9.3f} ms   ({on.size} runs)   "
+                      f"x{np.median(on) / np.median(off):.3f} of off   {n * (T - 1) / np.median(on) * 1e3:.3e} member-years/s", flush=True)
+
+
+if __name__ == "__main__":
+    main()
