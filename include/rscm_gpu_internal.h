@@ -121,6 +121,17 @@ RSCM_API int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* n
  * Runs on the calling thread's current device. */
 RSCM_API int rscm_gpu_selftest_normal(const uint64_t* k52, int64_t n, double* z);
 
+/* Element-wise, on the calling thread's current device, the hand-written math primitives of csrc/rk4_device.hpp and csrc/chem_body.hpp
+ * and the device library's log / exp as this library is compiled:
+ *     op 0  out[i] = log_f64(x[i])                  op 1  the library's log(x[i])          op 2  the library's exp(x[i])
+ *     op 3  out[i] = chem::pow_ratio(x[i], y[i])    op 4  guarded_rcp(x[i])
+ * y is read by op 3 only and may be NULL otherwise.  The kernel calls the very functions the kinds call.  It is representative of
+ * every inlined call site because the library is compiled with -ffp-contract=off and without fast-math and writes each FMA out: the
+ * compiler may not reassociate or fuse, so every instance performs the same IEEE operations.  tests/test_gpu_device_math.py holds
+ * the results to a high-precision reference.  RSCM_ERR_INVALID: an op outside 0..4, n < 0, x or out NULL, y NULL for op 3.  n == 0
+ * returns RSCM_OK. */
+RSCM_API int rscm_gpu_selftest_math(int32_t op, int64_t n, const double* x, const double* y, double* out);
+
 #ifdef __cplusplus
 }
 #endif

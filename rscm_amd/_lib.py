@@ -377,6 +377,7 @@ SIGNATURES = {
     "rscm_gpu_ocean_fit_selftest": (C.c_int, [C.c_int32, C.c_double, C.c_double, C.c_int64, _dp, _ip, _ip, _ip, _dp]),
     "rscm_ens_ocean_fast_info": (C.c_int, [_h, _ip, _dp]),
     "rscm_gpu_selftest_normal": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, _dp]),
+    "rscm_gpu_selftest_math": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp]),
     "rscm_gpu_selftest_div": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _bp]),
 }
 

@@ -4,8 +4,10 @@
 //   * counter-based Latin hypercube          crates/rscm-calibrate/src/parameter_set.rs:207-233
 //   * fills / row broadcast for collection initialisation (builder.rs:772-780)
 //   * the division self-test behind rscm_gpu_selftest_div
+//   * the logarithm / power / reciprocal self-test behind rscm_gpu_selftest_math
 #include <algorithm>
 
+#include "chem_body.hpp"
 #include "philox.hpp"
 #include "rk4_device.hpp"
 #include "rscm_device.hpp"
@@ -337,6 +339,26 @@ __global__ __launch_bounds__(kBlock) void divtest_kernel(const double* num, cons
     used_fast[i] = const_div_fast_ok(a, c) ? 1 : 0;
 }
 
+// out[i] = one of the hand-written primitives of rk4_device.hpp / chem_body.hpp, or the device library's log / exp, of x[i] (and
+// y[i]); OP as in rscm_gpu_selftest_math.  The functions themselves are called, not restated: with -ffp-contract=off, no fast-math and
+// every FMA written out the compiler has no licence to reassociate or fuse, so this instance and every instance inlined into a kind's
+// kernel perform the same sequence of IEEE operations on the same argument.
+template <int OP>
+__global__ __launch_bounds__(kBlock) void mathtest_kernel(const double* x, const double* y, double* out, int64_t n)
+{
+    const int64_t stride = (int64_t)gridDim.x * kBlock;
+    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
+        const double a = x[i];
+        double r;
+        if constexpr (OP == 0) r = log_f64(a);
+        else if constexpr (OP == 1) r = log(a);
+        else if constexpr (OP == 2) r = exp(a);
+        else if constexpr (OP == 3) r = chem::pow_ratio(a, y[i]);
+        else r = guarded_rcp(a);
+        out[i] = r;
+    }
+}
+
 inline unsigned grid_for(int64_t n, int64_t cap = 2048)
 {
     int64_t b = (n + kBlock - 1) / kBlock;
@@ -476,6 +498,21 @@ hipError_t launch_divtest(const double* num, const double* den, double* out_ref,
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(divtest_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                        s, num, den, out_ref, out_fast, used_fast, n);
+    return hipGetLastError();
+}
+
+hipError_t launch_mathtest(int32_t op, const double* x, const double* y, double* out, int64_t n, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (op < 0 || op >= kMathTestOps || (op == 3 && !y)) return hipErrorInvalidValue;
+    const dim3 grid(stream_grid(n)), block(kBlock);
+    switch (op) {
+    case 0: hipLaunchKernelGGL(mathtest_kernel<0>, grid, block, 0, s, x, y, out, n); break;
+    case 1: hipLaunchKernelGGL(mathtest_kernel<1>, grid, block, 0, s, x, y, out, n); break;
+    case 2: hipLaunchKernelGGL(mathtest_kernel<2>, grid, block, 0, s, x, y, out, n); break;
+    case 3: hipLaunchKernelGGL(mathtest_kernel<3>, grid, block, 0, s, x, y, out, n); break;
+    default: hipLaunchKernelGGL(mathtest_kernel<4>, grid, block, 0, s, x, y, out, n); break;
+    }
     return hipGetLastError();
 }
 

@@ -157,6 +157,7 @@ __device__ __forceinline__ double rk4_combine_fused2(double y, double k1, double
 // the freely distributable fdlibm e_log.c, error < 1 ulp), with the quotient as reciprocal estimate + one Newton step + one
 // correction of the quotient: ~40 instructions.  Same accuracy class as the library's (<= 1 ulp), not the same bits: every use sits in a
 // tolerance-parity kind (tests/test_gpu_parity.py: 1e-11).  Zero, negatives, denormals, inf and NaN take the library's log.
+// tests/test_gpu_device_math.py holds both claims to a high-precision reference on the device, through rscm_gpu_selftest_math.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ double log_f64(double x)
 {

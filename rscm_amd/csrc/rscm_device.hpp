@@ -873,5 +873,9 @@ hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_
 // path used by the kernels, for the parity test of the latter.
 hipError_t launch_divtest(const double* num, const double* den, double* out_ref,
                           double* out_fast, uint8_t* used_fast, int64_t n, hipStream_t s);
+// out[i] = op 0 log_f64(x[i]), 1 the device library's log, 2 its exp, 3 chem::pow_ratio(x[i], y[i]), 4 guarded_rcp(x[i]) (test hook,
+// rscm_gpu_selftest_math); y is read by op 3 only
+constexpr int32_t kMathTestOps = 5;
+hipError_t launch_mathtest(int32_t op, const double* x, const double* y, double* out, int64_t n, hipStream_t s);
 
 }  // namespace rscm

@@ -1891,6 +1891,25 @@ int rscm_gpu_selftest_normal(const uint64_t* k52, int64_t n, double* z)
     GUARD_END
 }
 
+int rscm_gpu_selftest_math(int32_t op, int64_t n, const double* x, const double* y, double* out)
+{
+    GUARD_BEGIN
+    const bool two = op == 3;   // pow_ratio reads y
+    if (op < 0 || op >= rscm::kMathTestOps) return fail(RSCM_ERR_INVALID, "selftest_math: op %d is not in [0, %d)", op, rscm::kMathTestOps);
+    if (n < 0 || !x || !out || (two && !y)) return fail(RSCM_ERR_INVALID, "bad arguments");
+    if (n == 0) return RSCM_OK;
+    double* d = nullptr;   // [n] x, [n] out, then [n] y for the two-argument op
+    HIPCHK(rscm::dev_malloc(&d, (two ? 3 : 2) * (size_t)n * sizeof(double)));
+    hipError_t e = hipMemcpy(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && two) e = hipMemcpy(d + 2 * n, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = rscm::launch_mathtest(op, d, two ? d + 2 * n : nullptr, d + n, n, nullptr);
+    if (e == hipSuccess) e = hipMemcpy(out, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "selftest_math: %s", hipGetErrorString(e));
+    return RSCM_OK;
+    GUARD_END
+}
+
 int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const double* den,
                           double* out_ref, double* out_fast, uint8_t* used_fast)
 {

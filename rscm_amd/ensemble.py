@@ -968,3 +968,16 @@ def selftest_div(num, den, device: int = 0):
     L.check(lib.rscm_gpu_selftest_div(device, a.size, L.dptr(a), L.dptr(b), L.dptr(ref),
                                       L.dptr(fast), L.bptr(used)))
     return ref, fast, used
+
+
+def selftest_math(op: int, x, y=None):
+    """out[i] of op 0 log_f64(x), 1 the device library's log, 2 its exp, 3 chem::pow_ratio(x, y), 4 guarded_rcp(x) on the current
+    device; see rscm_gpu_selftest_math."""
+    lib = L.load()
+    a = L.f64(x).ravel()
+    b = None if y is None else L.f64(y).ravel()
+    if b is not None and b.size != a.size:
+        raise ValueError(f"x has {a.size} elements, y {b.size}")
+    out = np.empty_like(a)
+    L.check(lib.rscm_gpu_selftest_math(int(op), a.size, L.dptr(a), None if b is None else L.dptr(b), L.dptr(out)))
+    return out

@@ -22,7 +22,8 @@ def test_test_hooks_are_not_in_the_public_header():
     public = _declared(("rscm_gpu.h",))
     hooks = _declared(("rscm_gpu_internal.h",))
     assert hooks and not (public & hooks)
-    for name in ("rscm_gpu_set_lockstep_fusion", "rscm_gpu_lockstep_stats", "rscm_gpu_selftest_div", "rscm_gpu_ocean_fit_selftest"):
+    for name in ("rscm_gpu_set_lockstep_fusion", "rscm_gpu_lockstep_stats", "rscm_gpu_selftest_div", "rscm_gpu_ocean_fit_selftest",
+                 "rscm_gpu_selftest_math"):
         assert name in hooks
 
 
