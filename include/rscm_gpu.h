@@ -91,8 +91,9 @@ extern "C" {
  *  12  two-layer mix handles -- per-member forcing as a scaled sum of shared components: rscm_ens_create_mix,
  *      rscm_ens_n_forcing_components, RSCM_TL_P_COEFF0, RSCM_TL_MAX_COMPONENTS
  *  13  seeded forcing noise of a two-layer handle (internal variability): rscm_ens_set_forcing_noise, rscm_ens_clear_forcing_noise,
- *      rscm_ens_forcing_noise, rscm_ens_forcing_noise_rows, RSCM_NOISE_STREAM_TAG */
-#define RSCM_GPU_ABI_MINOR 13
+ *      rscm_ens_forcing_noise, rscm_ens_forcing_noise_rows, RSCM_NOISE_STREAM_TAG
+ *  14  red (AR(1)) forcing noise: rscm_ens_set_forcing_noise_ar1, rscm_ens_forcing_noise_ar1 */
+#define RSCM_GPU_ABI_MINOR 14
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -525,9 +526,40 @@ RSCM_API int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma
 RSCM_API int rscm_ens_clear_forcing_noise(rscm_ens* h);
 /* The setting: *on 1 or 0, and the three numbers (0 when off).  Any pointer may be NULL. */
 RSCM_API int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, double* sigma, int64_t* member_offset);
-/* The term itself: out[(t - t_begin) * N + i] = sigma * z(seed, member_offset + i, t) for t in [t_begin, t_end) within [0, n_times];
+/* The term itself: out[(t - t_begin) * N + i] = sigma * z(seed, member_offset + i, t) for t in [t_begin, t_end) within [0, n_times]
+ * (with red noise, below: e_t, formed from index 0 on);
  * `out` is host memory, or with on_device != 0 device memory filled on the handle's stream.  RSCM_ERR_STATE without noise. */
 RSCM_API int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, double* out, int32_t on_device);
+/* Red forcing noise (ABI minor 14): AR(1) internal variability.  The variability that observations carry is persistent; with
+ * AR(1) noise on, member i of the handle has the global id g = member_offset + i and is forced at forcing-axis index t -- the index
+ * actually read, n + the offset of `source`, as above -- by F'_t = F_t + e_t, F the scenario value or the mix sum formed first.  Every
+ * operation below is rounded on its own, with no FMA, in BOTH arithmetic modes:
+ *     c     = sqrt(1 - phi*phi)                 three roundings
+ *     s_e   = sigma * c
+ *     e_0   = sigma * z(seed, g, 0)             stationary start: Var e_t = sigma^2 at every t
+ *     e_t   = (phi * e_{t-1}) + (s_e * z(seed, g, t))        t >= 1
+ *     F'_t  = F_t + e_t
+ * z is the deviate defined above: its stream tag, its Philox counter layout and the AS241 routine are the white noise's.  e does not
+ * depend on F: a NaN or Inf in F propagates into F' at that index only and leaves the noise of later indices alone.  The persistence
+ * is per forcing-axis index, not per year: on an uneven axis phi is the correlation between consecutive steps, whatever their length.
+ * What is stored is a cache of a pure function.  e_t is a function of (seed, sigma, phi, g, t) alone; the handle keeps one device value
+ * per member, every member's e at one forcing-axis index, and that index (-1: nothing cached).  A run over [step_begin, step_end) first
+ * reads index t0 = step_begin + the offset of `source`: t0 == 0 starts from e_0; a cache that stands at t0 - 1 is loaded; otherwise
+ * e_0 .. e_{t0-1} are formed again from the draws, O(t0) deviates per member, once.  The run leaves e at step_end - 1 + the offset, the
+ * last index drawn.  The index is dropped before a run is issued and set after all of it -- every member block and chunk of steps --
+ * was issued without error, and every setter of the noise drops it.  So rscm_ens_rewind, rscm_ens_set_initial, rscm_ens_set_time_index,
+ * rscm_ens_set_state, a restored checkpoint (which carries sigma, seed, member_offset and phi, not the values) and
+ * rscm_ens_gather_members into the handle need nothing of their own: the next run finds another index than it needs and forms e again,
+ * to the same bits.  rscm_ens_gather_members leaves the destination's noise alone as above: a destination with red noise of its own
+ * realises its own e from index 0, it does not inherit an ancestor's.
+ * phi == 0 IS the white setting: the same kernels and bits as rscm_ens_set_forcing_noise (which sets phi = 0), nothing cached (the
+ * formula's 0 * e term would change signed zeros at sigma == 0).  RSCM_ERR_INVALID: phi not finite or |phi| >= 1, and everything
+ * rscm_ens_set_forcing_noise refuses.  What a noise handle is refused (linking, lock-step, the samplers, the fused likelihood) holds
+ * unchanged, and rscm_ens_clear_forcing_noise clears phi and the cache with the rest. */
+RSCM_API int rscm_ens_set_forcing_noise_ar1(rscm_ens* h, uint64_t seed, double sigma, double phi, int64_t member_offset);
+/* *phi of the setting and *cached_index, the forcing-axis index the cache stands at; 0 and -1 when the noise is off or white.  Either
+ * pointer may be NULL. */
+RSCM_API int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t* cached_index);
 /* Initial value(s) at time index 0 of a state variable: n_values == 1 (broadcast) or N.
  * Also rewinds the time index to 0. */
 /* Linked input: row `input_row` of h's input block is read, member by member, from the stored series

@@ -251,6 +251,8 @@ SIGNATURES = {
     "rscm_ens_n_inputs": (C.c_int, [_h, _ip]),
     "rscm_ens_n_forcing_components": (C.c_int, [_h, _ip]),
     "rscm_ens_set_forcing_noise": (C.c_int, [_h, C.c_uint64, C.c_double, C.c_int64]),
+    "rscm_ens_set_forcing_noise_ar1": (C.c_int, [_h, C.c_uint64, C.c_double, C.c_double, C.c_int64]),
+    "rscm_ens_forcing_noise_ar1": (C.c_int, [_h, _dp, _ip]),
     "rscm_ens_clear_forcing_noise": (C.c_int, [_h]),
     "rscm_ens_forcing_noise": (C.c_int, [_h, _ip, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_int64)]),
     "rscm_ens_forcing_noise_rows": (C.c_int, [_h, C.c_int32, C.c_int32, _dp, C.c_int32]),

@@ -469,6 +469,7 @@ class ModelBuilder:
         self._grid_weights: Dict["GridType", List[float]] = {}
         self._mix: Optional[Tuple[str, Dict[str, Timeseries], Dict[str, float]]] = None   # with_forcing_components
         self._noise: Optional[Tuple[float, int]] = None   # with_forcing_noise: (sigma, seed)
+        self._noise_phi = 0.0                             # ... and its phi (0: white)
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -520,20 +521,24 @@ class ModelBuilder:
                      {n: float((scales or {}).get(n, 1.0)) for n in names})
         return self
 
-    def with_forcing_noise(self, sigma: float, seed: int) -> "ModelBuilder":
+    def with_forcing_noise(self, sigma: float, seed: int, phi: float = 0.0) -> "ModelBuilder":
         """Extension: internal variability.  Where ``build()`` returns the single two-layer ensemble (one ``TwoLayer`` reading
         its exogenous forcing, with or without ``with_forcing_components``), member i is forced by ``F + sigma * z(seed, i, t)``:
         seeded white noise in the heat flux into the upper layer, a pure function of (seed, member, index on the forcing axis)
         (``Ensemble.set_forcing_noise``).  Any other build -- a graph of linked ensembles, ``series_window``, a likelihood-only
         model -- raises ``ValueError``; so do ``ModelRunner`` and ``DeviceEnsembleSampler`` on such a builder: the likelihood of
         one noise realisation per walker is not a target the stretch move samples.  Run the model, score the stored series
-        (``Ensemble.loglik``), weight, resample and branch instead."""
-        sigma, seed = float(sigma), int(seed)
+        (``Ensemble.loglik``), weight, resample and branch instead.  ``phi != 0`` (``|phi| < 1``) makes the noise red: AR(1) with
+        lag-one correlation ``phi`` per index of the forcing axis and variance ``sigma**2`` at every index."""
+        sigma, seed, phi = float(sigma), int(seed), float(phi)
         if not (sigma >= 0.0 and math.isfinite(sigma)):
             raise ValueError(f"with_forcing_noise: sigma must be finite and not negative, got {sigma}")
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"with_forcing_noise: seed must fit 64 unsigned bits, got {seed}")
+        if not (math.isfinite(phi) and abs(phi) < 1.0):
+            raise ValueError(f"with_forcing_noise: phi must be finite with |phi| < 1, got {phi}")
         self._noise = (sigma, seed)
+        self._noise_phi = phi
         return self
 
     def _check_forcing_noise(self, store_series: bool, series_window) -> None:
@@ -593,7 +598,7 @@ class ModelBuilder:
             if vid > 0 and name in self._initial:
                 ens.set_initial(vid, self._initial[name])
         if self._noise is not None:
-            ens.set_forcing_noise(*self._noise)
+            ens.set_forcing_noise(*self._noise, phi=self._noise_phi)
         model = Model(ens, self._axis, sources, endogenous, plan["block"], dict(self._initial), plan["param_order"], plan["base_params"])
         model._builder = self
         return model
@@ -1200,7 +1205,7 @@ class ModelBuilder:
         ens.set_params(np.repeat(np.array(params, dtype=np.float64)[:, None], n_members, axis=1))
         ens.set_forcing(forcing, None, src)
         if self._noise is not None:   # (_check_forcing_noise: this is the two-layer ensemble)
-            ens.set_forcing_noise(*self._noise)
+            ens.set_forcing_noise(*self._noise, phi=self._noise_phi)
         for name, vid in ens.var_ids.items():
             if vid > 0 and name in self._initial:
                 ens.set_initial(vid, self._initial[name])

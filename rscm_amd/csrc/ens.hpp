@@ -119,6 +119,13 @@ struct rscm_ens {
     uint64_t noise_seed = 0;
     double noise_sigma = 0.0;
     int64_t noise_offset = 0;
+    // rscm_ens_set_forcing_noise_ar1 with phi != 0: the red term e_t, a pure function of (seed, sigma, phi, member id, t).  d_noise_state
+    // [N] caches every member's e at forcing-axis index noise_state_index (-1: nothing cached); allocated by the first red setting.
+    // step_launch drops the index before a run's first launch and sets it after the whole run was issued; every setter of the noise
+    // drops it.  A launch that does not find the index before its first re-forms e from the draws
+    double noise_phi = 0.0;
+    double* d_noise_state = nullptr;
+    int32_t noise_state_index = -1;
     int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
     double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;

@@ -361,7 +361,10 @@ struct TwoLayerArgs {
     const int32_t* obs_is_deep;   // [n_obs] 0: Surface Temperature, 1: Deep Ocean Temperature
     const double* obs_value;
     const double* obs_sigma;
-    double* loglik;               // [N]
+    union {
+        double* loglik;           // [N]
+        double* noise_state;      // [N] red noise (below): a stored run scores nothing and the fused likelihood carries no noise
+    };
     // Forcing noise (rscm_ens_set_forcing_noise; the NOISE instantiations: stand-alone stored runs, never linked).  noise_on 1: member
     // i of this launch is forced by F' = F + noise_sigma * z(noise_seed, noise_member0 + i, t) at forcing-axis index t = n + src_off
     // (forcing_noise.hpp).  noise_member0 is the id in the whole ensemble of the launch's first member: the handle's member_offset,
@@ -371,7 +374,17 @@ struct TwoLayerArgs {
     double noise_sigma;
     int64_t noise_member0;
     int32_t noise_on;
+    // Red noise (rscm_ens_set_forcing_noise_ar1 with phi != 0; the NOISE == 2 instantiations): F' = F + e_t with
+    //     e_0 = noise_sigma * z(.., 0),    e_t = noise_phi * e_{t-1} + (noise_sigma * sqrt(1 - noise_phi^2)) * z(.., t),
+    // every operation rounded on its own.  noise_state[i] (above, in the place of the fused likelihood's result: the struct has eight
+    // bytes left of the 240 the op union allows) is member i's slot of the handle's cache, moved with the block like noise_member0.
+    // noise_on kNoiseRedSpinUp: the launch forms e up to the index before its first from the draws (nothing to form when that first
+    // index is 0); kNoiseRedCached: noise_state holds e at the index before its first.  Either way the launch leaves e at the last
+    // index it drew, step_end - 1 + src_off, in noise_state
+    double noise_phi;
 };
+constexpr int32_t kNoiseWhite = 1, kNoiseRedSpinUp = 2, kNoiseRedCached = 3;   // TwoLayerArgs::noise_on (0: no noise)
+static_assert(sizeof(TwoLayerArgs) == 240, "TwoLayerArgs must not grow the fused launches' op union");
 
 // Reference periods of the fused likelihood (launch_two_layer_loglik_ref; DESIGN.md section 7, "Reference periods"), index 0: Surface
 // Temperature, 1: Deep Ocean Temperature.  A variable with on[v] is scored as the anomaly from the member's own mean b over the rows
@@ -708,9 +721,10 @@ inline bool two_layer_fits_lds(int32_t n_scen, int32_t n_comp, int32_t len)
     return two_layer_lds_bytes(n_scen, n_comp, len) <= (size_t)kMaxLds - 1024;
 }
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
-// out[(t - t_begin) * n_members + i] = sigma * z(seed, member0 + i, t) for t in [t_begin, t_end): the term a noise handle adds to its forcing
-hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end,
-                                     double* out, hipStream_t s);
+// out[(t - t_begin) * n_members + i] = sigma * z(seed, member0 + i, t) for t in [t_begin, t_end): the term a noise handle adds to its forcing;
+// with phi != 0 the red term e_t (TwoLayerArgs::noise_phi), formed from index 0 on and written from t_begin on
+hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n_members, int32_t t_begin,
+                                     int32_t t_end, double* out, hipStream_t s);
 // z[j] = the deviate of the 52-bit integer k52[j] (test hook, rscm_gpu_selftest_normal)
 hipError_t launch_normal_selftest(const uint64_t* k52, int64_t n, double* z, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);

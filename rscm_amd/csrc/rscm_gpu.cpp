@@ -762,6 +762,7 @@ int rscm_ens_destroy(rscm_ens* h)
     (void)hipFree(h->d_series);
     (void)hipFree(h->d_forcing);
     (void)hipFree(h->d_scen);
+    (void)hipFree(h->d_noise_state);
     (void)hipFree(h->d_status);
     (void)hipFree(h->d_nsub_tl);
     (void)hipFree(h->d_nsub_cc);
@@ -1814,23 +1815,35 @@ int rscm_ens_ocean_fast_info(rscm_ens* h, int32_t* uses_recurrence, double* fit_
     return RSCM_OK;
 }
 
-int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma, int64_t member_offset)
+int rscm_ens_set_forcing_noise_ar1(rscm_ens* h, uint64_t seed, double sigma, double phi, int64_t member_offset)
 {
     GUARD_BEGIN
     NEED(h);
     if (h->kind != RSCM_KIND_TWO_LAYER)
         return fail(RSCM_ERR_INVALID, "forcing noise is available for the two-layer kind only (RSCM_KIND_TWO_LAYER), this handle has kind %d", h->kind);
     if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(RSCM_ERR_INVALID, "sigma must be finite and not negative, got %g", sigma);
+    if (!std::isfinite(phi) || !(std::fabs(phi) < 1.0)) return fail(RSCM_ERR_INVALID, "phi must be finite with |phi| < 1, got %g", phi);
     if (member_offset < 0) return fail(RSCM_ERR_INVALID, "member_offset must not be negative, got %lld", (long long)member_offset);
     if (h->windowed || h->rows != h->T)
         return fail(RSCM_ERR_INVALID, "forcing noise needs a handle that stores its whole series (no windowed storage, no RSCM_FLAG_NO_SERIES)");
     if (h->n_linked > 0) return fail(RSCM_ERR_INVALID, "this handle has a linked input: the noise is added to a handle's own shared forcing");
+    if (phi != 0.0 && !h->d_noise_state) {   // (phi == 0 is the white setting: the white kernels, no buffer)
+        if (int rc = set_device(h)) return rc;
+        HIPCHK(rscm::dev_malloc(&h->d_noise_state, (size_t)h->N * sizeof(double)));
+    }
     h->noise_on = true;
     h->noise_seed = seed;
     h->noise_sigma = sigma;
+    h->noise_phi = phi == 0.0 ? 0.0 : phi;   // (-0.0 is white too)
     h->noise_offset = member_offset;
+    h->noise_state_index = -1;   // the cache belonged to the setting before
     return RSCM_OK;
     GUARD_END
+}
+
+int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma, int64_t member_offset)
+{
+    return rscm_ens_set_forcing_noise_ar1(h, seed, sigma, 0.0, member_offset);
 }
 
 int rscm_ens_clear_forcing_noise(rscm_ens* h)
@@ -1839,7 +1852,9 @@ int rscm_ens_clear_forcing_noise(rscm_ens* h)
     h->noise_on = false;
     h->noise_seed = 0;
     h->noise_sigma = 0.0;
+    h->noise_phi = 0.0;
     h->noise_offset = 0;
+    h->noise_state_index = -1;
     return RSCM_OK;
 }
 
@@ -1850,6 +1865,15 @@ int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, doubl
     if (seed) *seed = h->noise_seed;
     if (sigma) *sigma = h->noise_sigma;
     if (member_offset) *member_offset = h->noise_offset;
+    return RSCM_OK;
+}
+
+int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t* cached_index)
+{
+    NEED(h);
+    const bool red = h->noise_on && h->noise_phi != 0.0;
+    if (phi) *phi = red ? h->noise_phi : 0.0;
+    if (cached_index) *cached_index = red ? h->noise_state_index : -1;
     return RSCM_OK;
 }
 
@@ -1866,7 +1890,7 @@ int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, dou
     const size_t bytes = (size_t)(t_end - t_begin) * (size_t)h->N * sizeof(double);
     double* d = out;
     if (!on_device) HIPCHK(rscm::dev_malloc(&d, bytes));
-    hipError_t e = rscm::launch_forcing_noise_rows(h->noise_seed, h->noise_sigma, h->noise_offset, h->N, t_begin, t_end, d, h->stream);
+    hipError_t e = rscm::launch_forcing_noise_rows(h->noise_seed, h->noise_sigma, h->noise_phi, h->noise_offset, h->N, t_begin, t_end, d, h->stream);
     if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && !on_device) e = hipStreamSynchronize(h->stream);
     if (!on_device) (void)hipFree(d);

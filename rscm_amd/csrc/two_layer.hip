@@ -45,8 +45,9 @@ namespace {
 __device__ unsigned long long g_guard_counts[tl::kGuardKinds];
 
 // MIX: a mix handle's launch (a.n_comp >= 1): the staged table is [n_scen][n_comp][len], n_scen * n_comp rows laid out like scenarios
-// NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing
-template <int MODE, bool LDS, bool STORE, bool MIX = false, bool NOISE = false>
+// NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing, 1 white,
+// 2 red (a.noise_on kNoiseRedSpinUp or kNoiseRedCached)
+template <int MODE, bool LDS, bool STORE, bool MIX = false, int NOISE = 0>
 __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 {
     extern __shared__ double lds_forcing[];
@@ -76,6 +77,26 @@ __global__ __launch_bounds__(kBlock) void forcing_noise_rows_kernel(uint64_t see
     const uint64_t g = (uint64_t)(member0 + i);
     double* o = out + i;
     for (int32_t t = t_begin; t < t_end; ++t, o += n) *o = sigma * noise::draw(seed, g, (uint32_t)t);
+}
+
+// the same for red noise: e_t of two_layer_body.hpp, formed from index 0 on by the same statements and written from t_begin on
+__global__ __launch_bounds__(kBlock) void forcing_noise_red_rows_kernel(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n,
+                                                                        int32_t t_begin, int32_t t_end, double* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t g = (uint64_t)(member0 + i);
+    double* o = out + i;
+    const double se = sigma * __builtin_sqrt(1.0 - phi * phi);
+    double e = 0.0;
+    for (int32_t t = 0; t < t_end; ++t) {
+        const double z = noise::draw(seed, g, (uint32_t)t);
+        e = t == 0 ? sigma * z : (phi * e) + (se * z);
+        if (t >= t_begin) {
+            *o = e;
+            o += n;
+        }
+    }
 }
 
 __global__ __launch_bounds__(kBlock) void normal_selftest_kernel(const uint64_t* k52, int64_t n, double* z)
@@ -133,12 +154,21 @@ static hipError_t launch_impl(const TwoLayerArgs& a, int mode, hipStream_t s)
                          : (a.lds_forcing ? two_layer_kernel<1, true, STORE> : two_layer_kernel<1, false, STORE>));
     if (a.noise_on) {   // the stored run of a handle that is not linked: the only launch that carries noise
         if constexpr (STORE) {
-            if (a.link) return hipErrorInvalidValue;
-            kern = a.n_comp > 0
-                       ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, true> : two_layer_kernel<0, false, true, true, true>)
-                                    : (a.lds_forcing ? two_layer_kernel<1, true, true, true, true> : two_layer_kernel<1, false, true, true, true>))
-                       : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, true> : two_layer_kernel<0, false, true, false, true>)
-                                    : (a.lds_forcing ? two_layer_kernel<1, true, true, false, true> : two_layer_kernel<1, false, true, false, true>));
+            if (a.link || a.noise_on < kNoiseWhite || a.noise_on > kNoiseRedCached) return hipErrorInvalidValue;
+            if (a.noise_on == kNoiseWhite) {
+                kern = a.n_comp > 0
+                           ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 1> : two_layer_kernel<0, false, true, true, 1>)
+                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 1> : two_layer_kernel<1, false, true, true, 1>))
+                           : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 1> : two_layer_kernel<0, false, true, false, 1>)
+                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 1> : two_layer_kernel<1, false, true, false, 1>));
+            } else {
+                if (!a.noise_state) return hipErrorInvalidValue;
+                kern = a.n_comp > 0
+                           ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 2> : two_layer_kernel<0, false, true, true, 2>)
+                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 2> : two_layer_kernel<1, false, true, true, 2>))
+                           : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 2> : two_layer_kernel<0, false, true, false, 2>)
+                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 2> : two_layer_kernel<1, false, true, false, 2>));
+            }
         } else {
             return hipErrorInvalidValue;
         }
@@ -162,12 +192,13 @@ hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t 
     return launch_impl<false>(a, mode, s);
 }
 
-hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end,
-                                     double* out, hipStream_t s)
+hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n_members, int32_t t_begin,
+                                     int32_t t_end, double* out, hipStream_t s)
 {
     if (n_members <= 0 || t_end <= t_begin) return hipSuccess;
-    hipLaunchKernelGGL(forcing_noise_rows_kernel, dim3((unsigned)((n_members + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, seed, sigma, member0,
-                       n_members, t_begin, t_end, out);
+    const dim3 grid((unsigned)((n_members + kBlock - 1) / kBlock));
+    if (phi == 0.0) hipLaunchKernelGGL(forcing_noise_rows_kernel, grid, dim3(kBlock), 0, s, seed, sigma, member0, n_members, t_begin, t_end, out);
+    else hipLaunchKernelGGL(forcing_noise_red_rows_kernel, grid, dim3(kBlock), 0, s, seed, sigma, phi, member0, n_members, t_begin, t_end, out);
     return hipGetLastError();
 }
 

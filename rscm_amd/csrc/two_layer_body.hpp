@@ -296,14 +296,20 @@ enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuar
 // every product and sum rounded on its own in BOTH arithmetic modes (the file is compiled with -ffp-contract=off and nothing here is
 // written as an FMA).  NaN and Inf propagate, no row is skipped and none is padded with 0 * S (that would change -0.0, NaN and Inf):
 // the loop below is unrolled to eight with a wave-uniform k < K around each term, so the coefficients stay in registers.
-// NOISE (a handle with rscm_ens_set_forcing_noise; stand-alone STORE launches only, never linked): the forcing read at forcing-axis
-// index t = n + a.src_off -- the scenario value, or the mix sum formed first -- becomes
+// NOISE != 0 (a handle with rscm_ens_set_forcing_noise*; stand-alone STORE launches only, never linked): the forcing read at
+// forcing-axis index t = n + a.src_off -- the scenario value, or the mix sum formed first -- becomes, with NOISE == 1 (white),
 //     F' = F + a.noise_sigma * z(a.noise_seed, a.noise_member0 + i, t),
 // product and sum rounded on their own in BOTH modes, z the stateless deviate of forcing_noise.hpp.  forcing_at adds the term, so the
 // draw for year n + 1 is made in the look-ahead slot of year n and the box guard and the replay see F' like any forcing.  A Philox
 // block serves an even index and the odd one after it: the second pair of words waits in two registers for the next year (which
 // index they serve is wave-uniform), so the ten rounds run every other year.
-template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, bool NOISE = false>
+// NOISE == 2 (red, a.noise_phi != 0): F' = F + e_t with e_0 = sigma z_0 and e_t = (phi e_{t-1}) + ((sigma sqrt(1 - phi phi)) z_t), each
+// operation rounded on its own.  forcing_at is called once per index in ascending order, so e lives in a register and a year costs
+// two multiplies and an add on top of the white draw.  Before the year loop e is brought to the index before the launch's first:
+// loaded from a.noise_state (a.noise_on == kNoiseRedCached) or formed from index 0 on by the same statements as in the loop (a
+// wave-uniform trip count; the bits of the per-index definition by construction).  The launch ends with one store of e, which then
+// stands at the last index drawn, step_end - 1 + a.src_off.
+template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, int NOISE = 0>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
                                                int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
 {
@@ -343,8 +349,7 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
     [[maybe_unused]] const uint64_t noise_g = NOISE ? (uint64_t)(a.noise_member0 + i) : 0;
     [[maybe_unused]] uint32_t noise_lo = 0, noise_hi = 0;
     [[maybe_unused]] int32_t noise_t = -1;   // wave-uniform
-    [[maybe_unused]] auto noisy = [&](int32_t n, double f) -> double {
-        const int32_t t = n + a.src_off;
+    [[maybe_unused]] auto noise_z = [&](int32_t t) -> double {   // z(seed, g, t)
         uint32_t lo, hi;
         if (t == noise_t) {
             lo = noise_lo;
@@ -363,7 +368,29 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
                 noise_t = t + 1;
             }
         }
-        return f + a.noise_sigma * noise::normal_from_k(noise::k_of(lo, hi));
+        return noise::normal_from_k(noise::k_of(lo, hi));
+    };
+    // red noise: e at the last index drawn, and sigma sqrt(1 - phi^2) (three roundings, then the product)
+    constexpr bool RED = NOISE == 2;
+    [[maybe_unused]] double red_e = 0.0;
+    [[maybe_unused]] const double red_se = RED ? a.noise_sigma * __builtin_sqrt(1.0 - a.noise_phi * a.noise_phi) : 0.0;
+    [[maybe_unused]] auto red_advance = [&](int32_t t) {   // e_{t-1} -> e_t
+        const double z = noise_z(t);
+        red_e = t == 0 ? a.noise_sigma * z : (a.noise_phi * red_e) + (red_se * z);
+    };
+    if constexpr (RED) {
+        if (a.noise_on == kNoiseRedCached) red_e = a.noise_state[i];
+        else
+            for (int32_t t = 0, t0 = step_begin + a.src_off; t < t0; ++t) red_advance(t);
+    }
+    [[maybe_unused]] auto noisy = [&](int32_t n, double f) -> double {
+        const int32_t t = n + a.src_off;
+        if constexpr (RED) {
+            red_advance(t);
+            return f + red_e;
+        } else {
+            return f + a.noise_sigma * noise_z(t);
+        }
     };
     auto forcing_at = [&](int32_t n) -> double {
         if constexpr (MIX) {
@@ -523,6 +550,7 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
         }
     }
     if (cache.last_step()) a.status[i] = (is_finite(ts) && is_finite(td)) ? 0 : 1;
+    if constexpr (RED) a.noise_state[i] = red_e;
     if constexpr (!STORE) {
         // observations whose row is never reached were never computed -> member failure
         if (lik.oi < a.n_obs) lik.bad = true;

@@ -294,10 +294,10 @@ class ShardedEnsemble:
     def sample_lhs(self, seed: int, low, high) -> None:
         self.ensemble.sample_lhs(seed, low, high, self.offset, self.n_total)
 
-    def set_forcing_noise(self, sigma: float, seed: int) -> None:
-        """Forcing noise of the global ensemble (``Ensemble.set_forcing_noise``): the shard's first member is the offset, so a
-        member draws the same variability whichever rank holds it."""
-        self.ensemble.set_forcing_noise(sigma, seed, self.offset)
+    def set_forcing_noise(self, sigma: float, seed: int, phi: float = 0.0) -> None:
+        """Forcing noise of the global ensemble (``Ensemble.set_forcing_noise``, red with ``phi != 0``): the shard's first member
+        is the offset, so a member draws the same variability whichever rank holds it."""
+        self.ensemble.set_forcing_noise(sigma, seed, self.offset, phi)
 
     def set_params_global(self, soa: np.ndarray) -> None:
         self.ensemble.set_params(np.ascontiguousarray(soa[:, self.offset:self.offset + self.count]))

@@ -189,30 +189,53 @@ class Ensemble:
         L.check(self._lib.rscm_ens_set_forcing(self._h, self._var(var), s.shape[0], L.dptr(s),
                                                L.iptr(sc), source))
 
-    def set_forcing_noise(self, sigma: float, seed: int, member_offset: int = 0) -> None:
+    def set_forcing_noise(self, sigma: float, seed: int, member_offset: int = 0, phi: float = 0.0) -> None:
         """Internal variability (two-layer kind, mix ensembles included): member i is forced at forcing-axis index t by
         ``F + sigma * z(seed, member_offset + i, t)``, z a standard normal deviate that is a pure function of its three
         arguments (``rscm_ens_set_forcing_noise``) -- white in t, independent between members, the same whatever way the run is
         cut, rewound, checkpointed or branched.  ``member_offset`` is the global index of this ensemble's first member (a shard
         passes its own).  The fused ``run_loglik``, ``link_input``, ``run_lockstep`` and the device sampler refuse such an
-        ensemble; ``run()`` followed by ``loglik()`` scores it."""
+        ensemble; ``run()`` followed by ``loglik()`` scores it.
+
+        ``phi != 0`` (``|phi| < 1``) makes the noise red (``rscm_ens_set_forcing_noise_ar1``): ``F + e_t`` with
+        ``e_0 = sigma * z_0`` and ``e_t = phi * e_{t-1} + sigma * sqrt(1 - phi**2) * z_t``, variance ``sigma**2`` at every index
+        and lag-one correlation ``phi`` per forcing-axis index.  e is as pure a function as z; the ensemble caches each member's
+        value at the last index it ran (``forcing_noise_cached_index``) and forms it again from the draws wherever a run starts
+        elsewhere.  ``phi=0.0`` is the white setting, bit for bit."""
         seed = int(seed)
         if not 0 <= seed < 1 << 64:
             raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
-        L.check(self._lib.rscm_ens_set_forcing_noise(self._h, C.c_uint64(seed), float(sigma), int(member_offset)))
+        L.check(self._lib.rscm_ens_set_forcing_noise_ar1(self._h, C.c_uint64(seed), float(sigma), float(phi), int(member_offset)))
 
     def clear_forcing_noise(self) -> None:
         L.check(self._lib.rscm_ens_clear_forcing_noise(self._h))
 
     @property
     def forcing_noise(self) -> Optional[Dict[str, object]]:
-        """``{"sigma", "seed", "member_offset"}`` of ``set_forcing_noise``, or None without noise."""
-        on, seed, sigma, off = C.c_int32(), C.c_uint64(), C.c_double(), C.c_int64()
+        """``{"sigma", "seed", "member_offset"}`` of ``set_forcing_noise``, and ``"phi"`` where the noise is red (``phi != 0``);
+        None without noise."""
+        on, seed, sigma, off, phi = C.c_int32(), C.c_uint64(), C.c_double(), C.c_int64(), C.c_double()
         L.check(self._lib.rscm_ens_forcing_noise(self._h, C.byref(on), C.byref(seed), C.byref(sigma), C.byref(off)))
-        return {"sigma": sigma.value, "seed": seed.value, "member_offset": off.value} if on.value else None
+        if not on.value:
+            return None
+        L.check(self._lib.rscm_ens_forcing_noise_ar1(self._h, C.byref(phi), None))
+        noise = {"sigma": sigma.value, "seed": seed.value, "member_offset": off.value}
+        if phi.value != 0.0:
+            noise["phi"] = phi.value
+        return noise
+
+    @property
+    def forcing_noise_cached_index(self) -> int:
+        """The forcing-axis index at which the red noise's per-member values are cached, -1 when nothing is (white or no noise,
+        after any setter of the noise, before the first run): a run that starts right after it loads them, any other forms them
+        again from the draws."""
+        at = C.c_int32()
+        L.check(self._lib.rscm_ens_forcing_noise_ar1(self._h, None, C.byref(at)))
+        return at.value
 
     def forcing_noise_rows(self, t_begin: int = 0, t_end: Optional[int] = None) -> np.ndarray:
-        """``[t_end - t_begin][N]``: the term ``sigma * z`` the members' forcing gets at forcing-axis indices ``t_begin .. t_end - 1``."""
+        """``[t_end - t_begin][N]``: the term the members' forcing gets at forcing-axis indices ``t_begin .. t_end - 1``: ``sigma * z``,
+        or ``e`` of the red noise."""
         t_end = self.n_times if t_end is None else int(t_end)
         out = np.empty((max(t_end - int(t_begin), 0), self.n_members))
         L.check(self._lib.rscm_ens_forcing_noise_rows(self._h, int(t_begin), t_end, L.dptr(out), 0))
@@ -343,8 +366,10 @@ class Ensemble:
               "state": {name: self.get_series(v, k, k + 1)[0] for name, v in names.items()},
               "history": history, "internal": internal}
         noise = self.forcing_noise if self.kind == L.KIND_TWO_LAYER else None
-        if noise is not None:   # (stateless: the three numbers are all there is to carry)
+        if noise is not None:   # (a pure function of these numbers: the red noise's cached values are not carried)
             ck["forcing_noise"] = {"sigma": noise["sigma"], "seed": np.uint64(noise["seed"]), "member_offset": noise["member_offset"]}
+            if "phi" in noise:
+                ck["forcing_noise"]["phi"] = noise["phi"]
         return ck
 
     def restore(self, ck: Dict[str, object], clear_later_rows: bool = False) -> None:
@@ -360,7 +385,7 @@ class Ensemble:
             if noise is None:
                 self.clear_forcing_noise()
             else:
-                self.set_forcing_noise(float(noise["sigma"]), int(noise["seed"]), int(noise["member_offset"]))
+                self.set_forcing_noise(float(noise["sigma"]), int(noise["seed"]), int(noise["member_offset"]), float(noise.get("phi", 0.0)))
         k = int(ck["time_index"])
         # the stepper first: a windowed ensemble positions its window at k, then the rows go in
         internal = ck.get("internal")

@@ -3,7 +3,12 @@ noise on and off, in alternation.  Device-event times (rscm_ens_last_run_ms), tw
 median and the minimum are printed, and the ratio of the medians.  The draw is a Philox block every other year and an AS241
 deviate every year, on top of a year of ten RK4 sub-steps.  profiles/forcing_noise_bench.txt holds one output of this script.
 
-    python scripts/bench_forcing_noise.py [--runs 10] [--sizes 100000 1000000]"""
+With --phi the red (AR(1)) noise joins: off, white and red on the same handle in alternation, red against white as the ratio of the
+medians beside the white runs' own min-max spread, and one spin-up -- the second half of the axis run from index 375 with the
+red noise's cache in place and with it dropped (the launch then forms e_0 .. e_374 from the draws first).
+profiles/forcing_noise_red_bench.txt holds one such output.
+
+    python scripts/bench_forcing_noise.py [--runs 10] [--sizes 100000 1000000] [--phi 0.7]"""
 import argparse
 import os
 import sys
@@ -34,16 +39,34 @@ def ensemble(n, K, mode):
     return e
 
 
-def timed(e, runs):
-    """{"off": [ms], "on": [ms]} of one handle: two warm-up rounds, then `runs` rounds of off, on."""
-    out = {"off": [], "on": []}
+def timed(e, runs, phi=0.0):
+    """{"off": [ms], "on": [ms][, "red": [ms]]} of one handle: two warm-up rounds, then `runs` rounds of off, on[, red]."""
+    names = ("off", "on", "red") if phi else ("off", "on")
+    out = {name: [] for name in names}
     for r in range(runs + 2):
-        for name in ("off", "on"):
-            if name == "on":
-                e.set_forcing_noise(SIGMA, SEED)
-            else:
+        for name in names:
+            if name == "off":
                 e.clear_forcing_noise()
+            else:
+                e.set_forcing_noise(SIGMA, SEED, 0, phi if name == "red" else 0.0)
             e.rewind()
+            e.run()
+            if r >= 2:
+                out[name].append(e.last_run_ms())
+    return out
+
+
+def spin_up(e, runs, phi, at=375):
+    """{"cached": [ms], "spun up": [ms]}: run() from index `at` after run(at), the red noise's cache left in place or dropped."""
+    out = {"cached": [], "spun up": []}
+    e.set_forcing_noise(SIGMA, SEED, 0, phi)
+    for r in range(runs + 2):
+        for name in out:
+            e.rewind()
+            e.run(at)
+            if name == "spun up":
+                e.set_forcing_noise(SIGMA, SEED, 0, phi)   # any setter of the noise drops the cache
+            assert e.forcing_noise_cached_index == (at - 1 if name == "cached" else -1)
             e.run()
             if r >= 2:
                 out[name].append(e.last_run_ms())
@@ -54,19 +77,29 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10)
     ap.add_argument("--sizes", type=int, nargs="+", default=[100000, 1000000])
+    ap.add_argument("--phi", type=float, default=0.0, help="also time the red noise with this lag-one correlation, and one spin-up")
     a = ap.parse_args()
     for n in a.sizes:
         for mode, mode_name in ((rscm_amd.MODE_EXACT, "EXACT"), (rscm_amd.MODE_FAST, "FAST")):
             for K, what in ((0, "plain two-layer"), (4, "mix K=4")):
                 e = ensemble(n, K, mode)
-                ms = timed(e, a.runs)
+                ms = timed(e, a.runs, a.phi)
                 blocks, chunks = e.last_run_plan()
+                spin = spin_up(e, a.runs, a.phi) if a.phi else None
                 e.close()
                 off, on = np.asarray(ms["off"]), np.asarray(ms["on"])
                 print(f"{n} members x {T - 1} steps, {mode_name}, {what} (noise run cut into {blocks} block(s) x {chunks} chunk(s))")
                 print(f"  noise off  median {np.median(off):9.3f} ms   min {off.min():9.3f} ms   ({off.size} runs)")
                 print(f"  noise on   median {np.median(on):9.3f} ms   min {on.min():9.3f} ms   ({on.size} runs)   "
                       f"x{np.median(on) / np.median(off):.3f} of off   {n * (T - 1) / np.median(on) * 1e3:.3e} member-years/s", flush=True)
+                if a.phi:
+                    red = np.asarray(ms["red"])
+                    print(f"  red {a.phi:+.2f}  median {np.median(red):9.3f} ms   min {red.min():9.3f} ms   ({red.size} runs)   "
+                          f"x{np.median(red) / np.median(on):.3f} of white (white runs {on.min():.3f} .. {on.max():.3f} ms)   "
+                          f"{n * (T - 1) / np.median(red) * 1e3:.3e} member-years/s")
+                    c, u = np.asarray(spin["cached"]), np.asarray(spin["spun up"])
+                    print(f"  steps 375..749: cache in place median {np.median(c):9.3f} ms, dropped {np.median(u):9.3f} ms "
+                          f"(+{np.median(u) - np.median(c):.3f} ms for 375 deviates per member)", flush=True)
 
 
 if __name__ == "__main__":
