@@ -92,8 +92,10 @@ extern "C" {
  *      rscm_ens_n_forcing_components, RSCM_TL_P_COEFF0, RSCM_TL_MAX_COMPONENTS
  *  13  seeded forcing noise of a two-layer handle (internal variability): rscm_ens_set_forcing_noise, rscm_ens_clear_forcing_noise,
  *      rscm_ens_forcing_noise, rscm_ens_forcing_noise_rows, RSCM_NOISE_STREAM_TAG
- *  14  red (AR(1)) forcing noise: rscm_ens_set_forcing_noise_ar1, rscm_ens_forcing_noise_ar1 */
-#define RSCM_GPU_ABI_MINOR 14
+ *  14  red (AR(1)) forcing noise: rscm_ens_set_forcing_noise_ar1, rscm_ens_forcing_noise_ar1
+ *  15  per-member noise amplitude and persistence as parameter rows: RSCM_FLAG_NOISE_PARAMS, RSCM_TL_P_NOISE_SIGMA, RSCM_TL_P_NOISE_PHI,
+ *      rscm_ens_set_forcing_noise_members, rscm_ens_forcing_noise_members */
+#define RSCM_GPU_ABI_MINOR 15
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -378,6 +380,10 @@ extern "C" {
  * are the members' coefficients c_0 .. c_K-1 of the components. */
 #define RSCM_TL_P_COEFF0 6
 #define RSCM_TL_MAX_COMPONENTS 8
+/* A two-layer handle created with RSCM_FLAG_NOISE_PARAMS (plain: K = 0, or mix with K components) has two more rows after the
+ * coefficients, P = 6 + K + 2: every member's noise amplitude sigma_i and persistence phi_i (rscm_ens_set_forcing_noise_members). */
+#define RSCM_TL_P_NOISE_SIGMA(K) (RSCM_TL_P_COEFF0 + (K))
+#define RSCM_TL_P_NOISE_PHI(K) (RSCM_TL_P_COEFF0 + (K) + 1)
 
 /* VariableSource of the shared input as seen by its consumer (state/mod.rs:156-170) */
 #define RSCM_SRC_EXOGENOUS 0 /* read index n   */
@@ -429,6 +435,11 @@ RSCM_API int rscm_ens_create(int32_t kind, int64_t n_members, int32_t n_times, c
  * row of every state series -- for likelihood-only work through rscm_ens_run_loglik, where no
  * time series is ever written to HBM (12 GB per 1e6 members otherwise). */
 #define RSCM_FLAG_NO_SERIES 1u
+/* RSCM_FLAG_NOISE_PARAMS (ABI minor 15; rscm_ens_create_ex with RSCM_KIND_TWO_LAYER, and rscm_ens_create_mix): the handle gets the two
+ * parameter rows RSCM_TL_P_NOISE_SIGMA(K) and RSCM_TL_P_NOISE_PHI(K) that rscm_ens_set_forcing_noise_members reads (described there).
+ * RSCM_ERR_INVALID with any other kind, and together with RSCM_FLAG_NO_SERIES or RSCM_FLAG_WINDOWED: the noise needs stored series, so
+ * the rows could never be read. */
+#define RSCM_FLAG_NOISE_PARAMS 4u
 RSCM_API int rscm_ens_create_ex(int32_t kind, int64_t n_members, int32_t n_times,
                                 const double* time_bounds, int32_t device_id, uint32_t flags,
                                 rscm_ens** out);
@@ -460,7 +471,8 @@ RSCM_API int rscm_ens_create_windowed(int32_t kind, int64_t n_members, int32_t n
  * The coefficients c_k are parameter rows RSCM_TL_P_COEFF0 + k of the handle: rscm_ens_n_params reports 6 + K, and every call that
  * moves parameter rows (rscm_ens_set_params / _aos, rscm_ens_get_params, rscm_ens_params_devptr, rscm_ens_sample_lhs with 6 + K bounds,
  * the samplers' param_rows, rscm_ens_gather_members) carries them.  rscm_ens_n_inputs reports K.
- * kind must be RSCM_KIND_TWO_LAYER; flags 0 or RSCM_FLAG_NO_SERIES (no windowed storage); n_components in [1, RSCM_TL_MAX_COMPONENTS];
+ * kind must be RSCM_KIND_TWO_LAYER; flags 0, RSCM_FLAG_NO_SERIES or RSCM_FLAG_NOISE_PARAMS (no windowed storage, and not the two
+ * together); n_components in [1, RSCM_TL_MAX_COMPONENTS];
  * anything else is RSCM_ERR_INVALID.  A mix handle runs on its own: rscm_ens_link_input onto it, rscm_ens_run_lockstep and
  * rscm_sampler_create_graph with it, and rscm_ens_gather_members between handles of different component counts return
  * RSCM_ERR_INVALID (rscm_sampler_create takes it as the one evaluator). */
@@ -560,6 +572,51 @@ RSCM_API int rscm_ens_set_forcing_noise_ar1(rscm_ens* h, uint64_t seed, double s
 /* *phi of the setting and *cached_index, the forcing-axis index the cache stands at; 0 and -1 when the noise is off or white.  Either
  * pointer may be NULL. */
 RSCM_API int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t* cached_index);
+/* Per-member forcing noise (ABI minor 15): amplitude and persistence as parameter rows.  How much internal variability the system has,
+ * and how persistent it is, is as uncertain as any model parameter.  A two-layer handle created with RSCM_FLAG_NOISE_PARAMS (plain, K = 0,
+ * or mix with K components) carries member i's sigma_i in parameter row RSCM_TL_P_NOISE_SIGMA(K) = 6 + K and phi_i in row
+ * RSCM_TL_P_NOISE_PHI(K) = 6 + K + 1: rscm_ens_n_params reports 6 + K + 2, and every call that moves parameter rows carries the two
+ * rows like any other (rscm_ens_set_params / _aos, rscm_ens_get_params, rscm_ens_params_devptr, rscm_ens_sample_lhs with 6 + K + 2 bounds,
+ * rscm_ens_params_vector, rscm_ens_gather_members -- so the draws of a posterior inherit their ancestors' amplitude and persistence).
+ * rscm_ens_gather_members between a handle with the rows and one without is RSCM_ERR_INVALID, like differing component counts.
+ * With the per-member noise on, member i has the global id g = member_offset + i and is forced at forcing-axis index t by
+ * F'_t = F_t + e_t, F the scenario value or the mix sum formed first, where
+ *     c_i   = sqrt(1 - phi_i*phi_i)             three roundings
+ *     s_i   = sigma_i * c_i
+ *     e_0   = sigma_i * z(seed, g, 0)
+ *     e_t   = (phi_i * e_{t-1}) + (s_i * z(seed, g, t))        t >= 1
+ *     F'_t  = F_t + e_t
+ * -- every operation an IEEE f64 operation rounded on its own, with no FMA, in BOTH arithmetic modes; z is the deviate defined above,
+ * untouched.  This is the red formula, and it is used for every member, phi_i == 0 included: such a member gets the white VALUES
+ * sigma_i * z, and its forcing differs from the white setting's only in the sign of a zero ((0 * e) + (sigma_i z) where sigma_i z is a
+ * zero: -0.0 under the white setting can be +0.0 here).  With all rows uniform and phi != 0 the bits are those of
+ * rscm_ens_set_forcing_noise_ar1 with the same numbers.
+ * The rows are data (rscm_ens_sample_lhs fills them on the device), so nothing validates them: what the formula gives is what is
+ * defined, the rule for forcing ("NaN and Inf propagate") applied to these two rows.  A NaN or Inf in either row, or |phi_i| > 1 (the
+ * square root of a negative number), gives that member NaN forcing: its states are NaN and bit 0 of its status is set.  |phi_i| == 1
+ * gives s_i = 0 and a constant (phi_i = 1) or alternating (phi_i = -1) e.  A negative sigma_i mirrors the noise.  None of these touches
+ * another member.
+ * A handle with the flag and the noise OFF, or under rscm_ens_set_forcing_noise / _ar1, behaves exactly like one without the flag: the
+ * same kernels, the same bits, the two rows inert, and it is accepted wherever an unflagged handle is (links, lock-step, the samplers,
+ * the fused likelihood).
+ * rscm_ens_set_forcing_noise_members turns the per-member noise on.  RSCM_ERR_INVALID on a handle without the flag, and for everything
+ * rscm_ens_set_forcing_noise refuses (member_offset < 0, a linked input).  What a noise handle is refused holds unchanged (linking,
+ * lock-step, the samplers, the fused rscm_ens_run_loglik*).  rscm_ens_clear_forcing_noise turns it off; the handle-wide setters
+ * replace it and it replaces them.
+ * THE CACHE.  Here e_t is a function of (seed, sigma_i, phi_i, g, t) with the rows AS THEY STAND AT LAUNCH, so the cache of the red
+ * noise (one value per member and the index it stands at, above) is only valid while the rows are.  In this mode the cached index is
+ * dropped by everything that can change a parameter row:
+ *     rscm_ens_set_params, rscm_ens_set_params_aos, rscm_ens_sample_lhs, rscm_ens_gather_members into the handle
+ *     (a restored checkpoint sets the parameters, so it is among them),
+ * and for good once rscm_ens_params_devptr has been handed out: the caller may then write the rows at any time, so such a handle never
+ * trusts the cache across calls -- every run forms e again from index 0, and the index reads -1 after every run.  The chunks and
+ * member blocks INSIDE one run still hand e over through the cache as they do for the handle-wide red noise. */
+RSCM_API int rscm_ens_set_forcing_noise_members(rscm_ens* h, uint64_t seed, int64_t member_offset);
+/* *per_member: 1 while rscm_ens_set_forcing_noise_members is in force, else 0.  *sigma_row and *phi_row: the two parameter rows of a
+ * handle created with RSCM_FLAG_NOISE_PARAMS (whether the noise is on or not), -1 on any other handle.  Any pointer may be NULL.
+ * In this mode rscm_ens_forcing_noise reports on, seed, member_offset and sigma = 0, rscm_ens_forcing_noise_ar1 reports phi = 0 and
+ * the cached index, and rscm_ens_forcing_noise_rows returns e formed from the rows as they stand. */
+RSCM_API int rscm_ens_forcing_noise_members(const rscm_ens* h, int32_t* per_member, int32_t* sigma_row, int32_t* phi_row);
 /* Initial value(s) at time index 0 of a state variable: n_values == 1 (broadcast) or N.
  * Also rewinds the time index to 0. */
 /* Linked input: row `input_row` of h's input block is read, member by member, from the stored series

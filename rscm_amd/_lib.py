@@ -28,6 +28,7 @@ COMP_TWO_LAYER, COMP_CARBON_CYCLE = 0, 1
 MODE_EXACT, MODE_FAST = 0, 1
 FLAG_NO_SERIES = 1
 FLAG_WINDOWED = 2
+FLAG_NOISE_PARAMS = 4    # RSCM_FLAG_NOISE_PARAMS: two more two-layer parameter rows, the members' noise sigma and phi
 TL_P_COEFF0 = 6          # a mix ensemble's coefficient rows start here (RSCM_TL_P_COEFF0)
 TL_MAX_COMPONENTS = 8    # RSCM_TL_MAX_COMPONENTS
 NOISE_STREAM_TAG = 0x4E5A   # RSCM_NOISE_STREAM_TAG: the Philox stream of the forcing noise
@@ -253,6 +254,8 @@ SIGNATURES = {
     "rscm_ens_set_forcing_noise": (C.c_int, [_h, C.c_uint64, C.c_double, C.c_int64]),
     "rscm_ens_set_forcing_noise_ar1": (C.c_int, [_h, C.c_uint64, C.c_double, C.c_double, C.c_int64]),
     "rscm_ens_forcing_noise_ar1": (C.c_int, [_h, _dp, _ip]),
+    "rscm_ens_set_forcing_noise_members": (C.c_int, [_h, C.c_uint64, C.c_int64]),
+    "rscm_ens_forcing_noise_members": (C.c_int, [_h, _ip, _ip, _ip]),
     "rscm_ens_clear_forcing_noise": (C.c_int, [_h]),
     "rscm_ens_forcing_noise": (C.c_int, [_h, _ip, C.POINTER(C.c_uint64), _dp, C.POINTER(C.c_int64)]),
     "rscm_ens_forcing_noise_rows": (C.c_int, [_h, C.c_int32, C.c_int32, _dp, C.c_int32]),

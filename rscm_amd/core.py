@@ -470,6 +470,7 @@ class ModelBuilder:
         self._mix: Optional[Tuple[str, Dict[str, Timeseries], Dict[str, float]]] = None   # with_forcing_components
         self._noise: Optional[Tuple[float, int]] = None   # with_forcing_noise: (sigma, seed)
         self._noise_phi = 0.0                             # ... and its phi (0: white)
+        self._noise_params = False                        # with_forcing_noise_parameters: sigma and phi are parameter rows
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -539,7 +540,50 @@ class ModelBuilder:
             raise ValueError(f"with_forcing_noise: phi must be finite with |phi| < 1, got {phi}")
         self._noise = (sigma, seed)
         self._noise_phi = phi
+        self._noise_params = False
         return self
+
+    NOISE_PARAM_NAMES = ("forcing_noise|sigma", "forcing_noise|phi")
+
+    def with_forcing_noise_parameters(self, seed: int, sigma: float = 0.0, phi: float = 0.0) -> "ModelBuilder":
+        """Extension: internal variability whose amplitude and persistence are PARAMETERS.  As ``with_forcing_noise``, but the
+        two-layer ensemble is made with ``noise_params=True`` and ``"forcing_noise|sigma"`` and ``"forcing_noise|phi"`` are
+        appended to ``Model.param_order`` and ``base_params`` (after any ``forcing_scale|*``), with ``sigma`` and ``phi`` as their
+        base values: every member is forced with its own ``sigma_i`` and ``phi_i`` (``Ensemble.set_forcing_noise_members``), so
+        ``sample_lhs`` bounds, ``set_params`` and the posterior take the two like any parameter.  The base values are validated
+        as ``with_forcing_noise`` validates its own; values set later are data (``Ensemble.set_forcing_noise_members``).  The
+        refusals of ``with_forcing_noise`` apply unchanged, ``ModelRunner`` and ``DeviceEnsembleSampler`` included."""
+        self.with_forcing_noise(sigma, seed, phi)
+        self._noise_params = True
+        return self
+
+    def _with_noise_params(self, param_order, base_params):
+        """``param_order`` and ``base_params`` with the two noise parameters appended where ``with_forcing_noise_parameters`` asked."""
+        if not self._noise_params:
+            return tuple(param_order), np.array(base_params, dtype=np.float64)
+        return (tuple(param_order) + self.NOISE_PARAM_NAMES,
+                np.append(np.array(base_params, dtype=np.float64), [self._noise[0], self._noise_phi]))
+
+    def _set_noise(self, ens: Ensemble) -> None:
+        if self._noise is None:
+            return
+        if self._noise_params:
+            ens.set_forcing_noise_members(self._noise[1])
+        else:
+            ens.set_forcing_noise(*self._noise, phi=self._noise_phi)
+
+    def forcing_noise_plan(self, store_series: bool = True, series_window=None) -> Optional[Dict[str, object]]:
+        """What ``build()`` makes of ``with_forcing_noise*`` (None without it), formed on the host: ``per_member``, ``seed`` and the
+        ``param_order`` and ``base_params`` of the model.  Raises ``ValueError`` where ``build()`` would."""
+        if self._noise is None:
+            return None
+        self._check_forcing_noise(store_series, series_window)
+        mix = self.forcing_mix_plan()
+        if mix is not None:
+            order, base = mix["param_order"], mix["base_params"]
+        else:
+            order, base = self._with_noise_params(TL_PARAM_ORDER, [self._components[0].parameters[k] for k in TL_PARAM_ORDER])
+        return {"per_member": self._noise_params, "seed": self._noise[1], "param_order": order, "base_params": base}
 
     def _check_forcing_noise(self, store_series: bool, series_window) -> None:
         """Raises ``ValueError`` unless ``build()`` with these arguments yields the single two-layer (or mix) ensemble with
@@ -583,22 +627,21 @@ class ModelBuilder:
             rows.append(ts.interpolate_into(self._axis).values())
         names = tuple(components)
         base = [self._components[0].parameters[k] for k in TL_PARAM_ORDER] + [scales[n] for n in names]
-        return {"names": names, "param_order": TL_PARAM_ORDER + tuple(f"forcing_scale|{n}" for n in names),
-                "base_params": np.array(base, dtype=np.float64), "block": np.stack(rows)}
+        order, base = self._with_noise_params(TL_PARAM_ORDER + tuple(f"forcing_scale|{n}" for n in names), base)
+        return {"names": names, "param_order": order, "base_params": base, "block": np.stack(rows)}
 
     def _build_mix(self, n_members: int, store_series: bool) -> "Model":
         plan = self.forcing_mix_plan()
         endogenous, sources, _, _ = self._resolve()
         ens = Ensemble(L.KIND_TWO_LAYER, n_members, self._axis.bounds(), device=self._device, store_series=store_series,
-                       forcing_components=plan["names"])
+                       forcing_components=plan["names"], noise_params=self._noise_params)
         ens.set_step_size(L.COMP_TWO_LAYER, 0.1)
         ens.set_params(np.repeat(plan["base_params"][:, None], n_members, axis=1))
         ens.set_forcing(plan["block"][None], None, L.SRC_EXOGENOUS)
         for name, vid in ens.var_ids.items():
             if vid > 0 and name in self._initial:
                 ens.set_initial(vid, self._initial[name])
-        if self._noise is not None:
-            ens.set_forcing_noise(*self._noise, phi=self._noise_phi)
+        self._set_noise(ens)
         model = Model(ens, self._axis, sources, endogenous, plan["block"], dict(self._initial), plan["param_order"], plan["base_params"])
         model._builder = self
         return model
@@ -1198,14 +1241,16 @@ class ModelBuilder:
             return self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order)
         if not store_series and kind != L.KIND_TWO_LAYER:
             store_series = True  # likelihood-only handles exist for the two-layer kind
+        noise_params = self._noise is not None and self._noise_params   # (_check_forcing_noise: this is the two-layer ensemble)
+        if noise_params:
+            _, params = self._with_noise_params((), params)
         ens = Ensemble(kind, n_members, self._axis.bounds(), device=self._device,
-                       store_series=store_series)
+                       store_series=store_series, noise_params=noise_params)
         for comp_id, step in h.items():
             ens.set_step_size(comp_id, step)
         ens.set_params(np.repeat(np.array(params, dtype=np.float64)[:, None], n_members, axis=1))
         ens.set_forcing(forcing, None, src)
-        if self._noise is not None:   # (_check_forcing_noise: this is the two-layer ensemble)
-            ens.set_forcing_noise(*self._noise, phi=self._noise_phi)
+        self._set_noise(ens)
         for name, vid in ens.var_ids.items():
             if vid > 0 and name in self._initial:
                 ens.set_initial(vid, self._initial[name])
@@ -1220,6 +1265,8 @@ class ModelBuilder:
                        L.KIND_TERRESTRIAL_CARBON: L.TC_PARAM_NAMES, L.KIND_OCEAN_CARBON: L.OC_PARAM_NAMES,
                        L.KIND_HALOCARBON: L.HC_PARAM_NAMES, L.KIND_FOURBOX_OHU: L.FB_PARAM_NAMES,
                        L.KIND_OSPP: L.SP_PARAM_NAMES}[kind]
+        if noise_params:
+            param_order = tuple(param_order) + self.NOISE_PARAM_NAMES
         model = Model(ens, self._axis, sources, endogenous, forcing, dict(self._initial), param_order,
                       np.array(params, dtype=np.float64))
         model._builder = self

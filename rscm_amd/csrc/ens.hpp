@@ -127,6 +127,24 @@ struct rscm_ens {
     double* d_noise_state = nullptr;
     int32_t noise_state_index = -1;
     int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
+    // RSCM_FLAG_NOISE_PARAMS: the handle has the parameter rows noise_sigma_row() and noise_phi_row().  noise_members
+    // (rscm_ens_set_forcing_noise_members, with noise_on; noise_sigma and noise_phi are 0 then): e is formed per member from those rows as
+    // they stand at launch, so the cache is only as good as the rows.  The two rules, each kept in one place:
+    //   params_written()      whatever writes a parameter row calls it (rscm_ens_set_params[_aos], rscm_ens_sample_lhs,
+    //                         rscm_ens_gather_members into the handle; a restore goes through rscm_ens_set_params): the index is dropped
+    //   noise_cache_kept()    a run leaves its index behind only where nobody can write the rows unseen: never once
+    //                         rscm_ens_params_devptr has handed the block out
+    bool noise_rows = false;
+    bool noise_members = false;
+    int32_t noise_sigma_row() const { return noise_rows ? 6 + n_comp : -1; }
+    int32_t noise_phi_row() const { return noise_rows ? 6 + n_comp + 1 : -1; }
+    bool noise_red() const { return noise_on && (noise_members || noise_phi != 0.0); }   // the settings that cache e
+    bool noise_cache_kept() const { return !(noise_members && params_exposed); }
+    void params_written()
+    {
+        derived_dirty = true;
+        if (noise_members) noise_state_index = -1;
+    }
     double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;
     // OceanCarbon: flux history (internal state) and the tabulated impulse response

@@ -301,6 +301,11 @@ void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, con
             a.noise_state = h->d_noise_state;
             a.noise_phi = h->noise_phi;
         }
+        if (h->noise_members) {   // sigma_i and phi_i are parameter rows 6 + n_comp and the next: the kernel reads them through a.params
+            const int32_t t0 = step_begin + a.src_off;
+            a.noise_on = t0 > 0 && h->noise_state_index == t0 - 1 ? rscm::kNoiseMembersCached : rscm::kNoiseMembersSpinUp;
+            a.noise_state = h->d_noise_state;
+        }
     }
 }
 rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t end, int64_t m0, int64_t count)
@@ -310,7 +315,7 @@ rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t 
     c.step_begin = begin;
     c.step_end = end;
     c.lds_forcing = rscm::two_layer_fits_lds(a.n_scen, a.n_comp, end - begin) ? 1 : 0;
-    c.params = a.params + m0;   // every row moves with the block, a mix handle's coefficient rows included (stride N)
+    c.params = a.params + m0;   // every row moves with the block, a mix handle's coefficient rows and the noise rows included (stride N)
     if (a.scen) c.scen = a.scen + m0;
     c.ts = a.ts + m0;
     c.td = a.td + m0;
@@ -320,7 +325,7 @@ rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t 
     // (run_member_split issues the chunks of one block on one stream, in order)
     if (a.noise_on >= rscm::kNoiseRedSpinUp) {
         c.noise_state = a.noise_state + m0;
-        if (begin != a.step_begin) c.noise_on = rscm::kNoiseRedCached;
+        if (begin != a.step_begin) c.noise_on = a.noise_on >= rscm::kNoiseMembersSpinUp ? rscm::kNoiseMembersCached : rscm::kNoiseRedCached;
     }
     return c;
 }
@@ -610,7 +615,7 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
             if (step_end > step_begin) h->noise_state_index = -1;
             if (int rc = launch_whole_or_split(h, a, linked != 0, false, [mode](const rscm::TwoLayerArgs& c, hipStream_t st) { return rscm::launch_two_layer(c, mode, st); }))
                 return rc;
-            if (a.noise_on >= rscm::kNoiseRedSpinUp && step_end > step_begin) h->noise_state_index = step_end - 1 + a.src_off;
+            if (a.noise_on >= rscm::kNoiseRedSpinUp && step_end > step_begin && h->noise_cache_kept()) h->noise_state_index = step_end - 1 + a.src_off;
             return RSCM_OK;
         }
         case rscm::Family::Coupled: {

@@ -381,9 +381,14 @@ struct TwoLayerArgs {
     // noise_on kNoiseRedSpinUp: the launch forms e up to the index before its first from the draws (nothing to form when that first
     // index is 0); kNoiseRedCached: noise_state holds e at the index before its first.  Either way the launch leaves e at the last
     // index it drew, step_end - 1 + src_off, in noise_state
+    // Per-member noise (rscm_ens_set_forcing_noise_members; the NOISE == 3 instantiations): the same recurrence with member i's sigma_i and
+    // phi_i, read once per launch from parameter rows kTwoLayerCoeff0 + n_comp and the one after it through `params` and `uniform_rows`
+    // like the six parameters and the coefficients; noise_sigma and noise_phi are not read.  noise_on kNoiseMembersSpinUp /
+    // kNoiseMembersCached say what the two red values say.  Nothing was added to the struct: it is full
     double noise_phi;
 };
-constexpr int32_t kNoiseWhite = 1, kNoiseRedSpinUp = 2, kNoiseRedCached = 3;   // TwoLayerArgs::noise_on (0: no noise)
+// TwoLayerArgs::noise_on (0: no noise).  From kNoiseRedSpinUp on the launch keeps e in noise_state
+constexpr int32_t kNoiseWhite = 1, kNoiseRedSpinUp = 2, kNoiseRedCached = 3, kNoiseMembersSpinUp = 4, kNoiseMembersCached = 5;
 static_assert(sizeof(TwoLayerArgs) == 240, "TwoLayerArgs must not grow the fused launches' op union");
 
 // Reference periods of the fused likelihood (launch_two_layer_loglik_ref; DESIGN.md section 7, "Reference periods"), index 0: Surface
@@ -725,6 +730,9 @@ hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
 // with phi != 0 the red term e_t (TwoLayerArgs::noise_phi), formed from index 0 on and written from t_begin on
 hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n_members, int32_t t_begin,
                                      int32_t t_end, double* out, hipStream_t s);
+// the same for the per-member noise: member i's e_t from sigma_i = row sigma_row and phi_i = row phi_row of the [P][n_members] block
+hipError_t launch_forcing_noise_member_rows(uint64_t seed, const double* params, uint64_t uniform_rows, int32_t sigma_row, int32_t phi_row,
+                                            int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end, double* out, hipStream_t s);
 // z[j] = the deviate of the 52-bit integer k52[j] (test hook, rscm_gpu_selftest_normal)
 hipError_t launch_normal_selftest(const uint64_t* k52, int64_t n, double* z, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);

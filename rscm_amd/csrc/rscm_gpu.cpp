@@ -609,8 +609,8 @@ int rscm_ens_create_mix(int32_t kind, int64_t n_members, int32_t n_times, const 
     if (out) *out = nullptr;
     if (kind != RSCM_KIND_TWO_LAYER)
         return fail(RSCM_ERR_INVALID, "forcing components are available for the two-layer kind only (RSCM_KIND_TWO_LAYER), got kind %d", kind);
-    if (flags & ~(uint32_t)RSCM_FLAG_NO_SERIES)
-        return fail(RSCM_ERR_INVALID, "a mix handle takes flags 0 or RSCM_FLAG_NO_SERIES (no windowed storage), got 0x%x", flags);
+    if (flags & ~(uint32_t)(RSCM_FLAG_NO_SERIES | RSCM_FLAG_NOISE_PARAMS))
+        return fail(RSCM_ERR_INVALID, "a mix handle takes flags 0, RSCM_FLAG_NO_SERIES or RSCM_FLAG_NOISE_PARAMS (no windowed storage), got 0x%x", flags);
     if (n_components < 1 || n_components > RSCM_TL_MAX_COMPONENTS)
         return fail(RSCM_ERR_INVALID, "n_components must be in [1, %d], got %d", RSCM_TL_MAX_COMPONENTS, n_components);
     return create_handle(kind, n_members, n_times, time_bounds, device_id, flags, 16, 0, -1, nullptr, n_components, out);
@@ -622,7 +622,12 @@ static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const
                          rscm_ens** out)
 {
     GUARD_BEGIN
-    if (flags & ~(uint32_t)(RSCM_FLAG_NO_SERIES | RSCM_FLAG_WINDOWED)) return fail(RSCM_ERR_INVALID, "unknown flags 0x%x", flags);
+    if (flags & ~(uint32_t)(RSCM_FLAG_NO_SERIES | RSCM_FLAG_WINDOWED | RSCM_FLAG_NOISE_PARAMS)) return fail(RSCM_ERR_INVALID, "unknown flags 0x%x", flags);
+    if ((flags & RSCM_FLAG_NOISE_PARAMS) && kind != RSCM_KIND_TWO_LAYER)
+        return fail(RSCM_ERR_INVALID, "RSCM_FLAG_NOISE_PARAMS is only available for the two-layer kind");
+    if ((flags & RSCM_FLAG_NOISE_PARAMS) && (flags & (RSCM_FLAG_NO_SERIES | RSCM_FLAG_WINDOWED)))
+        return fail(RSCM_ERR_INVALID, "RSCM_FLAG_NOISE_PARAMS needs a handle that stores its whole series (no RSCM_FLAG_NO_SERIES, no windowed storage): "
+                    "the noise that reads the two rows is refused without");
     if ((flags & RSCM_FLAG_NO_SERIES) && kind != RSCM_KIND_TWO_LAYER)
         return fail(RSCM_ERR_INVALID, "RSCM_FLAG_NO_SERIES is only available for the two-layer kind");
     if ((flags & RSCM_FLAG_NO_SERIES) && (flags & RSCM_FLAG_WINDOWED))
@@ -660,6 +665,10 @@ static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const
         h->n_comp = n_components;
         h->P = RSCM_TL_P_COEFF0 + n_components;
         h->n_inputs = n_components;
+    }
+    if (flags & RSCM_FLAG_NOISE_PARAMS) {   // sigma_i and phi_i follow the six parameters and the coefficients
+        h->noise_rows = true;
+        h->P += 2;
     }
     h->bounds.assign(time_bounds, time_bounds + n_times + 1);
     h->initial_set.assign(h->V, 0);
@@ -931,7 +940,7 @@ int rscm_ens_set_params(rscm_ens* h, const double* soa)
             if (same) uni |= 1ull << j;
         }
         h->uniform_rows = h->params_exposed ? 0 : uni;  // a caller holding the device pointer may rewrite any row
-        h->derived_dirty = true;
+        h->params_written();
     }
     HIPCHK(hipStreamSynchronize(h->stream));
     h->params_set = true;
@@ -1270,6 +1279,9 @@ int rscm_ens_gather_members(rscm_ens* dst, int64_t dst_offset, rscm_ens* src, co
     if (dst->kind != src->kind) return fail(RSCM_ERR_INVALID, "kinds differ: destination %d, source %d", dst->kind, src->kind);
     if (dst->n_comp != src->n_comp)
         return fail(RSCM_ERR_INVALID, "the forcing component counts differ: destination %d, source %d", dst->n_comp, src->n_comp);
+    if (dst->noise_rows != src->noise_rows)
+        return fail(RSCM_ERR_INVALID, "one handle has the noise parameter rows (RSCM_FLAG_NOISE_PARAMS) and the other has not: destination %d, source %d",
+                    (int)dst->noise_rows, (int)src->noise_rows);
     if (dst->device != src->device) return fail(RSCM_ERR_INVALID, "the handles live on devices %d and %d", dst->device, src->device);
     if (dst->T != src->T || memcmp(dst->bounds.data(), src->bounds.data(), src->bounds.size() * sizeof(double)) != 0)
         return fail(RSCM_ERR_INVALID, "the time axes differ");
@@ -1387,7 +1399,7 @@ int rscm_ens_gather_members(rscm_ens* dst, int64_t dst_offset, rscm_ens* src, co
     } else if (dst_offset != 0)
         uni = 0;   // element 0, which the kernels read for such a row, is not among the members written
     dst->uniform_rows = uni;
-    dst->derived_dirty = true;
+    dst->params_written();
     dst->params_set = true;
     dst->mark_states_set();
     dst->time_index = k;
@@ -1559,6 +1571,7 @@ int rscm_ens_params_devptr(rscm_ens* h, void** out)
     // handle is ever treated as uniform again (rscm_ens_set_params keeps the flag clear as well).
     h->params_exposed = true;
     h->uniform_rows = 0;
+    h->params_written();   // (and noise_cache_kept() is false from here on)
     h->params_set = true;  // the caller fills it on the device
     return RSCM_OK;
 }
@@ -1737,7 +1750,7 @@ int rscm_ens_sample_lhs(rscm_ens* h, uint64_t seed, const double* low, const dou
     (void)hipFree(d_lh);
     if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "sample_lhs: %s", hipGetErrorString(e));
     h->uniform_rows = 0;   // conservatively: low + u (high - low) need not reproduce low's bits for every u
-    h->derived_dirty = true;
+    h->params_written();
     h->params_set = true;
     return RSCM_OK;
     GUARD_END
@@ -1835,6 +1848,7 @@ int rscm_ens_set_forcing_noise_ar1(rscm_ens* h, uint64_t seed, double sigma, dou
     h->noise_seed = seed;
     h->noise_sigma = sigma;
     h->noise_phi = phi == 0.0 ? 0.0 : phi;   // (-0.0 is white too)
+    h->noise_members = false;
     h->noise_offset = member_offset;
     h->noise_state_index = -1;   // the cache belonged to the setting before
     return RSCM_OK;
@@ -1846,6 +1860,20 @@ int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma, int64_t
     return rscm_ens_set_forcing_noise_ar1(h, seed, sigma, 0.0, member_offset);
 }
 
+int rscm_ens_set_forcing_noise_members(rscm_ens* h, uint64_t seed, int64_t member_offset)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!h->noise_rows)
+        return fail(RSCM_ERR_INVALID, "this handle has no noise parameter rows: create it with RSCM_FLAG_NOISE_PARAMS");
+    // a red setting with placeholder numbers: its refusals, the cache buffer, the dropped index
+    if (int rc = rscm_ens_set_forcing_noise_ar1(h, seed, 0.0, 0.5, member_offset)) return rc;
+    h->noise_phi = 0.0;   // sigma and phi are the rows' from here on
+    h->noise_members = true;
+    return RSCM_OK;
+    GUARD_END
+}
+
 int rscm_ens_clear_forcing_noise(rscm_ens* h)
 {
     NEED(h);
@@ -1853,6 +1881,7 @@ int rscm_ens_clear_forcing_noise(rscm_ens* h)
     h->noise_seed = 0;
     h->noise_sigma = 0.0;
     h->noise_phi = 0.0;
+    h->noise_members = false;
     h->noise_offset = 0;
     h->noise_state_index = -1;
     return RSCM_OK;
@@ -1871,9 +1900,18 @@ int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, doubl
 int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t* cached_index)
 {
     NEED(h);
-    const bool red = h->noise_on && h->noise_phi != 0.0;
+    const bool red = h->noise_red();
     if (phi) *phi = red ? h->noise_phi : 0.0;
     if (cached_index) *cached_index = red ? h->noise_state_index : -1;
+    return RSCM_OK;
+}
+
+int rscm_ens_forcing_noise_members(const rscm_ens* h, int32_t* per_member, int32_t* sigma_row, int32_t* phi_row)
+{
+    NEED(h);
+    if (per_member) *per_member = h->noise_on && h->noise_members ? 1 : 0;
+    if (sigma_row) *sigma_row = h->noise_sigma_row();
+    if (phi_row) *phi_row = h->noise_phi_row();
     return RSCM_OK;
 }
 
@@ -1890,7 +1928,10 @@ int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, dou
     const size_t bytes = (size_t)(t_end - t_begin) * (size_t)h->N * sizeof(double);
     double* d = out;
     if (!on_device) HIPCHK(rscm::dev_malloc(&d, bytes));
-    hipError_t e = rscm::launch_forcing_noise_rows(h->noise_seed, h->noise_sigma, h->noise_phi, h->noise_offset, h->N, t_begin, t_end, d, h->stream);
+    hipError_t e = h->noise_members
+                       ? rscm::launch_forcing_noise_member_rows(h->noise_seed, h->d_params, h->uniform_rows, h->noise_sigma_row(), h->noise_phi_row(),
+                                                                h->noise_offset, h->N, t_begin, t_end, d, h->stream)
+                       : rscm::launch_forcing_noise_rows(h->noise_seed, h->noise_sigma, h->noise_phi, h->noise_offset, h->N, t_begin, t_end, d, h->stream);
     if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && !on_device) e = hipStreamSynchronize(h->stream);
     if (!on_device) (void)hipFree(d);

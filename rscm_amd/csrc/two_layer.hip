@@ -46,7 +46,7 @@ __device__ unsigned long long g_guard_counts[tl::kGuardKinds];
 
 // MIX: a mix handle's launch (a.n_comp >= 1): the staged table is [n_scen][n_comp][len], n_scen * n_comp rows laid out like scenarios
 // NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing, 1 white,
-// 2 red (a.noise_on kNoiseRedSpinUp or kNoiseRedCached)
+// 2 red (a.noise_on kNoiseRedSpinUp or kNoiseRedCached), 3 red with per-member sigma and phi (kNoiseMembersSpinUp or kNoiseMembersCached)
 template <int MODE, bool LDS, bool STORE, bool MIX = false, int NOISE = 0>
 __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 {
@@ -87,6 +87,28 @@ __global__ __launch_bounds__(kBlock) void forcing_noise_red_rows_kernel(uint64_t
     if (i >= n) return;
     const uint64_t g = (uint64_t)(member0 + i);
     double* o = out + i;
+    const double se = sigma * __builtin_sqrt(1.0 - phi * phi);
+    double e = 0.0;
+    for (int32_t t = 0; t < t_end; ++t) {
+        const double z = noise::draw(seed, g, (uint32_t)t);
+        e = t == 0 ? sigma * z : (phi * e) + (se * z);
+        if (t >= t_begin) {
+            *o = e;
+            o += n;
+        }
+    }
+}
+
+// the same for the per-member noise: sigma and phi are member i's, read the way the stepping kernel reads them
+__global__ __launch_bounds__(kBlock) void forcing_noise_member_rows_kernel(uint64_t seed, const double* params, uint64_t uniform_rows,
+                                                                           int32_t sigma_row, int32_t phi_row, int64_t member0, int64_t n,
+                                                                           int32_t t_begin, int32_t t_end, double* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const uint64_t g = (uint64_t)(member0 + i);
+    double* o = out + i;
+    const double sigma = param_at(params, uniform_rows, sigma_row, n, i), phi = param_at(params, uniform_rows, phi_row, n, i);
     const double se = sigma * __builtin_sqrt(1.0 - phi * phi);
     double e = 0.0;
     for (int32_t t = 0; t < t_end; ++t) {
@@ -154,13 +176,20 @@ static hipError_t launch_impl(const TwoLayerArgs& a, int mode, hipStream_t s)
                          : (a.lds_forcing ? two_layer_kernel<1, true, STORE> : two_layer_kernel<1, false, STORE>));
     if (a.noise_on) {   // the stored run of a handle that is not linked: the only launch that carries noise
         if constexpr (STORE) {
-            if (a.link || a.noise_on < kNoiseWhite || a.noise_on > kNoiseRedCached) return hipErrorInvalidValue;
+            if (a.link || a.noise_on < kNoiseWhite || a.noise_on > kNoiseMembersCached) return hipErrorInvalidValue;
             if (a.noise_on == kNoiseWhite) {
                 kern = a.n_comp > 0
                            ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 1> : two_layer_kernel<0, false, true, true, 1>)
                                         : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 1> : two_layer_kernel<1, false, true, true, 1>))
                            : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 1> : two_layer_kernel<0, false, true, false, 1>)
                                         : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 1> : two_layer_kernel<1, false, true, false, 1>));
+            } else if (a.noise_on >= kNoiseMembersSpinUp) {
+                if (!a.noise_state) return hipErrorInvalidValue;
+                kern = a.n_comp > 0
+                           ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 3> : two_layer_kernel<0, false, true, true, 3>)
+                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 3> : two_layer_kernel<1, false, true, true, 3>))
+                           : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 3> : two_layer_kernel<0, false, true, false, 3>)
+                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 3> : two_layer_kernel<1, false, true, false, 3>));
             } else {
                 if (!a.noise_state) return hipErrorInvalidValue;
                 kern = a.n_comp > 0
@@ -199,6 +228,16 @@ hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, double phi, in
     const dim3 grid((unsigned)((n_members + kBlock - 1) / kBlock));
     if (phi == 0.0) hipLaunchKernelGGL(forcing_noise_rows_kernel, grid, dim3(kBlock), 0, s, seed, sigma, member0, n_members, t_begin, t_end, out);
     else hipLaunchKernelGGL(forcing_noise_red_rows_kernel, grid, dim3(kBlock), 0, s, seed, sigma, phi, member0, n_members, t_begin, t_end, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_forcing_noise_member_rows(uint64_t seed, const double* params, uint64_t uniform_rows, int32_t sigma_row, int32_t phi_row,
+                                            int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end, double* out, hipStream_t s)
+{
+    if (n_members <= 0 || t_end <= t_begin) return hipSuccess;
+    if (!params || sigma_row < 0 || phi_row < 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(forcing_noise_member_rows_kernel, dim3((unsigned)((n_members + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, seed, params,
+                       uniform_rows, sigma_row, phi_row, member0, n_members, t_begin, t_end, out);
     return hipGetLastError();
 }
 

@@ -309,6 +309,11 @@ enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuar
 // loaded from a.noise_state (a.noise_on == kNoiseRedCached) or formed from index 0 on by the same statements as in the loop (a
 // wave-uniform trip count; the bits of the per-index definition by construction).  The launch ends with one store of e, which then
 // stands at the last index drawn, step_end - 1 + a.src_off.
+// NOISE == 3 (per-member, rscm_ens_set_forcing_noise_members): the red statements with member i's own sigma_i and phi_i, parameter rows
+// kTwoLayerCoeff0 + K and the next (K = a.n_comp of a mix handle, else 0), read once per launch like every other row -- a row that
+// rscm_ens_set_params found uniform is one element for the wavefront.  sigma_i, phi_i and sigma_i sqrt(1 - phi_i phi_i) live in vector
+// registers (four more than NOISE == 2, where they are kernel arguments: the EXACT plain kernel crosses the 168-register step).  Nothing validates the rows: NaN, Inf or |phi_i| > 1 make that
+// lane's forcing NaN and leave every other lane alone; a lane whose forcing leaves the guard's box replays its year as with any forcing.
 template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, int NOISE = 0>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
                                                int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
@@ -371,15 +376,24 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
         return noise::normal_from_k(noise::k_of(lo, hi));
     };
     // red noise: e at the last index drawn, and sigma sqrt(1 - phi^2) (three roundings, then the product)
-    constexpr bool RED = NOISE == 2;
+    constexpr bool RED = NOISE >= 2;
+    constexpr bool MEMBERS = NOISE == 3;   // sigma and phi are the member's own
     [[maybe_unused]] double red_e = 0.0;
-    [[maybe_unused]] const double red_se = RED ? a.noise_sigma * __builtin_sqrt(1.0 - a.noise_phi * a.noise_phi) : 0.0;
+    [[maybe_unused]] double mem_sigma = 0.0, mem_phi = 0.0;
+    if constexpr (MEMBERS) {
+        mem_sigma = cache.param(a.params, a.uniform_rows, kTwoLayerCoeff0 + n_comp, N, i);
+        mem_phi = cache.param(a.params, a.uniform_rows, kTwoLayerCoeff0 + n_comp + 1, N, i);
+    }
+    [[maybe_unused]] const double red_se = MEMBERS ? mem_sigma * __builtin_sqrt(1.0 - mem_phi * mem_phi)
+                                           : RED   ? a.noise_sigma * __builtin_sqrt(1.0 - a.noise_phi * a.noise_phi)
+                                                   : 0.0;
     [[maybe_unused]] auto red_advance = [&](int32_t t) {   // e_{t-1} -> e_t
         const double z = noise_z(t);
-        red_e = t == 0 ? a.noise_sigma * z : (a.noise_phi * red_e) + (red_se * z);
+        if constexpr (MEMBERS) red_e = t == 0 ? mem_sigma * z : (mem_phi * red_e) + (red_se * z);
+        else red_e = t == 0 ? a.noise_sigma * z : (a.noise_phi * red_e) + (red_se * z);
     };
     if constexpr (RED) {
-        if (a.noise_on == kNoiseRedCached) red_e = a.noise_state[i];
+        if (a.noise_on == (MEMBERS ? kNoiseMembersCached : kNoiseRedCached)) red_e = a.noise_state[i];
         else
             for (int32_t t = 0, t0 = step_begin + a.src_off; t < t0; ++t) red_advance(t);
     }

@@ -299,6 +299,11 @@ class ShardedEnsemble:
         is the offset, so a member draws the same variability whichever rank holds it."""
         self.ensemble.set_forcing_noise(sigma, seed, self.offset, phi)
 
+    def set_forcing_noise_members(self, seed: int) -> None:
+        """Per-member forcing noise of the global ensemble (``Ensemble.set_forcing_noise_members``): the shard's first member is
+        the offset; the amplitude and persistence rows are the shard's slice of the global parameter block."""
+        self.ensemble.set_forcing_noise_members(seed, self.offset)
+
     def set_params_global(self, soa: np.ndarray) -> None:
         self.ensemble.set_params(np.ascontiguousarray(soa[:, self.offset:self.offset + self.count]))
 

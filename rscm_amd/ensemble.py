@@ -44,7 +44,7 @@ class DeviceVector:
 class Ensemble:
     def __init__(self, kind: int, n_members: int, time_bounds: Sequence[float], device: int = 0,
                  store_series: bool = True, window_rows: Optional[int] = None, output_stride: int = 0,
-                 output_vars: Optional[Sequence] = None, forcing_components=None):
+                 output_vars: Optional[Sequence] = None, forcing_components=None, noise_params: bool = False):
         """``window_rows``: keep only a sliding window of that many rows of every series
         (``RSCM_FLAG_WINDOWED``) plus, with ``output_stride`` > 0, every ``output_stride``-th row of
         ``output_vars`` (names or ids; None: all) -- for long axes stepped in lock-step.
@@ -52,7 +52,11 @@ class Ensemble:
         ``forcing_components`` (two-layer kind; an int K or a sequence of K names, 1 <= K <= 8): a *mix*
         ensemble (``rscm_ens_create_mix``).  ``set_forcing`` then takes K component series per scenario,
         ``[S][K][T]``, and member i is forced by ``((S_0 c_0 + S_1 c_1) + ...) + S_K-1 c_K-1`` with its own
-        coefficients c_k = parameter rows 6 .. 6+K-1 (``coefficient_row``): ``n_params`` is 6 + K."""
+        coefficients c_k = parameter rows 6 .. 6+K-1 (``coefficient_row``): ``n_params`` is 6 + K.
+
+        ``noise_params`` (two-layer kind, plain or mix, whole series stored): two more parameter rows after the coefficients
+        (``RSCM_FLAG_NOISE_PARAMS``), every member's noise amplitude and persistence (``noise_param_rows``,
+        ``set_forcing_noise_members``): ``n_params`` is 6 + K + 2."""
         self._lib = L.load()
         b = L.f64(time_bounds)
         if b.ndim != 1 or len(b) < 3:
@@ -76,6 +80,14 @@ class Ensemble:
             self.n_forcing_components = len(names)
             self.n_params = L.TL_P_COEFF0 + len(names)   # the coefficients are parameter rows 6 .. 6 + K - 1
             input_rows = names
+        self.noise_params = bool(noise_params)
+        if self.noise_params:
+            if kind != L.KIND_TWO_LAYER:
+                raise ValueError("noise_params are available for the two-layer kind only")
+            if window_rows is not None or not store_series:
+                raise ValueError("noise_params need an ensemble that stores its whole series (no window_rows, store_series=True)")
+            self.n_params += 2   # sigma_i and phi_i follow the six parameters and the coefficients
+        flag = L.FLAG_NOISE_PARAMS if self.noise_params else 0
         self.var_ids: Dict[str, int] = dict(var_ids)
         self.input_rows = input_rows  # names of the rows of the input block, or None
         self.n_inputs = len(input_rows) if input_rows else 1
@@ -85,7 +97,7 @@ class Ensemble:
         self.output_stride = int(output_stride) if self.window_rows else 0
         if self.n_forcing_components:
             L.check(self._lib.rscm_ens_create_mix(kind, self.n_members, self.n_times, L.dptr(b), device,
-                                                  0 if store_series else L.FLAG_NO_SERIES, self.n_forcing_components, C.byref(h)))
+                                                  flag if store_series else L.FLAG_NO_SERIES, self.n_forcing_components, C.byref(h)))
         elif self.window_rows:
             ov = None
             if output_vars is not None:
@@ -96,7 +108,7 @@ class Ensemble:
                                                        L.iptr(ov), C.byref(h)))
         else:
             L.check(self._lib.rscm_ens_create_ex(kind, self.n_members, self.n_times, L.dptr(b), device,
-                                                 0 if store_series else L.FLAG_NO_SERIES, C.byref(h)))
+                                                 flag if store_series else L.FLAG_NO_SERIES, C.byref(h)))
         self._h = h
         # the library and the tables of this package must agree on the shape of the kind
         got = [C.c_int32() for _ in range(3)]
@@ -207,17 +219,44 @@ class Ensemble:
             raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
         L.check(self._lib.rscm_ens_set_forcing_noise_ar1(self._h, C.c_uint64(seed), float(sigma), float(phi), int(member_offset)))
 
+    @property
+    def noise_param_rows(self):
+        """``(sigma_row, phi_row)``: the parameter rows that hold every member's noise amplitude and persistence
+        (``noise_params=True``; 6 + K and 6 + K + 1)."""
+        s, p = C.c_int32(), C.c_int32()
+        L.check(self._lib.rscm_ens_forcing_noise_members(self._h, None, C.byref(s), C.byref(p)))
+        if s.value < 0:
+            raise ValueError("this ensemble has no noise parameter rows (noise_params=True was not given)")
+        return s.value, p.value
+
+    def set_forcing_noise_members(self, seed: int, member_offset: int = 0) -> None:
+        """Internal variability with every member's own amplitude and persistence (``rscm_ens_set_forcing_noise_members``; an
+        ensemble made with ``noise_params=True``): member i is forced by ``F + e_t``, the red recurrence of ``set_forcing_noise``
+        with ``sigma_i`` and ``phi_i`` from the rows ``noise_param_rows`` as they stand when a run is launched.  The rows are
+        parameters like any other: ``sample_lhs`` draws them, ``set_weights_from_loglik`` weights them, ``params_vector`` with
+        ``quantile_vectors(..., weighted=True)`` reports their posterior, ``posterior()`` / ``branch()`` hand them to the draws.
+        Nothing validates them: a NaN or Inf row, or ``|phi_i| > 1``, gives that member NaN states and a failed status, nothing
+        else.  Everything that writes a parameter row drops the cached values (``forcing_noise_cached_index``); once
+        ``params_devptr`` has been taken every run forms them again."""
+        seed = int(seed)
+        if not 0 <= seed < 1 << 64:
+            raise ValueError(f"seed must fit 64 unsigned bits, got {seed}")
+        L.check(self._lib.rscm_ens_set_forcing_noise_members(self._h, C.c_uint64(seed), int(member_offset)))
+
     def clear_forcing_noise(self) -> None:
         L.check(self._lib.rscm_ens_clear_forcing_noise(self._h))
 
     @property
     def forcing_noise(self) -> Optional[Dict[str, object]]:
         """``{"sigma", "seed", "member_offset"}`` of ``set_forcing_noise``, and ``"phi"`` where the noise is red (``phi != 0``);
-        None without noise."""
-        on, seed, sigma, off, phi = C.c_int32(), C.c_uint64(), C.c_double(), C.c_int64(), C.c_double()
+        ``{"per_member": True, "seed", "member_offset"}`` under ``set_forcing_noise_members``; None without noise."""
+        on, seed, sigma, off, phi, per = C.c_int32(), C.c_uint64(), C.c_double(), C.c_int64(), C.c_double(), C.c_int32()
         L.check(self._lib.rscm_ens_forcing_noise(self._h, C.byref(on), C.byref(seed), C.byref(sigma), C.byref(off)))
         if not on.value:
             return None
+        L.check(self._lib.rscm_ens_forcing_noise_members(self._h, C.byref(per), None, None))
+        if per.value:
+            return {"per_member": True, "seed": seed.value, "member_offset": off.value}
         L.check(self._lib.rscm_ens_forcing_noise_ar1(self._h, C.byref(phi), None))
         noise = {"sigma": sigma.value, "seed": seed.value, "member_offset": off.value}
         if phi.value != 0.0:
@@ -366,7 +405,9 @@ class Ensemble:
               "state": {name: self.get_series(v, k, k + 1)[0] for name, v in names.items()},
               "history": history, "internal": internal}
         noise = self.forcing_noise if self.kind == L.KIND_TWO_LAYER else None
-        if noise is not None:   # (a pure function of these numbers: the red noise's cached values are not carried)
+        if noise is not None and noise.get("per_member"):   # (sigma_i and phi_i are in the parameter block already)
+            ck["forcing_noise"] = {"per_member": True, "seed": np.uint64(noise["seed"]), "member_offset": noise["member_offset"]}
+        elif noise is not None:   # (a pure function of these numbers: the red noise's cached values are not carried)
             ck["forcing_noise"] = {"sigma": noise["sigma"], "seed": np.uint64(noise["seed"]), "member_offset": noise["member_offset"]}
             if "phi" in noise:
                 ck["forcing_noise"]["phi"] = noise["phi"]
@@ -379,11 +420,16 @@ class Ensemble:
         if (ck["kind"] != self.kind or ck["n_members"] != self.n_members
                 or not np.array_equal(ck["bounds"], self.bounds)):
             raise ValueError("checkpoint does not match this ensemble (kind, members or time axis)")
+        per_member = bool((ck.get("forcing_noise") or {}).get("per_member", False))
+        if per_member and not self.noise_params:
+            raise ValueError("the checkpoint carries per-member forcing noise: restore it into an ensemble made with noise_params=True")
         self.set_params(ck["params"])
         if self.kind == L.KIND_TWO_LAYER:   # the noise setting is the checkpoint's: none where it has none
             noise = ck.get("forcing_noise")
             if noise is None:
                 self.clear_forcing_noise()
+            elif per_member:
+                self.set_forcing_noise_members(int(noise["seed"]), int(noise["member_offset"]))
             else:
                 self.set_forcing_noise(float(noise["sigma"]), int(noise["seed"]), int(noise["member_offset"]), float(noise.get("phi", 0.0)))
         k = int(ck["time_index"])
@@ -806,7 +852,9 @@ class Ensemble:
         Copies of one ancestor stay identical for ever under a shared forcing.  Giving ``dst`` its own forcing noise
         (``dst.set_forcing_noise(sigma, seed)`` in ``factory`` or afterwards; the noise belongs to ``dst`` like the forcing and
         a branch leaves it alone) is what makes them diverge: member j of ``dst`` then draws the variability of its own index,
-        whatever ancestor it copies."""
+        whatever ancestor it copies.  The handle-wide ``sigma`` and ``phi`` do not travel, they are ``dst``'s numbers; a ``dst`` made
+        with ``noise_params=True`` from a source that has the rows (``dst.set_forcing_noise_members(seed)``) inherits each
+        ancestor's amplitude and persistence with its other parameter rows, and realises its own noise under its own seed."""
         n_draws, scenarios = int(n_draws), int(scenarios)
         if n_draws < 1 or scenarios < 1:
             raise ValueError("need n_draws >= 1 and scenarios >= 1")

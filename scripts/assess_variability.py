@@ -1,0 +1,111 @@
+"""Internal variability with unknown amplitude and persistence, on the device: a two-layer ensemble whose noise amplitude sigma and
+lag-one correlation phi are parameter rows (``Ensemble(..., noise_params=True)``, ``set_forcing_noise_members``).
+
+  * a Latin hypercube over the six model parameters AND sigma, phi;
+  * the history 1850-2020 run under each member's own AR(1) noise, scored against a record (here: one run of a member with known
+    sigma and phi and its own seed, every fifth year), weighted (``loglik`` then ``set_weights_from_loglik``);
+  * the prior and the weighted quantiles of ``params_vector(sigma_row)`` and ``params_vector(phi_row)``, the weighted ones compared
+    with numpy;
+  * a posterior ensemble (``posterior()``) made with ``noise_params=True``: every draw inherits its ancestor's sigma and phi, realises
+    its own noise under its own seed, and is projected to 2100 -- the plume then carries the variability the record supports.
+
+A point likelihood of one realisation constrains sigma and phi only weakly (members with less noise fit a record's slow part better;
+DESIGN.md section 10, item 0: a likelihood that sees variance and autocorrelation is what is left to build).
+
+    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast]
+
+Prints one JSON line; exit code 0 iff every comparison holds."""
+import argparse
+import json
+import os
+import sys
+import warnings
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import rscm_amd  # noqa: E402
+
+Q = [0.05, 0.17, 0.5, 0.83, 0.95]
+YEARS = np.arange(1850.0, 2101.0)
+BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+NOW = 2020 - 1850   # the time index the record ends at
+LO = np.array([0.8, 0.0, 1.0, 0.5, 5.0, 50.0, 0.05, 0.0])
+HI = np.array([1.5, 0.1, 1.8, 1.0, 15.0, 200.0, 1.0, 0.95])
+TRUTH = np.array([1.1, 0.05, 1.3, 0.7, 8.0, 100.0, 0.4, 0.6])
+OBS_SIGMA = 0.12
+TS = "Surface Temperature"
+
+
+def forcing():
+    t = YEARS - 1850.0
+    return 0.035 * t + 0.25 * np.sin(2.0 * np.pi * t / 11.0)
+
+
+def make(n, mode, seed, offset=0):
+    e = rscm_amd.Ensemble(rscm_amd.KIND_TWO_LAYER, n, BOUNDS, noise_params=True)
+    e.set_mode(mode)
+    e.set_forcing(forcing())
+    e.set_initial(1, 0.0)
+    e.set_initial(2, 0.0)
+    e.set_forcing_noise_members(seed, offset)
+    return e
+
+
+def np_weighted(row, w):
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)
+        return np.nanquantile(row, Q, weights=w, method="inverted_cdf")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--members", type=int, default=100_000)
+    ap.add_argument("--draws", type=int, default=20_000)
+    ap.add_argument("--fast", action="store_true")
+    a = ap.parse_args()
+    mode = rscm_amd.MODE_FAST if a.fast else rscm_amd.MODE_EXACT
+
+    # the record: one member with known amplitude and persistence, a seed of its own
+    with make(1, mode, seed=99) as truth:
+        truth.set_params(TRUTH[:, None])
+        truth.run(NOW)
+        rows = np.arange(5, NOW + 1, 5)
+        record = truth.get_series(TS, 0, NOW + 1)[rows, 0]
+
+    with make(a.members, mode, seed=1) as ens:
+        sigma_row, phi_row = ens.noise_param_rows
+        ens.sample_lhs(20260327, LO, HI)
+        ens.run(NOW)
+        ll = ens.loglik([TS] * rows.size, rows, record, np.full(rows.size, OBS_SIGMA), on_device=True)
+        ens.set_weights_from_loglik(ll)
+        vectors = [ens.params_vector(sigma_row), ens.params_vector(phi_row)]
+        prior = ens.quantile_vectors(vectors, Q)["quantiles"]
+        post = ens.quantile_vectors(vectors, Q, weighted=True)["quantiles"]
+        P, w = ens.get_params(), ens.member_weights()
+        checks = {"weighted_quantiles_equal_numpy": bool(np.array_equal(post, np.stack([np_weighted(P[sigma_row], w), np_weighted(P[phi_row], w)])))}
+        ess = ens.weights_stats()["ess"]
+
+        # the posterior: the draws inherit sigma and phi with the other rows and realise their own noise to 2100
+        anc = ens.resample(a.draws, seed=7).to_host()
+        dst, _ = ens.posterior(lambda n: make(n, mode, seed=2), a.draws, seed=7)
+        with dst:
+            got = dst.get_params()
+            checks["draws_inherit_their_ancestors_rows"] = bool(np.array_equal(got, P[:, anc]))
+            dst.run()
+            plume = dst.quantile_rows(TS, Q, len(YEARS) - 1, len(YEARS))["quantiles"][0]
+            twins = np.flatnonzero(anc[1:] == anc[:-1])
+            last = dst.get_series(TS, len(YEARS) - 1)[0]
+            checks["draws_of_one_ancestor_diverge"] = bool(twins.size == 0 or (last[twins] != last[twins + 1]).any())
+
+    res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
+           "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
+           "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
+           "weighted": {"sigma": post[0].tolist(), "phi": post[1].tolist()},
+           "posterior_plume_2100_K": plume.tolist(), "checks": checks}
+    print(json.dumps(res), flush=True)
+    sys.exit(0 if all(checks.values()) else 1)
+
+
+if __name__ == "__main__":
+    main()
