@@ -94,8 +94,11 @@ extern "C" {
  *      rscm_ens_forcing_noise, rscm_ens_forcing_noise_rows, RSCM_NOISE_STREAM_TAG
  *  14  red (AR(1)) forcing noise: rscm_ens_set_forcing_noise_ar1, rscm_ens_forcing_noise_ar1
  *  15  per-member noise amplitude and persistence as parameter rows: RSCM_FLAG_NOISE_PARAMS, RSCM_TL_P_NOISE_SIGMA, RSCM_TL_P_NOISE_PHI,
- *      rscm_ens_set_forcing_noise_members, rscm_ens_forcing_noise_members */
-#define RSCM_GPU_ABI_MINOR 15
+ *      rscm_ens_set_forcing_noise_members, rscm_ens_forcing_noise_members
+ *  16  per-member variability statistics (mean, trend, variance, sd, lag-one autocorrelation) and a Gaussian likelihood over
+ *      per-member device vectors: rscm_ens_member_variability, RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE,
+ *      rscm_ens_loglik_vectors_device */
+#define RSCM_GPU_ABI_MINOR 16
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1068,6 +1071,49 @@ RSCM_API int rscm_ens_clear_member_groups(rscm_ens* h);
  * (-1) are left out.  No groups set, or weighted without weights: RSCM_ERR_STATE. */
 RSCM_API int rscm_ens_exceedance_grouped(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted,
                                          int64_t* hits, int64_t* total);
+
+/* ---- per-member variability statistics and a likelihood over per-member vectors (ABI minor 16) ---- */
+/* How variable is each member's series of var_id over a period: its mean, its trend, the variance and standard deviation about the
+ * trend and the lag-one autocorrelation of what is left, per member, on the device.  This is the one definition; the kernel
+ * (variability.hip), rscm_amd.variability.series_variability and the tests' numpy restatement apply it operation by operation.
+ *   Rows x_0 .. x_{R-1}: those of rscm_ens_set_baseline (t_begin, t_begin + t_stride, ... < t_end; any storage layout; every row
+ *   computed and resident, else RSCM_ERR_STATE).
+ *   Working series u_0 .. u_{n-1}:  RSCM_VAR_MEAN and RSCM_VAR_LINEAR  u_k = x_k, n = R;
+ *                                   RSCM_VAR_DIFFERENCE                u_k = x_{k+1} - x_k (one IEEE subtraction), n = R - 1.
+ *   n >= 3, else RSCM_ERR_INVALID.
+ *   Every operation below is one f64 operation rounded on its own (no FMA); sums run left to right from their first term.
+ *     tau_k = (double)k - h,  h = (n - 1) * 0.5  (exact)
+ *     S = u_0 + u_1 + ...                        m = S / n
+ *     RSCM_VAR_LINEAR:  Q = tau_0*u_0 + tau_1*u_1 + ...,  b = Q / Stt,  Stt = (double)(n (n^2 - 1)) / 12.0 with n (n^2 - 1) formed in int64;
+ *     the other modes:  b = +0.0
+ *     a_k = u_k - m;  RSCM_VAR_LINEAR:  a_k = (u_k - m) - b*tau_k
+ *     C0 = a_0*a_0 + a_1*a_1 + ...               C1 = a_0*a_1 + a_1*a_2 + ...  (n - 1 terms)
+ *     variance = C0 / n    sd = sqrt(variance)   r1 = C1 / C0
+ *   r1 is the biased estimator, so |r1| <= 1 up to rounding; C0 == 0 (a constant working series) gives NaN by 0/0.
+ * [5][N] doubles from *out_dev: mean (m), slope (b, per row index: per t_stride steps of the axis), variance, sd, r1.  A member
+ * with a non-finite value in any of its rows gets NaN in all five.
+ * The result is written to the handle-owned block of indicator slot `slot` (0 <= slot < 4): the slots are those of
+ * rscm_ens_member_indicators, and a slot holds the vectors of the last call on it, indicators or variability alike, until the next
+ * call on that slot.  A bad slot or mode: RSCM_ERR_INVALID; a select in flight: RSCM_ERR_STATE. */
+#define RSCM_VAR_MEAN 0       /* about the member's mean */
+#define RSCM_VAR_LINEAR 1     /* about the member's least-squares line over the row index */
+#define RSCM_VAR_DIFFERENCE 2 /* of the first differences of the rows, about their mean */
+RSCM_API int rscm_ens_member_variability(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t mode,
+                                         int32_t slot, void** out_dev);
+/* A Gaussian likelihood over per-member device vectors, continuing a point likelihood: vec_dev[n_vec] (a host array) holds device
+ * addresses of N doubles on the handle's device (variability statistics, indicators, rscm_ens_params_devptr rows), checked as
+ * rscm_ens_quantile_vectors checks its vectors; 1 <= n_vec <= 16; value[j] finite, sigma[j] finite and > 0 (RSCM_ERR_INVALID).
+ * Per member i: partial = 0.0; for j in order r = value[j] - v_j[i], chi = (r*r)/(sigma[j]*sigma[j]), partial += -0.5*chi -- the
+ * expressions of rscm_ens_loglik; the result is add_dev[i] + partial, or 0.0 + partial with add_dev NULL: the vectors count as one
+ * more variable group after the point likelihood's groups, so the sum is rscm_ens_loglik's total continued.  A non-finite v_j[i]
+ * gives -inf; so does a non-finite add_dev[i] (-inf stays -inf).
+ * There is no normalize flag: ln(2 pi) and ln(sigma[j]) are the same for every member and cancel in the weights; leaving them out
+ * keeps the call free of the device logarithm, and so bit-exact against the expressions above.
+ * The result lands in the handle's likelihood vector, the buffer of rscm_ens_loglik_device (*out_dev).  add_dev may BE that
+ * buffer -- each thread reads its own element before it writes it -- which is the intended use: rscm_ens_loglik_device, then this
+ * call with add_dev = its result. */
+RSCM_API int rscm_ens_loglik_vectors_device(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* value,
+                                            const double* sigma, const double* add_dev, void** out_dev);
 
 /* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
 /* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,

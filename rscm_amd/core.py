@@ -1506,6 +1506,12 @@ class GraphModel:
         ens, vid = self.variable_home(name)
         return ens.indicators(vid, t_begin, t_end, t_stride, thresholds, anomaly, slot)
 
+    def variability(self, name: str, t_begin: int, t_end: int, t_stride: int = 1, detrend: str = "linear", slot: int = 0) -> Dict[str, object]:
+        """``Ensemble.variability`` of ``name`` on its home ensemble: device vectors ``mean``, ``slope``, ``variance``, ``sd``,
+        ``r1``, which ``quantile_vectors``, ``exceedance`` and ``Ensemble.loglik_vectors`` read."""
+        ens, vid = self.variable_home(name)
+        return ens.variability(vid, t_begin, t_end, t_stride, detrend, slot)
+
     def quantile_vectors(self, vectors, q, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """``Ensemble.quantile_vectors`` on the ensemble that owns the vectors (every ensemble of the graph shares the member
         index and, after ``set_member_weights`` / ``set_weights_from_loglik`` / ``set_member_groups``, the weights and groups)."""

@@ -1,10 +1,13 @@
 // Host side of the handle's baseline (rscm_ens_set_baseline*, the anomaly select's b[i]), of the per-member indicators
 // (rscm_ens_member_indicators) and of the exceedance counts (rscm_ens_exceedance, rscm_ens_exceedance_grouped); kernels in indicators.hip.
+// Also of the per-member variability statistics (rscm_ens_member_variability), which share the rows and the slots of the indicators,
+// and of the Gaussian likelihood over per-member vectors (rscm_ens_loglik_vectors_device); kernels in variability.hip.
 //
 // Rows are resolved as the radix select resolves them (resolve_rows: full storage, the window, the output store) and must all be
 // computed.  The baseline and the indicator slots are handle-owned and kept across run and rewind, as the member weights are; a
 // staged select may read either, so neither changes while one is in flight.
 #include <cmath>
+#include <cstdio>
 #include <cstring>
 #include <limits>
 
@@ -63,6 +66,10 @@ int no_select(const rscm_ens* h)
     if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
     return RSCM_OK;
 }
+
+static_assert(rscm::kVarMean == RSCM_VAR_MEAN && rscm::kVarLinear == RSCM_VAR_LINEAR && rscm::kVarDifference == RSCM_VAR_DIFFERENCE,
+              "the detrending modes in rscm_device.hpp and rscm_gpu.h must agree");
+static_assert(5 <= 3 + rscm::kMaxThresholds, "the variability statistics share the indicator slots");
 
 }  // namespace
 
@@ -155,6 +162,71 @@ int rscm_ens_member_indicators(rscm_ens* h, int32_t var_id, int32_t t_begin, int
     if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
     if (int rc = run_indicators(h, rows, times, anomaly ? h->d_base : nullptr, true, n_thr, thr, h->d_ind[slot])) return rc;
     *out_dev = h->d_ind[slot];
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_member_variability(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t mode, int32_t slot,
+                                void** out_dev)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
+    *out_dev = nullptr;
+    if (slot < 0 || slot >= rscm_ens::kIndSlots) return fail(RSCM_ERR_INVALID, "slot %d: must be in [0, %d)", slot, rscm_ens::kIndSlots);
+    if (mode != RSCM_VAR_MEAN && mode != RSCM_VAR_LINEAR && mode != RSCM_VAR_DIFFERENCE)
+        return fail(RSCM_ERR_INVALID, "unknown detrending mode %d (RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE)", mode);
+    if (int rc = no_select(h)) return rc;
+    std::vector<const double*> rows;
+    std::vector<double> times;
+    if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
+    const int64_t n = (int64_t)rows.size() - (mode == RSCM_VAR_DIFFERENCE ? 1 : 0);   // the working series' length
+    if (n < 3) return fail(RSCM_ERR_INVALID, "the working series of %d rows has %lld terms: at least 3 are needed", (int)rows.size(), (long long)n);
+    const double stt = (double)(n * (n * n - 1)) / 12.0;
+    if (int rc = set_device(h)) return rc;
+    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
+    const double** d_rows = nullptr;
+    hipError_t e = rscm::dev_malloc(&d_rows, rows.size() * sizeof(double*));
+    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = rscm::launch_variability(d_rows, (int32_t)rows.size(), mode, stt, h->N, h->d_ind[slot], h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);
+    (void)hipFree(d_rows);
+    HIPCHK(e);
+    HIPCHK(es);
+    *out_dev = h->d_ind[slot];
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_loglik_vectors_device(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* value, const double* sigma,
+                                   const double* add_dev, void** out_dev)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
+    *out_dev = nullptr;
+    if (n_vec < 1 || n_vec > rscm::kMaxLoglikVectors || !vec_dev || !value || !sigma)
+        return fail(RSCM_ERR_INVALID, "bad vector list (1 to %d vectors, each with a value and a sigma)", rscm::kMaxLoglikVectors);
+    rscm::LoglikVectors v{};
+    for (int32_t j = 0; j < n_vec; ++j) {
+        if (!std::isfinite(value[j])) return fail(RSCM_ERR_INVALID, "vector %d: the target value is not finite", j);
+        if (!std::isfinite(sigma[j]) || !(sigma[j] > 0.0)) return fail(RSCM_ERR_INVALID, "vector %d: sigma must be finite and > 0", j);
+        v.value[j] = value[j];
+        v.sigma[j] = sigma[j];
+    }
+    if (int rc = set_device(h)) return rc;
+    for (int32_t j = 0; j < n_vec; ++j) {
+        char what[24];
+        std::snprintf(what, sizeof what, "vector %d", j);
+        if (int rc = check_member_vector(h, vec_dev[j], what)) return rc;
+        v.vec[j] = vec_dev[j];
+    }
+    if (add_dev)
+        if (int rc = check_member_vector(h, add_dev, "add_dev")) return rc;
+    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+    HIPCHK(rscm::launch_loglik_vectors(v, n_vec, add_dev, h->N, h->d_loglik, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out_dev = h->d_loglik;
     return RSCM_OK;
     GUARD_END
 }

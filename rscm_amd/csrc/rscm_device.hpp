@@ -888,6 +888,19 @@ hipError_t launch_exceedance(const double* d_v, const int64_t* d_w, int64_t N, i
 // the same per group: d_acc[g][n_thr + 1] (hits, then the total) over the members with d_group[i] == g; the caller zeroes it
 hipError_t launch_exceedance_grouped(const double* d_v, const int64_t* d_w, const int32_t* d_group, int32_t n_groups, int64_t N,
                                      int32_t n_thr, const Thresholds& thr, unsigned long long* d_acc, hipStream_t s);
+// per-member variability statistics (variability.hip) over rows d_rows[n_rows][N]: d_out[5][N] = mean, slope, variance, sd, r1 of
+// the working series (mode kVarMean / kVarLinear: the rows, kVarDifference: their first differences; the definition is stated in
+// include/rscm_gpu.h, rscm_ens_member_variability); stt = n (n^2 - 1) / 12 of the working series' length n, formed by the caller
+constexpr int kVarMean = 0, kVarLinear = 1, kVarDifference = 2;
+hipError_t launch_variability(const double* const* d_rows, int32_t n_rows, int32_t mode, double stt, int64_t N, double* d_out, hipStream_t s);
+// d_out[i] = (d_add ? d_add[i] : 0.0) + sum over j < n_vec of -0.5 ((value[j] - vec[j][i])^2 / sigma[j]^2), -inf where a vec[j][i] or
+// d_add[i] is not finite; d_add may be d_out
+constexpr int kMaxLoglikVectors = 16;
+struct LoglikVectors {
+    const double* vec[kMaxLoglikVectors];
+    double value[kMaxLoglikVectors], sigma[kMaxLoglikVectors];
+};
+hipError_t launch_loglik_vectors(const LoglikVectors& v, int32_t n_vec, const double* d_add, int64_t N, double* d_out, hipStream_t s);
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);

@@ -347,8 +347,14 @@ class ShardedEnsemble:
         max and ``bits`` (default ``53 - ceil(log2(n_total))``).  Returns the ``(ll_max, bits)`` used, the same on every rank.
         ``reference`` (``Ensemble.loglik``): the observations of those variables are anomalies from a reference period, so an
         anomaly plume (``quantile_rows_global(..., weighted=True, anomaly=True)``) is weighted by anomaly fit."""
-        from .ensemble import default_weight_bits
         ll = self.ensemble.loglik(obs_var, obs_tidx, obs_value, obs_sigma, normalize, on_device=True, reference=reference)
+        return self.constrain_loglik(ll, bits)
+
+    def constrain_loglik(self, ll, bits: Optional[int] = None):
+        """``constrain`` from a per-member log-likelihood of this rank's members (numpy or a ``DeviceVector``), e.g.
+        ``ensemble.loglik_vectors(...)`` over variability statistics, alone or added onto a point likelihood: the local max, a
+        MAX all-reduce, ``set_weights_from_loglik``.  Returns the ``(ll_max, bits)`` used, the same on every rank."""
+        from .ensemble import default_weight_bits
         ll_max = self.ensemble.loglik_max(ll)
         if is_distributed():
             import torch

@@ -632,6 +632,38 @@ class Ensemble:
         vec = [DeviceVector(base + 8 * n * j, n, np.float64, self) for j in range(3 + thr.size)]
         return {"mean": vec[0], "peak": vec[1], "peak_time": vec[2], "crossing": vec[3:]}
 
+    def variability(self, var, t_begin: int, t_end: int, t_stride: int = 1, detrend: str = "linear", slot: int = 0) -> Dict[str, object]:
+        """Per-member variability statistics of ``var`` over the rows ``t_begin, t_begin + t_stride, ... < t_end``, left on the
+        device in indicator slot ``slot`` (the slots of ``indicators``: a slot holds the vectors of the last call on it, of either
+        kind): ``{"mean", "slope", "variance", "sd", "r1"}``, ``DeviceVector``s of ``[N]`` float64.  ``detrend``: ``"mean"`` --
+        variance and lag-one autocorrelation ``r1`` about the member's mean; ``"linear"`` -- about its least-squares line, whose
+        ``slope`` is per row (per ``t_stride`` steps); ``"difference"`` -- of the first differences of the rows (``mean`` is then
+        the mean increment).  The definition is ``rscm_amd.variability.series_variability``'s, bit for bit (rscm_ens_member_variability).
+        At least three terms; a member with a non-finite value in any row has NaN in all five."""
+        from .variability import detrend_mode
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_member_variability(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride), detrend_mode(detrend),
+                                                      int(slot), C.byref(p)))
+        n, base = self.n_members, p.value
+        return {k: DeviceVector(base + 8 * n * j, n, np.float64, self) for j, k in enumerate(("mean", "slope", "variance", "sd", "r1"))}
+
+    def loglik_vectors(self, vectors, values, sigmas, add_to: Optional[DeviceVector] = None) -> DeviceVector:
+        """Gaussian log-likelihood per member over per-member device vectors (variability statistics, indicators,
+        ``params_vector`` rows): ``sum_j -0.5 ((values[j] - vectors[j][i]) / sigmas[j])^2``, added onto ``add_to`` -- a device
+        log-likelihood, typically ``loglik(..., on_device=True)``, which may be overwritten in place -- or onto zero.  No
+        normalisation terms: they are the same for every member and cancel in the weights.  A non-finite statistic or ``add_to``
+        gives ``-inf``.  The result is the handle's likelihood vector (rscm_ens_loglik_vectors_device)."""
+        arr, n_vec = self._vectors(vectors)
+        val, sig = np.atleast_1d(L.f64(values)), np.atleast_1d(L.f64(sigmas))
+        if not (n_vec == len(val) == len(sig)):
+            raise ValueError("vectors, values and sigmas differ in length")
+        add = None
+        if add_to is not None:
+            add = self._vectors([add_to])[0][0]
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_loglik_vectors_device(self._h, n_vec, arr, L.dptr(val), L.dptr(sig), add, C.byref(p)))
+        return DeviceVector(p.value, self.n_members, np.float64, self)
+
     def _vectors(self, vectors):
         vs = list(vectors)
         for v in vs:

@@ -9,8 +9,17 @@ lag-one correlation phi are parameter rows (``Ensemble(..., noise_params=True)``
   * a posterior ensemble (``posterior()``) made with ``noise_params=True``: every draw inherits its ancestor's sigma and phi, realises
     its own noise under its own seed, and is projected to 2100 -- the plume then carries the variability the record supports.
 
-A point likelihood of one realisation constrains sigma and phi only weakly (members with less noise fit a record's slow part better;
-DESIGN.md section 10, item 0: a likelihood that sees variance and autocorrelation is what is left to build).
+A point likelihood of one realisation constrains sigma and phi only weakly (members with less noise fit a record's slow part
+better), so the script then weights by the record's variability itself:
+
+  * the targets are the standard deviation and the lag-one autocorrelation of the first differences of the record's 171 annual
+    values, ``rscm_amd.variability.series_variability(record, "difference")`` -- the estimator ``Ensemble.variability`` applies to
+    every member on the device;
+  * their sigmas are the sampling errors of the two statistics over n differences, ``sd / sqrt(2 n)`` and ``sqrt((1 - r1^2) / n)``,
+    times ``sqrt(2)``: the record and a member are one realisation each, so the difference of their statistics carries both errors;
+  * ``loglik_vectors`` scores the members by the statistics alone and added onto the point likelihood; the sigma / phi quantiles and
+    the effective sample size of all three weightings are printed beside the prior.  The statistics constrain a ridge, not a point:
+    the temperature's variability depends on sigma, phi, the feedback and the heat capacities jointly.
 
     python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast]
 
@@ -25,6 +34,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rscm_amd  # noqa: E402
+from rscm_amd.variability import series_variability  # noqa: E402
 
 Q = [0.05, 0.17, 0.5, 0.83, 0.95]
 YEARS = np.arange(1850.0, 2101.0)
@@ -71,7 +81,8 @@ def main():
         truth.set_params(TRUTH[:, None])
         truth.run(NOW)
         rows = np.arange(5, NOW + 1, 5)
-        record = truth.get_series(TS, 0, NOW + 1)[rows, 0]
+        annual = truth.get_series(TS, 0, NOW + 1)[:, 0]
+        record = annual[rows]
 
     with make(a.members, mode, seed=1) as ens:
         sigma_row, phi_row = ens.noise_param_rows
@@ -98,10 +109,30 @@ def main():
             last = dst.get_series(TS, len(YEARS) - 1)[0]
             checks["draws_of_one_ancestor_diverge"] = bool(twins.size == 0 or (last[twins] != last[twins + 1]).any())
 
+        # the record's variability as the target: by the statistics alone, and added onto the point likelihood (ll, in place)
+        target = series_variability(annual, "difference")
+        n_diff = annual.size - 1
+        values = [target["sd"], target["r1"]]
+        sigmas = [np.sqrt(2.0) * target["sd"] / np.sqrt(2.0 * n_diff), np.sqrt(2.0) * np.sqrt((1.0 - target["r1"] ** 2) / n_diff)]
+        var = ens.variability(TS, 0, NOW + 1, detrend="difference")
+        stats = [var["sd"], var["r1"]]
+        constraint = {}
+        for name, add_to in (("both", ll), ("statistics", None)):
+            ens.set_weights_from_loglik(ens.loglik_vectors(stats, values, sigmas, add_to=add_to))
+            q = ens.quantile_vectors(vectors, Q, weighted=True)["quantiles"]
+            constraint[name] = {"sigma": q[0].tolist(), "phi": q[1].tolist(), "ess": ens.weights_stats()["ess"]}
+        w = ens.member_weights()
+        checks["statistics_weighted_quantiles_equal_numpy"] = bool(np.array_equal(
+            [constraint["statistics"]["sigma"], constraint["statistics"]["phi"]], np.stack([np_weighted(P[sigma_row], w), np_weighted(P[phi_row], w)])))
+
     res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
            "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
            "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
            "weighted": {"sigma": post[0].tolist(), "phi": post[1].tolist()},
+           "variability_target": {"sd": values[0], "r1": values[1], "sd_sigma": float(sigmas[0]), "r1_sigma": float(sigmas[1])},
+           "constraint": {"prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
+                          "point": {"sigma": post[0].tolist(), "phi": post[1].tolist(), "ess": ess},
+                          "statistics": constraint["statistics"], "both": constraint["both"]},
            "posterior_plume_2100_K": plume.tolist(), "checks": checks}
     print(json.dumps(res), flush=True)
     sys.exit(0 if all(checks.values()) else 1)
