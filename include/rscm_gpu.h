@@ -97,8 +97,10 @@ extern "C" {
  *      rscm_ens_set_forcing_noise_members, rscm_ens_forcing_noise_members
  *  16  per-member variability statistics (mean, trend, variance, sd, lag-one autocorrelation) and a Gaussian likelihood over
  *      per-member device vectors: rscm_ens_member_variability, RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE,
- *      rscm_ens_loglik_vectors_device */
-#define RSCM_GPU_ABI_MINOR 16
+ *      rscm_ens_loglik_vectors_device
+ *  17  per-member power spectra in frequency bands and a spectral (Whittle-type) likelihood over them: rscm_ens_member_spectrum,
+ *      rscm_gpu_spectrum_coefficients, rscm_ens_loglik_spectrum_device */
+#define RSCM_GPU_ABI_MINOR 17
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1114,6 +1116,57 @@ RSCM_API int rscm_ens_member_variability(rscm_ens* h, int32_t var_id, int32_t t_
  * call with add_dev = its result. */
 RSCM_API int rscm_ens_loglik_vectors_device(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* value,
                                             const double* sigma, const double* add_dev, void** out_dev);
+
+/* ---- per-member power spectra and a spectral likelihood (ABI minor 17) ---------------------------- */
+/* How each member's variability of var_id is spread over periods: the periodogram of the detrended series, averaged over bands of
+ * frequencies, per member, on the device.  The lag-one autocorrelation of rscm_ens_member_variability cannot tell strong short-lived
+ * noise from weak persistent noise once the ocean has filtered it; the shape of the spectrum over all resolved periods can.  This is
+ * the one definition; the kernel (spectrum.hip), rscm_amd.variability.series_spectrum and the tests' numpy restatement apply it
+ * operation by operation.
+ *   Rows, working series u_k, n, m, b, tau_k and the residuals a_k: EXACTLY those of rscm_ens_member_variability for the same mode --
+ *   the same three detrenders, n >= 3, the same operations in the same order.  Also n <= 4096 (RSCM_ERR_INVALID beyond), which bounds
+ *   the rounding error of the recurrence below (it grows with n and towards the lowest frequencies).
+ *   Frequencies j = 1 .. J, J = (n - 1) / 2 in integer division: the mean and, for even n, the Nyquist term are left out, so every
+ *   ordinate has two degrees of freedom.
+ *   Coefficients c2_j = 2 * C_j, C_j the double nearest cos(2 pi j / n), formed by the library on the host (j / n reduced by symmetry in
+ *   integers, then evaluated in long double; the doubling is exact); rscm_gpu_spectrum_coefficients returns the table the kernel is
+ *   given, and a restatement takes it from there, so that nothing depends on the caller's cosine.
+ *   Ordinate, by Goertzel's recurrence; every operation is one f64 operation rounded on its own (no FMA):
+ *     s1 = s2 = +0.0;  for k = 0 .. n - 1 in order:  s0 = (a_k + c2_j*s1) - s2;  s2 = s1;  s1 = s0
+ *     I_j = ((s1*s1 + s2*s2) - (c2_j*s1)*s2) / (double)n
+ *   With this scaling the mean ordinate of white noise is its variance, and (2 / n) (I_1 + ... + I_J) is the variance for odd n.
+ *   Bands: n_bands (1 .. 8) and edges[n_bands + 1], strictly ascending with edges[0] >= 1 and edges[n_bands] <= J + 1, else
+ *   RSCM_ERR_INVALID.  Band b holds the frequencies edges[b] <= j < edges[b + 1], m_b of them;
+ *     P_b = (I_{edges[b]} + I_{edges[b] + 1} + ...) / (double)m_b,  summed left to right in ascending j.
+ * [3 + n_bands][N] doubles from *out_dev: mean (m), slope (b), variance (C0 / n, the bits of rscm_ens_member_variability's: the band
+ * powers should add up to it), then P_0 .. P_{n_bands - 1}.  A member with a non-finite value in any of its rows gets NaN in every
+ * vector.  A constant working series has variance 0 and every P_b = 0.
+ * The result is written to indicator slot `slot` (a slot's block is [3 + 8][N]); slot rules and refusals are those of
+ * rscm_ens_member_variability: a bad slot or mode RSCM_ERR_INVALID, rows not computed or not resident or a select in flight
+ * RSCM_ERR_STATE.  Bit-exact against the restatement. */
+RSCM_API int rscm_ens_member_spectrum(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t mode,
+                                      int32_t n_bands, const int32_t* edges, int32_t slot, void** out_dev);
+/* out[J], J = (n - 1) / 2: c2_j = 2 * (the double nearest cos(2 pi j / n)) at out[j - 1], the table rscm_ens_member_spectrum gives its
+ * kernel for a working series of n terms; within 1 ulp of 2 cos(2 pi j / n), and +0.0 exactly where the cosine is zero.  Host only
+ * (no device is touched).  3 <= n <= 4096, else RSCM_ERR_INVALID. */
+RSCM_API int rscm_gpu_spectrum_coefficients(int32_t n, double* out /*[J]*/);
+/* A spectral likelihood over per-member band powers, continuing a point likelihood.  Under the hypothesis that the record is one more
+ * realisation of the member's process, the member's band power P_b and the record's I_b are two independent estimates of the same
+ * spectrum with 2 m_b degrees of freedom each, so I_b / P_b ~ F(2 m_b, 2 m_b) -- the approximation Whittle makes, applied to both
+ * sides.  The log density of I_b given P_b, member-independent terms dropped, is
+ *     ll_b = m_b * (ln P_b - 2 ln(P_b + I_b)),
+ * maximal at P_b = I_b; as m_b grows it tends to Whittle's -(ln S + I / S) per ordinate.
+ * vec_dev[n_vec] (a host array) holds device addresses of N doubles (band powers of rscm_ens_member_spectrum), checked as
+ * rscm_ens_loglik_vectors_device checks its vectors; 1 <= n_vec <= 16; record[j] (the record's I_b) finite and > 0, count[j] (m_b) >= 1,
+ * else RSCM_ERR_INVALID.  Per member i: partial = 0.0; for j in order t = P + record[j], term = (double)count[j] * (ln(P) - 2.0 * ln(t)),
+ * partial += term, with P = v_j[i]; the result is add_dev[i] + partial, or 0.0 + partial with add_dev NULL.  P non-finite or <= 0 gives
+ * -inf (a constant series has no spectrum); so does a non-finite add_dev[i].
+ * Because of the logarithm (the library's hand-written ln, within 1 ulp) this call is TOLERANCE-parity, not bit-exact: per member
+ * within (4 + n_vec) 2^-52 (|add_i| + sum_j m_j (|ln P_j| + 2 |ln t_j|)) of the expressions above evaluated exactly.  The statistic
+ * itself, rscm_ens_member_spectrum, stays bit-exact.
+ * The result lands in the handle's likelihood vector (*out_dev); add_dev may BE that buffer, as for rscm_ens_loglik_vectors_device. */
+RSCM_API int rscm_ens_loglik_spectrum_device(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* record,
+                                             const int32_t* count, const double* add_dev, void** out_dev);
 
 /* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
 /* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,

@@ -344,6 +344,10 @@ SIGNATURES = {
                                              C.POINTER(C.c_void_p)]),
     "rscm_ens_member_variability": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
     "rscm_ens_loglik_vectors_device": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), _dp, _dp, _dp, C.POINTER(C.c_void_p)]),
+    "rscm_ens_member_spectrum": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
+                                           C.POINTER(C.c_void_p)]),
+    "rscm_gpu_spectrum_coefficients": (C.c_int, [C.c_int32, _dp]),
+    "rscm_ens_loglik_spectrum_device": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), _dp, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_void_p)]),
     "rscm_ens_quantile_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, _dp]),
     "rscm_ens_select_begin_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32]),
     "rscm_ens_exceedance": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

@@ -1512,6 +1512,13 @@ class GraphModel:
         ens, vid = self.variable_home(name)
         return ens.variability(vid, t_begin, t_end, t_stride, detrend, slot)
 
+    def spectrum(self, name: str, t_begin: int, t_end: int, t_stride: int = 1, detrend: str = "difference", bands=8,
+                 slot: int = 0) -> Dict[str, object]:
+        """``Ensemble.spectrum`` of ``name`` on its home ensemble: device vectors ``mean``, ``slope``, ``variance`` and the band
+        powers ``power``, with the bands' ``edges`` and ``counts``; ``Ensemble.loglik_spectrum`` and ``quantile_vectors`` read them."""
+        ens, vid = self.variable_home(name)
+        return ens.spectrum(vid, t_begin, t_end, t_stride, detrend, bands, slot)
+
     def quantile_vectors(self, vectors, q, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """``Ensemble.quantile_vectors`` on the ensemble that owns the vectors (every ensemble of the graph shares the member
         index and, after ``set_member_weights`` / ``set_weights_from_loglik`` / ``set_member_groups``, the weights and groups)."""

@@ -901,6 +901,24 @@ struct LoglikVectors {
     double value[kMaxLoglikVectors], sigma[kMaxLoglikVectors];
 };
 hipError_t launch_loglik_vectors(const LoglikVectors& v, int32_t n_vec, const double* d_add, int64_t N, double* d_out, hipStream_t s);
+// per-member band powers (spectrum.hip) over rows d_rows[n_rows][N], mode and stt as launch_variability: d_out[3 + n_bands][N] = mean,
+// slope, variance, then the mean periodogram ordinate of each band (the definition is stated in include/rscm_gpu.h,
+// rscm_ens_member_spectrum).  d_c2[J] = 2 cos(2 pi j / n), j = 1 .. J = (n - 1) / 2, of the working series' length n (d_c2[j - 1];
+// rscm_gpu_spectrum_coefficients) followed by kSpectrumTablePad zeros, which the last tile of frequencies reads and does not use;
+// d_edges[n_bands + 1] int32 with 1 <= d_edges[0] < ... < d_edges[n_bands] <= J + 1: the caller
+// has checked them, the kernel reads d_c2 and writes d_out by them
+constexpr int kMaxSpectrumBands = 8;
+constexpr int kSpectrumTablePad = 32;
+static_assert(kMaxSpectrumBands <= kMaxThresholds, "the band powers share the indicator slots: [3 + kMaxThresholds][N]");
+hipError_t launch_spectrum(const double* const* d_rows, int32_t n_rows, int32_t mode, double stt, const double* d_c2, const int32_t* d_edges,
+                           int32_t n_bands, int64_t N, double* d_out, hipStream_t s);
+// d_out[i] = (d_add ? d_add[i] : 0.0) + sum over j < n_vec of count[j] (ln vec[j][i] - 2 ln(vec[j][i] + record[j])), -inf where a
+// vec[j][i] is not finite or <= 0 or d_add[i] is not finite; d_add may be d_out.  count[j] is the band's number of ordinates as a double.
+struct LoglikSpectrum {
+    const double* vec[kMaxLoglikVectors];
+    double record[kMaxLoglikVectors], count[kMaxLoglikVectors];
+};
+hipError_t launch_loglik_spectrum(const LoglikSpectrum& v, int32_t n_vec, const double* d_add, int64_t N, double* d_out, hipStream_t s);
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);

@@ -352,8 +352,10 @@ class ShardedEnsemble:
 
     def constrain_loglik(self, ll, bits: Optional[int] = None):
         """``constrain`` from a per-member log-likelihood of this rank's members (numpy or a ``DeviceVector``), e.g.
-        ``ensemble.loglik_vectors(...)`` over variability statistics, alone or added onto a point likelihood: the local max, a
-        MAX all-reduce, ``set_weights_from_loglik``.  Returns the ``(ll_max, bits)`` used, the same on every rank."""
+        ``ensemble.loglik_vectors(...)`` over variability statistics or ``ensemble.loglik_spectrum(...)`` over the band powers of
+        ``ensemble.spectrum(...)``, alone or added onto a point likelihood: the local max, a MAX all-reduce,
+        ``set_weights_from_loglik``.  Both statistics are per member -- a shard's vectors are the whole ensemble's, cut -- so the
+        sharded ensemble needs no entry point of its own for them.  Returns the ``(ll_max, bits)`` used, the same on every rank."""
         from .ensemble import default_weight_bits
         ll_max = self.ensemble.loglik_max(ll)
         if is_distributed():

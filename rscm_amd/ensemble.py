@@ -664,6 +664,55 @@ class Ensemble:
         L.check(self._lib.rscm_ens_loglik_vectors_device(self._h, n_vec, arr, L.dptr(val), L.dptr(sig), add, C.byref(p)))
         return DeviceVector(p.value, self.n_members, np.float64, self)
 
+    def spectrum(self, var, t_begin: int, t_end: int, t_stride: int = 1, detrend: str = "difference", bands=8, slot: int = 0) -> Dict[str, object]:
+        """Per-member power spectrum of ``var`` in frequency bands over the rows ``t_begin, t_begin + t_stride, ... < t_end``, left
+        on the device in indicator slot ``slot`` (the slots of ``indicators`` and ``variability``): ``{"mean", "slope", "variance",
+        "power": [one per band], "edges", "counts"}`` -- ``DeviceVector``s of ``[N]`` float64, and the band edges and the number of
+        frequencies per band as int32 arrays.  ``detrend`` as ``variability`` (``mean``, ``slope`` and ``variance`` are its bits).
+        ``bands``: how many bands (``rscm_amd.variability.band_edges`` then gives the edges; fewer come back when the series has
+        fewer frequencies) or an explicit list of 2 to 9 strictly ascending edges inside ``[1, J + 1]``, ``J = (n - 1) // 2`` of
+        the working series' ``n`` terms; band ``b`` holds the frequencies ``edges[b] <= j < edges[b + 1]`` (cycles per ``n``
+        terms).  ``power[b]`` is the mean periodogram ordinate of the band, scaled so that white noise has its variance there.
+        The definition is ``rscm_amd.variability.series_spectrum``'s, bit for bit (rscm_ens_member_spectrum).  3 to 4096 terms; a
+        member with a non-finite value in any row has NaN everywhere."""
+        from .variability import band_edges, detrend_mode
+        mode = detrend_mode(detrend)
+        n = len(range(int(t_begin), int(t_end), max(int(t_stride), 1))) - (1 if mode == L.VAR_DIFFERENCE else 0)
+        if isinstance(bands, (int, np.integer)):
+            edges = band_edges(n, int(bands)) if n >= 3 else np.array([1, 2], dtype=np.int32)    # (too short a series: the call refuses it)
+        else:
+            edges = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).ravel())
+            if edges.size < 2:
+                raise ValueError("bands: an explicit edge list needs at least two edges")
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_member_spectrum(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride), mode, edges.size - 1,
+                                                   edges.ctypes.data_as(C.POINTER(C.c_int32)), int(slot), C.byref(p)))
+        nm, base = self.n_members, p.value
+        vec = [DeviceVector(base + 8 * nm * j, nm, np.float64, self) for j in range(3 + edges.size - 1)]
+        return {"mean": vec[0], "slope": vec[1], "variance": vec[2], "power": vec[3:], "edges": edges,
+                "counts": np.diff(edges).astype(np.int32)}
+
+    def loglik_spectrum(self, power, record_power, counts, add_to: Optional[DeviceVector] = None) -> DeviceVector:
+        """Spectral log-likelihood per member over band powers (``spectrum(...)["power"]``) given the record's band powers
+        (``rscm_amd.variability.series_spectrum`` of the record with the same detrender and edges) and the bands' ``counts``:
+        ``sum_b counts[b] (ln P_b - 2 ln(P_b + record_power[b]))`` -- member and record as two realisations of one spectrum, the
+        F-ratio form of Whittle's likelihood, member-independent terms dropped -- added onto ``add_to`` (a device log-likelihood,
+        which may be overwritten in place) or onto zero.  A band power that is non-finite or ``<= 0``, or a non-finite
+        ``add_to``, gives ``-inf``.  The result is the handle's likelihood vector (rscm_ens_loglik_spectrum_device; to rounding,
+        not to the bit: it takes logarithms)."""
+        arr, n_vec = self._vectors(power)
+        rec = np.atleast_1d(L.f64(record_power))
+        cnt = np.ascontiguousarray(np.atleast_1d(np.asarray(counts, dtype=np.int32)))
+        if not (n_vec == len(rec) == len(cnt)):
+            raise ValueError("power, record_power and counts differ in length")
+        add = None
+        if add_to is not None:
+            add = self._vectors([add_to])[0][0]
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_loglik_spectrum_device(self._h, n_vec, arr, L.dptr(rec), cnt.ctypes.data_as(C.POINTER(C.c_int32)), add,
+                                                          C.byref(p)))
+        return DeviceVector(p.value, self.n_members, np.float64, self)
+
     def _vectors(self, vectors):
         vs = list(vectors)
         for v in vs:

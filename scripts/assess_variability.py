@@ -21,7 +21,12 @@ better), so the script then weights by the record's variability itself (DESIGN.m
     the effective sample size of all three weightings are printed beside the prior.  The statistics constrain a ridge, not a point:
     the temperature's variability depends on sigma, phi, the feedback and the heat capacities jointly.
 
-    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast]
+With ``--spectrum`` the record's power spectrum is the target as well: the band powers of the differences'
+periodogram, ``rscm_amd.variability.series_spectrum(record, "difference")`` against ``Ensemble.spectrum`` of every member, scored by
+``loglik_spectrum`` -- alone ("spectrum") and with the (sd, r1) likelihood added onto it ("spectrum_and_statistics").  One lag cannot
+tell strong short-lived noise from weak persistent noise once the ocean has filtered it; the spectrum's shape can.
+
+    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum]
 
 Prints one JSON line; exit code 0 iff every comparison holds."""
 import argparse
@@ -34,7 +39,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rscm_amd  # noqa: E402
-from rscm_amd.variability import series_variability  # noqa: E402
+from rscm_amd.variability import series_spectrum, series_variability  # noqa: E402
 
 Q = [0.05, 0.17, 0.5, 0.83, 0.95]
 YEARS = np.arange(1850.0, 2101.0)
@@ -73,6 +78,7 @@ def main():
     ap.add_argument("--members", type=int, default=100_000)
     ap.add_argument("--draws", type=int, default=20_000)
     ap.add_argument("--fast", action="store_true")
+    ap.add_argument("--spectrum", action="store_true", help="also weight by the record's band powers (loglik_spectrum)")
     a = ap.parse_args()
     mode = rscm_amd.MODE_FAST if a.fast else rscm_amd.MODE_EXACT
 
@@ -125,6 +131,23 @@ def main():
         checks["statistics_weighted_quantiles_equal_numpy"] = bool(np.array_equal(
             [constraint["statistics"]["sigma"], constraint["statistics"]["phi"]], np.stack([np_weighted(P[sigma_row], w), np_weighted(P[phi_row], w)])))
 
+        spectral = None
+        if a.spectrum:
+            rec = series_spectrum(annual, "difference")
+            spec = ens.spectrum(TS, 0, NOW + 1, detrend="difference", bands=rec["edges"], slot=1)
+            spectral = {"edges": rec["edges"].tolist(), "counts": rec["counts"].tolist(), "record_power": rec["power"]}
+            for name, with_stats in (("spectrum", False), ("spectrum_and_statistics", True)):
+                lls = ens.loglik_spectrum(spec["power"], rec["power"], rec["counts"])
+                if with_stats:
+                    lls = ens.loglik_vectors(stats, values, sigmas, add_to=lls)
+                ens.set_weights_from_loglik(lls)
+                q = ens.quantile_vectors(vectors, Q, weighted=True)["quantiles"]
+                constraint[name] = {"sigma": q[0].tolist(), "phi": q[1].tolist(), "ess": ens.weights_stats()["ess"]}
+            w = ens.member_weights()
+            checks["spectrum_weighted_quantiles_equal_numpy"] = bool(np.array_equal(
+                [constraint["spectrum_and_statistics"]["sigma"], constraint["spectrum_and_statistics"]["phi"]],
+                np.stack([np_weighted(P[sigma_row], w), np_weighted(P[phi_row], w)])))
+
     res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
            "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
            "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
@@ -134,6 +157,10 @@ def main():
                           "point": {"sigma": post[0].tolist(), "phi": post[1].tolist(), "ess": ess},
                           "statistics": constraint["statistics"], "both": constraint["both"]},
            "posterior_plume_2100_K": plume.tolist(), "checks": checks}
+    if spectral is not None:
+        res["spectrum_target"] = spectral
+        res["constraint"]["spectrum"] = constraint["spectrum"]
+        res["constraint"]["spectrum_and_statistics"] = constraint["spectrum_and_statistics"]
     print(json.dumps(res), flush=True)
     sys.exit(0 if all(checks.values()) else 1)
 
