@@ -114,36 +114,37 @@ struct rscm_ens {
     double* d_series = nullptr;  // [(V-1)][T][N], variable v at slot v-1
     double* d_forcing = nullptr; // [S][n_inputs][T]
     int32_t n_inputs = 1;        // rows per scenario of the shared input block
-    // rscm_ens_set_forcing_noise: member i is forced by F + noise_sigma * z(noise_seed, noise_offset + i, t) (forcing_noise.hpp)
-    bool noise_on = false;
+    // The forcing-noise setting (set_noise, rscm_gpu.cpp, behind rscm_ens_set_forcing_noise* and rscm_ens_clear_forcing_noise): member i
+    // is forced by F + e_t(noise_seed, noise_offset + i) of the kind noise_kind (rscm::kNoiseKind*; TwoLayerArgs, rscm_device.hpp).
+    // noise_sigma: white and red (0 otherwise); noise_phi: red (0 otherwise); the per-member kind reads both from parameter rows.
+    // The kinds that keep state (noise_red()): e is a pure function of (seed, sigma, phi, member id, t), and d_noise_state [N] caches
+    // every member's e at forcing-axis index noise_state_index (-1: nothing cached); allocated by the first such setting.  step_launch
+    // drops the index before a run's first launch and sets it after the whole run was issued; set_noise drops it.  A launch that does
+    // not find the index before its first re-forms e from the draws
+    int32_t noise_kind = rscm::kNoiseKindNone;
     uint64_t noise_seed = 0;
     double noise_sigma = 0.0;
-    int64_t noise_offset = 0;
-    // rscm_ens_set_forcing_noise_ar1 with phi != 0: the red term e_t, a pure function of (seed, sigma, phi, member id, t).  d_noise_state
-    // [N] caches every member's e at forcing-axis index noise_state_index (-1: nothing cached); allocated by the first red setting.
-    // step_launch drops the index before a run's first launch and sets it after the whole run was issued; every setter of the noise
-    // drops it.  A launch that does not find the index before its first re-forms e from the draws
     double noise_phi = 0.0;
+    int64_t noise_offset = 0;
     double* d_noise_state = nullptr;
     int32_t noise_state_index = -1;
     int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
-    // RSCM_FLAG_NOISE_PARAMS: the handle has the parameter rows noise_sigma_row() and noise_phi_row().  noise_members
-    // (rscm_ens_set_forcing_noise_members, with noise_on; noise_sigma and noise_phi are 0 then): e is formed per member from those rows as
-    // they stand at launch, so the cache is only as good as the rows.  The two rules, each kept in one place:
+    // RSCM_FLAG_NOISE_PARAMS: the handle has the parameter rows noise_sigma_row() and noise_phi_row() -- a fact of its shape, whatever
+    // the setting.  The per-member kind forms e from those rows as they stand at launch, so the cache is only as good as the rows.
+    // The two rules, each kept in one place:
     //   params_written()      whatever writes a parameter row calls it (rscm_ens_set_params[_aos], rscm_ens_sample_lhs,
     //                         rscm_ens_gather_members into the handle; a restore goes through rscm_ens_set_params): the index is dropped
     //   noise_cache_kept()    a run leaves its index behind only where nobody can write the rows unseen: never once
     //                         rscm_ens_params_devptr has handed the block out
     bool noise_rows = false;
-    bool noise_members = false;
     int32_t noise_sigma_row() const { return noise_rows ? 6 + n_comp : -1; }
     int32_t noise_phi_row() const { return noise_rows ? 6 + n_comp + 1 : -1; }
-    bool noise_red() const { return noise_on && (noise_members || noise_phi != 0.0); }   // the settings that cache e
-    bool noise_cache_kept() const { return !(noise_members && params_exposed); }
+    bool noise_red() const { return rscm::noise_kind_keeps_state(noise_kind); }   // the settings that cache e
+    bool noise_cache_kept() const { return !(noise_kind == rscm::kNoiseKindMembers && params_exposed); }
     void params_written()
     {
         derived_dirty = true;
-        if (noise_members) noise_state_index = -1;
+        if (noise_kind == rscm::kNoiseKindMembers) noise_state_index = -1;
     }
     double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;

@@ -290,21 +290,16 @@ void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, con
     a.count_guards = t_tl_count_guards;
     a.ts = h->series(RSCM_TL_VAR_TS);
     a.td = h->series(RSCM_TL_VAR_TD);
-    if (h->noise_on) {   // (rscm_ens_set_forcing_noise; step_launch refuses a linked or fused launch of such a handle)
-        a.noise_on = rscm::kNoiseWhite;
+    if (h->noise_kind) {   // (rscm_ens_set_forcing_noise*; step_launch refuses a linked or fused launch of such a handle)
+        a.noise_on = rscm::noise_code(h->noise_kind, false);
         a.noise_seed = h->noise_seed;
         a.noise_sigma = h->noise_sigma;
+        a.noise_phi = h->noise_phi;
         a.noise_member0 = h->noise_offset;
-        if (h->noise_phi != 0.0) {   // red: e at the index before this launch's first comes from the cache if it stands there
+        if (h->noise_red()) {   // e at the index before this launch's first comes from the cache if it stands there
             const int32_t t0 = step_begin + a.src_off;
-            a.noise_on = t0 > 0 && h->noise_state_index == t0 - 1 ? rscm::kNoiseRedCached : rscm::kNoiseRedSpinUp;
             a.noise_state = h->d_noise_state;
-            a.noise_phi = h->noise_phi;
-        }
-        if (h->noise_members) {   // sigma_i and phi_i are parameter rows 6 + n_comp and the next: the kernel reads them through a.params
-            const int32_t t0 = step_begin + a.src_off;
-            a.noise_on = t0 > 0 && h->noise_state_index == t0 - 1 ? rscm::kNoiseMembersCached : rscm::kNoiseMembersSpinUp;
-            a.noise_state = h->d_noise_state;
+            a.noise_on = rscm::noise_code(h->noise_kind, t0 > 0 && h->noise_state_index == t0 - 1);
         }
     }
 }
@@ -321,11 +316,11 @@ rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t 
     c.td = a.td + m0;
     c.status = a.status + m0;
     c.noise_member0 = a.noise_member0 + m0;   // the kernel counts members from the block's first: the noise is a function of the id in the ensemble
-    // red noise: a block's first chunk carries the run's decision, every later one loads what the chunk before it stored
+    // noise that keeps state: a block's first chunk carries the run's decision, every later one loads what the chunk before it stored
     // (run_member_split issues the chunks of one block on one stream, in order)
-    if (a.noise_on >= rscm::kNoiseRedSpinUp) {
+    if (rscm::noise_keeps_state(a.noise_on)) {
         c.noise_state = a.noise_state + m0;
-        if (begin != a.step_begin) c.noise_on = a.noise_on >= rscm::kNoiseMembersSpinUp ? rscm::kNoiseMembersCached : rscm::kNoiseRedCached;
+        if (begin != a.step_begin) c.noise_on = rscm::noise_code(rscm::noise_kind(a.noise_on), true);
     }
     return c;
 }
@@ -584,7 +579,7 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
     const rscm::Family family = h->info().family;
     if (h->n_comp > 0 && (linked || op_out))   // (rscm_ens_link_input and rscm_ens_run_lockstep refuse the handle before this)
         return fail(RSCM_ERR_INVALID, "a mix handle runs on its own: no linked input, no lock-step launch");
-    if (h->noise_on && (linked || op_out))   // (likewise refused before this)
+    if (h->noise_kind && (linked || op_out))   // (likewise refused before this)
         return fail(RSCM_ERR_INVALID, "a handle with forcing noise runs on its own: no linked input, no lock-step launch");
     if (op_out) {  // the step range is an argument of the fused launch, not part of the table
         if (!can_fuse(h)) return fail(RSCM_ERR_STATE, "this handle (kind %d) cannot be fused", h->kind);
@@ -611,11 +606,11 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
         case rscm::Family::TwoLayer: {
             rscm::TwoLayerArgs a{};
             fill_two_layer(h, step_begin, step_end, links, linked, a);
-            // the red noise's cache is dropped while the run is issued and stands at the run's last index only if all of it was
+            // the noise cache is dropped while the run is issued and stands at the run's last index only if all of it was
             if (step_end > step_begin) h->noise_state_index = -1;
             if (int rc = launch_whole_or_split(h, a, linked != 0, false, [mode](const rscm::TwoLayerArgs& c, hipStream_t st) { return rscm::launch_two_layer(c, mode, st); }))
                 return rc;
-            if (a.noise_on >= rscm::kNoiseRedSpinUp && step_end > step_begin && h->noise_cache_kept()) h->noise_state_index = step_end - 1 + a.src_off;
+            if (rscm::noise_keeps_state(a.noise_on) && step_end > step_begin && h->noise_cache_kept()) h->noise_state_index = step_end - 1 + a.src_off;
             return RSCM_OK;
         }
         case rscm::Family::Coupled: {

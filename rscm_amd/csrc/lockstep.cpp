@@ -366,7 +366,7 @@ int rscm_ens_run_lockstep(rscm_ens* const* handles, int32_t n_handles, int32_t s
         if (!handles[k]) return fail(RSCM_ERR_INVALID, "handle %d is NULL", k);
         if (handles[k]->n_comp > 0)
             return fail(RSCM_ERR_INVALID, "handle %d is a mix handle (rscm_ens_create_mix): it cannot be part of a lock-step run", k);
-        if (handles[k]->noise_on)
+        if (handles[k]->noise_kind)
             return fail(RSCM_ERR_INVALID, "handle %d has forcing noise (rscm_ens_set_forcing_noise): it cannot be part of a lock-step run", k);
         if (handles[k]->stream != handles[0]->stream)
             return fail(RSCM_ERR_STATE, "handle %d runs on another stream than handle 0", k);

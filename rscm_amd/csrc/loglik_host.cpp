@@ -347,7 +347,7 @@ static int run_loglik_impl(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, c
                            const int32_t* ref_var = nullptr, const int32_t* ref_begin = nullptr, const int32_t* ref_end = nullptr,
                            const int32_t* ref_stride = nullptr)
 {
-    if (h->noise_on)
+    if (h->noise_kind)
         return fail(RSCM_ERR_INVALID, "the fused run + likelihood is not available on a handle with forcing noise (rscm_ens_set_forcing_noise): "
                                       "run it and score the stored series with rscm_ens_loglik*");
     if (int rc = prepare_obs(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize)) return rc;

@@ -363,32 +363,54 @@ struct TwoLayerArgs {
     const double* obs_sigma;
     union {
         double* loglik;           // [N]
-        double* noise_state;      // [N] red noise (below): a stored run scores nothing and the fused likelihood carries no noise
+        double* noise_state;      // [N] the noise kinds that keep state (below): a stored run scores nothing and the fused likelihood carries no noise
     };
-    // Forcing noise (rscm_ens_set_forcing_noise; the NOISE instantiations: stand-alone stored runs, never linked).  noise_on 1: member
-    // i of this launch is forced by F' = F + noise_sigma * z(noise_seed, noise_member0 + i, t) at forcing-axis index t = n + src_off
-    // (forcing_noise.hpp).  noise_member0 is the id in the whole ensemble of the launch's first member: the handle's member_offset,
-    // plus the block's first member where the host launches a block (block_of, launch_host.cpp).  At the end: the other fields
-    // keep the offsets of the launches without it
+    // Forcing noise (rscm_ens_set_forcing_noise*; the NOISE instantiations: stand-alone stored runs, never linked).  noise_on is a
+    // kNoise* code (below): which kind of noise, noise_kind(), and for the kinds that keep state whether e is cached.  Member i of this
+    // launch is forced by F' = F + e_t at forcing-axis index t = n + src_off, z_t = z(noise_seed, noise_member0 + i, t) the stateless
+    // deviate of forcing_noise.hpp and every operation rounded on its own:
+    //   white    e_t = noise_sigma * z_t
+    //   red      e_0 = noise_sigma * z_0,    e_t = noise_phi * e_{t-1} + (noise_sigma * sqrt(1 - noise_phi^2)) * z_t
+    //   members  the red recurrence with member i's sigma_i and phi_i, read once per launch from parameter rows kTwoLayerCoeff0 + n_comp
+    //            and the one after it through `params` and `uniform_rows` like every other row; noise_sigma and noise_phi are not read
+    // noise_member0 is the id in the whole ensemble of the launch's first member: the handle's member_offset, plus the block's first
+    // member where the host launches a block (block_of, launch_host.cpp).  The kinds that keep state (noise_keeps_state()): noise_state[i]
+    // (above, in the place of the fused likelihood's result: the struct is full at the 240 bytes the op union allows) is member i's slot
+    // of the handle's cache, moved with the block like noise_member0.  A spin-up code: the launch forms e up to the index before its
+    // first from the draws (nothing to form when that first index is 0); a cached code: noise_state holds e there.  Either way the
+    // launch leaves e at the last index it drew, step_end - 1 + src_off, in noise_state.  At the end: the other fields keep the offsets
+    // of the launches without noise
     uint64_t noise_seed;
     double noise_sigma;
     int64_t noise_member0;
     int32_t noise_on;
-    // Red noise (rscm_ens_set_forcing_noise_ar1 with phi != 0; the NOISE == 2 instantiations): F' = F + e_t with
-    //     e_0 = noise_sigma * z(.., 0),    e_t = noise_phi * e_{t-1} + (noise_sigma * sqrt(1 - noise_phi^2)) * z(.., t),
-    // every operation rounded on its own.  noise_state[i] (above, in the place of the fused likelihood's result: the struct has eight
-    // bytes left of the 240 the op union allows) is member i's slot of the handle's cache, moved with the block like noise_member0.
-    // noise_on kNoiseRedSpinUp: the launch forms e up to the index before its first from the draws (nothing to form when that first
-    // index is 0); kNoiseRedCached: noise_state holds e at the index before its first.  Either way the launch leaves e at the last
-    // index it drew, step_end - 1 + src_off, in noise_state
-    // Per-member noise (rscm_ens_set_forcing_noise_members; the NOISE == 3 instantiations): the same recurrence with member i's sigma_i and
-    // phi_i, read once per launch from parameter rows kTwoLayerCoeff0 + n_comp and the one after it through `params` and `uniform_rows`
-    // like the six parameters and the coefficients; noise_sigma and noise_phi are not read.  noise_on kNoiseMembersSpinUp /
-    // kNoiseMembersCached say what the two red values say.  Nothing was added to the struct: it is full
     double noise_phi;
 };
-// TwoLayerArgs::noise_on (0: no noise).  From kNoiseRedSpinUp on the launch keeps e in noise_state
+// The kinds of forcing noise: a handle's setting (rscm_ens::noise_kind) and the NOISE template value of the two-layer kernels
+constexpr int32_t kNoiseKindNone = 0, kNoiseKindWhite = 1, kNoiseKindRed = 2, kNoiseKindMembers = 3;
+// TwoLayerArgs::noise_on (0: no noise): a kind, and for red and members whether noise_state holds e at the index before the launch's
+// first.  The kernels compare against these values and the ops of a fused launch are compared bytewise: the numbers are fixed.  What a
+// code means is stated by the three functions below and nowhere else
 constexpr int32_t kNoiseWhite = 1, kNoiseRedSpinUp = 2, kNoiseRedCached = 3, kNoiseMembersSpinUp = 4, kNoiseMembersCached = 5;
+constexpr int32_t noise_kind(int32_t on)   // kNoiseKindNone for 0 and for a value that is no code
+{
+    return on == kNoiseWhite                                         ? kNoiseKindWhite
+           : on == kNoiseRedSpinUp || on == kNoiseRedCached          ? kNoiseKindRed
+           : on == kNoiseMembersSpinUp || on == kNoiseMembersCached  ? kNoiseKindMembers
+                                                                     : kNoiseKindNone;
+}
+constexpr bool noise_kind_keeps_state(int32_t kind) { return kind == kNoiseKindRed || kind == kNoiseKindMembers; }
+constexpr bool noise_keeps_state(int32_t on) { return noise_kind_keeps_state(noise_kind(on)); }   // the launch reads or writes noise_state
+constexpr int32_t noise_code(int32_t kind, bool cached)
+{
+    return kind == kNoiseKindWhite     ? kNoiseWhite
+           : kind == kNoiseKindRed     ? (cached ? kNoiseRedCached : kNoiseRedSpinUp)
+           : kind == kNoiseKindMembers ? (cached ? kNoiseMembersCached : kNoiseMembersSpinUp)
+                                       : 0;
+}
+static_assert(noise_code(kNoiseKindWhite, true) == kNoiseWhite && noise_kind(noise_code(kNoiseKindMembers, true)) == kNoiseKindMembers &&
+                  noise_kind(noise_code(kNoiseKindRed, false)) == kNoiseKindRed && !noise_keeps_state(kNoiseWhite) && noise_kind(6) == kNoiseKindNone,
+              "noise_kind, noise_keeps_state and noise_code must agree");
 static_assert(sizeof(TwoLayerArgs) == 240, "TwoLayerArgs must not grow the fused launches' op union");
 
 // Reference periods of the fused likelihood (launch_two_layer_loglik_ref; DESIGN.md section 7, "Reference periods"), index 0: Surface
@@ -726,13 +748,12 @@ inline bool two_layer_fits_lds(int32_t n_scen, int32_t n_comp, int32_t len)
     return two_layer_lds_bytes(n_scen, n_comp, len) <= (size_t)kMaxLds - 1024;
 }
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
-// out[(t - t_begin) * n_members + i] = sigma * z(seed, member0 + i, t) for t in [t_begin, t_end): the term a noise handle adds to its forcing;
-// with phi != 0 the red term e_t (TwoLayerArgs::noise_phi), formed from index 0 on and written from t_begin on
-hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n_members, int32_t t_begin,
-                                     int32_t t_end, double* out, hipStream_t s);
-// the same for the per-member noise: member i's e_t from sigma_i = row sigma_row and phi_i = row phi_row of the [P][n_members] block
-hipError_t launch_forcing_noise_member_rows(uint64_t seed, const double* params, uint64_t uniform_rows, int32_t sigma_row, int32_t phi_row,
-                                            int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end, double* out, hipStream_t s);
+// out[(t - t_begin) * n_members + i] = e_t(seed, member0 + i) for t in [t_begin, t_end): the term a noise handle of this kind (kNoiseKind*,
+// not none) adds to its forcing (TwoLayerArgs).  White: sigma * z.  Red: formed from index 0 on and written from t_begin on.  Members:
+// the same from sigma_i = row sigma_row and phi_i = row phi_row of the [P][n_members] block; sigma and phi are not read
+hipError_t launch_forcing_noise_rows(int32_t kind, uint64_t seed, double sigma, double phi, const double* params, uint64_t uniform_rows,
+                                     int32_t sigma_row, int32_t phi_row, int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end,
+                                     double* out, hipStream_t stream);
 // z[j] = the deviate of the 52-bit integer k52[j] (test hook, rscm_gpu_selftest_normal)
 hipError_t launch_normal_selftest(const uint64_t* k52, int64_t n, double* z, hipStream_t s);
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s);

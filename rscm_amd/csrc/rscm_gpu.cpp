@@ -1031,7 +1031,7 @@ int rscm_ens_link_input(rscm_ens* h, int32_t input_row, rscm_ens* src, int32_t s
     if (h->n_comp > 0)
         return fail(RSCM_ERR_INVALID, "the forcing components of a mix handle (rscm_ens_create_mix) cannot be linked: they are shared "
                                       "scenario rows scaled per member");
-    if (h->noise_on)
+    if (h->noise_kind)
         return fail(RSCM_ERR_INVALID, "a handle with forcing noise (rscm_ens_set_forcing_noise) takes no linked input: the noise is added to "
                                       "its own shared forcing; clear the noise first");
     if (input_row < 0 || input_row >= h->n_inputs || input_row >= rscm::kMaxLinks)
@@ -1828,69 +1828,65 @@ int rscm_ens_ocean_fast_info(rscm_ens* h, int32_t* uses_recurrence, double* fit_
     return RSCM_OK;
 }
 
-int rscm_ens_set_forcing_noise_ar1(rscm_ens* h, uint64_t seed, double sigma, double phi, int64_t member_offset)
+// The one writer of a handle's forcing-noise setting (ens.hpp).  sigma: white and red; phi: red; 0 where the kind does not read them
+static int set_noise(rscm_ens* h, int32_t kind, uint64_t seed, double sigma, double phi, int64_t member_offset)
 {
     GUARD_BEGIN
-    NEED(h);
-    if (h->kind != RSCM_KIND_TWO_LAYER)
-        return fail(RSCM_ERR_INVALID, "forcing noise is available for the two-layer kind only (RSCM_KIND_TWO_LAYER), this handle has kind %d", h->kind);
-    if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(RSCM_ERR_INVALID, "sigma must be finite and not negative, got %g", sigma);
-    if (!std::isfinite(phi) || !(std::fabs(phi) < 1.0)) return fail(RSCM_ERR_INVALID, "phi must be finite with |phi| < 1, got %g", phi);
-    if (member_offset < 0) return fail(RSCM_ERR_INVALID, "member_offset must not be negative, got %lld", (long long)member_offset);
-    if (h->windowed || h->rows != h->T)
-        return fail(RSCM_ERR_INVALID, "forcing noise needs a handle that stores its whole series (no windowed storage, no RSCM_FLAG_NO_SERIES)");
-    if (h->n_linked > 0) return fail(RSCM_ERR_INVALID, "this handle has a linked input: the noise is added to a handle's own shared forcing");
-    if (phi != 0.0 && !h->d_noise_state) {   // (phi == 0 is the white setting: the white kernels, no buffer)
+    if (kind != rscm::kNoiseKindNone) {
+        if (h->kind != RSCM_KIND_TWO_LAYER)
+            return fail(RSCM_ERR_INVALID, "forcing noise is available for the two-layer kind only (RSCM_KIND_TWO_LAYER), this handle has kind %d", h->kind);
+        if (!(sigma >= 0.0) || !std::isfinite(sigma)) return fail(RSCM_ERR_INVALID, "sigma must be finite and not negative, got %g", sigma);
+        if (!std::isfinite(phi) || !(std::fabs(phi) < 1.0)) return fail(RSCM_ERR_INVALID, "phi must be finite with |phi| < 1, got %g", phi);
+        if (member_offset < 0) return fail(RSCM_ERR_INVALID, "member_offset must not be negative, got %lld", (long long)member_offset);
+        if (h->windowed || h->rows != h->T)
+            return fail(RSCM_ERR_INVALID, "forcing noise needs a handle that stores its whole series (no windowed storage, no RSCM_FLAG_NO_SERIES)");
+        if (h->n_linked > 0) return fail(RSCM_ERR_INVALID, "this handle has a linked input: the noise is added to a handle's own shared forcing");
+    }
+    if (rscm::noise_kind_keeps_state(kind) && !h->d_noise_state) {
         if (int rc = set_device(h)) return rc;
         HIPCHK(rscm::dev_malloc(&h->d_noise_state, (size_t)h->N * sizeof(double)));
     }
-    h->noise_on = true;
+    h->noise_kind = kind;
     h->noise_seed = seed;
     h->noise_sigma = sigma;
-    h->noise_phi = phi == 0.0 ? 0.0 : phi;   // (-0.0 is white too)
-    h->noise_members = false;
+    h->noise_phi = phi;
     h->noise_offset = member_offset;
     h->noise_state_index = -1;   // the cache belonged to the setting before
     return RSCM_OK;
     GUARD_END
 }
 
+int rscm_ens_set_forcing_noise_ar1(rscm_ens* h, uint64_t seed, double sigma, double phi, int64_t member_offset)
+{
+    NEED(h);
+    if (phi == 0.0) return set_noise(h, rscm::kNoiseKindWhite, seed, sigma, 0.0, member_offset);   // (-0.0 is white too: the white kernels, no buffer)
+    return set_noise(h, rscm::kNoiseKindRed, seed, sigma, phi, member_offset);
+}
+
 int rscm_ens_set_forcing_noise(rscm_ens* h, uint64_t seed, double sigma, int64_t member_offset)
 {
-    return rscm_ens_set_forcing_noise_ar1(h, seed, sigma, 0.0, member_offset);
+    NEED(h);
+    return set_noise(h, rscm::kNoiseKindWhite, seed, sigma, 0.0, member_offset);
 }
 
 int rscm_ens_set_forcing_noise_members(rscm_ens* h, uint64_t seed, int64_t member_offset)
 {
-    GUARD_BEGIN
     NEED(h);
     if (!h->noise_rows)
         return fail(RSCM_ERR_INVALID, "this handle has no noise parameter rows: create it with RSCM_FLAG_NOISE_PARAMS");
-    // a red setting with placeholder numbers: its refusals, the cache buffer, the dropped index
-    if (int rc = rscm_ens_set_forcing_noise_ar1(h, seed, 0.0, 0.5, member_offset)) return rc;
-    h->noise_phi = 0.0;   // sigma and phi are the rows' from here on
-    h->noise_members = true;
-    return RSCM_OK;
-    GUARD_END
+    return set_noise(h, rscm::kNoiseKindMembers, seed, 0.0, 0.0, member_offset);   // sigma and phi are the rows'
 }
 
 int rscm_ens_clear_forcing_noise(rscm_ens* h)
 {
     NEED(h);
-    h->noise_on = false;
-    h->noise_seed = 0;
-    h->noise_sigma = 0.0;
-    h->noise_phi = 0.0;
-    h->noise_members = false;
-    h->noise_offset = 0;
-    h->noise_state_index = -1;
-    return RSCM_OK;
+    return set_noise(h, rscm::kNoiseKindNone, 0, 0.0, 0.0, 0);
 }
 
 int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, double* sigma, int64_t* member_offset)
 {
     NEED(h);
-    if (on) *on = h->noise_on ? 1 : 0;
+    if (on) *on = h->noise_kind != rscm::kNoiseKindNone ? 1 : 0;
     if (seed) *seed = h->noise_seed;
     if (sigma) *sigma = h->noise_sigma;
     if (member_offset) *member_offset = h->noise_offset;
@@ -1900,16 +1896,15 @@ int rscm_ens_forcing_noise(const rscm_ens* h, int32_t* on, uint64_t* seed, doubl
 int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t* cached_index)
 {
     NEED(h);
-    const bool red = h->noise_red();
-    if (phi) *phi = red ? h->noise_phi : 0.0;
-    if (cached_index) *cached_index = red ? h->noise_state_index : -1;
+    if (phi) *phi = h->noise_phi;
+    if (cached_index) *cached_index = h->noise_red() ? h->noise_state_index : -1;
     return RSCM_OK;
 }
 
 int rscm_ens_forcing_noise_members(const rscm_ens* h, int32_t* per_member, int32_t* sigma_row, int32_t* phi_row)
 {
     NEED(h);
-    if (per_member) *per_member = h->noise_on && h->noise_members ? 1 : 0;
+    if (per_member) *per_member = h->noise_kind == rscm::kNoiseKindMembers ? 1 : 0;
     if (sigma_row) *sigma_row = h->noise_sigma_row();
     if (phi_row) *phi_row = h->noise_phi_row();
     return RSCM_OK;
@@ -1919,7 +1914,7 @@ int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, dou
 {
     GUARD_BEGIN
     NEED(h);
-    if (!h->noise_on) return fail(RSCM_ERR_STATE, "this handle has no forcing noise (rscm_ens_set_forcing_noise)");
+    if (!h->noise_kind) return fail(RSCM_ERR_STATE, "this handle has no forcing noise (rscm_ens_set_forcing_noise)");
     if (t_begin < 0 || t_end < t_begin || t_end > h->T)
         return fail(RSCM_ERR_INVALID, "rows [%d, %d) are not within the forcing axis [0, %d)", t_begin, t_end, h->T);
     if (t_end == t_begin) return RSCM_OK;
@@ -1928,10 +1923,8 @@ int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, dou
     const size_t bytes = (size_t)(t_end - t_begin) * (size_t)h->N * sizeof(double);
     double* d = out;
     if (!on_device) HIPCHK(rscm::dev_malloc(&d, bytes));
-    hipError_t e = h->noise_members
-                       ? rscm::launch_forcing_noise_member_rows(h->noise_seed, h->d_params, h->uniform_rows, h->noise_sigma_row(), h->noise_phi_row(),
-                                                                h->noise_offset, h->N, t_begin, t_end, d, h->stream)
-                       : rscm::launch_forcing_noise_rows(h->noise_seed, h->noise_sigma, h->noise_phi, h->noise_offset, h->N, t_begin, t_end, d, h->stream);
+    hipError_t e = rscm::launch_forcing_noise_rows(h->noise_kind, h->noise_seed, h->noise_sigma, h->noise_phi, h->d_params, h->uniform_rows,
+                                                   h->noise_sigma_row(), h->noise_phi_row(), h->noise_offset, h->N, t_begin, t_end, d, h->stream);
     if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
     if (e == hipSuccess && !on_device) e = hipStreamSynchronize(h->stream);
     if (!on_device) (void)hipFree(d);

@@ -269,7 +269,7 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
     rscm_ens* h = evaluator;
     NEED(h);
     if (h->windowed) return fail(RSCM_ERR_INVALID, "the sampler's evaluator must not be a windowed ensemble");
-    if (h->noise_on)
+    if (h->noise_kind)
         return fail(RSCM_ERR_INVALID, "the evaluating ensemble has forcing noise (rscm_ens_set_forcing_noise): the likelihood of one noise "
                                       "realisation per walker index is not a target the stretch move samples; clear the noise first");
     if (int rc = check_walkers(n_walkers, rank, n_ranks, stretch_a)) return rc;
@@ -346,7 +346,7 @@ int rscm_sampler_create_graph(rscm_ens* const* handles, int32_t n_handles, int32
         if (h->n_comp > 0)
             return fail(RSCM_ERR_INVALID, "handle %d is a mix handle (rscm_ens_create_mix): it cannot be part of a graph sampler; "
                                           "rscm_sampler_create takes it as its one evaluator", k);
-        if (h->noise_on)
+        if (h->noise_kind)
             return fail(RSCM_ERR_INVALID, "handle %d has forcing noise (rscm_ens_set_forcing_noise): it cannot be part of a graph sampler", k);
         if (h->N != n_walkers / 2 / n_ranks)
             return fail(RSCM_ERR_INVALID, "handle %d: every ensemble of the graph must have n_walkers / 2 / n_ranks = %d members, it has %lld", k,

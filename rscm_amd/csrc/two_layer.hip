@@ -36,6 +36,8 @@
 // division and unfused doubling.  Either way the stored bits equal the reference's arithmetic.
 #include "two_layer_body.hpp"
 
+#include <type_traits>
+
 namespace rscm {
 
 namespace {
@@ -45,8 +47,8 @@ namespace {
 __device__ unsigned long long g_guard_counts[tl::kGuardKinds];
 
 // MIX: a mix handle's launch (a.n_comp >= 1): the staged table is [n_scen][n_comp][len], n_scen * n_comp rows laid out like scenarios
-// NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing, 1 white,
-// 2 red (a.noise_on kNoiseRedSpinUp or kNoiseRedCached), 3 red with per-member sigma and phi (kNoiseMembersSpinUp or kNoiseMembersCached)
+// NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing, of the
+// kind noise_kind(a.noise_on): kNoiseKindWhite, kNoiseKindRed, or kNoiseKindMembers (red with per-member sigma and phi)
 template <int MODE, bool LDS, bool STORE, bool MIX = false, int NOISE = 0>
 __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
 {
@@ -68,55 +70,34 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     }
 }
 
-// sigma * z for rows [t_begin, t_end) x n members: what a noise handle adds to its forcing (rscm_ens_forcing_noise_rows)
-__global__ __launch_bounds__(kBlock) void forcing_noise_rows_kernel(uint64_t seed, double sigma, int64_t member0, int64_t n, int32_t t_begin,
-                                                                    int32_t t_end, double* out)
+// e_t for rows [t_begin, t_end) x n members: what a noise handle of kind KIND adds to its forcing (rscm_ens_forcing_noise_rows).  White:
+// sigma * z, as written.  Red: e_t of two_layer_body.hpp, formed from index 0 on by the same statements and written from t_begin on;
+// per-member: the same with sigma and phi member i's, read the way the stepping kernel reads them
+template <int KIND>
+__global__ __launch_bounds__(kBlock) void forcing_noise_rows_kernel(uint64_t seed, double sigma, double phi, const double* params,
+                                                                    uint64_t uniform_rows, int32_t sigma_row, int32_t phi_row, int64_t member0,
+                                                                    int64_t n, int32_t t_begin, int32_t t_end, double* out)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
     const uint64_t g = (uint64_t)(member0 + i);
     double* o = out + i;
-    for (int32_t t = t_begin; t < t_end; ++t, o += n) *o = sigma * noise::draw(seed, g, (uint32_t)t);
-}
-
-// the same for red noise: e_t of two_layer_body.hpp, formed from index 0 on by the same statements and written from t_begin on
-__global__ __launch_bounds__(kBlock) void forcing_noise_red_rows_kernel(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n,
-                                                                        int32_t t_begin, int32_t t_end, double* out)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t g = (uint64_t)(member0 + i);
-    double* o = out + i;
-    const double se = sigma * __builtin_sqrt(1.0 - phi * phi);
-    double e = 0.0;
-    for (int32_t t = 0; t < t_end; ++t) {
-        const double z = noise::draw(seed, g, (uint32_t)t);
-        e = t == 0 ? sigma * z : (phi * e) + (se * z);
-        if (t >= t_begin) {
-            *o = e;
-            o += n;
+    if constexpr (KIND == kNoiseKindWhite) {   // (not the recurrence with phi = 0: (0 * e) + (sigma * z) has another zero's sign, and NaN once e is not finite)
+        for (int32_t t = t_begin; t < t_end; ++t, o += n) *o = sigma * noise::draw(seed, g, (uint32_t)t);
+    } else {
+        if constexpr (KIND == kNoiseKindMembers) {
+            sigma = param_at(params, uniform_rows, sigma_row, n, i);
+            phi = param_at(params, uniform_rows, phi_row, n, i);
         }
-    }
-}
-
-// the same for the per-member noise: sigma and phi are member i's, read the way the stepping kernel reads them
-__global__ __launch_bounds__(kBlock) void forcing_noise_member_rows_kernel(uint64_t seed, const double* params, uint64_t uniform_rows,
-                                                                           int32_t sigma_row, int32_t phi_row, int64_t member0, int64_t n,
-                                                                           int32_t t_begin, int32_t t_end, double* out)
-{
-    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    const uint64_t g = (uint64_t)(member0 + i);
-    double* o = out + i;
-    const double sigma = param_at(params, uniform_rows, sigma_row, n, i), phi = param_at(params, uniform_rows, phi_row, n, i);
-    const double se = sigma * __builtin_sqrt(1.0 - phi * phi);
-    double e = 0.0;
-    for (int32_t t = 0; t < t_end; ++t) {
-        const double z = noise::draw(seed, g, (uint32_t)t);
-        e = t == 0 ? sigma * z : (phi * e) + (se * z);
-        if (t >= t_begin) {
-            *o = e;
-            o += n;
+        const double se = sigma * __builtin_sqrt(1.0 - phi * phi);
+        double e = 0.0;
+        for (int32_t t = 0; t < t_end; ++t) {
+            const double z = noise::draw(seed, g, (uint32_t)t);
+            e = t == 0 ? sigma * z : (phi * e) + (se * z);
+            if (t >= t_begin) {
+                *o = e;
+                o += n;
+            }
         }
     }
 }
@@ -160,55 +141,76 @@ __global__ __launch_bounds__(kBlock) void two_layer_ref_kernel(TwoLayerArgs a, T
 // cut runs take 2.31, the queue 2.45 with one wavefront per SIMD and worse with more (fewer blocks than wavefronts: every task waits for
 // its predecessor).  DESIGN.md section 4.1, profiles/r5_queue_experiment.txt, commit history of this file.)
 
+namespace {
+
+// The eight shapes of a two-layer kernel, told apart in this one place: f is called with (MODE, LDS, MIX) as integral constants
+template <class F>
+constexpr auto with_shape(int mode, bool lds, bool mix, F f)
+{
+    auto with_mix = [&](auto M, auto L) { return mix ? f(M, L, std::true_type{}) : f(M, L, std::false_type{}); };
+    auto with_lds = [&](auto M) { return lds ? with_mix(M, std::true_type{}) : with_mix(M, std::false_type{}); };
+    return mode == 0 ? with_lds(std::integral_constant<int, 0>{}) : with_lds(std::integral_constant<int, 1>{});
+}
+
+// The families: the stepping kernel per (STORE, NOISE), and the fused likelihood with reference periods
+using StepKernel = void (*)(TwoLayerArgs);
+using RefKernel = void (*)(TwoLayerArgs, TwoLayerRefArgs);
+template <bool STORE, int NOISE>
+constexpr StepKernel step_kernel(int mode, bool lds, bool mix)
+{
+    return with_shape(mode, lds, mix, [](auto M, auto L, auto X) -> StepKernel { return two_layer_kernel<M(), L(), STORE, X(), NOISE>; });
+}
+constexpr RefKernel ref_kernel(int mode, bool lds, bool mix)
+{
+    return with_shape(mode, lds, mix, [](auto M, auto L, auto X) -> RefKernel { return two_layer_ref_kernel<M(), L(), X()>; });
+}
+// (a transposed index fails the build here, not a run)
+static_assert(step_kernel<true, kNoiseKindRed>(0, true, false) == two_layer_kernel<0, true, true, false, 2>);
+static_assert(step_kernel<true, kNoiseKindMembers>(1, false, true) == two_layer_kernel<1, false, true, true, 3>);
+static_assert(step_kernel<false, kNoiseKindNone>(1, true, false) == two_layer_kernel<1, true, false, false, 0>);
+static_assert(ref_kernel(0, false, true) == two_layer_ref_kernel<0, false, true>);
+
+}  // namespace
+
+// What every two-layer launch is refused for: a component count out of range, a linked mix launch, a noise code that is none
+// (rscm_device.hpp), noise that is linked, and noise that keeps state without the state
+static bool args_ok(const TwoLayerArgs& a)
+{
+    if (a.n_comp < 0 || a.n_comp > kMaxForcingComponents || (a.n_comp > 0 && a.link)) return false;
+    if (a.noise_on && (a.link || noise_kind(a.noise_on) == kNoiseKindNone)) return false;
+    return !noise_keeps_state(a.noise_on) || a.noise_state;
+}
+
+// ... and how every one of them ends: `rest` is what the kernel takes after the arguments
+template <class... Rest>
+static hipError_t launch_shaped(void (*kern)(TwoLayerArgs, Rest...), const TwoLayerArgs& a, hipStream_t s, const Rest&... rest)
+{
+    const size_t lds = a.lds_forcing ? two_layer_lds_bytes(a.n_scen, a.n_comp, a.step_end - a.step_begin) : 0;
+    const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
+    if (lds > (size_t)kMaxStaticLds) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, s, a, rest...);
+    return hipGetLastError();
+}
+
 template <bool STORE>
 static hipError_t launch_impl(const TwoLayerArgs& a, int mode, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
     if (STORE && a.step_end <= a.step_begin) return hipSuccess;
-    if (a.n_comp < 0 || a.n_comp > kMaxForcingComponents || (a.n_comp > 0 && a.link)) return hipErrorInvalidValue;
-    const size_t lds = a.lds_forcing ? two_layer_lds_bytes(a.n_scen, a.n_comp, a.step_end - a.step_begin) : 0;
-    const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
-    void (*kern)(TwoLayerArgs) =
-        a.n_comp > 0
-            ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, STORE, true> : two_layer_kernel<0, false, STORE, true>)
-                         : (a.lds_forcing ? two_layer_kernel<1, true, STORE, true> : two_layer_kernel<1, false, STORE, true>))
-            : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, STORE> : two_layer_kernel<0, false, STORE>)
-                         : (a.lds_forcing ? two_layer_kernel<1, true, STORE> : two_layer_kernel<1, false, STORE>));
-    if (a.noise_on) {   // the stored run of a handle that is not linked: the only launch that carries noise
-        if constexpr (STORE) {
-            if (a.link || a.noise_on < kNoiseWhite || a.noise_on > kNoiseMembersCached) return hipErrorInvalidValue;
-            if (a.noise_on == kNoiseWhite) {
-                kern = a.n_comp > 0
-                           ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 1> : two_layer_kernel<0, false, true, true, 1>)
-                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 1> : two_layer_kernel<1, false, true, true, 1>))
-                           : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 1> : two_layer_kernel<0, false, true, false, 1>)
-                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 1> : two_layer_kernel<1, false, true, false, 1>));
-            } else if (a.noise_on >= kNoiseMembersSpinUp) {
-                if (!a.noise_state) return hipErrorInvalidValue;
-                kern = a.n_comp > 0
-                           ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 3> : two_layer_kernel<0, false, true, true, 3>)
-                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 3> : two_layer_kernel<1, false, true, true, 3>))
-                           : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 3> : two_layer_kernel<0, false, true, false, 3>)
-                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 3> : two_layer_kernel<1, false, true, false, 3>));
-            } else {
-                if (!a.noise_state) return hipErrorInvalidValue;
-                kern = a.n_comp > 0
-                           ? (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, true, 2> : two_layer_kernel<0, false, true, true, 2>)
-                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, true, 2> : two_layer_kernel<1, false, true, true, 2>))
-                           : (mode == 0 ? (a.lds_forcing ? two_layer_kernel<0, true, true, false, 2> : two_layer_kernel<0, false, true, false, 2>)
-                                        : (a.lds_forcing ? two_layer_kernel<1, true, true, false, 2> : two_layer_kernel<1, false, true, false, 2>));
-            }
-        } else {
-            return hipErrorInvalidValue;
+    if (!args_ok(a) || (a.noise_on && !STORE)) return hipErrorInvalidValue;   // noise: the stored run of a handle that is not linked, only
+    const bool lds = a.lds_forcing != 0, mix = a.n_comp > 0;
+    StepKernel kern = step_kernel<STORE, kNoiseKindNone>(mode, lds, mix);
+    if constexpr (STORE) {
+        switch (noise_kind(a.noise_on)) {
+            case kNoiseKindWhite: kern = step_kernel<true, kNoiseKindWhite>(mode, lds, mix); break;
+            case kNoiseKindRed: kern = step_kernel<true, kNoiseKindRed>(mode, lds, mix); break;
+            case kNoiseKindMembers: kern = step_kernel<true, kNoiseKindMembers>(mode, lds, mix); break;
         }
     }
-    if (lds > (size_t)kMaxStaticLds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, s, a);
-    return hipGetLastError();
+    return launch_shaped(kern, a, s);
 }
 
 hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s)
@@ -221,23 +223,18 @@ hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t 
     return launch_impl<false>(a, mode, s);
 }
 
-hipError_t launch_forcing_noise_rows(uint64_t seed, double sigma, double phi, int64_t member0, int64_t n_members, int32_t t_begin,
-                                     int32_t t_end, double* out, hipStream_t s)
+hipError_t launch_forcing_noise_rows(int32_t kind, uint64_t seed, double sigma, double phi, const double* params, uint64_t uniform_rows,
+                                     int32_t sigma_row, int32_t phi_row, int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end,
+                                     double* out, hipStream_t s)
 {
     if (n_members <= 0 || t_end <= t_begin) return hipSuccess;
-    const dim3 grid((unsigned)((n_members + kBlock - 1) / kBlock));
-    if (phi == 0.0) hipLaunchKernelGGL(forcing_noise_rows_kernel, grid, dim3(kBlock), 0, s, seed, sigma, member0, n_members, t_begin, t_end, out);
-    else hipLaunchKernelGGL(forcing_noise_red_rows_kernel, grid, dim3(kBlock), 0, s, seed, sigma, phi, member0, n_members, t_begin, t_end, out);
-    return hipGetLastError();
-}
-
-hipError_t launch_forcing_noise_member_rows(uint64_t seed, const double* params, uint64_t uniform_rows, int32_t sigma_row, int32_t phi_row,
-                                            int64_t member0, int64_t n_members, int32_t t_begin, int32_t t_end, double* out, hipStream_t s)
-{
-    if (n_members <= 0 || t_end <= t_begin) return hipSuccess;
-    if (!params || sigma_row < 0 || phi_row < 0) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(forcing_noise_member_rows_kernel, dim3((unsigned)((n_members + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, seed, params,
-                       uniform_rows, sigma_row, phi_row, member0, n_members, t_begin, t_end, out);
+    if (kind == kNoiseKindMembers && (!params || sigma_row < 0 || phi_row < 0)) return hipErrorInvalidValue;
+    auto kern = forcing_noise_rows_kernel<kNoiseKindWhite>;
+    if (kind == kNoiseKindRed) kern = forcing_noise_rows_kernel<kNoiseKindRed>;
+    else if (kind == kNoiseKindMembers) kern = forcing_noise_rows_kernel<kNoiseKindMembers>;
+    else if (kind != kNoiseKindWhite) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((n_members + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, seed, sigma, phi, params, uniform_rows,
+                       sigma_row, phi_row, member0, n_members, t_begin, t_end, out);
     return hipGetLastError();
 }
 
@@ -251,22 +248,8 @@ hipError_t launch_normal_selftest(const uint64_t* k52, int64_t n, double* z, hip
 hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefArgs& r, int mode, hipStream_t s)
 {
     if (a.n_members <= 0) return hipSuccess;
-    if (a.noise_on) return hipErrorInvalidValue;   // (the fused likelihood of a noise handle is refused at the entry points)
-    if (a.n_comp < 0 || a.n_comp > kMaxForcingComponents || (a.n_comp > 0 && a.link)) return hipErrorInvalidValue;
-    const size_t lds = a.lds_forcing ? two_layer_lds_bytes(a.n_scen, a.n_comp, a.step_end - a.step_begin) : 0;
-    const dim3 grid((unsigned)((a.n_members + kBlock - 1) / kBlock));
-    void (*kern)(TwoLayerArgs, TwoLayerRefArgs) =
-        a.n_comp > 0 ? (mode == 0 ? (a.lds_forcing ? two_layer_ref_kernel<0, true, true> : two_layer_ref_kernel<0, false, true>)
-                                  : (a.lds_forcing ? two_layer_ref_kernel<1, true, true> : two_layer_ref_kernel<1, false, true>))
-                     : (mode == 0 ? (a.lds_forcing ? two_layer_ref_kernel<0, true> : two_layer_ref_kernel<0, false>)
-                                  : (a.lds_forcing ? two_layer_ref_kernel<1, true> : two_layer_ref_kernel<1, false>));
-    if (lds > (size_t)kMaxStaticLds) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kern, grid, dim3(kBlock), lds, s, a, r);
-    return hipGetLastError();
+    if (!args_ok(a) || a.noise_on) return hipErrorInvalidValue;   // (the fused likelihood of a noise handle is refused at the entry points)
+    return launch_shaped(ref_kernel(mode, a.lds_forcing != 0, a.n_comp > 0), a, s, r);
 }
 
 hipError_t two_layer_guard_counts(int64_t* out)

@@ -296,20 +296,20 @@ enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuar
 // every product and sum rounded on its own in BOTH arithmetic modes (the file is compiled with -ffp-contract=off and nothing here is
 // written as an FMA).  NaN and Inf propagate, no row is skipped and none is padded with 0 * S (that would change -0.0, NaN and Inf):
 // the loop below is unrolled to eight with a wave-uniform k < K around each term, so the coefficients stay in registers.
-// NOISE != 0 (a handle with rscm_ens_set_forcing_noise*; stand-alone STORE launches only, never linked): the forcing read at
-// forcing-axis index t = n + a.src_off -- the scenario value, or the mix sum formed first -- becomes, with NOISE == 1 (white),
+// NOISE != 0 (the launcher passes noise_kind(a.noise_on), rscm_device.hpp; stand-alone STORE launches only, never linked): the forcing
+// read at forcing-axis index t = n + a.src_off -- the scenario value, or the mix sum formed first -- becomes, with NOISE == 1 (white),
 //     F' = F + a.noise_sigma * z(a.noise_seed, a.noise_member0 + i, t),
 // product and sum rounded on their own in BOTH modes, z the stateless deviate of forcing_noise.hpp.  forcing_at adds the term, so the
 // draw for year n + 1 is made in the look-ahead slot of year n and the box guard and the replay see F' like any forcing.  A Philox
 // block serves an even index and the odd one after it: the second pair of words waits in two registers for the next year (which
 // index they serve is wave-uniform), so the ten rounds run every other year.
-// NOISE == 2 (red, a.noise_phi != 0): F' = F + e_t with e_0 = sigma z_0 and e_t = (phi e_{t-1}) + ((sigma sqrt(1 - phi phi)) z_t), each
+// NOISE == 2 (red): F' = F + e_t with e_0 = sigma z_0 and e_t = (phi e_{t-1}) + ((sigma sqrt(1 - phi phi)) z_t), each
 // operation rounded on its own.  forcing_at is called once per index in ascending order, so e lives in a register and a year costs
 // two multiplies and an add on top of the white draw.  Before the year loop e is brought to the index before the launch's first:
 // loaded from a.noise_state (a.noise_on == kNoiseRedCached) or formed from index 0 on by the same statements as in the loop (a
 // wave-uniform trip count; the bits of the per-index definition by construction).  The launch ends with one store of e, which then
 // stands at the last index drawn, step_end - 1 + a.src_off.
-// NOISE == 3 (per-member, rscm_ens_set_forcing_noise_members): the red statements with member i's own sigma_i and phi_i, parameter rows
+// NOISE == 3 (per-member): the red statements with member i's own sigma_i and phi_i, parameter rows
 // kTwoLayerCoeff0 + K and the next (K = a.n_comp of a mix handle, else 0), read once per launch like every other row -- a row that
 // rscm_ens_set_params found uniform is one element for the wavefront.  sigma_i, phi_i and sigma_i sqrt(1 - phi_i phi_i) live in vector
 // registers (four more than NOISE == 2, where they are kernel arguments: the EXACT plain kernel crosses the 168-register step).  Nothing validates the rows: NaN, Inf or |phi_i| > 1 make that
