@@ -2,6 +2,8 @@
 // marshalling; launch_host.cpp: one launch range of one handle; lockstep.cpp: the lock-step scheduler of component graphs;
 // loglik_host.cpp: the likelihoods).  Not part of the boundary
 // (include/rscm_gpu.h) and not visible outside the library (-fvisibility=hidden).
+// Device allocation -- rscm::dev_malloc and rscm::DevBuf, the scoped owner every device temporary of the host layer is held
+// by -- lives in dev_buf.hpp, which this header includes.
 #pragma once
 
 #include "../../include/rscm_gpu.h"
@@ -17,25 +19,10 @@
 #include <limits>
 #include <new>
 #include <cstdlib>
-
-// Every device allocation of the host layer goes through dev_malloc.  Debug aid (RSCM_POISON_ALLOC=1 in the environment): it is filled with 0xFF bytes -- NaN as a
-// double, -1 as an integer, 255 as a status byte -- so that a kernel or a copy that reads memory nobody wrote shows up as a wrong
-// result in the parity tests instead of passing on whatever a fresh allocation happens to hold (usually zeros).  Off by default: one
-// fill per allocation.  The GPU tier is run once per round with it on.
-namespace rscm {
-template <class T>
-inline hipError_t dev_malloc(T** p, size_t n)
-{
-    static const bool poison = [] { const char* e = getenv("RSCM_POISON_ALLOC"); return e && atoi(e) != 0; }();
-    const hipError_t e = hipMalloc(reinterpret_cast<void**>(p), n);
-    if (e != hipSuccess || !poison || n == 0) return e;
-    const hipError_t f = hipMemset(*p, 0xFF, n);
-    return f == hipSuccess ? hipDeviceSynchronize() : f;
-}
-}  // namespace rscm
 #include <string>
 #include <vector>
 
+#include "dev_buf.hpp"
 #include "kinds.hpp"
 #include "rscm_device.hpp"
 
@@ -350,7 +337,10 @@ inline bool can_fuse(const rscm_ens* h) { return h->info().fusable && (h->kind !
 void select_release(rscm_ens* h);
 // the rows t_begin, t_begin + t_stride, ... < t_end of var_id that this model instance has computed (t <= time_index), as device
 // addresses (rscm_ens::row_ptr); *n_range = the rows of the whole range.  RSCM_ERR_STATE if a computed row is not resident.  The
-// caller has checked var_id and the range (select_host.cpp).
+// caller has checked var_id and the range (select_host.cpp).  The two checks that come first: var_id has a stored series and the range
+// lies on the axis (empty ranges refused with at_least_one); a handle that stores only its initial row serves no range past it.
+int check_row_range(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, bool at_least_one);
+int check_series_stored(const rscm_ens* h, int32_t t_end);
 int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                  int32_t* n_range);
 // RSCM_OK if p is device memory on h's device holding at least N doubles from p on, else RSCM_ERR_INVALID (select_host.cpp)
@@ -389,10 +379,10 @@ extern "C" {
 // and are run afresh for every score (rows at series(var) + t * N, the time index does not matter); else a handle's own likelihood (rows
 // where they are resident, rscm_ens::row_ptr; RSCM_ERR_STATE if one is not).
 int resolve_loglik_rows(rscm_ens* const* handles, int32_t n_handles, bool whole_series, const ObsList& o, const RefList& r, LoglikRows* out);
-// Lays rows, values, sigmas, groups and reference tables out in one device allocation, *d_blob (hipFree'd by the caller, also after a
-// failure), and points *args into it: ready for launch_loglik on `stream`.  The copy is enqueued on `stream` from rows.staging: rows
-// must live until the caller has synchronised that stream.
-int upload_loglik(LoglikRows& rows, const ObsList& o, int64_t n_members, double* out, hipStream_t stream, void** d_blob,
+// Lays rows, values, sigmas, groups and reference tables out in one device allocation, d_blob, and points *args into it: ready for
+// launch_loglik on `stream`.  The copy is enqueued on `stream` from rows.staging: rows must live until the caller has synchronised
+// that stream.
+int upload_loglik(LoglikRows& rows, const ObsList& o, int64_t n_members, double* out, hipStream_t stream, rscm::DevBuf<unsigned char>& d_blob,
                   rscm::LoglikArgs* args);
 int prepare_obs(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_t* obs_tidx, const double* obs_value, const double* obs_sigma,
                 int32_t normalize);

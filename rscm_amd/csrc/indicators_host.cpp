@@ -22,11 +22,8 @@ namespace {
 int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                 std::vector<double>& times)
 {
-    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
-    if (t_begin < 0 || t_end > h->T || t_begin >= t_end || t_stride < 1)
-        return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d (at least one row)", t_begin, t_end, t_stride);
-    if (!h->windowed && h->rows != h->T && t_end > 1)
-        return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
+    if (int rc = check_row_range(h, var_id, t_begin, t_end, t_stride, true)) return rc;
+    if (int rc = check_series_stored(h, t_end)) return rc;
     int32_t n_range = 0;
     if (int rc = resolve_rows(h, var_id, t_begin, t_end, t_stride, rows, &n_range)) return rc;
     if ((int32_t)rows.size() != n_range)
@@ -35,24 +32,33 @@ int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int
     return RSCM_OK;
 }
 
+// The device array of the row pointers, enqueued on the handle's stream: rows must live until the caller has synchronised it
+int upload_rows(rscm_ens* h, const std::vector<const double*>& rows, rscm::DevBuf<const double*>& d_rows)
+{
+    HIPCHK(d_rows.alloc(rows.size()));
+    HIPCHK(hipMemcpyAsync(d_rows.get(), rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    return RSCM_OK;
+}
+
+rscm::Thresholds thresholds(int32_t n_thr, const double* thr)
+{
+    rscm::Thresholds th{};
+    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
+    return th;
+}
+
 // Runs the indicator kernel over the rows into d_out ([1][N] with all false, else [3 + n_thr][N]) and waits for it
 int run_indicators(rscm_ens* h, const std::vector<const double*>& rows, const std::vector<double>& times, const double* d_base, bool all,
                    int32_t n_thr, const double* thr, double* d_out)
 {
-    rscm::Thresholds th{};
-    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
-    const double** d_rows = nullptr;
-    double* d_time = nullptr;
-    hipError_t e = rscm::dev_malloc(&d_rows, rows.size() * sizeof(double*));
-    if (e == hipSuccess) e = rscm::dev_malloc(&d_time, times.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_time, times.data(), times.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = rscm::launch_indicators(d_rows, d_time, (int32_t)rows.size(), d_base, h->N, all, n_thr, th, d_out, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_rows);
-    (void)hipFree(d_time);
-    HIPCHK(e);
-    HIPCHK(es);
+    rscm::DevBuf<const double*> d_rows;
+    rscm::DevBuf<double> d_time;
+    if (int rc = upload_rows(h, rows, d_rows)) return rc;
+    HIPCHK(d_time.alloc(times.size()));
+    HIPCHK(hipMemcpyAsync(d_time.get(), times.data(), times.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_indicators(d_rows.get(), d_time.get(), (int32_t)rows.size(), d_base, h->N, all, n_thr, thresholds(n_thr, thr), d_out,
+                                   h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return RSCM_OK;
 }
 
@@ -66,6 +72,42 @@ int check_thresholds(int32_t n_thr, const double* thr, int32_t lo)
 int no_select(const rscm_ens* h)
 {
     if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
+    return RSCM_OK;
+}
+
+// The slots of rscm_ens_member_indicators, _variability and _spectrum: the check, and the slot's buffer, allocated at first use
+int check_slot(int32_t slot)
+{
+    if (slot < 0 || slot >= rscm_ens::kIndSlots) return fail(RSCM_ERR_INVALID, "slot %d: must be in [0, %d)", slot, rscm_ens::kIndSlots);
+    return RSCM_OK;
+}
+
+int slot_buffer(rscm_ens* h, int32_t slot)
+{
+    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
+    return RSCM_OK;
+}
+
+int check_detrending(int32_t mode)
+{
+    if (mode != RSCM_VAR_MEAN && mode != RSCM_VAR_LINEAR && mode != RSCM_VAR_DIFFERENCE)
+        return fail(RSCM_ERR_INVALID, "unknown detrending mode %d (RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE)", mode);
+    return RSCM_OK;
+}
+
+// The working series of n_rows rows under a detrending mode: its length n, 3 to max_terms (0: no upper bound), and stt = n (n^2 - 1) / 12
+struct WorkingSeries {
+    int64_t n = 0;
+    double stt = 0.0;
+};
+int working_series(size_t n_rows, int32_t mode, int32_t max_terms, WorkingSeries* w)
+{
+    const int64_t n = (int64_t)n_rows - (mode == RSCM_VAR_DIFFERENCE ? 1 : 0);
+    if (n < 3 && !max_terms) return fail(RSCM_ERR_INVALID, "the working series of %d rows has %lld terms: at least 3 are needed", (int)n_rows, (long long)n);
+    if (max_terms && (n < 3 || n > max_terms))
+        return fail(RSCM_ERR_INVALID, "the working series of %d rows has %lld terms: 3 to %d are needed", (int)n_rows, (long long)n, max_terms);
+    w->n = n;
+    w->stt = (double)(n * (n * n - 1)) / 12.0;
     return RSCM_OK;
 }
 
@@ -99,6 +141,54 @@ void spectrum_coefficients(int32_t n, double* c2)
     }
 }
 
+// What the two likelihoods over per-member vectors check once their own numbers are in: every vector and add_dev (may be null) is a
+// member vector of the handle's device; vec takes the vectors, and d_loglik is there
+int loglik_vector_list(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* add_dev, const double** vec)
+{
+    if (int rc = set_device(h)) return rc;
+    for (int32_t j = 0; j < n_vec; ++j) {
+        char what[24];
+        std::snprintf(what, sizeof what, "vector %d", j);
+        if (int rc = check_member_vector(h, vec_dev[j], what)) return rc;
+        vec[j] = vec_dev[j];
+    }
+    if (add_dev)
+        if (int rc = check_member_vector(h, add_dev, "add_dev")) return rc;
+    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+    return RSCM_OK;
+}
+
+// rscm_ens_exceedance and, grouped, rscm_ens_exceedance_grouped: hits[G][n_thr] and total[G] over G = the handle's groups, else 1
+int exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted, bool grouped, int64_t* hits,
+               int64_t* total)
+{
+    if (!total || (n_thr > 0 && !hits)) return fail(RSCM_ERR_INVALID, "hits or total is NULL");
+    if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
+    if (grouped && !h->d_groups) return fail(RSCM_ERR_STATE, "no member groups: rscm_ens_set_member_groups first");
+    if (weighted && !h->d_weights)
+        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
+    if (int rc = set_device(h)) return rc;
+    if (int rc = check_member_vector(h, vec_dev, "vector")) return rc;
+    const rscm::Thresholds th = thresholds(n_thr, thr);
+    const int64_t* d_w = weighted ? h->d_weights : nullptr;
+    const int32_t G = grouped ? h->n_groups : 1;
+    std::vector<unsigned long long> acc((size_t)G * (n_thr + 1));
+    rscm::DevBuf<unsigned long long> d_acc;
+    HIPCHK(d_acc.alloc(acc.size()));
+    HIPCHK(hipMemsetAsync(d_acc.get(), 0, acc.size() * sizeof(unsigned long long), h->stream));
+    if (grouped)
+        HIPCHK(rscm::launch_exceedance_grouped(vec_dev, d_w, h->d_groups, G, h->N, n_thr, th, d_acc.get(), h->stream));
+    else
+        HIPCHK(rscm::launch_exceedance(vec_dev, d_w, h->N, n_thr, th, d_acc.get(), h->stream));
+    HIPCHK(hipMemcpyAsync(acc.data(), d_acc.get(), acc.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    for (int32_t g = 0; g < G; ++g) {
+        for (int32_t k = 0; k < n_thr; ++k) hits[(size_t)g * n_thr + k] = (int64_t)acc[(size_t)g * (n_thr + 1) + k];
+        total[g] = (int64_t)acc[(size_t)g * (n_thr + 1) + n_thr];
+    }
+    return RSCM_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -112,14 +202,10 @@ int rscm_ens_set_baseline(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t 
     std::vector<double> times;
     if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
     if (int rc = set_device(h)) return rc;
-    double* d_new = nullptr;
-    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(double)));
-    if (int rc = run_indicators(h, rows, times, nullptr, false, 0, nullptr, d_new)) {
-        (void)hipFree(d_new);
-        return rc;
-    }
-    (void)hipFree(h->d_base);
-    h->d_base = d_new;
+    rscm::DevBuf<double> d_new;
+    HIPCHK(d_new.alloc((size_t)h->N));
+    if (int rc = run_indicators(h, rows, times, nullptr, false, 0, nullptr, d_new.get())) return rc;
+    d_new.install(h->d_base);
     return RSCM_OK;
     GUARD_END
 }
@@ -133,17 +219,11 @@ int rscm_ens_set_baseline_values(rscm_ens* h, const double* b, int32_t on_device
     if (int rc = set_device(h)) return rc;
     if (on_device)
         if (int rc = check_member_vector(h, b, "baseline")) return rc;
-    double* d_new = nullptr;
-    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(double)));
-    hipError_t e = hipMemcpyAsync(d_new, b, (size_t)h->N * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                  h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_new);
-        HIPCHK(e);
-    }
-    (void)hipFree(h->d_base);
-    h->d_base = d_new;
+    rscm::DevBuf<double> d_new;
+    HIPCHK(d_new.alloc((size_t)h->N));
+    HIPCHK(hipMemcpyAsync(d_new.get(), b, (size_t)h->N * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    d_new.install(h->d_base);
     return RSCM_OK;
     GUARD_END
 }
@@ -179,7 +259,7 @@ int rscm_ens_member_indicators(rscm_ens* h, int32_t var_id, int32_t t_begin, int
     NEED(h);
     if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
     *out_dev = nullptr;
-    if (slot < 0 || slot >= rscm_ens::kIndSlots) return fail(RSCM_ERR_INVALID, "slot %d: must be in [0, %d)", slot, rscm_ens::kIndSlots);
+    if (int rc = check_slot(slot)) return rc;
     if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
     if (anomaly && !h->d_base) return fail(RSCM_ERR_STATE, "no baseline: rscm_ens_set_baseline or rscm_ens_set_baseline_values first");
     if (int rc = no_select(h)) return rc;
@@ -187,7 +267,7 @@ int rscm_ens_member_indicators(rscm_ens* h, int32_t var_id, int32_t t_begin, int
     std::vector<double> times;
     if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
     if (int rc = set_device(h)) return rc;
-    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
+    if (int rc = slot_buffer(h, slot)) return rc;
     if (int rc = run_indicators(h, rows, times, anomaly ? h->d_base : nullptr, true, n_thr, thr, h->d_ind[slot])) return rc;
     *out_dev = h->d_ind[slot];
     return RSCM_OK;
@@ -201,26 +281,20 @@ int rscm_ens_member_variability(rscm_ens* h, int32_t var_id, int32_t t_begin, in
     NEED(h);
     if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
     *out_dev = nullptr;
-    if (slot < 0 || slot >= rscm_ens::kIndSlots) return fail(RSCM_ERR_INVALID, "slot %d: must be in [0, %d)", slot, rscm_ens::kIndSlots);
-    if (mode != RSCM_VAR_MEAN && mode != RSCM_VAR_LINEAR && mode != RSCM_VAR_DIFFERENCE)
-        return fail(RSCM_ERR_INVALID, "unknown detrending mode %d (RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE)", mode);
+    if (int rc = check_slot(slot)) return rc;
+    if (int rc = check_detrending(mode)) return rc;
     if (int rc = no_select(h)) return rc;
     std::vector<const double*> rows;
     std::vector<double> times;
     if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
-    const int64_t n = (int64_t)rows.size() - (mode == RSCM_VAR_DIFFERENCE ? 1 : 0);   // the working series' length
-    if (n < 3) return fail(RSCM_ERR_INVALID, "the working series of %d rows has %lld terms: at least 3 are needed", (int)rows.size(), (long long)n);
-    const double stt = (double)(n * (n * n - 1)) / 12.0;
+    WorkingSeries w;
+    if (int rc = working_series(rows.size(), mode, 0, &w)) return rc;
     if (int rc = set_device(h)) return rc;
-    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
-    const double** d_rows = nullptr;
-    hipError_t e = rscm::dev_malloc(&d_rows, rows.size() * sizeof(double*));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = rscm::launch_variability(d_rows, (int32_t)rows.size(), mode, stt, h->N, h->d_ind[slot], h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_rows);
-    HIPCHK(e);
-    HIPCHK(es);
+    if (int rc = slot_buffer(h, slot)) return rc;
+    rscm::DevBuf<const double*> d_rows;
+    if (int rc = upload_rows(h, rows, d_rows)) return rc;
+    HIPCHK(rscm::launch_variability(d_rows.get(), (int32_t)rows.size(), mode, w.stt, h->N, h->d_ind[slot], h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     *out_dev = h->d_ind[slot];
     return RSCM_OK;
     GUARD_END
@@ -243,45 +317,36 @@ int rscm_ens_member_spectrum(rscm_ens* h, int32_t var_id, int32_t t_begin, int32
     NEED(h);
     if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
     *out_dev = nullptr;
-    if (slot < 0 || slot >= rscm_ens::kIndSlots) return fail(RSCM_ERR_INVALID, "slot %d: must be in [0, %d)", slot, rscm_ens::kIndSlots);
-    if (mode != RSCM_VAR_MEAN && mode != RSCM_VAR_LINEAR && mode != RSCM_VAR_DIFFERENCE)
-        return fail(RSCM_ERR_INVALID, "unknown detrending mode %d (RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE)", mode);
+    if (int rc = check_slot(slot)) return rc;
+    if (int rc = check_detrending(mode)) return rc;
     if (n_bands < 1 || n_bands > rscm::kMaxSpectrumBands || !edges)
         return fail(RSCM_ERR_INVALID, "bad band list (1 to %d bands, n_bands + 1 edges)", rscm::kMaxSpectrumBands);
     if (int rc = no_select(h)) return rc;
     std::vector<const double*> rows;
     std::vector<double> times;
     if (int rc = period_rows(h, var_id, t_begin, t_end, t_stride, rows, times)) return rc;
-    const int64_t n = (int64_t)rows.size() - (mode == RSCM_VAR_DIFFERENCE ? 1 : 0);   // the working series' length
-    if (n < 3 || n > kSpectrumMaxTerms)
-        return fail(RSCM_ERR_INVALID, "the working series of %d rows has %lld terms: 3 to %d are needed", (int)rows.size(), (long long)n,
-                    kSpectrumMaxTerms);
+    WorkingSeries w;
+    if (int rc = working_series(rows.size(), mode, kSpectrumMaxTerms, &w)) return rc;
+    const int64_t n = w.n;
     const int32_t J = (int32_t)((n - 1) / 2);
     if (edges[0] < 1 || edges[n_bands] > J + 1) return fail(RSCM_ERR_INVALID, "the band edges must lie in [1, %d] (J + 1 of %lld terms)", J + 1, (long long)n);
     for (int32_t b = 0; b < n_bands; ++b)
         if (edges[b] >= edges[b + 1]) return fail(RSCM_ERR_INVALID, "the band edges must be strictly ascending (edge %d)", b + 1);
-    const double stt = (double)(n * (n * n - 1)) / 12.0;
     // the table the kernel is given: c2[J], kSpectrumTablePad zeros the last tile may read, then the edges (8-byte aligned: int32 pairs)
     const size_t n_c2 = (size_t)J + rscm::kSpectrumTablePad;
     std::vector<double> table(n_c2 + (size_t)(n_bands + 2) / 2, 0.0);
     spectrum_coefficients((int32_t)n, table.data());
     std::memcpy(table.data() + n_c2, edges, (size_t)(n_bands + 1) * sizeof(int32_t));
     if (int rc = set_device(h)) return rc;
-    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
-    const double** d_rows = nullptr;
-    double* d_table = nullptr;
-    hipError_t e = rscm::dev_malloc(&d_rows, rows.size() * sizeof(double*));
-    if (e == hipSuccess) e = rscm::dev_malloc(&d_table, table.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_rows, rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess)
-        e = rscm::launch_spectrum(d_rows, (int32_t)rows.size(), mode, stt, d_table, reinterpret_cast<const int32_t*>(d_table + n_c2), n_bands, h->N,
-                                  h->d_ind[slot], h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_rows);
-    (void)hipFree(d_table);
-    HIPCHK(e);
-    HIPCHK(es);
+    if (int rc = slot_buffer(h, slot)) return rc;
+    rscm::DevBuf<const double*> d_rows;
+    rscm::DevBuf<double> d_table;
+    if (int rc = upload_rows(h, rows, d_rows)) return rc;
+    HIPCHK(d_table.alloc(table.size()));
+    HIPCHK(hipMemcpyAsync(d_table.get(), table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_spectrum(d_rows.get(), (int32_t)rows.size(), mode, w.stt, d_table.get(),
+                                 reinterpret_cast<const int32_t*>(d_table.get() + n_c2), n_bands, h->N, h->d_ind[slot], h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     *out_dev = h->d_ind[slot];
     return RSCM_OK;
     GUARD_END
@@ -303,16 +368,7 @@ int rscm_ens_loglik_spectrum_device(rscm_ens* h, int32_t n_vec, const double* co
         v.record[j] = record[j];
         v.count[j] = (double)count[j];
     }
-    if (int rc = set_device(h)) return rc;
-    for (int32_t j = 0; j < n_vec; ++j) {
-        char what[24];
-        std::snprintf(what, sizeof what, "vector %d", j);
-        if (int rc = check_member_vector(h, vec_dev[j], what)) return rc;
-        v.vec[j] = vec_dev[j];
-    }
-    if (add_dev)
-        if (int rc = check_member_vector(h, add_dev, "add_dev")) return rc;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+    if (int rc = loglik_vector_list(h, n_vec, vec_dev, add_dev, v.vec)) return rc;
     HIPCHK(rscm::launch_loglik_spectrum(v, n_vec, add_dev, h->N, h->d_loglik, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *out_dev = h->d_loglik;
@@ -336,16 +392,7 @@ int rscm_ens_loglik_vectors_device(rscm_ens* h, int32_t n_vec, const double* con
         v.value[j] = value[j];
         v.sigma[j] = sigma[j];
     }
-    if (int rc = set_device(h)) return rc;
-    for (int32_t j = 0; j < n_vec; ++j) {
-        char what[24];
-        std::snprintf(what, sizeof what, "vector %d", j);
-        if (int rc = check_member_vector(h, vec_dev[j], what)) return rc;
-        v.vec[j] = vec_dev[j];
-    }
-    if (add_dev)
-        if (int rc = check_member_vector(h, add_dev, "add_dev")) return rc;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+    if (int rc = loglik_vector_list(h, n_vec, vec_dev, add_dev, v.vec)) return rc;
     HIPCHK(rscm::launch_loglik_vectors(v, n_vec, add_dev, h->N, h->d_loglik, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *out_dev = h->d_loglik;
@@ -358,28 +405,7 @@ int rscm_ens_exceedance(rscm_ens* h, const double* vec_dev, int32_t n_thr, const
 {
     GUARD_BEGIN
     NEED(h);
-    if (!total || (n_thr > 0 && !hits)) return fail(RSCM_ERR_INVALID, "hits or total is NULL");
-    if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
-    if (weighted && !h->d_weights)
-        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
-    if (int rc = set_device(h)) return rc;
-    if (int rc = check_member_vector(h, vec_dev, "vector")) return rc;
-    rscm::Thresholds th{};
-    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
-    unsigned long long acc[rscm::kMaxThresholds + 1] = {};
-    unsigned long long* d_acc = nullptr;
-    const size_t bytes = (size_t)(n_thr + 1) * sizeof(unsigned long long);
-    hipError_t e = rscm::dev_malloc(&d_acc, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, bytes, h->stream);
-    if (e == hipSuccess) e = rscm::launch_exceedance(vec_dev, weighted ? h->d_weights : nullptr, h->N, n_thr, th, d_acc, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(acc, d_acc, bytes, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_acc);
-    HIPCHK(e);
-    HIPCHK(es);
-    for (int32_t k = 0; k < n_thr; ++k) hits[k] = (int64_t)acc[k];
-    *total = (int64_t)acc[n_thr];
-    return RSCM_OK;
+    return exceedance(h, vec_dev, n_thr, thr, weighted, false, hits, total);
     GUARD_END
 }
 
@@ -388,33 +414,7 @@ int rscm_ens_exceedance_grouped(rscm_ens* h, const double* vec_dev, int32_t n_th
 {
     GUARD_BEGIN
     NEED(h);
-    if (!total || (n_thr > 0 && !hits)) return fail(RSCM_ERR_INVALID, "hits or total is NULL");
-    if (int rc = check_thresholds(n_thr, thr, 0)) return rc;
-    if (!h->d_groups) return fail(RSCM_ERR_STATE, "no member groups: rscm_ens_set_member_groups first");
-    if (weighted && !h->d_weights)
-        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
-    if (int rc = set_device(h)) return rc;
-    if (int rc = check_member_vector(h, vec_dev, "vector")) return rc;
-    rscm::Thresholds th{};
-    for (int32_t k = 0; k < n_thr; ++k) th.v[k] = thr[k];
-    const int32_t G = h->n_groups;
-    std::vector<unsigned long long> acc((size_t)G * (n_thr + 1));
-    unsigned long long* d_acc = nullptr;
-    const size_t bytes = acc.size() * sizeof(unsigned long long);
-    hipError_t e = rscm::dev_malloc(&d_acc, bytes);
-    if (e == hipSuccess) e = hipMemsetAsync(d_acc, 0, bytes, h->stream);
-    if (e == hipSuccess)
-        e = rscm::launch_exceedance_grouped(vec_dev, weighted ? h->d_weights : nullptr, h->d_groups, G, h->N, n_thr, th, d_acc, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(acc.data(), d_acc, bytes, hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_acc);
-    HIPCHK(e);
-    HIPCHK(es);
-    for (int32_t g = 0; g < G; ++g) {
-        for (int32_t k = 0; k < n_thr; ++k) hits[(size_t)g * n_thr + k] = (int64_t)acc[(size_t)g * (n_thr + 1) + k];
-        total[g] = (int64_t)acc[(size_t)g * (n_thr + 1) + n_thr];
-    }
-    return RSCM_OK;
+    return exceedance(h, vec_dev, n_thr, thr, weighted, true, hits, total);
     GUARD_END
 }
 

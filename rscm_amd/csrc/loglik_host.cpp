@@ -91,7 +91,8 @@ int resolve_loglik_rows(rscm_ens* const* handles, int32_t n_handles, bool whole_
     return RSCM_OK;
 }
 
-int upload_loglik(LoglikRows& rows, const ObsList& o, int64_t n_members, double* out, hipStream_t stream, void** d_blob, rscm::LoglikArgs* args)
+int upload_loglik(LoglikRows& rows, const ObsList& o, int64_t n_members, double* out, hipStream_t stream, rscm::DevBuf<unsigned char>& d_blob,
+                  rscm::LoglikArgs* args)
 {
     const size_t sz_ptr = (size_t)o.n * sizeof(double*), sz_rptr = rows.ref_rows.size() * sizeof(double*), sz_d = (size_t)o.n * sizeof(double),
                  sz_i = (size_t)o.n * sizeof(int32_t), sz_off = rows.ref_off.size() * sizeof(int32_t);
@@ -108,11 +109,10 @@ int upload_loglik(LoglikRows& rows, const ObsList& o, int64_t n_members, double*
     }
     if (sz_rptr > 0) memcpy(blob.data() + off_rptr, rows.ref_rows.data(), sz_rptr);
     memcpy(blob.data() + off_off, rows.ref_off.data(), sz_off);
-    *d_blob = nullptr;
-    HIPCHK(rscm::dev_malloc(d_blob, blob.size()));
+    HIPCHK(d_blob.alloc(blob.size()));
     // enqueued, not waited for: the launch follows on the same stream and the caller synchronises once (rows.staging lives until then)
-    HIPCHK(hipMemcpyAsync(*d_blob, blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
-    const char* d = (const char*)*d_blob;
+    HIPCHK(hipMemcpyAsync(d_blob.get(), blob.data(), blob.size(), hipMemcpyHostToDevice, stream));
+    const char* d = (const char*)d_blob.get();
     args->n_members = n_members;
     args->n_obs = o.n;
     args->normalize = o.normalize ? 1 : 0;
@@ -139,16 +139,12 @@ static int loglik_on_device(rscm_ens* h, const ObsList& o, const RefList& r)
         HIPCHK(hipStreamSynchronize(h->stream));
         return RSCM_OK;
     }
-    void* d_blob = nullptr;
+    rscm::DevBuf<unsigned char> d_blob;
     rscm::LoglikArgs a{};
-    int rc = upload_loglik(rows, o, h->N, h->d_loglik, h->stream, &d_blob, &a);
-    if (rc == RSCM_OK) {
-        hipError_t e = rscm::launch_loglik(a, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(RSCM_ERR_DEVICE, "loglik: %s", hipGetErrorString(e));
-    }
-    (void)hipFree(d_blob);
-    return rc;
+    if (int rc = upload_loglik(rows, o, h->N, h->d_loglik, h->stream, d_blob, &a)) return rc;
+    HIPCHK(rscm::launch_loglik(a, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return RSCM_OK;
 }
 
 // the four entry points of the stored path: the result to the host (out) or left on the device (out_dev)
@@ -354,13 +350,11 @@ static int run_loglik_impl(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, c
     if (n_ref != 0)
         if (int rc = prepare_ref(h, n_ref, ref_var, ref_begin, ref_end, ref_stride)) return rc;
     if (int rc = check_loglik_ready(h)) return rc;
-    hipError_t e = hipEventRecord(h->ev0, h->stream);
-    if (e == hipSuccess) e = launch_loglik(h);
-    if (e == hipSuccess) e = hipEventRecord(h->ev1, h->stream);
-    if (e == hipSuccess && out_host)
-        e = hipMemcpyAsync(out_host, h->d_loglik, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "run_loglik: %s", hipGetErrorString(e));
+    HIPCHK(hipEventRecord(h->ev0, h->stream));
+    HIPCHK(launch_loglik(h));
+    HIPCHK(hipEventRecord(h->ev1, h->stream));
+    if (out_host) HIPCHK(hipMemcpyAsync(out_host, h->d_loglik, (size_t)h->N * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     h->timed = true;
     return RSCM_OK;
 }

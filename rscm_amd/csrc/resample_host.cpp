@@ -48,14 +48,13 @@ int rscm_ens_weights_stats(rscm_ens* h, int64_t* total, int64_t* n_nonzero, int6
     if (!h->d_weights) return fail(RSCM_ERR_STATE, "no member weights set");
     if (int rc = set_device(h)) return rc;
     const int32_t n_partial = rscm::weights_stats_partials(h->N);
-    unsigned long long* d_buf = nullptr;   // [5 * n_partial] partials, then the five results
-    HIPCHK(rscm::dev_malloc(&d_buf, (size_t)5 * (n_partial + 1) * sizeof(unsigned long long)));
+    rscm::DevBuf<unsigned long long> d_buf;   // [5 * n_partial] partials, then the five results
+    HIPCHK(d_buf.alloc((size_t)5 * (n_partial + 1)));
+    unsigned long long* d_res = d_buf.get() + (size_t)5 * n_partial;
     unsigned long long out[5] = {};
-    hipError_t e = rscm::launch_weights_stats(h->d_weights, h->N, d_buf, d_buf + (size_t)5 * n_partial, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_buf + (size_t)5 * n_partial, sizeof out, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_buf);
-    HIPCHK(e);
+    HIPCHK(rscm::launch_weights_stats(h->d_weights, h->N, d_buf.get(), d_res, h->stream));
+    HIPCHK(hipMemcpyAsync(out, d_res, sizeof out, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     *total = (int64_t)out[0];
     *n_nonzero = (int64_t)out[1];
     *w_max = (int64_t)out[2];
@@ -90,11 +89,10 @@ int rscm_ens_resample(rscm_ens* h, int64_t M, int64_t s, int64_t w_before, int64
     const int64_t k1 = first_draw_at((uint64_t)w_before + (uint64_t)w_local, q, r, (uint64_t)s, Mu);
     const int64_t n = k1 - k0;
     if (n > h->anc_capacity || !h->d_anc) {
-        int64_t* d_new = nullptr;
+        rscm::DevBuf<int64_t> d_new;
         const int64_t want = std::max<int64_t>(n, 1);
-        HIPCHK(rscm::dev_malloc(&d_new, (size_t)want * sizeof(int64_t)));
-        (void)hipFree(h->d_anc);
-        h->d_anc = d_new;
+        HIPCHK(d_new.alloc((size_t)want));
+        d_new.install(h->d_anc);
         h->anc_capacity = want;
     }
     HIPCHK(rscm::launch_ancestors(h->d_cumw, h->N, k0, n, Mu, q, r, (uint64_t)s, (uint64_t)w_before, h->d_anc, h->stream));

@@ -1319,22 +1319,20 @@ int rscm_ens_gather_members(rscm_ens* dst, int64_t dst_offset, rscm_ens* src, co
     }
 
     // the ancestors on the device, checked there before anything is written
-    int64_t* d_tmp = nullptr;
+    rscm::DevBuf<int64_t> d_tmp;
+    rscm::DevBuf<int32_t> d_flag;
     const int64_t* d_anc = anc;
-    struct Free { int64_t*& p; int32_t*& f; ~Free() { (void)hipFree(p); (void)hipFree(f); } };
-    int32_t* d_flag = nullptr;
-    Free guard{d_tmp, d_flag};
     if (count > 0) {
         if (!on_device) {
-            HIPCHK(rscm::dev_malloc(&d_tmp, (size_t)count * sizeof(int64_t)));
-            HIPCHK(hipMemcpyAsync(d_tmp, anc, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, dst->stream));
-            d_anc = d_tmp;
+            HIPCHK(d_tmp.alloc((size_t)count));
+            HIPCHK(hipMemcpyAsync(d_tmp.get(), anc, (size_t)count * sizeof(int64_t), hipMemcpyHostToDevice, dst->stream));
+            d_anc = d_tmp.get();
         }
         int32_t bad = 0;
-        HIPCHK(rscm::dev_malloc(&d_flag, sizeof(int32_t)));
-        HIPCHK(hipMemsetAsync(d_flag, 0, sizeof(int32_t), dst->stream));
-        HIPCHK(rscm::launch_ancestors_check(d_anc, count, src->N, d_flag, dst->stream));
-        HIPCHK(hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(d_flag.alloc(1));
+        HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(int32_t), dst->stream));
+        HIPCHK(rscm::launch_ancestors_check(d_anc, count, src->N, d_flag.get(), dst->stream));
+        HIPCHK(hipMemcpyAsync(&bad, d_flag.get(), sizeof bad, hipMemcpyDeviceToHost, dst->stream));
         HIPCHK(hipStreamSynchronize(dst->stream));
         if (bad) return fail(RSCM_ERR_INVALID, "an ancestor is outside [0, %lld)", (long long)src->N);
     }
@@ -1639,17 +1637,12 @@ int rscm_ens_summary_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_
     if (computed == 0) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
     const int32_t nb = rscm::summary_blocks(h->N);
-    double* d_partial = nullptr;
-    double* d_out = nullptr;
-    HIPCHK(rscm::dev_malloc(&d_partial, (size_t)computed * nb * 4 * sizeof(double)));
-    hipError_t e = rscm::dev_malloc(&d_out, (size_t)computed * 4 * sizeof(double));
-    if (e == hipSuccess)
-        e = rscm::launch_summary_rows(h->series(var_id) + (size_t)t_begin * h->N, h->N, computed, d_partial, nb, d_out, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, (size_t)computed * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_partial);
-    (void)hipFree(d_out);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "summary_series: %s", hipGetErrorString(e));
+    rscm::DevBuf<double> d_partial, d_out;
+    HIPCHK(d_partial.alloc((size_t)computed * nb * 4));
+    HIPCHK(d_out.alloc((size_t)computed * 4));
+    HIPCHK(rscm::launch_summary_rows(h->series(var_id) + (size_t)t_begin * h->N, h->N, computed, d_partial.get(), nb, d_out.get(), h->stream));
+    HIPCHK(hipMemcpyAsync(out, d_out.get(), (size_t)computed * 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return RSCM_OK;
     GUARD_END
 }
@@ -1672,19 +1665,14 @@ int rscm_ens_quantile_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32
     }
     if (computed == 0) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
-    double* d_q = nullptr;
-    double* d_out = nullptr;
     std::vector<double> host((size_t)computed * (n_q + 1));
-    HIPCHK(rscm::dev_malloc(&d_q, (size_t)n_q * sizeof(double)));
-    hipError_t e = rscm::dev_malloc(&d_out, host.size() * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_q, q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = rscm::launch_quantile_rows(h->series(var_id) + (size_t)t_begin * h->N, h->N, computed, d_q, n_q, d_out, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_q);
-    (void)hipFree(d_out);
-    if (e != hipSuccess)
-        return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "quantile_series: %s", hipGetErrorString(e));
+    rscm::DevBuf<double> d_q, d_out;
+    HIPCHK(d_q.alloc((size_t)n_q));
+    HIPCHK(d_out.alloc(host.size()));
+    HIPCHK(hipMemcpyAsync(d_q.get(), q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_quantile_rows(h->series(var_id) + (size_t)t_begin * h->N, h->N, computed, d_q.get(), n_q, d_out.get(), h->stream));
+    HIPCHK(hipMemcpyAsync(host.data(), d_out.get(), host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     for (int32_t r = 0; r < computed; ++r) {
         if (count) count[r] = host[(size_t)r * (n_q + 1)];
         for (int32_t k = 0; k < n_q; ++k) out[(size_t)r * n_q + k] = host[(size_t)r * (n_q + 1) + 1 + k];
@@ -1741,14 +1729,12 @@ int rscm_ens_sample_lhs(rscm_ens* h, uint64_t seed, const double* low, const dou
         if (m != 0.0 && m != 1.0) return fail(RSCM_ERR_INVALID, "GhgForcing method must be 0 or 1");
         h->ghg_method = (int32_t)m;
     }
-    double* d_lh = nullptr;
-    HIPCHK(rscm::dev_malloc(&d_lh, 2 * (size_t)h->P * sizeof(double)));
-    hipError_t e = hipMemcpyAsync(d_lh, low, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_lh + h->P, high, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = rscm::launch_lhs(h->d_params, h->P, h->N, seed, d_lh, d_lh + h->P, member_offset, n_total, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_lh);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "sample_lhs: %s", hipGetErrorString(e));
+    rscm::DevBuf<double> d_lh;   // [P] low, then [P] high
+    HIPCHK(d_lh.alloc(2 * (size_t)h->P));
+    HIPCHK(hipMemcpyAsync(d_lh.get(), low, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(d_lh.get() + h->P, high, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_lhs(h->d_params, h->P, h->N, seed, d_lh.get(), d_lh.get() + h->P, member_offset, n_total, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     h->uniform_rows = 0;   // conservatively: low + u (high - low) need not reproduce low's bits for every u
     h->params_written();
     h->params_set = true;
@@ -1920,15 +1906,16 @@ int rscm_ens_forcing_noise_rows(rscm_ens* h, int32_t t_begin, int32_t t_end, dou
     if (t_end == t_begin) return RSCM_OK;
     if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
     if (int rc = set_device(h)) return rc;
-    const size_t bytes = (size_t)(t_end - t_begin) * (size_t)h->N * sizeof(double);
-    double* d = out;
-    if (!on_device) HIPCHK(rscm::dev_malloc(&d, bytes));
-    hipError_t e = rscm::launch_forcing_noise_rows(h->noise_kind, h->noise_seed, h->noise_sigma, h->noise_phi, h->d_params, h->uniform_rows,
-                                                   h->noise_sigma_row(), h->noise_phi_row(), h->noise_offset, h->N, t_begin, t_end, d, h->stream);
-    if (e == hipSuccess && !on_device) e = hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && !on_device) e = hipStreamSynchronize(h->stream);
-    if (!on_device) (void)hipFree(d);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "forcing_noise_rows: %s", hipGetErrorString(e));
+    const size_t elems = (size_t)(t_end - t_begin) * (size_t)h->N;
+    rscm::DevBuf<double> tmp;   // host output: the rows are formed here
+    if (!on_device) HIPCHK(tmp.alloc(elems));
+    double* d = on_device ? out : tmp.get();
+    HIPCHK(rscm::launch_forcing_noise_rows(h->noise_kind, h->noise_seed, h->noise_sigma, h->noise_phi, h->d_params, h->uniform_rows,
+                                           h->noise_sigma_row(), h->noise_phi_row(), h->noise_offset, h->N, t_begin, t_end, d, h->stream));
+    if (!on_device) {
+        HIPCHK(hipMemcpyAsync(out, d, elems * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
+    }
     return RSCM_OK;
     GUARD_END
 }
@@ -1938,13 +1925,12 @@ int rscm_gpu_selftest_normal(const uint64_t* k52, int64_t n, double* z)
     GUARD_BEGIN
     if (n < 0 || !k52 || !z) return fail(RSCM_ERR_INVALID, "bad arguments");
     if (n == 0) return RSCM_OK;
-    double* d = nullptr;   // [n] integers, then [n] deviates
-    HIPCHK(rscm::dev_malloc(&d, 2 * (size_t)n * sizeof(double)));
-    hipError_t e = hipMemcpy(d, k52, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = rscm::launch_normal_selftest(reinterpret_cast<const uint64_t*>(d), n, d + n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(z, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "selftest_normal: %s", hipGetErrorString(e));
+    rscm::DevBuf<double> buf;   // [n] integers, then [n] deviates
+    HIPCHK(buf.alloc(2 * (size_t)n));
+    double* d = buf.get();
+    HIPCHK(hipMemcpy(d, k52, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(rscm::launch_normal_selftest(reinterpret_cast<const uint64_t*>(d), n, d + n, nullptr));
+    HIPCHK(hipMemcpy(z, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return RSCM_OK;
     GUARD_END
 }
@@ -1956,14 +1942,13 @@ int rscm_gpu_selftest_math(int32_t op, int64_t n, const double* x, const double*
     if (op < 0 || op >= rscm::kMathTestOps) return fail(RSCM_ERR_INVALID, "selftest_math: op %d is not in [0, %d)", op, rscm::kMathTestOps);
     if (n < 0 || !x || !out || (two && !y)) return fail(RSCM_ERR_INVALID, "bad arguments");
     if (n == 0) return RSCM_OK;
-    double* d = nullptr;   // [n] x, [n] out, then [n] y for the two-argument op
-    HIPCHK(rscm::dev_malloc(&d, (two ? 3 : 2) * (size_t)n * sizeof(double)));
-    hipError_t e = hipMemcpy(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess && two) e = hipMemcpy(d + 2 * n, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = rscm::launch_mathtest(op, d, two ? d + 2 * n : nullptr, d + n, n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "selftest_math: %s", hipGetErrorString(e));
+    rscm::DevBuf<double> buf;   // [n] x, [n] out, then [n] y for the two-argument op
+    HIPCHK(buf.alloc((two ? 3 : 2) * (size_t)n));
+    double* d = buf.get();
+    HIPCHK(hipMemcpy(d, x, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    if (two) HIPCHK(hipMemcpy(d + 2 * n, y, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(rscm::launch_mathtest(op, d, two ? d + 2 * n : nullptr, d + n, n, nullptr));
+    HIPCHK(hipMemcpy(out, d + n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
     return RSCM_OK;
     GUARD_END
 }
@@ -1975,19 +1960,17 @@ int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const
     if (n < 0 || !num || !den || !out_ref || !out_fast || !used_fast) return fail(RSCM_ERR_INVALID, "bad arguments");
     if (n == 0) return RSCM_OK;
     HIPCHK(hipSetDevice(device_id));
-    double* d = nullptr;
-    uint8_t* du = nullptr;
-    HIPCHK(rscm::dev_malloc(&d, 4 * (size_t)n * sizeof(double)));
-    hipError_t e = rscm::dev_malloc(&du, (size_t)n);
-    if (e == hipSuccess) e = hipMemcpy(d, num, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMemcpy(d + n, den, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = rscm::launch_divtest(d, d + n, d + 2 * n, d + 3 * n, du, n, nullptr);
-    if (e == hipSuccess) e = hipMemcpy(out_ref, d + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(out_fast, d + 3 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(used_fast, du, (size_t)n, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    (void)hipFree(du);
-    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "selftest_div: %s", hipGetErrorString(e));
+    rscm::DevBuf<double> buf;   // [n] num, den, out_ref, out_fast
+    rscm::DevBuf<uint8_t> du;
+    HIPCHK(buf.alloc(4 * (size_t)n));
+    HIPCHK(du.alloc((size_t)n));
+    double* d = buf.get();
+    HIPCHK(hipMemcpy(d, num, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + n, den, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(rscm::launch_divtest(d, d + n, d + 2 * n, d + 3 * n, du.get(), n, nullptr));
+    HIPCHK(hipMemcpy(out_ref, d + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_fast, d + 3 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(used_fast, du.get(), (size_t)n, hipMemcpyDeviceToHost));
     return RSCM_OK;
     GUARD_END
 }

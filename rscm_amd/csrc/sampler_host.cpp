@@ -38,7 +38,7 @@ struct rscm_sampler {
     // fused: the two-layer run+likelihood kernel scores a half; otherwise the half is run through
     // rscm_ens_run_async (any kind, stored series) and scored by the likelihood kernel
     bool fused = true;
-    void* d_sobs = nullptr;          // stored path: the tables lik points into (upload_loglik)
+    unsigned char* d_sobs = nullptr; // stored path: the tables lik points into (upload_loglik)
     rscm::LoglikArgs lik{};
     // the observations as given at creation (rscm_sampler_set_reference lays the stored path's tables out again)
     std::vector<int32_t> obs_owner, obs_var, obs_tidx;
@@ -224,19 +224,11 @@ int sampler_install_table(rscm_sampler* s, LoglikRows& rows)
 {
     rscm_ens* h = s->ev;
     if (int rc = set_device(h)) return rc;
-    void* d_new = nullptr;
+    rscm::DevBuf<unsigned char> d_new;
     rscm::LoglikArgs a{};
-    int rc = upload_loglik(rows, s->observations(), h->N, h->d_loglik, h->stream, &d_new, &a);
-    if (rc == RSCM_OK) {  // the copy is in, and no launch reads the previous table any more
-        const hipError_t e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(RSCM_ERR_DEVICE, "hipStreamSynchronize failed: %s", hipGetErrorString(e));
-    }
-    if (rc != RSCM_OK) {
-        (void)hipFree(d_new);
-        return rc;
-    }
-    (void)hipFree(s->d_sobs);
-    s->d_sobs = d_new;
+    if (int rc = upload_loglik(rows, s->observations(), h->N, h->d_loglik, h->stream, d_new, &a)) return rc;
+    HIPCHK(hipStreamSynchronize(h->stream));   // the copy is in, and no launch reads the previous table any more
+    d_new.install(s->d_sobs);
     s->lik = a;
     s->graph_last_step = rows.last_row;
     return RSCM_OK;

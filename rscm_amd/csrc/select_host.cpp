@@ -15,6 +15,8 @@
 // count, prefix, rank and out have n_comp x n_groups rows.  The member groups themselves (rscm_ens_set_member_groups) are at the end.
 #include <cmath>
 #include <limits>
+#include <memory>
+#include <utility>
 
 #include "ens.hpp"
 #include "select_keys.hpp"
@@ -31,35 +33,16 @@ struct SelectState {
     const int32_t* d_group = nullptr;
     int32_t v_rows() const { return n_comp * (n_groups ? n_groups : 1); }   // (row, group) pairs: the rows of commit and finish
     const double* d_base = nullptr;   // RSCM_SELECT_ANOMALY: the handle's baseline (it cannot change while the select is staged)
-    const double** d_rows = nullptr;
-    double* d_q = nullptr;
-    int64_t* d_hist = nullptr;
+    // the select's own buffers: they go with the state
+    rscm::DevBuf<const double*> d_rows;
+    rscm::DevBuf<double> d_q;
+    rscm::DevBuf<int64_t> d_hist;
     size_t hist_elems = 0;
-    int64_t* d_count = nullptr;
-    uint64_t* d_prefix = nullptr;
-    int64_t* d_rank = nullptr;
-    double* d_out = nullptr;
-    int32_t* d_over = nullptr;   // weighted: set by the first commit if a row's W exceeds 2^53
-
-    void release()
-    {
-        (void)hipFree(d_over);
-        d_over = nullptr;
-        (void)hipFree(d_rows);
-        (void)hipFree(d_q);
-        (void)hipFree(d_hist);
-        (void)hipFree(d_count);
-        (void)hipFree(d_prefix);
-        (void)hipFree(d_rank);
-        (void)hipFree(d_out);
-        d_rows = nullptr;
-        d_q = nullptr;
-        d_hist = nullptr;
-        d_count = nullptr;
-        d_prefix = nullptr;
-        d_rank = nullptr;
-        d_out = nullptr;
-    }
+    rscm::DevBuf<int64_t> d_count;
+    rscm::DevBuf<uint64_t> d_prefix;
+    rscm::DevBuf<int64_t> d_rank;
+    rscm::DevBuf<double> d_out;
+    rscm::DevBuf<int32_t> d_over;   // weighted: set by the first commit if a row's W exceeds 2^53
 };
 
 namespace {
@@ -103,16 +86,16 @@ int select_setup(rscm_ens* h, SelectState& s, const std::vector<const double*>& 
     if (int rc = set_device(h)) return rc;
     const size_t nr = (size_t)s.n_comp, nc = (size_t)s.v_rows(), nt = (size_t)s.n_t;
     s.hist_elems = nc * nt * rscm::kSelBins;
-    HIPCHK(rscm::dev_malloc(&s.d_rows, nr * sizeof(double*)));
-    HIPCHK(rscm::dev_malloc(&s.d_q, (size_t)n_q * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s.d_hist, s.hist_elems * sizeof(int64_t)));
-    HIPCHK(rscm::dev_malloc(&s.d_count, nc * sizeof(int64_t)));
-    HIPCHK(rscm::dev_malloc(&s.d_prefix, nc * nt * sizeof(uint64_t)));
-    HIPCHK(rscm::dev_malloc(&s.d_rank, nc * nt * sizeof(int64_t)));
-    HIPCHK(rscm::dev_malloc(&s.d_out, nc * (size_t)(n_q + 1) * sizeof(double)));
-    if (weighted) HIPCHK(rscm::dev_malloc(&s.d_over, sizeof(int32_t)));
-    HIPCHK(hipMemcpyAsync(s.d_rows, rows.data(), nr * sizeof(double*), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(s.d_q, q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(s.d_rows.alloc(nr));
+    HIPCHK(s.d_q.alloc((size_t)n_q));
+    HIPCHK(s.d_hist.alloc(s.hist_elems));
+    HIPCHK(s.d_count.alloc(nc));
+    HIPCHK(s.d_prefix.alloc(nc * nt));
+    HIPCHK(s.d_rank.alloc(nc * nt));
+    HIPCHK(s.d_out.alloc(nc * (size_t)(n_q + 1)));
+    if (weighted) HIPCHK(s.d_over.alloc(1));
+    HIPCHK(hipMemcpyAsync(s.d_rows.get(), rows.data(), nr * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(s.d_q.get(), q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));   // the host vectors go out of scope
     return RSCM_OK;
 }
@@ -121,12 +104,9 @@ int select_init(rscm_ens* h, SelectState& s, int32_t var_id, int32_t t_begin, in
                 int32_t flags)
 {
     if (int rc = select_flags(h, flags)) return rc;
-    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
-    if (t_begin < 0 || t_end > h->T || t_begin > t_end || t_stride < 1)
-        return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d", t_begin, t_end, t_stride);
+    if (int rc = check_row_range(h, var_id, t_begin, t_end, t_stride, false)) return rc;
     if (int rc = check_quantiles(n_q, q)) return rc;
-    if (!h->windowed && h->rows != h->T && t_end > 1)
-        return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
+    if (int rc = check_series_stored(h, t_end)) return rc;
     s.var = var_id;
     s.t_begin = t_begin;
     s.t_stride = t_stride;
@@ -164,12 +144,12 @@ int select_pass(rscm_ens* h, SelectState& s, int32_t* done, int64_t** buf_dev, i
     }
     if (int rc = set_device(h)) return rc;
     const size_t elems = (size_t)s.v_rows() * rscm::kSelBins * (s.pass == 0 ? 1 : (size_t)s.n_t);
-    HIPCHK(rscm::launch_select_hist(s.d_rows, s.weighted ? h->d_weights : nullptr, s.d_base, s.d_group, s.n_groups, h->N, s.n_comp, s.pass,
-                                    s.d_prefix, s.n_t, s.d_hist, elems, h->stream));
+    HIPCHK(rscm::launch_select_hist(s.d_rows.get(), s.weighted ? h->d_weights : nullptr, s.d_base, s.d_group, s.n_groups, h->N, s.n_comp, s.pass,
+                                    s.d_prefix.get(), s.n_t, s.d_hist.get(), elems, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     s.awaiting_commit = true;
     *done = 0;
-    if (buf_dev) *buf_dev = s.d_hist;
+    if (buf_dev) *buf_dev = s.d_hist.get();
     if (n) *n = (int64_t)elems;
     return RSCM_OK;
 }
@@ -179,14 +159,15 @@ int select_commit(rscm_ens* h, SelectState& s)
     if (!s.awaiting_commit) return fail(RSCM_ERR_STATE, "select: no pass to commit");
     if (int rc = set_device(h)) return rc;
     const bool check_w = s.weighted && s.pass == 0;   // the first weighted commit checks every row's W against 2^53
-    if (check_w) HIPCHK(hipMemsetAsync(s.d_over, 0, sizeof(int32_t), h->stream));
-    HIPCHK(rscm::launch_select_commit(s.d_hist, s.pass, s.v_rows(), s.n_t, s.d_q, s.d_count, s.d_prefix, s.d_rank, s.d_over, h->stream));
+    if (check_w) HIPCHK(hipMemsetAsync(s.d_over.get(), 0, sizeof(int32_t), h->stream));
+    HIPCHK(rscm::launch_select_commit(s.d_hist.get(), s.pass, s.v_rows(), s.n_t, s.d_q.get(), s.d_count.get(), s.d_prefix.get(), s.d_rank.get(),
+                                      s.d_over.get(), h->stream));
     s.awaiting_commit = false;
     if (++s.pass == rscm::kSelPasses)
-        HIPCHK(rscm::launch_select_finish(s.d_count, s.d_prefix, s.v_rows(), s.n_q, s.d_q, s.weighted, s.d_out, h->stream));
+        HIPCHK(rscm::launch_select_finish(s.d_count.get(), s.d_prefix.get(), s.v_rows(), s.n_q, s.d_q.get(), s.weighted, s.d_out.get(), h->stream));
     if (check_w) {
         int32_t over = 0;
-        HIPCHK(hipMemcpyAsync(&over, s.d_over, sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(&over, s.d_over.get(), sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         if (over)
             return fail(RSCM_ERR_INVALID, "weighted select: the weights of a row's non-NaN members%s sum to more than 2^53",
@@ -204,7 +185,7 @@ int select_result(rscm_ens* h, SelectState& s, double* out, double* count)
     std::vector<double> host((size_t)s.v_rows() * (s.n_q + 1));
     if (s.n_comp > 0) {
         if (int rc = set_device(h)) return rc;
-        HIPCHK(hipMemcpyAsync(host.data(), s.d_out, host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(hipMemcpyAsync(host.data(), s.d_out.get(), host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
     for (size_t r = 0; r < (size_t)s.n_rows * G; ++r) {
@@ -221,15 +202,11 @@ int select_begin(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, in
                  int32_t n_vec = 0, const double* const* vec = nullptr)
 {
     if (h->select) return fail(RSCM_ERR_STATE, "a select is already in flight on this handle: rscm_ens_select_end it first");
-    auto* s = new SelectState();
-    const int rc = vec || n_vec ? select_init_vectors(h, *s, n_vec, vec, n_q, q, flags)
-                                : select_init(h, *s, var_id, t_begin, t_end, t_stride, n_q, q, flags);
-    if (rc) {
-        s->release();
-        delete s;
+    auto s = std::make_unique<SelectState>();
+    if (int rc = vec || n_vec ? select_init_vectors(h, *s, n_vec, vec, n_q, q, flags)
+                              : select_init(h, *s, var_id, t_begin, t_end, t_stride, n_q, q, flags))
         return rc;
-    }
-    h->select = s;
+    h->select = s.release();
     return RSCM_OK;
 }
 
@@ -246,15 +223,29 @@ int quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, i
         rc = select_commit(h, s);
     }
     if (rc == RSCM_OK) rc = select_result(h, s, out, count);
-    if (s.d_rows) {
+    if (s.d_rows) {   // the stream is done with the buffers before s frees them
         (void)hipSetDevice(h->device);
         (void)hipStreamSynchronize(h->stream);
     }
-    s.release();
     return rc;
 }
 
 }  // namespace
+
+int check_row_range(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, bool at_least_one)
+{
+    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
+    if (t_begin < 0 || t_end > h->T || t_begin > t_end || (at_least_one && t_begin == t_end) || t_stride < 1)
+        return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d%s", t_begin, t_end, t_stride, at_least_one ? " (at least one row)" : "");
+    return RSCM_OK;
+}
+
+int check_series_stored(const rscm_ens* h, int32_t t_end)
+{
+    if (!h->windowed && h->rows != h->T && t_end > 1)
+        return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
+    return RSCM_OK;
+}
 
 int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                  int32_t* n_range)
@@ -294,8 +285,6 @@ int check_member_vector(const rscm_ens* h, const double* p, const char* what)
 
 void select_release(rscm_ens* h)
 {
-    if (!h->select) return;
-    h->select->release();
     delete h->select;
     h->select = nullptr;
 }
@@ -420,61 +409,48 @@ int rscm_ens_quantile_vectors(rscm_ens* h, int32_t n_vec, const double* const* v
 
 namespace {
 
-// Makes d_new[N] (device memory, taken over: freed on failure) the handle's weights if no weight is negative and they sum to at
-// most 2^53.  That bound on every handle keeps every histogram sum of the weighted select from wrapping (select.hip); on any
-// failure the weights set before stay.
-int install_weights(rscm_ens* h, int64_t* d_new)
+// Makes d_new[N] the handle's weights if no weight is negative and they sum to at most 2^53.  That bound on every handle keeps
+// every histogram sum of the weighted select from wrapping (select.hip); on any failure the weights set before stay.
+int install_weights(rscm_ens* h, rscm::DevBuf<int64_t> d_new)
 {
-    int32_t* d_flag = nullptr;
-    unsigned long long* d_total = nullptr;
+    rscm::DevBuf<int32_t> d_flag;
+    rscm::DevBuf<unsigned long long> d_total;
     int32_t neg = 0;
     unsigned long long total = 0;
-    hipError_t e = rscm::dev_malloc(&d_flag, sizeof(int32_t));
-    if (e == hipSuccess) e = rscm::dev_malloc(&d_total, sizeof total);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_total, 0, sizeof total, h->stream);
-    if (e == hipSuccess) e = rscm::launch_weights_check(d_new, h->N, d_flag, d_total, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&neg, d_flag, sizeof neg, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&total, d_total, sizeof total, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_flag);
-    (void)hipFree(d_total);
-    if (e != hipSuccess || neg || total > (1ull << 53)) {
-        (void)hipFree(d_new);
-        HIPCHK(e);
-        if (neg) return fail(RSCM_ERR_INVALID, "a member weight is negative");
-        return fail(RSCM_ERR_INVALID, "the member weights of this handle sum to more than 2^53");
-    }
-    (void)hipFree(h->d_weights);
-    h->d_weights = d_new;
+    HIPCHK(d_flag.alloc(1));
+    HIPCHK(d_total.alloc(1));
+    HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(int32_t), h->stream));
+    HIPCHK(hipMemsetAsync(d_total.get(), 0, sizeof total, h->stream));
+    HIPCHK(rscm::launch_weights_check(d_new.get(), h->N, d_flag.get(), d_total.get(), h->stream));
+    HIPCHK(hipMemcpyAsync(&neg, d_flag.get(), sizeof neg, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(&total, d_total.get(), sizeof total, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (neg) return fail(RSCM_ERR_INVALID, "a member weight is negative");
+    if (total > (1ull << 53)) return fail(RSCM_ERR_INVALID, "the member weights of this handle sum to more than 2^53");
+    d_new.install(h->d_weights);
     return RSCM_OK;
 }
 
-// ll on the device: the caller's pointer, or (host input) a copy in *tmp, which the caller frees
-int device_loglik(rscm_ens* h, const double* ll, int32_t on_device, double** tmp, const double** d_ll)
+// ll on the device: the caller's pointer, or (host input) a copy enqueued on the handle's stream into tmp
+int device_loglik(rscm_ens* h, const double* ll, int32_t on_device, rscm::DevBuf<double>& tmp, const double** d_ll)
 {
-    *tmp = nullptr;
-    if (on_device) {
-        *d_ll = ll;
-        return RSCM_OK;
-    }
-    HIPCHK(rscm::dev_malloc(tmp, (size_t)h->N * sizeof(double)));
-    HIPCHK(hipMemcpyAsync(*tmp, ll, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    *d_ll = *tmp;
+    *d_ll = ll;
+    if (on_device) return RSCM_OK;
+    HIPCHK(tmp.alloc((size_t)h->N));
+    HIPCHK(hipMemcpyAsync(tmp.get(), ll, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    *d_ll = tmp.get();
     return RSCM_OK;
 }
 
 int loglik_max(rscm_ens* h, const double* d_ll, double* out)
 {
-    unsigned long long* d_key = nullptr;
+    rscm::DevBuf<unsigned long long> d_key;
     unsigned long long key = rscm::order_key(-std::numeric_limits<double>::infinity());
-    hipError_t e = rscm::dev_malloc(&d_key, sizeof key);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_key, &key, sizeof key, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = rscm::launch_loglik_max(d_ll, h->d_status, h->N, d_key, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&key, d_key, sizeof key, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_key);
-    HIPCHK(e);
+    HIPCHK(d_key.alloc(1));
+    HIPCHK(hipMemcpyAsync(d_key.get(), &key, sizeof key, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_loglik_max(d_ll, h->d_status, h->N, d_key.get(), h->stream));
+    HIPCHK(hipMemcpyAsync(&key, d_key.get(), sizeof key, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     *out = rscm::key_value(key);
     return RSCM_OK;
 }
@@ -490,15 +466,10 @@ int rscm_ens_set_member_weights(rscm_ens* h, const int64_t* w, int32_t on_device
     if (!w) return fail(RSCM_ERR_INVALID, "weights are NULL");
     if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
     if (int rc = set_device(h)) return rc;
-    int64_t* d_new = nullptr;
-    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(int64_t)));
-    hipError_t e = hipMemcpyAsync(d_new, w, (size_t)h->N * sizeof(int64_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice,
-                                  h->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_new);
-        HIPCHK(e);
-    }
-    return install_weights(h, d_new);
+    rscm::DevBuf<int64_t> d_new;
+    HIPCHK(d_new.alloc((size_t)h->N));
+    HIPCHK(hipMemcpyAsync(d_new.get(), w, (size_t)h->N * sizeof(int64_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    return install_weights(h, std::move(d_new));
     GUARD_END
 }
 
@@ -517,13 +488,10 @@ int rscm_ens_loglik_max(rscm_ens* h, const double* ll, int32_t on_device, double
     NEED(h);
     if (!ll || !out) return fail(RSCM_ERR_INVALID, "ll or out is NULL");
     if (int rc = set_device(h)) return rc;
-    double* tmp = nullptr;
+    rscm::DevBuf<double> tmp;
     const double* d_ll = nullptr;
-    int rc = device_loglik(h, ll, on_device, &tmp, &d_ll);
-    if (rc == RSCM_OK) rc = loglik_max(h, d_ll, out);
-    (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(tmp);
-    return rc;
+    if (int rc = device_loglik(h, ll, on_device, tmp, &d_ll)) return rc;
+    return loglik_max(h, d_ll, out);   // synchronised: tmp has been read
     GUARD_END
 }
 
@@ -537,22 +505,16 @@ int rscm_ens_set_weights_from_loglik(rscm_ens* h, const double* ll, int32_t on_d
         return fail(RSCM_ERR_INVALID, "ll_max must be finite or -inf, got %g", ll_max);
     if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
     if (int rc = set_device(h)) return rc;
-    int64_t* d_new = nullptr;
-    HIPCHK(rscm::dev_malloc(&d_new, (size_t)h->N * sizeof(int64_t)));
-    double* tmp = nullptr;
-    const double* d_ll = nullptr;
-    int rc = device_loglik(h, ll, on_device, &tmp, &d_ll);
-    hipError_t e = hipSuccess;
-    if (rc == RSCM_OK) e = rscm::launch_weights_from_loglik(d_ll, h->d_status, h->N, ll_max, bits, d_new, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    (void)hipFree(tmp);
-    if (rc != RSCM_OK || e != hipSuccess || es != hipSuccess) {
-        (void)hipFree(d_new);
-        if (rc != RSCM_OK) return rc;
-        HIPCHK(e);
-        HIPCHK(es);
+    rscm::DevBuf<int64_t> d_new;
+    HIPCHK(d_new.alloc((size_t)h->N));
+    {
+        rscm::DevBuf<double> tmp;
+        const double* d_ll = nullptr;
+        if (int rc = device_loglik(h, ll, on_device, tmp, &d_ll)) return rc;
+        HIPCHK(rscm::launch_weights_from_loglik(d_ll, h->d_status, h->N, ll_max, bits, d_new.get(), h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
     }
-    return install_weights(h, d_new);   // refused if N weights of up to 2^bits sum to more than 2^53
+    return install_weights(h, std::move(d_new));   // refused if N weights of up to 2^bits sum to more than 2^53
     GUARD_END
 }
 
@@ -571,25 +533,17 @@ int rscm_ens_set_member_groups(rscm_ens* h, const int32_t* group, int32_t on_dev
         return fail(RSCM_ERR_INVALID, "n_groups = %d: must be in [1, %d]", n_groups, rscm::kMaxMemberGroups);
     if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
     if (int rc = set_device(h)) return rc;
-    int32_t* d_new = nullptr;
-    int32_t* d_flag = nullptr;
+    rscm::DevBuf<int32_t> d_new, d_flag;
     int32_t bad = 0;
-    const size_t bytes = (size_t)h->N * sizeof(int32_t);
-    hipError_t e = rscm::dev_malloc(&d_new, bytes);
-    if (e == hipSuccess) e = rscm::dev_malloc(&d_flag, sizeof(int32_t));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_new, group, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(d_flag, 0, sizeof(int32_t), h->stream);
-    if (e == hipSuccess) e = rscm::launch_groups_check(d_new, h->N, n_groups, d_flag, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&bad, d_flag, sizeof bad, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    (void)hipFree(d_flag);
-    if (e != hipSuccess || bad) {
-        (void)hipFree(d_new);
-        HIPCHK(e);
-        return fail(RSCM_ERR_INVALID, "a member's group id is outside [-1, %d)", n_groups);
-    }
-    (void)hipFree(h->d_groups);
-    h->d_groups = d_new;
+    HIPCHK(d_new.alloc((size_t)h->N));
+    HIPCHK(d_flag.alloc(1));
+    HIPCHK(hipMemcpyAsync(d_new.get(), group, (size_t)h->N * sizeof(int32_t), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(d_flag.get(), 0, sizeof(int32_t), h->stream));
+    HIPCHK(rscm::launch_groups_check(d_new.get(), h->N, n_groups, d_flag.get(), h->stream));
+    HIPCHK(hipMemcpyAsync(&bad, d_flag.get(), sizeof bad, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    if (bad) return fail(RSCM_ERR_INVALID, "a member's group id is outside [-1, %d)", n_groups);
+    d_new.install(h->d_groups);
     h->n_groups = n_groups;
     return RSCM_OK;
     GUARD_END

@@ -208,7 +208,7 @@ def test_the_shipped_library_reads_only_the_documented_environment():
         if f.endswith((".cpp", ".hip", ".hpp")):
             for m in re.finditer(r"getenv\(([^)]*)\)", open(os.path.join(csrc, f)).read()):
                 found.setdefault(f, []).append(m.group(1))
-    assert found == {"ens.hpp": ['"RSCM_POISON_ALLOC"'], "experiment_env.hpp": ["name"], "launch_host.cpp": ['"RSCM_SPLIT_RUNS"']}, found
+    assert found == {"dev_buf.hpp": ['"RSCM_POISON_ALLOC"'], "experiment_env.hpp": ["name"], "launch_host.cpp": ['"RSCM_SPLIT_RUNS"']}, found
     guard = open(os.path.join(csrc, "experiment_env.hpp")).read()
     assert guard.index("#ifdef RSCM_EXPERIMENTS") < guard.index("getenv(name)") < guard.index("#else")
     header = open(os.path.join(ROOT, "include", "rscm_gpu.h")).read()
