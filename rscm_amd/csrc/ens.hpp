@@ -25,6 +25,7 @@
 #include "dev_buf.hpp"
 #include "kinds.hpp"
 #include "rscm_device.hpp"
+#include "two_layer_year_facts.hpp"
 
 // thread-local error text behind rscm_gpu_last_error(); returns `code`
 int fail(int code, const char* fmt, ...);
@@ -83,6 +84,10 @@ struct rscm_ens {
     std::vector<int32_t> nsub_tl, nsub_cc;
     int32_t* d_nsub_tl = nullptr;
     int32_t* d_nsub_cc = nullptr;
+    // two-layer kind: what is proved once about the schedule and the forcing table for the uniform year (two_layer_year_facts.hpp).
+    // The schedule's part is rebuilt with nsub_tl (refresh_schedule) and not read while schedule_dirty; the table's part is formed by
+    // rscm_ens_set_forcing from the caller's array -- the only writer of d_forcing -- and dropped there before the table is touched
+    rscm::tl::YearFacts year_facts;
 
     double* d_params = nullptr;  // [P][N]
     int32_t ag_rows_set = 0;     // aggregate kind: 1 + the highest contributor row rscm_ens_set_forcing has ever been given data for

@@ -270,6 +270,15 @@ void fill_common(const rscm_ens* h, int32_t step_begin, int32_t step_end, Args& 
     a.status = h->d_status;
 }
 
+// The year's uniform facts of a launch of [a.step_begin, a.step_end) with a's source and offset (TwoLayerArgs::year_facts): 0 for a fused
+// launch (an empty range), and nothing about the forcing unless the launch reads the handle's plain table
+uint32_t two_layer_year_facts(const rscm_ens* h, const rscm::TwoLayerArgs& a)
+{
+    if (a.step_end <= a.step_begin) return 0;
+    const int32_t nsub = h->schedule_dirty ? 0 : h->year_facts.nsub_uniform(a.step_begin, a.step_end);
+    const bool plain = !a.link && a.n_comp == 0 && !a.noise_on && a.forcing == h->d_forcing && a.n_scen == h->n_scen;
+    return rscm::year_facts_word(nsub, plain && h->year_facts.forcing_boxed(a.step_begin, a.step_end, a.src_off));
+}
 // shared forcing and scenarios, sub-step table, guard hooks, series
 void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::InputLinks& links, int32_t linked, rscm::TwoLayerArgs& a)
 {
@@ -302,6 +311,7 @@ void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, con
             a.noise_on = rscm::noise_code(h->noise_kind, t0 > 0 && h->noise_state_index == t0 - 1);
         }
     }
+    a.year_facts = two_layer_year_facts(h, a);
 }
 rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t end, int64_t m0, int64_t count)
 {
@@ -608,7 +618,12 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
             fill_two_layer(h, step_begin, step_end, links, linked, a);
             // the noise cache is dropped while the run is issued and stands at the run's last index only if all of it was
             if (step_end > step_begin) h->noise_state_index = -1;
-            if (int rc = launch_whole_or_split(h, a, linked != 0, false, [mode](const rscm::TwoLayerArgs& c, hipStream_t st) { return rscm::launch_two_layer(c, mode, st); }))
+            // (a chunk of a cut run states the facts of its own steps: one step of another length costs one chunk the uniform year)
+            if (int rc = launch_whole_or_split(h, a, linked != 0, false, [mode, h](const rscm::TwoLayerArgs& c, hipStream_t st) {
+                    rscm::TwoLayerArgs d = c;
+                    d.year_facts = two_layer_year_facts(h, d);
+                    return rscm::launch_two_layer(d, mode, st);
+                }))
                 return rc;
             if (rscm::noise_keeps_state(a.noise_on) && step_end > step_begin && h->noise_cache_kept()) h->noise_state_index = step_end - 1 + a.src_off;
             return RSCM_OK;

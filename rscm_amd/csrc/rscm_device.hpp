@@ -384,8 +384,20 @@ struct TwoLayerArgs {
     double noise_sigma;
     int64_t noise_member0;
     int32_t noise_on;
+    uint32_t year_facts;     // what the host has proved about the launch's years (year_facts_word below; two_layer_year_facts.hpp); 0: nothing.
+                             // Sits in what was padding, like n_comp
     double noise_phi;
 };
+// TwoLayerArgs::year_facts: the low bits hold the sub-step count that every step of [step_begin, step_end) has (0: they differ, or
+// nobody looked), the top bit says that every forcing value the launch can read is +0 or a magnitude in the chunk guard's forcing box
+// (two_layer_chunk_box.hpp) -- set for a plain table only: no link, no mix, no noise.  A fused launch passes 0.
+constexpr uint32_t kYearForcingBoxed = 0x80000000u;
+constexpr uint32_t year_facts_word(int32_t nsub_uniform, bool forcing_boxed)
+{
+    return (nsub_uniform > 0 ? (uint32_t)nsub_uniform : 0u) | (forcing_boxed ? kYearForcingBoxed : 0u);
+}
+constexpr int32_t year_nsub_uniform(uint32_t facts) { return (int32_t)(facts & ~kYearForcingBoxed); }
+constexpr bool year_forcing_boxed(uint32_t facts) { return (facts & kYearForcingBoxed) != 0; }
 // The kinds of forcing noise: a handle's setting (rscm_ens::noise_kind) and the NOISE template value of the two-layer kernels
 constexpr int32_t kNoiseKindNone = 0, kNoiseKindWhite = 1, kNoiseKindRed = 2, kNoiseKindMembers = 3;
 // TwoLayerArgs::noise_on (0: no noise): a kind, and for red and members whether noise_state holds e at the index before the launch's

@@ -255,6 +255,7 @@ int refresh_schedule(rscm_ens* h)
                     "TwoLayer RK4 step %.17g does not land on the end of model step %d "
                     "([%.17g, %.17g]) within 5e-3 (the reference panics in get_last_step)",
                     h->h_tl, bad, h->bounds[bad], h->bounds[bad + 1]);
+    if (h->kind == RSCM_KIND_TWO_LAYER) h->year_facts.set_schedule(h->nsub_tl.data(), h->nsub_tl.size());
     HIPCHK(hipMemcpyAsync(h->d_nsub_tl, h->nsub_tl.data(), h->nsub_tl.size() * sizeof(int32_t),
                           hipMemcpyHostToDevice, h->stream));
     if (h->kind == RSCM_KIND_COUPLED || h->kind == RSCM_KIND_CARBON_CYCLE) {
@@ -981,6 +982,7 @@ int rscm_ens_set_forcing(rscm_ens* h, int32_t var_id, int32_t n_scen, const doub
                             scenario_of_member[i], n_scen);
     if (int rc = set_device(h)) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
+    h->year_facts.drop_forcing();   // from here on the table may change: the verdict on the new one is formed once it stands
     if (n_scen != h->n_scen || !h->d_forcing) {
         HIPCHK(hipFree(h->d_forcing));
         h->d_forcing = nullptr;
@@ -1008,6 +1010,7 @@ int rscm_ens_set_forcing(rscm_ens* h, int32_t var_id, int32_t n_scen, const doub
     h->n_scen = n_scen;
     h->source = source;
     h->forcing_set = true;
+    if (h->kind == RSCM_KIND_TWO_LAYER && h->n_comp == 0) h->year_facts.set_forcing(series, n_scen, h->T);   // (a plain table: [S][T])
     if (h->kind == RSCM_KIND_AGGREGATE) {  // rows after the last non-NaN one of the block stay out of the sums anyway
         int32_t used = 0;
         for (int32_t sidx = 0; sidx < n_scen; ++sidx)

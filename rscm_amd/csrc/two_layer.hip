@@ -64,7 +64,7 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
-    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE, NoCache, false, MIX, NOISE>(a, lds_forcing, i, a.step_begin, a.step_end);
+    const int32_t guard = tl::two_layer_body<MODE, LDS, STORE, NoCache, false, MIX, NOISE, true>(a, lds_forcing, i, a.step_begin, a.step_end);
     if constexpr (MODE == 0) {
         if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
     }
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(kBlock) void two_layer_ref_kernel(TwoLayerArgs a, T
     }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
-    const int32_t guard = tl::two_layer_body<MODE, LDS, false, NoCache, true, MIX>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(), &r);
+    const int32_t guard = tl::two_layer_body<MODE, LDS, false, NoCache, true, MIX, 0, true>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(), &r);
     if constexpr (MODE == 0) {
         if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
     }

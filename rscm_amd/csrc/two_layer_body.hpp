@@ -131,6 +131,20 @@ __device__ __forceinline__ bool params_in(const TLConst& p, double h, double hal
 // the sub-step count of the annual axis (h = 0.1): its year body is unrolled
 constexpr int32_t kUnrolledSubSteps = 10;
 
+// How a wavefront's years run (two_layer_body): the guard, and the two facts of the uniform year
+template <int32_t GUARD, bool UNIFORM = false, bool BOXED = false>
+struct YearLane {
+    static constexpr int32_t kGuard = GUARD;
+    static constexpr bool kUniform = UNIFORM, kBoxed = BOXED;
+};
+
+// Where the uniform year stores: the row the launch writes first, the same for the whole wavefront, and the member's index in it
+struct UniformRows {
+    double* ts = nullptr;
+    double* td = nullptr;
+    int64_t member = 0;
+};
+
 struct TLFast {
     double l0, a, ee, ed;  // lambda0/Cs, a/Cs, efficacy*eta/Cs, eta/Cd
 };
@@ -314,7 +328,8 @@ enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuar
 // rscm_ens_set_params found uniform is one element for the wavefront.  sigma_i, phi_i and sigma_i sqrt(1 - phi_i phi_i) live in vector
 // registers (four more than NOISE == 2, where they are kernel arguments: the EXACT plain kernel crosses the 168-register step).  Nothing validates the rows: NaN, Inf or |phi_i| > 1 make that
 // lane's forcing NaN and leave every other lane alone; a lane whose forcing leaves the guard's box replays its year as with any forcing.
-template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, int NOISE = 0>
+// ALONE: a stand-alone launch (two_layer.hip), whose a.year_facts the host has filled in; the fused launches (group.hip) pass none.
+template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, int NOISE = 0, bool ALONE = false>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
                                                int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
 {
@@ -471,17 +486,29 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
         // one decision per wavefront: every member in the boxes -> the state guard; in the chunk boxes as well -> the chunk guard
         const bool guard_states = __all(!a.numerator_guard && box::params_in(p, h, half_step));
         const bool guard_chunks = guard_states && __all(chunk::params_in(p, h, half_step, sixth));
+        // The uniform year (TwoLayerArgs::year_facts, proved by the host: two_layer_year_facts.hpp): every step of the launch has
+        // kUnrolledSubSteps sub-steps, so a wavefront under the chunk guard neither loads nor tests the count and the generic sub-step
+        // loops are not part of its year loop; with the forcing proved inside the chunk's box as well, the year's check of it is left
+        // out (it would have found acc = 0).  Same statements otherwise.  Kernel arguments: the choice is made once, outside the loop.
+        // The instantiations of fused launches, mix handles and noise do not have the lane: they compile to what they were.
+        constexpr bool kUniformLane = ALONE && !Cache::kOn && !MIX && !NOISE;
         // kGuard 0: a tag per numerator; 1: the state at every sub-step; kChunkSubSteps: the state at every kGuard-th sub-step
-        auto years = [&](auto guard) {
-            constexpr int32_t kGuard = decltype(guard)::value;
+        // (out: read by the uniform year only, and a parameter on purpose -- what the lambda captures, and in which order, stays what it
+        // was, and with it the code of the instantiations without the lane)
+        auto years = [&](auto lane, [[maybe_unused]] UniformRows out) {
+            constexpr int32_t kGuard = decltype(lane)::kGuard;
             constexpr bool kStates = kGuard > 0;
             constexpr bool kChunks = kGuard > 1;   // the chunk guard covers the unrolled 10-sub-step year only
+            constexpr bool kUniform = decltype(lane)::kUniform;   // every year has kUnrolledSubSteps sub-steps
+            constexpr bool kBoxed = decltype(lane)::kBoxed;       // ... and a forcing inside the chunk's box
+            static_assert(!kUniform || (kChunks && kUniformLane), "the uniform year belongs to the chunk guard of a plain launch");
+            static_assert(!kBoxed || kUniform, "the forcing's verdict is used by the uniform year only");
             for (int32_t n = step_begin; n < step_end; ++n) {
                 const double erf = erf_next;
-                const int32_t m = m_next;
+                const int32_t m = kUniform ? kUnrolledSubSteps : m_next;
                 const int32_t np = n < last ? n + 1 : n;
                 erf_next = forcing_ahead(n, np, erf_next);
-                m_next = a.nsub[np];
+                if constexpr (!kUniform) m_next = a.nsub[np];
                 const double ts0 = ts, td0 = td;
                 bool replay;
                 if constexpr (kStates) {
@@ -490,10 +517,10 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
                         if (tag) acc = max3_u32(acc, box_tag(ts, edge), box_tag(td, edge));
                         rk4_step_exact<true, false>(p, erf, h, half_step, sixth, ts, td, no_tags);
                     };
-                    if (kChunks && m == kUnrolledSubSteps) {
+                    if (kChunks && (kUniform || m == kUnrolledSubSteps)) {
                         // the chunk guard: the state at every kGuard-th sub-step against the chunk's boxes
                         constexpr uint32_t kEdge = box::neg_edge(chunk::kStateLo), kSpan = box::span(chunk::kStateLo, chunk::kStateHi);
-                        uint32_t acc = box::forcing_in<chunk::kForcingLo, chunk::kForcingHi>(erf) ? 0u : ~0u;
+                        uint32_t acc = kBoxed ? 0u : box::forcing_in<chunk::kForcingLo, chunk::kForcingHi>(erf) ? 0u : ~0u;
 #pragma unroll
                         for (int32_t s = 0; s < kUnrolledSubSteps; ++s) sub_step(acc, kEdge, s % kGuard == 0);
                         replay = acc >= kSpan;
@@ -524,21 +551,34 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
                     int32_t unused = 0;
                     for (int32_t s = 0; s < m; ++s) rk4_step_exact<false>(p, erf, h, half_step, sixth, ts, td, unused);
                 }
-                if constexpr (STORE) {
+                if constexpr (STORE && !kUniform) {
                     *out_ts = ts;
                     *out_td = td;
                     cache.put(0, ts);
                     cache.put(1, td);
                     out_ts += N;
                     out_td += N;
+                } else if constexpr (STORE) {   // a wave-uniform row and the member's index
+                    out.ts[out.member] = ts;
+                    out.td[out.member] = td;
+                    out.ts += N;
+                    out.td += N;
                 } else {
                     consume(n + 1);
                 }
             }
         };
-        if (guard_chunks) years(std::integral_constant<int32_t, chunk::kChunkSubSteps>());
-        else if (guard_states) years(std::integral_constant<int32_t, 1>());
-        else years(std::integral_constant<int32_t, 0>());
+        bool uniform_year = false;
+        if constexpr (kUniformLane) uniform_year = guard_chunks && year_nsub_uniform(a.year_facts) == kUnrolledSubSteps;
+        if (uniform_year) {
+            if constexpr (kUniformLane) {
+                const UniformRows rows{a.ts + (size_t)(step_begin + 1) * N, a.td + (size_t)(step_begin + 1) * N, i};
+                if (year_forcing_boxed(a.year_facts)) years(YearLane<chunk::kChunkSubSteps, true, true>(), rows);
+                else years(YearLane<chunk::kChunkSubSteps, true, false>(), rows);
+            }
+        } else if (guard_chunks) years(YearLane<chunk::kChunkSubSteps>(), UniformRows());
+        else if (guard_states) years(YearLane<1>(), UniformRows());
+        else years(YearLane<0>(), UniformRows());
         guard = guard_chunks ? kGuardChunks : guard_states ? kGuardStates : kGuardNumerators;
     } else {
         double inv_cs;
