@@ -99,8 +99,11 @@ extern "C" {
  *      per-member device vectors: rscm_ens_member_variability, RSCM_VAR_MEAN, RSCM_VAR_LINEAR, RSCM_VAR_DIFFERENCE,
  *      rscm_ens_loglik_vectors_device
  *  17  per-member power spectra in frequency bands and a spectral (Whittle-type) likelihood over them: rscm_ens_member_spectrum,
- *      rscm_gpu_spectrum_coefficients, rscm_ens_loglik_spectrum_device */
-#define RSCM_GPU_ABI_MINOR 17
+ *      rscm_gpu_spectrum_coefficients, rscm_ens_loglik_spectrum_device
+ *  18  diagnostic variables: per-member linear combinations of a handle's stored variables (ocean heat content) that every reader of
+ *      rows takes by variable id: rscm_ens_define_diagnostic, rscm_ens_diagnostic, rscm_ens_compute_diagnostic,
+ *      rscm_ens_clear_diagnostics, rscm_ens_n_diagnostics, RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX */
+#define RSCM_GPU_ABI_MINOR 18
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1167,6 +1170,57 @@ RSCM_API int rscm_gpu_spectrum_coefficients(int32_t n, double* out /*[J]*/);
  * The result lands in the handle's likelihood vector (*out_dev); add_dev may BE that buffer, as for rscm_ens_loglik_vectors_device. */
 RSCM_API int rscm_ens_loglik_spectrum_device(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* record,
                                              const int32_t* count, const double* add_dev, void** out_dev);
+
+/* ---- diagnostic variables (ABI minor 18) ---------------------------------------------------------- */
+/* A diagnostic variable of a handle is a linear combination of that handle's stored variables with per-member weights.  For member i
+ * and row t, with K terms (1 <= K <= RSCM_DIAG_MAX_TERMS), x_k = row t of the stored variable term_var[k], p the parameter block:
+ *     w_k[i] = term_scale[k] * p[term_param_row[k]][i]      (term_param_row[k] >= 0)
+ *     w_k[i] = term_scale[k]                                (term_param_row[k] == -1)
+ *     y[i]   = w_0[i] * x_0[i];   then for k = 1 .. K - 1 in order   y[i] = y[i] + w_k[i] * x_k[i]
+ * Every product and every sum is one f64 operation rounded on its own (no FMA); the weight is formed once per member and is the same
+ * for every row; NaN and Inf propagate by IEEE arithmetic (there is no per-member "bad" flag: the readers have their own).  Bit-exact
+ * against this statement.  The ocean heat content of a two-layer handle is (Ts, row 4), (Td, row 5): C Ts + Cd Td in W yr m^-2.
+ *
+ * Ids.  Diagnostics get the variable ids V, V + 1, ... (V = rscm_ens_n_vars, which keeps reporting the stored variables) in order
+ * of definition, at most RSCM_DIAG_MAX per handle; rscm_ens_n_diagnostics reports how many are defined.
+ *
+ * rscm_ens_define_diagnostic: RSCM_ERR_INVALID for n_terms outside 1..4, a term variable that is 0 (the input), negative or >= V (no
+ * diagnostic of a diagnostic), a parameter row outside -1 .. P - 1, a scale that is not finite, a fifth definition.
+ * rscm_ens_diagnostic reads a definition back (unused terms: 0, -1, 0.0) with the rows it holds now: *rows_held rows from *t_begin
+ * with *t_stride (0, 0, 1 when none are held or they are stale).  Any out pointer may be NULL.
+ * rscm_ens_compute_diagnostic forms the rows t_begin, t_begin + t_stride, ... < t_end into a store [R][N] the handle owns (allocated
+ * at first use, reused when large enough, freed by rscm_ens_destroy and rscm_ens_clear_diagnostics).  Every source row must be computed
+ * and resident: full storage, the window and the output store serve as for rscm_ens_member_indicators, with its refusals (a bad range
+ * or stride RSCM_ERR_INVALID; rows beyond the time index, rows no longer resident, a RSCM_FLAG_NO_SERIES handle with t_end > 1
+ * RSCM_ERR_STATE; on these the rows held before stay).  One range per diagnostic at a time: a new compute replaces the old rows.
+ * rscm_ens_clear_diagnostics removes the definitions and frees the stores.  A var_id that names no diagnostic: RSCM_ERR_INVALID.
+ * Define, compute and clear refuse with RSCM_ERR_STATE while a staged select is in flight (it may be reading the rows).
+ *
+ * Readers.  The id of a defined diagnostic is accepted by rscm_ens_select_begin* / rscm_ens_quantile_rows* (plain, weighted, anomaly,
+ * grouped), rscm_ens_set_baseline, rscm_ens_member_indicators, _variability, _spectrum, the stored likelihoods rscm_ens_loglik,
+ * _device, _ref, _ref_device (observation rows and reference-period rows), rscm_ens_summary and rscm_ens_get_series.  A row outside
+ * the held range is to them what a row that is not resident is on a windowed handle: RSCM_ERR_STATE.  Everything else keeps refusing
+ * the id as it refuses any var_id >= V (RSCM_ERR_INVALID): rscm_ens_series_devptr, rscm_ens_summary_series, rscm_ens_quantile_series,
+ * rscm_ens_link_input, rscm_ens_set_state, rscm_ens_set_initial, the fused rscm_ens_run_loglik*, the samplers' observation and
+ * reference lists, output_vars of rscm_ens_create_windowed.
+ *
+ * Staleness.  The rows are a snapshot of the sources at compute time.  The handle keeps a write epoch that moves with every entry
+ * point that can change a stored row, a parameter row or the time index: rscm_ens_run, _run_async, rscm_ens_run_lockstep (every
+ * handle of the run), rscm_ens_run_loglik*, a sampler's evaluation runs, rscm_ens_rewind, _clear_series, _clear_rows_after,
+ * _set_time_index, _set_state, _set_initial, _set_internal_state, _set_params, _set_params_aos, _sample_lhs, rscm_ens_gather_members
+ * (the destination), rscm_ens_set_forcing_noise*, _clear_forcing_noise, rscm_ens_set_mode.  A reader that finds the rows computed at
+ * another epoch gets RSCM_ERR_STATE, "diagnostic N is stale: compute it again".  Definitions survive all of these; only the rows go
+ * stale.  rscm_ens_params_devptr and rscm_ens_series_devptr do NOT move the epoch: writes through pointers the library handed out
+ * are the caller's to follow with a new rscm_ens_compute_diagnostic. */
+#define RSCM_DIAG_MAX_TERMS 4
+#define RSCM_DIAG_MAX 4
+RSCM_API int rscm_ens_define_diagnostic(rscm_ens* h, int32_t n_terms, const int32_t* term_var, const int32_t* term_param_row,
+                                        const double* term_scale, int32_t* var_id_out);
+RSCM_API int rscm_ens_diagnostic(rscm_ens* h, int32_t var_id, int32_t* n_terms, int32_t term_var[4], int32_t term_param_row[4],
+                                 double term_scale[4], int32_t* rows_held, int32_t* t_begin, int32_t* t_stride);
+RSCM_API int rscm_ens_compute_diagnostic(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride);
+RSCM_API int rscm_ens_clear_diagnostics(rscm_ens* h);
+RSCM_API int rscm_ens_n_diagnostics(const rscm_ens* h, int32_t* out);
 
 /* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
 /* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,

@@ -35,7 +35,8 @@ NOISE_STREAM_TAG = 0x4E5A   # RSCM_NOISE_STREAM_TAG: the Philox stream of the fo
 SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
 SELECT_ANOMALY = 2
 SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
-VAR_MEAN, VAR_LINEAR, VAR_DIFFERENCE = 0, 1, 2    # rscm_ens_member_variability's detrending modes
+DIAG_MAX_TERMS, DIAG_MAX = 4, 4    # RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX: terms per diagnostic variable, diagnostics per handle
+VAR_MEAN, VAR_LINEAR, VAR_DIFFERENCE = 0, 1, 2   # rscm_ens_member_variability's detrending modes
 
 TL_VARS = {"Effective Radiative Forcing": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2}
 CP_VARS = {"Emissions|CO2|Anthropogenic": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2,
@@ -348,6 +349,11 @@ SIGNATURES = {
                                            C.POINTER(C.c_void_p)]),
     "rscm_gpu_spectrum_coefficients": (C.c_int, [C.c_int32, _dp]),
     "rscm_ens_loglik_spectrum_device": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), _dp, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_void_p)]),
+    "rscm_ens_define_diagnostic": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _ip]),
+    "rscm_ens_diagnostic": (C.c_int, [_h, C.c_int32, _ip, _ip, _ip, _dp, _ip, _ip, _ip]),
+    "rscm_ens_compute_diagnostic": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "rscm_ens_clear_diagnostics": (C.c_int, [_h]),
+    "rscm_ens_n_diagnostics": (C.c_int, [_h, _ip]),
     "rscm_ens_quantile_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, _dp]),
     "rscm_ens_select_begin_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32]),
     "rscm_ens_exceedance": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

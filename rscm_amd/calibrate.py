@@ -310,6 +310,26 @@ def reference_rows(times, period) -> List[int]:
     return [n for n, t in enumerate(times) if start <= t <= end]
 
 
+
+def refuse_diagnostic_target(model, name: str) -> None:
+    """Targets name stored variables.  A diagnostic variable (``define_diagnostic``) has rows only once ``compute_diagnostic`` has
+    formed them, which the fused run + likelihood and the samplers' evaluation runs never do."""
+    names = model._diagnostics if hasattr(model, "ensembles") else model.ensemble._diagnostic_names
+    if name in names:
+        raise ValueError(f"{name!r} is a diagnostic variable: diagnostics are scored by run(), compute_diagnostic() and loglik() on "
+                         "the ensemble, because the fused run + likelihood and the samplers do not see them")
+
+
+def refuse_diagnostic_targets(runner, target) -> None:
+    """The same for a whole target against the diagnostics of the runner's builder (``ModelBuilder.with_diagnostic``), before any
+    model is built: what the samplers ask when they are made."""
+    names = {n for n, _, _ in getattr(getattr(runner, "_builder", None), "_diagnostics", ())}
+    for name, _ in target.variables():
+        if name in names:
+            raise ValueError(f"{name!r} is a diagnostic variable: diagnostics are scored by run(), compute_diagnostic() and loglik() "
+                             "on the ensemble, because the fused run + likelihood and the samplers do not see them")
+
+
 class GaussianLikelihood:
     """likelihood.rs:167-250.  ``ln_likelihood`` is the host form over the reference's
     ``{variable: {time: value}}`` output; the batch form runs on the device."""
@@ -447,12 +467,15 @@ class ModelRunner:
             if unknown:
                 raise ValueError(f"unknown (or ambiguous) model parameter(s) {unknown}; known: {sorted(probe.param_home)}")
             for v in self._outputs:
+                refuse_diagnostic_target(probe, v)
                 probe.variable_home(v)
             self._rows = []
             return
         unknown = [p for p in self._param_names if p not in probe.param_order]
         if unknown:
             raise ValueError(f"unknown model parameter(s) {unknown}; known: {list(probe.param_order)}")
+        for v in self._outputs:
+            refuse_diagnostic_target(probe, v)
         missing = [v for v in self._outputs if v not in probe.ensemble.var_ids]
         if missing:
             raise KeyError(f"Model output missing variable: {missing[0]}")
@@ -549,6 +572,7 @@ class ModelRunner:
         ov, ot, val, sig = [], [], [], []
         fused = not self._graph and probe.ensemble.kind == L.KIND_TWO_LAYER
         for name, vt in target.variables():
+            refuse_diagnostic_target(probe, name)
             if self._graph:
                 probe.variable_home(name)
             elif name not in probe.ensemble.var_ids or probe.ensemble.var_ids[name] == 0:
@@ -844,6 +868,7 @@ class EnsembleSampler:
                  target: Target, stretch_a: float = 2.0):
         if stretch_a <= 1.0:
             raise ValueError(f"Stretch move scale parameter must be > 1.0, got {stretch_a}")
+        refuse_diagnostic_targets(runner, target)
         self.params, self.runner, self.likelihood, self.target = params, runner, likelihood, target
         self.a = float(stretch_a)
         self.default_n_walkers = max(2 * len(params), 32)
@@ -980,6 +1005,7 @@ class DeviceEnsembleSampler:
         if getattr(getattr(runner, "_builder", None), "_noise", None) is not None:
             raise ValueError("DeviceEnsembleSampler: the runner's builder has forcing noise (with_forcing_noise); the likelihood of one "
                              "noise realisation per walker index is not a target the stretch move samples")
+        refuse_diagnostic_targets(runner, target)
         self.params, self.runner, self.likelihood, self.target = params, runner, likelihood, target
         self.a = float(stretch_a)
         self.default_n_walkers = max(2 * len(params), 32)
@@ -1007,6 +1033,7 @@ class DeviceEnsembleSampler:
     def _observations(self, model: Model):
         ov, ot, val, sig = [], [], [], []
         for name, vt in self.target.variables():
+            refuse_diagnostic_target(model, name)
             if name not in model.ensemble.var_ids or model.ensemble.var_ids[name] == 0:
                 raise KeyError(f"Model output missing variable: {name}")
             for obs in vt.observations:
@@ -1075,6 +1102,7 @@ class DeviceEnsembleSampler:
             p_rows = np.array([model.param_home[p][1] for p in self.runner.param_names], dtype=np.int32)
             oo, ov, ot, val, sig = [], [], [], [], []
             for name, vt in self.target.variables():
+                refuse_diagnostic_target(model, name)
                 owner_ens, vid = model.variable_home(name)
                 k = next(j for j, e in enumerate(handles) if e is owner_ens)
                 for obs in vt.observations:

@@ -471,6 +471,7 @@ class ModelBuilder:
         self._noise: Optional[Tuple[float, int]] = None   # with_forcing_noise: (sigma, seed)
         self._noise_phi = 0.0                             # ... and its phi (0: white)
         self._noise_params = False                        # with_forcing_noise_parameters: sigma and phi are parameter rows
+        self._diagnostics: List[Tuple[str, Dict[str, Optional[str]], Dict[str, float]]] = []   # with_diagnostic
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -521,6 +522,40 @@ class ModelBuilder:
         self._mix = (str(variable), {str(n): ts for n, ts in components.items()},
                      {n: float((scales or {}).get(n, 1.0)) for n in names})
         return self
+
+    def with_diagnostic(self, name: str, weights: Dict[str, Optional[str]], scales: Optional[Dict[str, float]] = None) -> "ModelBuilder":
+        """Extension: a diagnostic variable ``name`` of the built model -- per member ``sum_k scale_k p_k x_k`` over the entries
+        ``{variable: parameter name or None}`` of ``weights`` in their order, ``x_k`` the variable's row and ``p_k`` the member's
+        own value of the parameter (``None``: no parameter, the scale alone; ``scales`` default 1.0).  ``build()`` defines it on
+        the model's ensemble, the parameter resolved through ``Model.param_order`` (``"forcing_scale|*"`` and ``"forcing_noise|*"``
+        included), or in a graph on the variables' home (``GraphModel.define_diagnostic``).  Its rows are formed on request:
+        ``compute_diagnostic`` after ``run()`` (``Ensemble.define_diagnostic``)."""
+        if not weights or len(weights) > L.DIAG_MAX_TERMS:
+            raise ValueError(f"with_diagnostic takes 1 to {L.DIAG_MAX_TERMS} variables, got {len(weights)}")
+        unknown = [v for v in (scales or {}) if v not in weights]
+        if unknown:
+            raise ValueError(f"scales given for unknown variable(s) {unknown}; variables: {list(weights)}")
+        if any(name == n for n, _, _ in self._diagnostics):
+            raise ValueError(f"diagnostic {name!r} is defined already")
+        self._diagnostics.append((str(name), {str(v): (None if p is None else str(p)) for v, p in weights.items()},
+                                  {str(v): float((scales or {}).get(v, 1.0)) for v in weights}))
+        return self
+
+    def _define_diagnostics(self, model):
+        """What ``build()`` does with ``with_diagnostic``: on the ensemble of a ``Model`` or the homes of a ``GraphModel``."""
+        for name, weights, scales in self._diagnostics:
+            if isinstance(model, GraphModel):
+                model.define_diagnostic(name, [(v, p, scales[v]) for v, p in weights.items()])
+                continue
+            terms = []
+            for v, p in weights.items():
+                if p is not None and p not in model.param_order:
+                    raise ValueError(f"diagnostic {name!r}: {p!r} is no parameter of this model; parameters: {list(model.param_order)}")
+                terms.append((v, None if p is None else model.param_order.index(p), scales[v]))
+            if any(v not in model.ensemble.var_ids for v, _, _ in terms):
+                raise ValueError(f"diagnostic {name!r}: variables {[v for v, _, _ in terms]}; this model has {sorted(model.ensemble.var_ids)}")
+            model.ensemble.define_diagnostic(name, terms)
+        return model
 
     def with_forcing_noise(self, sigma: float, seed: int, phi: float = 0.0) -> "ModelBuilder":
         """Extension: internal variability.  Where ``build()`` returns the single two-layer ensemble (one ``TwoLayer`` reading
@@ -644,7 +679,7 @@ class ModelBuilder:
         self._set_noise(ens)
         model = Model(ens, self._axis, sources, endogenous, plan["block"], dict(self._initial), plan["param_order"], plan["base_params"])
         model._builder = self
-        return model
+        return self._define_diagnostics(model)
 
     def with_exogenous_collection(self, collection: TimeseriesCollection) -> "ModelBuilder":
         for name in collection.names():
@@ -1189,10 +1224,10 @@ class ModelBuilder:
         if series_window is not None:
             if any(getattr(c, "is_python", False) for c in self._components):
                 raise NotImplementedError("Python components read whole host series: no series_window for such graphs")
-            return self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order,
-                                     series_window, output_stride, outputs)
+            return self._define_diagnostics(self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order,
+                                                              series_window, output_stride, outputs))
         if any(getattr(c, "is_python", False) for c in self._components):
-            return self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order)
+            return self._define_diagnostics(self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order))
         types = [c.type_name for c in self._components]
         erf = "Effective Radiative Forcing"
         if types == ["TwoLayer"] and not aggregates:
@@ -1238,7 +1273,7 @@ class ModelBuilder:
             h = {}
         else:
             # any other graph of built-in components: one ensemble per component, linked on the device
-            return self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order)
+            return self._define_diagnostics(self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order))
         if not store_series and kind != L.KIND_TWO_LAYER:
             store_series = True  # likelihood-only handles exist for the two-layer kind
         noise_params = self._noise is not None and self._noise_params   # (_check_forcing_noise: this is the two-layer ensemble)
@@ -1270,7 +1305,7 @@ class ModelBuilder:
         model = Model(ens, self._axis, sources, endogenous, forcing, dict(self._initial), param_order,
                       np.array(params, dtype=np.float64))
         model._builder = self
-        return model
+        return self._define_diagnostics(model)
 
 
 def save_checkpoint(path, ck: Dict[str, object]) -> None:
@@ -1384,6 +1419,7 @@ class GraphModel:
         self._order = order
         self.ensembles = ensembles
         self._var_home = var_home          # variable name -> (owner, variable id)
+        self._diagnostics: Dict[str, Tuple[str, int]] = {}   # diagnostic name -> (owner, id): define_diagnostic
         self._links = links                # (consumer, row) pairs, for teardown
         self._exogenous = exogenous
         self._sources = sources
@@ -1463,10 +1499,55 @@ class GraphModel:
 
     def variable_home(self, name: str) -> Tuple[Ensemble, int]:
         """The ensemble and variable id that hold the scalar series of ``name``."""
+        if name in self._diagnostics:
+            owner, vid = self._diagnostics[name]
+            return self.ensembles[owner], vid
         if name not in self._var_home:
             raise KeyError(f"Model output missing variable: {name}")
         owner, vid = self._var_home[name]
         return self.ensembles[owner], vid
+
+    def define_diagnostic(self, name: str, terms) -> int:
+        """``Ensemble.define_diagnostic`` on the home ensemble the terms' variables share: ``terms`` is a sequence of
+        ``(variable name, parameter or None[, scale])``, the parameter a row of that ensemble or a name of ``param_home``
+        (``"Type.name"``, or the bare name where it is unique) that lives there.  ``variable_home(name)`` then resolves the
+        diagnostic, so ``quantile_rows``, ``indicators``, ``variability``, ``spectrum``, ``set_baseline`` and ``get_series`` take it
+        by name.  Variables of two ensembles: ``ValueError`` (a diagnostic does not cross handles)."""
+        if name in self._diagnostics or name in self._var_home:
+            raise ValueError(f"variable name {name!r} is taken")
+        terms = [tuple(t) for t in terms]
+        if not terms:
+            raise ValueError("a diagnostic needs at least one term")
+        for t in terms:
+            if t[0] in self._diagnostics:
+                raise ValueError(f"term {t!r}: a diagnostic combines stored variables, not diagnostics")
+            if t[0] not in self._var_home:
+                raise KeyError(f"Model output missing variable: {t[0]}")
+        homes = [self._var_home[t[0]] for t in terms]
+        owners = sorted({o for o, _ in homes})
+        if len(owners) != 1:
+            raise ValueError(f"diagnostic {name!r}: its variables live in the ensembles {owners}; all terms must share one home")
+        resolved = []
+        for t, (_, vid) in zip(terms, homes):
+            row = t[1]
+            if isinstance(row, str):
+                if row not in self.param_home or self.param_home[row][0] != owners[0]:
+                    raise ValueError(f"diagnostic {name!r}: parameter {row!r} is no parameter of {owners[0]!r}, the variables' home")
+                row = self.param_home[row][1]
+            resolved.append((vid, row) + tuple(t[2:3]))
+        vid = self.ensembles[owners[0]].define_diagnostic(name, resolved)
+        self._diagnostics[name] = (owners[0], vid)
+        return vid
+
+    def compute_diagnostic(self, name: str, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
+        """``Ensemble.compute_diagnostic`` of ``name`` on its home ensemble (``t_end=None``: up to and including the model's
+        current step)."""
+        if name not in self._diagnostics:
+            raise KeyError(f"no diagnostic named {name!r}")
+        for ens in self.ensembles.values():
+            ens.sync()
+        ens, vid = self.variable_home(name)
+        ens.compute_diagnostic(vid, t_begin, self.time_index + 1 if t_end is None else t_end, t_stride)
 
     def get_series(self, name: str, **kw) -> np.ndarray:
         ens, vid = self.variable_home(name)
@@ -1792,7 +1873,7 @@ class Model:
             unit = "K" if self.ensemble.kind == L.KIND_UDEB else "W/m^2"
             coll.add_fourbox_timeseries(fourbox[0], FourBoxTimeseries(boxes, self._axis, unit))
         for name, vid in self.ensemble.var_ids.items():
-            if vid in fb_ids:
+            if vid in fb_ids or vid >= self.ensemble.n_vars:   # (a diagnostic is no series of the collection: its rows are computed on request)
                 continue
             if vid == 0 and self.ensemble.input_rows:
                 for k, input_row in enumerate(self.ensemble.input_rows):  # the input block's series

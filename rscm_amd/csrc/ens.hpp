@@ -135,8 +135,43 @@ struct rscm_ens {
     bool noise_cache_kept() const { return !(noise_kind == rscm::kNoiseKindMembers && params_exposed); }
     void params_written()
     {
+        params_may_change();
+        rows_written();
+    }
+    // ... and what rscm_ens_params_devptr does for the writes it makes possible: those are the caller's to follow (no epoch moves)
+    void params_may_change()
+    {
         derived_dirty = true;
         if (noise_kind == rscm::kNoiseKindMembers) noise_state_index = -1;
+    }
+    // Diagnostic variables (diagnostic_host.cpp; kernel in diagnostic.hip): per-member linear combinations of the stored variables with
+    // ids V, V + 1, ..., their rows [held][N] for t_begin, t_begin + t_stride, ... in a store of their own.  The rows are a snapshot:
+    // write_epoch moves with everything that can change a stored row, a parameter row or the time index (rows_written(): step_finish
+    // for every run, params_written(), launch_loglik for the fused runs, set_noise, and the entry points that move the time index or
+    // write a state), and a store serves its rows only at the epoch it was computed at.
+    struct Diagnostic {
+        int32_t n_terms = 0;
+        int32_t var[RSCM_DIAG_MAX_TERMS] = {}, row[RSCM_DIAG_MAX_TERMS] = {};
+        double scale[RSCM_DIAG_MAX_TERMS] = {};
+        double* d_rows = nullptr;   // [capacity / N][N]
+        size_t capacity = 0;        // in doubles
+        int32_t held = 0, t_begin = 0, t_stride = 1;
+        uint64_t epoch = 0;
+    };
+    Diagnostic diag[RSCM_DIAG_MAX];
+    int32_t n_diag = 0;
+    uint64_t write_epoch = 1;
+    void rows_written() { ++write_epoch; }
+    bool is_diagnostic(int32_t var) const { return var >= V && var < V + n_diag; }
+    bool has_rows(int32_t var) const { return var >= 1 && var < V + n_diag; }   // a stored variable or a diagnostic
+    bool diagnostic_stale(int32_t var) const { return diag[var - V].held > 0 && diag[var - V].epoch != write_epoch; }
+    const double* diagnostic_row(int32_t var, int32_t t) const
+    {
+        if (!is_diagnostic(var)) return nullptr;
+        const Diagnostic& d = diag[var - V];
+        if (d.epoch != write_epoch || t < d.t_begin || (t - d.t_begin) % d.t_stride != 0) return nullptr;
+        const int32_t r = (t - d.t_begin) / d.t_stride;
+        return r < d.held ? d.d_rows + (size_t)r * N : nullptr;
     }
     double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;
@@ -255,9 +290,10 @@ struct rscm_ens {
     }
     // Device address of row t of a stored variable where it is resident: the output store (every
     // out_stride-th row of the output variables, up to the current index), else the window; nullptr
-    // if the row is not held any more.
+    // if the row is not held any more.  Of a diagnostic: its own store, where it holds the row and is not stale.
     const double* row_ptr(int32_t var, int32_t t) const
     {
+        if (var >= V) return diagnostic_row(var, t);   // (before the window: out_slot has no entry for a diagnostic)
         if (!windowed) return (rows == T || t == 0) ? series(var) + (size_t)t * N : nullptr;
         if (t >= win0 && t < win0 + rows) return series(var) + (size_t)t * N;  // the window is the live copy
         if (out_stride > 0 && out_slot[var] >= 0 && t % out_stride == 0 && t <= time_index)
@@ -346,8 +382,17 @@ void select_release(rscm_ens* h);
 // lies on the axis (empty ranges refused with at_least_one); a handle that stores only its initial row serves no range past it.
 int check_row_range(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, bool at_least_one);
 int check_series_stored(const rscm_ens* h, int32_t t_end);
+// RSCM_OK for a stored variable and for a diagnostic whose rows are current; RSCM_ERR_STATE "diagnostic N is stale: compute it again"
+// (diagnostic_host.cpp).  What every reader of a diagnostic's rows asks before it resolves them.
+int check_diagnostic_current(const rscm_ens* h, int32_t var_id);
+// frees the diagnostics' stores and forgets the definitions (rscm_ens_destroy; the stream has been synchronised)
+void diagnostics_release(rscm_ens* h);
 int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                  int32_t* n_range);
+// resolve_rows with its checks for a range every row of which must be computed (RSCM_ERR_STATE else), and the rows' times
+// (indicators_host.cpp): what the per-member statistics and the diagnostics' sources go through
+int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
+                std::vector<double>& times);
 // RSCM_OK if p is device memory on h's device holding at least N doubles from p on, else RSCM_ERR_INVALID (select_host.cpp)
 int check_member_vector(const rscm_ens* h, const double* p, const char* what);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (rscm_gpu.cpp)

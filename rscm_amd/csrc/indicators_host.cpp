@@ -15,8 +15,6 @@
 
 #include "ens.hpp"
 
-namespace {
-
 // The device row pointers and row times of the computed rows t_begin, t_begin + t_stride, ... < t_end of var_id; every row of the
 // range must be computed and resident
 int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
@@ -31,6 +29,8 @@ int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int
     for (int32_t t = t_begin; t < t_end; t += t_stride) times.push_back(h->bounds[t]);
     return RSCM_OK;
 }
+
+namespace {
 
 // The device array of the row pointers, enqueued on the handle's stream: rows must live until the caller has synchronised it
 int upload_rows(rscm_ens* h, const std::vector<const double*>& rows, rscm::DevBuf<const double*>& d_rows)

@@ -662,6 +662,7 @@ int step_finish(rscm_ens* h, int32_t step_begin, int32_t step_end)
 {
     const int32_t keep = h->keep_rows();
     h->time_index = step_end;
+    h->rows_written();
     if (h->windowed && step_end > step_begin) {
         if (h->n_out > 0)
             for (int32_t t = step_begin + 1; t <= step_end; ++t)

@@ -32,7 +32,11 @@ int resolve_loglik_rows(rscm_ens* const* handles, int32_t n_handles, bool whole_
     for (int32_t j = 0; j < o.n; ++j) {
         if (o.owner && (o.owner[j] < 0 || o.owner[j] >= n_handles)) return fail(RSCM_ERR_INVALID, "observation %d: owner %d out of range", j, o.owner[j]);
         const rscm_ens* h = handles[obs_owner(j)];
-        if (o.var[j] < 1 || o.var[j] >= h->V) return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, o.var[j]);
+        // (a handle's own likelihood reads a diagnostic's rows like any others; the samplers' evaluators are run afresh for every score)
+        if (!(whole_series ? o.var[j] >= 1 && o.var[j] < h->V : h->has_rows(o.var[j])))
+            return fail(RSCM_ERR_INVALID, "observation %d: variable %d has no stored series", j, o.var[j]);
+        if (!whole_series)
+            if (int rc = check_diagnostic_current(h, o.var[j])) return rc;
         if (o.tidx[j] < 0 || o.tidx[j] >= h->T) return fail(RSCM_ERR_INVALID, "observation %d: time index %d out of range", j, o.tidx[j]);
         if (!whole_series && o.tidx[j] > h->time_index) out->uncomputed = true;  // NaN there -> skipped by extract_outputs -> missing time -> Err
         out->last_row = std::max(out->last_row, o.tidx[j]);
@@ -334,6 +338,7 @@ hipError_t launch_loglik(rscm_ens* h)
     a.obs_tidx = (const int32_t*)(a.obs_sigma + h->obs_n);
     a.obs_is_deep = a.obs_tidx + h->obs_n;
     a.loglik = h->d_loglik;
+    h->rows_written();   // the fused run rewrites the stored rows (and a sampler's proposals the parameter block before it)
     if (h->ref_active) return rscm::launch_two_layer_loglik_ref(a, h->ref, h->mode, h->stream);
     return rscm::launch_two_layer_loglik(a, h->mode, h->stream);
 }

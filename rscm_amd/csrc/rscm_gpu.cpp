@@ -808,6 +808,7 @@ int rscm_ens_destroy(rscm_ens* h)
     (void)hipFree(h->d_base);
     (void)hipFree(h->d_groups);
     for (double* p : h->d_ind) (void)hipFree(p);
+    diagnostics_release(h);
     if (h->plan) {
         (void)hipFree(h->plan->d_ops);
         if (h->plan->staging) (void)hipHostFree(h->plan->staging);
@@ -827,6 +828,7 @@ int rscm_ens_destroy(rscm_ens* h)
 
 int rscm_ens_n_params(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->P; return RSCM_OK; }
 int rscm_ens_n_vars(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->V; return RSCM_OK; }
+int rscm_ens_n_diagnostics(const rscm_ens* h, int32_t* out) { NEED(h); if (!out) return fail(RSCM_ERR_INVALID, "out is NULL"); *out = h->n_diag; return RSCM_OK; }
 int rscm_ens_n_inputs(const rscm_ens* h, int32_t* out) { NEED(h); *out = h->n_inputs; return RSCM_OK; }
 int rscm_ens_n_forcing_components(const rscm_ens* h, int32_t* out) { NEED(h); if (!out) return fail(RSCM_ERR_INVALID, "out is NULL"); *out = h->n_comp; return RSCM_OK; }
 int rscm_ens_n_members(const rscm_ens* h, int64_t* out) { NEED(h); *out = h->N; return RSCM_OK; }
@@ -841,6 +843,7 @@ int rscm_ens_set_mode(rscm_ens* h, int32_t mode)
         h->ocean_forget_partial_sums();
     }
     h->mode = mode;
+    h->rows_written();   // the next run writes other bits
     return RSCM_OK;
 }
 
@@ -1102,6 +1105,7 @@ int rscm_ens_set_initial(rscm_ens* h, int32_t var_id, const double* values, int6
     HIPCHK(hipStreamSynchronize(h->stream));
     h->initial_set[var_id] = 1;
     h->time_index = 0;
+    h->rows_written();
     return RSCM_OK;
     GUARD_END
 }
@@ -1125,6 +1129,7 @@ int rscm_ens_set_state(rscm_ens* h, int32_t var_id, int32_t tidx, const double* 
         HIPCHK(hipMemcpyAsync(row, values, (size_t)h->N * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (tidx == 0) h->initial_set[var_id] = 1;
+    h->rows_written();
     return RSCM_OK;
     GUARD_END
 }
@@ -1145,6 +1150,7 @@ int rscm_ens_set_time_index(rscm_ens* h, int32_t tidx)
         if (int rc = window_seek(h, tidx)) return rc;
     }
     h->time_index = tidx;
+    h->rows_written();
     h->ocean_forget_partial_sums();
     return RSCM_OK;
     GUARD_END
@@ -1223,6 +1229,7 @@ int rscm_ens_set_internal_state(rscm_ens* h, const double* in, int64_t n_doubles
     if (h->windowed && time_index != h->time_index)
         if (int rc = window_seek(h, time_index)) return rc;
     h->time_index = time_index;
+    h->rows_written();
     h->ocean_forget_partial_sums();
     return RSCM_OK;
     GUARD_END
@@ -1419,6 +1426,7 @@ int rscm_ens_rewind(rscm_ens* h)
         if (int rc = window_reset(h, false)) return rc;
     }
     h->time_index = 0;
+    h->rows_written();
     h->ocean_forget_partial_sums();
     return RSCM_OK;
     GUARD_END
@@ -1438,6 +1446,7 @@ int rscm_ens_clear_series(rscm_ens* h)
             HIPCHK(rscm::launch_fill(h->series(v) + h->N, (int64_t)(h->rows - 1) * h->N,
                                      std::numeric_limits<double>::quiet_NaN(), h->stream));
     h->time_index = 0;
+    h->rows_written();
     h->ocean_forget_partial_sums();
     return RSCM_OK;
     GUARD_END
@@ -1456,6 +1465,7 @@ int rscm_ens_clear_rows_after(rscm_ens* h, int32_t tidx)
         for (int32_t v = 1; v < h->V; ++v)
             HIPCHK(rscm::launch_fill(h->series(v) + (size_t)(tidx + 1) * h->N, (int64_t)(h->T - 1 - tidx) * h->N,
                                      std::numeric_limits<double>::quiet_NaN(), h->stream));
+    h->rows_written();
     return RSCM_OK;
     GUARD_END
 }
@@ -1509,17 +1519,19 @@ int rscm_ens_get_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_
 {
     GUARD_BEGIN
     NEED(h);
-    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
+    if (!h->has_rows(var_id)) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
     if (t_begin < 0 || t_end > h->T || t_begin > t_end || t_stride < 1)
         return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d", t_begin, t_end, t_stride);
     if (!h->windowed && h->rows != h->T && t_end > 1)
         return fail(RSCM_ERR_STATE, "this handle stores only the initial row (RSCM_FLAG_NO_SERIES)");
     if (m_begin < 0 || m_end > h->N || m_begin > m_end || !out)
         return fail(RSCM_ERR_INVALID, "bad member range [%lld, %lld)", (long long)m_begin, (long long)m_end);
+    const bool diagnostic = h->is_diagnostic(var_id);
+    if (int rc = check_diagnostic_current(h, var_id)) return rc;
     const int64_t width = m_end - m_begin;
     if (width == 0 || t_begin == t_end) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
-    if (h->windowed) {  // row by row from wherever each row is resident: the output store or the window
+    if (h->windowed || diagnostic) {  // row by row from wherever each row is resident: the output store or the window; a diagnostic's store
         int64_t r = 0;
         for (int32_t t = t_begin; t < t_end; t += t_stride, ++r) {
             double* dst = out + r * width;
@@ -1528,6 +1540,10 @@ int rscm_ens_get_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_
                 continue;
             }
             const double* src = h->row_ptr(var_id, t);
+            if (!src && diagnostic) {
+                (void)hipStreamSynchronize(h->stream);   // the copies enqueued so far read the caller's buffer no longer
+                return fail(RSCM_ERR_STATE, "row %d of diagnostic %d is not held: rscm_ens_compute_diagnostic over a range with it first", t, var_id);
+            }
             if (!src)
                 return fail(RSCM_ERR_STATE, "row %d of variable %d is not resident: the window holds [%d, %d) and the output store every %d-th row%s",
                             t, var_id, h->win0, h->win0 + h->rows, h->out_stride, h->out_slot[var_id] < 0 ? " of other variables" : "");
@@ -1572,7 +1588,7 @@ int rscm_ens_params_devptr(rscm_ens* h, void** out)
     // handle is ever treated as uniform again (rscm_ens_set_params keeps the flag clear as well).
     h->params_exposed = true;
     h->uniform_rows = 0;
-    h->params_written();   // (and noise_cache_kept() is false from here on)
+    h->params_may_change();   // (and noise_cache_kept() is false from here on; the diagnostics' epoch does not move: rscm_gpu.h)
     h->params_set = true;  // the caller fills it on the device
     return RSCM_OK;
 }
@@ -1688,8 +1704,9 @@ int rscm_ens_summary(rscm_ens* h, int32_t var_id, int32_t tidx, double out[4])
 {
     GUARD_BEGIN
     NEED(h);
-    if (var_id < 1 || var_id >= h->V || tidx < 0 || tidx >= h->T || !out)
+    if (!h->has_rows(var_id) || tidx < 0 || tidx >= h->T || !out)
         return fail(RSCM_ERR_INVALID, "bad variable/time index");
+    if (int rc = check_diagnostic_current(h, var_id)) return rc;
     if (tidx > h->time_index) {
         out[0] = 0.0; out[1] = 0.0;
         out[2] = std::numeric_limits<double>::infinity();
@@ -1841,6 +1858,7 @@ static int set_noise(rscm_ens* h, int32_t kind, uint64_t seed, double sigma, dou
     h->noise_phi = phi;
     h->noise_offset = member_offset;
     h->noise_state_index = -1;   // the cache belonged to the setting before
+    h->rows_written();           // and so did every row a run has written
     return RSCM_OK;
     GUARD_END
 }

@@ -234,10 +234,10 @@ int quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, i
 
 int check_row_range(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, bool at_least_one)
 {
-    if (var_id < 1 || var_id >= h->V) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
+    if (!h->has_rows(var_id)) return fail(RSCM_ERR_INVALID, "variable %d has no stored series", var_id);
     if (t_begin < 0 || t_end > h->T || t_begin > t_end || (at_least_one && t_begin == t_end) || t_stride < 1)
         return fail(RSCM_ERR_INVALID, "bad time range [%d, %d) stride %d%s", t_begin, t_end, t_stride, at_least_one ? " (at least one row)" : "");
-    return RSCM_OK;
+    return check_diagnostic_current(h, var_id);
 }
 
 int check_series_stored(const rscm_ens* h, int32_t t_end)
@@ -255,6 +255,11 @@ int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_e
         ++*n_range;
         if (t > h->time_index) continue;   // never computed by this model instance
         const double* p = h->row_ptr(var_id, t);
+        if (!p && h->is_diagnostic(var_id)) {
+            const rscm_ens::Diagnostic& d = h->diag[var_id - h->V];
+            return fail(RSCM_ERR_STATE, "row %d of diagnostic %d is not held: it holds %d rows from %d with stride %d", t, var_id, d.held, d.t_begin,
+                        d.t_stride);
+        }
         if (!p)
             return fail(RSCM_ERR_STATE, "row %d of variable %d is not resident: the window holds [%d, %d) and the output store every %d-th row%s",
                         t, var_id, h->win0, h->win0 + h->rows, h->out_stride,

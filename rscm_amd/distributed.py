@@ -326,6 +326,15 @@ class ShardedEnsemble:
     def summary_global(self, var, tidx: int) -> Dict[str, float]:
         return reduce_summary(self.ensemble.summary(var, tidx))
 
+    def define_diagnostic(self, name: str, terms) -> int:
+        """``Ensemble.define_diagnostic`` on this rank's block.  The combination is per member, so the shards' rows are the
+        whole ensemble's and no collective is needed; ``quantile_rows_global`` and ``constrain`` then take the name."""
+        return self.ensemble.define_diagnostic(name, terms)
+
+    def compute_diagnostic(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
+        """``Ensemble.compute_diagnostic`` on this rank's block; every rank calls it with the same range."""
+        self.ensemble.compute_diagnostic(var, t_begin, t_end, t_stride)
+
     def quantile_rows_global(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
                              weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Quantiles of the global ensemble at the rows ``t_begin, t_begin + t_stride, ... < t_end`` (``quantile_rows_global``);

@@ -89,6 +89,8 @@ class Ensemble:
             self.n_params += 2   # sigma_i and phi_i follow the six parameters and the coefficients
         flag = L.FLAG_NOISE_PARAMS if self.noise_params else 0
         self.var_ids: Dict[str, int] = dict(var_ids)
+        self.n_vars = max(self.var_ids.values()) + 1   # the stored variables and the input; diagnostics get the ids from here on
+        self._diagnostic_names: Dict[str, int] = {}    # the names define_diagnostic added to var_ids
         self.input_rows = input_rows  # names of the rows of the input block, or None
         self.n_inputs = len(input_rows) if input_rows else 1
         h = C.c_void_p()
@@ -391,7 +393,7 @@ class Ensemble:
         ClimateUDEB / OceanCarbon.  The reference's checkpoint holds time_index, the whole collection
         and the component states (crates/rscm-core/src/model/runtime.rs:270-282)."""
         k = self.time_index
-        names = {n: v for n, v in self.var_ids.items() if v > 0} if all_variables else self.state_vars()
+        names = {n: v for n, v in self.var_ids.items() if 0 < v < self.n_vars} if all_variables else self.state_vars()   # (no diagnostics)
         depth = min(self._history_depth(), k)
         history = {name: self.get_series(v, k - depth, k) for name, v in self.state_vars().items()} if depth else {}
         n = C.c_int64()
@@ -713,6 +715,76 @@ class Ensemble:
                                                           C.byref(p)))
         return DeviceVector(p.value, self.n_members, np.float64, self)
 
+    # -- diagnostic variables ------------------------------------------------------------------
+    def define_diagnostic(self, name: str, terms) -> int:
+        """A diagnostic variable ``name``: a per-member linear combination of this ensemble's stored variables that every method
+        taking ``var`` then takes by name or id (``quantile_rows``, ``set_baseline``, ``indicators``, ``variability``,
+        ``spectrum``, ``loglik``, ``summary``, ``get_series``) once ``compute_diagnostic`` has formed its rows.  ``terms``: a
+        sequence of ``(var, param_row_or_None[, scale=1.0])``; member i's value in a row is ``w_0 x_0 + w_1 x_1 + ...`` summed left
+        to right, ``x_k`` that row of ``var`` and ``w_k = scale * params[param_row][i]`` (``scale`` alone with ``None``), every
+        product and sum rounded on its own (rscm_ens_define_diagnostic; at most 4 terms, 4 diagnostics).  Returns the new id."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("a diagnostic needs a name")
+        if name in self.var_ids:
+            raise ValueError(f"variable name {name!r} is taken")
+        tv, tr, ts = [], [], []
+        for term in terms:
+            term = tuple(term)
+            if len(term) not in (2, 3):
+                raise ValueError(f"term {term!r}: (var, param_row_or_None[, scale]) expected")
+            if isinstance(term[0], str) and term[0] in self._diagnostic_names:
+                raise ValueError(f"term {term!r}: a diagnostic combines stored variables, not diagnostics")
+            tv.append(self._var(term[0]))
+            tr.append(-1 if term[1] is None else int(term[1]))
+            ts.append(float(term[2]) if len(term) == 3 else 1.0)
+        tv, tr = (np.ascontiguousarray(x, dtype=np.int32) for x in (tv, tr))
+        ts = L.f64(ts)
+        vid = C.c_int32()
+        L.check(self._lib.rscm_ens_define_diagnostic(self._h, len(tv), L.iptr(tv), L.iptr(tr), L.dptr(ts), C.byref(vid)))
+        self.var_ids[name] = vid.value
+        self._diagnostic_names[name] = vid.value
+        return vid.value
+
+    def define_heat_content(self, name: str = "Ocean Heat Content", scale: float = 1.0) -> int:
+        """The ocean heat content of a two-layer ensemble (plain, mix or with noise rows alike) as a diagnostic:
+        ``H = (scale * C) Ts + (scale * Cd) Td`` with the member's own heat capacities, parameter rows 4 and 5 -- in W yr m^-2
+        at ``scale`` 1.  Over the Earth's surface (5.101e14 m^2, 3.156e7 s per year) 1 W yr m^-2 is 1.610e22 J: ``scale=16.10``
+        gives ZJ.  The reference integrates this quantity and drops it; its first differences (``detrend="difference"``) are the
+        year-to-year uptake."""
+        if self.kind != L.KIND_TWO_LAYER:
+            raise ValueError("define_heat_content: the two-layer kind only (its rows 4 and 5 are the heat capacities)")
+        return self.define_diagnostic(name, [("Surface Temperature", 4, scale), ("Deep Ocean Temperature", 5, scale)])
+
+    def compute_diagnostic(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
+        """Form the rows ``t_begin, t_begin + t_stride, ... < t_end`` of diagnostic ``var`` from the stored rows and the parameters
+        as they stand (``t_end=None``: up to and including the current time index).  They are a snapshot: after anything that
+        writes rows or parameters (``run``, ``rewind``, ``set_params``, ``restore``, being a ``branch`` destination, ...) readers
+        are refused until the next ``compute_diagnostic`` (rscm_ens_compute_diagnostic).  One range at a time."""
+        t_end = self.time_index + 1 if t_end is None else int(t_end)
+        L.check(self._lib.rscm_ens_compute_diagnostic(self._h, self._var(var), int(t_begin), t_end, int(t_stride)))
+
+    @property
+    def diagnostics(self) -> Dict[str, Dict[str, object]]:
+        """The definitions as the library holds them, by name: ``{"id", "terms": [(var id, param row or None, scale)],
+        "rows_held", "t_begin", "t_stride"}`` (``rows_held`` 0 when nothing is computed or the rows are stale)."""
+        out = {}
+        for name, vid in self._diagnostic_names.items():
+            n, held, tb, st = (C.c_int32() for _ in range(4))
+            tv, tr = np.zeros(L.DIAG_MAX_TERMS, dtype=np.int32), np.zeros(L.DIAG_MAX_TERMS, dtype=np.int32)
+            ts = np.zeros(L.DIAG_MAX_TERMS)
+            L.check(self._lib.rscm_ens_diagnostic(self._h, vid, C.byref(n), L.iptr(tv), L.iptr(tr), L.dptr(ts), C.byref(held), C.byref(tb),
+                                                  C.byref(st)))
+            out[name] = {"id": vid, "terms": [(int(tv[k]), None if tr[k] < 0 else int(tr[k]), float(ts[k])) for k in range(n.value)],
+                         "rows_held": held.value, "t_begin": tb.value, "t_stride": st.value}
+        return out
+
+    def clear_diagnostics(self) -> None:
+        """Remove every diagnostic: definitions, rows and names."""
+        L.check(self._lib.rscm_ens_clear_diagnostics(self._h))
+        for name in self._diagnostic_names:
+            del self.var_ids[name]
+        self._diagnostic_names = {}
+
     def _vectors(self, vectors):
         vs = list(vectors)
         for v in vs:
@@ -943,6 +1015,9 @@ class Ensemble:
         dst = factory(n_draws * scenarios)
         for sidx in range(scenarios):
             self.branch(dst, anc, sidx * n_draws)
+        for name, d in self.diagnostics.items():   # the projection can be summarised the way the source is (rows: dst's to compute)
+            if name not in dst.var_ids:
+                dst.define_diagnostic(name, d["terms"])
         scenario_of_member = np.repeat(np.arange(scenarios, dtype=np.int32), n_draws)
         if scenarios <= 64:   # more scenarios than the library has groups: the blocks stay ungrouped
             dst.set_member_groups(scenario_of_member, scenarios)

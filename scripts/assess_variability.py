@@ -26,7 +26,13 @@ periodogram, ``rscm_amd.variability.series_spectrum(record, "difference")`` agai
 ``loglik_spectrum`` -- alone ("spectrum") and with the (sd, r1) likelihood added onto it ("spectrum_and_statistics").  One lag cannot
 tell strong short-lived noise from weak persistent noise once the ocean has filtered it; the spectrum's shape can.
 
-    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum]
+With ``--heat-content`` the record is the truth member's ocean heat content as well as its temperature:
+``H = C Ts + Cd Td`` as a diagnostic variable of the ensemble (``define_heat_content``, ``compute_diagnostic``), whose first
+differences are the year-to-year heat uptake.  Their (sd, r1) -- and with ``--spectrum`` their band powers -- are scored like the
+temperature's and added onto the temperature's likelihoods; the effective sample size and the 5-50-95 % ranges of sigma, phi,
+lambda0 and the two heat capacities are printed for temperature alone and for temperature plus heat content.
+
+    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content]
 
 Prints one JSON line; exit code 0 iff every comparison holds."""
 import argparse
@@ -79,6 +85,7 @@ def main():
     ap.add_argument("--draws", type=int, default=20_000)
     ap.add_argument("--fast", action="store_true")
     ap.add_argument("--spectrum", action="store_true", help="also weight by the record's band powers (loglik_spectrum)")
+    ap.add_argument("--heat-content", action="store_true", help="also weight by the variability of the record's ocean heat content")
     a = ap.parse_args()
     mode = rscm_amd.MODE_FAST if a.fast else rscm_amd.MODE_EXACT
 
@@ -89,6 +96,7 @@ def main():
         rows = np.arange(5, NOW + 1, 5)
         annual = truth.get_series(TS, 0, NOW + 1)[:, 0]
         record = annual[rows]
+        annual_heat = TRUTH[4] * annual + TRUTH[5] * truth.get_series("Deep Ocean Temperature", 0, NOW + 1)[:, 0]
 
     with make(a.members, mode, seed=1) as ens:
         sigma_row, phi_row = ens.noise_param_rows
@@ -148,6 +156,44 @@ def main():
                 [constraint["spectrum_and_statistics"]["sigma"], constraint["spectrum_and_statistics"]["phi"]],
                 np.stack([np_weighted(P[sigma_row], w), np_weighted(P[phi_row], w)])))
 
+        heat = None
+        if a.heat_content:
+            # temperature alone: the (sd, r1) likelihood, with --spectrum the spectral one added; then the same estimators on the heat
+            # content's differences added onto it (the handle has one likelihood vector: every step continues it in place)
+            q3 = [0.05, 0.5, 0.95]
+            named = {"sigma": sigma_row, "phi": phi_row, "lambda0": 0, "heat_capacity_surface": 4, "heat_capacity_deep": 5}
+            pvec = [ens.params_vector(r) for r in named.values()]
+
+            def weigh(lls):
+                ens.set_weights_from_loglik(lls)
+                q = ens.quantile_vectors(pvec, q3, weighted=True)["quantiles"]
+                return {"ess": ens.weights_stats()["ess"], **{k: q[j].tolist() for j, k in enumerate(named)}}
+
+            hid = ens.define_heat_content()
+            ens.compute_diagnostic(hid, 0, NOW + 1)
+            htarget = series_variability(annual_heat, "difference")
+            hvalues = [htarget["sd"], htarget["r1"]]
+            hsigmas = [np.sqrt(2.0) * htarget["sd"] / np.sqrt(2.0 * n_diff), np.sqrt(2.0) * np.sqrt((1.0 - htarget["r1"] ** 2) / n_diff)]
+            lls = ens.loglik_vectors(stats, values, sigmas)
+            if a.spectrum:
+                lls = ens.loglik_spectrum(spec["power"], rec["power"], rec["counts"], add_to=lls)
+            heat = {"quantiles": q3, "target": {"sd": hvalues[0], "r1": hvalues[1], "sd_sigma": float(hsigmas[0]), "r1_sigma": float(hsigmas[1])},
+                    "prior": {k: q.tolist() for k, q in zip(named, ens.quantile_vectors(pvec, q3)["quantiles"])},
+                    "temperature": weigh(lls)}
+            hvar = ens.variability(hid, 0, NOW + 1, detrend="difference", slot=2)
+            lls = ens.loglik_vectors([hvar["sd"], hvar["r1"]], hvalues, hsigmas, add_to=lls)
+            if a.spectrum:
+                hrec = series_spectrum(annual_heat, "difference")
+                hspec = ens.spectrum(hid, 0, NOW + 1, detrend="difference", bands=hrec["edges"], slot=3)
+                lls = ens.loglik_spectrum(hspec["power"], hrec["power"], hrec["counts"], add_to=lls)
+                heat["spectrum_target"] = {"edges": hrec["edges"].tolist(), "record_power": hrec["power"]}
+            heat["temperature_and_heat_content"] = weigh(lls)
+            w = ens.member_weights()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                want = [np.nanquantile(P[r], q3, weights=w, method="inverted_cdf").tolist() for r in named.values()]
+            checks["heat_content_weighted_quantiles_equal_numpy"] = bool(want == [heat["temperature_and_heat_content"][k] for k in named])
+
     res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
            "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
            "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
@@ -161,6 +207,8 @@ def main():
         res["spectrum_target"] = spectral
         res["constraint"]["spectrum"] = constraint["spectrum"]
         res["constraint"]["spectrum_and_statistics"] = constraint["spectrum_and_statistics"]
+    if heat is not None:
+        res["heat_content"] = heat
     print(json.dumps(res), flush=True)
     sys.exit(0 if all(checks.values()) else 1)
 
