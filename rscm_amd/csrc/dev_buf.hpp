@@ -1,6 +1,6 @@
-// Device allocation of the host layer: dev_malloc, through which every allocation goes, and DevBuf, the scoped owner of a
-// short-lived one.  Depends on the HIP runtime API and the standard library only, so a host compiler can build it against stubs
-// (tests/c_abi/dev_buf_host.cpp).
+// Device allocation of the host layer: dev_malloc, through which every allocation goes, and DevBuf, the one owner of device
+// memory -- a call's temporary and a handle's member alike.  Depends on the HIP runtime API and the standard library only, so a
+// host compiler can build it against stubs (tests/c_abi/dev_buf_host.cpp).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -23,50 +23,51 @@ inline hipError_t dev_malloc(T** p, size_t n)
     return f == hipSuccess ? hipDeviceSynchronize() : f;
 }
 
-// A device temporary of the host layer: n elements of T from dev_malloc, freed when the owner goes out of scope -- HIPCHK, a
-// validation failure or an exception may return past it.  The destructor takes no stream: hipFree waits for the device's
-// outstanding work.  A buffer that outlives the call leaves through release() (to a raw handle member) or install().
+// size() elements of T from dev_malloc, freed when the owner dies: a local goes with its scope -- HIPCHK, a validation failure or
+// an exception may return past it -- and a member of a handle, a sampler or a lock-step plan goes with `delete`.  The destructor
+// takes no stream: hipFree waits for the device's outstanding work.  Reads as a T* wherever one is expected (a kernel argument, a
+// copy, a null test), so only the places that own a buffer name the type.  A buffer moves from a local into a member by
+// move-assignment, which frees what the member held: build aside, and move in once nothing can fail any more.
 template <class T>
 class DevBuf {
 public:
     DevBuf() = default;
-    DevBuf(DevBuf&& o) noexcept : p_(o.release()) {}
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }
     DevBuf& operator=(DevBuf&& o) noexcept
     {
         if (this != &o) {
-            (void)hipFree(p_);
-            p_ = o.release();
+            reset();
+            p_ = o.p_, n_ = o.n_;
+            o.p_ = nullptr, o.n_ = 0;
         }
         return *this;
     }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
-    ~DevBuf() { (void)hipFree(p_); }
+    ~DevBuf() { reset(); }
 
-    // n elements in place of what the owner held; goes inside HIPCHK
+    // n fresh elements in place of what the owner held; goes inside HIPCHK.  Empty after a failure
     hipError_t alloc(size_t n)
     {
+        reset();
+        const hipError_t e = dev_malloc(&p_, n * sizeof(T));
+        if (e == hipSuccess) n_ = n;
+        else p_ = nullptr;
+        return e;
+    }
+    // room for n elements: what the owner holds if that is enough (contents kept), else alloc(n) (contents gone)
+    hipError_t reserve(size_t n) { return n_ >= n ? hipSuccess : alloc(n); }
+    void reset()
+    {
         (void)hipFree(p_);
-        p_ = nullptr;
-        return dev_malloc(&p_, n * sizeof(T));
+        p_ = nullptr, n_ = 0;
     }
+    size_t size() const { return n_; }   // in elements
     T* get() const { return p_; }
-    explicit operator bool() const { return p_ != nullptr; }
-    // the caller owns the pointer from here on
-    T* release()
-    {
-        T* p = p_;
-        p_ = nullptr;
-        return p;
-    }
-    // "free old, keep new": the slot (a handle member) takes the buffer over and what it held is freed
-    void install(T*& slot)
-    {
-        (void)hipFree(slot);
-        slot = release();
-    }
+    operator T*() const { return p_; }
 
 private:
     T* p_ = nullptr;
+    size_t n_ = 0;
 };
 }  // namespace rscm

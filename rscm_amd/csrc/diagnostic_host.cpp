@@ -37,15 +37,6 @@ int check_diagnostic_current(const rscm_ens* h, int32_t var_id)
     return RSCM_OK;
 }
 
-void diagnostics_release(rscm_ens* h)
-{
-    for (rscm_ens::Diagnostic& d : h->diag) {
-        (void)hipFree(d.d_rows);
-        d = rscm_ens::Diagnostic();
-    }
-    h->n_diag = 0;
-}
-
 extern "C" {
 
 int rscm_ens_define_diagnostic(rscm_ens* h, int32_t n_terms, const int32_t* term_var, const int32_t* term_param_row, const double* term_scale,
@@ -120,13 +111,10 @@ int rscm_ens_compute_diagnostic(rscm_ens* h, int32_t var_id, int32_t t_begin, in
     if (reads_params && !h->params_set) return fail(RSCM_ERR_STATE, "parameters not set: a term's weight reads a parameter row");
     if (int rc = set_device(h)) return rc;
     const size_t need = R * (size_t)h->N;
-    if (d.capacity < need) {   // allocated at first use, reused when large enough; nobody reads the old rows (no select in flight)
-        rscm::DevBuf<double> d_new;
-        HIPCHK(d_new.alloc(need));
+    if (d.d_rows.size() < need) {   // allocated at first use, reused when large enough; nobody reads the old rows (no select in flight)
         HIPCHK(hipStreamSynchronize(h->stream));
-        d_new.install(d.d_rows);
-        d.capacity = need;
-        d.held = 0;
+        d.held = 0;   // too large to hold twice: the old rows go first, and a failed allocation leaves a store that serves none
+        HIPCHK(d.d_rows.reserve(need));
     }
     rscm::DevBuf<const double*> d_src;   // lives until the synchronise below
     HIPCHK(d_src.alloc(rows.size()));
@@ -160,7 +148,8 @@ int rscm_ens_clear_diagnostics(rscm_ens* h)
     if (h->n_diag > 0) {
         if (int rc = set_device(h)) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
-        diagnostics_release(h);
+        for (rscm_ens::Diagnostic& d : h->diag) d = rscm_ens::Diagnostic();   // the stores go with their definitions
+        h->n_diag = 0;
     }
     return RSCM_OK;
     GUARD_END

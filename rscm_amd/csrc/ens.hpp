@@ -2,8 +2,9 @@
 // marshalling; launch_host.cpp: one launch range of one handle; lockstep.cpp: the lock-step scheduler of component graphs;
 // loglik_host.cpp: the likelihoods).  Not part of the boundary
 // (include/rscm_gpu.h) and not visible outside the library (-fvisibility=hidden).
-// Device allocation -- rscm::dev_malloc and rscm::DevBuf, the scoped owner every device temporary of the host layer is held
-// by -- lives in dev_buf.hpp, which this header includes.
+// Device allocation -- rscm::dev_malloc and rscm::DevBuf, the owner of every device buffer of the host layer, a call's
+// temporaries and the d_* members of the handle, the sampler and the lock-step plan alike -- lives in dev_buf.hpp, which this
+// header includes.  Nothing here frees device memory by hand: `delete` of a handle is its whole teardown.
 #pragma once
 
 #include "../../include/rscm_gpu.h"
@@ -17,6 +18,7 @@
 #include <cstdio>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <new>
 #include <cstdlib>
 #include <string>
@@ -59,18 +61,45 @@ struct WindowDeferral {
 // table of fused-launch operations (csrc/group.hip) and what it currently holds.
 struct LockstepPlan {
     std::vector<rscm_ens*> handles;
-    rscm::GroupOp* d_ops = nullptr;          // [handles.size()]
+    rscm::DevBuf<rscm::GroupOp> d_ops;       // [handles.size()]
     std::vector<rscm::GroupOp> cached;       // the table's contents (step fields zeroed)
     std::vector<uint8_t> valid;
     rscm::GroupOp* staging = nullptr;        // page-locked ring the uploads are sourced from
     int32_t ring_pos = 0;
     static constexpr int32_t kRing = 128;
+    ~LockstepPlan() { if (staging) (void)hipHostFree(staging); }   // (d_ops makes the plan move-only)
 };
 
 // A staged quantile select in flight on a handle (rscm_ens_select_begin .. _end, rscm_gpu.cpp)
 struct SelectState;
 
-struct rscm_ens {
+// The queue side of a handle: its stream, the timing events and what a two-stream cut run adds.  A base of rscm_ens, so that it
+// is destroyed after every member of the handle -- the order teardown relies on (below).
+struct EnsQueues {
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // whole-axis runs as two member blocks on two streams in chunks of model steps (launch_host.cpp, plan_member_split): the second stream
+    // and the fork / join events, created with the first such run
+    hipStream_t split_stream = nullptr;
+    hipEvent_t split_fork = nullptr, split_join = nullptr;
+    ~EnsQueues()
+    {
+        if (split_stream) (void)hipStreamDestroy(split_stream);
+        if (split_fork) (void)hipEventDestroy(split_fork);
+        if (split_join) (void)hipEventDestroy(split_join);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+        if (own_stream && stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+// Teardown is `delete h` and nothing else, in this order: ~rscm_ens() synchronises the stream and lets go of what is not device
+// memory (the link reference counts, the staged select, the lock-step plan with its page-locked ring); then the members go, every
+// d_* buffer among them (rscm::DevBuf); then the base, EnsQueues, destroys the events and the stream the handle owns.  So no
+// buffer is freed under work in flight, and none outlives its stream.  The caller has made the handle's device current.
+struct rscm_ens : EnsQueues {
+    ~rscm_ens();   // rscm_gpu.cpp
     int32_t kind = 0;
     int64_t N = 0;
     int32_t T = 0;
@@ -82,29 +111,25 @@ struct rscm_ens {
     double h_tl = 0.1, h_cc = 0.1;
     bool schedule_dirty = true;
     std::vector<int32_t> nsub_tl, nsub_cc;
-    int32_t* d_nsub_tl = nullptr;
-    int32_t* d_nsub_cc = nullptr;
+    rscm::DevBuf<int32_t> d_nsub_tl;
+    rscm::DevBuf<int32_t> d_nsub_cc;
     // two-layer kind: what is proved once about the schedule and the forcing table for the uniform year (two_layer_year_facts.hpp).
     // The schedule's part is rebuilt with nsub_tl (refresh_schedule) and not read while schedule_dirty; the table's part is formed by
     // rscm_ens_set_forcing from the caller's array -- the only writer of d_forcing -- and dropped there before the table is touched
     rscm::tl::YearFacts year_facts;
 
-    double* d_params = nullptr;  // [P][N]
+    rscm::DevBuf<double> d_params;  // [P][N]
     int32_t ag_rows_set = 0;     // aggregate kind: 1 + the highest contributor row rscm_ens_set_forcing has ever been given data for
     uint64_t uniform_rows = 0;   // bit j: parameter row j (< 64) holds one value for every member (the kernels then read element 0: param_at)
+    int32_t last_blocks = 1, last_chunks = 1;   // how the last run was cut (rscm_ens_last_run_plan; the second stream: EnsQueues)
     // member constants of the kinds that have them (GhgForcing, TerrestrialCarbon; rscm_device.hpp, launch_*_derive): [kDerivedRows][N],
     // re-formed by ensure_derived() at the next run after anything wrote the parameter block
-    // whole-axis runs as two member blocks on two streams in chunks of model steps (launch_host.cpp, plan_member_split): the second stream
-    // and the fork / join events, created with the first such run
-    int32_t last_blocks = 1, last_chunks = 1;   // how the last run was cut (rscm_ens_last_run_plan)
-    hipStream_t split_stream = nullptr;
-    hipEvent_t split_fork = nullptr, split_join = nullptr;
-    double* d_derived = nullptr;
+    rscm::DevBuf<double> d_derived;
     bool derived_dirty = true;
     bool params_exposed = false; // rscm_ens_params_devptr handed the block out: uniform_rows stays 0 for the life of the handle
     bool derived_hold = false;   // inside one rscm_ens_run_lockstep call: the member constants were formed at its start and serve all its steps
-    double* d_series = nullptr;  // [(V-1)][T][N], variable v at slot v-1
-    double* d_forcing = nullptr; // [S][n_inputs][T]
+    rscm::DevBuf<double> d_series;  // [(V-1)][T][N], variable v at slot v-1
+    rscm::DevBuf<double> d_forcing; // [S][n_inputs][T]
     int32_t n_inputs = 1;        // rows per scenario of the shared input block
     // The forcing-noise setting (set_noise, rscm_gpu.cpp, behind rscm_ens_set_forcing_noise* and rscm_ens_clear_forcing_noise): member i
     // is forced by F + e_t(noise_seed, noise_offset + i) of the kind noise_kind (rscm::kNoiseKind*; TwoLayerArgs, rscm_device.hpp).
@@ -118,7 +143,7 @@ struct rscm_ens {
     double noise_sigma = 0.0;
     double noise_phi = 0.0;
     int64_t noise_offset = 0;
-    double* d_noise_state = nullptr;
+    rscm::DevBuf<double> d_noise_state;
     int32_t noise_state_index = -1;
     int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
     // RSCM_FLAG_NOISE_PARAMS: the handle has the parameter rows noise_sigma_row() and noise_phi_row() -- a fact of its shape, whatever
@@ -153,8 +178,7 @@ struct rscm_ens {
         int32_t n_terms = 0;
         int32_t var[RSCM_DIAG_MAX_TERMS] = {}, row[RSCM_DIAG_MAX_TERMS] = {};
         double scale[RSCM_DIAG_MAX_TERMS] = {};
-        double* d_rows = nullptr;   // [capacity / N][N]
-        size_t capacity = 0;        // in doubles
+        rscm::DevBuf<double> d_rows;   // [size() / N][N]: room for at least `held` rows
         int32_t held = 0, t_begin = 0, t_stride = 1;
         uint64_t epoch = 0;
     };
@@ -173,13 +197,13 @@ struct rscm_ens {
         const int32_t r = (t - d.t_begin) / d.t_stride;
         return r < d.held ? d.d_rows + (size_t)r * N : nullptr;
     }
-    double* d_ghg_tables = nullptr;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
+    rscm::DevBuf<double> d_ghg_tables;  // GhgForcing: [S][kGhgRows][T] derived scenario rows
     int32_t ghg_method = 1;
     // OceanCarbon: flux history (internal state) and the tabulated impulse response
-    double* d_ocean_hist = nullptr;  // [ocean_hist_rows][N]: a ring, pulse j in row j mod ocean_hist_rows
+    rscm::DevBuf<double> d_ocean_hist;  // [ocean_hist_rows][N]: a ring, pulse j in row j mod ocean_hist_rows
     int64_t ocean_hist_rows = 0;     // min((T-1)*12, max_hist + slack): the convolution never looks further back
-    double* d_ocean_irf = nullptr;   // [max(max_hist, 1)]
-    double* d_ocean_partial = nullptr;  // [(tile years - 1) * steps][N] split-tile running sums (one-step launches)
+    rscm::DevBuf<double> d_ocean_irf;   // [max(max_hist, 1)]
+    rscm::DevBuf<double> d_ocean_partial;  // [(tile years - 1) * steps][N] split-tile running sums (one-step launches)
     int32_t ocean_tile_base = -1;       // first step of the split tile d_ocean_partial belongs to, -1: none
     int32_t ocean_tile_years = 0;       // its length (depends on the arithmetic mode it was started in)
     int32_t ocean_steps = 0;
@@ -190,36 +214,33 @@ struct rscm_ens {
     bool ocean_recur_ok = false;
     int32_t ocean_near = 0;
     double ocean_fit_error = 0.0;
-    double* d_ocean_mode_state = nullptr;  // [kOceanModes][N]
-    double* d_ocean_mode_table = nullptr;  // [3][kOceanModes]: d_q, c_q, e_q
+    rscm::DevBuf<double> d_ocean_mode_state;  // [kOceanModes][N]
+    rscm::DevBuf<double> d_ocean_mode_table;  // [3][kOceanModes]: d_q, c_q, e_q
     int32_t ocean_modes_at = -1;           // time index the running sums stand at (-1: re-form them from the history)
-    int32_t* d_scen = nullptr;   // [N] or null
+    rscm::DevBuf<int32_t> d_scen;   // [N] or null
     int32_t n_scen = 0;
     int32_t source = RSCM_SRC_EXOGENOUS;
-    uint8_t* d_status = nullptr;
+    rscm::DevBuf<uint8_t> d_status;
 
     // ClimateUDEB internal state
-    double* d_ocean = nullptr;    // [2][NL][N]
-    int32_t udeb_ocean_layers = 0;   // layers d_ocean has room for
-    double* d_udeb_work = nullptr;   // [NL][N]  the any-layer-count kernel's c' array (udeb_any_body.hpp)
-    double* d_udeb_tables = nullptr; // [NL][6]  its geometry table
-    int32_t udeb_work_layers = 0;
-    double* d_scal = nullptr;     // [kUdebScalars][N]
-    double* d_hist = nullptr;     // [T][N]
-    double* d_tables = nullptr;   // geometry tables
-    double* d_bounds = nullptr;   // [T+1]
-    int32_t* d_win_kfull = nullptr;  // [T]
-    double* d_win_partw = nullptr;   // [T]
+    rscm::DevBuf<double> d_ocean;    // [2][NL][N], room for size() / (2 N) layers
+    rscm::DevBuf<double> d_udeb_work;   // [NL][N]  the any-layer-count kernel's c' array (udeb_any_body.hpp)
+    rscm::DevBuf<double> d_udeb_tables; // [max(NL, kUdebDevTableRows)][6]  its geometry table
+    int32_t udeb_work_layers() const { return (int32_t)(d_udeb_work.size() / (size_t)N); }   // layers d_udeb_work has room for
+    rscm::DevBuf<double> d_scal;     // [kUdebScalars][N]
+    rscm::DevBuf<double> d_hist;     // [T][N]
+    rscm::DevBuf<double> d_bounds;   // [T+1]
+    rscm::DevBuf<int32_t> d_win_kfull;  // [T]
+    rscm::DevBuf<double> d_win_partw;   // [T]
     int32_t udeb_n_layers = 0, udeb_steps = 0, udeb_land_hc = 0, udeb_efficacy = 0;
     bool udeb_ready = false;
     std::vector<double> udeb_tables;
 
-    double* d_partial = nullptr;  // summary scratch
-    double* d_out4 = nullptr;
-    double* d_loglik = nullptr;   // [N]
+    rscm::DevBuf<double> d_partial;  // summary scratch
+    rscm::DevBuf<double> d_out4;
+    rscm::DevBuf<double> d_loglik;   // [N]
     // observations prepared for the fused run+likelihood kernel (prepare_obs)
-    void* d_obs = nullptr;
-    size_t obs_capacity = 0;
+    rscm::DevBuf<unsigned char> d_obs;   // (grows: prepare_obs)
     int32_t obs_n = 0, obs_normalize = 0, obs_first_is_deep = 0;
     int32_t obs_last_tidx = 0;        // the latest time index any prepared observation refers to
     bool loglik_stop_at_last_obs = false;  // fused run+likelihood launches end there (the device sampler: only ln L is used)
@@ -228,14 +249,9 @@ struct rscm_ens {
     bool ref_active = false;
     rscm::TwoLayerRefArgs ref{};
     int32_t ref_last_row = 0;         // the latest reference row of any period
-    int32_t* d_ref_slot = nullptr;    // [obs_n]
-    size_t ref_slot_capacity = 0;
-    double* d_defer = nullptr;        // [n_deferred][N] model values waiting for their variable's b
-    size_t defer_capacity = 0;        // in rows
+    rscm::DevBuf<int32_t> d_ref_slot;    // [obs_n]
+    rscm::DevBuf<double> d_defer;        // [n_deferred][N] model values waiting for their variable's b; room for size() / N rows
 
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     bool timed = false;
 
     // linked inputs (rscm_ens_link_input)
@@ -246,20 +262,19 @@ struct rscm_ens {
     int32_t link_refs = 0;  // links of other ensembles into this one's series
 
     SelectState* select = nullptr;  // rscm_ens_select_begin .. rscm_ens_select_end
-    int64_t* d_weights = nullptr;   // [N] member weights of the weighted select (rscm_ens_set_member_weights)
+    rscm::DevBuf<int64_t> d_weights;   // [N] member weights of the weighted select (rscm_ens_set_member_weights)
     // posterior resampling (resample_host.cpp): the running sum of the weights with its scan scratch, and the ancestors of the last draw
-    int64_t* d_cumw = nullptr;      // [N + scan_scratch_elems(N)], allocated at the first rscm_ens_resample
-    int64_t* d_anc = nullptr;       // [anc_capacity] local member indices (rscm_ens_resample hands this out)
-    int64_t anc_capacity = 0;
+    rscm::DevBuf<int64_t> d_cumw;      // [N + scan_scratch_elems(N)], allocated at the first rscm_ens_resample
+    rscm::DevBuf<int64_t> d_anc;       // [size()] local member indices (rscm_ens_resample hands this out)
     // a destination of rscm_ens_gather_members: the time index its members were gathered at (-1: never a destination) and element 0 of
     // every parameter row of the source that configured it
     int32_t gather_k = -1;
     std::vector<double> gather_p0;
-    int32_t* d_groups = nullptr;    // [N] member groups of the grouped select and exceedance (rscm_ens_set_member_groups), -1: none
+    rscm::DevBuf<int32_t> d_groups;    // [N] member groups of the grouped select and exceedance (rscm_ens_set_member_groups), -1: none
     int32_t n_groups = 0;
-    double* d_base = nullptr;       // [N] baseline of the anomaly select and indicators (rscm_ens_set_baseline)
+    rscm::DevBuf<double> d_base;       // [N] baseline of the anomaly select and indicators (rscm_ens_set_baseline)
     static constexpr int32_t kIndSlots = 4;
-    double* d_ind[kIndSlots] = {};  // [3 + kMaxThresholds][N] per slot of rscm_ens_member_indicators, allocated at first use
+    rscm::DevBuf<double> d_ind[kIndSlots];  // [3 + kMaxThresholds][N] per slot of rscm_ens_member_indicators, allocated at first use
     LockstepPlan* plan = nullptr;  // rscm_ens_run_lockstep with this handle first
     WindowDeferral* defer = nullptr;  // set while rscm_ens_run_lockstep collects this handle's window upkeep (lockstep.cpp)
 
@@ -272,14 +287,14 @@ struct rscm_ens {
     int32_t win0 = 0;            // absolute time index of the first stored row
     int32_t lookback = 0;        // own rows before the current one that a step reads (chemistry kinds)
     bool read_ahead = false;     // a linked consumer may read index n+1 before this producer wrote it: rows after a slide must be NaN
-    double* d_row0 = nullptr;    // [V-1][N] the initial rows, saved when step 0 starts (rewind restores them)
+    rscm::DevBuf<double> d_row0;    // [V-1][N] the initial rows, saved when step 0 starts (rewind restores them)
     bool row0_saved = false;
     int32_t out_stride = 0;      // > 0: every out_stride-th row of the output variables is kept in d_out
     int32_t n_out = 0, out_rows = 0;
     std::vector<int32_t> out_vars;      // variable ids kept
     std::vector<int32_t> out_slot;      // per variable id: slot in d_out or -1
-    int32_t* d_out_vars = nullptr;
-    double* d_out = nullptr;     // [n_out][out_rows][N]
+    rscm::DevBuf<int32_t> d_out_vars;
+    rscm::DevBuf<double> d_out;     // [n_out][out_rows][N]
     int32_t keep_rows() const { return std::max(lookback + 1, 2); }
 
     // Base of series[var] such that row t lives at base + t * N (for a windowed handle the address of
@@ -385,8 +400,6 @@ int check_series_stored(const rscm_ens* h, int32_t t_end);
 // RSCM_OK for a stored variable and for a diagnostic whose rows are current; RSCM_ERR_STATE "diagnostic N is stale: compute it again"
 // (diagnostic_host.cpp).  What every reader of a diagnostic's rows asks before it resolves them.
 int check_diagnostic_current(const rscm_ens* h, int32_t var_id);
-// frees the diagnostics' stores and forgets the definitions (rscm_ens_destroy; the stream has been synchronised)
-void diagnostics_release(rscm_ens* h);
 int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                  int32_t* n_range);
 // resolve_rows with its checks for a range every row of which must be computed (RSCM_ERR_STATE else), and the rows' times

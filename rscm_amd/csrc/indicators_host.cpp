@@ -84,7 +84,7 @@ int check_slot(int32_t slot)
 
 int slot_buffer(rscm_ens* h, int32_t slot)
 {
-    if (!h->d_ind[slot]) HIPCHK(rscm::dev_malloc(&h->d_ind[slot], (size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N * sizeof(double)));
+    HIPCHK(h->d_ind[slot].reserve((size_t)(3 + rscm::kMaxThresholds) * (size_t)h->N));
     return RSCM_OK;
 }
 
@@ -154,7 +154,7 @@ int loglik_vector_list(rscm_ens* h, int32_t n_vec, const double* const* vec_dev,
     }
     if (add_dev)
         if (int rc = check_member_vector(h, add_dev, "add_dev")) return rc;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+    HIPCHK(h->d_loglik.reserve((size_t)h->N));
     return RSCM_OK;
 }
 
@@ -205,7 +205,7 @@ int rscm_ens_set_baseline(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t 
     rscm::DevBuf<double> d_new;
     HIPCHK(d_new.alloc((size_t)h->N));
     if (int rc = run_indicators(h, rows, times, nullptr, false, 0, nullptr, d_new.get())) return rc;
-    d_new.install(h->d_base);
+    h->d_base = std::move(d_new);
     return RSCM_OK;
     GUARD_END
 }
@@ -223,7 +223,7 @@ int rscm_ens_set_baseline_values(rscm_ens* h, const double* b, int32_t on_device
     HIPCHK(d_new.alloc((size_t)h->N));
     HIPCHK(hipMemcpyAsync(d_new.get(), b, (size_t)h->N * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
-    d_new.install(h->d_base);
+    h->d_base = std::move(d_new);
     return RSCM_OK;
     GUARD_END
 }
@@ -245,8 +245,7 @@ int rscm_ens_clear_baseline(rscm_ens* h)
     if (h->d_base) {
         if (int rc = set_device(h)) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_base);
-        h->d_base = nullptr;
+        h->d_base.reset();
     }
     return RSCM_OK;
     GUARD_END

@@ -31,7 +31,7 @@ int ensure_derived(rscm_ens* h)
     if (h->derived_hold && !h->derived_dirty && h->d_derived) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
     if (!h->d_derived) {
-        const hipError_t e = rscm::dev_malloc(&h->d_derived, (size_t)rscm::kDerivedRows * h->N * sizeof(double));
+        const hipError_t e = h->d_derived.alloc((size_t)rscm::kDerivedRows * h->N);
         if (e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "member constants of %lld members: %s", (long long)h->N, hipGetErrorString(e));
     }
@@ -394,7 +394,7 @@ int fill_udeb(const rscm_ens* h, int32_t step_begin, int32_t step_end, const rsc
     if (rscm::udeb_layers_unrolled(h->udeb_n_layers))   // by value, in the kernel-argument segment (rows past n_layers stay zero)
         memcpy(a.tables, h->udeb_tables.data(), h->udeb_tables.size() * sizeof(double));
     if (!rscm::udeb_layers_fixed(h->udeb_n_layers)) {
-        if (!h->d_udeb_tables || !h->d_udeb_work || h->udeb_work_layers < h->udeb_n_layers)
+        if (!h->d_udeb_tables || !h->d_udeb_work || h->udeb_work_layers() < h->udeb_n_layers)
             return fail(RSCM_ERR_STATE, "ClimateUDEB work arrays for %d layers not allocated", h->udeb_n_layers);
         a.tables_dev = h->d_udeb_tables;
         a.work = h->d_udeb_work;

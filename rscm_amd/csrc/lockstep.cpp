@@ -396,14 +396,15 @@ int rscm_ens_run_lockstep(rscm_ens* const* handles, int32_t n_handles, int32_t s
         if (!plan || plan->handles != list) {
             if (!plan) plan = lead->plan = new LockstepPlan();
             HIPCHK(hipStreamSynchronize(lead->stream));
-            HIPCHK(hipFree(plan->d_ops));
-            plan->d_ops = nullptr;
+            // the table of the new list is built aside: a failure leaves the plan of the old list whole
+            rscm::DevBuf<rscm::GroupOp> d_new;
+            HIPCHK(d_new.alloc((size_t)n_handles));
+            if (!plan->staging) HIPCHK(hipHostMalloc((void**)&plan->staging, LockstepPlan::kRing * sizeof(rscm::GroupOp), hipHostMallocDefault));
+            plan->d_ops = std::move(d_new);
             plan->handles = list;
             plan->cached.assign((size_t)n_handles, rscm::GroupOp());
             plan->valid.assign((size_t)n_handles, 0);
             plan->ring_pos = 0;
-            HIPCHK(rscm::dev_malloc(&plan->d_ops, (size_t)n_handles * sizeof(rscm::GroupOp)));
-            if (!plan->staging) HIPCHK(hipHostMalloc((void**)&plan->staging, LockstepPlan::kRing * sizeof(rscm::GroupOp), hipHostMallocDefault));
         }
     }
     // The window upkeep of the graph's handles (slides at the end of the step that fills a window, output rows) is collected while

@@ -137,7 +137,7 @@ static int loglik_on_device(rscm_ens* h, const ObsList& o, const RefList& r)
     LoglikRows rows;
     if (int rc = resolve_loglik_rows(&h, 1, false, o, r, &rows)) return rc;
     if (int rc = set_device(h)) return rc;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+    HIPCHK(h->d_loglik.reserve((size_t)h->N));
     if (rows.uncomputed) {
         HIPCHK(rscm::launch_fill(h->d_loglik, h->N, -std::numeric_limits<double>::infinity(), h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
@@ -248,14 +248,13 @@ int prepare_obs(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_
         bd[k] = obs_var[j] == RSCM_TL_VAR_TD ? 1 : 0;
     }
     HIPCHK(hipStreamSynchronize(h->stream));  // a launch may still be reading the previous plan
-    if (blob.size() > h->obs_capacity) {
-        HIPCHK(hipFree(h->d_obs));
-        h->d_obs = nullptr;
-        h->obs_capacity = 0;
-        HIPCHK(rscm::dev_malloc(&h->d_obs, blob.size()));
-        h->obs_capacity = blob.size();
-    }
-    HIPCHK(hipMemcpy(h->d_obs, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    HIPCHK(h->d_loglik.reserve((size_t)h->N));
+    // rewritten where it stands while it is large enough; a larger table is built aside and moved in once it is written, so a
+    // failure leaves the previous observations prepared, whole
+    rscm::DevBuf<unsigned char> d_grown;
+    if (h->d_obs.size() < blob.size()) HIPCHK(d_grown.alloc(blob.size()));
+    HIPCHK(hipMemcpy(d_grown ? d_grown : h->d_obs, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    if (d_grown) h->d_obs = std::move(d_grown);
     h->obs_merged_tidx.assign(bt, bt + n_obs);
     h->obs_merged_deep.assign(bd, bd + n_obs);
     h->ref_active = false;
@@ -265,7 +264,6 @@ int prepare_obs(rscm_ens* h, int32_t n_obs, const int32_t* obs_var, const int32_
     for (int32_t j = 0; j < n_obs; ++j) h->obs_last_tidx = std::max(h->obs_last_tidx, obs_tidx[j]);
     h->obs_normalize = normalize ? 1 : 0;
     h->obs_first_is_deep = first_var == RSCM_TL_VAR_TD ? 1 : 0;
-    if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
     return RSCM_OK;
 }
 
@@ -298,21 +296,13 @@ int prepare_ref(rscm_ens* h, int32_t n_ref, const int32_t* ref_var, const int32_
     }
     if (int rc = set_device(h)) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));  // a launch may still be using the previous layout
-    if (slot.size() > h->ref_slot_capacity) {
-        HIPCHK(hipFree(h->d_ref_slot));
-        h->d_ref_slot = nullptr;
-        h->ref_slot_capacity = 0;
-        HIPCHK(rscm::dev_malloc(&h->d_ref_slot, slot.size() * sizeof(int32_t)));
-        h->ref_slot_capacity = slot.size();
-    }
-    HIPCHK(hipMemcpy(h->d_ref_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if ((size_t)n_defer > h->defer_capacity) {
-        HIPCHK(hipFree(h->d_defer));
-        h->d_defer = nullptr;
-        h->defer_capacity = 0;
-        HIPCHK(rscm::dev_malloc(&h->d_defer, (size_t)n_defer * (size_t)h->N * sizeof(double)));
-        h->defer_capacity = (size_t)n_defer;
-    }
+    // (ref_active is off from the first line on: a failure below leaves a handle that scores without reference periods and
+    // launches on neither buffer.)  The slot table grows as the observation table does; the scratch, [n_defer][N], in place
+    rscm::DevBuf<int32_t> d_grown;
+    if (h->d_ref_slot.size() < slot.size()) HIPCHK(d_grown.alloc(slot.size()));
+    HIPCHK(hipMemcpy(d_grown ? d_grown : h->d_ref_slot, slot.data(), slot.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    if (d_grown) h->d_ref_slot = std::move(d_grown);
+    HIPCHK(h->d_defer.reserve((size_t)n_defer * (size_t)h->N));
     r.obs_slot = h->d_ref_slot;
     r.defer = h->d_defer;
     h->ref = r;
@@ -333,7 +323,7 @@ hipError_t launch_loglik(rscm_ens* h)
     a.n_obs = h->obs_n;
     a.normalize = h->obs_normalize;
     a.first_is_deep = h->obs_first_is_deep;
-    a.obs_value = (const double*)h->d_obs;
+    a.obs_value = (const double*)h->d_obs.get();
     a.obs_sigma = a.obs_value + h->obs_n;
     a.obs_tidx = (const int32_t*)(a.obs_sigma + h->obs_n);
     a.obs_is_deep = a.obs_tidx + h->obs_n;

@@ -76,7 +76,7 @@ int rscm_ens_resample(rscm_ens* h, int64_t M, int64_t s, int64_t w_before, int64
     if (s < 0 || s >= w_total) return fail(RSCM_ERR_INVALID, "the offset must be in [0, w_total), got %lld", (long long)s);
     if (w_before < 0 || w_before > w_total) return fail(RSCM_ERR_INVALID, "w_before = %lld is outside [0, w_total]", (long long)w_before);
     if (int rc = set_device(h)) return rc;
-    if (!h->d_cumw) HIPCHK(rscm::dev_malloc(&h->d_cumw, (size_t)(h->N + rscm::scan_scratch_elems(h->N)) * sizeof(int64_t)));
+    HIPCHK(h->d_cumw.reserve((size_t)(h->N + rscm::scan_scratch_elems(h->N))));
     HIPCHK(rscm::launch_inclusive_scan(h->d_weights, h->d_cumw, h->N, h->d_cumw + h->N, h->stream));
     int64_t w_local = 0;
     HIPCHK(hipMemcpyAsync(&w_local, h->d_cumw + (h->N - 1), sizeof w_local, hipMemcpyDeviceToHost, h->stream));
@@ -88,13 +88,7 @@ int rscm_ens_resample(rscm_ens* h, int64_t M, int64_t s, int64_t w_before, int64
     const int64_t k0 = first_draw_at((uint64_t)w_before, q, r, (uint64_t)s, Mu);
     const int64_t k1 = first_draw_at((uint64_t)w_before + (uint64_t)w_local, q, r, (uint64_t)s, Mu);
     const int64_t n = k1 - k0;
-    if (n > h->anc_capacity || !h->d_anc) {
-        rscm::DevBuf<int64_t> d_new;
-        const int64_t want = std::max<int64_t>(n, 1);
-        HIPCHK(d_new.alloc((size_t)want));
-        d_new.install(h->d_anc);
-        h->anc_capacity = want;
-    }
+    HIPCHK(h->d_anc.reserve((size_t)std::max<int64_t>(n, 1)));   // (the last draw's ancestors go: the caller was handed the address)
     HIPCHK(rscm::launch_ancestors(h->d_cumw, h->N, k0, n, Mu, q, r, (uint64_t)s, (uint64_t)w_before, h->d_anc, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *k_first = k0;

@@ -293,10 +293,11 @@ int configure_ocean(rscm_ens* h, int64_t n_check, Row row)
     const std::vector<double> tab = ocean_irf_table((int)model, row(RSCM_OC_P_IRF_SCALE, 0),
                                                     row(RSCM_OC_P_IRF_SWITCH_TIME, 0), (int64_t)max_hist);
     HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipFree(h->d_ocean_irf));
-    h->d_ocean_irf = nullptr;
-    HIPCHK(rscm::dev_malloc(&h->d_ocean_irf, tab.size() * sizeof(double)));
-    HIPCHK(hipMemcpy(h->d_ocean_irf, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    // The two small tables are built aside and moved in at the end, with the host's facts about them, once nothing can fail any
+    // more: until then -- and after a failure or the refusal below -- the old response is in force, whole.
+    rscm::DevBuf<double> d_irf, d_mode_table;
+    HIPCHK(d_irf.alloc(tab.size()));
+    HIPCHK(hipMemcpy(d_irf, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     // The flux history is a ring: the convolution reads at most max_history_months pulses back, a tile writes
     // up to 48 new ones before it is done reading (ocean.hip), the O(T) recurrence reads the pulse that leaves
     // the window.  On a monthly axis that is 48 KB per member instead of 864 KB (108 000 pulses).
@@ -310,41 +311,54 @@ int configure_ocean(rscm_ens* h, int64_t n_check, Row row)
             return fail(RSCM_ERR_STATE, "max_history_months changes the flux-history ring from %lld to %lld rows at time index %d: "
                         "rewind (rscm_ens_rewind / rscm_ens_set_time_index(0)) before changing it", (long long)h->ocean_hist_rows,
                         (long long)rows, h->time_index);
-        HIPCHK(hipFree(h->d_ocean_hist));
-        h->d_ocean_hist = nullptr;
-        const hipError_t e = rscm::dev_malloc(&h->d_ocean_hist, (size_t)rows * h->N * sizeof(double));
+        // too large to hold twice: the old ring goes first, and the handle is not ready until this call has come through
+        h->ocean_ready = false;
+        h->ocean_hist_rows = 0;
+        const hipError_t e = h->d_ocean_hist.alloc((size_t)rows * h->N);
         if (e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE,
                         "flux history of %lld members x %lld months: %s", (long long)h->N, (long long)rows, hipGetErrorString(e));
-        HIPCHK(hipMemset(h->d_ocean_hist, 0, (size_t)rows * h->N * sizeof(double)));
+        // cleared on the handle's own stream, where every later use of the ring is.  Measured: after a synchronous hipMemset, which
+        // goes through the null stream, with nothing else issued there afterwards, a process that had run for a while did not get the
+        // ring back from hipFree, handle after handle (tests/test_gpu_handle_teardown.py); presumably that fill command kept a reference
+        HIPCHK(hipMemsetAsync(h->d_ocean_hist, 0, (size_t)rows * h->N * sizeof(double), h->stream));
+        HIPCHK(hipStreamSynchronize(h->stream));
         h->ocean_hist_rows = rows;
     }
     if (!h->d_ocean_partial) {
-        const hipError_t e = rscm::dev_malloc(&h->d_ocean_partial, (size_t)(rscm::kOceanSplitYears - 1) * 12 * h->N * sizeof(double));
+        const hipError_t e = h->d_ocean_partial.alloc((size_t)(rscm::kOceanSplitYears - 1) * 12 * h->N);
         if (e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "split-tile sums of %lld members: %s",
                         (long long)h->N, hipGetErrorString(e));
     }
-    h->ocean_forget_partial_sums();  // sums parked under another response table are void
-    h->ocean_steps = 12;
-    h->ocean_max_hist = (int64_t)max_hist;
-    h->ocean_fit_error = ocean_fit_modes(tab, (int)model, row(RSCM_OC_P_IRF_SWITCH_TIME, 0), (int64_t)max_hist, &h->ocean_near, &h->ocean_modes);
-    h->ocean_recur_ok = h->ocean_fit_error >= 0.0 && h->ocean_fit_error <= kOceanFitTolerance;
-    if (h->ocean_recur_ok && !h->d_ocean_mode_state) {
-        const hipError_t e = rscm::dev_malloc(&h->d_ocean_mode_state, (size_t)rscm::kOceanModes * h->N * sizeof(double));
+    rscm::OceanModes modes{};
+    int32_t near = 0;
+    const double fit_error = ocean_fit_modes(tab, (int)model, row(RSCM_OC_P_IRF_SWITCH_TIME, 0), (int64_t)max_hist, &near, &modes);
+    const bool recur_ok = fit_error >= 0.0 && fit_error <= kOceanFitTolerance;
+    if (recur_ok && !h->d_ocean_mode_state) {
+        const hipError_t e = h->d_ocean_mode_state.alloc((size_t)rscm::kOceanModes * h->N);
         if (e != hipSuccess)
             return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "mode sums of %lld members: %s", (long long)h->N, hipGetErrorString(e));
     }
-    if (h->ocean_recur_ok) {
-        if (!h->d_ocean_mode_table) HIPCHK(rscm::dev_malloc(&h->d_ocean_mode_table, (size_t)3 * rscm::kOceanModes * sizeof(double)));
+    if (recur_ok) {
+        HIPCHK(d_mode_table.alloc((size_t)3 * rscm::kOceanModes));
         double t3[3 * rscm::kOceanModes];
         for (int q = 0; q < rscm::kOceanModes; ++q) {
-            t3[q] = h->ocean_modes.d[q];
-            t3[rscm::kOceanModes + q] = h->ocean_modes.c[q];
-            t3[2 * rscm::kOceanModes + q] = h->ocean_modes.e[q];
+            t3[q] = modes.d[q];
+            t3[rscm::kOceanModes + q] = modes.c[q];
+            t3[2 * rscm::kOceanModes + q] = modes.e[q];
         }
-        HIPCHK(hipMemcpy(h->d_ocean_mode_table, t3, sizeof t3, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(d_mode_table, t3, sizeof t3, hipMemcpyHostToDevice));
+        h->d_ocean_mode_table = std::move(d_mode_table);
     }
+    h->d_ocean_irf = std::move(d_irf);
+    h->ocean_forget_partial_sums();  // sums parked under another response table are void
+    h->ocean_steps = 12;
+    h->ocean_max_hist = (int64_t)max_hist;
+    h->ocean_modes = modes;
+    h->ocean_near = near;
+    h->ocean_fit_error = fit_error;
+    h->ocean_recur_ok = recur_ok;
     h->ocean_ready = true;
     return RSCM_OK;
 }
@@ -376,6 +390,9 @@ int configure_udeb(rscm_ens* h, int64_t n_check, Row row)
         return fail(RSCM_ERR_INVALID, "steps_per_year must be a positive integer, got %g", steps);
     const double eff = row(RSCM_UD_P_EFFICACY_APPLY, 0);
     if (eff != 0.0 && eff != 1.0 && eff != 2.0) return fail(RSCM_ERR_INVALID, "efficacy_apply must be 0, 1 or 2");
+    // From here on the handle's facts and buffers change one by one: it is not ready until all of them stand, so a failed
+    // allocation or copy below leaves nothing that would launch on a missing column or a table of another layer count
+    h->udeb_ready = false;
     h->udeb_n_layers = (int32_t)nl;
     h->udeb_steps = (int32_t)steps;
     h->udeb_land_hc = row(RSCM_UD_P_LAND_HC_ENABLED, 0) != 0.0 ? 1 : 0;
@@ -405,44 +422,37 @@ int configure_udeb(rscm_ens* h, int64_t n_check, Row row)
             kfull[n] = kf;
             partw[n] = pw;
         }
-        if (!h->d_win_kfull) HIPCHK(rscm::dev_malloc(&h->d_win_kfull, (size_t)h->T * sizeof(int32_t)));
-        if (!h->d_win_partw) HIPCHK(rscm::dev_malloc(&h->d_win_partw, (size_t)h->T * sizeof(double)));
+        HIPCHK(h->d_win_kfull.reserve((size_t)h->T));
+        HIPCHK(h->d_win_partw.reserve((size_t)h->T));
         HIPCHK(hipMemcpyAsync(h->d_win_kfull, kfull.data(), kfull.size() * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(h->d_win_partw, partw.data(), partw.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
     }
-    {   // the columns: room for 50 layers at least (any of the unrolled kernels), more if asked for
+    {   // the columns: room for 50 layers at least (any of the unrolled kernels), more if asked for.  Too large to hold twice: they
+        // grow in place (a failure leaves the handle not ready, above)
         const int32_t want = std::max(rscm::kUdebMaxOnChipLayers, h->udeb_n_layers);
-        if (want > h->udeb_ocean_layers) {
-            (void)hipFree(h->d_ocean);
-            h->d_ocean = nullptr;
-            h->udeb_ocean_layers = 0;
-            const hipError_t e = rscm::dev_malloc(&h->d_ocean, (size_t)2 * want * h->N * sizeof(double));
-            if (e != hipSuccess)
-                return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "ocean columns of %d layers x %lld members: %s", want,
-                            (long long)h->N, hipGetErrorString(e));
-            h->udeb_ocean_layers = want;
-        }
+        const hipError_t e = h->d_ocean.reserve((size_t)2 * want * h->N);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "ocean columns of %d layers x %lld members: %s", want,
+                        (long long)h->N, hipGetErrorString(e));
     }
     if (!rscm::udeb_layers_fixed(h->udeb_n_layers)) {   // the columns-in-HBM kernel (more than 64 layers; up to 64 only on request, as the
         // yardstick of the runtime-count kernels -- rscm_gpu_set_udeb_variant(3)): its c' array and its table live in device memory
-        if (h->udeb_n_layers > h->udeb_work_layers) {
-            (void)hipFree(h->d_udeb_work);
-            (void)hipFree(h->d_udeb_tables);
-            h->d_udeb_work = h->d_udeb_tables = nullptr;
-            h->udeb_work_layers = 0;
-            const hipError_t e = rscm::dev_malloc(&h->d_udeb_work, (size_t)h->udeb_n_layers * h->N * sizeof(double));
-            if (e != hipSuccess)
-                return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "work array of %d layers x %lld members: %s",
-                            h->udeb_n_layers, (long long)h->N, hipGetErrorString(e));
-            // (room for the largest on-chip capacity: the unrolled sweeps request the table rows of their whole capacity, and the rows past
-            // the layer count must read as zeros -- they are what makes those rows of the column exact no-ops)
-            HIPCHK(rscm::dev_malloc(&h->d_udeb_tables, (size_t)6 * std::max(h->udeb_n_layers, (int32_t)rscm::kUdebDevTableRows) * sizeof(double)));
-            h->udeb_work_layers = h->udeb_n_layers;
-        }
-        HIPCHK(hipMemsetAsync(h->d_udeb_tables, 0, (size_t)6 * std::max(h->udeb_work_layers, (int32_t)rscm::kUdebDevTableRows) * sizeof(double), h->stream));
-        HIPCHK(hipMemcpyAsync(h->d_udeb_tables, h->udeb_tables.data(), h->udeb_tables.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        const hipError_t e = h->d_udeb_work.reserve((size_t)h->udeb_n_layers * h->N);
+        if (e != hipSuccess)
+            return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "work array of %d layers x %lld members: %s",
+                        h->udeb_n_layers, (long long)h->N, hipGetErrorString(e));
+        // (room for the largest on-chip capacity: the unrolled sweeps request the table rows of their whole capacity, and the rows past
+        // the layer count must read as zeros -- they are what makes those rows of the column exact no-ops)
+        // The table is rewritten where it stands while it is large enough; a larger one is built aside and moved in once it is written
+        rscm::DevBuf<double> d_grown;
+        const size_t table_elems = (size_t)6 * std::max(h->udeb_n_layers, (int32_t)rscm::kUdebDevTableRows);
+        if (h->d_udeb_tables.size() < table_elems) HIPCHK(d_grown.alloc(table_elems));
+        const rscm::DevBuf<double>& d_table = d_grown ? d_grown : h->d_udeb_tables;
+        HIPCHK(hipMemsetAsync(d_table, 0, d_table.size() * sizeof(double), h->stream));
+        HIPCHK(hipMemcpyAsync(d_table, h->udeb_tables.data(), h->udeb_tables.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
+        if (d_grown) h->d_udeb_tables = std::move(d_grown);
     }
     h->udeb_ready = true;
     return RSCM_OK;
@@ -649,7 +659,7 @@ static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const
     if ((uint64_t)n_members > (uint64_t)std::numeric_limits<int32_t>::max() * 256ull)
         return fail(RSCM_ERR_INVALID, "n_members too large for one launch grid");
 
-    rscm_ens* h = new rscm_ens();
+    std::unique_ptr<rscm_ens> h(new rscm_ens());   // every return before the last goes through ~rscm_ens
     h->kind = kind;
     h->N = n_members;
     h->T = n_times;
@@ -682,10 +692,8 @@ static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const
             for (int32_t v = 1; v < h->V; ++v) h->out_vars.push_back(v);
         else
             for (int32_t k = 0; k < n_out_vars; ++k) {
-                if (out_vars[k] < 1 || out_vars[k] >= h->V || h->out_slot[out_vars[k]] >= 0) {
-                    delete h;
+                if (out_vars[k] < 1 || out_vars[k] >= h->V || h->out_slot[out_vars[k]] >= 0)
                     return fail(RSCM_ERR_INVALID, "output variable %d: not a stored variable of this kind, or listed twice", out_vars[k]);
-                }
                 h->out_slot[out_vars[k]] = k;
                 h->out_vars.push_back(out_vars[k]);
             }
@@ -693,65 +701,50 @@ static int create_handle(int32_t kind, int64_t n_members, int32_t n_times, const
         for (int32_t k = 0; k < h->n_out; ++k) h->out_slot[h->out_vars[k]] = k;
     }
 
-    auto cleanup = [&](int rc) {
-        rscm_ens_destroy(h);
-        return rc;
-    };
     hipError_t e = hipSetDevice(device_id);
-    if (e != hipSuccess) {
-        delete h;
-        return fail(RSCM_ERR_DEVICE, "hipSetDevice(%d): %s", device_id, hipGetErrorString(e));
-    }
-#define CK(expr)                                                                              \
-    do {                                                                                      \
-        hipError_t e2_ = (expr);                                                              \
-        if (e2_ != hipSuccess)                                                                \
-            return cleanup(fail(e2_ == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, \
-                                "%s failed: %s", #expr, hipGetErrorString(e2_)));             \
-    } while (0)
-    CK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "hipSetDevice(%d): %s", device_id, hipGetErrorString(e));
+    HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->own_stream = true;
-    CK(hipEventCreate(&h->ev0));
-    CK(hipEventCreate(&h->ev1));
+    HIPCHK(hipEventCreate(&h->ev0));
+    HIPCHK(hipEventCreate(&h->ev1));
     const size_t series_elems = (size_t)(h->V - 1) * (size_t)h->rows * (size_t)h->N;
-    CK(rscm::dev_malloc(&h->d_params, (size_t)h->P * h->N * sizeof(double)));
-    CK(rscm::dev_malloc(&h->d_series, series_elems * sizeof(double)));
-    CK(rscm::dev_malloc(&h->d_status, (size_t)h->N));
+    HIPCHK(h->d_params.alloc((size_t)h->P * h->N));
+    HIPCHK(h->d_series.alloc(series_elems));
+    HIPCHK(h->d_status.alloc((size_t)h->N));
     if (h->windowed) {
-        CK(rscm::dev_malloc(&h->d_row0, (size_t)(h->V - 1) * h->N * sizeof(double)));
+        HIPCHK(h->d_row0.alloc((size_t)(h->V - 1) * h->N));
         if (h->n_out > 0) {
             const size_t out_elems = (size_t)h->n_out * h->out_rows * h->N;
-            CK(rscm::dev_malloc(&h->d_out, out_elems * sizeof(double)));
-            CK(rscm::dev_malloc(&h->d_out_vars, (size_t)h->n_out * sizeof(int32_t)));
-            CK(hipMemcpy(h->d_out_vars, h->out_vars.data(), (size_t)h->n_out * sizeof(int32_t), hipMemcpyHostToDevice));
-            CK(rscm::launch_fill(h->d_out, (int64_t)out_elems, std::numeric_limits<double>::quiet_NaN(), h->stream));
+            HIPCHK(h->d_out.alloc(out_elems));
+            HIPCHK(h->d_out_vars.alloc((size_t)h->n_out));
+            HIPCHK(hipMemcpy(h->d_out_vars, h->out_vars.data(), (size_t)h->n_out * sizeof(int32_t), hipMemcpyHostToDevice));
+            HIPCHK(rscm::launch_fill(h->d_out, (int64_t)out_elems, std::numeric_limits<double>::quiet_NaN(), h->stream));
         }
     }
-    CK(rscm::dev_malloc(&h->d_nsub_tl, (size_t)(h->T - 1) * sizeof(int32_t)));
-    CK(rscm::dev_malloc(&h->d_nsub_cc, (size_t)(h->T - 1) * sizeof(int32_t)));
-    CK(rscm::dev_malloc(&h->d_partial, 4 * 1024 * sizeof(double)));
-    CK(rscm::dev_malloc(&h->d_out4, 4 * sizeof(double)));
+    HIPCHK(h->d_nsub_tl.alloc((size_t)(h->T - 1)));
+    HIPCHK(h->d_nsub_cc.alloc((size_t)(h->T - 1)));
+    HIPCHK(h->d_partial.alloc(4 * 1024));
+    HIPCHK(h->d_out4.alloc(4));
     if (kind == RSCM_KIND_UDEB) {
-        CK(rscm::dev_malloc(&h->d_scal, (size_t)rscm::kUdebScalars * h->N * sizeof(double)));
-        CK(rscm::dev_malloc(&h->d_hist, (size_t)h->T * h->N * sizeof(double)));
+        HIPCHK(h->d_scal.alloc((size_t)rscm::kUdebScalars * h->N));
+        HIPCHK(h->d_hist.alloc((size_t)h->T * h->N));
     }
     if (h->info().needs_bounds) {  // kinds that use the step length
-        CK(rscm::dev_malloc(&h->d_bounds, (size_t)(h->T + 1) * sizeof(double)));
-        CK(hipMemcpyAsync(h->d_bounds, h->bounds.data(), (size_t)(h->T + 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h->d_bounds.alloc((size_t)(h->T + 1)));
+        HIPCHK(hipMemcpyAsync(h->d_bounds, h->bounds.data(), (size_t)(h->T + 1) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
     if (kind == RSCM_KIND_AGGREGATE) {  // contributors that are neither linked nor set stay NaN = skipped
-        CK(rscm::dev_malloc(&h->d_forcing, (size_t)h->n_inputs * h->T * sizeof(double)));
-        CK(rscm::launch_fill(h->d_forcing, (int64_t)h->n_inputs * h->T, std::numeric_limits<double>::quiet_NaN(), h->stream));
+        HIPCHK(h->d_forcing.alloc((size_t)h->n_inputs * h->T));
+        HIPCHK(rscm::launch_fill(h->d_forcing, (int64_t)h->n_inputs * h->T, std::numeric_limits<double>::quiet_NaN(), h->stream));
         h->n_scen = 1;
         h->forcing_set = true;
     }
-    CK(hipMemsetAsync(h->d_status, 0, (size_t)h->N, h->stream));
+    HIPCHK(hipMemsetAsync(h->d_status, 0, (size_t)h->N, h->stream));
     // never-written entries are NaN (builder.rs:772-780)
-    CK(rscm::launch_fill(h->d_series, (int64_t)series_elems, std::numeric_limits<double>::quiet_NaN(),
+    HIPCHK(rscm::launch_fill(h->d_series, (int64_t)series_elems, std::numeric_limits<double>::quiet_NaN(),
                          h->stream));
-    CK(hipStreamSynchronize(h->stream));
-#undef CK
-    *out = h;
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out = h.release();
     return RSCM_OK;
     GUARD_END
 }
@@ -761,68 +754,20 @@ int rscm_ens_destroy(rscm_ens* h)
     if (!h) return RSCM_OK;
     if (h->link_refs > 0)
         return fail(RSCM_ERR_STATE, "%d linked input(s) of other ensembles still read this one's series: destroy or unlink them first", h->link_refs);
-    for (auto& l : h->links)
-        if (l.src) {
-            --l.src->link_refs;
-            l.src = nullptr;
-        }
     (void)hipSetDevice(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    (void)hipFree(h->d_params);
-    (void)hipFree(h->d_series);
-    (void)hipFree(h->d_forcing);
-    (void)hipFree(h->d_scen);
-    (void)hipFree(h->d_noise_state);
-    (void)hipFree(h->d_status);
-    (void)hipFree(h->d_nsub_tl);
-    (void)hipFree(h->d_nsub_cc);
-    (void)hipFree(h->d_ghg_tables);
-    (void)hipFree(h->d_ocean_hist);
-    (void)hipFree(h->d_ocean_irf);
-    (void)hipFree(h->d_ocean_partial);
-    (void)hipFree(h->d_ocean_mode_state);
-    (void)hipFree(h->d_ocean_mode_table);
-    (void)hipFree(h->d_ocean);
-    (void)hipFree(h->d_udeb_work);
-    (void)hipFree(h->d_udeb_tables);
-    (void)hipFree(h->d_derived);
-    if (h->split_stream) (void)hipStreamDestroy(h->split_stream);
-    if (h->split_fork) (void)hipEventDestroy(h->split_fork);
-    if (h->split_join) (void)hipEventDestroy(h->split_join);
-    (void)hipFree(h->d_scal);
-    (void)hipFree(h->d_hist);
-    (void)hipFree(h->d_tables);
-    (void)hipFree(h->d_bounds);
-    (void)hipFree(h->d_win_kfull);
-    (void)hipFree(h->d_win_partw);
-    (void)hipFree(h->d_partial);
-    (void)hipFree(h->d_out4);
-    (void)hipFree(h->d_loglik);
-    (void)hipFree(h->d_obs);
-    (void)hipFree(h->d_ref_slot);
-    (void)hipFree(h->d_defer);
-    select_release(h);
-    (void)hipFree(h->d_weights);
-    (void)hipFree(h->d_cumw);
-    (void)hipFree(h->d_anc);
-    (void)hipFree(h->d_base);
-    (void)hipFree(h->d_groups);
-    for (double* p : h->d_ind) (void)hipFree(p);
-    diagnostics_release(h);
-    if (h->plan) {
-        (void)hipFree(h->plan->d_ops);
-        if (h->plan->staging) (void)hipHostFree(h->plan->staging);
-        delete h->plan;
-        h->plan = nullptr;
-    }
-    (void)hipFree(h->d_row0);
-    (void)hipFree(h->d_out);
-    (void)hipFree(h->d_out_vars);
-    if (h->ev0) (void)hipEventDestroy(h->ev0);
-    if (h->ev1) (void)hipEventDestroy(h->ev1);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
     return RSCM_OK;
+}
+
+// What a handle holds that is not device memory; the buffers and then the stream follow (ens.hpp, at the struct).  The stream is
+// synchronised here, not in rscm_ens_destroy, so that a handle whose construction failed half-way goes the same way.
+rscm_ens::~rscm_ens()
+{
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (auto& l : links)
+        if (l.src) --l.src->link_refs;
+    select_release(this);
+    delete plan;
 }
 
 
@@ -986,30 +931,33 @@ int rscm_ens_set_forcing(rscm_ens* h, int32_t var_id, int32_t n_scen, const doub
     if (int rc = set_device(h)) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->year_facts.drop_forcing();   // from here on the table may change: the verdict on the new one is formed once it stands
-    if (n_scen != h->n_scen || !h->d_forcing) {
-        HIPCHK(hipFree(h->d_forcing));
-        h->d_forcing = nullptr;
-        HIPCHK(rscm::dev_malloc(&h->d_forcing, (size_t)n_scen * h->n_inputs * h->T * sizeof(double)));
-        if (h->kind == RSCM_KIND_GHG_FORCING) {
-            HIPCHK(hipFree(h->d_ghg_tables));
-            h->d_ghg_tables = nullptr;
-            HIPCHK(rscm::dev_malloc(&h->d_ghg_tables, (size_t)n_scen * rscm::kGhgRows * h->T * sizeof(double)));
-        }
+    // Tables of the same scenario count are rewritten where they stand.  Tables of another count are built aside and moved in,
+    // with n_scen, once they are written: a failure on the way leaves the handle with the tables and the count it had.
+    const bool resize = n_scen != h->n_scen || !h->d_forcing;
+    rscm::DevBuf<double> d_forcing_new, d_ghg_new;
+    rscm::DevBuf<int32_t> d_scen_new;
+    if (resize) {
+        HIPCHK(d_forcing_new.alloc((size_t)n_scen * h->n_inputs * h->T));
+        if (h->kind == RSCM_KIND_GHG_FORCING) HIPCHK(d_ghg_new.alloc((size_t)n_scen * rscm::kGhgRows * h->T));
     }
-    HIPCHK(hipMemcpyAsync(h->d_forcing, series, (size_t)n_scen * h->n_inputs * h->T * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    double* const d_forcing = resize ? d_forcing_new : h->d_forcing;
+    double* const d_ghg = resize ? d_ghg_new : h->d_ghg_tables;
+    HIPCHK(hipMemcpyAsync(d_forcing, series, (size_t)n_scen * h->n_inputs * h->T * sizeof(double), hipMemcpyHostToDevice, h->stream));
     std::vector<double> ghg_tab;  // must outlive the copy below (synchronised before return)
     if (h->kind == RSCM_KIND_GHG_FORCING) {
         ghg_tab = ghg_tables(series, n_scen, h->T);
-        HIPCHK(hipMemcpyAsync(h->d_ghg_tables, ghg_tab.data(), ghg_tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(d_ghg, ghg_tab.data(), ghg_tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     }
-    if (scenario_of_member) {
-        if (!h->d_scen) HIPCHK(rscm::dev_malloc(&h->d_scen, (size_t)h->N * sizeof(int32_t)));
-        HIPCHK(hipMemcpyAsync(h->d_scen, scenario_of_member, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-    } else if (h->d_scen) {
-        HIPCHK(hipFree(h->d_scen));
-        h->d_scen = nullptr;
+    if (scenario_of_member) {   // (indices into the new tables: never written over the old ones' while those may stay)
+        if (resize || !h->d_scen) HIPCHK(d_scen_new.alloc((size_t)h->N));
+        HIPCHK(hipMemcpyAsync(d_scen_new ? d_scen_new : h->d_scen, scenario_of_member, (size_t)h->N * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
     }
     HIPCHK(hipStreamSynchronize(h->stream));
+    if (resize) {
+        h->d_forcing = std::move(d_forcing_new);
+        if (h->kind == RSCM_KIND_GHG_FORCING) h->d_ghg_tables = std::move(d_ghg_new);
+    }
+    if (d_scen_new || !scenario_of_member) h->d_scen = std::move(d_scen_new);   // (omitted: the members' scenario table goes)
     h->n_scen = n_scen;
     h->source = source;
     h->forcing_set = true;
@@ -1850,7 +1798,7 @@ static int set_noise(rscm_ens* h, int32_t kind, uint64_t seed, double sigma, dou
     }
     if (rscm::noise_kind_keeps_state(kind) && !h->d_noise_state) {
         if (int rc = set_device(h)) return rc;
-        HIPCHK(rscm::dev_malloc(&h->d_noise_state, (size_t)h->N * sizeof(double)));
+        HIPCHK(h->d_noise_state.alloc((size_t)h->N));
     }
     h->noise_kind = kind;
     h->noise_seed = seed;

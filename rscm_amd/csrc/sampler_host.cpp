@@ -15,30 +15,30 @@ struct rscm_sampler {
     bool sharded = false;            // driven half-step by half-step with an exchange in between
     int32_t rank = 0, n_ranks = 1;   // sharded: this rank owns half-walkers [rank * n_local, (rank + 1) * n_local) of both halves
     int32_t n_local = 0;             // = members of the evaluator
-    double* d_send = nullptr;        // [D + 1][n_local]
-    double* d_recv = nullptr;        // [n_ranks][D + 1][n_local]
+    rscm::DevBuf<double> d_send;        // [D + 1][n_local]
+    rscm::DevBuf<double> d_recv;        // [n_ranks][D + 1][n_local]
     double stretch_a = 2.0;
     uint64_t seed = 0;
     int32_t iteration = 0;
     bool positions_set = false;
-    int32_t* d_rows = nullptr;
-    int32_t* d_kind = nullptr;
-    double* d_base = nullptr;
-    double* d_pa = nullptr;
-    double* d_pb = nullptr;
-    double* d_plo = nullptr;
-    double* d_phi = nullptr;
-    double* d_pos = nullptr;
-    double* d_logp = nullptr;
-    double* d_prop = nullptr;
-    double* d_z = nullptr;
-    double* d_lp = nullptr;
-    int64_t* d_nacc = nullptr;
-    int64_t* d_nprop = nullptr;
+    rscm::DevBuf<int32_t> d_rows;
+    rscm::DevBuf<int32_t> d_kind;
+    rscm::DevBuf<double> d_base;
+    rscm::DevBuf<double> d_pa;
+    rscm::DevBuf<double> d_pb;
+    rscm::DevBuf<double> d_plo;
+    rscm::DevBuf<double> d_phi;
+    rscm::DevBuf<double> d_pos;
+    rscm::DevBuf<double> d_logp;
+    rscm::DevBuf<double> d_prop;
+    rscm::DevBuf<double> d_z;
+    rscm::DevBuf<double> d_lp;
+    rscm::DevBuf<int64_t> d_nacc;
+    rscm::DevBuf<int64_t> d_nprop;
     // fused: the two-layer run+likelihood kernel scores a half; otherwise the half is run through
     // rscm_ens_run_async (any kind, stored series) and scored by the likelihood kernel
     bool fused = true;
-    unsigned char* d_sobs = nullptr; // stored path: the tables lik points into (upload_loglik)
+    rscm::DevBuf<unsigned char> d_sobs; // stored path: the tables lik points into (upload_loglik)
     rscm::LoglikArgs lik{};
     // the observations as given at creation (rscm_sampler_set_reference lays the stored path's tables out again)
     std::vector<int32_t> obs_owner, obs_var, obs_tidx;
@@ -51,7 +51,13 @@ struct rscm_sampler {
     std::vector<uint64_t> graph_sampled_rows;  // per handle: bit j = parameter row j is written by the proposal kernel
     bool graph_clear = false;                  // NaN the stored rows before every run (graphs in which a consumer runs ahead of its producer)
     int32_t graph_last_step = 0;
-    double** d_param_ptr = nullptr;            // [D] device addresses of the sampled rows
+    rscm::DevBuf<double*> d_param_ptr;         // [D] device addresses of the sampled rows
+    ~rscm_sampler()   // the buffers follow, once nothing on the evaluator's stream reads them any more
+    {
+        if (ev) (void)hipStreamSynchronize(ev->stream);
+        if (ev0) (void)hipEventDestroy(ev0);
+        if (ev1) (void)hipEventDestroy(ev1);
+    }
     ObsList observations() const
     {
         return {(int32_t)obs_var.size(), graph.empty() ? nullptr : obs_owner.data(), obs_var.data(), obs_tidx.data(), obs_value.data(),
@@ -166,7 +172,7 @@ int check_prior(int32_t d, const int32_t* prior_kind, const double* prior_a, con
 }
 
 // What both creators set, allocate and upload: the walkers' state, the priors, the exchange buffers, counters and events; the
-// observations are kept for rscm_sampler_set_reference.  On failure the caller destroys s.
+// observations are kept for rscm_sampler_set_reference.
 int sampler_init(rscm_sampler* s, rscm_ens* ev, int32_t n_walkers, int32_t n_dims, const int32_t* prior_kind, const double* prior_a,
                  const double* prior_b, const double* prior_low, const double* prior_high, const ObsList& o, double stretch_a, uint64_t seed,
                  int32_t rank, int32_t n_ranks)
@@ -189,20 +195,20 @@ int sampler_init(rscm_sampler* s, rscm_ens* ev, int32_t n_walkers, int32_t n_dim
     }
     s->normalize = o.normalize ? 1 : 0;
     const size_t W = (size_t)n_walkers, H = (size_t)ev->N, D = (size_t)n_dims;  // H: this rank's block of a half
-    HIPCHK(rscm::dev_malloc(&s->d_kind, D * sizeof(int32_t)));
-    HIPCHK(rscm::dev_malloc(&s->d_pa, D * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_pb, D * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_plo, D * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_phi, D * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_pos, D * W * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_logp, W * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_prop, D * H * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_z, H * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_lp, H * sizeof(double)));
-    HIPCHK(rscm::dev_malloc(&s->d_send, (D + 1) * H * sizeof(double)));   // 2 x (D + 1) x H doubles: also for one rank (the exchange of
-    HIPCHK(rscm::dev_malloc(&s->d_recv, (size_t)n_ranks * (D + 1) * H * sizeof(double)));   // a one-rank group is a copy)
-    HIPCHK(rscm::dev_malloc(&s->d_nacc, W * sizeof(int64_t)));
-    HIPCHK(rscm::dev_malloc(&s->d_nprop, W * sizeof(int64_t)));
+    HIPCHK(s->d_kind.alloc(D));
+    HIPCHK(s->d_pa.alloc(D));
+    HIPCHK(s->d_pb.alloc(D));
+    HIPCHK(s->d_plo.alloc(D));
+    HIPCHK(s->d_phi.alloc(D));
+    HIPCHK(s->d_pos.alloc(D * W));
+    HIPCHK(s->d_logp.alloc(W));
+    HIPCHK(s->d_prop.alloc(D * H));
+    HIPCHK(s->d_z.alloc(H));
+    HIPCHK(s->d_lp.alloc(H));
+    HIPCHK(s->d_send.alloc((D + 1) * H));   // 2 x (D + 1) x H doubles: also for one rank (the exchange of
+    HIPCHK(s->d_recv.alloc((size_t)n_ranks * (D + 1) * H));   // a one-rank group is a copy)
+    HIPCHK(s->d_nacc.alloc(W));
+    HIPCHK(s->d_nprop.alloc(W));
     HIPCHK(hipMemcpy(s->d_kind, prior_kind, D * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->d_pa, prior_a, D * sizeof(double), hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(s->d_pb, prior_b, D * sizeof(double), hipMemcpyHostToDevice));
@@ -228,7 +234,7 @@ int sampler_install_table(rscm_sampler* s, LoglikRows& rows)
     rscm::LoglikArgs a{};
     if (int rc = upload_loglik(rows, s->observations(), h->N, h->d_loglik, h->stream, d_new, &a)) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));   // the copy is in, and no launch reads the previous table any more
-    d_new.install(s->d_sobs);
+    s->d_sobs = std::move(d_new);
     s->lik = a;
     s->graph_last_step = rows.last_row;
     return RSCM_OK;
@@ -289,31 +295,26 @@ int rscm_sampler_create_sharded(rscm_ens* evaluator, int32_t n_walkers, int32_t 
     LoglikRows rows;   // stored path: resolved before anything is allocated, uploaded once the sampler exists
     if (fused) {
         if (int rc = prepare_obs(h, n_obs, obs_var, obs_tidx, obs_value, obs_sigma, normalize)) return rc;
-        h->loglik_stop_at_last_obs = true;   // cleared again by rscm_sampler_destroy
     } else {
         if (h->rows != h->T)
             return fail(RSCM_ERR_INVALID, "this evaluator stores no series: only the fused two-layer likelihood "
                                           "(ascending observation times) is available for it");
         if (int rc = resolve_loglik_rows(&h, 1, true, o, {}, &rows)) return rc;
         if (int rc = set_device(h)) return rc;
-        if (!h->d_loglik) HIPCHK(rscm::dev_malloc(&h->d_loglik, (size_t)h->N * sizeof(double)));
+        HIPCHK(h->d_loglik.reserve((size_t)h->N));
     }
-    rscm_sampler* s = new rscm_sampler();
+    std::unique_ptr<rscm_sampler> s(new rscm_sampler());
     s->fused = fused;
-    auto fill = [&]() -> int {
-        if (int rc = sampler_init(s, h, n_walkers, n_dims, prior_kind, prior_a, prior_b, prior_low, prior_high, o, stretch_a, seed, rank, n_ranks))
-            return rc;
-        HIPCHK(rscm::dev_malloc(&s->d_rows, (size_t)n_dims * sizeof(int32_t)));
-        HIPCHK(rscm::dev_malloc(&s->d_base, (size_t)h->P * sizeof(double)));
-        HIPCHK(hipMemcpy(s->d_rows, param_rows, (size_t)n_dims * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(s->d_base, base_params, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
-        return fused ? RSCM_OK : sampler_install_table(s, rows);   // the observation rows of the stored series, once
-    };
-    if (int rc = fill()) {
-        rscm_sampler_destroy(s);
+    if (int rc = sampler_init(s.get(), h, n_walkers, n_dims, prior_kind, prior_a, prior_b, prior_low, prior_high, o, stretch_a, seed, rank, n_ranks))
         return rc;
-    }
-    *out = s;
+    HIPCHK(s->d_rows.alloc((size_t)n_dims));
+    HIPCHK(s->d_base.alloc((size_t)h->P));
+    HIPCHK(hipMemcpy(s->d_rows, param_rows, (size_t)n_dims * sizeof(int32_t), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(s->d_base, base_params, (size_t)h->P * sizeof(double), hipMemcpyHostToDevice));
+    if (!fused)   // the observation rows of the stored series, once
+        if (int rc = sampler_install_table(s.get(), rows)) return rc;
+    if (fused) h->loglik_stop_at_last_obs = true;   // only now that the sampler stands; cleared again by rscm_sampler_destroy
+    *out = s.release();
     return RSCM_OK;
     GUARD_END
 }
@@ -366,27 +367,21 @@ int rscm_sampler_create_graph(rscm_ens* const* handles, int32_t n_handles, int32
     LoglikRows rows;
     if (int rc = resolve_loglik_rows(handles, n_handles, true, o, {}, &rows)) return rc;
     if (int rc = set_device(lead)) return rc;
-    if (!lead->d_loglik) HIPCHK(rscm::dev_malloc(&lead->d_loglik, (size_t)lead->N * sizeof(double)));
-    rscm_sampler* s = new rscm_sampler();
+    HIPCHK(lead->d_loglik.reserve((size_t)lead->N));
+    std::unique_ptr<rscm_sampler> s(new rscm_sampler());
     s->fused = false;
     s->graph.assign(handles, handles + n_handles);
     s->graph_sampled_rows = sampled;
     s->graph_clear = clear_between_runs != 0;
-    auto fill = [&]() -> int {
-        if (int rc = sampler_init(s, lead, n_walkers, n_dims, prior_kind, prior_a, prior_b, prior_low, prior_high, o, stretch_a, seed, rank, n_ranks))
-            return rc;
-        std::vector<double*> ptrs((size_t)n_dims);
-        for (int32_t d = 0; d < n_dims; ++d) ptrs[(size_t)d] = handles[param_owner[d]]->d_params + (size_t)param_rows[d] * (size_t)lead->N;
-        HIPCHK(rscm::dev_malloc((void**)&s->d_param_ptr, ptrs.size() * sizeof(double*)));
-        HIPCHK(hipMemcpy(s->d_param_ptr, ptrs.data(), ptrs.size() * sizeof(double*), hipMemcpyHostToDevice));
-        // the observation rows where their owners store them; one partial sum per (owner, variable) in the caller's order
-        return sampler_install_table(s, rows);
-    };
-    if (int rc = fill()) {
-        rscm_sampler_destroy(s);
+    if (int rc = sampler_init(s.get(), lead, n_walkers, n_dims, prior_kind, prior_a, prior_b, prior_low, prior_high, o, stretch_a, seed, rank, n_ranks))
         return rc;
-    }
-    *out = s;
+    std::vector<double*> ptrs((size_t)n_dims);
+    for (int32_t d = 0; d < n_dims; ++d) ptrs[(size_t)d] = handles[param_owner[d]]->d_params + (size_t)param_rows[d] * (size_t)lead->N;
+    HIPCHK(s->d_param_ptr.alloc(ptrs.size()));
+    HIPCHK(hipMemcpy(s->d_param_ptr, ptrs.data(), ptrs.size() * sizeof(double*), hipMemcpyHostToDevice));
+    // the observation rows where their owners store them; one partial sum per (owner, variable) in the caller's order
+    if (int rc = sampler_install_table(s.get(), rows)) return rc;
+    *out = s.release();
     return RSCM_OK;
     GUARD_END
 }
@@ -395,20 +390,10 @@ int rscm_sampler_destroy(rscm_sampler* s)
 {
     if (!s) return RSCM_OK;
     if (s->ev) {
-        (void)hipStreamSynchronize(s->ev->stream);
         s->ev->loglik_stop_at_last_obs = false;
         s->ev->ref_active = false;
     }
-    (void)hipFree(s->d_rows); (void)hipFree(s->d_kind); (void)hipFree(s->d_base); (void)hipFree(s->d_pa);
-    (void)hipFree(s->d_pb); (void)hipFree(s->d_plo); (void)hipFree(s->d_phi); (void)hipFree(s->d_pos); (void)hipFree(s->d_logp); (void)hipFree(s->d_prop);
-    (void)hipFree(s->d_z); (void)hipFree(s->d_lp); (void)hipFree(s->d_nacc); (void)hipFree(s->d_nprop);
-    (void)hipFree(s->d_sobs);
-    (void)hipFree((void*)s->d_param_ptr);
-    (void)hipFree(s->d_send);
-    (void)hipFree(s->d_recv);
-    if (s->ev0) (void)hipEventDestroy(s->ev0);
-    if (s->ev1) (void)hipEventDestroy(s->ev1);
-    delete s;
+    delete s;   // synchronises the evaluator's stream, then frees (~rscm_sampler)
     return RSCM_OK;
 }
 

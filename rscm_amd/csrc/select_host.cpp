@@ -432,7 +432,7 @@ int install_weights(rscm_ens* h, rscm::DevBuf<int64_t> d_new)
     HIPCHK(hipStreamSynchronize(h->stream));
     if (neg) return fail(RSCM_ERR_INVALID, "a member weight is negative");
     if (total > (1ull << 53)) return fail(RSCM_ERR_INVALID, "the member weights of this handle sum to more than 2^53");
-    d_new.install(h->d_weights);
+    h->d_weights = std::move(d_new);
     return RSCM_OK;
 }
 
@@ -548,7 +548,7 @@ int rscm_ens_set_member_groups(rscm_ens* h, const int32_t* group, int32_t on_dev
     HIPCHK(hipMemcpyAsync(&bad, d_flag.get(), sizeof bad, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     if (bad) return fail(RSCM_ERR_INVALID, "a member's group id is outside [-1, %d)", n_groups);
-    d_new.install(h->d_groups);
+    h->d_groups = std::move(d_new);
     h->n_groups = n_groups;
     return RSCM_OK;
     GUARD_END
@@ -572,8 +572,7 @@ int rscm_ens_clear_member_groups(rscm_ens* h)
     if (h->d_groups) {
         if (int rc = set_device(h)) return rc;
         HIPCHK(hipStreamSynchronize(h->stream));
-        (void)hipFree(h->d_groups);
-        h->d_groups = nullptr;
+        h->d_groups.reset();
         h->n_groups = 0;
     }
     return RSCM_OK;

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <stdexcept>
 #include <utility>
 
@@ -102,6 +103,35 @@ hipError_t three_allocations()
     return hipSuccess;
 }
 
+// a handle in small: several owners and an array of four, as rscm_ens has d_* members and d_ind[4]
+struct Handle {
+    DevBuf<double> a, b;
+    DevBuf<int32_t> c;
+    DevBuf<unsigned char> d;
+    DevBuf<double> slots[4];
+};
+
+// "build aside, move in": the member's new contents are allocated in a local; `leave` is a failure before the move
+hipError_t replace_table(Handle& h, size_t n, bool leave)
+{
+    DevBuf<double> d_new;
+    CHK(d_new.alloc(n));
+    if (leave) return hipErrorInvalidValue;
+    h.a = std::move(d_new);
+    return hipSuccess;
+}
+
+// create_handle in small: the object lives in a unique_ptr until everything that can fail has succeeded
+hipError_t create(Handle** out)
+{
+    std::unique_ptr<Handle> h(new Handle());
+    CHK(h->a.alloc(8));
+    CHK(h->c.alloc(8));
+    CHK(h->slots[2].alloc(8));
+    *out = h.release();
+    return hipSuccess;
+}
+
 void thrower()
 {
     DevBuf<double> a;
@@ -165,46 +195,134 @@ void scenarios(bool poison)
         CHECK(!b && c.get() == pa && g_frees == 1 && g_last_freed == pc && g_live == 1);
         DevBuf<double>& self = c;
         c = std::move(self);
-        CHECK(c.get() == pa && g_frees == 1);
+        CHECK(c.get() == pa && c.size() == 4 && g_frees == 1);
     }
     CHECK(g_live == 0 && g_mallocs == 2 && g_frees == 2);
 
-    // release(): nothing is freed, the caller's free brings the count to zero
+    // size() follows alloc, a move and a failed alloc; an empty owner reads as a null pointer
     reset_counts();
-    double* raw = nullptr;
+    {
+        DevBuf<double> a;
+        CHECK(a.size() == 0 && a == nullptr);
+        CHECK(a.alloc(7) == hipSuccess && a.size() == 7);
+        double* p = a;   // the implicit conversion every reader of a handle member goes through
+        CHECK(p == a.get() && a + 1 == p + 1);
+        DevBuf<double> b(std::move(a));
+        CHECK(a.size() == 0 && b.size() == 7);
+        g_fail_at = 1;
+        CHECK(b.alloc(9) == hipErrorOutOfMemory);
+        CHECK(!b && b.size() == 0 && g_frees == 1 && g_last_freed == p && g_live == 0);
+    }
+    CHECK(g_live == 0 && g_frees == 1);
+
+    // reserve(): smaller than, equal to and larger than size() -- no call, no call, one free and one allocation
+    reset_counts();
+    {
+        DevBuf<int64_t> a;
+        CHECK(a.reserve(0) == hipSuccess && !a && g_mallocs == 0);   // nothing asked of an empty owner
+        CHECK(a.reserve(8) == hipSuccess && a.size() == 8 && g_mallocs == 1 && g_frees == 0);
+        int64_t* first = a.get();
+        CHECK(a.reserve(4) == hipSuccess && a.get() == first && a.size() == 8);
+        CHECK(a.reserve(8) == hipSuccess && a.get() == first && a.size() == 8);
+        CHECK(g_mallocs == 1 && g_frees == 0);
+        CHECK(a.reserve(9) == hipSuccess && a.size() == 9);
+        a.get()[8] = 1;   // the whole of it is there
+        CHECK(g_mallocs == 2 && g_frees == 1 && g_last_freed == first && g_live == 1);
+    }
+    CHECK(g_live == 0 && g_frees == 2);
+
+    // reserve() whose allocation fails: empty, size() == 0, the old block freed exactly once (and not again by the destructor)
+    reset_counts();
     {
         DevBuf<double> a;
         CHECK(a.alloc(4) == hipSuccess);
-        raw = a.release();
-        CHECK(!a && raw != nullptr);
+        double* first = a.get();
+        g_fail_at = 1;
+        CHECK(a.reserve(16) == hipErrorOutOfMemory);
+        CHECK(!a && a.get() == nullptr && a.size() == 0 && g_frees == 1 && g_last_freed == first && g_live == 0);
+        CHECK(a.reserve(2) == hipSuccess && a.size() == 2);   // and the owner is usable afterwards
     }
-    CHECK(g_live == 1 && g_frees == 0);
-    CHECK(hipFree(raw) == hipSuccess);
+    CHECK(g_live == 0 && g_mallocs == 3 && g_frees == 2);
+
+    // reset(): frees, leaves the owner empty, and is harmless on an empty one
+    reset_counts();
+    {
+        DevBuf<double> a;
+        a.reset();
+        CHECK(g_frees == 0);
+        CHECK(a.alloc(4) == hipSuccess);
+        a.reset();
+        CHECK(!a && a.size() == 0 && g_frees == 1 && g_live == 0);
+        a.reset();
+        CHECK(g_frees == 1);
+    }
     CHECK(g_live == 0 && g_frees == 1);
 
-    // install(): the slot's old pointer is freed once and the owner no longer frees the new one
+    // move-assignment of a local into a member: the member's old block is freed once, the local ends empty and
+    // no longer frees the new one; into an empty member there is nothing to free
     reset_counts();
-    int32_t* slot = nullptr;
-    CHECK(rscm::dev_malloc(&slot, 4 * sizeof(int32_t)) == hipSuccess);
-    int32_t* old = slot;
     {
-        DevBuf<int32_t> a;
-        CHECK(a.alloc(4) == hipSuccess);
-        int32_t* fresh = a.get();
-        a.install(slot);
-        CHECK(!a && slot == fresh && g_frees == 1 && g_last_freed == old);
+        Handle h;
+        CHECK(h.c.alloc(4) == hipSuccess);
+        int32_t* old = h.c.get();
+        {
+            DevBuf<int32_t> d_new;
+            CHECK(d_new.alloc(6) == hipSuccess);
+            int32_t* fresh = d_new.get();
+            h.c = std::move(d_new);
+            CHECK(!d_new && d_new.size() == 0 && h.c.get() == fresh && h.c.size() == 6 && g_frees == 1 && g_last_freed == old);
+        }
+        CHECK(g_live == 1 && g_frees == 1);
+        {
+            DevBuf<double> d_new;
+            CHECK(d_new.alloc(4) == hipSuccess);
+            h.b = std::move(d_new);
+            CHECK(g_frees == 1 && h.b && h.b.size() == 4);
+        }
+        CHECK(g_live == 2);
+        h.c = DevBuf<int32_t>();   // an empty owner moved in: the member's block goes
+        CHECK(!h.c && g_frees == 2 && g_live == 1);
     }
-    CHECK(g_live == 1 && g_frees == 1);
-    {
-        DevBuf<int32_t> a;   // into an empty slot: nothing to free
-        int32_t* empty = nullptr;
-        CHECK(a.alloc(4) == hipSuccess);
-        a.install(empty);
-        CHECK(g_frees == 1 && empty != nullptr);
-        CHECK(hipFree(empty) == hipSuccess);
-    }
-    CHECK(hipFree(slot) == hipSuccess);
     CHECK(g_live == 0 && g_mallocs == 3 && g_frees == 3);
+
+    // a struct of owners and an array of four, some empty and some full: the destructor frees every block once
+    reset_counts();
+    {
+        Handle h;
+        CHECK(h.a.alloc(3) == hipSuccess && h.d.alloc(5) == hipSuccess);
+        CHECK(h.slots[1].reserve(2) == hipSuccess && h.slots[3].reserve(2) == hipSuccess);
+        CHECK(g_live == 4 && !h.b && !h.c && !h.slots[0] && !h.slots[2]);
+        CHECK(g_fills == (poison ? 4 : 0));
+    }
+    CHECK(g_live == 0 && g_mallocs == 4 && g_frees == 4);
+
+    // build aside, fail before the move: the member still holds its old block and its old size()
+    reset_counts();
+    {
+        Handle h;
+        CHECK(replace_table(h, 4, false) == hipSuccess);
+        double* old = h.a.get();
+        CHECK(replace_table(h, 8, true) == hipErrorInvalidValue);
+        CHECK(h.a.get() == old && h.a.size() == 4 && g_live == 1 && g_mallocs == 2 && g_frees == 1 && g_last_freed != old);
+        g_fail_at = 1;   // ... and so when the allocation aside is what fails
+        CHECK(replace_table(h, 8, false) == hipErrorOutOfMemory);
+        CHECK(h.a.get() == old && h.a.size() == 4 && g_live == 1 && g_frees == 1);
+        CHECK(replace_table(h, 8, false) == hipSuccess);
+        CHECK(h.a.size() == 8 && g_last_freed == old && g_live == 1);
+    }
+    CHECK(g_live == 0);
+
+    // a half-built object in a unique_ptr whose third allocation fails: nothing stays live, nothing is handed out
+    reset_counts();
+    {
+        Handle* made = nullptr;
+        g_fail_at = 3;
+        CHECK(create(&made) == hipErrorOutOfMemory);
+        CHECK(made == nullptr && g_live == 0 && g_mallocs == 3 && g_frees == 2);
+        CHECK(create(&made) == hipSuccess && made != nullptr && g_live == 3);
+        delete made;   // the whole teardown
+    }
+    CHECK(g_live == 0 && g_frees == 5);
 
     // an exception thrown past a live owner
     reset_counts();

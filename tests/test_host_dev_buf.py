@@ -1,8 +1,11 @@
-"""The scoped owner of the host layer's device temporaries, rscm::DevBuf, and rscm::dev_malloc (rscm_amd/csrc/dev_buf.hpp), on the
-host: tests/c_abi/dev_buf_host.cpp includes that header alone, defines hipMalloc, hipFree, hipMemset and hipDeviceSynchronize as
-counting stubs over malloc / free (one of them can fail the k-th allocation) and links no HIP library.  Built with AddressSanitizer
-and UndefinedBehaviorSanitizer as a stand-alone program, so a double free, a use after free or a leak past any of its scenarios --
-scope exit, early return, a failed allocation, moves, release(), install(), an exception -- ends the run."""
+"""The owner of the host layer's device buffers, rscm::DevBuf -- a call's temporaries and the d_* members of the handle, the sampler and
+the lock-step plan -- and rscm::dev_malloc (rscm_amd/csrc/dev_buf.hpp), on the host: tests/c_abi/dev_buf_host.cpp includes that header
+alone, defines hipMalloc, hipFree, hipMemset and hipDeviceSynchronize as counting stubs over malloc / free (one of them can fail the
+k-th allocation) and links no HIP library.  Built with AddressSanitizer and UndefinedBehaviorSanitizer as a stand-alone program, so a
+double free, a use after free or a leak past any of its scenarios ends the run: scope exit, early return, a failed allocation, a
+second alloc, moves, an exception; size() and the read as a pointer; reserve() below, at and above size() and with a failing
+allocation; reset(); move-assignment of a local into a full and into an empty member; a struct of owners with an array of four
+destroyed half full; "build aside, fail before the move"; a half-built object in a unique_ptr whose third allocation fails."""
 import os
 import subprocess
 
