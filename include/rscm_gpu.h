@@ -102,8 +102,11 @@ extern "C" {
  *      rscm_gpu_spectrum_coefficients, rscm_ens_loglik_spectrum_device
  *  18  diagnostic variables: per-member linear combinations of a handle's stored variables (ocean heat content) that every reader of
  *      rows takes by variable id: rscm_ens_define_diagnostic, rscm_ens_diagnostic, rscm_ens_compute_diagnostic,
- *      rscm_ens_clear_diagnostics, rscm_ens_n_diagnostics, RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX */
-#define RSCM_GPU_ABI_MINOR 18
+ *      rscm_ens_clear_diagnostics, rscm_ens_n_diagnostics, RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX
+ *  19  no entry point changed.  rscm_ens_quantile_series runs the radix select of rscm_ens_quantile_rows instead of a sort: the
+ *      same bits, except that where a quantile lands on a zero the sign is the select's (-0.0 orders before +0.0, a function of
+ *      the member set); the sort returned whichever zero sat first among the members, which the contract left unspecified */
+#define RSCM_GPU_ABI_MINOR 19
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -929,7 +932,10 @@ RSCM_API int rscm_ens_summary_series(rscm_ens* h, int32_t var_id, int32_t t_begi
  * NaN members left out, virtual index (n - 1) q, numpy's interpolation -- so the results carry numpy's
  * bits.  out[(t - t_begin)][n_q]; count[(t - t_begin)] (or NULL) = members that are not NaN.  Rows beyond
  * the current time index: count 0, quantiles NaN.  An extension: the reference has no ensemble
- * statistics; q in [0, 1]. */
+ * statistics; q in [0, 1], any n_q >= 1.  It is rscm_ens_quantile_rows with stride 1 on a handle that stores
+ * whole series (any other: RSCM_ERR_STATE), run over blocks of the list where n_q > 128: the same radix select,
+ * the same bits.  Where a quantile lands on a zero, -0.0 orders before +0.0, so the sign is a function of the
+ * member set and not of where the members sit. */
 RSCM_API int rscm_ens_quantile_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t n_q,
                                       const double* q, double* out, double* count);
 
@@ -937,8 +943,7 @@ RSCM_API int rscm_ens_quantile_series(rscm_ens* h, int32_t var_id, int32_t t_beg
 /* The quantiles rscm_ens_quantile_series defines (numpy.nanquantile, method "linear", the same bits) of stored variable var_id
  * over the rows t_begin, t_begin + t_stride, ... < t_end, read wherever each row is resident: full storage, the window of a
  * RSCM_FLAG_WINDOWED handle or its output store.  No sort and no member-sized scratch: a radix select of eight passes, each
- * one histogram of 256 int64 counts per row and target (two targets per quantile).  Signed zeros: -0.0 orders before +0.0
- * (rscm_ens_quantile_series' sort keeps the two in member order, so a zero result may carry the other sign there).
+ * one histogram of 256 int64 counts per row and target (two targets per quantile).
  * out[rows][n_q]; count[rows] (or NULL) = members that are not NaN.  Rows beyond the current time index: count 0, quantiles
  * NaN.  A row that is not resident (slid out of the window and not in the output store), or any row but 0 of a
  * RSCM_FLAG_NO_SERIES handle: RSCM_ERR_STATE.  q in [0, 1], 1 <= n_q <= 128. */

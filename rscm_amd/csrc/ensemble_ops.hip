@@ -213,41 +213,8 @@ __device__ __forceinline__ Stat4 block_reduce(Stat4 v)
     return v;  // valid in thread 0
 }
 
-__global__ __launch_bounds__(kBlock) void summary_partial_kernel(const double* row, int64_t n,
-                                                                 double* partial)
-{
-    Stat4 v = {0.0, 0.0, __builtin_inf(), -__builtin_inf()};
-    const int64_t stride = (int64_t)gridDim.x * kBlock;
-    for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < n; i += stride) {
-        const double x = row[i];
-        if (is_finite(x)) v = stat_merge(v, {1.0, x, x, x});
-    }
-    v = block_reduce(v);
-    if (threadIdx.x == 0) {
-        partial[4 * blockIdx.x + 0] = v.cnt;
-        partial[4 * blockIdx.x + 1] = v.sum;
-        partial[4 * blockIdx.x + 2] = v.mn;
-        partial[4 * blockIdx.x + 3] = v.mx;
-    }
-}
-
-__global__ __launch_bounds__(kBlock) void summary_final_kernel(const double* partial,
-                                                               int32_t n_blocks, double* out)
-{
-    Stat4 v = {0.0, 0.0, __builtin_inf(), -__builtin_inf()};
-    for (int32_t b = threadIdx.x; b < n_blocks; b += kBlock)
-        v = stat_merge(v, {partial[4 * b], partial[4 * b + 1], partial[4 * b + 2], partial[4 * b + 3]});
-    v = block_reduce(v);
-    if (threadIdx.x == 0) {
-        out[0] = v.cnt;
-        out[1] = v.sum;
-        out[2] = v.mn;
-        out[3] = v.mx;
-    }
-}
-
-// The same reduction for many time rows in one launch: blockIdx.y selects the row, the block
-// layout along x is the one launch_summary uses, so every row gets the bits a single-row call gives.
+// count / sum / min / max of the finite members of one row or of many time rows in one launch: blockIdx.y selects the row,
+// and the block layout along x depends on n alone, so a row gets the same bits whatever the number of rows beside it.
 __global__ __launch_bounds__(kBlock) void summary_rows_partial_kernel(const double* rows, int64_t n, double* partial)
 {
     const double* row = rows + (size_t)blockIdx.y * n;
@@ -455,16 +422,6 @@ hipError_t launch_loglik(const LoglikArgs& a, hipStream_t s)
 }
 
 int32_t summary_blocks(int64_t n) { return (int32_t)grid_for(n, 1024); }
-
-hipError_t launch_summary(const double* row, int64_t n, double* partial, int32_t n_blocks,
-                          double* out, hipStream_t s)
-{
-    hipLaunchKernelGGL(summary_partial_kernel, dim3(n_blocks), dim3(kBlock), 0, s, row, n, partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(summary_final_kernel, dim3(1), dim3(kBlock), 0, s, partial, n_blocks, out);
-    return hipGetLastError();
-}
 
 // rows: n_rows consecutive [n] rows; partial: [n_rows][n_blocks][4]; out: [n_rows][4]
 hipError_t launch_summary_rows(const double* rows, int64_t n, int32_t n_rows, double* partial, int32_t n_blocks,

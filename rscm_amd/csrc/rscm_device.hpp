@@ -833,15 +833,10 @@ struct WindowBatch {
     WindowOp ops[kMaxWindowOps];
 };
 hipError_t launch_window_batch(const WindowBatch& batch, int32_t n_ops, hipStream_t s);
-// partial[4*n_blocks] then reduced into out[4] = {count_finite, sum, min, max}
-hipError_t launch_summary(const double* row, int64_t n, double* partial, int32_t n_blocks,
-                          double* out, hipStream_t s);
+// per row of rows[n_rows][n]: partial[n_rows][n_blocks][4], then reduced into out[n_rows][4] = {count_finite, sum, min, max}
 int32_t summary_blocks(int64_t n);
 hipError_t launch_summary_rows(const double* rows, int64_t n, int32_t n_rows, double* partial, int32_t n_blocks,
                                double* out, hipStream_t s);
-// per row of rows[n_rows][N]: out[r] = {count of non-NaN, quantile q[0], ..., q[n_q-1]} (numpy nanquantile, linear)
-hipError_t launch_quantile_rows(const double* rows, int64_t N, int32_t n_rows, const double* d_q, int32_t n_q, double* d_out,
-                                hipStream_t s);
 // multi-pass radix select (select.hip): 8-bit digits, eight passes; one histogram of kSelBins int64 counts per row in pass 0, per
 // (row, target) later.  Unweighted, target 2k / 2k + 1 of a row is the lower / upper order statistic of quantile k; weighted
 // (int64 member weights d_w[N], numpy's "inverted_cdf"), the histograms sum weights and there is one target per quantile.
@@ -865,8 +860,8 @@ hipError_t launch_groups_check(const int32_t* d_group, int64_t N, int32_t n_grou
 // d_over non-null: the weighted commit, where d_count is the row's weight W and a row with W > 2^53 sets *d_over and gets NaN
 hipError_t launch_select_commit(const int64_t* d_hist, int32_t pass, int32_t n_rows, int32_t n_t, const double* d_q, int64_t* d_count,
                                 uint64_t* d_prefix, int64_t* d_rank, int32_t* d_over, hipStream_t s);
-// after the last commit: d_out[r] = {count (weighted: W), quantile q[0], ..., q[n_q-1]} from the selected keys, as
-// launch_quantile_rows (weighted: the values of the keys)
+// after the last commit: d_out[r] = {count (weighted: W), quantile q[0], ..., q[n_q-1]} from the selected keys: numpy's
+// nanquantile, method "linear" (weighted: the values of the keys)
 hipError_t launch_select_finish(const int64_t* d_count, const uint64_t* d_keys, int32_t n_rows, int32_t n_q, const double* d_q,
                                 bool weighted, double* d_out, hipStream_t s);
 // the member weights (weights.hip):

@@ -1614,40 +1614,6 @@ int rscm_ens_summary_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_
     GUARD_END
 }
 
-int rscm_ens_quantile_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t n_q, const double* q, double* out,
-                             double* count)
-{
-    GUARD_BEGIN
-    NEED(h);
-    if (var_id < 1 || var_id >= h->V || t_begin < 0 || t_end > h->T || t_begin > t_end || !out || n_q < 1 || !q)
-        return fail(RSCM_ERR_INVALID, "bad variable / time range / quantile list");
-    for (int32_t k = 0; k < n_q; ++k)
-        if (!(q[k] >= 0.0 && q[k] <= 1.0)) return fail(RSCM_ERR_INVALID, "Quantiles must be in the range [0, 1], got %g", q[k]);
-    if (h->windowed || h->rows != h->T) return fail(RSCM_ERR_STATE, "this handle does not store whole series (RSCM_FLAG_NO_SERIES / RSCM_FLAG_WINDOWED)");
-    const int32_t n_rows = t_end - t_begin;
-    const int32_t computed = std::max(0, std::min(t_end, h->time_index + 1) - t_begin);
-    for (int32_t r = computed; r < n_rows; ++r) {
-        for (int32_t k = 0; k < n_q; ++k) out[(size_t)r * n_q + k] = std::numeric_limits<double>::quiet_NaN();
-        if (count) count[r] = 0.0;
-    }
-    if (computed == 0) return RSCM_OK;
-    if (int rc = set_device(h)) return rc;
-    std::vector<double> host((size_t)computed * (n_q + 1));
-    rscm::DevBuf<double> d_q, d_out;
-    HIPCHK(d_q.alloc((size_t)n_q));
-    HIPCHK(d_out.alloc(host.size()));
-    HIPCHK(hipMemcpyAsync(d_q.get(), q, (size_t)n_q * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(rscm::launch_quantile_rows(h->series(var_id) + (size_t)t_begin * h->N, h->N, computed, d_q.get(), n_q, d_out.get(), h->stream));
-    HIPCHK(hipMemcpyAsync(host.data(), d_out.get(), host.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    for (int32_t r = 0; r < computed; ++r) {
-        if (count) count[r] = host[(size_t)r * (n_q + 1)];
-        for (int32_t k = 0; k < n_q; ++k) out[(size_t)r * n_q + k] = host[(size_t)r * (n_q + 1) + 1 + k];
-    }
-    return RSCM_OK;
-    GUARD_END
-}
-
 int rscm_ens_summary(rscm_ens* h, int32_t var_id, int32_t tidx, double out[4])
 {
     GUARD_BEGIN
@@ -1665,7 +1631,7 @@ int rscm_ens_summary(rscm_ens* h, int32_t var_id, int32_t tidx, double out[4])
     const int32_t nb = rscm::summary_blocks(h->N);
     const double* row = h->row_ptr(var_id, tidx);
     if (!row) return fail(RSCM_ERR_STATE, "row %d of variable %d is not resident on this handle", tidx, var_id);
-    HIPCHK(rscm::launch_summary(row, h->N, h->d_partial, nb, h->d_out4, h->stream));
+    HIPCHK(rscm::launch_summary_rows(row, h->N, 1, h->d_partial, nb, h->d_out4, h->stream));
     HIPCHK(hipMemcpyAsync(out, h->d_out4, 4 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     return RSCM_OK;

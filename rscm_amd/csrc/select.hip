@@ -1,16 +1,14 @@
 // Exact ensemble quantiles by a multi-pass radix select over resident rows, for gfx950 (MI355X).
 //
-// The same numbers as quantile.hip (numpy.nanquantile, method "linear"), reached without sorting and
-// without member-sized scratch: every double maps to an order-preserving 64-bit key (-0.0 before +0.0,
-// NaNs of either sign left out), and each target order statistic is found
+// numpy.nanquantile, method "linear", per row (rscm_ens_quantile_series, rscm_ens_quantile_rows and the staged
+// select), reached without sorting and without member-sized scratch: every double maps to an order-preserving
+// 64-bit key (-0.0 before +0.0, NaNs of either sign left out), and each target order statistic is found
 // digit by digit from the top.  Pass p histograms digit p (8 bits) of the members whose key matches a
 // target's prefix of p digits; a commit then picks, per (row, target), the bucket holding the target's
 // remaining rank and extends the prefix.  Eight passes give the whole key.
 //
-// Signed zeros: rocPRIM's radix sort (quantile.hip) takes -0.0 and +0.0 as one key and keeps them in
-// member order, so where a quantile lands on a zero its sign depends on where the members sit.  The
-// select's order (-0.0 first) depends on the member set alone, which is what lets shards combine; the
-// two paths agree bit for bit everywhere else.
+// Signed zeros: the order of the keys (-0.0 first) makes the sign of a zero result a function of the member
+// set alone, not of where the members sit, which is what lets shards combine.
 //
 // Everything summed across workgroups (and, by the caller, across ranks) is an int64 count or weight: integer
 // sums are exact and independent of their order, so the result does not depend on the block count,
@@ -311,8 +309,9 @@ __global__ void select_commit_kernel(const long long* __restrict__ hist, int32_t
 }
 
 // out[r][0] = count (kW: W), out[r][1 + k] = quantile q[k], NaN for a row without members.  kW: the value of the selected
-// key.  Unweighted: the two order statistics from their full keys, then numpy's _lerp exactly as quantile_kernel
-// (quantile.hip) applies it.
+// key.  Unweighted: the two order statistics a, b of numpy's virtual index (n - 1) q (_compute_virtual_index(n, q, 1, 1)) from
+// their full keys, then numpy's _lerp (function_base.py) with its own roundings, so the result carries numpy's bits:
+// a + (b - a) g, from b's side for g >= 0.5, and a itself where b - a == 0 (which also keeps inf - inf out).
 template <bool kW>
 __global__ void select_finish_kernel(const int64_t* __restrict__ count, const uint64_t* __restrict__ keys, int32_t n_rows, int32_t n_q,
                                      const double* __restrict__ q, double* __restrict__ out)

@@ -1,4 +1,4 @@
-// Host side of the staged quantile select (rscm_ens_select_* and rscm_ens_quantile_rows; kernels in select.hip), of its weighted
+// Host side of the staged quantile select (rscm_ens_select_*, rscm_ens_quantile_rows and rscm_ens_quantile_series; kernels in select.hip), of its weighted
 // form (rscm_ens_select_begin_weighted, rscm_ens_weighted_quantile_rows), of the flagged and vector forms
 // (rscm_ens_quantile_rows_ex, rscm_ens_select_begin_ex: anomalies against the handle's baseline; rscm_ens_quantile_vectors,
 // rscm_ens_select_begin_vectors: device vectors of N doubles as rows) and of the member weights it reads (weights.hip).
@@ -13,6 +13,7 @@
 // The grouped select (RSCM_SELECT_GROUPED) is the same again with (row, group) as the row of the commit and finish launches: the
 // histogram pass counts each member into its own group's histograms (select.hip), the buffers are [rows][n_groups][...], and
 // count, prefix, rank and out have n_comp x n_groups rows.  The member groups themselves (rscm_ens_set_member_groups) are at the end.
+#include <algorithm>
 #include <cmath>
 #include <limits>
 #include <memory>
@@ -377,6 +378,29 @@ int rscm_ens_quantile_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t
     GUARD_BEGIN
     NEED(h);
     return quantile_rows(h, var_id, t_begin, t_end, t_stride, n_q, q, out, count, 0);
+    GUARD_END
+}
+
+int rscm_ens_quantile_series(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t n_q, const double* q, double* out,
+                             double* count)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (var_id < 1 || var_id >= h->V || t_begin < 0 || t_end > h->T || t_begin > t_end || !out || n_q < 1 || !q)
+        return fail(RSCM_ERR_INVALID, "bad variable / time range / quantile list");
+    for (int32_t k = 0; k < n_q; ++k)
+        if (!(q[k] >= 0.0 && q[k] <= 1.0)) return fail(RSCM_ERR_INVALID, "Quantiles must be in the range [0, 1], got %g", q[k]);
+    if (h->windowed || h->rows != h->T) return fail(RSCM_ERR_STATE, "this handle does not store whole series (RSCM_FLAG_NO_SERIES / RSCM_FLAG_WINDOWED)");
+    if (t_begin == t_end) return RSCM_OK;
+    // any n_q: the select over consecutive blocks of the list, each block's columns into out[row][n_q]; every block counts alike
+    const size_t n_rows = (size_t)(t_end - t_begin);
+    std::vector<double> part(n_rows * (size_t)std::min(n_q, kMaxSelectQuantiles));
+    for (int32_t k0 = 0; k0 < n_q; k0 += kMaxSelectQuantiles) {
+        const int32_t nk = std::min(n_q - k0, kMaxSelectQuantiles);
+        if (int rc = quantile_rows(h, var_id, t_begin, t_end, 1, nk, q + k0, part.data(), k0 == 0 ? count : nullptr, 0)) return rc;
+        for (size_t r = 0; r < n_rows; ++r) std::copy_n(&part[r * nk], nk, &out[r * n_q + k0]);
+    }
+    return RSCM_OK;
     GUARD_END
 }
 

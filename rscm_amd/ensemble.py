@@ -556,9 +556,10 @@ class Ensemble:
 
     def quantile_rows(self, var, q, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
                       weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
-        """``quantile_series``'s numbers (the same bits) over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any
-        storage layout: full series, the window of a windowed handle or its output store (rscm_ens_quantile_rows_ex: a radix
-        select, no sort).  Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``.
+        """``quantile_series``'s numbers over the rows ``t_begin, t_begin + t_stride, ... < t_end`` of any storage layout: full
+        series, the window of a windowed handle or its output store (rscm_ens_quantile_rows_ex: the radix select that
+        ``quantile_series`` runs on full storage, so the same bits, signed zeros included; up to 128 quantiles a call).
+        Returns ``{"count": [rows], "quantiles": [rows][len(q)]}``.
 
         ``weighted``: ``numpy.nanquantile(row, q, weights=w, method="inverted_cdf")`` with the member weights
         (``set_member_weights`` / ``set_weights_from_loglik``; RSCM_SELECT_WEIGHTED).  Returns

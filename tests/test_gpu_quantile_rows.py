@@ -1,6 +1,6 @@
 """GPU tier: rscm_ens_quantile_rows and the staged select (csrc/select.hip) -- exact ensemble quantiles over any storage layout
-and over shards of one member set.  The oracle is numpy.nanquantile; on full storage the result must also carry the bits of
-rscm_ens_quantile_series (the sort-based path), signed zeros included."""
+and over shards of one member set.  The oracle is numpy.nanquantile; rscm_ens_quantile_series runs the same select on full
+storage and must carry the same bits, signed zeros included, for any number of quantiles."""
 import numpy as np
 import pytest
 
@@ -22,14 +22,6 @@ def ra():
 
 def _bits_equal(a, b):
     return np.array_equal(np.asarray(a).view(np.uint64), np.asarray(b).view(np.uint64))
-
-
-def _sort_bits_equal(select, sort):
-    """The select against rscm_ens_quantile_series: the same bits, except the sign of a zero result.  rocPRIM's radix sort takes
-    -0.0 and +0.0 as one key and keeps them in member order, so which zero the sort returns depends on where the members sit; the
-    select orders -0.0 before +0.0 (a function of the member set alone -- what makes a sharded select exact)."""
-    a, b = np.asarray(select), np.asarray(sort)
-    return bool(((a.view(np.uint64) == b.view(np.uint64)) | ((a == 0.0) & (b == 0.0))).all())
 
 
 def _nanq(rows, q):
@@ -76,7 +68,7 @@ def _two_layer(ra, n, P=None, t=None, steps=None):
 
 @pytest.mark.parametrize("n", [70_001, 4099, 3, 1])
 def test_quantile_rows_equals_quantile_series_and_numpy(ra, n):
-    """Full storage: the sort's bits (signed zeros included) and numpy's numbers, on adversarial rows written with set_state;
+    """Full storage: quantile_series' bits (signed zeros included) and numpy's numbers, on adversarial rows written with set_state;
     N odd (every other row starts 8-byte aligned), not a multiple of 64 or of the block; rows past the time index empty."""
     rng = np.random.default_rng(n)
     with _two_layer(ra, n, steps=60) as e:
@@ -84,7 +76,7 @@ def test_quantile_rows_equals_quantile_series_and_numpy(ra, n):
             e.set_state(1, 2 + k, row)
         got = e.quantile_rows(1, Q)
         ref = e.quantile_series(1, Q)
-        assert _sort_bits_equal(got["quantiles"], ref["quantiles"]) and np.array_equal(got["count"], ref["count"])
+        assert _bits_equal(got["quantiles"], ref["quantiles"]) and np.array_equal(got["count"], ref["count"])
         ts = e.get_series(1)
         assert np.array_equal(got["quantiles"][:61], _nanq(ts[:61], Q), equal_nan=True)
         assert np.array_equal(got["count"][:61], (~np.isnan(ts[:61])).sum(axis=1))
@@ -96,12 +88,75 @@ def test_quantile_rows_equals_quantile_series_and_numpy(ra, n):
         assert e.quantile_rows(1, Q, 5, 5)["quantiles"].shape == (0, len(Q))
         if n >= 3:                                                          # the select's order of zeros: -0.0 before +0.0
             e.set_state(1, 20, np.where(np.arange(n) % 2 == 0, 0.0, -0.0))
-            z = e.quantile_rows(1, [0.0, 1.0], 20, 21)["quantiles"][0]
-            assert np.signbit(z[0]) and not np.signbit(z[1])
+            for z in (e.quantile_rows(1, [0.0, 1.0], 20, 21)["quantiles"][0], e.quantile_series(1, [0.0, 1.0], 20, 21)["quantiles"][0]):
+                assert np.signbit(z[0]) and not np.signbit(z[1])
         with pytest.raises(Exception, match="Quantiles must be in the range"):
             e.quantile_rows(1, [1.5])
         with pytest.raises(Exception, match="bad time range"):
             e.quantile_rows(1, Q, 0, 10, 0)
+
+
+@pytest.mark.parametrize("n_q", [129, 300])
+def test_quantile_series_takes_more_quantiles_than_one_select(ra, n_q):
+    """quantile_series over a list longer than the select's 128 quantiles: numpy's numbers, the bits of quantile_rows called on
+    the same list in pieces of at most 128, and the non-NaN count, on adversarial rows (N odd, no multiple of 64 or the block)."""
+    n = 4099
+    rng = np.random.default_rng(n_q)
+    q = np.concatenate([[0.0, 1.0, 0.5, 0.5, 1.0, 0.0, 1e-12], rng.random(n_q - 7)])
+    q[127] = q[128] = 0.0                                                   # repeated across the first block boundary
+    q[-1] = 1.0
+    with _two_layer(ra, n, steps=12) as e:
+        for k, row in enumerate(_adversarial(rng, n)[:8]):
+            e.set_state(1, 2 + k, row)
+        rows = e.get_series(1)[2:10]
+        got = e.quantile_series(1, q, 2, 10)
+        assert got["quantiles"].shape == (8, n_q)
+        assert np.array_equal(got["quantiles"], _nanq(rows, q), equal_nan=True)
+        pieces = [e.quantile_rows(1, q[k:k + 128], 2, 10) for k in range(0, n_q, 128)]
+        assert _bits_equal(got["quantiles"], np.concatenate([p["quantiles"] for p in pieces], axis=1))
+        assert np.array_equal(got["count"], (~np.isnan(rows)).sum(axis=1))
+        assert all(np.array_equal(p["count"], got["count"]) for p in pieces)
+
+
+def test_quantile_series_leaves_a_staged_select_alone(ra):
+    """A staged select three passes in, quantile_series on another variable and range, then the staged select's other five
+    passes: both carry the bits they have when computed alone."""
+    n = 4099
+    rng = np.random.default_rng(11)
+    with _two_layer(ra, n, steps=60) as e:
+        for k, row in enumerate(_adversarial(rng, n)):
+            e.set_state(1, 2 + k, row)
+        alone_rows, alone_series = e.quantile_rows(1, Q, 0, 20), e.quantile_series(2, Q, 30, 70)
+        with e.select(1, Q, 0, 20) as s:
+            for _ in range(3):
+                assert s.next_pass() is not None
+                s.commit()
+            series = e.quantile_series(2, Q, 30, 70)
+            while s.next_pass() is not None:
+                s.commit()
+            staged = s.result()
+        for got, want in ((staged, alone_rows), (series, alone_series)):
+            assert _bits_equal(got["quantiles"], want["quantiles"]) and np.array_equal(got["count"], want["count"])
+
+
+def test_quantile_series_refusals_keep_code_and_text(ra):
+    """What quantile_series refuses, with the code and text it always had: handles without whole series are RSCM_ERR_STATE,
+    a bad range or an empty quantile list RSCM_ERR_INVALID; an empty range is a success of no rows."""
+    from rscm_amd import RscmGpuError
+    t = axis_values(1750, 1830)
+    b = np.append(t, t[-1] + 1.0)
+    for kw in (dict(window_rows=8), dict(store_series=False)):
+        with ra.Ensemble(ra.KIND_TWO_LAYER, 3, b, **kw) as e:
+            with pytest.raises(RscmGpuError, match="does not store whole series") as err:
+                e.quantile_series(1, Q)
+            assert err.value.code == 2                    # RSCM_ERR_STATE
+    with _two_layer(ra, 3, steps=10) as e:
+        for bad in (lambda: e.quantile_series(1, Q, 7, 5), lambda: e.quantile_series(1, [])):
+            with pytest.raises(RscmGpuError, match="bad variable / time range / quantile list") as err:
+                bad()
+            assert err.value.code == 1                    # RSCM_ERR_INVALID
+        empty = e.quantile_series(1, Q, 5, 5)
+        assert empty["quantiles"].shape == (0, len(Q)) and empty["count"].shape == (0,)
 
 
 def _staged_sum(parts, q, t_begin=0, t_end=None, t_stride=1):
@@ -157,7 +212,7 @@ def test_two_handles_summing_their_histograms_equal_the_whole(ra, split):
                 s.next_pass()
             with pytest.raises(Exception, match="still to run"):
                 s.result()
-            assert _sort_bits_equal(a.quantile_rows(1, Q)["quantiles"], a.quantile_series(1, Q)["quantiles"])   # untouched by it
+            assert _bits_equal(a.quantile_rows(1, Q)["quantiles"], a.quantile_series(1, Q)["quantiles"])   # untouched by it
 
 
 def _chain():
