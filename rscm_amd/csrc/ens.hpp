@@ -1,7 +1,9 @@
-// Host-side internals shared by the translation units of librscm_gpu.so (rscm_gpu.cpp: handles, validation,
-// marshalling; launch_host.cpp: one launch range of one handle; lockstep.cpp: the lock-step scheduler of component graphs;
-// loglik_host.cpp: the likelihoods).  Not part of the boundary
-// (include/rscm_gpu.h) and not visible outside the library (-fvisibility=hidden).
+// Host-side internals shared by the translation units of librscm_gpu.so (rscm_gpu.cpp: handles, parameters, forcing, links,
+// marshalling; kind_config.cpp: what the host builds from a kind's parameters and time axis; state_host.cpp: a handle's state in time
+// -- initial values, time index, checkpoint, branch, rewind; window_host.cpp: the windowed storage; noise_host.cpp: the forcing-noise
+// setting; selftest_host.cpp: the device self-tests; launch_host.cpp: one launch range of one handle; lockstep.cpp: the lock-step
+// scheduler of component graphs; loglik_host.cpp: the likelihoods).  Not part of the boundary (include/rscm_gpu.h) and not visible
+// outside the library (-fvisibility=hidden).
 // Device allocation -- rscm::dev_malloc and rscm::DevBuf, the owner of every device buffer of the host layer, a call's
 // temporaries and the d_* members of the handle, the sampler and the lock-step plan alike -- lives in dev_buf.hpp, which this
 // header includes.  Nothing here frees device memory by hand: `delete` of a handle is its whole teardown.
@@ -25,20 +27,25 @@
 #include <vector>
 
 #include "dev_buf.hpp"
+#include "internal_state.hpp"
 #include "kinds.hpp"
 #include "rscm_device.hpp"
+#include "structural_rows.hpp"
 #include "two_layer_year_facts.hpp"
 
 // thread-local error text behind rscm_gpu_last_error(); returns `code`
 int fail(int code, const char* fmt, ...);
 
-#define HIPCHK(expr)                                                                       \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return fail(e_ == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE,      \
-                        "%s failed: %s", #expr, hipGetErrorString(e_));                    \
+inline int hip_code(hipError_t e) { return e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE; }
+#define HIPCHK(expr)                                                                                     \
+    do {                                                                                                 \
+        hipError_t e_ = (expr);                                                                          \
+        if (e_ != hipSuccess) return fail(hip_code(e_), "%s failed: %s", #expr, hipGetErrorString(e_));  \
     } while (0)
+
+// n fresh elements in buf (grow: room for n, what it holds kept where that is enough -- DevBuf::reserve), or the failure under the
+// caller's words for what could not be had: "<what>: out of memory" (rscm_gpu.cpp)
+__attribute__((format(printf, 4, 5))) int alloc_or_fail(rscm::DevBuf<double>& buf, size_t n, bool grow, const char* what, ...);
 
 #define GUARD_BEGIN try {
 #define GUARD_END                                                                          \
@@ -131,7 +138,7 @@ struct rscm_ens : EnsQueues {
     rscm::DevBuf<double> d_series;  // [(V-1)][T][N], variable v at slot v-1
     rscm::DevBuf<double> d_forcing; // [S][n_inputs][T]
     int32_t n_inputs = 1;        // rows per scenario of the shared input block
-    // The forcing-noise setting (set_noise, rscm_gpu.cpp, behind rscm_ens_set_forcing_noise* and rscm_ens_clear_forcing_noise): member i
+    // The forcing-noise setting (set_noise, noise_host.cpp, behind rscm_ens_set_forcing_noise* and rscm_ens_clear_forcing_noise): member i
     // is forced by F + e_t(noise_seed, noise_offset + i) of the kind noise_kind (rscm::kNoiseKind*; TwoLayerArgs, rscm_device.hpp).
     // noise_sigma: white and red (0 otherwise); noise_phi: red (0 otherwise); the per-member kind reads both from parameter rows.
     // The kinds that keep state (noise_red()): e is a pure function of (seed, sigma, phi, member id, t), and d_noise_state [N] caches
@@ -148,32 +155,34 @@ struct rscm_ens : EnsQueues {
     int32_t n_comp = 0;          // rscm_ens_create_mix: forcing components K (then n_inputs == K and P == 6 + K), 0 for every other handle
     // RSCM_FLAG_NOISE_PARAMS: the handle has the parameter rows noise_sigma_row() and noise_phi_row() -- a fact of its shape, whatever
     // the setting.  The per-member kind forms e from those rows as they stand at launch, so the cache is only as good as the rows.
-    // The two rules, each kept in one place:
-    //   params_written()      whatever writes a parameter row calls it (rscm_ens_set_params[_aos], rscm_ens_sample_lhs,
-    //                         rscm_ens_gather_members into the handle; a restore goes through rscm_ens_set_params): the index is dropped
-    //   noise_cache_kept()    a run leaves its index behind only where nobody can write the rows unseen: never once
-    //                         rscm_ens_params_devptr has handed the block out
+    // A run leaves its index behind only where nobody can write the rows unseen: never once rscm_ens_params_devptr has handed the
+    // block out (noise_cache_kept()); whatever writes a parameter row from the host drops it (params_written(), below).
     bool noise_rows = false;
     int32_t noise_sigma_row() const { return noise_rows ? 6 + n_comp : -1; }
     int32_t noise_phi_row() const { return noise_rows ? 6 + n_comp + 1 : -1; }
     bool noise_red() const { return rscm::noise_kind_keeps_state(noise_kind); }   // the settings that cache e
     bool noise_cache_kept() const { return !(noise_kind == rscm::kNoiseKindMembers && params_exposed); }
-    void params_written()
-    {
-        params_may_change();
-        rows_written();
-    }
-    // ... and what rscm_ens_params_devptr does for the writes it makes possible: those are the caller's to follow (no epoch moves)
-    void params_may_change()
-    {
-        derived_dirty = true;
-        if (noise_kind == rscm::kNoiseKindMembers) noise_state_index = -1;
-    }
+    // The rules that drop what the handle has cached about its parameter block and about where it stands.  Nothing outside them assigns
+    // uniform_rows, derived_dirty or time_index but ensure_derived and step_finish (launch_host.cpp) and a fused launch's provisional index.
+    // The parameter block was written from the host and these rows hold one value for every member -- none once the block has been
+    // handed out: rscm_ens_set_params[_aos] (a restore goes through it), rscm_ens_sample_lhs, rscm_ens_gather_members into the handle
+    void params_written(uint64_t uniform) { uniform_rows = params_exposed ? 0 : uniform; params_may_change(); rows_written(); }
+    // A kernel is about to write these rows (~0: any), the samplers' proposals; the diagnostics' epoch moves with the run that follows
+    void params_kernel_writes(uint64_t rows) { uniform_rows &= ~rows; if (rows) derived_dirty = true; }
+    // rscm_ens_params_devptr: the writes it makes possible are the caller's to follow (no epoch moves)
+    void expose_params() { params_exposed = true; uniform_rows = 0; params_may_change(); }
+    void params_may_change() { derived_dirty = true; if (noise_kind == rscm::kNoiseKindMembers) noise_state_index = -1; }
+    // The stepper was put at index k from outside: rscm_ens_set_time_index, _set_internal_state, _rewind, _clear_series, the gather, the samplers' resets
+    void put_at(int32_t k) { time_index = k; rows_written(); ocean_forget_partial_sums(); }
+    // rscm_ens_set_initial, the one entry point that moves the index (to 0) and keeps OceanCarbon's sums.  The next launch starts at step 0
+    // (step_check), where ocean_advance (launch_host.cpp) never continues a parked tile -- only at a step after the tile's first -- so `part`
+    // is the same either way; but mode sums standing at 0 (after an empty run [0, 0)) are served, where put_at(0) would set `rebuild`.  Kept
+    void initial_written() { time_index = 0; rows_written(); }
     // Diagnostic variables (diagnostic_host.cpp; kernel in diagnostic.hip): per-member linear combinations of the stored variables with
     // ids V, V + 1, ..., their rows [held][N] for t_begin, t_begin + t_stride, ... in a store of their own.  The rows are a snapshot:
     // write_epoch moves with everything that can change a stored row, a parameter row or the time index (rows_written(): step_finish
-    // for every run, params_written(), launch_loglik for the fused runs, set_noise, and the entry points that move the time index or
-    // write a state), and a store serves its rows only at the epoch it was computed at.
+    // for every run, params_written(), launch_loglik for the fused runs, set_noise, put_at() / initial_written() and the entry points
+    // that write a state), and a store serves its rows only at the epoch it was computed at.
     struct Diagnostic {
         int32_t n_terms = 0;
         int32_t var[RSCM_DIAG_MAX_TERMS] = {}, row[RSCM_DIAG_MAX_TERMS] = {};
@@ -323,44 +332,12 @@ struct rscm_ens : EnsQueues {
     bool reads_end(const Link& l) const { return info().reads_end || l.off == 1; }
     // OceanCarbon: the sums parked for a split tile and the running mode sums no longer belong to where the handle stands
     void ocean_forget_partial_sums() { ocean_tile_base = -1; ocean_modes_at = -1; }
+    // The internal component state at index k (internal_state.hpp; none while the columns or the ring do not exist), the buffers of its
+    // runs, and whether the configuration it belongs to stands
+    rscm::StateRuns state_runs(int32_t k) const { return rscm::internal_state_runs(kind, k, {d_ocean ? udeb_n_layers : 0, rscm::kUdebScalars, ocean_steps, d_ocean_hist ? ocean_hist_rows : 0}); }
+    double* state_buf(rscm::StateBuf b) const { return b == rscm::StateBuf::UdebColumns ? d_ocean : b == rscm::StateBuf::UdebScalars ? d_scal : b == rscm::StateBuf::UdebHistory ? d_hist : d_ocean_hist; }
+    bool internal_ready() const { return kind == RSCM_KIND_UDEB ? udeb_ready : kind == RSCM_KIND_OCEAN_CARBON ? ocean_ready : true; }
 };
-
-// Parameter rows from which the HOST derives state when rscm_ens_set_params / rscm_ens_sample_lhs configure an ensemble
-// (ClimateUDEB's geometry tables and look-back windows, OceanCarbon's impulse-response table and mode fit, GhgForcing's
-// method switch, the N2O look-back): marked [u] in rscm_gpu.h.  They must hold ONE value for all members, and nothing that
-// writes parameters on the device (the samplers' proposals) may touch them -- the derived tables would silently stay those
-// of the base value, where the reference rebuilds the component for every parameter vector (model_runner.rs:257-266).
-// Returns the row's name for the error text, or nullptr.
-inline const char* structural_row(int32_t kind, int32_t row)
-{
-    if (kind == RSCM_KIND_UDEB) {
-        switch (row) {
-            case RSCM_UD_P_N_LAYERS: return "n_layers";
-            case RSCM_UD_P_MIXED_LAYER_DEPTH: return "mixed_layer_depth";
-            case RSCM_UD_P_LAYER_THICKNESS: return "layer_thickness";
-            case RSCM_UD_P_DEPTH_DEPENDENT_AREA: return "depth_dependent_area";
-            case RSCM_UD_P_LAND_HC_ENABLED: return "land_heat_capacity_enabled";
-            case RSCM_UD_P_EFFICACY_APPLY: return "efficacy_apply";
-            case RSCM_UD_P_OCEAN_TEMP_PROFILE: return "ocean_temp_profile";
-            case RSCM_UD_P_STEPS_PER_YEAR: return "steps_per_year";
-            case RSCM_UD_P_FEEDBACK_CUMT_PERIOD: return "feedback_cumt_period";
-            default: return nullptr;
-        }
-    }
-    if (kind == RSCM_KIND_OCEAN_CARBON) {
-        switch (row) {
-            case RSCM_OC_P_MODEL: return "model";
-            case RSCM_OC_P_IRF_SCALE: return "irf_scale";
-            case RSCM_OC_P_STEPS_PER_YEAR: return "steps_per_year";
-            case RSCM_OC_P_MAX_HISTORY_MONTHS: return "max_history_months";
-            case RSCM_OC_P_IRF_SWITCH_TIME: return "irf_switch_time";
-            default: return nullptr;
-        }
-    }
-    if (kind == RSCM_KIND_GHG_FORCING && row == RSCM_GH_P_METHOD) return "method";
-    if (kind == RSCM_KIND_N2O_CHEMISTRY && row == 4) return "stratospheric delay (sets the look-back)";
-    return nullptr;
-}
 
 inline int set_device(const rscm_ens* h)
 {
@@ -408,13 +385,28 @@ int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int
                 std::vector<double>& times);
 // RSCM_OK if p is device memory on h's device holding at least N doubles from p on, else RSCM_ERR_INVALID (select_host.cpp)
 int check_member_vector(const rscm_ens* h, const double* p, const char* what);
-// issue what a WindowDeferral holds on `stream` and make the new windows current (rscm_gpu.cpp)
+// issue what a WindowDeferral holds on `stream` and make the new windows current (window_host.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
-// the handle's own window and its RK4 sub-step tables (rscm_gpu.cpp)
+// the handle's own window (window_host.cpp)
 int window_reset(rscm_ens* h, bool clear);
 int window_slide(rscm_ens* h, int32_t new_win0);
+int window_seek(rscm_ens* h, int32_t k);
 int window_store_row(rscm_ens* h, int32_t t);
+
+// What the host builds from parameters and time axis (kind_config.cpp): the RK4 sub-step tables, GhgForcing's rows [S][kGhgRows][T] of conc [S][3][T] ...
 int refresh_schedule(rscm_ens* h);
+std::vector<double> ghg_tables(const double* conc, int32_t n_scen, int32_t T);
+// ... and the configuration derived from a parameter vector's structural rows (structural_rows.hpp): ClimateUDEB's tables and windows,
+// OceanCarbon's response table, ring and mode fit, GhgForcing's method.  Members 0 .. n_check - 1 are checked for uniformity: a block
+// [P][N] is {soa, N, 1, N}, one vector {p, 1, 0, 1}.  state_replaced: a branch is about to replace the internal state, so a change of its shape is no error
+struct ParamView {
+    const double* base; int64_t row_stride, member_stride, n_check;
+    double at(int32_t j, int64_t i = 0) const { return base[(size_t)j * row_stride + (size_t)i * member_stride]; }
+};
+int configure_kind(rscm_ens* h, const ParamView& p, bool state_replaced = false);
+// N2O: the rows the stratospheric delay looks back (n2o.rs:203-218).  Two callers: rscm_ens_set_params with the largest member value,
+// rscm_ens_sample_lhs with `high` of the delay's row
+inline int32_t n2o_lookback(double largest_delay) { return (int32_t)std::min(std::max(1.0, largest_delay), 1e6) + 1; }
 
 // An observation list and its reference periods as the boundary passes them.  owner: the handle of a list that each entry refers
 // to (the graph sampler), null: all refer to the first.

@@ -26,6 +26,7 @@ struct KindInfo {
     bool reads_end;       // linked inputs are read at the end of the step (index n + 1) whatever `source` said
     Family family;
     bool fusable;         // its one-step launch can join a fused launch (csrc/group.hip); GhgForcing: with linked inputs only
+    bool internal_state;  // its component keeps state besides the stored rows (the reference's ComponentState): internal_state.hpp
     int32_t op_cost;      // plan_split's estimate: one unit ~ a dependent round trip to memory plus a few dozen instructions; the
                           // chemistry's Prather passes, the forcing formulas' logarithms and the RK4 box models weigh by their
                           // instruction counts on top
@@ -33,25 +34,25 @@ struct KindInfo {
 
 // ClimateUDEB, OceanCarbon, HalocarbonChemistry and the fused coupled chain are heavy components: they keep their own launches.
 constexpr KindInfo kKinds[] = {
-    //  kind                        name                   P  V   in  states lb  bounds derive end   family         fusable cost
-    {RSCM_KIND_TWO_LAYER,          "TwoLayer",             6,  3,  1, 1,  2, 0, false, false, false, Family::TwoLayer,  true,  12},
-    {RSCM_KIND_COUPLED,            "Coupled",             10,  8,  1, 1,  5, 0, false, false, false, Family::Coupled,   false, 1},
-    {RSCM_KIND_UDEB,               "ClimateUDEB",         37,  8,  1, 1,  4, 0, true,  true,  true,  Family::Udeb,      false, 1},
-    {RSCM_KIND_GHG_FORCING,        "GhgForcing",          21,  4,  3, 1,  0, 0, false, true,  false, Family::Ghg,       true,  4},
-    {RSCM_KIND_OZONE_FORCING,      "OzoneForcing",        13,  4,  6, 1,  0, 0, false, false, false, Family::Pointwise, true,  2},
-    {RSCM_KIND_AEROSOL_DIRECT,     "AerosolDirect",       27,  5,  4, 1,  0, 0, false, false, false, Family::Pointwise, true,  2},
-    {RSCM_KIND_AEROSOL_INDIRECT,   "AerosolIndirect",      9,  2,  2, 1,  0, 0, false, false, false, Family::Pointwise, true,  1},
-    {RSCM_KIND_CH4_CHEMISTRY,      "CH4Chemistry",        18,  3,  5, 1,  1, 1, false, false, false, Family::Chem,      true,  6},   // previous()
-    {RSCM_KIND_N2O_CHEMISTRY,      "N2OChemistry",         6,  3,  1, 1,  1, 2, true,  false, false, Family::Chem,      true,  5},   // at_offset(-(strat_delay + 1))
-    {RSCM_KIND_CO2_BUDGET,         "CO2Budget",            2,  4,  4, 1,  1, 0, true,  false, false, Family::Carbon,    true,  1},
-    {RSCM_KIND_TERRESTRIAL_CARBON, "TerrestrialCarbon",   20,  6,  3, 1,  4, 0, true,  true,  false, Family::Carbon,    true,  4},
-    {RSCM_KIND_OCEAN_CARBON,       "OceanCarbon",         24,  4,  2, 1,  2, 0, true,  false, false, Family::Ocean,     false, 1},
-    {RSCM_KIND_HALOCARBON,         "HalocarbonChemistry", 293, 46, 41, 1, 41, 0, true,  false, false, Family::Halo,      false, 1},
-    {RSCM_KIND_FOURBOX_OHU,        "FourBoxOHU",           4,  5,  1, 1,  0, 0, false, false, false, Family::Pointwise, true,  1},
-    {RSCM_KIND_OSPP,               "OSPP",                13,  2,  2, 1,  0, 0, false, false, false, Family::Pointwise, true,  1},
-    {RSCM_KIND_CARBON_CYCLE,       "CarbonCycle",          3,  4,  2, 1,  3, 0, false, false, false, Family::Carbon,    true,  4},
-    {RSCM_KIND_CO2_ERF,            "CO2ERF",               2,  2,  1, 1,  0, 0, false, false, false, Family::Pointwise, true,  1},
-    {RSCM_KIND_AGGREGATE,          "Aggregate",            9,  2,  8, 1,  0, 0, false, false, true,  Family::Pointwise, true,  1},
+    //  kind                        name                   P  V   in  states lb  bounds derive end   family         fusable state  cost
+    {RSCM_KIND_TWO_LAYER,          "TwoLayer",             6,  3,  1, 1,  2, 0, false, false, false, Family::TwoLayer,  true,  false, 12},
+    {RSCM_KIND_COUPLED,            "Coupled",             10,  8,  1, 1,  5, 0, false, false, false, Family::Coupled,   false, false, 1},
+    {RSCM_KIND_UDEB,               "ClimateUDEB",         37,  8,  1, 1,  4, 0, true,  true,  true,  Family::Udeb,      false, true,  1},
+    {RSCM_KIND_GHG_FORCING,        "GhgForcing",          21,  4,  3, 1,  0, 0, false, true,  false, Family::Ghg,       true,  false, 4},
+    {RSCM_KIND_OZONE_FORCING,      "OzoneForcing",        13,  4,  6, 1,  0, 0, false, false, false, Family::Pointwise, true,  false, 2},
+    {RSCM_KIND_AEROSOL_DIRECT,     "AerosolDirect",       27,  5,  4, 1,  0, 0, false, false, false, Family::Pointwise, true,  false, 2},
+    {RSCM_KIND_AEROSOL_INDIRECT,   "AerosolIndirect",      9,  2,  2, 1,  0, 0, false, false, false, Family::Pointwise, true,  false, 1},
+    {RSCM_KIND_CH4_CHEMISTRY,      "CH4Chemistry",        18,  3,  5, 1,  1, 1, false, false, false, Family::Chem,      true,  false, 6},   // previous()
+    {RSCM_KIND_N2O_CHEMISTRY,      "N2OChemistry",         6,  3,  1, 1,  1, 2, true,  false, false, Family::Chem,      true,  false, 5},   // at_offset(-(strat_delay + 1))
+    {RSCM_KIND_CO2_BUDGET,         "CO2Budget",            2,  4,  4, 1,  1, 0, true,  false, false, Family::Carbon,    true,  false, 1},
+    {RSCM_KIND_TERRESTRIAL_CARBON, "TerrestrialCarbon",   20,  6,  3, 1,  4, 0, true,  true,  false, Family::Carbon,    true,  false, 4},
+    {RSCM_KIND_OCEAN_CARBON,       "OceanCarbon",         24,  4,  2, 1,  2, 0, true,  false, false, Family::Ocean,     false, true,  1},
+    {RSCM_KIND_HALOCARBON,         "HalocarbonChemistry", 293, 46, 41, 1, 41, 0, true,  false, false, Family::Halo,      false, false, 1},
+    {RSCM_KIND_FOURBOX_OHU,        "FourBoxOHU",           4,  5,  1, 1,  0, 0, false, false, false, Family::Pointwise, true,  false, 1},
+    {RSCM_KIND_OSPP,               "OSPP",                13,  2,  2, 1,  0, 0, false, false, false, Family::Pointwise, true,  false, 1},
+    {RSCM_KIND_CARBON_CYCLE,       "CarbonCycle",          3,  4,  2, 1,  3, 0, false, false, false, Family::Carbon,    true,  false, 4},
+    {RSCM_KIND_CO2_ERF,            "CO2ERF",               2,  2,  1, 1,  0, 0, false, false, false, Family::Pointwise, true,  false, 1},
+    {RSCM_KIND_AGGREGATE,          "Aggregate",            9,  2,  8, 1,  0, 0, false, false, true,  Family::Pointwise, true,  false, 1},
 };
 constexpr int32_t kNumKinds = (int32_t)(sizeof kKinds / sizeof kKinds[0]);
 

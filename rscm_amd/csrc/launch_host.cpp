@@ -30,11 +30,7 @@ int ensure_derived(rscm_ens* h)
     // derive kernel, ClimateUDEB's secant solve, every step)
     if (h->derived_hold && !h->derived_dirty && h->d_derived) return RSCM_OK;
     if (int rc = set_device(h)) return rc;
-    if (!h->d_derived) {
-        const hipError_t e = h->d_derived.alloc((size_t)rscm::kDerivedRows * h->N);
-        if (e != hipSuccess)
-            return fail(e == hipErrorOutOfMemory ? RSCM_ERR_NOMEM : RSCM_ERR_DEVICE, "member constants of %lld members: %s", (long long)h->N, hipGetErrorString(e));
-    }
+    if (int rc = alloc_or_fail(h->d_derived, (size_t)rscm::kDerivedRows * h->N, true, "member constants of %lld members", (long long)h->N)) return rc;
     switch (h->info().family) {
         case rscm::Family::Ghg: HIPCHK(rscm::launch_ghg_derive(h->d_params, h->uniform_rows, h->ghg_method, h->N, h->d_derived, h->stream)); break;
         case rscm::Family::Udeb: HIPCHK(rscm::launch_udeb_derive(h->d_params, h->uniform_rows, h->N, h->d_derived, h->stream)); break;

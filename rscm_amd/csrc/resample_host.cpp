@@ -1,6 +1,6 @@
 // Host side of the posterior resampling (kernels: resample.hip): exact weight statistics, the systematic draw of one handle's
 // share of a global draw, and the offset every rank derives for itself from the seed.  The gather of the drawn members,
-// rscm_ens_gather_members, lives in rscm_gpu.cpp next to the configuration code it re-runs.
+// rscm_ens_gather_members, lives in state_host.cpp with the rest of a handle's state in time.
 #include "ens.hpp"
 
 namespace {

@@ -113,8 +113,7 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         // change ln L), the likelihood kernel reads the observation rows where the owners store them
         for (size_t k = 0; k < s->graph.size(); ++k) {
             rscm_ens* g = s->graph[k];
-            g->uniform_rows &= ~s->graph_sampled_rows[k];
-            if (s->graph_sampled_rows[k]) g->derived_dirty = true;   // the proposal kernel is about to write its parameter block
+            g->params_kernel_writes(s->graph_sampled_rows[k]);   // the proposal kernel is about to write its parameter block
             if (int rc = s->graph_clear ? rscm_ens_clear_series(g) : rscm_ens_rewind(g)) return rc;
         }
         HIPCHK(rscm::launch_sampler_propose(a, s->ev->stream));
@@ -129,15 +128,14 @@ int sampler_half_step(rscm_sampler* s, int32_t half, int32_t identity)
         }
         return RSCM_OK;
     }
-    s->ev->uniform_rows = 0;  // the proposal kernel writes the evaluator's parameter block
-    s->ev->derived_dirty = true;
+    s->ev->params_kernel_writes(~0ull);  // the proposal kernel writes the evaluator's parameter block
     HIPCHK(rscm::launch_sampler_propose(a, s->ev->stream));
     if (s->fused) {
         HIPCHK(launch_loglik(s->ev));
     } else {
-        s->ev->time_index = 0;  // every evaluation is a fresh Model::run of the half
+        s->ev->put_at(0);  // every evaluation is a fresh Model::run of the half
         if (int rc = rscm_ens_run_async(s->ev, 0, s->ev->T - 1)) return rc;
-        s->ev->time_index = 0;
+        s->ev->put_at(0);
         HIPCHK(rscm::launch_loglik(s->lik, s->ev->stream));
     }
     HIPCHK(rscm::launch_sampler_accept(a, s->ev->stream));
@@ -402,7 +400,7 @@ static int sampler_ready(rscm_sampler* s)
 {
     rscm_ens* h = s->ev;
     if (!s->graph.empty()) return set_device(h);   // rscm_ens_run_lockstep checks every handle of the graph when it runs
-    h->time_index = 0;
+    h->put_at(0);
     return check_loglik_ready(h);
 }
 

@@ -4,7 +4,7 @@
 //   forcing_boxed    every forcing value the launch can read -- all scenarios, forcing-axis indices step_begin + src_off through
 //                    step_end - 1 + src_off, the look-ahead's clamp included -- is +0 or a magnitude in the chunk guard's forcing box
 //                    (two_layer_chunk_box.hpp; the kernel's box::forcing_in with those edges).  -0, denormals, Inf and NaN are outside.
-// Both are answered in O(1) from prefix counts: the schedule's when the schedule is built (rscm_gpu.cpp, refresh_schedule), the table's
+// Both are answered in O(1) from prefix counts: the schedule's when the schedule is built (kind_config.cpp, refresh_schedule), the table's
 // when rscm_ens_set_forcing is handed the caller's array; the table's verdict is dropped before anything can change the table.
 // Host only, no HIP: tests/c_abi/year_facts_host.cpp compiles this header on its own.
 #pragma once
