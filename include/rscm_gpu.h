@@ -105,8 +105,10 @@ extern "C" {
  *      rscm_ens_clear_diagnostics, rscm_ens_n_diagnostics, RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX
  *  19  no entry point changed.  rscm_ens_quantile_series runs the radix select of rscm_ens_quantile_rows instead of a sort: the
  *      same bits, except that where a quantile lands on a zero the sign is the select's (-0.0 orders before +0.0, a function of
- *      the member set); the sort returned whichever zero sat first among the members, which the contract left unspecified */
-#define RSCM_GPU_ABI_MINOR 19
+ *      the member set); the sort returned whichever zero sat first among the members, which the contract left unspecified
+ *  20  per-member covariability of two variables (covariance, correlation, regression slope, cross-correlation at up to three leads
+ *      and lags): rscm_ens_member_covariability, RSCM_COV_MAX_LAGS */
+#define RSCM_GPU_ABI_MINOR 20
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1176,6 +1178,46 @@ RSCM_API int rscm_gpu_spectrum_coefficients(int32_t n, double* out /*[J]*/);
 RSCM_API int rscm_ens_loglik_spectrum_device(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, const double* record,
                                              const int32_t* count, const double* add_dev, void** out_dev);
 
+/* ---- per-member covariability of two variables (ABI minor 20) -------------------------------------- */
+/* How two variables of one member move together over a period: the covariance, the correlation and the regression slope of y on x of
+ * their detrended series and the cross-correlation at up to RSCM_COV_MAX_LAGS leads and lags, per member, on the device -- how much
+ * heat a member takes up per degree of warming, and which of the two series leads.  This is the one definition; the kernel
+ * (covariability.hip), rscm_amd.variability.series_covariability and the tests' numpy restatement apply it operation by operation.
+ *   Rows x_0 .. x_{R-1} of var_x and y_0 .. y_{R-1} of var_y: those of rscm_ens_member_variability over the same t_begin, t_end,
+ *   t_stride.  Either variable may be a diagnostic (its rows must be held and not stale); var_x == var_y is allowed.
+ *   Working series u_0 .. u_{n-1} of x under mode_x and v_0 .. v_{n-1} of y under mode_y (RSCM_VAR_MEAN, _LINEAR, _DIFFERENCE):
+ *     neither mode is RSCM_VAR_DIFFERENCE:        u_k = x_k, v_k = y_k, n = R (rscm_ens_member_variability's);
+ *     a variable whose mode is RSCM_VAR_DIFFERENCE:  u_k = x_{k+1} - x_k (one IEEE subtraction), n = R - 1;
+ *     exactly one mode is RSCM_VAR_DIFFERENCE:    the OTHER variable is taken at the midpoints the differences span,
+ *                                                 u_k = (x_k + x_{k+1}) * 0.5 (one addition, one exact multiplication), n = R - 1, and is
+ *                                                 then detrended by its own mode: a year's heat uptake against that year's temperature.
+ *   0 <= n_lags <= RSCM_COV_MAX_LAGS and n >= 3 + n_lags, else RSCM_ERR_INVALID.
+ *   Residuals: rscm_ens_member_variability's, operation for operation.  tau_k, S, m, Q, Stt and b are formed per variable under its own
+ *   mode over the n terms; a_k is the residual of u and c_k the residual of v.  Every operation is one f64 operation rounded on its
+ *   own (no FMA); sums run left to right from their first term.
+ *   Products:
+ *     G_l    = a_0*c_l + a_1*c_{l+1} + ... + a_{n-1-l}*c_{n-1}   (l >= 0: x leads y by l terms)
+ *     G_{-l} = a_l*c_0 + a_{l+1}*c_1 + ... + a_{n-1}*c_{n-1-l}   (y leads x)
+ *     Cxx = a_0*a_0 + a_1*a_1 + ...     Cyy = c_0*c_0 + c_1*c_1 + ...
+ *     D = sqrt(Cxx) * sqrt(Cyy)         (two square roots, so that the product of two sums cannot overflow first)
+ * [5 + 2 n_lags][N] doubles from *out_dev, in this order: var_x = Cxx / n, var_y = Cyy / n, cov = G_0 / n, corr = G_0 / D,
+ * slope = G_0 / Cxx (of y on x), then r_{+1} = G_1 / D, r_{-1} = G_{-1} / D, ... r_{+n_lags}, r_{-n_lags}.  A member with a non-finite
+ * value in any row of EITHER variable gets NaN everywhere; a constant x or y gives NaN in corr, slope (x) and the lags by 0/0 and 0 in
+ * its variance.  |corr| and every |r_l| are <= 1 up to rounding (Cauchy-Schwarz over the terms each sum holds).
+ * Equalities that follow from the definition, bit for bit:
+ *   with no mode mixed (both or neither RSCM_VAR_DIFFERENCE), var_x is rscm_ens_member_variability's variance of var_x for the same
+ *   rows and mode_x, and var_y that of var_y;
+ *   exchanging (var_x, mode_x) with (var_y, mode_y) exchanges var_x with var_y and r_{+l} with r_{-l} and leaves cov and corr
+ *   unchanged: products commute and the order in k is the same.
+ * The regression of uptake on temperature is NOT an unbiased estimate of a feedback parameter (the noise sits in the flux and the
+ * temperature responds to it); a likelihood compares a member's estimate with a record's under the same estimator.
+ * The result is written to indicator slot `slot` (a slot's block is [3 + 8][N]: at three lags the 11 vectors fill it); slot rules and
+ * refusals are those of rscm_ens_member_variability: a bad slot, mode or n_lags RSCM_ERR_INVALID; rows not computed or not resident,
+ * a stale diagnostic or a select in flight RSCM_ERR_STATE.  Bit-exact against the restatement. */
+#define RSCM_COV_MAX_LAGS 3
+RSCM_API int rscm_ens_member_covariability(rscm_ens* h, int32_t var_x, int32_t var_y, int32_t t_begin, int32_t t_end, int32_t t_stride,
+                                           int32_t mode_x, int32_t mode_y, int32_t n_lags, int32_t slot, void** out_dev);
+
 /* ---- diagnostic variables (ABI minor 18) ---------------------------------------------------------- */
 /* A diagnostic variable of a handle is a linear combination of that handle's stored variables with per-member weights.  For member i
  * and row t, with K terms (1 <= K <= RSCM_DIAG_MAX_TERMS), x_k = row t of the stored variable term_var[k], p the parameter block:
@@ -1202,7 +1244,7 @@ RSCM_API int rscm_ens_loglik_spectrum_device(rscm_ens* h, int32_t n_vec, const d
  * Define, compute and clear refuse with RSCM_ERR_STATE while a staged select is in flight (it may be reading the rows).
  *
  * Readers.  The id of a defined diagnostic is accepted by rscm_ens_select_begin* / rscm_ens_quantile_rows* (plain, weighted, anomaly,
- * grouped), rscm_ens_set_baseline, rscm_ens_member_indicators, _variability, _spectrum, the stored likelihoods rscm_ens_loglik,
+ * grouped), rscm_ens_set_baseline, rscm_ens_member_indicators, _variability, _spectrum, _covariability, the stored likelihoods rscm_ens_loglik,
  * _device, _ref, _ref_device (observation rows and reference-period rows), rscm_ens_summary and rscm_ens_get_series.  A row outside
  * the held range is to them what a row that is not resident is on a windowed handle: RSCM_ERR_STATE.  Everything else keeps refusing
  * the id as it refuses any var_id >= V (RSCM_ERR_INVALID): rscm_ens_series_devptr, rscm_ens_summary_series, rscm_ens_quantile_series,

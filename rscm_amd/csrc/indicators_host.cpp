@@ -4,6 +4,7 @@
 // and of the Gaussian likelihood over per-member vectors (rscm_ens_loglik_vectors_device); kernels in variability.hip.
 // Also of the per-member band powers (rscm_ens_member_spectrum), their coefficient table (rscm_gpu_spectrum_coefficients) and the
 // spectral likelihood over band powers (rscm_ens_loglik_spectrum_device); kernels in spectrum.hip.
+// Also of the per-member covariability of two variables (rscm_ens_member_covariability); kernel in covariability.hip.
 //
 // Rows are resolved as the radix select resolves them (resolve_rows: full storage, the window, the output store) and must all be
 // computed.  The baseline and the indicator slots are handle-owned and kept across run and rewind, as the member weights are; a
@@ -114,6 +115,8 @@ int working_series(size_t n_rows, int32_t mode, int32_t max_terms, WorkingSeries
 static_assert(rscm::kVarMean == RSCM_VAR_MEAN && rscm::kVarLinear == RSCM_VAR_LINEAR && rscm::kVarDifference == RSCM_VAR_DIFFERENCE,
               "the detrending modes in rscm_device.hpp and rscm_gpu.h must agree");
 static_assert(5 <= 3 + rscm::kMaxThresholds, "the variability statistics share the indicator slots");
+static_assert(rscm::kCovMaxLags == RSCM_COV_MAX_LAGS && 5 + 2 * RSCM_COV_MAX_LAGS <= 3 + rscm::kMaxThresholds,
+              "the covariability statistics at every lag share the indicator slots");
 
 constexpr int32_t kSpectrumMaxTerms = 4096;   // the cap on the working series' length that bounds the recurrence's error
 
@@ -293,6 +296,42 @@ int rscm_ens_member_variability(rscm_ens* h, int32_t var_id, int32_t t_begin, in
     rscm::DevBuf<const double*> d_rows;
     if (int rc = upload_rows(h, rows, d_rows)) return rc;
     HIPCHK(rscm::launch_variability(d_rows.get(), (int32_t)rows.size(), mode, w.stt, h->N, h->d_ind[slot], h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out_dev = h->d_ind[slot];
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_member_covariability(rscm_ens* h, int32_t var_x, int32_t var_y, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t mode_x,
+                                  int32_t mode_y, int32_t n_lags, int32_t slot, void** out_dev)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
+    *out_dev = nullptr;
+    if (int rc = check_slot(slot)) return rc;
+    if (int rc = check_detrending(mode_x)) return rc;
+    if (int rc = check_detrending(mode_y)) return rc;
+    if (n_lags < 0 || n_lags > RSCM_COV_MAX_LAGS) return fail(RSCM_ERR_INVALID, "n_lags = %d: must be in [0, %d]", n_lags, RSCM_COV_MAX_LAGS);
+    if (int rc = no_select(h)) return rc;
+    std::vector<const double*> rows_x, rows_y;
+    std::vector<double> times_x, times_y;
+    if (int rc = period_rows(h, var_x, t_begin, t_end, t_stride, rows_x, times_x)) return rc;
+    if (int rc = period_rows(h, var_y, t_begin, t_end, t_stride, rows_y, times_y)) return rc;
+    // both working series have the length of the differenced one as soon as either variable is differenced (the other is taken at the midpoints)
+    const bool differenced = mode_x == RSCM_VAR_DIFFERENCE || mode_y == RSCM_VAR_DIFFERENCE;
+    WorkingSeries w;
+    if (int rc = working_series(rows_x.size(), differenced ? RSCM_VAR_DIFFERENCE : RSCM_VAR_MEAN, 0, &w)) return rc;
+    if (w.n < 3 + n_lags)
+        return fail(RSCM_ERR_INVALID, "the working series of %d rows has %lld terms: at least %d are needed at %d lags", (int)rows_x.size(), (long long)w.n,
+                    3 + n_lags, n_lags);
+    if (int rc = set_device(h)) return rc;
+    if (int rc = slot_buffer(h, slot)) return rc;
+    rscm::DevBuf<const double*> d_rows_x, d_rows_y;
+    if (int rc = upload_rows(h, rows_x, d_rows_x)) return rc;
+    if (int rc = upload_rows(h, rows_y, d_rows_y)) return rc;
+    HIPCHK(rscm::launch_covariability(d_rows_x.get(), d_rows_y.get(), (int32_t)rows_x.size(), mode_x, mode_y, n_lags, w.stt, h->N, h->d_ind[slot],
+                                      h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *out_dev = h->d_ind[slot];
     return RSCM_OK;

@@ -921,6 +921,14 @@ hipError_t launch_exceedance_grouped(const double* d_v, const int64_t* d_w, cons
 // include/rscm_gpu.h, rscm_ens_member_variability); stt = n (n^2 - 1) / 12 of the working series' length n, formed by the caller
 constexpr int kVarMean = 0, kVarLinear = 1, kVarDifference = 2;
 hipError_t launch_variability(const double* const* d_rows, int32_t n_rows, int32_t mode, double stt, int64_t N, double* d_out, hipStream_t s);
+// per-member covariability of two variables (covariability.hip) over rows d_rows_x[n_rows][N] and d_rows_y[n_rows][N]:
+// d_out[5 + 2 n_lags][N] = var_x, var_y, cov, corr, slope, then r_{+1}, r_{-1}, ... r_{+n_lags}, r_{-n_lags} (the definition is stated
+// in include/rscm_gpu.h, rscm_ens_member_covariability); the modes are launch_variability's, stt = n (n^2 - 1) / 12 of the working
+// series' common length n (n_rows - 1 when either mode is kVarDifference), formed by the caller; 0 <= n_lags <= kCovMaxLags
+constexpr int kCovMaxLags = 3;
+static_assert(5 + 2 * kCovMaxLags <= 3 + kMaxThresholds, "the covariability statistics share the indicator slots: [3 + kMaxThresholds][N]");
+hipError_t launch_covariability(const double* const* d_rows_x, const double* const* d_rows_y, int32_t n_rows, int32_t mode_x, int32_t mode_y,
+                                int32_t n_lags, double stt, int64_t N, double* d_out, hipStream_t s);
 // d_out[i] = (d_add ? d_add[i] : 0.0) + sum over j < n_vec of -0.5 ((value[j] - vec[j][i])^2 / sigma[j]^2), -inf where a vec[j][i] or
 // d_add[i] is not finite; d_add may be d_out
 constexpr int kMaxLoglikVectors = 16;

@@ -650,6 +650,28 @@ class Ensemble:
         n, base = self.n_members, p.value
         return {k: DeviceVector(base + 8 * n * j, n, np.float64, self) for j, k in enumerate(("mean", "slope", "variance", "sd", "r1"))}
 
+    def covariability(self, x, y, t_begin: int, t_end: int, t_stride: int = 1, detrend_x: str = "linear", detrend_y: str = "linear",
+                      lags: int = 0, slot: int = 0) -> Dict[str, object]:
+        """Per-member covariability of the variables ``x`` and ``y`` (stored or diagnostic; they may be the same) over the rows
+        ``t_begin, t_begin + t_stride, ... < t_end``, left on the device in indicator slot ``slot`` (the slots of ``indicators``,
+        ``variability`` and ``spectrum``): ``{"var_x", "var_y", "cov", "corr", "slope", "lead": [r_+1 ..], "lag": [r_-1 ..]}``,
+        ``DeviceVector``s of ``[N]`` float64, ``lead`` and ``lag`` lists of ``lags`` (0 to 3) vectors.  Each variable is detrended
+        as ``variability`` detrends it (``detrend_x``, ``detrend_y``); when exactly one of the two is ``"difference"``, the other is
+        taken at the midpoints ``(x[k] + x[k + 1]) / 2`` the differences span and then detrended by its own mode -- a year's heat
+        uptake against that year's temperature.  ``corr`` is the correlation of the two residual series and ``slope`` the
+        regression slope of ``y`` on ``x``; ``lead[l - 1]`` is their correlation with ``x`` leading ``y`` by ``l`` terms,
+        ``lag[l - 1]`` with ``y`` leading.  The definition is ``rscm_amd.variability.series_covariability``'s, bit for bit
+        (rscm_ens_member_covariability).  At least ``3 + lags`` terms; a member with a non-finite value in any row of either
+        variable has NaN everywhere, a constant series NaN in ``corr`` and the lags."""
+        from .variability import detrend_mode
+        lags = int(lags)
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_member_covariability(self._h, self._var(x), self._var(y), int(t_begin), int(t_end), int(t_stride),
+                                                        detrend_mode(detrend_x), detrend_mode(detrend_y), lags, int(slot), C.byref(p)))
+        n, base = self.n_members, p.value
+        vec = [DeviceVector(base + 8 * n * j, n, np.float64, self) for j in range(5 + 2 * lags)]
+        return {"var_x": vec[0], "var_y": vec[1], "cov": vec[2], "corr": vec[3], "slope": vec[4], "lead": vec[5::2], "lag": vec[6::2]}
+
     def loglik_vectors(self, vectors, values, sigmas, add_to: Optional[DeviceVector] = None) -> DeviceVector:
         """Gaussian log-likelihood per member over per-member device vectors (variability statistics, indicators,
         ``params_vector`` rows): ``sum_j -0.5 ((values[j] - vectors[j][i]) / sigmas[j])^2``, added onto ``add_to`` -- a device

@@ -4,7 +4,8 @@ the one definition).  Pure numpy; every operation is one float64 operation round
 over the rows, so a record put through this function and the same values put through the kernel agree bit for bit.
 
 The same for the band powers of ``Ensemble.spectrum`` (rscm_ens_member_spectrum): ``series_spectrum`` with the default band edges of
-``band_edges`` and the library's own coefficient table (``spectrum_coefficients``)."""
+``band_edges`` and the library's own coefficient table (``spectrum_coefficients``), and for the covariability of two series
+(``Ensemble.covariability``, rscm_ens_member_covariability): ``series_covariability``."""
 import ctypes as C
 from typing import Dict
 
@@ -71,6 +72,65 @@ def series_variability(x, detrend: str = "linear") -> Dict[str, object]:
     return {k: float(v[0]) for k, v in out.items()} if single else out
 
 
+def _pair_series(rows, mode, other):
+    """The working series of ``rows`` [R][N] under ``mode`` when the other variable's mode is ``other`` (rscm_ens_member_covariability):
+    the rows, their differences, or -- next to a differenced partner -- their midpoints."""
+    if mode == L.VAR_DIFFERENCE:
+        return rows[1:] - rows[:-1]
+    if other == L.VAR_DIFFERENCE:
+        return (rows[:-1] + rows[1:]) * 0.5
+    return rows
+
+
+COV_MAX_LAGS = L.COV_MAX_LAGS
+COV_STATISTICS = ("var_x", "var_y", "cov", "corr", "slope")
+
+
+def series_covariability(x, y, detrend_x: str = "linear", detrend_y: str = "linear", lags: int = 0) -> Dict[str, object]:
+    """``{"var_x", "var_y", "cov", "corr", "slope", "lead": [r_+1 ..], "lag": [r_-1 ..]}`` of the series ``x`` and ``y``: both
+    ``[R]`` (floats come back) or both ``[R][N]`` (rows by members: arrays of ``[N]``) -- ``Ensemble.covariability`` for a record.
+    ``detrend_x`` and ``detrend_y`` as ``series_variability``; when exactly one is ``"difference"`` the other series is taken at the
+    midpoints ``(x[k] + x[k + 1]) * 0.5`` and then detrended by its own mode.  ``lags``: 0 to 3; at least ``3 + lags`` terms in the
+    working series.  ``corr`` and ``slope`` (of ``y`` on ``x``) are those of the two residual series; ``lead[l - 1]`` is their
+    correlation with ``x`` leading ``y`` by ``l`` terms, ``lag[l - 1]`` with ``y`` leading.  Operation for operation the definition
+    of rscm_ens_member_covariability: what the kernel gives for the same values, bit for bit.  A non-finite value in either series
+    gives NaN everywhere; a constant series variance 0 and NaN in ``corr`` and the lags."""
+    mode_x, mode_y = detrend_mode(detrend_x), detrend_mode(detrend_y)
+    rx, ry = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if rx.ndim not in (1, 2) or rx.shape != ry.shape:
+        raise ValueError(f"series_covariability: two series of one shape [R] or [R][N] expected, got {rx.shape} and {ry.shape}")
+    lags = int(lags)
+    if not 0 <= lags <= COV_MAX_LAGS:
+        raise ValueError(f"series_covariability: lags must be in [0, {COV_MAX_LAGS}], got {lags}")
+    single = rx.ndim == 1
+    if single:
+        rx, ry = rx[:, None], ry[:, None]
+    n = rx.shape[0] - (1 if L.VAR_DIFFERENCE in (mode_x, mode_y) else 0)
+    if n < 3 + lags:
+        raise ValueError(f"series_covariability: the working series has {n} terms, at least {3 + lags} are needed at {lags} lags")
+    bad = ~(np.isfinite(rx).all(axis=0) & np.isfinite(ry).all(axis=0))
+    with np.errstate(all="ignore"):
+        a, _, _, Cxx = _series_residuals(_pair_series(rx, mode_x, mode_y), mode_x)
+        c, _, _, Cyy = _series_residuals(_pair_series(ry, mode_y, mode_x), mode_y)
+
+        def G(l):              # sum over k of a_k c_{k + l}, in order of k
+            lo = max(0, -l)
+            acc = a[lo] * c[lo + l]
+            for k in range(lo + 1, n - max(0, l)):
+                acc = acc + a[k] * c[k + l]
+            return acc
+
+        G0 = G(0)
+        D = np.sqrt(Cxx) * np.sqrt(Cyy)
+        out = {"var_x": Cxx / float(n), "var_y": Cyy / float(n), "cov": G0 / float(n), "corr": G0 / D, "slope": G0 / Cxx,
+               "lead": [G(l) / D for l in range(1, lags + 1)], "lag": [G(-l) / D for l in range(1, lags + 1)]}
+    nan = lambda v: np.where(bad, np.nan, v)
+    out = {k: [nan(w) for w in v] if isinstance(v, list) else nan(v) for k, v in out.items()}
+    if single:
+        out = {k: [float(w[0]) for w in v] if isinstance(v, list) else float(v[0]) for k, v in out.items()}
+    return out
+
+
 MAX_BANDS = 8          # rscm_ens_member_spectrum: 1 .. 8 bands
 MAX_TERMS = 4096       # ... over a working series of 3 .. 4096 terms
 
@@ -131,11 +191,9 @@ def spectrum_coefficients(n: int) -> np.ndarray:
     return out
 
 
-def _residuals(rows, mode):
-    """(a [n][N], m, b, C0 / n, bad) of ``rows`` [R][N]: the working series' residuals and the first three statistics, with the
+def _series_residuals(u, mode):
+    """(a [n][N], m, b, C0) of the working series ``u`` [n][N]: its residuals, mean, slope and their sum of squares, with the
     operations of ``series_variability``."""
-    bad = ~np.isfinite(rows).all(axis=0)
-    u = rows[1:] - rows[:-1] if mode == L.VAR_DIFFERENCE else rows
     n = u.shape[0]
     h = (n - 1) * 0.5
     tau = np.arange(n, dtype=np.float64) - h
@@ -157,7 +215,15 @@ def _residuals(rows, mode):
             ak = ak - b * tau[k]
         a[k] = ak
         C0 = ak * ak if k == 0 else C0 + ak * ak
-    return a, m, b, C0 / float(n), bad
+    return a, m, b, C0
+
+
+def _residuals(rows, mode):
+    """(a [n][N], m, b, C0 / n, bad) of ``rows`` [R][N]: the working series' residuals and the first three statistics."""
+    bad = ~np.isfinite(rows).all(axis=0)
+    u = rows[1:] - rows[:-1] if mode == L.VAR_DIFFERENCE else rows
+    a, m, b, C0 = _series_residuals(u, mode)
+    return a, m, b, C0 / float(u.shape[0]), bad
 
 
 def series_spectrum(x, detrend: str = "difference", edges=None) -> Dict[str, object]:

@@ -32,7 +32,15 @@ differences are the year-to-year heat uptake.  Their (sd, r1) -- and with ``--sp
 temperature's and added onto the temperature's likelihoods; the effective sample size and the 5-50-95 % ranges of sigma, phi,
 lambda0 and the two heat capacities are printed for temperature alone and for temperature plus heat content.
 
-    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content]
+With ``--covariability`` (it requires ``--heat-content``) the RELATION between the two series is a target too (DESIGN.md section
+8s): the correlation, the regression slope and the cross-correlations one year either way of the heat content's differences against
+the temperature at the midpoints, linearly detrended -- ``rscm_amd.variability.series_covariability(temperature, heat, "linear",
+"difference", 1)`` of the record against ``Ensemble.covariability`` of every member, scored by ``loglik_vectors`` alone
+("covariability") and added onto the temperature-plus-heat-content likelihood ("all").  The sigmas are the sampling errors over n
+terms times ``sqrt(2)``: ``(1 - r^2) / sqrt(n)`` for the correlations, ``sqrt((var_y - slope cov) / (n var_x))`` for the slope.  The
+effective sample size and the 5-50-95 % ranges of sigma, phi, lambda0, the efficacy and the two heat capacities are printed.
+
+    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content] [--covariability]
 
 Prints one JSON line; exit code 0 iff every comparison holds."""
 import argparse
@@ -45,7 +53,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rscm_amd  # noqa: E402
-from rscm_amd.variability import series_spectrum, series_variability  # noqa: E402
+from rscm_amd.variability import series_covariability, series_spectrum, series_variability  # noqa: E402
 
 Q = [0.05, 0.17, 0.5, 0.83, 0.95]
 YEARS = np.arange(1850.0, 2101.0)
@@ -86,7 +94,11 @@ def main():
     ap.add_argument("--fast", action="store_true")
     ap.add_argument("--spectrum", action="store_true", help="also weight by the record's band powers (loglik_spectrum)")
     ap.add_argument("--heat-content", action="store_true", help="also weight by the variability of the record's ocean heat content")
+    ap.add_argument("--covariability", action="store_true",
+                    help="also weight by the covariability of the record's heat uptake and temperature (requires --heat-content)")
     a = ap.parse_args()
+    if a.covariability and not a.heat_content:
+        ap.error("--covariability requires --heat-content")
     mode = rscm_amd.MODE_FAST if a.fast else rscm_amd.MODE_EXACT
 
     # the record: one member with known amplitude and persistence, a seed of its own
@@ -194,6 +206,41 @@ def main():
                 want = [np.nanquantile(P[r], q3, weights=w, method="inverted_cdf").tolist() for r in named.values()]
             checks["heat_content_weighted_quantiles_equal_numpy"] = bool(want == [heat["temperature_and_heat_content"][k] for k in named])
 
+        cov = None
+        if a.covariability:
+            # the relation between the two series: heat uptake (the differences) against the temperature at the midpoints, about its line;
+            # alone, and continued from the temperature-plus-heat-content likelihood (lls, in place)
+            cnamed = {"sigma": sigma_row, "phi": phi_row, "lambda0": 0, "efficacy": 2, "heat_capacity_surface": 4, "heat_capacity_deep": 5}
+            cvec = [ens.params_vector(r) for r in cnamed.values()]
+
+            def cweigh(l):
+                ens.set_weights_from_loglik(l)
+                q = ens.quantile_vectors(cvec, q3, weighted=True)["quantiles"]
+                return {"ess": ens.weights_stats()["ess"], **{k: q[j].tolist() for j, k in enumerate(cnamed)}}
+
+            ct = series_covariability(annual, annual_heat, "linear", "difference", 1)
+            cvalues = [ct["corr"], ct["slope"], ct["lead"][0], ct["lag"][0]]
+            rsig = lambda r: np.sqrt(2.0) * (1.0 - r * r) / np.sqrt(n_diff)
+            csigmas = [rsig(ct["corr"]), np.sqrt(2.0) * np.sqrt((ct["var_y"] - ct["slope"] * ct["cov"]) / (n_diff * ct["var_x"])),
+                       rsig(ct["lead"][0]), rsig(ct["lag"][0])]
+            cov = {"quantiles": q3, "target": dict(zip(("corr", "slope", "r_plus_1", "r_minus_1"), map(float, cvalues))),
+                   "target_sigma": dict(zip(("corr", "slope", "r_plus_1", "r_minus_1"), map(float, csigmas))),
+                   "prior": {k: q.tolist() for k, q in zip(cnamed, ens.quantile_vectors(cvec, q3)["quantiles"])}}
+            cov["temperature_and_heat_content"] = cweigh(lls)
+            c = ens.covariability(TS, hid, 0, NOW + 1, 1, "linear", "difference", 1, slot=1)
+            cstats = [c["corr"], c["slope"], c["lead"][0], c["lag"][0]]
+            cov["all"] = cweigh(ens.loglik_vectors(cstats, cvalues, csigmas, add_to=lls))
+            cov["covariability"] = cweigh(ens.loglik_vectors(cstats, cvalues, csigmas))
+            w = ens.member_weights()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                want = [np.nanquantile(P[r], q3, weights=w, method="inverted_cdf").tolist() for r in cnamed.values()]
+            checks["covariability_weighted_quantiles_equal_numpy"] = bool(want == [cov["covariability"][k] for k in cnamed])
+            # one member's vectors against the host estimator on its own rows, bit for bit
+            one = series_covariability(ens.get_series(TS, 0, NOW + 1)[:, :64], ens.get_series(hid, 0, NOW + 1)[:, :64], "linear", "difference", 1)
+            checks["covariability_equals_the_host_estimator"] = bool(all(
+                np.array_equal(d.to_host()[:64], h, equal_nan=True) for d, h in zip(cstats, [one["corr"], one["slope"], one["lead"][0], one["lag"][0]])))
+
     res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
            "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
            "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
@@ -209,6 +256,8 @@ def main():
         res["constraint"]["spectrum_and_statistics"] = constraint["spectrum_and_statistics"]
     if heat is not None:
         res["heat_content"] = heat
+    if cov is not None:
+        res["covariability"] = cov
     print(json.dumps(res), flush=True)
     sys.exit(0 if all(checks.values()) else 1)
 
