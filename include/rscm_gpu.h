@@ -107,8 +107,10 @@ extern "C" {
  *      same bits, except that where a quantile lands on a zero the sign is the select's (-0.0 orders before +0.0, a function of
  *      the member set); the sort returned whichever zero sat first among the members, which the contract left unspecified
  *  20  per-member covariability of two variables (covariance, correlation, regression slope, cross-correlation at up to three leads
- *      and lags): rscm_ens_member_covariability, RSCM_COV_MAX_LAGS */
-#define RSCM_GPU_ABI_MINOR 20
+ *      and lags): rscm_ens_member_covariability, RSCM_COV_MAX_LAGS
+ *  21  per-member co-spectra of two variables in frequency bands (squared coherence, gain and quadrature gain per band):
+ *      rscm_ens_member_cross_spectrum, rscm_gpu_spectrum_sines, RSCM_XSPEC_MAX_BANDS */
+#define RSCM_GPU_ABI_MINOR 21
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1218,6 +1220,59 @@ RSCM_API int rscm_ens_loglik_spectrum_device(rscm_ens* h, int32_t n_vec, const d
 RSCM_API int rscm_ens_member_covariability(rscm_ens* h, int32_t var_x, int32_t var_y, int32_t t_begin, int32_t t_end, int32_t t_stride,
                                            int32_t mode_x, int32_t mode_y, int32_t n_lags, int32_t slot, void** out_dev);
 
+/* ---- per-member co-spectra and coherence of two variables (ABI minor 21) --------------------------- */
+/* How two variables of one member move together PER FREQUENCY BAND: the squared coherence of their detrended series, the in-phase
+ * gain of y on x (uptake per degree in the band) and its out-of-phase part, per member, on the device.  Over a period the time-domain
+ * relation of rscm_ens_member_covariability mixes the slow band, where a feedback acts, with the fast band the noise fills; this
+ * scores them apart.  This is the one definition; the kernel (cross_spectrum.hip), rscm_amd.variability.series_cross_spectrum and the
+ * tests' numpy restatement apply it operation by operation.
+ *   Rows, working series u_k, v_k and their common length n: EXACTLY those of rscm_ens_member_covariability for the same var_x, var_y,
+ *   t_begin, t_end, t_stride, mode_x, mode_y -- each variable its own mode (RSCM_VAR_MEAN, _LINEAR, _DIFFERENCE); when exactly one is
+ *   differenced the other is taken at the midpoints (x_k + x_{k+1}) * 0.5; either may be a diagnostic; var_x == var_y is allowed.
+ *   Residuals a_k (of x) and c_k (of y), Cxx = a_0*a_0 + a_1*a_1 + ..., Cyy = c_0*c_0 + ...: that definition's, operation for operation.
+ *   3 <= n <= 4096, else RSCM_ERR_INVALID (the upper limit is rscm_ens_member_spectrum's, for the same reason).
+ *   Frequencies j = 1 .. J, J = (n - 1) / 2; c2_j from rscm_gpu_spectrum_coefficients; g_j, the double nearest sin(2 pi j / n), from
+ *   rscm_gpu_spectrum_sines; h_j = c2_j * 0.5 (exact).
+ *   Every operation is one f64 operation rounded on its own (no FMA); sums run left to right from their first term.
+ *   Two Goertzel recurrences with the same c2_j:
+ *     s1 = s2 = t1 = t2 = +0.0;  for k = 0 .. n - 1 in order:
+ *       s0 = (a_k + c2_j*s1) - s2;  s2 = s1;  s1 = s0          t0 = (c_k + c2_j*t1) - t2;  t2 = t1;  t1 = t0
+ *   Ordinates per frequency:
+ *     Ixx_j = ((s1*s1 + s2*s2) - (c2_j*s1)*s2) / (double)n     (rscm_ens_member_spectrum's I_j of x);   Iyy_j the same on t
+ *     K_j   = ((s1*t1 + s2*t2) - h_j*(s1*t2 + s2*t1)) / (double)n      the co-spectrum, Re X_a conj(X_c) / n
+ *     Q_j   = (g_j*(s2*t1 - s1*t2)) / (double)n                         the quadrature spectrum, Im X_a conj(X_c) / n
+ *   Q_j > 0 means x leads y: for c_k = a_{k-1} the cross term is |X_a|^2 e^{+iw}.
+ *   Bands: n_bands (1 .. RSCM_XSPEC_MAX_BANDS) and edges[n_bands + 1] under rscm_ens_member_spectrum's rules: strictly ascending,
+ *   edges[0] >= 1, edges[n_bands] <= J + 1, else RSCM_ERR_INVALID.  Only the frequencies inside [edges[0], edges[n_bands]) are
+ *   computed; a caller who wants more bands calls again on another slot.  Band b holds edges[b] <= j < edges[b + 1], m_b of them;
+ *     Pxx_b, Pyy_b, K_b, Q_b = the four ordinates summed in ascending j over the band, each sum divided by (double)m_b
+ *     D_b = sqrt(Pxx_b) * sqrt(Pyy_b),  kc = K_b / D_b,  qc = Q_b / D_b
+ * [2 + 3 n_bands][N] doubles from *out_dev, in this order: var_x = Cxx / n, var_y = Cyy / n, then per band
+ *   coh2_b = kc*kc + qc*qc,  gain_b = K_b / Pxx_b,  gain_quad_b = Q_b / Pxx_b.
+ * gain_b is the in-phase transfer of y on x in the band and gain_quad_b the out-of-phase part.  coh2_b <= 1 up to rounding
+ * (Cauchy-Schwarz over the band's ordinates); a band of ONE ordinate has coh2 = 1 to rounding, whatever the series.
+ * A member with a non-finite value in any row of EITHER variable gets NaN everywhere; a constant series gives 0 in its variance and
+ * NaN by 0/0: a constant x in every band output, a constant y in coh2_b (its gains are 0 / Pxx_b = 0).
+ * Equalities that follow from the definition, bit for bit:
+ *   var_x, var_y are rscm_ens_member_covariability's for the same arguments;
+ *   exchanging (var_x, mode_x) with (var_y, mode_y) leaves every coh2_b unchanged and exchanges var_x with var_y: K is symmetric in
+ *   the two state pairs and Q changes sign exactly;
+ *   with x == y every gain_quad_b is +-0.0 exactly; with y = 2 x (a diagnostic of one term of scale 2.0) coh2_b equals that of x with
+ *   itself, gain_b is exactly twice it and every gain_quad_b is +-0.0 exactly.
+ * The result is written to indicator slot `slot` (a slot's block is [3 + 8][N]: at three bands the 11 vectors fill it); slot rules and
+ * refusals are those of rscm_ens_member_covariability and rscm_ens_member_spectrum: a bad slot, mode, band count or edge list
+ * RSCM_ERR_INVALID; rows not computed or not resident, a stale diagnostic or a select in flight RSCM_ERR_STATE.  Bit-exact against
+ * the restatement. */
+#define RSCM_XSPEC_MAX_BANDS 3
+RSCM_API int rscm_ens_member_cross_spectrum(rscm_ens* h, int32_t var_x, int32_t var_y, int32_t t_begin, int32_t t_end, int32_t t_stride,
+                                            int32_t mode_x, int32_t mode_y, int32_t n_bands, const int32_t* edges, int32_t slot,
+                                            void** out_dev);
+/* out[J], J = (n - 1) / 2: g_j = the double nearest sin(2 pi j / n) at out[j - 1], the second table rscm_ens_member_cross_spectrum
+ * gives its kernel; formed as rscm_gpu_spectrum_coefficients forms the cosines (the angle folded in integers into the first octant,
+ * then evaluated in long double), within 1 ulp of sin(2 pi j / n) and always > 0 (j < n / 2).  Host only (no device is touched).
+ * 3 <= n <= 4096, else RSCM_ERR_INVALID. */
+RSCM_API int rscm_gpu_spectrum_sines(int32_t n, double* out /*[J]*/);
+
 /* ---- diagnostic variables (ABI minor 18) ---------------------------------------------------------- */
 /* A diagnostic variable of a handle is a linear combination of that handle's stored variables with per-member weights.  For member i
  * and row t, with K terms (1 <= K <= RSCM_DIAG_MAX_TERMS), x_k = row t of the stored variable term_var[k], p the parameter block:
@@ -1244,7 +1299,7 @@ RSCM_API int rscm_ens_member_covariability(rscm_ens* h, int32_t var_x, int32_t v
  * Define, compute and clear refuse with RSCM_ERR_STATE while a staged select is in flight (it may be reading the rows).
  *
  * Readers.  The id of a defined diagnostic is accepted by rscm_ens_select_begin* / rscm_ens_quantile_rows* (plain, weighted, anomaly,
- * grouped), rscm_ens_set_baseline, rscm_ens_member_indicators, _variability, _spectrum, _covariability, the stored likelihoods rscm_ens_loglik,
+ * grouped), rscm_ens_set_baseline, rscm_ens_member_indicators, _variability, _spectrum, _covariability, _cross_spectrum, the stored likelihoods rscm_ens_loglik,
  * _device, _ref, _ref_device (observation rows and reference-period rows), rscm_ens_summary and rscm_ens_get_series.  A row outside
  * the held range is to them what a row that is not resident is on a windowed handle: RSCM_ERR_STATE.  Everything else keeps refusing
  * the id as it refuses any var_id >= V (RSCM_ERR_INVALID): rscm_ens_series_devptr, rscm_ens_summary_series, rscm_ens_quantile_series,

@@ -38,6 +38,7 @@ SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
 DIAG_MAX_TERMS, DIAG_MAX = 4, 4    # RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX: terms per diagnostic variable, diagnostics per handle
 VAR_MEAN, VAR_LINEAR, VAR_DIFFERENCE = 0, 1, 2   # rscm_ens_member_variability's detrending modes
 COV_MAX_LAGS = 3                                  # rscm_ens_member_covariability: 0 .. 3 leads and lags
+XSPEC_MAX_BANDS = 3                               # rscm_ens_member_cross_spectrum: 1 .. 3 bands (RSCM_XSPEC_MAX_BANDS)
 
 TL_VARS = {"Effective Radiative Forcing": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2}
 CP_VARS = {"Emissions|CO2|Anthropogenic": 0, "Surface Temperature": 1, "Deep Ocean Temperature": 2,
@@ -351,6 +352,9 @@ SIGNATURES = {
     "rscm_ens_member_spectrum": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_int32,
                                            C.POINTER(C.c_void_p)]),
     "rscm_gpu_spectrum_coefficients": (C.c_int, [C.c_int32, _dp]),
+    "rscm_ens_member_cross_spectrum": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                                 C.POINTER(C.c_int32), C.c_int32, C.POINTER(C.c_void_p)]),
+    "rscm_gpu_spectrum_sines": (C.c_int, [C.c_int32, _dp]),
     "rscm_ens_loglik_spectrum_device": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), _dp, C.POINTER(C.c_int32), _dp, C.POINTER(C.c_void_p)]),
     "rscm_ens_define_diagnostic": (C.c_int, [_h, C.c_int32, _ip, _ip, _dp, _ip]),
     "rscm_ens_diagnostic": (C.c_int, [_h, C.c_int32, _ip, _ip, _ip, _dp, _ip, _ip, _ip]),

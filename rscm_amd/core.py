@@ -1511,7 +1511,7 @@ class GraphModel:
         """``Ensemble.define_diagnostic`` on the home ensemble the terms' variables share: ``terms`` is a sequence of
         ``(variable name, parameter or None[, scale])``, the parameter a row of that ensemble or a name of ``param_home``
         (``"Type.name"``, or the bare name where it is unique) that lives there.  ``variable_home(name)`` then resolves the
-        diagnostic, so ``quantile_rows``, ``indicators``, ``variability``, ``spectrum``, ``covariability``, ``set_baseline`` and ``get_series`` take it
+        diagnostic, so ``quantile_rows``, ``indicators``, ``variability``, ``spectrum``, ``covariability``, ``cross_spectrum``, ``set_baseline`` and ``get_series`` take it
         by name.  Variables of two ensembles: ``ValueError`` (a diagnostic does not cross handles)."""
         if name in self._diagnostics or name in self._var_home:
             raise ValueError(f"variable name {name!r} is taken")
@@ -1602,6 +1602,16 @@ class GraphModel:
         if ens_x is not ens_y:
             raise ValueError(f"covariability: {name_x!r} and {name_y!r} live in different ensembles; both variables must share one home")
         return ens_x.covariability(vid_x, vid_y, t_begin, t_end, t_stride, detrend_x, detrend_y, lags, slot)
+
+    def cross_spectrum(self, name_x: str, name_y: str, t_begin: int, t_end: int, t_stride: int = 1, detrend_x: str = "linear",
+                       detrend_y: str = "linear", bands=3, slot: int = 0) -> Dict[str, object]:
+        """``Ensemble.cross_spectrum`` of ``name_x`` and ``name_y`` on the home ensemble the two share: device vectors ``var_x``,
+        ``var_y`` and per band ``coherence2``, ``gain``, ``gain_quad``, with the bands' ``edges`` and ``counts``.  Variables of two
+        ensembles: ``ValueError`` (the statistic does not cross handles)."""
+        (ens_x, vid_x), (ens_y, vid_y) = self.variable_home(name_x), self.variable_home(name_y)
+        if ens_x is not ens_y:
+            raise ValueError(f"cross_spectrum: {name_x!r} and {name_y!r} live in different ensembles; both variables must share one home")
+        return ens_x.cross_spectrum(vid_x, vid_y, t_begin, t_end, t_stride, detrend_x, detrend_y, bands, slot)
 
     def spectrum(self, name: str, t_begin: int, t_end: int, t_stride: int = 1, detrend: str = "difference", bands=8,
                  slot: int = 0) -> Dict[str, object]:

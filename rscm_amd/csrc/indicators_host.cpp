@@ -5,6 +5,8 @@
 // Also of the per-member band powers (rscm_ens_member_spectrum), their coefficient table (rscm_gpu_spectrum_coefficients) and the
 // spectral likelihood over band powers (rscm_ens_loglik_spectrum_device); kernels in spectrum.hip.
 // Also of the per-member covariability of two variables (rscm_ens_member_covariability); kernel in covariability.hip.
+// Also of their co-spectra in frequency bands (rscm_ens_member_cross_spectrum) and its sine table (rscm_gpu_spectrum_sines); kernel in
+// cross_spectrum.hip.
 //
 // Rows are resolved as the radix select resolves them (resolve_rows: full storage, the window, the output store) and must all be
 // computed.  The baseline and the indicator slots are handle-owned and kept across run and rewind, as the member weights are; a
@@ -117,6 +119,8 @@ static_assert(rscm::kVarMean == RSCM_VAR_MEAN && rscm::kVarLinear == RSCM_VAR_LI
 static_assert(5 <= 3 + rscm::kMaxThresholds, "the variability statistics share the indicator slots");
 static_assert(rscm::kCovMaxLags == RSCM_COV_MAX_LAGS && 5 + 2 * RSCM_COV_MAX_LAGS <= 3 + rscm::kMaxThresholds,
               "the covariability statistics at every lag share the indicator slots");
+static_assert(rscm::kMaxCrossSpectrumBands == RSCM_XSPEC_MAX_BANDS && 2 + 3 * RSCM_XSPEC_MAX_BANDS <= 3 + rscm::kMaxThresholds,
+              "the cross-spectrum statistics of every band share the indicator slots");
 
 constexpr int32_t kSpectrumMaxTerms = 4096;   // the cap on the working series' length that bounds the recurrence's error
 
@@ -142,6 +146,37 @@ void spectrum_coefficients(int32_t n, double* c2)
         const double C = (double)v;
         c2[j - 1] = 2.0 * (neg ? -C : C);
     }
+}
+
+// g[j - 1] = the double nearest sin(2 pi j / n), j = 1 .. (n - 1) / 2: the same angle pi p / q, folded in integers into the first quadrant
+// (p -> q - p: the sine keeps its sign) and then into the first octant, where the sine of the complement is the cosine of what is left;
+// 2 p == q is 1.0 exactly.  j < n / 2 keeps every entry > 0.
+void spectrum_sines(int32_t n, double* g)
+{
+    const long double pi = 3.14159265358979323846264338327950288L;
+    const int64_t q = n;
+    for (int64_t j = 1; j <= (n - 1) / 2; ++j) {
+        int64_t p = 2 * j;
+        if (2 * p > q) p = q - p;
+        long double v;
+        if (2 * p == q)
+            v = 1.0L;
+        else if (4 * p <= q)
+            v = sinl(pi * (long double)p / (long double)q);
+        else
+            v = cosl(pi * (long double)(q - 2 * p) / (long double)(2 * q));
+        g[j - 1] = (double)v;
+    }
+}
+
+// The band list of rscm_ens_member_spectrum and rscm_ens_member_cross_spectrum against a working series of n terms
+int check_band_edges(int64_t n, int32_t n_bands, const int32_t* edges)
+{
+    const int32_t J = (int32_t)((n - 1) / 2);
+    if (edges[0] < 1 || edges[n_bands] > J + 1) return fail(RSCM_ERR_INVALID, "the band edges must lie in [1, %d] (J + 1 of %lld terms)", J + 1, (long long)n);
+    for (int32_t b = 0; b < n_bands; ++b)
+        if (edges[b] >= edges[b + 1]) return fail(RSCM_ERR_INVALID, "the band edges must be strictly ascending (edge %d)", b + 1);
+    return RSCM_OK;
 }
 
 // What the two likelihoods over per-member vectors check once their own numbers are in: every vector and add_dev (may be null) is a
@@ -367,9 +402,7 @@ int rscm_ens_member_spectrum(rscm_ens* h, int32_t var_id, int32_t t_begin, int32
     if (int rc = working_series(rows.size(), mode, kSpectrumMaxTerms, &w)) return rc;
     const int64_t n = w.n;
     const int32_t J = (int32_t)((n - 1) / 2);
-    if (edges[0] < 1 || edges[n_bands] > J + 1) return fail(RSCM_ERR_INVALID, "the band edges must lie in [1, %d] (J + 1 of %lld terms)", J + 1, (long long)n);
-    for (int32_t b = 0; b < n_bands; ++b)
-        if (edges[b] >= edges[b + 1]) return fail(RSCM_ERR_INVALID, "the band edges must be strictly ascending (edge %d)", b + 1);
+    if (int rc = check_band_edges(n, n_bands, edges)) return rc;
     // the table the kernel is given: c2[J], kSpectrumTablePad zeros the last tile may read, then the edges (8-byte aligned: int32 pairs)
     const size_t n_c2 = (size_t)J + rscm::kSpectrumTablePad;
     std::vector<double> table(n_c2 + (size_t)(n_bands + 2) / 2, 0.0);
@@ -384,6 +417,64 @@ int rscm_ens_member_spectrum(rscm_ens* h, int32_t var_id, int32_t t_begin, int32
     HIPCHK(hipMemcpyAsync(d_table.get(), table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(rscm::launch_spectrum(d_rows.get(), (int32_t)rows.size(), mode, w.stt, d_table.get(),
                                  reinterpret_cast<const int32_t*>(d_table.get() + n_c2), n_bands, h->N, h->d_ind[slot], h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out_dev = h->d_ind[slot];
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_gpu_spectrum_sines(int32_t n, double* out)
+{
+    GUARD_BEGIN
+    if (n < 3 || n > kSpectrumMaxTerms) return fail(RSCM_ERR_INVALID, "n = %d: the working series has 3 to %d terms", n, kSpectrumMaxTerms);
+    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
+    spectrum_sines(n, out);
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_member_cross_spectrum(rscm_ens* h, int32_t var_x, int32_t var_y, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t mode_x,
+                                   int32_t mode_y, int32_t n_bands, const int32_t* edges, int32_t slot, void** out_dev)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!out_dev) return fail(RSCM_ERR_INVALID, "out_dev is NULL");
+    *out_dev = nullptr;
+    if (int rc = check_slot(slot)) return rc;
+    if (int rc = check_detrending(mode_x)) return rc;
+    if (int rc = check_detrending(mode_y)) return rc;
+    if (n_bands < 1 || n_bands > RSCM_XSPEC_MAX_BANDS || !edges)
+        return fail(RSCM_ERR_INVALID, "bad band list (1 to %d bands, n_bands + 1 edges)", RSCM_XSPEC_MAX_BANDS);
+    if (int rc = no_select(h)) return rc;
+    std::vector<const double*> rows_x, rows_y;
+    std::vector<double> times_x, times_y;
+    if (int rc = period_rows(h, var_x, t_begin, t_end, t_stride, rows_x, times_x)) return rc;
+    if (int rc = period_rows(h, var_y, t_begin, t_end, t_stride, rows_y, times_y)) return rc;
+    // the common length of rscm_ens_member_covariability's working series, under the spectrum's cap
+    const bool differenced = mode_x == RSCM_VAR_DIFFERENCE || mode_y == RSCM_VAR_DIFFERENCE;
+    WorkingSeries w;
+    if (int rc = working_series(rows_x.size(), differenced ? RSCM_VAR_DIFFERENCE : RSCM_VAR_MEAN, kSpectrumMaxTerms, &w)) return rc;
+    const int64_t n = w.n;
+    const int32_t J = (int32_t)((n - 1) / 2);
+    if (int rc = check_band_edges(n, n_bands, edges)) return rc;
+    // the one table the kernel is given: c2[J] and the sines g[J], each followed by kSpectrumTablePad zeros the last tile may read, then
+    // the edges (8-byte aligned: int32 pairs)
+    const size_t n_tab = (size_t)J + rscm::kSpectrumTablePad;
+    std::vector<double> table(2 * n_tab + (size_t)(n_bands + 2) / 2, 0.0);
+    spectrum_coefficients((int32_t)n, table.data());
+    spectrum_sines((int32_t)n, table.data() + n_tab);
+    std::memcpy(table.data() + 2 * n_tab, edges, (size_t)(n_bands + 1) * sizeof(int32_t));
+    if (int rc = set_device(h)) return rc;
+    if (int rc = slot_buffer(h, slot)) return rc;
+    rscm::DevBuf<const double*> d_rows_x, d_rows_y;
+    rscm::DevBuf<double> d_table;
+    if (int rc = upload_rows(h, rows_x, d_rows_x)) return rc;
+    if (int rc = upload_rows(h, rows_y, d_rows_y)) return rc;
+    HIPCHK(d_table.alloc(table.size()));
+    HIPCHK(hipMemcpyAsync(d_table.get(), table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_cross_spectrum(d_rows_x.get(), d_rows_y.get(), (int32_t)rows_x.size(), mode_x, mode_y, w.stt, d_table.get(),
+                                       d_table.get() + n_tab, reinterpret_cast<const int32_t*>(d_table.get() + 2 * n_tab), n_bands, h->N,
+                                       h->d_ind[slot], h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     *out_dev = h->d_ind[slot];
     return RSCM_OK;

@@ -948,6 +948,16 @@ constexpr int kSpectrumTablePad = 32;
 static_assert(kMaxSpectrumBands <= kMaxThresholds, "the band powers share the indicator slots: [3 + kMaxThresholds][N]");
 hipError_t launch_spectrum(const double* const* d_rows, int32_t n_rows, int32_t mode, double stt, const double* d_c2, const int32_t* d_edges,
                            int32_t n_bands, int64_t N, double* d_out, hipStream_t s);
+// per-member co-spectra of two variables in frequency bands (cross_spectrum.hip) over rows d_rows_x[n_rows][N] and d_rows_y[n_rows][N],
+// modes and stt as launch_covariability: d_out[2 + 3 n_bands][N] = var_x, var_y, then per band the squared coherence, the gain of y on
+// x and its quadrature part (the definition is stated in include/rscm_gpu.h, rscm_ens_member_cross_spectrum).  d_c2 as launch_spectrum's;
+// d_sin[J] = sin(2 pi j / n) at d_sin[j - 1] (rscm_gpu_spectrum_sines), padded by kSpectrumTablePad zeros like d_c2; d_edges as
+// launch_spectrum's with 1 <= n_bands <= kMaxCrossSpectrumBands: the caller has checked them
+constexpr int kMaxCrossSpectrumBands = 3;
+static_assert(2 + 3 * kMaxCrossSpectrumBands <= 3 + kMaxThresholds, "the cross-spectrum statistics share the indicator slots: [3 + kMaxThresholds][N]");
+hipError_t launch_cross_spectrum(const double* const* d_rows_x, const double* const* d_rows_y, int32_t n_rows, int32_t mode_x, int32_t mode_y,
+                                 double stt, const double* d_c2, const double* d_sin, const int32_t* d_edges, int32_t n_bands, int64_t N,
+                                 double* d_out, hipStream_t s);
 // d_out[i] = (d_add ? d_add[i] : 0.0) + sum over j < n_vec of count[j] (ln vec[j][i] - 2 ln(vec[j][i] + record[j])), -inf where a
 // vec[j][i] is not finite or <= 0 or d_add[i] is not finite; d_add may be d_out.  count[j] is the band's number of ordinates as a double.
 struct LoglikSpectrum {

@@ -672,6 +672,41 @@ class Ensemble:
         vec = [DeviceVector(base + 8 * n * j, n, np.float64, self) for j in range(5 + 2 * lags)]
         return {"var_x": vec[0], "var_y": vec[1], "cov": vec[2], "corr": vec[3], "slope": vec[4], "lead": vec[5::2], "lag": vec[6::2]}
 
+    def cross_spectrum(self, x, y, t_begin: int, t_end: int, t_stride: int = 1, detrend_x: str = "linear", detrend_y: str = "linear",
+                       bands=3, slot: int = 0) -> Dict[str, object]:
+        """Per-member co-spectra of the variables ``x`` and ``y`` (stored or diagnostic; they may be the same) in frequency bands over
+        the rows ``t_begin, t_begin + t_stride, ... < t_end``, left on the device in indicator slot ``slot`` (the slots of
+        ``indicators``, ``variability``, ``spectrum`` and ``covariability``): ``{"var_x", "var_y", "coherence2": [one per band],
+        "gain": [..], "gain_quad": [..], "edges", "counts"}`` -- ``DeviceVector``s of ``[N]`` float64, and the band edges and the
+        number of frequencies per band as int32 arrays.  The working series and residuals are ``covariability``'s (``detrend_x``,
+        ``detrend_y``; next to a differenced partner a variable is taken at the midpoints), the frequencies and ``bands`` are
+        ``spectrum``'s, with at most 3 bands per call: a count (``rscm_amd.variability.band_edges`` then gives the edges) or 2 to 4
+        strictly ascending edges inside ``[1, J + 1]``; only the frequencies inside the edges are computed.  Per band,
+        ``coherence2`` is the squared coherence of the two residual series, ``gain`` the in-phase transfer of ``y`` on ``x`` (the
+        band's co-spectrum over the power of ``x``: uptake per degree) and ``gain_quad`` the out-of-phase part, positive where
+        ``x`` leads ``y``.  The definition is ``rscm_amd.variability.series_cross_spectrum``'s, bit for bit
+        (rscm_ens_member_cross_spectrum).  3 to 4096 terms; a member with a non-finite value in any row of either variable has NaN
+        everywhere, a constant series NaN in the band vectors."""
+        from .variability import band_edges, detrend_mode
+        mode_x, mode_y = detrend_mode(detrend_x), detrend_mode(detrend_y)
+        n = len(range(int(t_begin), int(t_end), max(int(t_stride), 1))) - (1 if L.VAR_DIFFERENCE in (mode_x, mode_y) else 0)
+        if isinstance(bands, (int, np.integer)):
+            if not 1 <= int(bands) <= L.XSPEC_MAX_BANDS:
+                raise ValueError(f"bands: 1 to {L.XSPEC_MAX_BANDS} bands per call, got {int(bands)}")
+            edges = band_edges(n, int(bands)) if n >= 3 else np.array([1, 2], dtype=np.int32)    # (too short a series: the call refuses it)
+        else:
+            edges = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).ravel())
+            if edges.size < 2:
+                raise ValueError("bands: an explicit edge list needs at least two edges")
+        p = C.c_void_p()
+        L.check(self._lib.rscm_ens_member_cross_spectrum(self._h, self._var(x), self._var(y), int(t_begin), int(t_end), int(t_stride), mode_x,
+                                                         mode_y, edges.size - 1, edges.ctypes.data_as(C.POINTER(C.c_int32)), int(slot),
+                                                         C.byref(p)))
+        nm, base = self.n_members, p.value
+        vec = [DeviceVector(base + 8 * nm * j, nm, np.float64, self) for j in range(2 + 3 * (edges.size - 1))]
+        return {"var_x": vec[0], "var_y": vec[1], "coherence2": vec[2::3], "gain": vec[3::3], "gain_quad": vec[4::3], "edges": edges,
+                "counts": np.diff(edges).astype(np.int32)}
+
     def loglik_vectors(self, vectors, values, sigmas, add_to: Optional[DeviceVector] = None) -> DeviceVector:
         """Gaussian log-likelihood per member over per-member device vectors (variability statistics, indicators,
         ``params_vector`` rows): ``sum_j -0.5 ((values[j] - vectors[j][i]) / sigmas[j])^2``, added onto ``add_to`` -- a device

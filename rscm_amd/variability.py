@@ -5,7 +5,9 @@ over the rows, so a record put through this function and the same values put thr
 
 The same for the band powers of ``Ensemble.spectrum`` (rscm_ens_member_spectrum): ``series_spectrum`` with the default band edges of
 ``band_edges`` and the library's own coefficient table (``spectrum_coefficients``), and for the covariability of two series
-(``Ensemble.covariability``, rscm_ens_member_covariability): ``series_covariability``."""
+(``Ensemble.covariability``, rscm_ens_member_covariability): ``series_covariability``, and for their co-spectra in frequency bands
+(``Ensemble.cross_spectrum``, rscm_ens_member_cross_spectrum): ``series_cross_spectrum`` with the library's sine table
+(``spectrum_sines``)."""
 import ctypes as C
 from typing import Dict
 
@@ -191,6 +193,16 @@ def spectrum_coefficients(n: int) -> np.ndarray:
     return out
 
 
+def spectrum_sines(n: int) -> np.ndarray:
+    """``[J]`` float64, ``J = (n - 1) // 2``: ``g_j`` = the double nearest ``sin(2 pi j / n)`` at ``[j - 1]``, from the library
+    (rscm_gpu_spectrum_sines) -- the second table the cross-spectrum kernel is given.  ``3 <= n <= 4096``.  Needs the built library,
+    not a GPU."""
+    n = int(n)
+    out = np.empty(max((n - 1) // 2, 0), dtype=np.float64)
+    L.check(L.load().rscm_gpu_spectrum_sines(n, out.ctypes.data_as(C.POINTER(C.c_double)) if out.size else None))
+    return out
+
+
 def _series_residuals(u, mode):
     """(a [n][N], m, b, C0) of the working series ``u`` [n][N]: its residuals, mean, slope and their sum of squares, with the
     operations of ``series_variability``."""
@@ -268,6 +280,74 @@ def series_spectrum(x, detrend: str = "difference", edges=None) -> Dict[str, obj
     if single:
         out = {"mean": float(out["mean"][0]), "slope": float(out["slope"][0]), "variance": float(out["variance"][0]),
                "power": [float(p[0]) for p in out["power"]]}
+    out["edges"] = edges
+    out["counts"] = np.diff(edges).astype(np.int32)
+    return out
+
+
+XSPEC_MAX_BANDS = L.XSPEC_MAX_BANDS
+
+
+def series_cross_spectrum(x, y, detrend_x: str = "linear", detrend_y: str = "linear", edges=None) -> Dict[str, object]:
+    """``{"var_x", "var_y", "coherence2": [one per band], "gain": [..], "gain_quad": [..], "edges", "counts"}`` of the series ``x``
+    and ``y``: both ``[R]`` (floats come back) or both ``[R][N]`` (rows by members: arrays of ``[N]``) --
+    ``Ensemble.cross_spectrum`` for a record.  ``detrend_x`` and ``detrend_y`` and the pairing at the midpoints as
+    ``series_covariability``; ``edges`` the band edges, 1 to 3 bands (default ``band_edges(n, 3)``).  Per band: the squared
+    coherence of the two residual series, the gain of ``y`` on ``x`` (co-spectrum over the power of ``x``) and its quadrature part
+    (positive where ``x`` leads), from two Goertzel recurrences over the residuals with the library's tables.  Operation for
+    operation the definition of rscm_ens_member_cross_spectrum: what the kernel gives for the same values, bit for bit.  3 to 4096
+    terms in the working series.  A non-finite value in either series gives NaN everywhere; a constant series variance 0 and NaN in
+    the band statistics."""
+    mode_x, mode_y = detrend_mode(detrend_x), detrend_mode(detrend_y)
+    rx, ry = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+    if rx.ndim not in (1, 2) or rx.shape != ry.shape:
+        raise ValueError(f"series_cross_spectrum: two series of one shape [R] or [R][N] expected, got {rx.shape} and {ry.shape}")
+    single = rx.ndim == 1
+    if single:
+        rx, ry = rx[:, None], ry[:, None]
+    n = rx.shape[0] - (1 if L.VAR_DIFFERENCE in (mode_x, mode_y) else 0)
+    if n < 3 or n > MAX_TERMS:
+        raise ValueError(f"series_cross_spectrum: the working series has {n} terms, 3 to {MAX_TERMS} are needed")
+    edges = band_edges(n, XSPEC_MAX_BANDS) if edges is None else check_edges(n, edges)
+    if edges.size - 1 > XSPEC_MAX_BANDS:
+        raise ValueError(f"series_cross_spectrum: 1 to {XSPEC_MAX_BANDS} bands, got {edges.size - 1}")
+    c2, g = spectrum_coefficients(n), spectrum_sines(n)
+    lo, hi = int(edges[0]), int(edges[-1])
+    bad = ~(np.isfinite(rx).all(axis=0) & np.isfinite(ry).all(axis=0))
+    dn = float(n)
+    with np.errstate(all="ignore"):
+        a, _, _, Cxx = _series_residuals(_pair_series(rx, mode_x, mode_y), mode_x)
+        c, _, _, Cyy = _series_residuals(_pair_series(ry, mode_y, mode_x), mode_y)
+        cf, gf = c2[lo - 1:hi - 1, None], g[lo - 1:hi - 1, None]         # [F][1] against the members' [N]
+        s1 = np.zeros((hi - lo, rx.shape[1]))
+        s2, t1, t2 = np.zeros_like(s1), np.zeros_like(s1), np.zeros_like(s1)
+        for k in range(n):
+            s0 = (a[k] + cf * s1) - s2
+            s2 = s1
+            s1 = s0
+            t0 = (c[k] + cf * t1) - t2
+            t2 = t1
+            t1 = t0
+        ordinates = (((s1 * s1 + s2 * s2) - (cf * s1) * s2) / dn, ((t1 * t1 + t2 * t2) - (cf * t1) * t2) / dn,
+                     ((s1 * t1 + s2 * t2) - (cf * 0.5) * (s1 * t2 + s2 * t1)) / dn, (gf * (s2 * t1 - s1 * t2)) / dn)
+        out = {"var_x": Cxx / dn, "var_y": Cyy / dn, "coherence2": [], "gain": [], "gain_quad": []}
+        for e0, e1 in zip(edges[:-1], edges[1:]):
+            mean = []
+            for I in ordinates:
+                acc = I[e0 - lo].copy()
+                for j in range(int(e0) + 1, int(e1)):
+                    acc = acc + I[j - lo]
+                mean.append(acc / float(int(e1) - int(e0)))
+            Pxx, Pyy, K, Q = mean
+            D = np.sqrt(Pxx) * np.sqrt(Pyy)
+            kc, qc = K / D, Q / D
+            out["coherence2"].append(kc * kc + qc * qc)
+            out["gain"].append(K / Pxx)
+            out["gain_quad"].append(Q / Pxx)
+    nan = lambda v: np.where(bad, np.nan, v)
+    out = {k: [nan(w) for w in v] if isinstance(v, list) else nan(v) for k, v in out.items()}
+    if single:
+        out = {k: [float(w[0]) for w in v] if isinstance(v, list) else float(v[0]) for k, v in out.items()}
     out["edges"] = edges
     out["counts"] = np.diff(edges).astype(np.int32)
     return out

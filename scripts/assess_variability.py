@@ -40,7 +40,16 @@ the temperature at the midpoints, linearly detrended -- ``rscm_amd.variability.s
 terms times ``sqrt(2)``: ``(1 - r^2) / sqrt(n)`` for the correlations, ``sqrt((var_y - slope cov) / (n var_x))`` for the slope.  The
 effective sample size and the 5-50-95 % ranges of sigma, phi, lambda0, the efficacy and the two heat capacities are printed.
 
+With ``--cross-spectrum`` (it requires ``--heat-content`` too) the relation is scored per frequency band: the
+squared coherence, the gain and the quadrature gain of the heat content's differences on the temperature at the midpoints, linearly
+detrended, in three bands -- ``rscm_amd.variability.series_cross_spectrum(temperature, heat, "linear", "difference")`` of the record
+against ``Ensemble.cross_spectrum`` of every member, scored by ``loglik_vectors`` alone ("cross_spectrum") and added onto the
+likelihoods before it ("all").  The sigmas are the usual large-sample ones for a band of m ordinates,
+``sqrt((1 - coh2) / (2 m coh2)) |gain|`` for both gains (``|gain|`` the magnitude of the complex gain, ``hypot(gain, gain_quad)``) and ``sqrt(2 / m) (1 - coh2) sqrt(coh2)`` for coh2, at the record's values,
+times ``sqrt(2)`` as for every other target here (record and member are one realisation each).
+
     python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content] [--covariability]
+                                         [--cross-spectrum]
 
 Prints one JSON line; exit code 0 iff every comparison holds."""
 import argparse
@@ -53,7 +62,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import rscm_amd  # noqa: E402
-from rscm_amd.variability import series_covariability, series_spectrum, series_variability  # noqa: E402
+from rscm_amd.variability import series_covariability, series_cross_spectrum, series_spectrum, series_variability  # noqa: E402
 
 Q = [0.05, 0.17, 0.5, 0.83, 0.95]
 YEARS = np.arange(1850.0, 2101.0)
@@ -96,9 +105,13 @@ def main():
     ap.add_argument("--heat-content", action="store_true", help="also weight by the variability of the record's ocean heat content")
     ap.add_argument("--covariability", action="store_true",
                     help="also weight by the covariability of the record's heat uptake and temperature (requires --heat-content)")
+    ap.add_argument("--cross-spectrum", action="store_true",
+                    help="also weight by the band coherence and gains of the record's heat uptake on its temperature (requires --heat-content)")
     a = ap.parse_args()
     if a.covariability and not a.heat_content:
         ap.error("--covariability requires --heat-content")
+    if a.cross_spectrum and not a.heat_content:
+        ap.error("--cross-spectrum requires --heat-content")
     mode = rscm_amd.MODE_FAST if a.fast else rscm_amd.MODE_EXACT
 
     # the record: one member with known amplitude and persistence, a seed of its own
@@ -241,6 +254,61 @@ def main():
             checks["covariability_equals_the_host_estimator"] = bool(all(
                 np.array_equal(d.to_host()[:64], h, equal_nan=True) for d, h in zip(cstats, [one["corr"], one["slope"], one["lead"][0], one["lag"][0]])))
 
+        xspec = None
+        if a.cross_spectrum:
+            # the relation per frequency band, alone and continued from every likelihood above
+            xnamed = {"sigma": sigma_row, "phi": phi_row, "lambda0": 0, "efficacy": 2, "heat_capacity_surface": 4, "heat_capacity_deep": 5}
+            xvec = [ens.params_vector(r) for r in xnamed.values()]
+
+            def xweigh(l):
+                ens.set_weights_from_loglik(l)
+                q = ens.quantile_vectors(xvec, q3, weighted=True)["quantiles"]
+                return {"ess": ens.weights_stats()["ess"], **{k: q[j].tolist() for j, k in enumerate(xnamed)}}
+
+            # the likelihoods before this one, formed again: the handle has ONE likelihood vector and four slots, and the branches above
+            # have reused both (the covariability branch ends on its own likelihood alone, in the spectrum's slot)
+            lls = ens.loglik_vectors(stats, values, sigmas)
+            if a.spectrum:
+                spec = ens.spectrum(TS, 0, NOW + 1, detrend="difference", bands=rec["edges"], slot=1)
+                lls = ens.loglik_spectrum(spec["power"], rec["power"], rec["counts"], add_to=lls)
+            lls = ens.loglik_vectors([hvar["sd"], hvar["r1"]], hvalues, hsigmas, add_to=lls)
+            if a.spectrum:
+                lls = ens.loglik_spectrum(hspec["power"], hrec["power"], hrec["counts"], add_to=lls)
+            if a.covariability:
+                c = ens.covariability(TS, hid, 0, NOW + 1, 1, "linear", "difference", 1, slot=1)
+                lls = ens.loglik_vectors([c["corr"], c["slope"], c["lead"][0], c["lag"][0]], cvalues, csigmas, add_to=lls)
+            xt = series_cross_spectrum(annual, annual_heat, "linear", "difference")
+            x = ens.cross_spectrum(TS, hid, 0, NOW + 1, 1, "linear", "difference", xt["edges"], slot=0)
+            xnames, xvalues, xsigmas, xstats = [], [], [], []
+            for b, m in enumerate(xt["counts"]):
+                coh2 = xt["coherence2"][b]
+                # |gain| is the magnitude of the complex gain: its in-phase and quadrature parts carry the same error
+                gsig = np.sqrt(2.0) * np.sqrt((1.0 - coh2) / (2.0 * m * coh2)) * np.hypot(xt["gain"][b], xt["gain_quad"][b])
+                for key, sig in (("coherence2", np.sqrt(2.0) * np.sqrt(2.0 / m) * (1.0 - coh2) * np.sqrt(coh2)),
+                                 ("gain", gsig), ("gain_quad", gsig)):
+                    if np.isfinite(sig) and sig > 0.0:         # (a band of one ordinate has coh2 = 1: no sampling error to score against)
+                        xnames.append(f"{key}_{b}")
+                        xvalues.append(float(xt[key][b]))
+                        xsigmas.append(float(sig))
+                        xstats.append(x[key][b])
+            xspec = {"quantiles": q3, "edges": xt["edges"].tolist(), "counts": xt["counts"].tolist(), "target": dict(zip(xnames, xvalues)),
+                     "target_sigma": dict(zip(xnames, xsigmas)),
+                     "prior": {k: q.tolist() for k, q in zip(xnamed, ens.quantile_vectors(xvec, q3)["quantiles"])}}
+            xspec["before"] = xweigh(lls)
+            xspec["all"] = xweigh(ens.loglik_vectors(xstats, xvalues, xsigmas, add_to=lls))
+            xspec["cross_spectrum"] = xweigh(ens.loglik_vectors(xstats, xvalues, xsigmas))
+            w = ens.member_weights()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                want = [np.nanquantile(P[r], q3, weights=w, method="inverted_cdf").tolist() for r in xnamed.values()]
+            checks["cross_spectrum_weighted_quantiles_equal_numpy"] = bool(want == [xspec["cross_spectrum"][k] for k in xnamed])
+            # 64 members' vectors against the host estimator on their own rows, bit for bit
+            one = series_cross_spectrum(ens.get_series(TS, 0, NOW + 1)[:, :64], ens.get_series(hid, 0, NOW + 1)[:, :64], "linear", "difference",
+                                        xt["edges"])
+            checks["cross_spectrum_equals_the_host_estimator"] = bool(all(
+                np.array_equal(x[key][b].to_host()[:64], one[key][b], equal_nan=True)
+                for key in ("coherence2", "gain", "gain_quad") for b in range(len(xt["counts"]))))
+
     res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
            "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
            "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
@@ -258,6 +326,8 @@ def main():
         res["heat_content"] = heat
     if cov is not None:
         res["covariability"] = cov
+    if xspec is not None:
+        res["cross_spectrum"] = xspec
     print(json.dumps(res), flush=True)
     sys.exit(0 if all(checks.values()) else 1)
 
