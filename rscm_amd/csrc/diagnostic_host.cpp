@@ -16,12 +16,6 @@ static_assert(rscm::kDiagMaxTerms == RSCM_DIAG_MAX_TERMS, "the term limit in dia
 
 namespace {
 
-int no_select(const rscm_ens* h)
-{
-    if (h->select) return fail(RSCM_ERR_STATE, "a select is in flight on this handle: rscm_ens_select_end it first");
-    return RSCM_OK;
-}
-
 int check_is_diagnostic(const rscm_ens* h, int32_t var_id)
 {
     if (!h->is_diagnostic(var_id))

@@ -383,6 +383,13 @@ int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_e
 // (indicators_host.cpp): what the per-member statistics and the diagnostics' sources go through
 int period_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                 std::vector<double>& times);
+// What the readers of such rows share besides (indicators_host.cpp): RSCM_ERR_STATE while a staged select is in flight; the device
+// array of the row pointers, enqueued on the handle's stream (rows must live until the caller has synchronised it); the check of an
+// indicator slot, and the slot's buffer d_ind[slot], allocated at first use
+int no_select(const rscm_ens* h);
+int upload_rows(rscm_ens* h, const std::vector<const double*>& rows, rscm::DevBuf<const double*>& d_rows);
+int check_slot(int32_t slot);
+int slot_buffer(rscm_ens* h, int32_t slot);
 // RSCM_OK if p is device memory on h's device holding at least N doubles from p on, else RSCM_ERR_INVALID (select_host.cpp)
 int check_member_vector(const rscm_ens* h, const double* p, const char* what);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (window_host.cpp)

@@ -1,112 +1,49 @@
 // Per-member power spectra of a stored variable in frequency bands, and the spectral likelihood over band powers, for gfx950 (MI355X).
 //
-// spectrum_kernel: one thread per member over the device array of row pointers, as variability_kernel (variability.hip) reads it:
-// lanes of a wave read consecutive members of one row, so every load is coalesced, and loads are issued kSpecBatch rows at a time.
-// The statistic is the one include/rscm_gpu.h states under rscm_ens_member_spectrum; working series, m, b and the residuals a_k are
-// those of rscm_ens_member_variability, operation for operation.  All passes run in one launch:
-//   pass 1          S, Q -> m = S / n, b = Q / Stt (RSCM_VAR_LINEAR; else +0.0), and whether any row is non-finite
+// spectrum_kernel: one thread per member; working series, walk, pass 1 and the residuals a_k are those of series_walk.hpp.  The
+// statistic is the one include/rscm_gpu.h states under rscm_ens_member_spectrum.  All passes run in one launch:
+//   pass 1          m, b, and whether any row is non-finite
 //   one pass per    tile of kSpecF frequencies j0 .. j0 + kSpecF - 1: the lane keeps s1, s2 of Goertzel's recurrence for every
-//   tile            frequency of the tile in registers (4 kSpecF VGPRs), re-forms a_k from the rows -- one expression, residual(), so
-//                   its bits cannot depend on the tile -- and advances all kSpecF recurrences with it:
+//   tile            frequency of the tile in registers (4 kSpecF VGPRs), re-forms a_k from the rows and advances all kSpecF
+//                   recurrences with it:
 //                       s0 = (a_k + c2_j * s1) - s2;  s2 = s1;  s1 = s0
-//                   (the two register sets exchange their names at every term, not their values: walk_terms hands the parity on)
+//                   (the two register sets exchange their names at every term, not their values: the walk hands the parity on)
 //                   kSpecF independent dependency chains per lane, three f64 operations per term and frequency, no memory operand
 //                   but the residual.  The first tile also forms C0 = a_0 a_0 + a_1 a_1 + ...
 //   after a tile    I_j = ((s1 s1 + s2 s2) - (c2_j s1) s2) / n in ascending j, added to the running band sum, which is carried in a
 //                   register across tiles; a band that ends at j is divided by its count and stored
-// Every operation is one f64 operation rounded on its own (-ffp-contract=off: no FMA); sums start at -0.0, the additive identity,
-// which is "starting from the first term" bit for bit.  c2_j = 2 cos(2 pi j / n) comes from the table the host uploads per call
-// (rscm_gpu_spectrum_coefficients), followed in the same allocation by the band edges; both are read at wave-uniform addresses, once
-// per tile and per band, so they travel as scalar loads and the coefficients sit in SGPRs during the pass.  Only the frequencies
-// inside [edges[0], edges[n_bands]) are computed; the last tile may be partial, and its idle recurrences run on the zeros the table
-// is padded with.  No per-member array, no scratch, no LDS.  Row traffic: 8 B x R x N x (1 + tiles).
+// c2_j = 2 cos(2 pi j / n) comes from the table the host uploads per call (rscm_gpu_spectrum_coefficients), followed in the same
+// allocation by the band edges; both are read at wave-uniform addresses, once per tile and per band, so they travel as scalar loads
+// and the coefficients sit in SGPRs during the pass.  Only the frequencies inside [edges[0], edges[n_bands]) are computed; the last
+// tile may be partial, and its idle recurrences run on the zeros the table is padded with.  Row traffic: 8 B x R x N x (1 + tiles).
 //
 // loglik_spectrum_kernel: out[i] = (add ? add[i] : 0.0) + sum_b m_b (ln P_b[i] - 2 ln(P_b[i] + I_b)) with log_f64 (rk4_device.hpp),
 // the expressions of rscm_ens_loglik_spectrum_device; -inf where a P_b[i] is non-finite or <= 0 or add[i] is non-finite.  add may be
 // out: a thread reads its own element before it writes it.
 #include <hip/hip_runtime.h>
 
-#include <type_traits>
-
 #include "rk4_device.hpp"
 #include "rscm_device.hpp"
+#include "series_walk.hpp"
 
 namespace rscm {
 
 namespace {
 
 constexpr int kSpecThreads = 256;
-constexpr int kSpecBatch = 8;   // rows whose loads a thread issues before it uses them (kVarBatch of variability.hip)
+constexpr int kSpecBatch = 8;   // terms whose loads a thread issues before it uses them
 // Frequencies per tile.  The listing (make asm-spectrum) decides: 4 kSpecF VGPRs of recurrence state, 2 kSpecBatch of rows in flight
 // and about forty more.  16 is the widest tile that fits 128 VGPRs -- four waves per SIMD, which the kernel asks the compiler for --
 // without scratch (118 / 126 / 120 VGPRs by mode); 20 needs 152-168.  profiles/spectrum_bench.txt has the listing's figures.
 constexpr int kSpecF = 16;
 static_assert(kSpecF - 1 <= kSpectrumTablePad, "a tile reads up to kSpecF - 1 coefficients past the last frequency");
 
-// f(u_k, k, parity of k) for k = 0 .. n - 1 in order, from member i's values in the rows; u_k is the row x_k or (RSCM_VAR_DIFFERENCE)
-// x_{k+1} - x_k, with x_0 loaded ahead so that every batch holds kSpecBatch terms in every mode.  The parity travels as a type: the
-// recurrence writes even terms into one register set and odd terms into the other, so no value moves between terms.  After the
-// batches the rest goes in pairs, then a last single term.
-using Even = std::integral_constant<bool, false>;
-using Odd = std::integral_constant<bool, true>;
-template <int kMode, bool kCheck, class F>
-__device__ __forceinline__ void walk_terms(const double* const* __restrict__ rows, int32_t n, int64_t i, bool& bad, F&& f)
-{
-    static_assert(kSpecBatch % 2 == 0, "a batch keeps the parity");
-    constexpr int kOff = kMode == kVarDifference ? 1 : 0;   // the row of term k is k + kOff
-    [[maybe_unused]] double x_prev = 0.0;
-    auto term = [&](double x) {
-        if constexpr (kCheck) bad = bad || !__builtin_isfinite(x);
-        if constexpr (kMode == kVarDifference) {
-            const double u = x - x_prev;
-            x_prev = x;
-            return u;
-        } else {
-            return x;
-        }
-    };
-    if constexpr (kMode == kVarDifference) {
-        x_prev = rows[0][i];
-        if constexpr (kCheck) bad = bad || !__builtin_isfinite(x_prev);
-    }
-    int32_t k = 0;
-    for (; k + kSpecBatch <= n; k += kSpecBatch) {
-        double x[kSpecBatch];
-#pragma unroll
-        for (int j = 0; j < kSpecBatch; ++j) x[j] = rows[kOff + k + j][i];
-#pragma unroll
-        for (int j = 0; j < kSpecBatch; j += 2) {
-            f(term(x[j]), k + j, Even{});
-            f(term(x[j + 1]), k + j + 1, Odd{});
-        }
-    }
-    for (; k + 2 <= n; k += 2) {
-        const double x0 = rows[kOff + k][i], x1 = rows[kOff + k + 1][i];
-        f(term(x0), k, Even{});
-        f(term(x1), k + 1, Odd{});
-    }
-    if (k < n) f(term(rows[kOff + k][i]), k, Even{});
-}
-
-// a_k of u_k: the one expression every pass re-forms the residual with.  tau_k = (double)k - h is carried as tau_{k-1} + 1.0: with
-// n <= 4096 both are exact (multiples of 0.5 below 2^12), so these are the bits of the definition's (double)k - h.
-template <int kMode>
-__device__ __forceinline__ double residual(double u, double& tau, double m, double b)
-{
-    double a = u - m;
-    if constexpr (kMode == kVarLinear) {
-        a = a - b * tau;
-        tau = tau + 1.0;
-    }
-    return a;
-}
-
 // One pass over the rows for the frequencies j0 .. j0 + kSpecF - 1 (those past the last one idle on the table's padding); kFirst: C0 too.  On return
 // s1 holds the recurrence's last value and s2 the one before it.
-template <int kMode, bool kFirst>
-__device__ __forceinline__ void tile_pass(const double* const* __restrict__ rows, int32_t n, int64_t i, double m, double b, double h,
-                                          const double* __restrict__ c2, int32_t j0, double (&c)[kSpecF],
-                                          double (&s1)[kSpecF], double (&s2)[kSpecF], double& C0)
+template <class S, bool kFirst>
+__device__ __forceinline__ void tile_pass(const double* const* const (&rows)[1], int32_t n, int64_t i, const Detrend<1>& d,
+                                          const double* __restrict__ c2, int32_t j0, double (&c)[kSpecF], double (&s1)[kSpecF],
+                                          double (&s2)[kSpecF], double& C0)
 {
 #pragma unroll
     for (int f = 0; f < kSpecF; ++f) {
@@ -115,9 +52,12 @@ __device__ __forceinline__ void tile_pass(const double* const* __restrict__ rows
         s2[f] = 0.0;
     }
     bool unused = false;
-    [[maybe_unused]] double tau = -h;
-    walk_terms<kMode, false>(rows, n, i, unused, [&](double u, int32_t, auto odd) {
-        const double a = residual<kMode>(u, tau, m, b);
+    [[maybe_unused]] double tau = -d.h;
+    walk_terms<S, kSpecBatch, false>(rows, n, i, unused, [&](const double (&u)[1], int32_t, auto odd) {
+        double r[1];
+        residuals<S>(u, tau, d, r);
+        if constexpr (S::any_linear) tau = tau + 1.0;
+        const double a = r[0];
         if constexpr (kFirst) C0 = C0 + a * a;
 #pragma unroll
         for (int f = 0; f < kSpecF; ++f) {
@@ -142,27 +82,17 @@ __device__ __forceinline__ void tile_pass(const double* const* __restrict__ rows
 // (amdgpu_waves_per_eu(4): left alone the compiler spends the room below its next occupancy step, 130-160 VGPRs and three waves)
 template <int kMode>
 __global__ __launch_bounds__(kSpecThreads) __attribute__((amdgpu_waves_per_eu(4))) void spectrum_kernel(
-    const double* const* __restrict__ rows, int32_t n_rows, double stt, const double* __restrict__ c2, const int32_t* __restrict__ edges,
+    const double* const* __restrict__ rows_x, int32_t n_rows, double stt, const double* __restrict__ c2, const int32_t* __restrict__ edges,
     int32_t n_bands, int64_t N, double* __restrict__ out)
 {
     const int64_t i = (int64_t)blockIdx.x * kSpecThreads + threadIdx.x;
     if (i >= N) return;
-    const int32_t n = kMode == kVarDifference ? n_rows - 1 : n_rows;
-    const double dn = (double)n, h = (double)(n - 1) * 0.5;
+    using S = Series<kMode>;
+    const double* const* const rows[1] = {rows_x};
+    const int32_t n = S::terms(n_rows);
+    const double dn = (double)n;
     bool bad = false;
-
-    double S = -0.0;
-    [[maybe_unused]] double Q = -0.0;
-    walk_terms<kMode, true>(rows, n, i, bad, [&](double u, int32_t k, auto) {
-        S = S + u;
-        if constexpr (kMode == kVarLinear) {
-            const double tau = (double)k - h;
-            Q = Q + tau * u;
-        }
-    });
-    const double m = S / dn;
-    double b = 0.0;
-    if constexpr (kMode == kVarLinear) b = Q / stt;
+    const Detrend<1> d = detrend_pass<S, kSpecBatch>(rows, n, stt, i, bad);
 
     const double qnan = __builtin_nan("");
     const int32_t j_begin = edges[0], j_end = edges[n_bands];
@@ -171,9 +101,9 @@ __global__ __launch_bounds__(kSpecThreads) __attribute__((amdgpu_waves_per_eu(4)
     for (int32_t j0 = j_begin; j0 < j_end; j0 += kSpecF) {
         double c[kSpecF], s1[kSpecF], s2[kSpecF];
         if (j0 == j_begin)
-            tile_pass<kMode, true>(rows, n, i, m, b, h, c2, j0, c, s1, s2, C0);
+            tile_pass<S, true>(rows, n, i, d, c2, j0, c, s1, s2, C0);
         else
-            tile_pass<kMode, false>(rows, n, i, m, b, h, c2, j0, c, s1, s2, C0);
+            tile_pass<S, false>(rows, n, i, d, c2, j0, c, s1, s2, C0);
 #pragma unroll
         for (int f = 0; f < kSpecF; ++f) {
             const int32_t j = j0 + f;
@@ -191,8 +121,8 @@ __global__ __launch_bounds__(kSpecThreads) __attribute__((amdgpu_waves_per_eu(4)
             }
         }
     }
-    out[i] = bad ? qnan : m;
-    out[N + i] = bad ? qnan : b;
+    out[i] = bad ? qnan : d.m[0];
+    out[N + i] = bad ? qnan : d.b[0];
     out[2 * N + i] = bad ? qnan : C0 / dn;
 }
 
@@ -221,15 +151,10 @@ hipError_t launch_spectrum(const double* const* d_rows, int32_t n_rows, int32_t 
     if (N <= 0) return hipSuccess;
     if (n_bands < 1 || n_bands > kMaxSpectrumBands) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((N + kSpecThreads - 1) / kSpecThreads));
-    if (mode == kVarMean)
-        hipLaunchKernelGGL(spectrum_kernel<kVarMean>, grid, dim3(kSpecThreads), 0, s, d_rows, n_rows, stt, d_c2, d_edges, n_bands, N, d_out);
-    else if (mode == kVarLinear)
-        hipLaunchKernelGGL(spectrum_kernel<kVarLinear>, grid, dim3(kSpecThreads), 0, s, d_rows, n_rows, stt, d_c2, d_edges, n_bands, N, d_out);
-    else if (mode == kVarDifference)
-        hipLaunchKernelGGL(spectrum_kernel<kVarDifference>, grid, dim3(kSpecThreads), 0, s, d_rows, n_rows, stt, d_c2, d_edges, n_bands, N, d_out);
-    else
-        return hipErrorInvalidValue;
-    return hipGetLastError();
+    return with_mode(mode, [&](auto m) {
+        hipLaunchKernelGGL(spectrum_kernel<decltype(m)::value>, grid, dim3(kSpecThreads), 0, s, d_rows, n_rows, stt, d_c2, d_edges, n_bands, N, d_out);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_loglik_spectrum(const LoglikSpectrum& v, int32_t n_vec, const double* d_add, int64_t N, double* d_out, hipStream_t s)

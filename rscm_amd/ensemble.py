@@ -9,7 +9,7 @@ index ``time_index + 1``; ``run()`` steps to the end of the axis.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
@@ -620,6 +620,25 @@ class Ensemble:
     def clear_baseline(self) -> None:
         L.check(self._lib.rscm_ens_clear_baseline(self._h))
 
+    def _slot_vectors(self, p, count: int) -> List[DeviceVector]:
+        """The first ``count`` rows of the indicator slot at ``p`` (a ``c_void_p`` an entry point filled) as ``DeviceVector``s of ``[N]`` float64."""
+        n = self.n_members
+        return [DeviceVector(p.value + 8 * n * j, n, np.float64, self) for j in range(count)]
+
+    @staticmethod
+    def _band_edge_array(bands, n: int, max_bands: Optional[int] = None) -> np.ndarray:
+        """``bands`` -- a count (at most ``max_bands`` where given; ``band_edges`` then gives the edges for ``n`` terms) or explicit
+        edges -- as the contiguous int32 edge array the C boundary takes."""
+        from .variability import band_edges
+        if isinstance(bands, (int, np.integer)):
+            if max_bands is not None and not 1 <= int(bands) <= max_bands:
+                raise ValueError(f"bands: 1 to {max_bands} bands per call, got {int(bands)}")
+            return band_edges(n, int(bands)) if n >= 3 else np.array([1, 2], dtype=np.int32)    # (too short a series: the call refuses it)
+        edges = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).ravel())
+        if edges.size < 2:
+            raise ValueError("bands: an explicit edge list needs at least two edges")
+        return edges
+
     def indicators(self, var, t_begin: int, t_end: int, t_stride: int = 1, thresholds=(), anomaly: bool = False,
                    slot: int = 0) -> Dict[str, object]:
         """Per-member indicators of ``var`` over the rows ``t_begin, t_begin + t_stride, ... < t_end`` (of the anomaly against
@@ -631,8 +650,7 @@ class Ensemble:
         p = C.c_void_p()
         L.check(self._lib.rscm_ens_member_indicators(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride), int(bool(anomaly)),
                                                      thr.size, L.dptr(thr), int(slot), C.byref(p)))
-        n, base = self.n_members, p.value
-        vec = [DeviceVector(base + 8 * n * j, n, np.float64, self) for j in range(3 + thr.size)]
+        vec = self._slot_vectors(p, 3 + thr.size)
         return {"mean": vec[0], "peak": vec[1], "peak_time": vec[2], "crossing": vec[3:]}
 
     def variability(self, var, t_begin: int, t_end: int, t_stride: int = 1, detrend: str = "linear", slot: int = 0) -> Dict[str, object]:
@@ -647,8 +665,7 @@ class Ensemble:
         p = C.c_void_p()
         L.check(self._lib.rscm_ens_member_variability(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride), detrend_mode(detrend),
                                                       int(slot), C.byref(p)))
-        n, base = self.n_members, p.value
-        return {k: DeviceVector(base + 8 * n * j, n, np.float64, self) for j, k in enumerate(("mean", "slope", "variance", "sd", "r1"))}
+        return dict(zip(("mean", "slope", "variance", "sd", "r1"), self._slot_vectors(p, 5)))
 
     def covariability(self, x, y, t_begin: int, t_end: int, t_stride: int = 1, detrend_x: str = "linear", detrend_y: str = "linear",
                       lags: int = 0, slot: int = 0) -> Dict[str, object]:
@@ -668,8 +685,7 @@ class Ensemble:
         p = C.c_void_p()
         L.check(self._lib.rscm_ens_member_covariability(self._h, self._var(x), self._var(y), int(t_begin), int(t_end), int(t_stride),
                                                         detrend_mode(detrend_x), detrend_mode(detrend_y), lags, int(slot), C.byref(p)))
-        n, base = self.n_members, p.value
-        vec = [DeviceVector(base + 8 * n * j, n, np.float64, self) for j in range(5 + 2 * lags)]
+        vec = self._slot_vectors(p, 5 + 2 * lags)
         return {"var_x": vec[0], "var_y": vec[1], "cov": vec[2], "corr": vec[3], "slope": vec[4], "lead": vec[5::2], "lag": vec[6::2]}
 
     def cross_spectrum(self, x, y, t_begin: int, t_end: int, t_stride: int = 1, detrend_x: str = "linear", detrend_y: str = "linear",
@@ -687,23 +703,15 @@ class Ensemble:
         ``x`` leads ``y``.  The definition is ``rscm_amd.variability.series_cross_spectrum``'s, bit for bit
         (rscm_ens_member_cross_spectrum).  3 to 4096 terms; a member with a non-finite value in any row of either variable has NaN
         everywhere, a constant series NaN in the band vectors."""
-        from .variability import band_edges, detrend_mode
+        from .variability import detrend_mode
         mode_x, mode_y = detrend_mode(detrend_x), detrend_mode(detrend_y)
         n = len(range(int(t_begin), int(t_end), max(int(t_stride), 1))) - (1 if L.VAR_DIFFERENCE in (mode_x, mode_y) else 0)
-        if isinstance(bands, (int, np.integer)):
-            if not 1 <= int(bands) <= L.XSPEC_MAX_BANDS:
-                raise ValueError(f"bands: 1 to {L.XSPEC_MAX_BANDS} bands per call, got {int(bands)}")
-            edges = band_edges(n, int(bands)) if n >= 3 else np.array([1, 2], dtype=np.int32)    # (too short a series: the call refuses it)
-        else:
-            edges = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).ravel())
-            if edges.size < 2:
-                raise ValueError("bands: an explicit edge list needs at least two edges")
+        edges = self._band_edge_array(bands, n, L.XSPEC_MAX_BANDS)
         p = C.c_void_p()
         L.check(self._lib.rscm_ens_member_cross_spectrum(self._h, self._var(x), self._var(y), int(t_begin), int(t_end), int(t_stride), mode_x,
                                                          mode_y, edges.size - 1, edges.ctypes.data_as(C.POINTER(C.c_int32)), int(slot),
                                                          C.byref(p)))
-        nm, base = self.n_members, p.value
-        vec = [DeviceVector(base + 8 * nm * j, nm, np.float64, self) for j in range(2 + 3 * (edges.size - 1))]
+        vec = self._slot_vectors(p, 2 + 3 * (edges.size - 1))
         return {"var_x": vec[0], "var_y": vec[1], "coherence2": vec[2::3], "gain": vec[3::3], "gain_quad": vec[4::3], "edges": edges,
                 "counts": np.diff(edges).astype(np.int32)}
 
@@ -735,20 +743,14 @@ class Ensemble:
         terms).  ``power[b]`` is the mean periodogram ordinate of the band, scaled so that white noise has its variance there.
         The definition is ``rscm_amd.variability.series_spectrum``'s, bit for bit (rscm_ens_member_spectrum).  3 to 4096 terms; a
         member with a non-finite value in any row has NaN everywhere."""
-        from .variability import band_edges, detrend_mode
+        from .variability import detrend_mode
         mode = detrend_mode(detrend)
         n = len(range(int(t_begin), int(t_end), max(int(t_stride), 1))) - (1 if mode == L.VAR_DIFFERENCE else 0)
-        if isinstance(bands, (int, np.integer)):
-            edges = band_edges(n, int(bands)) if n >= 3 else np.array([1, 2], dtype=np.int32)    # (too short a series: the call refuses it)
-        else:
-            edges = np.ascontiguousarray(np.asarray(bands, dtype=np.int32).ravel())
-            if edges.size < 2:
-                raise ValueError("bands: an explicit edge list needs at least two edges")
+        edges = self._band_edge_array(bands, n)
         p = C.c_void_p()
         L.check(self._lib.rscm_ens_member_spectrum(self._h, self._var(var), int(t_begin), int(t_end), int(t_stride), mode, edges.size - 1,
                                                    edges.ctypes.data_as(C.POINTER(C.c_int32)), int(slot), C.byref(p)))
-        nm, base = self.n_members, p.value
-        vec = [DeviceVector(base + 8 * nm * j, nm, np.float64, self) for j in range(3 + edges.size - 1)]
+        vec = self._slot_vectors(p, 3 + edges.size - 1)
         return {"mean": vec[0], "slope": vec[1], "variance": vec[2], "power": vec[3:], "edges": edges,
                 "counts": np.diff(edges).astype(np.int32)}
 

@@ -44,34 +44,14 @@ def series_variability(x, detrend: str = "linear") -> Dict[str, object]:
     n = u.shape[0]
     if n < 3:
         raise ValueError(f"series_variability: the working series has {n} terms, at least 3 are needed")
-    h = (n - 1) * 0.5
-    tau = np.arange(n, dtype=np.float64) - h
     with np.errstate(all="ignore"):
-        S = u[0].copy()
-        for k in range(1, n):
-            S = S + u[k]
-        m = S / float(n)
-        b = np.zeros_like(m)
-        if mode == L.VAR_LINEAR:
-            Q = tau[0] * u[0]
-            for k in range(1, n):
-                Q = Q + tau[k] * u[k]
-            b = Q / (float(n * (n * n - 1)) / 12.0)
-        C0 = C1 = prev = None
-        for k in range(n):
-            a = u[k] - m
-            if mode == L.VAR_LINEAR:
-                a = a - b * tau[k]
-            C0 = a * a if k == 0 else C0 + a * a
-            if k == 1:
-                C1 = prev * a
-            elif k > 1:
-                C1 = C1 + prev * a
-            prev = a
+        a, m, b, C0 = _series_residuals(u, mode)
+        C1 = a[0] * a[1]
+        for k in range(2, n):
+            C1 = C1 + a[k - 1] * a[k]
         variance = C0 / float(n)
         out = {"mean": m, "slope": b, "variance": variance, "sd": np.sqrt(variance), "r1": C1 / C0}
-    out = {k: np.where(bad, np.nan, v) for k, v in out.items()}
-    return {k: float(v[0]) for k, v in out.items()} if single else out
+    return _finish(out, bad, single)
 
 
 def _pair_series(rows, mode, other):
@@ -126,11 +106,7 @@ def series_covariability(x, y, detrend_x: str = "linear", detrend_y: str = "line
         D = np.sqrt(Cxx) * np.sqrt(Cyy)
         out = {"var_x": Cxx / float(n), "var_y": Cyy / float(n), "cov": G0 / float(n), "corr": G0 / D, "slope": G0 / Cxx,
                "lead": [G(l) / D for l in range(1, lags + 1)], "lag": [G(-l) / D for l in range(1, lags + 1)]}
-    nan = lambda v: np.where(bad, np.nan, v)
-    out = {k: [nan(w) for w in v] if isinstance(v, list) else nan(v) for k, v in out.items()}
-    if single:
-        out = {k: [float(w[0]) for w in v] if isinstance(v, list) else float(v[0]) for k, v in out.items()}
-    return out
+    return _finish(out, bad, single)
 
 
 MAX_BANDS = 8          # rscm_ens_member_spectrum: 1 .. 8 bands
@@ -238,6 +214,35 @@ def _residuals(rows, mode):
     return a, m, b, C0 / float(u.shape[0]), bad
 
 
+def _finish(out, bad, single):
+    """``out`` (arrays of ``[N]`` and lists of them) with NaN where ``bad``; for a ``single`` series as floats and lists of floats."""
+    nan = (lambda v: float(np.where(bad, np.nan, v)[0])) if single else (lambda v: np.where(bad, np.nan, v))
+    return {k: [nan(w) for w in v] if isinstance(v, list) else nan(v) for k, v in out.items()}
+
+
+def _goertzel(a, c):
+    """``(s1, s2)``, each ``[F][N]``: the last value and the one before it of Goertzel's recurrence over the residuals ``a`` [n][N]
+    with the coefficients ``c`` [F][1]."""
+    s1 = np.zeros((c.shape[0], a.shape[1]))
+    s2 = np.zeros_like(s1)
+    for ak in a:
+        s0 = (ak + c * s1) - s2
+        s2 = s1
+        s1 = s0
+    return s1, s2
+
+
+def _band_means(I, edges):
+    """The mean of the ordinates ``I`` [F][N] (frequency ``edges[0]`` first) over each band, summed in ascending frequency."""
+    lo, means = int(edges[0]), []
+    for e0, e1 in zip(edges[:-1], edges[1:]):
+        acc = I[e0 - lo].copy()
+        for j in range(int(e0) + 1, int(e1)):
+            acc = acc + I[j - lo]
+        means.append(acc / float(int(e1) - int(e0)))
+    return means
+
+
 def series_spectrum(x, detrend: str = "difference", edges=None) -> Dict[str, object]:
     """``{"mean", "slope", "variance", "power": [one per band], "edges", "counts"}`` of ``x``: ``[R]`` (one series: floats) or
     ``[R][N]`` (rows by members: arrays of ``[N]``) -- ``Ensemble.spectrum`` for a record.  ``detrend`` as
@@ -262,24 +267,10 @@ def series_spectrum(x, detrend: str = "difference", edges=None) -> Dict[str, obj
     with np.errstate(all="ignore"):
         a, m, b, variance, bad = _residuals(rows, mode)
         c = c2[lo - 1:hi - 1, None]                       # [F][1] against the members' [N]
-        s1 = np.zeros((hi - lo, rows.shape[1]))
-        s2 = np.zeros_like(s1)
-        for k in range(n):
-            s0 = (a[k] + c * s1) - s2
-            s2 = s1
-            s1 = s0
+        s1, s2 = _goertzel(a, c)
         I = ((s1 * s1 + s2 * s2) - (c * s1) * s2) / float(n)
-        power = []
-        for e0, e1 in zip(edges[:-1], edges[1:]):
-            acc = I[e0 - lo].copy()
-            for j in range(int(e0) + 1, int(e1)):
-                acc = acc + I[j - lo]
-            power.append(acc / float(int(e1) - int(e0)))
-    nan = lambda v: np.where(bad, np.nan, v)
-    out = {"mean": nan(m), "slope": nan(b), "variance": nan(variance), "power": [nan(p) for p in power]}
-    if single:
-        out = {"mean": float(out["mean"][0]), "slope": float(out["slope"][0]), "variance": float(out["variance"][0]),
-               "power": [float(p[0]) for p in out["power"]]}
+        out = {"mean": m, "slope": b, "variance": variance, "power": _band_means(I, edges)}
+    out = _finish(out, bad, single)
     out["edges"] = edges
     out["counts"] = np.diff(edges).astype(np.int32)
     return out
@@ -319,35 +310,17 @@ def series_cross_spectrum(x, y, detrend_x: str = "linear", detrend_y: str = "lin
         a, _, _, Cxx = _series_residuals(_pair_series(rx, mode_x, mode_y), mode_x)
         c, _, _, Cyy = _series_residuals(_pair_series(ry, mode_y, mode_x), mode_y)
         cf, gf = c2[lo - 1:hi - 1, None], g[lo - 1:hi - 1, None]         # [F][1] against the members' [N]
-        s1 = np.zeros((hi - lo, rx.shape[1]))
-        s2, t1, t2 = np.zeros_like(s1), np.zeros_like(s1), np.zeros_like(s1)
-        for k in range(n):
-            s0 = (a[k] + cf * s1) - s2
-            s2 = s1
-            s1 = s0
-            t0 = (c[k] + cf * t1) - t2
-            t2 = t1
-            t1 = t0
+        (s1, s2), (t1, t2) = _goertzel(a, cf), _goertzel(c, cf)
         ordinates = (((s1 * s1 + s2 * s2) - (cf * s1) * s2) / dn, ((t1 * t1 + t2 * t2) - (cf * t1) * t2) / dn,
                      ((s1 * t1 + s2 * t2) - (cf * 0.5) * (s1 * t2 + s2 * t1)) / dn, (gf * (s2 * t1 - s1 * t2)) / dn)
         out = {"var_x": Cxx / dn, "var_y": Cyy / dn, "coherence2": [], "gain": [], "gain_quad": []}
-        for e0, e1 in zip(edges[:-1], edges[1:]):
-            mean = []
-            for I in ordinates:
-                acc = I[e0 - lo].copy()
-                for j in range(int(e0) + 1, int(e1)):
-                    acc = acc + I[j - lo]
-                mean.append(acc / float(int(e1) - int(e0)))
-            Pxx, Pyy, K, Q = mean
+        for Pxx, Pyy, K, Q in zip(*(_band_means(I, edges) for I in ordinates)):
             D = np.sqrt(Pxx) * np.sqrt(Pyy)
             kc, qc = K / D, Q / D
             out["coherence2"].append(kc * kc + qc * qc)
             out["gain"].append(K / Pxx)
             out["gain_quad"].append(Q / Pxx)
-    nan = lambda v: np.where(bad, np.nan, v)
-    out = {k: [nan(w) for w in v] if isinstance(v, list) else nan(v) for k, v in out.items()}
-    if single:
-        out = {k: [float(w[0]) for w in v] if isinstance(v, list) else float(v[0]) for k, v in out.items()}
+    out = _finish(out, bad, single)
     out["edges"] = edges
     out["counts"] = np.diff(edges).astype(np.int32)
     return out

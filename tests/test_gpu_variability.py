@@ -26,7 +26,9 @@ BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
 SEED = 20260327
 DETREND = ("mean", "linear", "difference")
 SIZES = [1, 63, 64, 257, 1000]       # a single member; below, at and past a wave; a ragged last block; more than one block
-ROWS = [3, 4, 7, 8, 9, 10, 16, 17, 40]   # the least; below, at and one past the load batch of 8; two batches and one past; five
+# the least; below, at and one past the load batch of 8; a batch, a pair and a single term (11 terms: plain from 11 rows, differenced
+# from 12); two batches and one past; five
+ROWS = [3, 4, 7, 8, 9, 10, 11, 12, 16, 17, 40]
 
 
 @pytest.fixture(scope="module")
