@@ -77,6 +77,19 @@ RSCM_API int rscm_gpu_set_two_layer_guard(int32_t numerators);
  * (enable 1) or off (0) for the calling thread.  Waits for the device.  Counts only; the results are the same bits either way. */
 RSCM_API int rscm_gpu_two_layer_guard_counts(int32_t device_id, int32_t enable, int64_t* counts);
 
+/* Whether the calling THREAD's stand-alone, stored, EXACT two-layer runs of a plain forcing table with ten sub-steps in every step form
+ * their quotients in two instructions (csrc/rk4_device.hpp, pair_div; csrc/pair_div_verdict.hpp): -1 (default) from 512 model steps
+ * on -- the kernel that forms the member constants costs what the lane saves in about 430 steps, so a shorter run would lose by it
+ * if it were the only run of its parameter set; 0 never (the yardstick of tests/test_gpu_two_layer_pair_div.py); 1 whatever the
+ * run's length.  Wavefronts in which some member's heat capacity has no safe constants keep the three-instruction quotients.  The
+ * same bits either way. */
+RSCM_API int rscm_gpu_set_two_layer_pair_lane(int32_t mode);
+
+/* The wavefronts of the counting launches (rscm_gpu_two_layer_guard_counts, enable 1) whose uniform years formed their quotients with
+ * pair_div since the last call: copied to *count (if not null), then zeroed.  Such a wavefront is counted under its guard, the chunk
+ * guard, by rscm_gpu_two_layer_guard_counts as before.  Waits for the device. */
+RSCM_API int rscm_gpu_two_layer_pair_lanes(int32_t device_id, int64_t* count);
+
 /* 1 if this library was built with -DRSCM_EXPERIMENTS (`make -C rscm_amd/csrc EXPERIMENTS=1`): the environment-variable experiment
  * knobs of csrc/experiment_env.hpp (RSCM_SPLIT_CHUNK / _CHUNK2 / _FIRST, RSCM_LOCKSTEP_SPLIT, RSCM_UDEB_VARIANT) are compiled in.
  * 0 for the shipped library, whose launch plans read only the two variables documented in rscm_gpu.h ("Environment").
@@ -115,6 +128,15 @@ RSCM_API int rscm_gpu_ocean_fit_selftest(int32_t model, double irf_scale, double
  * The parity tests require out_ref == out_fast bit for bit wherever used_fast is 1. */
 RSCM_API int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const double* den,
                                    double* out_ref, double* out_fast, uint8_t* used_fast);
+
+/* Element-wise on the device: out_ieee[i] = num[i] / den[i] by the compiler's IEEE division; out_plain[i] the two-instruction quotient
+ * of csrc/rk4_device.hpp (pair_div) with the constants as defined, zh = RN(1/d) and zl = RN(1/d - zh); out_verdict[i] the same with the
+ * constants the verdict of csrc/pair_div_verdict.hpp chose for den[i] (NaN where it has none); variant[i] the verdict: 0 the constants
+ * as defined, 1 and 2 zl's neighbours, -1 no safe constants, -2 a divisor outside the box.  num_lo: the lower edge, as a binary
+ * exponent, of the numerator window the verdict is asked to hold for (-902 holds for every divisor the verdict accepts).  Wherever
+ * variant >= 0 and num[i] is +0 or a magnitude in [2^num_lo, 2^760), out_verdict must equal out_ieee bit for bit. */
+RSCM_API int rscm_gpu_selftest_pair_div(int32_t device_id, int64_t n, int32_t num_lo, const double* num, const double* den, double* out_ieee,
+                                        double* out_plain, double* out_verdict, int32_t* variant);
 
 /* z[j] = the device's normal deviate of the 52-bit integer k52[j] (the low 52 bits are used): the AS241 evaluation of a forcing-noise
  * draw (rscm_ens_set_forcing_noise in rscm_gpu.h) without the Philox block in front, so that chosen k put every branch in play.

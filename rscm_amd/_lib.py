@@ -290,6 +290,8 @@ SIGNATURES = {
     "rscm_gpu_set_run_plan": (C.c_int, [C.c_int32]),
     "rscm_gpu_set_two_layer_guard": (C.c_int, [C.c_int32]),
     "rscm_gpu_two_layer_guard_counts": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
+    "rscm_gpu_set_two_layer_pair_lane": (C.c_int, [C.c_int32]),
+    "rscm_gpu_two_layer_pair_lanes": (C.c_int, [C.c_int32, C.POINTER(C.c_int64)]),
     "rscm_gpu_experiments_build": (C.c_int, []),
     "rscm_gpu_derive_launches": (C.c_int, [C.POINTER(C.c_int64)]),
     "rscm_gpu_lockstep_stats": (C.c_int, [C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
@@ -404,6 +406,7 @@ SIGNATURES = {
     "rscm_gpu_selftest_normal": (C.c_int, [C.POINTER(C.c_uint64), C.c_int64, _dp]),
     "rscm_gpu_selftest_math": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp]),
     "rscm_gpu_selftest_div": (C.c_int, [C.c_int32, C.c_int64, _dp, _dp, _dp, _dp, _bp]),
+    "rscm_gpu_selftest_pair_div": (C.c_int, [C.c_int32, C.c_int64, C.c_int32, _dp, _dp, _dp, _dp, _dp, _ip]),
 }
 
 

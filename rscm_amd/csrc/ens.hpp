@@ -349,6 +349,7 @@ inline int set_device(const rscm_ens* h)
 // launches of several handles out of the same pieces.
 extern "C" {
 int step_check(rscm_ens* h, int32_t step_begin, int32_t step_end, bool derive = true);
+void set_two_layer_pair_lane(int32_t mode);     // A/B hook: -1 default, 0 never the two-instruction quotients, 1 whatever the run's length (calling thread)
 void set_two_layer_guard(int32_t numerators);  // test hook: 1 forces the EXACT two-layer per-numerator guard (calling thread)
 void set_run_plan(int32_t mode);          // A/B hook: -1 default, 0 one plain launch, 1 the two-stream cut where it applies (calling thread)
 void set_fail_chunk_launch(int32_t k);   // test hook: the k-th chunk launch of the calling thread's next cut run fails (0: off)

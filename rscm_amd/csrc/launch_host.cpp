@@ -41,6 +41,20 @@ int ensure_derived(rscm_ens* h)
     return RSCM_OK;
 }
 
+// The two-layer kind's member constants: zh, zl of the two-instruction quotient for both heat capacities ([4][N]; two_layer.hip,
+// two_layer_pair_div_kernel), held under the same rule -- dirty after anything that can write a parameter row, re-formed before every
+// run while the block is exposed -- but formed only on behalf of a run that will use them (pair_lane_wanted below): the samplers and
+// the fused likelihood change the parameters with every evaluation and never pay for them.
+static int ensure_pair_constants(rscm_ens* h)
+{
+    if (!h->derived_dirty && !h->params_exposed && h->d_derived) return RSCM_OK;
+    if (int rc = set_device(h)) return rc;
+    if (int rc = alloc_or_fail(h->d_derived, (size_t)4 * h->N, true, "quotient constants of %lld members", (long long)h->N)) return rc;
+    HIPCHK(rscm::launch_two_layer_pair_div(h->d_params, h->uniform_rows, h->N, h->d_derived, h->stream));
+    h->derived_dirty = false;
+    return RSCM_OK;
+}
+
 int step_check(rscm_ens* h, int32_t step_begin, int32_t step_end, bool derive)
 {
     NEED(h);
@@ -149,6 +163,15 @@ void set_run_plan(int32_t mode) { t_run_plan = mode; }
 // Test hook (rscm_gpu_set_two_layer_guard): 1 makes the calling thread's EXACT two-layer launches guard every numerator.
 static thread_local int32_t t_tl_numerator_guard = 0;
 void set_two_layer_guard(int32_t numerators) { t_tl_numerator_guard = numerators; }
+// A/B and test hook (rscm_gpu_set_two_layer_pair_lane): the two-instruction quotients of the calling thread's stand-alone stored EXACT
+// two-layer runs of the plain table with ten sub-steps everywhere -- -1 from kPairLaneMinSteps steps on (default), 0 never, 1 whatever
+// the run's length.
+static thread_local int32_t t_tl_pair_lane = -1;
+void set_two_layer_pair_lane(int32_t mode) { t_tl_pair_lane = mode; }
+// The run must earn back the kernel that forms the constants, even if it is the only run of its parameter set: that kernel takes 72 us
+// at 1e5 members and the lane saves 0.17 us per model step there (profiles/two_layer_pair_div.txt: 0.126 ms per 750 steps), which
+// breaks even at about 430 steps.  Both scale with the wavefronts per SIMD, so the count holds for other sizes.
+constexpr int32_t kPairLaneMinSteps = 512;
 // Test hook (rscm_gpu_two_layer_guard_counts): 1 makes the calling thread's stand-alone EXACT two-layer launches count their guards.
 static thread_local int32_t t_tl_count_guards = 0;
 int rscm_gpu_two_layer_guard_counts(int32_t device_id, int32_t enable, int64_t* counts)
@@ -159,6 +182,15 @@ int rscm_gpu_two_layer_guard_counts(int32_t device_id, int32_t enable, int64_t* 
     hipError_t e = rscm::two_layer_guard_counts(counts);
     if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "two_layer_guard_counts: %s", hipGetErrorString(e));
     t_tl_count_guards = enable;
+    return RSCM_OK;
+    GUARD_END
+}
+int rscm_gpu_two_layer_pair_lanes(int32_t device_id, int64_t* count)
+{
+    GUARD_BEGIN
+    HIPCHK(hipSetDevice(device_id));
+    hipError_t e = rscm::two_layer_pair_lanes(count);
+    if (e != hipSuccess) return fail(RSCM_ERR_DEVICE, "two_layer_pair_lanes: %s", hipGetErrorString(e));
     return RSCM_OK;
     GUARD_END
 }
@@ -268,15 +300,25 @@ void fill_common(const rscm_ens* h, int32_t step_begin, int32_t step_end, Args& 
 
 // The year's uniform facts of a launch of [a.step_begin, a.step_end) with a's source and offset (TwoLayerArgs::year_facts): 0 for a fused
 // launch (an empty range), and nothing about the forcing unless the launch reads the handle's plain table
-uint32_t two_layer_year_facts(const rscm_ens* h, const rscm::TwoLayerArgs& a)
+// pair: the launch is handed the handle's current quotient constants (the stored run of step_launch that asked for them; every chunk alike)
+uint32_t two_layer_year_facts(const rscm_ens* h, const rscm::TwoLayerArgs& a, bool pair = false)
 {
     if (a.step_end <= a.step_begin) return 0;
     const int32_t nsub = h->schedule_dirty ? 0 : h->year_facts.nsub_uniform(a.step_begin, a.step_end);
     const bool plain = !a.link && a.n_comp == 0 && !a.noise_on && a.forcing == h->d_forcing && a.n_scen == h->n_scen;
-    return rscm::year_facts_word(nsub, plain && h->year_facts.forcing_boxed(a.step_begin, a.step_end, a.src_off));
+    return rscm::year_facts_word(nsub, plain && h->year_facts.forcing_boxed(a.step_begin, a.step_end, a.src_off), plain && pair);
+}
+// Whether the stored run of [step_begin, step_end) is one the pair lane is for: EXACT, stand-alone, the plain table, ten sub-steps in
+// every step, and long enough (or the hook says so)
+bool pair_lane_wanted(const rscm_ens* h, int32_t step_begin, int32_t step_end, int32_t linked)
+{
+    if (t_tl_pair_lane == 0 || h->mode != RSCM_MODE_EXACT || linked || h->n_comp > 0 || h->noise_kind || !h->params_set) return false;
+    if (t_tl_pair_lane < 0 && step_end - step_begin < kPairLaneMinSteps) return false;
+    return !h->schedule_dirty && h->year_facts.nsub_uniform(step_begin, step_end) == 10;
 }
 // shared forcing and scenarios, sub-step table, guard hooks, series
-void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::InputLinks& links, int32_t linked, rscm::TwoLayerArgs& a)
+void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::InputLinks& links, int32_t linked, rscm::TwoLayerArgs& a,
+                    bool pair = false)   // pair: the launch is handed the handle's current quotient constants (step_launch)
 {
     fill_common(h, step_begin, step_end, a);
     a.row_stride = h->N;
@@ -307,7 +349,7 @@ void fill_two_layer(const rscm_ens* h, int32_t step_begin, int32_t step_end, con
             a.noise_on = rscm::noise_code(h->noise_kind, t0 > 0 && h->noise_state_index == t0 - 1);
         }
     }
-    a.year_facts = two_layer_year_facts(h, a);
+    a.year_facts = two_layer_year_facts(h, a, pair);
 }
 rscm::TwoLayerArgs block_of(const rscm::TwoLayerArgs& a, int32_t begin, int32_t end, int64_t m0, int64_t count)
 {
@@ -610,15 +652,20 @@ int step_launch(rscm_ens* h, int32_t step_begin, int32_t step_end, const rscm::I
     const int32_t mode = h->mode;
     switch (family) {
         case rscm::Family::TwoLayer: {
+            // the pair lane's constants are formed here, for the run that uses them, and stated to every chunk alike
+            const bool pair = step_end > step_begin && pair_lane_wanted(h, step_begin, step_end, linked);
+            if (pair)
+                if (int rc = ensure_pair_constants(h)) return rc;
             rscm::TwoLayerArgs a{};
-            fill_two_layer(h, step_begin, step_end, links, linked, a);
+            fill_two_layer(h, step_begin, step_end, links, linked, a, pair);
             // the noise cache is dropped while the run is issued and stands at the run's last index only if all of it was
             if (step_end > step_begin) h->noise_state_index = -1;
             // (a chunk of a cut run states the facts of its own steps: one step of another length costs one chunk the uniform year)
-            if (int rc = launch_whole_or_split(h, a, linked != 0, false, [mode, h](const rscm::TwoLayerArgs& c, hipStream_t st) {
+            if (int rc = launch_whole_or_split(h, a, linked != 0, false, [mode, h, pair](const rscm::TwoLayerArgs& c, hipStream_t st) {
                     rscm::TwoLayerArgs d = c;
-                    d.year_facts = two_layer_year_facts(h, d);
-                    return rscm::launch_two_layer(d, mode, st);
+                    d.year_facts = two_layer_year_facts(h, d, pair);
+                    // (the constants move with the block like every per-member row: its first member is d.params - h->d_params)
+                    return rscm::launch_two_layer(d, mode, st, pair ? h->d_derived.get() + (d.params - h->d_params.get()) : nullptr);
                 }))
                 return rc;
             if (rscm::noise_keeps_state(a.noise_on) && step_end > step_begin && h->noise_cache_kept()) h->noise_state_index = step_end - 1 + a.src_off;

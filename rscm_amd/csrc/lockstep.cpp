@@ -66,6 +66,13 @@ int rscm_gpu_set_two_layer_guard(int32_t numerators)
     return RSCM_OK;
 }
 
+int rscm_gpu_set_two_layer_pair_lane(int32_t mode)
+{
+    if (mode < -1 || mode > 1) return fail(RSCM_ERR_INVALID, "pair lane %d (-1 default, 0 never, 1 whatever the run's length)", mode);
+    set_two_layer_pair_lane(mode);
+    return RSCM_OK;
+}
+
 int rscm_gpu_derive_launches(int64_t* out)
 {
     const int64_t n = take_derive_launches();

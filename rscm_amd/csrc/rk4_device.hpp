@@ -45,6 +45,31 @@ namespace rscm {
 // (two_layer_body.hpp); scripts/two_layer_box_proof.py (check_wide_window) checks these
 // conditions for the header's constants and tests/test_gpu_two_layer_chunk_guard.py the
 // identity on the device, on both sides of every edge.
+//
+// The pair window.  For a divisor in the same box [2^-2, 2^14) whose constants
+//     zh = RN(1/d)     zl = RN(1/d - zh), or a neighbour of it
+// pair_div_verdict.hpp has found safe, the two-instruction quotient
+//     t = n*zl; q = fma(n, zh, t)
+// equals n/d bit for bit for
+//     n = +0,  or  |n| in [2^-902, 2^760)                                 "pair numerator window"
+// (pair_div_verdict.hpp, pairdiv::kNumLo/Hi).  The verdict tries every numerator significand whose
+// quotient lies close enough to a rounding boundary for the sum's error of < 2^-104 |n/d| to matter
+// (the argument is written out there and in scripts/pair_div_proof.py); it does so at one exponent,
+// which decides every exponent as long as no operation leaves the normal range.  That is the window:
+// zh lies in (2^-14, 2^2] and a tried non-zero zl is at least 2^-120 in magnitude (1 - d*zh is a
+// non-zero multiple of 2^-105 d; a neighbour loses at most a factor 1 - 2^-53), at most 2^-52, so with
+// |n| >= 2^-902 the product n*zl is at least 2^-1022, n*zh at least 2^-916 and n/d above 2^-916: all
+// normal; below 2^760 the largest of them, n*zh, stays below 2^762.  A zero zl (d a power of two)
+// makes t a zero and q = RN(n*zh) = n/d.  n = +0: t is +0 or -0, and fma(+0, zh, t) adds (+0) + (+-0),
+// which is +0 in round-to-nearest, as is +0 / d for the positive d of the box.  -0, Inf, NaN and
+// denormal numerators are outside, as they are for spec_div.  The window lies inside the wide window.
+// The chunk guard admits the deep equation's numerators down to 2^-893, inside it, but the surface
+// equation's down to 2^-946: below 2^-902 the one thing that can leave the normal range is n*zl, and
+// only for a tiny zl, so the verdict takes the lower edge it is to vouch for and refuses a divisor
+// whose tried zl is below 2^(-1022 - edge).  The constants for Cs are formed for the edge 2^-946
+// (pairdiv::kSurfaceNumFloor; zl below 2^-76: a chance of 2^-18 per member);
+// scripts/two_layer_box_proof.py (check_pair_window) asserts both edges against the chunk guard's
+// numerators from the headers' constants.
 // ---------------------------------------------------------------------------------------------
 
 // tag < 0  <=>  biased exponent of x in [512, 1535]: (hi << 1) moves exponent bit 10 to bit 31
@@ -100,6 +125,14 @@ __device__ __forceinline__ double spec_div(double n, double d, double r)
 {
     const double q = n * r;
     return __builtin_fma(__builtin_fma(-d, q, n), r, q);
+}
+
+// The two-instruction quotient; equals n/d bit for bit for a divisor in [2^-2, 2^14) with constants the verdict of
+// pair_div_verdict.hpp found safe, inside the pair numerator window.
+__device__ __forceinline__ double pair_div(double n, double zh, double zl)
+{
+    const double t = n * zl;
+    return __builtin_fma(n, zh, t);
 }
 
 struct ConstDiv {

@@ -390,14 +390,18 @@ struct TwoLayerArgs {
 };
 // TwoLayerArgs::year_facts: the low bits hold the sub-step count that every step of [step_begin, step_end) has (0: they differ, or
 // nobody looked), the top bit says that every forcing value the launch can read is +0 or a magnitude in the chunk guard's forcing box
-// (two_layer_chunk_box.hpp) -- set for a plain table only: no link, no mix, no noise.  A fused launch passes 0.
-constexpr uint32_t kYearForcingBoxed = 0x80000000u;
-constexpr uint32_t year_facts_word(int32_t nsub_uniform, bool forcing_boxed)
+// (two_layer_chunk_box.hpp) -- set for a plain table only: no link, no mix, no noise.  The bit below it says that the launch comes with
+// the member constants of the two-instruction quotient, formed from the parameter rows as they stand (launch_two_layer's pair_div:
+// stored stand-alone launches of the plain table only; the same in every chunk of a cut run).  The struct is full, so the pointer
+// travels beside it as a kernel argument of its own.  A fused launch passes 0.
+constexpr uint32_t kYearForcingBoxed = 0x80000000u, kYearPairValid = 0x40000000u;
+constexpr uint32_t year_facts_word(int32_t nsub_uniform, bool forcing_boxed, bool pair_valid = false)
 {
-    return (nsub_uniform > 0 ? (uint32_t)nsub_uniform : 0u) | (forcing_boxed ? kYearForcingBoxed : 0u);
+    return (nsub_uniform > 0 ? (uint32_t)nsub_uniform : 0u) | (forcing_boxed ? kYearForcingBoxed : 0u) | (pair_valid ? kYearPairValid : 0u);
 }
-constexpr int32_t year_nsub_uniform(uint32_t facts) { return (int32_t)(facts & ~kYearForcingBoxed); }
+constexpr int32_t year_nsub_uniform(uint32_t facts) { return (int32_t)(facts & ~(kYearForcingBoxed | kYearPairValid)); }
 constexpr bool year_forcing_boxed(uint32_t facts) { return (facts & kYearForcingBoxed) != 0; }
+constexpr bool year_pair_valid(uint32_t facts) { return (facts & kYearPairValid) != 0; }
 // The kinds of forcing noise: a handle's setting (rscm_ens::noise_kind) and the NOISE template value of the two-layer kernels
 constexpr int32_t kNoiseKindNone = 0, kNoiseKindWhite = 1, kNoiseKindRed = 2, kNoiseKindMembers = 3;
 // TwoLayerArgs::noise_on (0: no noise): a kind, and for red and members whether noise_state holds e at the index before the launch's
@@ -759,7 +763,7 @@ inline bool two_layer_fits_lds(int32_t n_scen, int32_t n_comp, int32_t len)
 {
     return two_layer_lds_bytes(n_scen, n_comp, len) <= (size_t)kMaxLds - 1024;
 }
-hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s);
+hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s, const double* pair_div = nullptr);
 // out[(t - t_begin) * n_members + i] = e_t(seed, member0 + i) for t in [t_begin, t_end): the term a noise handle of this kind (kNoiseKind*,
 // not none) adds to its forcing (TwoLayerArgs).  White: sigma * z.  Red: formed from index 0 on and written from t_begin on.  Members:
 // the same from sigma_i = row sigma_row and phi_i = row phi_row of the [P][n_members] block; sigma and phi are not read
@@ -773,6 +777,10 @@ hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefA
 // the current device's wavefront counts per guard of the counting launches (TwoLayerArgs::count_guards) into out[3] (if not null),
 // then zeroes them; waits for the device first
 hipError_t two_layer_guard_counts(int64_t* out);
+hipError_t two_layer_pair_lanes(int64_t* out);
+hipError_t launch_two_layer_pair_div(const double* params, uint64_t uniform_rows, int64_t n_members, double* out, hipStream_t s);
+hipError_t launch_pair_div_selftest(const double* num, const double* den, int64_t n, int32_t num_lo, double* ieee, double* plain, double* tried,
+                                    int32_t* variant, hipStream_t s);
 hipError_t launch_coupled(const CoupledArgs& a, int mode, hipStream_t s);
 hipError_t launch_udeb(const UdebArgs& a, hipStream_t s);
 bool udeb_layers_unrolled(int32_t n_layers);  // the layer counts whose columns stay on chip (2 .. kUdebMaxOnChipLayers)

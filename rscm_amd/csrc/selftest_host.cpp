@@ -58,4 +58,27 @@ int rscm_gpu_selftest_div(int32_t device_id, int64_t n, const double* num, const
     GUARD_END
 }
 
+int rscm_gpu_selftest_pair_div(int32_t device_id, int64_t n, int32_t num_lo, const double* num, const double* den, double* out_ieee,
+                               double* out_plain, double* out_verdict, int32_t* variant)
+{
+    GUARD_BEGIN
+    if (n < 0 || !num || !den || !out_ieee || !out_plain || !out_verdict || !variant) return fail(RSCM_ERR_INVALID, "bad arguments");
+    if (n == 0) return RSCM_OK;
+    HIPCHK(hipSetDevice(device_id));
+    rscm::DevBuf<double> buf;   // [n] num, den, ieee, plain, verdict
+    rscm::DevBuf<int32_t> dv;
+    HIPCHK(buf.alloc(5 * (size_t)n));
+    HIPCHK(dv.alloc((size_t)n));
+    double* d = buf.get();
+    HIPCHK(hipMemcpy(d, num, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d + n, den, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(rscm::launch_pair_div_selftest(d, d + n, n, num_lo, d + 2 * n, d + 3 * n, d + 4 * n, dv.get(), nullptr));
+    HIPCHK(hipMemcpy(out_ieee, d + 2 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_plain, d + 3 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out_verdict, d + 4 * n, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(variant, dv.get(), (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+    return RSCM_OK;
+    GUARD_END
+}
+
 }  // extern "C"

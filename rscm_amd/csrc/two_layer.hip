@@ -38,6 +38,8 @@
 
 #include <type_traits>
 
+#include "pair_div_verdict.hpp"
+
 namespace rscm {
 
 namespace {
@@ -45,6 +47,17 @@ namespace {
 // test hook (rscm_gpu_two_layer_guard_counts): per guard (tl::kGuardNumerators / kGuardStates / kGuardChunks), the wavefronts of the
 // counting launches that took it
 __device__ unsigned long long g_guard_counts[tl::kGuardKinds];
+// ... and of those, the wavefronts whose uniform years took the pair lane (rscm_gpu_two_layer_pair_lanes)
+__device__ unsigned long long g_pair_lanes;
+
+// a wavefront's first lane reports what two_layer_body returned
+__device__ __forceinline__ void count_guard(const TwoLayerArgs& a, int32_t guard)
+{
+    if (a.count_guards && (threadIdx.x & 63) == 0) {
+        atomicAdd(&g_guard_counts[guard & ~tl::kPairLaneBit], 1ull);
+        if (guard & tl::kPairLaneBit) atomicAdd(&g_pair_lanes, 1ull);
+    }
+}
 
 // MIX: a mix handle's launch (a.n_comp >= 1): the staged table is [n_scen][n_comp][len], n_scen * n_comp rows laid out like scenarios
 // NOISE: a launch with a.noise_on (stored runs only): the seeded term of forcing_noise.hpp on top of the staged or read forcing, of the
@@ -65,9 +78,63 @@ __global__ __launch_bounds__(kBlock) void two_layer_kernel(TwoLayerArgs a)
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
     const int32_t guard = tl::two_layer_body<MODE, LDS, STORE, NoCache, false, MIX, NOISE, true>(a, lds_forcing, i, a.step_begin, a.step_end);
-    if constexpr (MODE == 0) {
-        if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
+    if constexpr (MODE == 0) count_guard(a, guard);
+}
+
+// The plain stored EXACT launch with the members' pair_div constants beside its arguments (TwoLayerArgs is full): the kernel above, whose
+// uniform years form their quotients in two instructions in every wavefront whose members all have safe constants.  A kernel of its
+// own, so that the launches without the constants run the kernels they ran.  (The staging loop is two_layer_kernel's, restated: moved
+// into a function shared by the three kernels it reorders the prologue of every LDS instantiation, the mix, noise and FAST ones
+// included, which are to stay the instructions they were.)
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void two_layer_pair_kernel(TwoLayerArgs a, const double* pair_div)
+{
+    extern __shared__ double lds_forcing[];
+    if constexpr (LDS) {
+        const int32_t len = a.step_end - a.step_begin;
+        const int32_t total = a.n_scen * len;
+        for (int32_t idx = threadIdx.x; idx < total; idx += kBlock) {
+            const int32_t s = idx / len, k = idx - s * len;
+            lds_forcing[idx] = a.forcing[(size_t)s * a.n_times + a.step_begin + a.src_off + k];
+        }
+        __syncthreads();
     }
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= a.n_members) return;
+    count_guard(a, tl::two_layer_body<0, LDS, true, NoCache, false, false, 0, true, true>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(),
+                                                                                      nullptr, pair_div));
+}
+
+// The member constants of pair_div (rk4_device.hpp) for the two heat capacities, parameter rows 4 and 5 read the way the stepping kernel
+// reads them: out[0][i], out[1][i] = zh, zl for Cs (vouched for down to the surface equation's numerators, pairdiv::kSurfaceNumFloor),
+// out[2][i], out[3][i] for Cd; the constants the verdict tried, bit for bit, zh = 0 where it found none (pair_div_verdict.hpp).
+__global__ __launch_bounds__(kBlock) void two_layer_pair_div_kernel(const double* params, uint64_t uniform_rows, int64_t n, double* out)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const pairdiv::Constants s = pairdiv::verdict(param_at(params, uniform_rows, 4, n, i), pairdiv::kSurfaceNumFloor);
+    const pairdiv::Constants d = pairdiv::verdict(param_at(params, uniform_rows, 5, n, i));
+    out[i] = s.zh;
+    out[n + i] = s.zl;
+    out[2 * n + i] = d.zh;
+    out[3 * n + i] = d.zl;
+}
+
+// rscm_gpu_selftest_pair_div: per pair the IEEE quotient, pair_div with the constants as defined, pair_div with the verdict's constants
+// (NaN where it has none), and the verdict's variant.  num_lo: the window edge the verdict is asked for
+__global__ __launch_bounds__(kBlock) void pair_div_selftest_kernel(const double* num, const double* den, int64_t n, int32_t num_lo, double* ieee,
+                                                                   double* plain, double* tried, int32_t* variant)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const double x = num[j], d = den[j];
+    ieee[j] = x / d;
+    double zh, zl;
+    pairdiv::plain_constants(d, zh, zl);
+    plain[j] = pair_div(x, zh, zl);
+    const pairdiv::Constants c = pairdiv::verdict(d, num_lo);
+    tried[j] = c.zh != 0.0 ? pair_div(x, c.zh, c.zl) : __builtin_nan("");
+    variant[j] = c.variant;
 }
 
 // e_t for rows [t_begin, t_end) x n members: what a noise handle of kind KIND adds to its forcing (rscm_ens_forcing_noise_rows).  White:
@@ -126,9 +193,7 @@ __global__ __launch_bounds__(kBlock) void two_layer_ref_kernel(TwoLayerArgs a, T
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= a.n_members) return;
     const int32_t guard = tl::two_layer_body<MODE, LDS, false, NoCache, true, MIX, 0, true>(a, lds_forcing, i, a.step_begin, a.step_end, NoCache(), &r);
-    if constexpr (MODE == 0) {
-        if (a.count_guards && (threadIdx.x & 63) == 0) atomicAdd(&g_guard_counts[guard], 1ull);
-    }
+    if constexpr (MODE == 0) count_guard(a, guard);
 }
 
 }  // namespace
@@ -213,9 +278,13 @@ static hipError_t launch_impl(const TwoLayerArgs& a, int mode, hipStream_t s)
     return launch_shaped(kern, a, s);
 }
 
-hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s)
+// pair_div: the members' quotient constants for a launch whose year_facts say kYearPairValid (first member's; rows a.row_stride apart)
+hipError_t launch_two_layer(const TwoLayerArgs& a, int mode, hipStream_t s, const double* pair_div)
 {
-    return launch_impl<true>(a, mode, s);
+    if (!year_pair_valid(a.year_facts)) return launch_impl<true>(a, mode, s);
+    if (!pair_div || mode != 0 || a.n_comp != 0 || a.noise_on || a.link || !args_ok(a)) return hipErrorInvalidValue;
+    if (a.n_members <= 0 || a.step_end <= a.step_begin) return hipSuccess;
+    return launch_shaped(a.lds_forcing ? two_layer_pair_kernel<true> : two_layer_pair_kernel<false>, a, s, pair_div);
 }
 
 hipError_t launch_two_layer_loglik(const TwoLayerArgs& a, int mode, hipStream_t s)
@@ -250,6 +319,35 @@ hipError_t launch_two_layer_loglik_ref(const TwoLayerArgs& a, const TwoLayerRefA
     if (a.n_members <= 0) return hipSuccess;
     if (!args_ok(a) || a.noise_on) return hipErrorInvalidValue;   // (the fused likelihood of a noise handle is refused at the entry points)
     return launch_shaped(ref_kernel(mode, a.lds_forcing != 0, a.n_comp > 0), a, s, r);
+}
+
+hipError_t launch_two_layer_pair_div(const double* params, uint64_t uniform_rows, int64_t n_members, double* out, hipStream_t s)
+{
+    if (n_members <= 0) return hipSuccess;
+    hipLaunchKernelGGL(two_layer_pair_div_kernel, dim3((unsigned)((n_members + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, params, uniform_rows,
+                       n_members, out);
+    return hipGetLastError();
+}
+
+hipError_t launch_pair_div_selftest(const double* num, const double* den, int64_t n, int32_t num_lo, double* ieee, double* plain, double* tried,
+                                    int32_t* variant, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(pair_div_selftest_kernel, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, s, num, den, n, num_lo, ieee, plain,
+                       tried, variant);
+    return hipGetLastError();
+}
+
+// the wavefronts that took the pair lane in the counting launches since the last call; the count is reset
+hipError_t two_layer_pair_lanes(int64_t* out)
+{
+    unsigned long long c = 0;
+    hipError_t e = hipDeviceSynchronize();
+    if (e == hipSuccess) e = hipMemcpyFromSymbol(&c, HIP_SYMBOL(g_pair_lanes), sizeof c);
+    if (e != hipSuccess) return e;
+    if (out) *out = (int64_t)c;
+    const unsigned long long zero = 0;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_pair_lanes), &zero, sizeof zero);
 }
 
 hipError_t two_layer_guard_counts(int64_t* out)

@@ -25,16 +25,26 @@ struct TLConst {
 //   dts = (erf - lambda_eff*ts - heat_exchange_surface) / heat_capacity_surface
 //   dtd = (eta*temperature_difference) / heat_capacity_deep
 // SPEC: the three-instruction quotients; TAGS: with one window tag per numerator (the per-numerator guard).
-template <bool SPEC, bool TAGS = SPEC>
+// PAIR (with SPEC, without TAGS): the two quotients by pair_div with the member's constants *z, which the verdict of
+// pair_div_verdict.hpp found safe for both divisors (the pair lane of the uniform year); every other statement is the same.
+struct TLPair {
+    double zsh = 0.0, zsl = 0.0, zdh = 0.0, zdl = 0.0;   // zh, zl for Cs and for Cd
+};
+
+template <bool SPEC, bool TAGS = SPEC, bool PAIR = false>
 __device__ __forceinline__ void rhs_exact(const TLConst& p, double erf, double ts, double td,
-                                          double& dts, double& dtd, int32_t& acc)
+                                          double& dts, double& dtd, int32_t& acc, [[maybe_unused]] const TLPair* z = nullptr)
 {
+    static_assert(!PAIR || (SPEC && !TAGS), "pair_div belongs to the guarded speculative year");
     const double diff = ts - td;
     const double lambda_eff = p.lambda0 - p.a * ts;
     const double hx_s = p.eff_eta * diff;
     const double num_s = erf - lambda_eff * ts - hx_s;
     const double num_d = p.eta * diff;
-    if constexpr (SPEC) {
+    if constexpr (PAIR) {
+        dts = pair_div(num_s, z->zsh, z->zsl);
+        dtd = pair_div(num_d, z->zdh, z->zdl);
+    } else if constexpr (SPEC) {
         dts = spec_div(num_s, p.cs, p.rcs);
         dtd = spec_div(num_d, p.cd, p.rcd);
         if constexpr (TAGS) acc = max3_i32(acc, window_tag(num_s), window_tag(num_d));
@@ -44,16 +54,16 @@ __device__ __forceinline__ void rhs_exact(const TLConst& p, double erf, double t
     }
 }
 
-template <bool SPEC, bool TAGS = SPEC>
+template <bool SPEC, bool TAGS = SPEC, bool PAIR = false>
 __device__ __forceinline__ void rk4_step_exact(const TLConst& p, double erf, double h,
                                                double half_step, double sixth, double& ts,
-                                               double& td, int32_t& acc)
+                                               double& td, int32_t& acc, [[maybe_unused]] const TLPair* z = nullptr)
 {
     double k1s, k1d, k2s, k2d, k3s, k3d, k4s, k4d;
-    rhs_exact<SPEC, TAGS>(p, erf, ts, td, k1s, k1d, acc);
-    rhs_exact<SPEC, TAGS>(p, erf, ts + k1s * half_step, td + k1d * half_step, k2s, k2d, acc);
-    rhs_exact<SPEC, TAGS>(p, erf, ts + k2s * half_step, td + k2d * half_step, k3s, k3d, acc);
-    rhs_exact<SPEC, TAGS>(p, erf, ts + k3s * h, td + k3d * h, k4s, k4d, acc);
+    rhs_exact<SPEC, TAGS, PAIR>(p, erf, ts, td, k1s, k1d, acc, z);
+    rhs_exact<SPEC, TAGS, PAIR>(p, erf, ts + k1s * half_step, td + k1d * half_step, k2s, k2d, acc, z);
+    rhs_exact<SPEC, TAGS, PAIR>(p, erf, ts + k2s * half_step, td + k2d * half_step, k3s, k3d, acc, z);
+    rhs_exact<SPEC, TAGS, PAIR>(p, erf, ts + k3s * h, td + k3d * h, k4s, k4d, acc, z);
     if constexpr (SPEC) {
         // (k1 + k2*2) + k3*2: the doubling is exact, so the fused form rounds identically
         ts = rk4_combine_fused2(ts, k1s, k2s, k3s, k4s, sixth);
@@ -131,11 +141,11 @@ __device__ __forceinline__ bool params_in(const TLConst& p, double h, double hal
 // the sub-step count of the annual axis (h = 0.1): its year body is unrolled
 constexpr int32_t kUnrolledSubSteps = 10;
 
-// How a wavefront's years run (two_layer_body): the guard, and the two facts of the uniform year
-template <int32_t GUARD, bool UNIFORM = false, bool BOXED = false>
+// How a wavefront's years run (two_layer_body): the guard, the two facts of the uniform year, and whether its quotients are pair_div's
+template <int32_t GUARD, bool UNIFORM = false, bool BOXED = false, bool PAIR = false>
 struct YearLane {
     static constexpr int32_t kGuard = GUARD;
-    static constexpr bool kUniform = UNIFORM, kBoxed = BOXED;
+    static constexpr bool kUniform = UNIFORM, kBoxed = BOXED, kPair = PAIR;
 };
 
 // Where the uniform year stores: the row the launch writes first, the same for the whole wavefront, and the member's index in it
@@ -143,6 +153,7 @@ struct UniformRows {
     double* ts = nullptr;
     double* td = nullptr;
     int64_t member = 0;
+    TLPair z;   // the pair lane's constants (read by it alone)
 };
 
 struct TLFast {
@@ -302,6 +313,8 @@ __device__ __forceinline__ void lik_consume_ref(const TwoLayerArgs& a, const Two
 // Returns the guard of the wavefront's speculative years (EXACT; the same in every lane): kGuardNumerators, kGuardStates or
 // kGuardChunks; -1 in FAST mode.
 enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuardKinds = 3 };
+// ... with this bit on top where the wavefront's uniform years formed their quotients with pair_div (stand-alone stored launches only)
+constexpr int32_t kPairLaneBit = 0x100;
 
 // REF (with STORE == false): the fused likelihood with the reference periods of *ref (lik_consume_ref).
 // MIX (a mix handle, a.n_comp = K in 1..kMaxForcingComponents; stand-alone launches only, never linked): the forcing of member i is
@@ -329,10 +342,16 @@ enum : int32_t { kGuardNumerators = 0, kGuardStates = 1, kGuardChunks = 2, kGuar
 // registers (four more than NOISE == 2, where they are kernel arguments: the EXACT plain kernel crosses the 168-register step).  Nothing validates the rows: NaN, Inf or |phi_i| > 1 make that
 // lane's forcing NaN and leave every other lane alone; a lane whose forcing leaves the guard's box replays its year as with any forcing.
 // ALONE: a stand-alone launch (two_layer.hip), whose a.year_facts the host has filled in; the fused launches (group.hip) pass none.
-template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, int NOISE = 0, bool ALONE = false>
+// PAIRS (stand-alone stored EXACT launches of the plain table): pair_div holds the members' constants of the two-instruction quotient,
+// [4][N] with the rows' stride: zh, zl for Cs, then for Cd, zh = 0 where a divisor has no safe ones (two_layer.hip,
+// two_layer_pair_div_kernel); member i's are at pair_div[i].  The other instantiations take no such pointer and have no pair lane.
+template <int MODE, bool LDS, bool STORE, class Cache = NoCache, bool REF = false, bool MIX = false, int NOISE = 0, bool ALONE = false,
+          bool PAIRS = false>
 __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const double* lds_forcing, int64_t i, int32_t step_begin,
-                                               int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr)
+                                               int32_t step_end, const Cache& cache = Cache(), const TwoLayerRefArgs* ref = nullptr,
+                                               [[maybe_unused]] const double* pair_div = nullptr)
 {
+    static_assert(!PAIRS || (MODE == 0 && ALONE && STORE && !REF && !MIX && !NOISE && !Cache::kOn), "the pair lane belongs to the plain stored EXACT launch");
     static_assert(!(REF && STORE), "reference periods belong to the fused likelihood");
     static_assert(!NOISE || (STORE && !Cache::kOn), "forcing noise belongs to the stand-alone stored run");
     const int32_t len = step_end - step_begin;
@@ -503,6 +522,8 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
             constexpr bool kBoxed = decltype(lane)::kBoxed;       // ... and a forcing inside the chunk's box
             static_assert(!kUniform || (kChunks && kUniformLane), "the uniform year belongs to the chunk guard of a plain launch");
             static_assert(!kBoxed || kUniform, "the forcing's verdict is used by the uniform year only");
+            constexpr bool kPair = decltype(lane)::kPair;         // ... and safe pair_div constants for every member of the wavefront
+            static_assert(!kPair || (kUniform && PAIRS), "pair_div belongs to the uniform year of a launch that brings the constants");
             for (int32_t n = step_begin; n < step_end; ++n) {
                 const double erf = erf_next;
                 const int32_t m = kUniform ? kUnrolledSubSteps : m_next;
@@ -515,7 +536,8 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
                     int32_t no_tags = 0;
                     auto sub_step = [&](uint32_t& acc, uint32_t edge, bool tag) {
                         if (tag) acc = max3_u32(acc, box_tag(ts, edge), box_tag(td, edge));
-                        rk4_step_exact<true, false>(p, erf, h, half_step, sixth, ts, td, no_tags);
+                        if constexpr (kPair) rk4_step_exact<true, false, true>(p, erf, h, half_step, sixth, ts, td, no_tags, &out.z);
+                        else rk4_step_exact<true, false>(p, erf, h, half_step, sixth, ts, td, no_tags);
                     };
                     if (kChunks && (kUniform || m == kUnrolledSubSteps)) {
                         // the chunk guard: the state at every kGuard-th sub-step against the chunk's boxes
@@ -570,16 +592,38 @@ __device__ __forceinline__ int32_t two_layer_body(const TwoLayerArgs& a, const d
         };
         bool uniform_year = false;
         if constexpr (kUniformLane) uniform_year = guard_chunks && year_nsub_uniform(a.year_facts) == kUnrolledSubSteps;
+        // The pair lane ("Dividing by a constant in two instructions"): the host says that pair_div holds the
+        // members' constants as formed from the parameter rows that stand now, and every member of the wavefront has safe ones for both
+        // heat capacities (zh = 0 marks a divisor without).  The chunk guard keeps every numerator inside pair_div's window as it does
+        // inside spec_div's; a year that leaves it is replayed in IEEE arithmetic as before.
+        [[maybe_unused]] bool pair_lane = false;
         if (uniform_year) {
             if constexpr (kUniformLane) {
-                const UniformRows rows{a.ts + (size_t)(step_begin + 1) * N, a.td + (size_t)(step_begin + 1) * N, i};
-                if (year_forcing_boxed(a.year_facts)) years(YearLane<chunk::kChunkSubSteps, true, true>(), rows);
-                else years(YearLane<chunk::kChunkSubSteps, true, false>(), rows);
+                UniformRows rows{a.ts + (size_t)(step_begin + 1) * N, a.td + (size_t)(step_begin + 1) * N, i};
+                if constexpr (PAIRS) {
+                    if (year_pair_valid(a.year_facts)) {
+                        const double* z = pair_div + i;
+                        rows.z = TLPair{z[0], z[N], z[2 * N], z[3 * N]};
+                        pair_lane = __all(rows.z.zsh != 0.0 && rows.z.zdh != 0.0);
+                    }
+                }
+                const bool boxed = year_forcing_boxed(a.year_facts);
+                if constexpr (PAIRS) {
+                    if (pair_lane) {
+                        if (boxed) years(YearLane<chunk::kChunkSubSteps, true, true, true>(), rows);
+                        else years(YearLane<chunk::kChunkSubSteps, true, false, true>(), rows);
+                    }
+                }
+                if (!pair_lane) {
+                    if (boxed) years(YearLane<chunk::kChunkSubSteps, true, true>(), rows);
+                    else years(YearLane<chunk::kChunkSubSteps, true, false>(), rows);
+                }
             }
         } else if (guard_chunks) years(YearLane<chunk::kChunkSubSteps>(), UniformRows());
         else if (guard_states) years(YearLane<1>(), UniformRows());
         else years(YearLane<0>(), UniformRows());
         guard = guard_chunks ? kGuardChunks : guard_states ? kGuardStates : kGuardNumerators;
+        if (pair_lane) guard |= kPairLaneBit;
     } else {
         double inv_cs;
         const TLFast p = make_fast(lambda0, pa, efficacy, eta, cs, cd, inv_cs);

@@ -1259,6 +1259,17 @@ def selftest_div(num, den, device: int = 0):
     return ref, fast, used
 
 
+def selftest_pair_div(num, den, num_lo: int = -902, device: int = 0):
+    """(ieee, plain, verdict, variant) of num/den on the device; see rscm_gpu_selftest_pair_div."""
+    lib = L.load()
+    a, b = L.f64(num).ravel(), L.f64(den).ravel()
+    ieee, plain, tried = np.empty_like(a), np.empty_like(a), np.empty_like(a)
+    variant = np.empty(a.size, dtype=np.int32)
+    L.check(lib.rscm_gpu_selftest_pair_div(device, a.size, num_lo, L.dptr(a), L.dptr(b), L.dptr(ieee), L.dptr(plain), L.dptr(tried),
+                                           variant.ctypes.data_as(C.POINTER(C.c_int32))))
+    return ieee, plain, tried, variant
+
+
 def selftest_math(op: int, x, y=None):
     """out[i] of op 0 log_f64(x), 1 the device library's log, 2 its exp, 3 chem::pow_ratio(x, y), 4 guarded_rcp(x) on the current
     device; see rscm_gpu_selftest_math."""

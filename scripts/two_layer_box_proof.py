@@ -35,6 +35,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "rscm_amd", "csrc", "two_layer_box.hpp")
 CHUNK_HEADER = os.path.join(ROOT, "rscm_amd", "csrc", "two_layer_chunk_box.hpp")
+PAIR_HEADER = os.path.join(ROOT, "rscm_amd", "csrc", "pair_div_verdict.hpp")
 
 WINDOW_LO, WINDOW_HI = -511, 513     # numerator window [2^-511, 2^513): biased exponent in [512, 1535]
 DIVISOR_LO, DIVISOR_HI = -128, 129   # divisor window [2^-128, 2^129)
@@ -273,6 +274,28 @@ def prove_chunk(boxes, n_sub=None, log=None):
     return out
 
 
+def check_pair_window(boxes=None, pair=None, surface_lo=None):
+    """pair_div's numerator windows (pair_div_verdict.hpp) against what they need for divisors of the wide divisor box, and against
+    the chunk guard: every numerator prove_chunk() admits must be +0 or inside its window -- the deep equation's in [2^kNumLo, 2^kNumHi),
+    which holds for every divisor the verdict calls safe, the surface equation's in [2^kSurfaceNumFloor, 2^kNumHi), which the verdict is
+    asked for by name.  The needs (rk4_device.hpp, "the pair window"): a tried non-zero zl is at least 2^(-105 - dhi - 1) in magnitude,
+    so n zl is normal from 2^(-1022 + 105 + dhi + 1) on whatever the divisor; zh is at most 2^-dlo, so n zh stays finite below
+    2^(1023 + dlo); zh is above 2^-dhi and so is 1/d, so n zh and the quotient are normal above 2^(-1022 + dhi)."""
+    boxes = read_boxes(CHUNK_HEADER) if boxes is None else boxes
+    lo, hi = read_boxes(PAIR_HEADER)["Num"] if pair is None else pair
+    surface_lo = read_constants(PAIR_HEADER)["SurfaceNumFloor"] if surface_lo is None else surface_lo
+    dlo, dhi = boxes["WideDiv"]
+    if lo < -1022 + 105 + dhi + 1:
+        raise ProofError(f"numerators down to 2^{lo}: n*zl may be denormal (zl as small as 2^{-105 - dhi - 1})")
+    if hi - dlo >= 1023:
+        raise ProofError(f"numerators up to 2^{hi}: n*zh may overflow")
+    if min(lo, surface_lo) - dhi <= -1022:
+        raise ProofError(f"quotients down to 2^{min(lo, surface_lo) - dhi} may be denormal")
+    for nm, v in prove_chunk(boxes).items():
+        check_numerator(nm, v, (surface_lo if nm.startswith("num_s") else lo, hi))
+    return lo, hi, surface_lo
+
+
 def main():
     boxes = read_boxes()
     for k, (lo, hi) in sorted(boxes.items()):
@@ -295,6 +318,12 @@ def main():
         return 1
     lo, hi = chunk["WideNum"]
     print(f"every numerator of {n_sub} sub-steps is +0 or inside [2^{lo}, 2^{hi}); 2*k2 and 2*k3 are finite")
+    try:
+        lo, hi, slo = check_pair_window(chunk)
+    except ProofError as e:
+        print(f"FAILED: {e}")
+        return 1
+    print(f"... and inside pair_div's windows: [2^{lo}, 2^{hi}) for the deep equation's, [2^{slo}, 2^{hi}) for the surface equation's")
     return 0
 
 
