@@ -427,12 +427,16 @@ int32_t summary_blocks(int64_t n) { return (int32_t)grid_for(n, 1024); }
 hipError_t launch_summary_rows(const double* rows, int64_t n, int32_t n_rows, double* partial, int32_t n_blocks,
                                double* out, hipStream_t s)
 {
-    if (n_rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(summary_rows_partial_kernel, dim3(n_blocks, n_rows), dim3(kBlock), 0, s, rows, n, partial);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(summary_rows_final_kernel, dim3(n_rows), dim3(kBlock), 0, s, partial, n_blocks, out);
-    return hipGetLastError();
+    for (int32_t r0 = 0; r0 < n_rows; r0 += kMaxGridY) {   // rows in slices the grid's y dimension can index, as launch_select_hist
+        const int32_t nr = n_rows - r0 < kMaxGridY ? n_rows - r0 : kMaxGridY;
+        double* part = partial + 4 * (size_t)r0 * n_blocks;
+        hipLaunchKernelGGL(summary_rows_partial_kernel, dim3(n_blocks, nr), dim3(kBlock), 0, s, rows + (size_t)r0 * n, n, part);
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(summary_rows_final_kernel, dim3(nr), dim3(kBlock), 0, s, part, n_blocks, out + 4 * (size_t)r0);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,

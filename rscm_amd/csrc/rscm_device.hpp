@@ -841,6 +841,9 @@ struct WindowBatch {
     WindowOp ops[kMaxWindowOps];
 };
 hipError_t launch_window_batch(const WindowBatch& batch, int32_t n_ops, hipStream_t s);
+// the most rows one launch indexes with blockIdx.y (HIP's limit on gridDim.y): the launchers that put rows there -- the summaries
+// and the select's histograms -- go over a longer axis in slices of this many rows
+constexpr int32_t kMaxGridY = 65535;
 // per row of rows[n_rows][n]: partial[n_rows][n_blocks][4], then reduced into out[n_rows][4] = {count_finite, sum, min, max}
 int32_t summary_blocks(int64_t n);
 hipError_t launch_summary_rows(const double* rows, int64_t n, int32_t n_rows, double* partial, int32_t n_blocks,

@@ -376,7 +376,6 @@ hipError_t launch_select_hist(const double* const* d_rows, const int64_t* d_w, c
     hipError_t e = hipMemsetAsync(d_hist, 0, hist_elems * sizeof(int64_t), s);
     if (e != hipSuccess || n_rows <= 0 || N <= 0) return e;
     const unsigned bpr = (unsigned)select_blocks_per_row(N, n_rows);
-    constexpr int32_t kMaxGridY = 65535;
     if (d_group) {   // the grouped select: n_slots histograms per row, kSelGroup of them per launch
         const auto gkernel = d_w ? (d_base ? select_hist_kernel<true, true, true> : select_hist_kernel<true, false, true>)
                                  : (d_base ? select_hist_kernel<false, true, true> : select_hist_kernel<false, false, true>);
