@@ -116,7 +116,8 @@ RSCM_API int rscm_gpu_fail_chunk_launch(int32_t k);
  * O(T) recurrence: lags below `near_lags` months explicitly, the rest through decaying modes fitted to the
  * scaled impulse response (parameters/ocean_carbon.rs:85-216) by the host.  This runs that fit alone (no
  * GPU): the largest deviation of the fitted response from the tabulated one over the window (negative: the
- * parameters do not allow the recurrence and FAST keeps the tiled convolution), the number of modes, of
+ * parameters do not allow the recurrence, or the fit's amplitudes are too ill-conditioned for the device's double
+ * sums, and FAST keeps the tiled convolution -- the other outputs are then zero), the number of modes, of
  * modes that still weigh when a pulse leaves the window, and the largest amplitude. */
 RSCM_API int rscm_gpu_ocean_fit_selftest(int32_t model, double irf_scale, double irf_switch_time,
                                          int64_t max_history_months, double* max_error, int32_t* n_modes,

@@ -108,7 +108,9 @@ __device__ __forceinline__ void ocean_recur_run(const OceanArgs& a, const double
         const double dt = a.bounds[n + 1] - a.bounds[n];
         const double dt_month = dt / (double)STEPS;
         const double temp_factor = m.temp_on ? exp(m.temp_sens * delta_sst) : 1.0;
-        const bool leaving = m0 >= H;   // sub-steps of a step that straddles m = H take the general path below
+        // sub-steps of a step that straddles m = H (H no multiple of 12) take the general path below: EXIT 2, reached by
+        // tests/test_gpu_ocean_edges.py::test_recurrence_short_window at H = 245, 251, 487 and 493
+        const bool leaving = m0 >= H;
         const bool straddle = !leaving && m0 + STEPS > H;
         // The response values and mode constants of a step are wave-uniform and read with scalar loads.  They do not
         // fit the 102 SGPRs of a wave at once: an opaque zero offset per step keeps the compiler from hoisting them out

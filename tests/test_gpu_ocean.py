@@ -27,14 +27,27 @@ def orc():
     return cbind
 
 
-def _gpu(ra, bounds, P, inputs, pco2_0, cum_0, scen=None, chunks=()):
+def _gpu(ra, bounds, P, inputs, pco2_0, cum_0, scen=None, chunks=(), mode=None, recurrence=None, join_at=None, rewound=False):
+    """One run in launches that end at the time indices `chunks`.  `mode`: RSCM_MODE_* (the handle's default otherwise);
+    `recurrence`: what rscm_ens_ocean_fast_info must report for the handle; `join_at`: EXACT up to that index, `mode` from
+    there; `rewound`: the whole run a second time after a rewind, and that one's result."""
     with ra.Ensemble(ra.KIND_OCEAN_CARBON, P.shape[1], bounds) as e:
+        if mode is not None:
+            e.set_mode(ra.MODE_EXACT if join_at else mode)
         e.set_params(P)
         e.set_forcing(inputs, scen)
         e.set_initial(1, pco2_0)
         e.set_initial(2, cum_0)
+        if recurrence is not None:
+            assert _fast_info(e)[0] == recurrence
+        if rewound:
+            e.run()
+            e.rewind()
         for c in chunks:
             e.run(c)
+        if join_at:
+            e.run(join_at)
+            e.set_mode(mode)
         e.run()
         assert not e.status().any()
         return np.stack([e.get_series(v) for v in (1, 2, 3)])
@@ -277,7 +290,9 @@ def test_internal_state_kinds_refuse_time_jumps(ra, orc):
         assert np.array_equal(e.get_series(1), first)
 
 
-# measured over the three presets, temperature feedback on and off, 600 years: 5e-12 / 1.6e-11 / 5e-13 (printed below)
+# measured over the three presets, temperature feedback on and off, 600 years: 5e-12 / 1.6e-11 / 5e-13 (printed below);
+# at the shortest windows that take the recurrence, 61 years (tests/test_gpu_ocean_edges.py): 3D-GFDL 240 / 245 / 251 / 252 months
+# 1.33e-11 / 9.10e-12 / 8.08e-12 / 5.85e-12, 2D-BERN 480 / 487 / 493 months 3.18e-11 / 2.57e-11 / 3.06e-11
 FAST_TOL = 2e-10
 
 
@@ -295,9 +310,12 @@ def test_ocean_fast_mode_tolerance(ra, orc, model):
     explicitly, the older ones through 21 decaying modes fitted to the scaled impulse response (host fit,
     deviation from the table <= 5e-10, here ~1e-12) with one running sum each.  Against the EXACT mode
     (which equals the CPU oracle bit for bit) over 600 years -- the 500-year window fills and pulses leave
-    it -- the outputs agree to FAST_TOL = 2e-10 relative (measured <= 2e-11: printed).  Launch boundaries and
-    one-step launches do not change a bit of the FAST result; joining a run that EXACT began re-forms the
-    running sums from the flux history."""
+    it -- the outputs agree to FAST_TOL = 2e-10 relative (measured <= 2e-11: printed).  Launch boundaries do not
+    change a bit of the FAST result; the one-step launches here cover the first 89 of the 600 steps only, all of them
+    before any pulse leaves the window and before the ring wraps -- one step per launch across the exit, the straddle
+    step and the wrap is tests/test_gpu_ocean_edges.py::test_recurrence_short_window's.  Joining a run that EXACT
+    began re-forms the running sums from the flux history (every stage of the window:
+    test_recurrence_joins_a_run_that_exact_began there)."""
     rng = np.random.default_rng(12)
     n, T = 64, 601
     b = np.arange(T + 1, dtype=float) + 1750.0
