@@ -19,6 +19,11 @@ constexpr double kGtcPerPpm = 2.13;  // crates/rscm-components/src/constants.rs:
 // three-instruction quotient with the reciprocal hoisted (rk4_device.hpp), the numerators' exponent-window
 // tags folded into `acc` -- the year is replayed with the compiler's divisions if any tag falls outside,
 // as in the fused chain (coupled.hip, year<SPEC>), instead of a branch per division.
+// Held by tests/test_gpu_coupled_bits.py: with the device's own exp of alpha * T fed into a plain IEEE restatement of the year
+// (tests/host_coupled.py), the stand-alone kind -- table inputs, and linked into the four-handle graph in every launch shape --
+// gives that restatement's bits for every member: speculative == replayed == the reference's order, "linked == fused" included,
+// with lifetimes on both sides of the divisor window's edges, inf, 0 and NaN lifetimes (the replay condition below), zero numerators
+// and members running away to overflow (the fused doubling).  Against the CPU oracle the kind stays tolerance-parity: glibc's exp.
 template <bool SPEC>
 __device__ __forceinline__ int32_t carbon_cycle_year(double lifetime, double rlife, double conc_pi, double emis, double e_ppm, int32_t m, double hc,
                                                      double half_c, double sixth_c, double& conc, double& cum_u, double& cum_e, int32_t acc)

@@ -19,7 +19,15 @@
 // per-year lifetime and the per-member heat capacities use the speculative-year scheme of
 // two_layer.hip (three-instruction quotient + exponent-window tags, full IEEE division replay
 // when a tag falls outside).  exp/log come from the device math library and may differ from
-// glibc's by an ulp, so this kind is tolerance-parity (tests/test_gpu_parity.py), not bit-parity.
+// glibc's by an ulp, so AGAINST THE CPU ORACLE this kind is tolerance-parity (tests/test_gpu_parity.py:
+// 1e-11 on bounded members), not bit-parity.  Everything but those two values is held bit for bit, for
+// every member: tests/test_gpu_coupled_bits.py feeds the device's own exp / log_f64 of the year's two
+// arguments (rscm_gpu_selftest_math) into a plain IEEE restatement of the year (tests/host_coupled.py,
+// which equals the oracle bit for bit with glibc's exp / log in their place) and requires that
+// restatement's bits in all seven series and the status byte -- speculative year == replayed year ==
+// the reference's expression order -- on members that replay after year 0, sit on both sides of every
+// window edge, start a year with Ts = NaN (`settled` below), carry inf / NaN or run away through the
+// numerator window to overflow, in wavefronts shared with members whose speculative years stand.
 #include "carbon_body.hpp"
 #include "two_layer_body.hpp"
 

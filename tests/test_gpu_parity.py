@@ -15,7 +15,12 @@ Parity bars (stated here, as the task requires):
     |gpu - oracle| <= 1e-11 * max(1, |oracle|) on bounded members in RSCM_MODE_EXACT (the reference's
     expression order) and in RSCM_MODE_FAST (closed-form RK4 step of the linear carbon box, folded heat
     capacities, FMAs; measured 3e-13) alike -- every coupled test below runs in both.  Cumulative
-    emissions stay bit-exact in either mode.
+    emissions stay bit-exact in either mode.  What these tests do NOT hold: anything tighter than 1e-11,
+    and any member outside the `_bounded` mask (overflowing, inf and NaN members are not compared, the
+    status bytes only in the fuzz and only under the mask).  The EXACT arithmetic itself -- speculative
+    year == replayed year == the reference's expression order, every member, every series, the status
+    byte -- is held bit for bit in tests/test_gpu_coupled_bits.py, against a host restatement that takes
+    the two transcendental values per member-year from the device.
   * which kinds have a FAST arithmetic at all: two-layer, coupled, CarbonCycle, ClimateUDEB, OceanCarbon
     (include/rscm_gpu.h, RSCM_MODE_FAST); for every other kind the mode is accepted and changes nothing.
   * integer/index work (time indexing, scenario selection, status flags, LHS strata): exact.
@@ -960,7 +965,9 @@ def test_coupled_chain_fuzz(ra, orc, seed, mode):
     """Seeded random configurations of the fused coupled chain -- axis length, irregular step
     lengths, the two RK4 step sizes, 1 to 30 scenarios with or without a map, member-wise
     initial values, launch chunking -- against the oracle: 1e-11 on bounded members (device exp /
-    log), cumulative emissions (no transcendental) bit for bit, status flags exact.  (At most
+    log), cumulative emissions (no transcendental) bit for bit, status flags exact on those members.
+    (The same ten configurations, EXACT mode, every member, bit for bit with the device's exp / log
+    values: tests/test_gpu_coupled_bits.py.)  (At most
     30 x 199 x 8 B = 48 KB of emissions: always the static LDS staging.  The raised limit and the reads
     through L2 are in tests/test_gpu_input_staging.py.)"""
     rng = np.random.default_rng(5000 + seed)
