@@ -109,8 +109,11 @@ extern "C" {
  *  20  per-member covariability of two variables (covariance, correlation, regression slope, cross-correlation at up to three leads
  *      and lags): rscm_ens_member_covariability, RSCM_COV_MAX_LAGS
  *  21  per-member co-spectra of two variables in frequency bands (squared coherence, gain and quadrature gain per band):
- *      rscm_ens_member_cross_spectrum, rscm_gpu_spectrum_sines, RSCM_XSPEC_MAX_BANDS */
-#define RSCM_GPU_ABI_MINOR 21
+ *      rscm_ens_member_cross_spectrum, rscm_gpu_spectrum_sines, RSCM_XSPEC_MAX_BANDS
+ *  22  energy-budget diagnostics of a two-layer handle -- the member's forcing, radiative response, deep-ocean heat uptake and
+ *      top-of-atmosphere imbalance as diagnostic variables: rscm_ens_define_energy_budget, rscm_ens_diagnostic_quantity,
+ *      RSCM_BUDGET_FORCING, RSCM_BUDGET_RESPONSE, RSCM_BUDGET_DEEP_UPTAKE, RSCM_BUDGET_IMBALANCE */
+#define RSCM_GPU_ABI_MINOR 22
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1323,6 +1326,53 @@ RSCM_API int rscm_ens_diagnostic(rscm_ens* h, int32_t var_id, int32_t* n_terms, 
 RSCM_API int rscm_ens_compute_diagnostic(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride);
 RSCM_API int rscm_ens_clear_diagnostics(rscm_ens* h);
 RSCM_API int rscm_ens_n_diagnostics(const rscm_ens* h, int32_t* out);
+
+/* ---- energy-budget diagnostics (ABI minor 22) ------------------------------------------------------ */
+/* The terms of a two-layer member's energy budget as diagnostic variables: RSCM_KIND_TWO_LAYER handles only -- plain, mix
+ * (rscm_ens_create_mix) and every forcing-noise kind.  For member i and row t, Ts and Td its stored rows at t, p its parameter rows
+ * 0 .. 5 (lambda0, a, efficacy, eta, C, Cd), F its forcing (below), every line ONE f64 operation rounded on its own (no FMA), the same
+ * in either arithmetic mode:
+ *     ee  = p2 * p3              once per member
+ *     d   = Ts - Td
+ *     u   = p1 * Ts
+ *     lam = p0 - u
+ *     R   = lam * Ts             RSCM_BUDGET_RESPONSE      the radiative response (lambda0 - a Ts) Ts
+ *     X   = ee * d
+ *     H   = p3 * d               RSCM_BUDGET_DEEP_UPTAKE   the heat the deep ocean takes up, eta (Ts - Td)
+ *     g   = F - R
+ *     g   = g - X
+ *     N   = g + H                RSCM_BUDGET_IMBALANCE     the top-of-atmosphere imbalance, C dTs/dt + Cd dTd/dt
+ *     F                          RSCM_BUDGET_FORCING       the member's forcing
+ *     y   = scale * q            q the chosen quantity; multiplied even by 1.0
+ * (F - R) - X is the numerator of the reference's surface tendency (TwoLayer::calculate_dy_dt), N its third tendency.
+ *
+ * F is the forcing the stepping kernel applies to the step OUT of row t, bit for bit: forcing-axis index f = t + off, off = 0 for
+ * RSCM_SRC_EXOGENOUS and 1 for RSCM_SRC_UPSTREAM; the member's scenario's table value; on a mix handle S_0[f] * c_0, then
+ * + S_k[f] * c_k for k = 1 .. K - 1 in order; then + sigma * z(seed, member_offset + i, f) for white noise, or + e_f of the red or
+ * per-member recurrence formed from index 0 on (rscm_ens_set_forcing_noise*).  NaN and Inf propagate by IEEE arithmetic; there is no
+ * per-member flag.
+ *
+ * rscm_ens_define_energy_budget takes one of the RSCM_DIAG_MAX diagnostic slots; ids, rscm_ens_n_diagnostics and
+ * rscm_ens_clear_diagnostics work as for rscm_ens_define_diagnostic, and every reader of a diagnostic's rows takes the id.
+ * RSCM_ERR_INVALID for another kind, an unknown quantity, a scale that is not finite, a fifth definition, and for RSCM_BUDGET_FORCING
+ * and RSCM_BUDGET_IMBALANCE on a handle with a linked input (rscm_ens_link_input: the forcing is then another ensemble's series;
+ * the other two quantities need no forcing and are allowed).  RSCM_ERR_STATE while a staged select is in flight.
+ * rscm_ens_diagnostic_quantity reads a definition back; a linear diagnostic gives quantity 0 and scale 0.0.  rscm_ens_diagnostic on
+ * such an id reports n_terms = 0, the unused-term values and the held range.
+ * rscm_ens_compute_diagnostic serves both sorts; the source rows (Ts and Td) are resolved as a linear diagnostic's.  For the two
+ * quantities that read the forcing the host checks every forcing index before the launch: a row t with t + off >= n_times gets
+ * RSCM_ERR_INVALID naming the row (the last row of a RSCM_SRC_UPSTREAM handle: no step leaves it), a handle that has been linked since
+ * RSCM_ERR_INVALID, forcing that was never set RSCM_ERR_STATE.  Parameters that were never set: RSCM_ERR_STATE.
+ *
+ * Staleness.  The rows go stale with the write epoch like every diagnostic's.  Those of RSCM_BUDGET_FORCING and _IMBALANCE go stale
+ * as well with whatever replaces the forcing table, the scenario assignment or the source: rscm_ens_set_forcing (a mix handle's
+ * included), rscm_ens_link_input, rscm_ens_unlink_input.  The linear diagnostics and the other two quantities do not. */
+#define RSCM_BUDGET_FORCING 1
+#define RSCM_BUDGET_RESPONSE 2
+#define RSCM_BUDGET_DEEP_UPTAKE 3
+#define RSCM_BUDGET_IMBALANCE 4
+RSCM_API int rscm_ens_define_energy_budget(rscm_ens* h, int32_t quantity, double scale, int32_t* var_id_out);
+RSCM_API int rscm_ens_diagnostic_quantity(rscm_ens* h, int32_t var_id, int32_t* quantity, double* scale);
 
 /* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
 /* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,

@@ -472,6 +472,7 @@ class ModelBuilder:
         self._noise_phi = 0.0                             # ... and its phi (0: white)
         self._noise_params = False                        # with_forcing_noise_parameters: sigma and phi are parameter rows
         self._diagnostics: List[Tuple[str, Dict[str, Optional[str]], Dict[str, float]]] = []   # with_diagnostic
+        self._energy_budgets: List[Tuple[str, str, float]] = []   # with_energy_budget: (quantity, name, scale)
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -541,8 +542,24 @@ class ModelBuilder:
                                   {str(v): float((scales or {}).get(v, 1.0)) for v in weights}))
         return self
 
+    def with_energy_budget(self, quantity: str, name: Optional[str] = None, scale: float = 1.0) -> "ModelBuilder":
+        """Extension: a term of the two-layer energy budget as a diagnostic variable of the built model --
+        ``"forcing" | "response" | "deep_uptake" | "imbalance"`` (``Ensemble.define_energy_budget``; ``name`` defaults to the
+        quantity's own).  ``build()`` defines it on the model's two-layer ensemble, or in a graph on its one two-layer ensemble
+        (``GraphModel.define_energy_budget``: with a linked forcing the two forcing-free quantities only)."""
+        if quantity not in L.BUDGET_QUANTITIES:
+            raise ValueError(f"unknown energy-budget quantity {quantity!r}; one of {sorted(L.BUDGET_QUANTITIES)}")
+        name = L.BUDGET_DEFAULT_NAMES[quantity] if name is None else str(name)
+        if any(name == n for n, _, _ in self._diagnostics) or any(name == n for _, n, _ in self._energy_budgets):
+            raise ValueError(f"diagnostic {name!r} is defined already")
+        self._energy_budgets.append((str(quantity), name, float(scale)))
+        return self
+
     def _define_diagnostics(self, model):
-        """What ``build()`` does with ``with_diagnostic``: on the ensemble of a ``Model`` or the homes of a ``GraphModel``."""
+        """What ``build()`` does with ``with_diagnostic`` and ``with_energy_budget``: on the ensemble of a ``Model`` or the homes
+        of a ``GraphModel``."""
+        for quantity, name, scale in self._energy_budgets:
+            (model if isinstance(model, GraphModel) else model.ensemble).define_energy_budget(quantity, name, scale)
         for name, weights, scales in self._diagnostics:
             if isinstance(model, GraphModel):
                 model.define_diagnostic(name, [(v, p, scales[v]) for v, p in weights.items()])
@@ -1536,6 +1553,22 @@ class GraphModel:
                 row = self.param_home[row][1]
             resolved.append((vid, row) + tuple(t[2:3]))
         vid = self.ensembles[owners[0]].define_diagnostic(name, resolved)
+        self._diagnostics[name] = (owners[0], vid)
+        return vid
+
+    def define_energy_budget(self, quantity: str, name: Optional[str] = None, scale: float = 1.0) -> int:
+        """``Ensemble.define_energy_budget`` on the graph's one two-layer ensemble (``ValueError`` for none or for several).  Where
+        that ensemble's forcing is linked -- it usually is in a graph -- only ``"response"`` and ``"deep_uptake"`` are
+        available: the library refuses ``"forcing"`` and ``"imbalance"`` there."""
+        if quantity not in L.BUDGET_QUANTITIES:
+            raise ValueError(f"unknown energy-budget quantity {quantity!r}; one of {sorted(L.BUDGET_QUANTITIES)}")
+        name = L.BUDGET_DEFAULT_NAMES[quantity] if name is None else name
+        if name in self._diagnostics or name in self._var_home:
+            raise ValueError(f"variable name {name!r} is taken")
+        owners = [o for o, ens in self.ensembles.items() if ens.kind == L.KIND_TWO_LAYER]
+        if len(owners) != 1:
+            raise ValueError(f"define_energy_budget needs exactly one two-layer ensemble in the graph, found {len(owners)}: {owners}")
+        vid = self.ensembles[owners[0]].define_energy_budget(quantity, name, scale)
         self._diagnostics[name] = (owners[0], vid)
         return vid
 

@@ -7,6 +7,9 @@
 // every row computed and resident).  The rows are a snapshot of the sources at the handle's write epoch (ens.hpp, rows_written): a
 // reader that finds another epoch is told to compute again.  A staged select may be reading the rows, so nothing here runs while
 // one is in flight.
+//
+// An energy-budget diagnostic (energy_budget_host.cpp) takes one of the same slots and is computed through the same entry point: its
+// sources are the two state rows of the two-layer kind, its checks and its launch are budget_check and budget_launch.
 #include <cmath>
 
 #include "diagnostic.hpp"
@@ -57,6 +60,8 @@ int rscm_ens_define_diagnostic(rscm_ens* h, int32_t n_terms, const int32_t* term
         d.row[k] = term_param_row[k];
         d.scale[k] = term_scale[k];
     }
+    d.quantity = 0;
+    d.budget_scale = 0.0;
     d.held = 0;
     *var_id_out = h->V + h->n_diag++;
     return RSCM_OK;
@@ -76,7 +81,7 @@ int rscm_ens_diagnostic(rscm_ens* h, int32_t var_id, int32_t* n_terms, int32_t t
         if (term_param_row) term_param_row[k] = on ? d.row[k] : -1;
         if (term_scale) term_scale[k] = on ? d.scale[k] : 0.0;
     }
-    const bool current = d.held > 0 && d.epoch == h->write_epoch;
+    const bool current = d.held > 0 && h->diagnostic_current(d);
     if (rows_held) *rows_held = current ? d.held : 0;
     if (t_begin) *t_begin = current ? d.t_begin : 0;
     if (t_stride) *t_stride = current ? d.t_stride : 1;
@@ -93,13 +98,17 @@ int rscm_ens_compute_diagnostic(rscm_ens* h, int32_t var_id, int32_t t_begin, in
     // the sources' rows, term after term: [K][R]
     std::vector<const double*> rows, term_rows;
     std::vector<double> times;
-    for (int32_t k = 0; k < d.n_terms; ++k) {
+    const bool budget = d.quantity != 0;   // its sources: Ts, then Td
+    const int32_t budget_var[2] = {RSCM_TL_VAR_TS, RSCM_TL_VAR_TD};
+    for (int32_t k = 0; k < (budget ? 2 : d.n_terms); ++k) {
         term_rows.clear();
         times.clear();
-        if (int rc = period_rows(h, d.var[k], t_begin, t_end, t_stride, term_rows, times)) return rc;
+        if (int rc = period_rows(h, budget ? budget_var[k] : d.var[k], t_begin, t_end, t_stride, term_rows, times)) return rc;
         rows.insert(rows.end(), term_rows.begin(), term_rows.end());
     }
     const size_t R = times.size();
+    if (budget)
+        if (int rc = budget_check(h, d, t_begin, t_stride, (int32_t)R)) return rc;
     bool reads_params = false;
     for (int32_t k = 0; k < d.n_terms; ++k) reads_params = reads_params || d.row[k] >= 0;
     if (reads_params && !h->params_set) return fail(RSCM_ERR_STATE, "parameters not set: a term's weight reads a parameter row");
@@ -113,6 +122,17 @@ int rscm_ens_compute_diagnostic(rscm_ens* h, int32_t var_id, int32_t t_begin, in
     rscm::DevBuf<const double*> d_src;   // lives until the synchronise below
     HIPCHK(d_src.alloc(rows.size()));
     HIPCHK(hipMemcpyAsync(d_src.get(), rows.data(), rows.size() * sizeof(double*), hipMemcpyHostToDevice, h->stream));
+    if (budget) {
+        d.held = 0;   // (as below)
+        HIPCHK(budget_launch(h, d, d_src.get(), t_begin, t_stride, (int32_t)R));
+        HIPCHK(hipStreamSynchronize(h->stream));
+        d.held = (int32_t)R;
+        d.t_begin = t_begin;
+        d.t_stride = t_stride;
+        d.epoch = h->write_epoch;
+        d.forcing_epoch = h->forcing_epoch;
+        return RSCM_OK;
+    }
     rscm::DiagnosticArgs a{};
     a.d_rows = d_src.get();
     a.d_params = h->d_params;

@@ -183,26 +183,36 @@ struct rscm_ens : EnsQueues {
     // write_epoch moves with everything that can change a stored row, a parameter row or the time index (rows_written(): step_finish
     // for every run, params_written(), launch_loglik for the fused runs, set_noise, put_at() / initial_written() and the entry points
     // that write a state), and a store serves its rows only at the epoch it was computed at.
+    // An energy-budget diagnostic (energy_budget_host.cpp; kernels in energy_budget.hip) takes one of the same slots: quantity is its
+    // RSCM_BUDGET_* (0: a linear combination), budget_scale its scale, n_terms 0.  The two quantities that read the forcing are a
+    // snapshot of it as well: forcing_epoch moves with whatever replaces the forcing table, the scenario assignment or the source
+    // (rscm_ens_set_forcing, a mix handle's included) and with a link made or dropped, and their rows serve only at the forcing epoch
+    // they were computed at.  The linear diagnostics and the two forcing-free quantities do not look at it.
     struct Diagnostic {
         int32_t n_terms = 0;
         int32_t var[RSCM_DIAG_MAX_TERMS] = {}, row[RSCM_DIAG_MAX_TERMS] = {};
         double scale[RSCM_DIAG_MAX_TERMS] = {};
+        int32_t quantity = 0;
+        double budget_scale = 0.0;
         rscm::DevBuf<double> d_rows;   // [size() / N][N]: room for at least `held` rows
         int32_t held = 0, t_begin = 0, t_stride = 1;
-        uint64_t epoch = 0;
+        uint64_t epoch = 0, forcing_epoch = 0;
+        bool reads_forcing() const { return quantity == RSCM_BUDGET_FORCING || quantity == RSCM_BUDGET_IMBALANCE; }
     };
     Diagnostic diag[RSCM_DIAG_MAX];
     int32_t n_diag = 0;
-    uint64_t write_epoch = 1;
+    uint64_t write_epoch = 1, forcing_epoch = 1;
     void rows_written() { ++write_epoch; }
+    void forcing_replaced() { ++forcing_epoch; }
     bool is_diagnostic(int32_t var) const { return var >= V && var < V + n_diag; }
     bool has_rows(int32_t var) const { return var >= 1 && var < V + n_diag; }   // a stored variable or a diagnostic
-    bool diagnostic_stale(int32_t var) const { return diag[var - V].held > 0 && diag[var - V].epoch != write_epoch; }
+    bool diagnostic_current(const Diagnostic& d) const { return d.epoch == write_epoch && (!d.reads_forcing() || d.forcing_epoch == forcing_epoch); }
+    bool diagnostic_stale(int32_t var) const { return diag[var - V].held > 0 && !diagnostic_current(diag[var - V]); }
     const double* diagnostic_row(int32_t var, int32_t t) const
     {
         if (!is_diagnostic(var)) return nullptr;
         const Diagnostic& d = diag[var - V];
-        if (d.epoch != write_epoch || t < d.t_begin || (t - d.t_begin) % d.t_stride != 0) return nullptr;
+        if (!diagnostic_current(d) || t < d.t_begin || (t - d.t_begin) % d.t_stride != 0) return nullptr;
         const int32_t r = (t - d.t_begin) / d.t_stride;
         return r < d.held ? d.d_rows + (size_t)r * N : nullptr;
     }
@@ -378,6 +388,12 @@ int check_series_stored(const rscm_ens* h, int32_t t_end);
 // RSCM_OK for a stored variable and for a diagnostic whose rows are current; RSCM_ERR_STATE "diagnostic N is stale: compute it again"
 // (diagnostic_host.cpp).  What every reader of a diagnostic's rows asks before it resolves them.
 int check_diagnostic_current(const rscm_ens* h, int32_t var_id);
+// An energy-budget diagnostic inside rscm_ens_compute_diagnostic (energy_budget_host.cpp).  budget_check: what the host proves before
+// anything is launched for the rows t_begin + r * t_stride, r < n_rows -- parameters set, and for the quantities that read the forcing:
+// no linked input, forcing set, every forcing-axis index on the axis.  budget_launch: the kernel over the uploaded source rows
+// d_src [2][n_rows] (Ts, Td) into d.d_rows, enqueued on the handle's stream.
+int budget_check(const rscm_ens* h, const rscm_ens::Diagnostic& d, int32_t t_begin, int32_t t_stride, int32_t n_rows);
+hipError_t budget_launch(rscm_ens* h, rscm_ens::Diagnostic& d, const double* const* d_src, int32_t t_begin, int32_t t_stride, int32_t n_rows);
 int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                  int32_t* n_range);
 // resolve_rows with its checks for a range every row of which must be computed (RSCM_ERR_STATE else), and the rows' times

@@ -409,6 +409,7 @@ int rscm_ens_set_forcing(rscm_ens* h, int32_t var_id, int32_t n_scen, const doub
     if (int rc = set_device(h)) return rc;
     HIPCHK(hipStreamSynchronize(h->stream));
     h->year_facts.drop_forcing();   // from here on the table may change: the verdict on the new one is formed once it stands
+    h->forcing_replaced();          // ... and so do the rows of the energy-budget diagnostics that read the forcing (ens.hpp)
     // Tables of the same scenario count are rewritten where they stand.  Tables of another count are built aside and moved in,
     // with n_scen, once they are written: a failure on the way leaves the handle with the tables and the count it had.
     const bool resize = n_scen != h->n_scen || !h->d_forcing;
@@ -483,6 +484,7 @@ int rscm_ens_link_input(rscm_ens* h, int32_t input_row, rscm_ens* src, int32_t s
     l.var = src_var;
     l.off = source == RSCM_SRC_UPSTREAM ? 1 : 0;
     ++src->link_refs;
+    h->forcing_replaced();
     return RSCM_OK;
     GUARD_END
 }
@@ -507,6 +509,7 @@ int rscm_ens_unlink_input(rscm_ens* h, int32_t input_row)
         --l.src->link_refs;
         --h->n_linked;
         l = rscm_ens::Link{};
+        h->forcing_replaced();
     }
     return RSCM_OK;
 }

@@ -331,6 +331,12 @@ class ShardedEnsemble:
         whole ensemble's and no collective is needed; ``quantile_rows_global`` and ``constrain`` then take the name."""
         return self.ensemble.define_diagnostic(name, terms)
 
+    def define_energy_budget(self, quantity: str, name: Optional[str] = None, scale: float = 1.0) -> int:
+        """``Ensemble.define_energy_budget`` on this rank's block.  The quantities are per member; a shard's forcing noise is drawn
+        for its members' ids in the whole ensemble (the block's member offset, as in its run), so the shards' rows are the whole
+        ensemble's."""
+        return self.ensemble.define_energy_budget(quantity, name, scale)
+
     def compute_diagnostic(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
         """``Ensemble.compute_diagnostic`` on this rank's block; every rank calls it with the same range."""
         self.ensemble.compute_diagnostic(var, t_begin, t_end, t_stride)

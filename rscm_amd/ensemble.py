@@ -815,6 +815,33 @@ class Ensemble:
             raise ValueError("define_heat_content: the two-layer kind only (its rows 4 and 5 are the heat capacities)")
         return self.define_diagnostic(name, [("Surface Temperature", 4, scale), ("Deep Ocean Temperature", 5, scale)])
 
+    def define_energy_budget(self, quantity: str, name: Optional[str] = None, scale: float = 1.0) -> int:
+        """A term of a two-layer member's energy budget as a diagnostic variable (plain, mix and every noise kind), read by name
+        like any diagnostic once ``compute_diagnostic`` has formed its rows.  ``quantity``: ``"forcing"`` -- the forcing F the
+        member saw, its scenario or mix sum with its noise; ``"response"`` -- ``(lambda0 - a Ts) Ts``; ``"deep_uptake"`` --
+        ``eta (Ts - Td)``; ``"imbalance"`` -- the top-of-atmosphere imbalance ``N = F - response - (efficacy - 1) eta (Ts - Td)``,
+        which is ``C dTs/dt + Cd dTd/dt``.  Row t holds the value at the start of the step out of row t, in W m^-2 times ``scale``
+        (rscm_ens_define_energy_budget states the arithmetic).  ``name`` defaults to ``"Member Forcing"``, ``"Radiative
+        Response"``, ``"Deep Ocean Heat Uptake"``, ``"Top of Atmosphere Imbalance"``.  ``"forcing"`` and ``"imbalance"`` go
+        stale with ``set_forcing`` as well as with everything that makes a diagnostic stale, and are refused on an ensemble whose
+        forcing is linked.  ``covariability("Surface Temperature", N)["slope"]`` is each member's Gregory slope.  Returns the id."""
+        if quantity not in L.BUDGET_QUANTITIES:
+            raise ValueError(f"unknown energy-budget quantity {quantity!r}; one of {sorted(L.BUDGET_QUANTITIES)}")
+        name = L.BUDGET_DEFAULT_NAMES[quantity] if name is None else name
+        if not isinstance(name, str) or not name:
+            raise ValueError("a diagnostic needs a name")
+        if name in self.var_ids:
+            raise ValueError(f"variable name {name!r} is taken")
+        vid = C.c_int32()
+        L.check(self._lib.rscm_ens_define_energy_budget(self._h, L.BUDGET_QUANTITIES[quantity], float(scale), C.byref(vid)))
+        self.var_ids[name] = vid.value
+        self._diagnostic_names[name] = vid.value
+        return vid.value
+
+    def define_toa_imbalance(self, name: str = "Top of Atmosphere Imbalance", scale: float = 1.0) -> int:
+        """``define_energy_budget("imbalance", name, scale)``: the quantity observations constrain the feedback through."""
+        return self.define_energy_budget("imbalance", name, scale)
+
     def compute_diagnostic(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
         """Form the rows ``t_begin, t_begin + t_stride, ... < t_end`` of diagnostic ``var`` from the stored rows and the parameters
         as they stand (``t_end=None``: up to and including the current time index).  They are a snapshot: after anything that
@@ -826,8 +853,11 @@ class Ensemble:
     @property
     def diagnostics(self) -> Dict[str, Dict[str, object]]:
         """The definitions as the library holds them, by name: ``{"id", "terms": [(var id, param row or None, scale)],
-        "rows_held", "t_begin", "t_stride"}`` (``rows_held`` 0 when nothing is computed or the rows are stale)."""
+        "rows_held", "t_begin", "t_stride", "quantity", "scale"}`` (``rows_held`` 0 when nothing is computed or the rows are stale;
+        ``quantity`` is ``None`` and ``scale`` ``None`` for a linear diagnostic, the name of the energy-budget quantity and its
+        scale for one of ``define_energy_budget``, whose ``terms`` are empty)."""
         out = {}
+        quantity_names = {v: k for k, v in L.BUDGET_QUANTITIES.items()}
         for name, vid in self._diagnostic_names.items():
             n, held, tb, st = (C.c_int32() for _ in range(4))
             tv, tr = np.zeros(L.DIAG_MAX_TERMS, dtype=np.int32), np.zeros(L.DIAG_MAX_TERMS, dtype=np.int32)
@@ -836,6 +866,10 @@ class Ensemble:
                                                   C.byref(st)))
             out[name] = {"id": vid, "terms": [(int(tv[k]), None if tr[k] < 0 else int(tr[k]), float(ts[k])) for k in range(n.value)],
                          "rows_held": held.value, "t_begin": tb.value, "t_stride": st.value}
+            q, qs = C.c_int32(), C.c_double()
+            L.check(self._lib.rscm_ens_diagnostic_quantity(self._h, vid, C.byref(q), C.byref(qs)))
+            out[name]["quantity"] = quantity_names.get(q.value)
+            out[name]["scale"] = qs.value if q.value else None
         return out
 
     def clear_diagnostics(self) -> None:
@@ -1076,8 +1110,12 @@ class Ensemble:
         for sidx in range(scenarios):
             self.branch(dst, anc, sidx * n_draws)
         for name, d in self.diagnostics.items():   # the projection can be summarised the way the source is (rows: dst's to compute)
-            if name not in dst.var_ids:
+            if name in dst.var_ids:
+                continue
+            if d["quantity"] is None:
                 dst.define_diagnostic(name, d["terms"])
+            else:
+                dst.define_energy_budget(d["quantity"], name, d["scale"])
         scenario_of_member = np.repeat(np.arange(scenarios, dtype=np.int32), n_draws)
         if scenarios <= 64:   # more scenarios than the library has groups: the blocks stay ungrouped
             dst.set_member_groups(scenario_of_member, scenarios)

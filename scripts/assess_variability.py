@@ -48,7 +48,13 @@ likelihoods before it ("all").  The sigmas are the usual large-sample ones for a
 ``sqrt((1 - coh2) / (2 m coh2)) |gain|`` for both gains (``|gain|`` the magnitude of the complex gain, ``hypot(gain, gain_quad)``) and ``sqrt(2 / m) (1 - coh2) sqrt(coh2)`` for coh2, at the record's values,
 times ``sqrt(2)`` as for every other target here (record and member are one realisation each).
 
-    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content] [--covariability]
+With ``--toa-imbalance`` (it requires ``--heat-content`` too) the record's top-of-atmosphere imbalance is a target (DESIGN.md
+section 8u): N as an energy-budget diagnostic (``define_toa_imbalance``) of the truth member and of every member, the correlation
+and the regression slope of N on the temperature, both linearly detrended, lag 0 -- the record's Gregory slope --
+``series_covariability(temperature, N, "linear", "linear", 0)`` against ``Ensemble.covariability``, scored alone ("toa_imbalance")
+and added onto the temperature-plus-heat-content likelihood ("all"); the 5-95 % range of lambda0 with and without it goes to stderr.
+
+    python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content] [--covariability] [--toa-imbalance]
                                          [--cross-spectrum]
 
 Prints one JSON line; exit code 0 iff every comparison holds."""
@@ -107,7 +113,11 @@ def main():
                     help="also weight by the covariability of the record's heat uptake and temperature (requires --heat-content)")
     ap.add_argument("--cross-spectrum", action="store_true",
                     help="also weight by the band coherence and gains of the record's heat uptake on its temperature (requires --heat-content)")
+    ap.add_argument("--toa-imbalance", action="store_true",
+                    help="also weight by the covariability of the record's temperature and top-of-atmosphere imbalance (requires --heat-content)")
     a = ap.parse_args()
+    if a.toa_imbalance and not a.heat_content:
+        ap.error("--toa-imbalance requires --heat-content")
     if a.covariability and not a.heat_content:
         ap.error("--covariability requires --heat-content")
     if a.cross_spectrum and not a.heat_content:
@@ -122,6 +132,11 @@ def main():
         annual = truth.get_series(TS, 0, NOW + 1)[:, 0]
         record = annual[rows]
         annual_heat = TRUTH[4] * annual + TRUTH[5] * truth.get_series("Deep Ocean Temperature", 0, NOW + 1)[:, 0]
+        annual_toa = None
+        if a.toa_imbalance:
+            nid = truth.define_toa_imbalance()
+            truth.compute_diagnostic(nid, 0, NOW + 1)
+            annual_toa = truth.get_series(nid, 0, NOW + 1)[:, 0]
 
     with make(a.members, mode, seed=1) as ens:
         sigma_row, phi_row = ens.noise_param_rows
@@ -254,6 +269,53 @@ def main():
             checks["covariability_equals_the_host_estimator"] = bool(all(
                 np.array_equal(d.to_host()[:64], h, equal_nan=True) for d, h in zip(cstats, [one["corr"], one["slope"], one["lead"][0], one["lag"][0]])))
 
+        toa = None
+        if a.toa_imbalance:
+            # the quantity the feedback is observed through: N as a diagnostic variable, its regression on the
+            # temperature (both about their lines, lag 0: the Gregory slope of the record) alone and added onto the temperature-plus-
+            # heat-content likelihood, which is formed again (the branches above continued it in place)
+            tnamed = {"sigma": sigma_row, "phi": phi_row, "lambda0": 0, "efficacy": 2, "heat_capacity_surface": 4, "heat_capacity_deep": 5}
+            tvec = [ens.params_vector(r) for r in tnamed.values()]
+
+            def tweigh(l):
+                ens.set_weights_from_loglik(l)
+                q = ens.quantile_vectors(tvec, q3, weighted=True)["quantiles"]
+                return {"ess": ens.weights_stats()["ess"], **{k: q[j].tolist() for j, k in enumerate(tnamed)}}
+
+            lls = ens.loglik_vectors(stats, values, sigmas)
+            if a.spectrum:
+                spec = ens.spectrum(TS, 0, NOW + 1, detrend="difference", bands=rec["edges"], slot=1)
+                lls = ens.loglik_spectrum(spec["power"], rec["power"], rec["counts"], add_to=lls)
+            lls = ens.loglik_vectors([hvar["sd"], hvar["r1"]], hvalues, hsigmas, add_to=lls)
+            if a.spectrum:
+                lls = ens.loglik_spectrum(hspec["power"], hrec["power"], hrec["counts"], add_to=lls)
+            tt = series_covariability(annual, annual_toa, "linear", "linear", 0)
+            n_rows = annual.size
+            tvalues = [tt["corr"], tt["slope"]]
+            tsigmas = [np.sqrt(2.0) * (1.0 - tt["corr"] ** 2) / np.sqrt(n_rows),
+                       np.sqrt(2.0) * np.sqrt((tt["var_y"] - tt["slope"] * tt["cov"]) / (n_rows * tt["var_x"]))]
+            toa = {"quantiles": q3, "target": dict(zip(("corr", "slope"), map(float, tvalues))),
+                   "target_sigma": dict(zip(("corr", "slope"), map(float, tsigmas))),
+                   "prior": {k: q.tolist() for k, q in zip(tnamed, ens.quantile_vectors(tvec, q3)["quantiles"])},
+                   "temperature_and_heat_content": tweigh(lls)}
+            nid = ens.define_toa_imbalance()
+            ens.compute_diagnostic(nid, 0, NOW + 1)
+            c = ens.covariability(TS, nid, 0, NOW + 1, 1, "linear", "linear", 0, slot=1)
+            tstats = [c["corr"], c["slope"]]
+            toa["all"] = tweigh(ens.loglik_vectors(tstats, tvalues, tsigmas, add_to=lls))
+            toa["toa_imbalance"] = tweigh(ens.loglik_vectors(tstats, tvalues, tsigmas))
+            w = ens.member_weights()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore", RuntimeWarning)
+                want = [np.nanquantile(P[r], q3, weights=w, method="inverted_cdf").tolist() for r in tnamed.values()]
+            checks["toa_imbalance_weighted_quantiles_equal_numpy"] = bool(want == [toa["toa_imbalance"][k] for k in tnamed])
+            one = series_covariability(ens.get_series(TS, 0, NOW + 1)[:, :64], ens.get_series(nid, 0, NOW + 1)[:, :64], "linear", "linear", 0)
+            checks["toa_imbalance_equals_the_host_estimator"] = bool(all(
+                np.array_equal(d.to_host()[:64], h, equal_nan=True) for d, h in zip(tstats, [one["corr"], one["slope"]])))
+            for label, key in (("without the imbalance", "temperature_and_heat_content"), ("with it", "all"), ("the imbalance alone", "toa_imbalance")):
+                lo, _, hi = toa[key]["lambda0"]
+                print(f"lambda0 5-95 % {label}: {lo:.3f} .. {hi:.3f}  (ESS {toa[key]['ess']:.1f})", file=sys.stderr)
+
         xspec = None
         if a.cross_spectrum:
             # the relation per frequency band, alone and continued from every likelihood above
@@ -326,6 +388,8 @@ def main():
         res["heat_content"] = heat
     if cov is not None:
         res["covariability"] = cov
+    if toa is not None:
+        res["toa_imbalance"] = toa
     if xspec is not None:
         res["cross_spectrum"] = xspec
     print(json.dumps(res), flush=True)
