@@ -221,7 +221,7 @@ AG_VARS = {"contributors": 0, "aggregate": 1}
 AG_PARAM_NAMES = ("operation",) + tuple(f"weight_{k}" for k in range(AG_NINPUTS))
 AG_OPERATIONS = {"Sum": 0.0, "Mean": 1.0, "Weighted": 2.0, "Count": 3.0, "CountCarry": 4.0, "Quotient": 5.0}
 
-# per kind: (variable ids, parameter names, input rows of variable 0 or None for a single series)
+# per kind: (variable ids, number of parameter rows, input rows of variable 0 or None for a single series)
 KIND_TABLE = {
     KIND_TWO_LAYER: (TL_VARS, 6, None), KIND_COUPLED: (CP_VARS, 10, None), KIND_UDEB: (UD_VARS, 37, None),
     KIND_GHG_FORCING: (GH_VARS, 21, GH_INPUTS), KIND_OZONE_FORCING: (OZ_VARS, 13, OZ_INPUTS),
@@ -232,6 +232,20 @@ KIND_TABLE = {
     KIND_FOURBOX_OHU: (FB_VARS, 4, FB_INPUTS), KIND_OSPP: (SP_VARS, 13, SP_INPUTS),
     KIND_CARBON_CYCLE: (CC_VARS, 3, CC_INPUTS), KIND_CO2_ERF: (CE_VARS, 2, CE_INPUTS),
     KIND_AGGREGATE: (AG_VARS, 9, AG_INPUTS)}
+TL_PARAM_NAMES = ("lambda0", "a", "efficacy", "eta", "heat_capacity_surface", "heat_capacity_deep")
+CP_PARAM_NAMES = TL_PARAM_NAMES + ("tau", "conc_pi", "alpha_temperature", "erf_2xco2")
+# per kind: the names of its parameter rows, in row order
+PARAM_NAMES = {
+    KIND_TWO_LAYER: TL_PARAM_NAMES, KIND_COUPLED: CP_PARAM_NAMES, KIND_UDEB: UD_PARAM_NAMES,
+    KIND_GHG_FORCING: GH_PARAM_NAMES, KIND_OZONE_FORCING: OZ_PARAM_NAMES,
+    KIND_AEROSOL_DIRECT: AD_PARAM_NAMES, KIND_AEROSOL_INDIRECT: AI_PARAM_NAMES,
+    KIND_CH4_CHEMISTRY: CH4_PARAM_NAMES, KIND_N2O_CHEMISTRY: N2O_PARAM_NAMES,
+    KIND_CO2_BUDGET: CB_PARAM_NAMES, KIND_TERRESTRIAL_CARBON: TC_PARAM_NAMES,
+    KIND_OCEAN_CARBON: OC_PARAM_NAMES, KIND_HALOCARBON: HC_PARAM_NAMES,
+    KIND_FOURBOX_OHU: FB_PARAM_NAMES, KIND_OSPP: SP_PARAM_NAMES,
+    KIND_CARBON_CYCLE: CC_PARAM_NAMES, KIND_CO2_ERF: CE_PARAM_NAMES,
+    KIND_AGGREGATE: AG_PARAM_NAMES}
+assert all(len(PARAM_NAMES[kind]) == n_params for kind, (_, n_params, _) in KIND_TABLE.items())
 # FourBox variables stored as four scalar series: kind -> (name, first variable id)
 FOURBOX_VARS = {KIND_UDEB: ("Surface Temperature", 1),
                 KIND_AEROSOL_DIRECT: ("Effective Radiative Forcing|Aerosol|Direct", 1),

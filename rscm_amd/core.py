@@ -29,7 +29,9 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib as L
+from . import graph_plan
 from .ensemble import Ensemble, run_lockstep
+from .graph_plan import COMPONENT_KINDS, OWN_KERNEL_TYPES, STATELESS_KINDS, SUPPORTED, is_host_component  # noqa: F401
 
 NAN = float("nan")
 
@@ -433,27 +435,8 @@ class ComponentBuilder:
 
 
 # ------------------------------------------------------------------------------------ builder
-SUPPORTED = ("any graph of the built-in components with scalar links (one linked ensemble per component, "
-             "stepped in the reference's graph order); fused single-launch kernels for: "
-             "[ClimateUDEB] with exogenous 'Effective Radiative Forcing'",
-             "[GhgForcing] | [OzoneForcing] | [AerosolDirect] | [AerosolIndirect] | [CH4Chemistry] | "
-             "[N2OChemistry] | [CO2Budget] | [TerrestrialCarbon] | [OceanCarbon] | [HalocarbonChemistry] | "
-             "[FourBoxOceanHeatUptake] | [OceanSurfacePartialPressure] with their inputs as "
-             "exogenous series",
-             "[TwoLayer] with exogenous or upstream 'Effective Radiative Forcing'",
-             "[CarbonCycle, CO2ERF, TwoLayer] + Sum aggregate 'Effective Radiative Forcing' "
-             "over ['Effective Radiative Forcing|CO2'] (registration order as listed)")
-
-# single-component graphs whose inputs are all exogenous rows of the input block
-STATELESS_KINDS = {"GhgForcing": L.KIND_GHG_FORCING, "OzoneForcing": L.KIND_OZONE_FORCING,
-                   "AerosolDirect": L.KIND_AEROSOL_DIRECT, "AerosolIndirect": L.KIND_AEROSOL_INDIRECT,
-                   "CH4Chemistry": L.KIND_CH4_CHEMISTRY, "N2OChemistry": L.KIND_N2O_CHEMISTRY,
-                   "CO2Budget": L.KIND_CO2_BUDGET, "TerrestrialCarbon": L.KIND_TERRESTRIAL_CARBON,
-                   "OceanCarbon": L.KIND_OCEAN_CARBON, "HalocarbonChemistry": L.KIND_HALOCARBON,
-                   "FourBoxOceanHeatUptake": L.KIND_FOURBOX_OHU, "OceanSurfacePartialPressure": L.KIND_OSPP}
-
-TL_PARAM_ORDER = ("lambda0", "a", "efficacy", "eta", "heat_capacity_surface", "heat_capacity_deep")
-CP_PARAM_ORDER = TL_PARAM_ORDER + ("tau", "conc_pi", "alpha_temperature", "erf_2xco2")
+TL_PARAM_ORDER = L.TL_PARAM_NAMES
+CP_PARAM_ORDER = L.CP_PARAM_NAMES
 
 
 class ModelBuilder:
@@ -644,7 +627,7 @@ class ModelBuilder:
         types = [c.type_name for c in self._components]
         if series_window is not None:
             why = "series_window builds a graph of windowed ensembles"
-        elif any(getattr(c, "is_python", False) for c in self._components) or types != ["TwoLayer"]:
+        elif any(is_host_component(c) for c in self._components) or types != ["TwoLayer"]:
             why = f"this model (components {types}) builds a GraphModel or another kind"
         elif self._mix is None and self._resolve()[3]:
             why = "a schema aggregate in front of the TwoLayer builds a GraphModel"
@@ -666,7 +649,7 @@ class ModelBuilder:
         erf = "Effective Radiative Forcing"
         hint = ("per-member forcing components are available for the model that is one TwoLayer reading the variable as its "
                 "exogenous forcing; for any other graph put a Weighted aggregate (VariableSchema.add_aggregate) in front of the consumer")
-        if any(getattr(c, "is_python", False) for c in self._components) or types != ["TwoLayer"] or aggregates:
+        if any(is_host_component(c) for c in self._components) or types != ["TwoLayer"] or aggregates:
             raise ValueError(f"with_forcing_components: this model has components {types}"
                              f"{' and schema aggregates' if aggregates else ''}; {hint}")
         if variable != erf or variable not in exo_names:
@@ -788,22 +771,9 @@ class ModelBuilder:
 
     def _node_names(self) -> List[str]:
         """One graph-node name per component: its type name, except that all but the LAST registered
-        component of a type are "<type>#<k>".  The reference accepts several components that provide the
-        same variables (builder.rs:531-559: the later one becomes the owner, with an edge from the earlier
-        one); each of them writes index n+1 of the same series every step, so what stands is the write of
-        whichever runs LAST in the execution order (runtime.rs:504-527).  For components of one built-in
-        type -- same variables, same states -- the others' work is never seen: they keep their nodes (the
-        edges shape the breadth-first order) but get no ensemble (_build_graph)."""
-        last = {c.type_name: k for k, c in enumerate(self._components)}
-        seen: Dict[str, int] = {}
-        out = []
-        for k, c in enumerate(self._components):
-            if last[c.type_name] == k:
-                out.append(c.type_name)
-            else:
-                seen[c.type_name] = seen.get(c.type_name, 0) + 1
-                out.append(f"{c.type_name}#{seen[c.type_name]}")
-        return out
+        component of a type are "<type>#<k>" (``graph_plan.component_nodes``, which says why; which of them
+        gets an ensemble is decided by ``graph_plan.survivors``)."""
+        return [node.name for node in graph_plan.component_nodes(self._components)]
 
     def _graph_order(self, aggregates, topological: bool = False) -> List[str]:
         """Execution order of the reference: nodes in registration order (root, components,
@@ -881,7 +851,7 @@ class ModelBuilder:
                     indeg[b] += 1
         own_kernel = {0: False}
         for k, comp in enumerate(self._components, start=1):
-            own_kernel[k] = comp.type_name in OWN_KERNEL_TYPES or bool(getattr(comp, "is_python", False))
+            own_kernel[k] = comp.type_name in OWN_KERNEL_TYPES or is_host_component(comp)
         ready = sorted((n for n, d in indeg.items() if d == 0), key=lambda n: rank[names[n]])
         topo: List[str] = []
         last = False
@@ -898,320 +868,61 @@ class ModelBuilder:
             raise ValueError("the component graph has a cycle")
         return topo
 
-    def _build_graph(self, n_members: int, endogenous, sources, exo_names, aggregates,
-                     execution_order: str = "reference", series_window: Optional[int] = None, output_stride: int = 0,
-                     outputs: Optional[Sequence[str]] = None) -> "GraphModel":
-        T, bounds = len(self._axis), self._axis.bounds()
-        node_names = self._node_names()
-        for c, node in zip(self._components, node_names):
-            if c.type_name not in COMPONENT_KINDS and not getattr(c, "is_python", False):
-                raise NotImplementedError(f"component {c.type_name} has no GPU kernel; supported: " + "; ".join(SUPPORTED))
-            if node != c.type_name and getattr(c, "is_python", False):
-                # host components of one class may declare different variables: they would all be live
-                raise NotImplementedError(f"two Python components of the same type in one graph: {c.type_name}")
-        if execution_order not in ("reference", "topological"):
-            raise ValueError("execution_order must be 'reference' or 'topological'")
-        order = self._graph_order(aggregates, topological=execution_order == "topological")
-        missing = [n for n in node_names + [f"Aggregator:{a}" for a in aggregates] if n not in order]
-        if missing:
-            raise NotImplementedError(f"components not reachable from the graph root: {missing}")
-        # of several components of one type the one that runs last stands (see _node_names): the others
-        # take part in the ordering only, and the survivor goes by the plain type name from here on
-        runs_last: Dict[str, str] = {}
-        for n in order:
-            if not n.startswith("Aggregator:"):
-                runs_last[n.split("#")[0]] = n
-        by_node = dict(zip(node_names, self._components))
-        for at, n in enumerate(order):
-            if n.startswith("Aggregator:") or runs_last[n.split("#")[0]] == n:
-                continue
-            # an overridden component's values ARE seen by whoever reads index n+1 between it and the survivor
-            provided = {name for name, _, kind in by_node[n].definitions if kind in ("Output", "State")}
-            for reader in order[at + 1:order.index(runs_last[n.split("#")[0]])]:
-                if reader.startswith("Aggregator:"):
-                    reads = set(aggregates[reader[len("Aggregator:"):]][2])
-                else:
-                    reads = {name for name, _, kind in by_node[reader].definitions
-                             if kind == "Input" and sources.get((name, reader)) == "UpstreamOutput"}
-                if provided & reads:
-                    raise NotImplementedError(f"{reader} reads {sorted(provided & reads)} of {n} within the step, before "
-                                              f"{runs_last[n.split('#')[0]]} overrides them")
-        order = [n.split("#")[0] if not n.startswith("Aggregator:") else n for n in order
-                 if n.startswith("Aggregator:") or runs_last[n.split("#")[0]] == n]
-        components = [c for c, node in zip(self._components, node_names) if runs_last[c.type_name] == node]
-        for c, node in zip(self._components, node_names):
-            if runs_last[c.type_name] == node and node != c.type_name:
-                sources = dict(sources)
-                for name, _, kind in c.definitions:
-                    if kind in ("Input", "State"):
-                        sources[(name, c.type_name)] = sources[(name, node)]
+    def _fourbox_weights(self) -> List[float]:
+        return self._grid_weights.get(GridType.FourBox, [0.25, 0.25, 0.25, 0.25])
+
+    def _stored_as_scalar(self, name: str) -> bool:
+        return self._schema is not None and self._schema.grid_types.get(name) == GridType.Scalar
+
+    def _plan_graph(self, endogenous, sources, exo_names, aggregates, execution_order: str = "reference",
+                    series_window: Optional[int] = None, output_stride: int = 0,
+                    outputs: Optional[Sequence[str]] = None) -> graph_plan.GraphPlan:
+        """Every decision about a graph of linked ensembles, and every refusal, on the host (``rscm_amd/graph_plan.py``)."""
+        return graph_plan.plan_graph(self, endogenous, sources, exo_names, aggregates, execution_order, series_window, output_stride, outputs)
+
+    def _realise(self, plan: graph_plan.GraphPlan, n_members: int) -> "GraphModel":
+        """The stream and the ensembles of ``plan``, the library calls in the order the plan lists them."""
+        bounds = self._axis.bounds()
         stream = C.c_void_p()
         L.check(L.load().rscm_gpu_stream_create(self._device, C.byref(stream)))
-        ensembles: Dict[str, Ensemble] = {}
-        var_home: Dict[str, Tuple[str, int]] = {}
-        exogenous: Dict[str, np.ndarray] = {}
-        links: List[Tuple[str, int]] = []
-        model = GraphModel(self._axis, order, ensembles, var_home, links, exogenous, sources, stream, self._device, True)
+        model = GraphModel(self._axis, list(plan.order), {}, dict(plan.var_home), [], dict(plan.exogenous), plan.sources, stream,
+                           self._device, plan.feed_forward)
         model._builder = self
-        model._execution_order = execution_order
-        windowed = series_window is not None and series_window < T
-        model._windowed = windowed
-        model._output_stride = int(output_stride) if windowed else 1
-        want_out = None if outputs is None else set(outputs)
+        model._execution_order = plan.execution_order
+        model._windowed, model._output_stride = plan.windowed, plan.output_stride
+        model._reads_unwritten = plan.reads_unwritten
+        model._fourbox, model._fourbox_aggregates = dict(plan.fourbox), dict(plan.fourbox_aggregates)
+        model.param_home, model.base_params = dict(plan.param_home), dict(plan.base_params)
+        for name, host in plan.hosts.items():
+            node = model._host_nodes[name] = _HostNode(host.comp)
+            node.sources, node.device_reads = dict(host.sources), dict(host.device_reads)
+            node.series = {v: np.repeat(s[:, None], n_members, axis=1) for v, s in host.series.items()}
 
-        def make(kind: int, out_names=None) -> Ensemble:
-            """One ensemble of the graph; windowed graphs keep `series_window` rows of every series and
-            every `output_stride`-th row of the requested outputs (all variables if none were named)."""
-            if not windowed:
-                return Ensemble(kind, n_members, bounds, device=self._device)
-            ids = L.KIND_TABLE[kind][0]
-            keep = None
-            if want_out is not None:
-                names = out_names if out_names is not None else [n for n, v in ids.items() if v > 0]
-                fb = L.FOURBOX_VARS.get(kind)
-                keep = [ids[n] for n in names if n in want_out or (fb and fb[0] in want_out and fb[1] <= ids[n] < fb[1] + 4)]
-            return Ensemble(kind, n_members, bounds, device=self._device, window_rows=series_window,
-                            output_stride=output_stride if keep is None or keep else 0, output_vars=keep)
+        def link(spec: graph_plan.LinkSpec) -> None:
+            ens = model.ensembles[spec.consumer]
+            ens.link_input(spec.row, model.ensembles[spec.producer], spec.var, spec.source)
+            model._links.append((spec.consumer, spec.row))
+            if spec.before_producer:
+                L.check(L.load().rscm_ens_set_link_order_check(ens._h, 0))
 
         try:
-            def params_of(values) -> np.ndarray:
-                return np.repeat(np.array(values, dtype=np.float64)[:, None], n_members, axis=1)
-
-            owner_of: Dict[str, str] = {}  # storage ensemble of a Python component's variable -> the component
-            for comp in components:
-                if getattr(comp, "is_python", False):
-                    # a host component: its outputs live in one device series each (an aggregate-kind
-                    # ensemble used as storage, never launched), so that GPU components can link to them
-                    for name in comp.output_names():
-                        sname = f"{comp.type_name}:{name}"
-                        store = Ensemble(L.KIND_AGGREGATE, n_members, bounds, device=self._device)
-                        ensembles[sname] = store
-                        store.set_stream(stream.value)
-                        store.set_params(params_of([0.0] * (1 + L.AG_NINPUTS)))
-                        var_home[name] = (sname, 1)
-                        owner_of[sname] = comp.type_name
-                    model._host_nodes[comp.type_name] = _HostNode(comp)
-                    model._feed_forward = False
-                    continue
-                ens = make(COMPONENT_KINDS[comp.type_name])
-                ensembles[comp.type_name] = ens
+            for spec in plan.nodes:
+                ens = Ensemble(spec.kind, n_members, bounds, device=self._device, window_rows=spec.window_rows,
+                               output_stride=spec.output_stride, output_vars=spec.output_vars)
+                model.ensembles[spec.key] = ens
                 ens.set_stream(stream.value)
-                base = _component_params(comp)
-                ens.set_params(params_of(base))
-                model.base_params[comp.type_name] = np.array(base, dtype=np.float64)
-                for row, pname in enumerate(_component_param_names(comp)):
-                    model.param_home[f"{comp.type_name}.{pname}"] = (comp.type_name, row)
-                    # a bare name addresses the parameter only if no other component has one of that name
-                    model.param_home[pname] = (comp.type_name, row) if pname not in model.param_home else ("", -1)
-                if comp.type_name == "CarbonCycle":
-                    ens.set_step_size(L.COMP_CARBON_CYCLE, comp.step_size)
-                for name, _, kind in comp.definitions:
-                    if kind in ("Output", "State"):
-                        fb = L.FOURBOX_VARS.get(ens.kind)
-                        if fb and name == fb[0]:
-                            # A FourBox variable is four scalar series.  Whoever wants it as a scalar
-                            # -- the schema (write transform: the scalar is what the collection stores,
-                            # runtime.rs:452-470) or a reader (read transform, state/aggregating.rs:
-                            # 162-176) -- gets sum(value * weight) over the boxes, formed by a Weighted
-                            # aggregate ensemble that runs right after the producer, index by index.
-                            tname = f"Transform:{name}"
-                            tr = Ensemble(L.KIND_AGGREGATE, n_members, bounds, device=self._device,
-                                          window_rows=series_window if windowed else None,
-                                          output_stride=output_stride if (want_out is None or name in want_out) else 0)
-                            ensembles[tname] = tr
-                            tr.set_stream(stream.value)
-                            w = self._grid_weights.get(GridType.FourBox, [0.25, 0.25, 0.25, 0.25])
-                            tr.set_params(params_of([L.AG_OPERATIONS["Weighted"]] + list(w) + [0.0] * 4))
-                            for k in range(4):
-                                tr.link_input(k, ens, fb[1] + k, L.SRC_UPSTREAM)
-                                links.append((tname, k))
-                            at = order.index(comp.type_name) + 1
-                            if execution_order == "topological":
-                                # ... or, in the extension's order, after the own-kernel components that follow the
-                                # producer and do not read the variable: the transform then shares their successors' launch
-                                while (at < len(order) and order[at] in OWN_KERNEL_TYPES and order[at] in by_node and not any(
-                                        v == name and kind in ("Input", "State") for v, _, kind in by_node[order[at]].definitions)):
-                                    at += 1
-                            order.insert(at, tname)
-                            var_home[name] = (tname, 1)
-                            stored_scalar = self._schema is not None and self._schema.grid_types.get(name) == GridType.Scalar
-                            model._fourbox[name] = (comp.type_name, fb[1], stored_scalar)
-                            continue
-                        var_home[name] = (comp.type_name, ens.var_ids[name])
-            # An aggregate ensemble takes eight contributors.  More are folded left to right through
-            # partial-sum stages -- stage k adds up to seven further contributors to the partial of stage
-            # k-1 -- which keeps compute_aggregate's order of additions (schema.rs:760-802: one running sum
-            # over the contributors in declaration order, NaN skipped, all-NaN -> NaN), so the result
-            # carries the same bits.  Weighted: the partial enters the next stage with weight 1.  A Mean of
-            # more than eight is that Sum chain, a second chain that counts the non-NaN contributors, and a
-            # last stage that divides the one by the other (sum / n as f64, NaN for n = 0).
-            agg_stages: Dict[str, List[Tuple[str, List[str]]]] = {}
-
-            def add_stage(agg: str, name: str, op: str, rows: List[str], weights: List[float], out_var: str, final: bool) -> None:
-                ens = Ensemble(L.KIND_AGGREGATE, n_members, bounds, device=self._device,
-                               window_rows=series_window if windowed else None,
-                               output_stride=output_stride if (final and (want_out is None or agg in want_out)) else 0)
-                ensembles[name] = ens
-                ens.set_stream(stream.value)
-                w = list(weights) + [0.0] * (L.AG_NINPUTS - len(weights))
-                ens.set_params(params_of([L.AG_OPERATIONS[op]] + w))
-                var_home[out_var] = (name, 1)
-                agg_stages[agg].append((name, rows))
-
-            def chain(agg: str, op: str, carry_op: str, contributors: List[str], wts: List[float], tag: str, final: bool) -> str:
-                """Stages over `contributors`; returns the variable the last one writes."""
-                k, n_stage, out_var = 0, 0, ""
-                while True:
-                    first = n_stage == 0
-                    take = L.AG_NINPUTS if first else L.AG_NINPUTS - 1
-                    last = len(contributors) - k <= take
-                    chunk = contributors[k:k + take]
-                    wchunk = wts[k:k + take] if wts else []
-                    k += len(chunk)
-                    is_final = final and last
-                    name = f"Aggregator:{agg}" if is_final else f"Aggregator:{agg}#{tag}{n_stage}"
-                    rows = chunk if first else [out_var] + chunk
-                    wrow = wchunk if first else [1.0] + wchunk
-                    out_var = agg if is_final else f"{agg}#partial{tag}{n_stage}"
-                    add_stage(agg, name, op if first else carry_op, rows, wrow, out_var, is_final)
-                    n_stage += 1
-                    if last:
-                        return out_var
-
-            def scalar_aggregate(agg: str, op: str, contributors: List[str], weights) -> None:
-                agg_stages[agg] = []
-                if op == "Mean" and len(contributors) > L.AG_NINPUTS:
-                    total = chain(agg, "Sum", "Sum", contributors, [], "", False)
-                    count = chain(agg, "Count", "CountCarry", contributors, [], "count", False)
-                    add_stage(agg, f"Aggregator:{agg}", "Quotient", [total, count], [], agg, True)
-                else:
-                    chain(agg, op, op, contributors, list(weights or []), "", True)
-
-            for agg, (_, op, contributors, weights) in aggregates.items():
-                contributors = list(contributors)
-                grid = aggregates[agg].grid_type
-                if grid == GridType.Hemispheric:
-                    raise NotImplementedError(f"aggregate {agg!r}: no component of this package produces a Hemispheric variable")
-                if grid == GridType.FourBox:
-                    # AggregatorComponent::solve for a FourBox aggregate (schema.rs:902-923): compute_aggregate per region over the
-                    # contributors' values of that region.  A FourBox variable is four scalar series here, so the aggregate is four
-                    # scalar aggregates "<name>|box<k>" (k = 0..3: the reference's region order) over box k of every contributor,
-                    # plus the scalar view of the result -- sum(value * weight) over the boxes, what a component that declares the
-                    # variable as a scalar input reads (read transform, state/aggregating.rs:162-176) -- under the aggregate's name.
-                    stages: List[Tuple[str, List[str]]] = []
-                    homes = []
-                    for b in range(4):
-                        rows_b = []
-                        for c in contributors:
-                            cb = f"{c}|box{b}"
-                            if cb not in var_home:
-                                if c not in model._fourbox:
-                                    raise ValueError(f"Grid type mismatch: contributor {c!r} of the FourBox aggregate {agg!r} is not a FourBox variable")
-                                owner_c, first_c, _ = model._fourbox[c]
-                                var_home[cb] = (owner_c, first_c + b)
-                            rows_b.append(cb)
-                        scalar_aggregate(f"{agg}|box{b}", op, rows_b, weights)
-                        stages += agg_stages.pop(f"{agg}|box{b}")
-                        homes.append(var_home[f"{agg}|box{b}"])
-                    tname = f"Transform:{agg}"
-                    tr = Ensemble(L.KIND_AGGREGATE, n_members, bounds, device=self._device,
-                                  window_rows=series_window if windowed else None,
-                                  output_stride=output_stride if (want_out is None or agg in want_out) else 0)
-                    ensembles[tname] = tr
-                    tr.set_stream(stream.value)
-                    w = self._grid_weights.get(GridType.FourBox, [0.25, 0.25, 0.25, 0.25])
-                    tr.set_params(params_of([L.AG_OPERATIONS["Weighted"]] + list(w) + [0.0] * 4))
-                    var_home[agg] = (tname, 1)
-                    stages.append((tname, [f"{agg}|box{b}" for b in range(4)]))
-                    agg_stages[agg] = stages
-                    model._fourbox_aggregates[agg] = homes
-                    at = order.index(f"Aggregator:{agg}")
-                    order[at:at + 1] = [n for n, _ in stages]
-                    continue
-                scalar_aggregate(agg, op, contributors, weights)
-                stages = agg_stages[agg]
-                if len(stages) > 1:  # the partial stages run right before the aggregate itself
-                    at = order.index(f"Aggregator:{agg}")
-                    order[at:at] = [n for n, _ in stages[:-1]]
-            position = {name: k for k, name in enumerate(order)}
-
-            def wire(owner: str, rows: Sequence[str], read_end: bool) -> None:
-                ens = ensembles[owner]
-                table = np.full((len(ens.input_rows) if ens.input_rows else 1, T), NAN)
-                use_table = False
-                for k, name in enumerate(rows):
-                    if name in var_home:
-                        prod, vid = var_home[name]
-                        src = L.SRC_UPSTREAM if read_end or sources.get((name, owner)) == "UpstreamOutput" else L.SRC_EXOGENOUS
-                        ens.link_input(k, ensembles[prod], vid, src)
-                        links.append((owner, k))
-                        if position[owner_of.get(prod, prod)] > position[owner]:
-                            # lagged feedback, or -- the breadth-first order is not a topological one -- a
-                            # component that runs before the producer of what it reads at n+1 and, like
-                            # in the reference, finds NaN there
-                            model._feed_forward = False
-                            model._reads_unwritten = model._reads_unwritten or src == L.SRC_UPSTREAM
-                            L.check(L.load().rscm_ens_set_link_order_check(ens._h, 0))
-                    else:
-                        if name in endogenous:
-                            raise NotImplementedError(f"{name!r} is a FourBox variable: it cannot feed the scalar input of {owner}")
-                        vals = self._exogenous_on_axis(name, exo_names + list(rows))
-                        use_table = True
-                        if vals is not None:
-                            table[k] = vals
-                        exogenous[name] = table[k].copy()  # never supplied: a NaN series (builder.rs:772-780)
-                if use_table:
-                    ens.set_forcing(table if ens.input_rows else table[0])
-
-            model.param_home = {k: v for k, v in model.param_home.items() if v[1] >= 0}
-            for comp in components:
-                if getattr(comp, "is_python", False):
-                    node = model._host_nodes[comp.type_name]
-                    for name in comp.input_names():
-                        node.sources[name] = sources.get((name, comp.type_name), "Exogenous")
-                        node.series[name] = np.full((T, n_members), NAN)
-                        if name in var_home:
-                            node.device_reads[name] = var_home[name]
-                            if name in self._initial:
-                                node.series[name][0] = self._initial[name]
-                        else:
-                            if name in endogenous:
-                                raise NotImplementedError(f"{name!r} is a FourBox variable: it cannot feed the scalar input of {comp.type_name}")
-                            vals = self._exogenous_on_axis(name, exo_names + [name])
-                            if vals is not None:
-                                node.series[name][:] = vals[:, None]
-                            exogenous[name] = node.series[name][:, 0].copy()
-                    continue
-                ens = ensembles[comp.type_name]
-                rows = ens.input_rows or [n for n, v in ens.var_ids.items() if v == 0]
-                wire(comp.type_name, list(rows), ens.kind == L.KIND_UDEB)
-            for agg in aggregates:
-                for name, rows in agg_stages[agg]:
-                    wire(name, rows, True)
-            for name, (owner, vid) in var_home.items():
-                if name in self._initial:
-                    ensembles[owner].set_initial(vid, self._initial[name])
-            for agg, homes in model._fourbox_aggregates.items():
-                if agg in self._initial:  # one scalar for the four regions (builder.rs:797-804); the scalar view was set above
-                    w = self._grid_weights.get(GridType.FourBox, [0.25, 0.25, 0.25, 0.25])
-                    x0 = self._initial[agg]
-                    for owner_b, vid_b in homes:
-                        ensembles[owner_b].set_initial(vid_b, x0)
-                    s0 = 0.0
-                    for wk in w:
-                        s0 = s0 + x0 * wk
-                    ensembles[f"Transform:{agg}"].set_initial(1, s0)
-            for owner, ens in list(ensembles.items()):
-                fb = L.FOURBOX_VARS.get(ens.kind)
-                if fb and fb[0] in self._initial:  # a FourBox state initialised with one scalar (builder.rs:797-804)
-                    w = self._grid_weights.get(GridType.FourBox, [0.25, 0.25, 0.25, 0.25])
-                    x0 = self._initial[fb[0]]
-                    for v in range(fb[1], fb[1] + 4):
-                        ens.set_initial(v, x0)
-                    s0 = 0.0
-                    for wk in w:  # the scalar view of index 0, summed like aggregate_global
-                        s0 = s0 + x0 * wk
-                    ensembles[f"Transform:{fb[0]}"].set_initial(1, s0)
+                ens.set_params(np.repeat(np.array(spec.params, dtype=np.float64)[:, None], n_members, axis=1))
+                if spec.step_size is not None:
+                    ens.set_step_size(*spec.step_size)
+                for made_with_it in spec.links:
+                    link(made_with_it)
+            for consumer in plan.consumers:
+                for spec in consumer.links:
+                    link(spec)
+                if consumer.table is not None:
+                    model.ensembles[consumer.key].set_forcing(consumer.table)
+            for key, vid, value in plan.initial:
+                model.ensembles[key].set_initial(vid, value)
         except Exception:
             model.close()
             raise
@@ -1238,59 +949,16 @@ class ModelBuilder:
             if series_window is not None:
                 raise ValueError("with_forcing_components: a mix ensemble has no windowed storage (series_window)")
             return self._build_mix(n_members, store_series)
-        if series_window is not None:
-            if any(getattr(c, "is_python", False) for c in self._components):
-                raise NotImplementedError("Python components read whole host series: no series_window for such graphs")
-            return self._define_diagnostics(self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order,
-                                                              series_window, output_stride, outputs))
-        if any(getattr(c, "is_python", False) for c in self._components):
-            return self._define_diagnostics(self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order))
-        types = [c.type_name for c in self._components]
-        erf = "Effective Radiative Forcing"
-        if types == ["TwoLayer"] and not aggregates:
-            kind = L.KIND_TWO_LAYER
-            forcing = self._exogenous_on_axis(erf, exo_names)
-            if forcing is None:  # builder.rs:772-780: NaN series; run() then yields NaN
-                forcing = np.full(len(self._axis), NAN)
-            src = L.SRC_EXOGENOUS
-            params = [self._components[0].parameters[k] for k in TL_PARAM_ORDER]
-            h = {L.COMP_TWO_LAYER: 0.1}
-        elif (types == ["CarbonCycle", "CO2ERF", "TwoLayer"] and list(aggregates) == [erf]
-              and aggregates[erf][1] == "Sum"
-              and aggregates[erf][2] == ["Effective Radiative Forcing|CO2"]
-              # the fused coupled kernel carries ONE conc_pi row; two different pre-industrial
-              # concentrations run as the same graph of linked ensembles (one launch as well: all light)
-              and self._components[0].parameters["conc_pi"] == self._components[1].parameters["conc_pi"]):
-            kind = L.KIND_COUPLED
-            cc, ce, tl = self._components
-            assert sources[("Surface Temperature", "CarbonCycle")] == "Exogenous"
-            assert sources[(erf, "TwoLayer")] == "UpstreamOutput"
-            forcing = self._exogenous_on_axis("Emissions|CO2|Anthropogenic", exo_names)
-            if forcing is None:
-                forcing = np.full(len(self._axis), NAN)
-            src = L.SRC_EXOGENOUS
-            params = ([tl.parameters[k] for k in TL_PARAM_ORDER] +
-                      [cc.parameters["tau"], cc.parameters["conc_pi"],
-                       cc.parameters["alpha_temperature"], ce.parameters["erf_2xco2"]])
-            h = {L.COMP_TWO_LAYER: 0.1, L.COMP_CARBON_CYCLE: cc.step_size}
-        elif types == ["ClimateUDEB"] and not aggregates:
-            kind = L.KIND_UDEB
-            forcing = self._exogenous_on_axis(erf, exo_names)
-            if forcing is None:
-                forcing = np.full(len(self._axis), NAN)
-            src = L.SRC_EXOGENOUS
-            params = self._components[0].param_vector()
-            h = {}
-        elif len(types) == 1 and types[0] in STATELESS_KINDS and not aggregates:
-            kind = STATELESS_KINDS[types[0]]
-            rows = [self._exogenous_on_axis(name, exo_names) for name in L.KIND_TABLE[kind][2]]
-            forcing = np.stack([np.full(len(self._axis), NAN) if r is None else r for r in rows])
-            src = L.SRC_EXOGENOUS
-            params = self._components[0].param_vector()
-            h = {}
-        else:
-            # any other graph of built-in components: one ensemble per component, linked on the device
-            return self._define_diagnostics(self._build_graph(n_members, endogenous, sources, exo_names, aggregates, execution_order))
+        hosted = any(is_host_component(c) for c in self._components)
+        if series_window is not None and hosted:
+            raise NotImplementedError("Python components read whole host series: no series_window for such graphs")
+        fused = None if series_window is not None or hosted else self._fused_shape(sources, exo_names, aggregates)
+        if fused is None:
+            # any other graph: one ensemble per component, linked on the device (output_stride and outputs belong to series_window)
+            window = (series_window, output_stride, outputs) if series_window is not None else (None, 0, None)
+            plan = self._plan_graph(endogenous, sources, exo_names, aggregates, execution_order, *window)
+            return self._define_diagnostics(self._realise(plan, n_members))
+        kind, forcing, params, step_sizes = fused
         if not store_series and kind != L.KIND_TWO_LAYER:
             store_series = True  # likelihood-only handles exist for the two-layer kind
         noise_params = self._noise is not None and self._noise_params   # (_check_forcing_noise: this is the two-layer ensemble)
@@ -1298,10 +966,10 @@ class ModelBuilder:
             _, params = self._with_noise_params((), params)
         ens = Ensemble(kind, n_members, self._axis.bounds(), device=self._device,
                        store_series=store_series, noise_params=noise_params)
-        for comp_id, step in h.items():
+        for comp_id, step in step_sizes.items():
             ens.set_step_size(comp_id, step)
         ens.set_params(np.repeat(np.array(params, dtype=np.float64)[:, None], n_members, axis=1))
-        ens.set_forcing(forcing, None, src)
+        ens.set_forcing(forcing, None, L.SRC_EXOGENOUS)
         self._set_noise(ens)
         for name, vid in ens.var_ids.items():
             if vid > 0 and name in self._initial:
@@ -1309,20 +977,46 @@ class ModelBuilder:
             elif vid > 0 and "|" in name and name.split("|")[0] in self._initial and kind == L.KIND_UDEB:
                 # a FourBox state initialised with one scalar sets all four regions (builder.rs:797-804)
                 ens.set_initial(vid, self._initial[name.split("|")[0]])
-        param_order = {L.KIND_TWO_LAYER: TL_PARAM_ORDER, L.KIND_COUPLED: CP_PARAM_ORDER,
-                       L.KIND_UDEB: L.UD_PARAM_NAMES, L.KIND_GHG_FORCING: L.GH_PARAM_NAMES,
-                       L.KIND_OZONE_FORCING: L.OZ_PARAM_NAMES, L.KIND_AEROSOL_DIRECT: L.AD_PARAM_NAMES,
-                       L.KIND_AEROSOL_INDIRECT: L.AI_PARAM_NAMES, L.KIND_CH4_CHEMISTRY: L.CH4_PARAM_NAMES,
-                       L.KIND_N2O_CHEMISTRY: L.N2O_PARAM_NAMES, L.KIND_CO2_BUDGET: L.CB_PARAM_NAMES,
-                       L.KIND_TERRESTRIAL_CARBON: L.TC_PARAM_NAMES, L.KIND_OCEAN_CARBON: L.OC_PARAM_NAMES,
-                       L.KIND_HALOCARBON: L.HC_PARAM_NAMES, L.KIND_FOURBOX_OHU: L.FB_PARAM_NAMES,
-                       L.KIND_OSPP: L.SP_PARAM_NAMES}[kind]
-        if noise_params:
-            param_order = tuple(param_order) + self.NOISE_PARAM_NAMES
+        param_order = tuple(L.PARAM_NAMES[kind]) + (self.NOISE_PARAM_NAMES if noise_params else ())
         model = Model(ens, self._axis, sources, endogenous, forcing, dict(self._initial), param_order,
                       np.array(params, dtype=np.float64))
         model._builder = self
         return self._define_diagnostics(model)
+
+    def _exogenous_or_nan(self, name: str, exo_names: List[str]) -> np.ndarray:
+        """The exogenous series on the axis; never supplied: a NaN series (builder.rs:772-780), and run() then yields NaN."""
+        vals = self._exogenous_on_axis(name, exo_names)
+        return np.full(len(self._axis), NAN) if vals is None else vals
+
+    def _fused_shape(self, sources, exo_names, aggregates):
+        """``(kind, forcing, parameters, step sizes)`` of the single ensemble where the model is one of the four shapes a fused
+        kernel covers; None for any other graph."""
+        types = [c.type_name for c in self._components]
+        erf = "Effective Radiative Forcing"
+        if types == ["TwoLayer"] and not aggregates:
+            params = [self._components[0].parameters[k] for k in TL_PARAM_ORDER]
+            return L.KIND_TWO_LAYER, self._exogenous_or_nan(erf, exo_names), params, {L.COMP_TWO_LAYER: 0.1}
+        if (types == ["CarbonCycle", "CO2ERF", "TwoLayer"] and list(aggregates) == [erf]
+                and aggregates[erf][1] == "Sum"
+                and aggregates[erf][2] == ["Effective Radiative Forcing|CO2"]
+                # the fused coupled kernel carries ONE conc_pi row; two different pre-industrial
+                # concentrations run as the same graph of linked ensembles (one launch as well: all light)
+                and self._components[0].parameters["conc_pi"] == self._components[1].parameters["conc_pi"]):
+            cc, ce, tl = self._components
+            assert sources[("Surface Temperature", "CarbonCycle")] == "Exogenous"
+            assert sources[(erf, "TwoLayer")] == "UpstreamOutput"
+            params = ([tl.parameters[k] for k in TL_PARAM_ORDER] +
+                      [cc.parameters["tau"], cc.parameters["conc_pi"],
+                       cc.parameters["alpha_temperature"], ce.parameters["erf_2xco2"]])
+            return (L.KIND_COUPLED, self._exogenous_or_nan("Emissions|CO2|Anthropogenic", exo_names), params,
+                    {L.COMP_TWO_LAYER: 0.1, L.COMP_CARBON_CYCLE: cc.step_size})
+        if types == ["ClimateUDEB"] and not aggregates:
+            return L.KIND_UDEB, self._exogenous_or_nan(erf, exo_names), self._components[0].param_vector(), {}
+        if len(types) == 1 and types[0] in STATELESS_KINDS and not aggregates:
+            kind = STATELESS_KINDS[types[0]]
+            forcing = np.stack([self._exogenous_or_nan(name, exo_names) for name in L.KIND_TABLE[kind][2]])
+            return kind, forcing, self._components[0].param_vector(), {}
+        return None
 
 
 def save_checkpoint(path, ck: Dict[str, object]) -> None:
@@ -1375,39 +1069,8 @@ def load_checkpoint(path) -> Dict[str, object]:
     return out
 
 
-# components whose step is a kernel of their own (csrc/kinds.hpp, `fusable`); the others share fused launches
-OWN_KERNEL_TYPES = ("ClimateUDEB", "OceanCarbon", "HalocarbonChemistry")
-
-# type name -> ensemble kind, for graphs assembled from linked ensembles
-COMPONENT_KINDS = {"TwoLayer": L.KIND_TWO_LAYER, "ClimateUDEB": L.KIND_UDEB, "CarbonCycle": L.KIND_CARBON_CYCLE,
-                   "CO2ERF": L.KIND_CO2_ERF, **STATELESS_KINDS}
-
-
-def _component_param_names(comp) -> Tuple[str, ...]:
-    if comp.type_name == "TwoLayer":
-        return tuple(TL_PARAM_ORDER)
-    if comp.type_name == "CarbonCycle":
-        return tuple(L.CC_PARAM_NAMES)
-    if comp.type_name == "CO2ERF":
-        return tuple(L.CE_PARAM_NAMES)
-    kind = COMPONENT_KINDS[comp.type_name]
-    table = {L.KIND_UDEB: L.UD_PARAM_NAMES, L.KIND_GHG_FORCING: L.GH_PARAM_NAMES, L.KIND_OZONE_FORCING: L.OZ_PARAM_NAMES,
-             L.KIND_AEROSOL_DIRECT: L.AD_PARAM_NAMES, L.KIND_AEROSOL_INDIRECT: L.AI_PARAM_NAMES,
-             L.KIND_CH4_CHEMISTRY: L.CH4_PARAM_NAMES, L.KIND_N2O_CHEMISTRY: L.N2O_PARAM_NAMES,
-             L.KIND_CO2_BUDGET: L.CB_PARAM_NAMES, L.KIND_TERRESTRIAL_CARBON: L.TC_PARAM_NAMES,
-             L.KIND_OCEAN_CARBON: L.OC_PARAM_NAMES, L.KIND_HALOCARBON: L.HC_PARAM_NAMES,
-             L.KIND_FOURBOX_OHU: L.FB_PARAM_NAMES, L.KIND_OSPP: L.SP_PARAM_NAMES}
-    return tuple(table[kind])
-
-
-def _component_params(comp) -> List[float]:
-    if comp.type_name == "TwoLayer":
-        return [comp.parameters[k] for k in TL_PARAM_ORDER]
-    if comp.type_name == "CarbonCycle":
-        return [comp.parameters[k] for k in L.CC_PARAM_NAMES]
-    if comp.type_name == "CO2ERF":
-        return [comp.parameters[k] for k in L.CE_PARAM_NAMES]
-    return list(comp.param_vector())
+_component_param_names = graph_plan.component_param_names
+_component_params = graph_plan.component_params
 
 
 class _HostNode:
