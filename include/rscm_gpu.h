@@ -112,8 +112,10 @@ extern "C" {
  *      rscm_ens_member_cross_spectrum, rscm_gpu_spectrum_sines, RSCM_XSPEC_MAX_BANDS
  *  22  energy-budget diagnostics of a two-layer handle -- the member's forcing, radiative response, deep-ocean heat uptake and
  *      top-of-atmosphere imbalance as diagnostic variables: rscm_ens_define_energy_budget, rscm_ens_diagnostic_quantity,
- *      RSCM_BUDGET_FORCING, RSCM_BUDGET_RESPONSE, RSCM_BUDGET_DEEP_UPTAKE, RSCM_BUDGET_IMBALANCE */
-#define RSCM_GPU_ABI_MINOR 22
+ *      RSCM_BUDGET_FORCING, RSCM_BUDGET_RESPONSE, RSCM_BUDGET_DEEP_UPTAKE, RSCM_BUDGET_IMBALANCE
+ *  23  exact weighted means and covariances of per-member vectors across members, in a fixed-point integer accumulator that shards
+ *      add up: rscm_ens_moment_sums, rscm_gpu_moment_finish, rscm_ens_moments, RSCM_MOMENT_MAX_VECTORS, RSCM_MOMENT_BLOCK */
+#define RSCM_GPU_ABI_MINOR 23
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1088,6 +1090,55 @@ RSCM_API int rscm_ens_clear_member_groups(rscm_ens* h);
  * (-1) are left out.  No groups set, or weighted without weights: RSCM_ERR_STATE. */
 RSCM_API int rscm_ens_exceedance_grouped(rscm_ens* h, const double* vec_dev, int32_t n_thr, const double* thr, int32_t weighted,
                                          int64_t* hits, int64_t* total);
+
+/* ---- exact weighted means and covariances across members (ABI minor 23) --------------------------- */
+/* The weighted mean vector and covariance matrix of K per-member vectors over the members of a handle (of each member group, if
+ * asked), accumulated in integers: exact, independent of the order of summation, and summable across handles and ranks with a plain
+ * int64 SUM.  This is the one definition; the kernel (moments.hip), the finishing step (moments_finish.hpp) and the tests'
+ * restatement in Python integers and fractions apply it.
+ *   Inputs: vec_dev[K] (a host array), 1 <= K <= RSCM_MOMENT_MAX_VECTORS, of device addresses of N doubles on the handle's device,
+ *   as for rscm_ens_quantile_vectors.  flags: RSCM_SELECT_WEIGHTED and RSCM_SELECT_GROUPED; RSCM_SELECT_ANOMALY and unknown flags
+ *   are RSCM_ERR_INVALID; weighted without weights, or grouped without groups, RSCM_ERR_STATE.  G = n_groups when grouped, else 1.
+ *   Which members count: member i is counted in group g when group[i] == g (every member when not grouped) and all K of its values
+ *   are finite -- listwise, so that the matrix belongs to one population.  w_i is its member weight, 1 when not weighted (weights
+ *   that are set are ignored without the flag).  n_g is the number of counted members, W_g the sum of their w_i.
+ *   Order 1: S_a = sum_i w_i x_ia as an exact integer; mean_a = RN(S_a / W_g), the exact quotient rounded once, ties to even.
+ *   Order 2, about a centre c[G][K] of host doubles (the means above, or any finite doubles), for a <= b:
+ *     d_ia = x_ia - c_ga (one IEEE subtraction),  p_iab = d_ia * d_ib (one IEEE multiplication, no FMA),
+ *     C_ab = sum_i w_i p_iab, exact;  cov_ab = RN(C_ab / W_g).  The weights are frequencies and the divisor is W: a caller who
+ *   wants W - 1 has W.  A non-finite p_iab (a difference or a product of finite values that overflows) is not added: every
+ *   counted member with such a term, whatever its weight, adds one to the count of its sum's block, and a block with a non-zero
+ *   count finishes as NaN.  If any c_ga of a group is not finite, every term of every block of that group is counted so (the
+ *   limbs stay zero, n_g and W_g stay in place).  W == 0 finishes as NaN, a zero sum as +0.0.
+ *   The accumulator: one sum is a block of RSCM_MOMENT_BLOCK = 69 int64: 68 signed limbs, limb k in units of 2^(32 k - 1088), then
+ *   the count of non-finite terms.  A term is taken from the raw fields of the double (sign, E, fraction): the mantissa is the
+ *   fraction if E == 0, else 2^52 + fraction, and its lowest bit sits at accumulator bit max(E, 1) + 13.  w * mantissa (at most
+ *   106 bits) is cut into 32-bit digits at limb boundaries and each digit is added, with the term's sign, into its limb; carries
+ *   are deferred.  The 68 limbs cover every finite double times a total weight of 2^63: 2^53 per handle (the bound the member
+ *   weights already have) over 2^10 handles.  An int64 limb takes 2^31 digits before it can wrap: the number of counted members
+ *   over everything that is summed together must stay below 2^31, and the finishing step refuses more.
+ *   Raw limbs of two accumulations of the same terms need not be equal (deferred carries differ with the order); their canonical
+ *   value sum_k limb_k 2^(32 k) is.  That is what lets blocks of shards add up limb by limb.
+ *   Result of rscm_ens_moment_sums: out[G][2 + B * 69] int64, per group n, W, then B blocks: order 1 B = K, block a = S_a; order 2
+ *   B = K (K + 1) / 2 in the order (0,0), (0,1), ..., (0,K-1), (1,1), ....  out is host memory, or (on_device != 0) device memory on
+ *   the handle's device, e.g. the buffer of a collective.  order outside {1, 2}, order 2 without center, a NULL out or vec_dev, K out
+ *   of range, a vector that is not device memory of N doubles on the handle's device, N >= 2^31: RSCM_ERR_INVALID.  center is read
+ *   for order 2 only. */
+#define RSCM_MOMENT_MAX_VECTORS 8
+#define RSCM_MOMENT_BLOCK 69
+RSCM_API int rscm_ens_moment_sums(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t flags, int32_t order,
+                                  const double* center, int64_t* out, int32_t on_device);
+/* The finishing step; it needs no device and no handle, so that a host can finish after a reduction of its own:
+ * out[b] = RN(canonical(blocks[b]) * 2^-1088 / divisor[b]) for b < n_blocks over blocks[n_blocks][69].  The carries are normalised,
+ * the exact quotient is formed and rounded once: ties to even, results in the subnormal range exact on their grid, a result
+ * beyond the largest finite double infinite, a non-zero sum that rounds to zero keeps its sign, a zero sum is +0.0.  A block with
+ * a non-zero count, or divisor[b] == 0: NaN.  n_terms is the number of counted members over everything that was summed into the
+ * blocks: n_terms < 0 or >= 2^31, a negative divisor, a negative n_blocks or a NULL argument with n_blocks > 0: RSCM_ERR_INVALID. */
+RSCM_API int rscm_gpu_moment_finish(const int64_t* blocks, int32_t n_blocks, const int64_t* divisor, int64_t n_terms, double* out);
+/* The two passes and the finish on one handle: mean[G][K], cov[G][K][K] (symmetric, both triangles written), n[G], weight[G]; the
+ * centre of order 2 is mean.  A group with W == 0: NaN in mean and cov.  n and weight may be NULL.  Errors as rscm_ens_moment_sums. */
+RSCM_API int rscm_ens_moments(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t flags, double* mean, double* cov,
+                              int64_t* n, int64_t* weight);
 
 /* ---- per-member variability statistics and a likelihood over per-member vectors (ABI minor 16) ---- */
 /* How variable is each member's series of var_id over a period: its mean, its trend, the variance and standard deviation about the

@@ -35,6 +35,8 @@ NOISE_STREAM_TAG = 0x4E5A   # RSCM_NOISE_STREAM_TAG: the Philox stream of the fo
 SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
 SELECT_ANOMALY = 2
 SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
+MOMENT_MAX_VECTORS = 8   # rscm_ens_moment_sums / rscm_ens_moments
+MOMENT_BLOCK = 69        # int64 per sum: 68 limbs in units of 2^(32 k - 1088), then the count of non-finite terms
 DIAG_MAX_TERMS, DIAG_MAX = 4, 4    # RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX: terms per diagnostic variable, diagnostics per handle
 # RSCM_BUDGET_*: the energy-budget quantities of rscm_ens_define_energy_budget, and the names the front end gives them
 BUDGET_FORCING, BUDGET_RESPONSE, BUDGET_DEEP_UPTAKE, BUDGET_IMBALANCE = 1, 2, 3, 4
@@ -391,6 +393,9 @@ SIGNATURES = {
     "rscm_ens_member_groups_devptr": (C.c_int, [_h, C.POINTER(C.c_void_p), _ip]),
     "rscm_ens_clear_member_groups": (C.c_int, [_h]),
     "rscm_ens_exceedance_grouped": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rscm_ens_moment_sums": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, C.c_int32, _dp, C.POINTER(C.c_int64), C.c_int32]),
+    "rscm_gpu_moment_finish": (C.c_int, [C.POINTER(C.c_int64), C.c_int32, C.POINTER(C.c_int64), C.c_int64, _dp]),
+    "rscm_ens_moments": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, _dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "rscm_ens_weights_stats": (C.c_int, [_h, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     "rscm_ens_resample": (C.c_int, [_h, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_void_p)]),

@@ -1323,6 +1323,13 @@ class GraphModel:
         kw = {"grouped": True} if grouped else {}
         return vs[0].owner.quantile_vectors(vs, q, weighted=weighted, **kw)
 
+    def moments(self, vectors, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """``Ensemble.moments`` (exact weighted means, covariances and correlations across members) on the ensemble that owns the
+        vectors; the vectors of several ensembles of the graph go together, as for ``quantile_vectors``."""
+        vs = list(vectors)
+        kw = {"grouped": True} if grouped else {}
+        return vs[0].owner.moments(vs, weighted=weighted, **kw)
+
     def exceedance(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """``Ensemble.exceedance`` on the ensemble that owns the vector."""
         kw = {"grouped": True} if grouped else {}

@@ -927,6 +927,17 @@ hipError_t launch_exceedance(const double* d_v, const int64_t* d_w, int64_t N, i
 // the same per group: d_acc[g][n_thr + 1] (hits, then the total) over the members with d_group[i] == g; the caller zeroes it
 hipError_t launch_exceedance_grouped(const double* d_v, const int64_t* d_w, const int32_t* d_group, int32_t n_groups, int64_t N,
                                      int32_t n_thr, const Thresholds& thr, unsigned long long* d_acc, hipStream_t s);
+// the exact moment sums across members (moments.hip; the definition is stated in include/rscm_gpu.h, rscm_ens_moment_sums) of the
+// vectors d_vec[n_vec] (a device array of device addresses of N doubles): d_out[G][2 + n_sums * 69] += {n, W, the blocks} with
+// G = n_groups when d_group is non-null, else 1, and n_sums = n_vec (order 1) or n_vec (n_vec + 1) / 2 (order 2, about
+// d_centre[G][n_vec]); d_w non-null: the member weights.  The caller zeroes d_out; d_mask[(N + 63) / 64] is scratch.  N < 2^31.
+// The grid is capped at kMomBlocks blocks in x, which take kMomentMembersPerPass members per pass of their grid-stride loop.
+constexpr int kMaxMomentVectors = 8;
+constexpr int kMomBlocks = 1024;
+constexpr int64_t kMomentMembersPerPass = 262144;
+hipError_t launch_moment_sums(const double* const* d_vec, int32_t n_vec, const int64_t* d_w, const int32_t* d_group, int32_t n_groups,
+                              int32_t order, const double* d_centre, int64_t N, unsigned long long* d_mask, unsigned long long* d_out,
+                              hipStream_t s);
 // per-member variability statistics (variability.hip) over rows d_rows[n_rows][N]: d_out[5][N] = mean, slope, variance, sd, r1 of
 // the working series (mode kVarMean / kVarLinear: the rows, kVarDifference: their first differences; the definition is stated in
 // include/rscm_gpu.h, rscm_ens_member_variability); stt = n (n^2 - 1) / 12 of the working series' length n, formed by the caller

@@ -16,6 +16,7 @@ in the CPU tests), are:
 * ``ShardedEnsemble.constrain``: one all-reduce (MAX) of the local log-likelihood maxima;
 * ``quantile_vectors_global``: the same histogram all-reduces over per-member vectors (indicators, parameter rows);
 * ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums;
+* ``moments_global``: two all-reduces (int64 SUM) of the fixed-point moment sums, 69 int64 per mean and covariance entry;
 * ``weights_stats_global``: one all-reduce (int64 SUM) of the exact weight sums and one (MAX) of the largest weight;
 * ``resample_global``: one all-gather of each rank's exact summed weight (8 B per rank); no member crosses a rank.
 
@@ -224,6 +225,35 @@ def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool =
     return exceedance_result(acc[:-1], int(acc[-1]))
 
 
+def moments_global(ensemble, vectors, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.moments`` of the WHOLE sharded ensemble on every rank: each rank forms the order-1 sums of its shard of each
+    vector (``Ensemble.moment_sums``), the int64 arrays are SUM-reduced and every rank finishes the same means; then the order-2
+    sums about those means, reduced and finished the same way.  The sums are integers with deferred carries, exact and
+    independent of order, so the result has the same bits at any number of ranks and equals ``Ensemble.moments`` of the gathered
+    ensemble.  Two collectives and no data-path copy (with ``gloo`` the two small arrays pass through the host).  ``grouped``:
+    the same ``n_groups`` on every rank.  Fewer than 2^31 members may count over all ranks."""
+    from .ensemble import moment_means, moments_result
+    vs = list(vectors)
+    K = len(vs)
+    kw = {"grouped": True} if grouped else {}
+
+    def reduced(a):
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if not is_distributed():
+            return a
+        import torch
+        d = _dist()
+        t = torch.from_numpy(a.copy()).to(_device_for_backend())
+        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+        return t.cpu().numpy()
+
+    sums1 = reduced(ensemble.moment_sums(vs, 1, weighted=weighted, **kw))
+    G = sums1.shape[0]
+    mean = moment_means(sums1, K, G)
+    sums2 = reduced(ensemble.moment_sums(vs, 2, center=mean, weighted=weighted, **kw))
+    return moments_result(sums1, sums2, K, G, grouped=grouped)
+
+
 def weights_stats_global(ensemble, group=None) -> Dict[str, object]:
     """``Ensemble.weights_stats`` of the WHOLE sharded ensemble on every rank: the ranks' exact integers are SUM-reduced (``w_max``:
     MAX) -- sum w^2 as four 32-bit limbs, each of which sums without wrapping over any number of ranks an int64 can count -- and
@@ -351,6 +381,10 @@ class ShardedEnsemble:
     def quantile_vectors_global(self, vectors, q, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Quantiles of per-member vectors of the global ensemble (``quantile_vectors_global``)."""
         return quantile_vectors_global(self.ensemble, vectors, q, weighted=weighted, grouped=grouped)
+
+    def moments_global(self, vectors, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Exact means, covariances and correlations of per-member vectors over the global ensemble (``moments_global``)."""
+        return moments_global(self.ensemble, vectors, weighted=weighted, grouped=grouped)
 
     def exceedance_global(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""

@@ -970,6 +970,48 @@ class Ensemble:
                                               hits.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total)))
         return exceedance_result(hits, total.value)
 
+    def moment_sums(self, vectors, order: int, center=None, weighted: bool = False, grouped: bool = False) -> np.ndarray:
+        """The exact integer sums behind ``moments`` (rscm_ens_moment_sums) of up to eight ``[N]`` float64 ``DeviceVector``s:
+        int64 ``[G][2 + B * 69]``, per group the count n, the weight W and B blocks of 68 limbs and a count of non-finite terms --
+        ``order`` 1: B = K, the sums of w x; 2: B = K (K + 1) / 2, the sums of w (x_a - c_a)(x_b - c_b) about ``center`` ``[G][K]``
+        for a <= b.  G is 1 without ``grouped``.  The arrays of shards add up element by element; ``moments_result`` finishes them."""
+        arr, n_vec = self._vectors(vectors)
+        if not 1 <= n_vec <= L.MOMENT_MAX_VECTORS:
+            raise ValueError(f"moments: 1 to {L.MOMENT_MAX_VECTORS} vectors, got {n_vec}")
+        if order not in (1, 2):
+            raise ValueError("moments: order must be 1 or 2")
+        G = self._n_groups(grouped)
+        c = None
+        if order == 2:
+            if center is None:
+                raise ValueError("moments: order 2 needs a center")
+            c = np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))
+            if c.size != G * n_vec:
+                raise ValueError(f"center: need {G} x {n_vec} values, got {c.size}")
+        out = np.zeros((G, 2 + moment_blocks(n_vec, order) * L.MOMENT_BLOCK), dtype=np.int64)
+        L.check(self._lib.rscm_ens_moment_sums(self._h, n_vec, arr, select_flags(weighted, False, grouped), int(order),
+                                               None if c is None else L.dptr(c), out.ctypes.data_as(C.POINTER(C.c_int64)), 0))
+        return out
+
+    def moments(self, vectors, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Exact weighted mean vector and covariance matrix of up to eight ``[N]`` float64 ``DeviceVector``s over the members
+        (indicators, ``params_vector`` rows, a log-likelihood): ``{"count", "weight", "mean": [K], "cov": [K][K], "sd": [K],
+        "corr": [K][K]}``, with ``grouped`` per member group, the group dimension leading.  A member counts when all K of its
+        values are finite; ``weighted`` takes the member weights as frequencies (the divisor is their sum W).  Every mean and
+        covariance is the exact sum, accumulated in integers on the device, divided by W and rounded once, so the result has
+        the same bits whatever the order of the members, and ``rscm_amd.distributed.moments_global`` returns them for a sharded
+        ensemble.  W == 0: NaN."""
+        arr, K = self._vectors(vectors)
+        if not 1 <= K <= L.MOMENT_MAX_VECTORS:
+            raise ValueError(f"moments: 1 to {L.MOMENT_MAX_VECTORS} vectors, got {K}")
+        G = self._n_groups(grouped)
+        mean, cov = np.empty((G, K)), np.empty((G, K, K))
+        n, w = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        L.check(self._lib.rscm_ens_moments(self._h, K, arr, select_flags(weighted, False, grouped), L.dptr(mean), L.dptr(cov),
+                                           n.ctypes.data_as(i64), w.ctypes.data_as(i64)))
+        return moments_dict(n, w, mean, cov, grouped)
+
     def params_vector(self, row: int) -> DeviceVector:
         """Parameter row ``row`` of the ``[P][N]`` block as a ``DeviceVector`` (rscm_ens_params_devptr), e.g. for
         ``quantile_vectors``.  Once handed out, the block is read per member for the handle's life."""
@@ -1152,6 +1194,62 @@ def exceedance_grouped_result(hits, total) -> Dict[str, object]:
     with np.errstate(divide="ignore", invalid="ignore"):
         prob = np.where(total[:, None] != 0, hits.astype(np.float64) / total.astype(np.float64)[:, None], np.nan)
     return {"hits": hits, "total": total, "probability": prob}
+
+
+def moment_blocks(K: int, order: int) -> int:
+    """Blocks per group of ``Ensemble.moment_sums``: K sums of order 1, the K (K + 1) / 2 pairs a <= b of order 2."""
+    return K if order == 1 else K * (K + 1) // 2
+
+
+def moment_finish(blocks, divisor, n_terms: int) -> np.ndarray:
+    """rscm_gpu_moment_finish: ``blocks[B][69]`` int64 (68 limbs in units of 2^(32 k - 1088) and a count of non-finite terms) over
+    ``divisor`` (one int64, or one per block) as B doubles, each the exact quotient rounded once.  No device is needed."""
+    blocks = np.ascontiguousarray(blocks, dtype=np.int64).reshape(-1, L.MOMENT_BLOCK)
+    div = np.ascontiguousarray(np.broadcast_to(np.asarray(divisor, dtype=np.int64), (blocks.shape[0],)))
+    out = np.empty(blocks.shape[0])
+    i64 = C.POINTER(C.c_int64)
+    L.check(L.load().rscm_gpu_moment_finish(blocks.ctypes.data_as(i64), blocks.shape[0], div.ctypes.data_as(i64), int(n_terms), L.dptr(out)))
+    return out
+
+
+def moment_means(sums1, K: int, G: int) -> np.ndarray:
+    """``mean[G][K]`` from the (reduced) order-1 sums ``[G][2 + K * 69]`` of ``Ensemble.moment_sums``."""
+    sums1 = np.asarray(sums1, dtype=np.int64).reshape(G, 2 + K * L.MOMENT_BLOCK)
+    return np.stack([moment_finish(row[2:], row[1], row[0]) for row in sums1])
+
+
+def moments_dict(n, w, mean, cov, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """``{"count", "weight", "mean", "cov", "sd", "corr"}`` from ``n[G]``, ``w[G]``, ``mean[G][K]``, ``cov[G][K][K]``: ``sd_a =
+    sqrt(cov_aa)``, ``corr_ab = cov_ab / (sd_a sd_b)`` for a < b, mirrored; the diagonal is exactly 1.0 where ``cov_aa > 0``, NaN
+    otherwise.  Plain float64 numpy, the same on every rank.  Without ``grouped`` the group axis (of length 1) is dropped."""
+    n, w = np.asarray(n, dtype=np.int64), np.asarray(w, dtype=np.int64)
+    mean, cov = np.asarray(mean, dtype=np.float64), np.asarray(cov, dtype=np.float64)
+    K = mean.shape[-1]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = np.einsum("gaa->ga", cov)
+        sd = np.sqrt(var)
+        corr = np.empty_like(cov)
+        for a in range(K):
+            corr[:, a, a] = np.where(var[:, a] > 0.0, 1.0, np.nan)
+            for b in range(a + 1, K):
+                corr[:, a, b] = corr[:, b, a] = cov[:, a, b] / (sd[:, a] * sd[:, b])
+    out = {"count": n, "weight": w, "mean": mean, "cov": cov, "sd": sd, "corr": corr}
+    return out if grouped else {k: v[0] for k, v in out.items()}
+
+
+def moments_result(sums1, sums2, K: int, G: int, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """Finishes the (reduced) sums of ``Ensemble.moment_sums`` -- ``sums1[G][2 + K * 69]`` of order 1 and ``sums2[G][2 + K (K + 1)
+    / 2 * 69]`` of order 2 about ``moment_means(sums1, K, G)`` -- through rscm_gpu_moment_finish and forms ``moments_dict``."""
+    B = moment_blocks(K, 2)
+    sums2 = np.asarray(sums2, dtype=np.int64).reshape(G, 2 + B * L.MOMENT_BLOCK)
+    mean = moment_means(sums1, K, G)
+    cov = np.empty((G, K, K))
+    iu = np.triu_indices(K)          # row-major upper triangle: (0,0), (0,1), ..., (0,K-1), (1,1), ...
+    for g, row in enumerate(sums2):
+        tri = moment_finish(row[2:], row[1], row[0])
+        cov[g][iu] = tri
+        cov[g][(iu[1], iu[0])] = tri
+    return moments_dict(sums2[:, 0], sums2[:, 1], mean, cov, grouped)
 
 
 def select_flags(weighted: bool, anomaly: bool, grouped: bool) -> int:

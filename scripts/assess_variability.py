@@ -115,6 +115,8 @@ def main():
                     help="also weight by the band coherence and gains of the record's heat uptake on its temperature (requires --heat-content)")
     ap.add_argument("--toa-imbalance", action="store_true",
                     help="also weight by the covariability of the record's temperature and top-of-atmosphere imbalance (requires --heat-content)")
+    ap.add_argument("--correlations", action="store_true",
+                    help="also print the posterior correlation matrix of the parameters (Ensemble.moments) under the last weights formed")
     a = ap.parse_args()
     if a.toa_imbalance and not a.heat_content:
         ap.error("--toa-imbalance requires --heat-content")
@@ -371,6 +373,20 @@ def main():
                 np.array_equal(x[key][b].to_host()[:64], one[key][b], equal_nan=True)
                 for key in ("coherence2", "gain", "gain_quad") for b in range(len(xt["counts"]))))
 
+        correlations = None
+        if a.correlations:
+            # the posterior as numbers: exact weighted means, sd and correlations of all parameter rows under the weights the last
+            # estimator asked for has left on the handle
+            pnames = ["lambda0", "a", "efficacy", "eta", "heat_capacity_surface", "heat_capacity_deep", "sigma", "phi"]
+            prows = [0, 1, 2, 3, 4, 5, sigma_row, phi_row]
+            m = ens.moments([ens.params_vector(r) for r in prows], weighted=True)
+            correlations = {"parameters": pnames, "weight": int(m["weight"]), "count": int(m["count"]), "mean": m["mean"].tolist(),
+                            "sd": m["sd"].tolist(), "corr": m["corr"].tolist()}
+            print("posterior correlations (weights of the last estimator):", file=sys.stderr)
+            print(" " * 22 + " ".join(f"{k[:8]:>8}" for k in pnames), file=sys.stderr)
+            for k, row in zip(pnames, m["corr"]):
+                print(f"{k:>22}" + " ".join(f"{v:8.3f}" for v in row), file=sys.stderr)
+
     res = {"members": a.members, "draws": a.draws, "mode": "FAST" if a.fast else "EXACT", "quantiles": Q, "ess": ess,
            "truth": {"sigma": TRUTH[6], "phi": TRUTH[7]},
            "prior": {"sigma": prior[0].tolist(), "phi": prior[1].tolist()},
@@ -392,6 +408,8 @@ def main():
         res["toa_imbalance"] = toa
     if xspec is not None:
         res["cross_spectrum"] = xspec
+    if correlations is not None:
+        res["correlations"] = correlations
     print(json.dumps(res), flush=True)
     sys.exit(0 if all(checks.values()) else 1)
 
