@@ -114,8 +114,11 @@ extern "C" {
  *      top-of-atmosphere imbalance as diagnostic variables: rscm_ens_define_energy_budget, rscm_ens_diagnostic_quantity,
  *      RSCM_BUDGET_FORCING, RSCM_BUDGET_RESPONSE, RSCM_BUDGET_DEEP_UPTAKE, RSCM_BUDGET_IMBALANCE
  *  23  exact weighted means and covariances of per-member vectors across members, in a fixed-point integer accumulator that shards
- *      add up: rscm_ens_moment_sums, rscm_gpu_moment_finish, rscm_ens_moments, RSCM_MOMENT_MAX_VECTORS, RSCM_MOMENT_BLOCK */
-#define RSCM_GPU_ABI_MINOR 23
+ *      add up: rscm_ens_moment_sums, rscm_gpu_moment_finish, rscm_ens_moments, RSCM_MOMENT_MAX_VECTORS, RSCM_MOMENT_BLOCK
+ *  24  the same exact weighted mean and spread of a stored variable at every row, with its covariance with up to four per-member
+ *      vectors (the regression of each year on a parameter): rscm_ens_moment_rows_sums, rscm_ens_moment_rows,
+ *      RSCM_MOMENT_ROWS_MAX_VECTORS, RSCM_MOMENT_ROWS_MAX_BLOCKS */
+#define RSCM_GPU_ABI_MINOR 24
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1139,6 +1142,45 @@ RSCM_API int rscm_gpu_moment_finish(const int64_t* blocks, int32_t n_blocks, con
  * centre of order 2 is mean.  A group with W == 0: NaN in mean and cov.  n and weight may be NULL.  Errors as rscm_ens_moment_sums. */
 RSCM_API int rscm_ens_moments(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t flags, double* mean, double* cov,
                               int64_t* n, int64_t* weight);
+
+/* ---- exact weighted mean and spread of a stored variable at every row (ABI minor 24) ---------------- */
+/* The moments above for the rows of a stored variable instead of vectors: per row (and member group) the weighted mean and second
+ * moment of the variable across members, and its covariance with K per-member vectors, from one launch per order over all rows.
+ * This is the one definition; the kernel (moment_rows.hip), its integer pieces (moment_window.hpp) and the tests' restatement in
+ * Python integers (tests/host_moment_rows.py) apply it.
+ *   Rows: those of rscm_ens_quantile_rows, t_begin, t_begin + t_stride, ... < t_end of var_id, read where they are resident (full
+ *   storage, the window, the output store); a diagnostic by its id, RSCM_ERR_STATE when it is stale.  A row beyond the current time
+ *   index has n = 0, W = 0 and zero blocks (NaN once finished); a computed row that is not resident is RSCM_ERR_STATE, as is a call
+ *   while a staged select is in flight on the handle.
+ *   The value of member i in row t: x = series[t][i], or with RSCM_SELECT_ANOMALY x = series[t][i] - b[i], one rounded subtraction,
+ *   the bits rscm_ens_quantile_rows_ex sees under that flag; without a baseline RSCM_ERR_STATE.
+ *   Vectors: vec_dev[K], 0 <= K <= RSCM_MOMENT_ROWS_MAX_VECTORS, device addresses of N doubles on the handle's device (vec_dev may
+ *   be NULL when K == 0).
+ *   Which members count, per row: member i counts in row t when x is finite, all K of its vector values are finite and, with
+ *   RSCM_SELECT_GROUPED, its group is valid (it then counts in that group).  Every row has its own n and W: a member that is NaN
+ *   from some row on drops out of those rows only.  w_i is the member weight with RSCM_SELECT_WEIGHTED, else 1.
+ *   Sums: the limb scheme of rscm_ens_moment_sums, block for block (RSCM_MOMENT_BLOCK int64: 68 limbs, then the count of non-finite
+ *   terms).  Order 1, B = 1 + K blocks: S_x, S_v0 .. S_v(K-1) over the row's counted members.  Order 2, B = 1 + 2 K blocks about
+ *   center[rows][G][1 + K] (host doubles: the centre of x, then of each vector), in the order xx, x v_0 .. x v_(K-1),
+ *   v_0 v_0 .. v_(K-1) v_(K-1); a term is RN(RN(p - c_p) * RN(q - c_q)), no FMA.  A non-finite term is counted, not added; a
+ *   (row, group) with any non-finite centre has every term of every block counted so.
+ *   Result: out[rows][G][2 + B * 69] int64 -- n, W, the blocks -- for either order; host memory, or device memory on the handle's
+ *   device when on_device != 0.  Raw limbs of shards add element by element; canonical values are what compares.
+ *   rows * G * B may not exceed RSCM_MOMENT_ROWS_MAX_BLOCKS = 2^19 (751 rows x 64 groups x 9 blocks are 432 576; the array then
+ *   takes 552 bytes per block): RSCM_ERR_INVALID.  Also RSCM_ERR_INVALID: unknown flags, order outside {1, 2}, order 2 without
+ *   center, K out of range, a NULL out, a vector or a device out that is not device memory of the size on the handle's device, a
+ *   bad row range, N >= 2^31.  Weighted without weights, grouped without groups: RSCM_ERR_STATE. */
+#define RSCM_MOMENT_ROWS_MAX_VECTORS 4
+#define RSCM_MOMENT_ROWS_MAX_BLOCKS (1 << 19)
+RSCM_API int rscm_ens_moment_rows_sums(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_vec,
+                                       const double* const* vec_dev, int32_t flags, int32_t order, const double* center, int64_t* out,
+                                       int32_t on_device);
+/* The two passes and the finish (rscm_gpu_moment_finish) on one handle: mean[rows][G][1 + K] (of x, then of the vectors over the row's
+ * counted members), second[rows][G][1 + 2 K] (the order-2 sums about mean, divided by W, in the order above: the variance of x, its
+ * covariances with the vectors, the vectors' variances), n[rows][G], weight[rows][G]; n and weight may be NULL.  W == 0: NaN.
+ * Errors as rscm_ens_moment_rows_sums. */
+RSCM_API int rscm_ens_moment_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_vec,
+                                  const double* const* vec_dev, int32_t flags, double* mean, double* second, int64_t* n, int64_t* weight);
 
 /* ---- per-member variability statistics and a likelihood over per-member vectors (ABI minor 16) ---- */
 /* How variable is each member's series of var_id over a period: its mean, its trend, the variance and standard deviation about the

@@ -102,6 +102,12 @@ RSCM_API int rscm_gpu_experiments_build(void);
  * rscm_ens_run* / rscm_ens_run_lockstep call, not once per model step of it (tests/test_gpu_links.py). */
 RSCM_API int rscm_gpu_derive_launches(int64_t* out);
 
+/* Which path the terms of the calling THREAD's last rscm_ens_moment_rows_sums launch took (csrc/moment_rows.hip): out[0] the terms
+ * that lanes added inside their private limb windows, out[1] the terms that took the serial walk, out[2] the rebases (moves of a
+ * window that already had a base).  out[0] + out[1] is the number of finite non-zero terms over all rows and blocks of that launch
+ * (tests/test_gpu_moment_rows.py); a call that launched nothing leaves zeros.  rscm_ens_moment_rows leaves its order-2 launch's. */
+RSCM_API int rscm_gpu_moment_rows_last_stats(int64_t out[3]);
+
 /* Fault injection for the cut runs (rscm_ens_last_run_plan: member blocks x step chunks on two streams): the k-th chunk launch
  * (1-based, counted over both blocks in issue order) of the calling THREAD's next cut run is not issued and reports
  * hipErrorLaunchFailure instead.  The next cut run consumes the hook whether or not it issues as many as k launches (a k beyond the

@@ -1330,6 +1330,19 @@ class GraphModel:
         kw = {"grouped": True} if grouped else {}
         return vs[0].owner.moments(vs, weighted=weighted, **kw)
 
+    def moment_rows(self, name: str, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, vectors=(), weighted: bool = False,
+                    anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """``Ensemble.moment_rows`` (the exact weighted mean and spread of ``name`` at every row, and its covariance with per-member
+        vectors) on the variable's home ensemble.  The vectors must belong to that ensemble: ``ValueError`` otherwise (the rows are
+        read where they live, and the statistic does not cross handles)."""
+        ens, vid = self.variable_home(name)
+        vs = list(vectors)
+        for v in vs:
+            if getattr(v, "owner", None) is not ens:
+                raise ValueError(f"moment_rows: a vector does not belong to the home ensemble of {name!r}; take it from that ensemble")
+        kw = {"grouped": True} if grouped else {}
+        return ens.moment_rows(vid, t_begin, t_end, t_stride, vs, weighted=weighted, anomaly=anomaly, **kw)
+
     def exceedance(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """``Ensemble.exceedance`` on the ensemble that owns the vector."""
         kw = {"grouped": True} if grouped else {}

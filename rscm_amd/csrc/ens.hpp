@@ -409,6 +409,9 @@ int check_slot(int32_t slot);
 int slot_buffer(rscm_ens* h, int32_t slot);
 // RSCM_OK if p is device memory on h's device holding at least N doubles from p on, else RSCM_ERR_INVALID (select_host.cpp)
 int check_member_vector(const rscm_ens* h, const double* p, const char* what);
+// RSCM_OK if p is device memory on h's device holding at least n int64 from p on, else RSCM_ERR_INVALID: the `out` of the moment sums
+// when it is on the device (moments_host.cpp)
+int check_device_out(const rscm_ens* h, const int64_t* p, size_t n);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (window_host.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
 // the handle's own window (window_host.cpp)

@@ -15,11 +15,6 @@
 static_assert(RSCM_MOMENT_BLOCK == rscm::kMomentBlock, "the header states the block the finishing step reads");
 static_assert(RSCM_MOMENT_MAX_VECTORS == rscm::kMaxMomentVectors, "the header states the kernel's vector limit");
 
-namespace {
-
-int32_t moment_blocks(int32_t n_vec, int32_t order) { return order == 1 ? n_vec : n_vec * (n_vec + 1) / 2; }
-
-// RSCM_OK if p is device memory on h's device holding at least n int64 from p on
 int check_device_out(const rscm_ens* h, const int64_t* p, size_t n)
 {
     if ((uintptr_t)p & 7) return fail(RSCM_ERR_INVALID, "out is not 8-byte aligned");
@@ -37,6 +32,10 @@ int check_device_out(const rscm_ens* h, const int64_t* p, size_t n)
     }
     return RSCM_OK;
 }
+
+namespace {
+
+int32_t moment_blocks(int32_t n_vec, int32_t order) { return order == 1 ? n_vec : n_vec * (n_vec + 1) / 2; }
 
 int moment_sums(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t flags, int32_t order, const double* center, int64_t* out,
                 int32_t on_device)

@@ -938,6 +938,29 @@ constexpr int64_t kMomentMembersPerPass = 262144;
 hipError_t launch_moment_sums(const double* const* d_vec, int32_t n_vec, const int64_t* d_w, const int32_t* d_group, int32_t n_groups,
                               int32_t order, const double* d_centre, int64_t N, unsigned long long* d_mask, unsigned long long* d_out,
                               hipStream_t s);
+// the exact moment sums of stored rows (moment_rows.hip; the definition is stated in include/rscm_gpu.h, rscm_ens_moment_rows_sums):
+// out[n_rows][G][2 + B * 69] += {n, W, the blocks} of the rows `rows` (a device array of n_rows device addresses of N doubles), with
+// G = n_groups when group is non-null, else 1, and B = moment_rows_blocks(n_vec, order): order 1 the sums of x and of the n_vec member
+// vectors vec[k], order 2 those of xx, x v_k, v_k v_k about centre[n_rows][G][1 + n_vec].  w non-null: the member weights; base
+// non-null: x is the row's value minus base[i].  The caller zeroes out and stats[3] (window terms, walked terms, rebases); g_chunk is
+// the launcher's.  N < 2^31.  The grid is capped at kMomRowBlocks blocks in x, which take kMomentRowsMembersPerPass members per pass
+// of their grid-stride loop; a block's LDS bins take at most kMomentRowsLdsBytes, beyond which the groups are split over grid z.
+constexpr int kMaxMomentRowVectors = 4;
+constexpr int kMomRowBlocks = 32;
+constexpr int64_t kMomentRowsMembersPerPass = 8192;
+constexpr int32_t kMomentRowsLdsBytes = 61440;
+struct MomentRowsArgs {
+    const double* const* rows;
+    const double* vec[kMaxMomentRowVectors];
+    const int64_t* w;
+    const int32_t* group;
+    const double *base, *centre;
+    unsigned long long *out, *stats;
+    int64_t N;
+    int32_t n_rows, n_groups, g_chunk;
+};
+constexpr int32_t moment_rows_blocks(int32_t n_vec, int32_t order) { return order == 1 ? 1 + n_vec : 1 + 2 * n_vec; }
+hipError_t launch_moment_rows(MomentRowsArgs a, int32_t n_vec, int32_t order, hipStream_t s);
 // per-member variability statistics (variability.hip) over rows d_rows[n_rows][N]: d_out[5][N] = mean, slope, variance, sd, r1 of
 // the working series (mode kVarMean / kVarLinear: the rows, kVarDifference: their first differences; the definition is stated in
 // include/rscm_gpu.h, rscm_ens_member_variability); stt = n (n^2 - 1) / 12 of the working series' length n, formed by the caller

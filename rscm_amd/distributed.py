@@ -17,6 +17,7 @@ in the CPU tests), are:
 * ``quantile_vectors_global``: the same histogram all-reduces over per-member vectors (indicators, parameter rows);
 * ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums;
 * ``moments_global``: two all-reduces (int64 SUM) of the fixed-point moment sums, 69 int64 per mean and covariance entry;
+* ``moment_rows_global``: the same two all-reduces for the mean and spread of a stored variable at every row;
 * ``weights_stats_global``: one all-reduce (int64 SUM) of the exact weight sums and one (MAX) of the largest weight;
 * ``resample_global``: one all-gather of each rank's exact summed weight (8 B per rank); no member crosses a rank.
 
@@ -254,6 +255,42 @@ def moments_global(ensemble, vectors, group=None, weighted: bool = False, groupe
     return moments_result(sums1, sums2, K, G, grouped=grouped)
 
 
+def moment_rows_global(ensemble, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, vectors=(), group=None,
+                       weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.moment_rows`` of the WHOLE sharded ensemble on every rank, exactly as ``moments_global`` proceeds: each rank forms
+    the order-1 sums of its shard (``Ensemble.moment_rows_sums``), the int64 arrays are SUM-reduced and every rank finishes the same
+    means; then the order-2 sums about those means, reduced and finished the same way.  Two collectives; the result has the same bits
+    at any number of ranks and equals ``Ensemble.moment_rows`` of the gathered ensemble.  Every rank passes the same rows and its
+    shard of each vector in the same order and stands at the same time index; ``grouped``: the same ``n_groups`` on every rank.
+    Fewer than 2^31 members may count in a row over all ranks."""
+    from .ensemble import moment_rows_means, moment_rows_result
+    vs = list(vectors)
+    K = len(vs)
+    kw = {}
+    if weighted:
+        kw["weighted"] = True
+    if anomaly:
+        kw["anomaly"] = True
+    if grouped:
+        kw["grouped"] = True
+
+    def reduced(a):
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if not is_distributed():
+            return a
+        import torch
+        d = _dist()
+        t = torch.from_numpy(a.copy()).to(_device_for_backend())
+        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+        return t.cpu().numpy()
+
+    sums1 = reduced(ensemble.moment_rows_sums(var, 1, t_begin, t_end, t_stride, vectors=vs, **kw))
+    G = sums1.shape[1]
+    mean = moment_rows_means(sums1, K, G)
+    sums2 = reduced(ensemble.moment_rows_sums(var, 2, t_begin, t_end, t_stride, vectors=vs, center=mean, **kw))
+    return moment_rows_result(sums1, sums2, K, G, grouped=grouped)
+
+
 def weights_stats_global(ensemble, group=None) -> Dict[str, object]:
     """``Ensemble.weights_stats`` of the WHOLE sharded ensemble on every rank: the ranks' exact integers are SUM-reduced (``w_max``:
     MAX) -- sum w^2 as four 32-bit limbs, each of which sums without wrapping over any number of ranks an int64 can count -- and
@@ -385,6 +422,12 @@ class ShardedEnsemble:
     def moments_global(self, vectors, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Exact means, covariances and correlations of per-member vectors over the global ensemble (``moments_global``)."""
         return moments_global(self.ensemble, vectors, weighted=weighted, grouped=grouped)
+
+    def moment_rows_global(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, vectors=(), weighted: bool = False,
+                           anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Exact mean and spread of a stored variable at every row over the global ensemble, with its covariance with per-member
+        vectors (``moment_rows_global``)."""
+        return moment_rows_global(self.ensemble, var, t_begin, t_end, t_stride, vectors, weighted=weighted, anomaly=anomaly, grouped=grouped)
 
     def exceedance_global(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""

@@ -1012,6 +1012,58 @@ class Ensemble:
                                            n.ctypes.data_as(i64), w.ctypes.data_as(i64)))
         return moments_dict(n, w, mean, cov, grouped)
 
+    def _moment_rows_args(self, var, t_begin, t_end, t_stride, vectors):
+        arr, K = self._vectors(vectors)
+        if K > L.MOMENT_ROWS_MAX_VECTORS:
+            raise ValueError(f"moment_rows: at most {L.MOMENT_ROWS_MAX_VECTORS} vectors, got {K}")
+        t_end = self.n_times if t_end is None else t_end
+        rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
+        return self._var(var), t_end, rows, (arr if K else None), K
+
+    def moment_rows_sums(self, var, order: int, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, vectors=(), center=None,
+                         weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> np.ndarray:
+        """The exact integer sums behind ``moment_rows`` (rscm_ens_moment_rows_sums) over the rows ``t_begin, t_begin + t_stride, ...
+        < t_end`` of ``var`` and up to four ``[N]`` float64 ``DeviceVector``s: int64 ``[rows][G][2 + B * 69]``, per row and group the
+        count n, the weight W and B blocks of 68 limbs and a count of non-finite terms -- ``order`` 1: B = 1 + K, the sums of w x and
+        w v_k; 2: B = 1 + 2 K, the sums of the products xx, x v_k, v_k v_k of the differences from ``center`` ``[rows][G][1 + K]``.
+        G is 1 without ``grouped``.  The arrays of shards add up element by element; ``moment_rows_result`` finishes them."""
+        vid, t_end, rows, arr, K = self._moment_rows_args(var, t_begin, t_end, t_stride, vectors)
+        if order not in (1, 2):
+            raise ValueError("moment_rows: order must be 1 or 2")
+        G = self._n_groups(grouped)
+        c = None
+        if order == 2:
+            if center is None:
+                raise ValueError("moment_rows: order 2 needs a center")
+            c = np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))
+            if c.size != rows * G * (1 + K):
+                raise ValueError(f"center: need {rows} x {G} x {1 + K} values, got {c.size}")
+        out = np.zeros((rows, G, 2 + moment_rows_blocks(K, order) * L.MOMENT_BLOCK), dtype=np.int64)
+        L.check(self._lib.rscm_ens_moment_rows_sums(self._h, vid, t_begin, t_end, t_stride, K, arr, select_flags(weighted, anomaly, grouped),
+                                                    int(order), None if c is None else L.dptr(c), out.ctypes.data_as(C.POINTER(C.c_int64)), 0))
+        return out
+
+    def moment_rows(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, vectors=(), weighted: bool = False,
+                    anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """The plume as mean and spread: the exact weighted mean and variance of ``var`` across members at every row ``t_begin,
+        t_begin + t_stride, ... < t_end``, read wherever the rows are resident (full series, window, output store), and its
+        covariance with up to four ``[N]`` float64 ``DeviceVector``s (a parameter row, an indicator).  Returns ``{"count", "weight",
+        "mean", "var", "sd": [rows]}`` and, with vectors, ``{"vec_mean", "vec_var", "cov", "corr", "slope": [rows][K]}``: ``slope =
+        cov / vec_var`` is the row regressed on the vector, that year's value per unit of the parameter.  A member counts in a row
+        when its value there and all its vector values are finite, so every row has its own count; ``weighted`` takes the member
+        weights as frequencies, ``anomaly`` the member's value minus its baseline (the bits ``quantile_rows(anomaly=True)`` sees),
+        ``grouped`` gives one result per member group, the group dimension after rows.  Every mean, variance and covariance is the
+        exact sum, accumulated in integers on the device, over W, rounded once: the same bits for any order of the members, and
+        ``rscm_amd.distributed.moment_rows_global`` returns them for a sharded ensemble.  Rows beyond the time index: count 0, NaN."""
+        vid, t_end, rows, arr, K = self._moment_rows_args(var, t_begin, t_end, t_stride, vectors)
+        G = self._n_groups(grouped)
+        mean, second = np.empty((rows, G, 1 + K)), np.empty((rows, G, 1 + 2 * K))
+        n, w = np.zeros((rows, G), dtype=np.int64), np.zeros((rows, G), dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        L.check(self._lib.rscm_ens_moment_rows(self._h, vid, t_begin, t_end, t_stride, K, arr, select_flags(weighted, anomaly, grouped),
+                                               L.dptr(mean), L.dptr(second), n.ctypes.data_as(i64), w.ctypes.data_as(i64)))
+        return moment_rows_dict(n, w, mean, second, grouped)
+
     def params_vector(self, row: int) -> DeviceVector:
         """Parameter row ``row`` of the ``[P][N]`` block as a ``DeviceVector`` (rscm_ens_params_devptr), e.g. for
         ``quantile_vectors``.  Once handed out, the block is read per member for the handle's life."""
@@ -1250,6 +1302,51 @@ def moments_result(sums1, sums2, K: int, G: int, grouped: bool = True) -> Dict[s
         cov[g][iu] = tri
         cov[g][(iu[1], iu[0])] = tri
     return moments_dict(sums2[:, 0], sums2[:, 1], mean, cov, grouped)
+
+
+def moment_rows_blocks(K: int, order: int) -> int:
+    """Blocks per row and group of ``Ensemble.moment_rows_sums``: 1 + K sums of order 1, 1 + 2 K of order 2."""
+    return 1 + K if order == 1 else 1 + 2 * K
+
+
+def _moment_rows_finish(sums, B: int, G: int) -> np.ndarray:
+    """``[rows][G][B]`` doubles from sums ``[rows][G][2 + B * 69]``: every block over its (row, group)'s W, in one call."""
+    sums = np.asarray(sums, dtype=np.int64).reshape(-1, G, 2 + B * L.MOMENT_BLOCK)
+    if sums.shape[0] == 0:
+        return np.empty((0, G, B))
+    out = moment_finish(sums[:, :, 2:], np.repeat(sums[:, :, 1].reshape(-1), B), int(sums[:, :, 0].max()))
+    return out.reshape(-1, G, B)
+
+
+def moment_rows_means(sums1, K: int, G: int) -> np.ndarray:
+    """``mean[rows][G][1 + K]`` from the (reduced) order-1 sums of ``Ensemble.moment_rows_sums``: the centre of its order 2."""
+    return _moment_rows_finish(sums1, 1 + K, G)
+
+
+def moment_rows_dict(n, w, mean, second, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """The dict of ``Ensemble.moment_rows`` from ``n[rows][G]``, ``w[rows][G]``, ``mean[rows][G][1 + K]`` and ``second[rows][G][1 +
+    2 K]``: ``sd = sqrt(var)``, ``corr = cov / (sd * sqrt(vec_var))`` (the rule of ``moments_dict``), ``slope = cov / vec_var``, one
+    IEEE operation each on the finished values.  Plain float64 numpy, the same on every rank.  Without ``grouped`` the group axis
+    (of length 1) is dropped."""
+    n, w = np.asarray(n, dtype=np.int64), np.asarray(w, dtype=np.int64)
+    mean, second = np.asarray(mean, dtype=np.float64), np.asarray(second, dtype=np.float64)
+    K = mean.shape[-1] - 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        var = second[..., 0]
+        out = {"count": n, "weight": w, "mean": mean[..., 0], "var": var, "sd": np.sqrt(var)}
+        if K:
+            cov, vec_var = second[..., 1:1 + K], second[..., 1 + K:]
+            out.update({"vec_mean": mean[..., 1:], "vec_var": vec_var, "cov": cov,
+                        "corr": cov / (out["sd"][..., None] * np.sqrt(vec_var)), "slope": cov / vec_var})
+    return out if grouped else {k: v[:, 0] for k, v in out.items()}
+
+
+def moment_rows_result(sums1, sums2, K: int, G: int, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """Finishes the (reduced) sums of ``Ensemble.moment_rows_sums`` -- ``sums1[rows][G][2 + (1 + K) * 69]`` of order 1 and
+    ``sums2[rows][G][2 + (1 + 2 K) * 69]`` of order 2 about ``moment_rows_means(sums1, K, G)`` -- through rscm_gpu_moment_finish and
+    forms ``moment_rows_dict``."""
+    sums2 = np.asarray(sums2, dtype=np.int64).reshape(-1, G, 2 + (1 + 2 * K) * L.MOMENT_BLOCK)
+    return moment_rows_dict(sums2[:, :, 0], sums2[:, :, 1], moment_rows_means(sums1, K, G), _moment_rows_finish(sums2, 1 + 2 * K, G), grouped)
 
 
 def select_flags(weighted: bool, anomaly: bool, grouped: bool) -> int:
