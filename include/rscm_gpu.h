@@ -421,6 +421,15 @@ extern "C" {
                              bit-identical to the CPU oracle for the two-layer kind            */
 #define RSCM_MODE_FAST 1  /* FMA + reciprocal heat capacities; |rel diff| <= 1e-11 on bounded
                              trajectories (tests/test_gpu_parity.py states the tolerance).
+                             DOMAIN: the two-layer arithmetic of this mode (two-layer, coupled) folds the heat
+                             capacities into its coefficients and requires FINITE 1/Cs and eta/Cd.  Outside that
+                             domain -- a subnormal Cs or Cd, which no physical parameter set has -- a member the
+                             reference keeps finite (at rest under a zero forcing, 0/Cs = 0) may come out NaN
+                             (inf * 0) from the first row on, with its status byte set; nothing guards the hot loop
+                             against it.  The arithmetic itself -- every rounding, every member, inf and NaN, the
+                             status bytes -- is held bit for bit to a host restatement (tests/test_gpu_fast_bits.py,
+                             tests/host_fast.py, which lists exactly that class as its one exception against the
+                             oracle's status).
                              RSCM_KIND_OCEAN_CARBON: the history convolution in O(T) -- the last 60 (2D-BERN:
                              120) monthly lags explicitly, the older ones through 21 decaying modes fitted to the
                              impulse response; within 2e-10 of EXACT (tests/test_gpu_ocean.py; the tiled

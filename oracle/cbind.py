@@ -121,6 +121,8 @@ def lib() -> C.CDLL:
         L.orc_halo_aggregates.restype = None
         L.orc_halo_run.argtypes = [C.c_int64, C.c_int32, _dp, _dp, _dp, _ip, _dp, C.c_int64, C.c_int64]
         L.orc_halo_run.restype = C.c_int32
+        L.orc_fma.argtypes = [_dp, _dp, _dp, _dp, C.c_int64]
+        L.orc_fma.restype = None
         L.orc_udeb_lamcalc.argtypes = [_dp, C.c_double, _dp]
         L.orc_udeb_area_factors.argtypes = [_dp, _dp, _dp, _dp]
         L.orc_udeb_sst_to_air.argtypes = [_dp, C.c_double]
@@ -160,6 +162,17 @@ def _pmap(fn, n, threads):
             rcs = list(ex.map(lambda c: fn(*c), chunks))
     if any(rcs):
         raise RuntimeError(f"oracle returned {rcs}")
+
+
+def fma(a, b, c):
+    """C99 fma() per element, a*b + c with one rounding; the operands broadcast like a numpy ufunc's."""
+    a, b, c = (x if type(x) is np.ndarray and x.dtype == np.float64 else np.asarray(x, dtype=np.float64) for x in (a, b, c))
+    if not (a.shape == b.shape == c.shape):
+        a, b, c = np.broadcast_arrays(a, b, c)
+    out = np.empty(a.shape)
+    a, b, c = (np.ascontiguousarray(x) for x in (a, b, c))
+    lib().orc_fma(_d(a), _d(b), _d(c), _d(out), out.size)
+    return out
 
 
 def bounds_from_values(values):

@@ -312,3 +312,13 @@ ORC_API int orc_gaussian_loglik(int64_t N, int32_t T, const double* const* serie
     }
     return 0;
 }
+
+/*
+ * C99 fma() per element: a*b + c with ONE rounding.  For the host restatements of the FAST arithmetic
+ * (tests/host_fast.py): numpy has no fused multiply-add.  tests/test_host_fast.py holds it to exact
+ * rational arithmetic.
+ */
+ORC_API void orc_fma(const double* a, const double* b, const double* c, double* out, int64_t n)
+{
+    for (int64_t i = 0; i < n; ++i) out[i] = fma(a[i], b[i], c[i]);
+}

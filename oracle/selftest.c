@@ -20,6 +20,7 @@ int orc_coupled_run(int64_t, int32_t, const double*, const double*, int32_t, con
                     double*, double*, double*, double*, int64_t, int64_t);
 int orc_gaussian_loglik(int64_t, int32_t, const double* const*, int32_t, const int32_t*,
                         const int32_t*, const double*, const double*, int, double*, int64_t, int64_t);
+void orc_fma(const double*, const double*, const double*, double*, int64_t);
 
 int32_t orc_udeb_n_params(void);
 void orc_udeb_default_params(double*);
@@ -162,6 +163,12 @@ int main(void)
     if (orc_aggregate_sum(agg, 3) != 4.0) return 6;
     if (fabs(orc_co2_erf(3.7, 278.0, 556.0) - 3.7) > 1e-10) return 7;
     if (orc_rk4_nsteps(1750, 1751, 0.1) != 10 || !orc_rk4_endtime_ok(1750, 1751, 0.1)) return 8;
+    {   /* one rounding: (1 + 2^-30)^2 - 1 keeps the product's low bit */
+        const double x = 1.0 + 0x1p-30, fa[2] = {x, 2.0}, fb[2] = {x, 3.0}, fc[2] = {-1.0, 1.0};
+        double fo[2];
+        orc_fma(fa, fb, fc, fo, 2);
+        if (fo[0] != 0x1p-29 + 0x1p-60 || fo[1] != 7.0) return 11;
+    }
     {   /* ClimateUDEB: 3 members x 20 years */
         const int P = orc_udeb_n_params(), NU = 3, TU = 21;
         double* up = malloc(sizeof(double) * P * NU), ub[22], uf[21], init[4] = {0, 0, 0, 0};

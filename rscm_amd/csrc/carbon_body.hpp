@@ -72,7 +72,9 @@ __device__ __forceinline__ int32_t carbon_cycle_year(double lifetime, double rli
 // -- their RK4 increment (((E + 2E) + 2E) + E) h/6 depends on E alone, so the EXACT bits cost one addition per
 // sub-step.  No division: 1/tau is formed once per member, 1/2.13 is a constant.  Three FMAs and an addition per
 // sub-step against ~60 instructions of the EXACT body; within 3e-13 of the oracle on all three states
-// (tests/test_gpu_parity.py), shared by the fused chain (coupled.hip) and the linked component (below).
+// (tests/test_gpu_parity.py), shared by the fused chain (coupled.hip) and the linked component (below).  Held bit for bit, with the
+// device's exp fed into a numpy restatement of the statements below (tests/host_fast.py), for every member of the fused chain and of
+// the stand-alone kind -- lifetimes 0, inf and subnormal, an exp that overflows or underflows, inf / NaN inputs: tests/test_gpu_fast_bits.py.
 constexpr double kPpmPerGtc = 1.0 / 2.13;
 
 __device__ __forceinline__ void carbon_cycle_year_fast(double rtau, double alpha, double conc_pi, double emis, double temperature, int32_t m,

@@ -133,7 +133,10 @@ __device__ __forceinline__ int32_t year(const CPConst& p, double emis, int32_t m
 // (no division, one exp per year), CO2ERF and the Sum aggregate in their one arithmetic (a division by the
 // pre-industrial concentration and a log per year), TwoLayer with the heat capacities folded into its
 // coefficients and FMA stages (two_layer_body.hpp, rk4_year_fast) -- the very functions the linked components
-// call in this mode, so "four linked ensembles == the fused kind, bit for bit" holds per mode.
+// call in this mode, so "four linked ensembles == the fused kind, bit for bit" holds per mode.  Against the CPU oracle
+// tolerance-parity (1e-11 on bounded members, tests/test_gpu_parity.py); the arithmetic itself is held bit for bit, all seven series
+// and the status byte of every member, by tests/test_gpu_fast_bits.py: the device's own exp / log_f64 of the year's two arguments fed
+// into the numpy restatement of these statements (tests/host_fast.py).
 template <bool LDS>
 __global__ __launch_bounds__(kBlock) void coupled_fast_kernel(CoupledArgs a)
 {

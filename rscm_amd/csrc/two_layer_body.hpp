@@ -165,7 +165,9 @@ struct TLFast {
 //     Ts' = F/Cs - (l0 - a Ts) Ts - ee w          w' = Ts' - ed w
 // Four fused operations per stage instead of five (the difference need not be formed), 30 per RK4 step instead of 34; the
 // deep-ocean temperature is Ts - w at the end of the model step.  Within 1e-11 of the oracle on bounded members
-// (tests/test_gpu_parity.py; measured 1e-14).
+// (tests/test_gpu_parity.py; measured 6e-14).  The statements below are held bit for bit, for every member (runaway, inf, NaN and
+// the status byte included), to their restatement in numpy with an exact fma: tests/host_fast.py, tests/test_gpu_fast_bits.py.
+// Domain: finite 1/Cs and eta/Cd (include/rscm_gpu.h, RSCM_MODE_FAST).
 __device__ __forceinline__ void rhs_fast(const TLFast& p, double erf_cs, double ts, double w, double& dts, double& dw)
 {
     const double q = __builtin_fma(p.a, ts, -p.l0);   // -(lambda0 - a Ts)/Cs

@@ -20,7 +20,11 @@ Parity bars (stated here, as the task requires):
     status bytes only in the fuzz and only under the mask).  The EXACT arithmetic itself -- speculative
     year == replayed year == the reference's expression order, every member, every series, the status
     byte -- is held bit for bit in tests/test_gpu_coupled_bits.py, against a host restatement that takes
-    the two transcendental values per member-year from the device.
+    the two transcendental values per member-year from the device.  The FAST arithmetic of the two-layer kind,
+    the coupled chain and CarbonCycle -- every stage FMA, the combination's association, w = Ts - Td, NaN / inf
+    placement and the status byte of every member, bounded or not -- is held the same way in
+    tests/test_gpu_fast_bits.py against tests/host_fast.py, which tests/test_host_fast.py holds to the oracle at
+    this file's FAST_RTOL under this file's `_bounded` mask.
   * which kinds have a FAST arithmetic at all: two-layer, coupled, CarbonCycle, ClimateUDEB, OceanCarbon
     (include/rscm_gpu.h, RSCM_MODE_FAST); for every other kind the mode is accepted and changes nothing.
   * integer/index work (time indexing, scenario selection, status flags, LHS strata): exact.
