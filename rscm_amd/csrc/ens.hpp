@@ -412,6 +412,22 @@ int check_member_vector(const rscm_ens* h, const double* p, const char* what);
 // RSCM_OK if p is device memory on h's device holding at least n int64 from p on, else RSCM_ERR_INVALID: the `out` of the moment sums
 // when it is on the device (moments_host.cpp)
 int check_device_out(const rscm_ens* h, const int64_t* p, size_t n);
+// What rscm_ens_moment_sums and rscm_ens_moment_rows_sums share besides (moments_host.cpp).  Their refusals, in this order: flags
+// outside `allowed`, the order, order 2 without a centre, the vector list, a NULL out, a flag whose member weights, groups or
+// baseline the handle lacks, 2^31 members or more; then, on the handle's device, check_member_vector of every vector
+int check_moment_call(const rscm_ens* h, int32_t flags, int32_t allowed, int32_t order, const double* center, int32_t n_vec,
+                      const double* const* vec_dev, int32_t min_vec, int32_t max_vec, const int64_t* out);
+int check_member_vectors(const rscm_ens* h, int32_t n_vec, const double* const* vec_dev);
+// The centre on the device, enqueued on the handle's stream (none, for order 1: nothing): n records of `width` doubles, a record with a
+// non-finite entry all NaN, so that every term about it is counted as non-finite.  c, the host copy, lives until the stream is synchronised
+int upload_moment_centre(rscm_ens* h, const double* center, size_t n, size_t width, std::vector<double>& c, rscm::DevBuf<double>& d_centre);
+// The device array of `total` int64 the sums land in, zeroed on the handle's stream: the caller's `out` when it is on the device
+// (check_device_out first), else the temporary, which end_moment_out copies to `out` before it ends the call with its one synchronise
+int begin_moment_out(rscm_ens* h, int64_t* out, size_t total, int32_t on_device, rscm::DevBuf<unsigned long long>& d_tmp,
+                     unsigned long long** d_out);
+int end_moment_out(rscm_ens* h, int64_t* out, const unsigned long long* d_out, size_t total, int32_t on_device);
+// sums [RG][2 + B * 69] (n, W, B blocks) as out[RG][B], every block over its record's W, and n[RG], weight[RG] unless NULL
+int finish_moment_sums(const int64_t* sums, size_t RG, int32_t B, double* out, int64_t* n, int64_t* weight);
 // issue what a WindowDeferral holds on `stream` and make the new windows current (window_host.cpp)
 int window_flush(WindowDeferral* d, hipStream_t stream);
 // the handle's own window (window_host.cpp)

@@ -1,7 +1,7 @@
 // Exact weighted first and second moments of STORED ROWS across the members of an ensemble, for gfx950 (MI355X): the integer sums
 // behind rscm_ens_moment_rows_sums (the definition is stated in include/rscm_gpu.h).  The limb scheme is that of moments.hip -- a
-// sum is a block of 68 signed int64 limbs and a count of non-finite terms, a term w * mantissa is placed by the exponent -- and the
-// pure integer pieces are in moment_window.hpp, which a host compiler builds alone.
+// sum is a block of 68 signed int64 limbs and a count of non-finite terms, a term w * mantissa is placed by the exponent -- and both
+// share the pure integer pieces (moment_window.hpp, which a host compiler builds alone) and the wave helpers (moment_wave.hpp).
 //
 // One launch per order for all rows.  Grid: x over member tiles (grid-stride, capped at kMomRowBlocks blocks of four waves), y over
 // rows (a block works on one row at a time and strides over rows beyond 65535), z over chunks of member groups that fit the block's
@@ -21,7 +21,7 @@
 // settles its slots (mom_window_settle), the wave sums each of the eight slots over its lanes -- a butterfly that halves the slots
 // a lane carries at each of the first three steps, ten 64-bit exchanges instead of 48 -- and eight lanes add the eight sums to the
 // block's LDS bins at limbs base .. base + 7.  Terms below the window take the serial walk of moments.hip: the term becomes
-// wave-uniform (v_readlane, scalar shifts) and lanes 0 .. 4 add its five digits to the LDS bins.  Every digit of every term is
+// wave-uniform (moment_wave.hpp; scalar shifts) and lanes 0 .. 4 add its five digits to the LDS bins.  Every digit of every term is
 // added to its limb exactly once by integer adds, whichever path it took, so the canonical value does not depend on the path.
 // Overflow: see moment_window.hpp; a bin takes fewer than 2^31 digits below 2^32 in magnitude (N < 2^31), as in moments.hip.
 //
@@ -34,6 +34,7 @@
 // window, the terms that were walked, the rebases (moves of a window that had a base).
 #include <hip/hip_runtime.h>
 
+#include "moment_wave.hpp"
 #include "moment_window.hpp"
 #include "moments_finish.hpp"
 #include "rscm_device.hpp"
@@ -48,12 +49,6 @@ static_assert(kMomRowBlocks * kMomRowWaves * 64 == kMomentRowsMembersPerPass, "r
 
 __device__ __forceinline__ unsigned long long mr_xor(unsigned long long v, int off) { return __shfl_xor(v, off, 64); }
 
-__device__ __forceinline__ unsigned long long mr_wave_sum(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += mr_xor(v, off);
-    return v;
-}
-
 __device__ __forceinline__ int mr_wave_max(int v)
 {
     for (int off = 32; off > 0; off >>= 1) {
@@ -62,8 +57,6 @@ __device__ __forceinline__ int mr_wave_max(int v)
     }
     return __builtin_amdgcn_readfirstlane(v);
 }
-
-__device__ __forceinline__ uint32_t mr_readlane(uint32_t v, int j) { return (uint32_t)__builtin_amdgcn_readlane((int)v, j); }
 
 // The sum over the 64 lanes of each of the eight slots: afterwards lane l with (l & 7) == 0 holds the sum of slot l >> 3
 __device__ __forceinline__ unsigned long long mr_fold_slots(const uint64_t (&win)[kMomWin], int lane)
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(kMomRowThreads) void moment_rows_kernel(MomentRowsA
                 if (lane == 0 && n_bad[s]) atomicAdd(&bin[2 + s * kMomentBlock + kMomentLimbs], (unsigned long long)n_bad[s]);
                 n_bad[s] = 0u;
             }
-            const unsigned long long wsum = mr_wave_sum(acc_w);
+            const unsigned long long wsum = mom_wave_sum(acc_w);
             if (lane == 0) {
                 if (cnt) atomicAdd(&bin[0], (unsigned long long)cnt);
                 if (wsum) atomicAdd(&bin[1], wsum);
@@ -170,7 +163,7 @@ __global__ __launch_bounds__(kMomRowThreads) void moment_rows_kernel(MomentRowsA
                 unsigned long long sel = rem;
                 int32_t gj = 0;
                 if (grouped) {
-                    gj = (int32_t)mr_readlane((uint32_t)g, __ffsll(rem) - 1);
+                    gj = (int32_t)mom_readlane((uint32_t)g, __ffsll(rem) - 1);
                     sel = __ballot(ok && g == gj);
                 }
                 rem &= ~sel;
@@ -221,15 +214,14 @@ __global__ __launch_bounds__(kMomRowThreads) void moment_rows_kernel(MomentRowsA
                     st_walk += (unsigned int)__popcll(walk);
                     if (walk == 0ull) return;
                     // the serial walk: the term becomes wave-uniform and lanes 0 .. 4 add its digits to the bins
-                    const uint32_t lo0 = (uint32_t)lo, lo1 = (uint32_t)(lo >> 32), hi0 = (uint32_t)hi, hi1 = (uint32_t)(hi >> 32);
-                    const uint32_t info = pos | (neg << 12);
+                    const MomLaneTerm term = mom_lane_term(lo, hi, pos | (neg << 12));
                     unsigned long long* bin = mr_bins + (cur - g0) * kStride + 2 + s * kMomentBlock;
                     while (walk) {
                         const int j = __ffsll(walk) - 1;
                         walk &= walk - 1ull;
-                        const uint32_t inf = mr_readlane(info, j);
-                        const uint64_t plo = (uint64_t)mr_readlane(lo0, j) | ((uint64_t)mr_readlane(lo1, j) << 32);
-                        const uint64_t phi = (uint64_t)mr_readlane(hi0, j) | ((uint64_t)mr_readlane(hi1, j) << 32);
+                        const uint32_t inf = mom_uniform_info(term, j);
+                        uint64_t plo, phi;
+                        mom_uniform_product(term, j, plo, phi);
                         uint32_t dj[5];
                         mom_digits(plo, phi, inf & 31u, dj);
                         const int qj = (int)((inf & 0xFFFu) >> 5);

@@ -6,9 +6,6 @@
 // [rows][G][2 + blocks * 69], the caller's if it is on the device, else a temporary that is copied out; rows beyond the time index
 // stay zero.  Every temporary is a DevBuf, everything runs on the handle's stream, and one synchronise ends the call.
 #include <algorithm>
-#include <cmath>
-#include <cstdio>
-#include <limits>
 #include <vector>
 
 #include "ens.hpp"
@@ -23,20 +20,11 @@ thread_local int64_t t_last_stats[3] = {0, 0, 0};   // window terms, walked term
 int moment_rows_sums(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_vec, const double* const* vec_dev,
                      int32_t flags, int32_t order, const double* center, int64_t* out, int32_t on_device)
 {
-    if (flags & ~(RSCM_SELECT_WEIGHTED | RSCM_SELECT_ANOMALY | RSCM_SELECT_GROUPED))
-        return fail(RSCM_ERR_INVALID, "unknown moment flags 0x%x", flags);
-    if (order != 1 && order != 2) return fail(RSCM_ERR_INVALID, "order %d: must be 1 or 2", order);
-    if (order == 2 && !center) return fail(RSCM_ERR_INVALID, "order 2 needs a centre");
-    if (n_vec < 0 || n_vec > RSCM_MOMENT_ROWS_MAX_VECTORS || (n_vec > 0 && !vec_dev))
-        return fail(RSCM_ERR_INVALID, "bad vector list (0 to %d vectors)", RSCM_MOMENT_ROWS_MAX_VECTORS);
-    if (!out) return fail(RSCM_ERR_INVALID, "out is NULL");
+    if (int rc = check_moment_call(h, flags, RSCM_SELECT_WEIGHTED | RSCM_SELECT_ANOMALY | RSCM_SELECT_GROUPED, order, center, n_vec, vec_dev, 0,
+                                   RSCM_MOMENT_ROWS_MAX_VECTORS, out))
+        return rc;
     const bool weighted = (flags & RSCM_SELECT_WEIGHTED) != 0, grouped = (flags & RSCM_SELECT_GROUPED) != 0;
     const bool anomaly = (flags & RSCM_SELECT_ANOMALY) != 0;
-    if (weighted && !h->d_weights)
-        return fail(RSCM_ERR_STATE, "no member weights: rscm_ens_set_member_weights or rscm_ens_set_weights_from_loglik first");
-    if (grouped && !h->d_groups) return fail(RSCM_ERR_STATE, "no member groups: rscm_ens_set_member_groups first");
-    if (anomaly && !h->d_base) return fail(RSCM_ERR_STATE, "no baseline: rscm_ens_set_baseline or rscm_ens_set_baseline_values first");
-    if ((int64_t)h->N >= rscm::kMomentMaxTerms) return fail(RSCM_ERR_INVALID, "moments take fewer than 2^31 members per handle");
     if (int rc = no_select(h)) return rc;
     if (int rc = check_row_range(h, var_id, t_begin, t_end, t_stride, false)) return rc;
     if (int rc = check_series_stored(h, t_end)) return rc;
@@ -45,14 +33,9 @@ int moment_rows_sums(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end
     if (n_range * G * B > RSCM_MOMENT_ROWS_MAX_BLOCKS)
         return fail(RSCM_ERR_INVALID, "%lld rows x %d groups x %d blocks: more than %d blocks in one call", (long long)n_range, G, B,
                     RSCM_MOMENT_ROWS_MAX_BLOCKS);
-    if (int rc = set_device(h)) return rc;
     rscm::MomentRowsArgs a{};
-    for (int32_t k = 0; k < n_vec; ++k) {
-        char what[24];
-        std::snprintf(what, sizeof what, "vector %d", k);
-        if (int rc = check_member_vector(h, vec_dev[k], what)) return rc;
-        a.vec[k] = vec_dev[k];
-    }
+    if (int rc = check_member_vectors(h, n_vec, vec_dev)) return rc;
+    std::copy(vec_dev, vec_dev + n_vec, a.vec);
     const size_t stride = 2 + (size_t)B * rscm::kMomentBlock, total = (size_t)n_range * G * stride;
     if (on_device && total)
         if (int rc = check_device_out(h, out, total)) return rc;
@@ -67,26 +50,12 @@ int moment_rows_sums(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end
     rscm::DevBuf<unsigned long long> d_tmp, d_stats;
     std::vector<double> c;
     unsigned long long stats[3] = {0ull, 0ull, 0ull};
-    unsigned long long* d_out = reinterpret_cast<unsigned long long*>(out);
-    if (!on_device) {
-        HIPCHK(d_tmp.alloc(total));
-        d_out = d_tmp.get();
-    }
-    HIPCHK(hipMemsetAsync(d_out, 0, total * sizeof(int64_t), h->stream));
+    unsigned long long* d_out = nullptr;
+    if (int rc = begin_moment_out(h, out, total, on_device, d_tmp, &d_out)) return rc;
     if (!rows.empty()) {   // the computed rows come first: resolve_rows leaves out the rows beyond the time index
         if (int rc = upload_rows(h, rows, d_rows)) return rc;
-        const size_t C = 1 + (size_t)n_vec;
-        if (order == 2) {
-            // a (row, group) with a non-finite centre: every term of every block is counted as non-finite (NaN centres do that in the kernel)
-            c.assign(center, center + rows.size() * G * C);
-            for (size_t rg = 0; rg < rows.size() * G; ++rg) {
-                bool finite = true;
-                for (size_t k = 0; k < C; ++k) finite = finite && std::isfinite(c[rg * C + k]);
-                if (!finite) std::fill(c.begin() + rg * C, c.begin() + (rg + 1) * C, std::numeric_limits<double>::quiet_NaN());
-            }
-            HIPCHK(d_centre.alloc(c.size()));
-            HIPCHK(hipMemcpyAsync(d_centre.get(), c.data(), c.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
-        }
+        // one record per computed (row, group)
+        if (int rc = upload_moment_centre(h, order == 2 ? center : nullptr, rows.size() * G, 1 + (size_t)n_vec, c, d_centre)) return rc;
         HIPCHK(d_stats.alloc(3));
         HIPCHK(hipMemsetAsync(d_stats.get(), 0, sizeof stats, h->stream));
         a.rows = d_rows.get();
@@ -102,8 +71,7 @@ int moment_rows_sums(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end
         HIPCHK(rscm::launch_moment_rows(a, n_vec, order, h->stream));
         HIPCHK(hipMemcpyAsync(stats, d_stats.get(), sizeof stats, hipMemcpyDeviceToHost, h->stream));
     }
-    if (!on_device) HIPCHK(hipMemcpyAsync(out, d_out, total * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));   // the temporaries and the host copies above go out of scope
+    if (int rc = end_moment_out(h, out, d_out, total, on_device)) return rc;
     for (int k = 0; k < 3; ++k) t_last_stats[k] = (int64_t)stats[k];
     return RSCM_OK;
 }
@@ -135,23 +103,11 @@ int rscm_ens_moment_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t
                       ((flags & RSCM_SELECT_GROUPED) && h->d_groups ? (size_t)h->n_groups : 1);
     if ((int64_t)RG * B2 > RSCM_MOMENT_ROWS_MAX_BLOCKS)
         return fail(RSCM_ERR_INVALID, "%zu rows x groups x %d blocks: more than %d blocks in one call", RG, B2, RSCM_MOMENT_ROWS_MAX_BLOCKS);
-    const size_t s1 = 2 + (size_t)B1 * rscm::kMomentBlock, s2 = 2 + (size_t)B2 * rscm::kMomentBlock;
-    std::vector<int64_t> sums(std::max<size_t>(RG * s2, 1)), div((size_t)B2);   // (an empty range still passes a buffer)
-    auto finish_all = [&](size_t stride, int32_t B, double* dst) {
-        for (size_t rg = 0; rg < RG; ++rg) {
-            const int64_t* row = &sums[rg * stride];
-            std::fill(div.begin(), div.end(), row[1]);
-            if (rscm::moment_finish(row + 2, B, div.data(), row[0], dst + rg * B))
-                return fail(RSCM_ERR_INVALID, "moment finish: %lld counted members are outside [0, 2^31)", (long long)row[0]);
-            if (n) n[rg] = row[0];
-            if (weight) weight[rg] = row[1];
-        }
-        return (int)RSCM_OK;
-    };
+    std::vector<int64_t> sums(std::max<size_t>(RG * (2 + (size_t)B2 * rscm::kMomentBlock), 1));   // (an empty range still passes a buffer)
     if (int rc = moment_rows_sums(h, var_id, t_begin, t_end, t_stride, n_vec, vec_dev, flags, 1, nullptr, sums.data(), 0)) return rc;
-    if (int rc = finish_all(s1, B1, mean)) return rc;
+    if (int rc = finish_moment_sums(sums.data(), RG, B1, mean, n, weight)) return rc;
     if (int rc = moment_rows_sums(h, var_id, t_begin, t_end, t_stride, n_vec, vec_dev, flags, 2, mean, sums.data(), 0)) return rc;
-    return finish_all(s2, B2, second);
+    return finish_moment_sums(sums.data(), RG, B2, second, n, weight);
     GUARD_END
 }
 

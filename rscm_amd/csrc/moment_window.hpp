@@ -1,7 +1,7 @@
 // The pure integer pieces of the moments of stored rows (moment_rows.hip; the definition is stated in include/rscm_gpu.h,
 // rscm_ens_moment_rows_sums): a term as five 32-bit digits, a lane's private window of kMomWin limbs, and the fold of a window into
 // the 68-limb block of moments_finish.hpp.  No HIP and no floating point: a host compiler builds it alone
-// (tests/c_abi/moment_window_host.cpp), and the kernel includes the very same functions.
+// (tests/c_abi/moment_window_host.cpp), and the kernels include the very same functions (moments.hip those of the term alone).
 //
 // The window.  A term w * mantissa << pos (at most 106 + 31 bits above the limb boundary below pos) is five digits d_0 .. d_4, digit
 // k in limb q + k with q = pos >> 5.  A lane keeps kMomWin = 8 consecutive limbs, base .. base + 7, as uint64 registers; a term with

@@ -4,13 +4,14 @@
 // One sum -- S_a = sum w_i x_ia, or C_ab = sum w_i ((x_ia - c_a)(x_ib - c_b)) -- is a block of 68 signed int64 limbs, limb k in units
 // of 2^(32 k - 1088), and a count of non-finite terms.  A term is the integer w * mantissa (at most 106 bits) placed at the bit the
 // double's exponent names, cut into 32-bit digits at limb boundaries; every digit is added, with the term's sign, into its limb.
-// Integer adds: exact, and the order does not matter.
+// Integer adds: exact, and the order does not matter.  moment_rows.hip uses the same term, so it is stated once: its fields, product
+// and digits in moment_window.hpp (a host program checks them), the wave sum and the wave-uniform read of a term in moment_wave.hpp.
 //
 // moment_mask_kernel: per tile of 64 members one uint64 of the members that count (in a group, all n_vec values finite: listwise), and
 // the counts n and weight sums W per group, as exceedance_grouped_kernel forms its totals.
 // moment_sum_kernel: grid x over tiles (grid-stride, capped at kMomBlocks blocks of kMomWaves waves), y over the sums.  A wave loads a
 // tile, one member per lane, and each lane forms its own member's term: sign, bit position, the 128-bit product.  Then the wave
-// walks the members that have one: the term becomes wave-uniform (v_readlane, scalar shifts into five 32-bit digits) and LANE l
+// walks the members that have one: the term becomes wave-uniform (moment_wave.hpp; scalar shifts into five 32-bit digits) and LANE l
 // adds the digit that falls into LIMB l to a private int64 register -- no atomics, no conflicts.  Limbs 64 .. 67 (a second
 // register of lanes 0 .. 3) sit behind a wave-uniform branch that only terms of 2^959 and beyond take.  The registers hold the sums
 // of one member group and are flushed into the block's LDS bins [G][69] when the walked member's group differs, and at the end;
@@ -18,6 +19,8 @@
 // refuses N >= 2^31), so no register, bin or result limb wraps.
 #include <hip/hip_runtime.h>
 
+#include "moment_wave.hpp"
+#include "moment_window.hpp"
 #include "moments_finish.hpp"
 #include "rscm_device.hpp"
 
@@ -27,17 +30,6 @@ namespace {
 constexpr int kMomThreads = 256;
 constexpr int kMomWaves = kMomThreads / 64;
 static_assert(kMomBlocks * kMomWaves * 64 == kMomentMembersPerPass, "rscm_device.hpp states the members of one pass of the grid");
-
-__device__ __forceinline__ unsigned long long mom_wave_sum(unsigned long long v)
-{
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ bool mom_finite(double x)
-{
-    return (((unsigned long long)__double_as_longlong(x) >> 52) & 0x7FFull) != 0x7FFull;
-}
 
 template <bool kW, bool kG>
 __global__ __launch_bounds__(kMomThreads) void moment_mask_kernel(const double* const* __restrict__ vec, int32_t n_vec,
@@ -69,7 +61,7 @@ __global__ __launch_bounds__(kMomThreads) void moment_mask_kernel(const double* 
         }
         for (int32_t k = 0; k < n_vec; ++k) {
             const double* __restrict__ v = vec[k];
-            if (ok) ok = mom_finite(v[i]);
+            if (ok) ok = mom_finite_bits((uint64_t)__double_as_longlong(v[i]));
         }
         const unsigned long long m = __ballot(ok);
         if (lane == 0) mask[t] = m;
@@ -96,11 +88,6 @@ __global__ __launch_bounds__(kMomThreads) void moment_mask_kernel(const double* 
     __syncthreads();
     for (int32_t i = (int32_t)threadIdx.x; i < n_groups * 2; i += kMomThreads)
         if (bins[i]) atomicAdd(&out[(int64_t)(i >> 1) * out_stride + (i & 1)], bins[i]);
-}
-
-__device__ __forceinline__ uint32_t mom_readlane(uint32_t v, int j)
-{
-    return (uint32_t)__builtin_amdgcn_readlane((int)v, j);
 }
 
 // kOrder 1: the terms are x_a; 2: (x_a - c[g][a]) * (x_b - c[g][b]) for the pair (a, b) that blockIdx.y names
@@ -161,20 +148,18 @@ __global__ __launch_bounds__(kMomThreads) void moment_sum_kernel(const double* c
                 p = __dmul_rn(da, db);
             }
         }
-        const unsigned long long bits = (unsigned long long)__double_as_longlong(p);
-        const uint32_t e = (uint32_t)(bits >> 52) & 0x7FFu;
-        const unsigned long long frac = bits & ((1ull << 52) - 1ull);
-        const unsigned long long mant = e ? (frac | (1ull << 52)) : frac;
-        const unsigned long long lo = wt * mant, hi = __umul64hi(wt, mant);
-        // bit position (12 bits: at most 2046 + 13), sign, group
-        const uint32_t info = ((e ? e : 1u) + 13u) | ((uint32_t)(bits >> 63) << 12) | ((uint32_t)g << 13);
-        const unsigned long long bad = __ballot(in && e == 0x7FFu);
-        unsigned long long walk = __ballot(in && e != 0x7FFu && (lo | hi) != 0ull) | bad;
-        const uint32_t lo0 = (uint32_t)lo, lo1 = (uint32_t)(lo >> 32), hi0 = (uint32_t)hi, hi1 = (uint32_t)(hi >> 32);
+        uint64_t mant, lo, hi;
+        uint32_t pos, neg;
+        const bool finite = mom_fields((uint64_t)__double_as_longlong(p), mant, pos, neg);
+        mom_product(wt, mant, lo, hi);
+        const unsigned long long bad = __ballot(in && !finite);
+        unsigned long long walk = __ballot(in && finite && (lo | hi) != 0ull) | bad;
+        // info = bit position (12 bits: at most 2046 + 13) | sign << 12 | group << 13
+        const MomLaneTerm term = mom_lane_term(lo, hi, pos | (neg << 12) | ((uint32_t)g << 13));
         while (walk) {
             const int j = __ffsll(walk) - 1;
             walk &= walk - 1ull;
-            const uint32_t inf = mom_readlane(info, j);
+            const uint32_t inf = mom_uniform_info(term, j);
             if (kG) {
                 const int32_t gj = (int32_t)(inf >> 13);
                 if (gj != cur) {
@@ -186,22 +171,16 @@ __global__ __launch_bounds__(kMomThreads) void moment_sum_kernel(const double* c
                 ++n_bad;
                 continue;
             }
-            const unsigned long long plo = (unsigned long long)mom_readlane(lo0, j) | ((unsigned long long)mom_readlane(lo1, j) << 32);
-            const unsigned long long phi = (unsigned long long)mom_readlane(hi0, j) | ((unsigned long long)mom_readlane(hi1, j) << 32);
-            const uint32_t pos = inf & 0xFFFu;
-            const int q = (int)(pos >> 5);
-            const uint32_t r = pos & 31u;
-            // (phi : plo) << r, at most 137 bits, as five digits: digit k falls into limb q + k
-            const unsigned long long s0 = plo << r;
-            const unsigned long long s1 = (phi << r) | (r ? plo >> (64u - r) : 0ull);
-            const unsigned long long s2 = r ? phi >> (64u - r) : 0ull;
-            const uint32_t d0 = (uint32_t)s0, d1 = (uint32_t)(s0 >> 32), d2 = (uint32_t)s1, d3 = (uint32_t)(s1 >> 32), d4 = (uint32_t)s2;
-            const bool neg = (inf >> 12) & 1u;
-            const long long sign = -(long long)neg;   // 0 or -1, wave-uniform
+            const int q = (int)((inf & 0xFFFu) >> 5);
+            uint64_t plo, phi;
+            uint32_t d[5];   // digit k falls into limb q + k
+            mom_uniform_product(term, j, plo, phi);
+            mom_digits(plo, phi, inf & 31u, d);
+            const long long sign = -(long long)((inf >> 12) & 1u);   // 0 or -1, wave-uniform
             // five independent selects and a conditional negation: no branch per lane
             auto digit = [&](int k) -> long long {
-                const uint32_t d = (k == 0 ? d0 : 0u) | (k == 1 ? d1 : 0u) | (k == 2 ? d2 : 0u) | (k == 3 ? d3 : 0u) | (k == 4 ? d4 : 0u);
-                return ((long long)d ^ sign) - sign;
+                const uint32_t mine = (k == 0 ? d[0] : 0u) | (k == 1 ? d[1] : 0u) | (k == 2 ? d[2] : 0u) | (k == 3 ? d[3] : 0u) | (k == 4 ? d[4] : 0u);
+                return ((long long)mine ^ sign) - sign;
             };
             acc += digit(lane - q);
             if (q + 4 >= 64) acc_hi += digit(64 + lane - q);   // lanes beyond 3 hold no limb there: never flushed

@@ -204,6 +204,19 @@ def quantile_vectors_global(ensemble, vectors, q, group=None, weighted: bool = F
     return _reduce_select(ensemble.select_vectors(vectors, q, weighted=weighted, **kw), group)
 
 
+def _all_reduce_sum(a, group=None) -> np.ndarray:
+    """The int64 array ``a`` summed element by element over the ranks (exact and independent of order); single process: ``a``.
+    With ``gloo`` the array passes through the host."""
+    a = np.ascontiguousarray(a, dtype=np.int64)
+    if not is_distributed():
+        return a
+    import torch
+    d = _dist()
+    t = torch.from_numpy(a.copy()).to(_device_for_backend())
+    d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
+    return t.cpu().numpy()
+
+
 def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
     """``Ensemble.exceedance`` of the WHOLE sharded ensemble on every rank: the ranks' int64 hits and totals are SUM-reduced
     (exact and independent of order), then ``probability = hits / total``.  ``grouped``: per member group, ``[G][k] + [G]`` int64
@@ -212,18 +225,20 @@ def exceedance_global(ensemble, vector, thresholds, group=None, weighted: bool =
     local = ensemble.exceedance(vector, thresholds, weighted=weighted, **({"grouped": True} if grouped else {}))
     if not is_distributed():
         return local
-    import torch
-    d = _dist()
+    hits = np.asarray(local["hits"], dtype=np.int64)
+    acc = _all_reduce_sum(np.append(hits.ravel(), np.asarray(local["total"], dtype=np.int64)), group)   # [G][k] + [G], or [k] + 1
     if grouped:
-        hits = np.asarray(local["hits"], dtype=np.int64)
-        t = torch.from_numpy(np.concatenate([hits.ravel(), np.asarray(local["total"], dtype=np.int64)])).to(_device_for_backend())
-        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
-        acc = t.cpu().numpy()
         return exceedance_grouped_result(acc[:hits.size].reshape(hits.shape), acc[hits.size:])
-    t = torch.from_numpy(np.append(np.asarray(local["hits"], dtype=np.int64), np.int64(local["total"]))).to(_device_for_backend())
-    d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
-    acc = t.cpu().numpy()
     return exceedance_result(acc[:-1], int(acc[-1]))
+
+
+def _moments_reduced(sums, means, result, K: int, group, grouped: bool):
+    """The two collectives of the global moments: ``sums(order, center)`` of order 1 are reduced and finished into the means, the
+    sums of order 2 about them are reduced, and ``result`` finishes both.  G is the axis before the last of the sums."""
+    sums1 = _all_reduce_sum(sums(1, None), group)
+    G = sums1.shape[-2]
+    sums2 = _all_reduce_sum(sums(2, means(sums1, K, G)), group)
+    return result(sums1, sums2, K, G, grouped=grouped)
 
 
 def moments_global(ensemble, vectors, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
@@ -235,24 +250,9 @@ def moments_global(ensemble, vectors, group=None, weighted: bool = False, groupe
     the same ``n_groups`` on every rank.  Fewer than 2^31 members may count over all ranks."""
     from .ensemble import moment_means, moments_result
     vs = list(vectors)
-    K = len(vs)
     kw = {"grouped": True} if grouped else {}
-
-    def reduced(a):
-        a = np.ascontiguousarray(a, dtype=np.int64)
-        if not is_distributed():
-            return a
-        import torch
-        d = _dist()
-        t = torch.from_numpy(a.copy()).to(_device_for_backend())
-        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
-        return t.cpu().numpy()
-
-    sums1 = reduced(ensemble.moment_sums(vs, 1, weighted=weighted, **kw))
-    G = sums1.shape[0]
-    mean = moment_means(sums1, K, G)
-    sums2 = reduced(ensemble.moment_sums(vs, 2, center=mean, weighted=weighted, **kw))
-    return moments_result(sums1, sums2, K, G, grouped=grouped)
+    return _moments_reduced(lambda order, center: ensemble.moment_sums(vs, order, center=center, weighted=weighted, **kw),
+                            moment_means, moments_result, len(vs), group, grouped)
 
 
 def moment_rows_global(ensemble, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, vectors=(), group=None,
@@ -265,7 +265,6 @@ def moment_rows_global(ensemble, var, t_begin: int = 0, t_end: Optional[int] = N
     Fewer than 2^31 members may count in a row over all ranks."""
     from .ensemble import moment_rows_means, moment_rows_result
     vs = list(vectors)
-    K = len(vs)
     kw = {}
     if weighted:
         kw["weighted"] = True
@@ -273,22 +272,8 @@ def moment_rows_global(ensemble, var, t_begin: int = 0, t_end: Optional[int] = N
         kw["anomaly"] = True
     if grouped:
         kw["grouped"] = True
-
-    def reduced(a):
-        a = np.ascontiguousarray(a, dtype=np.int64)
-        if not is_distributed():
-            return a
-        import torch
-        d = _dist()
-        t = torch.from_numpy(a.copy()).to(_device_for_backend())
-        d.all_reduce(t, op=d.ReduceOp.SUM, group=group)
-        return t.cpu().numpy()
-
-    sums1 = reduced(ensemble.moment_rows_sums(var, 1, t_begin, t_end, t_stride, vectors=vs, **kw))
-    G = sums1.shape[1]
-    mean = moment_rows_means(sums1, K, G)
-    sums2 = reduced(ensemble.moment_rows_sums(var, 2, t_begin, t_end, t_stride, vectors=vs, center=mean, **kw))
-    return moment_rows_result(sums1, sums2, K, G, grouped=grouped)
+    return _moments_reduced(lambda order, center: ensemble.moment_rows_sums(var, order, t_begin, t_end, t_stride, vectors=vs, center=center, **kw),
+                            moment_rows_means, moment_rows_result, len(vs), group, grouped)
 
 
 def weights_stats_global(ensemble, group=None) -> Dict[str, object]:

@@ -978,17 +978,7 @@ class Ensemble:
         arr, n_vec = self._vectors(vectors)
         if not 1 <= n_vec <= L.MOMENT_MAX_VECTORS:
             raise ValueError(f"moments: 1 to {L.MOMENT_MAX_VECTORS} vectors, got {n_vec}")
-        if order not in (1, 2):
-            raise ValueError("moments: order must be 1 or 2")
-        G = self._n_groups(grouped)
-        c = None
-        if order == 2:
-            if center is None:
-                raise ValueError("moments: order 2 needs a center")
-            c = np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))
-            if c.size != G * n_vec:
-                raise ValueError(f"center: need {G} x {n_vec} values, got {c.size}")
-        out = np.zeros((G, 2 + moment_blocks(n_vec, order) * L.MOMENT_BLOCK), dtype=np.int64)
+        c, out = _moment_sums_args("moments", order, center, (self._n_groups(grouped), n_vec), moment_blocks(n_vec, order))
         L.check(self._lib.rscm_ens_moment_sums(self._h, n_vec, arr, select_flags(weighted, False, grouped), int(order),
                                                None if c is None else L.dptr(c), out.ctypes.data_as(C.POINTER(C.c_int64)), 0))
         return out
@@ -1028,17 +1018,7 @@ class Ensemble:
         w v_k; 2: B = 1 + 2 K, the sums of the products xx, x v_k, v_k v_k of the differences from ``center`` ``[rows][G][1 + K]``.
         G is 1 without ``grouped``.  The arrays of shards add up element by element; ``moment_rows_result`` finishes them."""
         vid, t_end, rows, arr, K = self._moment_rows_args(var, t_begin, t_end, t_stride, vectors)
-        if order not in (1, 2):
-            raise ValueError("moment_rows: order must be 1 or 2")
-        G = self._n_groups(grouped)
-        c = None
-        if order == 2:
-            if center is None:
-                raise ValueError("moment_rows: order 2 needs a center")
-            c = np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))
-            if c.size != rows * G * (1 + K):
-                raise ValueError(f"center: need {rows} x {G} x {1 + K} values, got {c.size}")
-        out = np.zeros((rows, G, 2 + moment_rows_blocks(K, order) * L.MOMENT_BLOCK), dtype=np.int64)
+        c, out = _moment_sums_args("moment_rows", order, center, (rows, self._n_groups(grouped), 1 + K), moment_rows_blocks(K, order))
         L.check(self._lib.rscm_ens_moment_rows_sums(self._h, vid, t_begin, t_end, t_stride, K, arr, select_flags(weighted, anomaly, grouped),
                                                     int(order), None if c is None else L.dptr(c), out.ctypes.data_as(C.POINTER(C.c_int64)), 0))
         return out
@@ -1264,10 +1244,35 @@ def moment_finish(blocks, divisor, n_terms: int) -> np.ndarray:
     return out
 
 
+def _moment_sums_args(what: str, order: int, center, center_shape, B: int):
+    """For ``Ensemble.moment_sums`` and ``Ensemble.moment_rows_sums``: the checked ``center`` ``[*leading][values per record]`` of
+    order 2 as a flat float64 array (``None`` at order 1), and the zeroed int64 output ``[*leading][2 + B * 69]``."""
+    if order not in (1, 2):
+        raise ValueError(f"{what}: order must be 1 or 2")
+    c = None
+    if order == 2:
+        if center is None:
+            raise ValueError(f"{what}: order 2 needs a center")
+        c = np.ascontiguousarray(np.asarray(center, dtype=np.float64).reshape(-1))
+        if c.size != int(np.prod(center_shape)):
+            raise ValueError(f"center: need {' x '.join(map(str, center_shape))} values, got {c.size}")
+    return c, np.zeros(tuple(center_shape[:-1]) + (2 + B * L.MOMENT_BLOCK,), dtype=np.int64)
+
+
+def _moment_sums_finish(sums, B: int, lead) -> np.ndarray:
+    """``[*lead][B]`` doubles from (reduced) sums ``[*lead][2 + B * 69]``: every block over its record's W, in one call of
+    rscm_gpu_moment_finish, which refuses a count outside [0, 2^31)."""
+    sums = np.asarray(sums, dtype=np.int64).reshape(*lead, 2 + B * L.MOMENT_BLOCK)
+    if sums.size == 0:
+        return np.empty(sums.shape[:-1] + (B,))
+    n = sums[..., 0]
+    out = moment_finish(sums[..., 2:], np.repeat(sums[..., 1].reshape(-1), B), int(n.min() if n.min() < 0 else n.max()))
+    return out.reshape(sums.shape[:-1] + (B,))
+
+
 def moment_means(sums1, K: int, G: int) -> np.ndarray:
     """``mean[G][K]`` from the (reduced) order-1 sums ``[G][2 + K * 69]`` of ``Ensemble.moment_sums``."""
-    sums1 = np.asarray(sums1, dtype=np.int64).reshape(G, 2 + K * L.MOMENT_BLOCK)
-    return np.stack([moment_finish(row[2:], row[1], row[0]) for row in sums1])
+    return _moment_sums_finish(sums1, K, (G,))
 
 
 def moments_dict(n, w, mean, cov, grouped: bool = True) -> Dict[str, np.ndarray]:
@@ -1294,14 +1299,12 @@ def moments_result(sums1, sums2, K: int, G: int, grouped: bool = True) -> Dict[s
     / 2 * 69]`` of order 2 about ``moment_means(sums1, K, G)`` -- through rscm_gpu_moment_finish and forms ``moments_dict``."""
     B = moment_blocks(K, 2)
     sums2 = np.asarray(sums2, dtype=np.int64).reshape(G, 2 + B * L.MOMENT_BLOCK)
-    mean = moment_means(sums1, K, G)
+    tri = _moment_sums_finish(sums2, B, (G,))
     cov = np.empty((G, K, K))
     iu = np.triu_indices(K)          # row-major upper triangle: (0,0), (0,1), ..., (0,K-1), (1,1), ...
-    for g, row in enumerate(sums2):
-        tri = moment_finish(row[2:], row[1], row[0])
-        cov[g][iu] = tri
-        cov[g][(iu[1], iu[0])] = tri
-    return moments_dict(sums2[:, 0], sums2[:, 1], mean, cov, grouped)
+    cov[:, iu[0], iu[1]] = tri
+    cov[:, iu[1], iu[0]] = tri
+    return moments_dict(sums2[:, 0], sums2[:, 1], moment_means(sums1, K, G), cov, grouped)
 
 
 def moment_rows_blocks(K: int, order: int) -> int:
@@ -1309,18 +1312,9 @@ def moment_rows_blocks(K: int, order: int) -> int:
     return 1 + K if order == 1 else 1 + 2 * K
 
 
-def _moment_rows_finish(sums, B: int, G: int) -> np.ndarray:
-    """``[rows][G][B]`` doubles from sums ``[rows][G][2 + B * 69]``: every block over its (row, group)'s W, in one call."""
-    sums = np.asarray(sums, dtype=np.int64).reshape(-1, G, 2 + B * L.MOMENT_BLOCK)
-    if sums.shape[0] == 0:
-        return np.empty((0, G, B))
-    out = moment_finish(sums[:, :, 2:], np.repeat(sums[:, :, 1].reshape(-1), B), int(sums[:, :, 0].max()))
-    return out.reshape(-1, G, B)
-
-
 def moment_rows_means(sums1, K: int, G: int) -> np.ndarray:
     """``mean[rows][G][1 + K]`` from the (reduced) order-1 sums of ``Ensemble.moment_rows_sums``: the centre of its order 2."""
-    return _moment_rows_finish(sums1, 1 + K, G)
+    return _moment_sums_finish(sums1, 1 + K, (-1, G))
 
 
 def moment_rows_dict(n, w, mean, second, grouped: bool = True) -> Dict[str, np.ndarray]:
@@ -1346,7 +1340,7 @@ def moment_rows_result(sums1, sums2, K: int, G: int, grouped: bool = True) -> Di
     ``sums2[rows][G][2 + (1 + 2 K) * 69]`` of order 2 about ``moment_rows_means(sums1, K, G)`` -- through rscm_gpu_moment_finish and
     forms ``moment_rows_dict``."""
     sums2 = np.asarray(sums2, dtype=np.int64).reshape(-1, G, 2 + (1 + 2 * K) * L.MOMENT_BLOCK)
-    return moment_rows_dict(sums2[:, :, 0], sums2[:, :, 1], moment_rows_means(sums1, K, G), _moment_rows_finish(sums2, 1 + 2 * K, G), grouped)
+    return moment_rows_dict(sums2[:, :, 0], sums2[:, :, 1], moment_rows_means(sums1, K, G), _moment_sums_finish(sums2, 1 + 2 * K, (-1, G)), grouped)
 
 
 def select_flags(weighted: bool, anomaly: bool, grouped: bool) -> int:
