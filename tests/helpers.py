@@ -50,16 +50,70 @@ def coupled_params(n, seed=SEED):
     return out
 
 
+def two_layer_noise_case(n, offset=0, n_total=None):
+    """(P [8][n], scenario [n]) of the noisy two-layer handles of the series, diagnostic and energy-budget files: the block
+    [offset, offset + n) of the draw of n_total members seeded by n_total -- the six two-layer rows, then the noise amplitude and
+    persistence rows -- with scenarios alternating 0, 1.  From 63 members on the last three of the draw are special: member
+    n_total - 3 is silent under zero forcing (sigma_i = 0 in scenario 0: a constant series), member n_total - 2 has the amplitude
+    1.7e308 (sigma_i z overflows) and member n_total - 1 has a NaN in parameter row 0."""
+    n_total = n if n_total is None else n_total
+    rng = np.random.default_rng(n_total)
+    P = np.vstack([two_layer_params(n_total), rng.uniform(0.1, 0.6, n_total), rng.uniform(0.0, 0.9, n_total)])
+    scen = (np.arange(n_total) % 2).astype(np.int32)
+    if n_total >= 63:
+        scen[n_total - 3], P[6, n_total - 3] = 0, 0.0
+        P[6, n_total - 2] = 1.7e308
+        P[0, n_total - 1] = np.nan
+    return np.ascontiguousarray(P[:, offset:offset + n]), np.ascontiguousarray(scen[offset:offset + n])
+
+
+def annual_bounds(T, start=1850):
+    """(YEARS [T], BOUNDS [T + 1]): an annual axis of T points from `start` and its time bounds."""
+    years = np.arange(start, start + T, dtype=np.float64)
+    return years, np.append(years, years[-1] + 1.0)
+
+
+def load_script(name, folder="scripts"):
+    """The module of <repository>/<folder>/<name>.py, executed afresh (folder "": bench.py, at the root)."""
+    import importlib.util
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location(name, os.path.join(root, folder, name + ".py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def magicc_chain():
+    return load_script("bench_magicc_chain")
+
+
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def same_values(a, b):
+    """Value equality of two arrays as float64: +0 equals -0 and any NaN equals any NaN; False on a shape mismatch.  Both sides are
+    converted to float64, so integers beyond 2^53 are not told apart: compare those with np.array_equal."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool(((a == b) | (np.isnan(a) & np.isnan(b))).all())
+
+
+def _bits_differ(a, b):
+    """Where two float64 arrays of one shape differ in their bits; any NaN == any NaN (payload bits are not part of the contract)."""
+    return (bits(a) != bits(b)).reshape(a.shape) & ~(np.isnan(a) & np.isnan(b))
+
+
+def same_bits(a, b):
+    """Bit equality of two arrays as float64: the sign of a zero counts and any NaN equals any NaN; False on a shape mismatch."""
+    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    return a.shape == b.shape and not bool(_bits_differ(a, b).any())
 
 
 def assert_bit_equal(a, b, what=""):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     assert a.shape == b.shape, (a.shape, b.shape)
-    bad = bits(a) != bits(b)
-    # any NaN == any NaN for parity purposes (payload bits are not part of the contract)
-    bad &= ~(np.isnan(a) & np.isnan(b))
+    bad = _bits_differ(a, b)
     if bad.any():
         idx = np.argwhere(bad)[0]
         raise AssertionError(f"{what}: {bad.sum()} of {bad.size} differ; first at {tuple(idx)}: "

@@ -4,6 +4,8 @@
 elementwise in float64, every product and sum one IEEE operation.  Nothing else."""
 import numpy as np
 
+from tests.helpers import two_layer_noise_case as two_layer_case  # noqa: F401  (the GPU file's two-layer handles)
+
 
 def weights(terms, P):
     """[K] weights, each [N] (or a scalar for a term without a parameter row); ``terms``: (source, param_row_or_None, scale)."""
@@ -36,22 +38,6 @@ def diagnostic_right_to_left(terms, sources, P):
 
 HEAT_CONTENT = [(1, 4, 1.0), (2, 5, 1.0)]    # C Ts + Cd Td of a two-layer handle: the GPU file's two-term case
 RANDOM_ROWS = (10, 11, 12)                   # the rows of that case that hold random_rows() instead of the run's values
-
-
-def two_layer_case(n, offset=0, n_total=None):
-    """(P [8][n], scenario [n]) of the GPU file's two-layer handles: the block [offset, offset + n) of the draw of n_total members,
-    the noise rows included.  From 63 members on the last three of the draw are special: a silent one under zero forcing (sigma_i
-    = 0: the weight -2.5 * sigma_i is -0.0), one whose amplitude overflows and one with a NaN parameter."""
-    from tests.helpers import two_layer_params
-    n_total = n if n_total is None else n_total
-    rng = np.random.default_rng(n_total)
-    P = np.vstack([two_layer_params(n_total), rng.uniform(0.1, 0.6, n_total), rng.uniform(0.0, 0.9, n_total)])
-    scen = (np.arange(n_total) % 2).astype(np.int32)
-    if n_total >= 63:
-        scen[n_total - 3], P[6, n_total - 3] = 0, 0.0
-        P[6, n_total - 2] = 1.7e308
-        P[0, n_total - 1] = np.nan
-    return np.ascontiguousarray(P[:, offset:offset + n]), np.ascontiguousarray(scen[offset:offset + n])
 
 
 def random_rows(n, offset=0, n_total=None):

@@ -458,7 +458,7 @@ def liveness(sp: Spec, V: List[np.ndarray], n: int = N_MEMBERS) -> np.ndarray:
     for c in range(len(sp.configs)):
         base = sp.run(block(sp, V[c], [], c), scen)
         for j in sp.free_rows():
-            live[c, j] = not np.array_equal(sp.run(block(sp, V[c], [j], c), scen), base, equal_nan=True)
+            live[c, j] = not helpers.same_values(sp.run(block(sp, V[c], [j], c), scen), base)
     return live
 
 

@@ -1,7 +1,7 @@
 """CPU tier of the covariability of two variables: ``rscm_amd.variability.series_covariability`` (what a user derives a record's
-targets with) against the numpy restatement of tests/host_covariability.py bit for bit over the nine mode pairs; the equalities
-the definition implies; the edges of the definition; data that tells a fused multiply-add from the definition; and the C boundary's
-text (rscm_ens_member_covariability)."""
+targets with) against the numpy restatement of tests/host_covariability.py value for value (+0 equal to -0, NaN to NaN) over the
+nine mode pairs; the equalities the definition implies; the edges of the definition; data that tells a fused multiply-add from the
+definition; and the C boundary's text (rscm_ens_member_covariability)."""
 import itertools
 import os
 import re
@@ -11,6 +11,7 @@ import pytest
 
 from tests import host_covariability as hc
 from tests import host_variability as hv
+from tests.helpers import same_values
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DETREND = ("mean", "linear", "difference")
@@ -35,10 +36,6 @@ def _terms(R, dx, dy):
     return R - (1 if "difference" in (dx, dy) else 0)
 
 
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
 @pytest.mark.parametrize("dx,dy", PAIRS)
 def test_series_covariability_equals_the_restatement(dx, dy):
     sc = _sc()
@@ -58,7 +55,7 @@ def test_series_covariability_equals_the_restatement(dx, dy):
             got, want = sc(x, y, dx, dy, lags), hc.covariability(x, y, dx, dy, lags)
             assert set(got) == set(hc.NAMES) | {"lead", "lag"} and len(got["lead"]) == len(got["lag"]) == lags
             for g, w in zip(hc.flat(got), hc.flat(want)):
-                assert g.shape == (23,) and _same(g, w), (dx, dy, R, lags)
+                assert g.shape == (23,) and same_values(g, w), (dx, dy, R, lags)
             for i in (4, 9):
                 assert all(np.isnan(g[i]) for g in hc.flat(got))
             assert got["var_x"][11] == 0.0 and np.isnan(got["corr"][11]) and np.isnan(got["slope"][11]) and all(np.isnan(g[11]) for g in got["lead"] + got["lag"])
@@ -66,29 +63,29 @@ def test_series_covariability_equals_the_restatement(dx, dy):
             assert all(np.isfinite(g[:4]).all() for g in hc.flat(got))
             one = sc(x[:, 2], y[:, 2], dx, dy, lags)                 # [R]: floats, the same bits
             for g, w in zip(hc.flat(one), hc.flat(want)):
-                assert isinstance(g, float) and _same(np.float64(g), w[2])
+                assert isinstance(g, float) and same_values(np.float64(g), w[2])
 
 
 @pytest.mark.parametrize("dx,dy", PAIRS)
 def test_exchange_and_variance_equalities(dx, dy):
-    """Exchanging the variables exchanges var_x with var_y and r_{+l} with r_{-l} and keeps cov and corr, bit for bit; with no mode
+    """Exchanging the variables exchanges var_x with var_y and r_{+l} with r_{-l} and keeps cov and corr, value for value; with no mode
     mixed var_x is the variance of the variability statistics."""
     for f in (_sc(), hc.covariability):
         for R in (4, 7, 40, 171):
             x, y = _rows(R, 64, seed=100 + R)
             lags = min(3, _terms(R, dx, dy) - 3)
             s, t = f(x, y, dx, dy, lags), f(y, x, dy, dx, lags)
-            assert _same(s["var_x"], t["var_y"]) and _same(s["var_y"], t["var_x"])
-            assert _same(s["cov"], t["cov"]) and _same(s["corr"], t["corr"])
+            assert same_values(s["var_x"], t["var_y"]) and same_values(s["var_y"], t["var_x"])
+            assert same_values(s["cov"], t["cov"]) and same_values(s["corr"], t["corr"])
             for l in range(lags):
-                assert _same(s["lead"][l], t["lag"][l]) and _same(s["lag"][l], t["lead"][l])
+                assert same_values(s["lead"][l], t["lag"][l]) and same_values(s["lag"][l], t["lead"][l])
             if (dx == "difference") == (dy == "difference"):
-                assert _same(s["var_x"], hv.variability(x, dx)["variance"]) and _same(s["var_y"], hv.variability(y, dy)["variance"])
+                assert same_values(s["var_x"], hv.variability(x, dx)["variance"]) and same_values(s["var_y"], hv.variability(y, dy)["variance"])
             same = f(x, x, dx, dx, lags)                             # a variable against itself
             ok = np.isfinite(same["corr"])
             assert ok.all() and np.abs(same["corr"] - 1.0).max() <= 4 * 2.0 ** -52 and np.abs(same["slope"] - 1.0).max() <= 4 * 2.0 ** -52
             for l in range(lags):
-                assert _same(same["lead"][l], same["lag"][l])
+                assert same_values(same["lead"][l], same["lag"][l])
 
 
 def test_correlations_are_bounded():
@@ -115,7 +112,7 @@ def test_a_fused_multiply_add_gives_other_bits():
     print("members whose bits differ under fused multiply-adds, of 4096:", differ)
     assert all(v > 0 for v in differ.values())
     got = _sc()(x, y, "mean", "mean", 1)
-    assert all(_same(g, w) for g, w in zip(hc.flat(got), hc.flat(plain)))
+    assert all(same_values(g, w) for g, w in zip(hc.flat(got), hc.flat(plain)))
 
 
 def test_midpoint_pairing():
@@ -128,7 +125,7 @@ def test_midpoint_pairing():
     for f in (_sc(), hc.covariability):
         s = f(x, y, "mean", "difference", 2)
         assert s["slope"][0] == 4.0 and abs(s["corr"][0] - 1.0) <= 2.0 ** -51
-        assert _same(s["var_x"], hv.variability(mid, "mean")["variance"])
+        assert same_values(s["var_x"], hv.variability(mid, "mean")["variance"])
         t = f(y, x, "difference", "mean", 2)
         assert t["var_y"][0] == s["var_x"][0] and t["slope"][0] == 0.25
 

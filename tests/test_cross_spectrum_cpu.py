@@ -1,8 +1,9 @@
 """CPU tier of the per-member co-spectra of two variables (include/rscm_gpu.h: rscm_ens_member_cross_spectrum,
 rscm_gpu_spectrum_sines): the sine table against a high-precision sine; ``rscm_amd.variability.series_cross_spectrum`` (what a user
-derives a record's targets with) against the numpy restatement of tests/host_cross_spectrum.py bit for bit; the band means against a
-direct cross-DFT in np.longdouble; the equalities the definition implies; the sign convention; data that tells a fused multiply-add
-from the definition; and the C boundary's text.  No GPU: the accessors are host code of the built library."""
+derives a record's targets with) against the numpy restatement of tests/host_cross_spectrum.py value for value (+0 equal to -0,
+NaN to NaN); the band means against a direct cross-DFT in np.longdouble; the equalities the definition implies; the sign
+convention; data that tells a fused multiply-add from the definition; and the C boundary's text.  No GPU: the accessors are host
+code of the built library."""
 import itertools
 import os
 import re
@@ -15,6 +16,7 @@ from tests import host_covariability as hc
 from tests import host_cross_spectrum as hx
 from tests import host_math as hm
 from tests import host_spectrum as hs
+from tests.helpers import same_values
 from tests.test_gpu_cross_spectrum import F           # the kernel's tile (kXSpecF of csrc/cross_spectrum.hip)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -26,10 +28,6 @@ TERMS = [3, 4, 5, 8, 9] + list(range(2 * F - 1, 2 * F + 5)) + [4 * F + 3, 4 * F 
 # What test_band_means_against_the_longdouble_cross_dft holds every band mean to, in units of sqrt(Pxx_b Pyy_b): the scale
 # tests/test_spectrum_cpu.py uses for band powers.  Measured worst over that test's cases: 9.7e-10 (n = 4096; 1.2e-11 at n = 750).
 DEVIATION = 1e-8
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
 
 
 def _rows(n, dx, dy):
@@ -95,7 +93,7 @@ def test_sines_within_one_ulp_and_refusals():
     for bad in (2, 0, -1, hs.MAX_TERMS + 1):
         assert lib.rscm_gpu_spectrum_sines(bad, _lib.dptr(buf)) == 1
     assert lib.rscm_gpu_spectrum_sines(8, None) == 1
-    assert _same(rv.spectrum_sines(170), tables[170])
+    assert same_values(rv.spectrum_sines(170), tables[170])
     with pytest.raises(_lib.RscmGpuError):
         rv.spectrum_sines(2)
     with pytest.raises(_lib.RscmGpuError):
@@ -120,7 +118,7 @@ def test_series_cross_spectrum_equals_the_restatement(dx, dy):
             assert len(got["coherence2"]) == len(got["gain"]) == len(got["gain_quad"]) == B
             assert list(got["edges"]) == [int(e) for e in edges] and list(got["counts"]) == list(np.diff(np.asarray(edges, dtype=np.int64)))
             for g, w in zip(hx.flat(got), hx.flat(want)):
-                assert g.shape == (N,) and _same(g, w), (dx, dy, n, list(edges))
+                assert g.shape == (N,) and same_values(g, w), (dx, dy, n, list(edges))
             for i in (4, 9):
                 assert all(np.isnan(g[i]) for g in hx.flat(got))
             assert got["var_x"][7] == 0.0 and got["var_y"][8] == 0.0
@@ -132,7 +130,7 @@ def test_series_cross_spectrum_equals_the_restatement(dx, dy):
         assert list(default["edges"]) == list(rv.band_edges(n, 3))
         one = rv.series_cross_spectrum(x[:, 2], y[:, 2], dx, dy)                                  # [R]: floats, the same bits
         for g, w in zip(hx.flat(one), hx.flat(default)):
-            assert isinstance(g, float) and _same(np.float64(g), w[2])
+            assert isinstance(g, float) and same_values(np.float64(g), w[2])
 
 
 # ---- the band means against the long-double cross-DFT ---------------------------------------------------------------------------------
@@ -164,7 +162,7 @@ def test_band_means_against_the_longdouble_cross_dft(n):
 
 def _neg_bits(a, b):
     """b is -a bit for bit (NaN against NaN)."""
-    return _same(a, -np.asarray(b)) and _same(np.signbit(a) | np.isnan(a), ~np.signbit(b) | np.isnan(b))
+    return same_values(a, -np.asarray(b)) and same_values(np.signbit(a) | np.isnan(a), ~np.signbit(b) | np.isnan(b))
 
 
 @pytest.mark.parametrize("dx,dy", PAIRS)
@@ -176,22 +174,22 @@ def test_equalities(dx, dy):
             edges = rv.band_edges(n, 3)
             s, t = f(x, y, dx, dy, edges), f(y, x, dy, dx, edges)
             cov = hc.covariability(x, y, dx, dy, 0)
-            assert _same(s["var_x"], cov["var_x"]) and _same(s["var_y"], cov["var_y"])
-            assert _same(s["var_x"], t["var_y"]) and _same(s["var_y"], t["var_x"])
+            assert same_values(s["var_x"], cov["var_x"]) and same_values(s["var_y"], cov["var_y"])
+            assert same_values(s["var_x"], t["var_y"]) and same_values(s["var_y"], t["var_x"])
             for b in range(len(edges) - 1):
-                assert _same(s["coherence2"][b], t["coherence2"][b])
+                assert same_values(s["coherence2"][b], t["coherence2"][b])
                 assert np.isfinite(s["coherence2"][b]).all()
             if f is hx.cross_spectrum:
                 for b in range(len(edges) - 1):
-                    assert _same(s["K"][b], t["K"][b]) and _neg_bits(s["Q"][b], t["Q"][b]) and _same(s["Pxx"][b], t["Pyy"][b])
+                    assert same_values(s["K"][b], t["K"][b]) and _neg_bits(s["Q"][b], t["Q"][b]) and same_values(s["Pxx"][b], t["Pyy"][b])
                     assert (s["Q"][b] != 0.0).any()
             same, twice = f(x, x, dx, dx, edges), f(x, 2.0 * x, dx, dx, edges)
             for b in range(len(edges) - 1):
                 assert (same["gain_quad"][b] == 0.0).all() and (twice["gain_quad"][b] == 0.0).all()
-                assert _same(twice["coherence2"][b], same["coherence2"][b])
-                assert _same(twice["gain"][b], 2.0 * same["gain"][b])
+                assert same_values(twice["coherence2"][b], same["coherence2"][b])
+                assert same_values(twice["gain"][b], 2.0 * same["gain"][b])
                 assert np.abs(same["gain"][b] - 1.0).max() <= 6 * DEVIATION and np.abs(same["coherence2"][b] - 1.0).max() <= 6 * DEVIATION
-            assert _same(twice["var_y"], 4.0 * same["var_x"])
+            assert same_values(twice["var_y"], 4.0 * same["var_x"])
 
 
 def test_coherence_is_bounded():
@@ -291,7 +289,7 @@ def test_a_fused_multiply_add_gives_other_bits():
     print("members whose bits differ under fused multiply-adds, of 1024:", differ)
     assert all(v > 256 for v in differ.values())
     got = rv.series_cross_spectrum(x, y, "mean", "mean", [1, 5])
-    assert all(_same(g, w) for g, w in zip(hx.flat(got), hx.flat(plain)))
+    assert all(same_values(g, w) for g, w in zip(hx.flat(got), hx.flat(plain)))
 
 
 # ---- the C boundary -------------------------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests._dist_grouped_worker import G, Q, THR, global_groups, global_rows
+from tests.helpers import same_values
 from tests.host_gselect import exceedance_grouped, sharded_gquantiles
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -44,7 +45,7 @@ def test_two_rank_gloo_grouped_quantiles_and_exceedance(n_total, tmp_path):
         assert x["world"] == 2
         got = np.array(x["bits"], dtype=np.uint64).view(np.float64)
         assert got.shape == (G, rows.shape[0], len(Q))
-        assert np.array_equal(got, want, equal_nan=True)
+        assert same_values(got, want)
         assert np.array_equal(got.view(np.uint64), whole.view(np.uint64))
         assert np.array_equal(np.array(x["strided_bits"], dtype=np.uint64), strided.view(np.uint64))
         assert x["count"] == count.tolist()

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 from tests._dist_indicator_worker import Q, REF, THR, global_series, global_weights
+from tests.helpers import same_values
 from tests.host_indicators import anomaly, baseline, exceedance_counts, indicators
 from tests.host_select import sharded_quantiles
 from tests.host_wselect import sharded_wquantiles
@@ -57,6 +58,6 @@ def test_two_rank_gloo_indicators(n_total, tmp_path):
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
                 want = np.nanquantile(a, Q, axis=1).T
-            assert np.array_equal(_unsign(_f(res[0][tag]["anomaly"])), _unsign(want), equal_nan=True)
+            assert same_values(_unsign(_f(res[0][tag]["anomaly"])), _unsign(want))
             assert res[0][tag]["n"] == (~np.isnan(a)).sum(axis=1).tolist()
             assert res[0][tag]["vn"] == (~np.isnan(vecs)).sum(axis=1).tolist()

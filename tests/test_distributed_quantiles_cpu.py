@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from tests._dist_quantile_worker import global_rows
+from tests.helpers import same_values
 from tests.host_select import sharded_quantiles
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -33,7 +34,7 @@ def test_two_rank_gloo_quantiles(n_total, tmp_path):
     for x in res:
         assert x["world"] == 2
         got = np.array(x["bits"], dtype=np.uint64).view(np.float64)
-        assert np.array_equal(got, want, equal_nan=True)
+        assert same_values(got, want)
         assert np.array_equal(got.view(np.uint64), whole.view(np.uint64))
         assert np.array_equal(np.array(x["strided_bits"], dtype=np.uint64), strided.view(np.uint64))
         assert x["count"] == (~np.isnan(rows)).sum(axis=1).tolist()

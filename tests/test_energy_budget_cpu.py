@@ -10,6 +10,7 @@ import pytest
 from rscm_amd import _lib
 from tests import host_diagnostic as hd
 from tests import host_energy_budget as hb
+from tests.helpers import same_values
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("rscm_ens_define_energy_budget", "rscm_ens_diagnostic_quantity")
@@ -66,15 +67,15 @@ def test_the_identity_holds_in_the_restatements_own_terms():
     with np.errstate(all="ignore"):
         X = (P[2] * P[3]) * (Ts - Td)
         N = ((t["forcing"] - t["response"]) - X) + t["deep_uptake"]
-    assert np.array_equal(N, t["imbalance"], equal_nan=True) and np.isfinite(N).any()
-    assert np.array_equal(t["deep_uptake"], P[3] * (Ts - Td), equal_nan=True)
+    assert same_values(N, t["imbalance"]) and np.isfinite(N).any()
+    assert same_values(t["deep_uptake"], P[3] * (Ts - Td))
     # scale: multiplied even by 1.0 (the same bits), and -2.5 is one more rounding of the quantity
-    assert np.array_equal(hb.budget("imbalance", Ts, Td, P, F, 1.0), N, equal_nan=True)
-    assert np.array_equal(hb.budget("response", Ts, Td, P, F, -2.5), -2.5 * t["response"], equal_nan=True)
+    assert same_values(hb.budget("imbalance", Ts, Td, P, F, 1.0), N)
+    assert same_values(hb.budget("response", Ts, Td, P, F, -2.5), -2.5 * t["response"])
     # with a = 0 the response is lambda0 Ts, the linear diagnostic [(Ts, row 0, 1.0)]
     P0 = P.copy()
     P0[1] = 0.0
-    assert np.array_equal(hb.budget("response", Ts, Td, P0, F), hd.diagnostic([(1, 0, 1.0)], [Ts], P0), equal_nan=True)
+    assert same_values(hb.budget("response", Ts, Td, P0, F), hd.diagnostic([(1, 0, 1.0)], [Ts], P0))
 
 
 def test_member_forcing_is_the_existing_restatements():

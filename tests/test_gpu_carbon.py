@@ -7,18 +7,12 @@ pools of O(1e3) GtC; the implicit pool update is contractive."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
 PI_POOLS = np.array([884.86, 92.77, 1681.53, 836.0])
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -58,9 +52,9 @@ def test_co2_budget_gpu_bit_exact(ra, orc, n):
     scen = (np.arange(n) % 2).astype(np.int32)
     want = orc.carbon_run(orc.CARBON_BUDGET, b, P, inputs, [c0], scen=scen, threads=4)
     got = _gpu(ra, ra.KIND_CO2_BUDGET, b, P, inputs, [c0], scen=scen)
-    assert np.array_equal(got, want, equal_nan=True)
+    assert same_values(got, want)
     assert (want[2, 1:, 1::2] == 0.0).any() or n == 1  # the non-positive-emissions branch occurs
-    assert np.array_equal(_gpu(ra, ra.KIND_CO2_BUDGET, b, P, inputs, [c0], scen=scen, chunks=(2, 90)), got, equal_nan=True)
+    assert same_values(_gpu(ra, ra.KIND_CO2_BUDGET, b, P, inputs, [c0], scen=scen, chunks=(2, 90)), got)
 
 
 @pytest.mark.parametrize("n", [1, 63, 1000])
@@ -89,7 +83,7 @@ def test_terrestrial_gpu_vs_oracle(ra, orc, n):
     assert (want[:4, 1:] >= 0.0).all()
     if n >= 63:  # scenario 1 (CO2 -> 0, heavy land use) drives the plant pool onto its floor at zero
         assert (want[0, -1, 1::2] == 0.0).any() and np.array_equal(got[0][want[0] == 0.0], want[0][want[0] == 0.0])
-    assert np.array_equal(_gpu(ra, ra.KIND_TERRESTRIAL_CARBON, b, P, inputs, init, scen=scen, chunks=(1, 150)), got, equal_nan=True)
+    assert same_values(_gpu(ra, ra.KIND_TERRESTRIAL_CARBON, b, P, inputs, init, scen=scen, chunks=(1, 150)), got)
 
 
 def test_carbon_through_the_reference_shaped_front(ra, orc):
@@ -126,7 +120,7 @@ def test_carbon_through_the_reference_shaped_front(ra, orc):
     m.close()
     want = orc.carbon_run(orc.CARBON_BUDGET, np.append(years, 2011.0), orc.carbon_default_params(orc.CARBON_BUDGET), np.stack(list(cb_in.values())), [311.0])
     for k, name in enumerate(("Atmospheric Concentration|CO2", "Emissions|CO2|Net", "Airborne Fraction|CO2")):
-        assert np.array_equal(res.get_timeseries_by_name(name).values(), want[k, :, 0], equal_nan=True), name
+        assert same_values(res.get_timeseries_by_name(name).values(), want[k, :, 0]), name
 
 
 def test_carbon_full_size_properties(ra, orc):

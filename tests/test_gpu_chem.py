@@ -8,17 +8,11 @@ grow over the run."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-11
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -87,7 +81,7 @@ def test_chem_gpu_vs_oracle(ra, orc, kind_name, n):
     _close(gl, wl, f"{kind_name} n={n} lifetime")
     # resume: the launch boundaries fall inside the lag window of the N2O delay
     rc, rl = _gpu(ra, kind, bounds, P, inputs, c0, scen=scen, chunks=(1, 3, 120))
-    assert np.array_equal(rc, gc, equal_nan=True) and np.array_equal(rl, gl, equal_nan=True)
+    assert same_values(rc, gc) and same_values(rl, gl)
     g0c, _ = _gpu(ra, kind, bounds, P, inputs[:1], c0)
     w0c, _ = orc.chem_run(kind, bounds, P, inputs[:1], c0)
     _close(g0c, w0c, f"{kind_name} n={n} one scenario")

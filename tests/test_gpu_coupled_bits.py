@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 from tests import host_coupled as hc
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
@@ -28,15 +29,6 @@ NAMES = {"ts": "Surface Temperature", "td": "Deep Ocean Temperature", "conc": "A
          "cum_uptake": "Cumulative Land Uptake", "cum_emis": "Cumulative Emissions|CO2", "erf_co2": "Effective Radiative Forcing|CO2",
          "erf_total": "Effective Radiative Forcing"}
 STATES = ("ts", "td", "conc", "cum_uptake", "cum_emis")
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -1,6 +1,6 @@
 """GPU tier of the per-member covariability of two variables (csrc/covariability.hip; rscm_ens_member_covariability;
 Ensemble.covariability, GraphModel.covariability).  The oracle is the numpy restatement of tests/host_covariability.py on rows
-copied to the host, compared bit for bit (any NaN equal to any NaN).
+copied to the host, compared by value (+0 equal to -0, any NaN equal to any NaN).
 
 The data are those of tests/test_gpu_variability.py: two-layer ensembles with per-member forcing noise on a 48-point annual axis,
 half the members under zero forcing and half under a ramp, with the ocean heat content as a diagnostic variable.  From 63 members
@@ -8,9 +8,7 @@ on, three members are special -- a silent one under zero forcing (constant serie
 amplitude that overflows -- and two more have +Inf written into one row of the surface temperature alone and -Inf into one row of
 the deep temperature alone."""
 import ctypes as C
-import importlib.util
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -18,13 +16,14 @@ import pytest
 from tests import host_covariability as hc
 from tests import host_likelihood as hl
 from tests import host_variability as hv
-from tests.helpers import two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import built_once, noise_ensemble, plant, refusal_code
+from tests.helpers import annual_bounds, magicc_chain, same_values
 
 pytestmark = pytest.mark.gpu
 
 T = 48
-YEARS = np.arange(1850, 1850 + T, dtype=np.float64)
-BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+YEARS, BOUNDS = annual_bounds(T)
 SEED = 20260327
 DETREND = ("mean", "linear", "difference")
 PAIRS = list(itertools.product(DETREND, DETREND))
@@ -36,86 +35,37 @@ ROWS = [3, 4, 5, 6, 7, 8, 9, 40]
 TS, TD, HEAT = 1, 2, "heat"
 
 
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _params(n, offset=0, n_total=None):
-    """[8][n]: the block [offset, offset + n) of the draw of n_total members, noise rows included, specials at the end of the draw."""
-    n_total = n if n_total is None else n_total
-    rng = np.random.default_rng(n_total)
-    P = np.vstack([two_layer_params(n_total), rng.uniform(0.1, 0.6, n_total), rng.uniform(0.0, 0.9, n_total)])
-    scen = (np.arange(n_total) % 2).astype(np.int32)
-    if n_total >= 63:
-        scen[n_total - 3], P[6, n_total - 3] = 0, 0.0      # silent under zero forcing: constant series
-        P[6, n_total - 2] = 1.7e308                        # sigma_i z overflows
-        P[0, n_total - 1] = np.nan
-    return np.ascontiguousarray(P[:, offset:offset + n]), np.ascontiguousarray(scen[offset:offset + n])
-
-
 def _ensemble(ra, n, offset=0, n_total=None, steps=None, **kw):
-    P, scen = _params(n, offset, n_total)
-    e = ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS, noise_params=True, **kw)
-    e.set_params(P)
-    e.set_forcing(np.stack([np.zeros(T), 0.05 * np.arange(T)]), scen)
-    e.set_initial(1, 0.0)
-    e.set_initial(2, 0.0)
-    e.set_forcing_noise_members(SEED, offset)
-    e.run(steps)
-    return e
+    return noise_ensemble(ra, n, BOUNDS, SEED, offset, n_total, steps, **kw)
 
 
 @pytest.fixture(scope="module")
 def cases(ra):
     """{N: (ensemble, {variable: its series [T][N] on the host})}, each built and run once and left unchanged."""
-    made = {}
+    def build(n):
+        e = _ensemble(ra, n)
+        if n >= 63:
+            for var, member, row, value in ((TS, 5, 1, np.inf), (TD, 7, 2, -np.inf)):
+                plant(e, var, member, row, value)
+        e.define_heat_content(HEAT)
+        e.compute_diagnostic(HEAT)
+        ser = {v: e.get_series(v) for v in (TS, TD, HEAT)}
+        for s in ser.values():
+            s.setflags(write=False)
+        return e, ser
 
-    def get(n):
-        if n not in made:
-            e = _ensemble(ra, n)
-            if n >= 63:
-                for var, member, row, value in ((TS, 5, 1, np.inf), (TD, 7, 2, -np.inf)):
-                    x = e.get_series(var, row, row + 1)[0]
-                    x[member] = value
-                    e.set_state(var, row, x)
-            e.define_heat_content(HEAT)
-            e.compute_diagnostic(HEAT)
-            ser = {v: e.get_series(v) for v in (TS, TD, HEAT)}
-            for s in ser.values():
-                s.setflags(write=False)
-            made[n] = (e, ser)
-        return made[n]
-
-    yield get
-    for e, _ in made.values():
-        e.close()
+    yield from built_once(build)
 
 
 def _host(d):
     return [v.to_host() for v in hc.flat(d)]
 
 
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
 def _check(got, want, what):
     want = hc.flat(want)
     assert len(got) == len(want), what
     for j, (g, w) in enumerate(zip(got, want)):
-        assert _same(g, w), (what, j, np.flatnonzero(~((g == w) | (np.isnan(g) & np.isnan(w))))[:5])
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
+        assert same_values(g, w), (what, j, np.flatnonzero(~((g == w) | (np.isnan(g) & np.isnan(w))))[:5])
 
 
 def _terms(R, dx, dy):
@@ -133,7 +83,7 @@ def test_statistics_equal_the_restatement(ra, cases, n):
     for (dx, dy), lags, R in itertools.product(PAIRS, LAGS, ROWS):
         kw = dict(detrend_x=dx, detrend_y=dy, lags=lags)
         if _terms(R, dx, dy) < 3 + lags:
-            assert _code(e.covariability, TS, TD, 0, R, **kw) == 1
+            assert refusal_code(e.covariability, TS, TD, 0, R, **kw) == 1
             continue
         res = e.covariability(TS, TD, 0, R, **kw)
         assert set(res) == set(hc.NAMES) | {"lead", "lag"} and len(res["lead"]) == len(res["lag"]) == lags
@@ -163,7 +113,7 @@ def test_pairs_with_a_diagnostic_and_a_variable_with_itself(cases, vx, vy):
 @pytest.mark.parametrize("n", [257, 1000])
 def test_exchange_and_variance_equalities_on_the_device(cases, n):
     """Exchanging (x, mode_x) with (y, mode_y) exchanges var_x with var_y and r_{+l} with r_{-l} and keeps cov and corr; with no
-    mode mixed var_x and var_y are the variances of variability() -- all bit for bit, on device results alone."""
+    mode mixed var_x and var_y are the variances of variability() -- all value for value (+0 equal to -0), on device results alone."""
     e, ser = cases(n)
     for vx, vy in ((TS, TD), (TS, HEAT)):
         for dx, dy in PAIRS:
@@ -171,52 +121,44 @@ def test_exchange_and_variance_equalities_on_the_device(cases, n):
             s = {k: [w.to_host() for w in v] if isinstance(v, list) else v.to_host() for k, v in s.items()}
             t = e.covariability(vy, vx, 3, T, 1, dy, dx, 3, slot=1)
             t = {k: [w.to_host() for w in v] if isinstance(v, list) else v.to_host() for k, v in t.items()}
-            assert _same(s["var_x"], t["var_y"]) and _same(s["var_y"], t["var_x"]) and _same(s["cov"], t["cov"]) and _same(s["corr"], t["corr"])
+            assert same_values(s["var_x"], t["var_y"]) and same_values(s["var_y"], t["var_x"]) and same_values(s["cov"], t["cov"]) and same_values(s["corr"], t["corr"])
             for l in range(3):
-                assert _same(s["lead"][l], t["lag"][l]) and _same(s["lag"][l], t["lead"][l])
-            assert np.isfinite(s["corr"][:5]).all() and not _same(s["lead"][0], s["lag"][0])
+                assert same_values(s["lead"][l], t["lag"][l]) and same_values(s["lag"][l], t["lead"][l])
+            assert np.isfinite(s["corr"][:5]).all() and not same_values(s["lead"][0], s["lag"][0])
             if (dx == "difference") == (dy == "difference"):
-                assert _same(s["var_x"], e.variability(vx, 3, T, detrend=dx, slot=2)["variance"].to_host())
-                assert _same(s["var_y"], e.variability(vy, 3, T, detrend=dy, slot=2)["variance"].to_host())
+                assert same_values(s["var_x"], e.variability(vx, 3, T, detrend=dx, slot=2)["variance"].to_host())
+                assert same_values(s["var_y"], e.variability(vy, 3, T, detrend=dy, slot=2)["variance"].to_host())
             live = np.isfinite(s["corr"])
             for g in [s["corr"]] + s["lead"] + s["lag"]:
                 assert np.abs(g[live]).max() <= 1.0 + 8 * T * 2.0 ** -53
 
 
-def _chain():
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_windowed_graph(ra):
     """Two outputs of one home ensemble of a windowed graph, from the output store, give the bits of the full-storage build; rows
     that are not resident are refused; two variables with different homes raise."""
-    mod = _chain()
-    plant, soil, co2 = "Carbon Pool|Plant", "Carbon Pool|Soil", "Atmospheric Concentration|CO2"
+    mod = magicc_chain()
+    plant_pool, soil, co2 = "Carbon Pool|Plant", "Carbon Pool|Soil", "Atmospheric Concentration|CO2"
     got = {}
     for key, kw in (("windowed", dict(series_window=16, output_stride=12)), ("full", {})):
         model = mod.build_chain(65, 30, "topological", steps_per_year=12, **kw)
         try:
             model.run()
-            ens, _ = model.variable_home(plant)
+            ens, _ = model.variable_home(plant_pool)
             assert model.variable_home(soil)[0] is ens and model.variable_home(co2)[0] is not ens
             n_times = ens.n_times
-            got[key] = {p: _host(model.covariability(plant, soil, 0, n_times, 12, p[0], p[1], 3, slot=1)) for p in PAIRS}
+            got[key] = {p: _host(model.covariability(plant_pool, soil, 0, n_times, 12, p[0], p[1], 3, slot=1)) for p in PAIRS}
             if key == "full":
-                x, y = model.get_series(plant, t_stride=12), model.get_series(soil, t_stride=12)
+                x, y = model.get_series(plant_pool, t_stride=12), model.get_series(soil, t_stride=12)
                 for p in PAIRS:
                     _check(got[key][p], hc.covariability(x, y, p[0], p[1], 3), ("chain", p))
             else:
-                assert _code(model.covariability, plant, soil, 0, 9, 3) == 2       # rows 3 and 6: outside the window and the output stride
+                assert refusal_code(model.covariability, plant_pool, soil, 0, 9, 3) == 2       # rows 3 and 6: outside the window and the output stride
             with pytest.raises(ValueError, match="share one home"):
-                model.covariability(plant, co2, 0, n_times, 12)
+                model.covariability(plant_pool, co2, 0, n_times, 12)
         finally:
             model.close()
     for p in PAIRS:
-        assert all(_same(a, b) for a, b in zip(got["windowed"][p], got["full"][p])), p
+        assert all(same_values(a, b) for a, b in zip(got["windowed"][p], got["full"][p])), p
 
 
 def test_slots_and_refusals(ra, cases):
@@ -224,19 +166,19 @@ def test_slots_and_refusals(ra, cases):
     ind = e.indicators(TS, 0, 30, thresholds=[0.2, 0.5], slot=0)
     keep = [ind["mean"].to_host(), ind["peak"].to_host()] + [c.to_host() for c in ind["crossing"]]
     cov = e.covariability(TS, TD, 0, 30, lags=3, slot=1)
-    assert all(_same(a, b) for a, b in zip(keep, [ind["mean"].to_host(), ind["peak"].to_host()] + [c.to_host() for c in ind["crossing"]]))
+    assert all(same_values(a, b) for a, b in zip(keep, [ind["mean"].to_host(), ind["peak"].to_host()] + [c.to_host() for c in ind["crossing"]]))
     assert cov["var_x"].ptr != ind["mean"].ptr
     want = hc.covariability(ser[TS][:30], ser[TD][:30], "linear", "linear", 3)
     _check(_host(cov), want, "slot 1")
     # a slot keeps the vectors of the last call of any kind: the last of eleven vectors survives a call on another slot, not one on its own
     last = cov["lag"][2]
     e.spectrum(TS, 0, 30, slot=2)
-    assert _same(last.to_host(), want["lag"][2])
+    assert same_values(last.to_host(), want["lag"][2])
     var = e.variability(TS, 0, 30, slot=1)
-    assert var["mean"].ptr == cov["var_x"].ptr and _same(var["variance"].to_host(), hv.variability(ser[TS][:30], "linear")["variance"])
+    assert var["mean"].ptr == cov["var_x"].ptr and same_values(var["variance"].to_host(), hv.variability(ser[TS][:30], "linear")["variance"])
     assert e.covariability(TS, TD, 0, 30, slot=0)["var_x"].ptr == ind["mean"].ptr
-    assert _code(e.covariability, TS, TD, 0, 30, slot=4) == 1 and _code(e.covariability, TS, TD, 0, 30, slot=-1) == 1
-    assert _code(e.covariability, TS, TD, 0, 30, lags=4) == 1 and _code(e.covariability, TS, TD, 0, 30, lags=-1) == 1
+    assert refusal_code(e.covariability, TS, TD, 0, 30, slot=4) == 1 and refusal_code(e.covariability, TS, TD, 0, 30, slot=-1) == 1
+    assert refusal_code(e.covariability, TS, TD, 0, 30, lags=4) == 1 and refusal_code(e.covariability, TS, TD, 0, 30, lags=-1) == 1
     with pytest.raises(ValueError):
         e.covariability(TS, TD, 0, 30, detrend_x="quadratic")
     with pytest.raises(ValueError):
@@ -248,21 +190,21 @@ def test_slots_and_refusals(ra, cases):
     assert call(e._h, 0, 1, 0, 30, 1, 0, 0, 0, 0, C.byref(p)) == 1 and call(e._h, 1, 0, 0, 30, 1, 0, 0, 0, 0, C.byref(p)) == 1     # no stored series
     assert call(e._h, 1, 7, 0, 30, 1, 0, 0, 0, 0, C.byref(p)) == 1                  # neither a stored variable nor a diagnostic
     assert call(e._h, 1, 2, 0, 30, 1, 0, 0, 0, 0, None) == 1
-    assert _code(e.covariability, TS, TD, 0, 2) == 1 and _code(e.covariability, TS, TD, 5, 5) == 1 and _code(e.covariability, TS, TD, 0, 30, 0) == 1
+    assert refusal_code(e.covariability, TS, TD, 0, 2) == 1 and refusal_code(e.covariability, TS, TD, 5, 5) == 1 and refusal_code(e.covariability, TS, TD, 0, 30, 0) == 1
     with e.select(1, [0.5], 0, 30) as s:
-        assert _code(e.covariability, TS, TD, 0, 30) == 2
+        assert refusal_code(e.covariability, TS, TD, 0, 30) == 2
         while s.next_pass() is not None:
             s.commit()
     with _ensemble(ra, 64, steps=10) as h:
         assert h.time_index == 10
-        assert _code(h.covariability, TS, TD, 0, 20) == 2                           # rows beyond the time index
+        assert refusal_code(h.covariability, TS, TD, 0, 20) == 2                           # rows beyond the time index
         vid = h.define_heat_content()
-        assert _code(h.covariability, TS, vid, 0, 11) == 2                          # no rows computed yet
+        assert refusal_code(h.covariability, TS, vid, 0, 11) == 2                          # no rows computed yet
         h.compute_diagnostic(vid, 0, 8)
-        assert _code(h.covariability, vid, TS, 0, 11) == 2                          # rows 8 .. 10 are not held
+        assert refusal_code(h.covariability, vid, TS, 0, 11) == 2                          # rows 8 .. 10 are not held
         h.covariability(vid, TS, 0, 8)
         h.run(20)
-        assert _code(h.covariability, TS, vid, 0, 8) == 2 and _code(h.covariability, vid, TS, 0, 8) == 2      # stale
+        assert refusal_code(h.covariability, TS, vid, 0, 8) == 2 and refusal_code(h.covariability, vid, TS, 0, 8) == 2      # stale
         h.covariability(TS, TD, 0, 21)
         h.compute_diagnostic(vid)
         h.covariability(TS, vid, 0, 21, lags=3)
@@ -305,4 +247,4 @@ def test_two_shards_give_the_halves(ra, cases):
             for p in pairs:
                 got = _host(h.covariability(TS, HEAT, 4, T, 1, p[0], p[1], 3))
                 for j, g in enumerate(got):
-                    assert _same(g, whole[p][j][offset:offset + count]), (p, j, offset)
+                    assert same_values(g, whole[p][j][offset:offset + count]), (p, j, offset)

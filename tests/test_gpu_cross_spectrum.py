@@ -1,6 +1,6 @@
 """GPU tier of the per-member co-spectra of two variables in frequency bands (csrc/cross_spectrum.hip;
 rscm_ens_member_cross_spectrum; Ensemble.cross_spectrum, GraphModel.cross_spectrum).  The oracle is the numpy restatement of
-tests/host_cross_spectrum.py on rows copied to the host, compared bit for bit (any NaN equal to any NaN).
+tests/host_cross_spectrum.py on rows copied to the host, compared by value (+0 equal to -0, any NaN equal to any NaN).
 
 The data are those of tests/test_gpu_covariability.py on an axis of 4 F + 8 = 40 annual points (F = 8, the kernel's tile of
 frequencies): two-layer ensembles with per-member forcing noise, half the members under zero forcing and half under a ramp, with the
@@ -9,9 +9,7 @@ ocean heat content as a diagnostic variable.  From 63 members on, three members 
 of the surface temperature alone and -Inf into one row of the deep temperature alone.  Every refusal below is a host-side check
 before any launch."""
 import ctypes as C
-import importlib.util
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -19,14 +17,15 @@ import pytest
 from tests import host_cross_spectrum as hx
 from tests import host_likelihood as hl
 from tests import host_variability as hv
-from tests.helpers import two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import built_once, noise_ensemble, plant, refusal_code
+from tests.helpers import annual_bounds, magicc_chain, same_values, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 F = 8                                # kXSpecF of csrc/cross_spectrum.hip: the frequencies a lane carries per pass over the rows
 T = 4 * F + 8
-YEARS = np.arange(1850, 1850 + T, dtype=np.float64)
-BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+YEARS, BOUNDS = annual_bounds(T)
 SEED = 20260327
 DETREND = ("mean", "linear", "difference")
 PAIRS = list(itertools.product(DETREND, DETREND))
@@ -40,88 +39,39 @@ MID = 2 * F + 3                      # the mid-size at which all nine mode pairs
 TS, TD, HEAT, TWICE = 1, 2, "heat", "twice"
 
 
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _params(n, offset=0, n_total=None):
-    """[8][n]: the block [offset, offset + n) of the draw of n_total members, noise rows included, specials at the end of the draw."""
-    n_total = n if n_total is None else n_total
-    rng = np.random.default_rng(n_total)
-    P = np.vstack([two_layer_params(n_total), rng.uniform(0.1, 0.6, n_total), rng.uniform(0.0, 0.9, n_total)])
-    scen = (np.arange(n_total) % 2).astype(np.int32)
-    if n_total >= 63:
-        scen[n_total - 3], P[6, n_total - 3] = 0, 0.0      # silent under zero forcing: constant series
-        P[6, n_total - 2] = 1.7e308                        # sigma_i z overflows
-        P[0, n_total - 1] = np.nan
-    return np.ascontiguousarray(P[:, offset:offset + n]), np.ascontiguousarray(scen[offset:offset + n])
-
-
 def _ensemble(ra, n, offset=0, n_total=None, steps=None, **kw):
-    P, scen = _params(n, offset, n_total)
-    e = ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS, noise_params=True, **kw)
-    e.set_params(P)
-    e.set_forcing(np.stack([np.zeros(T), 0.05 * np.arange(T)]), scen)
-    e.set_initial(1, 0.0)
-    e.set_initial(2, 0.0)
-    e.set_forcing_noise_members(SEED, offset)
-    e.run(steps)
-    return e
+    return noise_ensemble(ra, n, BOUNDS, SEED, offset, n_total, steps, **kw)
 
 
 @pytest.fixture(scope="module")
 def cases(ra):
     """{N: (ensemble, {variable: its series [T][N] on the host})}, each built and run once and left unchanged."""
-    made = {}
+    def build(n):
+        e = _ensemble(ra, n)
+        if n >= 63:
+            for var, member, row, value in ((TS, 5, 1, np.inf), (TD, 7, 2, -np.inf)):
+                plant(e, var, member, row, value)
+        e.define_heat_content(HEAT)
+        e.define_diagnostic(TWICE, [(TS, None, 2.0)])
+        e.compute_diagnostic(HEAT)
+        e.compute_diagnostic(TWICE)
+        ser = {v: e.get_series(v) for v in (TS, TD, HEAT, TWICE)}
+        for s in ser.values():
+            s.setflags(write=False)
+        return e, ser
 
-    def get(n):
-        if n not in made:
-            e = _ensemble(ra, n)
-            if n >= 63:
-                for var, member, row, value in ((TS, 5, 1, np.inf), (TD, 7, 2, -np.inf)):
-                    x = e.get_series(var, row, row + 1)[0]
-                    x[member] = value
-                    e.set_state(var, row, x)
-            e.define_heat_content(HEAT)
-            e.define_diagnostic(TWICE, [(TS, None, 2.0)])
-            e.compute_diagnostic(HEAT)
-            e.compute_diagnostic(TWICE)
-            ser = {v: e.get_series(v) for v in (TS, TD, HEAT, TWICE)}
-            for s in ser.values():
-                s.setflags(write=False)
-            made[n] = (e, ser)
-        return made[n]
-
-    yield get
-    for e, _ in made.values():
-        e.close()
+    yield from built_once(build)
 
 
 def _host(d):
     return [v.to_host() for v in hx.flat(d)]
 
 
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
 def _check(got, want, what):
     want = hx.flat(want)
     assert len(got) == len(want), what
     for j, (g, w) in enumerate(zip(got, want)):
-        assert _same(g, w), (what, j, np.flatnonzero(~((g == w) | (np.isnan(g) & np.isnan(w))))[:5])
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
+        assert same_values(g, w), (what, j, np.flatnonzero(~((g == w) | (np.isnan(g) & np.isnan(w))))[:5])
 
 
 def _rows(n, dx, dy):
@@ -190,19 +140,19 @@ def test_pairs_with_a_diagnostic_and_a_variable_with_itself(cases, vx, vy):
 @pytest.mark.parametrize("n", [257, 1000])
 def test_equalities_on_the_device(cases, n):
     """var_x, var_y are covariability()'s for the same arguments; the exchange keeps every coh2 and exchanges the variances; a variable
-    against itself and against twice itself: quadrature +-0.0, the same coherence, twice the gain -- bit for bit, on device results."""
+    against itself and against twice itself: quadrature +-0.0, the same coherence, twice the gain -- value for value, on device results."""
     e, ser = cases(n)
     host = lambda d: {k: [w.to_host() for w in v] if isinstance(v, list) else v.to_host() for k, v in d.items() if k not in ("edges", "counts")}
     for dx, dy in PAIRS:
         for vx, vy in ((TS, TD), (TS, HEAT)):
             s, t = host(e.cross_spectrum(vx, vy, 3, T, 1, dx, dy, 3, slot=0)), host(e.cross_spectrum(vy, vx, 3, T, 1, dy, dx, 3, slot=1))
             cov = e.covariability(vx, vy, 3, T, 1, dx, dy, 0, slot=2)
-            assert _same(s["var_x"], cov["var_x"].to_host()) and _same(s["var_y"], cov["var_y"].to_host())
-            assert _same(s["var_x"], t["var_y"]) and _same(s["var_y"], t["var_x"])
+            assert same_values(s["var_x"], cov["var_x"].to_host()) and same_values(s["var_y"], cov["var_y"].to_host())
+            assert same_values(s["var_x"], t["var_y"]) and same_values(s["var_y"], t["var_x"])
             live = np.isfinite(s["var_x"]) & (s["var_x"] > 0.0)
             assert live[:5].all()
             for b in range(3):
-                assert _same(s["coherence2"][b], t["coherence2"][b]) and np.isfinite(s["coherence2"][b][live]).all()
+                assert same_values(s["coherence2"][b], t["coherence2"][b]) and np.isfinite(s["coherence2"][b][live]).all()
                 # coh2 <= 1 up to the rounding bound tests/test_cross_spectrum_cpu.py derives (6 x 1e-8)
                 assert s["coherence2"][b][live].max() <= 1.0 + 6e-8 and s["coherence2"][b][live].min() >= 0.0
         same = host(e.cross_spectrum(TS, TS, 3, T, 1, dx, dx, 3, slot=0))
@@ -210,48 +160,40 @@ def test_equalities_on_the_device(cases, n):
         live = np.isfinite(same["var_x"]) & (same["var_x"] > 0.0)
         for b in range(3):
             assert (same["gain_quad"][b][live] == 0.0).all() and (twice["gain_quad"][b][live] == 0.0).all()
-            assert _same(twice["coherence2"][b], same["coherence2"][b])
-            assert _same(twice["gain"][b], 2.0 * same["gain"][b])
+            assert same_values(twice["coherence2"][b], same["coherence2"][b])
+            assert same_values(twice["gain"][b], 2.0 * same["gain"][b])
             assert np.abs(same["gain"][b][live] - 1.0).max() <= 6e-8
-
-
-def _chain():
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_windowed_graph(ra):
     """Two outputs of one home ensemble of a windowed graph, from the output store, give the bits of the full-storage build; rows
     that are not resident are refused; two variables with different homes raise."""
-    mod = _chain()
-    plant, soil, co2 = "Carbon Pool|Plant", "Carbon Pool|Soil", "Atmospheric Concentration|CO2"
+    mod = magicc_chain()
+    plant_pool, soil, co2 = "Carbon Pool|Plant", "Carbon Pool|Soil", "Atmospheric Concentration|CO2"
     pairs = SUBSET + [("mean", "mean")]
     got = {}
     for key, kw in (("windowed", dict(series_window=16, output_stride=12)), ("full", {})):
         model = mod.build_chain(65, 30, "topological", steps_per_year=12, **kw)
         try:
             model.run()
-            ens, _ = model.variable_home(plant)
+            ens, _ = model.variable_home(plant_pool)
             assert model.variable_home(soil)[0] is ens and model.variable_home(co2)[0] is not ens
             n_times = ens.n_times
-            got[key] = {p: _host(model.cross_spectrum(plant, soil, 0, n_times, 12, p[0], p[1], 3, slot=1)) for p in pairs}
+            got[key] = {p: _host(model.cross_spectrum(plant_pool, soil, 0, n_times, 12, p[0], p[1], 3, slot=1)) for p in pairs}
             if key == "full":
-                x, y = model.get_series(plant, t_stride=12), model.get_series(soil, t_stride=12)
+                x, y = model.get_series(plant_pool, t_stride=12), model.get_series(soil, t_stride=12)
                 for p in pairs:
                     terms = len(x) - (1 if "difference" in p else 0)
                     from rscm_amd.variability import band_edges
                     _check(got[key][p], hx.cross_spectrum(x, y, p[0], p[1], band_edges(terms, 3)), ("chain", p))
             else:
-                assert _code(model.cross_spectrum, plant, soil, 0, 9, 3) == 2       # rows 3 and 6: outside the window and the output stride
+                assert refusal_code(model.cross_spectrum, plant_pool, soil, 0, 9, 3) == 2       # rows 3 and 6: outside the window and the output stride
             with pytest.raises(ValueError, match="share one home"):
-                model.cross_spectrum(plant, co2, 0, n_times, 12)
+                model.cross_spectrum(plant_pool, co2, 0, n_times, 12)
         finally:
             model.close()
     for p in pairs:
-        assert all(_same(a, b) for a, b in zip(got["windowed"][p], got["full"][p])), p
+        assert all(same_values(a, b) for a, b in zip(got["windowed"][p], got["full"][p])), p
 
 
 def test_slots_and_refusals(ra, cases):
@@ -259,7 +201,7 @@ def test_slots_and_refusals(ra, cases):
     ind = e.indicators(TS, 0, 30, thresholds=[0.2, 0.5], slot=0)
     keep = [ind["mean"].to_host(), ind["peak"].to_host()] + [c.to_host() for c in ind["crossing"]]
     xs = e.cross_spectrum(TS, TD, 0, 30, bands=3, slot=1)
-    assert all(_same(a, b) for a, b in zip(keep, [ind["mean"].to_host(), ind["peak"].to_host()] + [c.to_host() for c in ind["crossing"]]))
+    assert all(same_values(a, b) for a, b in zip(keep, [ind["mean"].to_host(), ind["peak"].to_host()] + [c.to_host() for c in ind["crossing"]]))
     assert xs["var_x"].ptr != ind["mean"].ptr
     want = hx.cross_spectrum(ser[TS][:30], ser[TD][:30], "linear", "linear", xs["edges"])
     _check(_host(xs), want, "slot 1")
@@ -267,11 +209,11 @@ def test_slots_and_refusals(ra, cases):
     last = xs["gain_quad"][2]
     e.spectrum(TS, 0, 30, slot=2)
     e.covariability(TS, TD, 0, 30, lags=3, slot=0)
-    assert _same(last.to_host(), want["gain_quad"][2])
+    assert same_values(last.to_host(), want["gain_quad"][2])
     var = e.variability(TS, 0, 30, slot=1)
-    assert var["mean"].ptr == xs["var_x"].ptr and _same(var["variance"].to_host(), hv.variability(ser[TS][:30], "linear")["variance"])
+    assert var["mean"].ptr == xs["var_x"].ptr and same_values(var["variance"].to_host(), hv.variability(ser[TS][:30], "linear")["variance"])
     assert e.cross_spectrum(TS, TD, 0, 30, slot=0)["var_x"].ptr == ind["mean"].ptr
-    assert _code(e.cross_spectrum, TS, TD, 0, 30, slot=4) == 1 and _code(e.cross_spectrum, TS, TD, 0, 30, slot=-1) == 1
+    assert refusal_code(e.cross_spectrum, TS, TD, 0, 30, slot=4) == 1 and refusal_code(e.cross_spectrum, TS, TD, 0, 30, slot=-1) == 1
     with pytest.raises(ValueError):
         e.cross_spectrum(TS, TD, 0, 30, bands=0)
     with pytest.raises(ValueError):
@@ -282,9 +224,9 @@ def test_slots_and_refusals(ra, cases):
         e.cross_spectrum(TS, TD, 0, 30, detrend_y="quadratic")
     # J = 14 of 30 terms: five edges (four bands), edges out of order, equal, below 1, past J + 1
     for bad in ([1, 2, 3, 4, 5], [3, 2], [1, 4, 4], [0, 3], [1, 16], [1, 5, 3, 9]):
-        assert _code(e.cross_spectrum, TS, TD, 0, 30, bands=bad) == 1
+        assert refusal_code(e.cross_spectrum, TS, TD, 0, 30, bands=bad) == 1
     e.cross_spectrum(TS, TD, 0, 30, 1, "mean", "difference", [1, 15])                          # 29 terms: J + 1 = 15 is the last edge allowed
-    assert _code(e.cross_spectrum, TS, TD, 0, 30, 1, "mean", "difference", [1, 16]) == 1
+    assert refusal_code(e.cross_spectrum, TS, TD, 0, 30, 1, "mean", "difference", [1, 16]) == 1
     p = C.c_void_p()
     call = e._lib.rscm_ens_member_cross_spectrum
     edges = (C.c_int32 * 5)(1, 2, 3, 4, 5)
@@ -298,22 +240,22 @@ def test_slots_and_refusals(ra, cases):
     assert call(e._h, 1, 2, 0, 30, 1, 0, 0, 2, edges, 0, None) == 1
     assert call(e._h, 1, 2, 0, 30, 1, 0, 0, 3, edges, 0, C.byref(p)) == 0 and p.value is not None
     # n of 2, an empty range, a zero stride
-    assert _code(e.cross_spectrum, TS, TD, 0, 2) == 1 and _code(e.cross_spectrum, TS, TD, 0, 3, 1, "difference", "mean") == 1
-    assert _code(e.cross_spectrum, TS, TD, 5, 5) == 1 and _code(e.cross_spectrum, TS, TD, 0, 30, 0) == 1
+    assert refusal_code(e.cross_spectrum, TS, TD, 0, 2) == 1 and refusal_code(e.cross_spectrum, TS, TD, 0, 3, 1, "difference", "mean") == 1
+    assert refusal_code(e.cross_spectrum, TS, TD, 5, 5) == 1 and refusal_code(e.cross_spectrum, TS, TD, 0, 30, 0) == 1
     with e.select(1, [0.5], 0, 30) as s:
-        assert _code(e.cross_spectrum, TS, TD, 0, 30) == 2
+        assert refusal_code(e.cross_spectrum, TS, TD, 0, 30) == 2
         while s.next_pass() is not None:
             s.commit()
     with _ensemble(ra, 64, steps=10) as h:
         assert h.time_index == 10
-        assert _code(h.cross_spectrum, TS, TD, 0, 20) == 2                          # rows beyond the time index
+        assert refusal_code(h.cross_spectrum, TS, TD, 0, 20) == 2                          # rows beyond the time index
         vid = h.define_heat_content()
-        assert _code(h.cross_spectrum, TS, vid, 0, 11) == 2                         # no rows computed yet
+        assert refusal_code(h.cross_spectrum, TS, vid, 0, 11) == 2                         # no rows computed yet
         h.compute_diagnostic(vid, 0, 8)
-        assert _code(h.cross_spectrum, vid, TS, 0, 11) == 2                         # rows 8 .. 10 are not held
+        assert refusal_code(h.cross_spectrum, vid, TS, 0, 11) == 2                         # rows 8 .. 10 are not held
         h.cross_spectrum(vid, TS, 0, 8)
         h.run(20)
-        assert _code(h.cross_spectrum, TS, vid, 0, 8) == 2 and _code(h.cross_spectrum, vid, TS, 0, 8) == 2      # stale
+        assert refusal_code(h.cross_spectrum, TS, vid, 0, 8) == 2 and refusal_code(h.cross_spectrum, vid, TS, 0, 8) == 2      # stale
         h.cross_spectrum(TS, TD, 0, 21)
         h.compute_diagnostic(vid)
         h.cross_spectrum(TS, vid, 0, 21)
@@ -332,8 +274,8 @@ def test_more_than_4096_terms_are_refused(ra):
         e.set_initial(2, 0.0)
         e.set_forcing_noise_members(SEED, 0)
         e.run()
-        assert _code(e.cross_spectrum, TS, TD, 0, 4097, 1, "mean", "linear") == 1
-        assert _code(e.cross_spectrum, TS, TD, 0, 4098, 1, "difference", "linear") == 1
+        assert refusal_code(e.cross_spectrum, TS, TD, 0, 4097, 1, "mean", "linear") == 1
+        assert refusal_code(e.cross_spectrum, TS, TD, 0, 4098, 1, "difference", "linear") == 1
         edges = [2040, 2044, 2048]
         d = e.cross_spectrum(TS, TD, 0, 4097, 1, "linear", "difference", edges)
         _check(_host(d), hx.cross_spectrum(e.get_series(TS, 0, 4097), e.get_series(TD, 0, 4097), "linear", "difference", edges), "4096 terms")
@@ -376,4 +318,4 @@ def test_two_shards_give_the_halves(ra, cases):
             for p in pairs:
                 got = _host(h.cross_spectrum(TS, HEAT, 4, T, 1, p[0], p[1], 3))
                 for j, g in enumerate(got):
-                    assert _same(g, whole[p][j][offset:offset + count]), (p, j, offset)
+                    assert same_values(g, whole[p][j][offset:offset + count]), (p, j, offset)

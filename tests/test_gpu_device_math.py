@@ -9,19 +9,12 @@ import numpy as np
 import pytest
 
 from tests import host_math as M
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import bits
 
 pytestmark = pytest.mark.gpu
 LD = M.LD
 OP_LOG_F64, OP_LOG, OP_EXP, OP_POW_RATIO, OP_GUARDED_RCP = range(5)
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -45,10 +38,6 @@ def logs():
     ref["edges"] = (at + np.arange(edges.size), M.mp_reference("log", edges))
     x.setflags(write=False)
     return fam, x, ref
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def _maxima(got, ref):
@@ -97,7 +86,7 @@ def test_log_f64_fallback_branch_is_the_librarys_log(math):
     x = np.concatenate([den, neg, other])
     assert not ((x >= M.DBL_MIN) & np.isfinite(x)).any()
     mine, lib = math(OP_LOG_F64, x), math(OP_LOG, x)
-    assert np.array_equal(_bits(mine), _bits(lib))
+    assert np.array_equal(bits(mine), bits(lib))
     err = M.ulp_error(mine[:den.size], M.mp_reference("log", den))
     print("log_f64 on denormals, max ulp:", round(float(err.max()), 4))
     assert float(err.max()) <= 1.0
@@ -181,7 +170,7 @@ def test_guarded_rcp_inside_and_outside_the_divisor_window(math):
     assert float(err.max()) <= 1.0
     nan = np.isnan(outside)
     assert nan.sum() == 1 and np.isnan(go[nan]).all()
-    assert np.array_equal(_bits(go[~nan]), _bits(host_out[~nan]))        # signed zeros, signed infinities and denormal quotients included
+    assert np.array_equal(bits(go[~nan]), bits(host_out[~nan]))        # signed zeros, signed infinities and denormal quotients included
     assert np.isinf(go).sum() > 100 and ((go != 0.0) & (np.abs(go) < M.DBL_MIN)).sum() > 100
 
 

@@ -9,9 +9,7 @@ one with a NaN parameter; +Inf and -Inf written into one row each, a denormal in
 full mantissas (tests/test_diagnostic_cpu.py shows that they tell a fused multiply-add from the definition).  A coupled ensemble
 (8 variables, 10 parameters) carries the three- and four-term cases."""
 import ctypes as C
-import importlib.util
 import math
-import os
 import warnings
 
 import numpy as np
@@ -22,13 +20,14 @@ from tests import host_indicators as hi
 from tests import host_likelihood as hl
 from tests import host_spectrum as hs
 from tests import host_variability as hv
-from tests.helpers import coupled_params, two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import built_once, noise_ensemble, plant, refusal_code
+from tests.helpers import annual_bounds, coupled_params, magicc_chain, same_bits, same_values, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 T = 72
-YEARS = np.arange(1850, 1850 + T, dtype=np.float64)
-BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+YEARS, BOUNDS = annual_bounds(T)
 SEED = 20260418
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000]
 TILE, BATCH = 32, 4                  # kDiagTile and kDiagBatch of csrc/diagnostic.hpp
@@ -41,47 +40,8 @@ TL_DIAGS = {"copy": [(1, None, 1.0)], "deep": [(2, 5, -2.5)], "heat": hd.HEAT_CO
 CP_DIAGS = {"three": [(1, 0, 1.0), (3, None, -2.5), (5, 7, 16.1)], "four": [(1, 4, 1.0), (2, 5, 1.0), (3, None, 0.3), (4, 9, -2.5)]}
 
 
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
-
-
-def _bits_same(a, b):
-    """Bit for bit, the sign of a zero included; any NaN equal to any NaN."""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
-
-
-def _same(a, b):
-    """Bit equality with zeros compared without sign and every NaN equal to every NaN (the quantiles' and indicators' tests)."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
-        return False
-    ua = np.where((a == 0) | np.isnan(a), 0.0, a)
-    ub = np.where((b == 0) | np.isnan(b), 0.0, b)
-    return np.array_equal(ua.view(np.uint64), ub.view(np.uint64))
-
-
 def _ensemble(ra, n, offset=0, n_total=None, steps=None, special_rows=True):
-    P, scen = hd.two_layer_case(n, offset, n_total)
-    e = ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS, noise_params=True)
-    e.set_params(P)
-    e.set_forcing(np.stack([np.zeros(T), 0.05 * np.arange(T)]), scen)
-    e.set_initial(1, 0.0)
-    e.set_initial(2, 0.0)
-    e.set_forcing_noise_members(SEED, offset)
-    e.run(steps)
+    e = noise_ensemble(ra, n, BOUNDS, SEED, offset, n_total, steps)
     if special_rows and e.time_index >= max(hd.RANDOM_ROWS):
         x = hd.random_rows(n, offset, n_total)
         for v in (1, 2):
@@ -111,24 +71,16 @@ def _restate(terms, ser, P, tb, te, ts):
 @pytest.fixture(scope="module")
 def cases(ra):
     """{N: (ensemble with the four diagnostics defined, {variable id: [T][N] on the host}, its parameters)}, built once."""
-    made = {}
+    def build(n):
+        e = _ensemble(ra, n)
+        if n >= 63:
+            for member, row, value in ((5, 1, np.inf), (7, 2, -np.inf), (9, 3, 5e-324)):
+                plant(e, 1, member, row, value)
+        ids = _define_two_layer(e)
+        assert list(ids.values()) == [3, 4, 5, 6]                      # V, V + 1, ... in order of definition
+        return e, _series(e, 3), e.get_params()
 
-    def get(n):
-        if n not in made:
-            e = _ensemble(ra, n)
-            if n >= 63:
-                for member, row, value in ((5, 1, np.inf), (7, 2, -np.inf), (9, 3, 5e-324)):
-                    x = e.get_series(1, row, row + 1)[0]
-                    x[member] = value
-                    e.set_state(1, row, x)
-            ids = _define_two_layer(e)
-            assert list(ids.values()) == [3, 4, 5, 6]                      # V, V + 1, ... in order of definition
-            made[n] = (e, _series(e, 3), e.get_params())
-        return made[n]
-
-    yield get
-    for e, _, _ in made.values():
-        e.close()
+    yield from built_once(build)
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -139,7 +91,7 @@ def test_two_layer_diagnostics_equal_the_restatement(ra, cases, n):
         assert np.isnan(ser[1][13:, n - 1]).all() and (ser[1][:10, n - 3] == 0.0).all() and not np.isfinite(ser[1][:, n - 2]).all()
         w = hd.weights(TL_DIAGS["twice"], P)[0]
         assert w[n - 3] == 0.0 and np.signbit(w[n - 3])                    # a weight of -0.0
-    assert np.array_equal(ser[1][list(hd.RANDOM_ROWS)], hd.random_rows(n)[0]) and np.array_equal(P, hd.two_layer_case(n)[0], equal_nan=True)
+    assert np.array_equal(ser[1][list(hd.RANDOM_ROWS)], hd.random_rows(n)[0]) and same_values(P, hd.two_layer_case(n)[0])
     got_def = e.diagnostics
     assert got_def["heat"]["terms"] == [(1, 4, 1.0), (2, 5, 1.0)]          # define_heat_content is the explicit definition
     for name, terms in TL_DIAGS.items():
@@ -148,12 +100,12 @@ def test_two_layer_diagnostics_equal_the_restatement(ra, cases, n):
             e.compute_diagnostic(name, tb, te, ts)
             got = e.get_series(name, tb, te, ts)
             want = _restate(terms, ser, P, tb, te, ts)
-            assert _bits_same(got, want), (name, tb, te, ts, np.argwhere(got.view(np.uint64) != want.view(np.uint64))[:5])
+            assert same_bits(got, want), (name, tb, te, ts, np.argwhere(got.view(np.uint64) != want.view(np.uint64))[:5])
             held = e.diagnostics[name]
             assert (held["rows_held"], held["t_begin"], held["t_stride"]) == (len(range(tb, te, ts)), tb, ts)
         e.compute_diagnostic(name)                                         # t_end=None: up to and including the time index
-        assert e.diagnostics[name]["rows_held"] == T and _bits_same(e.get_series(name), _restate(terms, ser, P, 0, T, 1))
-    assert _bits_same(e.get_series("copy"), ser[1])                         # 1.0 * x is x
+        assert e.diagnostics[name]["rows_held"] == T and same_bits(e.get_series(name), _restate(terms, ser, P, 0, T, 1))
+    assert same_bits(e.get_series("copy"), ser[1])                         # 1.0 * x is x
     if n >= 63:
         heat = e.get_series("heat")
         assert np.isposinf(heat[1, 5]) and np.isneginf(heat[2, 7]) and np.isnan(heat[13:, n - 1]).all() and np.isfinite(heat[:, :5]).all()
@@ -187,11 +139,11 @@ def test_coupled_diagnostics_of_three_and_four_terms(ra, n):
             for tb, te, ts in RANGES:
                 e.compute_diagnostic(name, tb, te, ts)
                 got, want = e.get_series(name, tb, te, ts), _restate(terms, ser, P, tb, te, ts)
-                assert _bits_same(got, want), (name, tb, te, ts)
+                assert same_bits(got, want), (name, tb, te, ts)
         four = [(v, r, s) for v, r, s in CP_DIAGS["four"]]
         rows = list(hd.RANDOM_ROWS)
         if n >= 64:                                                        # the order matters on this data
-            assert not _bits_same(hd.diagnostic_right_to_left(four, [ser[v][rows] for v, _, _ in four], P),
+            assert not same_bits(hd.diagnostic_right_to_left(four, [ser[v][rows] for v, _, _ in four], P),
                                   hd.diagnostic(four, [ser[v][rows] for v, _, _ in four], P))
 
 
@@ -220,52 +172,52 @@ def test_every_consumer_reads_the_diagnostic(ra, cases):
     vid = e.var_ids["heat"]
     e.compute_diagnostic("heat", 0, R)
     H = _restate(hd.HEAT_CONTENT, ser, P, 0, R, 1)
-    assert _bits_same(e.get_series("heat", 0, R), H) and _bits_same(e.get_series(vid, 4, R, 5, 3, 200), H[4:R:5, 3:200])
+    assert same_bits(e.get_series("heat", 0, R), H) and same_bits(e.get_series(vid, 4, R, 5, 3, 200), H[4:R:5, 3:200])
     assert np.isnan(H).any() and np.isinf(H).any()
     # the selects: plain, weighted, anomaly, grouped
     got = e.quantile_rows("heat", Q, 0, R)
-    assert _same(got["quantiles"], _np_q(H)) and np.array_equal(got["count"], (~np.isnan(H)).sum(axis=1))
+    assert same_values(got["quantiles"], _np_q(H)) and np.array_equal(got["count"], (~np.isnan(H)).sum(axis=1))
     strided = e.quantile_rows(vid, Q, 1, R, 3)
-    assert _same(strided["quantiles"], _np_q(H[1:R:3]))
+    assert same_values(strided["quantiles"], _np_q(H[1:R:3]))
     rng = np.random.default_rng(n)
     w = rng.integers(1, 1 << 30, n, dtype=np.int64)
     w[rng.random(n) < 0.2] = 0
     e.set_member_weights(w)
     wq = e.quantile_rows("heat", Q, 0, R, weighted=True)
     want, W = _np_wq(H, w)
-    assert _same(wq["quantiles"], want) and np.array_equal(wq["weight"], W)
+    assert same_values(wq["quantiles"], want) and np.array_equal(wq["weight"], W)
     e.set_baseline("heat", 5, 15)
     b = hi.baseline(H[5:15])
-    assert np.array_equal(e.baseline(), b, equal_nan=True)
+    assert same_values(e.baseline(), b)
     a = hi.anomaly(H, b)
     aq = e.quantile_rows("heat", Q, 0, R, anomaly=True)
-    assert _same(aq["quantiles"], _np_q(a)) and np.array_equal(aq["count"], (~np.isnan(a)).sum(axis=1))
+    assert same_values(aq["quantiles"], _np_q(a)) and np.array_equal(aq["count"], (~np.isnan(a)).sum(axis=1))
     group = (np.arange(n) % 3).astype(np.int32)
     e.set_member_groups(group, 3)
     gq = e.quantile_rows("heat", Q, 0, R, grouped=True)
     assert gq["quantiles"].shape == (3, R, len(Q))
     for g in range(3):
-        assert _same(gq["quantiles"][g], _np_q(H[:, group == g])), g
+        assert same_values(gq["quantiles"][g], _np_q(H[:, group == g])), g
     with e.select("heat", Q, 0, R) as s:                                   # the staged form
         while s.next_pass() is not None:
             s.commit()
-        assert _same(s.result()["quantiles"], _np_q(H))
+        assert same_values(s.result()["quantiles"], _np_q(H))
     e.clear_member_groups()
     e.clear_baseline()
     # the per-member statistics
     thr = [float(np.nanmedian(H[R - 1]))]
     ind = e.indicators("heat", 0, R, thresholds=thr)
     want = hi.indicators(H, YEARS[:R], thr)
-    assert all(_same(ind[k].to_host(), want[k]) for k in ("mean", "peak", "peak_time")) and _same(ind["crossing"][0].to_host(), want["crossing"][0])
+    assert all(same_values(ind[k].to_host(), want[k]) for k in ("mean", "peak", "peak_time")) and same_values(ind["crossing"][0].to_host(), want["crossing"][0])
     for d in ("mean", "linear", "difference"):
         got, want = e.variability("heat", 0, R, detrend=d), hv.variability(H, d)
         for k in hv.NAMES:
-            assert np.array_equal(got[k].to_host(), want[k], equal_nan=True), (d, k)
+            assert same_values(got[k].to_host(), want[k]), (d, k)
     sp = e.spectrum("heat", 0, R, detrend="difference", bands=3)
     want = hs.spectrum(H, "difference", sp["edges"])
     for k in hs.FIRST:
-        assert np.array_equal(sp[k].to_host(), want[k], equal_nan=True), k
-    assert all(np.array_equal(p.to_host(), q, equal_nan=True) for p, q in zip(sp["power"], want["power"]))
+        assert same_values(sp[k].to_host(), want[k]), k
+    assert all(same_values(p.to_host(), q) for p, q in zip(sp["power"], want["power"]))
     # the stored likelihoods: bit for bit without the normalisation's logarithm, within its bound (rtol 1e-13, as the stored
     # likelihood's own tests) with it
     tidx = list(range(4, R, 4))
@@ -297,48 +249,40 @@ def test_every_consumer_reads_the_diagnostic(ra, cases):
 
 
 # ---------------------------------------------------------------------------------------------- storage layouts
-def _chain():
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_windowed_graph_with_an_output_store(ra):
     """A windowed graph that keeps every 12th row: a diagnostic over two carbon pools of one ensemble, by names, from rows in the
     output store and rows in the window; a range with a row that is no longer resident is refused and the rows held stay."""
-    model = _chain().build_chain(65, 30, "topological", steps_per_year=12, series_window=16, output_stride=12)
+    model = magicc_chain().build_chain(65, 30, "topological", steps_per_year=12, series_window=16, output_stride=12)
     try:
         model.run()
-        plant, soil = "Carbon Pool|Plant", "Carbon Pool|Soil"
-        ens, v_plant = model.variable_home(plant)
+        plant_pool, soil = "Carbon Pool|Plant", "Carbon Pool|Soil"
+        ens, v_plant = model.variable_home(plant_pool)
         assert model.variable_home(soil)[0] is ens
         with pytest.raises(ValueError, match="share one home"):
-            model.define_diagnostic("mixed", [(plant, None), ("Atmospheric Concentration|CO2", None)])
+            model.define_diagnostic("mixed", [(plant_pool, None), ("Atmospheric Concentration|CO2", None)])
         with pytest.raises(ValueError, match="no parameter of"):
-            model.define_diagnostic("wrong", [(plant, "CO2Budget.gtc_per_ppm")])
-        vid = model.define_diagnostic("pools", [(plant, "TerrestrialCarbon.beta", 2.0), (soil, None)])
+            model.define_diagnostic("wrong", [(plant_pool, "CO2Budget.gtc_per_ppm")])
+        vid = model.define_diagnostic("pools", [(plant_pool, "TerrestrialCarbon.beta", 2.0), (soil, None)])
         assert model.variable_home("pools") == (ens, vid) and vid == ens.n_vars
         beta = ens.get_params()[model.param_home["TerrestrialCarbon.beta"][1]]
         terms = [(0, 0, 2.0), (1, None, 1.0)]
         n_times = ens.n_times
         model.compute_diagnostic("pools", 0, n_times, 12)                  # the output store, and the last row from the window
-        want = hd.diagnostic(terms, [model.get_series(plant, t_stride=12), model.get_series(soil, t_stride=12)], beta[None, :])
-        assert _bits_same(model.get_series("pools", t_stride=12), want) and np.isfinite(want).any()
+        want = hd.diagnostic(terms, [model.get_series(plant_pool, t_stride=12), model.get_series(soil, t_stride=12)], beta[None, :])
+        assert same_bits(model.get_series("pools", t_stride=12), want) and np.isfinite(want).any()
         got = model.variability("pools", 0, n_times, 12, detrend="difference")
         ref = hv.variability(want, "difference")
-        assert all(np.array_equal(got[k].to_host(), ref[k], equal_nan=True) for k in hv.NAMES)
+        assert all(same_values(got[k].to_host(), ref[k]) for k in hv.NAMES)
         q = model.quantile_rows("pools", Q, t_stride=12)
-        assert _same(q["quantiles"], _np_q(want))
-        assert _code(model.compute_diagnostic, "pools", 0, 9, 3) == 2      # rows 3 and 6 of the sources are not resident any more
-        assert ens.diagnostics["pools"]["rows_held"] == len(want) and _bits_same(model.get_series("pools", t_stride=12), want)
+        assert same_values(q["quantiles"], _np_q(want))
+        assert refusal_code(model.compute_diagnostic, "pools", 0, 9, 3) == 2      # rows 3 and 6 of the sources are not resident any more
+        assert ens.diagnostics["pools"]["rows_held"] == len(want) and same_bits(model.get_series("pools", t_stride=12), want)
         k = model.time_index
         w0 = k - 1
         model.compute_diagnostic("pools", w0)                              # the window's last rows, up to the current step
-        win = hd.diagnostic(terms, [model.get_series(plant, t_begin=w0, t_end=k + 1), model.get_series(soil, t_begin=w0, t_end=k + 1)], beta[None, :])
-        assert _bits_same(model.get_series("pools", t_begin=w0, t_end=k + 1), win)
-        assert _code(model.get_series, "pools", t_stride=12) == 2          # the strided range is held no longer
+        win = hd.diagnostic(terms, [model.get_series(plant_pool, t_begin=w0, t_end=k + 1), model.get_series(soil, t_begin=w0, t_end=k + 1)], beta[None, :])
+        assert same_bits(model.get_series("pools", t_begin=w0, t_end=k + 1), win)
+        assert refusal_code(model.get_series, "pools", t_stride=12) == 2          # the strided range is held no longer
     finally:
         model.close()
 
@@ -355,14 +299,14 @@ def test_rows_go_stale_with_every_writer_and_come_back_with_a_compute(ra):
             k = e.time_index
             e.compute_diagnostic(vid)
             H = hd.diagnostic(hd.HEAT_CONTENT, [e.get_series(1, 0, k + 1), e.get_series(2, 0, k + 1)], e.get_params())
-            assert _bits_same(e.get_series(vid, 0, k + 1), H), what
+            assert same_bits(e.get_series(vid, 0, k + 1), H), what
             assert e.diagnostics["Ocean Heat Content"]["rows_held"] == k + 1
             return H
 
         def stale(what):
-            assert _code(e.summary, vid, 0) == 2, what
-            assert _code(e.get_series, vid, 0, 1) == 2 and _code(e.quantile_rows, vid, Q, 0, 1) == 2, what
-            assert _code(e.loglik, [vid], [0], [0.0], [1.0]) == 2 and _code(e.indicators, vid, 0, 1) == 2, what
+            assert refusal_code(e.summary, vid, 0) == 2, what
+            assert refusal_code(e.get_series, vid, 0, 1) == 2 and refusal_code(e.quantile_rows, vid, Q, 0, 1) == 2, what
+            assert refusal_code(e.loglik, [vid], [0], [0.0], [1.0]) == 2 and refusal_code(e.indicators, vid, 0, 1) == 2, what
             from rscm_amd._lib import RscmGpuError
             with pytest.raises(RscmGpuError, match="is stale: compute it again"):
                 e.set_baseline(vid, 0, 1)
@@ -373,7 +317,7 @@ def test_rows_go_stale_with_every_writer_and_come_back_with_a_compute(ra):
         # what hands out pointers does not move the epoch
         e.params_vector(4)
         e.series_devptr(1)
-        assert _bits_same(e.get_series(vid, 0, 41), first) and e.summary(vid, 40)["count"] > 0
+        assert same_bits(e.get_series(vid, 0, 41), first) and e.summary(vid, 40)["count"] > 0
         writers = {
             "run": lambda: e.run(50),
             "rewind": lambda: e.rewind(),
@@ -399,14 +343,14 @@ def test_refusals(ra):
     lib_q = [0.5]
     with _ensemble(ra, n) as e:
         # definitions
-        assert _code(e.define_diagnostic, "none", []) == 1
-        assert _code(e.define_diagnostic, "five", [(1, None)] * 5) == 1
+        assert refusal_code(e.define_diagnostic, "none", []) == 1
+        assert refusal_code(e.define_diagnostic, "five", [(1, None)] * 5) == 1
         for var in (0, 3, -1):
-            assert _code(e.define_diagnostic, "var", [(var, None)]) == 1
+            assert refusal_code(e.define_diagnostic, "var", [(var, None)]) == 1
         for row in (-2, 8):
-            assert _code(e.define_diagnostic, "row", [(1, row)]) == 1
+            assert refusal_code(e.define_diagnostic, "row", [(1, row)]) == 1
         for scale in (np.nan, np.inf, -np.inf):
-            assert _code(e.define_diagnostic, "scale", [(1, None, scale)]) == 1
+            assert refusal_code(e.define_diagnostic, "scale", [(1, None, scale)]) == 1
         assert e.diagnostics == {} and set(e.var_ids) == {"Effective Radiative Forcing", "Surface Temperature", "Deep Ocean Temperature"}
         ids = [e.define_diagnostic(f"d{k}", [(1, k, 1.0)]) for k in range(4)]
         assert ids == [3, 4, 5, 6]
@@ -414,41 +358,41 @@ def test_refusals(ra):
         assert e._lib.rscm_ens_n_diagnostics(e._h, C.byref(n_diag)) == 0 and n_diag.value == 4
         n_vars = C.c_int32()
         assert e._lib.rscm_ens_n_vars(e._h, C.byref(n_vars)) == 0 and n_vars.value == 3
-        assert _code(e.define_diagnostic, "fifth", [(1, None)]) == 1 and "fifth" not in e.var_ids
-        assert _code(e.define_diagnostic, "of a diagnostic", [(3, None)]) == 1
+        assert refusal_code(e.define_diagnostic, "fifth", [(1, None)]) == 1 and "fifth" not in e.var_ids
+        assert refusal_code(e.define_diagnostic, "of a diagnostic", [(3, None)]) == 1
         with pytest.raises(ValueError):
             e.define_diagnostic("d0", [(1, None)])                         # the name is taken
         with pytest.raises(ValueError):
             e.define_diagnostic("by name", [("d0", None)])
         # ranges and ids
         for tb, te, ts in ((5, 3, 1), (0, T + 1, 1), (4, 4, 1), (0, 10, 0), (-1, 4, 1)):
-            assert _code(e.compute_diagnostic, "d0", tb, te, ts) == 1, (tb, te, ts)
+            assert refusal_code(e.compute_diagnostic, "d0", tb, te, ts) == 1, (tb, te, ts)
         for var in (1, 0, 7, 99, -1):
-            assert _code(e.compute_diagnostic, var, 0, 4) == 1
+            assert refusal_code(e.compute_diagnostic, var, 0, 4) == 1
             assert e._lib.rscm_ens_diagnostic(e._h, var, None, None, None, None, None, None, None) == 1
         # a consumer on rows outside the held range; a diagnostic never computed
-        assert _code(e.get_series, "d1", 0, 4) == 2 and _code(e.variability, "d1", 0, 10) == 2
+        assert refusal_code(e.get_series, "d1", 0, 4) == 2 and refusal_code(e.variability, "d1", 0, 10) == 2
         e.compute_diagnostic("d0", 0, 20)
         e.variability("d0", 0, 20)
-        assert _code(e.variability, "d0", 0, 30) == 2 and _code(e.get_series, "d0", 0, 30) == 2 and _code(e.summary, "d0", 25) == 2
-        assert _code(e.quantile_rows, "d0", lib_q, 0, 30) == 2 and _code(e.loglik, ["d0"], [25], [0.0], [1.0]) == 2
-        assert _code(e.loglik, ["d0"], [5], [0.0], [1.0], reference={"d0": (15, 25)}) == 2
-        assert _code(e.set_baseline, "d0", 18, 22) == 2 and _code(e.spectrum, "d0", 10, 40) == 2
+        assert refusal_code(e.variability, "d0", 0, 30) == 2 and refusal_code(e.get_series, "d0", 0, 30) == 2 and refusal_code(e.summary, "d0", 25) == 2
+        assert refusal_code(e.quantile_rows, "d0", lib_q, 0, 30) == 2 and refusal_code(e.loglik, ["d0"], [25], [0.0], [1.0]) == 2
+        assert refusal_code(e.loglik, ["d0"], [5], [0.0], [1.0], reference={"d0": (15, 25)}) == 2
+        assert refusal_code(e.set_baseline, "d0", 18, 22) == 2 and refusal_code(e.spectrum, "d0", 10, 40) == 2
         e.compute_diagnostic("d0", 0, 30, 3)
-        assert _code(e.indicators, "d0", 0, 30) == 2                        # row 1 is not one of the strided rows
+        assert refusal_code(e.indicators, "d0", 0, 30) == 2                        # row 1 is not one of the strided rows
         e.indicators("d0", 0, 30, 3)
         # who keeps refusing the id
-        assert _code(e.series_devptr, "d0") == 1 and _code(e.summary_series, "d0") == 1 and _code(e.quantile_series, "d0", lib_q) == 1
-        assert _code(e.set_state, "d0", 3, 0.0) == 1 and _code(e.set_initial, "d0", 0.0) == 1
+        assert refusal_code(e.series_devptr, "d0") == 1 and refusal_code(e.summary_series, "d0") == 1 and refusal_code(e.quantile_series, "d0", lib_q) == 1
+        assert refusal_code(e.set_state, "d0", 3, 0.0) == 1 and refusal_code(e.set_initial, "d0", 0.0) == 1
         # a select in flight: define, compute and clear all refuse
         with e.select("d0", lib_q, 0, 30, 3) as s:
-            assert _code(e.compute_diagnostic, "d0", 0, 10) == 2 and _code(e.clear_diagnostics) == 2
+            assert refusal_code(e.compute_diagnostic, "d0", 0, 10) == 2 and refusal_code(e.clear_diagnostics) == 2
             while s.next_pass() is not None:
                 s.commit()
         e.clear_diagnostics()
-        assert e.diagnostics == {} and "d0" not in e.var_ids and _code(e.compute_diagnostic, 3, 0, 4) == 1
+        assert e.diagnostics == {} and "d0" not in e.var_ids and refusal_code(e.compute_diagnostic, 3, 0, 4) == 1
         with e.select(1, lib_q, 0, 30) as s:
-            assert _code(e.define_diagnostic, "late", [(1, None)]) == 2 and "late" not in e.var_ids
+            assert refusal_code(e.define_diagnostic, "late", [(1, None)]) == 2 and "late" not in e.var_ids
             while s.next_pass() is not None:
                 s.commit()
         assert e.define_diagnostic("again", [(2, None)]) == 3               # the id is free again
@@ -457,7 +401,7 @@ def test_refusals(ra):
     # rows beyond the time index; a handle that stores only its initial row
     with _ensemble(ra, n, steps=10) as e:
         vid = e.define_heat_content()
-        assert _code(e.compute_diagnostic, vid, 0, 20) == 2
+        assert refusal_code(e.compute_diagnostic, vid, 0, 20) == 2
         e.compute_diagnostic(vid)
         assert e.diagnostics["Ocean Heat Content"]["rows_held"] == 11
     with ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS, store_series=False) as e:
@@ -466,10 +410,10 @@ def test_refusals(ra):
         e.set_initial(1, 0.5)
         e.set_initial(2, 0.25)
         vid = e.define_heat_content()
-        assert _code(e.compute_diagnostic, vid, 0, 2) == 2
+        assert refusal_code(e.compute_diagnostic, vid, 0, 2) == 2
         e.compute_diagnostic(vid, 0, 1)
         P = e.get_params()
-        assert _bits_same(e.get_series(vid, 0, 1)[0], P[4] * 0.5 + P[5] * 0.25)
+        assert same_bits(e.get_series(vid, 0, 1)[0], P[4] * 0.5 + P[5] * 0.25)
     with ra.Ensemble(ra.KIND_UDEB, 4, BOUNDS) as e:
         with pytest.raises(ValueError):
             e.define_heat_content()
@@ -485,14 +429,14 @@ def test_linked_inputs_fused_runs_and_samplers_refuse_a_diagnostic(ra):
         e.run()
         vid = e.define_heat_content()
         e.compute_diagnostic(vid)
-        assert _code(consumer.link_input, 0, e, vid) == 1
-        assert _code(e.run_loglik, [vid], [5], [0.0], [1.0]) == 1
+        assert refusal_code(consumer.link_input, 0, e, vid) == 1
+        assert refusal_code(e.run_loglik, [vid], [5], [0.0], [1.0]) == 1
         assert e.diagnostics["Ocean Heat Content"]["rows_held"] == T        # (neither call ran anything)
         e.rewind()                                                         # (the fused run starts from index 0)
         e.compute_diagnostic(vid, 0, 1)
         assert e.summary(vid, 0)["count"] == n
         e.run_loglik([1], [5], [0.0], [1.0])                               # the fused run leaves the time index alone, but it is a run
-        assert _code(e.summary, vid, 0) == 2
+        assert refusal_code(e.summary, vid, 0) == 2
     from rscm_amd import calibrate as cal
     from rscm_amd import core
     from rscm_amd.two_layer import TwoLayerBuilder
@@ -509,7 +453,7 @@ def test_linked_inputs_fused_runs_and_samplers_refuse_a_diagnostic(ra):
         assert ens.diagnostics["Ocean Heat Content"]["terms"] == [(1, 4, 1.0), (2, 5, 1.0)]
         ens.compute_diagnostic("Ocean Heat Content")
         want = 8.0 * ens.get_series(1) + 100.0 * ens.get_series(2)
-        assert _bits_same(ens.get_series("Ocean Heat Content"), want)
+        assert same_bits(ens.get_series("Ocean Heat Content"), want)
         assert "Ocean Heat Content" not in model.timeseries().names()
     finally:
         model.close()
@@ -536,22 +480,22 @@ def test_two_shards_give_the_halves(ra, cases):
         with _ensemble(ra, count, offset, n, special_rows=False) as h:
             vid = h.define_heat_content("heat")
             h.compute_diagnostic(vid, 13, T)
-            assert _bits_same(h.get_series(vid, 13, T), whole[:, offset:offset + count]), offset
+            assert same_bits(h.get_series(vid, 13, T), whole[:, offset:offset + count]), offset
     # ShardedEnsemble forwards define and compute to its block; the global select and constrain() then take the name
     from rscm_amd.distributed import ShardedEnsemble
     sh = ShardedEnsemble(n, lambda count, device: _ensemble(ra, count, special_rows=False), rank=0, world=1)
     try:
         vid = sh.define_diagnostic("heat", [("Surface Temperature", 4), ("Deep Ocean Temperature", 5)])
         sh.compute_diagnostic("heat", 13, T)
-        assert _bits_same(sh.ensemble.get_series(vid, 13, T), whole)
+        assert same_bits(sh.ensemble.get_series(vid, 13, T), whole)
         got = sh.quantile_rows_global("heat", Q, 13, T)
-        assert _same(got["quantiles"], _np_q(whole)) and np.array_equal(got["count"], (~np.isnan(whole)).sum(axis=1))
+        assert same_values(got["quantiles"], _np_q(whole)) and np.array_equal(got["count"], (~np.isnan(whole)).sum(axis=1))
         tidx, obs = [20, 40], [float(np.nanmedian(whole[20 - 13])), float(np.nanmedian(whole[40 - 13]))]
         ll_max, bits = sh.constrain(["heat"] * 2, tidx, obs, [5.0, 5.0])
         want = hl.loglik({vid: np.vstack([np.full((13, n), np.nan), whole])}, [vid] * 2, tidx, obs, [5.0, 5.0])
         assert ll_max == want[np.isfinite(want) & (sh.ensemble.status() == 0)].max() and sh.ensemble.member_weights().max() == 2 ** bits
         wq = sh.quantile_rows_global("heat", Q, 13, T, weighted=True)
-        assert _same(wq["quantiles"], _np_wq(whole, sh.ensemble.member_weights())[0])
+        assert same_values(wq["quantiles"], _np_wq(whole, sh.ensemble.member_weights())[0])
     finally:
         sh.ensemble.close()
 
@@ -571,6 +515,6 @@ def test_a_posterior_defines_what_its_source_defines(ra, cases):
         assert all(v["rows_held"] == 0 for v in dst.diagnostics.values()) and dst.time_index == T - 1
         dst.compute_diagnostic("heat", T - 1, T)
         want = hd.diagnostic(hd.HEAT_CONTENT, [dst.get_series(1, T - 1, T), dst.get_series(2, T - 1, T)], dst.get_params())
-        assert _bits_same(dst.get_series("heat", T - 1, T), want)
+        assert same_bits(dst.get_series("heat", T - 1, T), want)
     finally:
         dst.close()

@@ -24,13 +24,14 @@ from tests import host_indicators as hi
 from tests import host_likelihood as hl
 from tests import host_spectrum as hs
 from tests import host_variability as hv
-from tests.helpers import two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import refusal_code
+from tests.helpers import annual_bounds, same_bits, same_values, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 T = 72
-YEARS = np.arange(1850, 1850 + T, dtype=np.float64)
-BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+YEARS, BOUNDS = annual_bounds(T)
 SEED = 20260422
 SIZES = [1, 63, 64, 65, 255, 256, 257, 1000]
 _HPP = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "rscm_amd", "csrc", "diagnostic.hpp")).read()
@@ -41,38 +42,6 @@ RANGES = ([(0, R, 1) for R in (1, BATCH - 1, BATCH, BATCH + 1, 2 * BATCH + 1, TI
           + [(0, T, 1), (2, T, 3), (T - 5, T, 1)])
 Q = [0.05, 0.5, 0.95]
 TS, TD = 1, 2
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
-
-
-def _bits_same(a, b):
-    """Bit for bit, the sign of a zero included; any NaN equal to any NaN."""
-    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(((a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))).all())
-
-
-def _same(a, b):
-    """Bit equality with zeros compared without sign and every NaN equal to every NaN (the quantiles' and indicators' tests)."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    if a.shape != b.shape or not np.array_equal(np.isnan(a), np.isnan(b)):
-        return False
-    ua = np.where((a == 0) | np.isnan(a), 0.0, a)
-    ub = np.where((b == 0) | np.isnan(b), 0.0, b)
-    return np.array_equal(ua.view(np.uint64), ub.view(np.uint64))
 
 
 def _table(K):
@@ -150,7 +119,7 @@ class Case:
             for tb, te, ts in ranges:
                 e.compute_diagnostic(vid, tb, te, ts)
                 got, want = e.get_series(vid, tb, te, ts), self.want(quantity, tb, te, ts, scale)
-                assert _bits_same(got, want), (quantity, tb, te, ts, np.argwhere(got.view(np.uint64) != want.view(np.uint64))[:5])
+                assert same_bits(got, want), (quantity, tb, te, ts, np.argwhere(got.view(np.uint64) != want.view(np.uint64))[:5])
                 held = e.diagnostics[e_name(e, vid)]
                 assert (held["rows_held"], held["t_begin"], held["t_stride"]) == (len(range(tb, te, ts)), tb, ts)
 
@@ -197,11 +166,11 @@ def test_plain_handle_with_two_scenarios(ra, n):
         _special_members(c)
         # on a plain handle the forcing is the member's scenario's table value, exactly; the last row is served (index T - 1 exists)
         c.e.compute_diagnostic("Member Forcing", 0, T)
-        assert _bits_same(c.e.get_series("Member Forcing"), c.table[c.scen].T)
+        assert same_bits(c.e.get_series("Member Forcing"), c.table[c.scen].T)
         if n >= 64:
             rows = list(hd.RANDOM_ROWS)
             wrong = hb.imbalance_wrong_association(c.ts[rows], c.td[rows], c.P, c.F[:, rows].T)
-            assert not _bits_same(wrong, c.want("imbalance", 10, 13, 1))        # the association matters on this data
+            assert not same_bits(wrong, c.want("imbalance", 10, 13, 1))        # the association matters on this data
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -234,8 +203,8 @@ def test_noise_kinds_on_a_plain_and_on_a_mix_handle(ra, kind, K):
         base = hb.member_forcing(c.table, c.P, c.scen, K)                   # [N][T] without the noise
         c.e.compute_diagnostic(ids["forcing"], 0, T)
         with np.errstate(all="ignore"):
-            assert _bits_same(c.e.get_series(ids["forcing"]), base.T + c.e.forcing_noise_rows(0, T))
-        assert not _bits_same(c.e.get_series(ids["forcing"])[:, :5], base.T[:, :5])
+            assert same_bits(c.e.get_series(ids["forcing"]), base.T + c.e.forcing_noise_rows(0, T))
+        assert not same_bits(c.e.get_series(ids["forcing"])[:, :5], base.T[:, :5])
 
 
 def test_upstream_source_reads_the_next_index(ra):
@@ -246,10 +215,10 @@ def test_upstream_source_reads_the_next_index(ra):
         c.check({q: ids[q] for q in ("forcing", "imbalance")}, ranges)
         c.check({q: ids[q] for q in ("response", "deep_uptake")})
         c.e.compute_diagnostic(ids["forcing"], 0, T - 1)
-        assert _bits_same(c.e.get_series(ids["forcing"], 0, T - 1), c.table[c.scen].T[1:])
+        assert same_bits(c.e.get_series(ids["forcing"], 0, T - 1), c.table[c.scen].T[1:])
         for q in ("forcing", "imbalance"):
             c.e.compute_diagnostic(ids[q], 0, T - 1)
-            assert _code(c.e.compute_diagnostic, ids[q], 0, T) == 1 and _code(c.e.compute_diagnostic, ids[q], T - 1, T) == 1
+            assert refusal_code(c.e.compute_diagnostic, ids[q], 0, T) == 1 and refusal_code(c.e.compute_diagnostic, ids[q], T - 1, T) == 1
             assert c.e.diagnostics[e_name(c.e, ids[q])]["rows_held"] == T - 1           # a refused compute leaves the rows held
         c.e.compute_diagnostic(ids["response"], T - 1, T)
 
@@ -280,7 +249,7 @@ def test_the_response_without_curvature_is_the_linear_diagnostic(ra):
         r, lin = e.define_energy_budget("response"), e.define_diagnostic("lambda0 Ts", [(TS, 0, 1.0)])
         e.compute_diagnostic(r, 0, T)
         e.compute_diagnostic(lin, 0, T)
-        assert _bits_same(e.get_series(r), e.get_series(lin)) and np.isfinite(e.get_series(r)[:, :5]).all()
+        assert same_bits(e.get_series(r), e.get_series(lin)) and np.isfinite(e.get_series(r)[:, :5]).all()
         assert e.diagnostics["lambda0 Ts"]["quantity"] is None and e.diagnostics["lambda0 Ts"]["scale"] is None
         q, s = C.c_int32(-1), C.c_double(-1.0)
         assert e._lib.rscm_ens_diagnostic_quantity(e._h, lin, C.byref(q), C.byref(s)) == 0 and (q.value, s.value) == (0, 0.0)
@@ -313,23 +282,23 @@ def noisy(ra):
 def test_the_selects_read_the_imbalance(noisy):
     c, vid, N = noisy
     e, n, R, name = c.e, c.n, 48, "Top of Atmosphere Imbalance"
-    assert e.var_ids[name] == vid and _bits_same(e.get_series(name, 0, R), N) and _bits_same(e.get_series(vid, 4, R, 5, 3, 200), N[4:R:5, 3:200])
+    assert e.var_ids[name] == vid and same_bits(e.get_series(name, 0, R), N) and same_bits(e.get_series(vid, 4, R, 5, 3, 200), N[4:R:5, 3:200])
     assert np.isnan(N).any() and np.isfinite(N[:, :5]).all()
     got = e.quantile_rows(name, Q, 0, R)
-    assert _same(got["quantiles"], _np_q(N)) and np.array_equal(got["count"], (~np.isnan(N)).sum(axis=1))
+    assert same_values(got["quantiles"], _np_q(N)) and np.array_equal(got["count"], (~np.isnan(N)).sum(axis=1))
     group = (np.arange(n) % 3).astype(np.int32)
     e.set_member_groups(group, 3)
     gq = e.quantile_rows(name, Q, 0, R, grouped=True)
     assert gq["quantiles"].shape == (3, R, len(Q))
     for g in range(3):
-        assert _same(gq["quantiles"][g], _np_q(N[:, group == g])), g
+        assert same_values(gq["quantiles"][g], _np_q(N[:, group == g])), g
     e.clear_member_groups()
     e.set_baseline(name, 5, 15)
     b = hi.baseline(N[5:15])
-    assert np.array_equal(e.baseline(), b, equal_nan=True)
+    assert same_values(e.baseline(), b)
     a = hi.anomaly(N, b)
     aq = e.quantile_rows(name, Q, 0, R, anomaly=True)
-    assert _same(aq["quantiles"], _np_q(a)) and np.array_equal(aq["count"], (~np.isnan(a)).sum(axis=1))
+    assert same_values(aq["quantiles"], _np_q(a)) and np.array_equal(aq["count"], (~np.isnan(a)).sum(axis=1))
     e.clear_baseline()
 
 
@@ -339,25 +308,25 @@ def test_the_member_statistics_read_the_imbalance(noisy):
     thr = [float(np.nanmedian(N[R - 1]))]
     ind = e.indicators(name, 0, R, thresholds=thr)
     want = hi.indicators(N, YEARS[:R], thr)
-    assert all(_same(ind[k].to_host(), want[k]) for k in ("mean", "peak", "peak_time")) and _same(ind["crossing"][0].to_host(), want["crossing"][0])
+    assert all(same_values(ind[k].to_host(), want[k]) for k in ("mean", "peak", "peak_time")) and same_values(ind["crossing"][0].to_host(), want["crossing"][0])
     for d in ("mean", "linear", "difference"):
         got, want = e.variability(name, 0, R, detrend=d), hv.variability(N, d)
         for k in hv.NAMES:
-            assert np.array_equal(got[k].to_host(), want[k], equal_nan=True), (d, k)
+            assert same_values(got[k].to_host(), want[k]), (d, k)
     sp = e.spectrum(name, 0, R, detrend="linear", bands=3)
     want = hs.spectrum(N, "linear", sp["edges"])
     for k in hs.FIRST:
-        assert np.array_equal(sp[k].to_host(), want[k], equal_nan=True), k
-    assert all(np.array_equal(p.to_host(), q, equal_nan=True) for p, q in zip(sp["power"], want["power"]))
+        assert same_values(sp[k].to_host(), want[k]), k
+    assert all(same_values(p.to_host(), q) for p, q in zip(sp["power"], want["power"]))
     ts = c.ts[:R]
     for dx, dy, lags in (("linear", "linear", 0), ("mean", "difference", 2)):
         got = [v.to_host() for v in hc.flat(e.covariability("Surface Temperature", name, 0, R, 1, dx, dy, lags))]
         for j, (g, w) in enumerate(zip(got, hc.flat(hc.covariability(ts, N, dx, dy, lags)))):
-            assert np.array_equal(g, w, equal_nan=True), (dx, dy, lags, j)
+            assert same_values(g, w), (dx, dy, lags, j)
     xs = e.cross_spectrum("Surface Temperature", name, 0, R, 1, "linear", "linear", bands=3)
     got = [v.to_host() for v in hx.flat(xs)]
     for j, (g, w) in enumerate(zip(got, hx.flat(hx.cross_spectrum(ts, N, "linear", "linear", xs["edges"])))):
-        assert np.array_equal(g, w, equal_nan=True), j
+        assert same_values(g, w), j
 
 
 def test_the_likelihood_and_the_summary_read_the_imbalance(noisy):
@@ -417,14 +386,14 @@ def test_staleness_follows_the_write_epoch_and_the_forcing_epoch(ra):
             for q in names:
                 e.compute_diagnostic(ids[q])
                 want = (hd.diagnostic(hd.HEAT_CONTENT, [c.ts[:k + 1], c.td[:k + 1]], c.P) if q == "heat" else c.want(q, 0, k + 1, 1))
-                assert _bits_same(e.get_series(ids[q], 0, k + 1), want), (what, q)
+                assert same_bits(e.get_series(ids[q], 0, k + 1), want), (what, q)
                 assert e.diagnostics[e_name(e, ids[q])]["rows_held"] == k + 1
 
         def stale(what, names=tuple(ids)):
             from rscm_amd._lib import RscmGpuError
             for q in names:
                 vid = ids[q]
-                assert _code(e.summary, vid, 0) == 2 and _code(e.get_series, vid, 0, 1) == 2 and _code(e.quantile_rows, vid, Q, 0, 1) == 2, (what, q)
+                assert refusal_code(e.summary, vid, 0) == 2 and refusal_code(e.get_series, vid, 0, 1) == 2 and refusal_code(e.quantile_rows, vid, Q, 0, 1) == 2, (what, q)
                 with pytest.raises(RscmGpuError, match="is stale: compute it again"):
                     e.set_baseline(vid, 0, 1)
                 assert e.diagnostics[e_name(e, vid)]["rows_held"] == 0, (what, q)
@@ -486,14 +455,14 @@ def test_refusals(ra):
         for quantity in (0, 5, -1):
             assert e._lib.rscm_ens_define_energy_budget(e._h, quantity, 1.0, C.byref(vid)) == 1
         for scale in (np.nan, np.inf, -np.inf):
-            assert _code(e.define_energy_budget, "imbalance", "scaled", scale) == 1
+            assert refusal_code(e.define_energy_budget, "imbalance", "scaled", scale) == 1
         assert e._lib.rscm_ens_define_energy_budget(e._h, 4, 1.0, None) == 1
         assert e.diagnostics == {} and "scaled" not in e.var_ids
         ids = _define_all(e)
         n_diag = C.c_int32()
         assert e._lib.rscm_ens_n_diagnostics(e._h, C.byref(n_diag)) == 0 and n_diag.value == 4
-        assert _code(e.define_energy_budget, "imbalance", "fifth") == 1 and "fifth" not in e.var_ids
-        assert _code(e.define_heat_content) == 1                            # the slots are the linear diagnostics' too
+        assert refusal_code(e.define_energy_budget, "imbalance", "fifth") == 1 and "fifth" not in e.var_ids
+        assert refusal_code(e.define_heat_content) == 1                            # the slots are the linear diagnostics' too
         with pytest.raises(ValueError):
             e.define_energy_budget("imbalance")                             # the default name is taken
         with pytest.raises(ValueError):
@@ -501,44 +470,44 @@ def test_refusals(ra):
         assert e._lib.rscm_ens_diagnostic_quantity(e._h, 2, None, None) == 1 and e._lib.rscm_ens_diagnostic_quantity(e._h, 7, None, None) == 1
         # ranges, as for any diagnostic
         for tb, te, ts in ((5, 3, 1), (0, T + 1, 1), (4, 4, 1), (0, 10, 0), (-1, 4, 1)):
-            assert _code(e.compute_diagnostic, ids["imbalance"], tb, te, ts) == 1, (tb, te, ts)
+            assert refusal_code(e.compute_diagnostic, ids["imbalance"], tb, te, ts) == 1, (tb, te, ts)
         # a select in flight: define and compute refuse
         e.compute_diagnostic(ids["imbalance"], 0, 30)
         with e.select(ids["imbalance"], [0.5], 0, 30) as s:
-            assert _code(e.compute_diagnostic, ids["imbalance"], 0, 10) == 2 and _code(e.clear_diagnostics) == 2
+            assert refusal_code(e.compute_diagnostic, ids["imbalance"], 0, 10) == 2 and refusal_code(e.clear_diagnostics) == 2
             while s.next_pass() is not None:
                 s.commit()
         e.clear_diagnostics()
-        assert e.diagnostics == {} and "Member Forcing" not in e.var_ids and _code(e.compute_diagnostic, 3, 0, 4) == 1
+        assert e.diagnostics == {} and "Member Forcing" not in e.var_ids and refusal_code(e.compute_diagnostic, 3, 0, 4) == 1
         with e.select(TS, [0.5], 0, 30) as s:
-            assert _code(e.define_energy_budget, "response") == 2 and "Radiative Response" not in e.var_ids
+            assert refusal_code(e.define_energy_budget, "response") == 2 and "Radiative Response" not in e.var_ids
             while s.next_pass() is not None:
                 s.commit()
         assert e.define_toa_imbalance() == 3                                # the id is free again
         # the fused run + likelihood refuses the id as it refuses any diagnostic
-        assert _code(e.run_loglik, [3], [5], [0.0], [1.0]) == 1
+        assert refusal_code(e.run_loglik, [3], [5], [0.0], [1.0]) == 1
     # rows beyond the time index
     with Case(ra, n, steps=10) as c:
         vid = c.e.define_toa_imbalance()
-        assert _code(c.e.compute_diagnostic, vid, 0, 20) == 2
+        assert refusal_code(c.e.compute_diagnostic, vid, 0, 20) == 2
         c.e.compute_diagnostic(vid)
         assert c.e.diagnostics["Top of Atmosphere Imbalance"]["rows_held"] == 11
     # another kind
     with ra.Ensemble(ra.KIND_UDEB, 4, BOUNDS) as e:
-        assert _code(e.define_energy_budget, "response") == 1 and _code(e.define_toa_imbalance) == 1
+        assert refusal_code(e.define_energy_budget, "response") == 1 and refusal_code(e.define_toa_imbalance) == 1
     with ra.Ensemble(ra.KIND_COUPLED, 4, BOUNDS) as e:
-        assert _code(e.define_energy_budget, "forcing") == 1
+        assert refusal_code(e.define_energy_budget, "forcing") == 1
     # forcing never set, parameters never set
     with ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS) as e:
         ids = {q: e.define_energy_budget(q) for q in ("forcing", "response", "imbalance")}
         e.set_initial(TS, 0.5)
         e.set_initial(TD, 0.25)
-        assert all(_code(e.compute_diagnostic, v, 0, 1) == 2 for v in ids.values())     # no parameters
+        assert all(refusal_code(e.compute_diagnostic, v, 0, 1) == 2 for v in ids.values())     # no parameters
         P = two_layer_params(n)
         e.set_params(P)
-        assert _code(e.compute_diagnostic, ids["forcing"], 0, 1) == 2 and _code(e.compute_diagnostic, ids["imbalance"], 0, 1) == 2
+        assert refusal_code(e.compute_diagnostic, ids["forcing"], 0, 1) == 2 and refusal_code(e.compute_diagnostic, ids["imbalance"], 0, 1) == 2
         e.compute_diagnostic(ids["response"], 0, 1)
-        assert _bits_same(e.get_series(ids["response"], 0, 1)[0], (P[0] - P[1] * 0.5) * 0.5)
+        assert same_bits(e.get_series(ids["response"], 0, 1)[0], (P[0] - P[1] * 0.5) * 0.5)
         e.set_forcing(0.05 * np.arange(T))
         e.compute_diagnostic(ids["forcing"], 0, 1)
 
@@ -559,19 +528,19 @@ def test_a_linked_handle_in_both_directions(ra):
             e.compute_diagnostic(v)
         e.link_input(0, src, TS)
         try:
-            assert _code(e.get_series, ids["imbalance"], 0, 1) == 2        # the link replaced the forcing: stale
-            assert _code(e.compute_diagnostic, ids["forcing"]) == 1 and _code(e.compute_diagnostic, ids["imbalance"]) == 1
+            assert refusal_code(e.get_series, ids["imbalance"], 0, 1) == 2        # the link replaced the forcing: stale
+            assert refusal_code(e.compute_diagnostic, ids["forcing"]) == 1 and refusal_code(e.compute_diagnostic, ids["imbalance"]) == 1
             assert e.summary(ids["response"], 0)["count"] == n             # current still
             e.compute_diagnostic(ids["response"])
             # linked first: the two that read the forcing are refused at define time, the other two are defined
             e.clear_diagnostics()
-            assert _code(e.define_energy_budget, "forcing") == 1 and _code(e.define_toa_imbalance) == 1
+            assert refusal_code(e.define_energy_budget, "forcing") == 1 and refusal_code(e.define_toa_imbalance) == 1
             assert "Member Forcing" not in e.var_ids and e.diagnostics == {}
             up = e.define_energy_budget("deep_uptake")
             e.compute_diagnostic(up)
             P = e.get_params()
             want = hb.budget("deep_uptake", e.get_series(TS, 0, 21), e.get_series(TD, 0, 21), P, np.zeros((21, n)))
-            assert _bits_same(e.get_series(up, 0, 21), want)
+            assert same_bits(e.get_series(up, 0, 21), want)
         finally:
             e.unlink_input(0)
         vid = e.define_toa_imbalance()                                      # unlinked again: available again
@@ -598,7 +567,7 @@ def test_the_samplers_and_the_builder_refuse_the_names(ra):
         ens.compute_diagnostic("Top of Atmosphere Imbalance")
         P = ens.get_params()
         Fm = np.repeat(F[:, None], 8, axis=1)
-        assert _bits_same(ens.get_series("Top of Atmosphere Imbalance"), hb.budget("imbalance", ens.get_series(TS), ens.get_series(TD), P, Fm))
+        assert same_bits(ens.get_series("Top of Atmosphere Imbalance"), hb.budget("imbalance", ens.get_series(TS), ens.get_series(TD), P, Fm))
         assert "Top of Atmosphere Imbalance" not in model.timeseries().names()
     finally:
         model.close()
@@ -631,13 +600,13 @@ def test_a_windowed_handle_with_an_output_store(ra):
         e.compute_diagnostic(vid, 0, T - 3, 4)                              # the output store
         ts, td = e.get_series(TS, 0, T - 3, 4), e.get_series(TD, 0, T - 3, 4)
         want = hb.budget("response", ts, td, P, np.zeros_like(ts))
-        assert _bits_same(e.get_series(vid, 0, T - 3, 4), want) and np.isfinite(want).all() and len(want) == 18
-        assert _code(e.compute_diagnostic, vid, 0, 9, 3) == 2              # rows 3 and 6 are not resident any more
+        assert same_bits(e.get_series(vid, 0, T - 3, 4), want) and np.isfinite(want).all() and len(want) == 18
+        assert refusal_code(e.compute_diagnostic, vid, 0, 9, 3) == 2              # rows 3 and 6 are not resident any more
         assert e.diagnostics["Radiative Response"]["rows_held"] == 18
         k = e.time_index
         e.compute_diagnostic(vid, k - 2)                                    # the window's last rows
         ts, td = e.get_series(TS, k - 2, k + 1), e.get_series(TD, k - 2, k + 1)
-        assert _bits_same(e.get_series(vid, k - 2, k + 1), hb.budget("response", ts, td, P, np.zeros_like(ts)))
+        assert same_bits(e.get_series(vid, k - 2, k + 1), hb.budget("response", ts, td, P, np.zeros_like(ts)))
 
 
 def test_two_shards_give_the_halves(ra):
@@ -648,12 +617,12 @@ def test_two_shards_give_the_halves(ra):
         for q, vid in ids.items():
             whole.e.compute_diagnostic(vid, 0, T)
             rows[q] = whole.e.get_series(vid)
-            assert _bits_same(rows[q], whole.want(q, 0, T, 1))
+            assert same_bits(rows[q], whole.want(q, 0, T, 1))
         for offset, count in ((0, k), (k, n - k)):
             with Case(ra, count, noise=NOISES["members"], offset=offset, n_total=n, random_rows=False) as h:
                 for q, vid in _define_all(h.e).items():
                     h.e.compute_diagnostic(vid, 0, T)
-                    assert _bits_same(h.e.get_series(vid), rows[q][:, offset:offset + count]), (q, offset)
+                    assert same_bits(h.e.get_series(vid), rows[q][:, offset:offset + count]), (q, offset)
         from rscm_amd.distributed import ShardedEnsemble
         made = []
 
@@ -665,9 +634,9 @@ def test_two_shards_give_the_halves(ra):
         try:
             vid = sh.define_energy_budget("imbalance")
             sh.compute_diagnostic("Top of Atmosphere Imbalance", 0, T)
-            assert _bits_same(sh.ensemble.get_series(vid), rows["imbalance"])
+            assert same_bits(sh.ensemble.get_series(vid), rows["imbalance"])
             got = sh.quantile_rows_global("Top of Atmosphere Imbalance", Q, 0, T)
-            assert _same(got["quantiles"], _np_q(rows["imbalance"]))
+            assert same_values(got["quantiles"], _np_q(rows["imbalance"]))
         finally:
             sh.ensemble.close()
 
@@ -700,6 +669,6 @@ def test_a_posterior_defines_what_its_source_defines(ra):
             P = dst.get_params()
             F = hb.member_forcing(table, P, np.ones(40, dtype=np.int32), 0, ("members", SEED + 11))
             want = hb.budget("imbalance", dst.get_series(TS, k0, T), dst.get_series(TD, k0, T), P, F[:, k0:].T, -2.5)
-            assert _bits_same(dst.get_series("Top of Atmosphere Imbalance", k0, T), want) and np.isfinite(want).all()
+            assert same_bits(dst.get_series("Top of Atmosphere Imbalance", k0, T), want) and np.isfinite(want).all()
         finally:
             dst.close()

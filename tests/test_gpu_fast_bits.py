@@ -21,6 +21,7 @@ import pytest
 
 from tests import host_coupled as hc
 from tests import host_fast as hf
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
@@ -30,15 +31,6 @@ NAMES = {"ts": "Surface Temperature", "td": "Deep Ocean Temperature", "conc": "A
          "erf_total": "Effective Radiative Forcing"}
 STATES = ("ts", "td", "conc", "cum_uptake", "cum_emis")
 CARBON = ("conc", "cum_uptake", "cum_emis")
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

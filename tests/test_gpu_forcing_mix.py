@@ -16,6 +16,7 @@ import pytest
 
 from tests import host_forcing_mix as hm
 from tests import host_resample as hr
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import assert_bit_equal, two_layer_params
 from tests.host_sampler import lhs_matrix
 
@@ -26,15 +27,6 @@ T = 41
 BOUNDS = np.concatenate([[1750.0], 1750.0 + np.cumsum(np.where(np.arange(T) % 7 == 3, 0.5, 1.0))])   # uneven steps
 FAST_RTOL = 1e-11
 TS, TD = "Surface Temperature", "Deep Ocean Temperature"
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -7,25 +7,17 @@ Tolerance: |gpu - oracle| <= 1e-12 * max(1, |oracle|).  The kernel factorises ln
 reference's expressions; the forcings are O(1) W/m^2, so this is ~4 decimal digits above f64
 rounding and 7 below the reference's own MAGICC7 tolerance (rtol 1e-5)."""
 import json
-import os
 
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
 from tests.test_oracle_ghg import ATOL, GOLD, RTOL, ghg_params_from_config, scenario_concentrations
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
 NAMES = {"co2_erf": 1, "ch4_erf": 2, "n2o_erf": 3}
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -102,7 +94,7 @@ def test_ghg_gpu_ensemble_vs_oracle(ra, orc, method, n):
     # three launches give the same bits as one
     again = _gpu(ra, T, P, conc, scen=scen, chunks=(1, 100))
     for k in NAMES:
-        assert np.array_equal(again[k], got[k], equal_nan=True), k
+        assert same_values(again[k], got[k]), k
     # without a scenario map every member reads scenario 0
     got0 = _gpu(ra, T, P, conc[:1])
     _assert_close(got0, orc.ghg_run(T, P, conc[:1]), f"{method} n={n} one scenario")

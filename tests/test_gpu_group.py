@@ -9,18 +9,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn, magicc_chain
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 def _fusion(on: bool):
@@ -33,16 +25,6 @@ def _stats():
     a, b = C.c_int64(), C.c_int64()
     L.check(L.load().rscm_gpu_lockstep_stats(C.byref(a), C.byref(b)))
     return a.value, b.value
-
-
-def _chain():
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 @pytest.fixture(autouse=True)
@@ -239,7 +221,7 @@ def test_light_graph_with_lds_slots_matches_the_unfused_run(ra):
 
 @pytest.mark.parametrize("execution_order", ["reference", "topological"])
 def test_fused_magicc_graph_keeps_the_bits(ra, execution_order):
-    mod = _chain()
+    mod = magicc_chain()
     years, N = 60, 200
     _fusion(False)
     plain = mod.build_chain(N, years, execution_order)
@@ -281,7 +263,7 @@ def test_independent_ops_of_a_step_on_two_wavefronts(ra, execution_order):
     (they are tied to one wavefront).  A ragged last workgroup (N = 203) and windowed series are part of it."""
     import ctypes as C
     from rscm_amd import _lib as L
-    mod = _chain()
+    mod = magicc_chain()
     lib = L.load()
     years, N = 40, 203
 
@@ -325,7 +307,7 @@ def test_merged_launches_keep_the_bits(ra, execution_order):
     workgroup, and a run made in two calls (the prologue / epilogue of the merged schedule at a call boundary)."""
     from rscm_amd import _lib as L
     from rscm_amd.ensemble import run_lockstep
-    mod = _chain()
+    mod = magicc_chain()
     lib = L.load()
     years, N = 30, 203
 
@@ -387,7 +369,7 @@ def test_merged_launches_keep_the_bits(ra, execution_order):
 
 
 def test_fused_windowed_graph_keeps_the_bits(ra):
-    mod = _chain()
+    mod = magicc_chain()
     years, N = 70, 128
     _fusion(False)
     plain = mod.build_chain(N, years, "reference")

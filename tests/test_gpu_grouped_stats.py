@@ -11,7 +11,9 @@ import numpy as np
 import pytest
 
 from tests import host_resample as hr
-from tests.helpers import f_syn, two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import refusal_code
+from tests.helpers import f_syn, magicc_chain, same_bits, two_layer_params
 from tests.host_gselect import exceedance_grouped, sharded_gquantiles
 
 pytestmark = pytest.mark.gpu
@@ -25,22 +27,6 @@ QS = {1: [0.5], 3: [0.05, 0.5, 0.95], 8: [0.0, 0.1, 0.25, 0.5, 0.75, 0.9, 1.0, 1
 COMBOS = [(1, 1, "random"), (1, 8, "interleaved"), (2, 3, "blocks"), (3, 3, "interleaved"), (3, 9, "single"), (5, 3, "empty"),
           (5, 1, "allnan"), (17, 1, "random"), (17, 9, "interleaved"), (64, 3, "blocks"), (64, 9, "random")]
 RESTATED = {(2, 3, "blocks"), (3, 3, "interleaved")}    # also against tests/host_gselect.py (slow in Python)
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _same(a, b):
-    """Bit equality, any NaN equal to any NaN."""
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(((np.ascontiguousarray(a).view(np.uint64) == np.ascontiguousarray(b).view(np.uint64))
-                                        | (np.isnan(a) & np.isnan(b))).all())
 
 
 def _two_layer(ra, n, P=None, steps=STEPS, bounds=BOUNDS, forcing=None):
@@ -129,13 +115,13 @@ def test_grouped_select_equals_numpy_on_the_subsets(ra, n):
                 want, cnt = _want(x, group, G, q, w if weighted else None)
                 what = (n, G, nq, kind, weighted, anomaly)
                 assert np.array_equal(got[key][:, :STEPS + 1], cnt), what
-                assert _same(got["quantiles"][:, :STEPS + 1], want), what
+                assert same_bits(got["quantiles"][:, :STEPS + 1], want), what
                 assert (got[key][:, STEPS + 1:] == 0).all() and np.isnan(got["quantiles"][:, STEPS + 1:]).all(), what
                 if (G, nq, kind) in RESTATED:
                     host = sharded_gquantiles([x], [group], G, q, [w] if weighted else None)[0]
-                    assert np.array_equal(host[key], cnt) and _same(host["quantiles"], want), what
+                    assert np.array_equal(host[key], cnt) and same_bits(host["quantiles"], want), what
             strided = e.quantile_rows(1, q, 1, 9, 3, grouped=True)
-            assert _same(strided["quantiles"], _want(ser[1:9:3], group, G, q)[0]), (n, G, nq, kind)
+            assert same_bits(strided["quantiles"], _want(ser[1:9:3], group, G, q)[0]), (n, G, nq, kind)
 
 
 @pytest.mark.parametrize("n", [3, 65, 4097])
@@ -199,12 +185,12 @@ def test_grouped_vectors_and_exceedance(ra, n):
         for weighted in (False, True):
             got = e.quantile_vectors(vecs, QS[3], weighted=weighted, grouped=True)
             want, cnt = _want(host, group, G, QS[3], w if weighted else None)
-            assert _same(got["quantiles"], want) and np.array_equal(got["weight" if weighted else "count"], cnt)
+            assert same_bits(got["quantiles"], want) and np.array_equal(got["weight" if weighted else "count"], cnt)
             with e.select_vectors(vecs, QS[3], weighted=weighted, grouped=True) as s:
                 while s.next_pass() is not None:
                     s.commit()
                 staged = s.result()
-            assert _same(staged["quantiles"], want)
+            assert same_bits(staged["quantiles"], want)
             exc = e.exceedance(ind["peak"], thr, weighted=weighted, grouped=True)
             hits, total = exceedance_grouped(host[0], group, G, thr, w if weighted else None)
             assert np.array_equal(exc["hits"], hits) and np.array_equal(exc["total"], total)
@@ -277,20 +263,10 @@ def test_two_handles_summing_their_histograms_equal_the_whole(ra, weighted):
             assert np.array_equal(r[key], want[key])
 
 
-def _chain():
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_windowed_strided_graph_gives_the_full_storage_numbers(ra):
     """GraphModel.set_member_groups / quantile_rows(grouped=True) on a windowed graph that keeps every 12th row equal numpy on
     get_series(t_stride=12) of the group's members, and the same graph on full storage."""
-    mod = _chain()
+    mod = magicc_chain()
     n, G = 1001, 3
     group = (np.arange(n) % (G + 1) - 1).astype(np.int32)
     names = ["Surface Temperature", "Atmospheric Concentration|CO2"]
@@ -304,13 +280,13 @@ def test_windowed_strided_graph_gives_the_full_storage_numbers(ra):
                 got = model.quantile_rows(name, QS[3], t_stride=12, grouped=True)
                 ser = model.get_series(name, t_stride=12)
                 want, cnt = _want(ser, group, G, QS[3])
-                assert _same(got["quantiles"], want) and np.array_equal(got["count"], cnt), (name, kw)
+                assert same_bits(got["quantiles"], want) and np.array_equal(got["count"], cnt), (name, kw)
                 res[(name, bool(kw))] = got["quantiles"]
             peak = model.indicators("Surface Temperature", 0, model.time_index + 1, 12, thresholds=[0.5])["peak"]
             exc = model.exceedance(peak, [0.5], grouped=True)
             hits, total = exceedance_grouped(peak.to_host(), group, G, [0.5])
             assert np.array_equal(exc["hits"], hits) and np.array_equal(exc["total"], total)
-            assert _same(model.quantile_vectors([peak], QS[3], grouped=True)["quantiles"], _want(peak.to_host()[None, :], group, G, QS[3])[0])
+            assert same_bits(model.quantile_vectors([peak], QS[3], grouped=True)["quantiles"], _want(peak.to_host()[None, :], group, G, QS[3])[0])
         finally:
             model.close()
     for name in names:
@@ -335,8 +311,8 @@ def test_posterior_sets_the_scenarios_as_groups(ra):
             ser = dst.get_series(1)
             for s in range(S):
                 want, cnt = _nanq(ser[:, s * M:(s + 1) * M], QS[3])
-                assert _same(got["quantiles"][s], want) and np.array_equal(got["count"][s], cnt)
-            assert not _same(got["quantiles"][0, -1], got["quantiles"][1, -1])
+                assert same_bits(got["quantiles"][s], want) and np.array_equal(got["count"][s], cnt)
+            assert not same_bits(got["quantiles"][0, -1], got["quantiles"][1, -1])
             # a branch leaves the groups set beforehand on the destination alone
             dst.rewind()
             assert np.array_equal(dst.member_groups(), scen)
@@ -349,7 +325,7 @@ def test_posterior_sets_the_scenarios_as_groups(ra):
             other.run()
             assert np.array_equal(other.member_groups(), mine)
             got = other.quantile_rows(1, QS[3], K, None, grouped=True)
-            assert _same(got["quantiles"], _want(other.get_series(1, K), mine, 2, QS[3])[0])
+            assert same_bits(got["quantiles"], _want(other.get_series(1, K), mine, 2, QS[3])[0])
             other.clear_member_groups()
             assert other.n_groups == 0
 
@@ -402,7 +378,6 @@ def test_refusals(ra):
 
 def test_a_group_weight_past_2_53_is_refused_on_both_handles(ra):
     """Each handle's weights sum to less than 2^53 and so does every group on its own handle; group 1 of the two together does not."""
-    from rscm_amd import RscmGpuError
     with _two_layer(ra, 101, steps=5) as a, _two_layer(ra, 101, steps=5) as b:
         for h in (a, b):
             w = np.ones(101, dtype=np.int64)
@@ -416,9 +391,7 @@ def test_a_group_weight_past_2_53_is_refused_on_both_handles(ra):
         try:
             total = np.sum([s.next_pass().to_host() for s in sels], axis=0)
             for s in sels:
-                with pytest.raises(RscmGpuError) as err:
-                    s.commit(total)
-                assert err.value.code == 1
+                assert refusal_code(s.commit, total) == 1
         finally:
             for s in sels:
                 s.close()

@@ -7,17 +7,11 @@ order: |gpu - oracle| <= 1e-12 * max(1, |oracle|)."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -72,7 +66,7 @@ def test_halocarbon_gpu_vs_oracle(ra, orc, n):
         for row in (1, 37, T - 1):
             assert tuple(got[41:, row, i]) == orc.halo_aggregates(P[:, i].copy(), dict(zip(orc.HALO_SPECIES, got[:41, row, i])))
     # launches that split inside a 16-row aggregate chunk give the same bits
-    assert np.array_equal(_gpu(ra, b, P, E, c0, scen=scen, chunks=(1, 21, 40)), got, equal_nan=True)
+    assert same_values(_gpu(ra, b, P, E, c0, scen=scen, chunks=(1, 21, 40)), got)
 
 
 def test_halocarbon_through_the_reference_shaped_front(ra, orc):

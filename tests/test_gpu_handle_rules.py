@@ -14,21 +14,13 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
 from tests.test_gpu_ocean import _case, _fast_info
 
 pytestmark = pytest.mark.gpu
 
 N, T, STOP = 65, 8, 3
 BOUNDS = np.arange(T + 1, dtype=float) + 1850.0
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from rscm_amd import _lib as L
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import assert_bit_equal, coupled_params, f_syn, two_layer_params
 from tests.test_gpu_parity import CP_INIT, CP_NAMES, FAST_RTOL, _bounded, _close
 
@@ -28,14 +29,6 @@ SIZES = (S_STATIC, S_STATIC + 1, S_LAST, S_LAST + 1)
 YEARS = 1900.0 + np.arange(T, dtype=np.float64)
 BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
 _WANT = {}
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    L.load()
-    assert L.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -17,19 +17,11 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn, f_syn, two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn, f_syn, magicc_chain, two_layer_params
 from tests.host_lockstep import read_at_steps, relative_error
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 class Stream:
@@ -641,16 +633,6 @@ def test_full_emissions_driven_magicc_graph_closed_loop(ra, execution_order):
     model.close()
 
 
-def _load_chain_module():
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def _closed_loop_member(model, exo, init, contributors, b, member, series=None):
     """The closed-loop check of test_full_emissions_driven_magicc_graph_closed_loop for one member of
     an ensemble of chains (topological or reference order alike): every component's outputs
@@ -755,7 +737,7 @@ def test_magicc_graph_on_a_monthly_axis_closed_loop(ra):
     fertilisation factor.  Members spread over the ensemble (first and last lane of a wavefront, the
     last member) pass the closed-loop check against all ten component oracles at the single-component
     tolerances; the other members are compared through ensemble-level properties."""
-    mod = _load_chain_module()
+    mod = magicc_chain()
     years, spy, N = 24, 12, 10_240
     t, exo, init, contributors = mod.chain_inputs(years, spy)
     b = np.append(t, t[-1] + (t[-1] - t[-2]))
@@ -1053,12 +1035,7 @@ def test_graph_checkpoint_resumes_the_full_chain_bit_identically(ra, tmp_path):
     chemistry looks back at (N2O: strat_delay + 1), and the internal component states -- ClimateUDEB's
     ocean columns and temperature history, OceanCarbon's flux history.  A fresh model object restored
     at step 33 (odd: inside a split ocean tile) continues to the same bits."""
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = magicc_chain()
     years, N = 70, 96
     a = mod.build_chain(N, years, "topological")
     a.run()
@@ -1098,12 +1075,7 @@ def test_graph_rollback_into_the_same_model_in_reference_order(ra):
     breadth-first order (where the forcing aggregate runs before some of its producers and must find
     NaN at n+1): the rows the first pass wrote beyond the checkpoint must not be seen by the second.
     The continuation carries the bits of the uninterrupted run."""
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = magicc_chain()
     years, N = 40, 64
     m = mod.build_chain(N, years, "reference")
     assert m._reads_unwritten
@@ -1404,13 +1376,8 @@ def test_python_components_in_a_gpu_graph(ra):
 def test_chain_members_are_independent(ra):
     """Every member of an ensemble run of the ten-component graph equals the one-member model with that
     member's parameters, bit for bit (no cross-member coupling anywhere in the linked kernels)."""
-    import importlib.util
-    import os
     from rscm_amd import _lib as L
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = magicc_chain()
     years, N = 40, 5
     big = mod.build_chain(N, years, "topological")
     P_ud = big.ensembles["ClimateUDEB"].get_params()
@@ -1436,12 +1403,7 @@ def test_chain_full_size_properties(ra):
     same model object gives the same bits (launch order, split ocean tiles and the cleared series are
     deterministic), and the first 777 members equal a 777-member ensemble with their parameters (the
     result of a member does not depend on the ensemble it sits in, its block or its lane)."""
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = magicc_chain()
     years, N, n_small = 150, 100_000, 777
     big = mod.build_chain(N, years, "topological")
     big.run()
@@ -1471,13 +1433,8 @@ def test_graph_models_release_what_they_allocate(ra):
     runtime's own pools (code objects, queue scratch -- a one-off few hundred MB) have settled over
     the first cycles, 24 more cycles leave the free memory where it was.  A leak of one ensemble's
     buffers per cycle would show as > 300 MB here."""
-    import importlib.util
-    import os
     from rscm_amd import _lib as L
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
+    mod = magicc_chain()
 
     def cycle(k):
         m = mod.build_chain(20_000, 20, "topological" if k % 2 else "reference")

@@ -10,20 +10,12 @@ import numpy as np
 import pytest
 
 from tests import host_lockstep as H
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import assert_bit_equal
 
 pytestmark = pytest.mark.gpu
 
 FUZZ_SEEDS = range(32)
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(autouse=True)

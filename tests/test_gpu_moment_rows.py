@@ -14,22 +14,15 @@ import pytest
 
 from tests import host_moment_rows as hr
 from tests import host_moments as hm
-from tests.helpers import f_syn, two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import refusal_code
+from tests.helpers import f_syn, magicc_chain, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T_AXIS = np.arange(1750.0, 1758.0)          # 8 rows
 DBL_MAX = float(np.finfo(np.float64).max)
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 def _members_per_pass() -> int:
@@ -41,13 +34,6 @@ def _members_per_pass() -> int:
     threads = int(re.search(r"constexpr int kMomRowThreads = (\d+);", hip).group(1))
     assert per_pass == blocks * threads
     return per_pass
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
 
 
 def _stats(e):
@@ -341,7 +327,7 @@ def test_anomaly_of_a_reference_period(ra):
         sub = e.moment_rows(1, 1, 6, 2, anomaly=True)
         _same_dict(sub, {k: v[1:6:2] for k, v in ref.items()}, "strided")
         e.clear_baseline()
-        assert _code(e.moment_rows, 1, 0, 3, anomaly=True) == 2
+        assert refusal_code(e.moment_rows, 1, 0, 3, anomaly=True) == 2
 
 
 # ---- shards, device memory, storage layouts ---------------------------------------------------------------------------------------
@@ -414,8 +400,8 @@ def test_windowed_handle(ra):
         assert (kept["count"] == n).all() and (kept["slope"][1:, 0] != 0.0).all()
         last = w.moment_rows(1, 36, 41, vectors=vw)                                    # the window's last rows
         _same_dict(last, {k: x[36:41] for k, x in want.items()}, "window")
-        assert _code(w.moment_rows, 1, 0, 3) == 2                                      # row 1 is neither in the window nor kept
-        assert _code(w.moment_rows_sums, 1, 1, 31, 34) == 2
+        assert refusal_code(w.moment_rows, 1, 0, 3) == 2                                      # row 1 is neither in the window nor kept
+        assert refusal_code(w.moment_rows_sums, 1, 1, 31, 34) == 2
 
 
 def test_rows_past_the_time_index(ra):
@@ -439,31 +425,23 @@ def test_a_diagnostic_by_name(ra):
     n = 129
     with _rows_ens(ra, n) as e:
         vid = e.define_heat_content()
-        assert _code(e.moment_rows, "Ocean Heat Content") == 2
+        assert refusal_code(e.moment_rows, "Ocean Heat Content") == 2
         e.compute_diagnostic(vid)
         got = e.moment_rows("Ocean Heat Content", vectors=[e.params_vector(4)])
         ref = hr.ungrouped(hr.moment_rows(e.get_series(vid), e.get_params()[4:5]))
         _same_dict(got, ref, "heat content")
         assert (got["count"] == n).all() and (got["var"][2:] > 0).all()   # (the members part from row 2 on)
         e.set_state(1, 0, 0.25)
-        assert _code(e.moment_rows, "Ocean Heat Content") == 2
+        assert refusal_code(e.moment_rows, "Ocean Heat Content") == 2
         from rscm_amd._lib import RscmGpuError
         with pytest.raises(RscmGpuError, match="is stale: compute it again"):
             e.moment_rows_sums(vid, 1)
 
 
-def _chain():
-    import importlib.util
-    spec = importlib.util.spec_from_file_location("bench_magicc_chain", os.path.join(ROOT, "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_graph_model_moment_rows(ra):
     """By variable name on a graph: the home ensemble's rows, regressed on a parameter of that ensemble; a vector of another
     ensemble raises."""
-    mod = _chain()
+    mod = magicc_chain()
     n = 257
     model = mod.build_chain(n, 12, "topological")
     try:
@@ -529,14 +507,14 @@ def test_refusals(ra):
         near_end = (C.POINTER(C.c_double) * 1)(C.cast(C.c_void_p(v.params_vector(7).ptr + 8 * (n - 10)), C.POINTER(C.c_double)))
         assert sums(n_vec=1, a=near_end) == _lib.ERR_INVALID
         with e.select(1, [0.5], 0, 8):
-            assert _code(e.moment_rows, 1) == 2
+            assert refusal_code(e.moment_rows, 1) == 2
         e.moment_rows(1)
     # more blocks than one call takes: 751 rows x 64 groups x 9 blocks are within the cap, 1000 rows of them are not; fewer groups are
     assert 751 * 64 * 9 <= (1 << 19) < 1000 * 64 * 9
     with _rows_ens(ra, 8, steps=0, t=np.arange(1000.0)) as e, _vec_ens(ra, 8) as v:
         vecs = _load(v, rng.standard_normal((4, 8)))
         e.set_member_groups(np.arange(8, dtype=np.int32), 64)
-        assert _code(e.moment_rows, 1, vectors=vecs, grouped=True) == 1
-        assert _code(e.moment_rows_sums, 1, 2, vectors=vecs, center=np.zeros((1000, 64, 5)), grouped=True) == 1
+        assert refusal_code(e.moment_rows, 1, vectors=vecs, grouped=True) == 1
+        assert refusal_code(e.moment_rows_sums, 1, 2, vectors=vecs, center=np.zeros((1000, 64, 5)), grouped=True) == 1
         got = e.moment_rows(1, vectors=vecs)
         assert got["count"].tolist() == [8] + [0] * 999

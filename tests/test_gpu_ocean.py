@@ -8,17 +8,11 @@ device math library: |gpu - oracle| <= 1e-12 * max(1, |oracle|)."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -74,14 +68,14 @@ def test_ocean_gpu_bit_exact_without_temperature_feedback(ra, orc, model):
     scen = (np.arange(n) % 2).astype(np.int32)
     want = orc.ocean_run(b, P, inputs, 278.0, 0.0, scen=scen, threads=8)
     got = _gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen)
-    assert np.array_equal(got, want, equal_nan=True)
+    assert same_values(got, want)
     # three launches, boundaries inside a year group of the convolution: the same bits
-    assert np.array_equal(_gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen, chunks=(1, 17)), got, equal_nan=True)
+    assert same_values(_gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen, chunks=(1, 17)), got)
     # one step per launch (Model::step, linked graphs): the steps are paired up into split two-year
     # tiles -- the same bits again, also when single steps and longer launches alternate
-    assert np.array_equal(_gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen, chunks=range(1, T)), got, equal_nan=True)
+    assert same_values(_gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen, chunks=range(1, T)), got)
     mixed = (1, 2, 3, 10, 11, 12, 13, 30, 31, 58, 59)
-    assert np.array_equal(_gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen, chunks=mixed), got, equal_nan=True)
+    assert same_values(_gpu(ra, b, P, inputs, 278.0, 0.0, scen=scen, chunks=mixed), got)
 
 
 @pytest.mark.parametrize("n", [1, 63, 257])
@@ -100,7 +94,7 @@ def test_ocean_gpu_vs_oracle(ra, orc, n):
     err = np.abs(got[ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))
     assert err.max() <= TOL, f"max deviation {err.max():.3e}"
     off = np.arange(n) % 3 == 0
-    assert np.array_equal(got[:, :, off], want[:, :, off], equal_nan=True)  # members without the exp: exact
+    assert same_values(got[:, :, off], want[:, :, off])  # members without the exp: exact
 
 
 def test_ocean_one_step_launches_in_any_pattern(ra, orc):
@@ -153,8 +147,8 @@ def test_ocean_one_step_launches_in_any_pattern(ra, orc):
     # steps 0 and 1 are one tile, step 2 starts the next: time index 3 is the middle of a tile
     rerun, first = stepped(ones, rewind_at=3)
     check(rerun, "ones, rewound in the middle of a tile")
-    assert np.array_equal(rerun[:, :4], first, equal_nan=True)
-    assert np.array_equal(rerun, all_ones, equal_nan=True)
+    assert same_values(rerun[:, :4], first)
+    assert same_values(rerun, all_ones)
 
 
 @pytest.mark.parametrize("max_hist", [0, 5, 12, 30, 100])
@@ -167,9 +161,9 @@ def test_ocean_gpu_bounded_history(ra, orc, max_hist):
     P, inputs = _case(orc, "HILDA", n, T, rng, enable_temp_feedback=0.0, max_history_months=max_hist)
     want = orc.ocean_run(b, P, inputs[:1], 280.0, 0.0, threads=8)
     got = _gpu(ra, b, P, inputs[:1], 280.0, 0.0)
-    assert np.array_equal(got, want, equal_nan=True)
-    assert np.array_equal(_gpu(ra, b, P, inputs[:1], 280.0, 0.0, chunks=(3, 20)), got, equal_nan=True)
-    assert np.array_equal(_gpu(ra, b, P, inputs[:1], 280.0, 0.0, chunks=range(1, T)), got, equal_nan=True)  # split tiles
+    assert same_values(got, want)
+    assert same_values(_gpu(ra, b, P, inputs[:1], 280.0, 0.0, chunks=(3, 20)), got)
+    assert same_values(_gpu(ra, b, P, inputs[:1], 280.0, 0.0, chunks=range(1, T)), got)  # split tiles
 
 
 def test_ocean_through_the_reference_shaped_front(ra, orc):
@@ -235,7 +229,7 @@ def test_ocean_error_conventions(ra, orc):
         e.set_initial(1, 400.0)
         e.set_initial(2, 0.0)
         e.run()
-        assert np.array_equal(e.get_series(1), short, equal_nan=True)
+        assert same_values(e.get_series(1), short)
 
 
 def test_ocean_full_window_properties(ra, orc):
@@ -346,18 +340,18 @@ def test_ocean_fast_mode_tolerance(ra, orc, model):
     exact, fit = run(ra.MODE_EXACT)
     fast, _ = run(ra.MODE_FAST)
     want = orc.ocean_run(b, P[:, 1:3].copy(), inputs[:1], 278.0, 0.0, threads=2)   # member 1: no temperature feedback
-    assert np.array_equal(exact[:, :, 1:2], want[:, :, :1], equal_nan=True)
+    assert same_values(exact[:, :, 1:2], want[:, :, :1])
     ok = ~np.isnan(exact)
     err = np.abs(fast[ok] - exact[ok]) / np.maximum(1.0, np.abs(exact[ok]))
     print(f"{model}: fit deviation {fit:.2e}, FAST vs EXACT over {T - 1} years: max relative deviation {err.max():.2e}")
     assert 0.0 < err.max() <= FAST_TOL, err.max()
     assert (np.isnan(fast) == np.isnan(exact)).all()
     # launch boundaries / one step per launch: the running sums and the last pulses are carried exactly
-    assert np.array_equal(run(ra.MODE_FAST, chunks=(1, 2, 17, 300, 301, 555))[0], fast, equal_nan=True)
-    assert np.array_equal(run(ra.MODE_FAST, chunks=range(1, 90))[0], fast, equal_nan=True)
+    assert same_values(run(ra.MODE_FAST, chunks=(1, 2, 17, 300, 301, 555))[0], fast)
+    assert same_values(run(ra.MODE_FAST, chunks=range(1, 90))[0], fast)
     # EXACT for 520 years (pulses have started leaving the window), then FAST: the sums are re-formed from the history
     joined, _ = run(ra.MODE_FAST, switch_at=520)
-    assert np.array_equal(joined[:, :521], exact[:, :521], equal_nan=True)
+    assert same_values(joined[:, :521], exact[:, :521])
     errj = np.abs(joined[ok] - exact[ok]) / np.maximum(1.0, np.abs(exact[ok]))
     assert errj.max() <= FAST_TOL
 

@@ -18,6 +18,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.helpers import same_values
 from tests.test_gpu_ocean import FAST_TOL, TOL, _case, _fast_info, _gpu, orc, ra  # noqa: F401  (ra, orc: fixtures)
 
 pytestmark = pytest.mark.gpu
@@ -57,10 +58,6 @@ def _deviation(got, want):
     return (np.abs(got[ok] - want[ok]) / np.maximum(1.0, np.abs(want[ok]))).max()
 
 
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
 # ---------------------------------------------------------------------------------------------------------------------
 # A. the tiled convolution at window lengths beside the tile widths
 BESIDE_TILES = [("HILDA", H) for H in (1, 11, 13, 23, 24, 25, 35, 36, 37, 47, 48, 49)] + \
@@ -79,9 +76,9 @@ def test_tiled_exact_window_beside_a_tile_width(ra, orc, model, H):
     months."""
     case = _setup(orc, model, H)
     got = _run(ra, case, mode=ra.MODE_EXACT, recurrence=False)
-    assert _same(got, case[4])
+    assert same_values(got, case[4])
     for what, chunks in PATTERNS.items():
-        assert _same(_run(ra, case, mode=ra.MODE_EXACT, chunks=chunks), got), what
+        assert same_values(_run(ra, case, mode=ra.MODE_EXACT, chunks=chunks), got), what
 
 
 @pytest.mark.parametrize("model,H", SHORT + BESIDE_TILES + ILL_CONDITIONED)
@@ -95,11 +92,11 @@ def test_tiled_fast_window_beside_a_tile_width(ra, orc, model, H):
     dev = _deviation(got, case[4])
     print(f"{model} H = {H}: FAST (fused tiles) vs oracle: max relative deviation {dev:.2e}")
     if H <= 1:
-        assert _same(got, case[4])
+        assert same_values(got, case[4])
     else:
         assert 0.0 < dev <= FUSED_TOL, dev
     for what, chunks in PATTERNS.items():
-        assert _same(_run(ra, case, mode=ra.MODE_FAST, chunks=chunks), got), what
+        assert same_values(_run(ra, case, mode=ra.MODE_FAST, chunks=chunks), got), what
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -147,7 +144,7 @@ def test_recurrence_short_window(ra, orc, model, H, near):
     assert got_near == near
     exact = _run(ra, case, mode=ra.MODE_EXACT, recurrence=True)
     off = np.arange(N) % 2 == 1   # members without the temperature feedback
-    assert _same(exact[:, :, off], want[:, :, off])
+    assert same_values(exact[:, :, off], want[:, :, off])
     assert _deviation(exact, want) <= TOL
     fast = _run(ra, case, mode=ra.MODE_FAST, recurrence=True)
     dev, dev_on = _deviation(fast, want), _deviation(fast[:, :, ~off], want[:, :, ~off])
@@ -162,9 +159,9 @@ def test_recurrence_short_window(ra, orc, model, H, near):
     assert len(after_wraps) >= 4
     for what, chunks in {"one step per launch": ONES, "step S on its own": (S, S + 1), "a boundary at S + 1": (S + 1,),
                          "launches that start after a wrap": after_wraps}.items():
-        assert _same(_run(ra, case, mode=ra.MODE_FAST, chunks=chunks), fast), (what, chunks)
+        assert same_values(_run(ra, case, mode=ra.MODE_FAST, chunks=chunks), fast), (what, chunks)
     # FAST, rewind, FAST: the running sums start from nothing again
-    assert _same(_run(ra, case, mode=ra.MODE_FAST, rewound=True), fast)
+    assert same_values(_run(ra, case, mode=ra.MODE_FAST, rewound=True), fast)
 
 
 @pytest.mark.parametrize("model,H,near", RECURRENCE)
@@ -178,7 +175,7 @@ def test_recurrence_joins_a_run_that_exact_began(ra, orc, model, H, near):
     S = H // 12
     for k in [1, 2, 3, 4, near // 12 + 1, S, S + 1] + [w + 1 for w in _wrap_years(H)]:
         joined = _run(ra, case, mode=ra.MODE_FAST, recurrence=True, join_at=k)
-        assert _same(joined[:, :k + 1], exact[:, :k + 1]), k
+        assert same_values(joined[:, :k + 1], exact[:, :k + 1]), k
         dev = _deviation(joined, want)
         assert dev <= FAST_TOL, (k, dev)
-        assert not _same(joined[:, k + 1:], exact[:, k + 1:]), k   # the rest did run FAST
+        assert not same_values(joined[:, k + 1:], exact[:, k + 1:]), k   # the rest did run FAST

@@ -32,21 +32,14 @@ import pytest
 from rscm_amd import _lib as L
 from tests import host_lockstep as H
 from tests import param_rows as R
-from tests.helpers import assert_bit_equal
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import assert_bit_equal, same_values
 
 pytestmark = pytest.mark.gpu
 N = R.N_MEMBERS
 FAST_KINDS = (L.KIND_TWO_LAYER, L.KIND_COUPLED, L.KIND_UDEB, L.KIND_OCEAN_CARBON, L.KIND_CARBON_CYCLE)
 # six small handles with 18 series: with the one to four series of the handle in front of them the 20 slots are spent
 CROWD = (L.KIND_FOURBOX_OHU,) * 4 + (L.KIND_AEROSOL_INDIRECT, L.KIND_CO2_ERF)
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    L.load()
-    assert L.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -188,7 +181,7 @@ def test_every_row_on_the_uniform_and_the_per_member_path(ra, stream, kind):
             acts = False
             for c in configs:
                 want = check(_one(sp, j, True), c, f"(b) row {j} ({sp.names[j]}) alone varied", "b")
-                acts = acts or not np.array_equal(want, base[c], equal_nan=True)
+                acts = acts or not same_values(want, base[c])
             # the comparisons were not vacuous: the row acts somewhere, or it is one of the rows no solve reads
             assert acts != (sp.names[j] in R.DEAD_ROWS.get(kind, ())), f"{sp.name}: row {j} ({sp.names[j]}): acts {acts}"
         masks = R.random_masks(sp)

@@ -7,17 +7,11 @@ ozone temperature feedback, members on the zero branches)."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
+
 pytestmark = pytest.mark.gpu
 TOL = 1e-12
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -108,7 +102,7 @@ def test_pointwise_gpu_vs_oracle(ra, orc, kind_name, n):
     if kind == orc.PW_OZONE:
         assert np.array_equal(got[2][1:], want[2][1:])  # temperature feedback: one multiply
     # three launches give the same bits as one; one scenario without a map reads scenario 0
-    assert np.array_equal(_gpu(ra, kind, T, P, inputs, scen=scen, chunks=(1, 77)), got, equal_nan=True)
+    assert same_values(_gpu(ra, kind, T, P, inputs, scen=scen, chunks=(1, 77)), got)
     w0 = orc.pointwise_run(kind, T, P, inputs[:1])
     g0 = _gpu(ra, kind, T, P, inputs[:1])
     assert (np.abs(g0[:, 1:] - w0[:, 1:]) <= TOL * np.maximum(1.0, np.abs(w0[:, 1:]))).all()

@@ -4,20 +4,12 @@ storage and must carry the same bits, signed zeros included, for any number of q
 import numpy as np
 import pytest
 
-from tests.helpers import axis_values, f_syn, two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import axis_values, f_syn, magicc_chain, same_values, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 Q = [0.0, 1.0, 0.5, 1e-12, 0.05, 0.17, 0.83, 0.95]
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 def _bits_equal(a, b):
@@ -78,7 +70,7 @@ def test_quantile_rows_equals_quantile_series_and_numpy(ra, n):
         ref = e.quantile_series(1, Q)
         assert _bits_equal(got["quantiles"], ref["quantiles"]) and np.array_equal(got["count"], ref["count"])
         ts = e.get_series(1)
-        assert np.array_equal(got["quantiles"][:61], _nanq(ts[:61], Q), equal_nan=True)
+        assert same_values(got["quantiles"][:61], _nanq(ts[:61], Q))
         assert np.array_equal(got["count"][:61], (~np.isnan(ts[:61])).sum(axis=1))
         assert (got["count"][61:] == 0).all() and np.isnan(got["quantiles"][61:]).all()
         sub = e.quantile_rows("Surface Temperature", Q, 1, 75, 3)          # stride > 1, across the time index
@@ -111,7 +103,7 @@ def test_quantile_series_takes_more_quantiles_than_one_select(ra, n_q):
         rows = e.get_series(1)[2:10]
         got = e.quantile_series(1, q, 2, 10)
         assert got["quantiles"].shape == (8, n_q)
-        assert np.array_equal(got["quantiles"], _nanq(rows, q), equal_nan=True)
+        assert same_values(got["quantiles"], _nanq(rows, q))
         pieces = [e.quantile_rows(1, q[k:k + 128], 2, 10) for k in range(0, n_q, 128)]
         assert _bits_equal(got["quantiles"], np.concatenate([p["quantiles"] for p in pieces], axis=1))
         assert np.array_equal(got["count"], (~np.isnan(rows)).sum(axis=1))
@@ -215,22 +207,12 @@ def test_two_handles_summing_their_histograms_equal_the_whole(ra, split):
             assert _bits_equal(a.quantile_rows(1, Q)["quantiles"], a.quantile_series(1, Q)["quantiles"])   # untouched by it
 
 
-def _chain():
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_windowed_graph_quantile_rows(ra):
     """The MAGICC chain, monthly steps, a 16-row window and every 12th row kept (configs[3]'s storage at a few thousand members):
     GraphModel.quantile_rows over the annual rows is numpy.nanquantile of get_series(t_stride=12), mid-run and at the end, for
     five variables; rows still in the window are read there; a row that is in neither is RSCM_ERR_STATE."""
     from rscm_amd import RscmGpuError
-    mod = _chain()
+    mod = magicc_chain()
     names = ["Surface Temperature", "Atmospheric Concentration|CO2", "Effective Radiative Forcing", "Sea Surface Temperature",
              "Atmospheric Concentration|CH4"]
     model = mod.build_chain(3001, 30, "topological", steps_per_year=12, series_window=16, output_stride=12)
@@ -245,12 +227,12 @@ def test_windowed_graph_quantile_rows(ra):
             for name in names:
                 got = model.quantile_rows(name, Q, t_stride=12)
                 ser = model.get_series(name, t_stride=12)
-                assert np.array_equal(got["quantiles"], _nanq(ser, Q), equal_nan=True), (stop, name)
+                assert same_values(got["quantiles"], _nanq(ser, Q)), (stop, name)
                 assert np.array_equal(got["count"], (~np.isnan(ser)).sum(axis=1)), (stop, name)
                 assert np.isfinite(got["quantiles"][1: ti // 12 + 1]).all(), (stop, name)
                 w0 = ti - 2                               # rows of the window, at every index
                 win = model.quantile_rows(name, Q, w0, ti + 1)
-                assert np.array_equal(win["quantiles"], _nanq(model.get_series(name, t_begin=w0, t_end=ti + 1), Q), equal_nan=True)
+                assert same_values(win["quantiles"], _nanq(model.get_series(name, t_begin=w0, t_end=ti + 1), Q))
             with pytest.raises(RscmGpuError, match="not resident") as err:
                 model.quantile_rows("Surface Temperature", Q, 13, 14)
             assert err.value.code == 2                    # RSCM_ERR_STATE

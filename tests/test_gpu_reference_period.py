@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 from tests import host_likelihood as hl
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import TL_RANGES, assert_bit_equal, axis_values, emissions_syn, f_syn, two_layer_params
 from tests.host_indicators import anomaly, baseline
 
@@ -22,15 +23,6 @@ pytestmark = pytest.mark.gpu
 TS, TD = 1, 2
 NAMES = ["lambda0", "a", "efficacy", "eta", "heat_capacity_surface", "heat_capacity_deep"]
 DEFAULTS = dict(lambda0=1.0, a=0.0, efficacy=1.0, eta=0.7, heat_capacity_surface=8.0, heat_capacity_deep=100.0)
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()  # fails loudly when the HIP extension is missing
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 def _rows(a, b, step=1):

@@ -10,7 +10,8 @@ knows, so the restatement predicts every proposal, partner, accept decision and 
 import numpy as np
 import pytest
 
-from tests.helpers import TL_RANGES, SEED, emissions_syn
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import TL_RANGES, SEED, bits, emissions_syn
 from tests.host_sampler import HostStretchMove, lhs_matrix, marginal
 from tests.test_gpu_sampler import NAMES, _problem, setup  # noqa: F401  (setup: that module's fixture)
 
@@ -20,13 +21,9 @@ RANGES = dict(zip(NAMES, TL_RANGES))
 DIMS = {1: ["lambda0"], 2: ["lambda0", "efficacy"], 6: NAMES}
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same_bits(a, b):
+def _identical_bits(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and np.array_equal(_bits(a), _bits(b))
+    return a.shape == b.shape and np.array_equal(bits(a), bits(b))
 
 
 # ------------------------------------------------------------------------------------------ the whole chain
@@ -65,8 +62,8 @@ def test_device_chain_equals_restatement(setup, D, a, seed, W, G, S):
     want_pos, want_lp = sm.run(S)
     assert len(chain) == S and chain.total_iterations == S
     for s in range(S):
-        assert _same_bits(chain._samples[s], want_pos[s]), f"sweep {s + 1}: positions"
-        assert _same_bits(chain._log_probs[s], want_lp[s]), f"sweep {s + 1}: log probabilities"
+        assert _identical_bits(chain._samples[s], want_pos[s]), f"sweep {s + 1}: positions"
+        assert _identical_bits(chain._log_probs[s], want_lp[s]), f"sweep {s + 1}: log probabilities"
     assert np.array_equal(dev.n_accepted, sm.n_accepted) and (dev.n_proposed == S).all()
     assert np.array_equal(dev.n_proposed, sm.n_proposed)
     assert sm.n_accepted.sum() < S * W and (W == 2 or sm.n_accepted.sum() > 0)   # some moves rejected, some accepted
@@ -80,7 +77,7 @@ def test_device_chain_equals_restatement(setup, D, a, seed, W, G, S):
     thin = dev.run(S, cal.WalkerInit.explicit(pos), thin=3, n_walkers=W, seed=seed, n_groups=G)
     assert thin.total_iterations == S and len(thin) == len(range(0, S, 3))
     for k, s in enumerate(range(0, S, 3)):
-        assert _same_bits(thin._samples[k], want_pos[s]) and _same_bits(thin._log_probs[k], want_lp[s])
+        assert _identical_bits(thin._samples[k], want_pos[s]) and _identical_bits(thin._log_probs[k], want_lp[s])
     print(f"\nchain D={D} a={a} seed={seed} W={W} groups={G}: {sm.n_decisions} decisions bit-exact, "
           f"acceptance {sm.n_accepted.sum() / sm.n_proposed.sum():.3f}")
     runner.close()
@@ -106,14 +103,14 @@ def _check_half_steps(chain, D, a, seed, W, score, rtol, atol, G=1):
                 tol = atol + rtol * np.abs(new)
             marg = marginal(st.u, lr, new, score_tol=tol)
             rec = nxt[act]
-            old = (_bits(rec) == _bits(pos[act])).all(axis=1)
-            prop = (_bits(rec) == _bits(st.proposal)).all(axis=1)
+            old = (bits(rec) == bits(pos[act])).all(axis=1)
+            prop = (bits(rec) == bits(st.proposal)).all(axis=1)
             assert (old | prop).all(), f"sweep {s + 2} half {half}: a position that is neither the old one nor the proposal"
             moved = ~old
             bad = (moved != want) & ~marg
             assert not bad.any(), (f"sweep {s + 2} half {half}: walkers {act[bad][:8]} decided otherwise "
                                    f"(device moved: {moved[bad][:8]}, scores {new[bad][:8]} vs old {lp[act][bad][:8]})")
-            assert _same_bits(nlp[act][~moved], lp[act][~moved])
+            assert _identical_bits(nlp[act][~moved], lp[act][~moved])
             assert np.allclose(nlp[act][moved], new[moved], rtol=rtol, atol=atol) and np.isfinite(nlp[act][moved]).all()
             n_dec += len(act)
             n_marg += int(marg.sum())
@@ -220,15 +217,6 @@ LHS_KINDS = [  # kind name, low, high: different parameter counts, one row with 
 LHS_SEEDS = [0, SEED, 2 ** 32 + 7, 2 ** 64 - 1]
 
 
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
 def _lhs(ra, kind, n_local, seed, lo, hi, offset, n_total):
     t = np.arange(1750.0, 1753.0)
     with ra.Ensemble(getattr(ra, kind), n_local, np.append(t, t[-1] + 1.0)) as e:
@@ -244,13 +232,13 @@ def test_device_lhs_equals_restatement(ra, n):
     kind, lo, hi = LHS_KINDS[i % len(LHS_KINDS)]
     seed = LHS_SEEDS[(i // len(LHS_KINDS) + i) % len(LHS_SEEDS)]
     got = _lhs(ra, kind, n, seed, lo, hi, 0, n)
-    assert _same_bits(got, lhs_matrix(seed, lo, hi, 0, n, n)), f"{kind} n={n} seed={seed}"
+    assert _identical_bits(got, lhs_matrix(seed, lo, hi, 0, n, n)), f"{kind} n={n} seed={seed}"
     entries = got.size
     if n >= 5:
         cuts = sorted({0, 1, min(n, n // 3 + 5), (2 * n) // 3 - 1, n})
         for a0, a1 in zip(cuts[:-1], cuts[1:]):
             part = _lhs(ra, kind, a1 - a0, seed, lo, hi, a0, n)
-            assert _same_bits(part, got[:, a0:a1]), f"{kind} n={n} members [{a0}, {a1})"
+            assert _identical_bits(part, got[:, a0:a1]), f"{kind} n={n} members [{a0}, {a1})"
             entries += part.size
     print(f"\nlhs {kind} n={n} seed={seed}: {entries} entries bit-exact")
 
@@ -259,8 +247,8 @@ def test_device_lhs_equals_restatement_1e6(ra):
     n, seed = 1_000_003, 2 ** 64 - 1
     kind, lo, hi = LHS_KINDS[1]
     got = _lhs(ra, kind, n, seed, lo, hi, 0, n)
-    assert _same_bits(got, lhs_matrix(seed, lo, hi, 0, n, n))
+    assert _identical_bits(got, lhs_matrix(seed, lo, hi, 0, n, n))
     # a block of the same global ensemble at an odd offset
     part = _lhs(ra, kind, 70001, seed, lo, hi, 333_333, n)
-    assert _same_bits(part, got[:, 333_333:403_334])
+    assert _identical_bits(part, got[:, 333_333:403_334])
     print(f"\nlhs {kind} n={n} seed={seed}: {got.size + part.size} entries bit-exact")

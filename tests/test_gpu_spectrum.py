@@ -1,7 +1,7 @@
 """GPU tier of the per-member band powers and of the spectral likelihood over them (csrc/spectrum.hip; rscm_ens_member_spectrum,
 rscm_ens_loglik_spectrum_device; Ensemble.spectrum, Ensemble.loglik_spectrum, GraphModel.spectrum).  The oracle of the statistic is
-the numpy restatement of tests/host_spectrum.py on rows copied to the host, compared bit for bit (any NaN equal to any NaN); the
-likelihood takes logarithms and is held to a derived bound against the restatement in np.longdouble.
+the numpy restatement of tests/host_spectrum.py on rows copied to the host, compared by value (+0 equal to -0, any NaN equal to
+any NaN); the likelihood takes logarithms and is held to a derived bound against the restatement in np.longdouble.
 
 The data are those of tests/test_gpu_variability.py on a longer axis: two-layer ensembles with per-member forcing noise
 (noise_params=True, set_forcing_noise_members) on a 72-point annual axis (4 F + 8 with the kernel's tile of F = 16 frequencies), half
@@ -9,8 +9,6 @@ the members under zero forcing and half under a ramp.  From 63 members on, three
 forcing (a constant series), one with a NaN parameter (NaN rows) and one with an amplitude that overflows -- and two more have
 +Inf / -Inf written into one row."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
@@ -18,14 +16,15 @@ import pytest
 from tests import host_likelihood as hl
 from tests import host_spectrum as hs
 from tests import host_variability as hv
-from tests.helpers import two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import built_once, noise_ensemble, plant, refusal_code
+from tests.helpers import annual_bounds, magicc_chain, same_values, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 F = 16                               # kSpecF of csrc/spectrum.hip: the frequencies a lane carries per pass over the rows
 T = 4 * F + 8
-YEARS = np.arange(1850, 1850 + T, dtype=np.float64)
-BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+YEARS, BOUNDS = annual_bounds(T)
 SEED = 20260327
 DETREND = ("mean", "linear", "difference")
 SIZES = [1, 63, 64, 257, 1000]       # a single member; below, at and past a wave; a ragged last block; more than one block
@@ -36,61 +35,23 @@ SIZES = [1, 63, 64, 257, 1000]       # a single member; below, at and past a wav
 TERMS = [3, 4, 7, 8, 9, 10, 2 * F - 1, 2 * F, 2 * F + 1, 2 * F + 2, 2 * F + 3, 2 * F + 4, 4 * F + 3, 4 * F + 4]
 
 
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _params(n, offset=0, n_total=None):
-    """[8][n]: the block [offset, offset + n) of the draw of n_total members, noise rows included, specials at the end of the draw."""
-    n_total = n if n_total is None else n_total
-    rng = np.random.default_rng(n_total)
-    P = np.vstack([two_layer_params(n_total), rng.uniform(0.1, 0.6, n_total), rng.uniform(0.0, 0.9, n_total)])
-    scen = (np.arange(n_total) % 2).astype(np.int32)
-    if n_total >= 63:
-        scen[n_total - 3], P[6, n_total - 3] = 0, 0.0      # silent under zero forcing: a constant series
-        P[6, n_total - 2] = 1.7e308                        # sigma_i z overflows
-        P[0, n_total - 1] = np.nan
-    return np.ascontiguousarray(P[:, offset:offset + n]), np.ascontiguousarray(scen[offset:offset + n])
-
-
 def _ensemble(ra, n, offset=0, n_total=None, steps=None, **kw):
-    P, scen = _params(n, offset, n_total)
-    e = ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS, noise_params=True, **kw)
-    e.set_params(P)
-    e.set_forcing(np.stack([np.zeros(T), 0.05 * np.arange(T)]), scen)
-    e.set_initial(1, 0.0)
-    e.set_initial(2, 0.0)
-    e.set_forcing_noise_members(SEED, offset)
-    e.run(steps)
-    return e
+    return noise_ensemble(ra, n, BOUNDS, SEED, offset, n_total, steps, **kw)
 
 
 @pytest.fixture(scope="module")
 def cases(ra):
     """{N: (ensemble, its Surface Temperature series [T][N] on the host)}, each built and run once and left unchanged."""
-    made = {}
+    def build(n):
+        e = _ensemble(ra, n)
+        if n >= 63:
+            for member, row, value in ((5, 1, np.inf), (7, 2, -np.inf)):
+                plant(e, 1, member, row, value)
+        ser = e.get_series(1)
+        ser.setflags(write=False)
+        return e, ser
 
-    def get(n):
-        if n not in made:
-            e = _ensemble(ra, n)
-            if n >= 63:
-                for member, row, value in ((5, 1, np.inf), (7, 2, -np.inf)):
-                    x = e.get_series(1, row, row + 1)[0]
-                    x[member] = value
-                    e.set_state(1, row, x)
-            ser = e.get_series(1)
-            ser.setflags(write=False)
-            made[n] = (e, ser)
-        return made[n]
-
-    yield get
-    for e, _ in made.values():
-        e.close()
+    yield from built_once(build)
 
 
 def _host(d):
@@ -106,14 +67,7 @@ def _check(got, want, what):
     gv, wv = _vectors(got), _vectors(want)
     assert len(gv) == len(wv), what
     for k, (g, w) in enumerate(zip(gv, wv)):
-        assert np.array_equal(g, w, equal_nan=True), (what, k, np.flatnonzero(~((g == w) | (np.isnan(g) & np.isnan(w))))[:5])
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
+        assert same_values(g, w), (what, k, np.flatnonzero(~((g == w) | (np.isnan(g) & np.isnan(w))))[:5])
 
 
 def _band_choices(n):
@@ -164,23 +118,15 @@ def test_first_three_are_variabilitys_bits(cases):
             want = {k: var[k].to_host() for k in hs.FIRST}
             spec = e.spectrum(1, 0, R, detrend=detrend, slot=1)
             for k in hs.FIRST:
-                assert np.array_equal(spec[k].to_host(), want[k], equal_nan=True), (detrend, R, k)
+                assert same_values(spec[k].to_host(), want[k]), (detrend, R, k)
             ref = hv.variability(ser[:R], detrend)
-            assert all(np.array_equal(want[k], ref[k], equal_nan=True) for k in hs.FIRST)
-
-
-def _chain():
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
+            assert all(same_values(want[k], ref[k]) for k in hs.FIRST)
 
 
 def test_storage_layouts(ra):
     """A windowed graph's output-store rows give the band powers of the full-storage build of the same graph; rows that are not
     resident, or not yet computed, are refused."""
-    mod = _chain()
+    mod = magicc_chain()
     name, n = "Surface Temperature", 301
     got = {}
     for key, kw in (("windowed", dict(series_window=16, output_stride=12)), ("full", {})):
@@ -198,14 +144,14 @@ def test_storage_layouts(ra):
                 for d in DETREND:
                     _check(got[key][d], hs.spectrum(ser, d, edges[d]), ("chain", d))
             else:
-                assert _code(model.spectrum, name, 0, 9, 3) == 2          # rows 3 and 6: outside the window and the output stride
+                assert refusal_code(model.spectrum, name, 0, 9, 3) == 2          # rows 3 and 6: outside the window and the output stride
         finally:
             model.close()
     for d in DETREND:
         _check(got["windowed"][d], got["full"][d], ("windowed against full", d))
     with _ensemble(ra, 64, steps=10) as e:
         assert e.time_index == 10
-        assert _code(e.spectrum, 1, 0, 20) == 2                           # rows beyond the time index
+        assert refusal_code(e.spectrum, 1, 0, 20) == 2                           # rows beyond the time index
         e.spectrum(1, 0, 11)
 
 
@@ -214,7 +160,7 @@ def test_slots_and_refusals(ra, cases):
     var = e.variability(1, 0, 30, slot=0)
     keep = {k: var[k].to_host() for k in hv.NAMES}
     spec = e.spectrum(1, 0, 40, detrend="linear", bands=8, slot=1)
-    assert all(np.array_equal(var[k].to_host(), keep[k], equal_nan=True) for k in hv.NAMES)
+    assert all(same_values(var[k].to_host(), keep[k]) for k in hv.NAMES)
     assert spec["mean"].ptr != var["mean"].ptr
     kept = _host(spec)
     _check(kept, hs.spectrum(ser[:40], "linear", spec["edges"]), "slot 1")
@@ -222,8 +168,8 @@ def test_slots_and_refusals(ra, cases):
     e.indicators(1, 0, 30, thresholds=[0.2], slot=2)
     _check(_host(spec), kept, "slot 1 after calls on slots 0 and 2")
     assert e.spectrum(1, 0, 30, slot=0)["mean"].ptr == var["mean"].ptr          # the slots are the indicators'
-    assert _code(e.spectrum, 1, 0, 30, slot=4) == 1
-    assert _code(e.spectrum, 1, 0, 30, slot=-1) == 1
+    assert refusal_code(e.spectrum, 1, 0, 30, slot=4) == 1
+    assert refusal_code(e.spectrum, 1, 0, 30, slot=-1) == 1
     with pytest.raises(ValueError):
         e.spectrum(1, 0, 30, detrend="quadratic")
     p = C.c_void_p()
@@ -233,16 +179,16 @@ def test_slots_and_refusals(ra, cases):
     assert e._lib.rscm_ens_member_spectrum(e._h, 0, 0, 30, 1, 0, 1, two, 0, C.byref(p)) == 1       # no stored series
     assert e._lib.rscm_ens_member_spectrum(e._h, 1, 0, 30, 1, 0, 1, None, 0, C.byref(p)) == 1      # no edges
     # too short: two terms, and two differences
-    assert _code(e.spectrum, 1, 0, 2, detrend="mean") == 1 and _code(e.spectrum, 1, 0, 3, detrend="difference") == 1
-    assert _code(e.spectrum, 1, 5, 5) == 1
+    assert refusal_code(e.spectrum, 1, 0, 2, detrend="mean") == 1 and refusal_code(e.spectrum, 1, 0, 3, detrend="difference") == 1
+    assert refusal_code(e.spectrum, 1, 5, 5) == 1
     # the edges: 30 rows, "mean": n = 30, J = 14, edges inside [1, 15]
     for edges in ([1, 5, 5], [3, 2], [0, 4], [1, 16], [-1, 3], list(range(1, 11))):
-        assert _code(e.spectrum, 1, 0, 30, detrend="mean", bands=edges) == 1, edges
+        assert refusal_code(e.spectrum, 1, 0, 30, detrend="mean", bands=edges) == 1, edges
     e.spectrum(1, 0, 30, detrend="mean", bands=[1, 15])
     e.spectrum(1, 0, 30, detrend="mean", bands=list(range(1, 10)))
-    assert _code(e.spectrum, 1, 0, 28, detrend="difference", bands=[1, 15]) == 1       # n = 27: J + 1 = 14
+    assert refusal_code(e.spectrum, 1, 0, 28, detrend="difference", bands=[1, 15]) == 1       # n = 27: J + 1 = 14
     with e.select(1, [0.5], 0, 30) as s:
-        assert _code(e.spectrum, 1, 0, 30) == 2
+        assert refusal_code(e.spectrum, 1, 0, 30) == 2
         while s.next_pass() is not None:
             s.commit()
 
@@ -259,8 +205,8 @@ def test_more_than_4096_terms_are_refused(ra):
         e.set_initial(2, 0.0)
         e.set_forcing_noise_members(SEED, 0)
         e.run()
-        assert _code(e.spectrum, 1, 0, 4097, detrend="mean") == 1
-        assert _code(e.spectrum, 1, 0, 4098, detrend="difference") == 1
+        assert refusal_code(e.spectrum, 1, 0, 4097, detrend="mean") == 1
+        assert refusal_code(e.spectrum, 1, 0, 4098, detrend="difference") == 1
         d = e.spectrum(1, 0, 4097, detrend="difference")
         _check(_host(d), hs.spectrum(e.get_series(1, 0, 4097), "difference", d["edges"]), "4096 terms")
 
@@ -279,7 +225,7 @@ def scored(cases):
     dev = list(diff["power"]) + list(lin["power"])
     host = [p.to_host() for p in dev]
     want = hs.spectrum(ser, "difference", diff["edges"])["power"] + hs.spectrum(ser, "linear", lin["edges"])["power"]
-    assert all(np.array_equal(h, w, equal_nan=True) for h, w in zip(host, want))
+    assert all(same_values(h, w) for h, w in zip(host, want))
     counts = [int(c) for c in diff["counts"]] + [int(c) for c in lin["counts"]]
     rec = ser[:, 2]                                                    # one member's series serves as the record
     record = series_spectrum(rec, "difference", diff["edges"])["power"] + series_spectrum(rec, "linear", lin["edges"])["power"]
@@ -338,14 +284,14 @@ def test_loglik_spectrum_onto_a_point_likelihood(scored):
 
 def test_loglik_spectrum_refusals(scored):
     e, ser, dev, host, counts, record = scored
-    assert _code(e.loglik_spectrum, dev[:1], [0.0], [1]) == 1
-    assert _code(e.loglik_spectrum, dev[:1], [-1.0], [1]) == 1
-    assert _code(e.loglik_spectrum, dev[:1], [np.nan], [1]) == 1
-    assert _code(e.loglik_spectrum, dev[:1], [np.inf], [1]) == 1
-    assert _code(e.loglik_spectrum, dev[:1], [0.1], [0]) == 1
-    assert _code(e.loglik_spectrum, dev[:1], [0.1], [-2]) == 1
-    assert _code(e.loglik_spectrum, [], [], []) == 1
-    assert _code(e.loglik_spectrum, [dev[0]] * 17, [0.1] * 17, [1] * 17) == 1
+    assert refusal_code(e.loglik_spectrum, dev[:1], [0.0], [1]) == 1
+    assert refusal_code(e.loglik_spectrum, dev[:1], [-1.0], [1]) == 1
+    assert refusal_code(e.loglik_spectrum, dev[:1], [np.nan], [1]) == 1
+    assert refusal_code(e.loglik_spectrum, dev[:1], [np.inf], [1]) == 1
+    assert refusal_code(e.loglik_spectrum, dev[:1], [0.1], [0]) == 1
+    assert refusal_code(e.loglik_spectrum, dev[:1], [0.1], [-2]) == 1
+    assert refusal_code(e.loglik_spectrum, [], [], []) == 1
+    assert refusal_code(e.loglik_spectrum, [dev[0]] * 17, [0.1] * 17, [1] * 17) == 1
     e.loglik_spectrum([dev[0]] * 16, [0.1] * 16, [1] * 16)
     with pytest.raises(ValueError):
         e.loglik_spectrum(dev[:2], [0.1], [1])
@@ -369,4 +315,4 @@ def test_two_shards_give_the_halves(ra, cases):
             for d in DETREND:
                 got = _host(h.spectrum(1, 4, T, detrend=d))
                 for g, w in zip(_vectors(got), _vectors(whole[d])):
-                    assert np.array_equal(g, w[offset:offset + count], equal_nan=True), (d, offset)
+                    assert same_values(g, w[offset:offset + count]), (d, offset)

@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 from scripts import two_layer_box_proof as proof
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import SEED, assert_bit_equal, axis_values, f_syn, two_layer_params
 from tests.test_gpu_two_layer_guard import BASE, _edge_values, _guard, _run, _three_ways
 
@@ -13,15 +14,6 @@ pytestmark = pytest.mark.gpu
 CHUNK = proof.read_boxes(proof.CHUNK_HEADER)
 # parameter rows and their chunk boxes (efficacy * eta is boxed as a product: row 2 is efficacy, set apart below)
 ROWS = {0: CHUNK["Lambda0"], 1: CHUNK["A"], 3: CHUNK["Eta"], 4: CHUNK["Cs"], 5: CHUNK["Cd"]}
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import SEED, TL_RANGES, assert_bit_equal, axis_values, f_syn, two_layer_params
 
 pytestmark = pytest.mark.gpu
@@ -13,15 +14,6 @@ pytestmark = pytest.mark.gpu
 BASE = np.array([1.0, 0.0, 1.0, 0.7, 8.0, 100.0])
 # (lo, hi) exponents of the parameter boxes, in parameter-row order (efficacy * eta is boxed as a product: row 2 is efficacy)
 BOXES = {0: (-16, 6), 1: (-64, 2), 3: (-16, 6), 4: (-2, 10), 5: (-2, 14)}
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

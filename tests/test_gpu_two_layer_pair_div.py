@@ -5,35 +5,24 @@ rscm_gpu_selftest_pair_div; the stored bits with the lane (rscm_gpu_set_two_laye
 wavefronts that take it, that are kept out by one member and that get in through a neighbouring constant; the constants after every
 way of writing a parameter row; cut runs; and who never takes the lane.  Every comparison is bit for bit."""
 import ctypes as C
-import importlib.util
 import json
 import os
 
 import numpy as np
 import pytest
 
-from tests.helpers import SEED, assert_bit_equal, bits, f_syn
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import SEED, assert_bit_equal, bits, f_syn, load_script
 from tests.test_gpu_two_layer_guard import BASE
 from tests.test_gpu_two_layer_uniform_year import TD, TS, _annual, _counts
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_spec = importlib.util.spec_from_file_location("pair_div_proof", os.path.join(ROOT, "scripts", "pair_div_proof.py"))
-P = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(P)
+P = load_script("pair_div_proof")
 GOLDEN = json.load(open(os.path.join(ROOT, "tests", "golden", "pair_div_unsafe.json")))
 NUM_LO, NUM_HI, DEEP_LO = P.NUM_LO, 760, P.SURFACE_NUM_FLOOR
 DIV_LO, DIV_HI = -2, 14
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -8,6 +8,7 @@ run and the fused likelihood, between a cut run and a plain one."""
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
 from tests.helpers import SEED, assert_bit_equal, f_syn, two_layer_params
 from tests.test_gpu_two_layer_guard import BASE, _guard
 
@@ -17,15 +18,6 @@ TS, TD = "Surface Temperature", "Deep Ocean Temperature"
 # the chunk forcing box is [2^-128, 2^13) and +0 (csrc/two_layer_chunk_box.hpp)
 EDGE_VALUES = {"minus-zero": -0.0, "2^13": 2.0 ** 13, "below-2^13": np.nextafter(2.0 ** 13, 0.0), "2^-128": 2.0 ** -128,
                "below-2^-128": np.nextafter(2.0 ** -128, 0.0), "denormal": 5e-324, "1e300": 1e300, "inf": np.inf, "nan": np.nan}
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1, "no HIP device visible"
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")

@@ -11,6 +11,8 @@ import os
 import numpy as np
 import pytest
 
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import same_values
 from tests.test_oracle_udeb import PHASED, RECORDED, W, phased_ok, scenario_inputs
 
 pytestmark = pytest.mark.gpu
@@ -19,15 +21,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ude
 NAMES = {"st0": "Surface Temperature|NorthernOcean", "st1": "Surface Temperature|NorthernLand",
          "st2": "Surface Temperature|SouthernOcean", "st3": "Surface Temperature|SouthernLand",
          "heat_uptake": "Heat Uptake", "ohc": "Ocean Heat Content", "sst": "Sea Surface Temperature"}
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
 
 
 @pytest.fixture(scope="module")
@@ -140,7 +133,7 @@ def test_udeb_gpu_any_layer_count(ra, orc, n_layers):
     assert all(np.isnan(got[k][1:, 7]).all() for k in NAMES)
     again, _ = _gpu(ra, b, P, F, scen=scen, chunks=(1, 29))
     for k in NAMES:
-        assert np.array_equal(again[k], got[k], equal_nan=True), k
+        assert same_values(again[k], got[k]), k
     fast, _ = _gpu(ra, b, P, F, scen=scen, mode=ra.MODE_FAST)
     _assert_close(fast, want, f"{n_layers} layers, FAST")
     if n_layers <= 128:
@@ -151,7 +144,7 @@ def test_udeb_gpu_any_layer_count(ra, orc, n_layers):
                     other, st_v = _gpu(ra, b, P, F, scen=scen, chunks=(17,), mode=mode)
                     assert (st_v == st).all()
                     for k in NAMES:
-                        assert np.array_equal(other[k], ref[k], equal_nan=True), (v, mode, k)
+                        assert same_values(other[k], ref[k]), (v, mode, k)
         finally:
             _variant(ra, -1)
 
@@ -177,7 +170,7 @@ def test_udeb_gpu_runtime_layer_count_one_thread_kernel(ra, orc, n_layers):
     finally:
         _variant(ra, -1)
     for k in NAMES:
-        assert np.array_equal(two[k], got[k], equal_nan=True), k
+        assert same_values(two[k], got[k]), k
 
 
 def test_udeb_gpu_layer_count_errors(ra, orc):
@@ -215,11 +208,11 @@ def test_udeb_gpu_fast_mode(ra, orc, n_members):
     assert 0.0 < worst < 1e-11
     again, _ = _gpu(ra, b, P, F, scen=scen, chunks=(1, 50), mode=ra.MODE_FAST)
     for k in NAMES:
-        assert np.array_equal(again[k], got[k], equal_nan=True), k
+        assert same_values(again[k], got[k]), k
     if n_members > 32768:   # the first members through the other kernel: the same bits
         small, _ = _gpu(ra, b, P[:, :256].copy(), F, scen=scen[:256].copy(), mode=ra.MODE_FAST)
         for k in NAMES:
-            assert np.array_equal(small[k], got[k][:, :256], equal_nan=True), k
+            assert same_values(small[k], got[k][:, :256]), k
 
 
 def test_udeb_gpu_ensemble_vs_oracle(ra, orc):
@@ -238,7 +231,7 @@ def test_udeb_gpu_ensemble_vs_oracle(ra, orc):
     # resume: three launches give the same bits as one
     again, _ = _gpu(ra, b, P, F, scen=scen, chunks=(1, 37))
     for k in NAMES:
-        assert np.array_equal(again[k], got[k], equal_nan=True), k
+        assert same_values(again[k], got[k]), k
 
 
 @pytest.mark.parametrize("n_members", [96, 40000])   # the two-wavefront kernel (a hemisphere per wavefront) and the one-thread kernel
@@ -438,12 +431,12 @@ def test_udeb_runs_cut_into_member_blocks_and_chunks_keep_the_bits(ra, orc, n_la
     assert plans == [(1, 1)] * 5, plans
     assert np.array_equal(st_cut, st_one) and not st_cut.any()
     for k in NAMES:
-        assert np.array_equal(cut_rows[k], one_rows[k], equal_nan=True), k
-        assert np.array_equal(cut_sample[k], one_sample[k], equal_nan=True), k
+        assert same_values(cut_rows[k], one_rows[k]), k
+        assert same_values(cut_sample[k], one_sample[k]), k
     for key in ck_cut:   # ocean columns, scalars, history: the internal state
         a, c = ck_cut[key], ck_one[key]
         if isinstance(a, np.ndarray):
-            assert np.array_equal(a, c, equal_nan=True), key
+            assert same_values(a, c), key
     pick = np.arange(34_960, 35_060)
     want, wst = orc.udeb_run(b, P[:, pick].copy(), F, scen=scen[pick].copy(), threads=8)
     assert not wst.any()
@@ -496,4 +489,4 @@ def test_udeb_runtime_layer_count_one_step_per_launch(ra, orc, n_layers, n):
         while not e.finished():
             e.step()
         for k, v in NAMES.items():
-            assert np.array_equal(e.get_series(v), whole[k], equal_nan=True), k
+            assert same_values(e.get_series(v), whole[k]), k

@@ -1,28 +1,27 @@
 """GPU tier of the per-member variability statistics and of the Gaussian likelihood over per-member vectors
 (csrc/variability.hip; rscm_ens_member_variability, rscm_ens_loglik_vectors_device; Ensemble.variability, Ensemble.loglik_vectors,
 GraphModel.variability).  The oracle is the numpy restatement of tests/host_variability.py on rows copied to the host, compared
-bit for bit (any NaN equal to any NaN).
+by value (+0 equal to -0, any NaN equal to any NaN).
 
 The data: two-layer ensembles with per-member forcing noise (noise_params=True, set_forcing_noise_members) on a 48-point annual
 axis, half the members under zero forcing and half under a ramp.  From 63 members on, three members are special -- a silent one
 under zero forcing (a constant series), one with a NaN parameter (NaN rows) and one with an amplitude that overflows -- and two
 more have +Inf / -Inf written into one row."""
 import ctypes as C
-import importlib.util
-import os
 
 import numpy as np
 import pytest
 
 from tests import host_likelihood as hl
 from tests import host_variability as hv
-from tests.helpers import two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.gpu_support import built_once, noise_ensemble, plant, refusal_code
+from tests.helpers import annual_bounds, magicc_chain, same_values, two_layer_params
 
 pytestmark = pytest.mark.gpu
 
 T = 48
-YEARS = np.arange(1850, 1850 + T, dtype=np.float64)
-BOUNDS = np.append(YEARS, YEARS[-1] + 1.0)
+YEARS, BOUNDS = annual_bounds(T)
 SEED = 20260327
 DETREND = ("mean", "linear", "difference")
 SIZES = [1, 63, 64, 257, 1000]       # a single member; below, at and past a wave; a ragged last block; more than one block
@@ -31,61 +30,23 @@ SIZES = [1, 63, 64, 257, 1000]       # a single member; below, at and past a wav
 ROWS = [3, 4, 7, 8, 9, 10, 11, 12, 16, 17, 40]
 
 
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _params(n, offset=0, n_total=None):
-    """[8][n]: the block [offset, offset + n) of the draw of n_total members, noise rows included, specials at the end of the draw."""
-    n_total = n if n_total is None else n_total
-    rng = np.random.default_rng(n_total)
-    P = np.vstack([two_layer_params(n_total), rng.uniform(0.1, 0.6, n_total), rng.uniform(0.0, 0.9, n_total)])
-    scen = (np.arange(n_total) % 2).astype(np.int32)
-    if n_total >= 63:
-        scen[n_total - 3], P[6, n_total - 3] = 0, 0.0      # silent under zero forcing: a constant series
-        P[6, n_total - 2] = 1.7e308                        # sigma_i z overflows
-        P[0, n_total - 1] = np.nan
-    return np.ascontiguousarray(P[:, offset:offset + n]), np.ascontiguousarray(scen[offset:offset + n])
-
-
 def _ensemble(ra, n, offset=0, n_total=None, steps=None, **kw):
-    P, scen = _params(n, offset, n_total)
-    e = ra.Ensemble(ra.KIND_TWO_LAYER, n, BOUNDS, noise_params=True, **kw)
-    e.set_params(P)
-    e.set_forcing(np.stack([np.zeros(T), 0.05 * np.arange(T)]), scen)
-    e.set_initial(1, 0.0)
-    e.set_initial(2, 0.0)
-    e.set_forcing_noise_members(SEED, offset)
-    e.run(steps)
-    return e
+    return noise_ensemble(ra, n, BOUNDS, SEED, offset, n_total, steps, **kw)
 
 
 @pytest.fixture(scope="module")
 def cases(ra):
     """{N: (ensemble, its Surface Temperature series [T][N] on the host)}, each built and run once and left unchanged."""
-    made = {}
+    def build(n):
+        e = _ensemble(ra, n)
+        if n >= 63:
+            for member, row, value in ((5, 1, np.inf), (7, 2, -np.inf)):
+                plant(e, 1, member, row, value)
+        ser = e.get_series(1)
+        ser.setflags(write=False)
+        return e, ser
 
-    def get(n):
-        if n not in made:
-            e = _ensemble(ra, n)
-            if n >= 63:
-                for member, row, value in ((5, 1, np.inf), (7, 2, -np.inf)):
-                    x = e.get_series(1, row, row + 1)[0]
-                    x[member] = value
-                    e.set_state(1, row, x)
-            ser = e.get_series(1)
-            ser.setflags(write=False)
-            made[n] = (e, ser)
-        return made[n]
-
-    yield get
-    for e, _ in made.values():
-        e.close()
+    yield from built_once(build)
 
 
 def _host(d):
@@ -95,14 +56,7 @@ def _host(d):
 def _check(got, want, what):
     assert set(got) == set(hv.NAMES)
     for k in hv.NAMES:
-        assert np.array_equal(got[k], want[k], equal_nan=True), (what, k, np.flatnonzero(~((got[k] == want[k]) | (np.isnan(got[k]) & np.isnan(want[k]))))[:5])
-
-
-def _code(fn, *a, **k):
-    from rscm_amd._lib import RscmGpuError
-    with pytest.raises(RscmGpuError) as err:
-        fn(*a, **k)
-    return err.value.code
+        assert same_values(got[k], want[k]), (what, k, np.flatnonzero(~((got[k] == want[k]) | (np.isnan(got[k]) & np.isnan(want[k]))))[:5])
 
 
 @pytest.mark.parametrize("n", SIZES)
@@ -114,7 +68,7 @@ def test_statistics_equal_the_restatement(ra, cases, n):
     for detrend in DETREND:
         for R in ROWS:
             if detrend == "difference" and R == 3:
-                assert _code(e.variability, 1, 0, R, detrend=detrend) == 1       # two differences
+                assert refusal_code(e.variability, 1, 0, R, detrend=detrend) == 1       # two differences
                 continue
             got, want = _host(e.variability(1, 0, R, detrend=detrend)), hv.variability(ser[:R], detrend)
             _check(got, want, (detrend, R))
@@ -128,18 +82,10 @@ def test_statistics_equal_the_restatement(ra, cases, n):
         _check(_host(e.variability(1, T - 5, T, detrend=detrend, slot=3)), hv.variability(ser[T - 5:], detrend), (detrend, "last rows"))
 
 
-def _chain():
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
 def test_storage_layouts(ra):
     """A windowed graph's output-store rows give the statistics of the full-storage build of the same graph; rows that are not
     resident, or not yet computed, are refused."""
-    mod = _chain()
+    mod = magicc_chain()
     name, n = "Surface Temperature", 301
     got = {}
     for key, kw in (("windowed", dict(series_window=16, output_stride=12)), ("full", {})):
@@ -154,14 +100,14 @@ def test_storage_layouts(ra):
                 for d in DETREND:
                     _check(got[key][d], hv.variability(ser, d), ("chain", d))
             else:
-                assert _code(model.variability, name, 0, 9, 3) == 2          # rows 3 and 6: outside the window and the output stride
+                assert refusal_code(model.variability, name, 0, 9, 3) == 2          # rows 3 and 6: outside the window and the output stride
         finally:
             model.close()
     for d in DETREND:
         _check(got["windowed"][d], got["full"][d], ("windowed against full", d))
     with _ensemble(ra, 64, steps=10) as e:
         assert e.time_index == 10
-        assert _code(e.variability, 1, 0, 20) == 2                           # rows beyond the time index
+        assert refusal_code(e.variability, 1, 0, 20) == 2                           # rows beyond the time index
         e.variability(1, 0, 11)
     with ra.Ensemble(ra.KIND_TWO_LAYER, 64, BOUNDS, window_rows=8, output_stride=5) as w:    # (a windowed handle takes no noise rows)
         w.set_params(two_layer_params(64))
@@ -170,7 +116,7 @@ def test_storage_layouts(ra):
         w.set_initial(2, 0.0)
         while w.time_index < T - 1:
             w.run(min(w.time_index + 4, T - 1))
-        assert _code(w.variability, 1, 0, 3) == 2                            # row 1 is neither in the window nor in the output store
+        assert refusal_code(w.variability, 1, 0, 3) == 2                            # row 1 is neither in the window nor in the output store
         _check(_host(w.variability(1, 0, T, 5, detrend="difference")), hv.variability(w.get_series(1, 0, T, 5), "difference"), "output store")
 
 
@@ -180,21 +126,21 @@ def test_slots_and_refusals(ra, cases):
     keep = [ind["mean"].to_host(), ind["peak"].to_host(), ind["peak_time"].to_host()] + [c.to_host() for c in ind["crossing"]]
     var = e.variability(1, 0, 30, slot=1)
     again = [ind["mean"].to_host(), ind["peak"].to_host(), ind["peak_time"].to_host()] + [c.to_host() for c in ind["crossing"]]
-    assert all(np.array_equal(a, b, equal_nan=True) for a, b in zip(keep, again))
+    assert all(same_values(a, b) for a, b in zip(keep, again))
     assert var["mean"].ptr != ind["mean"].ptr
     _check(_host(var), hv.variability(ser[:30], "linear"), "slot 1")
     assert e.variability(1, 0, 30, slot=0)["mean"].ptr == ind["mean"].ptr         # the slots are the indicators'
-    assert _code(e.variability, 1, 0, 30, slot=4) == 1
-    assert _code(e.variability, 1, 0, 30, slot=-1) == 1
+    assert refusal_code(e.variability, 1, 0, 30, slot=4) == 1
+    assert refusal_code(e.variability, 1, 0, 30, slot=-1) == 1
     with pytest.raises(ValueError):
         e.variability(1, 0, 30, detrend="quadratic")
     p = C.c_void_p()
     for mode in (-1, 3):
         assert e._lib.rscm_ens_member_variability(e._h, 1, 0, 30, 1, mode, 0, C.byref(p)) == 1 and p.value is None
     assert e._lib.rscm_ens_member_variability(e._h, 0, 0, 30, 1, 0, 0, C.byref(p)) == 1       # no stored series
-    assert _code(e.variability, 1, 0, 2) == 1 and _code(e.variability, 1, 5, 5) == 1
+    assert refusal_code(e.variability, 1, 0, 2) == 1 and refusal_code(e.variability, 1, 5, 5) == 1
     with e.select(1, [0.5], 0, 30) as s:
-        assert _code(e.variability, 1, 0, 30) == 2
+        assert refusal_code(e.variability, 1, 0, 30) == 2
         while s.next_pass() is not None:
             s.commit()
 
@@ -216,7 +162,7 @@ def scored(cases):
     dev = [diff["sd"], diff["r1"], lin["slope"], lin["sd"], ind["mean"], e.params_vector(sig_row)]
     host = [want_diff["sd"], want_diff["r1"], want_lin["slope"], want_lin["sd"], mean10, e.get_params()[sig_row]]
     for d, h in zip(dev, host):
-        assert np.array_equal(d.to_host(), h, equal_nan=True)
+        assert same_values(d.to_host(), h)
     return e, ser, dev, host
 
 
@@ -270,12 +216,12 @@ def test_loglik_vectors_onto_a_point_likelihood(scored):
 
 def test_loglik_vectors_refusals(scored):
     e, ser, dev, host = scored
-    assert _code(e.loglik_vectors, dev[:1], [0.1], [0.0]) == 1
-    assert _code(e.loglik_vectors, dev[:1], [0.1], [-1.0]) == 1
-    assert _code(e.loglik_vectors, dev[:1], [0.1], [np.inf]) == 1
-    assert _code(e.loglik_vectors, dev[:1], [np.nan], [1.0]) == 1
-    assert _code(e.loglik_vectors, [], [], []) == 1
-    assert _code(e.loglik_vectors, [dev[0]] * 17, [0.1] * 17, [1.0] * 17) == 1
+    assert refusal_code(e.loglik_vectors, dev[:1], [0.1], [0.0]) == 1
+    assert refusal_code(e.loglik_vectors, dev[:1], [0.1], [-1.0]) == 1
+    assert refusal_code(e.loglik_vectors, dev[:1], [0.1], [np.inf]) == 1
+    assert refusal_code(e.loglik_vectors, dev[:1], [np.nan], [1.0]) == 1
+    assert refusal_code(e.loglik_vectors, [], [], []) == 1
+    assert refusal_code(e.loglik_vectors, [dev[0]] * 17, [0.1] * 17, [1.0] * 17) == 1
     with pytest.raises(ValueError):
         e.loglik_vectors(dev[:2], [0.1], [1.0])
     from rscm_amd import _lib
@@ -298,4 +244,4 @@ def test_two_shards_give_the_halves(ra, cases):
             for d in DETREND:
                 got = _host(h.variability(1, 4, T, detrend=d))
                 for name in hv.NAMES:
-                    assert np.array_equal(got[name], whole[d][name][offset:offset + count], equal_nan=True), (d, name, offset)
+                    assert same_values(got[name], whole[d][name][offset:offset + count]), (d, name, offset)

@@ -8,28 +8,10 @@ per GPU x 9001 monthly points x the ten-component MAGICC graph) fits one MI355X 
 import numpy as np
 import pytest
 
-from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn, f_syn, two_layer_params
+from tests.gpu_support import ra  # noqa: F401
+from tests.helpers import assert_bit_equal, axis_values, coupled_params, emissions_syn, f_syn, magicc_chain, two_layer_params
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ra():
-    import rscm_amd
-    from rscm_amd import _lib
-    _lib.load()
-    assert _lib.device_count() >= 1
-    return rscm_amd
-
-
-def _chain():
-    import importlib.util
-    import os
-    spec = importlib.util.spec_from_file_location(
-        "bench_magicc_chain", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 def test_windowed_two_layer_keeps_the_bits(ra):
@@ -217,7 +199,7 @@ def test_windowed_magicc_graph_equals_full_storage(ra, execution_order):
     variable kept, against the same graph storing whole series: every kept row carries the same bits.  In
     the reference's breadth-first order the forcing aggregate reads rows its producers have not written
     yet and must find NaN there after every slide of their windows."""
-    mod = _chain()
+    mod = magicc_chain()
     years, N = 90, 96
     full = mod.build_chain(N, years, execution_order)
     full.run()
@@ -257,7 +239,7 @@ def test_windowed_magicc_graph_equals_full_storage(ra, execution_order):
 
 
 def test_windowed_outputs_can_be_a_subset(ra):
-    mod = _chain()
+    mod = magicc_chain()
     years, N = 30, 64
     names = ["Sea Surface Temperature", "Atmospheric Concentration|CO2", "Effective Radiative Forcing", "Surface Temperature"]
     win = mod.build_chain(N, years, "topological", series_window=8, output_stride=10, outputs=names)
@@ -281,7 +263,7 @@ def test_configs3_shape_fits_one_gpu(ra):
     with a 16-row window and annual (every 12th) outputs of every variable the graph allocates well under
     250 GB -- and steps."""
     from rscm_amd import _lib as L
-    mod = _chain()
+    mod = magicc_chain()
     free0, total = L.mem_info(0)
     N, years, spy = 125_000, 750, 12
     model = mod.build_chain(N, years, "topological", steps_per_year=spy, series_window=16, output_stride=12)
@@ -372,7 +354,7 @@ def test_windowed_graph_in_fast_mode(ra):
     fresh model re-forms the mode sums from the flux history (Horner instead of the incremental recurrence), so
     the continuation agrees to the FAST tolerance, not to the bit."""
     from rscm_amd import _lib as L
-    mod = _chain()
+    mod = magicc_chain()
     years, N = 80, 96
     full = mod.build_chain(N, years, "topological")
     full.set_mode(L.MODE_FAST)

@@ -8,7 +8,6 @@ has to reproduce both exactly.  The plan-level tests below assert decisions that
 the transform's position, the links that run ahead of their producer; and that every refusal is raised before a stream or an
 ensemble exists.  ``python -m tests.test_graph_plan_cpu`` rewrites the golden file."""
 import hashlib
-import importlib.util
 import json
 import math
 import os
@@ -24,6 +23,7 @@ from rscm_amd.component import Component, Input, Output, PythonComponent, State
 from rscm_amd.components import CarbonCycleBuilder, CO2ERFBuilder, FourBoxOceanHeatUptakeBuilder
 from rscm_amd.two_layer import TwoLayerBuilder
 from tests import host_graph_recorder as hr
+from tests.helpers import magicc_chain
 from tests.test_host_frontend import P_TL, _coupled_builder
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,13 +34,6 @@ INIT = {"Cumulative Land Uptake": 0.0, "Cumulative Emissions|CO2": 0.0, "Atmosph
         "Surface Temperature": 0.0, "Deep Ocean Temperature": 0.0}
 TL_A = dict(lambda0=0.9, a=0.02, efficacy=1.1, eta=0.6, heat_capacity_surface=7.0, heat_capacity_deep=90.0)
 ERF = "Effective Radiative Forcing"
-
-
-def _chain_module():
-    spec = importlib.util.spec_from_file_location("bench_magicc_chain", os.path.join(ROOT, "scripts", "bench_magicc_chain.py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
 
 
 # ------------------------------------------------------------------------------------ the graphs
@@ -215,7 +208,7 @@ def python_alone(copies=1):
 
 def chain(order, **kw):
     """scripts/bench_magicc_chain.py::build_chain on 12 years: ten components, one aggregate of eight, a write transform."""
-    return lambda n: _chain_module().build_chain(n, 12, order, **kw)
+    return lambda n: magicc_chain().build_chain(n, 12, order, **kw)
 
 
 CHAIN_OUTPUTS = ["Surface Temperature", "Atmospheric Concentration|CO2", "Carbon Pool|Soil"]

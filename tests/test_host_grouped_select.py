@@ -9,6 +9,7 @@ import warnings
 import numpy as np
 import pytest
 
+from tests.helpers import same_bits
 from tests.host_gselect import HostGSelect, exceedance_grouped, sharded_gquantiles
 from tests.host_select import HostSelect
 
@@ -45,15 +46,6 @@ def _want(rows, group, G):
             np.stack([(~np.isnan(rows[:, group == g])).sum(axis=1) for g in range(G)]))
 
 
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def _same(a, b):
-    a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
-    return a.shape == b.shape and bool(((_bits(a) == _bits(b)) | (np.isnan(a) & np.isnan(b))).all())
-
-
 @pytest.mark.parametrize("n", SIZES)
 def test_subset_through_host_select_is_numpy_once_rounding_leaves_no_negative_zero(n):
     rng = np.random.default_rng(100 + n)
@@ -61,7 +53,7 @@ def test_subset_through_host_select_is_numpy_once_rounding_leaves_no_negative_ze
     s = HostSelect(rows, Q)
     while s.next_pass() is not None:
         s.commit()
-    assert _same(s.result()["quantiles"], _nanq(rows))
+    assert same_bits(s.result()["quantiles"], _nanq(rows))
     raw = np.round(rng.standard_normal((1, 4099)) * 0.04, 1)       # about a third of its zeros are -0.0 without the + 0.0
     assert (np.signbit(raw) & (raw == 0)).any() and not (np.signbit(raw + 0.0) & (raw == 0)).any()
 
@@ -74,7 +66,7 @@ def test_grouped_restatement_equals_numpy_on_the_subsets(n, G):
     res = sharded_gquantiles([rows], [group], G, Q)[0]
     want, count = _want(rows, group, G)
     assert res["quantiles"].shape == (G, rows.shape[0], len(Q))
-    assert _same(res["quantiles"], want) and np.array_equal(res["count"], count)
+    assert same_bits(res["quantiles"], want) and np.array_equal(res["count"], count)
     if G > 1:
         assert (res["count"][G - 1] == 0).all() and np.isnan(res["quantiles"][G - 1]).all()   # the empty group
 
@@ -106,9 +98,9 @@ def test_sharded_composition_with_a_group_absent_from_a_shard(n, weighted):
         parts = sharded_gquantiles([rows[:, i] for i in idx], [group[i] for i in idx], G, Q, None if w is None else [w[i] for i in idx])
         for p in parts:
             for k in whole:
-                assert _same(p[k], whole[k]) if k == "quantiles" else np.array_equal(p[k], whole[k])
+                assert same_bits(p[k], whole[k]) if k == "quantiles" else np.array_equal(p[k], whole[k])
     if not weighted:
-        assert _same(whole["quantiles"], _want(rows, group, G)[0])
+        assert same_bits(whole["quantiles"], _want(rows, group, G)[0])
 
 
 @pytest.mark.parametrize("n", [2, 65, 4099])
@@ -128,7 +120,7 @@ def test_weighted_form_equals_numpy_inverted_cdf(n):
             with warnings.catch_warnings():
                 warnings.simplefilter("ignore", RuntimeWarning)
                 want[live] = np.nanquantile(sub[live], Q, axis=1, weights=np.broadcast_to(ws, sub[live].shape), method="inverted_cdf").T
-        assert _same(res["quantiles"][g], want)
+        assert same_bits(res["quantiles"][g], want)
 
 
 def test_group_weight_past_2_53_is_refused_at_the_first_commit():

@@ -6,6 +6,7 @@ import math
 import numpy as np
 import pytest
 
+from tests.helpers import same_values
 from tests.host_indicators import anomaly, baseline, exceedance_counts, indicators
 
 THR = (1.5, 2.0, 3.0)
@@ -50,7 +51,7 @@ def test_indicators_match_the_definitions(anom):
     for i in range(x.shape[1]):
         want = _member([float(a) for a in vals[:, i]], list(times), THR)
         have = [got["mean"][i], got["peak"][i], got["peak_time"][i]] + [c[i] for c in got["crossing"]]
-        assert np.array_equal(np.array(have), np.array(want), equal_nan=True), i
+        assert same_values(np.array(have), np.array(want)), i
     if not anom:
         assert got["peak_time"][5] == times[3] and got["peak_time"][3] == times[0]
         assert all(c[6] == np.inf for c in got["crossing"]) and np.isnan(got["crossing"][0][0])
@@ -61,14 +62,14 @@ def test_baseline_is_the_left_to_right_mean_and_nan_propagates():
     x, _ = _rows()
     b = baseline(x[:10])
     assert np.isnan(b[0]) and b[2] == np.inf and b[3] == -np.inf
-    assert np.array_equal(b, indicators(x[:10], np.arange(10.0))["mean"], equal_nan=True)   # mean over R_ref == baseline
+    assert same_values(b, indicators(x[:10], np.arange(10.0))["mean"])   # mean over R_ref == baseline
     acc = x[0].copy()
     for r in x[1:10]:
         acc = acc + r
-    assert np.array_equal(b, acc / 10, equal_nan=True)
+    assert same_values(b, acc / 10)
     assert np.isnan(baseline(x[15:20])[1]) and not np.isnan(baseline(x[:10])[1])
     a = anomaly(x, b)
-    assert np.array_equal(a, x - b, equal_nan=True)
+    assert same_values(a, x - b)
 
 
 def test_exceedance_counts_and_uneven_shards():

@@ -3,6 +3,7 @@ shards of one member set split 1 to 5 ways -- the algorithm pinned before the GP
 import numpy as np
 import pytest
 
+from tests.helpers import same_values
 from tests.host_select import HostSelect, key_value, order_keys, sharded_quantiles
 
 Q = [0.0, 1.0, 0.5, 1e-12, 0.05, 0.95, 0.17, 0.83]
@@ -61,7 +62,7 @@ def test_sharded_select_equals_nanquantile(split):
     res = sharded_quantiles(shards, Q)
     want = _nanq(rows, Q)
     for r in res:                                                      # every shard ends with the same numbers
-        assert np.array_equal(r["quantiles"], want, equal_nan=True)
+        assert same_values(r["quantiles"], want)
         assert np.array_equal(r["count"], (~np.isnan(rows)).sum(axis=1))
         assert np.array_equal(r["quantiles"].view(np.uint64), res[0]["quantiles"].view(np.uint64))
 

@@ -6,6 +6,7 @@ import warnings
 import numpy as np
 import pytest
 
+from tests.helpers import same_values
 from tests.host_wselect import HostWSelect, sharded_wquantiles, weight_target
 
 Q = [0.0, 1.0, 0.5, 1e-12, 0.05, 0.95, 0.17, 0.83, 1.0 - 1e-12, 1.0 / 3.0]
@@ -91,7 +92,7 @@ def test_unit_and_constant_weights_equal_unweighted_inverted_cdf():
         want = np.nanquantile(rows, Q, axis=1, method="inverted_cdf").T
     for k in (1, 7, 1 << 40):
         got = sharded_wquantiles([rows], [np.full(101, k, dtype=np.int64)], Q)[0]["quantiles"]
-        assert np.array_equal(_unsign(got), _unsign(want), equal_nan=True)
+        assert same_values(_unsign(got), _unsign(want))
 
 
 @pytest.mark.parametrize("split", [2, 3, 5])

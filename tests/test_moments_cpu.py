@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from tests import host_moments as hm
+from tests.helpers import same_values
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -164,7 +165,7 @@ def test_moments_result_finishes_reference_sums_to_the_reference(lib):
     assert got["count"][G - 1] == 0 and np.isnan(got["mean"][G - 1]).all() and np.isnan(got["corr"][G - 1]).all()
     assert (got["cov"][:G - 1, 0, 3] == 2.0 * got["cov"][:G - 1, 0, 0]).all() and (got["cov"][:G - 1, 3, 3] == 4.0 * got["cov"][:G - 1, 0, 0]).all()
     assert (np.abs(got["corr"][:G - 1, 0, 3] - 1.0) <= 2.0 ** -52).all()     # cov / (sd sd): sd^2 is cov to within an ulp, no more
-    assert np.array_equal(got["cov"], got["cov"].transpose(0, 2, 1), equal_nan=True)
+    assert same_values(got["cov"], got["cov"].transpose(0, 2, 1))
 
 
 def test_sd_and_corr_rules():

@@ -11,6 +11,8 @@ import pytest
 
 from oracle import cbind
 
+from tests.helpers import same_values
+
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "udeb_magicc7.json")
 W = np.array([0.5 * 0.58, 0.5 * 0.42, 0.5 * 0.79, 0.5 * 0.21])  # tests/regression/helpers.py:94-103
 
@@ -159,7 +161,7 @@ def test_udeb_ensemble_threads_and_scenarios():
     many, s2 = cbind.udeb_run(b, P, F, scen=scen, threads=5)
     assert not s1.any() and not s2.any()
     for k in cbind.UDEB_VARS:
-        assert np.array_equal(one[k], many[k], equal_nan=True)
+        assert same_values(one[k], many[k])
     # higher ECS -> warmer after 30 years under the same scenario
     ecs = P[cbind.UDEB_PARAM_NAMES.index("ecs")]
     kap = P[cbind.UDEB_PARAM_NAMES.index("kappa")]

@@ -3,23 +3,12 @@ scripts/pair_div_proof.py derives the bound J(s, k) on how close, in units j of 
 boundary for pair_div to miss the IEEE quotient, and tries EVERY divisor against EVERY numerator at 8, 9 and 10 bits of precision.
 Every failure must lie within J; the header's way of listing the candidates must yield every numerator within its bound; and the
 numerators the chunk guard admits must lie inside the windows the header states (scripts/two_layer_box_proof.py, check_pair_window)."""
-import importlib.util
-import os
-
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.helpers import load_script
 
-
-def _load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "scripts", name + ".py"))
-    mod = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(mod)
-    return mod
-
-
-P = _load("pair_div_proof")
-B = _load("two_layer_box_proof")
+P = load_script("pair_div_proof")
+B = load_script("two_layer_box_proof")
 
 
 @pytest.fixture(scope="module", params=[8, 9, 10])

@@ -5,7 +5,6 @@ scripts/pair_div_proof.py, bit for bit, on about 1e4 divisors: both heat-capacit
 significands with one to five trailing zeros, 1 +- ulp and the edges of the divisor box.  tests/golden/pair_div_unsafe.json lists
 divisors of those ranges whose constants as defined fail, each with a failing numerator.  The last test is the cap on what the pair
 lane can give: the share of 64-member blocks of the benchmark's Latin hypercube in which every heat capacity has safe constants."""
-import importlib.util
 import json
 import math
 import os
@@ -22,15 +21,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import host_sampler  # noqa: E402
 
-_spec = importlib.util.spec_from_file_location("pair_div_proof", os.path.join(ROOT, "scripts", "pair_div_proof.py"))
-P = importlib.util.module_from_spec(_spec)
-_spec.loader.exec_module(P)
+from tests.helpers import load_script  # noqa: E402
+
+P = load_script("pair_div_proof")
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "pair_div_unsafe.json")
 # bench.py's headline draw, from bench.py itself: the parameter ranges, the seed and the default size
-_bspec = importlib.util.spec_from_file_location("rscm_bench_for_pair_div", os.path.join(ROOT, "bench.py"))
-_bench = importlib.util.module_from_spec(_bspec)
-_bspec.loader.exec_module(_bench)
+_bench = load_script("bench", folder="")
 BENCH_LOW, BENCH_HIGH, BENCH_SEED = list(_bench.TL_LOW), list(_bench.TL_HIGH), _bench.SEED
 
 

@@ -12,14 +12,11 @@ from rscm_amd import variability as rv
 from tests import host_math as hm
 from tests import host_spectrum as hs
 from tests import host_variability as hv
+from tests.helpers import same_values
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LD = np.longdouble
 DETREND = ("mean", "linear", "difference")
-
-
-def _same(a, b):
-    return np.array_equal(np.asarray(a), np.asarray(b), equal_nan=True)
 
 
 # ---- the coefficient table ------------------------------------------------------------------------------------------------------------
@@ -77,7 +74,7 @@ def test_coefficients_exact_zero_and_refusals(tables):
     for n in (2, 0, -1, hs.MAX_TERMS + 1):
         assert lib.rscm_gpu_spectrum_coefficients(n, _lib.dptr(buf)) == 1
     assert lib.rscm_gpu_spectrum_coefficients(8, None) == 1
-    assert _same(rv.spectrum_coefficients(170), tables[170])
+    assert same_values(rv.spectrum_coefficients(170), tables[170])
     with pytest.raises(_lib.RscmGpuError):
         rv.spectrum_coefficients(2)
 
@@ -98,9 +95,9 @@ def test_series_spectrum_against_the_longdouble_dft(n):
         got = rv.series_spectrum(rows, detrend)
         want = hs.spectrum(rows, detrend, got["edges"])
         for k in hs.FIRST:
-            assert _same(got[k], want[k]), (detrend, k)
+            assert same_values(got[k], want[k]), (detrend, k)
         assert len(got["power"]) == len(want["power"]) == len(got["edges"]) - 1
-        assert all(_same(p, w) for p, w in zip(got["power"], want["power"])), detrend
+        assert all(same_values(p, w) for p, w in zip(got["power"], want["power"])), detrend
         a = np.stack(hs.residuals(rows, detrend)[0])
         I = hs.dft_ordinates_ld(a)
         for b, (e0, e1) in enumerate(zip(got["edges"][:-1], got["edges"][1:])):
@@ -180,7 +177,7 @@ def test_first_three_are_series_variability(detrend):
     s, v = rv.series_spectrum(x, detrend), rv.series_variability(x, detrend)
     w = hv.variability(x, detrend)
     for k in hs.FIRST:
-        assert _same(s[k], v[k]) and _same(s[k], w[k]), k
+        assert same_values(s[k], v[k]) and same_values(s[k], w[k]), k
 
 
 def test_header_abi_minor():

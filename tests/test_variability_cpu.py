@@ -1,6 +1,6 @@
 """CPU tier of the variability statistics: ``rscm_amd.variability.series_variability`` (what a user derives a record's targets
-with) against the numpy restatement of tests/host_variability.py bit for bit; the estimator against the known moments of AR(1)
-noise; the edges of the definition; and the C boundary's text (ABI minor 16)."""
+with) against the numpy restatement of tests/host_variability.py value for value (+0 equal to -0, NaN to NaN); the estimator
+against the known moments of AR(1) noise; the edges of the definition; and the C boundary's text (ABI minor 16)."""
 import os
 import re
 
@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import host_variability as hv
+from tests.helpers import same_values
 from tests.host_forcing_noise_red import red_noise
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -41,11 +42,11 @@ def test_series_variability_equals_the_restatement(detrend, R):
     got, want = sv(rows, detrend), hv.variability(rows, detrend)
     assert set(got) == set(hv.NAMES)
     for k in hv.NAMES:
-        assert got[k].shape == (37,) and np.array_equal(got[k], want[k], equal_nan=True), (k, detrend, R)
+        assert got[k].shape == (37,) and same_values(got[k], want[k]), (k, detrend, R)
     for i in (0, 4, 9, 11):                                       # [R]: floats, the same bits
         one = sv(rows[:, i], detrend)
         for k in hv.NAMES:
-            assert isinstance(one[k], float) and np.array_equal(np.float64(one[k]), want[k][i], equal_nan=True), (k, i)
+            assert isinstance(one[k], float) and same_values(np.float64(one[k]), want[k][i]), (k, i)
 
 
 @pytest.mark.parametrize("phi", [0.0, 0.6, 0.9])
