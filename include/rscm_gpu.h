@@ -117,8 +117,10 @@ extern "C" {
  *      add up: rscm_ens_moment_sums, rscm_gpu_moment_finish, rscm_ens_moments, RSCM_MOMENT_MAX_VECTORS, RSCM_MOMENT_BLOCK
  *  24  the same exact weighted mean and spread of a stored variable at every row, with its covariance with up to four per-member
  *      vectors (the regression of each year on a parameter): rscm_ens_moment_rows_sums, rscm_ens_moment_rows,
- *      RSCM_MOMENT_ROWS_MAX_VECTORS, RSCM_MOMENT_ROWS_MAX_BLOCKS */
-#define RSCM_GPU_ABI_MINOR 24
+ *      RSCM_MOMENT_ROWS_MAX_VECTORS, RSCM_MOMENT_ROWS_MAX_BLOCKS
+ *  25  the device Latin hypercube through Normal, LogNormal and truncated priors: rscm_ens_sample_lhs_priors, RSCM_PRIOR_UNIFORM,
+ *      RSCM_PRIOR_NORMAL, RSCM_PRIOR_LOGNORMAL, RSCM_PRIOR_REFLECT */
+#define RSCM_GPU_ABI_MINOR 25
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -502,6 +504,7 @@ RSCM_API int rscm_ens_create_windowed(int32_t kind, int64_t n_members, int32_t n
  * RSCM_KIND_AGGREGATE, which skips NaN contributors.
  * The coefficients c_k are parameter rows RSCM_TL_P_COEFF0 + k of the handle: rscm_ens_n_params reports 6 + K, and every call that
  * moves parameter rows (rscm_ens_set_params / _aos, rscm_ens_get_params, rscm_ens_params_devptr, rscm_ens_sample_lhs with 6 + K bounds,
+ * rscm_ens_sample_lhs_priors with 6 + K priors,
  * the samplers' param_rows, rscm_ens_gather_members) carries them.  rscm_ens_n_inputs reports K.
  * kind must be RSCM_KIND_TWO_LAYER; flags 0, RSCM_FLAG_NO_SERIES or RSCM_FLAG_NOISE_PARAMS (no windowed storage, and not the two
  * together); n_components in [1, RSCM_TL_MAX_COMPONENTS];
@@ -609,6 +612,7 @@ RSCM_API int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t*
  * or mix with K components) carries member i's sigma_i in parameter row RSCM_TL_P_NOISE_SIGMA(K) = 6 + K and phi_i in row
  * RSCM_TL_P_NOISE_PHI(K) = 6 + K + 1: rscm_ens_n_params reports 6 + K + 2, and every call that moves parameter rows carries the two
  * rows like any other (rscm_ens_set_params / _aos, rscm_ens_get_params, rscm_ens_params_devptr, rscm_ens_sample_lhs with 6 + K + 2 bounds,
+ * rscm_ens_sample_lhs_priors with as many priors,
  * rscm_ens_params_vector, rscm_ens_gather_members -- so the draws of a posterior inherit their ancestors' amplitude and persistence).
  * rscm_ens_gather_members between a handle with the rows and one without is RSCM_ERR_INVALID, like differing component counts.
  * With the per-member noise on, member i has the global id g = member_offset + i and is forced at forcing-axis index t by
@@ -623,7 +627,7 @@ RSCM_API int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t*
  * sigma_i * z, and its forcing differs from the white setting's only in the sign of a zero ((0 * e) + (sigma_i z) where sigma_i z is a
  * zero: -0.0 under the white setting can be +0.0 here).  With all rows uniform and phi != 0 the bits are those of
  * rscm_ens_set_forcing_noise_ar1 with the same numbers.
- * The rows are data (rscm_ens_sample_lhs fills them on the device), so nothing validates them: what the formula gives is what is
+ * The rows are data (rscm_ens_sample_lhs and rscm_ens_sample_lhs_priors fill them on the device), so nothing validates them: what the formula gives is what is
  * defined, the rule for forcing ("NaN and Inf propagate") applied to these two rows.  A NaN or Inf in either row, or |phi_i| > 1 (the
  * square root of a negative number), gives that member NaN forcing: its states are NaN and bit 0 of its status is set.  |phi_i| == 1
  * gives s_i = 0 and a constant (phi_i = 1) or alternating (phi_i = -1) e.  A negative sigma_i mirrors the noise.  None of these touches
@@ -638,7 +642,7 @@ RSCM_API int rscm_ens_forcing_noise_ar1(const rscm_ens* h, double* phi, int32_t*
  * THE CACHE.  Here e_t is a function of (seed, sigma_i, phi_i, g, t) with the rows AS THEY STAND AT LAUNCH, so the cache of the red
  * noise (one value per member and the index it stands at, above) is only valid while the rows are.  In this mode the cached index is
  * dropped by everything that can change a parameter row:
- *     rscm_ens_set_params, rscm_ens_set_params_aos, rscm_ens_sample_lhs, rscm_ens_gather_members into the handle
+ *     rscm_ens_set_params, rscm_ens_set_params_aos, rscm_ens_sample_lhs, rscm_ens_sample_lhs_priors, rscm_ens_gather_members into the handle
  *     (a restored checkpoint sets the parameters, so it is among them),
  * and for good once rscm_ens_params_devptr has been handed out: the caller may then write the rows at any time, so such a handle never
  * trusts the cache across calls -- every run forms e again from index 0, and the index reads -1 after every run.  The chunks and
@@ -1414,7 +1418,7 @@ RSCM_API int rscm_gpu_spectrum_sines(int32_t n, double* out /*[J]*/);
  * Staleness.  The rows are a snapshot of the sources at compute time.  The handle keeps a write epoch that moves with every entry
  * point that can change a stored row, a parameter row or the time index: rscm_ens_run, _run_async, rscm_ens_run_lockstep (every
  * handle of the run), rscm_ens_run_loglik*, a sampler's evaluation runs, rscm_ens_rewind, _clear_series, _clear_rows_after,
- * _set_time_index, _set_state, _set_initial, _set_internal_state, _set_params, _set_params_aos, _sample_lhs, rscm_ens_gather_members
+ * _set_time_index, _set_state, _set_initial, _set_internal_state, _set_params, _set_params_aos, _sample_lhs, _sample_lhs_priors, rscm_ens_gather_members
  * (the destination), rscm_ens_set_forcing_noise*, _clear_forcing_noise, rscm_ens_set_mode.  A reader that finds the rows computed at
  * another epoch gets RSCM_ERR_STATE, "diagnostic N is stale: compute it again".  Definitions survive all of these; only the rows go
  * stale.  rscm_ens_params_devptr and rscm_ens_series_devptr do NOT move the epoch: writes through pointers the library handed out
@@ -1527,6 +1531,44 @@ RSCM_API int rscm_ens_get_params(rscm_ens* h, double* out_soa);
  * ensemble generate their rows with no communication. */
 RSCM_API int rscm_ens_sample_lhs(rscm_ens* h, uint64_t seed, const double* low, const double* high,
                         int64_t member_offset, int64_t n_total);
+
+/* The same hypercube through each row's own inverse CDF: a prior ensemble of Uniform, Normal and LogNormal rows, each optionally
+ * truncated, drawn where it runs.  The seven arrays hold one entry per parameter row.  For member i (global id g = member_offset + i)
+ * and row j, u is EXACTLY what rscm_ens_sample_lhs forms -- the same keys, the same Feistel stratum, u = stratum * interval +
+ * U_j(g) * interval with interval = 1 / n_total -- so the strata of a row are those of rscm_ens_sample_lhs with the same seed.  Then
+ *   RSCM_PRIOR_UNIFORM    x = a + u * (b - a): the bits of rscm_ens_sample_lhs with low = a, high = b; a == b fixes the row.  p0, p1,
+ *                         lo, hi are not read.
+ *   RSCM_PRIOR_NORMAL     t = p0 + u * (p1 - p0), moved into [2^-1022, 1 - 2^-53] (t below the first becomes it, t above the second
+ *   RSCM_PRIOR_LOGNORMAL  becomes it: u = 0 and a sum that rounds to 1 stay away from -inf / +inf; Q gives -37.52 and 8.21 there);
+ *                         z = Q(t), negated when kind carries RSCM_PRIOR_REFLECT; y = a + b * z; x = y (NORMAL: mean a, standard
+ *                         deviation b) or x = exp(y), the device library's exp (LOGNORMAL: ln x has mean a, standard deviation b);
+ *                         last x below lo becomes lo and x above hi becomes hi (the inverse of a rounded p0 may land an ulp outside
+ *                         the support, and a log-prior must never see such a draw).  Without truncation p0 = 0, p1 = 1, lo = -inf,
+ *                         hi = +inf.
+ * Q is the standard normal quantile, Wichura's AS241 PPND16 on the double t: q = t - 1/2; for |q| <= 0.425 the central rational
+ * q A(r) / B(r), r = 0.180625 - q q; otherwise p = min(t, 1 - t) (t if q < 0, else 1 - t), r = sqrt(-ln p) with ln written out in
+ * + - * / (the logarithm of the forcing noise), the near-tail pair C, D at r - 1.6 for r <= 5 and the far-tail pair E, F at r - 5
+ * beyond, the quotient negated for q < 0; one division.  Every operation is an f64 + - * / or sqrt rounded on its own, nothing is
+ * fused, so a host restatement gives the same bits (tests/host_lhs_priors.py); on t = (2k + 1) 2^-53 it is the forcing noise's deviate
+ * of the integer k (rscm_ens_set_forcing_noise).  The exponential of a LOGNORMAL row is the library's: within 2 ulp, not pinned.
+ * p0 < p1 are the prior's CDF at the truncation bounds and the caller supplies them: Phi((lo - a) / b) and Phi((hi - a) / b) (ln lo,
+ * ln hi for LOGNORMAL).  When the support lies above the centre (lo >= a, or ln lo >= a) the caller passes the SURVIVAL probabilities
+ * p0 = Phi(-beta), p1 = Phi(-alpha) with alpha = (lo - a) / b, beta = (hi - a) / b, and the flag: the doubles are dense near 0 and not
+ * near 1, so this keeps the resolution of a far upper tail (a standard normal truncated to [6, 8]: unreflected, 1e5 strata give 99 998
+ * distinct values; reflected, all 1e5).  A reflected column DECREASES with its stratum; it holds one draw per stratum of the truncated
+ * prior all the same, a Latin hypercube.
+ * RSCM_ERR_INVALID: a NULL array; a member block outside the global ensemble; a kind that is none of the three, with or without the
+ * flag; the flag on RSCM_PRIOR_UNIFORM; for NORMAL and LOGNORMAL b <= 0 or not finite, not 0 <= p0 < p1 <= 1, not lo <= hi; a row
+ * marked [u] of the handle's kind that is not RSCM_PRIOR_UNIFORM with a == b; N2O's stratospheric delay that is not RSCM_PRIOR_UNIFORM
+ * (its b sizes the look-back, as `high` does).  Afterwards the handle stands as rscm_ens_sample_lhs leaves it: parameters set, every
+ * cache of the parameter block dropped (the per-member noise cache among them), the diagnostics' epoch moved. */
+#define RSCM_PRIOR_UNIFORM 0
+#define RSCM_PRIOR_NORMAL 1
+#define RSCM_PRIOR_LOGNORMAL 2
+#define RSCM_PRIOR_REFLECT 0x100 /* or-ed into NORMAL / LOGNORMAL: p0, p1 are survival probabilities, z = -Q(t) */
+RSCM_API int rscm_ens_sample_lhs_priors(rscm_ens* h, uint64_t seed, const int32_t* kind, const double* a, const double* b,
+                                        const double* p0, const double* p1, const double* lo, const double* hi,
+                                        int64_t member_offset, int64_t n_total);
 
 /* ---- pinned host buffers -------------------------------------------------------------------- */
 /* Page-locked host memory for the buffers handed to rscm_ens_get_series / rscm_ens_set_params:

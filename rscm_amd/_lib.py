@@ -32,6 +32,7 @@ FLAG_NOISE_PARAMS = 4    # RSCM_FLAG_NOISE_PARAMS: two more two-layer parameter 
 TL_P_COEFF0 = 6          # a mix ensemble's coefficient rows start here (RSCM_TL_P_COEFF0)
 TL_MAX_COMPONENTS = 8    # RSCM_TL_MAX_COMPONENTS
 NOISE_STREAM_TAG = 0x4E5A   # RSCM_NOISE_STREAM_TAG: the Philox stream of the forcing noise
+PRIOR_UNIFORM, PRIOR_NORMAL, PRIOR_LOGNORMAL, PRIOR_REFLECT = 0, 1, 2, 0x100   # RSCM_PRIOR_*: rscm_ens_sample_lhs_priors
 SELECT_WEIGHTED = 1   # rscm_ens_quantile_rows_ex / _select_begin_ex / vector selects
 SELECT_ANOMALY = 2
 SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
@@ -429,6 +430,7 @@ SIGNATURES = {
     "rscm_ens_summary": (C.c_int, [_h, C.c_int32, C.c_int32, _dp]),
     "rscm_ens_get_params": (C.c_int, [_h, _dp]),
     "rscm_ens_sample_lhs": (C.c_int, [_h, C.c_uint64, _dp, _dp, C.c_int64, C.c_int64]),
+    "rscm_ens_sample_lhs_priors": (C.c_int, [_h, C.c_uint64, _ip, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int64, C.c_int64]),
     "rscm_gpu_host_alloc": (C.c_int, [C.c_int64, C.POINTER(C.c_void_p)]),
     "rscm_gpu_host_free": (C.c_int, [C.c_void_p]),
     "rscm_gpu_copy_to_host": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64]),

@@ -171,6 +171,66 @@ class Bound:
         return np.where((x < self._low) | (x > self._high), -np.inf, self.distribution.ln_pdf_n(x))
 
 
+def _std_normal_cdf(x: float) -> float:
+    return 0.5 * math.erfc(-x / math.sqrt(2.0))
+
+
+def prior_table(priors, n_params: int, base=None):
+    """The seven arrays of ``rscm_ens_sample_lhs_priors`` (include/rscm_gpu.h), each ``[n_params]``: ``(kind, a, b, p0, p1, lo, hi)``.
+    ``priors`` maps a parameter row to its distribution -- ``Uniform``, ``Normal``, ``LogNormal`` or a ``Bound`` of one of them; a row
+    it does not name stays fixed at ``base[row]`` (a uniform row with ``a == b``).  ``Bound(Uniform)`` intersects the two intervals.
+    A truncated Normal or LogNormal gets the prior's CDF at its bounds, Phi(x) = erfc(-x / sqrt 2) / 2 in the z-scale
+    ``alpha = (low - mean) / sd``, ``beta = (high - mean) / sd`` (the logarithms of the bounds for a LogNormal): ``p0 = Phi(alpha)``,
+    ``p1 = Phi(beta)``, or, when the support lies above the centre (``low >= mean``), the survival probabilities
+    ``p0 = Phi(-beta)``, ``p1 = Phi(-alpha)`` with ``PRIOR_REFLECT``, which keep the resolution of a far upper tail."""
+    n_params = int(n_params)
+    kind = np.zeros(n_params, dtype=np.int32)
+    p0, p1 = np.zeros(n_params), np.ones(n_params)
+    lo, hi = np.full(n_params, -math.inf), np.full(n_params, math.inf)
+    if base is None:
+        missing = sorted(set(range(n_params)) - {int(r) for r in priors})
+        if missing:
+            raise ValueError(f"prior_table: rows {missing} have no prior and there is no base value to fix them at")
+        a = np.zeros(n_params)
+    else:
+        a = np.array(base, dtype=np.float64)
+        if a.shape != (n_params,):
+            raise ValueError(f"prior_table: base needs one entry per parameter ({n_params}), got shape {a.shape}")
+    b = a.copy()
+    for row, d in priors.items():
+        j = int(row)
+        if j != row or not 0 <= j < n_params:
+            raise ValueError(f"prior_table: row {row!r} is not a parameter row of 0 .. {n_params - 1}")
+        low, high = -math.inf, math.inf
+        if isinstance(d, Bound):
+            low, high, d = d.low, d.high, d.inner()
+        if isinstance(d, Uniform):
+            a[j], b[j] = max(d.low, low), min(d.high, high)
+            if a[j] > b[j]:
+                raise ValueError(f"prior_table: row {j}: the bounds [{low}, {high}] do not meet Uniform({d.low}, {d.high})")
+            continue
+        if isinstance(d, Normal):
+            kind[j], a[j], b[j] = L.PRIOR_NORMAL, d.mean, d.std_dev
+            z_low, z_high = low, high
+        elif isinstance(d, LogNormal):
+            kind[j], a[j], b[j] = L.PRIOR_LOGNORMAL, d.mu, d.sigma
+            if high <= 0.0:
+                raise ValueError(f"prior_table: row {j}: the bounds [{low}, {high}] hold nothing of a LogNormal")
+            z_low, z_high = (math.log(low) if low > 0.0 else -math.inf), math.log(high)
+        else:
+            raise NotImplementedError(f"prior {type(d).__name__} has no device form")
+        alpha, beta = (z_low - a[j]) / b[j], (z_high - a[j]) / b[j]
+        if z_low >= a[j]:
+            kind[j] |= L.PRIOR_REFLECT
+            p0[j], p1[j] = _std_normal_cdf(-beta), _std_normal_cdf(-alpha)
+        else:
+            p0[j], p1[j] = _std_normal_cdf(alpha), _std_normal_cdf(beta)
+        if not p0[j] < p1[j]:
+            raise ValueError(f"prior_table: row {j}: the prior has no probability between {low} and {high} that a double resolves")
+        lo[j], hi[j] = low, high
+    return kind, a, b, p0, p1, lo, hi
+
+
 class ParameterSet:
     """parameter_set.rs: ordered named priors; ``sample_lhs`` per :207-233."""
 
@@ -200,6 +260,18 @@ class ParameterSet:
             lo.append(b[0] if b else -math.inf)
             hi.append(b[1] if b else math.inf)
         return lo, hi
+
+    def rows(self, names_to_rows) -> Dict[int, object]:
+        """``{row: distribution}`` for ``Ensemble.sample_lhs_priors``.  ``names_to_rows``: the parameter names of an ensemble in row
+        order (``Model.param_order``, through which a ``ModelRunner`` resolves its parameter names too -- ``"forcing_scale|<name>"``,
+        ``"forcing_noise|sigma"`` and ``"forcing_noise|phi"`` among them), or a mapping from name to row.  Every name of the set must
+        be among them."""
+        if not hasattr(names_to_rows, "keys"):
+            names_to_rows = {name: j for j, name in enumerate(names_to_rows)}
+        unknown = [n for n in self._names if n not in names_to_rows]
+        if unknown:
+            raise KeyError(f"ParameterSet.rows: {unknown} name no parameter row (rows: {list(names_to_rows)})")
+        return {int(names_to_rows[n]): d for n, d in zip(self._names, self._dists)}
 
     def sample_random(self, n: int, rng: Optional[np.random.Generator] = None) -> np.ndarray:
         rng = rng or np.random.default_rng()

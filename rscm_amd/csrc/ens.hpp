@@ -165,7 +165,7 @@ struct rscm_ens : EnsQueues {
     // The rules that drop what the handle has cached about its parameter block and about where it stands.  Nothing outside them assigns
     // uniform_rows, derived_dirty or time_index but ensure_derived and step_finish (launch_host.cpp) and a fused launch's provisional index.
     // The parameter block was written from the host and these rows hold one value for every member -- none once the block has been
-    // handed out: rscm_ens_set_params[_aos] (a restore goes through it), rscm_ens_sample_lhs, rscm_ens_gather_members into the handle
+    // handed out: rscm_ens_set_params[_aos] (a restore goes through it), rscm_ens_sample_lhs[_priors], rscm_ens_gather_members into the handle
     void params_written(uint64_t uniform) { uniform_rows = params_exposed ? 0 : uniform; params_may_change(); rows_written(); }
     // A kernel is about to write these rows (~0: any), the samplers' proposals; the diagnostics' epoch moves with the run that follows
     void params_kernel_writes(uint64_t rows) { uniform_rows &= ~rows; if (rows) derived_dirty = true; }

@@ -8,6 +8,7 @@
 #include <algorithm>
 
 #include "chem_body.hpp"
+#include "forcing_noise.hpp"
 #include "philox.hpp"
 #include "rk4_device.hpp"
 #include "rscm_device.hpp"
@@ -293,6 +294,50 @@ __global__ __launch_bounds__(kBlock) void lhs_kernel(double* params, int32_t n_p
     }
 }
 
+// The same hypercube through each row's own inverse CDF (include/rscm_gpu.h, rscm_ens_sample_lhs_priors): u is formed as lhs_kernel
+// forms it, a uniform row is lhs_kernel's expression on (a, b), a Normal or LogNormal row goes through noise::normal_from_p.  The row's
+// seven values come from rows[j] by scalar loads and its kind is the same for every lane, so the branch is a scalar one and a uniform
+// row never runs the quantile.  The branch alone does not make a uniform row free: the quantile's sixty coefficients are hoisted out
+// of the row loop into registers (152 VGPRs against lhs_kernel's 24, three waves per SIMD instead of eight), so a call without a
+// Normal or LogNormal row is launched as the instance QUANTILE = false, which holds lhs_kernel's loop and nothing else.
+// tests/host_lhs_priors.py restates it.
+template <bool QUANTILE>
+__global__ __launch_bounds__(kBlock) void lhs_priors_kernel(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
+                                                            const LhsPriorRow* rows, int64_t member_offset, int64_t n_total,
+                                                            uint32_t half_bits)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n_local) return;
+    const uint64_t g = (uint64_t)(member_offset + i);
+    const double interval_size = 1.0 / (double)n_total;
+    for (int32_t j = 0; j < n_params; ++j) {
+        const uint32_t k0 = (uint32_t)seed ^ (0x9E3779B9u * (uint32_t)(j + 1));
+        const uint32_t k1 = (uint32_t)(seed >> 32) + (uint32_t)j;
+        const uint64_t stratum = feistel_perm(g, (uint64_t)n_total, half_bits, k0, k1);
+        uint32_t c[4] = {(uint32_t)g, (uint32_t)(g >> 32), 0xA5A5u, (uint32_t)j};
+        philox4x32_10(c, k0, ~k1);
+        const double u01 = u01_from_bits(c[0], c[1]);
+        const double u = (double)stratum * interval_size + u01 * interval_size;
+        const LhsPriorRow r = rows[j];
+        const int32_t family = r.kind & ~kPriorReflect;
+        double x;
+        if (!QUANTILE || family == kPriorUniform) {
+            x = r.a + u * (r.b - r.a);
+        } else {
+            double t = r.p0 + u * (r.p1 - r.p0);
+            t = t < 0x1p-1022 ? 0x1p-1022 : t;
+            t = t > 1.0 - 0x1p-53 ? 1.0 - 0x1p-53 : t;
+            double z = noise::normal_from_p(t);
+            if (r.kind & kPriorReflect) z = -z;
+            x = r.a + r.b * z;
+            if (family == kPriorLogNormal) x = exp(x);
+            x = x < r.lo ? r.lo : x;
+            x = x > r.hi ? r.hi : x;
+        }
+        params[(size_t)j * n_local + i] = x;
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void divtest_kernel(const double* num, const double* den,
                                                          double* out_ref, double* out_fast,
                                                          uint8_t* used_fast, int64_t n)
@@ -450,6 +495,21 @@ hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_
     hipLaunchKernelGGL(lhs_kernel, dim3((unsigned)((n_local + kBlock - 1) / kBlock)), dim3(kBlock),
                        0, s, params, n_params, n_local, seed, low, high, member_offset, n_total,
                        bits / 2);
+    return hipGetLastError();
+}
+
+hipError_t launch_lhs_priors(double* params, int32_t n_params, int64_t n_local, uint64_t seed, const LhsPriorRow* rows, bool any_quantile,
+                             int64_t member_offset, int64_t n_total, hipStream_t s)
+{
+    if (n_local <= 0) return hipSuccess;
+    uint32_t bits = 2;   // as launch_lhs
+    while ((1ull << bits) < (uint64_t)n_total) ++bits;
+    if (bits & 1u) ++bits;
+    const dim3 grid((unsigned)((n_local + kBlock - 1) / kBlock)), block(kBlock);
+    if (any_quantile)
+        hipLaunchKernelGGL(lhs_priors_kernel<true>, grid, block, 0, s, params, n_params, n_local, seed, rows, member_offset, n_total, bits / 2);
+    else
+        hipLaunchKernelGGL(lhs_priors_kernel<false>, grid, block, 0, s, params, n_params, n_local, seed, rows, member_offset, n_total, bits / 2);
     return hipGetLastError();
 }
 

@@ -60,12 +60,13 @@ __device__ __forceinline__ double poly7(double r, double c7, double c6, double c
     return p * r + c0;
 }
 
-// The deviate of a 52-bit integer k.  The central branch (|q| <= 0.425, 85 % of draws) and the near tail (r <= 5) are both computed
-// and selected: with 15 % of lanes in the tail nearly every wavefront would run both anyway.  The far tail (p < e^-25, one draw in
-// 4e10) is a real branch.
-__device__ __forceinline__ double normal_from_k(uint64_t k)
+// Q(u): the standard normal quantile of a probability u in [2^-1022, 1 - 2^-53] (include/rscm_gpu.h, rscm_ens_sample_lhs_priors; the
+// callers keep u inside: ln_small wants a normal f64).  q = u - 1/2 is one rounded subtraction (exact for u >= 1/4), 1 - u is exact
+// for u >= 1/2.  The central branch (|q| <= 0.425, 85 % of uniform draws) and the near tail (r <= 5) are both computed and selected:
+// with 15 % of lanes in the tail nearly every wavefront would run both anyway.  The far tail (p < e^-25, one uniform draw in 4e10; every
+// lane of a prior truncated out there) is a real branch.
+__device__ __forceinline__ double normal_from_p(double u)
 {
-    const double u = (double)(2 * k + 1) * (1.0 / 9007199254740992.0);
     const double q = u - 0.5;
     const double aq = __builtin_fabs(q);
     // central: r = 0.180625 - q^2, z = q A(r) / B(r)
@@ -96,6 +97,12 @@ __device__ __forceinline__ double normal_from_k(uint64_t k)
     const double num = central ? num_c : (q < 0.0 ? -num_t : num_t);
     const double den = central ? den_c : den_t;
     return num / den;
+}
+
+// The deviate of a 52-bit integer k: Q at u = (2k + 1) 2^-53, where q and 1 - u are exact
+__device__ __forceinline__ double normal_from_k(uint64_t k)
+{
+    return normal_from_p((double)(2 * k + 1) * (1.0 / 9007199254740992.0));
 }
 
 // The Philox block of (seed, g, t >> 1): words (0,1) serve even t, words (2,3) odd t

@@ -1013,6 +1013,14 @@ hipError_t launch_loglik_spectrum(const LoglikSpectrum& v, int32_t n_vec, const 
 hipError_t launch_lhs(double* params, int32_t n_params, int64_t n_local, uint64_t seed,
                       const double* low, const double* high, int64_t member_offset,
                       int64_t n_total, hipStream_t s);
+// The hypercube of launch_lhs through each row's inverse CDF (rscm_ens_sample_lhs_priors in include/rscm_gpu.h states it): rows[n_params]
+// on the device, one entry per parameter row with the seven values of the entry point's seven arrays; the caller has checked them.
+// any_quantile: whether a row is not kPriorUniform (false selects the kernel instance without the quantile's registers).
+// kind: RSCM_PRIOR_UNIFORM / _NORMAL / _LOGNORMAL, the last two with or without RSCM_PRIOR_REFLECT (rscm_gpu.cpp static_asserts the four)
+constexpr int32_t kPriorUniform = 0, kPriorNormal = 1, kPriorLogNormal = 2, kPriorReflect = 0x100;
+struct LhsPriorRow { double a, b, p0, p1, lo, hi; int32_t kind, pad; };
+hipError_t launch_lhs_priors(double* params, int32_t n_params, int64_t n_local, uint64_t seed, const LhsPriorRow* rows, bool any_quantile,
+                             int64_t member_offset, int64_t n_total, hipStream_t s);
 // out[i] = a[i] / b[i] through (1) the compiler's IEEE division and (2) the hoisted-reciprocal
 // path used by the kernels, for the parity test of the latter.
 hipError_t launch_divtest(const double* num, const double* den, double* out_ref,

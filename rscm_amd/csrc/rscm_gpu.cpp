@@ -35,6 +35,8 @@ static_assert(rscm::kNoiseStreamTag == RSCM_NOISE_STREAM_TAG, "the noise stream'
 static_assert(RSCM_NOISE_STREAM_TAG != 0x57A7u && RSCM_NOISE_STREAM_TAG != 0xACCEu && RSCM_NOISE_STREAM_TAG != 0x5EEDu &&
                   RSCM_NOISE_STREAM_TAG != 0xA5A5u && RSCM_NOISE_STREAM_TAG != RSCM_RESAMPLE_STREAM_TAG,
               "every Philox stream of the library has a tag of its own");
+static_assert(rscm::kPriorUniform == RSCM_PRIOR_UNIFORM && rscm::kPriorNormal == RSCM_PRIOR_NORMAL && rscm::kPriorLogNormal == RSCM_PRIOR_LOGNORMAL &&
+                  rscm::kPriorReflect == RSCM_PRIOR_REFLECT, "the prior kinds in rscm_device.hpp and rscm_gpu.h must agree");
 static_assert(rscm::kMaxForcingComponents == RSCM_TL_MAX_COMPONENTS && rscm::kTwoLayerCoeff0 == RSCM_TL_P_COEFF0 && RSCM_TL_P_COEFF0 == RSCM_TL_NPARAMS,
               "the mix handle's constants in rscm_device.hpp and rscm_gpu.h must agree");
 static_assert(rscm::kKindOzoneForcing == RSCM_KIND_OZONE_FORCING && rscm::kKindAerosolDirect == RSCM_KIND_AEROSOL_DIRECT &&
@@ -754,6 +756,52 @@ int rscm_ens_sample_lhs(rscm_ens* h, uint64_t seed, const double* low, const dou
     HIPCHK(rscm::launch_lhs(h->d_params, h->P, h->N, seed, d_lh.get(), d_lh.get() + h->P, member_offset, n_total, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
     h->params_written(0);   // conservatively: low + u (high - low) need not reproduce low's bits for every u
+    h->params_set = true;
+    return RSCM_OK;
+    GUARD_END
+}
+
+int rscm_ens_sample_lhs_priors(rscm_ens* h, uint64_t seed, const int32_t* kind, const double* a, const double* b, const double* p0,
+                               const double* p1, const double* lo, const double* hi, int64_t member_offset, int64_t n_total)
+{
+    GUARD_BEGIN
+    NEED(h);
+    if (!kind || !a || !b || !p0 || !p1 || !lo || !hi) return fail(RSCM_ERR_INVALID, "a prior array is NULL");
+    if (member_offset < 0 || n_total < 1 || member_offset + h->N > n_total)
+        return fail(RSCM_ERR_INVALID, "member block [%lld, %lld) outside the global ensemble of %lld",
+                    (long long)member_offset, (long long)(member_offset + h->N), (long long)n_total);
+    std::vector<rscm::LhsPriorRow> rows((size_t)h->P);
+    bool any_quantile = false;
+    for (int32_t j = 0; j < h->P; ++j) {
+        const int32_t family = kind[j] & ~RSCM_PRIOR_REFLECT;
+        if (family != RSCM_PRIOR_UNIFORM && family != RSCM_PRIOR_NORMAL && family != RSCM_PRIOR_LOGNORMAL)
+            return fail(RSCM_ERR_INVALID, "parameter row %d: unknown prior kind %d", j, kind[j]);
+        if (family == RSCM_PRIOR_UNIFORM) {
+            if (kind[j] != RSCM_PRIOR_UNIFORM) return fail(RSCM_ERR_INVALID, "parameter row %d: RSCM_PRIOR_REFLECT on a uniform row", j);
+        } else {
+            if (!(b[j] > 0.0) || !std::isfinite(b[j])) return fail(RSCM_ERR_INVALID, "parameter row %d: the scale b must be positive and finite", j);
+            if (!(0.0 <= p0[j] && p0[j] < p1[j] && p1[j] <= 1.0)) return fail(RSCM_ERR_INVALID, "parameter row %d: needs 0 <= p0 < p1 <= 1", j);
+            if (!(lo[j] <= hi[j])) return fail(RSCM_ERR_INVALID, "parameter row %d: needs lo <= hi", j);
+        }
+        rows[(size_t)j] = {a[j], b[j], p0[j], p1[j], lo[j], hi[j], kind[j], 0};
+        any_quantile |= family != RSCM_PRIOR_UNIFORM;
+    }
+    if (int rc = set_device(h)) return rc;
+    for (const rscm::StructuralRow& s : rscm::kStructuralRows) {   // (N2O's delay is not `uniform`: the look-back is sized for the largest)
+        if (s.kind != h->kind) continue;
+        if (kind[s.row] != RSCM_PRIOR_UNIFORM)
+            return fail(RSCM_ERR_INVALID, "parameter row %d (%s) is structural: its prior must be RSCM_PRIOR_UNIFORM", s.row, s.name);
+        if (s.uniform && a[s.row] != b[s.row])
+            return fail(RSCM_ERR_INVALID, "parameter row %d (%s) is structural: a must equal b", s.row, s.name);
+    }
+    if (int rc = configure_kind(h, {a, 1, 0, 1})) return rc;   // (a == b in every structural row)
+    if (h->kind == RSCM_KIND_N2O_CHEMISTRY) h->lookback = n2o_lookback(b[rscm::kN2oDelayRow]);   // no member draws a larger delay
+    rscm::DevBuf<rscm::LhsPriorRow> d_rows;
+    HIPCHK(d_rows.alloc(rows.size()));
+    HIPCHK(hipMemcpyAsync(d_rows.get(), rows.data(), rows.size() * sizeof(rscm::LhsPriorRow), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(rscm::launch_lhs_priors(h->d_params, h->P, h->N, seed, d_rows.get(), any_quantile, member_offset, n_total, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    h->params_written(0);   // as rscm_ens_sample_lhs
     h->params_set = true;
     return RSCM_OK;
     GUARD_END

@@ -346,6 +346,10 @@ class ShardedEnsemble:
     def sample_lhs(self, seed: int, low, high) -> None:
         self.ensemble.sample_lhs(seed, low, high, self.offset, self.n_total)
 
+    def sample_lhs_priors(self, seed: int, priors, base=None) -> None:
+        """This shard's block of the global hypercube through the rows' priors (``Ensemble.sample_lhs_priors``)."""
+        self.ensemble.sample_lhs_priors(seed, priors, base, self.offset, self.n_total)
+
     def set_forcing_noise(self, sigma: float, seed: int, phi: float = 0.0) -> None:
         """Forcing noise of the global ensemble (``Ensemble.set_forcing_noise``, red with ``phi != 0``): the shard's first member
         is the offset, so a member draws the same variability whichever rank holds it."""

@@ -321,6 +321,17 @@ class Ensemble:
         L.check(self._lib.rscm_ens_sample_lhs(self._h, C.c_uint64(seed), L.dptr(lo), L.dptr(hi),
                                               member_offset, n_total))
 
+    def sample_lhs_priors(self, seed: int, priors, base=None, member_offset: int = 0, n_total: Optional[int] = None) -> None:
+        """The Latin hypercube of ``sample_lhs`` -- the same strata for the same seed -- through each row's own inverse CDF on the
+        device (``rscm_ens_sample_lhs_priors``).  ``priors``: ``{row: distribution}`` of ``calibrate.Uniform`` / ``Normal`` /
+        ``LogNormal`` or a ``Bound`` of one (``ParameterSet.rows`` makes it from a named set); the rows it leaves out stay fixed at
+        ``base[row]``.  A block of a larger ensemble takes ``member_offset`` and ``n_total`` as ``sample_lhs`` does."""
+        from .calibrate import prior_table
+        kind, a, b, p0, p1, lo, hi = prior_table(priors, self.n_params, base)
+        n_total = self.n_members if n_total is None else n_total
+        L.check(self._lib.rscm_ens_sample_lhs_priors(self._h, C.c_uint64(seed), L.iptr(kind), L.dptr(a), L.dptr(b), L.dptr(p0),
+                                                     L.dptr(p1), L.dptr(lo), L.dptr(hi), member_offset, n_total))
+
     def get_params(self) -> np.ndarray:
         out = np.empty((self.n_params, self.n_members))
         L.check(self._lib.rscm_ens_get_params(self._h, L.dptr(out)))
