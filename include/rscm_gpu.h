@@ -119,8 +119,10 @@ extern "C" {
  *      vectors (the regression of each year on a parameter): rscm_ens_moment_rows_sums, rscm_ens_moment_rows,
  *      RSCM_MOMENT_ROWS_MAX_VECTORS, RSCM_MOMENT_ROWS_MAX_BLOCKS
  *  25  the device Latin hypercube through Normal, LogNormal and truncated priors: rscm_ens_sample_lhs_priors, RSCM_PRIOR_UNIFORM,
- *      RSCM_PRIOR_NORMAL, RSCM_PRIOR_LOGNORMAL, RSCM_PRIOR_REFLECT */
-#define RSCM_GPU_ABI_MINOR 25
+ *      RSCM_PRIOR_NORMAL, RSCM_PRIOR_LOGNORMAL, RSCM_PRIOR_REFLECT
+ *  26  the exceedance of up to eight thresholds, fixed or per row, and the rank of a record inside the plume, for every row of a
+ *      stored variable in one launch: rscm_ens_exceedance_rows, RSCM_EXCEEDANCE_ROWS_MAX_THRESHOLDS */
+#define RSCM_GPU_ABI_MINOR 26
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1194,6 +1196,39 @@ RSCM_API int rscm_ens_moment_rows_sums(rscm_ens* h, int32_t var_id, int32_t t_be
  * Errors as rscm_ens_moment_rows_sums. */
 RSCM_API int rscm_ens_moment_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_vec,
                                   const double* const* vec_dev, int32_t flags, double* mean, double* second, int64_t* n, int64_t* weight);
+
+/* ---- exceedance and observation rank of a stored variable at every row (ABI minor 26) --------------- */
+/* rscm_ens_exceedance for the rows of a stored variable instead of one vector, with thresholds that may differ per row: the
+ * exceedance probability as a series, and, with a record as the per-row threshold, the rank of the record inside the plume.  This
+ * is the one definition; the kernel (exceedance_rows.hip), rscm_amd's finishers and the tests' restatement in numpy and Python
+ * integers (tests/host_exceedance_rows.py) apply it.
+ *   Rows: those of rscm_ens_moment_rows_sums, t_begin, t_begin + t_stride, ... < t_end of var_id, read where they are resident (full
+ *   storage, the window, the output store); a diagnostic by its id, RSCM_ERR_STATE when it is stale.  A computed row that is not
+ *   resident is RSCM_ERR_STATE, as is a call while a staged select is in flight on the handle.
+ *   Thresholds: K = n_thr per row, 1 <= K <= RSCM_EXCEEDANCE_ROWS_MAX_THRESHOLDS, host doubles: thr[K], the same for every row
+ *   (thr_per_row == 0), or thr[rows][K] (thr_per_row != 0).
+ *   The value of member i in row t: x = series[t][i], or with RSCM_SELECT_ANOMALY x = series[t][i] - b[i], one rounded subtraction,
+ *   the bits rscm_ens_quantile_rows_ex and rscm_ens_moment_rows_sums see under that flag; without a baseline RSCM_ERR_STATE.
+ *   Which members take part, per row: member i takes part in row t when x is not NaN; infinities take part, as in
+ *   rscm_ens_exceedance.  Its weight is 1, or the member weight w[i] with RSCM_SELECT_WEIGHTED (without weights RSCM_ERR_STATE).
+ *   With RSCM_SELECT_GROUPED it counts in group g[i], and a member of no group (-1) is left out (without groups RSCM_ERR_STATE);
+ *   G = n_groups when grouped, else 1.
+ *   Per row and group, as int64:
+ *     total   = the summed weight of the members that take part;
+ *     hits[k] = the summed weight of those with x >= thr[k];
+ *     equal[k] = the summed weight of those with x == thr[k] (IEEE comparison: -0 equals +0).
+ *   A NaN threshold gives hits[k] = equal[k] = 0 for that row and k and leaves total alone: how a record marks a row without an
+ *   observation.  Thresholds of +-Inf compare as IEEE compares them.  A row beyond the current time index has zeros everywhere.
+ *   The sums are integers: exact, independent of the order of summation, and those of shards add up to the whole ensemble's.  The
+ *   limit on the summed weight is that of rscm_ens_exceedance: a handle's member weights sum to at most 2^53
+ *   (rscm_ens_set_member_weights), so nothing wraps over fewer than 2^10 handles.
+ *   Result: hits[rows][G][K], equal[rows][G][K] (may be NULL: not formed), total[rows][G], host memory.
+ *   RSCM_ERR_INVALID: unknown flags, K out of range, a NULL thr, hits or total, a bad row range or stride, a variable without a
+ *   stored series. */
+#define RSCM_EXCEEDANCE_ROWS_MAX_THRESHOLDS 8
+RSCM_API int rscm_ens_exceedance_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_thr,
+                                      const double* thr, int32_t thr_per_row, int32_t flags, int64_t* hits, int64_t* equal,
+                                      int64_t* total);
 
 /* ---- per-member variability statistics and a likelihood over per-member vectors (ABI minor 16) ---- */
 /* How variable is each member's series of var_id over a period: its mean, its trend, the variance and standard deviation about the

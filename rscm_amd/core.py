@@ -1343,6 +1343,22 @@ class GraphModel:
         kw = {"grouped": True} if grouped else {}
         return ens.moment_rows(vid, t_begin, t_end, t_stride, vs, weighted=weighted, anomaly=anomaly, **kw)
 
+    def exceedance_rows(self, name: str, thresholds, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                        anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """``Ensemble.exceedance_rows`` (the exceedance of ``[K]`` or ``[rows][K]`` thresholds at every row of ``name``) on the
+        variable's home ensemble."""
+        ens, vid = self.variable_home(name)
+        kw = {"grouped": True} if grouped else {}
+        return ens.exceedance_rows(vid, thresholds, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, **kw)
+
+    def rank_rows(self, name: str, record, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                  anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """``Ensemble.rank_rows`` (where the record ``[rows]`` lies inside the plume of ``name`` at every row) on the variable's
+        home ensemble."""
+        ens, vid = self.variable_home(name)
+        kw = {"grouped": True} if grouped else {}
+        return ens.rank_rows(vid, record, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, **kw)
+
     def exceedance(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """``Ensemble.exceedance`` on the ensemble that owns the vector."""
         kw = {"grouped": True} if grouped else {}

@@ -961,6 +961,27 @@ struct MomentRowsArgs {
 };
 constexpr int32_t moment_rows_blocks(int32_t n_vec, int32_t order) { return order == 1 ? 1 + n_vec : 1 + 2 * n_vec; }
 hipError_t launch_moment_rows(MomentRowsArgs a, int32_t n_vec, int32_t order, hipStream_t s);
+// exceedance and rank sums of stored rows (exceedance_rows.hip; the definition is stated in include/rscm_gpu.h,
+// rscm_ens_exceedance_rows): acc[n_rows][G][exceedance_rows_stride(n_thr, equal)] += {total, hits[n_thr], equal[n_thr] when asked} of the
+// rows `rows` (a device array of n_rows device addresses of N doubles), with G = n_groups when group is non-null, else 1.  The
+// thresholds are thr.v[n_thr] for every row, or thr_rows[n_rows][n_thr] (device) when that is non-null.  w non-null: the member
+// weights; base non-null: the value is the row's minus base[i].  The caller zeroes acc.  The grid is capped at kExcRowsBlocks blocks
+// in x, which take kExceedanceRowsMembersPerPass members per pass of their grid-stride loop: a destination collects at most that many adders.
+constexpr int kExcRowsBlocks = 32;
+constexpr int64_t kExceedanceRowsMembersPerPass = 8192;
+struct ExceedanceRowsArgs {
+    const double* const* rows;
+    const double* thr_rows;
+    const int64_t* w;
+    const int32_t* group;
+    const double* base;
+    unsigned long long* acc;
+    Thresholds thr;
+    int64_t N;
+    int32_t n_rows, n_groups, n_thr;
+};
+constexpr int32_t exceedance_rows_stride(int32_t n_thr, bool equal) { return 1 + (equal ? 2 : 1) * n_thr; }
+hipError_t launch_exceedance_rows(const ExceedanceRowsArgs& a, bool equal, hipStream_t s);
 // per-member variability statistics (variability.hip) over rows d_rows[n_rows][N]: d_out[5][N] = mean, slope, variance, sd, r1 of
 // the working series (mode kVarMean / kVarLinear: the rows, kVarDifference: their first differences; the definition is stated in
 // include/rscm_gpu.h, rscm_ens_member_variability); stt = n (n^2 - 1) / 12 of the working series' length n, formed by the caller

@@ -18,6 +18,7 @@ in the CPU tests), are:
 * ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums;
 * ``moments_global``: two all-reduces (int64 SUM) of the fixed-point moment sums, 69 int64 per mean and covariance entry;
 * ``moment_rows_global``: the same two all-reduces for the mean and spread of a stored variable at every row;
+* ``exceedance_rows_global``, ``rank_rows_global``: one all-reduce (int64 SUM) of the per-row hits, equals and totals;
 * ``weights_stats_global``: one all-reduce (int64 SUM) of the exact weight sums and one (MAX) of the largest weight;
 * ``resample_global``: one all-gather of each rank's exact summed weight (8 B per rank); no member crosses a rank.
 
@@ -276,6 +277,42 @@ def moment_rows_global(ensemble, var, t_begin: int = 0, t_end: Optional[int] = N
                             moment_rows_means, moment_rows_result, len(vs), group, grouped)
 
 
+def _row_flags(weighted: bool, anomaly: bool, grouped: bool) -> Dict[str, bool]:
+    """A keyword goes to the ensemble only when set, as in ``quantile_rows_global``."""
+    return {k: True for k, v in (("weighted", weighted), ("anomaly", anomaly), ("grouped", grouped)) if v}
+
+
+def _reduce_together(arrays, group=None):
+    """The int64 arrays SUM-reduced in ONE collective (concatenated, then cut back to their shapes)."""
+    arrays = [np.asarray(a, dtype=np.int64) for a in arrays]
+    acc = _all_reduce_sum(np.concatenate([a.ravel() for a in arrays]), group)
+    cuts = np.cumsum([a.size for a in arrays])[:-1]
+    return [part.reshape(a.shape) for part, a in zip(np.split(acc, cuts), arrays)]
+
+
+def exceedance_rows_global(ensemble, var, thresholds, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, group=None,
+                           weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.exceedance_rows`` of the WHOLE sharded ensemble on every rank: the ranks' int64 hits and totals of every row are
+    SUM-reduced in one collective (exact and independent of order), then ``ensemble.exceedance_rows_result`` forms the
+    probabilities.  Every rank passes the same rows and thresholds and stands at the same time index; ``grouped``: the same
+    ``n_groups`` on every rank."""
+    from .ensemble import exceedance_rows_result
+    local = ensemble.exceedance_rows(var, thresholds, t_begin, t_end, t_stride, **_row_flags(weighted, anomaly, grouped))
+    hits, total = _reduce_together([local["hits"], local["total"]], group)
+    return exceedance_rows_result(hits, total, grouped)
+
+
+def rank_rows_global(ensemble, var, record, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, group=None,
+                     weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.rank_rows`` of the WHOLE sharded ensemble on every rank: the ranks' int64 sums below, equal to and around the
+    record at every row are SUM-reduced in one collective, then ``ensemble.rank_rows_result`` forms the mid-rank.  Every rank
+    passes the same rows and record."""
+    from .ensemble import rank_rows_result
+    local = ensemble.rank_rows(var, record, t_begin, t_end, t_stride, **_row_flags(weighted, anomaly, grouped))
+    below, equal, total = _reduce_together([local["below"], local["equal"], local["total"]], group)
+    return rank_rows_result(total - below, equal, total, record, grouped)
+
+
 def weights_stats_global(ensemble, group=None) -> Dict[str, object]:
     """``Ensemble.weights_stats`` of the WHOLE sharded ensemble on every rank: the ranks' exact integers are SUM-reduced (``w_max``:
     MAX) -- sum w^2 as four 32-bit limbs, each of which sums without wrapping over any number of ranks an int64 can count -- and
@@ -417,6 +454,17 @@ class ShardedEnsemble:
         """Exact mean and spread of a stored variable at every row over the global ensemble, with its covariance with per-member
         vectors (``moment_rows_global``)."""
         return moment_rows_global(self.ensemble, var, t_begin, t_end, t_stride, vectors, weighted=weighted, anomaly=anomaly, grouped=grouped)
+
+    def exceedance_rows_global(self, var, thresholds, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1,
+                               weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Exceedance probabilities of a stored variable at every row over the global ensemble (``exceedance_rows_global``)."""
+        return exceedance_rows_global(self.ensemble, var, thresholds, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly,
+                                      grouped=grouped)
+
+    def rank_rows_global(self, var, record, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                         anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Where a record lies inside the global ensemble's plume at every row (``rank_rows_global``)."""
+        return rank_rows_global(self.ensemble, var, record, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, grouped=grouped)
 
     def exceedance_global(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""

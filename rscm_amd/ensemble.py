@@ -1055,6 +1055,46 @@ class Ensemble:
                                                L.dptr(mean), L.dptr(second), n.ctypes.data_as(i64), w.ctypes.data_as(i64)))
         return moment_rows_dict(n, w, mean, second, grouped)
 
+    def _exceedance_rows_sums(self, var, thr, per_row, t_begin, t_end, t_stride, weighted, anomaly, grouped, with_equal):
+        """rscm_ens_exceedance_rows: int64 ``hits[rows][G][K]``, ``equal`` (None unless asked for) and ``total[rows][G]``."""
+        G = self._n_groups(grouped)
+        rows = len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0
+        K = thr.shape[-1]
+        hits, total = np.zeros((rows, G, K), dtype=np.int64), np.zeros((rows, G), dtype=np.int64)
+        equal = np.zeros((rows, G, K), dtype=np.int64) if with_equal else None
+        i64 = C.POINTER(C.c_int64)
+        L.check(self._lib.rscm_ens_exceedance_rows(self._h, self._var(var), t_begin, t_end, t_stride, K, L.dptr(thr), int(per_row),
+                                                   select_flags(weighted, anomaly, grouped), hits.ctypes.data_as(i64),
+                                                   equal.ctypes.data_as(i64) if with_equal else None, total.ctypes.data_as(i64)))
+        return hits, equal, total
+
+    def exceedance_rows(self, var, thresholds, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                        anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Exceedance as a series: at every row ``t_begin, t_begin + t_stride, ... < t_end`` of ``var``, read wherever the rows are
+        resident, the members (with ``weighted`` their summed weight) at or above each threshold.  ``thresholds`` is ``[K]``, the
+        same for every row, or ``[rows][K]``, 1 <= K <= 8; any other shape is a ``ValueError``.  Returns ``{"hits": [rows][K] int64,
+        "total": [rows] int64 (the members that are not NaN in that row, or their weight), "probability": hits / total}``, NaN where
+        total is 0; with ``grouped`` per member group, the group axis after the rows.  ``anomaly`` takes the member's value minus its
+        baseline (the bits ``quantile_rows(anomaly=True)`` sees).  A NaN threshold gives hits 0 and leaves total alone.  Integer
+        sums in one launch for all rows: exact, so those of shards add up (``rscm_amd.distributed.exceedance_rows_global``).  Rows
+        beyond the time index: zeros, NaN."""
+        t_end = self.n_times if t_end is None else t_end
+        thr, per_row = exceedance_rows_thresholds(thresholds, len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0)
+        hits, _, total = self._exceedance_rows_sums(var, thr, per_row, t_begin, t_end, t_stride, weighted, anomaly, grouped, False)
+        return exceedance_rows_result(hits, total, grouped)
+
+    def rank_rows(self, var, record, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                  anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Where a record lies inside the plume: for every row the summed weight of the members below the observed value
+        (``below``), equal to it (``equal``) and of all members that are not NaN there (``total``), int64 ``[rows]``, and the
+        mid-rank ``pit = (2 below + equal) / (2 total)``, the record's probability integral transform.  ``record`` is ``[rows]``;
+        NaN marks a row without an observation (``below = total``, ``equal = 0``, ``pit`` NaN).  ``rank_histogram`` bins the rows.
+        Flags, rows and exactness as ``exceedance_rows``, whose kernel this is with the record as the per-row threshold."""
+        t_end = self.n_times if t_end is None else t_end
+        rec = rank_rows_record(record, len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0)
+        hits, equal, total = self._exceedance_rows_sums(var, rec[:, None], True, t_begin, t_end, t_stride, weighted, anomaly, grouped, True)
+        return rank_rows_result(hits[..., 0], equal[..., 0], total, rec, grouped)
+
     def params_vector(self, row: int) -> DeviceVector:
         """Parameter row ``row`` of the ``[P][N]`` block as a ``DeviceVector`` (rscm_ens_params_devptr), e.g. for
         ``quantile_vectors``.  Once handed out, the block is read per member for the handle's life."""
@@ -1237,6 +1277,93 @@ def exceedance_grouped_result(hits, total) -> Dict[str, object]:
     with np.errstate(divide="ignore", invalid="ignore"):
         prob = np.where(total[:, None] != 0, hits.astype(np.float64) / total.astype(np.float64)[:, None], np.nan)
     return {"hits": hits, "total": total, "probability": prob}
+
+
+def exceedance_rows_thresholds(thresholds, rows: int):
+    """The checked thresholds of ``Ensemble.exceedance_rows`` over ``rows`` rows: ``(float64 array, per_row)`` from ``[K]`` (the
+    same for every row) or ``[rows][K]``, 1 <= K <= 8.  Any other shape is a ``ValueError``; no library call is made."""
+    thr = np.asarray(thresholds, dtype=np.float64)
+    K = thr.shape[-1] if thr.ndim in (1, 2) else 0
+    if not 1 <= K <= L.EXCEEDANCE_ROWS_MAX_THRESHOLDS or (thr.ndim == 2 and thr.shape[0] != rows):
+        raise ValueError(f"exceedance_rows: thresholds must be [K] or [{rows}][K] with 1 <= K <= {L.EXCEEDANCE_ROWS_MAX_THRESHOLDS}, "
+                         f"got shape {thr.shape}")
+    return np.ascontiguousarray(thr), thr.ndim == 2
+
+
+def rank_rows_record(record, rows: int) -> np.ndarray:
+    """The checked record of ``Ensemble.rank_rows`` over ``rows`` rows: float64 ``[rows]``, else a ``ValueError``."""
+    rec = np.asarray(record, dtype=np.float64)
+    if rec.shape != (rows,):
+        raise ValueError(f"rank_rows: the record must be [{rows}], got shape {rec.shape}")
+    return np.ascontiguousarray(rec)
+
+
+def _int_ratio(num: np.ndarray, den: np.ndarray) -> np.ndarray:
+    """``num / den`` of non-negative int64 arrays of one shape as float64, each the exact quotient rounded once; NaN where den is 0."""
+    out = np.full(num.shape, np.nan)
+    ok = den != 0
+    if max(int(num.max(initial=0)), int(den.max(initial=0))) <= 1 << 53:     # both convert exactly: one IEEE division
+        out[ok] = num[ok].astype(np.float64) / den[ok].astype(np.float64)
+    else:                                                                    # Python's int / int rounds the exact quotient once
+        out[ok] = [n / d for n, d in zip(num[ok].tolist(), den[ok].tolist())]
+    return out
+
+
+def _rows_groups(a, lead: np.ndarray = None) -> np.ndarray:
+    """int64 ``[rows][G]...``: an array whose group axis (of length 1) was dropped gets it back; ``lead`` is one that has it."""
+    a = np.asarray(a, dtype=np.int64)
+    if lead is not None:
+        return a.reshape(lead.shape[:2])
+    return a[:, None, :] if a.ndim == 2 else a
+
+
+def exceedance_rows_result(hits, total, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """The dict of ``Ensemble.exceedance_rows`` from the (reduced) int64 sums ``hits[rows][G][K]`` and ``total[rows][G]`` (G = 1
+    without groups; that axis may be absent): ``probability = hits / total``, the exact quotient rounded once, NaN where total is
+    0.  Without ``grouped`` the group axis is dropped."""
+    hits = _rows_groups(hits)
+    total = _rows_groups(total, hits)
+    out = {"hits": hits, "total": total, "probability": _int_ratio(hits, np.broadcast_to(total[..., None], hits.shape))}
+    return out if grouped else {k: v[:, 0] for k, v in out.items()}
+
+
+def rank_rows_result(hits, equal, total, record, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """The dict of ``Ensemble.rank_rows`` from the (reduced) int64 sums ``hits``, ``equal`` and ``total``, each ``[rows][G]`` (G = 1
+    without groups; that axis may be absent), of ``Ensemble.exceedance_rows``' kernel with ``record[rows]`` as the per-row
+    threshold: ``below = total - hits``, and the mid-rank ``pit = (2 below + equal) / (2 total)``, the exact quotient rounded
+    once, NaN where the record is NaN or total is 0.  Without ``grouped`` the group axis is dropped."""
+    total = np.asarray(total, dtype=np.int64)
+    total = total[:, None] if total.ndim == 1 else total
+    hits, equal = _rows_groups(hits, total), _rows_groups(equal, total)
+    record = np.asarray(record, dtype=np.float64).reshape(total.shape[0])
+    below = total - hits
+    pit = _int_ratio(2 * below + equal, 2 * total)
+    pit[np.isnan(record)] = np.nan
+    out = {"below": below, "equal": equal, "total": total, "pit": pit}
+    return out if grouped else {k: v[:, 0] for k, v in out.items()}
+
+
+def rank_histogram(below, equal, total, n_bins: int, record=None) -> np.ndarray:
+    """The rank histogram of ``Ensemble.rank_rows``' ``below``, ``equal`` and ``total`` (``[rows]``, or ``[rows][G]``): int64
+    ``[n_bins]`` (``[G][n_bins]``), the number of rows whose mid-rank falls into each of ``n_bins`` equal bins of [0, 1], bin
+    ``floor(n_bins (2 below + equal) / (2 total))`` in Python integers -- no float binning -- with the top edge (a record at or
+    above every member) in the last bin.  A flat histogram says the plume is neither too narrow nor too wide.  Rows without
+    weight (total 0) have no rank and are left out, and so are the rows whose ``record`` (``[rows]``, if given) is NaN: pass the
+    record that ``rank_rows`` took, since a row without an observation reads ``below = total`` like one above every member."""
+    n_bins = int(n_bins)
+    if n_bins < 1:
+        raise ValueError("rank_histogram: n_bins must be at least 1")
+    below, equal, total = (np.asarray(a, dtype=np.int64) for a in (below, equal, total))
+    if not (below.shape == equal.shape == total.shape and below.ndim in (1, 2)):
+        raise ValueError("rank_histogram: below, equal and total must share one shape, [rows] or [rows][G]")
+    has = np.ones(below.shape[0], dtype=bool) if record is None else ~np.isnan(np.asarray(record, dtype=np.float64).reshape(below.shape[0]))
+    b2, e2, t2 = (a.reshape(a.shape[0], -1) for a in (below, equal, total))
+    out = np.zeros((b2.shape[1], n_bins), dtype=np.int64)
+    for r in np.flatnonzero(has):
+        for g, (b, e, t) in enumerate(zip(b2[r].tolist(), e2[r].tolist(), t2[r].tolist())):
+            if t > 0:
+                out[g, min(n_bins * (2 * b + e) // (2 * t), n_bins - 1)] += 1
+    return out if below.ndim == 2 else out[0]
 
 
 def moment_blocks(K: int, order: int) -> int:
