@@ -121,8 +121,11 @@ extern "C" {
  *  25  the device Latin hypercube through Normal, LogNormal and truncated priors: rscm_ens_sample_lhs_priors, RSCM_PRIOR_UNIFORM,
  *      RSCM_PRIOR_NORMAL, RSCM_PRIOR_LOGNORMAL, RSCM_PRIOR_REFLECT
  *  26  the exceedance of up to eight thresholds, fixed or per row, and the rank of a record inside the plume, for every row of a
- *      stored variable in one launch: rscm_ens_exceedance_rows, RSCM_EXCEEDANCE_ROWS_MAX_THRESHOLDS */
-#define RSCM_GPU_ABI_MINOR 26
+ *      stored variable in one launch: rscm_ens_exceedance_rows, RSCM_EXCEEDANCE_ROWS_MAX_THRESHOLDS
+ *  27  running means of a stored variable or of a diagnostic over the time axis as diagnostic variables, which every reader of rows
+ *      then takes by id: rscm_ens_define_running_mean, rscm_ens_diagnostic_running_mean, RSCM_RUNMEAN_MAX_WINDOW,
+ *      RSCM_RUNMEAN_TRAILING, RSCM_RUNMEAN_CENTRED */
+#define RSCM_GPU_ABI_MINOR 27
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1514,6 +1517,43 @@ RSCM_API int rscm_ens_n_diagnostics(const rscm_ens* h, int32_t* out);
 #define RSCM_BUDGET_IMBALANCE 4
 RSCM_API int rscm_ens_define_energy_budget(rscm_ens* h, int32_t quantity, double scale, int32_t* var_id_out);
 RSCM_API int rscm_ens_diagnostic_quantity(rscm_ens* h, int32_t var_id, int32_t* quantity, double* scale);
+
+/* ---- running means (ABI minor 27) ------------------------------------------------------------------ */
+/* The mean of W = window rows of a variable, `step` time indices apart, as a diagnostic variable.  For member i, x[u] row u of the
+ * source for that member, and back = W - 1 (RSCM_RUNMEAN_TRAILING: the window ends at t) or (W - 1) / 2 in integer division
+ * (RSCM_RUNMEAN_CENTRED: W = 20 spans t - 9 .. t + 10), the row at time index t is
+ *     s = x[t - back * step];   then for j = 1 .. W - 1 in that order   s = s + x[t + (j - back) * step];   y = s / (double)W
+ * Every add and the one division is one IEEE f64 operation rounded on its own: no FMA, no reciprocal, no pairwise tree, and no sliding
+ * update (s + new - old) -- a row is a pure function of its own W terms.  An Inf or NaN in row k of the source therefore reaches
+ * exactly the rows whose window holds k, and every later row is untouched.  Bit-exact against this statement.
+ * step is the spacing of the window's terms: step = 12 gives a 20-year mean from every twelfth row of a monthly axis; step = 1 and
+ * window = 12 computed with t_stride = 12 gives the annual means of monthly rows.
+ *
+ * rscm_ens_define_running_mean.  source_var is a stored variable 1 .. V - 1 or a linear or energy-budget diagnostic defined earlier
+ * on the handle: the first diagnostic whose source may be a diagnostic.  RSCM_ERR_INVALID for the input (0), a source that is itself
+ * a running mean, an id that is not defined, a window outside 2 .. RSCM_RUNMEAN_MAX_WINDOW, an align other than the two constants,
+ * step < 1, a fifth definition; RSCM_ERR_STATE while a staged select is in flight.  The definition takes one of the RSCM_DIAG_MAX
+ * slots; ids, rscm_ens_n_diagnostics and rscm_ens_clear_diagnostics work as for rscm_ens_define_diagnostic, and every reader of a
+ * diagnostic's rows takes the id.  rscm_ens_diagnostic and rscm_ens_diagnostic_quantity answer as for an energy-budget diagnostic: no
+ * terms, quantity 0.  rscm_ens_diagnostic_running_mean reads the definition back; a diagnostic that is no running mean gives
+ * source_var 0 (and 0 for the rest).  Any out pointer may be NULL.
+ *
+ * rscm_ens_compute_diagnostic forms the rows t_begin, t_begin + t_stride, ... < t_end, the last of them t_last.  t_stride must be a
+ * multiple of step (RSCM_ERR_INVALID).  The source rows reach from t_begin - back * step to t_last + (W - 1 - back) * step at spacing
+ * step, and every one of them -- those between two windows where t_stride > W * step included -- must lie on the axis
+ * (RSCM_ERR_INVALID) and be computed and resident, in full storage, the window or the output store (RSCM_ERR_STATE, as for a
+ * linear diagnostic's sources); the rows of a diagnostic source must be held and current at exactly those time indices
+ * (RSCM_ERR_STATE).  Nothing is padded with NaN: a row whose window is incomplete is refused, not invented.  A refused compute
+ * leaves the rows held before in place.
+ *
+ * Staleness.  The rows are a snapshot at the write epoch like every diagnostic's.  A running mean whose source reads the forcing
+ * (RSCM_BUDGET_FORCING, RSCM_BUDGET_IMBALANCE) goes stale with the forcing as that source does.  Once formed the rows do not depend
+ * on the source's store: computing the source again over another range leaves them valid. */
+#define RSCM_RUNMEAN_MAX_WINDOW 64
+#define RSCM_RUNMEAN_TRAILING 0
+#define RSCM_RUNMEAN_CENTRED  1
+RSCM_API int rscm_ens_define_running_mean(rscm_ens* h, int32_t source_var, int32_t window, int32_t align, int32_t step, int32_t* var_id_out);
+RSCM_API int rscm_ens_diagnostic_running_mean(rscm_ens* h, int32_t var_id, int32_t* source_var, int32_t* window, int32_t* align, int32_t* step);
 
 /* ---- posterior ensembles: systematic resampling and branching (ABI minor 10) --------------------- */
 /* Exact statistics of the member weights, formed on the device in integers: *total = sum w, *n_nonzero = the members with w != 0,

@@ -46,6 +46,9 @@ BUDGET_FORCING, BUDGET_RESPONSE, BUDGET_DEEP_UPTAKE, BUDGET_IMBALANCE = 1, 2, 3,
 BUDGET_QUANTITIES = {"forcing": BUDGET_FORCING, "response": BUDGET_RESPONSE, "deep_uptake": BUDGET_DEEP_UPTAKE, "imbalance": BUDGET_IMBALANCE}
 BUDGET_DEFAULT_NAMES = {"forcing": "Member Forcing", "response": "Radiative Response", "deep_uptake": "Deep Ocean Heat Uptake",
                         "imbalance": "Top of Atmosphere Imbalance"}
+# rscm_ens_define_running_mean: the longest window, the two alignments and the names the front end gives them
+RUNMEAN_MAX_WINDOW, RUNMEAN_TRAILING, RUNMEAN_CENTRED = 64, 0, 1
+RUNMEAN_ALIGN = {"trailing": RUNMEAN_TRAILING, "centre": RUNMEAN_CENTRED}
 VAR_MEAN, VAR_LINEAR, VAR_DIFFERENCE = 0, 1, 2  # rscm_ens_member_variability's detrending modes
 COV_MAX_LAGS = 3                                  # rscm_ens_member_covariability: 0 .. 3 leads and lags
 XSPEC_MAX_BANDS = 3                               # rscm_ens_member_cross_spectrum: 1 .. 3 bands (RSCM_XSPEC_MAX_BANDS)
@@ -389,6 +392,8 @@ SIGNATURES = {
     "rscm_ens_n_diagnostics": (C.c_int, [_h, _ip]),
     "rscm_ens_define_energy_budget": (C.c_int, [_h, C.c_int32, C.c_double, _ip]),
     "rscm_ens_diagnostic_quantity": (C.c_int, [_h, C.c_int32, _ip, _dp]),
+    "rscm_ens_define_running_mean": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _ip]),
+    "rscm_ens_diagnostic_running_mean": (C.c_int, [_h, C.c_int32, _ip, _ip, _ip, _ip]),
     "rscm_ens_quantile_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32, _dp, _dp]),
     "rscm_ens_select_begin_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32]),
     "rscm_ens_exceedance": (C.c_int, [_h, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),

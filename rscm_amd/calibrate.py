@@ -396,7 +396,8 @@ def refuse_diagnostic_targets(runner, target) -> None:
     """The same for a whole target against the diagnostics of the runner's builder (``ModelBuilder.with_diagnostic``), before any
     model is built: what the samplers ask when they are made."""
     builder = getattr(runner, "_builder", None)
-    names = {n for n, _, _ in getattr(builder, "_diagnostics", ())} | {n for _, n, _ in getattr(builder, "_energy_budgets", ())}
+    names = {n for n, _, _ in getattr(builder, "_diagnostics", ())} | {n for _, n, _ in getattr(builder, "_energy_budgets", ())} | {
+        n for n, *_ in getattr(builder, "_running_means", ())}
     for name, _ in target.variables():
         if name in names:
             raise ValueError(f"{name!r} is a diagnostic variable: diagnostics are scored by run(), compute_diagnostic() and loglik() "

@@ -456,6 +456,7 @@ class ModelBuilder:
         self._noise_params = False                        # with_forcing_noise_parameters: sigma and phi are parameter rows
         self._diagnostics: List[Tuple[str, Dict[str, Optional[str]], Dict[str, float]]] = []   # with_diagnostic
         self._energy_budgets: List[Tuple[str, str, float]] = []   # with_energy_budget: (quantity, name, scale)
+        self._running_means: List[Tuple[str, str, int, str, int]] = []   # with_running_mean: (name, source, window, align, step)
 
     def with_time_axis(self, time_axis: TimeAxis) -> "ModelBuilder":
         self._axis = time_axis
@@ -538,9 +539,24 @@ class ModelBuilder:
         self._energy_budgets.append((str(quantity), name, float(scale)))
         return self
 
+    def with_running_mean(self, name: str, source: str, window: int = 20, align: str = "centre", step: int = 1) -> "ModelBuilder":
+        """Extension: a diagnostic variable ``name`` of the built model, the running mean of ``source`` -- a variable of the model
+        or a diagnostic of ``with_diagnostic`` / ``with_energy_budget`` -- over ``window`` rows ``step`` time indices apart
+        (``Ensemble.define_running_mean``).  ``build()`` defines it after the other diagnostics, on the model's ensemble or in a
+        graph on the source's home (``GraphModel.define_running_mean``)."""
+        from .variability import running_mean_back
+        running_mean_back(window, align)
+        if int(step) < 1:
+            raise ValueError(f"step must be at least 1, got {step}")
+        taken = [n for n, _, _ in self._diagnostics] + [n for _, n, _ in self._energy_budgets] + [n for n, *_ in self._running_means]
+        if name in taken:
+            raise ValueError(f"diagnostic {name!r} is defined already")
+        self._running_means.append((str(name), str(source), int(window), str(align), int(step)))
+        return self
+
     def _define_diagnostics(self, model):
-        """What ``build()`` does with ``with_diagnostic`` and ``with_energy_budget``: on the ensemble of a ``Model`` or the homes
-        of a ``GraphModel``."""
+        """What ``build()`` does with ``with_diagnostic``, ``with_energy_budget`` and ``with_running_mean``: on the ensemble of a
+        ``Model`` or the homes of a ``GraphModel``."""
         for quantity, name, scale in self._energy_budgets:
             (model if isinstance(model, GraphModel) else model.ensemble).define_energy_budget(quantity, name, scale)
         for name, weights, scales in self._diagnostics:
@@ -555,6 +571,8 @@ class ModelBuilder:
             if any(v not in model.ensemble.var_ids for v, _, _ in terms):
                 raise ValueError(f"diagnostic {name!r}: variables {[v for v, _, _ in terms]}; this model has {sorted(model.ensemble.var_ids)}")
             model.ensemble.define_diagnostic(name, terms)
+        for name, source, window, align, step in self._running_means:   # last: their sources may be the diagnostics above
+            (model if isinstance(model, GraphModel) else model.ensemble).define_running_mean(name, source, window, align, step)
         return model
 
     def with_forcing_noise(self, sigma: float, seed: int, phi: float = 0.0) -> "ModelBuilder":
@@ -1235,15 +1253,30 @@ class GraphModel:
         self._diagnostics[name] = (owners[0], vid)
         return vid
 
-    def compute_diagnostic(self, name: str, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
-        """``Ensemble.compute_diagnostic`` of ``name`` on its home ensemble (``t_end=None``: up to and including the model's
-        current step)."""
+    def define_running_mean(self, name: str, source: str, window: int = 20, align: str = "centre", step: int = 1) -> int:
+        """``Ensemble.define_running_mean`` on the home ensemble of ``source``, a variable of the graph or a diagnostic defined on
+        it before.  ``variable_home(name)`` then resolves it like any diagnostic."""
+        if name in self._diagnostics or name in self._var_home:
+            raise ValueError(f"variable name {name!r} is taken")
+        ens, src = self.variable_home(source)
+        owner = next(o for o, e in self.ensembles.items() if e is ens)
+        vid = ens.define_running_mean(name, src, window, align, step)
+        self._diagnostics[name] = (owner, vid)
+        return vid
+
+    def compute_diagnostic(self, name: str, t_begin: Optional[int] = None, t_end: Optional[int] = None, t_stride: int = 1) -> None:
+        """``Ensemble.compute_diagnostic`` of ``name`` on its home ensemble (``t_begin=None``: row 0, ``t_end=None``: up to and
+        including the model's current step; for a running mean the first and one past the last row with a full window at or
+        below it)."""
         if name not in self._diagnostics:
             raise KeyError(f"no diagnostic named {name!r}")
         for ens in self.ensembles.values():
             ens.sync()
         ens, vid = self.variable_home(name)
-        ens.compute_diagnostic(vid, t_begin, self.time_index + 1 if t_end is None else t_end, t_stride)
+        if ens.diagnostics_running_mean(vid) is not None:
+            lo, hi = ens.running_mean_range(vid, time_index=self.time_index)
+            t_begin, t_end = (lo if t_begin is None else t_begin), (hi if t_end is None else t_end)
+        ens.compute_diagnostic(vid, 0 if t_begin is None else t_begin, self.time_index + 1 if t_end is None else t_end, t_stride)
 
     def get_series(self, name: str, **kw) -> np.ndarray:
         ens, vid = self.variable_home(name)

@@ -9,7 +9,8 @@
 // one is in flight.
 //
 // An energy-budget diagnostic (energy_budget_host.cpp) takes one of the same slots and is computed through the same entry point: its
-// sources are the two state rows of the two-layer kind, its checks and its launch are budget_check and budget_launch.
+// sources are the two state rows of the two-layer kind, its checks and its launch are budget_check and budget_launch.  So does a running
+// mean (running_mean_host.cpp), whose whole compute is running_mean_compute.
 #include <cmath>
 
 #include "diagnostic.hpp"
@@ -95,6 +96,7 @@ int rscm_ens_compute_diagnostic(rscm_ens* h, int32_t var_id, int32_t t_begin, in
     if (int rc = check_is_diagnostic(h, var_id)) return rc;
     if (int rc = no_select(h)) return rc;
     rscm_ens::Diagnostic& d = h->diag[var_id - h->V];
+    if (d.rm_source != 0) return running_mean_compute(h, d, t_begin, t_end, t_stride);
     // the sources' rows, term after term: [K][R]
     std::vector<const double*> rows, term_rows;
     std::vector<double> times;

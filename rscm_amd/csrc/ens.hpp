@@ -188,16 +188,22 @@ struct rscm_ens : EnsQueues {
     // snapshot of it as well: forcing_epoch moves with whatever replaces the forcing table, the scenario assignment or the source
     // (rscm_ens_set_forcing, a mix handle's included) and with a link made or dropped, and their rows serve only at the forcing epoch
     // they were computed at.  The linear diagnostics and the two forcing-free quantities do not look at it.
+    // A running mean (running_mean_host.cpp; kernel in running_mean.hip) takes a slot as well: rm_source is the variable it averages
+    // (0: no running mean) -- a stored variable or a diagnostic of a lower slot that is no running mean itself -- over rm_window terms
+    // rm_step time indices apart, aligned rm_align (RSCM_RUNMEAN_*); n_terms and quantity are 0.  rm_forcing: its source reads the
+    // forcing, so its rows go stale with the forcing epoch too.  Once formed, its rows do not depend on the source's store.
     struct Diagnostic {
         int32_t n_terms = 0;
         int32_t var[RSCM_DIAG_MAX_TERMS] = {}, row[RSCM_DIAG_MAX_TERMS] = {};
         double scale[RSCM_DIAG_MAX_TERMS] = {};
         int32_t quantity = 0;
         double budget_scale = 0.0;
+        int32_t rm_source = 0, rm_window = 0, rm_align = 0, rm_step = 1;
+        bool rm_forcing = false;
         rscm::DevBuf<double> d_rows;   // [size() / N][N]: room for at least `held` rows
         int32_t held = 0, t_begin = 0, t_stride = 1;
         uint64_t epoch = 0, forcing_epoch = 0;
-        bool reads_forcing() const { return quantity == RSCM_BUDGET_FORCING || quantity == RSCM_BUDGET_IMBALANCE; }
+        bool reads_forcing() const { return quantity == RSCM_BUDGET_FORCING || quantity == RSCM_BUDGET_IMBALANCE || rm_forcing; }
     };
     Diagnostic diag[RSCM_DIAG_MAX];
     int32_t n_diag = 0;
@@ -394,6 +400,9 @@ int check_diagnostic_current(const rscm_ens* h, int32_t var_id);
 // d_src [2][n_rows] (Ts, Td) into d.d_rows, enqueued on the handle's stream.
 int budget_check(const rscm_ens* h, const rscm_ens::Diagnostic& d, int32_t t_begin, int32_t t_stride, int32_t n_rows);
 hipError_t budget_launch(rscm_ens* h, rscm_ens::Diagnostic& d, const double* const* d_src, int32_t t_begin, int32_t t_stride, int32_t n_rows);
+// A running-mean diagnostic inside rscm_ens_compute_diagnostic (running_mean_host.cpp): every check of the range and of the source's
+// rows, the launch and the bookkeeping of the store.  A refusal leaves the rows held before in place.
+int running_mean_compute(rscm_ens* h, rscm_ens::Diagnostic& d, int32_t t_begin, int32_t t_end, int32_t t_stride);
 int resolve_rows(const rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, std::vector<const double*>& rows,
                  int32_t* n_range);
 // resolve_rows with its checks for a range every row of which must be computed (RSCM_ERR_STATE else), and the rows' times

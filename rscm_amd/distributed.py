@@ -430,7 +430,12 @@ class ShardedEnsemble:
         ensemble's."""
         return self.ensemble.define_energy_budget(quantity, name, scale)
 
-    def compute_diagnostic(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
+    def define_running_mean(self, name: str, source, window: int = 20, align: str = "centre", step: int = 1) -> int:
+        """``Ensemble.define_running_mean`` on this rank's block.  The mean is per member, so the shards' rows are the blocks of
+        the whole ensemble's."""
+        return self.ensemble.define_running_mean(name, source, window, align, step)
+
+    def compute_diagnostic(self, var, t_begin: Optional[int] = None, t_end: Optional[int] = None, t_stride: int = 1) -> None:
         """``Ensemble.compute_diagnostic`` on this rank's block; every rank calls it with the same range."""
         self.ensemble.compute_diagnostic(var, t_begin, t_end, t_stride)
 

@@ -9,7 +9,7 @@ index ``time_index + 1``; ``run()`` steps to the end of the axis.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -853,20 +853,72 @@ class Ensemble:
         """``define_energy_budget("imbalance", name, scale)``: the quantity observations constrain the feedback through."""
         return self.define_energy_budget("imbalance", name, scale)
 
-    def compute_diagnostic(self, var, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1) -> None:
+    def define_running_mean(self, name: str, source, window: int = 20, align: str = "centre", step: int = 1) -> int:
+        """A diagnostic variable ``name``: the running mean of ``source`` -- a stored variable, or a linear or energy-budget
+        diagnostic defined before (name or id) -- over ``window`` rows ``step`` time indices apart.  ``align``: ``"centre"`` (the
+        window of row t starts ``(window - 1) // 2`` terms before it: 20 terms span t - 9 .. t + 10) or ``"trailing"`` (it ends at
+        t).  The terms are added in time order, one float64 add each, and divided by ``float(window)``; there is no sliding update,
+        so a non-finite source row reaches the rows whose window holds it and no other (rscm_ens_define_running_mean states the
+        arithmetic; ``rscm_amd.variability.series_running_mean`` is the same estimator for a record).  Every method that takes
+        ``var`` takes the name once ``compute_diagnostic`` has formed the rows: ``indicators`` gives the crossing of the 20-year
+        mean, ``exceedance_rows`` its probability, ``loglik`` scores a decadal mean.  ``step=12`` averages every twelfth row of a
+        monthly axis; ``step=1, window=12`` computed with ``t_stride=12`` gives annual means of monthly rows.  Window 2 .. 64;
+        takes one of the 4 diagnostic slots.  Returns the new id."""
+        if not isinstance(name, str) or not name:
+            raise ValueError("a diagnostic needs a name")
+        if name in self.var_ids:
+            raise ValueError(f"variable name {name!r} is taken")
+        if align not in L.RUNMEAN_ALIGN:
+            raise ValueError(f"align must be one of {sorted(L.RUNMEAN_ALIGN)}, got {align!r}")
+        vid = C.c_int32()
+        L.check(self._lib.rscm_ens_define_running_mean(self._h, self._var(source), int(window), L.RUNMEAN_ALIGN[align], int(step), C.byref(vid)))
+        self.var_ids[name] = vid.value
+        self._diagnostic_names[name] = vid.value
+        return vid.value
+
+    def diagnostics_running_mean(self, vid: int) -> Optional[Dict[str, object]]:
+        """The running-mean definition behind diagnostic ``vid`` as ``diagnostics`` reports it, ``None`` for another sort."""
+        src, w, al, st = (C.c_int32() for _ in range(4))
+        L.check(self._lib.rscm_ens_diagnostic_running_mean(self._h, vid, C.byref(src), C.byref(w), C.byref(al), C.byref(st)))
+        if src.value == 0:
+            return None
+        return {"source": src.value, "window": w.value, "align": {v: k for k, v in L.RUNMEAN_ALIGN.items()}[al.value], "step": st.value}
+
+    def running_mean_range(self, var, time_index: Optional[int] = None) -> Tuple[int, int]:
+        """``(t_begin, t_end)`` of running-mean diagnostic ``var``: the first row whose window is complete, and one past the last
+        row whose window ends at or below ``time_index`` (default: the ensemble's own).  What ``compute_diagnostic`` takes for
+        ``None``.  ``t_end <= t_begin`` while no row has a full window."""
+        rm = self.diagnostics_running_mean(self._var(var))
+        if rm is None:
+            raise ValueError(f"{var!r} is no running mean")
+        from .variability import running_mean_back
+        back = running_mean_back(rm["window"], rm["align"]) * rm["step"]
+        ahead = (rm["window"] - 1) * rm["step"] - back
+        return back, (self.time_index if time_index is None else int(time_index)) - ahead + 1
+
+    def compute_diagnostic(self, var, t_begin: Optional[int] = None, t_end: Optional[int] = None, t_stride: int = 1) -> None:
         """Form the rows ``t_begin, t_begin + t_stride, ... < t_end`` of diagnostic ``var`` from the stored rows and the parameters
-        as they stand (``t_end=None``: up to and including the current time index).  They are a snapshot: after anything that
+        as they stand (``t_begin=None``: row 0; ``t_end=None``: up to and including the current time index).  For a running mean
+        (``define_running_mean``) ``t_begin=None`` is the first row with a full window and ``t_end=None`` one past the last row
+        with a full window at or below the time index (``running_mean_range``); explicit values are passed through and may be
+        refused -- no row is padded.  The rows are a snapshot: after anything that
         writes rows or parameters (``run``, ``rewind``, ``set_params``, ``restore``, being a ``branch`` destination, ...) readers
         are refused until the next ``compute_diagnostic`` (rscm_ens_compute_diagnostic).  One range at a time."""
+        vid = self._var(var)
+        if (t_begin is None or t_end is None) and vid >= self.n_vars and self.diagnostics_running_mean(vid) is not None:
+            lo, hi = self.running_mean_range(vid)
+            t_begin, t_end = (lo if t_begin is None else int(t_begin)), (hi if t_end is None else int(t_end))
+        t_begin = 0 if t_begin is None else int(t_begin)
         t_end = self.time_index + 1 if t_end is None else int(t_end)
-        L.check(self._lib.rscm_ens_compute_diagnostic(self._h, self._var(var), int(t_begin), t_end, int(t_stride)))
+        L.check(self._lib.rscm_ens_compute_diagnostic(self._h, vid, t_begin, t_end, int(t_stride)))
 
     @property
     def diagnostics(self) -> Dict[str, Dict[str, object]]:
         """The definitions as the library holds them, by name: ``{"id", "terms": [(var id, param row or None, scale)],
-        "rows_held", "t_begin", "t_stride", "quantity", "scale"}`` (``rows_held`` 0 when nothing is computed or the rows are stale;
-        ``quantity`` is ``None`` and ``scale`` ``None`` for a linear diagnostic, the name of the energy-budget quantity and its
-        scale for one of ``define_energy_budget``, whose ``terms`` are empty)."""
+        "rows_held", "t_begin", "t_stride", "quantity", "scale", "running_mean"}`` (``rows_held`` 0 when nothing is computed or the
+        rows are stale; ``quantity`` is ``None`` and ``scale`` ``None`` for a linear diagnostic, the name of the energy-budget
+        quantity and its scale for one of ``define_energy_budget``, whose ``terms`` are empty; ``running_mean`` is ``None``, or
+        ``{"source": id, "window", "align", "step"}`` for one of ``define_running_mean``, whose ``terms`` are empty too)."""
         out = {}
         quantity_names = {v: k for k, v in L.BUDGET_QUANTITIES.items()}
         for name, vid in self._diagnostic_names.items():
@@ -881,6 +933,7 @@ class Ensemble:
             L.check(self._lib.rscm_ens_diagnostic_quantity(self._h, vid, C.byref(q), C.byref(qs)))
             out[name]["quantity"] = quantity_names.get(q.value)
             out[name]["scale"] = qs.value if q.value else None
+            out[name]["running_mean"] = self.diagnostics_running_mean(vid)
         return out
 
     def clear_diagnostics(self) -> None:
@@ -1237,7 +1290,11 @@ class Ensemble:
         for name, d in self.diagnostics.items():   # the projection can be summarised the way the source is (rows: dst's to compute)
             if name in dst.var_ids:
                 continue
-            if d["quantity"] is None:
+            if d["running_mean"] is not None:   # after its source (ids are in order of definition); the source by name, dst's id
+                rm = d["running_mean"]
+                source = next(n for n, v in self.var_ids.items() if v == rm["source"])
+                dst.define_running_mean(name, source, rm["window"], rm["align"], rm["step"])
+            elif d["quantity"] is None:
                 dst.define_diagnostic(name, d["terms"])
             else:
                 dst.define_energy_budget(d["quantity"], name, d["scale"])

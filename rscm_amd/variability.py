@@ -7,9 +7,12 @@ The same for the band powers of ``Ensemble.spectrum`` (rscm_ens_member_spectrum)
 ``band_edges`` and the library's own coefficient table (``spectrum_coefficients``), and for the covariability of two series
 (``Ensemble.covariability``, rscm_ens_member_covariability): ``series_covariability``, and for their co-spectra in frequency bands
 (``Ensemble.cross_spectrum``, rscm_ens_member_cross_spectrum): ``series_cross_spectrum`` with the library's sine table
-(``spectrum_sines``)."""
+(``spectrum_sines``).
+
+And for the running-mean diagnostics (``Ensemble.define_running_mean``, rscm_ens_define_running_mean): ``series_running_mean`` puts a
+record through the mean the members' rows go through, so that a period-mean target comes out of the estimator it is compared with."""
 import ctypes as C
-from typing import Dict
+from typing import Dict, Tuple
 
 import numpy as np
 
@@ -25,6 +28,42 @@ def detrend_mode(detrend) -> int:
         return DETREND[detrend]
     except (KeyError, TypeError):
         raise ValueError(f"detrend must be one of {sorted(DETREND)}, got {detrend!r}") from None
+
+
+def running_mean_back(window: int, align: str = "centre") -> int:
+    """The terms of a running-mean window that lie before its row: ``window - 1`` for ``"trailing"``, ``(window - 1) // 2`` for
+    ``"centre"`` (a window of 20 spans t - 9 .. t + 10).  ``ValueError`` for a window outside 2 .. 64 or another ``align``."""
+    window = int(window)
+    if window < 2 or window > L.RUNMEAN_MAX_WINDOW:
+        raise ValueError(f"window must be in 2 .. {L.RUNMEAN_MAX_WINDOW}, got {window}")
+    if align not in L.RUNMEAN_ALIGN:
+        raise ValueError(f"align must be one of {sorted(L.RUNMEAN_ALIGN)}, got {align!r}")
+    return window - 1 if align == "trailing" else (window - 1) // 2
+
+
+def series_running_mean(series, window: int, align: str = "centre", step: int = 1) -> Tuple[np.ndarray, int]:
+    """``(values, first_index)``: the running mean of ``series`` -- ``[R]`` or ``[R][N]``, rows by members -- as
+    ``Ensemble.define_running_mean(name, source, window, align, step)`` forms it, for every row whose window is complete:
+    ``values[k]`` belongs to row ``first_index + k`` of the series, ``first_index = back * step`` (``running_mean_back``), and
+    there are ``R - (window - 1) * step`` of them.  For row t: ``s = x[t - back*step]``, then ``s = s + x[t + (j - back)*step]`` for
+    ``j = 1 .. window - 1`` in that order, then ``s / float(window)``; every add and the division is one float64 operation, so a
+    record put through this function and the same values put through the kernel agree bit for bit (rscm_ens_define_running_mean
+    states the arithmetic).  Nothing is padded: a series shorter than one window is a ``ValueError``."""
+    back = running_mean_back(window, align)
+    window, step = int(window), int(step)
+    if step < 1:
+        raise ValueError(f"step must be at least 1, got {step}")
+    x = np.asarray(series, dtype=np.float64)
+    if x.ndim not in (1, 2):
+        raise ValueError(f"series_running_mean: [R] or [R][N] expected, got shape {x.shape}")
+    n = x.shape[0] - (window - 1) * step
+    if n < 1:
+        raise ValueError(f"series_running_mean: {x.shape[0]} rows hold no window of {window} terms {step} apart")
+    with np.errstate(all="ignore"):
+        s = x[0:n].copy()
+        for j in range(1, window):
+            s = s + x[j * step:j * step + n]
+        return s / float(window), back * step
 
 
 def series_variability(x, detrend: str = "linear") -> Dict[str, object]:

@@ -54,6 +54,12 @@ and the regression slope of N on the temperature, both linearly detrended, lag 0
 ``series_covariability(temperature, N, "linear", "linear", 0)`` against ``Ensemble.covariability``, scored alone ("toa_imbalance")
 and added onto the temperature-plus-heat-content likelihood ("all"); the 5-95 % range of lambda0 with and without it goes to stderr.
 
+With ``--running-mean W`` the 1.5 K crossing of the history is read twice: the first YEAR at or above 1.5 K
+(``indicators`` on the annual values, which carry each member's own variability) and the first W-year centred mean at or above it
+(``define_running_mean``, ``compute_diagnostic``, then ``indicators`` on the diagnostic); the 5 %, 50 % and 95 % points of the two
+crossing times under the point likelihood's weights go to stderr side by side and into the JSON line (a member that never crosses
+counts as +inf).
+
     python scripts/assess_variability.py [--members 100000] [--draws 20000] [--fast] [--spectrum] [--heat-content] [--covariability] [--toa-imbalance]
                                          [--cross-spectrum]
 
@@ -115,6 +121,8 @@ def main():
                     help="also weight by the band coherence and gains of the record's heat uptake on its temperature (requires --heat-content)")
     ap.add_argument("--toa-imbalance", action="store_true",
                     help="also weight by the covariability of the record's temperature and top-of-atmosphere imbalance (requires --heat-content)")
+    ap.add_argument("--running-mean", type=int, default=0, metavar="W",
+                    help="also print the weighted 1.5 K crossing time from annual values beside that of the W-year centred mean (2 .. 64)")
     ap.add_argument("--correlations", action="store_true",
                     help="also print the posterior correlation matrix of the parameters (Ensemble.moments) under the last weights formed")
     a = ap.parse_args()
@@ -124,6 +132,8 @@ def main():
         ap.error("--covariability requires --heat-content")
     if a.cross_spectrum and not a.heat_content:
         ap.error("--cross-spectrum requires --heat-content")
+    if a.running_mean and not 2 <= a.running_mean <= 64:
+        ap.error("--running-mean takes a window of 2 .. 64 years")
     mode = rscm_amd.MODE_FAST if a.fast else rscm_amd.MODE_EXACT
 
     # the record: one member with known amplitude and persistence, a seed of its own
@@ -152,6 +162,26 @@ def main():
         P, w = ens.get_params(), ens.member_weights()
         checks = {"weighted_quantiles_equal_numpy": bool(np.array_equal(post, np.stack([np_weighted(P[sigma_row], w), np_weighted(P[phi_row], w)])))}
         ess = ens.weights_stats()["ess"]
+
+        crossing = None
+        if a.running_mean:
+            # the first year at or above 1.5 K, and the first W-year centred mean at or above it, over the history under the point
+            # likelihood's weights: lower empirical quantiles, +inf for a member that never crosses
+            level, q3c = 1.5, [0.05, 0.5, 0.95]
+            mid = ens.define_running_mean(f"{TS}|{a.running_mean}-year mean", TS, a.running_mean, "centre")
+            ens.compute_diagnostic(mid)
+            lo, hi = ens.running_mean_range(mid)
+            annual_x = ens.indicators(TS, 0, NOW + 1, thresholds=[level], slot=2)["crossing"][0].to_host()
+            mean_x = ens.indicators(mid, lo, hi, thresholds=[level], slot=3)["crossing"][0].to_host()
+            ok = ~(np.isnan(annual_x) | np.isnan(mean_x)) & (w > 0)
+            crossing = {"level_K": level, "window": a.running_mean, "quantiles": q3c, "members": int(ok.sum()),
+                        "annual": np.quantile(annual_x[ok], q3c, weights=w[ok], method="inverted_cdf").tolist(),
+                        "running_mean": np.quantile(mean_x[ok], q3c, weights=w[ok], method="inverted_cdf").tolist(),
+                        "mean_rows": [float(YEARS[lo]), float(YEARS[hi - 1])]}
+            print(f"1.5 K crossing in 1850-2020, {crossing['members']} weighted members, 5 / 50 / 95 %:", file=sys.stderr)
+            print("  first year at or above it            " + "  ".join(f"{v:7.1f}" for v in crossing["annual"]), file=sys.stderr)
+            print(f"  first {a.running_mean:2d}-year centred mean at or above " + "  ".join(f"{v:7.1f}" for v in crossing["running_mean"]),
+                  file=sys.stderr)
 
         # the posterior: the draws inherit sigma and phi with the other rows and realise their own noise to 2100
         anc = ens.resample(a.draws, seed=7).to_host()
@@ -408,6 +438,8 @@ def main():
         res["toa_imbalance"] = toa
     if xspec is not None:
         res["cross_spectrum"] = xspec
+    if crossing is not None:
+        res["crossing_1p5K"] = crossing
     if correlations is not None:
         res["correlations"] = correlations
     print(json.dumps(res), flush=True)
