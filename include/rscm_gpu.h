@@ -124,8 +124,11 @@ extern "C" {
  *      stored variable in one launch: rscm_ens_exceedance_rows, RSCM_EXCEEDANCE_ROWS_MAX_THRESHOLDS
  *  27  running means of a stored variable or of a diagnostic over the time axis as diagnostic variables, which every reader of rows
  *      then takes by id: rscm_ens_define_running_mean, rscm_ens_diagnostic_running_mean, RSCM_RUNMEAN_MAX_WINDOW,
- *      RSCM_RUNMEAN_TRAILING, RSCM_RUNMEAN_CENTRED */
-#define RSCM_GPU_ABI_MINOR 27
+ *      RSCM_RUNMEAN_TRAILING, RSCM_RUNMEAN_CENTRED
+ *  28  histograms across members, in exact integers that shards add up: of a stored variable at every row, of up to eight
+ *      per-member vectors with shared or own edges, and of two vectors jointly: rscm_ens_histogram_rows, rscm_ens_histogram_vectors,
+ *      rscm_ens_histogram2d, RSCM_HISTOGRAM_MAX_EDGES, RSCM_HISTOGRAM_MAX_SLOTS, RSCM_HISTOGRAM_MAX_VECTORS */
+#define RSCM_GPU_ABI_MINOR 28
 
 #if defined(__GNUC__)
 #define RSCM_API __attribute__((visibility("default")))
@@ -1232,6 +1235,52 @@ RSCM_API int rscm_ens_moment_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, 
 RSCM_API int rscm_ens_exceedance_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_thr,
                                       const double* thr, int32_t thr_per_row, int32_t flags, int64_t* hits, int64_t* equal,
                                       int64_t* total);
+
+/* ---- histograms across members: of a stored variable at every row, of member vectors, of two vectors jointly (ABI minor 28) ---- */
+/* The distribution itself, where rscm_ens_exceedance_rows gives its tail at a few thresholds: per row and member group the summed
+ * weight of the members in each bin between ascending edges.  This is the one definition; the kernels (histogram.hip, with the bin
+ * of a value in histogram_bin.hpp), rscm_amd's finishers and the tests' restatement in numpy and Python integers
+ * (tests/host_histogram.py) apply it.
+ *   Edges: e[0] < e[1] < ... < e[E-1], host doubles, finite and strictly ascending, 2 <= E <= RSCM_HISTOGRAM_MAX_EDGES; B = E - 1
+ *   bins.  Anything else is RSCM_ERR_INVALID.
+ *   Binning: for a value v that is not NaN let k be the number of edges with e[j] <= v (IEEE comparisons: -0 equals +0, and
+ *   infinities take part).  k == 0: v counts in `below`.  1 <= k <= B: in bin k - 1, so bin j holds e[j] <= v < e[j+1].  k == E: in
+ *   the last bin when v == e[E-1] (the last edge is closed), else in `above`.  This is numpy.histogram(x, bins=e, weights=w) with
+ *   int64 weights, plus the two counts outside.
+ *   Who takes part follows rscm_ens_exceedance_rows: a member takes part when its value is not NaN; its weight is 1, or the member
+ *   weight w[i] with RSCM_SELECT_WEIGHTED; with RSCM_SELECT_GROUPED it counts in group g[i], and a member whose id is outside
+ *   [0, G) is left out (G = n_groups when grouped, else 1); with RSCM_SELECT_ANOMALY the value is series[t][i] - b[i], one rounded
+ *   subtraction.  A flag without its weights, groups or baseline is RSCM_ERR_STATE.
+ *   All sums are int64: exact, independent of the order of summation, total = below + sum(counts) + above holds exactly, and the
+ *   sums of shards add up to the whole ensemble's.  The limit on the summed weight is that of rscm_ens_exceedance.
+ *   Slots: a block of the kernel keeps a call's bins in LDS, G (B + 2) slots in one dimension and G (Bx By + 1) in two; more than
+ *   RSCM_HISTOGRAM_MAX_SLOTS is RSCM_ERR_INVALID, and the message names the product.  That holds 3 groups x 1024 bins, 64 groups x
+ *   126 bins and a joint histogram of 64 x 64.
+ * rscm_ens_histogram_rows: the rows t_begin, t_begin + t_stride, ... < t_end of var_id, resolved as rscm_ens_exceedance_rows
+ * resolves them (full storage, the window, the output store; a diagnostic by its id, RSCM_ERR_STATE when it is stale or a computed
+ * row is not resident, or while a staged select is in flight).  Result, host memory: counts[rows][G][B], below[rows][G],
+ * above[rows][G], total[rows][G]; a row beyond the current time index has zeros everywhere.  One launch for all rows.
+ * RSCM_ERR_INVALID besides: unknown flags, a NULL result, a bad row range or stride, a variable without a stored series. */
+#define RSCM_HISTOGRAM_MAX_EDGES 1025
+#define RSCM_HISTOGRAM_MAX_SLOTS 8192
+#define RSCM_HISTOGRAM_MAX_VECTORS 8
+RSCM_API int rscm_ens_histogram_rows(rscm_ens* h, int32_t var_id, int32_t t_begin, int32_t t_end, int32_t t_stride, int32_t n_edges,
+                                     const double* edges, int32_t flags, int64_t* counts, int64_t* below, int64_t* above, int64_t* total);
+/* The same of 1 <= n_vec <= RSCM_HISTOGRAM_MAX_VECTORS per-member device vectors (vec_dev[n_vec], a host array of device addresses
+ * of N doubles, checked as rscm_ens_quantile_vectors checks its vectors), which serve as the rows: indicators, parameter rows, a
+ * log-likelihood.  edges[E] is shared (edges_per_vector == 0), or edges[n_vec][E] gives every vector its own, each table checked as
+ * above.  NaN is left out per vector, not listwise.  RSCM_SELECT_ANOMALY is RSCM_ERR_INVALID.  Result: counts[n_vec][G][B], below,
+ * above, total [n_vec][G].  The kernel is that of the rows with an edge table per row. */
+RSCM_API int rscm_ens_histogram_vectors(rscm_ens* h, int32_t n_vec, const double* const* vec_dev, int32_t n_edges, const double* edges,
+                                        int32_t edges_per_vector, int32_t flags, int64_t* counts, int64_t* below, int64_t* above,
+                                        int64_t* total);
+/* The joint histogram of two per-member device vectors: a member takes part when neither value is NaN, and counts in
+ * counts[G][Bx][By] at (bin of x among edges_x, bin of y among edges_y) when both values fall into a bin, in outside[G] when either
+ * is below its first or above its last edge; total[G] = sum(counts) + outside is the weight taking part.  Flags, edges and errors as
+ * rscm_ens_histogram_vectors. */
+RSCM_API int rscm_ens_histogram2d(rscm_ens* h, const double* x_dev, const double* y_dev, int32_t n_edges_x, const double* edges_x,
+                                  int32_t n_edges_y, const double* edges_y, int32_t flags, int64_t* counts, int64_t* outside,
+                                  int64_t* total);
 
 /* ---- per-member variability statistics and a likelihood over per-member vectors (ABI minor 16) ---- */
 /* How variable is each member's series of var_id over a period: its mean, its trend, the variance and standard deviation about the

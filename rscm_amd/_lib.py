@@ -39,6 +39,7 @@ SELECT_GROUPED = 4    # one result per member group (rscm_ens_set_member_groups)
 MOMENT_MAX_VECTORS = 8   # rscm_ens_moment_sums / rscm_ens_moments
 MOMENT_ROWS_MAX_VECTORS = 4   # rscm_ens_moment_rows_sums / rscm_ens_moment_rows
 EXCEEDANCE_ROWS_MAX_THRESHOLDS = 8   # rscm_ens_exceedance_rows
+HISTOGRAM_MAX_EDGES, HISTOGRAM_MAX_SLOTS, HISTOGRAM_MAX_VECTORS = 1025, 8192, 8   # rscm_ens_histogram_rows / _vectors / 2d
 MOMENT_BLOCK = 69        # int64 per sum: 68 limbs in units of 2^(32 k - 1088), then the count of non-finite terms
 DIAG_MAX_TERMS, DIAG_MAX = 4, 4    # RSCM_DIAG_MAX_TERMS, RSCM_DIAG_MAX: terms per diagnostic variable, diagnostics per handle
 # RSCM_BUDGET_*: the energy-budget quantities of rscm_ens_define_energy_budget, and the names the front end gives them
@@ -411,6 +412,12 @@ SIGNATURES = {
     "rscm_gpu_moment_rows_last_stats": (C.c_int, [C.POINTER(C.c_int64)]),
     "rscm_ens_exceedance_rows": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.c_int32,
                                            C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rscm_ens_histogram_rows": (C.c_int, [_h, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64),
+                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rscm_ens_histogram_vectors": (C.c_int, [_h, C.c_int32, C.POINTER(_dp), C.c_int32, _dp, C.c_int32, C.c_int32, C.POINTER(C.c_int64),
+                                             C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "rscm_ens_histogram2d": (C.c_int, [_h, _dp, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       C.POINTER(C.c_int64)]),
     "rscm_ens_weights_stats": (C.c_int, [_h, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_uint64)]),
     "rscm_ens_resample": (C.c_int, [_h, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_void_p)]),

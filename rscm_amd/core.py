@@ -1384,6 +1384,14 @@ class GraphModel:
         kw = {"grouped": True} if grouped else {}
         return ens.exceedance_rows(vid, thresholds, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, **kw)
 
+    def histogram_rows(self, name: str, edges, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                       anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """``Ensemble.histogram_rows`` (the members in each bin between ``edges`` at every row of ``name``) on the variable's home
+        ensemble."""
+        ens, vid = self.variable_home(name)
+        kw = {"grouped": True} if grouped else {}
+        return ens.histogram_rows(vid, edges, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, **kw)
+
     def rank_rows(self, name: str, record, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
                   anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """``Ensemble.rank_rows`` (where the record ``[rows]`` lies inside the plume of ``name`` at every row) on the variable's

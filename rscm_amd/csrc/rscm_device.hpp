@@ -982,6 +982,38 @@ struct ExceedanceRowsArgs {
 };
 constexpr int32_t exceedance_rows_stride(int32_t n_thr, bool equal) { return 1 + (equal ? 2 : 1) * n_thr; }
 hipError_t launch_exceedance_rows(const ExceedanceRowsArgs& a, bool equal, hipStream_t s);
+// histograms of stored rows and of member vectors (histogram.hip; the definition is stated in include/rscm_gpu.h,
+// rscm_ens_histogram_rows): acc[n_rows][G][B + 2] += {counts[B], below, above} of the rows `rows` (a device array of n_rows device
+// addresses of N doubles) among the ascending edges edges[E] (edge_stride 0: the same for every row) or edges[n_rows][E] (edge_stride
+// E), device memory, B = E - 1, with G = n_groups when group is non-null, else 1.  w non-null: the member weights; base non-null: the
+// value is the row's minus base[i].  The two-dimensional form: acc[G][Bx * By + 1] += {counts[Bx][By], outside} of the member vectors
+// x and y among edges[Ex] followed by edges[Ey].  The caller zeroes acc and has checked the edges and the slots, G (B + 2) or
+// G (Bx By + 1), against kHistogramMaxSlots: a block keeps them in LDS beside the edges.  The grid is capped at kHistBlocks blocks in
+// x, which take kHistogramMembersPerPass members per pass of their grid-stride loop: a destination collects at most that many adders.
+constexpr int32_t kHistogramMaxEdges = 1025;
+constexpr int32_t kHistogramMaxSlots = 8192;
+constexpr int kHistBlocks = 32;
+constexpr int64_t kHistogramMembersPerPass = 8192;
+struct HistogramArgs {
+    const double* const* rows;
+    const double* edges;
+    const int64_t* w;
+    const int32_t* group;
+    const double* base;
+    unsigned long long* acc;
+    int64_t N;
+    int32_t n_rows, n_groups, n_edges, edge_stride;
+};
+struct Histogram2dArgs {
+    const double *x, *y, *edges;
+    const int64_t* w;
+    const int32_t* group;
+    unsigned long long* acc;
+    int64_t N;
+    int32_t n_groups, n_edges_x, n_edges_y;
+};
+hipError_t launch_histogram(const HistogramArgs& a, hipStream_t s);
+hipError_t launch_histogram2d(const Histogram2dArgs& a, hipStream_t s);
 // per-member variability statistics (variability.hip) over rows d_rows[n_rows][N]: d_out[5][N] = mean, slope, variance, sd, r1 of
 // the working series (mode kVarMean / kVarLinear: the rows, kVarDifference: their first differences; the definition is stated in
 // include/rscm_gpu.h, rscm_ens_member_variability); stt = n (n^2 - 1) / 12 of the working series' length n, formed by the caller

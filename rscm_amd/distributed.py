@@ -18,6 +18,7 @@ in the CPU tests), are:
 * ``exceedance_global``: one all-reduce (int64 SUM) of the exceedance counts or weight sums;
 * ``moments_global``: two all-reduces (int64 SUM) of the fixed-point moment sums, 69 int64 per mean and covariance entry;
 * ``moment_rows_global``: the same two all-reduces for the mean and spread of a stored variable at every row;
+* ``histogram_rows_global``, ``histogram_vectors_global``, ``histogram2d_global``: one all-reduce (int64 SUM) of the bin sums;
 * ``exceedance_rows_global``, ``rank_rows_global``: one all-reduce (int64 SUM) of the per-row hits, equals and totals;
 * ``weights_stats_global``: one all-reduce (int64 SUM) of the exact weight sums and one (MAX) of the largest weight;
 * ``resample_global``: one all-gather of each rank's exact summed weight (8 B per rank); no member crosses a rank.
@@ -313,6 +314,33 @@ def rank_rows_global(ensemble, var, record, t_begin: int = 0, t_end: Optional[in
     return rank_rows_result(total - below, equal, total, record, grouped)
 
 
+def histogram_rows_global(ensemble, var, edges, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, group=None,
+                          weighted: bool = False, anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.histogram_rows`` of the WHOLE sharded ensemble on every rank: the ranks' int64 counts, below, above and totals of
+    every row are SUM-reduced in one collective (exact and independent of order), then ``ensemble.histogram_result`` forms the
+    probabilities.  Every rank passes the same rows and edges and stands at the same time index; ``grouped``: the same ``n_groups``
+    on every rank."""
+    from .ensemble import histogram_result
+    local = ensemble.histogram_rows(var, edges, t_begin, t_end, t_stride, **_row_flags(weighted, anomaly, grouped))
+    return histogram_result(*_reduce_together([local[k] for k in ("counts", "below", "above", "total")], group), grouped)
+
+
+def histogram_vectors_global(ensemble, vectors, edges, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.histogram_vectors`` of the WHOLE sharded ensemble on every rank: one SUM-reduction of the int64 sums, then
+    ``ensemble.histogram_result``.  Every rank passes its shard of each vector in the same order, and the same edges."""
+    from .ensemble import histogram_result
+    local = ensemble.histogram_vectors(list(vectors), edges, **_row_flags(weighted, False, grouped))
+    return histogram_result(*_reduce_together([local[k] for k in ("counts", "below", "above", "total")], group), grouped)
+
+
+def histogram2d_global(ensemble, x, y, edges_x, edges_y, group=None, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+    """``Ensemble.histogram2d`` of the WHOLE sharded ensemble on every rank: one SUM-reduction of the int64 counts, outside and
+    totals, then ``ensemble.histogram2d_result``.  Every rank passes its shard of the two vectors and the same edges."""
+    from .ensemble import histogram2d_result
+    local = ensemble.histogram2d(x, y, edges_x, edges_y, **_row_flags(weighted, False, grouped))
+    return histogram2d_result(*_reduce_together([local[k] for k in ("counts", "outside", "total")], group), grouped)
+
+
 def weights_stats_global(ensemble, group=None) -> Dict[str, object]:
     """``Ensemble.weights_stats`` of the WHOLE sharded ensemble on every rank: the ranks' exact integers are SUM-reduced (``w_max``:
     MAX) -- sum w^2 as four 32-bit limbs, each of which sums without wrapping over any number of ranks an int64 can count -- and
@@ -470,6 +498,19 @@ class ShardedEnsemble:
                          anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
         """Where a record lies inside the global ensemble's plume at every row (``rank_rows_global``)."""
         return rank_rows_global(self.ensemble, var, record, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, grouped=grouped)
+
+    def histogram_rows_global(self, var, edges, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                              anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """The histogram of a stored variable at every row over the global ensemble (``histogram_rows_global``)."""
+        return histogram_rows_global(self.ensemble, var, edges, t_begin, t_end, t_stride, weighted=weighted, anomaly=anomaly, grouped=grouped)
+
+    def histogram_vectors_global(self, vectors, edges, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """Histograms of per-member vectors over the global ensemble (``histogram_vectors_global``)."""
+        return histogram_vectors_global(self.ensemble, vectors, edges, weighted=weighted, grouped=grouped)
+
+    def histogram2d_global(self, x, y, edges_x, edges_y, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """The joint histogram of two per-member vectors over the global ensemble (``histogram2d_global``)."""
+        return histogram2d_global(self.ensemble, x, y, edges_x, edges_y, weighted=weighted, grouped=grouped)
 
     def exceedance_global(self, vector, thresholds, weighted: bool = False, grouped: bool = False) -> Dict[str, object]:
         """Exceedance probabilities of a per-member vector over the global ensemble (``exceedance_global``)."""

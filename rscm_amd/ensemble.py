@@ -1148,6 +1148,63 @@ class Ensemble:
         hits, equal, total = self._exceedance_rows_sums(var, rec[:, None], True, t_begin, t_end, t_stride, weighted, anomaly, grouped, True)
         return rank_rows_result(hits[..., 0], equal[..., 0], total, rec, grouped)
 
+    def histogram_rows(self, var, edges, t_begin: int = 0, t_end: Optional[int] = None, t_stride: int = 1, weighted: bool = False,
+                       anomaly: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """The plume as a density over value and time: at every row ``t_begin, t_begin + t_stride, ... < t_end`` of ``var``, read
+        wherever the rows are resident, the members (with ``weighted`` their summed weight) in each of the ``B = E - 1`` bins
+        between ``edges`` (``[E]``, finite and strictly ascending, 2 <= E <= 1025): ``numpy.histogram``'s bins, the last edge
+        closed.  Returns ``{"counts": [rows][B], "below", "above", "total": [rows] int64, "probability": counts / total}``, NaN
+        where total is 0; ``below`` and ``above`` hold what lies outside the edges, and ``total = below + sum(counts) + above`` the
+        members that are not NaN in that row.  With ``grouped`` per member group, the group axis after the rows (at most 8192
+        slots: groups x (B + 2)); ``anomaly`` takes the member's value minus its baseline.  Integer sums in one launch for all
+        rows: exact, so those of shards add up (``rscm_amd.distributed.histogram_rows_global``).  Bad edges are a ``ValueError``
+        before any library call.  Rows beyond the time index: zeros, NaN."""
+        t_end = self.n_times if t_end is None else t_end
+        e = histogram_edges(edges, "histogram_rows: edges")
+        G, rows, B = self._n_groups(grouped), (len(range(t_begin, t_end, t_stride)) if t_stride > 0 else 0), e.size - 1
+        counts = np.zeros((rows, G, B), dtype=np.int64)
+        below, above, total = (np.zeros((rows, G), dtype=np.int64) for _ in range(3))
+        i64 = C.POINTER(C.c_int64)
+        L.check(self._lib.rscm_ens_histogram_rows(self._h, self._var(var), t_begin, t_end, t_stride, e.size, L.dptr(e),
+                                                  select_flags(weighted, anomaly, grouped), counts.ctypes.data_as(i64),
+                                                  below.ctypes.data_as(i64), above.ctypes.data_as(i64), total.ctypes.data_as(i64)))
+        return histogram_result(counts, below, above, total, grouped)
+
+    def histogram_vectors(self, vectors, edges, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """``histogram_rows`` with 1 to 8 ``[N]`` float64 ``DeviceVector``s as the rows: the posterior density of a parameter
+        (``params_vector``) or of an indicator.  ``edges`` is ``[E]``, shared, or ``[len(vectors)][E]``, one table per vector
+        (parameters have different ranges); any other shape is a ``ValueError``.  NaN is left out per vector.  Returns the dict
+        of ``histogram_rows`` with the vectors as the leading axis."""
+        arr, n_vec = self._vectors(vectors)
+        if not 1 <= n_vec <= L.HISTOGRAM_MAX_VECTORS:
+            raise ValueError(f"histogram_vectors: 1 to {L.HISTOGRAM_MAX_VECTORS} vectors, got {n_vec}")
+        e = histogram_edges(edges, "histogram_vectors: edges", n_vec)
+        G, B = self._n_groups(grouped), e.shape[-1] - 1
+        counts = np.zeros((n_vec, G, B), dtype=np.int64)
+        below, above, total = (np.zeros((n_vec, G), dtype=np.int64) for _ in range(3))
+        i64 = C.POINTER(C.c_int64)
+        L.check(self._lib.rscm_ens_histogram_vectors(self._h, n_vec, arr, e.shape[-1], L.dptr(e), int(e.ndim == 2),
+                                                     select_flags(weighted, False, grouped), counts.ctypes.data_as(i64),
+                                                     below.ctypes.data_as(i64), above.ctypes.data_as(i64), total.ctypes.data_as(i64)))
+        return histogram_result(counts, below, above, total, grouped)
+
+    def histogram2d(self, x, y, edges_x, edges_y, weighted: bool = False, grouped: bool = False) -> Dict[str, np.ndarray]:
+        """The joint density of two ``[N]`` float64 ``DeviceVector``s, one panel of a corner plot: ``{"counts": [Bx][By] int64,
+        "outside", "total": int64, "probability": counts / total}``.  A member takes part when neither value is NaN; it counts in
+        ``counts`` when both values fall into a bin of their edges (``numpy.histogram2d``'s bins) and in ``outside`` otherwise;
+        ``total = sum(counts) + outside``.  With ``grouped`` per member group, the group axis leading (at most 8192 slots:
+        groups x (Bx By + 1))."""
+        arr, _n = self._vectors([x, y])
+        ex, ey = histogram_edges(edges_x, "histogram2d: edges_x"), histogram_edges(edges_y, "histogram2d: edges_y")
+        G = self._n_groups(grouped)
+        counts = np.zeros((G, ex.size - 1, ey.size - 1), dtype=np.int64)
+        outside, total = np.zeros(G, dtype=np.int64), np.zeros(G, dtype=np.int64)
+        i64 = C.POINTER(C.c_int64)
+        L.check(self._lib.rscm_ens_histogram2d(self._h, arr[0], arr[1], ex.size, L.dptr(ex), ey.size, L.dptr(ey),
+                                               select_flags(weighted, False, grouped), counts.ctypes.data_as(i64),
+                                               outside.ctypes.data_as(i64), total.ctypes.data_as(i64)))
+        return histogram2d_result(counts, outside, total, grouped)
+
     def params_vector(self, row: int) -> DeviceVector:
         """Parameter row ``row`` of the ``[P][N]`` block as a ``DeviceVector`` (rscm_ens_params_devptr), e.g. for
         ``quantile_vectors``.  Once handed out, the block is read per member for the handle's life."""
@@ -1421,6 +1478,94 @@ def rank_histogram(below, equal, total, n_bins: int, record=None) -> np.ndarray:
             if t > 0:
                 out[g, min(n_bins * (2 * b + e) // (2 * t), n_bins - 1)] += 1
     return out if below.ndim == 2 else out[0]
+
+
+def histogram_edges(edges, what: str = "edges", tables: Optional[int] = None) -> np.ndarray:
+    """The checked edges of a histogram call as a contiguous float64 array: ``[E]``, or with ``tables`` also ``[tables][E]``; 2 <= E
+    <= 1025, every table finite and strictly ascending.  Anything else is a ``ValueError``; no library call is made."""
+    e = np.asarray(edges, dtype=np.float64)
+    shapes = f"[E] or [{tables}][E]" if tables is not None else "[E]"
+    if not (e.ndim == 1 or (tables is not None and e.ndim == 2 and e.shape[0] == tables)):
+        raise ValueError(f"{what} must be {shapes}, got shape {e.shape}")
+    if not 2 <= e.shape[-1] <= L.HISTOGRAM_MAX_EDGES:
+        raise ValueError(f"{what}: 2 to {L.HISTOGRAM_MAX_EDGES} edges, got {e.shape[-1]}")
+    if not (np.isfinite(e).all() and (e[..., 1:] > e[..., :-1]).all()):
+        raise ValueError(f"{what} must be finite and strictly ascending")
+    return np.ascontiguousarray(e)
+
+
+def histogram_result(counts, below, above, total, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """The dict of ``Ensemble.histogram_rows`` and ``histogram_vectors`` from the (reduced) int64 sums ``counts[rows][G][B]`` and
+    ``below``, ``above``, ``total`` ``[rows][G]`` (G = 1 without groups; that axis may be absent): ``probability = counts / total``,
+    the exact quotient rounded once, NaN where total is 0.  Without ``grouped`` the group axis is dropped."""
+    counts = _rows_groups(counts)
+    below, above, total = (_rows_groups(a, counts) for a in (below, above, total))
+    out = {"counts": counts, "below": below, "above": above, "total": total,
+           "probability": _int_ratio(counts, np.broadcast_to(total[..., None], counts.shape))}
+    return out if grouped else {k: v[:, 0] for k, v in out.items()}
+
+
+def histogram2d_result(counts, outside, total, grouped: bool = True) -> Dict[str, np.ndarray]:
+    """The dict of ``Ensemble.histogram2d`` from the (reduced) int64 sums ``counts[G][Bx][By]``, ``outside[G]`` and ``total[G]`` (G =
+    1 without groups; that axis may be absent): ``probability = counts / total``, the exact quotient rounded once, NaN where total
+    is 0.  Without ``grouped`` the group axis is dropped."""
+    counts = np.asarray(counts, dtype=np.int64)
+    counts = counts[None] if counts.ndim == 2 else counts
+    outside, total = (np.asarray(a, dtype=np.int64).reshape(counts.shape[0]) for a in (outside, total))
+    out = {"counts": counts, "outside": outside, "total": total,
+           "probability": _int_ratio(counts, np.broadcast_to(total[:, None, None], counts.shape))}
+    return out if grouped else {k: v[0] for k, v in out.items()}
+
+
+def crps_bracket(hist, edges, record) -> Dict[str, np.ndarray]:
+    """A rigorous bracket of the continuous ranked probability score of every row of a histogram against ``record``, without a sort:
+    ``{"lower", "upper"}``, float64 of the shape of ``hist["total"]`` (``[rows]``, or ``[rows][G]``).  ``hist`` is the dict of
+    ``histogram_rows`` or ``histogram_vectors`` (or ``histogram_result`` of reduced sums), ``edges`` its ``[E]`` edges (``[rows][E]``
+    for per-vector edges), ``record`` is ``[rows]``.
+
+    With ``C_k`` the weight below ``e[k]`` and ``T`` the total, the weighted empirical distribution ``F`` of the row satisfies
+    ``C_k / T <= F(x) <= C_{k+1} / T`` inside bin k.  The record's bin is split at ``y``; left of ``y`` the CRPS integrates ``F^2``,
+    right of it ``(1 - F)^2``.  ``lower`` is the sum of ``width (C_k / T)^2`` over the pieces left of ``y`` plus ``width (1 - C_{k+1}
+    / T)^2`` over those right of it; ``upper`` swaps ``C_k`` and ``C_{k+1}``.  Everything is formed in ``fractions.Fraction``
+    (differences of doubles are exact) and each bound is rounded once.  The bracket contains the CRPS of the weighted empirical
+    distribution and is at most as wide as the widest bin; the exact score needs the sorted members.
+
+    A row gives ``(nan, nan)`` when the bracket would not hold or means nothing: weight outside the edges (``below`` or ``above``
+    non-zero), ``T == 0``, a NaN record, or a record outside ``[e[0], e[E-1]]``."""
+    from fractions import Fraction
+    counts = np.asarray(hist["counts"], dtype=np.int64)
+    shape = counts.shape[:-1]
+    rows, B = counts.shape[0], counts.shape[-1]
+    c3 = counts.reshape(rows, -1, B)
+    below, above, total = (np.asarray(hist[k], dtype=np.int64).reshape(rows, -1) for k in ("below", "above", "total"))
+    e = np.asarray(edges, dtype=np.float64)
+    rec = np.asarray(record, dtype=np.float64)
+    if rec.shape != (rows,):
+        raise ValueError(f"crps_bracket: the record must be [{rows}], got shape {rec.shape}")
+    if e.shape not in ((B + 1,), (rows, B + 1)):
+        raise ValueError(f"crps_bracket: edges must be [{B + 1}] or [{rows}][{B + 1}], got shape {e.shape}")
+    e = np.broadcast_to(e, (rows, B + 1))
+    lower, upper = np.full(c3.shape[:2], np.nan), np.full(c3.shape[:2], np.nan)
+    for r in range(rows):
+        y = float(rec[r])
+        if y != y or not e[r, 0] <= y <= e[r, B]:
+            continue
+        ef, yf = [Fraction(v) for v in e[r].tolist()], Fraction(y)
+        for g in range(c3.shape[1]):
+            T = int(total[r, g])
+            if T == 0 or below[r, g] != 0 or above[r, g] != 0:
+                continue
+            lo = hi = Fraction(0)
+            C = 0
+            for k, c in enumerate(c3[r, g].tolist()):
+                a, b = Fraction(C, T), Fraction(C + c, T)      # C_k / T <= F <= C_{k+1} / T inside bin k
+                C += c
+                left = min(max(yf, ef[k]), ef[k + 1]) - ef[k]  # the part of the bin left of y
+                right = (ef[k + 1] - ef[k]) - left
+                lo += left * a * a + right * (1 - b) * (1 - b)
+                hi += left * b * b + right * (1 - a) * (1 - a)
+            lower[r, g], upper[r, g] = float(lo), float(hi)
+    return {"lower": lower.reshape(shape), "upper": upper.reshape(shape)}
 
 
 def moment_blocks(K: int, order: int) -> int:
